@@ -32,6 +32,11 @@ Extra objects in the JSON line:
   epe_vs_reference  the parity half of the metric: the 13 committed verification patterns through the HIP
                 path (outside the timed region), compared with the digests / dense flows the reference produced
                 (tests/golden/: fixtures are data; no oracle involved)
+
+``--dump-outputs DIR`` writes the flow of the last timed step (u, v: what the plan hands its caller) to DIR/u.npy and
+DIR/v.npy as float32 -- whole when both fit in 64 MiB, otherwise the same fixed, seeded sample of flat positions from
+each, the positions in DIR/sample_index.npy (float64).  The inputs are seeded, so two builds run with the same
+arguments can be compared output for output.  With N ranks, rank 0 writes its own shard.
 """
 from __future__ import annotations
 
@@ -46,6 +51,9 @@ ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT / "optical-flow-fpga_amd" / "python"))
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_BUDGET_BYTES = 64 * 2 ** 20   # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 21              # values per field when the whole flow does not fit: u, v (4 B) + the index (8 B) = 32 MiB
+DUMP_SEED = 0
 
 
 def algorithmic_bytes_per_pair(dims, levels: int, iters_run) -> dict:
@@ -166,6 +174,40 @@ def self_launch(argv) -> int:
     return r.returncode
 
 
+def dump_outputs(out_dir: str, fields: dict) -> list:
+    """--dump-outputs: write each output as out_dir/<name>.npy (float32).  fields: name -> the device tensors that
+    together hold that output, in job order (one per GPU for --multi inproc; equal sizes across names).  Whole arrays when
+    all fit in DUMP_BUDGET_BYTES; otherwise DUMP_SAMPLE values of each at the same seeded flat positions, which go to
+    sample_index.npy.  Returns the names of the files written."""
+    import numpy as np
+    import torch
+
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    sizes = {name: sum(t.numel() for t in ts) for name, ts in fields.items()}
+    n = next(iter(sizes.values()))
+    assert all(s == n for s in sizes.values()), sizes
+    written = []
+    if 4 * n * len(fields) <= DUMP_BUDGET_BYTES:
+        (out / "sample_index.npy").unlink(missing_ok=True)   # a sample of an earlier run must not pair up with these
+        for name, ts in fields.items():
+            np.save(out / f"{name}.npy", torch.cat([t.cpu() for t in ts]).numpy().astype(np.float32, copy=False))
+            written.append(f"{name}.npy")
+        return written
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+    for name, ts in fields.items():
+        parts, begin = [], 0
+        for t in ts:
+            sel = idx[(idx >= begin) & (idx < begin + t.numel())] - begin
+            parts.append(t.reshape(-1)[torch.from_numpy(sel).to(t.device)].cpu())
+            begin += t.numel()
+        np.save(out / f"{name}.npy", torch.cat(parts).numpy().astype(np.float32, copy=False))
+        written.append(f"{name}.npy")
+    np.save(out / "sample_index.npy", idx.astype(np.float64))
+    written.append("sample_index.npy")
+    return written
+
+
 def epe_vs_reference() -> dict | None:
     """BASELINE metric, second half ("+ EPE vs Python ref"): the 13 verification patterns (tests/golden/
     patterns_320x240.npz) through the HIP path, single-scale and pyramidal, against what the reference produced on
@@ -262,6 +304,9 @@ def run_inproc(args) -> None:
         step()
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        files = dump_outputs(args.dump_outputs, {"u": [sh[4] for sh in shards], "v": [sh[5] for sh in shards]})
+        print(f"bench.py: wrote {', '.join(files)} to {args.dump_outputs}", file=sys.stderr)
     lay0 = shards[0][0]
     H, W = lay0.height, lay0.width
     pairs = sum(sh[0].pairs_local for sh in shards)
@@ -309,7 +354,12 @@ def main() -> None:
     ap.add_argument("--gather", action="store_true",
                     help="after the timed region: gather the flow shards of all ranks to rank 0 through the process group "
                          "(RCCL on device tensors) and report gather_ms / gather_GBs next to, never inside, `value`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: write the flow of the last one to DIR/u.npy, v.npy (float32; a fixed, seeded "
+                         "sample with DIR/sample_index.npy when the whole flow exceeds 64 MiB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and args.multi == "ranks" and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(sys.argv[1:]))   # before torch / the GPU are touched
     if args.gpus > 1 and args.multi == "inproc":
@@ -367,6 +417,9 @@ def main() -> None:
     # bracketing all 15 launches of a step costs ~3 % of the step time
     elapsed = run_timed(group, step, torch.cuda.synchronize, args.steps, args.warmup,
                         before_timed=lambda: plan.set_profiling(2))
+    if args.dump_outputs and rank == 0:
+        files = dump_outputs(args.dump_outputs, {"u": [u], "v": [v]})
+        print(f"bench.py: wrote {', '.join(files)} to {args.dump_outputs}", file=sys.stderr)
     dom = plan.kernel_times().get("lk_iter_finest", {"total_ms": 0.0, "launches": 0})
     # informational per-kernel breakdown from a few extra, untimed steps with every launch bracketed
     plan.set_profiling(1)

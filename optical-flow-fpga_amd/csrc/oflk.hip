@@ -151,6 +151,16 @@ int level_dims(int H, int W, int levels, double scale, int *dims)
 // windows with a tiled kernel (3x3 ... 11x11); every other admissible size runs the generic one-thread-per-pixel kernel
 inline bool tiled_window(int hw) { return hw >= 1 && hw <= 5; }
 
+// The envelope of OFLK_ARITH_TOLERANT (include/oflk.h): the (levels, iterations) cells of the 5x5 window where its relaxations
+// were measured to keep the worst mean EPE of the 13 verification patterns at or under a third of the 1e-4 px bar, with the
+// reference's iteration counts (tests/test_tolerant_model.py sweeps L 1..4 x K 1..5).  Every other cell runs exactly.
+// oracle/oflk_tolerant_model.py (tolerant_spec) states the same set.
+inline bool tolerant_relaxes(int levels, int hw, int iterations)
+{
+    if (hw != 2) return false;
+    return (levels == 1 && (iterations == 1 || iterations == 2)) || (levels == 3 && (iterations == 2 || iterations == 3));
+}
+
 int window_hw(int window_size, int *hw)
 {
     if (window_size < 1) return fail(OFLK_ERR_INVALID, "window_size must be >= 1");
@@ -226,6 +236,12 @@ struct oflk_plan {
 };
 
 namespace {
+
+// fused multiply-adds in the Gaussian pyramid: OFLK_ARITH_CONTRACTED, and OFLK_ARITH_TOLERANT inside its envelope
+inline bool contracted_pyramid(const oflk_plan *p)
+{
+    return p && (p->arith == OFLK_ARITH_CONTRACTED || (p->arith == OFLK_ARITH_TOLERANT && tolerant_relaxes(p->L, p->hw, p->K)));
+}
 
 struct Prof {
     oflk_plan *p;
@@ -586,7 +602,7 @@ int launch_pyr_down(oflk_plan *plan, const GaussW &gauss, hipStream_t s, const f
         for (int k = 0; k <= 8; k++) a.w[k] = gauss.w[k];
         dim3 grid((wo + kPTW - 1) / kPTW, (ho + kPTH - 1) / kPTH, nimg);
         Prof pr(plan, s, KC_PYR_FUSED);
-        const bool fma = plan && plan->arith != OFLK_ARITH_EXACT;   // opt-in (contracted / tolerant); never the default
+        const bool fma = contracted_pyramid(plan);   // opt-in (contracted / tolerant); never the default
         if (extra && extra->u8) {
             if (fma) hipLaunchKernelGGL((k_pyr_down<unsigned char, true>), grid, dim3(256), 0, s, a);
             else hipLaunchKernelGGL((k_pyr_down<unsigned char, false>), grid, dim3(256), 0, s, a);
@@ -612,7 +628,7 @@ int launch_pyr_down(oflk_plan *plan, const GaussW &gauss, hipStream_t s, const f
     }
     {
         Prof pr(plan, s, KC_BLUR);
-        const bool fma = plan && plan->arith != OFLK_ARITH_EXACT;   // the unfused chain keeps the plan's arithmetic
+        const bool fma = contracted_pyramid(plan);   // the unfused chain keeps the plan's arithmetic
         if (fma) hipLaunchKernelGGL((k_blur<0, true>), grid2d(w, h, nimg), dim3(256), 0, s, in, tmpA, h, w, gauss);
         else hipLaunchKernelGGL((k_blur<0, false>), grid2d(w, h, nimg), dim3(256), 0, s, in, tmpA, h, w, gauss);
         HIP_TRY(hipGetLastError());
@@ -633,7 +649,7 @@ int launch_pyr_down(oflk_plan *plan, const GaussW &gauss, hipStream_t s, const f
     r.vec_store = (wo & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
     {
         Prof pr(plan, s, KC_RESAMPLE);
-        if (plan && plan->arith != OFLK_ARITH_EXACT) hipLaunchKernelGGL((k_resample<1, true>), grid_resample(wo, ho, nimg), dim3(256), 0, s, r);
+        if (contracted_pyramid(plan)) hipLaunchKernelGGL((k_resample<1, true>), grid_resample(wo, ho, nimg), dim3(256), 0, s, r);
         else hipLaunchKernelGGL((k_resample<1, false>), grid_resample(wo, ho, nimg), dim3(256), 0, s, r);
     }
     HIP_TRY(hipGetLastError());
@@ -966,9 +982,9 @@ int plan_pyramidal(oflk_plan *p, const void *d_prev_in, const void *d_curr_in, b
     for (int l = 0; l < L; l++) {
         const int h = p->dims[2 * l], w = p->dims[2 * l + 1];
         const size_t n = (size_t)h * w;
-        // tolerant mode: the two finest levels take the streaming kernel (order-free window sums, fused-lerp warp), and the flow
-        // upsampling into such a level is fused into its first iteration
-        const bool stream = p->arith == OFLK_ARITH_TOLERANT && p->hw == 2 && l >= L - 2 && h > 4 && w > 4;
+        // tolerant mode inside its envelope: the two finest levels take the streaming kernel (order-free window sums, fused-lerp
+        // warp), and the flow upsampling into such a level is fused into its first iteration
+        const bool stream = p->arith == OFLK_ARITH_TOLERANT && tolerant_relaxes(L, p->hw, K) && l >= L - 2 && h > 4 && w > 4;
         const bool fuse_up = stream && l > 0 && K >= 1 && p->dims[2 * (l - 1)] >= 2 && p->dims[2 * (l - 1) + 1] >= 2;
         if (l > 0 && !fuse_up) {
             // upsample_flow (:195-197) from whichever slot holds level l-1's result
@@ -1311,6 +1327,11 @@ OFLK_API int oflk_set_host_arithmetic(int mode)
         return fail(OFLK_ERR_INVALID, "arithmetic mode must be OFLK_ARITH_EXACT (0), OFLK_ARITH_CONTRACTED (1) or OFLK_ARITH_TOLERANT (2), got %d", mode);
     g_host_arith.store(mode);
     return OFLK_OK;
+}
+
+OFLK_API int oflk_tolerant_relaxes(int levels, int window_size, int iterations)
+{
+    return window_size >= 1 && tolerant_relaxes(levels, window_size / 2, iterations) ? 1 : 0;
 }
 
 OFLK_API int oflk_multi_rehearsal(int workers)

@@ -78,6 +78,7 @@ SIGNATURES = {
     "oflk_plan_set_kernels": (ctypes.c_int, [_vp, ctypes.c_int]),
     "oflk_multi_rehearsal": (ctypes.c_int, [ctypes.c_int]),
     "oflk_set_host_arithmetic": (ctypes.c_int, [ctypes.c_int]),
+    "oflk_tolerant_relaxes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "oflk_plan_metrics": (ctypes.c_int, [_vp, _vp, _vp, _f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), _vp]),
     "oflk_flow_metrics": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     "oflk_plan_kernel_times": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long), ctypes.c_int]),

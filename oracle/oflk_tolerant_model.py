@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE ONLY (tests/, tools/, bench.py's checker legs).  The model states the arithmetic of the library's
 opt-in OFLK_ARITH_TOLERANT mode with one switch per stage x level x iteration; `tolerant_spec` is the assignment the
-library ships."""
+library ships (its switches, `streaming_spec`, inside the envelope `ENVELOPE`; exact outside it)."""
 from __future__ import annotations
 
 import ctypes
@@ -49,12 +49,22 @@ class Spec:
         return s
 
 
-def tolerant_spec(levels: int = 3, iters: int = 3, shape=None) -> Spec:
-    """what OFLK_ARITH_TOLERANT computes (keep in step with plan_pyramidal in csrc/oflk.hip and DESIGN.md section 2): the
-    pyramid with fused multiply-adds; on the two finest levels the streaming kernel -- fused-lerp fp64 warp, window sums
-    vertical first then horizontal -- with the flow upsampling INTO such a level in the fused-lerp form too (it is fused
-    into the level's first iteration); coarser levels exact.  shape = (H, W): levels too small for the streaming kernel
-    (5 pixels or fewer along an axis) run exactly, as in the library."""
+# (levels, iterations) cells of the 5x5 window where OFLK_ARITH_TOLERANT relaxes anything: the cells whose worst mean EPE on
+# the 13 verification patterns is at most a third of the 1e-4 px bar, with the reference's iteration counts
+# (tests/test_tolerant_model.py measures every cell).  Mirrors tolerant_relaxes in csrc/oflk.hip.
+ENVELOPE = frozenset({(1, 1), (1, 2), (3, 2), (3, 3)})
+
+
+def tolerant_relaxes(levels: int, iters: int, window_size: int = 5) -> bool:
+    return window_size // 2 == 2 and (int(levels), int(iters)) in ENVELOPE
+
+
+def streaming_spec(levels: int = 3, iters: int = 3, shape=None) -> Spec:
+    """the tolerant mode's switches, set whatever the cell: the pyramid with fused multiply-adds; on the two finest levels
+    the streaming kernel -- fused-lerp fp64 warp, window sums vertical first then horizontal -- with the flow upsampling
+    INTO such a level in the fused-lerp form too (it is fused into the level's first iteration); coarser levels exact.
+    shape = (H, W): levels too small for the streaming kernel (5 pixels or fewer along an axis) run exactly, as in the
+    library."""
     s = Spec(levels, iters)
     s.pyr[:] = PYR["contracted"]
     dims = O.pyramid_dims(int(shape[0]), int(shape[1]), levels, 0.5) if shape is not None else None
@@ -65,6 +75,21 @@ def tolerant_spec(levels: int = 3, iters: int = 3, shape=None) -> Spec:
         s.sums[l, :] = SUMS["sep_vfirst"]
         if l > 0 and iters >= 1 and (dims is None or (dims[l - 1][0] >= 2 and dims[l - 1][1] >= 2)):
             s.up[l] = UP["lerp64"]
+    return s
+
+
+def tolerant_spec(levels: int = 3, iters: int = 3, shape=None, window_size: int = 5) -> Spec:
+    """what OFLK_ARITH_TOLERANT computes (keep in step with plan_pyramidal in csrc/oflk.hip and DESIGN.md section 2): the
+    switches of streaming_spec inside the envelope, every switch off (the exact arithmetic, pyramid included) outside it"""
+    if tolerant_relaxes(levels, iters, window_size):
+        return streaming_spec(levels, iters, shape)
+    return Spec(levels, iters)
+
+
+def contracted_spec(levels: int = 3, iters: int = 3) -> Spec:
+    """what OFLK_ARITH_CONTRACTED computes: the pyramid with fused multiply-adds, everything else exact"""
+    s = Spec(levels, iters)
+    s.pyr[:] = PYR["contracted"]
     return s
 
 

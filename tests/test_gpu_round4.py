@@ -144,9 +144,6 @@ def test_tolerant_mode_within_tolerance_of_the_reference(golden_dir):
                                        dense["bench_1080p_pair0__v"].astype(np.float32))
     assert list(runs[0]) == list(dense["bench_1080p_pair0__iters"])
     assert report["bench_1080p_pair0"] <= TOL, report
-    out = Path(__file__).resolve().parents[1] / "gpurun_out"
-    out.mkdir(exist_ok=True)
-    (out / "tolerant_epe.json").write_text(json.dumps({"mean_epe_vs_reference": report, "max": max(report.values()), "bar": TOL}, indent=1))
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -352,18 +349,20 @@ def test_contracted_mode_against_the_reference_dense_flows(golden_dir):
 
 
 def test_tolerant_mode_keeps_the_exit_decision_band_and_its_exact_redo(oracle):
-    """In the tolerant mode a level's mean |d| differs from the reference's by the mode's arithmetic AND by the summation
-    order, so a decision taken within the band around 0.01 is flagged exactly as in the exact mode, and
-    oflk_plan_resolve_uncertain redoes the pair EXACTLY (its own exact pyramid): the redone pair equals the oracle -- inside
-    any tolerance -- while pairs far from the threshold stay the tolerant model's.  Frames curr_t = prev + t * (shifted - prev),
-    t bisected on the device's own first mean of the coarsest level until it sits 2e-5 (relative) above the threshold."""
+    """The flag and its exact redo work in the tolerant mode: frames curr_t = prev + t * (shifted - prev), t bisected on the
+    DEVICE's own first mean of the (single, streaming) level until it sits 2e-5 (relative) above the threshold -- inside the
+    band -- are flagged, and oflk_plan_resolve_uncertain redoes the pair EXACTLY (its own exact pyramid): the redone pair
+    equals the oracle, while a pair far from the threshold stays the tolerant model's.  This cannot see a decision that the
+    mode's arithmetic flips OUTSIDE the band (it bisects on the device's mean, not the reference's): that the band is wide
+    enough for the mode is measured on the CPU, tests/test_tolerant_model.py
+    (test_tolerant_mode_moves_near_threshold_means_by_far_less_than_the_band).  L = 1, K = 2 is inside the envelope."""
     import torch
 
     import _oflk
     import oflk_tolerant_model as M
     from oflk_synth import synth_pair
 
-    H, W, L, K = 96, 128, 2, 3
+    H, W, L, K = 96, 128, 1, 2
     prev, shifted = synth_pair(H, W, 0, dx=0.75, dy=-0.5)
     delta = (shifted - prev).astype(np.float64)
     dev = torch.device("cuda", 0)

@@ -6,6 +6,11 @@
     dense flows THE REFERENCE produced (tests/golden/dense_reference_flows.npz, made by make_golden_dense.py importing
     it): the 13 verification patterns and pair 0 of the bench workload at 1920x1080
   * a relaxation the ablation found over the bar (an fp32 pyramid) is indeed caught by this test's measure
+  * the envelope (oflk_tolerant_relaxes in csrc/oflk.hip, ENVELOPE in the model): every (levels, iterations) cell of L 1..4 x
+    K 1..5 graded against the oracle on the 13 patterns -- inside it the relaxed arithmetic keeps a factor of three under
+    the bar with the reference's iteration counts, outside it the mode is the exact arithmetic bit for bit, and the relaxed
+    switches miss that rule there (the envelope is exactly the rule's set); the contracted mode graded the same way
+  * the exit-decision band: near-threshold means of the relaxed arithmetic sit well inside the band the library flags
 """
 import numpy as np
 import pytest
@@ -111,3 +116,199 @@ def test_tolerant_arithmetic_on_the_reference_made_mid_size_cases(oracle, golden
     u, v, _, runs = M.pyramidal(p, q, M.tolerant_spec(L, K, (h, w)), 5)
     assert list(runs) == list(oruns), (key, list(runs), list(oruns))
     assert _epe(u, v, ou, ov) <= TOL, key
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the envelope: every (levels, iterations) cell the library accepts for the 5x5 window, graded against the oracle (whose
+# flows are the reference's: tests/test_oracle_golden.py)
+# ---------------------------------------------------------------------------------------------------------------
+CELLS = [(L, K) for L in range(1, 5) for K in range(1, 6)]
+
+
+def _worst(oracle, patterns, L, K, spec_of):
+    """(worst mean EPE over the 13 patterns, every iteration count equal, every flow equal bit for bit) of the model with
+    spec_of(L, K) against the oracle"""
+    import oflk_tolerant_model as M
+
+    worst, same_runs, same_flow = 0.0, True, True
+    for n, (p, c) in patterns.items():
+        ou, ov, olog, oruns = oracle.lucas_kanade_pyramidal_ex(p, c, L, 5, K)
+        u, v, log, runs = M.pyramidal(p, c, spec_of(L, K, p.shape), 5)
+        worst = max(worst, _epe(u, v, ou, ov))
+        same_runs &= list(runs) == list(oruns)
+        same_flow &= bool(np.array_equal(u, ou) and np.array_equal(v, ov) and np.array_equal(log, olog))
+    return worst, same_runs, same_flow
+
+
+def test_the_library_states_the_same_envelope():
+    """oflk_tolerant_relaxes (what gates the streaming kernel and the contracted pyramid of a tolerant plan) == the model's
+    ENVELOPE, for every window size and far beyond the swept cells"""
+    import _oflk
+    import oflk_tolerant_model as M
+
+    lib = _oflk.lib()
+    for L in range(0, 10):
+        for K in range(0, 10):
+            for win in range(0, 16):
+                assert bool(lib.oflk_tolerant_relaxes(L, win, K)) == M.tolerant_relaxes(L, K, win), (L, K, win)
+    assert {(L, K) for L in range(10) for K in range(10) if lib.oflk_tolerant_relaxes(L, 5, K)} == set(M.ENVELOPE)
+
+
+def test_every_tolerant_switch_of_the_library_goes_through_the_envelope():
+    """the plan's arithmetic mode is only ever tested through tolerant_relaxes (the streaming kernel, the fused upsampling)
+    or contracted_pyramid (the pyramid): no gate of the library can relax a cell outside the envelope on its own"""
+    import re
+    from pathlib import Path
+
+    csrc = Path(__file__).resolve().parents[1] / "optical-flow-fpga_amd" / "csrc"
+    for f in sorted(csrc.glob("*.hip")) + sorted(csrc.glob("*.hpp")):
+        code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", f.read_text(), flags=re.S))
+        for line in code.splitlines():
+            if re.search(r"\barith\s*[!=]=", line):
+                assert "tolerant_relaxes(" in line, (f.name, line.strip())
+
+
+@pytest.mark.parametrize("cell", CELLS, ids=[f"L{L}K{K}" for L, K in CELLS])
+def test_tolerant_mode_in_every_cell(oracle, patterns, cell):
+    """inside the envelope: worst mean EPE <= TOL / 3 and the oracle's iteration counts.  Outside it: the shipped statement
+    is the exact arithmetic (every switch off) and equals the oracle bit for bit -- and the relaxed switches, forced on, do
+    miss the rule there, so no cell that keeps the rule is left out"""
+    import oflk_tolerant_model as M
+
+    L, K = cell
+    if cell in M.ENVELOPE:
+        worst, same_runs, _ = _worst(oracle, patterns, L, K, M.tolerant_spec)
+        assert same_runs, cell
+        assert worst <= TOL / 3, (cell, worst)
+        return
+    s = M.tolerant_spec(L, K, (240, 320))
+    assert not any(a.any() for a in (s.pyr, s.up, s.warp, s.sums, s.solve)), cell
+    _, same_runs, same_flow = _worst(oracle, patterns, L, K, M.tolerant_spec)
+    assert same_runs and same_flow, cell
+    worst, same_runs, _ = _worst(oracle, patterns, L, K, M.streaming_spec)
+    assert worst > TOL / 3 or not same_runs, (cell, worst, "keeps the rule: it belongs in the envelope")
+
+
+@pytest.mark.parametrize("cell", CELLS, ids=[f"L{L}K{K}" for L, K in CELLS])
+def test_contracted_mode_in_every_cell(oracle, patterns, cell):
+    """OFLK_ARITH_CONTRACTED (the contracted pyramid alone, in every cell: it has no envelope) keeps the same rule"""
+    import oflk_tolerant_model as M
+
+    L, K = cell
+    worst, same_runs, _ = _worst(oracle, patterns, L, K, lambda L_, K_, shape: M.contracted_spec(L_, K_))
+    assert same_runs, cell
+    assert worst <= TOL / 3, (cell, worst)
+
+
+def test_the_exclusion_is_not_vacuous(oracle, patterns):
+    """the relaxed switches forced on at L=4, K=2 put rotate_large far over the bar: amplification at a few ill-conditioned
+    pixels, not drift (the contracted pyramid alone moves nothing there)"""
+    import oflk_tolerant_model as M
+
+    p, c = patterns["rotate_large"]
+    ou, ov, _, _ = oracle.lucas_kanade_pyramidal_ex(p, c, 4, 5, 2)
+    u, v, _, _ = M.pyramidal(p, c, M.streaming_spec(4, 2, p.shape), 5)
+    assert _epe(u, v, ou, ov) > TOL
+    u, v, _, _ = M.pyramidal(p, c, M.contracted_spec(4, 2), 5)
+    assert np.array_equal(u, ou) and np.array_equal(v, ov)
+
+
+@pytest.mark.parametrize("key", ["e1", "e2", "e3", "m1", "m5"])
+def test_every_envelope_cell_on_the_reference_made_cases(oracle, golden_dir, key):
+    """the frames of the reference-made 5x5 cases (early exits after 1 and 2 iterations, sub-pixel smooth motion, an odd
+    481x643 shape) run in every envelope cell: mean EPE <= TOL / 3 against the oracle's flow at that cell, same iteration
+    counts"""
+    import json
+
+    import oflk_tolerant_model as M
+    from oflk_synth import synth_pair, synth_pair_smooth
+
+    c = json.loads((golden_dir / "reference_fullsize.json").read_text())[key]
+    h, w = c["shape"]
+    gen = synth_pair_smooth if c.get("smooth") else synth_pair
+    p, q = gen(h, w, c.get("pair_index", 0), c.get("dx", 3.0), c.get("dy", -1.5))
+    for L, K in sorted(M.ENVELOPE):
+        ou, ov, _, oruns = oracle.lucas_kanade_pyramidal_ex(p, q, L, 5, K)
+        u, v, _, runs = M.pyramidal(p, q, M.tolerant_spec(L, K, (h, w)), 5)
+        assert list(runs) == list(oruns), (key, L, K, list(runs), list(oruns))
+        assert _epe(u, v, ou, ov) <= TOL / 3, (key, L, K)
+
+
+def test_every_envelope_cell_on_the_bench_pair(oracle):
+    import oflk_tolerant_model as M
+    from oflk_synth import synth_pair
+
+    p, c = synth_pair(1080, 1920, 0)
+    for L, K in sorted(M.ENVELOPE):
+        ou, ov, _, oruns = oracle.lucas_kanade_pyramidal_ex(p, c, L, 5, K)
+        u, v, _, runs = M.pyramidal(p, c, M.tolerant_spec(L, K, p.shape), 5)
+        assert list(runs) == list(oruns), (L, K)
+        assert _epe(u, v, ou, ov) <= TOL / 3, (L, K)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the exit-decision band.  The library flags a decision when the level's exactly accumulated mean |d| lies within
+# decision_guard(n) (relative, csrc/oflk_kernels.hpp) of 0.01, in every arithmetic mode.  That band is sized by NumPy's
+# summation error; the relaxed arithmetic moves the mean too, so its shift of a mean NEAR 0.01 is measured here and must
+# stay within a quarter of the band.
+# ---------------------------------------------------------------------------------------------------------------
+def decision_guard(npix: int) -> float:
+    """csrc/oflk_kernels.hpp decision_guard"""
+    return max(5e-5, (np.ceil(npix / 8192.0) + 32.0) * 2.0 ** -24)
+
+
+def test_tolerant_mode_moves_near_threshold_means_by_far_less_than_the_band(oracle):
+    """Pairs whose logged means sit near the threshold, in every envelope cell, built two ways: curr = prev + t * (shifted -
+    prev) with t bisected on the ORACLE's mean at an iteration >= 1 (0 when K = 1) of each streaming level, and smooth sub-pixel
+    pairs (synth_pair_smooth) that leave their loops early.  For every logged mean of a streaming level within [0.5, 2] x
+    0.01 -- taken while every earlier exit decision agreed, so that it is the arithmetic's shift and not the aftermath of a
+    flipped (flagged) decision upstream -- |model mean - oracle mean| / oracle mean <= decision_guard(level pixels) / 4.
+    Measured maximum 8.1e-7 (L=3, K=2 and K=3), against a quarter band of 1.25e-5."""
+    import oflk_tolerant_model as M
+    from oflk_synth import synth_pair, synth_pair_smooth
+
+    thr = float(np.float32(0.01))
+    H, W = 96, 128
+    worst, seen = {}, {}
+
+    def collect(p, c, L, K):
+        ou, ov, olog, oruns = oracle.lucas_kanade_pyramidal_ex(p, c, L, 5, K)
+        s = M.tolerant_spec(L, K, p.shape)
+        _, _, mlog, mruns = M.pyramidal(p, c, s, 5)
+        dims = oracle.pyramid_dims(H, W, L)
+        for l in range(L):
+            if not s.sums[l].any() or list(oruns[:l]) != list(mruns[:l]):
+                continue
+            for k in range(min(oruns[l], mruns[l])):
+                for ax in range(2):
+                    o, m = float(olog[l, k, ax]), float(mlog[l, k, ax])
+                    if 0.5 * thr <= o <= 2.0 * thr:
+                        r = abs(m - o) / o / decision_guard(dims[l][0] * dims[l][1])
+                        worst[(L, K)] = max(worst.get((L, K), 0.0), r)
+                        seen[(L, K)] = seen.get((L, K), 0) + 1
+        return olog, oruns
+
+    for (L, K) in sorted(M.ENVELOPE):
+        for pi, (dx, dy) in ((0, (0.75, -0.5)), (1, (3.0, -1.5)), (2, (0.2, 0.1))):
+            prev, shifted = synth_pair(H, W, pi, dx=dx, dy=dy)
+            delta = (shifted - prev).astype(np.float64)
+            for l in range(max(L - 2, 0), L):
+                k = min(1, K - 1)
+
+                def mean_at(t):
+                    olog, oruns = collect(prev, (prev + t * delta).astype(np.float32), L, K)
+                    return float(max(olog[l, k])) if oruns[l] > k else 0.0   # left the loop before k: below
+
+                lo, hi = 0.0, 1.0
+                assert mean_at(lo) < thr < mean_at(hi), (L, K, l, pi)
+                for _ in range(24):
+                    mid = 0.5 * (lo + hi)
+                    if mean_at(mid) < thr:
+                        lo = mid
+                    else:
+                        hi = mid
+        for pi in range(4):
+            for dx, dy in ((0.01, 0.0), (0.02, 0.01), (0.04, -0.02), (0.06, 0.03), (0.1, 0.05), (0.3, 0.1)):
+                collect(*synth_pair_smooth(H, W, pi, dx, dy), L, K)
+    assert set(seen) == set(M.ENVELOPE) and min(seen.values()) >= 100, seen
+    assert max(worst.values()) <= 0.25, worst

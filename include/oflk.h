@@ -216,10 +216,12 @@ int oflk_plan_read_log(oflk_plan *plan, float *residual_log, int *iters_run, voi
 
 /* After oflk_plan_pyramidal + read_log: uncertain[b*levels + l] has bit k set when the early-exit test
  * after iteration k of level l (python/lucas_kanade_pyramidal.py:221-223) was decided with a mean
- * within the level's band around the 0.01 threshold: max(5e-5, (ceil(npix / 8192) + 32) * 2^-24) relative, i.e.
- * 5e-5 up to 6.9 Mpx levels, 6.2e-5 at 4K, 2.4e-4 at 8K.  The reference sums np.mean in fp32 (pairwise, in
- * 8192-element pieces), the device in exact fixed point; the two can only decide differently inside
- * that band, so 0 everywhere means "provably the reference's iteration counts".  Synchronises. */
+ * within the level's band around the 0.01 threshold, oflk_decision_guard (below): NumPy's error bound
+ * (ceil(npix / 8192) + 32) * 2^-24 plus the device's (oflk_device_mean_error at 0.01), at least 5e-5 relative, i.e.
+ * 5e-5 up to 1080p, 6.3e-5 at 4K, 2.44e-4 at 8K.  The reference sums np.mean in fp32 (pairwise, in 8192-element
+ * pieces); the device adds partial sums formed in fp32 / fp64 and each rounded to a 2^-20 px grid (one per block of
+ * the tile kernel, one per wave of the streaming kernel) -- neither is exact, and the band covers both errors, so
+ * 0 everywhere means "provably the reference's iteration counts".  Synchronises. */
 int oflk_plan_read_uncertain(oflk_plan *plan, int *uncertain, void *stream);
 
 /* Closes that band: every pair of the last pass with a flagged decision is redone -- that pair alone, with
@@ -279,8 +281,8 @@ int oflk_plan_read_level_flow(oflk_plan *plan, int level, int pair, float *u, fl
  * kernels are held to that statement bit for bit in every cell (tests/test_gpu_tolerant_envelope.py), so the tolerance is a
  * property of one written-down arithmetic, not of a GPU run.
  * In both opt-in modes the exit-decision flags keep their meaning: a decision is flagged when the level's mean |d| lies within
- * the same band around 0.01 as in the exact mode, sized by NumPy's summation error at the level's pixel count (at least 5e-5
- * relative).  The band needs no widening for the opt-in arithmetic: on constructed near-threshold pairs in every envelope
+ * the band around 0.01 of the kernel that summed it (oflk_decision_guard: NumPy's summation error at the level's pixel count
+ * plus the device's, at least 5e-5 relative).  The band needs no widening for the opt-in arithmetic itself: on constructed near-threshold pairs in every envelope
  * cell, a logged mean within [0.5, 2] x 0.01 differs from the reference's by at most 8.1e-7 relative (the tests hold it to a
  * quarter of the band).  oflk_plan_resolve_uncertain redoes a flagged pair in EXACT arithmetic from the caller's frames (its
  * own exact pyramid): a redone pair is the reference's result, which is inside any tolerance.  Windows without a fused
@@ -297,6 +299,19 @@ int oflk_set_host_arithmetic(int mode);
 /* 1 when OFLK_ARITH_TOLERANT relaxes anything in a pass of `levels` levels, `window_size` window and `iterations`
  * iterations (its envelope, above), 0 when the mode runs that configuration exactly.  Host-only; never fails. */
 int oflk_tolerant_relaxes(int levels, int window_size, int iterations);
+/* The exit band's two terms for one pair's level of level_h x level_w pixels, by how the level sums |d|:
+ * OFLK_SUM_TILES (the tile kernels: every level of exact / contracted plans, coarse levels of tolerant ones),
+ * OFLK_SUM_STREAMING (the streaming kernel: the tolerant mode's two finest levels inside its envelope), OFLK_SUM_HOST
+ * (windows without a fused iteration kernel: NumPy's own mean, taken on the host).  oflk_device_mean_error: E_dev, the
+ * worst-case relative error of the logged / compared mean against the exact mean `mean` of the same d (it grows as the
+ * mean shrinks: the grid roundings are absolute); for OFLK_SUM_HOST, NumPy's bound.  oflk_decision_guard: the relative
+ * half-width of the band in which decisions are flagged (0 for OFLK_SUM_HOST, which decides as NumPy does).  The
+ * derivation is at decision_guard in csrc/oflk_kernels.hpp.  Host-only; never fail. */
+#define OFLK_SUM_TILES 0
+#define OFLK_SUM_STREAMING 1
+#define OFLK_SUM_HOST 2
+double oflk_device_mean_error(int path, int level_h, int level_w, double mean);
+double oflk_decision_guard(int path, int level_h, int level_w);
 
 /* Which kernel runs a single-scale pass (oflk_plan_single_scale / _u8; results are the reference's either way).
  * The 5x5 and 7x7 windows have a streaming kernel (no LDS; window sums vertical-then-horizontal), which equals np.sum's order exactly

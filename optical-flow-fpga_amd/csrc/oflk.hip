@@ -1059,7 +1059,10 @@ int plan_pyramidal(oflk_plan *p, const void *d_prev_in, const void *d_curr_in, b
         e.uncertain = p->uncertain();
         for (int l = 0; l < L; l++) {
             const double t = (double)e.thr[l];
-            const double g = decision_guard(e.counts[l]);
+            const int h = p->dims[2 * l], w = p->dims[2 * l + 1];
+            // the same choice of kernel as the level's launches above
+            const bool stream = p->arith == OFLK_ARITH_TOLERANT && tolerant_relaxes(L, p->hw, K) && l >= L - 2 && h > 4 && w > 4;
+            const double g = decision_guard(stream ? SUM_STREAM : SUM_TILES, h, w);
             e.guard_lo[l] = (unsigned long long)std::floor(t * (1.0 - g));
             e.guard_hi[l] = (unsigned long long)std::ceil(t * (1.0 + g));
         }
@@ -1332,6 +1335,16 @@ OFLK_API int oflk_set_host_arithmetic(int mode)
 OFLK_API int oflk_tolerant_relaxes(int levels, int window_size, int iterations)
 {
     return window_size >= 1 && tolerant_relaxes(levels, window_size / 2, iterations) ? 1 : 0;
+}
+
+OFLK_API double oflk_device_mean_error(int path, int level_h, int level_w, double mean)
+{
+    return device_mean_error(path, level_h, level_w, mean);
+}
+
+OFLK_API double oflk_decision_guard(int path, int level_h, int level_w)
+{
+    return decision_guard(path, level_h, level_w);
 }
 
 OFLK_API int oflk_multi_rehearsal(int workers)

@@ -670,9 +670,9 @@ template <int HW> struct LkGeom {
 // the means, how many iterations of the level were executed before the early exit
 // (:221-223) and hence which ping-pong slot holds the current flow.
 //
-// The reference's np.mean is an fp32 pairwise sum; the two agree to ~1e-7 relative, which can
-// flip the "< 0.01" test only when the mean sits within that distance of the threshold
-// (DESIGN.md "Known deviations").
+// The totals are not exact: every block's fp32/fp64 sum is rounded to the 2^-20 grid once, and the
+// reference's np.mean is an fp32 pairwise sum; either can flip the "< 0.01" test only when the mean sits
+// within their combined error of the threshold (device_mean_error, decision_guard; DESIGN.md "Known deviations").
 // ---------------------------------------------------------------------------
 constexpr int kAccShards = 8;
 constexpr int kAccStride = 64;   // u64 words between shards (512 B: every shard on a line, and likely a channel, of its own)
@@ -2772,25 +2772,64 @@ struct ExportArgs {
     unsigned long long thr[OFLK_MAX_LEVELS];    // early-exit thresholds as totals
     float *log;                  // [B][L][K][2]
     int *iters_run;              // [B][L]
-    int *uncertain;              // [B][L]: bit k set = the exit decision after iteration k was taken within kDecisionGuard of the threshold
+    int *uncertain;              // [B][L]: bit k set = the exit decision after iteration k was taken within decision_guard of the threshold
     unsigned long long guard_lo[OFLK_MAX_LEVELS], guard_hi[OFLK_MAX_LEVELS];   // totals bounding that band
     size_t plane;
 };
 
-// The early-exit test compares np.mean(np.abs(d)) -- an fp32 pairwise sum in 8192-element pieces added
-// up one after the other (error bound ~ pieces x 2^-24 relative) -- with float32(0.01); the device
-// compares an exactly accumulated fixed-point total instead.  The two decisions can only differ when a
-// mean lies within the summation error of the threshold: every decision taken within +-kDecisionGuard
-// (relative) of it is reported, so a caller can tell "provably the reference's decision" from "too
-// close to call" (never seen outside constructed inputs; tests/test_gpu_round2.py builds them).
-// The band follows the level's size: NumPy adds ceil(n / 8192) pieces one after the other (each itself a
-// pairwise sum, a few 2^-24), so its worst-case error grows with the pixel count and passes 5e-5 at ~6.9 Mpx
-// (a 4K finest level: 6.2e-5, 8K: 2.4e-4).
-constexpr double kDecisionGuard = 5e-5;   // floor of the band
-inline double decision_guard(double npix)
+// The early-exit test compares np.mean(np.abs(d)) -- an fp32 pairwise sum in 8192-element pieces added up one after the
+// other, then one fp32 division -- with float32(0.01).  For non-negative terms its error relative to the exact mean m is
+// at most numpy_mean_error(n) = (ceil(n / 8192) + 32) 2^-24 (a sum's depth in roundings: the pieces, plus 6 halvings, 16
+// strided adds and 3 combining adds inside a piece, plus the division, and slack).
+//
+// The device does NOT compare an exact total.  It compares T, an integer sum of partial sums each formed in floating point
+// and then rounded to the 2^-20 px grid (kAccScale); the decision is T < conv_threshold(n), i.e. float32(T 2^-20 / n) <
+// 0.01f.  Against the exact mean m of the same d, device_mean_error(path, H, W, m) bounds it relatively (E_dev):
+//   - fp32 sums of non-negative terms before the rounding: at most depth x 2^-24 relative (each term passes through at most
+//     `depth` roundings).  k_lkw (SUM_TILES): 2 k5NY terms per thread added in turn (2 k5NY - 1 roundings), then the
+//     6-step DPP reduction of the wave: 2 k5NY + 5.  k_lks (SUM_STREAM): 2 x 3 terms of three rows per lane: 5.
+//   - fp64 sums after it (waves and tiles of a block; a lane's row groups and the wave's butterfly): < (H + 16) 2^-53.
+//   - the roundings to the grid: at most 2^-21 px each, one per PARTIAL, i.e. an absolute error of partials 2^-21 / n on
+//     the mean -- it does not shrink with the mean, so relative to m it is partials 2^-21 / (n m).  k_lkw rounds per
+//     block (at most one per 64 x 8 k5NY tile); k_lks per wave (strips of 120 columns x segments of >= 8 rows; see
+//     launch_lks, whose last segment rule caps them at max(1, H / 8)).  Partials without a pixel are 0 and exact.
+//   - the clamp at kAccBlockMax = 2^28 px per partial: a clamped total alone is >= 2^28 px, a mean >= 0.01 at any plane
+//     below 2.6e10 px (a plane is < 2^30), so the clamp never turns "not below" into "below".
+//   - the logged mean (and the threshold T is compared with) is float32(T 2^-20 / n): 2^-24.
+// SUM_HOST (windows without a fused iteration kernel, resolve_pair): the host takes NumPy's own mean in NumPy's order, so
+// its decisions ARE the reference's (E_dev against NumPy is 0, against m it is numpy_mean_error) and nothing is flagged.
+//
+// The two decisions can differ only when m lies within numpy_mean_error(n) + E_dev(0.01) (+ 2^-24 for the second-order
+// terms) of the threshold: every decision taken within decision_guard (relative, at least kDecisionGuard) of it is
+// reported, so a caller can tell "provably the reference's decision" from "too close to call" (never seen outside
+// constructed inputs; tests/test_gpu_exit_band.py builds them).  NumPy's term grows with the pixel count and passes 5e-5
+// at ~6.9 Mpx; E_dev at 0.01 is ~13 x 2^-24 for k_lkw and ~7 x 2^-24 for k_lks at the sizes the bench runs, so the band
+// is 5e-5 up to 1080p and (NumPy + E_dev) above: 4K 6.31e-5 (k_lkw), 8K 2.44e-4.
+enum SumPath { SUM_TILES = OFLK_SUM_TILES, SUM_STREAM = OFLK_SUM_STREAMING, SUM_HOST = OFLK_SUM_HOST };
+constexpr double kU32 = 5.9604644775390625e-08;   // 2^-24
+constexpr double kDecisionGuard = 5e-5;           // floor of the band
+inline double numpy_mean_error(double npix) { return (std::ceil(npix / 8192.0) + 32.0) * kU32; }
+// rounded partial sums of one pair's level of H x W pixels
+inline double device_mean_partials(int path, int H, int W)
 {
-    const double pieces = std::ceil(npix / 8192.0);
-    return std::max(kDecisionGuard, (pieces + 32.0) * 5.9604644775390625e-08);   // 2^-24
+    if (path == SUM_TILES) return std::ceil(W / 64.0) * std::ceil(H / (8.0 * k5NY));
+    if (path == SUM_STREAM) return std::ceil(W / 120.0) * std::max(1, H / 8);
+    return 0.0;
+}
+inline double device_mean_fp32_depth(int path) { return path == SUM_TILES ? 2 * k5NY + 5 : path == SUM_STREAM ? 5 : 0; }
+// E_dev: |device mean - m| <= device_mean_error(path, H, W, m) * m
+inline double device_mean_error(int path, int H, int W, double mean)
+{
+    if (path == SUM_HOST) return numpy_mean_error((double)H * W);
+    const double d = device_mean_fp32_depth(path);
+    const double rel = d * kU32 * (1.0 + d * kU32) + (H + 16.0) * 1.1102230246251565e-16 + kU32;
+    return rel + device_mean_partials(path, H, W) * 4.76837158203125e-07 / ((double)H * W * mean);   // 2^-53, 2^-21
+}
+inline double decision_guard(int path, int H, int W)
+{
+    if (path == SUM_HOST) return 0.0;
+    const double n = (double)H * W;
+    return std::min(1.0, std::max(kDecisionGuard, numpy_mean_error(n) + device_mean_error(path, H, W, 0.01) + kU32));
 }
 
 // End of a pyramidal call.  (1) Pairs whose finest level exited early hold their result in

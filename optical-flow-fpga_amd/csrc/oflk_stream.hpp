@@ -545,17 +545,17 @@ __global__ __launch_bounds__(256) OFLK_LKS_ATTR void k_lks(LkArgs a)
         }
     }
     if constexpr (MODE == MODE_ITER) {
-        // the wave's totals in the accumulators' fixed point: integer adds commute, so neither the lane order here nor the
-        // order of the waves' atomics matters
-        const double cap = kAccBlockMax / 64.0;
-        dsu = dsu < cap ? dsu : cap;   // (also catches NaN)
-        dsv = dsv < cap ? dsv : cap;
-        long long tu = __double2ll_rn(dsu * kAccScale), tv = __double2ll_rn(dsv * kAccScale);
+        // the wave's totals in fp64 (a butterfly: every lane ends with the same sum), then ONE rounding to the accumulators'
+        // fixed point per wave (device_mean_error counts these roundings); integer adds commute, so the order of the waves'
+        // atomics does not matter
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) {
-            tu += __shfl_xor(tu, m, 64);
-            tv += __shfl_xor(tv, m, 64);
+            dsu += __shfl_xor(dsu, m, 64);
+            dsv += __shfl_xor(dsv, m, 64);
         }
+        dsu = dsu < kAccBlockMax ? dsu : kAccBlockMax;   // (also catches NaN)
+        dsv = dsv < kAccBlockMax ? dsv : kAccBlockMax;
+        long long tu = __double2ll_rn(dsu * kAccScale), tv = __double2ll_rn(dsv * kAccScale);
         if (touch == 1.5e38f) tu += 1;   // never true for pixel data; makes `touch` observable
         if (lane == 0) {
             unsigned long long *slot = a.acc + acc_index(b, a.level, a.iter, a.L, a.K) + kAccStride * (task & (kAccShards - 1));

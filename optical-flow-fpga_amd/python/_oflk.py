@@ -68,6 +68,8 @@ SIGNATURES = {
     "oflk_plan_resolve_uncertain": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32p]),
     "oflk_plan_resolve_uncertain_u8": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32p]),
     "oflk_last_resolved": (ctypes.c_int, []),
+    "oflk_device_mean_error": (ctypes.c_double, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double]),
+    "oflk_decision_guard": (ctypes.c_double, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "oflk_plan_read_uncertain": (ctypes.c_int, [_vp, _i32p, _vp]),
     "oflk_plan_read_level_flow": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _f32p, _f32p, _vp]),
     "oflk_pyramidal_last_level_flow": (ctypes.c_int, [ctypes.c_int] * 8 + [_f32p, _f32p]),
@@ -209,7 +211,8 @@ class Plan:
         return log, runs
 
     def read_uncertain(self, stream: int = 0) -> np.ndarray:
-        """[B][levels] bit masks: bit k = exit decision after iteration k taken within 5e-5 of the threshold."""
+        """[B][levels] bit masks: bit k = exit decision after iteration k taken within the level's band around the threshold
+        (oflk_decision_guard: at least 5e-5 relative)."""
         m = np.zeros((self.B, self.levels), np.int32)
         check(lib().oflk_plan_read_uncertain(self._h, m.ctypes.data_as(_i32p), stream))
         return m

@@ -143,6 +143,74 @@ OFLK_EXPORT float oflk_oracle_mean_abs(const float *d, size_t n)
     return (float)((double)s / (double)n);
 }
 
+/* The exact mean of |d| (test infrastructure for the early-exit band, not a NumPy restatement): every |d| is
+ * M * 2^(e - 150) with a 24-bit integer M, so the sum is gathered without rounding as one integer per binary exponent
+ * (each below n * 2^24 <= 2^53, hence an exact double once scaled), the <= 254 scaled integers are added with
+ * Shewchuk's exact, correctly rounded summation, and the sum is divided by n once in fp64.  The result is within two
+ * fp64 roundings (2^-52 relative) of the true mean.  NaN / inf terms give NaN / inf; an empty array gives NaN, as np.mean does. */
+static double exact_sum_f64(const double *x, int m)
+{
+    double p[80];
+    int np = 0;
+    for (int i = 0; i < m; i++) {
+        double v = x[i];
+        int j = 0;
+        for (int k = 0; k < np; k++) {
+            double y = p[k];
+            if (fabs(v) < fabs(y)) {
+                const double t = v;
+                v = y;
+                y = t;
+            }
+            const double hi = v + y, lo = y - (hi - v);
+            if (lo != 0.0) p[j++] = lo;
+            v = hi;
+        }
+        p[j] = v;
+        np = j + 1;
+    }
+    /* the partials do not overlap and grow: add them from the top, then break a half-way tie the right way */
+    double hi = 0.0, lo = 0.0;
+    int k = np;
+    if (k > 0) {
+        hi = p[--k];
+        while (k > 0) {
+            const double a = hi, y = p[--k];
+            hi = a + y;
+            lo = y - (hi - a);
+            if (lo != 0.0) break;
+        }
+        if (k > 0 && ((lo < 0.0 && p[k - 1] < 0.0) || (lo > 0.0 && p[k - 1] > 0.0))) {
+            const double y = lo * 2.0, a = hi + y;
+            if (y == a - hi) hi = a;
+        }
+    }
+    return hi;
+}
+
+OFLK_EXPORT double oflk_oracle_exact_mean_abs(const float *d, size_t n)
+{
+    if (n == 0 || n > ((size_t)1 << 29)) return NAN;   /* 2^29 * 2^24: every per-exponent total stays an exact double */
+    uint64_t acc[255] = {0};
+    double special = 0.0;
+    for (size_t i = 0; i < n; i++) {
+        uint32_t b;
+        memcpy(&b, &d[i], 4);
+        b &= 0x7fffffffu;
+        const uint32_t e = b >> 23, m = b & 0x7fffffu;
+        if (e == 255u) {
+            special += fabsf(d[i]);
+            continue;
+        }
+        if (e) acc[e] += m | 0x800000u;
+        else acc[1] += m;   /* subnormal: M * 2^-149 = M * 2^(1 - 150) */
+    }
+    if (special != 0.0 || special != special) return special;
+    double t[255];
+    for (int e = 0; e < 255; e++) t[e] = ldexp((double)acc[e], e - 150);
+    return exact_sum_f64(t, 255) / (double)n;
+}
+
 /* ------------------------------------------------------------------------- */
 /* compute_gradients  (lucas_kanade_core.py:15-45)                           */
 /* ------------------------------------------------------------------------- */
@@ -521,9 +589,11 @@ OFLK_EXPORT void oflk_oracle_upsample_flow(const float *u, const float *v, int H
  * residual_log[(l*iters + k)*2 + {0,1}] = mean|du|, mean|dv| of iteration k at
  * level l (only the first iters_run[l] entries of a level are written).
  * Returns 0, or -1 on bad arguments.                                         */
-OFLK_EXPORT int oflk_oracle_pyramidal(const float *prev, const float *curr, int H, int W,
-                                      int levels, int window_size, int iters, float *u_out,
-                                      float *v_out, float *residual_log, int *iters_run)
+/* exact_log (optional, [levels][iters][2] doubles): the exact mean of |du|, |dv| of every executed (level, iteration)
+ * (oflk_oracle_exact_mean_abs), next to the NumPy-order means of residual_log */
+OFLK_EXPORT int oflk_oracle_pyramidal_x(const float *prev, const float *curr, int H, int W,
+                                        int levels, int window_size, int iters, float *u_out,
+                                        float *v_out, float *residual_log, int *iters_run, double *exact_log)
 {
     if (levels < 1 || levels > 32 || H < 1 || W < 1) return -1;
     int dims[64];
@@ -571,6 +641,10 @@ OFLK_EXPORT int oflk_oracle_pyramidal(const float *prev, const float *curr, int 
                 residual_log[((size_t)l * iters + k) * 2 + 0] = mu;
                 residual_log[((size_t)l * iters + k) * 2 + 1] = mv;
             }
+            if (exact_log) {
+                exact_log[((size_t)l * iters + k) * 2 + 0] = oflk_oracle_exact_mean_abs(du, n);
+                exact_log[((size_t)l * iters + k) * 2 + 1] = oflk_oracle_exact_mean_abs(dv, n);
+            }
             if (iters_run) iters_run[l] = k + 1;
             if (mu < 0.01f && mv < 0.01f) break; /* :221-223, fp32 vs float32(0.01) */
         }
@@ -588,4 +662,12 @@ OFLK_EXPORT int oflk_oracle_pyramidal(const float *prev, const float *curr, int 
         free(pc[l]);
     }
     return 0;
+}
+
+OFLK_EXPORT int oflk_oracle_pyramidal(const float *prev, const float *curr, int H, int W,
+                                      int levels, int window_size, int iters, float *u_out,
+                                      float *v_out, float *residual_log, int *iters_run)
+{
+    return oflk_oracle_pyramidal_x(prev, curr, H, W, levels, window_size, iters, u_out, v_out, residual_log, iters_run,
+                                   NULL);
 }

@@ -61,6 +61,10 @@ def lib() -> ctypes.CDLL:
         L.oflk_oracle_upsample_flow.argtypes = [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f32p, _f32p]
         L.oflk_oracle_pyramidal.argtypes = [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f32p, _f32p, _f32p, _i32p]
         L.oflk_oracle_pyramidal.restype = ctypes.c_int
+        L.oflk_oracle_pyramidal_x.argtypes = L.oflk_oracle_pyramidal.argtypes + [_f64p]
+        L.oflk_oracle_pyramidal_x.restype = ctypes.c_int
+        L.oflk_oracle_exact_mean_abs.argtypes = [_f32p, ctypes.c_size_t]
+        L.oflk_oracle_exact_mean_abs.restype = ctypes.c_double
         L.oflk_oracle_build_pyramid_w.argtypes = [_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, _f64p, ctypes.c_int, ctypes.POINTER(_f32p)]
     return _lib
 
@@ -193,19 +197,31 @@ def upsample_flow(flow_u, flow_v, target_shape) -> Tuple[np.ndarray, np.ndarray]
     return uo, vo
 
 
+def exact_mean_abs(a) -> float:
+    """The mean of |a| without rounding error in the sum: an exact sum of the float32 values, one fp64 division
+    (not NumPy's arithmetic; the yardstick that np.mean's and the library's means are held to)."""
+    a = _c(a)
+    return float(lib().oflk_oracle_exact_mean_abs(_p(a), a.size))
+
+
 def lucas_kanade_pyramidal_ex(frame_prev, frame_curr, num_levels: int = 3, window_size: int = 5,
-                              num_iterations: int = 3):
-    """Returns (u, v, residual_log[levels, iters, 2], iters_run[levels])."""
+                              num_iterations: int = 3, exact_means: bool = False):
+    """Returns (u, v, residual_log[levels, iters, 2], iters_run[levels]); with exact_means also exact_log[levels, iters, 2]
+    (float64): the exact mean (exact_mean_abs) of the same |du|, |dv| of every executed (level, iteration), 0 elsewhere."""
     p, c = _c(frame_prev), _c(frame_curr)
     H, W = p.shape
     u, v = np.empty((H, W), np.float32), np.empty((H, W), np.float32)
     log = np.zeros((num_levels, max(num_iterations, 1), 2), np.float32)
+    xlog = np.zeros((num_levels, max(num_iterations, 1), 2), np.float64)
     runs = np.zeros(num_levels, np.int32)
-    rc = lib().oflk_oracle_pyramidal(_p(p), _p(c), H, W, int(num_levels), int(window_size),
-                                     int(num_iterations), _p(u), _p(v), _p(log),
-                                     runs.ctypes.data_as(_i32p))
+    rc = lib().oflk_oracle_pyramidal_x(_p(p), _p(c), H, W, int(num_levels), int(window_size),
+                                       int(num_iterations), _p(u), _p(v), _p(log),
+                                       runs.ctypes.data_as(_i32p),
+                                       xlog.ctypes.data_as(_f64p) if exact_means else None)
     if rc != 0:
         raise ValueError("oflk_oracle_pyramidal: bad arguments")
+    if exact_means:
+        return u, v, log[:, :num_iterations], runs, xlog[:, :num_iterations]
     return u, v, log[:, :num_iterations], runs
 
 

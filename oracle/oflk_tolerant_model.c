@@ -31,6 +31,7 @@ void oflk_oracle_pyramid_dims(int, int, int, double, int *);
 void oflk_oracle_warp(const float *, const float *, const float *, int, int, float *);
 void oflk_oracle_upsample_flow(const float *, const float *, int, int, int, int, float *, float *);
 float oflk_oracle_mean_abs(const float *, size_t);
+double oflk_oracle_exact_mean_abs(const float *, size_t);
 int oflk_oracle_gaussian_kernel1d(double, double *);
 
 /* ---- variants ------------------------------------------------------------------------------------------- */
@@ -375,10 +376,11 @@ static void lk_variant(const float *prev, const float *curr, int H, int W, int w
  * pyr_v[l]            variant of the pyramid step that PRODUCES level l (l < levels-1), both frames
  * up_v[l]             variant of the flow upsample INTO level l (l >= 1)
  * warp_v / sums_v / solve_v [l*iters + k]   variants of iteration k of level l
- * Returns 0 or -1.  residual_log / iters_run as oflk_oracle_pyramidal. */
-OFLK_EXPORT int oflk_model_pyramidal(const float *prev, const float *curr, int H, int W, int levels, int win, int iters,
-                                     const int *pyr_v, const int *up_v, const int *warp_v, const int *sums_v,
-                                     const int *solve_v, float *u_out, float *v_out, float *residual_log, int *iters_run)
+ * Returns 0 or -1.  residual_log / iters_run / exact_log as oflk_oracle_pyramidal_x. */
+OFLK_EXPORT int oflk_model_pyramidal_x(const float *prev, const float *curr, int H, int W, int levels, int win, int iters,
+                                       const int *pyr_v, const int *up_v, const int *warp_v, const int *sums_v,
+                                       const int *solve_v, float *u_out, float *v_out, float *residual_log, int *iters_run,
+                                       double *exact_log)
 {
     if (levels < 1 || levels > 32 || H < 1 || W < 1) return -1;
     int dims[64];
@@ -434,6 +436,10 @@ OFLK_EXPORT int oflk_model_pyramidal(const float *prev, const float *curr, int H
                 residual_log[((size_t)l * iters + k) * 2 + 0] = mu;
                 residual_log[((size_t)l * iters + k) * 2 + 1] = mv;
             }
+            if (exact_log) {
+                exact_log[((size_t)l * iters + k) * 2 + 0] = oflk_oracle_exact_mean_abs(du, n);
+                exact_log[((size_t)l * iters + k) * 2 + 1] = oflk_oracle_exact_mean_abs(dv, n);
+            }
             if (iters_run) iters_run[l] = k + 1;
             if (mu < 0.01f && mv < 0.01f) break;
         }
@@ -448,4 +454,12 @@ OFLK_EXPORT int oflk_model_pyramidal(const float *prev, const float *curr, int H
         free(pc[l]);
     }
     return 0;
+}
+
+OFLK_EXPORT int oflk_model_pyramidal(const float *prev, const float *curr, int H, int W, int levels, int win, int iters,
+                                     const int *pyr_v, const int *up_v, const int *warp_v, const int *sums_v,
+                                     const int *solve_v, float *u_out, float *v_out, float *residual_log, int *iters_run)
+{
+    return oflk_model_pyramidal_x(prev, curr, H, W, levels, win, iters, pyr_v, up_v, warp_v, sums_v, solve_v, u_out, v_out,
+                                  residual_log, iters_run, NULL);
 }

@@ -27,6 +27,8 @@ def _lib():
     if not _bound:
         L.oflk_model_pyramidal.argtypes = [O._f32p, O._f32p] + [ctypes.c_int] * 5 + [_i32p] * 5 + [O._f32p] * 3 + [_i32p]
         L.oflk_model_pyramidal.restype = ctypes.c_int
+        L.oflk_model_pyramidal_x.argtypes = L.oflk_model_pyramidal.argtypes + [O._f64p]
+        L.oflk_model_pyramidal_x.restype = ctypes.c_int
         _bound = True
     return L
 
@@ -93,18 +95,22 @@ def contracted_spec(levels: int = 3, iters: int = 3) -> Spec:
     return s
 
 
-def pyramidal(prev, curr, spec: Spec, window_size: int = 5):
-    """(u, v, residual_log[levels, iters, 2], iters_run[levels]) of the model with `spec`"""
+def pyramidal(prev, curr, spec: Spec, window_size: int = 5, exact_means: bool = False):
+    """(u, v, residual_log[levels, iters, 2], iters_run[levels]) of the model with `spec`; with exact_means also
+    exact_log[levels, iters, 2] (float64), as oflk_oracle.lucas_kanade_pyramidal_ex"""
     p, c = O._c(prev), O._c(curr)
     H, W = p.shape
     L, K = spec.levels, spec.iters
     u, v = np.empty((H, W), np.float32), np.empty((H, W), np.float32)
     log = np.zeros((L, max(K, 1), 2), np.float32)
+    xlog = np.zeros((L, max(K, 1), 2), np.float64)
     runs = np.zeros(L, np.int32)
     arrs = [np.ascontiguousarray(a, np.int32) for a in (spec.pyr, spec.up, spec.warp, spec.sums, spec.solve)]
-    rc = _lib().oflk_model_pyramidal(O._p(p), O._p(c), H, W, L, int(window_size), K,
-                                     *[a.ctypes.data_as(_i32p) for a in arrs], O._p(u), O._p(v), O._p(log),
-                                     runs.ctypes.data_as(_i32p))
+    rc = _lib().oflk_model_pyramidal_x(O._p(p), O._p(c), H, W, L, int(window_size), K,
+                                       *[a.ctypes.data_as(_i32p) for a in arrs], O._p(u), O._p(v), O._p(log),
+                                       runs.ctypes.data_as(_i32p), xlog.ctypes.data_as(O._f64p) if exact_means else None)
     if rc != 0:
         raise ValueError("oflk_model_pyramidal: bad arguments")
+    if exact_means:
+        return u, v, log[:, :K], runs, xlog[:, :K]
     return u, v, log[:, :K], runs

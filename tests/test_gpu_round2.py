@@ -348,7 +348,7 @@ def _threshold_family(oracle, H=96, W=128, L=2, K=3):
 
 def test_exit_decisions_next_to_the_threshold(oracle):
     """A ladder of inputs around the crossing (both sides, relative offsets 1e-7 ... 3e-2).  The device decides
-    from an exact fixed-point total, the reference from an fp32 pairwise sum: they can differ only inside the
+    from a total of grid-rounded partial sums, the reference from an fp32 pairwise sum: they can differ only inside the
     guard band, where the decision is flagged and the host entry point redoes the pair in NumPy's own order
     (oflk_plan_resolve_uncertain).  Required: EVERY input takes the oracle's iteration counts, log and flow;
     inputs further than 1e-3 from the threshold are never redone; the ladder does reach the band."""
@@ -385,7 +385,7 @@ def test_exit_decisions_next_to_the_threshold(oracle):
 
 def test_guard_band_follows_the_level_size(oracle):
     """np.mean adds ceil(n / 8192) fp32 pieces one after the other, so its worst-case error grows with
-    the level: at 3840x2160 the band is (1013 + 32) * 2^-24 = 6.2e-5 relative, wider than the 5e-5 floor small
+    the level: at 3840x2160 the band is (1013 + 32) * 2^-24 = 6.2e-5 relative plus the device's 0.08e-5, wider than the 5e-5 floor small
     levels use.  A 4K level whose first mean lies 5.6e-5 above the threshold (bisected on the device's own exact
     mean) must be flagged, and the redone pair must equal the oracle."""
     import torch

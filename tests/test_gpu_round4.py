@@ -20,7 +20,9 @@ import json
 from pathlib import Path
 
 import numpy as np
+import oflk_oracle as O
 import pytest
+from test_tolerant_model import assert_log_within_bounds, level_sum_path
 
 pytestmark = pytest.mark.gpu
 
@@ -45,10 +47,10 @@ def _run(plan, p, c, u8=False):
     return u.cpu().numpy(), v.cpu().numpy(), log, runs
 
 
-def _model(p, c, L, K):
+def _model(p, c, L, K, exact_means=False):
     import oflk_tolerant_model as M
 
-    return M.pyramidal(p.astype(np.float32), c.astype(np.float32), M.tolerant_spec(L, K, p.shape), 5)
+    return M.pyramidal(p.astype(np.float32), c.astype(np.float32), M.tolerant_spec(L, K, p.shape), 5, exact_means=exact_means)
 
 
 def _pair(rng, H, W, kind):
@@ -77,12 +79,15 @@ def test_tolerant_kernels_equal_their_cpu_model(shape, kind):
         plan = _oflk.Plan(0, 1, H, W, L, 5, K)
         plan.set_arithmetic(2)
         u, v, log, runs = _run(plan, p[None], c[None])
-        mu, mv, mlog, mruns = _model(p, c, L, K)
+        mu, mv, mlog, mruns, xlog = _model(p, c, L, K, exact_means=True)
         assert list(runs[0]) == list(mruns), (shape, kind, L, K, runs, mruns)
         bad = np.argwhere(~((u[0] == mu) & (v[0] == mv)))
         assert bad.size == 0, (shape, kind, L, K, len(bad), bad[:5])
-        for l in range(L):   # the device sums |d| in fixed point, NumPy in fp32 pairwise: an outlier among few pixels costs NumPy 1e-5
-            np.testing.assert_allclose(log[0, l, :runs[0, l]], mlog[l, :runs[0, l]], rtol=2e-5, atol=1e-12)
+        # the device's log within E_dev, the model's NumPy-order log within NumPy's bound, of the exact means of the same d
+        # (each level's pair of bounds at most 2e-5 at the threshold)
+        dims = O.pyramid_dims(H, W, L)
+        paths = [level_sum_path(2, L, K, 5, dims, l) for l in range(L)]
+        assert_log_within_bounds(log[0], mlog, xlog, mruns, dims, paths, (shape, kind, L, K), at_threshold_at_most=2e-5)
         plan.close()
 
 

@@ -13,6 +13,7 @@ import json
 
 import numpy as np
 import pytest
+from test_tolerant_model import assert_log_within_bounds, level_sum_path
 
 pytestmark = pytest.mark.gpu
 
@@ -73,12 +74,14 @@ def test_tolerant_plan_equals_its_cpu_model_in_every_cell(shape):
             u, v, log, runs = _run(plan, p[None], c[None])
         finally:
             plan.close()
-        mu, mv, mlog, mruns = M.pyramidal(p, c, M.tolerant_spec(L, K, shape), 5)
+        mu, mv, mlog, mruns, xlog = M.pyramidal(p, c, M.tolerant_spec(L, K, shape), 5, exact_means=True)
         assert list(runs[0]) == list(mruns), (shape, L, K, runs, mruns)
         bad = np.argwhere(~((u[0] == mu) & (v[0] == mv)))
         assert bad.size == 0, (shape, L, K, len(bad), bad[:5])
-        for l in range(L):   # the device sums |d| in fixed point, NumPy in fp32 pairwise: an outlier among few pixels costs NumPy 1e-5
-            np.testing.assert_allclose(log[0, l, :runs[0, l]], mlog[l, :runs[0, l]], rtol=2e-5, atol=1e-12)
+        # the device's log within E_dev, the model's NumPy-order log within NumPy's bound, of the exact means of the same d
+        dims = M.O.pyramid_dims(H, W, L)
+        paths = [level_sum_path(2, L, K, 5, dims, l) for l in range(L)]
+        assert_log_within_bounds(log[0], mlog, xlog, mruns, dims, paths, (shape, L, K), at_threshold_at_most=2e-5)
 
 
 @pytest.mark.parametrize("cell", [(4, 3), (4, 2), (2, 3), (2, 1), (1, 5)], ids=["L4K3-deep", "L4K2", "L2K3-shallow", "L2K1", "L1K5"])

@@ -2259,7 +2259,10 @@ __global__ __launch_bounds__(256) void k_warp(const float *__restrict__ img,
 // ---------------------------------------------------------------------------
 // BASELINE config 5: single-scale LK with fp16 gradients and fp16 accumulators (opt-in; NOT the
 // reference's arithmetic -- the reference is fp32 throughout, lucas_kanade_core.py:110-133 -- so this
-// mode is judged by its EPE against the exact result, tests/test_gpu_fp16.py, never by equality).
+// mode's accuracy claim is its EPE against the exact result, tests/test_gpu_fp16.py).  Its correctness
+// claim: it equals a stated CPU model, oracle/oflk_fp16_model.py, up to the v_rcp_f32 of the solve (same
+// zero set, within 2 ulp elsewhere).  A change to any rounding or to the order of any addition below must
+// change the model with it.
 //
 // What fp16 buys: two planes per instruction and, because exactness is given up anyway, SEPARABLE
 // window sums -- which lets the kernel stream: NO LDS and NO barrier.  A wave owns a strip of image

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Randomised differential run: HIP path vs the CPU oracle on random shapes, parameters and data
 (development tool, run on the GPU box; the committed test-suite holds the fixed cases).
-Usage: python3 tools/fuzz_parity.py [cases] [seed] | batch [cases] [seed] | rtl [cases] [seed] | tol [cases] [seed] | stream [cases] [seed]"""
+Usage: python3 tools/fuzz_parity.py [cases] [seed] | batch [cases] [seed] | rtl [cases] [seed] | tol [cases] [seed] | stream [cases] [seed]
+       | fp16 [cases] [seed]"""
 import os
 import sys
 from pathlib import Path
@@ -231,6 +232,53 @@ def stream_main(cases, seed):
     sys.exit(1 if bad else 0)
 
 
+def fp16_main(cases, seed):
+    """fp16 single-scale mode: a plan against its CPU statement (oracle/oflk_fp16_model.py) -- the same zero set, within
+    2 float32 ulp elsewhere -- on random shapes, windows, batch sizes, pixel_max values (frames scaled to [0, pixel_max])
+    and pointers one float past 8-byte alignment"""
+    import torch
+
+    import _oflk
+    import oflk_fp16_model as M
+
+    rng = np.random.default_rng(seed)
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream().cuda_stream
+    bad, worst = 0, 0
+    for i in range(cases):
+        H, W = int(rng.integers(1, 300)), int(rng.integers(1, 520))
+        B = int(rng.integers(1, 5))
+        win = int(rng.choice([3, 5, 7, 9, 11]))
+        pm = float(rng.choice([1.0, 255.0, 1023.0, 4095.0, 65535.0, float(rng.uniform(0.5, 3e4))]))
+        offset = int(rng.integers(0, 2))
+        a = rng.uniform(0, 1, (B, H, W))
+        if i % 3 == 0:     # smooth texture
+            yy, xx = np.mgrid[0:H, 0:W]
+            a = 0.5 + 0.45 * np.sin(xx / rng.uniform(2, 9)) * np.cos(yy / rng.uniform(2, 9)) + 0.05 * a
+        b = np.roll(a, (int(rng.integers(-2, 3)), int(rng.integers(-2, 3))), (1, 2)) + rng.normal(0, 0.01, (B, H, W))
+        p = (np.clip(a, 0, 1) * pm).astype(np.float32)
+        c = (np.clip(b, 0, 1) * pm).astype(np.float32)
+        n = B * H * W
+        bufs = [torch.zeros(n + 1, dtype=torch.float32, device=dev) for _ in range(4)]
+        tp, tc, tu, tv = (x[offset:offset + n].view(B, H, W) for x in bufs)
+        tp.copy_(torch.from_numpy(p))
+        tc.copy_(torch.from_numpy(c))
+        plan = _oflk.Plan(0, B, H, W, 1, win, 0)
+        plan.single_scale_fp16(tp.data_ptr(), tc.data_ptr(), tu.data_ptr(), tv.data_ptr(), pm, st)
+        torch.cuda.synchronize()
+        plan.close()
+        mu, mv = M.fp16_flow(p, c, win, pm)
+        zeros, d = M.compare(tu.cpu().numpy(), tv.cpu().numpy(), mu, mv)
+        worst = max(worst, d)
+        if not zeros or d > 2:
+            bad += 1
+            print(f"MISMATCH fp16 case {i}: B={B} H={H} W={W} win={win} pixel_max={pm} offset={offset} zeros={zeros} ulp={d}", flush=True)
+        if i % 50 == 49:
+            print(f"{i + 1} fp16 cases, {bad} mismatches, worst {worst} ulp", flush=True)
+    print(f"done: {cases} fp16 cases, {bad} mismatches, worst {worst} ulp")
+    sys.exit(1 if bad else 0)
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "stream":
         return stream_main(int(sys.argv[2]) if len(sys.argv) > 2 else 200, int(sys.argv[3]) if len(sys.argv) > 3 else 1)
@@ -238,6 +286,8 @@ def main():
         return tol_main(int(sys.argv[2]) if len(sys.argv) > 2 else 200, int(sys.argv[3]) if len(sys.argv) > 3 else 1)
     if len(sys.argv) > 1 and sys.argv[1] == "rtl":
         return rtl_main(int(sys.argv[2]) if len(sys.argv) > 2 else 200, int(sys.argv[3]) if len(sys.argv) > 3 else 1)
+    if len(sys.argv) > 1 and sys.argv[1] == "fp16":
+        return fp16_main(int(sys.argv[2]) if len(sys.argv) > 2 else 300, int(sys.argv[3]) if len(sys.argv) > 3 else 1)
     if len(sys.argv) > 1 and sys.argv[1] == "batch":
         return batch_main(int(sys.argv[2]) if len(sys.argv) > 2 else 30, int(sys.argv[3]) if len(sys.argv) > 3 else 1)
     cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200

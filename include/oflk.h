@@ -165,6 +165,22 @@ int oflk_pyramidal_batch_multi(const float *prev, const float *curr, int B, int 
 int oflk_pyramidal_u8_multi(const unsigned char *prev, const unsigned char *curr, int B, int H, int W,
                             int levels, int window_size, int iters, int n_gpus, float *u, float *v,
                             float *residual_log, int *iters_run);
+/* ---- frame sequences (video) ---------------------------------------------------- */
+/* T frames [T][H][W] in, the T-1 flows (t -> t+1) out: u, v are [T-1][H][W], residual_log [T-1][levels][iters][2] and
+ * iters_run [T-1][levels] (both may be NULL) -- exactly what oflk_pyramidal_batch returns for the T-1 pairs
+ * (frames[t], frames[t+1]), value for value, iteration counts and oflk_last_resolved() included.  Each frame is uploaded
+ * once (a large call goes in chunks of C pairs, whose C+1 frames share the boundary frame with the next chunk) and its
+ * Gaussian pyramid is built once, not once as curr and again as prev.  T < 2 is OFLK_ERR_INVALID.  The _multi form is
+ * the chunk queue of oflk_pyramidal_batch_multi over the T-1 pairs (a chunk of pairs [b0, b1) reads frames [b0, b1]).
+ * oflk_single_scale_sequence has no pyramid to share: it halves the upload, and keeps the two APIs alike. */
+int oflk_pyramidal_sequence(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
+                            float *u, float *v, float *residual_log, int *iters_run);
+int oflk_pyramidal_sequence_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size, int iters,
+                               float *u, float *v, float *residual_log, int *iters_run);
+int oflk_pyramidal_sequence_multi(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                  int n_gpus, float *u, float *v, float *residual_log, int *iters_run);
+int oflk_single_scale_sequence(const float *frames, int T, int H, int W, int window_size, float *u, float *v);
+
 /* Rehearsal of the chunk queue above on a box with fewer GPUs than workers (tests): `workers` > 0 makes the *_multi entry
  * points run that many queue workers, worker i on device i % n_gpus (workers of one device take turns on it); 0 restores
  * one worker per device.  Results do not change. */
@@ -209,6 +225,14 @@ int oflk_plan_single_scale_u8(oflk_plan *plan, const unsigned char *d_prev, cons
                               float *d_u, float *d_v, void *stream);
 int oflk_plan_pyramidal_u8(oflk_plan *plan, const unsigned char *d_prev, const unsigned char *d_curr,
                            float *d_u, float *d_v, void *stream);
+/* The pyramidal pass over a frame sequence: a plan created with B pairs, d_frames = [B+1][H][W], d_u, d_v = [B][H][W]; flow b
+ * is frames b -> b+1.  It is the pair pass with d_prev = d_frames and d_curr = d_frames + H*W (uint8: H*W bytes) -- same
+ * values, log, iteration counts, uncertain flags and level flows as oflk_plan_pyramidal on copies of those two arrays --
+ * except that the pyramid is built for the B+1 frames once instead of for 2B images.  Any plan serves both forms; the
+ * workspace does not grow.  The reads below mean what they mean after a pair pass, and the resolve calls take the aliased
+ * pointers: oflk_plan_resolve_uncertain{,_u8}(plan, d_frames, d_frames + H*W, d_u, d_v, ...). */
+int oflk_plan_pyramidal_sequence(oflk_plan *plan, const float *d_frames, float *d_u, float *d_v, void *stream);
+int oflk_plan_pyramidal_sequence_u8(oflk_plan *plan, const unsigned char *d_frames, float *d_u, float *d_v, void *stream);
 
 /* After oflk_plan_pyramidal: copy the residual log / iteration counts of the last
  * enqueued pass to the host (synchronises `stream`).  Either pointer may be NULL. */
@@ -231,7 +255,8 @@ int oflk_plan_read_uncertain(oflk_plan *plan, int *uncertain, void *stream);
  * The pair's slices of d_u / d_v, its log, iteration counts and flags are replaced, so afterwards the
  * whole batch is the reference's result with the reference's iteration counts.  Slow (a host round trip
  * per iteration) and rare (never seen outside constructed inputs).  d_prev / d_curr are the frames the
- * pass was given; *resolved (may be NULL) receives the number of pairs redone.  Synchronises.
+ * pass was given (after a sequence pass: d_frames and d_frames + H*W); *resolved (may be NULL) receives the number of
+ * pairs redone.  Synchronises.
  * The host entry points (oflk_pyramidal*, oflk_pyramidal_u8*) do this themselves after every call;
  * oflk_last_resolved() tells how many pairs the calling thread's last such call redid. */
 int oflk_plan_resolve_uncertain(oflk_plan *plan, const float *d_prev, const float *d_curr, float *d_u, float *d_v,

@@ -187,7 +187,7 @@ struct oflk_plan {
     int dims[2 * OFLK_MAX_LEVELS] = {0};
     size_t ws_bytes = 0;
     // workspace
-    float *pyr[OFLK_MAX_LEVELS] = {nullptr};      // l < L-1: [2B][h][w] (prev then curr)
+    float *pyr[OFLK_MAX_LEVELS] = {nullptr};      // l < L-1: [2B][h][w] (prev then curr); a sequence uses [B+1][h][w]
     float *tmpA = nullptr, *tmpB = nullptr;       // blur temporaries [2B][H][W]
     // per level one block: [slot 0..1][B][h][w] of interleaved float2 {u, v} (see LkArgs)
     float *flow[OFLK_MAX_LEVELS] = {nullptr};
@@ -195,7 +195,8 @@ struct oflk_plan {
     //   acc[B][L][K][kAccShards][kAccStride] (u64) | iters_run[B][L] (i32) | uncertain[B][L] (i32) | log[B][L][K][2] (f32)
     unsigned long long *state = nullptr;
     // uint8 plans only, and only when the fused pyramid kernel cannot take the frames (it always can for
-    // scale 0.5 unless a level is tiny): float32 copies of the caller's frames, allocated on first need
+    // scale 0.5 unless a level is tiny): float32 copies of the caller's frames, allocated on first need --
+    // [B+1][H][W] (prev, or a sequence's B+1 frames) and [B][H][W] (curr)
     float *u8_stage[2] = {nullptr, nullptr};
     // scratch of oflk_plan_resolve_uncertain (one pair, unfused, planar), allocated on first use
     struct Exact {
@@ -823,7 +824,9 @@ int plan_single_scale(oflk_plan *p, const void *d_prev, const void *d_curr, bool
     }
     return launch_lk<MODE_SINGLE>(p, s, KC_LK_SINGLE, p->hw, a, p->B, u8);
 }
-int plan_pyramidal(oflk_plan *p, const void *d_prev, const void *d_curr, bool u8, float *d_u, float *d_v, hipStream_t s);
+// seq: d_curr == d_prev + one plane, both inside one buffer of B+1 frames (oflk_plan_pyramidal_sequence)
+int plan_pyramidal(oflk_plan *p, const void *d_prev, const void *d_curr, bool u8, float *d_u, float *d_v, hipStream_t s,
+                   bool seq = false);
 int resolve_pair(oflk_plan *p, int b, const void *d_prev_in, const void *d_curr_in, bool u8, float *d_u, float *d_v, hipStream_t s);
 }  // namespace
 
@@ -906,26 +909,45 @@ OFLK_API int oflk_plan_pyramidal_u8(oflk_plan *p, const unsigned char *d_prev, c
     return plan_pyramidal(p, d_prev, d_curr, true, d_u, d_v, (hipStream_t)stream);
 }
 
+// A sequence is the pair batch whose pair b reads frames b and b+1 of one buffer: curr = frames + one plane (for uint8 one
+// plane of BYTES).  Every kernel addresses pair b as prev + b * plane and curr + b * plane, so only the pyramid changes.
+OFLK_API int oflk_plan_pyramidal_sequence(oflk_plan *p, const float *d_frames, float *d_u, float *d_v, void *stream)
+{
+    if (!p || !d_frames) return fail(OFLK_ERR_INVALID, "NULL argument");
+    return plan_pyramidal(p, d_frames, d_frames + (size_t)p->H * p->W, false, d_u, d_v, (hipStream_t)stream, true);
+}
+
+OFLK_API int oflk_plan_pyramidal_sequence_u8(oflk_plan *p, const unsigned char *d_frames, float *d_u, float *d_v, void *stream)
+{
+    if (!p || !d_frames) return fail(OFLK_ERR_INVALID, "NULL argument");
+    return plan_pyramidal(p, d_frames, d_frames + (size_t)p->H * p->W, true, d_u, d_v, (hipStream_t)stream, true);
+}
+
 namespace {
 int plan_pyramidal(oflk_plan *p, const void *d_prev_in, const void *d_curr_in, bool u8, float *d_u, float *d_v,
-                   hipStream_t s)
+                   hipStream_t s, bool seq)
 {
     if (!p || !d_prev_in || !d_curr_in || !d_u || !d_v) return fail(OFLK_ERR_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(p->device));
     const int B = p->B, L = p->L, K = p->K;
+    // images the pyramid is built for: prev and curr of every pair, or every frame of a sequence once
+    const int nimg = seq ? B + 1 : 2 * B;
     int rc;
     if (u8 && L > 1 &&
         !pyr_fused_fits(p->dims[2 * (L - 1)], p->dims[2 * (L - 1) + 1], p->dims[2 * (L - 2)], p->dims[2 * (L - 2) + 1], p->gauss)) {
         // the unfused pyramid kernels read float32: convert once and run the float path
-        const size_t n = (size_t)B * p->H * p->W;
+        const size_t N = (size_t)p->H * p->W, n = (size_t)B * N;
         size_t tot = 0;
-        for (auto &q : p->u8_stage)
-            if (!q && (rc = dmalloc(&q, n, &tot))) return rc;
+        for (int i = 0; i < 2; i++)
+            if (!p->u8_stage[i] && (rc = dmalloc(&p->u8_stage[i], i == 0 ? n + N : n, &tot))) return rc;
         p->ws_bytes += tot;
-        dim3 grid((unsigned)((n + 4095) / 4096));
-        hipLaunchKernelGGL(k_u8_to_f32, grid, dim3(256), 0, s, static_cast<const unsigned char *>(d_prev_in), p->u8_stage[0], n);
+        const size_t n0 = seq ? n + N : n;   // a sequence's B+1 frames all go to the first stage
+        hipLaunchKernelGGL(k_u8_to_f32, dim3((unsigned)((n0 + 4095) / 4096)), dim3(256), 0, s, static_cast<const unsigned char *>(d_prev_in),
+                           p->u8_stage[0], n0);
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_u8_to_f32, grid, dim3(256), 0, s, static_cast<const unsigned char *>(d_curr_in), p->u8_stage[1], n);
+        if (seq) return plan_pyramidal(p, p->u8_stage[0], p->u8_stage[0] + N, false, d_u, d_v, s, true);
+        hipLaunchKernelGGL(k_u8_to_f32, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, s, static_cast<const unsigned char *>(d_curr_in),
+                           p->u8_stage[1], n);
         HIP_TRY(hipGetLastError());
         return plan_pyramidal(p, p->u8_stage[0], p->u8_stage[1], false, d_u, d_v, s);
     }
@@ -967,14 +989,15 @@ int plan_pyramidal(oflk_plan *p, const void *d_prev_in, const void *d_curr_in, b
         int ho = p->dims[2 * l], wo = p->dims[2 * l + 1];
         if (l == L - 2) {
             // the finest level is the caller's frames (image.copy() at :40 is a no-op here):
-            // prev and curr in one launch, images 0..B-1 from d_prev, B..2B-1 from d_curr
-            first.in2 = d_curr;
-            first.nsplit = B;
+            // prev and curr in one launch, images 0..B-1 from d_prev, B..2B-1 from d_curr;
+            // a sequence's B+1 frames are one buffer (in2 unused)
+            first.in2 = seq ? nullptr : d_curr;
+            first.nsplit = seq ? 0 : B;
             first.u8 = u8;
-            rc = launch_pyr_down(p, p->gauss, s, d_prev, p->pyr[l], p->tmpA, p->tmpB, 2 * B, h, w, ho, wo, &first);
+            rc = launch_pyr_down(p, p->gauss, s, d_prev, p->pyr[l], p->tmpA, p->tmpB, nimg, h, w, ho, wo, &first);
             if (rc) return rc;
         } else {
-            rc = launch_pyr_down(p, p->gauss, s, p->pyr[l + 1], p->pyr[l], p->tmpA, p->tmpB, 2 * B, h, w, ho, wo);
+            rc = launch_pyr_down(p, p->gauss, s, p->pyr[l + 1], p->pyr[l], p->tmpA, p->tmpB, nimg, h, w, ho, wo);
             if (rc) return rc;
         }
     }
@@ -1011,7 +1034,8 @@ int plan_pyramidal(oflk_plan *p, const void *d_prev_in, const void *d_curr_in, b
             if (rc) return rc;
         }
         const float *lp = (l == L - 1) ? d_prev : p->pyr[l];
-        const float *lc = (l == L - 1) ? d_curr : p->pyr[l] + (size_t)B * n;
+        // pair b's curr image: pyramid image B + b, or a sequence's frame b + 1
+        const float *lc = (l == L - 1) ? d_curr : p->pyr[l] + (size_t)(seq ? 1 : B) * n;
         for (int k = 0; k < K; k++) {
             LkArgs a{};
             a.prev = lp; a.curr = lc;
@@ -1583,9 +1607,11 @@ int check_hw(const void *a, const void *b, int H, int W)
 // thread until it is done, which is why the two directions have a thread each.  Frame pairs are independent, so
 // the results do not depend on the cut (tests/test_gpu_round3.py).  A synchronous float32 call moves 33 MB per
 // 1080p pair over the link, half of it each way: overlapped, the floor is one direction's time.
+// seq: a frame sequence (curr == prev + one plane); a chunk of C pairs takes its C+1 frames into one slot buffer, so the
+// frame on the boundary of two chunks is uploaded by both.
 template <class PIXELS>
 int run_batch_chunked(HostCtx *c, int dev, const PIXELS *prev, const PIXELS *curr, int B, int C, int H, int W, int levels,
-                      int window_size, int iters, float *u, float *v, float *residual_log, int *iters_run)
+                      int window_size, int iters, float *u, float *v, float *residual_log, int *iters_run, bool seq = false)
 {
     constexpr bool U8 = sizeof(PIXELS) == 1;
     const bool single = levels == 0;
@@ -1594,7 +1620,7 @@ int run_batch_chunked(HostCtx *c, int dev, const PIXELS *prev, const PIXELS *cur
     const size_t plane = (size_t)H * W;
     const int nchunk = (B + C - 1) / C;
     int rc;
-    if ((rc = host_ring(*c, (size_t)C * plane * sizeof(PIXELS), (size_t)C * plane))) return rc;
+    if ((rc = host_ring(*c, (size_t)(seq ? C + 1 : C) * plane * sizeof(PIXELS), (size_t)C * plane))) return rc;
     oflk_plan *pc = nullptr, *pt = nullptr;
     if ((rc = host_plan(*c, dev, C, H, W, Lp, window_size, Kp, &pc))) return rc;
     const int tail = B - (nchunk - 1) * C;
@@ -1673,8 +1699,12 @@ int run_batch_chunked(HostCtx *c, int dev, const PIXELS *prev, const PIXELS *cur
     auto h2d = [&](int k) -> int {
         const int slot = k & 1, nb = k == nchunk - 1 ? tail : C;
         const size_t off = (size_t)k * C * plane, bytes = (size_t)nb * plane * sizeof(PIXELS);
-        HIP_TRY(hipMemcpyAsync(c->ring_in[slot][0], prev + off, bytes, hipMemcpyHostToDevice, c->s_in));
-        HIP_TRY(hipMemcpyAsync(c->ring_in[slot][1], curr + off, bytes, hipMemcpyHostToDevice, c->s_in));
+        if (seq) {
+            HIP_TRY(hipMemcpyAsync(c->ring_in[slot][0], prev + off, bytes + plane * sizeof(PIXELS), hipMemcpyHostToDevice, c->s_in));
+        } else {
+            HIP_TRY(hipMemcpyAsync(c->ring_in[slot][0], prev + off, bytes, hipMemcpyHostToDevice, c->s_in));
+            HIP_TRY(hipMemcpyAsync(c->ring_in[slot][1], curr + off, bytes, hipMemcpyHostToDevice, c->s_in));
+        }
         HIP_TRY(hipEventRecord(ev_in[slot], c->s_in));
         return OFLK_OK;
     };
@@ -1689,9 +1719,10 @@ int run_batch_chunked(HostCtx *c, int dev, const PIXELS *prev, const PIXELS *cur
             if (out_rc != OFLK_OK) { g.unlock(); return finish(OFLK_OK); }
         }
         if ((rc = hipStreamWaitEvent(c->s_comp, ev_in[slot], 0)) != hipSuccess) return finish(fail(OFLK_ERR_HIP, "hipStreamWaitEvent"));
-        const void *dp = c->ring_in[slot][0], *dc = c->ring_in[slot][1];
+        const void *dp = c->ring_in[slot][0];
+        const void *dc = seq ? static_cast<const void *>(static_cast<const PIXELS *>(dp) + plane) : c->ring_in[slot][1];
         float *du = c->ring_out[slot][0], *dv = c->ring_out[slot][1];
-        rc = single ? plan_single_scale(p, dp, dc, U8, du, dv, c->s_comp) : plan_pyramidal(p, dp, dc, U8, du, dv, c->s_comp);
+        rc = single ? plan_single_scale(p, dp, dc, U8, du, dv, c->s_comp) : plan_pyramidal(p, dp, dc, U8, du, dv, c->s_comp, seq);
         if (rc) return finish(rc);
         // the next chunk's frames travel while this one is computed (the kernels that read its slot, chunk k-1's, are done:
         // the previous turn of this loop ended by waiting for them)
@@ -1724,10 +1755,11 @@ int run_batch_chunked(HostCtx *c, int dev, const PIXELS *prev, const PIXELS *cur
 
 // One batch on one device, host pointers in and out.  PIXELS: float or unsigned char frames (the
 // uint8 kernels read the frames as they are: no float32 copy of them exists on the device).
-// levels == 0 selects single-scale.
+// levels == 0 selects single-scale.  seq: prev holds a sequence of B+1 frames and curr == prev + one plane (each frame is
+// uploaded once, and a pyramidal pass builds each frame's pyramid once).
 template <class PIXELS>
 int run_batch_on(int dev, const PIXELS *prev, const PIXELS *curr, int B, int H, int W, int levels, int window_size,
-                 int iters, float *u, float *v, float *residual_log, int *iters_run)
+                 int iters, float *u, float *v, float *residual_log, int *iters_run, bool seq = false)
 {
     constexpr bool U8 = sizeof(PIXELS) == 1;
     t_resolved = 0;   // of THIS call (oflk_last_resolved)
@@ -1744,27 +1776,29 @@ int run_batch_on(int dev, const PIXELS *prev, const PIXELS *curr, int B, int H, 
         const size_t pair_out = (size_t)H * W * sizeof(float);
         const int C = (int)std::max<size_t>(1, ((size_t)32 << 20) / std::max<size_t>(pair_out, 1));
         if (B >= 4 * C && (size_t)B * pair_out >= ((size_t)64 << 20))
-            return run_batch_chunked<PIXELS>(c, dev, prev, curr, B, C, H, W, levels, window_size, iters, u, v, residual_log, iters_run);
+            return run_batch_chunked<PIXELS>(c, dev, prev, curr, B, C, H, W, levels, window_size, iters, u, v, residual_log, iters_run,
+                                             seq);
     }
     oflk_plan *p = nullptr;
     if ((rc = host_plan(*c, dev, B, H, W, single ? 1 : levels, window_size, single ? 0 : iters, &p))) return rc;
-    const size_t n = (size_t)B * H * W, obytes = n * sizeof(float);
-    if ((rc = host_io(*c, n))) return rc;
+    const size_t plane = (size_t)H * W, n = (size_t)B * plane, obytes = n * sizeof(float);
+    const size_t nin = seq ? n + plane : n;   // frames in the first device buffer (a sequence: all B+1)
+    if ((rc = host_io(*c, nin))) return rc;
     const void *dp, *dc;
     if (U8) {
-        if ((rc = host_u8(*c, n))) return rc;
-        HIP_TRY(hipMemcpyAsync(c->u8[0], prev, n, hipMemcpyHostToDevice, nullptr));
-        HIP_TRY(hipMemcpyAsync(c->u8[1], curr, n, hipMemcpyHostToDevice, nullptr));
+        if ((rc = host_u8(*c, nin))) return rc;
+        HIP_TRY(hipMemcpyAsync(c->u8[0], prev, nin, hipMemcpyHostToDevice, nullptr));
+        if (!seq) HIP_TRY(hipMemcpyAsync(c->u8[1], curr, n, hipMemcpyHostToDevice, nullptr));
         dp = c->u8[0];
-        dc = c->u8[1];
+        dc = seq ? c->u8[0] + plane : c->u8[1];
     } else {
-        HIP_TRY(hipMemcpyAsync(c->io[0], prev, obytes, hipMemcpyHostToDevice, nullptr));
-        HIP_TRY(hipMemcpyAsync(c->io[1], curr, obytes, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(c->io[0], prev, nin * sizeof(float), hipMemcpyHostToDevice, nullptr));
+        if (!seq) HIP_TRY(hipMemcpyAsync(c->io[1], curr, obytes, hipMemcpyHostToDevice, nullptr));
         dp = c->io[0];
-        dc = c->io[1];
+        dc = seq ? c->io[0] + plane : c->io[1];
     }
     rc = single ? plan_single_scale(p, dp, dc, U8, c->io[2], c->io[3], nullptr)
-                : plan_pyramidal(p, dp, dc, U8, c->io[2], c->io[3], nullptr);
+                : plan_pyramidal(p, dp, dc, U8, c->io[2], c->io[3], nullptr, seq);
     if (rc) return rc;
     // exit decisions the device could not take with certainty are redone in NumPy's own summation order
     if (!single && iters > 0) {
@@ -1795,9 +1829,10 @@ void shard_range(int total, int i, int n, int *begin, int *end)
 // devices do not get fixed shards: the batch is cut into chunks of consecutive pairs and every device's host thread pulls
 // the next chunk from a shared counter until none is left -- a device whose pairs converge early simply takes more chunks.
 // No data crosses between devices, and a pair's result does not depend on which device computed it or in which chunk.
+// seq: a sequence (curr == prev + one plane); the chunk of pairs [b0, b1) reads frames [b0, b1].
 template <class PIXELS>
 int run_batch_multi(const PIXELS *prev, const PIXELS *curr, int B, int H, int W, int levels, int window_size, int iters,
-                    int n_gpus, float *u, float *v, float *residual_log, int *iters_run)
+                    int n_gpus, float *u, float *v, float *residual_log, int *iters_run, bool seq = false)
 {
     int rc = check_hw(prev, curr, H, W);
     if (rc) return rc;
@@ -1812,7 +1847,7 @@ int run_batch_multi(const PIXELS *prev, const PIXELS *curr, int B, int H, int W,
     workers_n = std::min(workers_n, B);   // never more workers than pairs
     if (workers_n == 1)
         return run_batch_on<PIXELS>(g_device.load(), prev, curr, B, H, W, levels, window_size, iters, u, v, residual_log,
-                                    iters_run);
+                                    iters_run, seq);
     const size_t plane = (size_t)H * W;
     const int Lc = std::max(levels, 1), Kc = std::max(iters, 1);
     // chunks: about four per worker, so that the last ones even out what the data made uneven; at least one pair
@@ -1833,7 +1868,7 @@ int run_batch_multi(const PIXELS *prev, const PIXELS *curr, int B, int H, int W,
                 const int c = run_batch_on<PIXELS>(dev, prev + off, curr + off, b1 - b0, H, W, levels, window_size, iters,
                                                    u + off, v + off,
                                                    residual_log ? residual_log + (size_t)b0 * Lc * Kc * 2 : nullptr,
-                                                   iters_run ? iters_run + (size_t)b0 * Lc : nullptr);
+                                                   iters_run ? iters_run + (size_t)b0 * Lc : nullptr, seq);
                 redone[(size_t)g] += t_resolved;                  // the worker's count of pairs redone
                 if (c) {
                     codes[(size_t)g] = c;
@@ -2002,6 +2037,54 @@ OFLK_API int oflk_pyramidal_u8_multi(const unsigned char *prev, const unsigned c
     if (levels < 1) return fail(OFLK_ERR_INVALID, "levels must be in [1,%d] (got %d)", OFLK_MAX_LEVELS, levels);
     return run_batch_multi<unsigned char>(prev, curr, B, H, W, levels, window_size, iters, n_gpus, u, v, residual_log,
                                           iters_run);
+}
+
+// ---- frame sequences: T frames in, the T-1 flows (t -> t+1) out, each frame uploaded once and its pyramid built once -------
+namespace {
+// n_gpus == 0: the single-device path (oflk_set_device's device); levels == 0: single-scale
+template <class PIXELS>
+int run_sequence(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, int n_gpus, bool multi,
+                 float *u, float *v, float *residual_log, int *iters_run)
+{
+    int rc = check_hw(frames, frames, H, W);
+    if (rc) return rc;
+    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
+    const PIXELS *next = frames + (size_t)H * W;   // pair b is (frames[b], next[b])
+    if (multi) return run_batch_multi<PIXELS>(frames, next, T - 1, H, W, levels, window_size, iters, n_gpus, u, v, residual_log,
+                                              iters_run, true);
+    return run_batch_on<PIXELS>(g_device.load(), frames, next, T - 1, H, W, levels, window_size, iters, u, v, residual_log,
+                                iters_run, true);
+}
+}  // namespace
+
+OFLK_API int oflk_pyramidal_sequence(const float *frames, int T, int H, int W, int levels, int window_size, int iters, float *u,
+                                     float *v, float *residual_log, int *iters_run)
+{
+    t_resolved = 0;
+    if (levels < 1) return fail(OFLK_ERR_INVALID, "levels must be in [1,%d] (got %d)", OFLK_MAX_LEVELS, levels);
+    return run_sequence<float>(frames, T, H, W, levels, window_size, iters, 0, false, u, v, residual_log, iters_run);
+}
+
+OFLK_API int oflk_pyramidal_sequence_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                        float *u, float *v, float *residual_log, int *iters_run)
+{
+    t_resolved = 0;
+    if (levels < 1) return fail(OFLK_ERR_INVALID, "levels must be in [1,%d] (got %d)", OFLK_MAX_LEVELS, levels);
+    return run_sequence<unsigned char>(frames, T, H, W, levels, window_size, iters, 0, false, u, v, residual_log, iters_run);
+}
+
+OFLK_API int oflk_pyramidal_sequence_multi(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                           int n_gpus, float *u, float *v, float *residual_log, int *iters_run)
+{
+    t_resolved = 0;
+    if (levels < 1) return fail(OFLK_ERR_INVALID, "levels must be in [1,%d] (got %d)", OFLK_MAX_LEVELS, levels);
+    return run_sequence<float>(frames, T, H, W, levels, window_size, iters, n_gpus, true, u, v, residual_log, iters_run);
+}
+
+OFLK_API int oflk_single_scale_sequence(const float *frames, int T, int H, int W, int window_size, float *u, float *v)
+{
+    t_resolved = 0;
+    return run_sequence<float>(frames, T, H, W, 0, window_size, 0, 0, false, u, v, nullptr, nullptr);
 }
 
 namespace {

@@ -59,6 +59,12 @@ SIGNATURES = {
     "oflk_single_scale_batch_multi": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f32p, _f32p]),
     "oflk_pyramidal_batch_multi": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f32p, _f32p, _f32p, _i32p]),
     "oflk_pyramidal_u8_multi": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f32p, _f32p, _f32p, _i32p]),
+    "oflk_pyramidal_sequence": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [_f32p, _f32p, _f32p, _i32p]),
+    "oflk_pyramidal_sequence_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [_f32p, _f32p, _f32p, _i32p]),
+    "oflk_pyramidal_sequence_multi": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 7 + [_f32p, _f32p, _f32p, _i32p]),
+    "oflk_single_scale_sequence": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 4 + [_f32p, _f32p]),
+    "oflk_plan_pyramidal_sequence": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "oflk_plan_pyramidal_sequence_u8": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "oflk_shard_range": (None, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, _i32p]),
     "oflk_single_scale_fp16": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, _f32p, _f32p]),
     "oflk_rtl_stream_length": (ctypes.c_long, [ctypes.c_int, ctypes.c_int]),
@@ -154,6 +160,32 @@ def ptr(a: np.ndarray):
     return a.ctypes.data_as(_f32p)
 
 
+def as_sequence(frames) -> Tuple[np.ndarray, bool]:
+    """Frames of a sequence -- a (T, H, W) array or a sequence of 2-D arrays -- as one contiguous (T, H, W) array: uint8
+    when every frame is uint8 (True is returned), float32 otherwise.  ValueError for T < 2, frames that are not 2-D, mixed
+    shapes or mixed dtypes; nothing here touches a device."""
+    if isinstance(frames, np.ndarray):
+        if frames.ndim != 3:
+            raise ValueError(f"expected a (T, H, W) array of frames, got shape {frames.shape}")
+        items = list(frames)
+    else:
+        items = [np.asarray(f) for f in frames]
+        for f in items:
+            if f.ndim != 2:
+                raise ValueError(f"every frame must be a 2-D array, got shape {f.shape}")
+        if items and len({f.shape for f in items}) > 1:
+            raise ValueError(f"frames of mixed shapes: {sorted({f.shape for f in items})}")
+        if items and len({f.dtype for f in items}) > 1:
+            raise ValueError(f"frames of mixed dtypes: {sorted(str(d) for d in {f.dtype for f in items})}")
+    if len(items) < 2:
+        raise ValueError(f"a sequence needs at least 2 frames, got {len(items)}")
+    u8 = items[0].dtype == np.uint8
+    arr = np.ascontiguousarray(frames if isinstance(frames, np.ndarray) else np.stack(items), dtype=np.uint8 if u8 else np.float32)
+    if arr.shape[1] < 1 or arr.shape[2] < 1:
+        raise ValueError(f"empty frames: shape {arr.shape}")
+    return arr, u8
+
+
 def same_shape(*arrs: np.ndarray) -> Tuple[int, int]:
     s = arrs[0].shape
     for a in arrs[1:]:
@@ -192,6 +224,12 @@ class Plan:
 
     def pyramidal(self, d_prev: int, d_curr: int, d_u: int, d_v: int, stream: int = 0) -> None:
         check(lib().oflk_plan_pyramidal(self._h, d_prev, d_curr, d_u, d_v, stream))
+
+    def pyramidal_sequence(self, d_frames: int, d_u: int, d_v: int, stream: int = 0, u8: bool = False) -> None:
+        """d_frames: device frames [B+1][H][W] (float32, or uint8 with u8=True); flow b (frames b -> b+1) into d_u, d_v
+        [B][H][W].  Resolve flagged pairs with resolve_uncertain(d_frames, d_frames + H*W * itemsize, ...)."""
+        fn = lib().oflk_plan_pyramidal_sequence_u8 if u8 else lib().oflk_plan_pyramidal_sequence
+        check(fn(self._h, d_frames, d_u, d_v, stream))
 
     def single_scale_fp16(self, d_prev: int, d_curr: int, d_u: int, d_v: int, pixel_max: float = 255.0, stream: int = 0) -> None:
         """BASELINE config 5: fp16 gradients / accumulators (opt-in, approximate)."""

@@ -64,6 +64,18 @@ def lucas_kanade_single_scale(
     return u, v
 
 
+def lucas_kanade_single_scale_sequence(frames, window_size: int = 5):
+    """(u, v), each (T-1, H, W) float32: single-scale flow of every consecutive pair of a (T, H, W) float frame sequence
+    (uint8 frames are converted to float32 first, which gives the same values).  Each frame is uploaded once."""
+    arr, _ = _oflk.as_sequence(frames)
+    arr = np.ascontiguousarray(arr, np.float32)
+    T, H, W = arr.shape
+    u = np.empty((T - 1, H, W), np.float32)
+    v = np.empty((T - 1, H, W), np.float32)
+    _oflk.check(_oflk.lib().oflk_single_scale_sequence(_oflk.ptr(arr), T, H, W, int(window_size), _oflk.ptr(u), _oflk.ptr(v)))
+    return u, v
+
+
 def lucas_kanade_single_scale_fp16(frame_prev, frame_curr, window_size: int = 5, pixel_max: float = 255.0):
     """Opt-in reduced-precision single-scale flow: fp16 gradients and fp16 window accumulators
     (BASELINE.json config 5; oflk_single_scale_fp16).  No counterpart in the reference, whose

@@ -188,6 +188,37 @@ def lucas_kanade_pyramidal(
     return u, v
 
 
+def lucas_kanade_pyramidal_sequence_with_log(frames, num_levels: int = 3, window_size: int = 5, num_iterations: int = 3):
+    """Flows (t -> t+1) of a frame sequence, silently; returns (u, v, residual_log, iters_run).
+
+    frames: a (T, H, W) array or a sequence of T 2-D arrays, T >= 2 (all uint8: the uint8 path, as for a pair).
+    u, v are (T-1, H, W) float32; residual_log is (T-1, levels, iters, 2) and iters_run (T-1, levels), each pair's entries
+    as lucas_kanade_pyramidal_with_log gives them.  Every flow equals that of the pair (frames[t], frames[t+1]); the
+    library uploads each frame once and builds its pyramid once.  The reference has no sequence function: nothing is printed.
+    """
+    arr, u8 = _oflk.as_sequence(frames)
+    T, H, W = arr.shape
+    log = np.zeros((T - 1, max(num_levels, 1), max(num_iterations, 1), 2), np.float32)
+    runs = np.zeros((T - 1, max(num_levels, 1)), np.int32)
+    u = np.empty((T - 1, H, W), np.float32)
+    v = np.empty((T - 1, H, W), np.float32)
+    if u8:
+        _oflk.check(_oflk.lib().oflk_pyramidal_sequence_u8(arr.ctypes.data, T, H, W, int(num_levels), int(window_size),
+                                                           int(num_iterations), _oflk.ptr(u), _oflk.ptr(v), _oflk.ptr(log),
+                                                           runs.ctypes.data_as(_i32p)))
+    else:
+        _oflk.check(_oflk.lib().oflk_pyramidal_sequence(_oflk.ptr(arr), T, H, W, int(num_levels), int(window_size),
+                                                        int(num_iterations), _oflk.ptr(u), _oflk.ptr(v), _oflk.ptr(log),
+                                                        runs.ctypes.data_as(_i32p)))
+    return u, v, log, runs
+
+
+def lucas_kanade_pyramidal_sequence(frames, num_levels: int = 3, window_size: int = 5, num_iterations: int = 3):
+    """(u, v), each (T-1, H, W) float32: the pyramidal flow of every consecutive pair of a (T, H, W) frame sequence."""
+    u, v, _, _ = lucas_kanade_pyramidal_sequence_with_log(frames, num_levels, window_size, num_iterations)
+    return u, v
+
+
 def _dump_levels(key, shapes, u, v) -> None:
     """The reference's per-level PNG side effect (:226), after the call, best-effort."""
     num_levels = key[3]

@@ -31,6 +31,15 @@ def shard_range(total: int, rank: int, world: int) -> Tuple[int, int]:
     return begin, begin + base + (1 if rank < extra else 0)
 
 
+def sequence_shard(T: int, rank: int, world: int) -> Tuple[int, int]:
+    """[pair_begin, pair_end) of the T-1 flows (t -> t+1) of a T-frame sequence owned by `rank` (shard_range over the
+    pairs).  The rank reads frames [pair_begin, pair_end] -- one more than its pairs -- so neighbouring ranks with pairs
+    share one frame.  A rank may own no pair when world > T-1."""
+    if int(T) < 2:
+        raise ValueError(f"a sequence needs T >= 2 frames, got {T}")
+    return shard_range(int(T) - 1, rank, world)
+
+
 class Group:
     """Thin wrapper so single-process runs need no process group."""
 

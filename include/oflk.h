@@ -181,6 +181,27 @@ int oflk_pyramidal_sequence_multi(const float *frames, int T, int H, int W, int 
                                   int n_gpus, float *u, float *v, float *residual_log, int *iters_run);
 int oflk_single_scale_sequence(const float *frames, int T, int H, int W, int window_size, float *u, float *v);
 
+/* ---- forward-backward flow of frame sequences ---------------------------------- */
+/* Both directions of every consecutive pair and their consistency: uf, vf [T-1][H][W] are the forward flows (frames t ->
+ * t+1, oflk_pyramidal_sequence's values), ub, vb the backward flows (frames t+1 -> t, the values oflk_pyramidal_sequence
+ * gives flow T-2-t on the reversed frames), all four required.  err_f / valid_f (forward, on frame t's grid) and err_b /
+ * valid_b (backward, on frame t+1's grid) are oflk_fb_consistency's outputs with alpha, beta; each may be NULL (all four
+ * NULL skips the check).  Flagged pairs of both directions are resolved (oflk_last_resolved() counts both), and
+ * oflk_set_host_arithmetic applies.  Each frame is uploaded once and its pyramid built once for both directions.  A
+ * large call goes in chunks of C pairs (C+1 frames, the boundary frame shared with the next chunk) one after the other,
+ * without the PCIe overlap of oflk_pyramidal_sequence; results do not depend on the cut.  T < 2, NULL flows, alpha or beta
+ * negative or not finite: OFLK_ERR_INVALID. */
+int oflk_pyramidal_sequence_fb(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
+                               float alpha, float beta, float *uf, float *vf, float *ub, float *vb, float *err_f,
+                               float *err_b, unsigned char *valid_f, unsigned char *valid_b);
+int oflk_pyramidal_sequence_fb_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                  float alpha, float beta, float *uf, float *vf, float *ub, float *vb, float *err_f,
+                                  float *err_b, unsigned char *valid_f, unsigned char *valid_b);
+/* oflk_fb_consistency (below) on host arrays [B][H][W] (synchronous) */
+int oflk_fb_consistency_host(const float *uf, const float *vf, const float *ub, const float *vb, int B, int H, int W,
+                             float alpha, float beta, float *err_f, float *err_b, unsigned char *valid_f,
+                             unsigned char *valid_b);
+
 /* Rehearsal of the chunk queue above on a box with fewer GPUs than workers (tests): `workers` > 0 makes the *_multi entry
  * points run that many queue workers, worker i on device i % n_gpus (workers of one device take turns on it); 0 restores
  * one worker per device.  Results do not change. */
@@ -233,6 +254,41 @@ int oflk_plan_pyramidal_u8(oflk_plan *plan, const unsigned char *d_prev, const u
  * pointers: oflk_plan_resolve_uncertain{,_u8}(plan, d_frames, d_frames + H*W, d_u, d_v, ...). */
 int oflk_plan_pyramidal_sequence(oflk_plan *plan, const float *d_frames, float *d_u, float *d_v, void *stream);
 int oflk_plan_pyramidal_sequence_u8(oflk_plan *plan, const unsigned char *d_frames, float *d_u, float *d_v, void *stream);
+/* Both directions of a sequence on one pyramid: the forward pass of oflk_plan_pyramidal_sequence into d_uf, d_vf, then the
+ * backward pass (flow b is frames b+1 -> b) into d_ub, d_vb, all [B][H][W].  The B+1 frames' pyramid is built once; the
+ * backward pass runs the same level loop with prev and curr exchanged, on a second per-call state block (iteration counts,
+ * log, uncertain flags) that the plan allocates on its first bidirectional call.  Values, logs and flags of either
+ * direction equal those of oflk_plan_pyramidal_sequence on the frames (forward) or on the reversed frames (backward, pair
+ * B-1-b).  Asynchronous, no host synchronisation: after one eager call the pass can be captured into a graph.
+ * oflk_plan_read_log / read_uncertain report the forward pass, the _backward forms below the backward one;
+ * oflk_plan_read_level_flow reports the backward pass after a bidirectional call.  Flagged pairs are the caller's to
+ * resolve (oflk_plan_resolve_uncertain_sequence_fb), before oflk_fb_consistency. */
+int oflk_plan_pyramidal_sequence_fb(oflk_plan *plan, const float *d_frames, float *d_uf, float *d_vf, float *d_ub,
+                                    float *d_vb, void *stream);
+int oflk_plan_pyramidal_sequence_fb_u8(oflk_plan *plan, const unsigned char *d_frames, float *d_uf, float *d_vf,
+                                       float *d_ub, float *d_vb, void *stream);
+/* oflk_plan_read_log / oflk_plan_read_uncertain of the backward pass of the last bidirectional call (synchronise) */
+int oflk_plan_read_log_backward(oflk_plan *plan, float *residual_log, int *iters_run, void *stream);
+int oflk_plan_read_uncertain_backward(oflk_plan *plan, int *uncertain, void *stream);
+/* oflk_plan_resolve_uncertain for both directions of a bidirectional call: forward pairs from (d_frames, d_frames + H*W)
+ * into d_uf, d_vf, backward pairs from (d_frames + H*W, d_frames) into d_ub, d_vb, each into its own state block.
+ * *resolved (may be NULL) counts the pairs redone in both directions.  Level flows (read_level_flow) stay the backward
+ * pass's.  Synchronises. */
+int oflk_plan_resolve_uncertain_sequence_fb(oflk_plan *plan, const float *d_frames, float *d_uf, float *d_vf, float *d_ub,
+                                            float *d_vb, void *stream, int *resolved);
+int oflk_plan_resolve_uncertain_sequence_fb_u8(oflk_plan *plan, const unsigned char *d_frames, float *d_uf, float *d_vf,
+                                               float *d_ub, float *d_vb, void *stream, int *resolved);
+/* Forward-backward consistency of B flow pairs (Sundaram, Brox & Keutzer 2010), one launch, device pointers [B][H][W]:
+ * F = (d_uf, d_vf) frames b -> b+1, G = (d_ub, d_vb) frames b+1 -> b.  float32, each operation rounded on its own:
+ *   bu = warp_image(ub, uf, vf), bv = warp_image(vb, uf, vf)   (the reference's warp_image, python/lucas_kanade_pyramidal.py:66-97)
+ *   e2 = (uf+bu)^2 + (vf+bv)^2;  err_f = sqrt(e2) (correctly rounded)
+ *   m2 = (uf^2 + vf^2) + (bu^2 + bv^2)
+ *   valid_f = (0 <= x+uf <= W-1) & (0 <= y+vf <= H-1) (float64) & (e2 <= alpha*m2 + beta)   (1 or 0)
+ * err_f / valid_f live on frame b's grid; err_b / valid_b are the same with F and G exchanged, on frame b+1's grid.
+ * Any output may be NULL, not all four.  alpha, beta finite and >= 0 (Sundaram et al.: 0.01, 0.5).  Asynchronous. */
+int oflk_fb_consistency(const float *d_uf, const float *d_vf, const float *d_ub, const float *d_vb, int B, int H, int W,
+                        float alpha, float beta, float *d_err_f, float *d_err_b, unsigned char *d_valid_f,
+                        unsigned char *d_valid_b, void *stream);
 
 /* After oflk_plan_pyramidal: copy the residual log / iteration counts of the last
  * enqueued pass to the host (synchronises `stream`).  Either pointer may be NULL. */
@@ -267,7 +323,8 @@ int oflk_last_resolved(void);
 
 /* Final flow of a coarser pyramid level (level < levels-1; the finest level's flow is the result) of
  * pair `pair` of the last pass, to host arrays of that level's size -- what the reference hands to
- * visualize_pyramid_level at python/lucas_kanade_pyramidal.py:226.  Synchronises. */
+ * visualize_pyramid_level at python/lucas_kanade_pyramidal.py:226.  After oflk_plan_pyramidal_sequence_fb{,_u8}: the
+ * backward pass's level flows (pair b: frames b+1 -> b).  Synchronises. */
 int oflk_plan_read_level_flow(oflk_plan *plan, int level, int pair, float *u, float *v, void *stream);
 
 /* Arithmetic of the plan's fp64 stages.  OFLK_ARITH_EXACT (the default of plans and of the host entry points): SciPy's

@@ -194,6 +194,10 @@ struct oflk_plan {
     // per-call state, one allocation, zeroed by k_call_init at the start of every call:
     //   acc[B][L][K][kAccShards][kAccStride] (u64) | iters_run[B][L] (i32) | uncertain[B][L] (i32) | log[B][L][K][2] (f32)
     unsigned long long *state = nullptr;
+    // the backward pass's state block (same layout), allocated on the first bidirectional call; the backward pass swaps it
+    // with `state` while it runs (StateSwap), so every accessor below serves both
+    unsigned long long *state_b = nullptr;
+    bool last_fb = false;   // the last pyramidal pass was bidirectional: the level flows are the backward pass's
     // uint8 plans only, and only when the fused pyramid kernel cannot take the frames (it always can for
     // scale 0.5 unless a level is tiny): float32 copies of the caller's frames, allocated on first need --
     // [B+1][H][W] (prev, or a sequence's B+1 frames) and [B][H][W] (curr)
@@ -237,6 +241,20 @@ struct oflk_plan {
 };
 
 namespace {
+
+// the backward pass's state block in place of the forward one for the lifetime of this object (on = false: no swap)
+struct StateSwap {
+    oflk_plan *p;
+    bool on;
+    StateSwap(oflk_plan *p_, bool on_) : p(p_), on(on_ && p_->state_b)
+    {
+        if (on) std::swap(p->state, p->state_b);
+    }
+    ~StateSwap()
+    {
+        if (on) std::swap(p->state, p->state_b);
+    }
+};
 
 // fused multiply-adds in the Gaussian pyramid: OFLK_ARITH_CONTRACTED, and OFLK_ARITH_TOLERANT inside its envelope
 inline bool contracted_pyramid(const oflk_plan *p)
@@ -681,6 +699,7 @@ void plan_free(oflk_plan *p)
     if (p->tmpA) (void)hipFree(p->tmpA);
     if (p->tmpB) (void)hipFree(p->tmpB);
     if (p->state) (void)hipFree(p->state);
+    if (p->state_b) (void)hipFree(p->state_b);
     if (p->redo) (void)hipFree(p->redo);
     for (auto &q : p->u8_stage)
         if (q) (void)hipFree(q);
@@ -824,10 +843,13 @@ int plan_single_scale(oflk_plan *p, const void *d_prev, const void *d_curr, bool
     }
     return launch_lk<MODE_SINGLE>(p, s, KC_LK_SINGLE, p->hw, a, p->B, u8);
 }
-// seq: d_curr == d_prev + one plane, both inside one buffer of B+1 frames (oflk_plan_pyramidal_sequence)
+// seq: d_curr == d_prev + one plane, both inside one buffer of B+1 frames (oflk_plan_pyramidal_sequence); d_ub, d_vb
+// (a sequence only): the backward flows too, on the same pyramid (oflk_plan_pyramidal_sequence_fb)
 int plan_pyramidal(oflk_plan *p, const void *d_prev, const void *d_curr, bool u8, float *d_u, float *d_v, hipStream_t s,
-                   bool seq = false);
-int resolve_pair(oflk_plan *p, int b, const void *d_prev_in, const void *d_curr_in, bool u8, float *d_u, float *d_v, hipStream_t s);
+                   bool seq = false, float *d_ub = nullptr, float *d_vb = nullptr);
+// level_out = false: the coarser levels' flows are not written where oflk_plan_read_level_flow looks
+int resolve_pair(oflk_plan *p, int b, const void *d_prev_in, const void *d_curr_in, bool u8, float *d_u, float *d_v, hipStream_t s,
+                 bool level_out = true);
 }  // namespace
 
 OFLK_API int oflk_plan_single_scale(oflk_plan *p, const float *d_prev, const float *d_curr,
@@ -923,16 +945,41 @@ OFLK_API int oflk_plan_pyramidal_sequence_u8(oflk_plan *p, const unsigned char *
     return plan_pyramidal(p, d_frames, d_frames + (size_t)p->H * p->W, true, d_u, d_v, (hipStream_t)stream, true);
 }
 
+// Both directions on one pyramid: the backward pass is the forward one with prev and curr exchanged (plan_pyramidal)
+OFLK_API int oflk_plan_pyramidal_sequence_fb(oflk_plan *p, const float *d_frames, float *d_uf, float *d_vf, float *d_ub,
+                                             float *d_vb, void *stream)
+{
+    if (!p || !d_frames || !d_ub || !d_vb) return fail(OFLK_ERR_INVALID, "NULL argument");
+    return plan_pyramidal(p, d_frames, d_frames + (size_t)p->H * p->W, false, d_uf, d_vf, (hipStream_t)stream, true, d_ub, d_vb);
+}
+
+OFLK_API int oflk_plan_pyramidal_sequence_fb_u8(oflk_plan *p, const unsigned char *d_frames, float *d_uf, float *d_vf,
+                                                float *d_ub, float *d_vb, void *stream)
+{
+    if (!p || !d_frames || !d_ub || !d_vb) return fail(OFLK_ERR_INVALID, "NULL argument");
+    return plan_pyramidal(p, d_frames, d_frames + (size_t)p->H * p->W, true, d_uf, d_vf, (hipStream_t)stream, true, d_ub, d_vb);
+}
+
 namespace {
+int iterate_levels(oflk_plan *p, hipStream_t s, const float *d_prev, const float *d_curr, size_t img_prev, size_t img_curr,
+                   bool u8, float *d_u, float *d_v);
+
 int plan_pyramidal(oflk_plan *p, const void *d_prev_in, const void *d_curr_in, bool u8, float *d_u, float *d_v,
-                   hipStream_t s, bool seq)
+                   hipStream_t s, bool seq, float *d_ub, float *d_vb)
 {
     if (!p || !d_prev_in || !d_curr_in || !d_u || !d_v) return fail(OFLK_ERR_INVALID, "NULL argument");
+    const bool fb = d_ub || d_vb;
+    if (fb && (!seq || !d_ub || !d_vb)) return fail(OFLK_ERR_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(p->device));
-    const int B = p->B, L = p->L, K = p->K;
+    const int B = p->B, L = p->L;
+    int rc;
+    if (fb && !p->state_b) {
+        // the backward pass's state block, once per plan (this allocation is why the first bidirectional call is eager)
+        if ((rc = dmalloc(&p->state_b, p->state_words() / 2, &p->ws_bytes))) return rc;
+    }
+    p->last_fb = fb;
     // images the pyramid is built for: prev and curr of every pair, or every frame of a sequence once
     const int nimg = seq ? B + 1 : 2 * B;
-    int rc;
     if (u8 && L > 1 &&
         !pyr_fused_fits(p->dims[2 * (L - 1)], p->dims[2 * (L - 1) + 1], p->dims[2 * (L - 2)], p->dims[2 * (L - 2) + 1], p->gauss)) {
         // the unfused pyramid kernels read float32: convert once and run the float path
@@ -945,7 +992,7 @@ int plan_pyramidal(oflk_plan *p, const void *d_prev_in, const void *d_curr_in, b
         hipLaunchKernelGGL(k_u8_to_f32, dim3((unsigned)((n0 + 4095) / 4096)), dim3(256), 0, s, static_cast<const unsigned char *>(d_prev_in),
                            p->u8_stage[0], n0);
         HIP_TRY(hipGetLastError());
-        if (seq) return plan_pyramidal(p, p->u8_stage[0], p->u8_stage[0] + N, false, d_u, d_v, s, true);
+        if (seq) return plan_pyramidal(p, p->u8_stage[0], p->u8_stage[0] + N, false, d_u, d_v, s, true, d_ub, d_vb);
         hipLaunchKernelGGL(k_u8_to_f32, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, s, static_cast<const unsigned char *>(d_curr_in),
                            p->u8_stage[1], n);
         HIP_TRY(hipGetLastError());
@@ -967,6 +1014,11 @@ int plan_pyramidal(oflk_plan *p, const void *d_prev_in, const void *d_curr_in, b
         // np.mean in NumPy's order, the exit test on the host) -- exact, and as slow as that sounds
         for (int b = 0; b < B; b++)
             if ((rc = resolve_pair(p, b, d_prev_in, d_curr_in, u8, d_u, d_v, s))) return rc;
+        if (fb) {   // the backward pairs: frames exchanged, into the second state block
+            StateSwap sw(p, true);
+            for (int b = 0; b < B; b++)
+                if ((rc = resolve_pair(p, b, d_curr_in, d_prev_in, u8, d_ub, d_vb, s))) return rc;
+        }
         return OFLK_OK;
     }
 
@@ -1002,6 +1054,29 @@ int plan_pyramidal(oflk_plan *p, const void *d_prev_in, const void *d_curr_in, b
         }
     }
 
+    // pair b reads pyramid images b and B + b, or a sequence's frames b and b + 1
+    if ((rc = iterate_levels(p, s, d_prev, d_curr, 0, seq ? 1 : B, u8, d_u, d_v)) || !fb) return rc;
+    // the backward pass on the same pyramid: pair b reads frames b + 1 and b, with its own state block and the coarsest
+    // level's flow cleared again (stream order puts this after the forward pass's last reads of both)
+    StateSwap sw(p, true);
+    PyrExtra z;
+    z.zero_words = reinterpret_cast<unsigned *>(p->state);
+    z.n_zero_words = p->state_words();
+    z.zero_u = reinterpret_cast<float *>(p->fl(0, 0));
+    z.zero_v = z.zero_u + (size_t)B * p->npix(0);
+    z.n_zero_flow = (size_t)B * p->npix(0);
+    if ((rc = launch_call_init(p, s, z))) return rc;
+    return iterate_levels(p, s, d_curr, d_prev, 1, 0, u8, d_ub, d_vb);
+}
+
+// The level loop (lucas_kanade_pyramidal.py:186-223) and the export of one direction: pair b reads prev image img_prev + b
+// and curr image img_curr + b of every coarser pyramid level, and d_prev / d_curr + b * plane at the finest level.  The
+// plan's per-call state (acc, iters_run, uncertain, log) and the coarsest level's flow are already cleared.
+int iterate_levels(oflk_plan *p, hipStream_t s, const float *d_prev, const float *d_curr, size_t img_prev, size_t img_curr,
+                   bool u8, float *d_u, float *d_v)
+{
+    const int B = p->B, L = p->L, K = p->K;
+    int rc;
     for (int l = 0; l < L; l++) {
         const int h = p->dims[2 * l], w = p->dims[2 * l + 1];
         const size_t n = (size_t)h * w;
@@ -1033,9 +1108,8 @@ int plan_pyramidal(oflk_plan *p, const void *d_prev_in, const void *d_curr_in, b
             rc = launch_upsample(p, s, r, B);
             if (rc) return rc;
         }
-        const float *lp = (l == L - 1) ? d_prev : p->pyr[l];
-        // pair b's curr image: pyramid image B + b, or a sequence's frame b + 1
-        const float *lc = (l == L - 1) ? d_curr : p->pyr[l] + (size_t)(seq ? 1 : B) * n;
+        const float *lp = (l == L - 1) ? d_prev : p->pyr[l] + img_prev * n;
+        const float *lc = (l == L - 1) ? d_curr : p->pyr[l] + img_curr * n;
         for (int k = 0; k < K; k++) {
             LkArgs a{};
             a.prev = lp; a.curr = lc;
@@ -1164,7 +1238,8 @@ int np_mean_abs(oflk_plan *p, const float *d, size_t n, hipStream_t s, float *me
 // One pair, the reference's own sequence of steps (lucas_kanade_pyramidal.py:173-223) with the standalone
 // kernels -- pyramid, warp, single-scale LK, flow += d, upsample, all value-identical to the fused path --
 // and the exit decision taken on the HOST from NumPy-order means.  Results and log replace pair b's.
-int resolve_pair(oflk_plan *p, int b, const void *d_prev_in, const void *d_curr_in, bool u8, float *d_u, float *d_v, hipStream_t s)
+int resolve_pair(oflk_plan *p, int b, const void *d_prev_in, const void *d_curr_in, bool u8, float *d_u, float *d_v, hipStream_t s,
+                 bool level_out)
 {
     const int L = p->L, K = p->K, H = p->H, W = p->W;
     const size_t N = (size_t)H * W;
@@ -1255,7 +1330,7 @@ int resolve_pair(oflk_plan *p, int b, const void *d_prev_in, const void *d_curr_
     HIP_TRY(hipMemcpyAsync(d_v + (size_t)b * N, x.v[L - 1], N * sizeof(float), hipMemcpyDeviceToDevice, s));
     // the coarser levels' final flows where oflk_plan_read_level_flow looks for them: the interleaved slot the
     // (new) iteration count of the level selects (strided copies: u into the .x, v into the .y of every float2)
-    for (int l = 0; l < L - 1; l++) {
+    for (int l = 0; level_out && l < L - 1; l++) {
         const size_t n = p->npix(l);
         float *dst = reinterpret_cast<float *>(p->fl(l, runs[(size_t)l] & 1) + (size_t)b * n);
         HIP_TRY(hipMemcpy2DAsync(dst, sizeof(float2), x.u[l], sizeof(float), sizeof(float), n, hipMemcpyDeviceToDevice, s));
@@ -1270,7 +1345,7 @@ int resolve_pair(oflk_plan *p, int b, const void *d_prev_in, const void *d_curr_
 }
 
 int resolve_uncertain(oflk_plan *p, const void *d_prev, const void *d_curr, bool u8, float *d_u, float *d_v, hipStream_t s,
-                      int *resolved)
+                      int *resolved, bool level_out = true)
 {
     if (!p || !d_prev || !d_curr || !d_u || !d_v) return fail(OFLK_ERR_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(p->device));
@@ -1282,11 +1357,28 @@ int resolve_uncertain(oflk_plan *p, const void *d_prev, const void *d_curr, bool
         bool any = false;
         for (int l = 0; l < p->L; l++) any = any || flags[(size_t)b * p->L + l] != 0;
         if (!any) continue;
-        int rc = resolve_pair(p, b, d_prev, d_curr, u8, d_u, d_v, s);
+        int rc = resolve_pair(p, b, d_prev, d_curr, u8, d_u, d_v, s, level_out);
         if (rc) return rc;
         n++;
     }
     if (resolved) *resolved = n;
+    return OFLK_OK;
+}
+
+// both directions of a bidirectional sequence pass; the level flows stay the backward pass's
+int resolve_uncertain_fb(oflk_plan *p, const void *d_frames, bool u8, float *d_uf, float *d_vf, float *d_ub, float *d_vb,
+                         hipStream_t s, int *resolved)
+{
+    if (!p || !d_frames || !d_uf || !d_vf || !d_ub || !d_vb) return fail(OFLK_ERR_INVALID, "NULL argument");
+    if (!p->state_b) return fail(OFLK_ERR_INVALID, "the plan has run no bidirectional pass");
+    const void *d_next = static_cast<const char *>(d_frames) + (size_t)p->H * p->W * (u8 ? 1 : sizeof(float));
+    int nf = 0, nb = 0, rc;
+    if ((rc = resolve_uncertain(p, d_frames, d_next, u8, d_uf, d_vf, s, &nf, !p->last_fb))) return rc;
+    {
+        StateSwap sw(p, true);
+        if ((rc = resolve_uncertain(p, d_next, d_frames, u8, d_ub, d_vb, s, &nb))) return rc;
+    }
+    if (resolved) *resolved = nf + nb;
     return OFLK_OK;
 }
 
@@ -1304,6 +1396,18 @@ OFLK_API int oflk_plan_resolve_uncertain_u8(oflk_plan *p, const unsigned char *d
     return resolve_uncertain(p, d_prev, d_curr, true, d_u, d_v, (hipStream_t)stream, resolved);
 }
 
+OFLK_API int oflk_plan_resolve_uncertain_sequence_fb(oflk_plan *p, const float *d_frames, float *d_uf, float *d_vf, float *d_ub,
+                                                     float *d_vb, void *stream, int *resolved)
+{
+    return resolve_uncertain_fb(p, d_frames, false, d_uf, d_vf, d_ub, d_vb, (hipStream_t)stream, resolved);
+}
+
+OFLK_API int oflk_plan_resolve_uncertain_sequence_fb_u8(oflk_plan *p, const unsigned char *d_frames, float *d_uf, float *d_vf,
+                                                        float *d_ub, float *d_vb, void *stream, int *resolved)
+{
+    return resolve_uncertain_fb(p, d_frames, true, d_uf, d_vf, d_ub, d_vb, (hipStream_t)stream, resolved);
+}
+
 OFLK_API int oflk_last_resolved(void) { return t_resolved; }
 
 OFLK_API int oflk_plan_read_uncertain(oflk_plan *p, int *uncertain, void *stream)
@@ -1316,6 +1420,22 @@ OFLK_API int oflk_plan_read_uncertain(oflk_plan *p, int *uncertain, void *stream
     return OFLK_OK;
 }
 
+OFLK_API int oflk_plan_read_log_backward(oflk_plan *p, float *residual_log, int *iters_run, void *stream)
+{
+    if (!p) return fail(OFLK_ERR_INVALID, "NULL plan");
+    if (!p->state_b) return fail(OFLK_ERR_INVALID, "the plan has run no bidirectional pass");
+    StateSwap sw(p, true);
+    return oflk_plan_read_log(p, residual_log, iters_run, stream);
+}
+
+OFLK_API int oflk_plan_read_uncertain_backward(oflk_plan *p, int *uncertain, void *stream)
+{
+    if (!p) return fail(OFLK_ERR_INVALID, "NULL plan");
+    if (!p->state_b) return fail(OFLK_ERR_INVALID, "the plan has run no bidirectional pass");
+    StateSwap sw(p, true);
+    return oflk_plan_read_uncertain(p, uncertain, stream);
+}
+
 OFLK_API int oflk_plan_read_level_flow(oflk_plan *p, int level, int pair, float *u, float *v, void *stream)
 {
     if (!p || !u || !v) return fail(OFLK_ERR_INVALID, "NULL argument");
@@ -1324,6 +1444,7 @@ OFLK_API int oflk_plan_read_level_flow(oflk_plan *p, int level, int pair, float 
     if (pair < 0 || pair >= p->B) return fail(OFLK_ERR_INVALID, "pair %d out of range [0,%d)", pair, p->B);
     HIP_TRY(hipSetDevice(p->device));
     hipStream_t s = (hipStream_t)stream;
+    StateSwap sw(p, p->last_fb);   // after a bidirectional pass the slots hold the backward flows
     int executed = 0;
     HIP_TRY(hipMemcpyAsync(&executed, p->iters_run() + (size_t)pair * p->L + level, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -2085,6 +2206,157 @@ OFLK_API int oflk_single_scale_sequence(const float *frames, int T, int H, int W
 {
     t_resolved = 0;
     return run_sequence<float>(frames, T, H, W, 0, window_size, 0, 0, false, u, v, nullptr, nullptr);
+}
+
+// ---- forward-backward consistency ------------------------------------------------------------------------------------
+namespace {
+int check_fb(const void *uf, const void *vf, const void *ub, const void *vb, int B, int H, int W, float alpha, float beta,
+             const void *ef, const void *eb, const void *qf, const void *qb)
+{
+    if (!uf || !vf || !ub || !vb) return fail(OFLK_ERR_INVALID, "NULL flow argument");
+    if (!ef && !eb && !qf && !qb) return fail(OFLK_ERR_INVALID, "every output is NULL");
+    if (B < 1) return fail(OFLK_ERR_INVALID, "B must be >= 1 (got %d)", B);
+    if (!(std::isfinite(alpha) && alpha >= 0.0f) || !(std::isfinite(beta) && beta >= 0.0f))
+        return fail(OFLK_ERR_INVALID, "alpha and beta must be finite and >= 0 (got %g, %g)", (double)alpha, (double)beta);
+    return check_hw(uf, vf, H, W);   // lean_taps' 32-bit byte offsets and 24-bit row products
+}
+
+int fb_launch(const float *uf, const float *vf, const float *ub, const float *vb, int B, int H, int W, float alpha, float beta,
+              float *ef, float *eb, unsigned char *qf, unsigned char *qb, hipStream_t s)
+{
+    FbArgs a{};
+    a.uf = uf; a.vf = vf; a.ub = ub; a.vb = vb;
+    a.err_f = ef; a.err_b = eb; a.valid_f = qf; a.valid_b = qb;
+    a.H = H; a.W = W;
+    a.alpha = alpha; a.beta = beta;
+    const int dirs = ((ef || qf) ? 1 : 0) | ((eb || qb) ? 2 : 0);   // >= 1 (check_fb)
+    const dim3 grid = grid2d(W, H, B);
+#define OFLK_LAUNCH_FB(NARROW)                                                                   \
+    do {                                                                                         \
+        if (dirs == 1) hipLaunchKernelGGL((k_fb_check<NARROW, 1>), grid, dim3(256), 0, s, a);    \
+        else if (dirs == 2) hipLaunchKernelGGL((k_fb_check<NARROW, 2>), grid, dim3(256), 0, s, a); \
+        else hipLaunchKernelGGL((k_fb_check<NARROW, 3>), grid, dim3(256), 0, s, a);             \
+    } while (0)
+    if (W == 1) OFLK_LAUNCH_FB(true);
+    else OFLK_LAUNCH_FB(false);
+#undef OFLK_LAUNCH_FB
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+
+// Both directions of a sequence and their consistency, host pointers.  Chunks of C pairs (C+1 frames) run one after the
+// other on the null stream: one bidirectional plan pass, the flagged pairs of both directions resolved, one check launch.
+template <class PIXELS>
+int run_sequence_fb(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
+                    float *uf, float *vf, float *ub, float *vb, float *ef, float *eb, unsigned char *qf, unsigned char *qb)
+{
+    constexpr bool U8 = sizeof(PIXELS) == 1;
+    t_resolved = 0;
+    int rc = check_hw(frames, frames, H, W);
+    if (rc) return rc;
+    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
+    if (levels < 1) return fail(OFLK_ERR_INVALID, "levels must be in [1,%d] (got %d)", OFLK_MAX_LEVELS, levels);
+    const bool check = ef || eb || qf || qb;
+    if (check && (rc = check_fb(uf, vf, ub, vb, T - 1, H, W, alpha, beta, ef, eb, qf, qb))) return rc;
+    if (!uf || !vf || !ub || !vb) return fail(OFLK_ERR_INVALID, "NULL flow argument");
+    const int dev = g_device.load();
+    HostCtx *c = nullptr;
+    std::unique_lock<std::mutex> lk;
+    if ((rc = acquire(dev, &c, lk))) return rc;
+    const int B = T - 1;
+    const size_t plane = (size_t)H * W, pair_out = plane * sizeof(float);
+    // the chunk rule of run_batch_on: ~32 MB of flow per plane and chunk, from four chunks on
+    const int C0 = (int)std::max<size_t>(1, ((size_t)32 << 20) / std::max<size_t>(pair_out, 1));
+    const int C = (B >= 4 * C0 && (size_t)B * pair_out >= ((size_t)64 << 20)) ? C0 : B;
+    Arena ar;
+    PIXELS *d_frames = nullptr;
+    float *d[4] = {nullptr, nullptr, nullptr, nullptr}, *d_e[2] = {nullptr, nullptr};
+    unsigned char *d_q[2] = {nullptr, nullptr};
+    if ((rc = ar.get(&d_frames, (size_t)(C + 1) * plane))) return rc;
+    for (auto &q : d)
+        if ((rc = ar.get(&q, (size_t)C * plane))) return rc;
+    if ((ef && (rc = ar.get(&d_e[0], (size_t)C * plane))) || (eb && (rc = ar.get(&d_e[1], (size_t)C * plane))) ||
+        (qf && (rc = ar.get(&d_q[0], (size_t)C * plane))) || (qb && (rc = ar.get(&d_q[1], (size_t)C * plane))))
+        return rc;
+    for (int b0 = 0; b0 < B; b0 += C) {
+        const int nb = std::min(C, B - b0);
+        const size_t off = (size_t)b0 * plane, n = (size_t)nb * plane;
+        oflk_plan *p = nullptr;
+        if ((rc = host_plan(*c, dev, nb, H, W, levels, window_size, iters, &p))) return rc;
+        HIP_TRY(hipMemcpyAsync(d_frames, frames + off, (n + plane) * sizeof(PIXELS), hipMemcpyHostToDevice, nullptr));
+        if ((rc = plan_pyramidal(p, d_frames, d_frames + plane, U8, d[0], d[1], nullptr, true, d[2], d[3]))) return rc;
+        if (iters > 0) {
+            int n_res = 0;
+            if ((rc = resolve_uncertain_fb(p, d_frames, U8, d[0], d[1], d[2], d[3], nullptr, &n_res))) return rc;
+            t_resolved += n_res;
+        }
+        if (check && (rc = fb_launch(d[0], d[1], d[2], d[3], nb, H, W, alpha, beta, d_e[0], d_e[1], d_q[0], d_q[1], nullptr)))
+            return rc;
+        float *outs[4] = {uf, vf, ub, vb};
+        for (int i = 0; i < 4; i++) HIP_TRY(hipMemcpyAsync(outs[i] + off, d[i], n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+        if (ef) HIP_TRY(hipMemcpyAsync(ef + off, d_e[0], n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+        if (eb) HIP_TRY(hipMemcpyAsync(eb + off, d_e[1], n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+        if (qf) HIP_TRY(hipMemcpyAsync(qf + off, d_q[0], n, hipMemcpyDeviceToHost, nullptr));
+        if (qb) HIP_TRY(hipMemcpyAsync(qb + off, d_q[1], n, hipMemcpyDeviceToHost, nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));   // the chunk's buffers are reused by the next
+    }
+    return OFLK_OK;
+}
+}  // namespace
+
+OFLK_API int oflk_fb_consistency(const float *d_uf, const float *d_vf, const float *d_ub, const float *d_vb, int B, int H, int W,
+                                 float alpha, float beta, float *d_err_f, float *d_err_b, unsigned char *d_valid_f,
+                                 unsigned char *d_valid_b, void *stream)
+{
+    int rc = check_fb(d_uf, d_vf, d_ub, d_vb, B, H, W, alpha, beta, d_err_f, d_err_b, d_valid_f, d_valid_b);
+    if (rc) return rc;
+    return fb_launch(d_uf, d_vf, d_ub, d_vb, B, H, W, alpha, beta, d_err_f, d_err_b, d_valid_f, d_valid_b, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_fb_consistency_host(const float *uf, const float *vf, const float *ub, const float *vb, int B, int H, int W,
+                                      float alpha, float beta, float *err_f, float *err_b, unsigned char *valid_f,
+                                      unsigned char *valid_b)
+{
+    int rc = check_fb(uf, vf, ub, vb, B, H, W, alpha, beta, err_f, err_b, valid_f, valid_b);
+    if (rc) return rc;
+    HostCtx *c = nullptr;
+    std::unique_lock<std::mutex> lk;
+    if ((rc = acquire(g_device.load(), &c, lk))) return rc;
+    Arena ar;
+    const size_t n = (size_t)B * H * W;
+    const float *in[4] = {uf, vf, ub, vb};
+    float *d[4] = {nullptr, nullptr, nullptr, nullptr}, *d_e[2] = {nullptr, nullptr};
+    unsigned char *d_q[2] = {nullptr, nullptr};
+    for (int i = 0; i < 4; i++) {
+        if ((rc = ar.get(&d[i], n))) return rc;
+        HIP_TRY(hipMemcpyAsync(d[i], in[i], n * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    }
+    if ((err_f && (rc = ar.get(&d_e[0], n))) || (err_b && (rc = ar.get(&d_e[1], n))) || (valid_f && (rc = ar.get(&d_q[0], n))) ||
+        (valid_b && (rc = ar.get(&d_q[1], n))))
+        return rc;
+    if ((rc = fb_launch(d[0], d[1], d[2], d[3], B, H, W, alpha, beta, d_e[0], d_e[1], d_q[0], d_q[1], nullptr))) return rc;
+    if (err_f) HIP_TRY(hipMemcpyAsync(err_f, d_e[0], n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    if (err_b) HIP_TRY(hipMemcpyAsync(err_b, d_e[1], n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    if (valid_f) HIP_TRY(hipMemcpyAsync(valid_f, d_q[0], n, hipMemcpyDeviceToHost, nullptr));
+    if (valid_b) HIP_TRY(hipMemcpyAsync(valid_b, d_q[1], n, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return OFLK_OK;
+}
+
+OFLK_API int oflk_pyramidal_sequence_fb(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                        float alpha, float beta, float *uf, float *vf, float *ub, float *vb, float *err_f,
+                                        float *err_b, unsigned char *valid_f, unsigned char *valid_b)
+{
+    return run_sequence_fb<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, uf, vf, ub, vb, err_f, err_b, valid_f,
+                                  valid_b);
+}
+
+OFLK_API int oflk_pyramidal_sequence_fb_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size,
+                                           int iters, float alpha, float beta, float *uf, float *vf, float *ub, float *vb,
+                                           float *err_f, float *err_b, unsigned char *valid_f, unsigned char *valid_b)
+{
+    return run_sequence_fb<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, uf, vf, ub, vb, err_f, err_b,
+                                          valid_f, valid_b);
 }
 
 namespace {

@@ -2257,6 +2257,85 @@ __global__ __launch_bounds__(256) void k_warp(const float *__restrict__ img,
 }
 
 // ---------------------------------------------------------------------------
+// Forward-backward consistency (oflk_fb_consistency).  Pair b has F = (uf, vf), the flow of frames b -> b+1, and
+// G = (ub, vb), the flow of frames b+1 -> b.  float32 throughout except where stated; every operation is rounded on its
+// own (no contraction):
+//   bu = warp_image(ub, uf, vf); bv = warp_image(vb, uf, vf)      the reference's warp_image (k_warp's taps and sum)
+//   eu = uf + bu;  ev = vf + bv
+//   e2 = eu*eu + ev*ev                                            each product rounded, then the sum
+//   err_f = sqrt(e2)                                              correctly rounded
+//   m2 = (uf*uf + vf*vf) + (bu*bu + bv*bv)                        in this order
+//   inside = (0 <= x + uf <= W-1) & (0 <= y + vf <= H-1)          float64, as warp_image forms its coordinates
+//   valid_f = inside & (e2 <= alpha*m2 + beta)                    product, then sum
+// err_b / valid_b: the same on frame b+1's grid with F and G exchanged.  A target outside the frame samples 0 (the
+// reference's cval), so there err = |F| and valid = 0.  One thread per pixel, both directions: the four flows at the
+// pixel are coalesced loads, the eight tap pairs gather from the partner flow near the pixel (L1 / L2 hits).
+// Algorithmic traffic with every output: 16 B read + 8 + 2 B written per pixel.
+struct FbArgs {
+    const float *uf, *vf, *ub, *vb;   // [B][H][W]
+    float *err_f, *err_b;             // [B][H][W] or NULL
+    unsigned char *valid_f, *valid_b; // [B][H][W] (0 / 1) or NULL
+    int H, W;
+    float alpha, beta;
+};
+
+// one direction's statement from its sample of the partner flow: own flow (u, v), taps t, the partner's loaded tap pairs
+__device__ __forceinline__ void fb_finish(float u, float v, const LeanTaps &t, PairF a0, PairF a1, PairF c0, PairF c1, float alpha,
+                                          float beta, float &err, unsigned char &valid)
+{
+    const float bu = lean_finish(t, a0, a1), bv = lean_finish(t, c0, c1);
+    const float eu = __fadd_rn(u, bu), ev = __fadd_rn(v, bv);
+    const float e2 = __fadd_rn(__fmul_rn(eu, eu), __fmul_rn(ev, ev));
+    const float m2 = __fadd_rn(__fadd_rn(__fmul_rn(u, u), __fmul_rn(v, v)), __fadd_rn(__fmul_rn(bu, bu), __fmul_rn(bv, bv)));
+    err = sqrtf(e2);   // llvm.sqrt.f32: correctly rounded under -fhip-fp32-correctly-rounded-divide-sqrt (__fsqrt_rn is the
+                       // native 1-ulp v_sqrt_f32 unless OCML_BASIC_ROUNDED_OPERATIONS is defined)
+    valid = (t.inside && e2 <= __fadd_rn(__fmul_rn(alpha, m2), beta)) ? 1 : 0;
+}
+
+// grid: (ceil(W / 64), ceil(H / 4), B), 256 threads: a wave is 64 consecutive pixels of one row.  Both directions' taps
+// are formed first and all eight gathers issued before any result is stored, so that a wave has them in flight together
+// (issued in turn with stores between them, the launch took 2.86 instead of 2.40 ms at 128 x 1080p).  A variant whose
+// threads walked 8 rows (64 x 32 pixels per block, for L1 / L2 reuse of the gathered rows) measured the same 2.40 ms.
+// NARROW: W == 1 (lean_load's one-column form); DIRS: bit 0 forward, bit 1 backward (the directions with an output).
+// Both are template parameters so that the gathers are straight-line code the compiler can count its waits over.
+template <bool NARROW, int DIRS>
+__global__ __launch_bounds__(256) void k_fb_check(FbArgs a)
+{
+    constexpr bool fwd = DIRS & 1, bwd = DIRS & 2;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= a.W || y >= a.H) return;
+    const size_t base = (size_t)blockIdx.z * ((size_t)a.H * (size_t)a.W);
+    const size_t i = base + (size_t)y * a.W + x;
+    const LeanGeom lg = lean_geom(a.H, a.W);
+    const float uf = a.uf[i], vf = a.vf[i], ub = a.ub[i], vb = a.vb[i];
+    LeanTaps tf{}, tb{};
+    PairF f0{}, f1{}, f2{}, f3{}, g0{}, g1{}, g2{}, g3{};
+    if (fwd) tf = lean_taps(lg, y, x, uf, vf);
+    if (bwd) tb = lean_taps(lg, y, x, ub, vb);
+    if (fwd) {   // forward: G sampled at x + F
+        lean_load<NARROW>(lg, a.ub + base, tf, f0, f1);
+        lean_load<NARROW>(lg, a.vb + base, tf, f2, f3);
+    }
+    if (bwd) {   // backward: F sampled at x + G
+        lean_load<NARROW>(lg, a.uf + base, tb, g0, g1);
+        lean_load<NARROW>(lg, a.vf + base, tb, g2, g3);
+    }
+    float e;
+    unsigned char ok;
+    if (fwd) {
+        fb_finish(uf, vf, tf, f0, f1, f2, f3, a.alpha, a.beta, e, ok);
+        if (a.err_f) a.err_f[i] = e;
+        if (a.valid_f) a.valid_f[i] = ok;
+    }
+    if (bwd) {
+        fb_finish(ub, vb, tb, g0, g1, g2, g3, a.alpha, a.beta, e, ok);
+        if (a.err_b) a.err_b[i] = e;
+        if (a.valid_b) a.valid_b[i] = ok;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // BASELINE config 5: single-scale LK with fp16 gradients and fp16 accumulators (opt-in; NOT the
 // reference's arithmetic -- the reference is fp32 throughout, lucas_kanade_core.py:110-133 -- so this
 // mode's accuracy claim is its EPE against the exact result, tests/test_gpu_fp16.py).  Its correctness

@@ -65,6 +65,16 @@ SIGNATURES = {
     "oflk_single_scale_sequence": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 4 + [_f32p, _f32p]),
     "oflk_plan_pyramidal_sequence": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "oflk_plan_pyramidal_sequence_u8": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "oflk_plan_pyramidal_sequence_fb": (ctypes.c_int, [_vp] * 7),
+    "oflk_plan_pyramidal_sequence_fb_u8": (ctypes.c_int, [_vp] * 7),
+    "oflk_plan_read_log_backward": (ctypes.c_int, [_vp, _f32p, _i32p, _vp]),
+    "oflk_plan_read_uncertain_backward": (ctypes.c_int, [_vp, _i32p, _vp]),
+    "oflk_plan_resolve_uncertain_sequence_fb": (ctypes.c_int, [_vp] * 7 + [_i32p]),
+    "oflk_plan_resolve_uncertain_sequence_fb_u8": (ctypes.c_int, [_vp] * 7 + [_i32p]),
+    "oflk_fb_consistency": (ctypes.c_int, [_vp] * 4 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [_vp] * 5),
+    "oflk_fb_consistency_host": (ctypes.c_int, [_f32p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [_f32p, _f32p, _vp, _vp]),
+    "oflk_pyramidal_sequence_fb": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 2 + [_f32p] * 6 + [_vp, _vp]),
+    "oflk_pyramidal_sequence_fb_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 2 + [_f32p] * 6 + [_vp, _vp]),
     "oflk_shard_range": (None, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, _i32p]),
     "oflk_single_scale_fp16": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, _f32p, _f32p]),
     "oflk_rtl_stream_length": (ctypes.c_long, [ctypes.c_int, ctypes.c_int]),
@@ -231,6 +241,34 @@ class Plan:
         fn = lib().oflk_plan_pyramidal_sequence_u8 if u8 else lib().oflk_plan_pyramidal_sequence
         check(fn(self._h, d_frames, d_u, d_v, stream))
 
+    def pyramidal_sequence_fb(self, d_frames: int, d_uf: int, d_vf: int, d_ub: int, d_vb: int, stream: int = 0,
+                              u8: bool = False) -> None:
+        """Both directions on one pyramid: flow b (frames b -> b+1) into d_uf, d_vf and (frames b+1 -> b) into d_ub, d_vb, all
+        [B][H][W].  Resolve flagged pairs with resolve_uncertain_sequence_fb, then run fb_consistency."""
+        fn = lib().oflk_plan_pyramidal_sequence_fb_u8 if u8 else lib().oflk_plan_pyramidal_sequence_fb
+        check(fn(self._h, d_frames, d_uf, d_vf, d_ub, d_vb, stream))
+
+    def read_log_backward(self, stream: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """read_log of the backward pass of the last pyramidal_sequence_fb call."""
+        log = np.zeros((self.B, self.levels, max(self.iters, 1), 2), np.float32)
+        runs = np.zeros((self.B, self.levels), np.int32)
+        check(lib().oflk_plan_read_log_backward(self._h, ptr(log), runs.ctypes.data_as(_i32p), stream))
+        return log, runs
+
+    def read_uncertain_backward(self, stream: int = 0) -> np.ndarray:
+        """read_uncertain of the backward pass of the last pyramidal_sequence_fb call."""
+        m = np.zeros((self.B, self.levels), np.int32)
+        check(lib().oflk_plan_read_uncertain_backward(self._h, m.ctypes.data_as(_i32p), stream))
+        return m
+
+    def resolve_uncertain_sequence_fb(self, d_frames: int, d_uf: int, d_vf: int, d_ub: int, d_vb: int, stream: int = 0,
+                                      u8: bool = False) -> int:
+        """Redo the flagged pairs of both directions of the last pyramidal_sequence_fb call; returns how many (both)."""
+        n = ctypes.c_int(0)
+        fn = lib().oflk_plan_resolve_uncertain_sequence_fb_u8 if u8 else lib().oflk_plan_resolve_uncertain_sequence_fb
+        check(fn(self._h, d_frames, d_uf, d_vf, d_ub, d_vb, stream, ctypes.byref(n)))
+        return int(n.value)
+
     def single_scale_fp16(self, d_prev: int, d_curr: int, d_u: int, d_v: int, pixel_max: float = 255.0, stream: int = 0) -> None:
         """BASELINE config 5: fp16 gradients / accumulators (opt-in, approximate)."""
         check(lib().oflk_plan_single_scale_fp16(self._h, d_prev, d_curr, d_u, d_v, float(pixel_max), stream))
@@ -300,3 +338,19 @@ class Plan:
         if k < 0:
             check(k)
         return {names[i].decode(): {"total_ms": ms[i], "launches": cnt[i]} for i in range(k)}
+
+
+def check_fb_params(alpha: float, beta: float) -> Tuple[float, float]:
+    """alpha, beta of the forward-backward test as float32; ValueError unless both are finite and >= 0."""
+    with np.errstate(over="ignore"):   # a value beyond float32's range becomes inf, and is refused below
+        a, b = np.float32(alpha), np.float32(beta)
+    if not (np.isfinite(a) and a >= 0 and np.isfinite(b) and b >= 0):
+        raise ValueError(f"alpha and beta must be finite and >= 0, got {alpha!r}, {beta!r}")
+    return float(a), float(b)
+
+
+def fb_consistency(d_uf: int, d_vf: int, d_ub: int, d_vb: int, B: int, H: int, W: int, alpha: float = 0.01, beta: float = 0.5,
+                   d_err_f: int = 0, d_err_b: int = 0, d_valid_f: int = 0, d_valid_b: int = 0, stream: int = 0) -> None:
+    """oflk_fb_consistency on device pointers ([B][H][W]; err float32, valid uint8); 0 leaves an output out (not all four)."""
+    check(lib().oflk_fb_consistency(d_uf, d_vf, d_ub, d_vb, int(B), int(H), int(W), float(alpha), float(beta),
+                                    d_err_f or None, d_err_b or None, d_valid_f or None, d_valid_b or None, stream))

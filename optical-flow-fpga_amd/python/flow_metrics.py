@@ -97,3 +97,28 @@ def compute_all_metrics_gpu(u_pred, v_pred, u_true: float, v_true: float, mask: 
     _oflk.check(_oflk.lib().oflk_flow_metrics(_oflk.ptr(u), _oflk.ptr(v), 1, H, W, _oflk.ptr(ut), _oflk.ptr(vt),
                                               y0, y1, x0, x1, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
     return dict(zip(METRIC_NAMES, (float(x) for x in out[0])))
+
+
+def forward_backward_consistency(u_f, v_f, u_b, v_b, alpha: float = 0.01, beta: float = 0.5):
+    """Forward-backward check of flow pairs on the GPU (oflk_fb_consistency; there is no CPU path).
+
+    u_f, v_f: flow frames t -> t+1; u_b, v_b: flow frames t+1 -> t; (H, W) or (B, H, W), all one shape.  Returns
+    (err_f, err_b, valid_f, valid_b) in that shape: err_f = |F + G(x + F)| (float32, frame t's grid), valid_f = the
+    target x + F lies inside the frame and err_f^2 <= alpha (|F|^2 + |G(x + F)|^2) + beta (bool); err_b / valid_b the
+    same with F and G exchanged (frame t+1's grid).  G(x + F) is the reference's warp_image sample.
+    """
+    import _oflk
+
+    a, b = _oflk.check_fb_params(alpha, beta)
+    arrs = [np.ascontiguousarray(x, dtype=np.float32) for x in (u_f, v_f, u_b, v_b)]
+    shape = arrs[0].shape
+    if any(x.shape != shape for x in arrs) or len(shape) not in (2, 3):
+        raise ValueError(f"expected four flows of one (H, W) or (B, H, W) shape, got {[x.shape for x in arrs]}")
+    B, H, W = (1,) + shape if len(shape) == 2 else shape
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f"empty flows: shape {shape}")
+    err_f, err_b = np.empty(shape, np.float32), np.empty(shape, np.float32)
+    valid_f, valid_b = np.empty(shape, np.uint8), np.empty(shape, np.uint8)
+    _oflk.check(_oflk.lib().oflk_fb_consistency_host(*(_oflk.ptr(x) for x in arrs), B, H, W, a, b, _oflk.ptr(err_f),
+                                                     _oflk.ptr(err_b), valid_f.ctypes.data, valid_b.ctypes.data))
+    return err_f, err_b, valid_f.astype(bool), valid_b.astype(bool)

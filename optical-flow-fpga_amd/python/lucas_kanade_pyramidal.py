@@ -24,7 +24,7 @@ import argparse
 import ctypes
 import os
 from pathlib import Path
-from typing import List, Tuple
+from typing import List, NamedTuple, Tuple
 
 import numpy as np
 import numpy.typing as npt
@@ -217,6 +217,41 @@ def lucas_kanade_pyramidal_sequence(frames, num_levels: int = 3, window_size: in
     """(u, v), each (T-1, H, W) float32: the pyramidal flow of every consecutive pair of a (T, H, W) frame sequence."""
     u, v, _, _ = lucas_kanade_pyramidal_sequence_with_log(frames, num_levels, window_size, num_iterations)
     return u, v
+
+
+class SequenceFB(NamedTuple):
+    """Result of lucas_kanade_pyramidal_sequence_fb; every field is (T-1, H, W).  Index t is the pair (frames[t],
+    frames[t+1]): *_fwd fields live on frame t's grid, *_bwd fields on frame t+1's."""
+    u_fwd: np.ndarray      # flow frames[t] -> frames[t+1] (float32)
+    v_fwd: np.ndarray
+    u_bwd: np.ndarray      # flow frames[t+1] -> frames[t] (float32)
+    v_bwd: np.ndarray
+    err_fwd: np.ndarray    # |F + G(x + F)| in px (float32)
+    err_bwd: np.ndarray    # |G + F(x + G)| in px (float32)
+    valid_fwd: np.ndarray  # bool: the forward vector passes the forward-backward test
+    valid_bwd: np.ndarray
+
+
+def lucas_kanade_pyramidal_sequence_fb(frames, num_levels: int = 3, window_size: int = 5, num_iterations: int = 3,
+                                       alpha: float = 0.01, beta: float = 0.5) -> SequenceFB:
+    """Forward and backward flows of every consecutive pair of a frame sequence, and their consistency.
+
+    frames: a (T, H, W) array or a sequence of T 2-D arrays, T >= 2 (all uint8: the uint8 path).  u_fwd / v_fwd equal
+    lucas_kanade_pyramidal_sequence(frames); u_bwd[t] / v_bwd[t] equal the flow of the pair (frames[t+1], frames[t]).  A
+    forward vector is valid when its target lies inside frame t+1 and |F + G(x + F)|^2 <= alpha (|F|^2 + |G(x + F)|^2) +
+    beta (Sundaram, Brox & Keutzer 2010; G(x + F) is warp_image's bilinear sample, 0 outside the frame); the backward test
+    is the same with F and G exchanged.  Each frame is uploaded once and its pyramid built once for both directions.
+    """
+    a, b = _oflk.check_fb_params(alpha, beta)
+    arr, u8 = _oflk.as_sequence(frames)
+    T, H, W = arr.shape
+    out = [np.empty((T - 1, H, W), np.float32) for _ in range(6)]
+    valid = [np.empty((T - 1, H, W), np.uint8) for _ in range(2)]
+    fn = _oflk.lib().oflk_pyramidal_sequence_fb_u8 if u8 else _oflk.lib().oflk_pyramidal_sequence_fb
+    src = arr.ctypes.data if u8 else _oflk.ptr(arr)
+    _oflk.check(fn(src, T, H, W, int(num_levels), int(window_size), int(num_iterations), a, b,
+                   *(_oflk.ptr(o) for o in out), valid[0].ctypes.data, valid[1].ctypes.data))
+    return SequenceFB(*out[:4], out[4], out[5], valid[0].astype(bool), valid[1].astype(bool))
 
 
 def _dump_levels(key, shapes, u, v) -> None:

@@ -202,6 +202,26 @@ int oflk_fb_consistency_host(const float *uf, const float *vf, const float *ub, 
                              float alpha, float beta, float *err_f, float *err_b, unsigned char *valid_f,
                              unsigned char *valid_b);
 
+/* ---- point tracks through frame sequences ------------------------------------------------------------------------- */
+/* Frames in, tracks out: run_sequence_fb's chunk loop (the bidirectional plan pass, flagged pairs of both directions
+ * resolved), then one oflk_track_points launch per chunk that continues from the previous chunk's last row.  No flow and
+ * no mask leaves the device: tracks [T][N][2] (x, y) and visible [T][N] (0 / 1) are the rows of frames 0 .. T-1 of
+ * oflk_track_points (below) on the sequence's flows.  Queries: qt [N] frame indices (NULL: every query at frame 0), qxy
+ * [N][2] (x, y).  oflk_set_host_arithmetic applies to the flows and oflk_last_resolved() counts the pairs redone; the
+ * tracking arithmetic has one mode only.  T < 2, N < 1, a NULL qxy / tracks / visible, a query frame outside [0, T-1],
+ * alpha or beta negative or not finite: OFLK_ERR_INVALID, before any device call. */
+int oflk_pyramidal_sequence_tracks(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                   float alpha, float beta, const int *qt, const float *qxy, int N, float *tracks,
+                                   unsigned char *visible);
+int oflk_pyramidal_sequence_tracks_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                      float alpha, float beta, const int *qt, const float *qxy, int N, float *tracks,
+                                      unsigned char *visible);
+/* oflk_track_points (below) on host flows of a whole sequence (T = B+1 frames, t0 = 0; synchronous): tracks [B+1][N][2],
+ * visible [B+1][N].  Checks as oflk_pyramidal_sequence_tracks, and the flows' as oflk_fb_consistency_host. */
+int oflk_track_points_host(const float *uf, const float *vf, const float *ub, const float *vb, int B, int H, int W,
+                           float alpha, float beta, const int *qt, const float *qxy, int N, float *tracks,
+                           unsigned char *visible);
+
 /* Rehearsal of the chunk queue above on a box with fewer GPUs than workers (tests): `workers` > 0 makes the *_multi entry
  * points run that many queue workers, worker i on device i % n_gpus (workers of one device take turns on it); 0 restores
  * one worker per device.  Results do not change. */
@@ -289,6 +309,30 @@ int oflk_plan_resolve_uncertain_sequence_fb_u8(oflk_plan *plan, const unsigned c
 int oflk_fb_consistency(const float *d_uf, const float *d_vf, const float *d_ub, const float *d_vb, int B, int H, int W,
                         float alpha, float beta, float *d_err_f, float *d_err_b, unsigned char *d_valid_f,
                         unsigned char *d_valid_b, void *stream);
+/* Point tracks through B flow pairs, one launch, device pointers: F = (d_uf, d_vf) and G = (d_ub, d_vb) [B][H][W] are pairs
+ * t0 .. t0+B-1 of a sequence (F: frames t -> t+1, G: frames t+1 -> t).  Query n is (t_q, x_q, y_q): frame d_qt[n] (d_qt
+ * NULL: every query at frame 0) and the float32 point d_qxy[n] = (x, y), x along W.  sample(img, x, y) is the reference's
+ * warp_image at one float64 point (SciPy's map_coordinates, order 1, cval 0; float32 result).  float32, each operation
+ * rounded on its own, positions carried as float32:
+ *   rows t < t_q: (NaN, NaN), visible 0;  x_q, y_q not finite or outside [0, W-1] x [0, H-1]: every row NaN / 0
+ *   row t_q: (x, y) = (x_q + 0, y_q + 0), visible 1                     (a query at -0 reads as +0)
+ *   for t = t_q .. :  us = sample(uf[t], x, y); vs = sample(vf[t], x, y)
+ *                     qx = f64(x) + f64(us); qy = f64(y) + f64(vs)
+ *                     inside = 0 <= qx <= W-1 and 0 <= qy <= H-1                          (float64, closed)
+ *                     bu = sample(ub[t], qx, qy); bv = sample(vb[t], qx, qy)
+ *                     eu = us + bu; ev = vs + bv; e2 = eu*eu + ev*ev; m2 = (us*us + vs*vs) + (bu*bu + bv*bv)
+ *                     ok = inside and e2 <= alpha*m2 + beta
+ *                     not ok: every later row NaN / 0 (the track ends: occluded, inconsistent or out of the frame)
+ *                     ok: (x, y) = (f32(qx), f32(qy)) (nearest even) is row t+1, visible 1
+ * d_tracks [B+1][N][2] (8-byte aligned) and d_visible [B+1][N] are the rows of frames t0 .. t0+B.  Row 0 is READ for
+ * queries with qt < t0 (the previous call's last row: the whole state of a track) and written for qt >= t0; every other
+ * row is written, so calls over consecutive pieces of a sequence give the tracks of one call.  A query point outside the
+ * frame is not an error (a never-visible track).  B, N < 1, t0 < 0, NULL flows / queries / outputs, alpha or beta
+ * negative or not finite: OFLK_ERR_INVALID.  The point chain is serial: a few thousand points are bound by two dependent
+ * gathers per pair.  Asynchronous. */
+int oflk_track_points(const float *d_uf, const float *d_vf, const float *d_ub, const float *d_vb, int B, int H, int W,
+                      float alpha, float beta, int t0, const int *d_qt, const float *d_qxy, int N, float *d_tracks,
+                      unsigned char *d_visible, void *stream);
 
 /* After oflk_plan_pyramidal: copy the residual log / iteration counts of the last
  * enqueued pass to the host (synchronises `stream`).  Either pointer may be NULL. */

@@ -2210,14 +2210,20 @@ OFLK_API int oflk_single_scale_sequence(const float *frames, int T, int H, int W
 
 // ---- forward-backward consistency ------------------------------------------------------------------------------------
 namespace {
+int check_alpha_beta(float alpha, float beta)
+{
+    if (!(std::isfinite(alpha) && alpha >= 0.0f) || !(std::isfinite(beta) && beta >= 0.0f))
+        return fail(OFLK_ERR_INVALID, "alpha and beta must be finite and >= 0 (got %g, %g)", (double)alpha, (double)beta);
+    return OFLK_OK;
+}
+
 int check_fb(const void *uf, const void *vf, const void *ub, const void *vb, int B, int H, int W, float alpha, float beta,
              const void *ef, const void *eb, const void *qf, const void *qb)
 {
     if (!uf || !vf || !ub || !vb) return fail(OFLK_ERR_INVALID, "NULL flow argument");
     if (!ef && !eb && !qf && !qb) return fail(OFLK_ERR_INVALID, "every output is NULL");
     if (B < 1) return fail(OFLK_ERR_INVALID, "B must be >= 1 (got %d)", B);
-    if (!(std::isfinite(alpha) && alpha >= 0.0f) || !(std::isfinite(beta) && beta >= 0.0f))
-        return fail(OFLK_ERR_INVALID, "alpha and beta must be finite and >= 0 (got %g, %g)", (double)alpha, (double)beta);
+    if (int rc = check_alpha_beta(alpha, beta)) return rc;
     return check_hw(uf, vf, H, W);   // lean_taps' 32-bit byte offsets and 24-bit row products
 }
 
@@ -2244,13 +2250,43 @@ int fb_launch(const float *uf, const float *vf, const float *ub, const float *vb
     return OFLK_OK;
 }
 
+// Pairs per chunk of run_sequence_fb / run_sequence_tracks (the chunk rule of run_batch_on): ~32 MB of flow per plane and
+// chunk, from four chunks on; otherwise the whole sequence
+int fb_chunk_pairs(int B, size_t plane)
+{
+    const size_t pair_out = plane * sizeof(float);
+    const int C0 = (int)std::max<size_t>(1, ((size_t)32 << 20) / std::max<size_t>(pair_out, 1));
+    return (B >= 4 * C0 && (size_t)B * pair_out >= ((size_t)64 << 20)) ? C0 : B;
+}
+
+// One chunk of a bidirectional host call on the null stream: frames b0 .. b0+nb uploaded into d_frames, the bidirectional
+// plan pass into d[0..3] (uf, vf, ub, vb), the flagged pairs of both directions resolved (counted into t_resolved)
+template <class PIXELS>
+int fb_chunk(HostCtx &c, int dev, const PIXELS *frames, int b0, int nb, int H, int W, int levels, int window_size, int iters,
+             PIXELS *d_frames, float *const *d)
+{
+    constexpr bool U8 = sizeof(PIXELS) == 1;
+    const size_t plane = (size_t)H * W;
+    oflk_plan *p = nullptr;
+    int rc;
+    if ((rc = host_plan(c, dev, nb, H, W, levels, window_size, iters, &p))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_frames, frames + (size_t)b0 * plane, (size_t)(nb + 1) * plane * sizeof(PIXELS), hipMemcpyHostToDevice,
+                           nullptr));
+    if ((rc = plan_pyramidal(p, d_frames, d_frames + plane, U8, d[0], d[1], nullptr, true, d[2], d[3]))) return rc;
+    if (iters > 0) {
+        int n_res = 0;
+        if ((rc = resolve_uncertain_fb(p, d_frames, U8, d[0], d[1], d[2], d[3], nullptr, &n_res))) return rc;
+        t_resolved += n_res;
+    }
+    return OFLK_OK;
+}
+
 // Both directions of a sequence and their consistency, host pointers.  Chunks of C pairs (C+1 frames) run one after the
 // other on the null stream: one bidirectional plan pass, the flagged pairs of both directions resolved, one check launch.
 template <class PIXELS>
 int run_sequence_fb(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
                     float *uf, float *vf, float *ub, float *vb, float *ef, float *eb, unsigned char *qf, unsigned char *qb)
 {
-    constexpr bool U8 = sizeof(PIXELS) == 1;
     t_resolved = 0;
     int rc = check_hw(frames, frames, H, W);
     if (rc) return rc;
@@ -2264,10 +2300,8 @@ int run_sequence_fb(const PIXELS *frames, int T, int H, int W, int levels, int w
     std::unique_lock<std::mutex> lk;
     if ((rc = acquire(dev, &c, lk))) return rc;
     const int B = T - 1;
-    const size_t plane = (size_t)H * W, pair_out = plane * sizeof(float);
-    // the chunk rule of run_batch_on: ~32 MB of flow per plane and chunk, from four chunks on
-    const int C0 = (int)std::max<size_t>(1, ((size_t)32 << 20) / std::max<size_t>(pair_out, 1));
-    const int C = (B >= 4 * C0 && (size_t)B * pair_out >= ((size_t)64 << 20)) ? C0 : B;
+    const size_t plane = (size_t)H * W;
+    const int C = fb_chunk_pairs(B, plane);
     Arena ar;
     PIXELS *d_frames = nullptr;
     float *d[4] = {nullptr, nullptr, nullptr, nullptr}, *d_e[2] = {nullptr, nullptr};
@@ -2281,15 +2315,7 @@ int run_sequence_fb(const PIXELS *frames, int T, int H, int W, int levels, int w
     for (int b0 = 0; b0 < B; b0 += C) {
         const int nb = std::min(C, B - b0);
         const size_t off = (size_t)b0 * plane, n = (size_t)nb * plane;
-        oflk_plan *p = nullptr;
-        if ((rc = host_plan(*c, dev, nb, H, W, levels, window_size, iters, &p))) return rc;
-        HIP_TRY(hipMemcpyAsync(d_frames, frames + off, (n + plane) * sizeof(PIXELS), hipMemcpyHostToDevice, nullptr));
-        if ((rc = plan_pyramidal(p, d_frames, d_frames + plane, U8, d[0], d[1], nullptr, true, d[2], d[3]))) return rc;
-        if (iters > 0) {
-            int n_res = 0;
-            if ((rc = resolve_uncertain_fb(p, d_frames, U8, d[0], d[1], d[2], d[3], nullptr, &n_res))) return rc;
-            t_resolved += n_res;
-        }
+        if ((rc = fb_chunk(*c, dev, frames, b0, nb, H, W, levels, window_size, iters, d_frames, d))) return rc;
         if (check && (rc = fb_launch(d[0], d[1], d[2], d[3], nb, H, W, alpha, beta, d_e[0], d_e[1], d_q[0], d_q[1], nullptr)))
             return rc;
         float *outs[4] = {uf, vf, ub, vb};
@@ -2357,6 +2383,151 @@ OFLK_API int oflk_pyramidal_sequence_fb_u8(const unsigned char *frames, int T, i
 {
     return run_sequence_fb<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, uf, vf, ub, vb, err_f, err_b,
                                           valid_f, valid_b);
+}
+
+// ---- point tracks ----------------------------------------------------------------------------------------------------
+namespace {
+// the query arguments of every track entry point; qt (host forms only, may be NULL) must lie in [0, T-1]
+int check_queries(const int *qt, int T, const void *qxy, int N, const void *tracks, const void *visible)
+{
+    if (!qxy || !tracks || !visible) return fail(OFLK_ERR_INVALID, "NULL query or output argument");
+    if (N < 1) return fail(OFLK_ERR_INVALID, "N must be >= 1 (got %d)", N);
+    for (int n = 0; qt && n < N; n++)
+        if (qt[n] < 0 || qt[n] >= T) return fail(OFLK_ERR_INVALID, "query %d: frame %d outside [0,%d]", n, qt[n], T - 1);
+    return OFLK_OK;
+}
+
+// the flows' and the test's arguments as oflk_fb_consistency takes them, then the queries'
+int check_track(const float *uf, const float *vf, const float *ub, const float *vb, int B, int H, int W, float alpha, float beta,
+                const int *qt, const float *qxy, int N, const float *tracks, const unsigned char *visible)
+{
+    int rc = check_fb(uf, vf, ub, vb, B, H, W, alpha, beta, tracks, nullptr, nullptr, nullptr);
+    return rc ? rc : check_queries(qt, B + 1, qxy, N, tracks, visible);
+}
+
+int track_launch(const float *uf, const float *vf, const float *ub, const float *vb, int B, int H, int W, float alpha, float beta,
+                 int t0, const int *qt, const float *qxy, int N, float *tracks, unsigned char *visible, hipStream_t s)
+{
+    TrackArgs a{};
+    a.uf = uf; a.vf = vf; a.ub = ub; a.vb = vb;
+    a.qt = qt; a.qxy = qxy;
+    a.tracks = tracks; a.visible = visible;
+    a.B = B; a.H = H; a.W = W; a.N = N; a.t0 = t0;
+    a.alpha = alpha; a.beta = beta;
+    const dim3 grid((unsigned)((N + 63) / 64));
+    if (W == 1) hipLaunchKernelGGL(k_track<true>, grid, dim3(64), 0, s, a);
+    else hipLaunchKernelGGL(k_track<false>, grid, dim3(64), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+
+// Tracks of a whole sequence, host pointers: run_sequence_fb's chunks (bidirectional plan pass, flagged pairs of both
+// directions resolved), then one track launch per chunk that continues from the previous chunk's last row.  Only the
+// queries go up and only the tracks come down.
+template <class PIXELS>
+int run_sequence_tracks(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
+                        float beta, const int *qt, const float *qxy, int N, float *tracks, unsigned char *visible)
+{
+    t_resolved = 0;
+    int rc = check_hw(frames, frames, H, W);
+    if (rc) return rc;
+    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
+    if (levels < 1) return fail(OFLK_ERR_INVALID, "levels must be in [1,%d] (got %d)", OFLK_MAX_LEVELS, levels);
+    if ((rc = check_alpha_beta(alpha, beta)) || (rc = check_queries(qt, T, qxy, N, tracks, visible))) return rc;
+    const int dev = g_device.load();
+    HostCtx *c = nullptr;
+    std::unique_lock<std::mutex> lk;
+    if ((rc = acquire(dev, &c, lk))) return rc;
+    const int B = T - 1;
+    const size_t plane = (size_t)H * W, row = (size_t)N;
+    const int C = fb_chunk_pairs(B, plane);
+    Arena ar;
+    PIXELS *d_frames = nullptr;
+    float *d[4] = {nullptr, nullptr, nullptr, nullptr}, *d_qxy = nullptr, *d_tr = nullptr;
+    int *d_qt = nullptr;
+    unsigned char *d_vis = nullptr;
+    if ((rc = ar.get(&d_frames, (size_t)(C + 1) * plane))) return rc;
+    for (auto &q : d)
+        if ((rc = ar.get(&q, (size_t)C * plane))) return rc;
+    if ((rc = ar.get(&d_qxy, 2 * row)) || (qt && (rc = ar.get(&d_qt, row))) || (rc = ar.get(&d_tr, (size_t)(C + 1) * 2 * row)) ||
+        (rc = ar.get(&d_vis, (size_t)(C + 1) * row)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(d_qxy, qxy, 2 * row * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    if (qt) HIP_TRY(hipMemcpyAsync(d_qt, qt, row * sizeof(int), hipMemcpyHostToDevice, nullptr));
+    for (int b0 = 0; b0 < B; b0 += C) {
+        const int nb = std::min(C, B - b0);
+        if (b0 > 0) {   // row 0 of this chunk is the previous (full, C-pair) chunk's last row
+            HIP_TRY(hipMemcpyAsync(d_tr, d_tr + (size_t)C * 2 * row, 2 * row * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(d_vis, d_vis + (size_t)C * row, row, hipMemcpyDeviceToDevice, nullptr));
+        }
+        if ((rc = fb_chunk(*c, dev, frames, b0, nb, H, W, levels, window_size, iters, d_frames, d))) return rc;
+        if ((rc = track_launch(d[0], d[1], d[2], d[3], nb, H, W, alpha, beta, b0, d_qt, d_qxy, N, d_tr, d_vis, nullptr))) return rc;
+        const int r0 = b0 > 0 ? 1 : 0;   // row 0 of a later chunk is already on the host
+        const size_t nr = (size_t)(nb + 1 - r0);
+        HIP_TRY(hipMemcpyAsync(tracks + (size_t)(b0 + r0) * 2 * row, d_tr + (size_t)r0 * 2 * row, nr * 2 * row * sizeof(float),
+                               hipMemcpyDeviceToHost, nullptr));
+        HIP_TRY(hipMemcpyAsync(visible + (size_t)(b0 + r0) * row, d_vis + (size_t)r0 * row, nr * row, hipMemcpyDeviceToHost, nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));   // the chunk's buffers are reused by the next
+    }
+    return OFLK_OK;
+}
+}  // namespace
+
+OFLK_API int oflk_track_points(const float *d_uf, const float *d_vf, const float *d_ub, const float *d_vb, int B, int H, int W,
+                               float alpha, float beta, int t0, const int *d_qt, const float *d_qxy, int N, float *d_tracks,
+                               unsigned char *d_visible, void *stream)
+{
+    int rc = check_track(d_uf, d_vf, d_ub, d_vb, B, H, W, alpha, beta, nullptr, d_qxy, N, d_tracks, d_visible);
+    if (rc) return rc;
+    if (t0 < 0) return fail(OFLK_ERR_INVALID, "t0 must be >= 0 (got %d)", t0);
+    if (reinterpret_cast<uintptr_t>(d_tracks) % 8 != 0) return fail(OFLK_ERR_INVALID, "d_tracks must be 8-byte aligned");
+    return track_launch(d_uf, d_vf, d_ub, d_vb, B, H, W, alpha, beta, t0, d_qt, d_qxy, N, d_tracks, d_visible, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_track_points_host(const float *uf, const float *vf, const float *ub, const float *vb, int B, int H, int W,
+                                    float alpha, float beta, const int *qt, const float *qxy, int N, float *tracks,
+                                    unsigned char *visible)
+{
+    int rc = check_track(uf, vf, ub, vb, B, H, W, alpha, beta, qt, qxy, N, tracks, visible);
+    if (rc) return rc;
+    HostCtx *c = nullptr;
+    std::unique_lock<std::mutex> lk;
+    if ((rc = acquire(g_device.load(), &c, lk))) return rc;
+    Arena ar;
+    const size_t n = (size_t)B * H * W, row = (size_t)N, rows = (size_t)(B + 1) * row;
+    const float *in[4] = {uf, vf, ub, vb};
+    float *d[4] = {nullptr, nullptr, nullptr, nullptr}, *d_qxy = nullptr, *d_tr = nullptr;
+    int *d_qt = nullptr;
+    unsigned char *d_vis = nullptr;
+    for (int i = 0; i < 4; i++) {
+        if ((rc = ar.get(&d[i], n))) return rc;
+        HIP_TRY(hipMemcpyAsync(d[i], in[i], n * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    }
+    if ((rc = ar.get(&d_qxy, 2 * row)) || (qt && (rc = ar.get(&d_qt, row))) || (rc = ar.get(&d_tr, 2 * rows)) ||
+        (rc = ar.get(&d_vis, rows)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(d_qxy, qxy, 2 * row * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    if (qt) HIP_TRY(hipMemcpyAsync(d_qt, qt, row * sizeof(int), hipMemcpyHostToDevice, nullptr));
+    if ((rc = track_launch(d[0], d[1], d[2], d[3], B, H, W, alpha, beta, 0, d_qt, d_qxy, N, d_tr, d_vis, nullptr))) return rc;
+    HIP_TRY(hipMemcpyAsync(tracks, d_tr, 2 * rows * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipMemcpyAsync(visible, d_vis, rows, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return OFLK_OK;
+}
+
+OFLK_API int oflk_pyramidal_sequence_tracks(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                            float alpha, float beta, const int *qt, const float *qxy, int N, float *tracks,
+                                            unsigned char *visible)
+{
+    return run_sequence_tracks<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, qt, qxy, N, tracks, visible);
+}
+
+OFLK_API int oflk_pyramidal_sequence_tracks_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size,
+                                               int iters, float alpha, float beta, const int *qt, const float *qxy, int N,
+                                               float *tracks, unsigned char *visible)
+{
+    return run_sequence_tracks<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, qt, qxy, N, tracks,
+                                              visible);
 }
 
 namespace {

@@ -2336,6 +2336,86 @@ __global__ __launch_bounds__(256) void k_fb_check(FbArgs a)
 }
 
 // ---------------------------------------------------------------------------
+// Point tracks (oflk_track_points): query n starts at (x_q, y_q) on frame t_q and follows the forward flows while each
+// step passes the forward-backward test.  Per step of pair t, float32 except where stated, each operation rounded on
+// its own:
+//   us = sample(uf[t], x, y); vs = sample(vf[t], x, y)       warp_image's bilinear sample at one point (lean_taps_at)
+//   qx = f64(x) + f64(us); qy = f64(y) + f64(vs)
+//   fb_finish at q: bu, bv = samples of ub[t], vb[t] at q; ok = inside(q, closed, float64) & (e2 <= alpha*m2 + beta)
+//   ok: (x, y) = (f32(qx), f32(qy)) is row t+1 (visible 1); otherwise the track ends (NaN, visible 0 from there on)
+// A query outside [0, W-1] x [0, H-1] (NaN included) never starts; a query at -0 reads as +0 (lean_taps_at's range
+// test reads the sign bit).  Positions are float32 between steps, so the last written row is a track's whole state:
+// row 0 of a launch is read for queries of an earlier frame (the previous launch's last row).
+// One thread per query, looping over the launch's pairs: the chain of a point is serial, two dependent gather rounds
+// per pair (uf, vf at p as PairF loads, then ub, vb at q = p + F) and one store of the row (float2 + uint8).  64 B
+// gathered and 9 B written per point-step.  Dense query grids get their parallelism from N; a sparse set of a few
+// thousand points occupies a fraction of the CUs and is bound by the latency of those two rounds per pair, which this
+// kernel does not try to hide.  One-wave blocks spread a sparse set over as many CUs as it has waves.
+struct TrackArgs {
+    const float *uf, *vf, *ub, *vb;   // [B][H][W]: pairs t0 .. t0+B-1
+    const int *qt;                    // [N] query frames, or NULL (every query at frame 0)
+    const float *qxy;                 // [N][2] (x, y)
+    float *tracks;                    // [B+1][N][2]: rows of frames t0 .. t0+B
+    unsigned char *visible;           // [B+1][N]
+    int B, H, W, N, t0;
+    float alpha, beta;
+};
+
+template <bool NARROW>
+__global__ __launch_bounds__(64) void k_track(TrackArgs a)
+{
+    const int n = blockIdx.x * 64 + threadIdx.x;
+    if (n >= a.N) return;
+    const LeanGeom lg = lean_geom(a.H, a.W);
+    const size_t plane = (size_t)a.H * (size_t)a.W, N = (size_t)a.N;
+    float2 *rows = reinterpret_cast<float2 *>(a.tracks);
+    const int qt = a.qt ? a.qt[n] : 0;
+    const float qx = a.qxy[2 * (size_t)n], qy = a.qxy[2 * (size_t)n + 1];
+    const bool q_in = qx >= 0.0f && qx <= (float)(a.W - 1) && qy >= 0.0f && qy <= (float)(a.H - 1);   // NaN: false
+    const bool earlier = qt < a.t0;
+    const long long r_q = earlier ? -1 : (long long)qt - a.t0;   // the query's row in this launch (> B: a later launch)
+    bool alive = false;
+    float x = 0.0f, y = 0.0f;
+    if (earlier) {   // a track of an earlier launch: row 0 is its state
+        alive = a.visible[n] != 0;
+        const float2 p = rows[n];
+        x = p.x;
+        y = p.y;
+    }
+    const float nan = __builtin_nanf("");
+    for (int r = 0; r <= a.B; r++) {
+        if (r > 0 && alive) {   // pair r - 1
+            const size_t off = (size_t)(r - 1) * plane;
+            const LeanTaps tp = lean_taps_at(lg, (double)y, (double)x);
+            PairF u0, u1, v0, v1;
+            lean_load<NARROW>(lg, a.uf + off, tp, u0, u1);
+            lean_load<NARROW>(lg, a.vf + off, tp, v0, v1);
+            const float us = lean_finish(tp, u0, u1), vs = lean_finish(tp, v0, v1);
+            const double px = (double)x + (double)us, py = (double)y + (double)vs;
+            const LeanTaps tq = lean_taps_at(lg, py, px);   // outside: off0 = 0, the samples are 0 and ok = 0
+            PairF b0, b1, c0, c1;
+            lean_load<NARROW>(lg, a.ub + off, tq, b0, b1);
+            lean_load<NARROW>(lg, a.vb + off, tq, c0, c1);
+            float e;
+            unsigned char ok;
+            fb_finish(us, vs, tq, b0, b1, c0, c1, a.alpha, a.beta, e, ok);
+            alive = ok != 0;
+            x = __double2float_rn(px);
+            y = __double2float_rn(py);
+        }
+        if (r == r_q) {
+            alive = q_in;
+            x = qx + 0.0f;   // -0 -> +0
+            y = qy + 0.0f;
+        }
+        if (r == 0 && earlier) continue;   // row 0 is the caller's
+        const size_t i = (size_t)r * N + (size_t)n;
+        rows[i] = alive ? make_float2(x, y) : make_float2(nan, nan);
+        a.visible[i] = alive ? 1 : 0;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // BASELINE config 5: single-scale LK with fp16 gradients and fp16 accumulators (opt-in; NOT the
 // reference's arithmetic -- the reference is fp32 throughout, lucas_kanade_core.py:110-133 -- so this
 // mode's accuracy claim is its EPE against the exact result, tests/test_gpu_fp16.py).  Its correctness

@@ -75,6 +75,10 @@ SIGNATURES = {
     "oflk_fb_consistency_host": (ctypes.c_int, [_f32p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [_f32p, _f32p, _vp, _vp]),
     "oflk_pyramidal_sequence_fb": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 2 + [_f32p] * 6 + [_vp, _vp]),
     "oflk_pyramidal_sequence_fb_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 2 + [_f32p] * 6 + [_vp, _vp]),
+    "oflk_track_points": (ctypes.c_int, [_vp] * 4 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, _vp]),
+    "oflk_track_points_host": (ctypes.c_int, [_f32p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
+    "oflk_pyramidal_sequence_tracks": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 2 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
+    "oflk_pyramidal_sequence_tracks_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 2 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
     "oflk_shard_range": (None, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, _i32p]),
     "oflk_single_scale_fp16": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, _f32p, _f32p]),
     "oflk_rtl_stream_length": (ctypes.c_long, [ctypes.c_int, ctypes.c_int]),
@@ -354,3 +358,27 @@ def fb_consistency(d_uf: int, d_vf: int, d_ub: int, d_vb: int, B: int, H: int, W
     """oflk_fb_consistency on device pointers ([B][H][W]; err float32, valid uint8); 0 leaves an output out (not all four)."""
     check(lib().oflk_fb_consistency(d_uf, d_vf, d_ub, d_vb, int(B), int(H), int(W), float(alpha), float(beta),
                                     d_err_f or None, d_err_b or None, d_valid_f or None, d_valid_b or None, stream))
+
+
+def as_queries(queries, T: int) -> Tuple[Optional[np.ndarray], np.ndarray]:
+    """Track queries as the C ABI takes them: (qt, qxy) with qt int32 (N,) frame indices in [0, T-1] (None for (N, 2)
+    queries: every one at frame 0) and qxy float32 (N, 2) (x, y).  queries: (N, 3) (t, x, y) or (N, 2) (x, y), N >= 1.
+    ValueError otherwise; nothing here touches a device."""
+    q = np.asarray(queries)
+    if q.ndim != 2 or q.shape[1] not in (2, 3) or q.shape[0] < 1:
+        raise ValueError(f"queries must be an (N, 3) (t, x, y) or (N, 2) (x, y) array with N >= 1, got shape {q.shape}")
+    if q.shape[1] == 2:
+        return None, np.ascontiguousarray(q, np.float32)
+    t = q[:, 0]
+    if not np.all(np.isfinite(t)) or not np.array_equal(t, np.floor(t)) or t.min() < 0 or t.max() > T - 1:
+        raise ValueError(f"query frames must be integers in [0, {T - 1}]")
+    return np.ascontiguousarray(t, np.int32), np.ascontiguousarray(q[:, 1:], np.float32)
+
+
+def track_points(d_uf: int, d_vf: int, d_ub: int, d_vb: int, B: int, H: int, W: int, d_qxy: int, N: int, d_tracks: int,
+                 d_visible: int, alpha: float = 0.01, beta: float = 0.5, t0: int = 0, d_qt: int = 0, stream: int = 0) -> None:
+    """oflk_track_points on device pointers: flows [B][H][W] of pairs t0 .. t0+B-1, queries d_qxy [N][2] float32 (x, y) and
+    d_qt [N] int32 (0: every query at frame 0), rows of frames t0 .. t0+B into d_tracks [B+1][N][2] float32 and d_visible
+    [B+1][N] uint8 (row 0 is read for queries of an earlier frame: the previous call's last row)."""
+    check(lib().oflk_track_points(d_uf, d_vf, d_ub, d_vb, int(B), int(H), int(W), float(alpha), float(beta), int(t0),
+                                  d_qt or None, d_qxy, int(N), d_tracks, d_visible, stream))

@@ -122,3 +122,29 @@ def forward_backward_consistency(u_f, v_f, u_b, v_b, alpha: float = 0.01, beta: 
     _oflk.check(_oflk.lib().oflk_fb_consistency_host(*(_oflk.ptr(x) for x in arrs), B, H, W, a, b, _oflk.ptr(err_f),
                                                      _oflk.ptr(err_b), valid_f.ctypes.data, valid_b.ctypes.data))
     return err_f, err_b, valid_f.astype(bool), valid_b.astype(bool)
+
+
+def track_points(u_f, v_f, u_b, v_b, queries, alpha: float = 0.01, beta: float = 0.5):
+    """Point tracks through host flows on the GPU (oflk_track_points_host; there is no CPU path).
+
+    u_f, v_f: flows frames t -> t+1; u_b, v_b: flows frames t+1 -> t; all (T-1, H, W).  queries: (N, 3) (t, x, y) or
+    (N, 2) (x, y, at frame 0).  Each point starts on its frame and follows the forward flow, sampled bilinearly at its
+    float32 position, while every step passes the forward-backward test of forward_backward_consistency at that position;
+    its track ends at the first step that fails or leaves the frame.  Returns (tracks (T, N, 2) float32 (x, y), NaN
+    where not visible; visible (T, N) bool).
+    """
+    import _oflk
+
+    a, b = _oflk.check_fb_params(alpha, beta)
+    arrs = [np.ascontiguousarray(x, dtype=np.float32) for x in (u_f, v_f, u_b, v_b)]
+    shape = arrs[0].shape
+    if any(x.shape != shape for x in arrs) or len(shape) != 3 or min(shape) < 1:
+        raise ValueError(f"expected four flows of one (T-1, H, W) shape, got {[x.shape for x in arrs]}")
+    B, H, W = shape
+    qt, qxy = _oflk.as_queries(queries, B + 1)
+    N = qxy.shape[0]
+    tracks, visible = np.empty((B + 1, N, 2), np.float32), np.empty((B + 1, N), np.uint8)
+    _oflk.check(_oflk.lib().oflk_track_points_host(*(_oflk.ptr(x) for x in arrs), B, H, W, a, b,
+                                                   None if qt is None else qt.ctypes.data_as(_oflk._i32p), _oflk.ptr(qxy), N,
+                                                   _oflk.ptr(tracks), visible.ctypes.data))
+    return tracks, visible.astype(bool)

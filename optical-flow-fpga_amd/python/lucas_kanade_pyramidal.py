@@ -254,6 +254,36 @@ def lucas_kanade_pyramidal_sequence_fb(frames, num_levels: int = 3, window_size:
     return SequenceFB(*out[:4], out[4], out[5], valid[0].astype(bool), valid[1].astype(bool))
 
 
+class SequenceTracks(NamedTuple):
+    """Result of lucas_kanade_pyramidal_sequence_tracks: row t is frame t."""
+    tracks: np.ndarray    # (T, N, 2) float32 (x, y); NaN where not visible
+    visible: np.ndarray   # (T, N) bool
+
+
+def lucas_kanade_pyramidal_sequence_tracks(frames, queries, num_levels: int = 3, window_size: int = 5, num_iterations: int = 3,
+                                           alpha: float = 0.01, beta: float = 0.5) -> SequenceTracks:
+    """Point tracks through a frame sequence, stopped at occlusions.
+
+    frames: as lucas_kanade_pyramidal_sequence_fb (all uint8: the uint8 path).  queries: (N, 3) (t, x, y) or (N, 2) (x, y,
+    at frame 0), x along W.  Each point starts on its frame and follows the forward flow (bilinear samples at its float32
+    position) while every step passes the forward-backward test of lucas_kanade_pyramidal_sequence_fb at that position
+    (alpha, beta); the track ends at the first step that fails or leaves the frame, and a point outside the frame never
+    starts.  The flows stay on the device: only the tracks come back.
+    """
+    a, b = _oflk.check_fb_params(alpha, beta)
+    arr, u8 = _oflk.as_sequence(frames)
+    T, H, W = arr.shape
+    qt, qxy = _oflk.as_queries(queries, T)
+    N = qxy.shape[0]
+    tracks, visible = np.empty((T, N, 2), np.float32), np.empty((T, N), np.uint8)
+    fn = _oflk.lib().oflk_pyramidal_sequence_tracks_u8 if u8 else _oflk.lib().oflk_pyramidal_sequence_tracks
+    src = arr.ctypes.data if u8 else _oflk.ptr(arr)
+    _oflk.check(fn(src, T, H, W, int(num_levels), int(window_size), int(num_iterations), a, b,
+                   None if qt is None else qt.ctypes.data_as(_oflk._i32p), _oflk.ptr(qxy), N, _oflk.ptr(tracks),
+                   visible.ctypes.data))
+    return SequenceTracks(tracks, visible.astype(bool))
+
+
 def _dump_levels(key, shapes, u, v) -> None:
     """The reference's per-level PNG side effect (:226), after the call, best-effort."""
     num_levels = key[3]

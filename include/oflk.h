@@ -222,6 +222,40 @@ int oflk_track_points_host(const float *uf, const float *vf, const float *ub, co
                            float alpha, float beta, const int *qt, const float *qxy, int N, float *tracks,
                            unsigned char *visible);
 
+/* ---- Shi-Tomasi corners and detect-then-track (KLT) -------------------------------------------------------------- */
+/* The statement (tests/feature_model.py).  One frame f [H][W], float32 or uint8 (converted exactly); window w = 2h+1, odd,
+ * 3 <= w <= 11 (other windows: OFLK_ERR_UNSUPPORTED).  Score map S [H][W] float32:
+ *   Ix, Iy = compute_gradients(f, f) (Sobel/8 of (f + f) / 2, the "symm" ring);  P = Ix*Ix, Ix*Iy, Iy*Iy (float32)
+ *   R[y,x] = ((P[y,x-h] + P[y,x-h+1]) + ...) + P[y,x+h];  A[y,x] = ((R[y-h,x] + R[y-h+1,x]) + ...) + R[y+h,x]  (float32)
+ *   a, b, c = Axx, Axy, Ayy;  S = 0 where y < h, y >= H-h, x < h or x >= W-h;  elsewhere, float64, each op rounded:
+ *   det = a*c - b*b;  S = f32(2*det / ((a + c) + sqrt((a-c)*(a-c) + 4*b*b))) if det > 0, else 0;  non-finite S: 0
+ * Selection (q = quality_level in [0,1], md = min_distance >= 0, K = max_corners >= 1):
+ *   M = max(S) (M == 0: no features);  candidate: S > 0, f64(S) > f64(q)*f64(M), S >= each of its (up to) 8 neighbours
+ *   priority: S descending, then y*W + x ascending;  greedy in that order: accept unless an accepted point lies at
+ *   dx*dx + dy*dy < md*md (integers, float64);  stop after K
+ *   count;  xy [K][2] float32 (x, y) in acceptance order;  score [K];  rows from count on: (NaN, NaN), score 0
+ * Frames smaller than the window give count 0.  F < 1, a NULL pointer, q outside [0,1] or not finite, md negative or not
+ * finite, K < 1: OFLK_ERR_INVALID, before any device call. */
+/* F frames -> F score maps (synchronous) */
+int oflk_corner_score_host(const float *frames, int F, int H, int W, int window_size, float *score);
+int oflk_corner_score_host_u8(const unsigned char *frames, int F, int H, int W, int window_size, float *score);
+/* F frames -> count [F], xy [F][K][2], score [F][K] (synchronous) */
+int oflk_good_features_host(const float *frames, int F, int H, int W, int window_size, float quality_level,
+                            float min_distance, int max_corners, int *count, float *xy, float *score);
+int oflk_good_features_host_u8(const unsigned char *frames, int F, int H, int W, int window_size, float quality_level,
+                               float min_distance, int max_corners, int *count, float *xy, float *score);
+/* Detect, then track: the features of frame 0 (window = the LK window_size, which must therefore be a corner window) are
+ * the queries of oflk_pyramidal_sequence_tracks, N = K, every query at frame 0; the NaN rows are never-visible tracks.
+ * Equals oflk_good_features_host on frame 0 followed by oflk_pyramidal_sequence_tracks on its xy, byte for byte; the
+ * features are born on the device from chunk 0's frames, no host round trip.  count [1], xy [K][2], score [K],
+ * tracks [T][K][2], visible [T][K].  Checks as both. */
+int oflk_pyramidal_sequence_klt(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                float alpha, float beta, float quality_level, float min_distance, int max_corners,
+                                int *count, float *xy, float *score, float *tracks, unsigned char *visible);
+int oflk_pyramidal_sequence_klt_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                   float alpha, float beta, float quality_level, float min_distance, int max_corners,
+                                   int *count, float *xy, float *score, float *tracks, unsigned char *visible);
+
 /* Rehearsal of the chunk queue above on a box with fewer GPUs than workers (tests): `workers` > 0 makes the *_multi entry
  * points run that many queue workers, worker i on device i % n_gpus (workers of one device take turns on it); 0 restores
  * one worker per device.  Results do not change. */
@@ -333,6 +367,19 @@ int oflk_fb_consistency(const float *d_uf, const float *d_vf, const float *d_ub,
 int oflk_track_points(const float *d_uf, const float *d_vf, const float *d_ub, const float *d_vb, int B, int H, int W,
                       float alpha, float beta, int t0, const int *d_qt, const float *d_qxy, int N, float *d_tracks,
                       unsigned char *d_visible, void *stream);
+/* Shi-Tomasi scores (statement above) of F frames, device pointers: d_frames [F][H][W] float32, or uint8 with u8 != 0;
+ * d_score [F][H][W].  Asynchronous; one launch. */
+int oflk_corner_score(const void *d_frames, int u8, int F, int H, int W, int window_size, float *d_score, void *stream);
+/* Bytes of the caller's workspace for oflk_good_features of this shape (the worst case: H*W candidates per frame, 8 bytes
+ * each, the score maps and, for min_distance > 1, the occupancy grid). */
+int oflk_good_features_workspace(int F, int H, int W, int window_size, float min_distance, int max_corners, size_t *bytes);
+/* Features of F frames (statement above), device pointers: d_count [F], d_xy [F][K][2] (8-byte aligned), d_score [F][K];
+ * d_workspace 256-byte aligned, of at least oflk_good_features_workspace bytes (less: OFLK_ERR_INVALID).  Four kernel
+ * launches (the per-frame counters zeroed, score, candidates, selection: one workgroup per frame, no host round trip), so
+ * the call can be captured into a graph.  Asynchronous. */
+int oflk_good_features(const void *d_frames, int u8, int F, int H, int W, int window_size, float quality_level,
+                       float min_distance, int max_corners, void *d_workspace, size_t workspace_bytes, int *d_count,
+                       float *d_xy, float *d_score, void *stream);
 
 /* After oflk_plan_pyramidal: copy the residual log / iteration counts of the last
  * enqueued pass to the host (synchronises `stream`).  Either pointer may be NULL. */

@@ -2385,6 +2385,227 @@ OFLK_API int oflk_pyramidal_sequence_fb_u8(const unsigned char *frames, int T, i
                                           valid_f, valid_b);
 }
 
+// ---- Shi-Tomasi corners ----------------------------------------------------------------------------------------------
+namespace {
+int check_corner_window(int window_size)
+{
+    if (window_size < 3 || window_size > 11 || window_size % 2 == 0)
+        return fail(OFLK_ERR_UNSUPPORTED, "corner windows are odd sizes in [3,11] (got %d)", window_size);
+    return OFLK_OK;
+}
+
+// the selection's parameters (every value OFLK_ERR_INVALID)
+int check_select(float q, float md, int K)
+{
+    if (!(std::isfinite(q) && q >= 0.0f && q <= 1.0f))
+        return fail(OFLK_ERR_INVALID, "quality_level must be in [0,1] (got %g)", (double)q);
+    if (!(std::isfinite(md) && md >= 0.0f)) return fail(OFLK_ERR_INVALID, "min_distance must be finite and >= 0 (got %g)", (double)md);
+    if (K < 1) return fail(OFLK_ERR_INVALID, "max_corners must be >= 1 (got %d)", K);
+    return OFLK_OK;
+}
+
+// The workspace of oflk_good_features, 256-byte aligned pieces: fmax [F] and ncand [F] (zeroed by k_corner_init), S
+// [F][H][W], keys [F][H*W] (the worst case: every pixel a candidate) and, for md > 1, the grid [F][gh][gw][4]
+struct FeatGeom {
+    int cell = 0, gw = 0, gh = 0;
+    size_t off_cnt = 0, off_s = 0, off_keys = 0, off_grid = 0, bytes = 0;
+};
+
+FeatGeom feat_geom(int F, int H, int W, float md)
+{
+    FeatGeom g;
+    if (md > 1.0f) {   // cells of side ceil(md) (one cell once that covers the frame)
+        g.cell = (int)std::min<double>(std::ceil((double)md), (double)std::max(H, W));
+        g.gw = (W + g.cell - 1) / g.cell;
+        g.gh = (H + g.cell - 1) / g.cell;
+    }
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t nF = (size_t)F, plane = (size_t)H * (size_t)W;
+    g.off_cnt = al(nF * sizeof(unsigned));
+    g.off_s = g.off_cnt + al(nF * sizeof(unsigned));
+    g.off_keys = g.off_s + al(nF * plane * sizeof(float));
+    g.off_grid = g.off_keys + al(nF * plane * sizeof(unsigned long long));
+    g.bytes = g.off_grid + (g.cell ? al(nF * (size_t)g.gw * g.gh * 4 * sizeof(int)) : 0);
+    return g;
+}
+
+int corner_score_launch(const void *frames, bool u8, int F, int H, int W, int window_size, float *score, unsigned *fmax,
+                        hipStream_t s)
+{
+    CornerArgs a{};
+    a.frames = frames;
+    a.score = score;
+    a.fmax = fmax;
+    a.F = F; a.H = H; a.W = W;
+    const dim3 grid((unsigned)((W + kCsTW - 1) / kCsTW), (unsigned)std::min((H + kCsTH - 1) / kCsTH, 65535),
+                    (unsigned)std::min(F, 65535));
+#define OFLK_CS(HWIN)                                                                                                  \
+    case HWIN:                                                                                                        \
+        if (u8) hipLaunchKernelGGL((k_corner_score<unsigned char, HWIN>), grid, dim3(256), 0, s, a);                  \
+        else hipLaunchKernelGGL((k_corner_score<float, HWIN>), grid, dim3(256), 0, s, a);                             \
+        break;
+    switch (window_size / 2) {
+        OFLK_CS(1) OFLK_CS(2) OFLK_CS(3) OFLK_CS(4) OFLK_CS(5)
+        default: return fail(OFLK_ERR_UNSUPPORTED, "corner window %d not built", window_size);
+    }
+#undef OFLK_CS
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+
+// score, candidates and selection of F frames on stream s; the arguments are checked
+int good_features_launch(const void *frames, bool u8, int F, int H, int W, int window_size, float q, float md, int K,
+                         void *workspace, int *count, float *xy, float *score, hipStream_t s)
+{
+    const FeatGeom g = feat_geom(F, H, W, md);
+    char *w = static_cast<char *>(workspace);
+    unsigned *fmax = reinterpret_cast<unsigned *>(w), *ncand = reinterpret_cast<unsigned *>(w + g.off_cnt);
+    float *S = reinterpret_cast<float *>(w + g.off_s);
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(w + g.off_keys);
+    hipLaunchKernelGGL(k_corner_init, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, s, fmax, ncand, F);
+    HIP_TRY(hipGetLastError());
+    int rc = corner_score_launch(frames, u8, F, H, W, window_size, S, fmax, s);
+    if (rc) return rc;
+    CandArgs c{};
+    c.score = S; c.fmax = fmax; c.keys = keys; c.ncand = ncand;
+    c.F = F; c.H = H; c.W = W;
+    c.q = (double)q;
+    hipLaunchKernelGGL(k_corner_cand, dim3((unsigned)((W + 63) / 64), (unsigned)std::min((H + 3) / 4, 65535),
+                                           (unsigned)std::min(F, 65535)), dim3(256), 0, s, c);
+    HIP_TRY(hipGetLastError());
+    SelectArgs a{};
+    a.keys = keys; a.ncand = ncand;
+    a.grid = g.cell ? reinterpret_cast<int *>(w + g.off_grid) : nullptr;
+    a.count = count; a.xy = xy; a.score = score;
+    a.F = F; a.H = H; a.W = W; a.K = K;
+    a.cell = std::max(g.cell, 1); a.gw = g.gw; a.gh = g.gh;
+    a.md2 = (double)md * (double)md;
+    a.use_grid = g.cell != 0;
+    hipLaunchKernelGGL(k_corner_select, dim3((unsigned)std::min(F, 65535)), dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+
+int check_corner_frames(const void *frames, int F, int H, int W)
+{
+    if (!frames) return fail(OFLK_ERR_INVALID, "NULL frames");
+    if (F < 1) return fail(OFLK_ERR_INVALID, "F must be >= 1 (got %d)", F);
+    return check_hw(frames, frames, H, W);
+}
+
+template <class PIXELS>
+int corner_score_host(const PIXELS *frames, int F, int H, int W, int window_size, float *score)
+{
+    int rc = check_corner_frames(frames, F, H, W);
+    if (rc) return rc;
+    if (!score) return fail(OFLK_ERR_INVALID, "NULL score");
+    if ((rc = check_corner_window(window_size))) return rc;
+    HostCtx *c = nullptr;
+    std::unique_lock<std::mutex> lk;
+    if ((rc = acquire(g_device.load(), &c, lk))) return rc;
+    Arena ar;
+    const size_t n = (size_t)F * H * W;
+    PIXELS *d_f = nullptr;
+    float *d_s = nullptr;
+    if ((rc = ar.get(&d_f, n)) || (rc = ar.get(&d_s, n))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_f, frames, n * sizeof(PIXELS), hipMemcpyHostToDevice, nullptr));
+    if ((rc = corner_score_launch(d_f, sizeof(PIXELS) == 1, F, H, W, window_size, d_s, nullptr, nullptr))) return rc;
+    HIP_TRY(hipMemcpyAsync(score, d_s, n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return OFLK_OK;
+}
+
+template <class PIXELS>
+int good_features_host(const PIXELS *frames, int F, int H, int W, int window_size, float q, float md, int K, int *count,
+                       float *xy, float *score)
+{
+    int rc = check_corner_frames(frames, F, H, W);
+    if (rc) return rc;
+    if (!count || !xy || !score) return fail(OFLK_ERR_INVALID, "NULL output argument");
+    if ((rc = check_select(q, md, K)) || (rc = check_corner_window(window_size))) return rc;
+    HostCtx *c = nullptr;
+    std::unique_lock<std::mutex> lk;
+    if ((rc = acquire(g_device.load(), &c, lk))) return rc;
+    Arena ar;
+    const size_t n = (size_t)F * H * W, nk = (size_t)F * K;
+    PIXELS *d_f = nullptr;
+    char *d_ws = nullptr;
+    int *d_cnt = nullptr;
+    float *d_xy = nullptr, *d_sc = nullptr;
+    if ((rc = ar.get(&d_f, n)) || (rc = ar.get(&d_ws, feat_geom(F, H, W, md).bytes)) || (rc = ar.get(&d_cnt, (size_t)F)) ||
+        (rc = ar.get(&d_xy, 2 * nk)) || (rc = ar.get(&d_sc, nk)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(d_f, frames, n * sizeof(PIXELS), hipMemcpyHostToDevice, nullptr));
+    if ((rc = good_features_launch(d_f, sizeof(PIXELS) == 1, F, H, W, window_size, q, md, K, d_ws, d_cnt, d_xy, d_sc, nullptr)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(count, d_cnt, (size_t)F * sizeof(int), hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipMemcpyAsync(xy, d_xy, 2 * nk * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipMemcpyAsync(score, d_sc, nk * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return OFLK_OK;
+}
+}  // namespace
+
+OFLK_API int oflk_corner_score(const void *d_frames, int u8, int F, int H, int W, int window_size, float *d_score, void *stream)
+{
+    int rc = check_corner_frames(d_frames, F, H, W);
+    if (rc) return rc;
+    if (!d_score) return fail(OFLK_ERR_INVALID, "NULL d_score");
+    if ((rc = check_corner_window(window_size))) return rc;
+    return corner_score_launch(d_frames, u8 != 0, F, H, W, window_size, d_score, nullptr, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_corner_score_host(const float *frames, int F, int H, int W, int window_size, float *score)
+{
+    return corner_score_host<float>(frames, F, H, W, window_size, score);
+}
+
+OFLK_API int oflk_corner_score_host_u8(const unsigned char *frames, int F, int H, int W, int window_size, float *score)
+{
+    return corner_score_host<unsigned char>(frames, F, H, W, window_size, score);
+}
+
+OFLK_API int oflk_good_features_workspace(int F, int H, int W, int window_size, float min_distance, int max_corners,
+                                          size_t *bytes)
+{
+    if (!bytes) return fail(OFLK_ERR_INVALID, "NULL bytes");
+    if (F < 1) return fail(OFLK_ERR_INVALID, "F must be >= 1 (got %d)", F);
+    int rc = check_hw(bytes, bytes, H, W);
+    if (rc || (rc = check_select(0.0f, min_distance, max_corners)) || (rc = check_corner_window(window_size))) return rc;
+    *bytes = feat_geom(F, H, W, min_distance).bytes;
+    return OFLK_OK;
+}
+
+OFLK_API int oflk_good_features(const void *d_frames, int u8, int F, int H, int W, int window_size, float quality_level,
+                                float min_distance, int max_corners, void *d_workspace, size_t workspace_bytes, int *d_count,
+                                float *d_xy, float *d_score, void *stream)
+{
+    int rc = check_corner_frames(d_frames, F, H, W);
+    if (rc) return rc;
+    if (!d_workspace || !d_count || !d_xy || !d_score) return fail(OFLK_ERR_INVALID, "NULL workspace or output argument");
+    if ((rc = check_select(quality_level, min_distance, max_corners)) || (rc = check_corner_window(window_size))) return rc;
+    const size_t need = feat_geom(F, H, W, min_distance).bytes;
+    if (workspace_bytes < need)
+        return fail(OFLK_ERR_INVALID, "workspace of %zu bytes, %zu needed (oflk_good_features_workspace)", workspace_bytes, need);
+    if (reinterpret_cast<uintptr_t>(d_workspace) % 256 != 0 || reinterpret_cast<uintptr_t>(d_xy) % 8 != 0)
+        return fail(OFLK_ERR_INVALID, "d_workspace must be 256-byte aligned and d_xy 8-byte aligned");
+    return good_features_launch(d_frames, u8 != 0, F, H, W, window_size, quality_level, min_distance, max_corners, d_workspace,
+                                d_count, d_xy, d_score, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_good_features_host(const float *frames, int F, int H, int W, int window_size, float quality_level,
+                                     float min_distance, int max_corners, int *count, float *xy, float *score)
+{
+    return good_features_host<float>(frames, F, H, W, window_size, quality_level, min_distance, max_corners, count, xy, score);
+}
+
+OFLK_API int oflk_good_features_host_u8(const unsigned char *frames, int F, int H, int W, int window_size, float quality_level,
+                                        float min_distance, int max_corners, int *count, float *xy, float *score)
+{
+    return good_features_host<unsigned char>(frames, F, H, W, window_size, quality_level, min_distance, max_corners, count, xy,
+                                             score);
+}
+
 // ---- point tracks ----------------------------------------------------------------------------------------------------
 namespace {
 // the query arguments of every track entry point; qt (host forms only, may be NULL) must lie in [0, T-1]
@@ -2423,17 +2644,34 @@ int track_launch(const float *uf, const float *vf, const float *ub, const float 
 
 // Tracks of a whole sequence, host pointers: run_sequence_fb's chunks (bidirectional plan pass, flagged pairs of both
 // directions resolved), then one track launch per chunk that continues from the previous chunk's last row.  Only the
-// queries go up and only the tracks come down.
+// queries go up and only the tracks come down.  With `det` (oflk_pyramidal_sequence_klt) the queries are born on the
+// device instead: good_features_launch on frame 0 of chunk 0's frames writes its xy straight into the query buffer (N = K;
+// the NaN rows are never-visible tracks), and count, xy and score come down at the end.
+struct Detect {
+    float q, md;
+    int K;
+    int *count;
+    float *xy, *score;
+};
+
 template <class PIXELS>
 int run_sequence_tracks(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
-                        float beta, const int *qt, const float *qxy, int N, float *tracks, unsigned char *visible)
+                        float beta, const int *qt, const float *qxy, int N, float *tracks, unsigned char *visible,
+                        const Detect *det = nullptr)
 {
     t_resolved = 0;
     int rc = check_hw(frames, frames, H, W);
     if (rc) return rc;
     if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
     if (levels < 1) return fail(OFLK_ERR_INVALID, "levels must be in [1,%d] (got %d)", OFLK_MAX_LEVELS, levels);
-    if ((rc = check_alpha_beta(alpha, beta)) || (rc = check_queries(qt, T, qxy, N, tracks, visible))) return rc;
+    if ((rc = check_alpha_beta(alpha, beta))) return rc;
+    if (det) {
+        if (!det->count || !det->xy || !det->score || !tracks || !visible) return fail(OFLK_ERR_INVALID, "NULL output argument");
+        if ((rc = check_select(det->q, det->md, det->K)) || (rc = check_corner_window(window_size))) return rc;
+        N = det->K;
+    } else if ((rc = check_queries(qt, T, qxy, N, tracks, visible))) {
+        return rc;
+    }
     const int dev = g_device.load();
     HostCtx *c = nullptr;
     std::unique_lock<std::mutex> lk;
@@ -2452,7 +2690,14 @@ int run_sequence_tracks(const PIXELS *frames, int T, int H, int W, int levels, i
     if ((rc = ar.get(&d_qxy, 2 * row)) || (qt && (rc = ar.get(&d_qt, row))) || (rc = ar.get(&d_tr, (size_t)(C + 1) * 2 * row)) ||
         (rc = ar.get(&d_vis, (size_t)(C + 1) * row)))
         return rc;
-    HIP_TRY(hipMemcpyAsync(d_qxy, qxy, 2 * row * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    char *d_ws = nullptr;
+    int *d_cnt = nullptr;
+    float *d_sc = nullptr;
+    if (det) {
+        if ((rc = ar.get(&d_ws, feat_geom(1, H, W, det->md).bytes)) || (rc = ar.get(&d_cnt, 1)) || (rc = ar.get(&d_sc, row))) return rc;
+    } else {
+        HIP_TRY(hipMemcpyAsync(d_qxy, qxy, 2 * row * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    }
     if (qt) HIP_TRY(hipMemcpyAsync(d_qt, qt, row * sizeof(int), hipMemcpyHostToDevice, nullptr));
     for (int b0 = 0; b0 < B; b0 += C) {
         const int nb = std::min(C, B - b0);
@@ -2461,6 +2706,14 @@ int run_sequence_tracks(const PIXELS *frames, int T, int H, int W, int levels, i
             HIP_TRY(hipMemcpyAsync(d_vis, d_vis + (size_t)C * row, row, hipMemcpyDeviceToDevice, nullptr));
         }
         if ((rc = fb_chunk(*c, dev, frames, b0, nb, H, W, levels, window_size, iters, d_frames, d))) return rc;
+        if (det && b0 == 0) {   // frame 0 is d_frames[0]: its features become the queries
+            if ((rc = good_features_launch(d_frames, sizeof(PIXELS) == 1, 1, H, W, window_size, det->q, det->md, det->K, d_ws, d_cnt,
+                                           d_qxy, d_sc, nullptr)))
+                return rc;
+            HIP_TRY(hipMemcpyAsync(det->count, d_cnt, sizeof(int), hipMemcpyDeviceToHost, nullptr));
+            HIP_TRY(hipMemcpyAsync(det->xy, d_qxy, 2 * row * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+            HIP_TRY(hipMemcpyAsync(det->score, d_sc, row * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+        }
         if ((rc = track_launch(d[0], d[1], d[2], d[3], nb, H, W, alpha, beta, b0, d_qt, d_qxy, N, d_tr, d_vis, nullptr))) return rc;
         const int r0 = b0 > 0 ? 1 : 0;   // row 0 of a later chunk is already on the host
         const size_t nr = (size_t)(nb + 1 - r0);
@@ -2528,6 +2781,25 @@ OFLK_API int oflk_pyramidal_sequence_tracks_u8(const unsigned char *frames, int 
 {
     return run_sequence_tracks<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, qt, qxy, N, tracks,
                                               visible);
+}
+
+OFLK_API int oflk_pyramidal_sequence_klt(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                         float alpha, float beta, float quality_level, float min_distance, int max_corners,
+                                         int *count, float *xy, float *score, float *tracks, unsigned char *visible)
+{
+    const Detect det{quality_level, min_distance, max_corners, count, xy, score};
+    return run_sequence_tracks<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, nullptr, nullptr, 0, tracks,
+                                      visible, &det);
+}
+
+OFLK_API int oflk_pyramidal_sequence_klt_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size,
+                                            int iters, float alpha, float beta, float quality_level, float min_distance,
+                                            int max_corners, int *count, float *xy, float *score, float *tracks,
+                                            unsigned char *visible)
+{
+    const Detect det{quality_level, min_distance, max_corners, count, xy, score};
+    return run_sequence_tracks<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, nullptr, nullptr, 0,
+                                              tracks, visible, &det);
 }
 
 namespace {

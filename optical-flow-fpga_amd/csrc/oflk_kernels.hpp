@@ -3157,4 +3157,392 @@ __global__ __launch_bounds__(256) void k_flow_metrics(MetricArgs a)
         a.partial[((size_t)b * kMetricBlocks + blockIdx.x) * kMetricTerms + threadIdx.x] = red[threadIdx.x][0];
 }
 
+// ---------------------------------------------------------------------------
+// Shi-Tomasi corners (oflk_corner_score, oflk_good_features).  The statement (tests/feature_model.py, DESIGN.md, oflk.h):
+// a, b, c = the float32 window sums of Ix*Ix, Ix*Iy, Iy*Iy of compute_gradients(f, f), each row summed left to right
+// over x-h .. x+h, then those row sums top to bottom over y-h .. y+h; S = 0 outside the pixels lucas_kanade_from_gradients
+// solves; inside, in float64 with each operation rounded, det = a*c - b*b, S = f32(2*det / ((a + c) + sqrt((a-c)*(a-c)
+// + 4*b*b))) where det > 0, else 0; a non-finite S is 0.
+//
+// k_corner_score: one 64 x 16 tile of S per block.  The frame tile and its halo of h+1 (clamped: the one-pixel "symm"
+// ring of convolve2d) are staged in LDS as (f + f) * 0.5; the products of the (64+2h) x (16+2h) region are formed with
+// k_gradients' Sobel operations, then the row sums, then the column sums and the fp64 eigenvalue.  Products at positions
+// outside the frame are formed from clamped values and never reach an interior pixel's window.  Algorithmic traffic:
+// the frame in (4 B/px, uint8 1 B/px) and S out (4 B/px); the halo re-reads hit L2.  Each frame's max (S >= 0 and
+// finite, so its bits order as its values) is a wave reduction and one atomicMax per wave on fmax[f] (zeroed first).
+constexpr int kCsTW = 64, kCsTH = 16;
+
+struct CornerArgs {
+    const void *frames;   // [F][H][W] float or uint8
+    float *score;         // [F][H][W]
+    unsigned *fmax;       // [F] bits of each frame's max S (atomicMax; zeroed by the caller), or NULL
+    int F, H, W;
+};
+
+__device__ inline float corner_min_eig(float a32, float b32, float c32)
+{
+    const double a = a32, b = b32, c = c32;
+    const double det = a * c - b * b;
+    if (!(det > 0.0)) return 0.0f;
+    const double tr = a + c, d = a - c;
+    const double disc = __builtin_sqrt(d * d + 4.0 * b * b);   // llvm.sqrt.f64: correctly rounded on gfx950
+    const float s = __double2float_rn((2.0 * det) / (tr + disc));
+    return __builtin_isfinite(s) ? s : 0.0f;
+}
+
+template <class PIX, int HW>
+__global__ __launch_bounds__(256) void k_corner_score(CornerArgs a)
+{
+    constexpr int PW = kCsTW + 2 * HW, PH = kCsTH + 2 * HW;   // the product region
+    constexpr int FW = PW + 2, FH = PH + 2;                   // the frame region
+    __shared__ float sf[FH][FW];
+    __shared__ float sp[3][PH][PW];
+    __shared__ float sr[3][PH][kCsTW];
+    const int tid = threadIdx.x, H = a.H, W = a.W;
+    const int tiles_y = (H + kCsTH - 1) / kCsTH;
+    const size_t plane = (size_t)H * (size_t)W;
+    for (int f = blockIdx.z; f < a.F; f += gridDim.z) {
+        const PIX *src = static_cast<const PIX *>(a.frames) + (size_t)f * plane;
+        float *dst = a.score + (size_t)f * plane;
+        for (int ty = blockIdx.y; ty < tiles_y; ty += gridDim.y) {
+            const int x0 = blockIdx.x * kCsTW, y0 = ty * kCsTH;
+            __syncthreads();   // the previous tile's LDS reads are done
+            for (int i = tid; i < FH * FW; i += 256) {
+                const int r = i / FW, c = i - r * FW;
+                const int yy = min(max(y0 - HW - 1 + r, 0), H - 1), xx = min(max(x0 - HW - 1 + c, 0), W - 1);
+                const float v = (float)src[(size_t)yy * W + xx];
+                const float s = v + v;   // (prev + curr) / 2 as k_gradients, prev = curr
+                sf[r][c] = s * 0.5f;
+            }
+            __syncthreads();
+            for (int i = tid; i < PH * PW; i += 256) {   // product at region (r, c) = frame region (r+1, c+1)
+                const int r = i / PW, c = i - r * PW;
+                const float a_mm = sf[r][c], a_m0 = sf[r][c + 1], a_mp = sf[r][c + 2];
+                const float a_0m = sf[r + 1][c], a_0p = sf[r + 1][c + 2];
+                const float a_pm = sf[r + 2][c], a_p0 = sf[r + 2][c + 1], a_pp = sf[r + 2][c + 2];
+                float ix = a_pp * -0.125f;   // k_gradients' operations, in its order
+                ix = fmaf(a_pm, 0.125f, ix);
+                ix = fmaf(a_0p, -0.25f, ix);
+                ix = fmaf(a_0m, 0.25f, ix);
+                ix = fmaf(a_mp, -0.125f, ix);
+                ix = fmaf(a_mm, 0.125f, ix);
+                float iy = a_pp * -0.125f;
+                iy = fmaf(a_p0, -0.25f, iy);
+                iy = fmaf(a_pm, -0.125f, iy);
+                iy = fmaf(a_mp, 0.125f, iy);
+                iy = fmaf(a_m0, 0.25f, iy);
+                iy = fmaf(a_mm, 0.125f, iy);
+                sp[0][r][c] = ix * ix;
+                sp[1][r][c] = ix * iy;
+                sp[2][r][c] = iy * iy;
+            }
+            __syncthreads();
+            for (int i = tid; i < 3 * PH * kCsTW; i += 256) {   // row sums, left to right
+                const int k = i / (PH * kCsTW), rem = i - k * (PH * kCsTW), r = rem / kCsTW, c = rem - r * kCsTW;
+                float s = sp[k][r][c];
+#pragma unroll
+                for (int j = 1; j <= 2 * HW; j++) s = s + sp[k][r][c + j];
+                sr[k][r][c] = s;
+            }
+            __syncthreads();
+            unsigned best = 0;
+            for (int i = tid; i < kCsTH * kCsTW; i += 256) {   // column sums, top to bottom, and the eigenvalue
+                const int r = i / kCsTW, c = i - r * kCsTW, y = y0 + r, x = x0 + c;
+                float t[3];
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    float s = sr[k][r][c];
+#pragma unroll
+                    for (int j = 1; j <= 2 * HW; j++) s = s + sr[k][r + j][c];
+                    t[k] = s;
+                }
+                const bool inner = y >= HW && y < H - HW && x >= HW && x < W - HW;
+                const float S = inner ? corner_min_eig(t[0], t[1], t[2]) : 0.0f;
+                if (y < H && x < W) {
+                    dst[(size_t)y * W + x] = S;
+                    best = max(best, __float_as_uint(S));
+                }
+            }
+            if (a.fmax) {
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) best = max(best, (unsigned)__shfl_xor((int)best, o, 64));
+                if ((tid & 63) == 0 && best) atomicMax(a.fmax + f, best);
+            }
+        }
+    }
+}
+
+// Candidates (oflk_good_features): S > 0, f64(S) > f64(q) * f64(M) and S >= each of its (up to) 8 neighbours, compacted
+// per frame into keys[f][0 .. ncand[f]) as (~bits(S)) << 32 | (y*W + x): ascending keys are the priority order (S
+// descending, then raster index).  One pixel per thread; the neighbours are read only above the threshold.  The order of
+// the list is not deterministic; the key makes every later order total.  At most H*W keys per frame.
+struct CandArgs {
+    const float *score;            // [F][H][W]
+    const unsigned *fmax;          // [F]
+    unsigned long long *keys;      // [F][H*W]
+    unsigned *ncand;               // [F] (zeroed by the caller)
+    int F, H, W;
+    double q;
+};
+
+__global__ __launch_bounds__(256) void k_corner_cand(CandArgs a)
+{
+    const int H = a.H, W = a.W, x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int rows_y = (H + 3) / 4;
+    const size_t plane = (size_t)H * (size_t)W;
+    for (int f = blockIdx.z; f < a.F; f += gridDim.z) {
+        const float *S = a.score + (size_t)f * plane;
+        const double thr = a.q * (double)__uint_as_float(a.fmax[f]);
+        for (int by = blockIdx.y; by < rows_y; by += gridDim.y) {
+            const int y = by * 4 + (threadIdx.x >> 6);
+            bool cand = false;
+            float s = 0.0f;
+            if (x < W && y < H) {
+                s = S[(size_t)y * W + x];
+                cand = s > 0.0f && (double)s > thr;
+                if (cand) {
+                    for (int dy = -1; dy <= 1; dy++)
+                        for (int dx = -1; dx <= 1; dx++) {
+                            const int yy = y + dy, xx = x + dx;
+                            if ((dy || dx) && yy >= 0 && yy < H && xx >= 0 && xx < W && !(s >= S[(size_t)yy * W + xx])) cand = false;
+                        }
+                }
+            }
+            const unsigned long long m = __ballot(cand);
+            if (m) {
+                const int lane = threadIdx.x & 63;
+                unsigned base = 0;
+                if (lane == __builtin_ctzll(m)) base = atomicAdd(a.ncand + f, (unsigned)__popcll(m));
+                base = (unsigned)__shfl((int)base, __builtin_ctzll(m), 64);
+                if (cand) {
+                    const unsigned rank = (unsigned)__popcll(m & ((1ull << lane) - 1));
+                    a.keys[(size_t)f * plane + base + rank] =
+                        ((unsigned long long)(~__float_as_uint(s)) << 32) | (unsigned)(y * W + x);
+                }
+            }
+        }
+    }
+}
+
+// fmax[f] = ncand[f] = 0 ahead of k_corner_score / k_corner_cand
+__global__ __launch_bounds__(256) void k_corner_init(unsigned *fmax, unsigned *ncand, int F)
+{
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f < F) {
+        fmax[f] = 0;
+        ncand[f] = 0;
+    }
+}
+
+// k_corner_select: the sequential greedy of the statement, one 256-thread workgroup per frame, no host round trip.
+//   slab:    the lowest keys (highest priority) not yet taken that fit in LDS (kSelCap): a radix descent on 8-bit digits
+//            of the key, one histogram pass over the frame's list per digit, stopping once half the slab is filled;
+//            the slab's keys gathered into LDS and bitonic-sorted
+//   batches: 256 keys of the slab in order; each is tested against the accepted points in the occupancy grid (cells
+//            of side c = ceil(md), 4 slots each: an accepted point's conflicts lie in its 3 x 3 cells, and a cell of
+//            side c - 1 < md holds at most 4 points pairwise >= md apart); the survivors are then resolved among
+//            themselves in priority order -- each knows its earlier conflicting survivors (a 256-bit mask), and rounds
+//            of "accepted if every earlier conflict is rejected, rejected if one is accepted" settle at least the
+//            earliest open one per round; the first K - count accepted are written and entered into the grid
+//   md <= 1: distinct pixels are >= 1 apart, so every candidate is accepted in order (no grid)
+// Until K are accepted or the list is exhausted.  Rows from count on are (NaN, NaN), score 0.
+constexpr int kSelCap = 4096;
+
+struct SelectArgs {
+    const unsigned long long *keys;   // [F][H*W]
+    const unsigned *ncand;            // [F]
+    int *grid;                        // [F][gw*gh*4] (md > 1)
+    int *count;                       // [F]
+    float *xy;                        // [F][K][2]
+    float *score;                     // [F][K]
+    int F, H, W, K, cell, gw, gh;
+    double md2;
+    bool use_grid;
+};
+
+__global__ __launch_bounds__(256) void k_corner_select(SelectArgs a)
+{
+    __shared__ unsigned long long slab[kSelCap];
+    __shared__ unsigned hist[256];
+    __shared__ unsigned long long s_lo, s_hi, s_prefix;
+    __shared__ unsigned s_taken, s_fill;
+    __shared__ int s_shift, s_done;
+    __shared__ int bx[256], by[256];
+    __shared__ unsigned long long acc_m[4], rej_m[4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, W = a.W, K = a.K;
+    const size_t plane = (size_t)a.H * (size_t)W;
+    const int gcells = a.gw * a.gh;
+    for (int f = blockIdx.x; f < a.F; f += gridDim.x) {
+        const unsigned n = a.ncand[f];
+        const unsigned long long *keys = a.keys + (size_t)f * plane;
+        int *grid = a.use_grid ? a.grid + (size_t)f * gcells * 4 : nullptr;
+        float2 *xy = reinterpret_cast<float2 *>(a.xy) + (size_t)f * K;
+        float *sc = a.score + (size_t)f * K;
+        __syncthreads();   // the previous frame's LDS is no longer read
+        if (grid) {
+            for (int i = tid; i < gcells * 4; i += 256) grid[i] = -1;
+            __threadfence();
+        }
+        if (tid == 0) s_lo = 0;
+        int accepted = 0;   // uniform
+        __syncthreads();
+        while (accepted < K) {
+            // ---- the slab [lo, hi): a radix descent over the keys >= lo
+            if (tid == 0) { s_prefix = 0; s_shift = 64; s_taken = 0; s_done = 0; }
+            __syncthreads();
+            const unsigned long long lo = s_lo;
+            while (!s_done) {
+                const int shift = s_shift - 8;
+                const unsigned long long prefix = s_prefix;
+                hist[tid] = 0;
+                __syncthreads();
+                for (unsigned i = tid; i < n; i += 256) {
+                    const unsigned long long k = keys[i];
+                    if (k >= lo && (shift == 56 || (k >> (shift + 8)) == prefix)) atomicAdd(&hist[(unsigned)(k >> shift) & 255u], 1u);
+                }
+                __syncthreads();
+                if (tid == 0) {
+                    unsigned taken = s_taken;
+                    int b = 0;
+                    for (; b < 256; b++) {
+                        if (taken + hist[b] > (unsigned)kSelCap) break;
+                        taken += hist[b];
+                    }
+                    s_taken = taken;
+                    if (b == 256) {   // every key under the prefix fits
+                        const unsigned long long up = prefix + 1;
+                        s_hi = (shift == 56 || (up >> (64 - shift - 8)) != 0) ? ~0ull : up << (shift + 8);
+                        s_done = 1;
+                    } else {
+                        const unsigned long long p = (prefix << 8) | (unsigned)b;
+                        s_prefix = p;
+                        s_shift = shift;
+                        if (taken >= (unsigned)kSelCap / 2 || shift == 0) {
+                            s_hi = p << shift;
+                            s_done = 1;
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+            const unsigned cap = s_taken;
+            const unsigned long long hi = s_hi;
+            if (cap == 0) break;   // the list is exhausted
+            // ---- gather and sort the slab (never beyond the count of the descent: every slab index stays in LDS)
+            if (tid == 0) s_fill = 0;
+            __syncthreads();
+            for (unsigned i = tid; i < n; i += 256) {
+                const unsigned long long k = keys[i];
+                if (k >= lo && k < hi) {
+                    const unsigned j = atomicAdd(&s_fill, 1u);
+                    if (j < cap) slab[j] = k;
+                }
+            }
+            __syncthreads();
+            const unsigned taken = min(s_fill, cap);
+            unsigned P = 256;
+            while (P < taken) P <<= 1;
+            for (unsigned i = taken + tid; i < P; i += 256) slab[i] = ~0ull;
+            __syncthreads();
+            for (unsigned k = 2; k <= P; k <<= 1)
+                for (unsigned j = k >> 1; j > 0; j >>= 1) {
+                    for (unsigned i = tid; i < P; i += 256) {
+                        const unsigned l = i ^ j;
+                        if (l > i) {
+                            const unsigned long long u = slab[i], v = slab[l];
+                            if ((u > v) == ((i & k) == 0)) {
+                                slab[i] = v;
+                                slab[l] = u;
+                            }
+                        }
+                    }
+                    __syncthreads();
+                }
+            // ---- resolve the slab in batches of 256, in priority order
+            for (unsigned b0 = 0; b0 < taken && accepted < K; b0 += 256) {
+                const unsigned i = b0 + tid;
+                const unsigned long long key = i < taken ? slab[i] : 0ull;
+                const bool valid = i < taken && (unsigned)key < (unsigned)plane;   // a pixel of the frame
+                const int idx = (int)(unsigned)key, y = idx / W, x = idx - y * W;
+                bool alive = valid;
+                if (grid && alive) {
+                    const int cx = x / a.cell, cy = y / a.cell;
+                    for (int gy = max(cy - 1, 0); gy <= min(cy + 1, a.gh - 1); gy++)
+                        for (int gx = max(cx - 1, 0); gx <= min(cx + 1, a.gw - 1); gx++)
+                            for (int sl = 0; sl < 4; sl++) {
+                                const int p = __hip_atomic_load(grid + ((size_t)gy * a.gw + gx) * 4 + sl, __ATOMIC_RELAXED,
+                                                                __HIP_MEMORY_SCOPE_AGENT);
+                                if (p >= 0) {
+                                    const long long dy = p / W - y, dx = p % W - x;
+                                    if ((double)(dx * dx + dy * dy) < a.md2) alive = false;
+                                }
+                            }
+                }
+                bool acc = alive;
+                if (grid) {
+                    bx[tid] = x;
+                    by[tid] = y;
+                    const unsigned long long am = __ballot(alive);
+                    if (lane == 0) { acc_m[wv] = 0; rej_m[wv] = ~am; }
+                    __syncthreads();
+                    unsigned long long conf[4] = {0, 0, 0, 0};
+                    if (alive)
+                        for (int j = 0; j < tid; j++) {
+                            if (!((rej_m[j >> 6] >> (j & 63)) & 1)) {
+                                const long long dy = by[j] - y, dx = bx[j] - x;
+                                if ((double)(dx * dx + dy * dy) < a.md2) conf[j >> 6] |= 1ull << (j & 63);
+                            }
+                        }
+                    int state = alive ? 0 : 2;   // 0 open, 1 accepted, 2 rejected
+                    for (;;) {
+                        bool hit = false, clear = true;
+                        for (int w = 0; w < 4; w++) {
+                            hit |= (conf[w] & acc_m[w]) != 0;
+                            clear &= (conf[w] & ~rej_m[w]) == 0;
+                        }
+                        const int ns = state ? state : (hit ? 2 : (clear ? 1 : 0));
+                        const unsigned long long na = __ballot(ns == 1 && state == 0), nr = __ballot(ns == 2 && state == 0);
+                        state = ns;
+                        __syncthreads();   // every wave has read the masks
+                        if (lane == 0) { acc_m[wv] |= na; rej_m[wv] |= nr; }
+                        if (!__syncthreads_or(state == 0)) break;
+                    }
+                    acc = state == 1;
+                }
+                const unsigned long long am = __ballot(acc);
+                if (lane == 0) acc_m[wv] = am;
+                __syncthreads();
+                int below = __popcll(am & ((1ull << lane) - 1)), total = 0;
+                for (int w = 0; w < 4; w++) {
+                    const int c = __popcll(acc_m[w]);
+                    if (w < wv) below += c;
+                    total += c;
+                }
+                const int slot = accepted + below;
+                if (acc && slot < K) {
+                    xy[slot] = make_float2((float)x, (float)y);
+                    sc[slot] = __uint_as_float(~(unsigned)(key >> 32));
+                    if (grid) {
+                        int *cellp = grid + ((size_t)(y / a.cell) * a.gw + x / a.cell) * 4;
+                        for (int sl = 0; sl < 4; sl++)
+                            if (atomicCAS(cellp + sl, -1, idx) == -1) break;
+                    }
+                }
+                accepted = min(K, accepted + total);
+                __threadfence();
+                __syncthreads();
+            }
+            if (tid == 0) s_lo = hi;
+            __syncthreads();
+            if (hi == ~0ull) break;
+        }
+        const float nan = __builtin_nanf("");
+        for (int i = accepted + tid; i < K; i += 256) {
+            xy[i] = make_float2(nan, nan);
+            sc[i] = 0.0f;
+        }
+        if (tid == 0) a.count[f] = accepted;
+    }
+}
+
 }  // namespace oflk

@@ -79,6 +79,15 @@ SIGNATURES = {
     "oflk_track_points_host": (ctypes.c_int, [_f32p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
     "oflk_pyramidal_sequence_tracks": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 2 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
     "oflk_pyramidal_sequence_tracks_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 2 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
+    "oflk_corner_score": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_vp, _vp]),
+    "oflk_corner_score_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 4 + [_f32p]),
+    "oflk_corner_score_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_f32p]),
+    "oflk_good_features_workspace": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    "oflk_good_features": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [ctypes.c_float] * 2 + [ctypes.c_int, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp]),
+    "oflk_good_features_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 4 + [ctypes.c_float] * 2 + [ctypes.c_int, _i32p, _f32p, _f32p]),
+    "oflk_good_features_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [ctypes.c_float] * 2 + [ctypes.c_int, _i32p, _f32p, _f32p]),
+    "oflk_pyramidal_sequence_klt": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 4 + [ctypes.c_int, _i32p, _f32p, _f32p, _f32p, _vp]),
+    "oflk_pyramidal_sequence_klt_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 4 + [ctypes.c_int, _i32p, _f32p, _f32p, _f32p, _vp]),
     "oflk_shard_range": (None, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, _i32p]),
     "oflk_single_scale_fp16": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, _f32p, _f32p]),
     "oflk_rtl_stream_length": (ctypes.c_long, [ctypes.c_int, ctypes.c_int]),
@@ -382,3 +391,67 @@ def track_points(d_uf: int, d_vf: int, d_ub: int, d_vb: int, B: int, H: int, W: 
     [B+1][N] uint8 (row 0 is read for queries of an earlier frame: the previous call's last row)."""
     check(lib().oflk_track_points(d_uf, d_vf, d_ub, d_vb, int(B), int(H), int(W), float(alpha), float(beta), int(t0),
                                   d_qt or None, d_qxy, int(N), d_tracks, d_visible, stream))
+
+
+CORNER_WINDOWS = (3, 5, 7, 9, 11)
+
+
+def check_feature_params(max_corners, quality_level: float, min_distance: float, window_size: int) -> Tuple[int, float, float, int]:
+    """The detection parameters as the C ABI takes them: (K, q, md, window) with q, md float32; ValueError unless K >= 1,
+    q in [0, 1], md finite and >= 0 and the window odd in [3, 11].  Nothing here touches a device."""
+    if isinstance(max_corners, bool) or int(max_corners) != max_corners or int(max_corners) < 1:
+        raise ValueError(f"max_corners must be an integer >= 1, got {max_corners!r}")
+    with np.errstate(over="ignore"):
+        q, md = np.float32(quality_level), np.float32(min_distance)
+    if not (np.isfinite(q) and 0 <= q <= 1):
+        raise ValueError(f"quality_level must be in [0, 1], got {quality_level!r}")
+    if not (np.isfinite(md) and md >= 0):
+        raise ValueError(f"min_distance must be finite and >= 0, got {min_distance!r}")
+    if window_size not in CORNER_WINDOWS:
+        raise ValueError(f"window_size must be one of {CORNER_WINDOWS}, got {window_size!r}")
+    return int(max_corners), float(q), float(md), int(window_size)
+
+
+def as_frames(frames) -> Tuple[np.ndarray, bool]:
+    """One frame (H, W) or a batch (F, H, W) (an array or a sequence of 2-D arrays) as a contiguous (F, H, W) array: uint8
+    when every frame is uint8 (True is returned), float32 otherwise.  ValueError for anything else; no device call."""
+    if isinstance(frames, np.ndarray) and frames.ndim == 2:
+        frames = frames[None]
+    if isinstance(frames, np.ndarray):
+        if frames.ndim != 3:
+            raise ValueError(f"expected an (H, W) frame or an (F, H, W) batch, got shape {frames.shape}")
+        items = list(frames)
+    else:
+        items = [np.asarray(f) for f in frames]
+        if any(f.ndim != 2 for f in items) or len({f.shape for f in items}) > 1:
+            raise ValueError("expected 2-D frames of one shape")
+    if not items or items[0].shape[0] < 1 or items[0].shape[1] < 1:
+        raise ValueError("no frames, or empty frames")
+    u8 = all(f.dtype == np.uint8 for f in items)
+    arr = np.ascontiguousarray(frames if isinstance(frames, np.ndarray) else np.stack(items), dtype=np.uint8 if u8 else np.float32)
+    return arr, u8
+
+
+def corner_score(d_frames: int, F: int, H: int, W: int, d_score: int, window_size: int = 5, u8: bool = False,
+                 stream: int = 0) -> None:
+    """oflk_corner_score on device pointers: frames [F][H][W] (float32, or uint8 with u8) -> d_score [F][H][W] float32."""
+    check(lib().oflk_corner_score(d_frames, int(bool(u8)), int(F), int(H), int(W), int(window_size), d_score, stream))
+
+
+def good_features_workspace(F: int, H: int, W: int, window_size: int = 5, min_distance: float = 10.0,
+                            max_corners: int = 100) -> int:
+    """bytes of oflk_good_features' workspace for this shape"""
+    n = ctypes.c_size_t(0)
+    check(lib().oflk_good_features_workspace(int(F), int(H), int(W), int(window_size), float(min_distance), int(max_corners),
+                                             ctypes.byref(n)))
+    return int(n.value)
+
+
+def good_features(d_frames: int, F: int, H: int, W: int, d_workspace: int, workspace_bytes: int, d_count: int, d_xy: int,
+                  d_score: int, max_corners: int, quality_level: float = 0.01, min_distance: float = 10.0,
+                  window_size: int = 5, u8: bool = False, stream: int = 0) -> None:
+    """oflk_good_features on device pointers: frames [F][H][W] -> d_count [F] int32, d_xy [F][K][2] float32 (x, y),
+    d_score [F][K] float32; d_workspace of at least good_features_workspace bytes."""
+    check(lib().oflk_good_features(d_frames, int(bool(u8)), int(F), int(H), int(W), int(window_size), float(quality_level),
+                                   float(min_distance), int(max_corners), d_workspace, int(workspace_bytes), d_count, d_xy,
+                                   d_score, stream))

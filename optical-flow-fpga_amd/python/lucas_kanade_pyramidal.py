@@ -284,6 +284,36 @@ def lucas_kanade_pyramidal_sequence_tracks(frames, queries, num_levels: int = 3,
     return SequenceTracks(tracks, visible.astype(bool))
 
 
+class SequenceKLT(NamedTuple):
+    """Result of lucas_kanade_pyramidal_sequence_klt: n features of frame 0 and their tracks (row t is frame t)."""
+    xy: np.ndarray        # (n, 2) float32 (x, y) in acceptance order
+    tracks: np.ndarray    # (T, n, 2) float32 (x, y); NaN where not visible
+    visible: np.ndarray   # (T, n) bool
+
+
+def lucas_kanade_pyramidal_sequence_klt(frames, max_corners: int, quality_level: float = 0.01, min_distance: float = 10.0,
+                                        num_levels: int = 3, window_size: int = 5, num_iterations: int = 3,
+                                        alpha: float = 0.01, beta: float = 0.5) -> SequenceKLT:
+    """Detect, then track (KLT): Shi-Tomasi features of frame 0 (lucas_kanade_core.good_features_to_track, with the LK
+    window_size as the detection window, so it must be odd in [3, 11]) followed by lucas_kanade_pyramidal_sequence_tracks
+    on them.  The features are born on the device; only they and the tracks come back.  frames: as
+    lucas_kanade_pyramidal_sequence_fb (all uint8: the uint8 path).
+    """
+    a, b = _oflk.check_fb_params(alpha, beta)
+    K, q, md, win = _oflk.check_feature_params(max_corners, quality_level, min_distance, window_size)
+    arr, u8 = _oflk.as_sequence(frames)
+    T, H, W = arr.shape
+    count = np.zeros(1, np.int32)
+    xy, score = np.empty((K, 2), np.float32), np.empty(K, np.float32)
+    tracks, visible = np.empty((T, K, 2), np.float32), np.empty((T, K), np.uint8)
+    fn = _oflk.lib().oflk_pyramidal_sequence_klt_u8 if u8 else _oflk.lib().oflk_pyramidal_sequence_klt
+    src = arr.ctypes.data if u8 else _oflk.ptr(arr)
+    _oflk.check(fn(src, T, H, W, int(num_levels), win, int(num_iterations), a, b, q, md, K, count.ctypes.data_as(_oflk._i32p),
+                   _oflk.ptr(xy), _oflk.ptr(score), _oflk.ptr(tracks), visible.ctypes.data))
+    n = int(count[0])
+    return SequenceKLT(xy[:n], tracks[:, :n], visible[:, :n].astype(bool))
+
+
 def _dump_levels(key, shapes, u, v) -> None:
     """The reference's per-level PNG side effect (:226), after the call, best-effort."""
     num_levels = key[3]

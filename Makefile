@@ -13,7 +13,10 @@ test-gpu:         ## on an MI355X: HIP vs oracle / reference digests
 bench:            ## one JSON line (128 pairs of 1080p per step, 3-level pyramidal)
 	$(PY) bench.py
 
+bench-full:       ## the same line with every other leg (per-kernel times, arithmetic modes, CPU baseline, parity)
+	$(PY) bench.py --full
+
 profiles:         ## regenerate profiles/<tag>_* on the GPU box
 	bash tools/profiles_r04.sh
 
-.PHONY: build test test-gpu bench profiles
+.PHONY: build test test-gpu bench bench-full profiles

@@ -21,12 +21,24 @@ Frame pairs are independent units: ranks share nothing on the data path; the onl
 the barrier of the fence, the MAX of the elapsed time and one SUM of per-rank result totals
 (RCCL, backend "nccl"), all outside or around the timed region (oflk_dist.run_timed).
 
-Extra objects in the JSON line:
+A plain run does what the headline figure needs and no more: set up, warm up, time the steps, write
+--dump-outputs, print the line.  Besides the headline it carries only what the timed region itself
+yields (roofline, whole_call, job_stats).  Everything that takes work of its own runs with ``--full``
+(rank 0; the --no-* switches still drop single legs there); in a plain run those objects are null.
+``--multi inproc`` has no such legs: --full changes nothing there.
+
+Objects in the JSON line beside the headline:
   roofline      dominant kernel (fused LK iteration at the finest level): algorithmic bytes per
                 launch / average launch duration from HIP events on the launch stream during the
                 timed region; plus the instruction-side bounds of that kernel (valu_pipe,
-                issue_cadence: tools/issue_bounds.py) when profiles/ holds them for this workload
+                issue_cadence: tools/issue_bounds.py) when profiles/ holds them for this workload.
+                Its HBM traffic comes from profiles/, or with --full from rocprofv3 child passes of this run
+  whole_call    algorithmic bytes of the whole call over the step time
+--full only:
   roofline_pyr  the same for the fused pyramid kernel (fp64-bound by SciPy's arithmetic)
+  kernels       per-kernel times from a few extra steps with every launch bracketed
+  contracted_arithmetic, tolerance_mode  the opt-in arithmetic modes, timed and graded (never `value`)
+  single_scale_batched, one_pair_per_call  BASELINE configs[1] batched, and one pair per call
   cpu_baseline  the CPU oracle (a bit-exact port of the reference's NumPy/SciPy arithmetic) timed on
                 this host on a bounded sample (N = 1 only)
   epe_vs_reference  the parity half of the metric: the 13 committed verification patterns through the HIP
@@ -86,7 +98,7 @@ def profile_file(pattern: str, pairs: int, shape, any_pairs: bool = False) -> di
 
 
 def live_traffic(pairs: int, shape, timeout_s: int = 240) -> dict | None:
-    """HBM bytes per launch of the dominant kernel, measured during this bench run: two child processes run the same
+    """HBM bytes per launch of the dominant kernel, measured during this bench run (--full): two child processes run the same
     workload (tools/kbench.py: same plan, same synthetic frames) under `rocprofv3 --kernel-trace --pmc FETCH_SIZE` and
     `... --pmc WRITE_SIZE` (separate passes, as /opt/skills/guides/MI355X_MICROARCH.md prescribes; counters in units of
     1024 B, FETCH_SIZE doubled on gfx950).  Returns None when rocprofv3 is missing, when this process is itself being
@@ -339,18 +351,22 @@ def main() -> None:
     ap.add_argument("--levels", type=int, default=3)
     ap.add_argument("--window", type=int, default=5)
     ap.add_argument("--iters", type=int, default=3)
-    ap.add_argument("--cpu-sample-pairs", type=int, default=16, help="1080p pairs the CPU oracle is timed on (~10 s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-one-pair", action="store_true", help="skip the informational batch-of-1 timing")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, also run everything else the line can report: per-kernel times, the "
+                         "contracted and tolerant arithmetic, the single-scale batch, one pair per call, the CPU baseline, "
+                         "the 13-pattern parity check and the rocprofv3 traffic passes (the --no-* switches drop single legs)")
+    ap.add_argument("--cpu-sample-pairs", type=int, default=16, help="1080p pairs the CPU oracle is timed on (~10 s; --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-one-pair", action="store_true", help="--full: skip the single-scale batch and the batch-of-1 timing")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not run the two rocprofv3 --pmc child passes; take roofline.traffic from profiles/")
+                    help="--full: do not run the rocprofv3 --pmc child passes; take roofline.traffic from profiles/")
     # rehearsal switches (a one-GPU box cannot host two RCCL ranks): gloo for the three small collectives, and
     # every rank on one device -- exercises the N > 1 code path end to end; the numbers of such a run mean nothing
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--force-device", type=int, default=None, help="use this GPU on every rank (rehearsal only)")
     ap.add_argument("--multi", default="ranks", choices=["ranks", "inproc"],
                     help="N > 1: one process per GPU (default) or ONE process with a plan per GPU")
-    ap.add_argument("--no-parity", action="store_true", help="skip the 13-pattern EPE check after the timed region")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the 13-pattern EPE check after the timed region")
     ap.add_argument("--gather", action="store_true",
                     help="after the timed region: gather the flow shards of all ranks to rank 0 through the process group "
                          "(RCCL on device tensors) and report gather_ms / gather_GBs next to, never inside, `value`")
@@ -421,12 +437,14 @@ def main() -> None:
         files = dump_outputs(args.dump_outputs, {"u": [u], "v": [v]})
         print(f"bench.py: wrote {', '.join(files)} to {args.dump_outputs}", file=sys.stderr)
     dom = plan.kernel_times().get("lk_iter_finest", {"total_ms": 0.0, "launches": 0})
-    # informational per-kernel breakdown from a few extra, untimed steps with every launch bracketed
-    plan.set_profiling(1)
-    for _ in range(min(args.steps, 5)):
-        step()
-    torch.cuda.synchronize()
-    ktimes = plan.kernel_times()
+    ktimes = {}
+    if args.full:
+        # informational per-kernel breakdown from a few extra, untimed steps with every launch bracketed
+        plan.set_profiling(1)
+        for _ in range(min(args.steps, 5)):
+            step()
+        torch.cuda.synchronize()
+        ktimes = plan.kernel_times()
     plan.set_profiling(0)
     log, runs = plan.read_log(stream)
     uncertain = int(plan.read_uncertain(stream).astype(bool).sum())
@@ -452,7 +470,7 @@ def main() -> None:
         achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9
         tr = profile_file("hbm_traffic", B, (H, W))
         live = None
-        if world == 1 and not args.no_live_traffic and args.levels == 3 and args.window == 5 and args.iters == 3:
+        if args.full and world == 1 and not args.no_live_traffic and args.levels == 3 and args.window == 5 and args.iters == 3:
             live = live_traffic(B, (H, W))
         ib = profile_file("issue_bounds", B, (H, W), any_pairs=True)
         roofline = {"bound": "hbm", "binding_pipe": "valu", "timed_with_profiling": 2,
@@ -464,7 +482,9 @@ def main() -> None:
                                        "under rocprofv3 --kernel-trace --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes, "
                                        f"FETCH_SIZE x2 on gfx950); launches averaged {live['launches_averaged']}") if live else
                                       ((f"profiles/{tr['_file']}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes "
-                                        f"over this command (tools/measure_traffic.sh); the live passes of this run were skipped or failed") if tr else None),
+                                        f"over this command (tools/measure_traffic.sh); "
+                                        + ("the live passes of this run were skipped or failed" if args.full else "live passes run with --full only"))
+                                       if tr else None),
                     "avg_launch_us": round(avg_ms * 1e3, 2), "algorithmic_bytes_per_launch": bytes_per_launch,
                     "hbm_floor_us": round(bytes_per_launch / HBM_PEAK_GBS / 1e3, 1)}
         if ib:
@@ -518,12 +538,12 @@ def main() -> None:
              "frac_of_peak": round(step_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4)}
     kernels = {k: {"avg_us": round(1e3 * t["total_ms"] / t["launches"], 2), "launches": t["launches"],
                    "share": round(t["total_ms"] / max(sum(x["total_ms"] for x in ktimes.values()), 1e-12), 4)}
-               for k, t in ktimes.items() if t["launches"]}
+               for k, t in ktimes.items() if t["launches"]} if args.full else None
 
     # ---- the opt-in contracted arithmetic (fused multiply-adds in the Gaussian pyramid; include/oflk.h): informational,
     # never `value` -- what it buys on this workload and how many flow values it changes against the exact result ----
     contracted = None
-    if rank == 0 and world == 1 and L > 1:
+    if args.full and rank == 0 and world == 1 and L > 1:
         u_ex, v_ex = u.clone(), v.clone()
         plan.set_arithmetic(1)
         for _ in range(2):
@@ -551,7 +571,7 @@ def main() -> None:
     # flows (tests/golden/dense_reference_flows.npz, made by importing it): the 13 verification patterns and pair 0 of this
     # workload; the bar is the north star's mean endpoint error <= 1e-4 px per field ----
     tolerant = None
-    if rank == 0 and world == 1 and L > 1 and args.window in (4, 5):
+    if args.full and rank == 0 and world == 1 and L > 1 and args.window in (4, 5):
         plan.set_arithmetic(2)
         for _ in range(2):
             step()
@@ -627,7 +647,7 @@ def main() -> None:
     # ---- BASELINE configs[1], batched: 256 pairs of 640x480, single-scale 5x5 (the streaming kernel: exact on these 8-bit
     # frames, doubtful tiles redone in NumPy's order inside the call); informational, 16 B/px algorithmic ----
     single = None
-    if rank == 0 and world == 1 and not args.no_one_pair:
+    if args.full and rank == 0 and world == 1 and not args.no_one_pair:
         try:
             hs = [synth_pair(480, 640, pair_index=i) for i in range(2)]
             sp = torch.stack([torch.from_numpy(hs[i % 2][0]) for i in range(256)]).to(dev)
@@ -654,7 +674,7 @@ def main() -> None:
 
     # ---- one pair per call (BASELINE config 3 read literally): latency-bound, informational ----
     one_pair = None
-    if rank == 0 and world == 1 and not args.no_one_pair:
+    if args.full and rank == 0 and world == 1 and not args.no_one_pair:
         plan1 = _oflk.Plan(local_rank, 1, H, W, L, args.window, K)
         for _ in range(5):
             plan1.pyramidal(prev.data_ptr(), curr.data_ptr(), u.data_ptr(), v.data_ptr(), stream)
@@ -671,7 +691,7 @@ def main() -> None:
 
     # ---- CPU baseline: the oracle on this host's cores (rank 0, N = 1) --------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, str(ROOT / "oracle"))
         import oflk_oracle as O  # checker/baseline only; never on the measured path
 
@@ -707,7 +727,7 @@ def main() -> None:
             pass
 
     parity = None
-    if rank == 0 and not args.no_parity:
+    if args.full and rank == 0 and not args.no_parity:
         if local_rank != 0:
             _oflk.check(_oflk.lib().oflk_set_device(local_rank))
         parity = epe_vs_reference()

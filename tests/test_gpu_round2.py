@@ -599,14 +599,14 @@ def test_bench_launches_its_own_ranks():
     root = Path(__file__).resolve().parents[1]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--backend", "gloo",
-                          "--force-device", "0", "--height", "120", "--width", "160", "--pairs", "3", "--no-cpu-baseline",
+                          "--force-device", "0", "--height", "120", "--width", "160", "--pairs", "3", "--full", "--no-cpu-baseline",
                           "--no-one-pair"], capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), out.stdout[-2000:]
     j = json.loads(lines[0])
     assert j["n_gpus"] == 2 and j["config"]["pairs_per_step_job"] == 6 and "REHEARSAL" in j["data"]
-    # the parity half of the metric rides in the same line: the reference's 26 flow fields, value for value
+    # the parity half of the metric rides in the same line (--full): the reference's 26 flow fields, value for value
     e = j["epe_vs_reference"]
     assert e["patterns"] == 13 and e["digests_equal"] == 26 and e["max_mean_epe"] == 0.0 and e["iteration_counts_equal"] == 13
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round-4 profiles (run on the GPU box from the repo root; ~10 minutes):  bash tools/profiles_r04.sh
-#   r04_bench.json                         the contract line (exact value + tolerance_mode + single-scale / gather extras)
+#   r04_bench.json                         the contract line with --full (exact value + tolerance_mode + single-scale / gather extras)
 #   r04_rocprofv3_kernel_stats.csv         rocprofv3 --kernel-trace --stats of the bench command
 #   r04_rocprofv3_dominant_kernel.json     finest-level launches of the exact iteration kernel k_lkw<2, ITER>
 #   r04_rocprofv3_tolerant_kernel.json     ... of the streaming kernel k_lks<ITER> (tolerance_mode's dominant kernel)
@@ -15,7 +15,7 @@ make -C optical-flow-fpga_amd/csrc asm > gpurun_out/asm_$TAG.log 2>&1 || true   
 S=$R/gpurun_out/stats_$TAG
 rm -rf $S && mkdir -p $S
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $S -- python3 $R/bench.py --no-cpu-baseline --no-one-pair --no-live-traffic > $S/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $S -- python3 $R/bench.py --full --no-cpu-baseline --no-one-pair --no-live-traffic > $S/bench.log 2>&1
 cd $R
 grep -h '^{' $S/bench.log | tail -1 > profiles/${TAG}_bench_under_rocprof.json
 python3 tools/dominant_from_trace.py $S profiles/${TAG}_rocprofv3_dominant_kernel.json
@@ -76,10 +76,10 @@ echo "== counters done"
 python3 -m pytest tests/test_gpu_round4.py -q -k "within_tolerance" > gpurun_out/tol_tests_$TAG.log 2>&1 && cp gpurun_out/tolerant_epe.json profiles/${TAG}_tolerant_epe.json || true
 python3 tools/host_latency.py > profiles/${TAG}_host_latency.txt 2>&1 && python3 tools/host_latency.py batch >> profiles/${TAG}_host_latency.txt 2>&1 || true
 python3 tools/measure_configs.py profiles/${TAG}_configs.json > gpurun_out/cfg_$TAG.log 2>&1 || tail -3 gpurun_out/cfg_$TAG.log
-python3 bench.py --config 4k64 --steps 5 --warmup 1 --no-one-pair > gpurun_out/bench_4k64_$TAG.log 2>&1 || tail -3 gpurun_out/bench_4k64_$TAG.log
-grep -h '^{' gpurun_out/bench_4k64_$TAG.log | tail -1 > profiles/${TAG}_bench_4k64_1gpu.json
+python3 bench.py --full --config 4k64 --steps 5 --warmup 1 --no-one-pair > $S/bench_4k64.log 2>&1 || tail -3 $S/bench_4k64.log
+grep -h '^{' $S/bench_4k64.log | tail -1 > profiles/${TAG}_bench_4k64_1gpu.json
 echo "== configs done"
-python3 bench.py > gpurun_out/bench_$TAG.log 2>&1
-grep -h '^{' gpurun_out/bench_$TAG.log | tail -1 > profiles/${TAG}_bench.json
+python3 bench.py --full > $S/bench_line.log 2>&1
+grep -h '^{' $S/bench_line.log | tail -1 > profiles/${TAG}_bench.json
 python3 -c "import json; b=json.load(open('profiles/${TAG}_bench.json')); print(b['value'], b['tolerance_mode']['value'], b['roofline']['frac'], b['tolerance_mode']['roofline'])"
 rm -rf gpurun_out/profiles_$TAG && mkdir -p gpurun_out/profiles_$TAG && cp -r profiles/${TAG}_* gpurun_out/profiles_$TAG/

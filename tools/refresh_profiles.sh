@@ -1,7 +1,7 @@
 #!/bin/bash
 # Regenerate everything under profiles/ for one tag (run on the GPU box from the repo root):
 #   bash tools/refresh_profiles.sh r02
-# 1. bench.py line (default workload)            -> profiles/<tag>_bench.json
+# 1. bench.py --full line (default workload)     -> profiles/<tag>_bench.json
 # 2. rocprofv3 --kernel-trace --stats of the same -> profiles/<tag>_rocprofv3_kernel_stats.csv
 #                                                    profiles/<tag>_bench_under_rocprof.json
 #                                                    profiles/<tag>_rocprofv3_dominant_kernel.json (finest-level launches only)
@@ -14,7 +14,7 @@ mkdir -p gpurun_out profiles/${TAG}_pmc
 S=$R/gpurun_out/stats_$TAG
 rm -rf $S && mkdir -p $S
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $S -- python3 $R/bench.py --no-cpu-baseline --no-one-pair --no-live-traffic > $S/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $S -- python3 $R/bench.py --full --no-cpu-baseline --no-one-pair --no-live-traffic > $S/bench.log 2>&1
 cd $R
 grep -h '^{' $S/bench.log | tail -1 > profiles/${TAG}_bench_under_rocprof.json
 python3 tools/dominant_from_trace.py $S profiles/${TAG}_rocprofv3_dominant_kernel.json
@@ -66,11 +66,11 @@ python3 -m pytest tests/test_gpu_round3.py -q -k contracted > gpurun_out/contrac
 python3 tools/host_latency.py > profiles/${TAG}_host_latency.txt 2>&1 && python3 tools/host_latency.py batch >> profiles/${TAG}_host_latency.txt 2>&1 || true
 # 7. every BASELINE config that fits one GPU, and BASELINE configs[3] as one job on this GPU
 python3 tools/measure_configs.py profiles/${TAG}_configs.json > gpurun_out/cfg_$TAG.log 2>&1 || tail -3 gpurun_out/cfg_$TAG.log
-python3 bench.py --config 4k64 --steps 5 --warmup 1 --no-one-pair > gpurun_out/bench_4k64_$TAG.log 2>&1 || tail -3 gpurun_out/bench_4k64_$TAG.log
-grep -h '^{' gpurun_out/bench_4k64_$TAG.log | tail -1 > profiles/${TAG}_bench_4k64_1gpu.json
+python3 bench.py --full --config 4k64 --steps 5 --warmup 1 --no-one-pair > $S/bench_4k64.log 2>&1 || tail -3 $S/bench_4k64.log
+grep -h '^{' $S/bench_4k64.log | tail -1 > profiles/${TAG}_bench_4k64_1gpu.json
 # the bench line proper, last so that it sees the fresh traffic file
-python3 bench.py > gpurun_out/bench_$TAG.log 2>&1
-grep -h '^{' gpurun_out/bench_$TAG.log | tail -1 > profiles/${TAG}_bench.json
+python3 bench.py --full > $S/bench_line.log 2>&1
+grep -h '^{' $S/bench_line.log | tail -1 > profiles/${TAG}_bench.json
 cat profiles/${TAG}_bench.json
 python3 tools/profiles_summary.py $TAG || true
 # gpurun merges only gpurun_out/ back to the build container: leave a copy of everything there

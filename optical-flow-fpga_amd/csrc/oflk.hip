@@ -1583,29 +1583,77 @@ struct HostCtx {
     unsigned char *u8[2] = {nullptr, nullptr};              // device uint8 frames
     size_t u8_elems = 0;
     // chunked host calls (run_batch_chunked): two slots of chunk-sized frames in / flow out, three streams
-    void *ring_in[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [slot][prev, curr], PIXELS
-    float *ring_out[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // [slot][u, v]
+    unsigned char *ring_in[4] = {nullptr, nullptr, nullptr, nullptr};   // [2 * slot + (prev, curr)], PIXELS
+    float *ring_out[4] = {nullptr, nullptr, nullptr, nullptr};          // [2 * slot + (u, v)]
     size_t ring_in_bytes = 0, ring_out_elems = 0;
     hipStream_t s_in = nullptr, s_comp = nullptr, s_out = nullptr;
 };
 HostCtx g_ctx[kMaxDevices];
 
-// lock the context of `dev` and make the device current for the calling thread
-int acquire(int dev, HostCtx **out, std::unique_lock<std::mutex> &lk)
+// One host-pointer call: the lock on the context of its device, the device made current for the calling thread, and the
+// call's own device buffers, freed before the lock is released.  Everything is staged on the null stream; sync() is the
+// last step of a call, so that the caller's arrays are complete when it returns.
+class HostCall {
+  public:
+    HostCtx *c = nullptr;
+    int dev = -1;
+
+    int begin(int device = g_device.load())
+    {
+        if (device < 0 || device >= kMaxDevices) return fail(OFLK_ERR_INVALID, "device %d out of range", device);
+        lk = std::unique_lock<std::mutex>(g_ctx[device].mu);
+        int rc = ensure_device(device);
+        if (rc) return rc;
+        c = &g_ctx[device];
+        dev = device;
+        return OFLK_OK;
+    }
+    // a buffer of n elements for this call; none (NULL) when `want` is false, for an output the caller did not ask for
+    template <typename T>
+    int alloc(T **d, size_t n, bool want = true)
+    {
+        *d = nullptr;
+        return want ? ar.get(d, n) : OFLK_OK;
+    }
+    template <typename T>
+    int upload(T **d, const T *host, size_t n)
+    {
+        int rc = ar.get(d, n);
+        return rc ? rc : to_device(*d, host, n);
+    }
+    template <typename T>
+    int to_device(T *d, const T *host, size_t n)
+    {
+        HIP_TRY(hipMemcpyAsync(d, host, n * sizeof(T), hipMemcpyHostToDevice, nullptr));
+        return OFLK_OK;
+    }
+    template <typename T>
+    int to_host(T *host, const T *d, size_t n)
+    {
+        HIP_TRY(hipMemcpyAsync(host, d, n * sizeof(T), hipMemcpyDeviceToHost, nullptr));
+        return OFLK_OK;
+    }
+    int sync()
+    {
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return OFLK_OK;
+    }
+
+  private:
+    std::unique_lock<std::mutex> lk;   // declared before ar: destroyed after it
+    Arena ar;
+};
+
+bool has_shape(const oflk_plan *q, int B, int H, int W, int L, int win, int K)
 {
-    if (dev < 0 || dev >= kMaxDevices) return fail(OFLK_ERR_INVALID, "device %d out of range", dev);
-    lk = std::unique_lock<std::mutex>(g_ctx[dev].mu);
-    int rc = ensure_device(dev);
-    if (rc) return rc;
-    *out = &g_ctx[dev];
-    return OFLK_OK;
+    return q->B == B && q->H == H && q->W == W && q->L == L && q->win == win && q->K == K;
 }
 
 int host_plan(HostCtx &c, int dev, int B, int H, int W, int L, int win, int K, oflk_plan **out)
 {
     for (size_t i = 0; i < c.plans.size(); i++) {
         oflk_plan *q = c.plans[i];
-        if (q->B == B && q->H == H && q->W == W && q->L == L && q->win == win && q->K == K) {
+        if (has_shape(q, B, H, W, L, win, K)) {
             c.plans.erase(c.plans.begin() + (long)i);
             c.plans.insert(c.plans.begin(), q);
             q->arith = g_host_arith.load();
@@ -1632,37 +1680,34 @@ int host_plan(HostCtx &c, int dev, int B, int H, int W, int L, int win, int K, o
     return OFLK_OK;
 }
 
-int host_io(HostCtx &c, size_t need)
+// the cached plan of an earlier host call of this shape on the current device (not created here)
+int cached_plan(HostCtx &c, int B, int H, int W, int L, int win, int K, oflk_plan **out)
 {
-    if (need <= c.io_elems) return OFLK_OK;
-    for (auto &q : c.io) {
-        if (q) (void)hipFree(q);
-        q = nullptr;
-    }
-    c.io_elems = 0;
-    size_t tot = 0;
-    for (auto &q : c.io) {
-        int rc = dmalloc(&q, need, &tot);
-        if (rc) return rc;
-    }
-    c.io_elems = need;
-    return OFLK_OK;
+    for (oflk_plan *q : c.plans)
+        if (has_shape(q, B, H, W, L, win, K)) {
+            *out = q;
+            return OFLK_OK;
+        }
+    return fail(OFLK_ERR_INVALID, "no pyramidal call of this shape (B=%d, %dx%d, %d levels, window %d, %d iterations) "
+                                  "has run on this device yet", B, W, H, L, win, K);
 }
 
-int host_u8(HostCtx &c, size_t need)
+// A set of cached device buffers of `have` elements each, grown to `need`: all freed, then all allocated again
+template <typename T, size_t N>
+int grow(T *(&set)[N], size_t &have, size_t need)
 {
-    if (need <= c.u8_elems) return OFLK_OK;
-    for (auto &q : c.u8) {
+    if (need <= have) return OFLK_OK;
+    for (T *&q : set) {
         if (q) (void)hipFree(q);
         q = nullptr;
     }
-    c.u8_elems = 0;
+    have = 0;
     size_t tot = 0;
-    for (auto &q : c.u8) {
+    for (T *&q : set) {
         int rc = dmalloc(&q, need, &tot);
         if (rc) return rc;
     }
-    c.u8_elems = need;
+    have = need;
     return OFLK_OK;
 }
 
@@ -1677,38 +1722,17 @@ int host_ring(HostCtx &c, size_t in_bytes, size_t out_elems)
             return fail(OFLK_ERR_HIP, "hipStreamCreateWithFlags failed: %s", hipGetErrorString(e));
         }
     }
-    size_t tot = 0;
-    if (in_bytes > c.ring_in_bytes) {
-        for (auto &slot : c.ring_in)
-            for (auto &q : slot) {
-                if (q) (void)hipFree(q);
-                q = nullptr;
-            }
-        c.ring_in_bytes = 0;
-        for (auto &slot : c.ring_in)
-            for (auto &q : slot) {
-                unsigned char *b = nullptr;
-                int rc = dmalloc(&b, in_bytes, &tot);
-                if (rc) return rc;
-                q = b;
-            }
-        c.ring_in_bytes = in_bytes;
-    }
-    if (out_elems > c.ring_out_elems) {
-        for (auto &slot : c.ring_out)
-            for (auto &q : slot) {
-                if (q) (void)hipFree(q);
-                q = nullptr;
-            }
-        c.ring_out_elems = 0;
-        for (auto &slot : c.ring_out)
-            for (auto &q : slot) {
-                int rc = dmalloc(&q, out_elems, &tot);
-                if (rc) return rc;
-            }
-        c.ring_out_elems = out_elems;
-    }
-    return OFLK_OK;
+    int rc = grow(c.ring_in, c.ring_in_bytes, in_bytes);
+    return rc ? rc : grow(c.ring_out, c.ring_out_elems, out_elems);
+}
+
+// Pairs per chunk of a chunked host call: ~32 MB of flow per plane (four 1080p pairs, one 4K pair), worth it from four chunks
+// on.  Below B exactly when the call is chunked (B: the whole batch in one piece).
+int chunk_pairs(int B, int H, int W)
+{
+    const size_t pair_out = (size_t)H * W * sizeof(float);
+    const int C = (int)std::max<size_t>(1, ((size_t)32 << 20) / std::max<size_t>(pair_out, 1));
+    return B >= 4 * C && (size_t)B * pair_out >= ((size_t)64 << 20) ? C : B;
 }
 
 int check_hw(const void *a, const void *b, int H, int W)
@@ -1780,8 +1804,8 @@ int run_batch_chunked(HostCtx *c, int dev, const PIXELS *prev, const PIXELS *cur
             }
             const int slot = k & 1, nb = k == nchunk - 1 ? tail : C;
             const size_t off = (size_t)k * C * plane, bytes = (size_t)nb * plane * sizeof(float);
-            hipError_t e = hipMemcpyAsync(u + off, c->ring_out[slot][0], bytes, hipMemcpyDeviceToHost, c->s_out);
-            if (e == hipSuccess) e = hipMemcpyAsync(v + off, c->ring_out[slot][1], bytes, hipMemcpyDeviceToHost, c->s_out);
+            hipError_t e = hipMemcpyAsync(u + off, c->ring_out[2 * slot], bytes, hipMemcpyDeviceToHost, c->s_out);
+            if (e == hipSuccess) e = hipMemcpyAsync(v + off, c->ring_out[2 * slot + 1], bytes, hipMemcpyDeviceToHost, c->s_out);
             if (e == hipSuccess) e = hipStreamSynchronize(c->s_out);
             std::lock_guard<std::mutex> g(mu);
             if (e != hipSuccess) {
@@ -1821,10 +1845,10 @@ int run_batch_chunked(HostCtx *c, int dev, const PIXELS *prev, const PIXELS *cur
         const int slot = k & 1, nb = k == nchunk - 1 ? tail : C;
         const size_t off = (size_t)k * C * plane, bytes = (size_t)nb * plane * sizeof(PIXELS);
         if (seq) {
-            HIP_TRY(hipMemcpyAsync(c->ring_in[slot][0], prev + off, bytes + plane * sizeof(PIXELS), hipMemcpyHostToDevice, c->s_in));
+            HIP_TRY(hipMemcpyAsync(c->ring_in[2 * slot], prev + off, bytes + plane * sizeof(PIXELS), hipMemcpyHostToDevice, c->s_in));
         } else {
-            HIP_TRY(hipMemcpyAsync(c->ring_in[slot][0], prev + off, bytes, hipMemcpyHostToDevice, c->s_in));
-            HIP_TRY(hipMemcpyAsync(c->ring_in[slot][1], curr + off, bytes, hipMemcpyHostToDevice, c->s_in));
+            HIP_TRY(hipMemcpyAsync(c->ring_in[2 * slot], prev + off, bytes, hipMemcpyHostToDevice, c->s_in));
+            HIP_TRY(hipMemcpyAsync(c->ring_in[2 * slot + 1], curr + off, bytes, hipMemcpyHostToDevice, c->s_in));
         }
         HIP_TRY(hipEventRecord(ev_in[slot], c->s_in));
         return OFLK_OK;
@@ -1840,9 +1864,9 @@ int run_batch_chunked(HostCtx *c, int dev, const PIXELS *prev, const PIXELS *cur
             if (out_rc != OFLK_OK) { g.unlock(); return finish(OFLK_OK); }
         }
         if ((rc = hipStreamWaitEvent(c->s_comp, ev_in[slot], 0)) != hipSuccess) return finish(fail(OFLK_ERR_HIP, "hipStreamWaitEvent"));
-        const void *dp = c->ring_in[slot][0];
-        const void *dc = seq ? static_cast<const void *>(static_cast<const PIXELS *>(dp) + plane) : c->ring_in[slot][1];
-        float *du = c->ring_out[slot][0], *dv = c->ring_out[slot][1];
+        const void *dp = c->ring_in[2 * slot];
+        const void *dc = seq ? static_cast<const void *>(static_cast<const PIXELS *>(dp) + plane) : c->ring_in[2 * slot + 1];
+        float *du = c->ring_out[2 * slot], *dv = c->ring_out[2 * slot + 1];
         rc = single ? plan_single_scale(p, dp, dc, U8, du, dv, c->s_comp) : plan_pyramidal(p, dp, dc, U8, du, dv, c->s_comp, seq);
         if (rc) return finish(rc);
         // the next chunk's frames travel while this one is computed (the kernels that read its slot, chunk k-1's, are done:
@@ -1888,36 +1912,28 @@ int run_batch_on(int dev, const PIXELS *prev, const PIXELS *curr, int B, int H, 
     if (rc) return rc;
     if (!u || !v) return fail(OFLK_ERR_INVALID, "NULL output");
     if (B < 1) return fail(OFLK_ERR_INVALID, "B must be >= 1");
-    HostCtx *c = nullptr;
-    std::unique_lock<std::mutex> lk;
-    if ((rc = acquire(dev, &c, lk))) return rc;
+    HostCall call;
+    if ((rc = call.begin(dev))) return rc;
+    HostCtx *c = call.c;
     const bool single = levels == 0;
-    {
-        // chunks of ~32 MB of flow per plane (four 1080p pairs, one 4K pair); worth it from four chunks on
-        const size_t pair_out = (size_t)H * W * sizeof(float);
-        const int C = (int)std::max<size_t>(1, ((size_t)32 << 20) / std::max<size_t>(pair_out, 1));
-        if (B >= 4 * C && (size_t)B * pair_out >= ((size_t)64 << 20))
-            return run_batch_chunked<PIXELS>(c, dev, prev, curr, B, C, H, W, levels, window_size, iters, u, v, residual_log, iters_run,
-                                             seq);
-    }
+    const int C = chunk_pairs(B, H, W);
+    if (C < B)
+        return run_batch_chunked<PIXELS>(c, dev, prev, curr, B, C, H, W, levels, window_size, iters, u, v, residual_log, iters_run,
+                                         seq);
     oflk_plan *p = nullptr;
     if ((rc = host_plan(*c, dev, B, H, W, single ? 1 : levels, window_size, single ? 0 : iters, &p))) return rc;
-    const size_t plane = (size_t)H * W, n = (size_t)B * plane, obytes = n * sizeof(float);
+    const size_t plane = (size_t)H * W, n = (size_t)B * plane;
     const size_t nin = seq ? n + plane : n;   // frames in the first device buffer (a sequence: all B+1)
-    if ((rc = host_io(*c, nin))) return rc;
-    const void *dp, *dc;
-    if (U8) {
-        if ((rc = host_u8(*c, nin))) return rc;
-        HIP_TRY(hipMemcpyAsync(c->u8[0], prev, nin, hipMemcpyHostToDevice, nullptr));
-        if (!seq) HIP_TRY(hipMemcpyAsync(c->u8[1], curr, n, hipMemcpyHostToDevice, nullptr));
-        dp = c->u8[0];
-        dc = seq ? c->u8[0] + plane : c->u8[1];
+    if ((rc = grow(c->io, c->io_elems, nin))) return rc;
+    PIXELS **in = nullptr;   // the context's frame buffers of this pixel type
+    if constexpr (U8) {
+        if ((rc = grow(c->u8, c->u8_elems, nin))) return rc;
+        in = c->u8;
     } else {
-        HIP_TRY(hipMemcpyAsync(c->io[0], prev, nin * sizeof(float), hipMemcpyHostToDevice, nullptr));
-        if (!seq) HIP_TRY(hipMemcpyAsync(c->io[1], curr, obytes, hipMemcpyHostToDevice, nullptr));
-        dp = c->io[0];
-        dc = seq ? c->io[0] + plane : c->io[1];
+        in = c->io;
     }
+    if ((rc = call.to_device(in[0], prev, nin)) || (!seq && (rc = call.to_device(in[1], curr, n)))) return rc;
+    const void *dp = in[0], *dc = seq ? in[0] + plane : in[1];
     rc = single ? plan_single_scale(p, dp, dc, U8, c->io[2], c->io[3], nullptr)
                 : plan_pyramidal(p, dp, dc, U8, c->io[2], c->io[3], nullptr, seq);
     if (rc) return rc;
@@ -1927,13 +1943,8 @@ int run_batch_on(int dev, const PIXELS *prev, const PIXELS *curr, int B, int H, 
         if ((rc = resolve_uncertain(p, dp, dc, U8, c->io[2], c->io[3], nullptr, &n_res))) return rc;
         t_resolved += n_res;
     }
-    HIP_TRY(hipMemcpyAsync(u, c->io[2], obytes, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipMemcpyAsync(v, c->io[3], obytes, hipMemcpyDeviceToHost, nullptr));
-    if (single) {
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        return OFLK_OK;
-    }
-    return oflk_plan_read_log(p, residual_log, iters_run, nullptr);
+    if ((rc = call.to_host(u, c->io[2], n)) || (rc = call.to_host(v, c->io[3], n))) return rc;
+    return single ? call.sync() : oflk_plan_read_log(p, residual_log, iters_run, nullptr);   // the log's read syncs too
 }
 
 // contiguous share of `total` units for shard `i` of `n`; sizes differ by at most one
@@ -2065,20 +2076,17 @@ OFLK_API int oflk_single_scale_fp16(const float *prev, const float *curr, int B,
     if (rc) return rc;
     if (!u || !v) return fail(OFLK_ERR_INVALID, "NULL output");
     if (B < 1) return fail(OFLK_ERR_INVALID, "B must be >= 1");
-    HostCtx *c = nullptr;
-    std::unique_lock<std::mutex> lk;
-    if ((rc = acquire(g_device.load(), &c, lk))) return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    HostCtx *c = call.c;
     oflk_plan *p = nullptr;
-    if ((rc = host_plan(*c, g_device.load(), B, H, W, 1, window_size, 0, &p))) return rc;
-    const size_t n = (size_t)B * H * W, bytes = n * sizeof(float);
-    if ((rc = host_io(*c, n))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->io[0], prev, bytes, hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(hipMemcpyAsync(c->io[1], curr, bytes, hipMemcpyHostToDevice, nullptr));
+    if ((rc = host_plan(*c, call.dev, B, H, W, 1, window_size, 0, &p))) return rc;
+    const size_t n = (size_t)B * H * W;
+    if ((rc = grow(c->io, c->io_elems, n))) return rc;
+    if ((rc = call.to_device(c->io[0], prev, n)) || (rc = call.to_device(c->io[1], curr, n))) return rc;
     if ((rc = oflk_plan_single_scale_fp16(p, c->io[0], c->io[1], c->io[2], c->io[3], pixel_max, nullptr))) return rc;
-    HIP_TRY(hipMemcpyAsync(u, c->io[2], bytes, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipMemcpyAsync(v, c->io[3], bytes, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return OFLK_OK;
+    if ((rc = call.to_host(u, c->io[2], n)) || (rc = call.to_host(v, c->io[3], n))) return rc;
+    return call.sync();
 }
 
 // ---- RTL-bit-accurate integer mode ---------------------------------
@@ -2120,20 +2128,17 @@ OFLK_API int oflk_rtl_flow_u8(const unsigned char *prev, const unsigned char *cu
 {
     int rc = check_rtl(prev, curr, B, H, W, u, v);
     if (rc) return rc;
-    HostCtx *c = nullptr;
-    std::unique_lock<std::mutex> lk;
-    if ((rc = acquire(g_device.load(), &c, lk))) return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    HostCtx *c = call.c;
     const size_t n = (size_t)B * H * W, m = (size_t)B * (size_t)oflk_rtl_stream_length(H, W);
-    if ((rc = host_u8(*c, n))) return rc;
-    if ((rc = host_io(*c, (m + 1) / 2))) return rc;   // two int16 planes in the float32 scratch planes 2 and 3
+    if ((rc = grow(c->u8, c->u8_elems, n))) return rc;
+    if ((rc = grow(c->io, c->io_elems, (m + 1) / 2))) return rc;   // two int16 planes in the float32 scratch planes 2 and 3
     short *d_u = reinterpret_cast<short *>(c->io[2]), *d_v = reinterpret_cast<short *>(c->io[3]);
-    HIP_TRY(hipMemcpyAsync(c->u8[0], prev, n, hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(hipMemcpyAsync(c->u8[1], curr, n, hipMemcpyHostToDevice, nullptr));
+    if ((rc = call.to_device(c->u8[0], prev, n)) || (rc = call.to_device(c->u8[1], curr, n))) return rc;
     if ((rc = oflk_rtl_flow_u8_device(c->u8[0], c->u8[1], B, H, W, d_u, d_v, nullptr))) return rc;
-    HIP_TRY(hipMemcpyAsync(u, d_u, m * sizeof(short), hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipMemcpyAsync(v, d_v, m * sizeof(short), hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return OFLK_OK;
+    if ((rc = call.to_host(u, d_u, m)) || (rc = call.to_host(v, d_v, m))) return rc;
+    return call.sync();
 }
 
 // ---- one process, several GPUs: the batch sharded over devices 0 .. n_gpus-1 ---------------
@@ -2250,83 +2255,88 @@ int fb_launch(const float *uf, const float *vf, const float *ub, const float *vb
     return OFLK_OK;
 }
 
-// Pairs per chunk of run_sequence_fb / run_sequence_tracks (the chunk rule of run_batch_on): ~32 MB of flow per plane and
-// chunk, from four chunks on; otherwise the whole sequence
-int fb_chunk_pairs(int B, size_t plane)
-{
-    const size_t pair_out = plane * sizeof(float);
-    const int C0 = (int)std::max<size_t>(1, ((size_t)32 << 20) / std::max<size_t>(pair_out, 1));
-    return (B >= 4 * C0 && (size_t)B * pair_out >= ((size_t)64 << 20)) ? C0 : B;
-}
-
-// One chunk of a bidirectional host call on the null stream: frames b0 .. b0+nb uploaded into d_frames, the bidirectional
-// plan pass into d[0..3] (uf, vf, ub, vb), the flagged pairs of both directions resolved (counted into t_resolved)
-template <class PIXELS>
-int fb_chunk(HostCtx &c, int dev, const PIXELS *frames, int b0, int nb, int H, int W, int levels, int window_size, int iters,
-             PIXELS *d_frames, float *const *d)
+// Both directions of a sequence, host pointers.  Chunks of C pairs (C+1 frames, chunk_pairs) run one after the other on the
+// null stream: the chunk's frames go up, one bidirectional plan pass writes d[0..3] (uf, vf, ub, vb), the flagged pairs of both
+// directions are resolved (counted into t_resolved), the caller's own work on the chunk runs, and the stream is synchronized,
+// as the next chunk reuses the buffers.  The caller's parts:
+//   check()                            its own arguments, after the sequence's and before any device call
+//   setup(call, C)                     its per-call buffers and uploads
+//   chunk(call, b0, nb, d_frames, d)   its work on pairs b0 .. b0+nb-1, whose frames b0 .. b0+nb are in d_frames
+template <class PIXELS, class Check, class Setup, class Chunk>
+int run_sequence_bidir(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, Check check, Setup setup,
+                       Chunk chunk)
 {
     constexpr bool U8 = sizeof(PIXELS) == 1;
-    const size_t plane = (size_t)H * W;
-    oflk_plan *p = nullptr;
-    int rc;
-    if ((rc = host_plan(c, dev, nb, H, W, levels, window_size, iters, &p))) return rc;
-    HIP_TRY(hipMemcpyAsync(d_frames, frames + (size_t)b0 * plane, (size_t)(nb + 1) * plane * sizeof(PIXELS), hipMemcpyHostToDevice,
-                           nullptr));
-    if ((rc = plan_pyramidal(p, d_frames, d_frames + plane, U8, d[0], d[1], nullptr, true, d[2], d[3]))) return rc;
-    if (iters > 0) {
-        int n_res = 0;
-        if ((rc = resolve_uncertain_fb(p, d_frames, U8, d[0], d[1], d[2], d[3], nullptr, &n_res))) return rc;
-        t_resolved += n_res;
-    }
-    return OFLK_OK;
-}
-
-// Both directions of a sequence and their consistency, host pointers.  Chunks of C pairs (C+1 frames) run one after the
-// other on the null stream: one bidirectional plan pass, the flagged pairs of both directions resolved, one check launch.
-template <class PIXELS>
-int run_sequence_fb(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
-                    float *uf, float *vf, float *ub, float *vb, float *ef, float *eb, unsigned char *qf, unsigned char *qb)
-{
     t_resolved = 0;
     int rc = check_hw(frames, frames, H, W);
     if (rc) return rc;
     if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
     if (levels < 1) return fail(OFLK_ERR_INVALID, "levels must be in [1,%d] (got %d)", OFLK_MAX_LEVELS, levels);
-    const bool check = ef || eb || qf || qb;
-    if (check && (rc = check_fb(uf, vf, ub, vb, T - 1, H, W, alpha, beta, ef, eb, qf, qb))) return rc;
-    if (!uf || !vf || !ub || !vb) return fail(OFLK_ERR_INVALID, "NULL flow argument");
-    const int dev = g_device.load();
-    HostCtx *c = nullptr;
-    std::unique_lock<std::mutex> lk;
-    if ((rc = acquire(dev, &c, lk))) return rc;
+    if ((rc = check())) return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
     const int B = T - 1;
     const size_t plane = (size_t)H * W;
-    const int C = fb_chunk_pairs(B, plane);
-    Arena ar;
+    const int C = chunk_pairs(B, H, W);
     PIXELS *d_frames = nullptr;
-    float *d[4] = {nullptr, nullptr, nullptr, nullptr}, *d_e[2] = {nullptr, nullptr};
-    unsigned char *d_q[2] = {nullptr, nullptr};
-    if ((rc = ar.get(&d_frames, (size_t)(C + 1) * plane))) return rc;
+    float *d[4];
+    if ((rc = call.alloc(&d_frames, (size_t)(C + 1) * plane))) return rc;
     for (auto &q : d)
-        if ((rc = ar.get(&q, (size_t)C * plane))) return rc;
-    if ((ef && (rc = ar.get(&d_e[0], (size_t)C * plane))) || (eb && (rc = ar.get(&d_e[1], (size_t)C * plane))) ||
-        (qf && (rc = ar.get(&d_q[0], (size_t)C * plane))) || (qb && (rc = ar.get(&d_q[1], (size_t)C * plane))))
-        return rc;
+        if ((rc = call.alloc(&q, (size_t)C * plane))) return rc;
+    if ((rc = setup(call, C))) return rc;
     for (int b0 = 0; b0 < B; b0 += C) {
         const int nb = std::min(C, B - b0);
+        oflk_plan *p = nullptr;
+        if ((rc = host_plan(*call.c, call.dev, nb, H, W, levels, window_size, iters, &p))) return rc;
+        if ((rc = call.to_device(d_frames, frames + (size_t)b0 * plane, (size_t)(nb + 1) * plane))) return rc;
+        if ((rc = plan_pyramidal(p, d_frames, d_frames + plane, U8, d[0], d[1], nullptr, true, d[2], d[3]))) return rc;
+        if (iters > 0) {
+            int n_res = 0;
+            if ((rc = resolve_uncertain_fb(p, d_frames, U8, d[0], d[1], d[2], d[3], nullptr, &n_res))) return rc;
+            t_resolved += n_res;
+        }
+        if ((rc = chunk(call, b0, nb, d_frames, d)) || (rc = call.sync())) return rc;
+    }
+    return OFLK_OK;
+}
+
+// Both directions of a sequence and their consistency, host pointers: run_sequence_bidir's chunks, one check launch each
+template <class PIXELS>
+int run_sequence_fb(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
+                    float *uf, float *vf, float *ub, float *vb, float *ef, float *eb, unsigned char *qf, unsigned char *qb)
+{
+    const bool check = ef || eb || qf || qb;
+    const size_t plane = (size_t)H * W;
+    float *d_e[2] = {nullptr, nullptr};
+    unsigned char *d_q[2] = {nullptr, nullptr};
+    auto checks = [&]() -> int {
+        int rc;
+        if (check && (rc = check_fb(uf, vf, ub, vb, T - 1, H, W, alpha, beta, ef, eb, qf, qb))) return rc;
+        if (!uf || !vf || !ub || !vb) return fail(OFLK_ERR_INVALID, "NULL flow argument");
+        return OFLK_OK;
+    };
+    auto setup = [&](HostCall &call, int C) -> int {
+        const size_t n = (size_t)C * plane;
+        int rc;
+        if ((rc = call.alloc(&d_e[0], n, ef)) || (rc = call.alloc(&d_e[1], n, eb)) || (rc = call.alloc(&d_q[0], n, qf)) ||
+            (rc = call.alloc(&d_q[1], n, qb)))
+            return rc;
+        return OFLK_OK;
+    };
+    auto chunk = [&](HostCall &call, int b0, int nb, const PIXELS *, float *const *d) -> int {
         const size_t off = (size_t)b0 * plane, n = (size_t)nb * plane;
-        if ((rc = fb_chunk(*c, dev, frames, b0, nb, H, W, levels, window_size, iters, d_frames, d))) return rc;
+        int rc;
         if (check && (rc = fb_launch(d[0], d[1], d[2], d[3], nb, H, W, alpha, beta, d_e[0], d_e[1], d_q[0], d_q[1], nullptr)))
             return rc;
         float *outs[4] = {uf, vf, ub, vb};
-        for (int i = 0; i < 4; i++) HIP_TRY(hipMemcpyAsync(outs[i] + off, d[i], n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-        if (ef) HIP_TRY(hipMemcpyAsync(ef + off, d_e[0], n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-        if (eb) HIP_TRY(hipMemcpyAsync(eb + off, d_e[1], n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-        if (qf) HIP_TRY(hipMemcpyAsync(qf + off, d_q[0], n, hipMemcpyDeviceToHost, nullptr));
-        if (qb) HIP_TRY(hipMemcpyAsync(qb + off, d_q[1], n, hipMemcpyDeviceToHost, nullptr));
-        HIP_TRY(hipStreamSynchronize(nullptr));   // the chunk's buffers are reused by the next
-    }
-    return OFLK_OK;
+        for (int i = 0; i < 4; i++)
+            if ((rc = call.to_host(outs[i] + off, d[i], n))) return rc;
+        if ((ef && (rc = call.to_host(ef + off, d_e[0], n))) || (eb && (rc = call.to_host(eb + off, d_e[1], n))) ||
+            (qf && (rc = call.to_host(qf + off, d_q[0], n))) || (qb && (rc = call.to_host(qb + off, d_q[1], n))))
+            return rc;
+        return OFLK_OK;
+    };
+    return run_sequence_bidir<PIXELS>(frames, T, H, W, levels, window_size, iters, checks, setup, chunk);
 }
 }  // namespace
 
@@ -2345,28 +2355,22 @@ OFLK_API int oflk_fb_consistency_host(const float *uf, const float *vf, const fl
 {
     int rc = check_fb(uf, vf, ub, vb, B, H, W, alpha, beta, err_f, err_b, valid_f, valid_b);
     if (rc) return rc;
-    HostCtx *c = nullptr;
-    std::unique_lock<std::mutex> lk;
-    if ((rc = acquire(g_device.load(), &c, lk))) return rc;
-    Arena ar;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
     const size_t n = (size_t)B * H * W;
     const float *in[4] = {uf, vf, ub, vb};
-    float *d[4] = {nullptr, nullptr, nullptr, nullptr}, *d_e[2] = {nullptr, nullptr};
-    unsigned char *d_q[2] = {nullptr, nullptr};
-    for (int i = 0; i < 4; i++) {
-        if ((rc = ar.get(&d[i], n))) return rc;
-        HIP_TRY(hipMemcpyAsync(d[i], in[i], n * sizeof(float), hipMemcpyHostToDevice, nullptr));
-    }
-    if ((err_f && (rc = ar.get(&d_e[0], n))) || (err_b && (rc = ar.get(&d_e[1], n))) || (valid_f && (rc = ar.get(&d_q[0], n))) ||
-        (valid_b && (rc = ar.get(&d_q[1], n))))
+    float *d[4], *d_e[2];
+    unsigned char *d_q[2];
+    for (int i = 0; i < 4; i++)
+        if ((rc = call.upload(&d[i], in[i], n))) return rc;
+    if ((rc = call.alloc(&d_e[0], n, err_f)) || (rc = call.alloc(&d_e[1], n, err_b)) || (rc = call.alloc(&d_q[0], n, valid_f)) ||
+        (rc = call.alloc(&d_q[1], n, valid_b)))
         return rc;
     if ((rc = fb_launch(d[0], d[1], d[2], d[3], B, H, W, alpha, beta, d_e[0], d_e[1], d_q[0], d_q[1], nullptr))) return rc;
-    if (err_f) HIP_TRY(hipMemcpyAsync(err_f, d_e[0], n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    if (err_b) HIP_TRY(hipMemcpyAsync(err_b, d_e[1], n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    if (valid_f) HIP_TRY(hipMemcpyAsync(valid_f, d_q[0], n, hipMemcpyDeviceToHost, nullptr));
-    if (valid_b) HIP_TRY(hipMemcpyAsync(valid_b, d_q[1], n, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return OFLK_OK;
+    if ((err_f && (rc = call.to_host(err_f, d_e[0], n))) || (err_b && (rc = call.to_host(err_b, d_e[1], n))) ||
+        (valid_f && (rc = call.to_host(valid_f, d_q[0], n))) || (valid_b && (rc = call.to_host(valid_b, d_q[1], n))))
+        return rc;
+    return call.sync();
 }
 
 OFLK_API int oflk_pyramidal_sequence_fb(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
@@ -2500,19 +2504,15 @@ int corner_score_host(const PIXELS *frames, int F, int H, int W, int window_size
     if (rc) return rc;
     if (!score) return fail(OFLK_ERR_INVALID, "NULL score");
     if ((rc = check_corner_window(window_size))) return rc;
-    HostCtx *c = nullptr;
-    std::unique_lock<std::mutex> lk;
-    if ((rc = acquire(g_device.load(), &c, lk))) return rc;
-    Arena ar;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
     const size_t n = (size_t)F * H * W;
-    PIXELS *d_f = nullptr;
-    float *d_s = nullptr;
-    if ((rc = ar.get(&d_f, n)) || (rc = ar.get(&d_s, n))) return rc;
-    HIP_TRY(hipMemcpyAsync(d_f, frames, n * sizeof(PIXELS), hipMemcpyHostToDevice, nullptr));
+    PIXELS *d_f;
+    float *d_s;
+    if ((rc = call.upload(&d_f, frames, n)) || (rc = call.alloc(&d_s, n))) return rc;
     if ((rc = corner_score_launch(d_f, sizeof(PIXELS) == 1, F, H, W, window_size, d_s, nullptr, nullptr))) return rc;
-    HIP_TRY(hipMemcpyAsync(score, d_s, n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return OFLK_OK;
+    if ((rc = call.to_host(score, d_s, n))) return rc;
+    return call.sync();
 }
 
 template <class PIXELS>
@@ -2523,26 +2523,22 @@ int good_features_host(const PIXELS *frames, int F, int H, int W, int window_siz
     if (rc) return rc;
     if (!count || !xy || !score) return fail(OFLK_ERR_INVALID, "NULL output argument");
     if ((rc = check_select(q, md, K)) || (rc = check_corner_window(window_size))) return rc;
-    HostCtx *c = nullptr;
-    std::unique_lock<std::mutex> lk;
-    if ((rc = acquire(g_device.load(), &c, lk))) return rc;
-    Arena ar;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
     const size_t n = (size_t)F * H * W, nk = (size_t)F * K;
-    PIXELS *d_f = nullptr;
-    char *d_ws = nullptr;
-    int *d_cnt = nullptr;
-    float *d_xy = nullptr, *d_sc = nullptr;
-    if ((rc = ar.get(&d_f, n)) || (rc = ar.get(&d_ws, feat_geom(F, H, W, md).bytes)) || (rc = ar.get(&d_cnt, (size_t)F)) ||
-        (rc = ar.get(&d_xy, 2 * nk)) || (rc = ar.get(&d_sc, nk)))
+    PIXELS *d_f;
+    char *d_ws;
+    int *d_cnt;
+    float *d_xy, *d_sc;
+    if ((rc = call.upload(&d_f, frames, n)) || (rc = call.alloc(&d_ws, feat_geom(F, H, W, md).bytes)) ||
+        (rc = call.alloc(&d_cnt, (size_t)F)) || (rc = call.alloc(&d_xy, 2 * nk)) || (rc = call.alloc(&d_sc, nk)))
         return rc;
-    HIP_TRY(hipMemcpyAsync(d_f, frames, n * sizeof(PIXELS), hipMemcpyHostToDevice, nullptr));
     if ((rc = good_features_launch(d_f, sizeof(PIXELS) == 1, F, H, W, window_size, q, md, K, d_ws, d_cnt, d_xy, d_sc, nullptr)))
         return rc;
-    HIP_TRY(hipMemcpyAsync(count, d_cnt, (size_t)F * sizeof(int), hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipMemcpyAsync(xy, d_xy, 2 * nk * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipMemcpyAsync(score, d_sc, nk * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return OFLK_OK;
+    if ((rc = call.to_host(count, d_cnt, (size_t)F)) || (rc = call.to_host(xy, d_xy, 2 * nk)) ||
+        (rc = call.to_host(score, d_sc, nk)))
+        return rc;
+    return call.sync();
 }
 }  // namespace
 
@@ -2642,11 +2638,11 @@ int track_launch(const float *uf, const float *vf, const float *ub, const float 
     return OFLK_OK;
 }
 
-// Tracks of a whole sequence, host pointers: run_sequence_fb's chunks (bidirectional plan pass, flagged pairs of both
-// directions resolved), then one track launch per chunk that continues from the previous chunk's last row.  Only the
-// queries go up and only the tracks come down.  With `det` (oflk_pyramidal_sequence_klt) the queries are born on the
-// device instead: good_features_launch on frame 0 of chunk 0's frames writes its xy straight into the query buffer (N = K;
-// the NaN rows are never-visible tracks), and count, xy and score come down at the end.
+// Tracks of a whole sequence, host pointers: run_sequence_bidir's chunks, then one track launch per chunk that continues
+// from the previous chunk's last row.  Only the queries go up and only the tracks come down.  With `det`
+// (oflk_pyramidal_sequence_klt) the queries are born on the device instead: good_features_launch on frame 0 of chunk 0's
+// frames writes its xy straight into the query buffer (N = K; the NaN rows are never-visible tracks), and count, xy and
+// score come down with chunk 0.
 struct Detect {
     float q, md;
     int K;
@@ -2659,70 +2655,57 @@ int run_sequence_tracks(const PIXELS *frames, int T, int H, int W, int levels, i
                         float beta, const int *qt, const float *qxy, int N, float *tracks, unsigned char *visible,
                         const Detect *det = nullptr)
 {
-    t_resolved = 0;
-    int rc = check_hw(frames, frames, H, W);
-    if (rc) return rc;
-    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
-    if (levels < 1) return fail(OFLK_ERR_INVALID, "levels must be in [1,%d] (got %d)", OFLK_MAX_LEVELS, levels);
-    if ((rc = check_alpha_beta(alpha, beta))) return rc;
-    if (det) {
+    int C = 0;   // pairs per chunk (setup)
+    float *d_qxy = nullptr, *d_tr = nullptr, *d_sc = nullptr;
+    int *d_qt = nullptr, *d_cnt = nullptr;
+    unsigned char *d_vis = nullptr;
+    char *d_ws = nullptr;
+    auto checks = [&]() -> int {
+        int rc = check_alpha_beta(alpha, beta);
+        if (rc) return rc;
+        if (!det) return check_queries(qt, T, qxy, N, tracks, visible);
         if (!det->count || !det->xy || !det->score || !tracks || !visible) return fail(OFLK_ERR_INVALID, "NULL output argument");
         if ((rc = check_select(det->q, det->md, det->K)) || (rc = check_corner_window(window_size))) return rc;
         N = det->K;
-    } else if ((rc = check_queries(qt, T, qxy, N, tracks, visible))) {
-        return rc;
-    }
-    const int dev = g_device.load();
-    HostCtx *c = nullptr;
-    std::unique_lock<std::mutex> lk;
-    if ((rc = acquire(dev, &c, lk))) return rc;
-    const int B = T - 1;
-    const size_t plane = (size_t)H * W, row = (size_t)N;
-    const int C = fb_chunk_pairs(B, plane);
-    Arena ar;
-    PIXELS *d_frames = nullptr;
-    float *d[4] = {nullptr, nullptr, nullptr, nullptr}, *d_qxy = nullptr, *d_tr = nullptr;
-    int *d_qt = nullptr;
-    unsigned char *d_vis = nullptr;
-    if ((rc = ar.get(&d_frames, (size_t)(C + 1) * plane))) return rc;
-    for (auto &q : d)
-        if ((rc = ar.get(&q, (size_t)C * plane))) return rc;
-    if ((rc = ar.get(&d_qxy, 2 * row)) || (qt && (rc = ar.get(&d_qt, row))) || (rc = ar.get(&d_tr, (size_t)(C + 1) * 2 * row)) ||
-        (rc = ar.get(&d_vis, (size_t)(C + 1) * row)))
-        return rc;
-    char *d_ws = nullptr;
-    int *d_cnt = nullptr;
-    float *d_sc = nullptr;
-    if (det) {
-        if ((rc = ar.get(&d_ws, feat_geom(1, H, W, det->md).bytes)) || (rc = ar.get(&d_cnt, 1)) || (rc = ar.get(&d_sc, row))) return rc;
-    } else {
-        HIP_TRY(hipMemcpyAsync(d_qxy, qxy, 2 * row * sizeof(float), hipMemcpyHostToDevice, nullptr));
-    }
-    if (qt) HIP_TRY(hipMemcpyAsync(d_qt, qt, row * sizeof(int), hipMemcpyHostToDevice, nullptr));
-    for (int b0 = 0; b0 < B; b0 += C) {
-        const int nb = std::min(C, B - b0);
+        return OFLK_OK;
+    };
+    auto setup = [&](HostCall &call, int pairs) -> int {
+        const size_t row = (size_t)N;
+        int rc;
+        C = pairs;
+        if ((rc = det ? call.alloc(&d_qxy, 2 * row) : call.upload(&d_qxy, qxy, 2 * row)) ||
+            (qt && (rc = call.upload(&d_qt, qt, row))) || (rc = call.alloc(&d_tr, (size_t)(C + 1) * 2 * row)) ||
+            (rc = call.alloc(&d_vis, (size_t)(C + 1) * row)))
+            return rc;
+        if (det && ((rc = call.alloc(&d_ws, feat_geom(1, H, W, det->md).bytes)) || (rc = call.alloc(&d_cnt, 1)) ||
+                    (rc = call.alloc(&d_sc, row))))
+            return rc;
+        return OFLK_OK;
+    };
+    auto chunk = [&](HostCall &call, int b0, int nb, const PIXELS *d_frames, float *const *d) -> int {
+        const size_t row = (size_t)N;
+        int rc;
         if (b0 > 0) {   // row 0 of this chunk is the previous (full, C-pair) chunk's last row
             HIP_TRY(hipMemcpyAsync(d_tr, d_tr + (size_t)C * 2 * row, 2 * row * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
             HIP_TRY(hipMemcpyAsync(d_vis, d_vis + (size_t)C * row, row, hipMemcpyDeviceToDevice, nullptr));
         }
-        if ((rc = fb_chunk(*c, dev, frames, b0, nb, H, W, levels, window_size, iters, d_frames, d))) return rc;
         if (det && b0 == 0) {   // frame 0 is d_frames[0]: its features become the queries
             if ((rc = good_features_launch(d_frames, sizeof(PIXELS) == 1, 1, H, W, window_size, det->q, det->md, det->K, d_ws, d_cnt,
                                            d_qxy, d_sc, nullptr)))
                 return rc;
-            HIP_TRY(hipMemcpyAsync(det->count, d_cnt, sizeof(int), hipMemcpyDeviceToHost, nullptr));
-            HIP_TRY(hipMemcpyAsync(det->xy, d_qxy, 2 * row * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-            HIP_TRY(hipMemcpyAsync(det->score, d_sc, row * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+            if ((rc = call.to_host(det->count, d_cnt, 1)) || (rc = call.to_host(det->xy, d_qxy, 2 * row)) ||
+                (rc = call.to_host(det->score, d_sc, row)))
+                return rc;
         }
         if ((rc = track_launch(d[0], d[1], d[2], d[3], nb, H, W, alpha, beta, b0, d_qt, d_qxy, N, d_tr, d_vis, nullptr))) return rc;
         const int r0 = b0 > 0 ? 1 : 0;   // row 0 of a later chunk is already on the host
         const size_t nr = (size_t)(nb + 1 - r0);
-        HIP_TRY(hipMemcpyAsync(tracks + (size_t)(b0 + r0) * 2 * row, d_tr + (size_t)r0 * 2 * row, nr * 2 * row * sizeof(float),
-                               hipMemcpyDeviceToHost, nullptr));
-        HIP_TRY(hipMemcpyAsync(visible + (size_t)(b0 + r0) * row, d_vis + (size_t)r0 * row, nr * row, hipMemcpyDeviceToHost, nullptr));
-        HIP_TRY(hipStreamSynchronize(nullptr));   // the chunk's buffers are reused by the next
-    }
-    return OFLK_OK;
+        if ((rc = call.to_host(tracks + (size_t)(b0 + r0) * 2 * row, d_tr + (size_t)r0 * 2 * row, nr * 2 * row)) ||
+            (rc = call.to_host(visible + (size_t)(b0 + r0) * row, d_vis + (size_t)r0 * row, nr * row)))
+            return rc;
+        return OFLK_OK;
+    };
+    return run_sequence_bidir<PIXELS>(frames, T, H, W, levels, window_size, iters, checks, setup, chunk);
 }
 }  // namespace
 
@@ -2743,29 +2726,21 @@ OFLK_API int oflk_track_points_host(const float *uf, const float *vf, const floa
 {
     int rc = check_track(uf, vf, ub, vb, B, H, W, alpha, beta, qt, qxy, N, tracks, visible);
     if (rc) return rc;
-    HostCtx *c = nullptr;
-    std::unique_lock<std::mutex> lk;
-    if ((rc = acquire(g_device.load(), &c, lk))) return rc;
-    Arena ar;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
     const size_t n = (size_t)B * H * W, row = (size_t)N, rows = (size_t)(B + 1) * row;
     const float *in[4] = {uf, vf, ub, vb};
-    float *d[4] = {nullptr, nullptr, nullptr, nullptr}, *d_qxy = nullptr, *d_tr = nullptr;
+    float *d[4], *d_qxy, *d_tr;
     int *d_qt = nullptr;
-    unsigned char *d_vis = nullptr;
-    for (int i = 0; i < 4; i++) {
-        if ((rc = ar.get(&d[i], n))) return rc;
-        HIP_TRY(hipMemcpyAsync(d[i], in[i], n * sizeof(float), hipMemcpyHostToDevice, nullptr));
-    }
-    if ((rc = ar.get(&d_qxy, 2 * row)) || (qt && (rc = ar.get(&d_qt, row))) || (rc = ar.get(&d_tr, 2 * rows)) ||
-        (rc = ar.get(&d_vis, rows)))
+    unsigned char *d_vis;
+    for (int i = 0; i < 4; i++)
+        if ((rc = call.upload(&d[i], in[i], n))) return rc;
+    if ((rc = call.upload(&d_qxy, qxy, 2 * row)) || (qt && (rc = call.upload(&d_qt, qt, row))) ||
+        (rc = call.alloc(&d_tr, 2 * rows)) || (rc = call.alloc(&d_vis, rows)))
         return rc;
-    HIP_TRY(hipMemcpyAsync(d_qxy, qxy, 2 * row * sizeof(float), hipMemcpyHostToDevice, nullptr));
-    if (qt) HIP_TRY(hipMemcpyAsync(d_qt, qt, row * sizeof(int), hipMemcpyHostToDevice, nullptr));
     if ((rc = track_launch(d[0], d[1], d[2], d[3], B, H, W, alpha, beta, 0, d_qt, d_qxy, N, d_tr, d_vis, nullptr))) return rc;
-    HIP_TRY(hipMemcpyAsync(tracks, d_tr, 2 * rows * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipMemcpyAsync(visible, d_vis, rows, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return OFLK_OK;
+    if ((rc = call.to_host(tracks, d_tr, 2 * rows)) || (rc = call.to_host(visible, d_vis, rows))) return rc;
+    return call.sync();
 }
 
 OFLK_API int oflk_pyramidal_sequence_tracks(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
@@ -2802,40 +2777,24 @@ OFLK_API int oflk_pyramidal_sequence_klt_u8(const unsigned char *frames, int T, 
                                               tracks, visible, &det);
 }
 
-namespace {
-// the cached plan of an earlier host call of this shape on the current device (not created here)
-int cached_plan(HostCtx &c, int B, int H, int W, int L, int win, int K, oflk_plan **out)
-{
-    for (oflk_plan *q : c.plans)
-        if (q->B == B && q->H == H && q->W == W && q->L == L && q->win == win && q->K == K) {
-            *out = q;
-            return OFLK_OK;
-        }
-    return fail(OFLK_ERR_INVALID, "no pyramidal call of this shape (B=%d, %dx%d, %d levels, window %d, %d iterations) "
-                                  "has run on this device yet", B, W, H, L, win, K);
-}
-}  // namespace
-
 OFLK_API int oflk_pyramidal_last_level_flow(int B, int H, int W, int levels, int window_size, int iters, int level,
                                             int pair, float *u, float *v)
 {
-    HostCtx *c = nullptr;
-    std::unique_lock<std::mutex> lk;
-    int rc = acquire(g_device.load(), &c, lk);
+    HostCall call;
+    int rc = call.begin();
     if (rc) return rc;
     oflk_plan *p = nullptr;
-    if ((rc = cached_plan(*c, B, H, W, levels, window_size, iters, &p))) return rc;
+    if ((rc = cached_plan(*call.c, B, H, W, levels, window_size, iters, &p))) return rc;
     return oflk_plan_read_level_flow(p, level, pair, u, v, nullptr);
 }
 
 OFLK_API int oflk_pyramidal_last_uncertain(int B, int H, int W, int levels, int window_size, int iters, int *uncertain)
 {
-    HostCtx *c = nullptr;
-    std::unique_lock<std::mutex> lk;
-    int rc = acquire(g_device.load(), &c, lk);
+    HostCall call;
+    int rc = call.begin();
     if (rc) return rc;
     oflk_plan *p = nullptr;
-    if ((rc = cached_plan(*c, B, H, W, levels, window_size, iters, &p))) return rc;
+    if ((rc = cached_plan(*call.c, B, H, W, levels, window_size, iters, &p))) return rc;
     return oflk_plan_read_uncertain(p, uncertain, nullptr);
 }
 
@@ -2914,15 +2873,11 @@ OFLK_API int oflk_flow_metrics(const float *u, const float *v, int B, int H, int
     int rc = check_hw(u, v, H, W);
     if (rc) return rc;
     if (B < 1) return fail(OFLK_ERR_INVALID, "B must be >= 1");
-    HostCtx *c = nullptr;
-    std::unique_lock<std::mutex> lk;
-    if ((rc = acquire(g_device.load(), &c, lk))) return rc;
-    Arena ar;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
     const size_t n = (size_t)B * H * W;
-    float *d_u = nullptr, *d_v = nullptr;
-    if ((rc = ar.get(&d_u, n)) || (rc = ar.get(&d_v, n))) return rc;
-    HIP_TRY(hipMemcpyAsync(d_u, u, n * sizeof(float), hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(hipMemcpyAsync(d_v, v, n * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    float *d_u, *d_v;
+    if ((rc = call.upload(&d_u, u, n)) || (rc = call.upload(&d_v, v, n))) return rc;
     return metrics_device(d_u, d_v, B, H, W, u_true, v_true, y0, y1, x0, x1, out, nullptr);
 }
 
@@ -2942,24 +2897,18 @@ OFLK_API int oflk_compute_gradients(const float *prev, const float *curr, int H,
     int rc = check_hw(prev, curr, H, W);
     if (rc) return rc;
     if (!Ix || !Iy || !It) return fail(OFLK_ERR_INVALID, "NULL output");
-    HostCtx *c = nullptr;
-    std::unique_lock<std::mutex> lk;
-    if ((rc = acquire(g_device.load(), &c, lk))) return rc;
-    Arena ar;
-    size_t n = (size_t)H * W, bytes = n * sizeof(float);
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const size_t n = (size_t)H * W;
     float *d[5];
-    for (auto &q : d)
-        if ((rc = ar.get(&q, n))) return rc;
-    HIP_TRY(hipMemcpyAsync(d[0], prev, bytes, hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(hipMemcpyAsync(d[1], curr, bytes, hipMemcpyHostToDevice, nullptr));
+    if ((rc = call.upload(&d[0], prev, n)) || (rc = call.upload(&d[1], curr, n)) || (rc = call.alloc(&d[2], n)) ||
+        (rc = call.alloc(&d[3], n)) || (rc = call.alloc(&d[4], n)))
+        return rc;
     hipLaunchKernelGGL(k_gradients, grid2d(W, H, 1), dim3(256), 0, nullptr, (const float *)d[0],
                        (const float *)d[1], d[2], d[3], d[4], H, W);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(Ix, d[2], bytes, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipMemcpyAsync(Iy, d[3], bytes, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipMemcpyAsync(It, d[4], bytes, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return OFLK_OK;
+    if ((rc = call.to_host(Ix, d[2], n)) || (rc = call.to_host(Iy, d[3], n)) || (rc = call.to_host(It, d[4], n))) return rc;
+    return call.sync();
 }
 
 OFLK_API int oflk_from_gradients(const float *Ix, const float *Iy, const float *It, int H, int W,
@@ -2970,27 +2919,21 @@ OFLK_API int oflk_from_gradients(const float *Ix, const float *Iy, const float *
     if (!It || !u || !v) return fail(OFLK_ERR_INVALID, "NULL argument");
     int hw = 0;
     if ((rc = window_hw(window_size, &hw))) return rc;
-    HostCtx *c = nullptr;
-    std::unique_lock<std::mutex> lk;
-    if ((rc = acquire(g_device.load(), &c, lk))) return rc;
-    Arena ar;
-    size_t n = (size_t)H * W, bytes = n * sizeof(float);
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const size_t n = (size_t)H * W;
     float *d[5];
-    for (auto &q : d)
-        if ((rc = ar.get(&q, n))) return rc;
-    HIP_TRY(hipMemcpyAsync(d[0], Ix, bytes, hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(hipMemcpyAsync(d[1], Iy, bytes, hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(hipMemcpyAsync(d[2], It, bytes, hipMemcpyHostToDevice, nullptr));
+    if ((rc = call.upload(&d[0], Ix, n)) || (rc = call.upload(&d[1], Iy, n)) || (rc = call.upload(&d[2], It, n)) ||
+        (rc = call.alloc(&d[3], n)) || (rc = call.alloc(&d[4], n)))
+        return rc;
     LkArgs a{};
     a.prev = d[0]; a.curr = d[1]; a.aux = d[2];
     a.ou = d[3]; a.ov = d[4];
     a.H = H; a.W = W;
     rc = launch_lk<MODE_GRADS>(nullptr, nullptr, KC_LK_SINGLE, hw, a, 1);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(u, d[3], bytes, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipMemcpyAsync(v, d[4], bytes, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return OFLK_OK;
+    if ((rc = call.to_host(u, d[3], n)) || (rc = call.to_host(v, d[4], n))) return rc;
+    return call.sync();
 }
 
 namespace {
@@ -3023,30 +2966,25 @@ int build_pyramid_host(const float *image, int H, int W, int levels, double scal
     if ((rc = level_dims(H, W, levels, scale_factor, dims))) return rc;
     for (int l = 0; l < levels; l++)
         if (!out_levels[l]) return fail(OFLK_ERR_INVALID, "out_levels[%d] is NULL", l);
-    HostCtx *c = nullptr;
-    std::unique_lock<std::mutex> lk;
-    if ((rc = acquire(g_device.load(), &c, lk))) return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
     GaussW gauss;
     if (given) gauss = *given;
     else if ((rc = make_gauss(1.0 / scale_factor, &gauss))) return rc;
-    Arena ar;
-    size_t N = (size_t)H * W;
-    float *cur = nullptr, *nxt = nullptr, *tA = nullptr, *tB = nullptr;
-    if ((rc = ar.get(&cur, N)) || (rc = ar.get(&nxt, N)) || (rc = ar.get(&tA, N)) || (rc = ar.get(&tB, N)))
+    const size_t N = (size_t)H * W;
+    float *cur, *nxt, *tA, *tB;
+    if ((rc = call.upload(&cur, image, N)) || (rc = call.alloc(&nxt, N)) || (rc = call.alloc(&tA, N)) || (rc = call.alloc(&tB, N)))
         return rc;
-    HIP_TRY(hipMemcpyAsync(cur, image, N * sizeof(float), hipMemcpyHostToDevice, nullptr));
     std::memcpy(out_levels[levels - 1], image, N * sizeof(float));  // image.copy(), :40
     for (int l = levels - 2; l >= 0; l--) {
         int h = dims[2 * (l + 1)], w = dims[2 * (l + 1) + 1];
         int ho = dims[2 * l], wo = dims[2 * l + 1];
         rc = launch_pyr_down(nullptr, gauss, nullptr, cur, nxt, tA, tB, 1, h, w, ho, wo);
         if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(out_levels[l], nxt, (size_t)ho * wo * sizeof(float), hipMemcpyDeviceToHost,
-                               nullptr));
+        if ((rc = call.to_host(out_levels[l], nxt, (size_t)ho * wo))) return rc;
         std::swap(cur, nxt);
     }
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return OFLK_OK;
+    return call.sync();
 }
 }  // namespace
 
@@ -3056,23 +2994,18 @@ OFLK_API int oflk_warp(const float *image, const float *flow_u, const float *flo
     int rc = check_hw(image, flow_u, H, W);
     if (rc) return rc;
     if (!flow_v || !out) return fail(OFLK_ERR_INVALID, "NULL argument");
-    HostCtx *c = nullptr;
-    std::unique_lock<std::mutex> lk;
-    if ((rc = acquire(g_device.load(), &c, lk))) return rc;
-    Arena ar;
-    size_t n = (size_t)H * W, bytes = n * sizeof(float);
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const size_t n = (size_t)H * W;
     float *d[4];
-    for (auto &q : d)
-        if ((rc = ar.get(&q, n))) return rc;
-    HIP_TRY(hipMemcpyAsync(d[0], image, bytes, hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(hipMemcpyAsync(d[1], flow_u, bytes, hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(hipMemcpyAsync(d[2], flow_v, bytes, hipMemcpyHostToDevice, nullptr));
+    if ((rc = call.upload(&d[0], image, n)) || (rc = call.upload(&d[1], flow_u, n)) || (rc = call.upload(&d[2], flow_v, n)) ||
+        (rc = call.alloc(&d[3], n)))
+        return rc;
     hipLaunchKernelGGL(k_warp, grid2d(W, H, 1), dim3(256), 0, nullptr, (const float *)d[0],
                        (const float *)d[1], (const float *)d[2], d[3], H, W);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, d[3], bytes, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return OFLK_OK;
+    if ((rc = call.to_host(out, d[3], n))) return rc;
+    return call.sync();
 }
 
 OFLK_API int oflk_upsample_flow(const float *flow_u, const float *flow_v, int Hc, int Wc, int Ht,
@@ -3081,16 +3014,13 @@ OFLK_API int oflk_upsample_flow(const float *flow_u, const float *flow_v, int Hc
     int rc = check_hw(flow_u, flow_v, Hc, Wc);
     if (rc) return rc;
     if ((rc = check_hw(u_out, v_out, Ht, Wt))) return rc;
-    HostCtx *c = nullptr;
-    std::unique_lock<std::mutex> lk;
-    if ((rc = acquire(g_device.load(), &c, lk))) return rc;
-    Arena ar;
-    size_t nc = (size_t)Hc * Wc, nt = (size_t)Ht * Wt;
-    float *du = nullptr, *dv = nullptr, *ou = nullptr, *ov = nullptr;
-    if ((rc = ar.get(&du, nc)) || (rc = ar.get(&dv, nc)) || (rc = ar.get(&ou, nt)) || (rc = ar.get(&ov, nt)))
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const size_t nc = (size_t)Hc * Wc, nt = (size_t)Ht * Wt;
+    float *du, *dv, *ou, *ov;
+    if ((rc = call.upload(&du, flow_u, nc)) || (rc = call.upload(&dv, flow_v, nc)) || (rc = call.alloc(&ou, nt)) ||
+        (rc = call.alloc(&ov, nt)))
         return rc;
-    HIP_TRY(hipMemcpyAsync(du, flow_u, nc * sizeof(float), hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(hipMemcpyAsync(dv, flow_v, nc * sizeof(float), hipMemcpyHostToDevice, nullptr));
     ResampleArgs r{};
     r.in[0] = du; r.in[1] = dv;
     r.out[0] = ou; r.out[1] = ov;
@@ -3102,8 +3032,6 @@ OFLK_API int oflk_upsample_flow(const float *flow_u, const float *flow_v, int Hc
     r.nplanes = 2;
     r.apply_scale = 1;
     if ((rc = launch_upsample(nullptr, nullptr, r, 1))) return rc;
-    HIP_TRY(hipMemcpyAsync(u_out, ou, nt * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipMemcpyAsync(v_out, ov, nt * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return OFLK_OK;
+    if ((rc = call.to_host(u_out, ou, nt)) || (rc = call.to_host(v_out, ov, nt))) return rc;
+    return call.sync();
 }

@@ -281,7 +281,7 @@ def test_klt_equals_detection_then_tracks_small(u8):
 
 @pytest.mark.parametrize("u8", [False, True], ids=["f32", "u8"])
 def test_klt_equals_detection_then_tracks_chunked_1080p(u8):
-    """17 frames of 1080p: four chunks under fb_chunk_pairs"""
+    """17 frames of 1080p: four chunks under chunk_pairs"""
     frames = _video(17, 1080, 1920, seed=8, u8=u8)
     n, vis = _klt_vs_pieces(frames, 2000, 0.01, 10.0)
     assert n == 2000 and vis[-1].mean() > 0.5

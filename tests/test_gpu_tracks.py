@@ -181,7 +181,7 @@ def test_sequence_tracks_equal_statement_on_fb_flows(T, H, W):
 
 
 def test_chunked_1080p_equals_host_form_on_the_downloaded_flows():
-    """T = 18 at 1080p: run_sequence_fb's rule cuts the 17 pairs into chunks of 4, 4, 4, 4 and 1"""
+    """T = 18 at 1080p: the chunk rule (chunk_pairs) cuts the 17 pairs into chunks of 4, 4, 4, 4 and 1"""
     import flow_metrics
     import lucas_kanade_pyramidal as P
 

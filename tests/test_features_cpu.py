@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import feature_model as M
+import feature_scenes as FS
 
 ROOT = Path(__file__).resolve().parents[1]
 FEATURE_SYMBOLS = ["oflk_corner_score", "oflk_corner_score_host", "oflk_corner_score_host_u8", "oflk_good_features_workspace",
@@ -270,3 +271,136 @@ def test_new_symbols_are_declared_and_exported():
         assert name in declared, f"{name} not declared in include/oflk.h"
         assert hasattr(L, name), f"{name} not exported by liboflk.so"
         assert name in _oflk.SIGNATURES
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the scenes of tests/test_gpu_feature_edges.py (tests/feature_scenes.py): each reaches its path, and the statement's
+# greedy equals a brute force without the grid on it
+# ---------------------------------------------------------------------------------------------------------------
+NX = FS.f32_next
+EDGE_MDS = [0.0, 1.0, NX(1.0, np.inf), 2.5, 7.0, NX(7.0, -np.inf), NX(7.0, np.inf), 10.0, FS.CHAIN_MD, NX(8.0, np.inf)]
+
+
+def _same_selection(a, b, what):
+    n, xy, sc = a
+    m, wxy, wsc = b
+    assert n == m, (what, n, m)
+    assert np.array_equal(xy, wxy, equal_nan=True), what
+    assert np.array_equal(sc.view(np.int32), wsc.view(np.int32)), what
+
+
+@pytest.fixture(scope="module")
+def full_size_scenes():
+    return {"lattice": M.score(FS.lattice(), 5), "lattice2": M.score(FS.lattice(contrasts=(190.0, 150.0)), 5),
+            "klt": M.score(FS.lattice(shift=(0, 0)), 5),
+            **{o: M.score(FS.chain_rows(o), 5) for o in FS.CHAIN_ORDERS}}
+
+
+def test_lattice_scenes_tie_more_than_three_slabs(full_size_scenes):
+    """the descent must cut slabs inside the raster-index digits: more than 3 x 4 096 candidates share the top score"""
+    for name in ("lattice", "lattice2", "klt"):
+        assert FS.top_ties(full_size_scenes[name]) > 3 * 4096, name
+
+
+def test_chain_scenes_chain_across_batches(full_size_scenes):
+    """a run of at least 300 consecutive candidates in priority order, each conflicting with the one before it; in the
+    alternating scene each blob has its own score, high and low in turn"""
+    for order in ("increasing", "decreasing"):
+        assert FS.conflict_runs(full_size_scenes[order], 0.0, FS.CHAIN_MD) >= 300, order
+    S = full_size_scenes["alternating"]
+    ys, xs, _ = M.candidates(S, 0.0)
+    s = S[ys, xs]
+    assert len(np.unique(s)) * 4 == len(s), "four tied plateau pixels per blob, every blob its own score"
+    row = S[3, 3:3 + 7 * 8:7]
+    assert (row[0::2, None] > row[None, 1::2]).all(), row
+
+
+def test_chain_md_conflicts_with_neighbours_only():
+    """in a chain row every pixel of a blob lies within CHAIN_MD of every pixel of its neighbours and not within it of
+    any pixel of the blob after next, or of another row"""
+    s, g, md2 = FS.CHAIN_STEP, FS.CHAIN_GAP, FS.CHAIN_MD ** 2
+    px = [(dx, dy) for dx in (0, 1) for dy in (0, 1)]
+    assert all((s + bx - ax) ** 2 + (by - ay) ** 2 < md2 for ax, ay in px for bx, by in px)
+    assert all((2 * s + bx - ax) ** 2 + (by - ay) ** 2 >= md2 for ax, ay in px for bx, by in px)
+    assert (g - 1) ** 2 >= md2
+
+
+def test_exact_pair_scene():
+    """every dot is one candidate, and candidates lie at each exact offset"""
+    f, pairs = FS.exact_pairs()
+    S = M.score(f, 3)
+    assert len(M.candidates(S, 0.0)[0]) == 2 * len(pairs)
+    assert set(FS.PAIR_OFFSETS) <= FS.candidate_offsets(S)
+    ys, xs, _ = M.candidates(S, 0.0)
+    rank = {(int(x), int(y)): i for i, (y, x) in enumerate(zip(ys, xs))}
+    same = [rank[a] // 256 == rank[b] // 256 for _, _, a, b in pairs]
+    assert any(same) and not all(same), "some pairs share a 256-key batch, some do not"
+
+
+def test_value_scenes_reach_overflow_underflow_and_non_finite_pixels():
+    for H, W in ((17, 65), (47, 1000)):
+        v = FS.value_frames(H, W, seed=3)
+        for win in M.WINDOWS:
+            tiny = M.score(v["tiny"], win)
+            assert (tiny > 0).any() and (tiny[tiny > 0] < np.finfo(np.float32).tiny).all(), "subnormal scores"
+        with np.errstate(over="ignore", invalid="ignore"):
+            a, b, c = M.tensor(v["huge"], 5)
+        assert not np.isfinite(a).all() and (M.score(v["huge"], 3) > 0).any(), "overflowing sums next to finite scores"
+        nf = v["nonfinite"]
+        assert np.isnan(nf).any() and np.isposinf(nf).any() and np.isneginf(nf).any()
+        assert (M.score(nf, 5) > 0).any()
+        assert (v["negative"] < 0).all() and v["u16"].max() > 60000 and v["unit"].max() < 1.0
+
+
+def test_tall_frame_has_its_best_blobs_past_the_grid_caps():
+    f = FS.tall_frame()
+    assert f.shape == (FS.TALL_H, FS.TALL_W) and (FS.TALL_H + 15) // 16 > 65535 and (FS.TALL_H + 3) // 4 > 65535
+    hot = np.flatnonzero((f == 230.0).any(1))
+    assert hot.min() >= FS.TALL_H - 64 and hot.max() >= 16 * 65535
+    warm = np.flatnonzero((f == 210.0).any(1))
+    assert warm.min() >= 262136 and warm.max() >= 4 * 65535
+
+
+def test_truncation_is_the_smaller_max_corners():
+    S = M.score(FS.lattice(240, 320), 5)
+    for md in (0.0, NX(7.0, np.inf)):
+        full = M.select(S, 0.0, md, 100000)
+        for K in (1, 255, 256, 257, full[0] - 1, full[0], full[0] + 1):
+            _same_selection(M.select(S, 0.0, md, K), FS.truncate(full, K), f"md={md} K={K}")
+
+
+def _crop_scenes():
+    """every new scene at 240 x 320 or smaller, keeping its spacing: (name, S, md values)"""
+    out = [("lattice", M.score(FS.lattice(240, 320), 5), EDGE_MDS),
+           ("lattice2", M.score(FS.lattice(240, 320, contrasts=(190.0, 150.0)), 5), EDGE_MDS),
+           ("klt", M.score(FS.lattice(240, 320, shift=(3, 6)), 5), EDGE_MDS)]
+    out += [(o, M.score(FS.chain_rows(o, 240, 320), 5), EDGE_MDS) for o in FS.CHAIN_ORDERS]
+    f, _ = FS.exact_pairs(rows=4, cols=14)
+    out.append(("pairs", M.score(f, 3), [5.0, NX(5.0, np.inf), NX(5.0, -np.inf), 2.5, np.sqrt(5.0), np.sqrt(8.0)]))
+    out += [(f"grid {H}x{W}", M.score(FS.grid_frame(H, W), 5), FS.grid_mds(H, W)) for H, W in FS.GRID_SHAPES]
+    with np.errstate(over="ignore", invalid="ignore"):
+        out += [(f"values {k}", M.score(v, 5), [0.0, 2.5, 7.0]) for k, v in FS.value_frames(47, 191, seed=5).items()]
+    out += [(f"small {i}", M.score(f, 5), [0.0, 2.5]) for i, f in enumerate(FS.small_frames())]
+    out.append(("unlike blob", M.score(FS.small_frames(240, 320)[4], 5), [0.0, 2.5]))
+    tall = FS.tall_frame()
+    out.append(("tall bottom", M.score(tall[-240:], 5), [0.0, 5.0]))
+    return out
+
+
+@pytest.mark.parametrize("name,S,mds", _crop_scenes(), ids=lambda v: v if isinstance(v, str) else "")
+def test_statement_greedy_equals_brute_force_on_scene_crops(name, S, mds):
+    for md in mds:
+        for q in (0.0, 0.01):
+            full = FS.brute_select(S, q, md, S.size + 1)
+            for K in sorted({1, 255, 256, 257, max(full[0] - 1, 1), full[0] + 1}):
+                _same_selection(M.select(S, q, md, K), FS.truncate(full, K), f"{name} q={q} md={md!r} K={K}")
+
+
+@pytest.mark.parametrize("name", ["lattice", "lattice2", "increasing", "decreasing", "alternating"])
+def test_statement_greedy_at_full_size_is_ordered_and_spaced(full_size_scenes, name):
+    """at 1080p the brute force is too slow: the accepted points are in priority order and no two lie closer than md"""
+    S = full_size_scenes[name]
+    for md in (NX(1.0, np.inf), 2.5, NX(7.0, np.inf), FS.CHAIN_MD):
+        n, xy, sc = M.select(S, 0.0, md, 30000)
+        assert n > 4096
+        FS.check_greedy_output(S, md, n, xy, sc)

@@ -382,7 +382,16 @@ int oflk_good_features(const void *d_frames, int u8, int F, int H, int W, int wi
                        float *d_xy, float *d_score, void *stream);
 
 /* After oflk_plan_pyramidal: copy the residual log / iteration counts of the last
- * enqueued pass to the host (synchronises `stream`).  Either pointer may be NULL. */
+ * enqueued pass to the host (synchronises `stream`).  Either pointer may be NULL.
+ * A logged mean is NaN exactly where the reference's np.mean(np.abs(d)) is NaN, and +inf exactly where it is +inf
+ * (finite frames give both: window products or the solve's numerators that overflow); a finite logged mean is the
+ * device's fixed-point mean, within oflk_device_mean_error of the exact mean.  One exception: a block whose FINITE |d|
+ * sum passes 2^28 px is clamped there, so where |d| is that large the logged mean is below the reference's and at
+ * least 2^28 / (H*W) px, and the printed log can differ from the reference's stdout (tests/test_gpu_ranges.py asserts
+ * this statement).  Exit decisions and iteration counts are the reference's.
+ * Non-finite values: NaN and +-inf pixels and flows give the reference's values in every entry point, flows and stages
+ * (oflk_gradients included: the zero taps of the Sobel kernels are multiplied too, so 0 * inf is NaN, as in the
+ * reference's convolve2d). */
 int oflk_plan_read_log(oflk_plan *plan, float *residual_log, int *iters_run, void *stream);
 
 /* After oflk_plan_pyramidal + read_log: uncertain[b*levels + l] has bit k set when the early-exit test
@@ -439,7 +448,10 @@ int oflk_plan_read_level_flow(oflk_plan *plan, int level, int pair, float *u, fl
  *   - coarser levels: exact.
  * The envelope is the set of (levels, iterations) cells of the 5x5 window where the worst mean EPE of the 13 verification
  * patterns (320x240) against the reference is at most a third of the north star's bar of 1e-4 px and every iteration count
- * is the reference's: {(1,1), (1,2), (3,2), (3,3)}.  Measured worst mean EPE per cell (tests/test_tolerant_model.py):
+ * is the reference's: {(1,1), (1,2), (3,2), (3,3)}.  The bar is promised for frames whose pixels lie in [-255, 255] (the
+ * 8-bit range and its normalised, signed, subnormal and underflowing forms: tests/test_gpu_ranges.py, every cell); on
+ * larger values it is not (16-bit frames with a 25 000 temporal step: mean EPE 0.13 .. 0.3 px at (1,1) and (1,2), 30 ..
+ * 100 px at (3,2) and (3,3)).  Measured worst mean EPE per cell (tests/test_tolerant_model.py):
  *       L \ K    1        2        3        4        5
  *         1      0        2.3e-5   4.6e-4   5.6e-4   1.7e-3
  *         2      3.5e-5   7.7e-5   9.6e-5   5.7e-4   2.6e-4

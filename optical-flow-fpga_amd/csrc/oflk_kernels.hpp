@@ -678,15 +678,30 @@ constexpr int kAccShards = 8;
 constexpr int kAccStride = 64;   // u64 words between shards (512 B: every shard on a line, and likely a channel, of its own)
 constexpr double kAccScale = 1048576.0;       // 2^20 steps per pixel of |d|
 constexpr double kAccBlockMax = 268435456.0;  // 2^28: a block's sum is clamped here (also catches NaN)
+constexpr int kAccNanWord = 2;   // word 2 of shard 0: non-finite partials of |du| / |dv| (lk_report_nan)
 
 __device__ __forceinline__ size_t acc_index(int b, int l, int k, int L, int K)
 {
     return ((((size_t)b * L + l) * K + k) * kAccShards) * kAccStride;
 }
 
+// A NaN or +inf partial (a NaN or infinite flow: window products or the solve's numerators that overflow) is clamped
+// to kAccBlockMax like any large one (NaN fails every compare), so the exit decision stays "not below", as with the
+// reference's NaN / inf mean.  The logged mean must be NaN / inf too: the partial sets its bit in the (pair, level,
+// iteration) flag word -- bit 0 / 1: a |du| / |dv| partial was NaN, bit 2 / 3: it was +inf -- and k_export_fixup logs
+// NaN, else +inf, for it.  |d| >= 0, so no partial is -inf.  Before the clamp.
+__device__ __forceinline__ void lk_report_nan(unsigned long long *acc0, double su, double sv)
+{
+    const double inf = __builtin_inf();
+    const unsigned long long bits = (su != su ? 1ull : 0ull) | (sv != sv ? 2ull : 0ull) | (su == inf ? 4ull : 0ull) |
+                                    (sv == inf ? 8ull : 0ull);
+    if (bits) __hip_atomic_fetch_or(acc0 + kAccNanWord, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // one thread per block, after the block's last tile
 __device__ __forceinline__ void lk_report(const LkArgs &a, int b, double su, double sv)
 {
+    lk_report_nan(a.acc + acc_index(b, a.level, a.iter, a.L, a.K), su, sv);
     su = su < kAccBlockMax ? su : kAccBlockMax;
     sv = sv < kAccBlockMax ? sv : kAccBlockMax;
     unsigned long long *slot = a.acc + acc_index(b, a.level, a.iter, a.L, a.K) + kAccStride * (blockIdx.x & (kAccShards - 1));
@@ -2894,6 +2909,15 @@ __global__ __launch_bounds__(256) void k_gradients(const float *__restrict__ pre
     iy = fmaf(a_mp, 0.125f, iy);
     iy = fmaf(a_m0, 0.25f, iy);
     iy = fmaf(a_mm, 0.125f, iy);
+    // convolve2d also multiplies the kernels' zero taps (the middle column of Sobel x, the middle row of Sobel y): they
+    // add +-0 to a sum, which only moves the sign of a zero result, except that 0 * inf is NaN.  Added last, as fmas.
+    const float a_00 = avg(y, x);
+    ix = fmaf(a_p0, 0.0f, ix);
+    ix = fmaf(a_00, 0.0f, ix);
+    ix = fmaf(a_m0, 0.0f, ix);
+    iy = fmaf(a_0p, 0.0f, iy);
+    iy = fmaf(a_00, 0.0f, iy);
+    iy = fmaf(a_0m, 0.0f, iy);
     size_t i = base + (size_t)y * W + x;
     Ix[i] = ix;
     Iy[i] = iy;
@@ -3011,6 +3035,11 @@ __global__ __launch_bounds__(256) void k_export_fixup(ExportArgs a)
             lk_totals(a.acc, b, l, k, a.L, a.K, tu, tv);
             mu = lk_mean_of(tu, a.counts[l]);
             mv = lk_mean_of(tv, a.counts[l]);
+            const unsigned long long nf = a.acc[acc_index(b, l, k, a.L, a.K) + kAccNanWord];   // lk_report_nan
+            if (nf & 4ull) mu = __builtin_inff();
+            if (nf & 8ull) mv = __builtin_inff();
+            if (nf & 1ull) mu = __builtin_nanf("");
+            if (nf & 2ull) mv = __builtin_nanf("");
             // decision "both below": it could have gone the other way iff one mean is inside the band
             // while the other is not clearly above it
             const bool near_u = tu >= a.guard_lo[l] && tu <= a.guard_hi[l], near_v = tv >= a.guard_lo[l] && tv <= a.guard_hi[l];

@@ -553,6 +553,7 @@ __global__ __launch_bounds__(256) OFLK_LKS_ATTR void k_lks(LkArgs a)
             dsu += __shfl_xor(dsu, m, 64);
             dsv += __shfl_xor(dsv, m, 64);
         }
+        if (lane == 0) lk_report_nan(a.acc + acc_index(b, a.level, a.iter, a.L, a.K), dsu, dsv);
         dsu = dsu < kAccBlockMax ? dsu : kAccBlockMax;   // (also catches NaN)
         dsv = dsv < kAccBlockMax ? dsv : kAccBlockMax;
         long long tu = __double2ll_rn(dsu * kAccScale), tv = __double2ll_rn(dsv * kAccScale);

@@ -454,11 +454,13 @@ static inline int mirror_tap(int idx, int len)
 
 static inline float bilinear_f64(const float *img, int H, int W, double y, double x)
 {
-    /* map_coordinate(): constant mode -> out of [0, len-1] means cval */
-    if (y < 0.0 || y > (double)(H - 1) || x < 0.0 || x > (double)(W - 1)) return 0.0f;
-    /* NaN coordinates: every comparison above is false; floor(NaN) is NaN and
-     * the cast below is undefined in C; SciPy has the same hole.  The path
-     * never produces NaN coordinates from finite inputs. */
+    /* map_coordinate(): constant mode -> out of [0, len-1] means cval.  Written
+     * as "not inside" so that a NaN coordinate is outside too: SciPy returns
+     * cval for NaN and +-inf coordinates, and the casts below are then only
+     * reached with finite values in range.  NaN coordinates do occur: finite
+     * frames whose window products overflow give NaN flows (det = inf, the
+     * numerator inf - inf), and the pyramidal loop warps with them. */
+    if (!(y >= 0.0 && y <= (double)(H - 1) && x >= 0.0 && x <= (double)(W - 1))) return 0.0f;
     double fy = floor(y), fx = floor(x);
     int y0 = (int)fy, x0 = (int)fx;
     /* get_spline_interpolation_weights(order 1): w0 = 1 - frac, w1 = 1 - w0 */

@@ -196,6 +196,10 @@ static void warp_variant(const float *img, const float *u, const float *v, int H
             } else {
                 /* fractions from the flow alone, in fp32: frac(gx + u) = u - floor(u) (exact in fp32 unless u is a tiny
                  * negative number); integer cell = gx + (int)floor(u) */
+                if (!(fabsf(u[i]) < 1e9f) || !(fabsf(v[i]) < 1e9f)) {   /* NaN, inf, far outside: before any cast */
+                    out[i] = 0.0f;
+                    continue;
+                }
                 const float flu = floorf(u[i]), flv = floorf(v[i]);
                 float rx = u[i] - flu, ry = v[i] - flv;
                 long x0 = (long)gx + (long)flu, y0 = (long)gy + (long)flv;
@@ -204,7 +208,7 @@ static void warp_variant(const float *img, const float *u, const float *v, int H
                 /* inside: 0 <= x0 + rx <= W-1 */
                 const int in_x = x0 >= 0 && (x0 < W - 1 || (x0 == W - 1 && rx == 0.0f));
                 const int in_y = y0 >= 0 && (y0 < H - 1 || (y0 == H - 1 && ry == 0.0f));
-                if (!(in_x && in_y) || !(fabsf(u[i]) < 1e9f) || !(fabsf(v[i]) < 1e9f)) {
+                if (!(in_x && in_y)) {
                     out[i] = 0.0f;
                     continue;
                 }

@@ -528,12 +528,29 @@ int oflk_plan_kernel_times(oflk_plan *plan, const char **names, double *total_ms
 /* compute_all_metrics(u_pred, v_pred, u_true, v_true, mask) of python/flow_metrics.py:166-201
  * (mean_absolute_error :14-40, root_mean_square_error :43-70, endpoint_error :73-103,
  * angular_error :106-163) for the rectangular test regions the verifier builds
- * (mask[y0:y1, x0:x1] = True with NumPy slice semantics, python/optical_flow_verifier.py:96-138).
- *   u_true, v_true : host arrays [B], the constant ground-truth vector of each pair
- *   out            : host array [B][5] = mae_u, mae_v, rmse, epe, aae (degrees)
- * Element-wise arithmetic is the reference's fp32; sums and arccos are fp64, so values agree
- * with the reference's fp32 pairwise means to ~1e-6 relative (not bit for bit).
- * oflk_plan_metrics reads device-resident flows [B][H][W] of the plan's shape and
+ * (mask[y0:y1, x0:x1] = True, python/optical_flow_verifier.py:96-138).
+ *   u_true, v_true : host arrays [B], the constant ground-truth vector of each pair, taken as float32
+ *   out            : host array [B][5] = mae_u, mae_v, rmse, epe, aae (degrees), each a float32 value
+ * The statement (tests/metrics_model.py states it in NumPy, tests/test_gpu_metrics_edges.py holds the kernel to it):
+ *   rectangle  NumPy slice semantics per bound: i < 0 -> i + n, then clip to [0, n]; bounds beyond the frame are
+ *              clipped, a reversed or zero-width slice is empty.  No pixel outside the rectangle is read.
+ *   per pixel  the reference's fp32 operations, each rounded on its own: eu = u - ut, ev = v - vt, sq = eu*eu + ev*ev,
+ *              sqrt(sq), mag2 = u*u + v*v, c = (u*ut + v*vt + 1) / (sqrt(mag2 + 1) * sqrt(ut*ut + vt*vt + 1)), c clipped
+ *              to [-1, 1] as np.clip does: a NaN c stays NaN
+ *   sums       of |eu|, |ev|, sq, sqrt(sq) and acos((double)c) * 57.29577951308232 in fp64 over the n pixels
+ *   out        (float)(sum / n) for mae_u, mae_v, epe, aae; sqrtf((float)(sum_sq / n)) for rmse.  An empty rectangle
+ *              gives NaN (0 / 0).  aae is 0.0 exactly when sqrt(ut^2 + vt^2) < 1e-6 and every pixel of the rectangle
+ *              has sqrtf(mag2) < 1e-6f ("nothing moves and nothing was predicted", :141-145): a NaN pixel has not, an
+ *              empty rectangle has.
+ * Non-finite inputs give the reference's values: a NaN flow value inside the rectangle makes that plane's mae, rmse,
+ * epe and aae NaN; an infinite one makes its mae, rmse and epe +inf and aae NaN (inf / inf); a finite value whose
+ * square overflows makes rmse and epe +inf and leaves aae finite (that pixel's cosine is 0); values outside the
+ * rectangle change nothing.  A finite result is within one float32 ulp of the exact-sum value (the fp64 sums of n <=
+ * 3.3e7 non-negative terms are within 3.7e-9 relative) and agrees with the reference's fp32 pairwise means to NumPy's
+ * own bound, (ceil(n / 8192) + 32) * 2^-24 relative (aae: plus NumPy's fp32 arccos, 1.5e-5 degrees per term); it is
+ * not bit-equal to them.  A pair's numbers do not depend on the batch it is in; any B >= 1 is accepted (beyond 65 535
+ * pairs a block of the kernel walks several).  NULL pointers and B, H, W < 1 return OFLK_ERR_INVALID.
+ * oflk_plan_metrics reads device-resident flows [B][H][W] of the plan's shape (4-byte alignment is enough) and
  * synchronises `stream`; oflk_flow_metrics takes host arrays. */
 int oflk_plan_metrics(oflk_plan *plan, const float *d_u, const float *d_v, const float *u_true,
                       const float *v_true, int y0, int y1, int x0, int x1, double *out, void *stream);

@@ -2829,10 +2829,11 @@ int metrics_device(const float *d_u, const float *d_v, int B, int H, int W, cons
     MetricArgs a{};
     a.u = d_u; a.v = d_v;
     a.u_true = d_true; a.v_true = d_true + B;
-    a.H = H; a.W = W;
+    a.B = B; a.H = H; a.W = W;
     a.y0 = y0; a.y1 = y1; a.x0 = x0; a.x1 = x1;
     a.partial = d_part;
-    hipLaunchKernelGGL(k_flow_metrics, dim3(kMetricBlocks, (unsigned)B), dim3(256), 0, s, a);
+    // gridDim.y stops at 65 535: beyond it a block walks several pairs, each pair's partials laid out as before
+    hipLaunchKernelGGL(k_flow_metrics, dim3(kMetricBlocks, (unsigned)std::min(B, kMetricMaxGridY)), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError());
     std::vector<double> part((size_t)B * kMetricBlocks * kMetricTerms);
     HIP_TRY(hipMemcpyAsync(part.data(), d_part, part.size() * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -2841,8 +2842,7 @@ int metrics_device(const float *d_u, const float *d_v, int B, int H, int W, cons
         double t[kMetricTerms] = {0, 0, 0, 0, 0, 0};
         for (int k = 0; k < kMetricBlocks; k++) {
             const double *q = &part[((size_t)b * kMetricBlocks + k) * kMetricTerms];
-            for (int i = 0; i < kMetricTerms - 1; i++) t[i] += q[i];
-            t[kMetricTerms - 1] = std::max(t[kMetricTerms - 1], q[kMetricTerms - 1]);
+            for (int i = 0; i < kMetricTerms; i++) t[i] += q[i];
         }
         double *o = out + (size_t)b * 5;
         const double n = (double)count;   // an empty mask gives nan, as np.mean of an empty array does
@@ -2850,9 +2850,10 @@ int metrics_device(const float *d_u, const float *d_v, int B, int H, int W, cons
         o[1] = (double)(float)(t[1] / n);
         o[2] = (double)std::sqrt((float)(t[2] / n));   // np.sqrt of the fp32 mean (:69)
         o[3] = (double)(float)(t[3] / n);
-        // "nothing moves and nothing was predicted" (:143-146)
+        // "nothing moves and nothing was predicted" (:143-146): t[5] counts the region's pixels that are not below 1e-6,
+        // NaN ones included; an empty region has none
         const double mt = std::sqrt((double)u_true[b] * u_true[b] + (double)v_true[b] * v_true[b]);
-        o[4] = (mt < 1e-6 && t[5] < (double)1e-6f) ? 0.0 : (double)(float)(t[4] / n);
+        o[4] = (mt < 1e-6 && t[5] == 0.0) ? 0.0 : (double)(float)(t[4] / n);
     }
     return OFLK_OK;
 }
@@ -2873,6 +2874,7 @@ OFLK_API int oflk_flow_metrics(const float *u, const float *v, int B, int H, int
     int rc = check_hw(u, v, H, W);
     if (rc) return rc;
     if (B < 1) return fail(OFLK_ERR_INVALID, "B must be >= 1");
+    if (!u_true || !v_true || !out) return fail(OFLK_ERR_INVALID, "NULL argument");   // before anything is uploaded
     HostCall call;
     if ((rc = call.begin())) return rc;
     const size_t n = (size_t)B * H * W;

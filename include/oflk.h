@@ -18,6 +18,9 @@
  *     oflk_last_error() returns a human-readable message for the calling thread.
  *   - There is NO CPU fallback: every compute entry point runs hand-written HIP
  *     kernels and fails with OFLK_ERR_NO_DEVICE when no gfx950 GPU is usable.
+ *   - Frames are at most 2^23 - 1 (8 388 607) rows and columns and fewer than 2^30 pixels (plans: 2^29): the kernels form
+ *     row offsets with the signed 24-bit multiply and byte offsets in 32 bits.  Anything larger is refused with
+ *     OFLK_ERR_UNSUPPORTED before any device call.
  *   - "host" entry points take host pointers and are synchronous (H2D, kernels,
  *     D2H inside the call).  "plan" entry points take device pointers, enqueue
  *     on a caller-supplied hipStream_t and return without synchronising.
@@ -74,7 +77,12 @@ int oflk_single_scale(const float *prev, const float *curr, int H, int W, int wi
 int oflk_pyramid_level_dims(int H, int W, int levels, double scale_factor, int *dims_out);
 
 /* build_gaussian_pyramid(image, num_levels, scale_factor) -> [coarse .. fine]
- * replaces python/lucas_kanade_pyramidal.py:23-63; out_levels[l] must hold H_l*W_l floats */
+ * replaces python/lucas_kanade_pyramidal.py:23-63; out_levels[l] must hold H_l*W_l floats.
+ * Any scale_factor in (0, 1] whose Gaussian radius int(4 / scale_factor + 0.5) is at most 64 (scale_factor >= about 0.063).
+ * A step runs the fused kernel (k_pyr_down: blur and resampling in one launch, the blurred tile in LDS) when the radius is 8,
+ * i.e. scale_factor in (8/17, 8/15], and every 32 x 16 output tile's source span fits the 66 x 34 LDS tile: always at 0.5,
+ * at some sizes elsewhere in that band.  Every other step runs the unfused chain (k_blur along y, k_blur along x,
+ * k_resample) with the same operations in the same order.  oflk_pyramid_step_fused tells which. */
 int oflk_build_pyramid(const float *image, int H, int W, int levels, double scale_factor,
                        float *const *out_levels);
 
@@ -93,9 +101,22 @@ int oflk_warp(const float *image, const float *flow_u, const float *flow_v, int 
               float *out);
 
 /* upsample_flow(flow_u, flow_v, (Ht, Wt)) -> (u, v)
- * replaces python/lucas_kanade_pyramidal.py:100-138 */
+ * replaces python/lucas_kanade_pyramidal.py:100-138.  Any coarse and target shape, shrinking included.  The staged kernel
+ * (k_upsample: the coarse cells of a 256 x 16 output block in LDS) serves every target whose blocks each span at most 136
+ * coarse columns and 10 coarse rows: every ratio of about 1.9 or more per axis (ratio 2 at every size), and any ratio on a
+ * coarse field of at most 10 x 136.  Smaller ratios, equal shapes and shrinking targets on larger fields run the gathering
+ * kernel (k_resample) with the same arithmetic.  oflk_upsample_staged tells which. */
 int oflk_upsample_flow(const float *flow_u, const float *flow_v, int Hc, int Wc, int Ht, int Wt,
                        float *u_out, float *v_out);
+
+/* Which kernel a stage call runs: host-only, never fail (0 for sizes below 1), usable without a GPU.  They evaluate the
+ * launchers' own decisions, so that a test can name the kernel it compares.
+ * oflk_upsample_staged: 1 when oflk_upsample_flow (and the flow upsampling of a pyramidal pass) of Hc x Wc to Ht x Wt runs
+ * k_upsample, 0 when it runs k_resample.
+ * oflk_pyramid_step_fused: 1 when the pyramid step from h x w to ho x wo with a Gaussian of this radius runs k_pyr_down, 0
+ * when it runs the unfused chain (always 0 for a radius other than 8). */
+int oflk_upsample_staged(int Hc, int Wc, int Ht, int Wt);
+int oflk_pyramid_step_fused(int h, int w, int ho, int wo, int radius);
 
 /* lucas_kanade_pyramidal(frame_prev, frame_curr, num_levels, window_size, num_iterations) -> (u, v)
  * replaces python/lucas_kanade_pyramidal.py:141-228.

@@ -100,6 +100,10 @@ double np_pairwise_f64(const double *a, size_t n)
     return np_pairwise_f64(a, n2) + np_pairwise_f64(a + n2, n - n2);
 }
 
+// The kernels form row offsets with __mul24, the SIGNED 24-bit multiply (v_mad_i32_i24: both operands sign-extended from
+// bit 23): a row index or a width of 2^23 or more would read as negative.  Every entry check refuses such frames.
+constexpr int kMaxDim = 1 << 23;
+
 int make_gauss(double sigma, GaussW *g)
 {
     if (!(sigma > 0.0)) return fail(OFLK_ERR_INVALID, "sigma must be positive");
@@ -764,8 +768,10 @@ OFLK_API int oflk_plan_create(oflk_plan **out, int device, int B, int H, int W, 
     *out = nullptr;
     if (B < 1) return fail(OFLK_ERR_INVALID, "B must be >= 1");
     if (iters < 0) return fail(OFLK_ERR_INVALID, "iters must be >= 0");
-    if ((size_t)H * (size_t)W >= ((size_t)1 << 29) || H >= (1 << 24) || W >= (1 << 24))
+    if ((size_t)H * (size_t)W >= ((size_t)1 << 29))
         return fail(OFLK_ERR_UNSUPPORTED, "frames of 2^29 pixels or more are not supported");  // 32-bit byte offsets into float2 planes
+    if (H >= kMaxDim || W >= kMaxDim)
+        return fail(OFLK_ERR_UNSUPPORTED, "frames of 2^23 rows or columns or more are not supported (got %d x %d)", H, W);
     int hw = 0;
     int rc = window_hw(window_size, &hw);
     if (rc) return rc;
@@ -1482,6 +1488,19 @@ OFLK_API int oflk_tolerant_relaxes(int levels, int window_size, int iterations)
     return window_size >= 1 && tolerant_relaxes(levels, window_size / 2, iterations) ? 1 : 0;
 }
 
+OFLK_API int oflk_upsample_staged(int Hc, int Wc, int Ht, int Wt)
+{
+    return Hc >= 1 && Wc >= 1 && Ht >= 1 && Wt >= 1 && upsample_fits(Hc, Wc, Ht, Wt) ? 1 : 0;
+}
+
+OFLK_API int oflk_pyramid_step_fused(int h, int w, int ho, int wo, int radius)
+{
+    if (h < 1 || w < 1 || ho < 1 || wo < 1) return 0;
+    GaussW g{};
+    g.radius = radius;   // the only field of the weights that the decision reads
+    return pyr_fused_fits(h, w, ho, wo, g) ? 1 : 0;
+}
+
 OFLK_API double oflk_device_mean_error(int path, int level_h, int level_w, double mean)
 {
     return device_mean_error(path, level_h, level_w, mean);
@@ -1739,8 +1758,10 @@ int check_hw(const void *a, const void *b, int H, int W)
 {
     if (!a || !b) return fail(OFLK_ERR_INVALID, "NULL array argument");
     if (H < 1 || W < 1) return fail(OFLK_ERR_INVALID, "H and W must be >= 1 (got %d x %d)", H, W);
-    if ((size_t)H * (size_t)W >= ((size_t)1 << 30) || H >= (1 << 24) || W >= (1 << 24))
+    if ((size_t)H * (size_t)W >= ((size_t)1 << 30))
         return fail(OFLK_ERR_UNSUPPORTED, "frames of 2^30 pixels or more are not supported");  // 32-bit byte offsets
+    if (H >= kMaxDim || W >= kMaxDim)
+        return fail(OFLK_ERR_UNSUPPORTED, "frames of 2^23 rows or columns or more are not supported (got %d x %d)", H, W);
     return OFLK_OK;
 }
 
@@ -2229,7 +2250,7 @@ int check_fb(const void *uf, const void *vf, const void *ub, const void *vb, int
     if (!ef && !eb && !qf && !qb) return fail(OFLK_ERR_INVALID, "every output is NULL");
     if (B < 1) return fail(OFLK_ERR_INVALID, "B must be >= 1 (got %d)", B);
     if (int rc = check_alpha_beta(alpha, beta)) return rc;
-    return check_hw(uf, vf, H, W);   // lean_taps' 32-bit byte offsets and 24-bit row products
+    return check_hw(uf, vf, H, W);   // lean_taps' 32-bit byte offsets and signed 24-bit row products
 }
 
 int fb_launch(const float *uf, const float *vf, const float *ub, const float *vb, int B, int H, int W, float alpha, float beta,

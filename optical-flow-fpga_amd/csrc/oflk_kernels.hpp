@@ -222,7 +222,7 @@ __device__ __forceinline__ LeanTaps lean_taps_at(const LeanGeom &g, double y, do
     t.wy1 = 1.0 - t.wy0;
     t.wx1 = 1.0 - t.wx0;
     const int y0 = (int)fy, x0 = (int)fx;      // in range whenever `inside`
-    const unsigned cell = (unsigned)__mul24(y0, g.W) + (unsigned)x0;   // H, W < 2^24 (host check)
+    const unsigned cell = (unsigned)__mul24(y0, g.W) + (unsigned)x0;   // signed 24-bit multiply: H, W < 2^23 (host check)
     t.off0 = t.inside ? cell * 4u : 0u;
     return t;
 }
@@ -246,7 +246,7 @@ __device__ __forceinline__ LeanFrac lean_frac_at(const LeanGeom &g, double y, do
     t.ry = y - fy;
     t.rx = x - fx;
     const int y0 = (int)fy, x0 = (int)fx;      // in range whenever `inside`
-    const unsigned cell = (unsigned)__mul24(y0, g.W) + (unsigned)x0;   // H, W < 2^24 (host check)
+    const unsigned cell = (unsigned)__mul24(y0, g.W) + (unsigned)x0;   // signed 24-bit multiply: H, W < 2^23 (host check)
     t.off0 = t.inside ? cell * 4u : 0u;
     return t;
 }

@@ -42,6 +42,20 @@ def test_version_and_device_count_never_fail():
     assert _oflk.device_count() >= 0
 
 
+def test_stage_predicates_are_declared_and_answer_without_a_device():
+    """oflk_upsample_staged / oflk_pyramid_step_fused: host-only like oflk_tolerant_relaxes, 0 or 1 for any arguments
+    (what they decide is tested in tests/test_stages_cpu.py)"""
+    import _oflk
+
+    L = _oflk.lib()
+    assert {"oflk_upsample_staged", "oflk_pyramid_step_fused"} <= set(declared_functions())
+    assert L.oflk_upsample_staged(540, 960, 1080, 1920) == 1 and L.oflk_upsample_staged(240, 320, 240, 320) == 0
+    assert L.oflk_pyramid_step_fused(1080, 1920, 540, 960, 8) == 1 and L.oflk_pyramid_step_fused(1080, 1920, 648, 1152, 7) == 0
+    for args in ((0, 0, 0, 0), (-5, 3, 7, 9), (1 << 30, 1 << 30, 1, 1)):
+        assert L.oflk_upsample_staged(*args) in (0, 1)
+        assert L.oflk_pyramid_step_fused(*args, 8) in (0, 1)
+
+
 @pytest.mark.parametrize("shape,levels", [((240, 320), 3), ((1080, 1920), 3), ((2160, 3840), 3), ((37, 53), 3),
                                           ((241, 321), 4), ((5, 7), 2)])
 def test_level_dims_follow_int_truncation(oracle, shape, levels):

@@ -542,8 +542,10 @@ def test_printed_log_equals_the_reference_stdout(golden_dir, name, capsys, monke
 
 @pytest.mark.parametrize("sf", [0.6, 0.4, 0.75, 0.3])
 def test_pyramid_other_scale_factors_equal_the_reference(golden_dir, sf):
-    """oflk_build_pyramid away from the default scale factor (unfused blur / resample kernels, Gaussian weights from
-    libm): equal to the reference's own pyramids (tests/golden/pyramid_scales.npz)."""
+    """oflk_build_pyramid_w (what the shim calls: the Gaussian weights formed with NumPy as SciPy forms them) away from the
+    default scale factor, on the unfused blur / resample kernels: equal to the reference's own pyramids
+    (tests/golden/pyramid_scales.npz).  oflk_build_pyramid itself, with libm's weights, is held to the all-C oracle in
+    tests/test_gpu_stages.py."""
     import lucas_kanade_pyramidal as P
 
     z = np.load(golden_dir / "pyramid_scales.npz")

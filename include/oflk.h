@@ -277,6 +277,47 @@ int oflk_pyramidal_sequence_klt_u8(const unsigned char *frames, int T, int H, in
                                    float alpha, float beta, float quality_level, float min_distance, int max_corners,
                                    int *count, float *xy, float *score, float *tracks, unsigned char *visible);
 
+/* ---- replenished KLT: re-detect corners away from the live tracks --------------------------------------------------- */
+/* The statement (tests/replenish_model.py).  A fixed budget of K = max_corners slots; a slot holds at most one live track at
+ * a time, and when its track ends a later detection may start a new one in it.  detect_every = D >= 1; the LK window is
+ * the detection window (a corner window).  State per slot n: position (x, y) float32 and alive; every slot starts dead.
+ * For t = 0 .. T-1:
+ *   step (t > 0):  every alive slot takes the step of pair t-1 of oflk_track_points (two samples of the forward flow, the
+ *                  forward-backward test at the landing point, the position rounded to float32); a slot whose step fails is
+ *                  dead from row t on
+ *   detect (t % D == 0 and t < T-1):
+ *                  free = the dead slots, ascending;  seeds = (rint(x_n), rint(y_n)) of the alive slots (float32
+ *                  round-half-even, as integers; alive positions lie inside the frame, so the seeds do)
+ *                  S, M and the candidates of frame t are those of the corner statement above (M over the whole frame), in
+ *                  its priority order;  greedy in that order: accept unless a seed or an already accepted point lies at
+ *                  dx*dx + dy*dy < md*md (integers, float64);  stop after len(free) acceptances.  md = 0 refuses nothing.
+ *                  the i-th accepted point goes to slot free[i]: position ((float)x, (float)y), alive, born[t][slot] = 1;
+ *                  detected[t] = the number of acceptances (0 on frames without detection)
+ *   row t:         tracks[t][n] = (x, y) if alive, else (NaN, NaN);  visible[t][n] = alive
+ * tracks [T][K][2], visible [T][K], born [T][K] (0 / 1; born implies visible), detected [T].  A slot's rows are cut into
+ * tracks at its born marks.  With D >= T only frame 0 detects and tracks / visible equal oflk_pyramidal_sequence_klt's byte
+ * for byte.  Everything stays on the device between the frames going up and the rows coming down: a chunk's pairs are
+ * tracked in segments cut at the detection frames.  detect_every < 1, a NULL output and every check of
+ * oflk_pyramidal_sequence_klt: OFLK_ERR_INVALID / OFLK_ERR_UNSUPPORTED before any device call. */
+int oflk_pyramidal_sequence_klt_replenish(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                          float alpha, float beta, float quality_level, float min_distance, int max_corners,
+                                          int detect_every, float *tracks, unsigned char *visible, unsigned char *born,
+                                          int *detected);
+int oflk_pyramidal_sequence_klt_replenish_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size,
+                                             int iters, float alpha, float beta, float quality_level, float min_distance,
+                                             int max_corners, int detect_every, float *tracks, unsigned char *visible,
+                                             unsigned char *born, int *detected);
+/* One detection of that statement on host arrays (synchronous): frame [H][W] of index t >= 0, the slots' row xy [K][2] and
+ * visible [K] in; qt [K] and qxy [K][2] in and out (slot free[i] gets qt = t and the i-th point, every other slot keeps its
+ * bytes); born [K] and detected [1] out.  A visible slot whose position is outside [0, W-1] x [0, H-1] (NaN included) keeps
+ * its slot and seeds nothing. */
+int oflk_replenish_features_host(const float *frame, int H, int W, int window_size, float quality_level, float min_distance,
+                                 int max_corners, int t, const float *xy, const unsigned char *visible, int *qt, float *qxy,
+                                 unsigned char *born, int *detected);
+int oflk_replenish_features_host_u8(const unsigned char *frame, int H, int W, int window_size, float quality_level,
+                                    float min_distance, int max_corners, int t, const float *xy, const unsigned char *visible,
+                                    int *qt, float *qxy, unsigned char *born, int *detected);
+
 /* Rehearsal of the chunk queue above on a box with fewer GPUs than workers (tests): `workers` > 0 makes the *_multi entry
  * points run that many queue workers, worker i on device i % n_gpus (workers of one device take turns on it); 0 restores
  * one worker per device.  Results do not change. */
@@ -401,6 +442,19 @@ int oflk_good_features_workspace(int F, int H, int W, int window_size, float min
 int oflk_good_features(const void *d_frames, int u8, int F, int H, int W, int window_size, float quality_level,
                        float min_distance, int max_corners, void *d_workspace, size_t workspace_bytes, int *d_count,
                        float *d_xy, float *d_score, void *stream);
+/* Bytes of the caller's workspace for oflk_replenish_features: oflk_good_features' for one frame, the seed grid (one int
+ * per cell of side ceil(min_distance), at most H*W), 12 bytes per slot and the free slots' count. */
+int oflk_replenish_features_workspace(int H, int W, int window_size, float min_distance, int max_corners, size_t *bytes);
+/* One detection of the replenish statement above, device pointers: d_frame [H][W] (uint8 with u8 != 0) of index t, the
+ * slots' row d_xy [K][2] and d_visible [K] in; d_qt [K] and d_qxy [K][2] (8-byte aligned) in and out, so that the next
+ * oflk_track_points launch with t0 = t starts the new points; d_born [K], d_detected [1] out.  d_workspace 256-byte
+ * aligned, of at least oflk_replenish_features_workspace bytes (less: OFLK_ERR_INVALID).  Seven kernel launches (counters,
+ * score, seed grid cleared, seeds linked, free list, candidates, selection), no host round trip: the call can be captured
+ * into a graph.  Asynchronous. */
+int oflk_replenish_features(const void *d_frame, int u8, int H, int W, int window_size, float quality_level,
+                            float min_distance, int max_corners, int t, const float *d_xy, const unsigned char *d_visible,
+                            void *d_workspace, size_t workspace_bytes, int *d_qt, float *d_qxy, unsigned char *d_born,
+                            int *d_detected, void *stream);
 
 /* After oflk_plan_pyramidal: copy the residual log / iteration counts of the last
  * enqueued pass to the host (synchronises `stream`).  Either pointer may be NULL.

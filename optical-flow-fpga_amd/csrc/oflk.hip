@@ -2495,8 +2495,8 @@ int good_features_launch(const void *frames, bool u8, int F, int H, int W, int w
     c.score = S; c.fmax = fmax; c.keys = keys; c.ncand = ncand;
     c.F = F; c.H = H; c.W = W;
     c.q = (double)q;
-    hipLaunchKernelGGL(k_corner_cand, dim3((unsigned)((W + 63) / 64), (unsigned)std::min((H + 3) / 4, 65535),
-                                           (unsigned)std::min(F, 65535)), dim3(256), 0, s, c);
+    hipLaunchKernelGGL(k_corner_cand<false>, dim3((unsigned)((W + 63) / 64), (unsigned)std::min((H + 3) / 4, 65535),
+                                                  (unsigned)std::min(F, 65535)), dim3(256), 0, s, c);
     HIP_TRY(hipGetLastError());
     SelectArgs a{};
     a.keys = keys; a.ncand = ncand;
@@ -2506,7 +2506,7 @@ int good_features_launch(const void *frames, bool u8, int F, int H, int W, int w
     a.cell = std::max(g.cell, 1); a.gw = g.gw; a.gh = g.gh;
     a.md2 = (double)md * (double)md;
     a.use_grid = g.cell != 0;
-    hipLaunchKernelGGL(k_corner_select, dim3((unsigned)std::min(F, 65535)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_corner_select<false>, dim3((unsigned)std::min(F, 65535)), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError());
     return OFLK_OK;
 }
@@ -2558,6 +2558,127 @@ int good_features_host(const PIXELS *frames, int F, int H, int W, int window_siz
         return rc;
     if ((rc = call.to_host(count, d_cnt, (size_t)F)) || (rc = call.to_host(xy, d_xy, 2 * nk)) ||
         (rc = call.to_host(score, d_sc, nk)))
+        return rc;
+    return call.sync();
+}
+
+// The workspace of oflk_replenish_features: feat_geom of one frame, then the seed grid's heads [sgh][sgw] (cells of side
+// ceil(md), at most the frame; md = 0: none), its nodes [K], the free list [K] and its length [1]
+struct ReplGeom {
+    FeatGeom f;
+    int cell = 0, gw = 0, gh = 0;
+    size_t off_head = 0, off_node = 0, off_free = 0, off_nfree = 0, bytes = 0;
+};
+
+ReplGeom repl_geom(int H, int W, float md, int K)
+{
+    ReplGeom g;
+    g.f = feat_geom(1, H, W, md);
+    if (md > 0.0f) {
+        g.cell = (int)std::min<double>(std::ceil((double)md), (double)std::max(H, W));
+        g.gw = (W + g.cell - 1) / g.cell;
+        g.gh = (H + g.cell - 1) / g.cell;
+    }
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    g.off_head = g.f.bytes;
+    g.off_node = g.off_head + al((size_t)g.gw * g.gh * sizeof(int));
+    g.off_free = g.off_node + al((size_t)K * sizeof(int2));
+    g.off_nfree = g.off_free + al((size_t)K * sizeof(int));
+    g.bytes = g.off_nfree + 256;
+    return g;
+}
+
+// One detection of the replenish statement on stream s, no host round trip: the slots' state (xy, visible) of frame t in,
+// the new points into the free slots of qt / qxy, born [K] and detected [1] out.  The arguments are checked.
+int replenish_launch(const void *frame, bool u8, int H, int W, int window_size, float q, float md, int K, int t, const float *xy,
+                     const unsigned char *visible, void *workspace, int *qt, float *qxy, unsigned char *born, int *detected,
+                     hipStream_t s)
+{
+    const ReplGeom g = repl_geom(H, W, md, K);
+    char *w = static_cast<char *>(workspace);
+    unsigned *fmax = reinterpret_cast<unsigned *>(w), *ncand = reinterpret_cast<unsigned *>(w + g.f.off_cnt);
+    float *S = reinterpret_cast<float *>(w + g.f.off_s);
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(w + g.f.off_keys);
+    int *head = g.cell ? reinterpret_cast<int *>(w + g.off_head) : nullptr;
+    int2 *node = reinterpret_cast<int2 *>(w + g.off_node);
+    int *free_list = reinterpret_cast<int *>(w + g.off_free), *nfree = reinterpret_cast<int *>(w + g.off_nfree);
+    hipLaunchKernelGGL(k_corner_init, dim3(1), dim3(256), 0, s, fmax, ncand, 1);
+    HIP_TRY(hipGetLastError());
+    int rc = corner_score_launch(frame, u8, 1, H, W, window_size, S, fmax, s);
+    if (rc) return rc;
+    if (head) {
+        const int cells = g.gw * g.gh;
+        hipLaunchKernelGGL(k_seed_clear, dim3((unsigned)std::min((cells + 255) / 256, 1024)), dim3(256), 0, s, head, cells);
+        HIP_TRY(hipGetLastError());
+    }
+    SeedArgs sa{};
+    sa.xy = xy; sa.visible = visible; sa.born = born; sa.head = head; sa.node = node;
+    sa.K = K; sa.H = H; sa.W = W; sa.cell = std::max(g.cell, 1); sa.gw = g.gw;
+    hipLaunchKernelGGL(k_seed_link, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, s, sa);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_free_list, dim3(1), dim3(256), 0, s, visible, K, free_list, nfree);
+    HIP_TRY(hipGetLastError());
+    CandArgs c{};
+    c.score = S; c.fmax = fmax; c.keys = keys; c.ncand = ncand;
+    c.F = 1; c.H = H; c.W = W;
+    c.q = (double)q;
+    c.head = head; c.node = node; c.cell = std::max(g.cell, 1); c.gw = g.gw; c.gh = g.gh;
+    c.md2 = (double)md * (double)md;
+    const dim3 cgrid((unsigned)((W + 63) / 64), (unsigned)std::min((H + 3) / 4, 65535), 1);
+    if (head) hipLaunchKernelGGL(k_corner_cand<true>, cgrid, dim3(256), 0, s, c);
+    else hipLaunchKernelGGL(k_corner_cand<false>, cgrid, dim3(256), 0, s, c);
+    HIP_TRY(hipGetLastError());
+    SelectArgs a{};
+    a.keys = keys; a.ncand = ncand;
+    a.grid = g.f.cell ? reinterpret_cast<int *>(w + g.f.off_grid) : nullptr;
+    a.count = detected; a.xy = qxy; a.score = nullptr;
+    a.F = 1; a.H = H; a.W = W; a.K = K;
+    a.cell = std::max(g.f.cell, 1); a.gw = g.f.gw; a.gh = g.f.gh;
+    a.md2 = (double)md * (double)md;
+    a.use_grid = g.f.cell != 0;
+    a.free = free_list; a.nfree = nfree; a.qt = qt; a.born = born; a.t = t;
+    hipLaunchKernelGGL(k_corner_select<true>, dim3(1), dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+
+// the arguments of one detection, host or device pointers
+int check_replenish(const void *frame, int H, int W, int window_size, float q, float md, int K, int t, const void *xy,
+                    const void *visible, const void *qt, const void *qxy, const void *born, const void *detected)
+{
+    int rc = check_corner_frames(frame, 1, H, W);
+    if (rc) return rc;
+    if (!xy || !visible || !qt || !qxy || !born || !detected) return fail(OFLK_ERR_INVALID, "NULL slot state or output argument");
+    if (t < 0) return fail(OFLK_ERR_INVALID, "t must be >= 0 (got %d)", t);
+    if ((rc = check_select(q, md, K))) return rc;
+    return check_corner_window(window_size);
+}
+
+template <class PIXELS>
+int replenish_host(const PIXELS *frame, int H, int W, int window_size, float q, float md, int K, int t, const float *xy,
+                   const unsigned char *visible, int *qt, float *qxy, unsigned char *born, int *detected)
+{
+    int rc = check_replenish(frame, H, W, window_size, q, md, K, t, xy, visible, qt, qxy, born, detected);
+    if (rc) return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const size_t row = (size_t)K;
+    PIXELS *d_f;
+    char *d_ws;
+    float *d_xy, *d_qxy;
+    unsigned char *d_vis, *d_born;
+    int *d_qt, *d_det;
+    if ((rc = call.upload(&d_f, frame, (size_t)H * W)) || (rc = call.alloc(&d_ws, repl_geom(H, W, md, K).bytes)) ||
+        (rc = call.upload(&d_xy, xy, 2 * row)) || (rc = call.upload(&d_vis, visible, row)) ||
+        (rc = call.upload(&d_qt, const_cast<const int *>(qt), row)) ||
+        (rc = call.upload(&d_qxy, const_cast<const float *>(qxy), 2 * row)) || (rc = call.alloc(&d_born, row)) ||
+        (rc = call.alloc(&d_det, 1)))
+        return rc;
+    if ((rc = replenish_launch(d_f, sizeof(PIXELS) == 1, H, W, window_size, q, md, K, t, d_xy, d_vis, d_ws, d_qt, d_qxy, d_born,
+                               d_det, nullptr)))
+        return rc;
+    if ((rc = call.to_host(qt, d_qt, row)) || (rc = call.to_host(qxy, d_qxy, 2 * row)) || (rc = call.to_host(born, d_born, row)) ||
+        (rc = call.to_host(detected, d_det, 1)))
         return rc;
     return call.sync();
 }
@@ -2623,6 +2744,51 @@ OFLK_API int oflk_good_features_host_u8(const unsigned char *frames, int F, int 
                                              score);
 }
 
+OFLK_API int oflk_replenish_features_workspace(int H, int W, int window_size, float min_distance, int max_corners, size_t *bytes)
+{
+    if (!bytes) return fail(OFLK_ERR_INVALID, "NULL bytes");
+    int rc = check_hw(bytes, bytes, H, W);
+    if (rc || (rc = check_select(0.0f, min_distance, max_corners)) || (rc = check_corner_window(window_size))) return rc;
+    *bytes = repl_geom(H, W, min_distance, max_corners).bytes;
+    return OFLK_OK;
+}
+
+OFLK_API int oflk_replenish_features(const void *d_frame, int u8, int H, int W, int window_size, float quality_level,
+                                     float min_distance, int max_corners, int t, const float *d_xy,
+                                     const unsigned char *d_visible, void *d_workspace, size_t workspace_bytes, int *d_qt,
+                                     float *d_qxy, unsigned char *d_born, int *d_detected, void *stream)
+{
+    int rc = check_replenish(d_frame, H, W, window_size, quality_level, min_distance, max_corners, t, d_xy, d_visible, d_qt, d_qxy,
+                             d_born, d_detected);
+    if (rc) return rc;
+    if (!d_workspace) return fail(OFLK_ERR_INVALID, "NULL workspace");
+    const size_t need = repl_geom(H, W, min_distance, max_corners).bytes;
+    if (workspace_bytes < need)
+        return fail(OFLK_ERR_INVALID, "workspace of %zu bytes, %zu needed (oflk_replenish_features_workspace)", workspace_bytes,
+                    need);
+    if (reinterpret_cast<uintptr_t>(d_workspace) % 256 != 0 || reinterpret_cast<uintptr_t>(d_qxy) % 8 != 0)
+        return fail(OFLK_ERR_INVALID, "d_workspace must be 256-byte aligned and d_qxy 8-byte aligned");
+    return replenish_launch(d_frame, u8 != 0, H, W, window_size, quality_level, min_distance, max_corners, t, d_xy, d_visible,
+                            d_workspace, d_qt, d_qxy, d_born, d_detected, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_replenish_features_host(const float *frame, int H, int W, int window_size, float quality_level,
+                                          float min_distance, int max_corners, int t, const float *xy,
+                                          const unsigned char *visible, int *qt, float *qxy, unsigned char *born, int *detected)
+{
+    return replenish_host<float>(frame, H, W, window_size, quality_level, min_distance, max_corners, t, xy, visible, qt, qxy, born,
+                                 detected);
+}
+
+OFLK_API int oflk_replenish_features_host_u8(const unsigned char *frame, int H, int W, int window_size, float quality_level,
+                                             float min_distance, int max_corners, int t, const float *xy,
+                                             const unsigned char *visible, int *qt, float *qxy, unsigned char *born,
+                                             int *detected)
+{
+    return replenish_host<unsigned char>(frame, H, W, window_size, quality_level, min_distance, max_corners, t, xy, visible, qt,
+                                         qxy, born, detected);
+}
+
 // ---- point tracks ----------------------------------------------------------------------------------------------------
 namespace {
 // the query arguments of every track entry point; qt (host forms only, may be NULL) must lie in [0, T-1]
@@ -2664,11 +2830,19 @@ int track_launch(const float *uf, const float *vf, const float *ub, const float 
 // (oflk_pyramidal_sequence_klt) the queries are born on the device instead: good_features_launch on frame 0 of chunk 0's
 // frames writes its xy straight into the query buffer (N = K; the NaN rows are never-visible tracks), and count, xy and
 // score come down with chunk 0.
+// With det->every >= 1 (oflk_pyramidal_sequence_klt_replenish) the K queries are slots instead: every slot starts dead
+// (k_slots_init), a chunk's pairs are walked in segments cut at the detection frames (t % every == 0), and before the
+// segment that begins at such a frame s replenish_launch on frame s fills free slots (qt = s, qxy) from the slots' row
+// of s; the segment's launch (t0 = s) then starts those slots on its row 0 and continues the others from it.  That
+// launch makes the row of s final, so a chunk that begins at a detection frame sends its row 0 again, born with it.
 struct Detect {
     float q, md;
     int K;
     int *count;
     float *xy, *score;
+    int every = 0;
+    unsigned char *born = nullptr;
+    int *detected = nullptr;
 };
 
 template <class PIXELS>
@@ -2678,14 +2852,20 @@ int run_sequence_tracks(const PIXELS *frames, int T, int H, int W, int levels, i
 {
     int C = 0;   // pairs per chunk (setup)
     float *d_qxy = nullptr, *d_tr = nullptr, *d_sc = nullptr;
-    int *d_qt = nullptr, *d_cnt = nullptr;
-    unsigned char *d_vis = nullptr;
+    int *d_qt = nullptr, *d_cnt = nullptr, *d_det = nullptr;
+    unsigned char *d_vis = nullptr, *d_born = nullptr;
     char *d_ws = nullptr;
+    const bool slots = det && det->born;   // the replenish call
     auto checks = [&]() -> int {
         int rc = check_alpha_beta(alpha, beta);
         if (rc) return rc;
         if (!det) return check_queries(qt, T, qxy, N, tracks, visible);
-        if (!det->count || !det->xy || !det->score || !tracks || !visible) return fail(OFLK_ERR_INVALID, "NULL output argument");
+        if (slots) {
+            if (!det->detected || !tracks || !visible) return fail(OFLK_ERR_INVALID, "NULL output argument");
+            if (det->every < 1) return fail(OFLK_ERR_INVALID, "detect_every must be >= 1 (got %d)", det->every);
+        } else if (!det->count || !det->xy || !det->score || !tracks || !visible) {
+            return fail(OFLK_ERR_INVALID, "NULL output argument");
+        }
         if ((rc = check_select(det->q, det->md, det->K)) || (rc = check_corner_window(window_size))) return rc;
         N = det->K;
         return OFLK_OK;
@@ -2698,6 +2878,16 @@ int run_sequence_tracks(const PIXELS *frames, int T, int H, int W, int levels, i
             (qt && (rc = call.upload(&d_qt, qt, row))) || (rc = call.alloc(&d_tr, (size_t)(C + 1) * 2 * row)) ||
             (rc = call.alloc(&d_vis, (size_t)(C + 1) * row)))
             return rc;
+        if (slots) {
+            if ((rc = call.alloc(&d_ws, repl_geom(H, W, det->md, det->K).bytes)) || (rc = call.alloc(&d_qt, row)) ||
+                (rc = call.alloc(&d_born, (size_t)(C + 1) * row)) || (rc = call.alloc(&d_det, (size_t)T)))
+                return rc;
+            hipLaunchKernelGGL(k_slots_init, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, d_qt,
+                               reinterpret_cast<float2 *>(d_qxy), reinterpret_cast<float2 *>(d_tr), d_vis, N);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemsetAsync(d_det, 0, (size_t)T * sizeof(int), nullptr));
+            return OFLK_OK;
+        }
         if (det && ((rc = call.alloc(&d_ws, feat_geom(1, H, W, det->md).bytes)) || (rc = call.alloc(&d_cnt, 1)) ||
                     (rc = call.alloc(&d_sc, row))))
             return rc;
@@ -2709,6 +2899,32 @@ int run_sequence_tracks(const PIXELS *frames, int T, int H, int W, int levels, i
         if (b0 > 0) {   // row 0 of this chunk is the previous (full, C-pair) chunk's last row
             HIP_TRY(hipMemcpyAsync(d_tr, d_tr + (size_t)C * 2 * row, 2 * row * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
             HIP_TRY(hipMemcpyAsync(d_vis, d_vis + (size_t)C * row, row, hipMemcpyDeviceToDevice, nullptr));
+        }
+        if (slots) {
+            const size_t plane = (size_t)H * W;
+            const int D = det->every;
+            HIP_TRY(hipMemsetAsync(d_born, 0, (size_t)(nb + 1) * row, nullptr));
+            for (int s0 = b0; s0 < b0 + nb;) {   // segments [s0, e) of pairs; s0 <= T-2
+                const int e = (int)std::min<long long>(b0 + nb, ((long long)s0 / D + 1) * D), r = s0 - b0;
+                if (s0 % D == 0 &&
+                    (rc = replenish_launch(d_frames + (size_t)r * plane, sizeof(PIXELS) == 1, H, W, window_size, det->q, det->md,
+                                           det->K, s0, d_tr + (size_t)r * 2 * row, d_vis + (size_t)r * row, d_ws, d_qt, d_qxy,
+                                           d_born + (size_t)r * row, d_det + s0, nullptr)))
+                    return rc;
+                if ((rc = track_launch(d[0] + (size_t)r * plane, d[1] + (size_t)r * plane, d[2] + (size_t)r * plane,
+                                       d[3] + (size_t)r * plane, e - s0, H, W, alpha, beta, s0, d_qt, d_qxy, N,
+                                       d_tr + (size_t)r * 2 * row, d_vis + (size_t)r * row, nullptr)))
+                    return rc;
+                s0 = e;
+            }
+            const int r0 = b0 > 0 && b0 % D != 0 ? 1 : 0;   // row 0 of a chunk that begins with a detection goes again
+            const size_t nr = (size_t)(nb + 1 - r0);
+            if ((rc = call.to_host(tracks + (size_t)(b0 + r0) * 2 * row, d_tr + (size_t)r0 * 2 * row, nr * 2 * row)) ||
+                (rc = call.to_host(visible + (size_t)(b0 + r0) * row, d_vis + (size_t)r0 * row, nr * row)) ||
+                (rc = call.to_host(det->born + (size_t)(b0 + r0) * row, d_born + (size_t)r0 * row, nr * row)))
+                return rc;
+            if (b0 + nb == T - 1 && (rc = call.to_host(det->detected, d_det, (size_t)T))) return rc;
+            return OFLK_OK;
         }
         if (det && b0 == 0) {   // frame 0 is d_frames[0]: its features become the queries
             if ((rc = good_features_launch(d_frames, sizeof(PIXELS) == 1, 1, H, W, window_size, det->q, det->md, det->K, d_ws, d_cnt,
@@ -2794,6 +3010,28 @@ OFLK_API int oflk_pyramidal_sequence_klt_u8(const unsigned char *frames, int T, 
                                             unsigned char *visible)
 {
     const Detect det{quality_level, min_distance, max_corners, count, xy, score};
+    return run_sequence_tracks<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, nullptr, nullptr, 0,
+                                              tracks, visible, &det);
+}
+
+OFLK_API int oflk_pyramidal_sequence_klt_replenish(const float *frames, int T, int H, int W, int levels, int window_size,
+                                                   int iters, float alpha, float beta, float quality_level, float min_distance,
+                                                   int max_corners, int detect_every, float *tracks, unsigned char *visible,
+                                                   unsigned char *born, int *detected)
+{
+    if (!born) return fail(OFLK_ERR_INVALID, "NULL output argument");
+    const Detect det{quality_level, min_distance, max_corners, nullptr, nullptr, nullptr, detect_every, born, detected};
+    return run_sequence_tracks<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, nullptr, nullptr, 0, tracks,
+                                      visible, &det);
+}
+
+OFLK_API int oflk_pyramidal_sequence_klt_replenish_u8(const unsigned char *frames, int T, int H, int W, int levels,
+                                                      int window_size, int iters, float alpha, float beta, float quality_level,
+                                                      float min_distance, int max_corners, int detect_every, float *tracks,
+                                                      unsigned char *visible, unsigned char *born, int *detected)
+{
+    if (!born) return fail(OFLK_ERR_INVALID, "NULL output argument");
+    const Detect det{quality_level, min_distance, max_corners, nullptr, nullptr, nullptr, detect_every, born, detected};
     return run_sequence_tracks<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, nullptr, nullptr, 0,
                                               tracks, visible, &det);
 }

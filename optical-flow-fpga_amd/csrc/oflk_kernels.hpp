@@ -3307,6 +3307,9 @@ __global__ __launch_bounds__(256) void k_corner_score(CornerArgs a)
 // per frame into keys[f][0 .. ncand[f]) as (~bits(S)) << 32 | (y*W + x): ascending keys are the priority order (S
 // descending, then raster index).  One pixel per thread; the neighbours are read only above the threshold.  The order of
 // the list is not deterministic; the key makes every later order total.  At most H*W keys per frame.
+// SEEDS (oflk_replenish_features, F = 1): a candidate with a seed at dx*dx + dy*dy < md*md is dropped here, before it
+// costs the selection anything.  The seeds hang in chained lists off a grid of cells of side `cell` >= md (k_seed_link),
+// so a seed that close lies in the 3 x 3 cells around the pixel: their lists are walked until the first hit.
 struct CandArgs {
     const float *score;            // [F][H][W]
     const unsigned *fmax;          // [F]
@@ -3314,8 +3317,13 @@ struct CandArgs {
     unsigned *ncand;               // [F] (zeroed by the caller)
     int F, H, W;
     double q;
+    const int *head;               // SEEDS: [gh][gw] first node of each cell's list, -1 at its end
+    const int2 *node;              // SEEDS: [K] (next node, seed pixel y*W + x)
+    int cell, gw, gh;              // SEEDS
+    double md2;                    // SEEDS
 };
 
+template <bool SEEDS>
 __global__ __launch_bounds__(256) void k_corner_cand(CandArgs a)
 {
     const int H = a.H, W = a.W, x = blockIdx.x * 64 + (threadIdx.x & 63);
@@ -3337,6 +3345,19 @@ __global__ __launch_bounds__(256) void k_corner_cand(CandArgs a)
                             const int yy = y + dy, xx = x + dx;
                             if ((dy || dx) && yy >= 0 && yy < H && xx >= 0 && xx < W && !(s >= S[(size_t)yy * W + xx])) cand = false;
                         }
+                }
+                if constexpr (SEEDS) {
+                    if (cand) {
+                        const int cx = x / a.cell, cy = y / a.cell;
+                        for (int gy = max(cy - 1, 0); gy <= min(cy + 1, a.gh - 1); gy++)
+                            for (int gx = max(cx - 1, 0); gx <= min(cx + 1, a.gw - 1); gx++)
+                                for (int n = a.head[(size_t)gy * a.gw + gx]; n >= 0 && cand;) {
+                                    const int2 nd = a.node[n];
+                                    const long long dy = nd.y / W - y, dx = nd.y % W - x;
+                                    if ((double)(dx * dx + dy * dy) < a.md2) cand = false;
+                                    n = nd.x;
+                                }
+                    }
                 }
             }
             const unsigned long long m = __ballot(cand);
@@ -3377,6 +3398,9 @@ __global__ __launch_bounds__(256) void k_corner_init(unsigned *fmax, unsigned *n
 //            earliest open one per round; the first K - count accepted are written and entered into the grid
 //   md <= 1: distinct pixels are >= 1 apart, so every candidate is accepted in order (no grid)
 // Until K are accepted or the list is exhausted.  Rows from count on are (NaN, NaN), score 0.
+// SLOTS (oflk_replenish_features, F = 1): the budget is min(K, *nfree), read from the device, and the i-th acceptance goes
+// to slot free[i] of qt (= t), xy (the queries) and born (= 1); no other slot is written, no score, no NaN fill; count is
+// detected[t].
 constexpr int kSelCap = 4096;
 
 struct SelectArgs {
@@ -3389,8 +3413,13 @@ struct SelectArgs {
     int F, H, W, K, cell, gw, gh;
     double md2;
     bool use_grid;
+    const int *free, *nfree;          // SLOTS: [K] the free slots, ascending, and [1] their number
+    int *qt;                          // SLOTS: [K]
+    unsigned char *born;              // SLOTS: [K]
+    int t;                            // SLOTS: the frame's index
 };
 
+template <bool SLOTS>
 __global__ __launch_bounds__(256) void k_corner_select(SelectArgs a)
 {
     __shared__ unsigned long long slab[kSelCap];
@@ -3400,7 +3429,9 @@ __global__ __launch_bounds__(256) void k_corner_select(SelectArgs a)
     __shared__ int s_shift, s_done;
     __shared__ int bx[256], by[256];
     __shared__ unsigned long long acc_m[4], rej_m[4];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, W = a.W, K = a.K;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, W = a.W;
+    int K = a.K;
+    if constexpr (SLOTS) K = min(K, *a.nfree);
     const size_t plane = (size_t)a.H * (size_t)W;
     const int gcells = a.gw * a.gh;
     for (int f = blockIdx.x; f < a.F; f += gridDim.x) {
@@ -3551,8 +3582,15 @@ __global__ __launch_bounds__(256) void k_corner_select(SelectArgs a)
                 }
                 const int slot = accepted + below;
                 if (acc && slot < K) {
-                    xy[slot] = make_float2((float)x, (float)y);
-                    sc[slot] = __uint_as_float(~(unsigned)(key >> 32));
+                    if constexpr (SLOTS) {
+                        const int dst = a.free[slot];
+                        xy[dst] = make_float2((float)x, (float)y);
+                        a.qt[dst] = a.t;
+                        a.born[dst] = 1;
+                    } else {
+                        xy[slot] = make_float2((float)x, (float)y);
+                        sc[slot] = __uint_as_float(~(unsigned)(key >> 32));
+                    }
                     if (grid) {
                         int *cellp = grid + ((size_t)(y / a.cell) * a.gw + x / a.cell) * 4;
                         for (int sl = 0; sl < 4; sl++)
@@ -3567,13 +3605,96 @@ __global__ __launch_bounds__(256) void k_corner_select(SelectArgs a)
             __syncthreads();
             if (hi == ~0ull) break;
         }
-        const float nan = __builtin_nanf("");
-        for (int i = accepted + tid; i < K; i += 256) {
-            xy[i] = make_float2(nan, nan);
-            sc[i] = 0.0f;
+        if constexpr (!SLOTS) {
+            const float nan = __builtin_nanf("");
+            for (int i = accepted + tid; i < K; i += 256) {
+                xy[i] = make_float2(nan, nan);
+                sc[i] = 0.0f;
+            }
         }
         if (tid == 0) a.count[f] = accepted;
     }
+}
+
+// ---- replenishment (oflk_replenish_features): the slots' side of one detection -------------------------------------------
+// Slot n of K holds at most one live track: visible[n] != 0 and its position xy[n] on the detection frame.
+//   k_seed_clear  head[c] = -1 for every cell of the seed grid
+//   k_seed_link   one thread per slot: born[n] = 0; an alive slot enters its seed (rint(x), rint(y)) (v_rndne_f32: float32
+//                 round-half-even) into the list of its cell, node[n] = (old head, y*W + x) with one atomic exchange on the
+//                 head.  Any number of seeds may share a cell or a pixel (tracks do sit on top of each other), which is why
+//                 they do not go into the selection's four-slot occupancy grid.  An alive slot whose position is not in
+//                 [0, W-1] x [0, H-1] (NaN included; the sequence call never has one) keeps its slot and seeds nothing.
+//                 md = 0 refuses nothing: no lists (head == NULL).
+//   k_free_list   one workgroup: the dead slots in ascending order and their number.  Thread i counts the dead of the
+//                 i-th of 256 contiguous pieces, a scan over the 256 counts gives its first index, and it writes its
+//                 piece's.  O(K / 256) serial byte loads per thread: ~400 at K = 10^5, which is what bounds K here.
+// Cost of the seeds: K threads to link, and in k_corner_cand<true> per pixel that is a local maximum above the
+// threshold one walk of the lists of its 3 x 3 cells, ended by the first seed within md.  That is O(seeds in those cells),
+// independent of md*md: a few for md well below the frame, and for md beyond the frame's diagonal (one cell) the first
+// node of the list ends every walk.  The worst case is K tests per surviving candidate (every seed in the 3 x 3 cells and
+// none within md), e.g. md near the frame's size with the seeds stacked in a far corner.
+struct SeedArgs {
+    const float *xy;                // [K][2]
+    const unsigned char *visible;   // [K]
+    unsigned char *born;            // [K]
+    int *head;                      // [gh][gw], or NULL (md = 0)
+    int2 *node;                     // [K]
+    int K, H, W, cell, gw;
+};
+
+__global__ __launch_bounds__(256) void k_seed_clear(int *head, int cells)
+{
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < cells; i += gridDim.x * 256) head[i] = -1;
+}
+
+__global__ __launch_bounds__(256) void k_seed_link(SeedArgs a)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= a.K) return;
+    a.born[n] = 0;
+    if (!a.head || !a.visible[n]) return;
+    const float x = a.xy[2 * (size_t)n], y = a.xy[2 * (size_t)n + 1];
+    if (!(x >= 0.0f && x <= (float)(a.W - 1) && y >= 0.0f && y <= (float)(a.H - 1))) return;
+    const int sx = (int)__builtin_rintf(x), sy = (int)__builtin_rintf(y);   // in the frame, as x and y are
+    int *h = a.head + (size_t)(sy / a.cell) * a.gw + sx / a.cell;
+    a.node[n] = make_int2(atomicExch(h, n), sy * a.W + sx);
+}
+
+__global__ __launch_bounds__(256) void k_free_list(const unsigned char *__restrict__ visible, int K, int *__restrict__ free,
+                                                   int *__restrict__ nfree)
+{
+    __shared__ int wsum[4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const long long per = ((long long)K + 255) / 256;
+    const int lo = (int)min((long long)K, per * tid), hi = (int)min((long long)K, per * (tid + 1));
+    int c = 0;
+    for (int n = lo; n < hi; n++) c += visible[n] == 0;
+    int incl = c;   // inclusive scan over the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
+    }
+    if (lane == 63) wsum[wv] = incl;
+    __syncthreads();
+    int base = incl - c;
+    for (int w = 0; w < wv; w++) base += wsum[w];
+    for (int n = lo; n < hi; n++)
+        if (visible[n] == 0) free[base++] = n;
+    if (tid == 255) *nfree = base;
+}
+
+// every slot dead ahead of frame 0's detection (oflk_pyramidal_sequence_klt_replenish): a query frame that no launch
+// starts, and a row 0 that k_track reads as ended
+__global__ __launch_bounds__(256) void k_slots_init(int *qt, float2 *qxy, float2 *row, unsigned char *visible, int K)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= K) return;
+    const float nan = __builtin_nanf("");
+    qt[n] = -1;
+    qxy[n] = make_float2(nan, nan);
+    row[n] = make_float2(nan, nan);
+    visible[n] = 0;
 }
 
 }  // namespace oflk

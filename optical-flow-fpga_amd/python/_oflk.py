@@ -90,6 +90,12 @@ SIGNATURES = {
     "oflk_good_features_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [ctypes.c_float] * 2 + [ctypes.c_int, _i32p, _f32p, _f32p]),
     "oflk_pyramidal_sequence_klt": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 4 + [ctypes.c_int, _i32p, _f32p, _f32p, _f32p, _vp]),
     "oflk_pyramidal_sequence_klt_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 4 + [ctypes.c_int, _i32p, _f32p, _f32p, _f32p, _vp]),
+    "oflk_pyramidal_sequence_klt_replenish": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 4 + [ctypes.c_int] * 2 + [_f32p, _vp, _vp, _i32p]),
+    "oflk_pyramidal_sequence_klt_replenish_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 4 + [ctypes.c_int] * 2 + [_f32p, _vp, _vp, _i32p]),
+    "oflk_replenish_features_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [ctypes.c_int] * 2 + [_f32p, _vp, _i32p, _f32p, _vp, _i32p]),
+    "oflk_replenish_features_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [ctypes.c_int] * 2 + [_f32p, _vp, _i32p, _f32p, _vp, _i32p]),
+    "oflk_replenish_features_workspace": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    "oflk_replenish_features": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [ctypes.c_float] * 2 + [ctypes.c_int] * 2 + [_vp, _vp, _vp, ctypes.c_size_t] + [_vp] * 5),
     "oflk_shard_range": (None, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, _i32p]),
     "oflk_single_scale_fp16": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, _f32p, _f32p]),
     "oflk_rtl_stream_length": (ctypes.c_long, [ctypes.c_int, ctypes.c_int]),
@@ -457,3 +463,22 @@ def good_features(d_frames: int, F: int, H: int, W: int, d_workspace: int, works
     check(lib().oflk_good_features(d_frames, int(bool(u8)), int(F), int(H), int(W), int(window_size), float(quality_level),
                                    float(min_distance), int(max_corners), d_workspace, int(workspace_bytes), d_count, d_xy,
                                    d_score, stream))
+
+
+def replenish_features_workspace(H: int, W: int, window_size: int = 5, min_distance: float = 10.0, max_corners: int = 100) -> int:
+    """bytes of oflk_replenish_features' workspace for this shape"""
+    n = ctypes.c_size_t(0)
+    check(lib().oflk_replenish_features_workspace(int(H), int(W), int(window_size), float(min_distance), int(max_corners),
+                                                  ctypes.byref(n)))
+    return int(n.value)
+
+
+def replenish_features(d_frame: int, H: int, W: int, t: int, d_xy: int, d_visible: int, d_workspace: int, workspace_bytes: int,
+                       d_qt: int, d_qxy: int, d_born: int, d_detected: int, max_corners: int, quality_level: float = 0.01,
+                       min_distance: float = 10.0, window_size: int = 5, u8: bool = False, stream: int = 0) -> None:
+    """oflk_replenish_features on device pointers: one detection on frame t [H][W] away from the alive slots of d_xy [K][2] /
+    d_visible [K]; the new points go into the free slots of d_qt [K] int32 (= t) and d_qxy [K][2], d_born [K] uint8 marks
+    them and d_detected [1] int32 counts them; d_workspace of at least replenish_features_workspace bytes."""
+    check(lib().oflk_replenish_features(d_frame, int(bool(u8)), int(H), int(W), int(window_size), float(quality_level),
+                                        float(min_distance), int(max_corners), int(t), d_xy, d_visible, d_workspace,
+                                        int(workspace_bytes), d_qt, d_qxy, d_born, d_detected, stream))

@@ -171,3 +171,62 @@ def features_to_queries(xy, count=None, t: int = 0) -> npt.NDArray[np.float32]:
         raise ValueError(f"expected (n, 2) features, or (F, K, 2) with a count per frame; got shape {xy.shape}")
     rows = [np.column_stack([np.full(int(n), t + f, np.float32), xy[f, :int(n)]]) for f, n in enumerate(count)]
     return np.concatenate(rows).astype(np.float32) if rows else np.zeros((0, 3), np.float32)
+
+
+def replenish_features(frame, xy, visible, max_corners=None, quality_level: float = 0.01, min_distance: float = 10.0,
+                       window_size: int = 5, t: int = 0, qt=None, qxy=None):
+    """One detection of the replenished KLT on the GPU: Shi-Tomasi features of `frame` (H, W) away from the live tracks.
+
+    xy (K, 2) float32 (x, y) and visible (K,) are the slots' row on this frame: a slot that is not visible is free.  The
+    candidates of good_features_to_track are taken in its order, skipping one within min_distance of the rounded position
+    of a visible slot or of a point already taken, until every free slot is filled; the i-th point goes to the i-th free
+    slot.  Returns (qt (K,) int32, qxy (K, 2) float32, born (K,) bool, detected): qt / qxy are the given arrays (default
+    -1 / NaN) with the born slots set to t and their points, every other slot unchanged; they are what
+    oflk_track_points takes to start the new tracks at frame t.  The statement is in include/oflk.h.
+    """
+    if np.ndim(frame) != 2:
+        raise ValueError(f"expected one (H, W) frame, got shape {np.shape(frame)}")
+    xy = np.ascontiguousarray(xy, np.float32)
+    vis = np.ascontiguousarray(np.asarray(visible) != 0, np.uint8)
+    if xy.ndim != 2 or xy.shape[1] != 2 or vis.shape != (xy.shape[0],):
+        raise ValueError(f"expected xy (K, 2) and visible (K,), got {xy.shape} and {vis.shape}")
+    K = xy.shape[0]
+    if max_corners is not None and int(max_corners) != K:
+        raise ValueError(f"max_corners {max_corners!r} is not the number of slots {K}")
+    K, q, md, win = _oflk.check_feature_params(K, quality_level, min_distance, window_size)
+    if isinstance(t, bool) or int(t) != t or int(t) < 0:
+        raise ValueError(f"t must be an integer >= 0, got {t!r}")
+    arr, u8 = _oflk.as_frames(frame)
+    _, H, W = arr.shape
+    qt = np.full(K, -1, np.int32) if qt is None else np.array(qt, np.int32, copy=True, order="C")
+    qxy = np.full((K, 2), np.nan, np.float32) if qxy is None else np.array(qxy, np.float32, copy=True, order="C")
+    if qt.shape != (K,) or qxy.shape != (K, 2):
+        raise ValueError(f"expected qt ({K},) and qxy ({K}, 2), got {qt.shape} and {qxy.shape}")
+    born = np.empty(K, np.uint8)
+    detected = np.zeros(1, np.int32)
+    fn = _oflk.lib().oflk_replenish_features_host_u8 if u8 else _oflk.lib().oflk_replenish_features_host
+    src = arr.ctypes.data if u8 else _oflk.ptr(arr)
+    _oflk.check(fn(src, H, W, win, q, md, K, int(t), _oflk.ptr(xy), vis.ctypes.data, qt.ctypes.data_as(_oflk._i32p),
+                   _oflk.ptr(qxy), born.ctypes.data, detected.ctypes.data_as(_oflk._i32p)))
+    return qt, qxy, born.astype(bool), int(detected[0])
+
+
+def split_tracks(visible, born):
+    """The tracks of a replenished call's slots: [(slot, t_first, t_last)] sorted by slot, then t_first.  visible, born:
+    (T, K); a track begins where born is set and lasts while its slot stays visible and no new track is born in it.  Host
+    only.  ValueError if the masks do not go together (born without visible, or visible rising without born)."""
+    vis, born = np.asarray(visible) != 0, np.asarray(born) != 0
+    if vis.ndim != 2 or vis.shape != born.shape:
+        raise ValueError(f"expected visible and born of one (T, K) shape, got {vis.shape} and {born.shape}")
+    before = np.vstack([np.zeros((1, vis.shape[1]), bool), vis[:-1]])
+    if (born & ~vis).any() or (vis & ~before & ~born).any():
+        raise ValueError("born must imply visible, and visible may only rise where born is set")
+    T = vis.shape[0]
+    out = []
+    for n in np.flatnonzero(born.any(0)).tolist():
+        starts = np.flatnonzero(born[:, n]).tolist()
+        for i, t0 in enumerate(starts):
+            stop = starts[i + 1] if i + 1 < len(starts) else T
+            gone = np.flatnonzero(~vis[t0:stop, n])
+            out.append((n, t0, t0 + int(gone[0]) - 1 if len(gone) else stop - 1))
+    return out

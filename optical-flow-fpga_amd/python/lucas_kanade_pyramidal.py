@@ -314,6 +314,40 @@ def lucas_kanade_pyramidal_sequence_klt(frames, max_corners: int, quality_level:
     return SequenceKLT(xy[:n], tracks[:, :n], visible[:, :n].astype(bool))
 
 
+class SequenceKLTReplenish(NamedTuple):
+    """Result of lucas_kanade_pyramidal_sequence_klt_replenish: K slots, row t is frame t.  A slot holds one track at a
+    time; lucas_kanade_core.split_tracks(visible, born) lists them."""
+    tracks: np.ndarray     # (T, K, 2) float32 (x, y); NaN where not visible
+    visible: np.ndarray    # (T, K) bool
+    born: np.ndarray       # (T, K) bool: a new track begins in this slot on this frame
+    detected: np.ndarray   # (T,) int32: points born on each frame
+
+
+def lucas_kanade_pyramidal_sequence_klt_replenish(frames, max_corners: int, detect_every: int, quality_level: float = 0.01,
+                                                  min_distance: float = 10.0, num_levels: int = 3, window_size: int = 5,
+                                                  num_iterations: int = 3, alpha: float = 0.01,
+                                                  beta: float = 0.5) -> SequenceKLTReplenish:
+    """KLT with replenishment: lucas_kanade_pyramidal_sequence_klt over max_corners slots, detecting again on every
+    detect_every-th frame (0, D, 2D, .. below the last) away from the live tracks and starting the new points in the
+    slots whose tracks have ended (lucas_kanade_core.replenish_features is one such detection).  Frames go up and the
+    rows come down; the flows, the detections and the hand-over between them stay on the device.  With detect_every >=
+    the number of frames the tracks are lucas_kanade_pyramidal_sequence_klt's, over all K slots.
+    """
+    a, b = _oflk.check_fb_params(alpha, beta)
+    K, q, md, win = _oflk.check_feature_params(max_corners, quality_level, min_distance, window_size)
+    if isinstance(detect_every, bool) or int(detect_every) != detect_every or int(detect_every) < 1:
+        raise ValueError(f"detect_every must be an integer >= 1, got {detect_every!r}")
+    arr, u8 = _oflk.as_sequence(frames)
+    T, H, W = arr.shape
+    tracks, visible = np.empty((T, K, 2), np.float32), np.empty((T, K), np.uint8)
+    born, detected = np.empty((T, K), np.uint8), np.empty(T, np.int32)
+    fn = _oflk.lib().oflk_pyramidal_sequence_klt_replenish_u8 if u8 else _oflk.lib().oflk_pyramidal_sequence_klt_replenish
+    src = arr.ctypes.data if u8 else _oflk.ptr(arr)
+    _oflk.check(fn(src, T, H, W, int(num_levels), win, int(num_iterations), a, b, q, md, K, min(int(detect_every), 2 ** 31 - 1),
+                   _oflk.ptr(tracks), visible.ctypes.data, born.ctypes.data, detected.ctypes.data_as(_oflk._i32p)))
+    return SequenceKLTReplenish(tracks, visible.astype(bool), born.astype(bool), detected)
+
+
 def _dump_levels(key, shapes, u, v) -> None:
     """The reference's per-level PNG side effect (:226), after the call, best-effort."""
     num_levels = key[3]

@@ -10,9 +10,14 @@ around device-form calls on one stream (median of --steps after --warmup); host 
       per frame (the frames of a batch run concurrently, one workgroup each).
   (c) oflk_pyramidal_sequence_klt against oflk_pyramidal_sequence_tracks on the points it detected, host to host,
       --frames frames (3/5/3), K = 10 000; both results are compared byte for byte.
+With --replenish it measures the replenished KLT instead (K = 10 000, md 10, q 0.01):
+  (d) one oflk_replenish_features call by torch events: on frame 0 with every slot free and no seeds, and in the steady
+      state -- frame 1, the slots of frame 0's detection alive at its points but every tenth, which is free;
+  (e) oflk_pyramidal_sequence_klt_replenish for detect_every 4 and 16 against oflk_pyramidal_sequence_klt on the same
+      frames, host to host, alternating which goes first.
 It prints one JSON line per measurement.
 
-    python tools/feature_bench.py [--batch 128] [--frames 129] [--steps 5] [--warmup 1] [--pixels f32,u8]
+    python tools/feature_bench.py [--batch 128] [--frames 129] [--steps 5] [--warmup 1] [--pixels f32,u8] [--replenish]
 """
 import argparse
 import json
@@ -37,6 +42,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--pixels", default="f32,u8")
     ap.add_argument("--skip-klt", action="store_true")
+    ap.add_argument("--replenish", action="store_true", help="parts (d) and (e) only")
     args = ap.parse_args()
     steps = max(1, min(args.steps, 20))
     import numpy as np
@@ -46,7 +52,7 @@ def main():
     from oflk_synth import synth_pair
 
     F, T, H, W = args.batch, args.frames, args.height, args.width
-    n = max(F, T)
+    n = T if args.replenish else max(F, T)
     base = synth_pair(H, W, pair_index=0)[0].astype(np.float32)
     rng = np.random.default_rng(0)
     f32 = np.empty((n, H, W), np.float32)
@@ -69,7 +75,78 @@ def main():
             ms.append(a.elapsed_time(b))
         return statistics.median(ms)
 
-    for pix in args.pixels.split(","):
+    for pix in args.pixels.split(",") if args.replenish else ():
+        u8 = pix == "u8"
+        K, q, md = 10000, 0.01, 10.0
+        # (d) one detection
+        d_f = torch.from_numpy(frames[pix][:2]).to(dev)
+        nbytes = _oflk.replenish_features_workspace(H, W, 5, md, K)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        xy = torch.full((K, 2), float("nan"), dtype=torch.float32, device=dev)
+        vis = torch.zeros((K,), dtype=torch.uint8, device=dev)
+        qt = torch.full((K,), -1, dtype=torch.int32, device=dev)
+        qxy = torch.full((K, 2), float("nan"), dtype=torch.float32, device=dev)
+        born = torch.empty((K,), dtype=torch.uint8, device=dev)
+        det = torch.empty((1,), dtype=torch.int32, device=dev)
+
+        def detect(f, t):
+            _oflk.replenish_features(d_f[f].data_ptr(), H, W, t, xy.data_ptr(), vis.data_ptr(), ws.data_ptr(), nbytes,
+                                     qt.data_ptr(), qxy.data_ptr(), born.data_ptr(), det.data_ptr(), K, q, md, 5, u8=u8,
+                                     stream=st.cuda_stream)
+
+        first_ms = timed(lambda: detect(0, 0))
+        first_n = int(det.cpu()[0])
+        xy.copy_(qxy)   # the steady state: frame 0's points alive, every tenth slot free
+        vis.copy_(born)
+        vis[::10] = 0
+        free = int((vis == 0).sum().cpu())
+        steady_ms = timed(lambda: detect(1, 1))
+        print(json.dumps({"tool": "feature_bench", "part": "d", "pixels": pix, "height": H, "width": W, "K": K, "md": md, "q": q,
+                          "steps": steps, "frame0_all_free_ms": round(first_ms, 3), "frame0_detected": first_n,
+                          "steady_free_slots": free, "steady_ms": round(steady_ms, 3), "steady_detected": int(det.cpu()[0])}),
+              flush=True)
+        del d_f, ws
+        torch.cuda.empty_cache()
+        # (e) host to host
+        fr = np.ascontiguousarray(frames[pix][:T])
+        L = _oflk.lib()
+        src = fr.ctypes.data if u8 else _oflk.ptr(fr)
+        klt_fn = L.oflk_pyramidal_sequence_klt_u8 if u8 else L.oflk_pyramidal_sequence_klt
+        rep_fn = L.oflk_pyramidal_sequence_klt_replenish_u8 if u8 else L.oflk_pyramidal_sequence_klt_replenish
+        cnt = np.zeros(1, np.int32)
+        kxy, ksc = np.empty((K, 2), np.float32), np.empty(K, np.float32)
+        ktr, kvis = np.empty((T, K, 2), np.float32), np.empty((T, K), np.uint8)
+        rtr, rvis, rborn = np.empty((T, K, 2), np.float32), np.empty((T, K), np.uint8), np.empty((T, K), np.uint8)
+        rdet = np.empty(T, np.int32)
+
+        def klt():
+            _oflk.check(klt_fn(src, T, H, W, 3, 5, 3, 0.01, 0.5, q, md, K, cnt.ctypes.data_as(_oflk._i32p), _oflk.ptr(kxy),
+                               _oflk.ptr(ksc), _oflk.ptr(ktr), kvis.ctypes.data))
+
+        def rep(D):
+            _oflk.check(rep_fn(src, T, H, W, 3, 5, 3, 0.01, 0.5, q, md, K, D, _oflk.ptr(rtr), rvis.ctypes.data, rborn.ctypes.data,
+                               rdet.ctypes.data_as(_oflk._i32p)))
+
+        for D in (4, 16):
+            forms = (("klt", klt), ("replenish", lambda: rep(D)))
+            for _ in range(args.warmup):
+                for _, fn in forms:
+                    fn()
+            ms = {"klt": [], "replenish": []}
+            for i in range(steps):
+                for name, fn in (forms if i % 2 == 0 else forms[::-1]):
+                    t0 = time.perf_counter()
+                    fn()
+                    ms[name].append((time.perf_counter() - t0) * 1e3)
+            a, b = statistics.median(ms["replenish"]), statistics.median(ms["klt"])
+            nd = len(range(0, T - 1, D))
+            print(json.dumps({"tool": "feature_bench", "part": "e", "pixels": pix, "frames": T, "height": H, "width": W, "K": K,
+                              "detect_every": D, "detections": nd, "steps": steps, "replenish_ms": round(a, 3),
+                              "klt_ms": round(b, 3), "ratio": round(a / b, 3),
+                              "ms_per_later_detection": round((a - b) / max(nd - 1, 1), 3),
+                              "born_after_frame0": int(rdet[1:].sum()), "visible_last_klt": int(kvis[-1].sum()),
+                              "visible_last_replenish": int(rvis[-1].sum())}), flush=True)
+    for pix in () if args.replenish else args.pixels.split(","):
         u8 = pix == "u8"
         d_f = torch.from_numpy(frames[pix][:F]).to(dev)
         px = F * H * W

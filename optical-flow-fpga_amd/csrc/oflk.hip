@@ -20,6 +20,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/oflk.h"
@@ -319,6 +320,61 @@ unsigned long long conv_threshold(double count)
     return hi;
 }
 
+// ---- dispatch: a runtime fact lifted to a compile-time one and handed to a generic lambda.  Every templated kernel is
+// launched through these; a launch site nests them and names the kernel once, e.g.
+//   with_bool(vec, [&](auto VEC) { hipLaunchKernelGGL((k<decltype(VEC)::value>), grid, block, 0, s, a); });
+// A site instantiates exactly the combinations its lambdas are called with: where a product of the runtime facts would
+// hold a kernel that is not built, the site narrows it with `if constexpr`.
+template <class T> struct Pix { using type = T; };   // the frames' element type, as a tag
+template <int V> constexpr std::integral_constant<int, V> int_c{};
+
+template <class F>
+void with_bool(bool b, F &&f)
+{
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+template <class F>
+void with_pix(bool u8, F &&f)
+{
+    if (u8) f(Pix<unsigned char>{});
+    else f(Pix<float>{});
+}
+
+// f(int_c<v>) for the one of Vs that v equals; false, and no call, when it is none of them
+template <int... Vs, class F>
+bool with_int(int v, F &&f)
+{
+    return ((v == Vs ? (f(int_c<Vs>), true) : false) || ...);
+}
+
+// the half windows with tiled kernels (tiled_window)
+template <class F>
+bool with_half_window(int hw, F &&f) { return with_int<1, 2, 3, 4, 5>(hw, f); }
+
+// is q a multiple of m bytes (m a power of two)?  The vector instantiations of the kernels want their planes aligned.
+inline bool aligned(const void *q, unsigned m) { return (reinterpret_cast<uintptr_t>(q) & (m - 1)) == 0; }
+
+// Segments of a launch that gives one wave a strip of columns times a segment of rows (k_lks, k_lk16d): `seg_rows` rows each
+// when the launch has rounds of the chip's `slots` wave slots to spare (a segment pays extra rows of loads), sized so that
+// the launch is a whole number of rounds; shorter ones, of at least 40 rows, when it would otherwise leave slots of its one
+// round empty.  thin_rows > 0: a launch that cannot fill half the slots even so trades rows per segment, down to
+// thin_rows, for parallel waves.  Never under 8 rows.
+struct Segments { int segs, rows; };
+Segments wave_segments(int H, long strips, long slots, int seg_rows, int thin_rows)
+{
+    long segs = ((long)H + seg_rows - 1) / seg_rows;
+    const double rounds = (double)(strips * segs) / (double)slots;
+    if (rounds > 0.75) segs = std::max<long>(1, (long)std::ceil(rounds - 0.25) * slots / strips);
+    else segs = std::max(segs, std::min(slots / std::max<long>(strips, 1), std::max<long>(1, H / 40)));   // fill the one round, >= 40 rows each
+    if (thin_rows > 0 && strips * segs < slots / 2)
+        segs = std::max(segs, std::min(slots / 2 / std::max<long>(strips, 1), std::max<long>(1, H / thin_rows)));
+    segs = std::min<long>(segs, std::max<long>(1, H / 8));
+    const int rows = (int)(((long)H + segs - 1) / segs);
+    return {(H + rows - 1) / rows, rows};
+}
+
 // resident blocks of the redo pass after the streaming single-scale kernel: one per CU -- an empty list (the common case)
 // then costs 7 us instead of the 22 us of a full round of 1024 blocks, a long one is walked four times slower
 #ifndef OFLK_REDO_BLOCKS
@@ -350,12 +406,11 @@ int launch_lk(oflk_plan *plan, hipStream_t s, int cls, int hw, const LkArgs &a_i
             return fail(OFLK_ERR_UNSUPPORTED, "the fused iteration has no kernel for half window %d", hw);   // (plans of such windows run unfused)
         } else {
             const dim3 grid((a.W + 63) / 64, (a.H + 3) / 4, (unsigned)B);
-            if constexpr (MODE == MODE_SINGLE) {
-                if (u8) hipLaunchKernelGGL((k_lk_generic<MODE_SINGLE, unsigned char>), grid, dim3(256), 0, s, a, hw);
-                else hipLaunchKernelGGL((k_lk_generic<MODE_SINGLE, float>), grid, dim3(256), 0, s, a, hw);
-            } else {
-                hipLaunchKernelGGL((k_lk_generic<MODE_GRADS, float>), grid, dim3(256), 0, s, a, hw);
-            }
+            const auto generic = [&](auto PIX) {
+                hipLaunchKernelGGL((k_lk_generic<MODE, typename decltype(PIX)::type>), grid, dim3(256), 0, s, a, hw);
+            };
+            if constexpr (MODE == MODE_SINGLE) with_pix(u8, generic);
+            else generic(Pix<float>{});
             HIP_TRY(hipGetLastError());
             return OFLK_OK;
         }
@@ -405,53 +460,36 @@ int launch_lk(oflk_plan *plan, hipStream_t s, int cls, int hw, const LkArgs &a_i
 #endif
     // the VEC instantiation moves 16 / 8 bytes per lane: every plane must start 16-byte aligned
     // (each row then does, W % 4 == 0); anything else takes the element-wise instantiation
-    auto al16 = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
-    auto al4 = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 3u) == 0; };
-    const bool frames_ok = u8 ? (al4(a.prev) && al4(a.curr)) : (al16(a.prev) && al16(a.curr));   // uint8: 4 pixels per dword
-    const bool vec = (a.W & 3) == 0 && frames_ok && al16(a.aux) && al16(a.fl[0]) && al16(a.fl[1]) && al16(a.ou) && al16(a.ov);
-#define OFLK_LAUNCH_LKW(HWV)                                                                          \
-    do {                                                                                              \
-        if constexpr (MODE != MODE_GRADS) {                                                           \
-            if (u8) {                                                                                 \
-                if (vec) hipLaunchKernelGGL((k_lkw<HWV, MODE, true, unsigned char>), grid, dim3(256), 0, s, a);  \
-                else hipLaunchKernelGGL((k_lkw<HWV, MODE, false, unsigned char>), grid, dim3(256), 0, s, a);     \
-                break;                                                                                \
-            }                                                                                         \
-        }                                                                                             \
-        if (vec) hipLaunchKernelGGL((k_lkw<HWV, MODE, true>), grid, dim3(256), 0, s, a);                  \
-        else hipLaunchKernelGGL((k_lkw<HWV, MODE, false>), grid, dim3(256), 0, s, a);                     \
-    } while (0)
+    const bool frames_ok = u8 ? (aligned(a.prev, 4) && aligned(a.curr, 4)) : (aligned(a.prev, 16) && aligned(a.curr, 16));   // uint8: 4 pixels per dword
+    const bool vec = (a.W & 3) == 0 && frames_ok && aligned(a.aux, 16) && aligned(a.fl[0], 16) && aligned(a.fl[1], 16) &&
+                     aligned(a.ou, 16) && aligned(a.ov, 16);
+    // REDOL: the instantiation that walks the redo list
+    const auto tile = [&](auto HW, auto REDOL) {
+        const auto typed = [&](auto PIX) {
+            with_bool(vec, [&](auto VEC) {
+                hipLaunchKernelGGL((k_lkw<decltype(HW)::value, MODE, decltype(VEC)::value, typename decltype(PIX)::type, decltype(REDOL)::value>),
+                                   grid, dim3(256), 0, s, a);
+            });
+        };
+        if constexpr (MODE == MODE_GRADS) typed(Pix<float>{});   // gradients are float planes
+        else with_pix(u8, typed);
+    };
     if constexpr (MODE == MODE_SINGLE) {
-        if (a.redo_pass && hw == 3) {   // the 7x7 kernel's list-walking instantiation
-            if (u8) {
-                if (vec) hipLaunchKernelGGL((k_lkw<3, MODE_SINGLE, true, unsigned char, true>), grid, dim3(256), 0, s, a);
-                else hipLaunchKernelGGL((k_lkw<3, MODE_SINGLE, false, unsigned char, true>), grid, dim3(256), 0, s, a);
-            } else {
-                if (vec) hipLaunchKernelGGL((k_lkw<3, MODE_SINGLE, true, float, true>), grid, dim3(256), 0, s, a);
-                else hipLaunchKernelGGL((k_lkw<3, MODE_SINGLE, false, float, true>), grid, dim3(256), 0, s, a);
-            }
+        if (a.redo_pass && hw == 3) {   // only the 7x7 kernel has the list-walking instantiation
+            tile(int_c<3>, std::true_type{});
             HIP_TRY(hipGetLastError());
             return OFLK_OK;
         }
     }
-    switch (hw) {
-        case 1: OFLK_LAUNCH_LKW(1); break;
-        case 2: OFLK_LAUNCH_LKW(2); break;
-        case 3: OFLK_LAUNCH_LKW(3); break;
-        case 4: OFLK_LAUNCH_LKW(4); break;
-        case 5: OFLK_LAUNCH_LKW(5); break;
-        default: return fail(OFLK_ERR_UNSUPPORTED, "half window %d not built", hw);
-    }
-#undef OFLK_LAUNCH_LKW
+    if (!with_half_window(hw, [&](auto HW) { tile(HW, std::false_type{}); })) return fail(OFLK_ERR_UNSUPPORTED, "half window %d not built", hw);
     HIP_TRY(hipGetLastError());
     return OFLK_OK;
 }
 
 // k_lks (oflk_stream.hpp): the streaming form of the 5x5 kernel (single-scale: 7x7 too), for passes whose window sums need
 // not be in NumPy's order (the tolerant mode's fine levels; single-scale on integer-valued frames, where any order is
-// exact).  One wave per (strip of 120 output columns, segment of Hs rows); segments are sized so that the launch is a whole
-// number of rounds of the chip's wave slots at the kernel's occupancy, ~128 rows each when there are rounds to spare (a
-// segment pays 2 (hw + 1) extra rows), shorter ones when the launch would otherwise leave wave slots empty.
+// exact).  One wave per (strip of 120 output columns, segment of Hs rows); wave_segments sizes the segments, ~128 rows each
+// when there are rounds to spare (a segment pays 2 (hw + 1) extra rows).
 #ifndef OFLK_LKS_SEG_ROWS
 #define OFLK_LKS_SEG_ROWS 128
 #endif
@@ -463,55 +501,34 @@ int launch_lks(oflk_plan *plan, hipStream_t s, int cls, const LkArgs &a_in, int 
     Prof pr(plan, s, cls);
     const long strips = ((long)a.W + kLksOutW - 1) / kLksOutW * B;
     const long slots = 256 * 4 * (MODE == MODE_SINGLE ? 4 : OFLK_LKS_WAVES);   // wave slots of the chip at the kernel's occupancy (SINGLE: ~100 VGPRs)
-    long segs = ((long)a.H + OFLK_LKS_SEG_ROWS - 1) / OFLK_LKS_SEG_ROWS;   // a segment pays 6 extra rows: ~128 rows each when the launch has rounds to spare
-    const double rounds = (double)(strips * segs) / (double)slots;
-    if (rounds > 0.75) segs = std::max<long>(1, (long)std::ceil(rounds - 0.25) * slots / strips);
-    else segs = std::max(segs, std::min(slots / std::max<long>(strips, 1), std::max<long>(1, a.H / 40)));   // fill the one round, >= 40 rows each
-    // a launch that cannot fill the slots even so (a single pair in the tolerant mode) trades rows per segment for parallel waves
-    if (strips * segs < slots / 2) segs = std::max(segs, std::min(slots / 2 / std::max<long>(strips, 1), std::max<long>(1, a.H / 12)));
-    segs = std::min<long>(segs, std::max<long>(1, a.H / 8));
-    a.Hs = (int)(((long)a.H + segs - 1) / segs);
-    a.segs = (a.H + a.Hs - 1) / a.Hs;
+    // a segment pays 6 extra rows; a launch that cannot fill the slots (a single pair in the tolerant mode) goes down to 12 rows
+    const Segments sg = wave_segments(a.H, strips, slots, OFLK_LKS_SEG_ROWS, 12);
+    a.Hs = sg.rows;
+    a.segs = sg.segs;
     const long nwave = strips * a.segs;
     dim3 grid((unsigned)((nwave + 3) / 4)), block(256);
-    auto al = [](const void *q, unsigned m) { return (reinterpret_cast<uintptr_t>(q) & (m - 1)) == 0; };
-    const bool frames_ok = u8 ? (al(a.prev, 2) && al(a.curr, 2)) : (al(a.prev, 8) && al(a.curr, 8));
-    const bool vec = (a.W & 1) == 0 && a.W >= 2 && frames_ok && al(a.ou, 8) && al(a.ov, 8) &&
-                     (MODE != MODE_ITER || (al(a.fl[0], 16) && al(a.fl[1], 16)));
-#define OFLK_LAUNCH_LKS(WV)                                                                                   \
-    do {                                                                                                      \
-        if (u8) {                                                                                             \
-            if (vec) hipLaunchKernelGGL((k_lks<MODE, true, WV, unsigned char>), grid, block, 0, s, a);        \
-            else hipLaunchKernelGGL((k_lks<MODE, false, WV, unsigned char>), grid, block, 0, s, a);           \
-        } else {                                                                                              \
-            if (vec) hipLaunchKernelGGL((k_lks<MODE, true, WV, float>), grid, block, 0, s, a);                \
-            else hipLaunchKernelGGL((k_lks<MODE, false, WV, float>), grid, block, 0, s, a);                   \
-        }                                                                                                     \
-    } while (0)
+    const bool frames_ok = u8 ? (aligned(a.prev, 2) && aligned(a.curr, 2)) : (aligned(a.prev, 8) && aligned(a.curr, 8));
+    const bool vec = (a.W & 1) == 0 && a.W >= 2 && frames_ok && aligned(a.ou, 8) && aligned(a.ov, 8) &&
+                     (MODE != MODE_ITER || (aligned(a.fl[0], 16) && aligned(a.fl[1], 16)));
+    // WV: the warp's arithmetic; UPS: the flow upsampling fused in; HW: the half window
+    const auto stream = [&](auto WV, auto UPS, auto HW) {
+        with_pix(u8, [&](auto PIX) {
+            with_bool(vec, [&](auto VEC) {
+                hipLaunchKernelGGL((k_lks<MODE, decltype(VEC)::value, decltype(WV)::value, typename decltype(PIX)::type, decltype(UPS)::value,
+                                          decltype(HW)::value>), grid, block, 0, s, a);
+            });
+        });
+    };
     if constexpr (MODE == MODE_ITER) {
-        if (a.up_src != nullptr) {
-            // first iteration of a level with the flow upsampling fused in (tolerant mode)
-            if (u8) {
-                if (vec) hipLaunchKernelGGL((k_lks<MODE_ITER, true, WARP_LERP64, unsigned char, true>), grid, block, 0, s, a);
-                else hipLaunchKernelGGL((k_lks<MODE_ITER, false, WARP_LERP64, unsigned char, true>), grid, block, 0, s, a);
-            } else {
-                if (vec) hipLaunchKernelGGL((k_lks<MODE_ITER, true, WARP_LERP64, float, true>), grid, block, 0, s, a);
-                else hipLaunchKernelGGL((k_lks<MODE_ITER, false, WARP_LERP64, float, true>), grid, block, 0, s, a);
-            }
-        } else if (warp == WARP_LERP64) OFLK_LAUNCH_LKS(WARP_LERP64);
-        else OFLK_LAUNCH_LKS(WARP_SCIPY);
-    } else if (hw == 3) {
-        if (u8) {
-            if (vec) hipLaunchKernelGGL((k_lks<MODE_SINGLE, true, WARP_SCIPY, unsigned char, false, 3>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((k_lks<MODE_SINGLE, false, WARP_SCIPY, unsigned char, false, 3>), grid, block, 0, s, a);
-        } else {
-            if (vec) hipLaunchKernelGGL((k_lks<MODE_SINGLE, true, WARP_SCIPY, float, false, 3>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((k_lks<MODE_SINGLE, false, WARP_SCIPY, float, false, 3>), grid, block, 0, s, a);
-        }
+        // a level's first iteration with the flow upsampling fused in (tolerant mode) exists for the fused-lerp warp only
+        if (a.up_src != nullptr) stream(int_c<WARP_LERP64>, std::true_type{}, int_c<2>);
+        else if (warp == WARP_LERP64) stream(int_c<WARP_LERP64>, std::false_type{}, int_c<2>);
+        else stream(int_c<WARP_SCIPY>, std::false_type{}, int_c<2>);
+    } else if (hw == 3) {   // single-scale only
+        stream(int_c<WARP_SCIPY>, std::false_type{}, int_c<3>);
     } else {
-        OFLK_LAUNCH_LKS(WARP_SCIPY);
+        stream(int_c<WARP_SCIPY>, std::false_type{}, int_c<2>);
     }
-#undef OFLK_LAUNCH_LKS
     HIP_TRY(hipGetLastError());
     return OFLK_OK;
 }
@@ -520,43 +537,44 @@ inline dim3 grid2d(int W, int H, int n) { return dim3((W + 63) / 64, (H + 3) / 4
 // k_resample: 4 outputs per thread along x
 inline dim3 grid_resample(int W, int H, int n) { return dim3((W + 255) / 256, (H + 3) / 4, n); }
 
-// does every 32 x 16 coarse tile's source span fit the fused kernel's LDS tile?
-// (exactly the index arithmetic of k_pyr_down, evaluated for each tile row / column)
-bool pyr_fused_fits(int h, int w, int ho, int wo, const GaussW &g)
+// Does the source span of every run of `tile` resampled indices (T of them, spread over S source ones) fit `cap` staged
+// source elements?  Exactly the index arithmetic of k_pyr_down and k_upsample, evaluated for each tile row / column.
+bool span_ok(int S, int T, int tile, int cap)
 {
-    if (g.radius != 8) return false;
-    auto span_ok = [](int S, int T, int tile, int cap) {
-        Linspace l = make_linspace(S, T);
-        auto at = [&](int i) { return T <= 1 ? 0.0 : (i == T - 1 ? l.last : (double)i * l.step); };
-        for (int t0 = 0; t0 < T; t0 += tile) {
-            int last = std::min(t0 + tile, T) - 1;
-            int lo = (int)std::floor(at(t0));
-            if (t0 + tile >= T) lo = std::min(lo, std::max(S - 2, 0));
-            int hi = std::min((int)std::floor(at(last)) + 1, S - 1);
-            if (hi - lo + 1 > cap) return false;
-        }
-        return true;
-    };
-    return span_ok(h, ho, kPTH, kPBH) && span_ok(w, wo, kPTW, kPBW);
+    Linspace l = make_linspace(S, T);
+    auto at = [&](int i) { return T <= 1 ? 0.0 : (i == T - 1 ? l.last : (double)i * l.step); };
+    for (int t0 = 0; t0 < T; t0 += tile) {
+        int last = std::min(t0 + tile, T) - 1;
+        int lo = (int)std::floor(at(t0));
+        if (t0 + tile >= T) lo = std::min(lo, std::max(S - 2, 0));
+        int hi = std::min((int)std::floor(at(last)) + 1, S - 1);
+        if (hi - lo + 1 > cap) return false;
+    }
+    return true;
 }
 
-// does every 256 x 4 output block of k_upsample find its coarse source span inside the
-// staged LDS tile?  (same index arithmetic as the kernel)
-bool upsample_fits(int hc, int wc, int ht, int wt)
+// does every 32 x 16 coarse tile's source span fit the fused kernel's LDS tile?
+bool pyr_fused_fits(int h, int w, int ho, int wo, const GaussW &g)
 {
-    auto span_ok = [](int S, int T, int tile, int cap) {
-        Linspace l = make_linspace(S, T);
-        auto at = [&](int i) { return T <= 1 ? 0.0 : (i == T - 1 ? l.last : (double)i * l.step); };
-        for (int t0 = 0; t0 < T; t0 += tile) {
-            int last = std::min(t0 + tile, T) - 1;
-            int lo = (int)std::floor(at(t0));
-            if (t0 + tile >= T) lo = std::min(lo, std::max(S - 2, 0));
-            int hi = std::min((int)std::floor(at(last)) + 1, S - 1);
-            if (hi - lo + 1 > cap) return false;
-        }
-        return true;
-    };
-    return span_ok(hc, ht, kUTH, kUSH) && span_ok(wc, wt, kUTW, kUSW);
+    return g.radius == 8 && span_ok(h, ho, kPTH, kPBH) && span_ok(w, wo, kPTW, kPBW);
+}
+
+// does every 256 x 4 output block of k_upsample find its coarse source span inside the staged LDS tile?
+bool upsample_fits(int hc, int wc, int ht, int wt) { return span_ok(hc, ht, kUTH, kUSH) && span_ok(wc, wt, kUTW, kUSW); }
+
+// The geometry of upsample_flow from a coarse hc x wc field to h x w (lucas_kanade_pyramidal.py:122-136): both planes,
+// values scaled by the size ratios.  The caller adds its planes.
+ResampleArgs upsample_args(int hc, int wc, int h, int w)
+{
+    ResampleArgs r{};
+    r.scale[0] = (float)((double)w / (double)wc);  // scale_x (:123, :135)
+    r.scale[1] = (float)((double)h / (double)hc);  // scale_y (:122, :136)
+    r.H = hc; r.W = wc; r.Ho = h; r.Wo = w;
+    r.ly = make_linspace(hc, h);
+    r.lx = make_linspace(wc, w);
+    r.nplanes = 2;
+    r.apply_scale = 1;
+    return r;
 }
 
 // upsample_flow of `nimg` flow fields (both planes); r is fully populated by the caller
@@ -564,8 +582,7 @@ int launch_upsample(oflk_plan *plan, hipStream_t s, const ResampleArgs &r_in, in
 {
     ResampleArgs r = r_in;
     // 16-byte stores want Wo % 4 == 0 and 16-byte aligned output planes (hipMalloc / torch give that)
-    auto al16 = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
-    r.vec_store = (r.Wo & 3) == 0 && al16(r.out[0]) && (r.interleaved || al16(r.out[1]));
+    r.vec_store = (r.Wo & 3) == 0 && aligned(r.out[0], 16) && (r.interleaved || aligned(r.out[1], 16));
     Prof pr(plan, s, KC_UPSAMPLE);
     if (upsample_fits(r.H, r.W, r.Ho, r.Wo)) {
         dim3 grid((r.Wo + kUTW - 1) / kUTW, (r.Ho + kUTH - 1) / kUTH, nimg);
@@ -587,6 +604,19 @@ struct PyrExtra {
     size_t n_zero_flow = 0;
     bool u8 = false;                  // the input images are uint8 (the caller's frames of a uint8 plan)
 };
+
+// the clear that every pass of a pyramidal call starts from: the per-call state (acc, iters_run, uncertain, log) = 0 and
+// flow = zeros at the coarsest level (lucas_kanade_pyramidal.py:182-184; slot 0: u then v, B * n floats each)
+PyrExtra call_clear(const oflk_plan *p)
+{
+    PyrExtra x;
+    x.zero_words = reinterpret_cast<unsigned *>(p->state);
+    x.n_zero_words = p->state_words();
+    x.n_zero_flow = (size_t)p->B * p->npix(0);
+    x.zero_u = reinterpret_cast<float *>(p->fl(0, 0));
+    x.zero_v = x.zero_u + x.n_zero_flow;
+    return x;
+}
 
 int launch_call_init(oflk_plan *plan, hipStream_t s, const PyrExtra &x)
 {
@@ -626,13 +656,11 @@ int launch_pyr_down(oflk_plan *plan, const GaussW &gauss, hipStream_t s, const f
         dim3 grid((wo + kPTW - 1) / kPTW, (ho + kPTH - 1) / kPTH, nimg);
         Prof pr(plan, s, KC_PYR_FUSED);
         const bool fma = contracted_pyramid(plan);   // opt-in (contracted / tolerant); never the default
-        if (extra && extra->u8) {
-            if (fma) hipLaunchKernelGGL((k_pyr_down<unsigned char, true>), grid, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((k_pyr_down<unsigned char, false>), grid, dim3(256), 0, s, a);
-        } else {
-            if (fma) hipLaunchKernelGGL((k_pyr_down<float, true>), grid, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((k_pyr_down<float, false>), grid, dim3(256), 0, s, a);
-        }
+        with_pix(extra && extra->u8, [&](auto PIX) {
+            with_bool(fma, [&](auto FMA) {
+                hipLaunchKernelGGL((k_pyr_down<typename decltype(PIX)::type, decltype(FMA)::value>), grid, dim3(256), 0, s, a);
+            });
+        });
         HIP_TRY(hipGetLastError());
         return OFLK_OK;
     }
@@ -652,11 +680,13 @@ int launch_pyr_down(oflk_plan *plan, const GaussW &gauss, hipStream_t s, const f
     {
         Prof pr(plan, s, KC_BLUR);
         const bool fma = contracted_pyramid(plan);   // the unfused chain keeps the plan's arithmetic
-        if (fma) hipLaunchKernelGGL((k_blur<0, true>), grid2d(w, h, nimg), dim3(256), 0, s, in, tmpA, h, w, gauss);
-        else hipLaunchKernelGGL((k_blur<0, false>), grid2d(w, h, nimg), dim3(256), 0, s, in, tmpA, h, w, gauss);
+        with_bool(fma, [&](auto FMA) {
+            hipLaunchKernelGGL((k_blur<0, decltype(FMA)::value>), grid2d(w, h, nimg), dim3(256), 0, s, in, tmpA, h, w, gauss);
+        });
         HIP_TRY(hipGetLastError());
-        if (fma) hipLaunchKernelGGL((k_blur<1, true>), grid2d(w, h, nimg), dim3(256), 0, s, (const float *)tmpA, tmpB, h, w, gauss);
-        else hipLaunchKernelGGL((k_blur<1, false>), grid2d(w, h, nimg), dim3(256), 0, s, (const float *)tmpA, tmpB, h, w, gauss);
+        with_bool(fma, [&](auto FMA) {
+            hipLaunchKernelGGL((k_blur<1, decltype(FMA)::value>), grid2d(w, h, nimg), dim3(256), 0, s, (const float *)tmpA, tmpB, h, w, gauss);
+        });
         HIP_TRY(hipGetLastError());
     }
     ResampleArgs r{};
@@ -669,11 +699,12 @@ int launch_pyr_down(oflk_plan *plan, const GaussW &gauss, hipStream_t s, const f
     r.lx = make_linspace(w, wo);
     r.nplanes = 1;
     r.apply_scale = 0;
-    r.vec_store = (wo & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
+    r.vec_store = (wo & 3) == 0 && aligned(out, 16);
     {
         Prof pr(plan, s, KC_RESAMPLE);
-        if (contracted_pyramid(plan)) hipLaunchKernelGGL((k_resample<1, true>), grid_resample(wo, ho, nimg), dim3(256), 0, s, r);
-        else hipLaunchKernelGGL((k_resample<1, false>), grid_resample(wo, ho, nimg), dim3(256), 0, s, r);
+        with_bool(contracted_pyramid(plan), [&](auto FMA) {
+            hipLaunchKernelGGL((k_resample<1, decltype(FMA)::value>), grid_resample(wo, ho, nimg), dim3(256), 0, s, r);
+        });
     }
     HIP_TRY(hipGetLastError());
     return OFLK_OK;
@@ -876,9 +907,8 @@ OFLK_API int oflk_plan_single_scale_fp16(oflk_plan *p, const float *d_prev, cons
     int k = 0;
     while ((double)taps * std::pow(0.5 * (double)pixel_max * std::ldexp(1.0, -k), 2.0) > 60000.0) k++;
     // one wave per (strip of 128 - 4 ceil(R/2) output columns, segment of Hs rows): two columns per lane (k_lk16d;
-    // 7x7: 77 VGPRs = 6 waves per SIMD, halo 6 %).  Segments are sized so that the launch is a whole number of
-    // rounds of the chip's wave slots at the kernel's occupancy, with ~64 rows each (a segment pays 2R extra rows
-    // of loads).
+    // 7x7: 77 VGPRs = 6 waves per SIMD, halo 6 %).  wave_segments sizes the segments, ~64 rows each (a segment pays 2R
+    // extra rows of loads).
     Lk16sArgs g{};
     g.prev = d_prev; g.curr = d_curr; g.u = d_u; g.v = d_v;
     g.H = p->H; g.W = p->W; g.B = p->B;
@@ -890,31 +920,18 @@ OFLK_API int oflk_plan_single_scale_fp16(oflk_plan *p, const float *d_prev, cons
     const int outw = 2 * (64 - 2 * ((hw + 2) / 2));
     const long strips = ((long)g.W + outw - 1) / outw * g.B;
     const long slots = hw <= 2 ? 8192 : hw == 3 ? 6144 : hw == 4 ? 5120 : 4096;   // wave slots of the chip at 8 / 8 / 6 / 5 / 4 waves per SIMD
-    long segs = ((long)g.H + 63) / 64;
-    const double rounds = (double)(strips * segs) / (double)slots;
-    if (rounds > 0.75) segs = std::max<long>(1, (long)std::ceil(rounds - 0.25) * slots / strips);
-    else segs = std::max(segs, std::min(slots / std::max<long>(strips, 1), std::max<long>(1, g.H / 40)));   // fill the one round, >= 40 rows each
-    segs = std::min<long>(segs, std::max<long>(1, g.H / 8));
-    g.Hs = (int)(((long)g.H + segs - 1) / segs);
-    g.segs = (g.H + g.Hs - 1) / g.Hs;
+    const Segments sg = wave_segments(g.H, strips, slots, 64, 0);
+    g.Hs = sg.rows;
+    g.segs = sg.segs;
     const long nwave = strips * g.segs;
     dim3 sgrid((unsigned)((nwave + 3) / 4)), sblock(256);
-    auto al8 = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 7u) == 0; };
-    const bool vec8 = (g.W & 1) == 0 && g.W >= 2 && al8(d_prev) && al8(d_curr) && al8(d_u) && al8(d_v);   // 8-byte column pairs
-#define OFLK_LAUNCH_LK16D(HWV)                                                                 \
-    do {                                                                                       \
-        if (vec8) hipLaunchKernelGGL((k_lk16d<HWV, true>), sgrid, sblock, 0, s, g);            \
-        else hipLaunchKernelGGL((k_lk16d<HWV, false>), sgrid, sblock, 0, s, g);                \
-    } while (0)
-    switch (hw) {
-        case 1: OFLK_LAUNCH_LK16D(1); break;
-        case 2: OFLK_LAUNCH_LK16D(2); break;
-        case 3: OFLK_LAUNCH_LK16D(3); break;
-        case 4: OFLK_LAUNCH_LK16D(4); break;
-        case 5: OFLK_LAUNCH_LK16D(5); break;
-        default: return fail(OFLK_ERR_UNSUPPORTED, "half window %d not built", hw);
-    }
-#undef OFLK_LAUNCH_LK16D
+    const bool vec8 = (g.W & 1) == 0 && g.W >= 2 && aligned(d_prev, 8) && aligned(d_curr, 8) && aligned(d_u, 8) && aligned(d_v, 8);   // 8-byte column pairs
+    const bool built = with_half_window(hw, [&](auto HW) {
+        with_bool(vec8, [&](auto VEC) {
+            hipLaunchKernelGGL((k_lk16d<decltype(HW)::value, decltype(VEC)::value>), sgrid, sblock, 0, s, g);
+        });
+    });
+    if (!built) return fail(OFLK_ERR_UNSUPPORTED, "half window %d not built", hw);
     HIP_TRY(hipGetLastError());
     return OFLK_OK;
 }
@@ -1028,14 +1045,8 @@ int plan_pyramidal(oflk_plan *p, const void *d_prev_in, const void *d_curr_in, b
         return OFLK_OK;
     }
 
-    // per-call state (acc, iters_run, log) = 0 and flow = zeros at the coarsest level (:182-184):
-    // carried by the first pyramid launch, or a launch of its own when there is no pyramid
-    PyrExtra first;
-    first.zero_words = reinterpret_cast<unsigned *>(p->state);
-    first.n_zero_words = p->state_words();
-    first.zero_u = reinterpret_cast<float *>(p->fl(0, 0));   // slot 0 of the coarsest level: 2 * B * n floats
-    first.zero_v = first.zero_u + (size_t)B * p->npix(0);
-    first.n_zero_flow = (size_t)B * p->npix(0);
+    // the call's clear: carried by the first pyramid launch, or a launch of its own when there is no pyramid
+    PyrExtra first = call_clear(p);
     if (L == 1) {
         rc = launch_call_init(p, s, first);
         if (rc) return rc;
@@ -1065,14 +1076,16 @@ int plan_pyramidal(oflk_plan *p, const void *d_prev_in, const void *d_curr_in, b
     // the backward pass on the same pyramid: pair b reads frames b + 1 and b, with its own state block and the coarsest
     // level's flow cleared again (stream order puts this after the forward pass's last reads of both)
     StateSwap sw(p, true);
-    PyrExtra z;
-    z.zero_words = reinterpret_cast<unsigned *>(p->state);
-    z.n_zero_words = p->state_words();
-    z.zero_u = reinterpret_cast<float *>(p->fl(0, 0));
-    z.zero_v = z.zero_u + (size_t)B * p->npix(0);
-    z.n_zero_flow = (size_t)B * p->npix(0);
-    if ((rc = launch_call_init(p, s, z))) return rc;
+    if ((rc = launch_call_init(p, s, call_clear(p)))) return rc;
     return iterate_levels(p, s, d_curr, d_prev, 1, 0, u8, d_ub, d_vb);
+}
+
+// Does level l run the streaming kernel?  Tolerant mode inside its envelope: the two finest levels (order-free window sums,
+// fused-lerp warp).  The launches of the level and the guards of its exit decisions (k_export_fixup) both follow this.
+bool level_streams(const oflk_plan *p, int l)
+{
+    return p->arith == OFLK_ARITH_TOLERANT && tolerant_relaxes(p->L, p->hw, p->K) && l >= p->L - 2 && p->dims[2 * l] > 4 &&
+           p->dims[2 * l + 1] > 4;
 }
 
 // The level loop (lucas_kanade_pyramidal.py:186-223) and the export of one direction: pair b reads prev image img_prev + b
@@ -1086,31 +1099,20 @@ int iterate_levels(oflk_plan *p, hipStream_t s, const float *d_prev, const float
     for (int l = 0; l < L; l++) {
         const int h = p->dims[2 * l], w = p->dims[2 * l + 1];
         const size_t n = (size_t)h * w;
-        // tolerant mode inside its envelope: the two finest levels take the streaming kernel (order-free window sums, fused-lerp
-        // warp), and the flow upsampling into such a level is fused into its first iteration
-        const bool stream = p->arith == OFLK_ARITH_TOLERANT && tolerant_relaxes(L, p->hw, K) && l >= L - 2 && h > 4 && w > 4;
+        // the flow upsampling into a level of the streaming kernel is fused into its first iteration
+        const bool stream = level_streams(p, l);
         const bool fuse_up = stream && l > 0 && K >= 1 && p->dims[2 * (l - 1)] >= 2 && p->dims[2 * (l - 1) + 1] >= 2;
         if (l > 0 && !fuse_up) {
             // upsample_flow (:195-197) from whichever slot holds level l-1's result
-            const int hc = p->dims[2 * (l - 1)], wc = p->dims[2 * (l - 1) + 1];
-            ResampleArgs r{};
+            ResampleArgs r = upsample_args(p->dims[2 * (l - 1)], p->dims[2 * (l - 1) + 1], h, w);
             // interleaved planes: slot s of level l-1 sits s * (B*n_c) float2 elements after slot 0
             r.interleaved = 1;
             r.in[0] = reinterpret_cast<const float *>(p->fl(l - 1, 0));
-            r.in[1] = nullptr;
             r.acc = p->acc();
             r.acc_level = l - 1; r.L = L; r.K = p->Kc(); r.iters = K;
             r.acc_thr = conv_threshold((double)p->npix(l - 1));
             r.in_sel_stride = (size_t)B * p->npix(l - 1);
             r.out[0] = reinterpret_cast<float *>(p->fl(l, 0));
-            r.out[1] = nullptr;
-            r.scale[0] = (float)((double)w / (double)wc);  // scale_x (:123, :135)
-            r.scale[1] = (float)((double)h / (double)hc);  // scale_y (:122, :136)
-            r.H = hc; r.W = wc; r.Ho = h; r.Wo = w;
-            r.ly = make_linspace(hc, h);
-            r.lx = make_linspace(wc, w);
-            r.nplanes = 2;
-            r.apply_scale = 1;
             rc = launch_upsample(p, s, r, B);
             if (rc) return rc;
         }
@@ -1127,17 +1129,15 @@ int iterate_levels(oflk_plan *p, hipStream_t s, const float *d_prev, const float
             a.level = l; a.iter = k; a.L = L; a.K = p->Kc();
             a.H = h; a.W = w;
             if (fuse_up && k == 0) {
-                const int hc = p->dims[2 * (l - 1)], wc = p->dims[2 * (l - 1) + 1];
+                const ResampleArgs r = upsample_args(p->dims[2 * (l - 1)], p->dims[2 * (l - 1) + 1], h, w);
                 a.up_src = p->fl(l - 1, 0);
                 a.up_slot_stride = (size_t)B * p->npix(l - 1);
                 a.up_level = l - 1;
                 a.up_iters = K;
                 a.up_thr = conv_threshold((double)p->npix(l - 1));
-                a.Hc = hc; a.Wc = wc;
-                a.up_ly = make_linspace(hc, h);
-                a.up_lx = make_linspace(wc, w);
-                a.up_sx = (float)((double)w / (double)wc);   // scale_x (:123, :135)
-                a.up_sy = (float)((double)h / (double)hc);   // scale_y (:122, :136)
+                a.Hc = r.H; a.Wc = r.W;
+                a.up_ly = r.ly; a.up_lx = r.lx;
+                a.up_sx = r.scale[0]; a.up_sy = r.scale[1];
             }
             if (stream) rc = launch_lks<MODE_ITER>(p, s, l == L - 1 ? KC_LK_ITER_FINEST : KC_LK_ITER, a, B, u8 && l == L - 1, WARP_LERP64);
             else rc = launch_lk<MODE_ITER>(p, s, l == L - 1 ? KC_LK_ITER_FINEST : KC_LK_ITER, p->hw, a, B, u8 && l == L - 1);
@@ -1163,10 +1163,7 @@ int iterate_levels(oflk_plan *p, hipStream_t s, const float *d_prev, const float
         e.uncertain = p->uncertain();
         for (int l = 0; l < L; l++) {
             const double t = (double)e.thr[l];
-            const int h = p->dims[2 * l], w = p->dims[2 * l + 1];
-            // the same choice of kernel as the level's launches above
-            const bool stream = p->arith == OFLK_ARITH_TOLERANT && tolerant_relaxes(L, p->hw, K) && l >= L - 2 && h > 4 && w > 4;
-            const double g = decision_guard(stream ? SUM_STREAM : SUM_TILES, h, w);
+            const double g = decision_guard(level_streams(p, l) ? SUM_STREAM : SUM_TILES, p->dims[2 * l], p->dims[2 * l + 1]);
             e.guard_lo[l] = (unsigned long long)std::floor(t * (1.0 - g));
             e.guard_hi[l] = (unsigned long long)std::ceil(t * (1.0 + g));
         }
@@ -1298,17 +1295,9 @@ int resolve_pair(oflk_plan *p, int b, const void *d_prev_in, const void *d_curr_
         const int h = p->dims[2 * l], w = p->dims[2 * l + 1];
         const size_t n = (size_t)h * w;
         if (l > 0) {
-            const int hc = p->dims[2 * (l - 1)], wc = p->dims[2 * (l - 1) + 1];
-            ResampleArgs r{};
+            ResampleArgs r = upsample_args(p->dims[2 * (l - 1)], p->dims[2 * (l - 1) + 1], h, w);
             r.in[0] = x.u[l - 1]; r.in[1] = x.v[l - 1];
             r.out[0] = x.u[l]; r.out[1] = x.v[l];
-            r.scale[0] = (float)((double)w / (double)wc);
-            r.scale[1] = (float)((double)h / (double)hc);
-            r.H = hc; r.W = wc; r.Ho = h; r.Wo = w;
-            r.ly = make_linspace(hc, h);
-            r.lx = make_linspace(wc, w);
-            r.nplanes = 2;
-            r.apply_scale = 1;
             if ((rc = launch_upsample(nullptr, s, r, 1))) return rc;
         }
         const float *lp = (l == L - 1) ? fp : x.pyr[l];
@@ -1466,19 +1455,26 @@ OFLK_API int oflk_plan_read_level_flow(oflk_plan *p, int level, int pair, float 
     return OFLK_OK;
 }
 
+namespace {
+int check_arith(int mode)
+{
+    if (mode != OFLK_ARITH_EXACT && mode != OFLK_ARITH_CONTRACTED && mode != OFLK_ARITH_TOLERANT)
+        return fail(OFLK_ERR_INVALID, "arithmetic mode must be OFLK_ARITH_EXACT (0), OFLK_ARITH_CONTRACTED (1) or OFLK_ARITH_TOLERANT (2), got %d", mode);
+    return OFLK_OK;
+}
+}  // namespace
+
 OFLK_API int oflk_plan_set_arithmetic(oflk_plan *p, int mode)
 {
     if (!p) return fail(OFLK_ERR_INVALID, "NULL plan");
-    if (mode != OFLK_ARITH_EXACT && mode != OFLK_ARITH_CONTRACTED && mode != OFLK_ARITH_TOLERANT)
-        return fail(OFLK_ERR_INVALID, "arithmetic mode must be OFLK_ARITH_EXACT (0), OFLK_ARITH_CONTRACTED (1) or OFLK_ARITH_TOLERANT (2), got %d", mode);
+    if (int rc = check_arith(mode)) return rc;
     p->arith = mode;
     return OFLK_OK;
 }
 
 OFLK_API int oflk_set_host_arithmetic(int mode)
 {
-    if (mode != OFLK_ARITH_EXACT && mode != OFLK_ARITH_CONTRACTED && mode != OFLK_ARITH_TOLERANT)
-        return fail(OFLK_ERR_INVALID, "arithmetic mode must be OFLK_ARITH_EXACT (0), OFLK_ARITH_CONTRACTED (1) or OFLK_ARITH_TOLERANT (2), got %d", mode);
+    if (int rc = check_arith(mode)) return rc;
     g_host_arith.store(mode);
     return OFLK_OK;
 }
@@ -2263,15 +2259,12 @@ int fb_launch(const float *uf, const float *vf, const float *ub, const float *vb
     a.alpha = alpha; a.beta = beta;
     const int dirs = ((ef || qf) ? 1 : 0) | ((eb || qb) ? 2 : 0);   // >= 1 (check_fb)
     const dim3 grid = grid2d(W, H, B);
-#define OFLK_LAUNCH_FB(NARROW)                                                                   \
-    do {                                                                                         \
-        if (dirs == 1) hipLaunchKernelGGL((k_fb_check<NARROW, 1>), grid, dim3(256), 0, s, a);    \
-        else if (dirs == 2) hipLaunchKernelGGL((k_fb_check<NARROW, 2>), grid, dim3(256), 0, s, a); \
-        else hipLaunchKernelGGL((k_fb_check<NARROW, 3>), grid, dim3(256), 0, s, a);             \
-    } while (0)
-    if (W == 1) OFLK_LAUNCH_FB(true);
-    else OFLK_LAUNCH_FB(false);
-#undef OFLK_LAUNCH_FB
+    const bool some = with_int<1, 2, 3>(dirs, [&](auto DIRS) {
+        with_bool(W == 1, [&](auto NARROW) {
+            hipLaunchKernelGGL((k_fb_check<decltype(NARROW)::value, decltype(DIRS)::value>), grid, dim3(256), 0, s, a);
+        });
+    });
+    if (!some) return fail(OFLK_ERR_INVALID, "every output is NULL");
     HIP_TRY(hipGetLastError());
     return OFLK_OK;
 }
@@ -2464,16 +2457,12 @@ int corner_score_launch(const void *frames, bool u8, int F, int H, int W, int wi
     a.F = F; a.H = H; a.W = W;
     const dim3 grid((unsigned)((W + kCsTW - 1) / kCsTW), (unsigned)std::min((H + kCsTH - 1) / kCsTH, 65535),
                     (unsigned)std::min(F, 65535));
-#define OFLK_CS(HWIN)                                                                                                  \
-    case HWIN:                                                                                                        \
-        if (u8) hipLaunchKernelGGL((k_corner_score<unsigned char, HWIN>), grid, dim3(256), 0, s, a);                  \
-        else hipLaunchKernelGGL((k_corner_score<float, HWIN>), grid, dim3(256), 0, s, a);                             \
-        break;
-    switch (window_size / 2) {
-        OFLK_CS(1) OFLK_CS(2) OFLK_CS(3) OFLK_CS(4) OFLK_CS(5)
-        default: return fail(OFLK_ERR_UNSUPPORTED, "corner window %d not built", window_size);
-    }
-#undef OFLK_CS
+    const bool built = with_half_window(window_size / 2, [&](auto HW) {
+        with_pix(u8, [&](auto PIX) {
+            hipLaunchKernelGGL((k_corner_score<typename decltype(PIX)::type, decltype(HW)::value>), grid, dim3(256), 0, s, a);
+        });
+    });
+    if (!built) return fail(OFLK_ERR_UNSUPPORTED, "corner window %d not built", window_size);
     HIP_TRY(hipGetLastError());
     return OFLK_OK;
 }
@@ -2625,8 +2614,7 @@ int replenish_launch(const void *frame, bool u8, int H, int W, int window_size, 
     c.head = head; c.node = node; c.cell = std::max(g.cell, 1); c.gw = g.gw; c.gh = g.gh;
     c.md2 = (double)md * (double)md;
     const dim3 cgrid((unsigned)((W + 63) / 64), (unsigned)std::min((H + 3) / 4, 65535), 1);
-    if (head) hipLaunchKernelGGL(k_corner_cand<true>, cgrid, dim3(256), 0, s, c);
-    else hipLaunchKernelGGL(k_corner_cand<false>, cgrid, dim3(256), 0, s, c);
+    with_bool(head != nullptr, [&](auto SEEDS) { hipLaunchKernelGGL(k_corner_cand<decltype(SEEDS)::value>, cgrid, dim3(256), 0, s, c); });
     HIP_TRY(hipGetLastError());
     SelectArgs a{};
     a.keys = keys; a.ncand = ncand;
@@ -2819,8 +2807,7 @@ int track_launch(const float *uf, const float *vf, const float *ub, const float 
     a.B = B; a.H = H; a.W = W; a.N = N; a.t0 = t0;
     a.alpha = alpha; a.beta = beta;
     const dim3 grid((unsigned)((N + 63) / 64));
-    if (W == 1) hipLaunchKernelGGL(k_track<true>, grid, dim3(64), 0, s, a);
-    else hipLaunchKernelGGL(k_track<false>, grid, dim3(64), 0, s, a);
+    with_bool(W == 1, [&](auto NARROW) { hipLaunchKernelGGL(k_track<decltype(NARROW)::value>, grid, dim3(64), 0, s, a); });
     HIP_TRY(hipGetLastError());
     return OFLK_OK;
 }
@@ -3282,16 +3269,9 @@ OFLK_API int oflk_upsample_flow(const float *flow_u, const float *flow_v, int Hc
     if ((rc = call.upload(&du, flow_u, nc)) || (rc = call.upload(&dv, flow_v, nc)) || (rc = call.alloc(&ou, nt)) ||
         (rc = call.alloc(&ov, nt)))
         return rc;
-    ResampleArgs r{};
+    ResampleArgs r = upsample_args(Hc, Wc, Ht, Wt);
     r.in[0] = du; r.in[1] = dv;
     r.out[0] = ou; r.out[1] = ov;
-    r.scale[0] = (float)((double)Wt / (double)Wc);
-    r.scale[1] = (float)((double)Ht / (double)Hc);
-    r.H = Hc; r.W = Wc; r.Ho = Ht; r.Wo = Wt;
-    r.ly = make_linspace(Hc, Ht);
-    r.lx = make_linspace(Wc, Wt);
-    r.nplanes = 2;
-    r.apply_scale = 1;
     if ((rc = launch_upsample(nullptr, nullptr, r, 1))) return rc;
     if ((rc = call.to_host(u_out, ou, nt)) || (rc = call.to_host(v_out, ov, nt))) return rc;
     return call.sync();

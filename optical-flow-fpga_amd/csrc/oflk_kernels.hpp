@@ -2978,7 +2978,7 @@ struct ExportArgs {
 //   - the roundings to the grid: at most 2^-21 px each, one per PARTIAL, i.e. an absolute error of partials 2^-21 / n on
 //     the mean -- it does not shrink with the mean, so relative to m it is partials 2^-21 / (n m).  k_lkw rounds per
 //     block (at most one per 64 x 8 k5NY tile); k_lks per wave (strips of 120 columns x segments of >= 8 rows; see
-//     launch_lks, whose last segment rule caps them at max(1, H / 8)).  Partials without a pixel are 0 and exact.
+//     wave_segments, whose last rule caps them at max(1, H / 8)).  Partials without a pixel are 0 and exact.
 //   - the clamp at kAccBlockMax = 2^28 px per partial: a clamped total alone is >= 2^28 px, a mean >= 0.01 at any plane
 //     below 2.6e10 px (a plane is < 2^30), so the clamp never turns "not below" into "below".
 //   - the logged mean (and the threshold T is compared with) is float32(T 2^-20 / n): 2^-24.

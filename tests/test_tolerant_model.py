@@ -390,7 +390,7 @@ def _const(pattern: str, file: str) -> int:
 
 
 def _lks_segments(H: int, W: int, B: int):
-    """(segments, rows per segment) of a k_lks iteration launch: launch_lks in csrc/oflk.hip, restated"""
+    """(segments, rows per segment) of a k_lks iteration launch: wave_segments as launch_lks calls it in csrc/oflk.hip, restated"""
     out_w = _const(r"constexpr int kLksOutW = (\d+);", "oflk_stream.hpp")
     waves = _const(r"#define OFLK_LKS_WAVES (\d+)", "oflk_stream.hpp")
     seg_rows = _const(r"#define OFLK_LKS_SEG_ROWS (\d+)", "oflk.hip")

@@ -2422,29 +2422,51 @@ int check_select(float q, float md, int K)
     return OFLK_OK;
 }
 
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// a grid of cells of side ceil(md) over the frame (one cell once that covers the frame); none unless `on`
+struct CellGrid { int cell, gw, gh; };
+
+CellGrid cell_grid(bool on, float md, int H, int W)
+{
+    if (!on) return {};
+    const int cell = (int)std::min<double>(std::ceil((double)md), (double)std::max(H, W));
+    return {cell, (W + cell - 1) / cell, (H + cell - 1) / cell};
+}
+
 // The workspace of oflk_good_features, 256-byte aligned pieces: fmax [F] and ncand [F] (zeroed by k_corner_init), S
-// [F][H][W], keys [F][H*W] (the worst case: every pixel a candidate) and, for md > 1, the grid [F][gh][gw][4]
-struct FeatGeom {
-    int cell = 0, gw = 0, gh = 0;
-    size_t off_cnt = 0, off_s = 0, off_keys = 0, off_grid = 0, bytes = 0;
+// [F][H][W], keys [F][H*W] (the worst case: every pixel a candidate) and, for md > 1, the grid [F][gh][gw][4].
+// That of oflk_replenish_features (slots = K) is the one of one frame, then the seed grid's heads [gh][gw] (md = 0:
+// none), its nodes [K], the free list [K] and its length [1].
+struct FeatWs {
+    CellGrid occ, seed;   // the selection's occupancy grid and the seeds' grid
+    unsigned *fmax, *ncand;
+    float *S;
+    unsigned long long *keys;
+    int *grid, *head, *free, *nfree;   // grid, head: NULL without their cells
+    int2 *node;
+    size_t bytes;
 };
 
-FeatGeom feat_geom(int F, int H, int W, float md)
+// the pieces of a workspace at `base` (NULL: only `bytes` is of use)
+FeatWs feat_ws(void *base, int F, int H, int W, float md, int slots)
 {
-    FeatGeom g;
-    if (md > 1.0f) {   // cells of side ceil(md) (one cell once that covers the frame)
-        g.cell = (int)std::min<double>(std::ceil((double)md), (double)std::max(H, W));
-        g.gw = (W + g.cell - 1) / g.cell;
-        g.gh = (H + g.cell - 1) / g.cell;
-    }
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    FeatWs v{};
+    v.occ = cell_grid(md > 1.0f, md, H, W);
+    if (slots) v.seed = cell_grid(md > 0.0f, md, H, W);
+    auto take = [&](auto *&p, size_t n) {   // the next piece: n elements
+        p = n ? reinterpret_cast<std::remove_reference_t<decltype(p)>>(reinterpret_cast<uintptr_t>(base) + v.bytes) : nullptr;
+        v.bytes += align256(n * sizeof(*p));
+    };
     const size_t nF = (size_t)F, plane = (size_t)H * (size_t)W;
-    g.off_cnt = al(nF * sizeof(unsigned));
-    g.off_s = g.off_cnt + al(nF * sizeof(unsigned));
-    g.off_keys = g.off_s + al(nF * plane * sizeof(float));
-    g.off_grid = g.off_keys + al(nF * plane * sizeof(unsigned long long));
-    g.bytes = g.off_grid + (g.cell ? al(nF * (size_t)g.gw * g.gh * 4 * sizeof(int)) : 0);
-    return g;
+    take(v.fmax, nF); take(v.ncand, nF);
+    take(v.S, nF * plane); take(v.keys, nF * plane);
+    take(v.grid, nF * (size_t)v.occ.gw * v.occ.gh * 4);
+    if (slots) {
+        take(v.head, (size_t)v.seed.gw * v.seed.gh);
+        take(v.node, (size_t)slots); take(v.free, (size_t)slots); take(v.nfree, 1);
+    }
+    return v;
 }
 
 int corner_score_launch(const void *frames, bool u8, int F, int H, int W, int window_size, float *score, unsigned *fmax,
@@ -2467,35 +2489,57 @@ int corner_score_launch(const void *frames, bool u8, int F, int H, int W, int wi
     return OFLK_OK;
 }
 
-// score, candidates and selection of F frames on stream s; the arguments are checked
-int good_features_launch(const void *frames, bool u8, int F, int H, int W, int window_size, float q, float md, int K,
-                         void *workspace, int *count, float *xy, float *score, hipStream_t s)
+// The slot side of a detection (the replenish statement, F = 1): the slots' state (xy, visible) of frame t in; the new
+// points go into the free slots of qt and of the selection's xy (the queries), born [K] and detected [1] out
+struct SlotSide {
+    const float *xy; const unsigned char *visible;
+    int *qt; unsigned char *born; int *detected; int t;
+};
+
+// Score, candidates and selection of F frames on stream s, no host round trip; the arguments are checked.  Without
+// slots the selection writes count, xy and score; with them it fills free slots and uses neither count nor score.
+int detect_launch(const void *frames, bool u8, int F, int H, int W, int window_size, float q, float md, int K, const FeatWs &ws,
+                  int *count, float *xy, float *score, const SlotSide *slots, hipStream_t s)
 {
-    const FeatGeom g = feat_geom(F, H, W, md);
-    char *w = static_cast<char *>(workspace);
-    unsigned *fmax = reinterpret_cast<unsigned *>(w), *ncand = reinterpret_cast<unsigned *>(w + g.off_cnt);
-    float *S = reinterpret_cast<float *>(w + g.off_s);
-    unsigned long long *keys = reinterpret_cast<unsigned long long *>(w + g.off_keys);
-    hipLaunchKernelGGL(k_corner_init, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, s, fmax, ncand, F);
-    HIP_TRY(hipGetLastError());
-    int rc = corner_score_launch(frames, u8, F, H, W, window_size, S, fmax, s);
-    if (rc) return rc;
+    const unsigned fz = (unsigned)std::min(F, 65535);
     CandArgs c{};
-    c.score = S; c.fmax = fmax; c.keys = keys; c.ncand = ncand;
+    c.score = ws.S; c.fmax = ws.fmax; c.keys = ws.keys; c.ncand = ws.ncand;
     c.F = F; c.H = H; c.W = W;
     c.q = (double)q;
-    hipLaunchKernelGGL(k_corner_cand<false>, dim3((unsigned)((W + 63) / 64), (unsigned)std::min((H + 3) / 4, 65535),
-                                                  (unsigned)std::min(F, 65535)), dim3(256), 0, s, c);
-    HIP_TRY(hipGetLastError());
     SelectArgs a{};
-    a.keys = keys; a.ncand = ncand;
-    a.grid = g.cell ? reinterpret_cast<int *>(w + g.off_grid) : nullptr;
-    a.count = count; a.xy = xy; a.score = score;
+    a.keys = ws.keys; a.ncand = ws.ncand; a.grid = ws.grid;
+    a.count = slots ? slots->detected : count; a.xy = xy; a.score = slots ? nullptr : score;
     a.F = F; a.H = H; a.W = W; a.K = K;
-    a.cell = std::max(g.cell, 1); a.gw = g.gw; a.gh = g.gh;
+    a.cell = std::max(ws.occ.cell, 1); a.gw = ws.occ.gw; a.gh = ws.occ.gh;
     a.md2 = (double)md * (double)md;
-    a.use_grid = g.cell != 0;
-    hipLaunchKernelGGL(k_corner_select<false>, dim3((unsigned)std::min(F, 65535)), dim3(256), 0, s, a);
+    a.use_grid = ws.occ.cell != 0;
+    hipLaunchKernelGGL(k_corner_init, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, s, ws.fmax, ws.ncand, F);
+    HIP_TRY(hipGetLastError());
+    int rc = corner_score_launch(frames, u8, F, H, W, window_size, ws.S, ws.fmax, s);
+    if (rc) return rc;
+    if (slots) {   // the seeds' lists and the free list, and what the two kernels take of them
+        if (ws.head) {
+            const int cells = ws.seed.gw * ws.seed.gh;
+            hipLaunchKernelGGL(k_seed_clear, dim3((unsigned)std::min((cells + 255) / 256, 1024)), dim3(256), 0, s, ws.head, cells);
+            HIP_TRY(hipGetLastError());
+        }
+        SeedArgs sa{};
+        sa.xy = slots->xy; sa.visible = slots->visible; sa.born = slots->born; sa.head = ws.head; sa.node = ws.node;
+        sa.K = K; sa.H = H; sa.W = W; sa.cell = std::max(ws.seed.cell, 1); sa.gw = ws.seed.gw;
+        hipLaunchKernelGGL(k_seed_link, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, s, sa);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_free_list, dim3(1), dim3(256), 0, s, slots->visible, K, ws.free, ws.nfree);
+        HIP_TRY(hipGetLastError());
+        c.head = ws.head; c.node = ws.node; c.cell = sa.cell; c.gw = ws.seed.gw; c.gh = ws.seed.gh;
+        c.md2 = a.md2;
+        a.free = ws.free; a.nfree = ws.nfree; a.qt = slots->qt; a.born = slots->born; a.t = slots->t;
+    }
+    const dim3 cgrid((unsigned)((W + 63) / 64), (unsigned)std::min((H + 3) / 4, 65535), fz);
+    with_bool(ws.head != nullptr, [&](auto SEEDS) { hipLaunchKernelGGL(k_corner_cand<decltype(SEEDS)::value>, cgrid, dim3(256), 0, s, c); });
+    HIP_TRY(hipGetLastError());
+    with_bool(slots != nullptr, [&](auto SLOTS) {
+        hipLaunchKernelGGL(k_corner_select<decltype(SLOTS)::value>, dim3(fz), dim3(256), 0, s, a);
+    });
     HIP_TRY(hipGetLastError());
     return OFLK_OK;
 }
@@ -2540,94 +2584,16 @@ int good_features_host(const PIXELS *frames, int F, int H, int W, int window_siz
     char *d_ws;
     int *d_cnt;
     float *d_xy, *d_sc;
-    if ((rc = call.upload(&d_f, frames, n)) || (rc = call.alloc(&d_ws, feat_geom(F, H, W, md).bytes)) ||
+    if ((rc = call.upload(&d_f, frames, n)) || (rc = call.alloc(&d_ws, feat_ws(nullptr, F, H, W, md, 0).bytes)) ||
         (rc = call.alloc(&d_cnt, (size_t)F)) || (rc = call.alloc(&d_xy, 2 * nk)) || (rc = call.alloc(&d_sc, nk)))
         return rc;
-    if ((rc = good_features_launch(d_f, sizeof(PIXELS) == 1, F, H, W, window_size, q, md, K, d_ws, d_cnt, d_xy, d_sc, nullptr)))
+    if ((rc = detect_launch(d_f, sizeof(PIXELS) == 1, F, H, W, window_size, q, md, K, feat_ws(d_ws, F, H, W, md, 0), d_cnt, d_xy,
+                            d_sc, nullptr, nullptr)))
         return rc;
     if ((rc = call.to_host(count, d_cnt, (size_t)F)) || (rc = call.to_host(xy, d_xy, 2 * nk)) ||
         (rc = call.to_host(score, d_sc, nk)))
         return rc;
     return call.sync();
-}
-
-// The workspace of oflk_replenish_features: feat_geom of one frame, then the seed grid's heads [sgh][sgw] (cells of side
-// ceil(md), at most the frame; md = 0: none), its nodes [K], the free list [K] and its length [1]
-struct ReplGeom {
-    FeatGeom f;
-    int cell = 0, gw = 0, gh = 0;
-    size_t off_head = 0, off_node = 0, off_free = 0, off_nfree = 0, bytes = 0;
-};
-
-ReplGeom repl_geom(int H, int W, float md, int K)
-{
-    ReplGeom g;
-    g.f = feat_geom(1, H, W, md);
-    if (md > 0.0f) {
-        g.cell = (int)std::min<double>(std::ceil((double)md), (double)std::max(H, W));
-        g.gw = (W + g.cell - 1) / g.cell;
-        g.gh = (H + g.cell - 1) / g.cell;
-    }
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    g.off_head = g.f.bytes;
-    g.off_node = g.off_head + al((size_t)g.gw * g.gh * sizeof(int));
-    g.off_free = g.off_node + al((size_t)K * sizeof(int2));
-    g.off_nfree = g.off_free + al((size_t)K * sizeof(int));
-    g.bytes = g.off_nfree + 256;
-    return g;
-}
-
-// One detection of the replenish statement on stream s, no host round trip: the slots' state (xy, visible) of frame t in,
-// the new points into the free slots of qt / qxy, born [K] and detected [1] out.  The arguments are checked.
-int replenish_launch(const void *frame, bool u8, int H, int W, int window_size, float q, float md, int K, int t, const float *xy,
-                     const unsigned char *visible, void *workspace, int *qt, float *qxy, unsigned char *born, int *detected,
-                     hipStream_t s)
-{
-    const ReplGeom g = repl_geom(H, W, md, K);
-    char *w = static_cast<char *>(workspace);
-    unsigned *fmax = reinterpret_cast<unsigned *>(w), *ncand = reinterpret_cast<unsigned *>(w + g.f.off_cnt);
-    float *S = reinterpret_cast<float *>(w + g.f.off_s);
-    unsigned long long *keys = reinterpret_cast<unsigned long long *>(w + g.f.off_keys);
-    int *head = g.cell ? reinterpret_cast<int *>(w + g.off_head) : nullptr;
-    int2 *node = reinterpret_cast<int2 *>(w + g.off_node);
-    int *free_list = reinterpret_cast<int *>(w + g.off_free), *nfree = reinterpret_cast<int *>(w + g.off_nfree);
-    hipLaunchKernelGGL(k_corner_init, dim3(1), dim3(256), 0, s, fmax, ncand, 1);
-    HIP_TRY(hipGetLastError());
-    int rc = corner_score_launch(frame, u8, 1, H, W, window_size, S, fmax, s);
-    if (rc) return rc;
-    if (head) {
-        const int cells = g.gw * g.gh;
-        hipLaunchKernelGGL(k_seed_clear, dim3((unsigned)std::min((cells + 255) / 256, 1024)), dim3(256), 0, s, head, cells);
-        HIP_TRY(hipGetLastError());
-    }
-    SeedArgs sa{};
-    sa.xy = xy; sa.visible = visible; sa.born = born; sa.head = head; sa.node = node;
-    sa.K = K; sa.H = H; sa.W = W; sa.cell = std::max(g.cell, 1); sa.gw = g.gw;
-    hipLaunchKernelGGL(k_seed_link, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, s, sa);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_free_list, dim3(1), dim3(256), 0, s, visible, K, free_list, nfree);
-    HIP_TRY(hipGetLastError());
-    CandArgs c{};
-    c.score = S; c.fmax = fmax; c.keys = keys; c.ncand = ncand;
-    c.F = 1; c.H = H; c.W = W;
-    c.q = (double)q;
-    c.head = head; c.node = node; c.cell = std::max(g.cell, 1); c.gw = g.gw; c.gh = g.gh;
-    c.md2 = (double)md * (double)md;
-    const dim3 cgrid((unsigned)((W + 63) / 64), (unsigned)std::min((H + 3) / 4, 65535), 1);
-    with_bool(head != nullptr, [&](auto SEEDS) { hipLaunchKernelGGL(k_corner_cand<decltype(SEEDS)::value>, cgrid, dim3(256), 0, s, c); });
-    HIP_TRY(hipGetLastError());
-    SelectArgs a{};
-    a.keys = keys; a.ncand = ncand;
-    a.grid = g.f.cell ? reinterpret_cast<int *>(w + g.f.off_grid) : nullptr;
-    a.count = detected; a.xy = qxy; a.score = nullptr;
-    a.F = 1; a.H = H; a.W = W; a.K = K;
-    a.cell = std::max(g.f.cell, 1); a.gw = g.f.gw; a.gh = g.f.gh;
-    a.md2 = (double)md * (double)md;
-    a.use_grid = g.f.cell != 0;
-    a.free = free_list; a.nfree = nfree; a.qt = qt; a.born = born; a.t = t;
-    hipLaunchKernelGGL(k_corner_select<true>, dim3(1), dim3(256), 0, s, a);
-    HIP_TRY(hipGetLastError());
-    return OFLK_OK;
 }
 
 // the arguments of one detection, host or device pointers
@@ -2656,14 +2622,15 @@ int replenish_host(const PIXELS *frame, int H, int W, int window_size, float q, 
     float *d_xy, *d_qxy;
     unsigned char *d_vis, *d_born;
     int *d_qt, *d_det;
-    if ((rc = call.upload(&d_f, frame, (size_t)H * W)) || (rc = call.alloc(&d_ws, repl_geom(H, W, md, K).bytes)) ||
+    if ((rc = call.upload(&d_f, frame, (size_t)H * W)) || (rc = call.alloc(&d_ws, feat_ws(nullptr, 1, H, W, md, K).bytes)) ||
         (rc = call.upload(&d_xy, xy, 2 * row)) || (rc = call.upload(&d_vis, visible, row)) ||
         (rc = call.upload(&d_qt, const_cast<const int *>(qt), row)) ||
         (rc = call.upload(&d_qxy, const_cast<const float *>(qxy), 2 * row)) || (rc = call.alloc(&d_born, row)) ||
         (rc = call.alloc(&d_det, 1)))
         return rc;
-    if ((rc = replenish_launch(d_f, sizeof(PIXELS) == 1, H, W, window_size, q, md, K, t, d_xy, d_vis, d_ws, d_qt, d_qxy, d_born,
-                               d_det, nullptr)))
+    const SlotSide slots{d_xy, d_vis, d_qt, d_born, d_det, t};
+    if ((rc = detect_launch(d_f, sizeof(PIXELS) == 1, 1, H, W, window_size, q, md, K, feat_ws(d_ws, 1, H, W, md, K), nullptr, d_qxy,
+                            nullptr, &slots, nullptr)))
         return rc;
     if ((rc = call.to_host(qt, d_qt, row)) || (rc = call.to_host(qxy, d_qxy, 2 * row)) || (rc = call.to_host(born, d_born, row)) ||
         (rc = call.to_host(detected, d_det, 1)))
@@ -2698,7 +2665,7 @@ OFLK_API int oflk_good_features_workspace(int F, int H, int W, int window_size, 
     if (F < 1) return fail(OFLK_ERR_INVALID, "F must be >= 1 (got %d)", F);
     int rc = check_hw(bytes, bytes, H, W);
     if (rc || (rc = check_select(0.0f, min_distance, max_corners)) || (rc = check_corner_window(window_size))) return rc;
-    *bytes = feat_geom(F, H, W, min_distance).bytes;
+    *bytes = feat_ws(nullptr, F, H, W, min_distance, 0).bytes;
     return OFLK_OK;
 }
 
@@ -2710,13 +2677,13 @@ OFLK_API int oflk_good_features(const void *d_frames, int u8, int F, int H, int 
     if (rc) return rc;
     if (!d_workspace || !d_count || !d_xy || !d_score) return fail(OFLK_ERR_INVALID, "NULL workspace or output argument");
     if ((rc = check_select(quality_level, min_distance, max_corners)) || (rc = check_corner_window(window_size))) return rc;
-    const size_t need = feat_geom(F, H, W, min_distance).bytes;
+    const size_t need = feat_ws(nullptr, F, H, W, min_distance, 0).bytes;
     if (workspace_bytes < need)
         return fail(OFLK_ERR_INVALID, "workspace of %zu bytes, %zu needed (oflk_good_features_workspace)", workspace_bytes, need);
     if (reinterpret_cast<uintptr_t>(d_workspace) % 256 != 0 || reinterpret_cast<uintptr_t>(d_xy) % 8 != 0)
         return fail(OFLK_ERR_INVALID, "d_workspace must be 256-byte aligned and d_xy 8-byte aligned");
-    return good_features_launch(d_frames, u8 != 0, F, H, W, window_size, quality_level, min_distance, max_corners, d_workspace,
-                                d_count, d_xy, d_score, (hipStream_t)stream);
+    return detect_launch(d_frames, u8 != 0, F, H, W, window_size, quality_level, min_distance, max_corners,
+                         feat_ws(d_workspace, F, H, W, min_distance, 0), d_count, d_xy, d_score, nullptr, (hipStream_t)stream);
 }
 
 OFLK_API int oflk_good_features_host(const float *frames, int F, int H, int W, int window_size, float quality_level,
@@ -2737,7 +2704,7 @@ OFLK_API int oflk_replenish_features_workspace(int H, int W, int window_size, fl
     if (!bytes) return fail(OFLK_ERR_INVALID, "NULL bytes");
     int rc = check_hw(bytes, bytes, H, W);
     if (rc || (rc = check_select(0.0f, min_distance, max_corners)) || (rc = check_corner_window(window_size))) return rc;
-    *bytes = repl_geom(H, W, min_distance, max_corners).bytes;
+    *bytes = feat_ws(nullptr, 1, H, W, min_distance, max_corners).bytes;
     return OFLK_OK;
 }
 
@@ -2750,14 +2717,16 @@ OFLK_API int oflk_replenish_features(const void *d_frame, int u8, int H, int W, 
                              d_born, d_detected);
     if (rc) return rc;
     if (!d_workspace) return fail(OFLK_ERR_INVALID, "NULL workspace");
-    const size_t need = repl_geom(H, W, min_distance, max_corners).bytes;
+    const size_t need = feat_ws(nullptr, 1, H, W, min_distance, max_corners).bytes;
     if (workspace_bytes < need)
         return fail(OFLK_ERR_INVALID, "workspace of %zu bytes, %zu needed (oflk_replenish_features_workspace)", workspace_bytes,
                     need);
     if (reinterpret_cast<uintptr_t>(d_workspace) % 256 != 0 || reinterpret_cast<uintptr_t>(d_qxy) % 8 != 0)
         return fail(OFLK_ERR_INVALID, "d_workspace must be 256-byte aligned and d_qxy 8-byte aligned");
-    return replenish_launch(d_frame, u8 != 0, H, W, window_size, quality_level, min_distance, max_corners, t, d_xy, d_visible,
-                            d_workspace, d_qt, d_qxy, d_born, d_detected, (hipStream_t)stream);
+    const SlotSide slots{d_xy, d_visible, d_qt, d_born, d_detected, t};
+    return detect_launch(d_frame, u8 != 0, 1, H, W, window_size, quality_level, min_distance, max_corners,
+                         feat_ws(d_workspace, 1, H, W, min_distance, max_corners), nullptr, d_qxy, nullptr, &slots,
+                         (hipStream_t)stream);
 }
 
 OFLK_API int oflk_replenish_features_host(const float *frame, int H, int W, int window_size, float quality_level,
@@ -2812,126 +2781,158 @@ int track_launch(const float *uf, const float *vf, const float *ub, const float 
     return OFLK_OK;
 }
 
-// Tracks of a whole sequence, host pointers: run_sequence_bidir's chunks, then one track launch per chunk that continues
-// from the previous chunk's last row.  Only the queries go up and only the tracks come down.  With `det`
-// (oflk_pyramidal_sequence_klt) the queries are born on the device instead: good_features_launch on frame 0 of chunk 0's
-// frames writes its xy straight into the query buffer (N = K; the NaN rows are never-visible tracks), and count, xy and
-// score come down with chunk 0.
-// With det->every >= 1 (oflk_pyramidal_sequence_klt_replenish) the K queries are slots instead: every slot starts dead
-// (k_slots_init), a chunk's pairs are walked in segments cut at the detection frames (t % every == 0), and before the
-// segment that begins at such a frame s replenish_launch on frame s fills free slots (qt = s, qxy) from the slots' row
-// of s; the segment's launch (t0 = s) then starts those slots on its row 0 and continues the others from it.  That
-// launch makes the row of s final, so a chunk that begins at a detection frame sends its row 0 again, born with it.
-struct Detect {
-    float q, md;
-    int K;
-    int *count;
-    float *xy, *score;
-    int every = 0;
-    unsigned char *born = nullptr;
-    int *detected = nullptr;
+struct TrackRows {   // the device side of every sequence track call: the queries and one chunk's rows
+    int *qt = nullptr;                     // [N]; NULL: every query starts on frame 0
+    float *qxy = nullptr, *tr = nullptr;   // [N][2] and [C+1][N][2]
+    unsigned char *vis = nullptr;          // [C+1][N]
 };
 
-template <class PIXELS>
+// Tracks of a whole sequence, host pointers: run_sequence_bidir's chunks; only the tracks come down.  The calls differ in
+// the frames on which queries come into existence, the detection frames: the multiples of `every` (0: none).  A chunk's
+// pairs are walked in segments cut there.  Before the segment that begins at such a frame s, detect(call, R, s, r, frame)
+// puts new queries (qt, qxy) into R from row r of the chunk; the segment's launch (t0 = s) starts them on its row 0 and
+// continues the others.  A call's other parts: checks(), setup(call, R, C), begin(nb) ahead of a chunk's segments and
+// extras(call, b0, nb, r0) after its rows r0 .. nb have gone down.
+template <class PIXELS, class Checks, class Setup, class Begin, class Detect, class Extras>
 int run_sequence_tracks(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
-                        float beta, const int *qt, const float *qxy, int N, float *tracks, unsigned char *visible,
-                        const Detect *det = nullptr)
+                        float beta, int N, float *tracks, unsigned char *visible, int every, Checks checks, Setup setup,
+                        Begin begin, Detect detect, Extras extras)
 {
+    const size_t row = (size_t)N, plane = (size_t)H * W;
     int C = 0;   // pairs per chunk (setup)
-    float *d_qxy = nullptr, *d_tr = nullptr, *d_sc = nullptr;
-    int *d_qt = nullptr, *d_cnt = nullptr, *d_det = nullptr;
-    unsigned char *d_vis = nullptr, *d_born = nullptr;
-    char *d_ws = nullptr;
-    const bool slots = det && det->born;   // the replenish call
-    auto checks = [&]() -> int {
-        int rc = check_alpha_beta(alpha, beta);
-        if (rc) return rc;
-        if (!det) return check_queries(qt, T, qxy, N, tracks, visible);
-        if (slots) {
-            if (!det->detected || !tracks || !visible) return fail(OFLK_ERR_INVALID, "NULL output argument");
-            if (det->every < 1) return fail(OFLK_ERR_INVALID, "detect_every must be >= 1 (got %d)", det->every);
-        } else if (!det->count || !det->xy || !det->score || !tracks || !visible) {
-            return fail(OFLK_ERR_INVALID, "NULL output argument");
-        }
-        if ((rc = check_select(det->q, det->md, det->K)) || (rc = check_corner_window(window_size))) return rc;
-        N = det->K;
-        return OFLK_OK;
-    };
-    auto setup = [&](HostCall &call, int pairs) -> int {
-        const size_t row = (size_t)N;
+    TrackRows R;
+    auto detection_frame = [&](int s) { return every && s % every == 0; };
+    auto all_checks = [&]() -> int { const int rc = check_alpha_beta(alpha, beta); return rc ? rc : checks(); };
+    auto all_setup = [&](HostCall &call, int pairs) -> int {
         int rc;
         C = pairs;
-        if ((rc = det ? call.alloc(&d_qxy, 2 * row) : call.upload(&d_qxy, qxy, 2 * row)) ||
-            (qt && (rc = call.upload(&d_qt, qt, row))) || (rc = call.alloc(&d_tr, (size_t)(C + 1) * 2 * row)) ||
-            (rc = call.alloc(&d_vis, (size_t)(C + 1) * row)))
-            return rc;
-        if (slots) {
-            if ((rc = call.alloc(&d_ws, repl_geom(H, W, det->md, det->K).bytes)) || (rc = call.alloc(&d_qt, row)) ||
-                (rc = call.alloc(&d_born, (size_t)(C + 1) * row)) || (rc = call.alloc(&d_det, (size_t)T)))
-                return rc;
-            hipLaunchKernelGGL(k_slots_init, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, d_qt,
-                               reinterpret_cast<float2 *>(d_qxy), reinterpret_cast<float2 *>(d_tr), d_vis, N);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemsetAsync(d_det, 0, (size_t)T * sizeof(int), nullptr));
-            return OFLK_OK;
-        }
-        if (det && ((rc = call.alloc(&d_ws, feat_geom(1, H, W, det->md).bytes)) || (rc = call.alloc(&d_cnt, 1)) ||
-                    (rc = call.alloc(&d_sc, row))))
-            return rc;
-        return OFLK_OK;
+        if ((rc = call.alloc(&R.tr, (size_t)(C + 1) * 2 * row)) || (rc = call.alloc(&R.vis, (size_t)(C + 1) * row))) return rc;
+        return setup(call, R, C);
     };
     auto chunk = [&](HostCall &call, int b0, int nb, const PIXELS *d_frames, float *const *d) -> int {
-        const size_t row = (size_t)N;
         int rc;
         if (b0 > 0) {   // row 0 of this chunk is the previous (full, C-pair) chunk's last row
-            HIP_TRY(hipMemcpyAsync(d_tr, d_tr + (size_t)C * 2 * row, 2 * row * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
-            HIP_TRY(hipMemcpyAsync(d_vis, d_vis + (size_t)C * row, row, hipMemcpyDeviceToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(R.tr, R.tr + (size_t)C * 2 * row, 2 * row * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(R.vis, R.vis + (size_t)C * row, row, hipMemcpyDeviceToDevice, nullptr));
         }
-        if (slots) {
-            const size_t plane = (size_t)H * W;
-            const int D = det->every;
-            HIP_TRY(hipMemsetAsync(d_born, 0, (size_t)(nb + 1) * row, nullptr));
-            for (int s0 = b0; s0 < b0 + nb;) {   // segments [s0, e) of pairs; s0 <= T-2
-                const int e = (int)std::min<long long>(b0 + nb, ((long long)s0 / D + 1) * D), r = s0 - b0;
-                if (s0 % D == 0 &&
-                    (rc = replenish_launch(d_frames + (size_t)r * plane, sizeof(PIXELS) == 1, H, W, window_size, det->q, det->md,
-                                           det->K, s0, d_tr + (size_t)r * 2 * row, d_vis + (size_t)r * row, d_ws, d_qt, d_qxy,
-                                           d_born + (size_t)r * row, d_det + s0, nullptr)))
-                    return rc;
-                if ((rc = track_launch(d[0] + (size_t)r * plane, d[1] + (size_t)r * plane, d[2] + (size_t)r * plane,
-                                       d[3] + (size_t)r * plane, e - s0, H, W, alpha, beta, s0, d_qt, d_qxy, N,
-                                       d_tr + (size_t)r * 2 * row, d_vis + (size_t)r * row, nullptr)))
-                    return rc;
-                s0 = e;
-            }
-            const int r0 = b0 > 0 && b0 % D != 0 ? 1 : 0;   // row 0 of a chunk that begins with a detection goes again
-            const size_t nr = (size_t)(nb + 1 - r0);
-            if ((rc = call.to_host(tracks + (size_t)(b0 + r0) * 2 * row, d_tr + (size_t)r0 * 2 * row, nr * 2 * row)) ||
-                (rc = call.to_host(visible + (size_t)(b0 + r0) * row, d_vis + (size_t)r0 * row, nr * row)) ||
-                (rc = call.to_host(det->born + (size_t)(b0 + r0) * row, d_born + (size_t)r0 * row, nr * row)))
+        if ((rc = begin(nb))) return rc;
+        for (int s0 = b0; s0 < b0 + nb;) {   // segments [s0, e) of pairs; s0 <= T-2
+            const int e = every ? (int)std::min<long long>(b0 + nb, ((long long)s0 / every + 1) * every) : b0 + nb, r = s0 - b0;
+            const size_t fo = (size_t)r * plane;
+            if (detection_frame(s0) && (rc = detect(call, R, s0, r, d_frames + fo))) return rc;
+            if ((rc = track_launch(d[0] + fo, d[1] + fo, d[2] + fo, d[3] + fo, e - s0, H, W, alpha, beta, s0, R.qt, R.qxy, N,
+                                   R.tr + (size_t)r * 2 * row, R.vis + (size_t)r * row, nullptr)))
                 return rc;
-            if (b0 + nb == T - 1 && (rc = call.to_host(det->detected, d_det, (size_t)T))) return rc;
-            return OFLK_OK;
+            s0 = e;
         }
-        if (det && b0 == 0) {   // frame 0 is d_frames[0]: its features become the queries
-            if ((rc = good_features_launch(d_frames, sizeof(PIXELS) == 1, 1, H, W, window_size, det->q, det->md, det->K, d_ws, d_cnt,
-                                           d_qxy, d_sc, nullptr)))
-                return rc;
-            if ((rc = call.to_host(det->count, d_cnt, 1)) || (rc = call.to_host(det->xy, d_qxy, 2 * row)) ||
-                (rc = call.to_host(det->score, d_sc, row)))
-                return rc;
-        }
-        if ((rc = track_launch(d[0], d[1], d[2], d[3], nb, H, W, alpha, beta, b0, d_qt, d_qxy, N, d_tr, d_vis, nullptr))) return rc;
-        const int r0 = b0 > 0 ? 1 : 0;   // row 0 of a later chunk is already on the host
+        // row 0 of a later chunk is already on the host, unless the chunk begins at a detection frame: that segment's
+        // launch is what makes the row final, so it goes again
+        const int r0 = b0 > 0 && !detection_frame(b0) ? 1 : 0;
         const size_t nr = (size_t)(nb + 1 - r0);
-        if ((rc = call.to_host(tracks + (size_t)(b0 + r0) * 2 * row, d_tr + (size_t)r0 * 2 * row, nr * 2 * row)) ||
-            (rc = call.to_host(visible + (size_t)(b0 + r0) * row, d_vis + (size_t)r0 * row, nr * row)))
+        if ((rc = call.to_host(tracks + (size_t)(b0 + r0) * 2 * row, R.tr + (size_t)r0 * 2 * row, nr * 2 * row)) ||
+            (rc = call.to_host(visible + (size_t)(b0 + r0) * row, R.vis + (size_t)r0 * row, nr * row)))
+            return rc;
+        return extras(call, b0, nb, r0);
+    };
+    return run_sequence_bidir<PIXELS>(frames, T, H, W, levels, window_size, iters, all_checks, all_setup, chunk);
+}
+
+constexpr auto no_part = [](auto &&...) -> int { return OFLK_OK; };   // a part that a call does not have
+
+// oflk_pyramidal_sequence_tracks: no detection frame; only the queries go up
+template <class PIXELS>
+int sequence_tracks(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
+                    const int *qt, const float *qxy, int N, float *tracks, unsigned char *visible)
+{
+    auto checks = [&]() -> int { return check_queries(qt, T, qxy, N, tracks, visible); };
+    auto setup = [&](HostCall &call, TrackRows &R, int) -> int {
+        const int rc = call.upload(&R.qxy, qxy, 2 * (size_t)N);
+        return rc || !qt ? rc : call.upload(&R.qt, qt, (size_t)N);
+    };
+    return run_sequence_tracks<PIXELS>(frames, T, H, W, levels, window_size, iters, alpha, beta, N, tracks, visible, 0, checks,
+                                       setup, no_part, no_part, no_part);
+}
+
+// oflk_pyramidal_sequence_klt: frame 0, the only multiple of T, is the detection frame.  Its xy go straight into the query
+// buffer (N = K; the NaN rows are never-visible tracks), and count, xy and score come down with chunk 0.
+template <class PIXELS>
+int sequence_klt(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
+                 float q, float md, int K, int *count, float *xy, float *score, float *tracks, unsigned char *visible)
+{
+    const size_t row = (size_t)K;
+    char *d_ws = nullptr;
+    int *d_cnt = nullptr;
+    float *d_sc = nullptr;
+    auto checks = [&]() -> int {
+        if (!count || !xy || !score || !tracks || !visible) return fail(OFLK_ERR_INVALID, "NULL output argument");
+        const int rc = check_select(q, md, K);
+        return rc ? rc : check_corner_window(window_size);
+    };
+    auto setup = [&](HostCall &call, TrackRows &R, int) -> int {
+        int rc;
+        if ((rc = call.alloc(&R.qxy, 2 * row)) || (rc = call.alloc(&d_ws, feat_ws(nullptr, 1, H, W, md, 0).bytes)) ||
+            (rc = call.alloc(&d_cnt, 1)) || (rc = call.alloc(&d_sc, row)))
             return rc;
         return OFLK_OK;
     };
-    return run_sequence_bidir<PIXELS>(frames, T, H, W, levels, window_size, iters, checks, setup, chunk);
+    auto detect = [&](HostCall &call, TrackRows &R, int, int, const PIXELS *d_frame) -> int {
+        int rc = detect_launch(d_frame, sizeof(PIXELS) == 1, 1, H, W, window_size, q, md, K, feat_ws(d_ws, 1, H, W, md, 0), d_cnt,
+                               R.qxy, d_sc, nullptr, nullptr);
+        if (rc || (rc = call.to_host(count, d_cnt, 1)) || (rc = call.to_host(xy, R.qxy, 2 * row)) ||
+            (rc = call.to_host(score, d_sc, row)))
+            return rc;
+        return OFLK_OK;
+    };
+    return run_sequence_tracks<PIXELS>(frames, T, H, W, levels, window_size, iters, alpha, beta, K, tracks, visible, T, checks,
+                                       setup, no_part, detect, no_part);
+}
+
+// oflk_pyramidal_sequence_klt_replenish: the K queries are slots, every one dead at first (k_slots_init).  On every
+// detect_every-th frame s the detection fills free slots (qt = s, qxy) from the slots' row of s, born with them.
+template <class PIXELS>
+int sequence_klt_replenish(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
+                           float beta, float q, float md, int K, int detect_every, float *tracks, unsigned char *visible,
+                           unsigned char *born, int *detected)
+{
+    if (!born) return fail(OFLK_ERR_INVALID, "NULL output argument");
+    const size_t row = (size_t)K;
+    char *d_ws = nullptr;
+    unsigned char *d_born = nullptr;
+    int *d_det = nullptr;
+    auto checks = [&]() -> int {
+        if (!detected || !tracks || !visible) return fail(OFLK_ERR_INVALID, "NULL output argument");
+        if (detect_every < 1) return fail(OFLK_ERR_INVALID, "detect_every must be >= 1 (got %d)", detect_every);
+        const int rc = check_select(q, md, K);
+        return rc ? rc : check_corner_window(window_size);
+    };
+    auto setup = [&](HostCall &call, TrackRows &R, int C) -> int {
+        int rc;
+        if ((rc = call.alloc(&R.qxy, 2 * row)) || (rc = call.alloc(&d_ws, feat_ws(nullptr, 1, H, W, md, K).bytes)) ||
+            (rc = call.alloc(&R.qt, row)) || (rc = call.alloc(&d_born, (size_t)(C + 1) * row)) ||
+            (rc = call.alloc(&d_det, (size_t)T)))
+            return rc;
+        hipLaunchKernelGGL(k_slots_init, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, nullptr, R.qt,
+                           reinterpret_cast<float2 *>(R.qxy), reinterpret_cast<float2 *>(R.tr), R.vis, K);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemsetAsync(d_det, 0, (size_t)T * sizeof(int), nullptr));
+        return OFLK_OK;
+    };
+    auto begin = [&](int nb) -> int { HIP_TRY(hipMemsetAsync(d_born, 0, (size_t)(nb + 1) * row, nullptr)); return OFLK_OK; };
+    auto detect = [&](HostCall &, TrackRows &R, int s, int r, const PIXELS *d_frame) -> int {
+        const SlotSide slots{R.tr + (size_t)r * 2 * row, R.vis + (size_t)r * row, R.qt, d_born + (size_t)r * row, d_det + s, s};
+        return detect_launch(d_frame, sizeof(PIXELS) == 1, 1, H, W, window_size, q, md, K, feat_ws(d_ws, 1, H, W, md, K), nullptr,
+                             R.qxy, nullptr, &slots, nullptr);
+    };
+    auto extras = [&](HostCall &call, int b0, int nb, int r0) -> int {
+        int rc = call.to_host(born + (size_t)(b0 + r0) * row, d_born + (size_t)r0 * row, (size_t)(nb + 1 - r0) * row);
+        if (!rc && b0 + nb == T - 1) rc = call.to_host(detected, d_det, (size_t)T);
+        return rc;
+    };
+    return run_sequence_tracks<PIXELS>(frames, T, H, W, levels, window_size, iters, alpha, beta, K, tracks, visible, detect_every,
+                                       checks, setup, begin, detect, extras);
 }
 }  // namespace
+
 
 OFLK_API int oflk_track_points(const float *d_uf, const float *d_vf, const float *d_ub, const float *d_vb, int B, int H, int W,
                                float alpha, float beta, int t0, const int *d_qt, const float *d_qxy, int N, float *d_tracks,
@@ -2971,24 +2972,22 @@ OFLK_API int oflk_pyramidal_sequence_tracks(const float *frames, int T, int H, i
                                             float alpha, float beta, const int *qt, const float *qxy, int N, float *tracks,
                                             unsigned char *visible)
 {
-    return run_sequence_tracks<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, qt, qxy, N, tracks, visible);
+    return sequence_tracks<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, qt, qxy, N, tracks, visible);
 }
 
 OFLK_API int oflk_pyramidal_sequence_tracks_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size,
                                                int iters, float alpha, float beta, const int *qt, const float *qxy, int N,
                                                float *tracks, unsigned char *visible)
 {
-    return run_sequence_tracks<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, qt, qxy, N, tracks,
-                                              visible);
+    return sequence_tracks<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, qt, qxy, N, tracks, visible);
 }
 
 OFLK_API int oflk_pyramidal_sequence_klt(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
                                          float alpha, float beta, float quality_level, float min_distance, int max_corners,
                                          int *count, float *xy, float *score, float *tracks, unsigned char *visible)
 {
-    const Detect det{quality_level, min_distance, max_corners, count, xy, score};
-    return run_sequence_tracks<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, nullptr, nullptr, 0, tracks,
-                                      visible, &det);
+    return sequence_klt<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, quality_level, min_distance, max_corners,
+                               count, xy, score, tracks, visible);
 }
 
 OFLK_API int oflk_pyramidal_sequence_klt_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size,
@@ -2996,9 +2995,8 @@ OFLK_API int oflk_pyramidal_sequence_klt_u8(const unsigned char *frames, int T, 
                                             int max_corners, int *count, float *xy, float *score, float *tracks,
                                             unsigned char *visible)
 {
-    const Detect det{quality_level, min_distance, max_corners, count, xy, score};
-    return run_sequence_tracks<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, nullptr, nullptr, 0,
-                                              tracks, visible, &det);
+    return sequence_klt<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, quality_level, min_distance,
+                                       max_corners, count, xy, score, tracks, visible);
 }
 
 OFLK_API int oflk_pyramidal_sequence_klt_replenish(const float *frames, int T, int H, int W, int levels, int window_size,
@@ -3006,10 +3004,8 @@ OFLK_API int oflk_pyramidal_sequence_klt_replenish(const float *frames, int T, i
                                                    int max_corners, int detect_every, float *tracks, unsigned char *visible,
                                                    unsigned char *born, int *detected)
 {
-    if (!born) return fail(OFLK_ERR_INVALID, "NULL output argument");
-    const Detect det{quality_level, min_distance, max_corners, nullptr, nullptr, nullptr, detect_every, born, detected};
-    return run_sequence_tracks<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, nullptr, nullptr, 0, tracks,
-                                      visible, &det);
+    return sequence_klt_replenish<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, quality_level, min_distance,
+                                         max_corners, detect_every, tracks, visible, born, detected);
 }
 
 OFLK_API int oflk_pyramidal_sequence_klt_replenish_u8(const unsigned char *frames, int T, int H, int W, int levels,
@@ -3017,10 +3013,8 @@ OFLK_API int oflk_pyramidal_sequence_klt_replenish_u8(const unsigned char *frame
                                                       float min_distance, int max_corners, int detect_every, float *tracks,
                                                       unsigned char *visible, unsigned char *born, int *detected)
 {
-    if (!born) return fail(OFLK_ERR_INVALID, "NULL output argument");
-    const Detect det{quality_level, min_distance, max_corners, nullptr, nullptr, nullptr, detect_every, born, detected};
-    return run_sequence_tracks<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, nullptr, nullptr, 0,
-                                              tracks, visible, &det);
+    return sequence_klt_replenish<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, quality_level,
+                                                 min_distance, max_corners, detect_every, tracks, visible, born, detected);
 }
 
 OFLK_API int oflk_pyramidal_last_level_flow(int B, int H, int W, int levels, int window_size, int iters, int level,

@@ -243,6 +243,57 @@ int oflk_track_points_host(const float *uf, const float *vf, const float *ub, co
                            float alpha, float beta, const int *qt, const float *qxy, int N, float *tracks,
                            unsigned char *visible);
 
+/* ---- sparse pyramidal LK: points in, points out, no dense flow --------------------------------------------------------- */
+/* The statement (tests/sparse_model.py).  The shape of calcOpticalFlowPyrLK: points in, next points + status + error out,
+ * at a cost proportional to N * window^2 * levels * iterations, not to H*W.  Pyramids: build_gaussian_pyramid of each frame,
+ * level 0 the coarsest, level L-1 the frame itself, sizes (h_l, w_l) = oflk_pyramid_level_dims at scale 0.5; exact
+ * arithmetic always (oflk_set_host_arithmetic and oflk_plan_set_arithmetic do not apply).  sample(img, x, y) is the
+ * reference's warp_image at one float64 point (map_coordinates, order 1, cval 0; float32 result).  Window w = 2h+1, odd,
+ * 3 <= w <= 11; K = iters >= 1.  float32 except where stated, each operation rounded on its own.
+ *   step(A, B, x, y), a float32 point of frame A inside [0, W-1] x [0, H-1]:
+ *     g = (0, 0)
+ *     for l = 0 .. L-1:
+ *       l > 0:  g = (g.x * f32(w_l / w_{l-1}), g.y * f32(h_l / h_{l-1}))          upsample_flow's ratios (float64 quotients)
+ *       (xl, yl) = (f64(x), f64(y)) at l = L-1;  elsewhere (f64(x) * (w_l - 1) / (W - 1), f64(y) * (h_l - 1) / (H - 1)),
+ *                  float64, multiply then divide: the linspace geometry the level was resampled with
+ *       P[j][i] = sample(A_l, xl + i, yl + j),  i, j in [-(h+1), h+1]               the template, once per level
+ *       for k = 0 .. K-1:
+ *         Q[j][i] = sample(B_l, (xl + f64(g.x)) + i, (yl + f64(g.y)) + j)
+ *         (du, dv) = the centre pixel (h+1, h+1) of the reference's lucas_kanade_single_scale(P, Q, w) on the two
+ *                    (w+2) x (w+2) patches: (P + Q) / 2, Sobel / 8 in convolve2d's order, It = P - Q, five np.sum of w*w
+ *                    contiguous products, Cramer's rule where abs(det) > 1e-4 (else 0);  solved = abs(det) > 1e-4
+ *         g = g + (du, dv);  leave the level when abs(du) < f32(0.01) and abs(dv) < f32(0.01)
+ *     qx = f64(x) + f64(g.x);  qy = f64(y) + f64(g.y)
+ *     ok = solved of the finest level's last evaluated iteration, and qx, qy finite, and 0 <= qx <= W-1, 0 <= qy <= H-1
+ *          (float64, closed)
+ *     residual = f32(np.sum(abs(Pc - Qc)) / f32(w*w)):  Pc the w x w centre of the finest level's P,
+ *                Qc[j][i] = sample(B, qx + i, qy + j), i, j in [-h, h]
+ * oflk_sparse_lk: one pair, host pointers, synchronous.  pts [N][2] (x, y) in; next_pts [N][2] = (f32(qx), f32(qy)), status
+ * [N] = ok, residual [N] out (written whatever ok says: where no system was solved the point stays where it was, status 0).
+ * A point that is not finite or lies outside the frame gives status 0, a NaN position and a NaN residual.
+ * Refusals, before any device call: a pyramid level with a dimension below 2, or a window outside the odd sizes 3 ... 11:
+ * OFLK_ERR_UNSUPPORTED;  iters < 1, levels < 1, N < 1, NULL pointers: OFLK_ERR_INVALID.  Frames are finite. */
+int oflk_sparse_lk(const float *prev, const float *curr, int H, int W, int levels, int window_size, int iters,
+                   const float *pts, int N, float *next_pts, unsigned char *status, float *residual);
+int oflk_sparse_lk_u8(const unsigned char *prev, const unsigned char *curr, int H, int W, int levels, int window_size,
+                      int iters, const float *pts, int N, float *next_pts, unsigned char *status, float *residual);
+/* Sparse tracks, frames in, tracks out.  Rows, queries and NaN conventions are oflk_pyramidal_sequence_tracks'; the step
+ * of an alive point (x, y) on pair t is
+ *   (qx, qy, g, ok, r) = step(frame t, frame t+1, x, y);   if ok: (_, _, g', ok', _) = step(frame t+1, frame t, f32(qx), f32(qy))
+ *   us, vs = g;  bu, bv = g';  eu = us + bu; ev = vs + bv; e2 = eu*eu + ev*ev; m2 = (us*us + vs*vs) + (bu*bu + bv*bv)
+ *   alive = ok and ok' and e2 <= alpha*m2 + beta and r <= max_residual;   (x, y) = (f32(qx), f32(qy))
+ * The residual test is part of the tracker: a point the occluder has covered usually passes the forward-backward test (both
+ * steps lock onto the occluder's texture) and fails this one.  max_residual = +inf disables it.  Chunks of C+1 frames go up
+ * (the boundary frame shared, the last row carried, as oflk_pyramidal_sequence_tracks; with no flow on the device a chunk
+ * holds up to 64 pairs), only the rows come down; positions are float32 between steps, so results do not depend on the cut.
+ * Checks as oflk_sparse_lk and oflk_pyramidal_sequence_tracks; max_residual negative or NaN: OFLK_ERR_INVALID. */
+int oflk_pyramidal_sequence_sparse_tracks(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                          float alpha, float beta, float max_residual, const int *qt, const float *qxy, int N,
+                                          float *tracks, unsigned char *visible);
+int oflk_pyramidal_sequence_sparse_tracks_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size,
+                                             int iters, float alpha, float beta, float max_residual, const int *qt,
+                                             const float *qxy, int N, float *tracks, unsigned char *visible);
+
 /* ---- Shi-Tomasi corners and detect-then-track (KLT) -------------------------------------------------------------- */
 /* The statement (tests/feature_model.py).  One frame f [H][W], float32 or uint8 (converted exactly); window w = 2h+1, odd,
  * 3 <= w <= 11 (other windows: OFLK_ERR_UNSUPPORTED).  Score map S [H][W] float32:
@@ -329,8 +380,10 @@ void oflk_shard_range(int total, int shard, int n_shards, int *begin, int *end);
 /* ---- device-resident plan API (pipelines, bench) -------------------------- */
 typedef struct oflk_plan oflk_plan;
 
-/* Allocate the workspace (pyramids, flow ping-pong buffers, reduction scratch)
- * for B pairs of H x W on `device`.  levels = 1 and iters = 0 gives a plan that
+/* A plan for B pairs of H x W on `device`.  Creation allocates the pyramids and the reduction scratch; the flow
+ * ping-pong buffers and blur temporaries of the dense pyramidal passes are allocated by the plan's first such pass, so a
+ * plan that only serves oflk_plan_sparse_tracks never holds them (and the first pass of a kind is not capturable).
+ * oflk_plan_workspace_bytes reports what is allocated at the moment.  levels = 1 and iters = 0 gives a plan that
  * can only run oflk_plan_single_scale.
  *   window_size : 1 ... 45.  Like the reference (lucas_kanade_core.py:104, :110) a size w uses the (2*(w/2)+1)^2
  *                 window, so 4 and 5 both mean 5x5.  3x3 ... 11x11 (sizes 2 ... 11) run the tiled kernels.  Every other
@@ -429,6 +482,17 @@ int oflk_fb_consistency(const float *d_uf, const float *d_vf, const float *d_ub,
 int oflk_track_points(const float *d_uf, const float *d_vf, const float *d_ub, const float *d_vb, int B, int H, int W,
                       float alpha, float beta, int t0, const int *d_qt, const float *d_qxy, int N, float *d_tracks,
                       unsigned char *d_visible, void *stream);
+/* Sparse tracks (statement at oflk_sparse_lk) through the plan's B pairs, device pointers: d_frames [B+1][H][W] float32, or
+ * uint8 with u8 != 0, are frames t0 .. t0+B.  Builds the B+1 pyramids once, then one track launch (one wave per query,
+ * looping over the pairs).  d_qt, d_qxy, N, t0, d_tracks [B+1][N][2], d_visible [B+1][N] and the use of row 0 as
+ * oflk_track_points.  Device workspace: the plan's pyramid levels below the frame and nothing of frame size -- a plan that
+ * only serves sparse calls holds no flow slot and no blur temporary; only where a level is too small for the fused pyramid
+ * kernel the unfused chain's temporaries for B+1 images (and float32 copies of uint8 frames) are allocated, on first need.
+ * The plan's window, levels and iterations are checked as oflk_sparse_lk's.  Asynchronous, no host synchronisation; can be
+ * captured into a graph after one eager call. */
+int oflk_plan_sparse_tracks(oflk_plan *plan, const void *d_frames, int u8, float alpha, float beta, float max_residual,
+                            int t0, const int *d_qt, const float *d_qxy, int N, float *d_tracks, unsigned char *d_visible,
+                            void *stream);
 /* Shi-Tomasi scores (statement above) of F frames, device pointers: d_frames [F][H][W] float32, or uint8 with u8 != 0;
  * d_score [F][H][W].  Asynchronous; one launch. */
 int oflk_corner_score(const void *d_frames, int u8, int F, int H, int W, int window_size, float *d_score, void *stream);

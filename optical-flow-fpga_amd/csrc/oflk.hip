@@ -8,6 +8,7 @@
 // compute entry point returns OFLK_ERR_NO_DEVICE.
 #include "oflk_kernels.hpp"
 #include "oflk_stream.hpp"
+#include "oflk_sparse.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -193,8 +194,12 @@ struct oflk_plan {
     size_t ws_bytes = 0;
     // workspace
     float *pyr[OFLK_MAX_LEVELS] = {nullptr};      // l < L-1: [2B][h][w] (prev then curr); a sequence uses [B+1][h][w]
-    float *tmpA = nullptr, *tmpB = nullptr;       // blur temporaries [2B][H][W]
-    // per level one block: [slot 0..1][B][h][w] of interleaved float2 {u, v} (see LkArgs)
+    // blur temporaries [tmp_imgs][H][W] of the unfused pyramid chain, allocated on first need (ensure_tmp): 2B images by
+    // the first dense pyramidal pass; a sparse pass only where a level does not fit the fused kernel, and then B+1
+    float *tmpA = nullptr, *tmpB = nullptr;
+    size_t tmp_imgs = 0;
+    // per level one block: [slot 0..1][B][h][w] of interleaved float2 {u, v} (see LkArgs); allocated by the first dense
+    // pyramidal pass (ensure_dense_ws): a plan that only serves sparse calls never holds a flow field
     float *flow[OFLK_MAX_LEVELS] = {nullptr};
     // per-call state, one allocation, zeroed by k_call_init at the start of every call:
     //   acc[B][L][K][kAccShards][kAccStride] (u64) | iters_run[B][L] (i32) | uncertain[B][L] (i32) | log[B][L][K][2] (f32)
@@ -723,6 +728,34 @@ int dmalloc(T **p, size_t n, size_t *total)
     return OFLK_OK;
 }
 
+// blur temporaries for `nimg` images of the plan's frame size (the unfused pyramid chain)
+int ensure_tmp(oflk_plan *p, size_t nimg)
+{
+    if (p->tmp_imgs >= nimg) return OFLK_OK;
+    const size_t N = (size_t)p->H * p->W;
+    for (float **q : {&p->tmpA, &p->tmpB}) {
+        if (*q) {
+            (void)hipFree(*q);
+            p->ws_bytes -= std::max<size_t>(p->tmp_imgs * N * sizeof(float), 256);
+        }
+        *q = nullptr;
+    }
+    p->tmp_imgs = 0;
+    int rc = dmalloc(&p->tmpA, nimg * N, &p->ws_bytes);
+    if (!rc) rc = dmalloc(&p->tmpB, nimg * N, &p->ws_bytes);
+    if (!rc) p->tmp_imgs = nimg;
+    return rc;
+}
+
+// what only the dense pyramidal passes use: every level's two flow slots and blur temporaries for 2B images
+int ensure_dense_ws(oflk_plan *p)
+{
+    int rc;
+    for (int l = 0; l < p->L; l++)
+        if (!p->flow[l] && (rc = dmalloc(&p->flow[l], (size_t)2 * 2 * p->B * p->npix(l), &p->ws_bytes))) return rc;   // two interleaved slots
+    return p->L > 1 ? ensure_tmp(p, 2 * (size_t)p->B) : OFLK_OK;
+}
+
 void plan_free(oflk_plan *p)
 {
     if (!p) return;
@@ -817,16 +850,9 @@ OFLK_API int oflk_plan_create(oflk_plan **out, int device, int B, int H, int W, 
     p->B = B; p->H = H; p->W = W; p->L = levels; p->win = window_size; p->hw = hw; p->K = iters;
     std::memcpy(p->dims, dims, sizeof(int) * 2 * levels);
     rc = make_gauss(2.0, &p->gauss);  // sigma = 1/scale_factor, scale_factor = 0.5 (:24, :46)
-    const size_t N = (size_t)H * W;
-    if (!rc && levels > 1) {
-        rc = dmalloc(&p->tmpA, 2 * (size_t)B * N, &p->ws_bytes);
-        if (!rc) rc = dmalloc(&p->tmpB, 2 * (size_t)B * N, &p->ws_bytes);
-    }
-    for (int l = 0; l < levels && !rc; l++) {
-        size_t n = (size_t)dims[2 * l] * dims[2 * l + 1];
-        if (l < levels - 1) rc = dmalloc(&p->pyr[l], 2 * (size_t)B * n, &p->ws_bytes);
-        if (!rc && (iters > 0 || levels > 1)) rc = dmalloc(&p->flow[l], (size_t)2 * 2 * B * n, &p->ws_bytes);   // two interleaved slots
-    }
+    // the pyramid, the per-call state and the redo list; the dense passes' flow slots and blur temporaries come with the
+    // first pass that needs them (ensure_dense_ws), which is why a plan's first pass of a kind is eager
+    for (int l = 0; l < levels - 1 && !rc; l++) rc = dmalloc(&p->pyr[l], 2 * (size_t)B * p->npix(l), &p->ws_bytes);
     if (!rc) rc = dmalloc(&p->state, p->state_words() / 2, &p->ws_bytes);
     if (!rc && (p->hw == 2 || p->hw == 3)) {
         // redo list of the single-scale streaming kernel (LkArgs::redo): all zero between calls
@@ -987,6 +1013,58 @@ namespace {
 int iterate_levels(oflk_plan *p, hipStream_t s, const float *d_prev, const float *d_curr, size_t img_prev, size_t img_curr,
                    bool u8, float *d_u, float *d_v);
 
+// Can the fused pyramid kernel take the caller's uint8 frames?  (Always for scale 0.5 unless a level is tiny.)  Where it
+// cannot, the unfused kernels read float32: stage_u8 converts the frames once into the plan's u8_stage buffers.
+bool u8_needs_stage(const oflk_plan *p)
+{
+    const int L = p->L;
+    return L > 1 &&
+           !pyr_fused_fits(p->dims[2 * (L - 1)], p->dims[2 * (L - 1) + 1], p->dims[2 * (L - 2)], p->dims[2 * (L - 2) + 1], p->gauss);
+}
+
+// seq: the B+1 frames at d_prev all go to the first stage; otherwise prev and curr to one each
+int stage_u8(oflk_plan *p, hipStream_t s, const void *d_prev_in, const void *d_curr_in, bool seq)
+{
+    const size_t N = (size_t)p->H * p->W, n = (size_t)p->B * N;
+    size_t tot = 0;
+    int rc;
+    for (int i = 0; i < (seq ? 1 : 2); i++)
+        if (!p->u8_stage[i] && (rc = dmalloc(&p->u8_stage[i], i == 0 ? n + N : n, &tot))) return rc;
+    p->ws_bytes += tot;
+    const size_t n0 = seq ? n + N : n;
+    hipLaunchKernelGGL(k_u8_to_f32, dim3((unsigned)((n0 + 4095) / 4096)), dim3(256), 0, s, static_cast<const unsigned char *>(d_prev_in),
+                       p->u8_stage[0], n0);
+    HIP_TRY(hipGetLastError());
+    if (seq) return OFLK_OK;
+    hipLaunchKernelGGL(k_u8_to_f32, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, s, static_cast<const unsigned char *>(d_curr_in),
+                       p->u8_stage[1], n);
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+
+// The pyramids of a pass (lucas_kanade_pyramidal.py:173-174), fine -> coarse, into p->pyr: of prev and curr of every pair
+// (images 0..B-1 from d_prev, B..2B-1 from d_curr, one launch per level), or of a sequence's B+1 frames, each once (one
+// buffer at d_prev).  The finest level is the caller's frames (image.copy() at :40 is a no-op here).  `first` rides on the
+// first launch: the call's clear, and whether the frames are uint8.
+int build_pyramids(oflk_plan *p, hipStream_t s, const float *d_prev, const float *d_curr, bool seq, PyrExtra first)
+{
+    const int B = p->B, L = p->L, nimg = seq ? B + 1 : 2 * B;
+    for (int l = L - 2; l >= 0; l--) {
+        int h = p->dims[2 * (l + 1)], w = p->dims[2 * (l + 1) + 1];
+        int ho = p->dims[2 * l], wo = p->dims[2 * l + 1];
+        int rc;
+        if (l == L - 2) {
+            first.in2 = seq ? nullptr : d_curr;
+            first.nsplit = seq ? 0 : B;
+            rc = launch_pyr_down(p, p->gauss, s, d_prev, p->pyr[l], p->tmpA, p->tmpB, nimg, h, w, ho, wo, &first);
+        } else {
+            rc = launch_pyr_down(p, p->gauss, s, p->pyr[l + 1], p->pyr[l], p->tmpA, p->tmpB, nimg, h, w, ho, wo);
+        }
+        if (rc) return rc;
+    }
+    return OFLK_OK;
+}
+
 int plan_pyramidal(oflk_plan *p, const void *d_prev_in, const void *d_curr_in, bool u8, float *d_u, float *d_v,
                    hipStream_t s, bool seq, float *d_ub, float *d_vb)
 {
@@ -1001,35 +1079,19 @@ int plan_pyramidal(oflk_plan *p, const void *d_prev_in, const void *d_curr_in, b
         if ((rc = dmalloc(&p->state_b, p->state_words() / 2, &p->ws_bytes))) return rc;
     }
     p->last_fb = fb;
-    // images the pyramid is built for: prev and curr of every pair, or every frame of a sequence once
-    const int nimg = seq ? B + 1 : 2 * B;
-    if (u8 && L > 1 &&
-        !pyr_fused_fits(p->dims[2 * (L - 1)], p->dims[2 * (L - 1) + 1], p->dims[2 * (L - 2)], p->dims[2 * (L - 2) + 1], p->gauss)) {
+    if (u8 && u8_needs_stage(p)) {
         // the unfused pyramid kernels read float32: convert once and run the float path
-        const size_t N = (size_t)p->H * p->W, n = (size_t)B * N;
-        size_t tot = 0;
-        for (int i = 0; i < 2; i++)
-            if (!p->u8_stage[i] && (rc = dmalloc(&p->u8_stage[i], i == 0 ? n + N : n, &tot))) return rc;
-        p->ws_bytes += tot;
-        const size_t n0 = seq ? n + N : n;   // a sequence's B+1 frames all go to the first stage
-        hipLaunchKernelGGL(k_u8_to_f32, dim3((unsigned)((n0 + 4095) / 4096)), dim3(256), 0, s, static_cast<const unsigned char *>(d_prev_in),
-                           p->u8_stage[0], n0);
-        HIP_TRY(hipGetLastError());
-        if (seq) return plan_pyramidal(p, p->u8_stage[0], p->u8_stage[0] + N, false, d_u, d_v, s, true, d_ub, d_vb);
-        hipLaunchKernelGGL(k_u8_to_f32, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, s, static_cast<const unsigned char *>(d_curr_in),
-                           p->u8_stage[1], n);
-        HIP_TRY(hipGetLastError());
+        if ((rc = stage_u8(p, s, d_prev_in, d_curr_in, seq))) return rc;
+        if (seq) return plan_pyramidal(p, p->u8_stage[0], p->u8_stage[0] + (size_t)p->H * p->W, false, d_u, d_v, s, true, d_ub, d_vb);
         return plan_pyramidal(p, p->u8_stage[0], p->u8_stage[1], false, d_u, d_v, s);
     }
     // typed float for the common case; with u8 the kernels of the finest level read them as uint8
     const float *d_prev = static_cast<const float *>(d_prev_in), *d_curr = static_cast<const float *>(d_curr_in);
 
     // every level's flow lives in two interleaved {u, v} ping-pong slots of the plan; only the finest
-    // level's last launch writes the caller's planar planes (k_export_fixup de-interleaves the rest)
-    if (!p->flow[0]) {   // a plan created with levels = 1, iters = 0 (single-scale use) asked for a pyramidal pass after all
-        for (int l = 0; l < L; l++)
-            if ((rc = dmalloc(&p->flow[l], (size_t)2 * 2 * B * p->npix(l), &p->ws_bytes))) return rc;
-    }
+    // level's last launch writes the caller's planar planes (k_export_fixup de-interleaves the rest).  They and the blur
+    // temporaries are allocated by a plan's first dense pass (this allocation is why that pass is eager)
+    if ((rc = ensure_dense_ws(p))) return rc;
 
     if (!tiled_window(p->hw)) {
         // 1x1 / 13x13 and larger windows have no fused iteration kernel: every pair runs the reference's own sequence of
@@ -1052,24 +1114,8 @@ int plan_pyramidal(oflk_plan *p, const void *d_prev_in, const void *d_curr_in, b
         if (rc) return rc;
     }
 
-    // ---- pyramids (lucas_kanade_pyramidal.py:173-174), fine -> coarse ---------
-    for (int l = L - 2; l >= 0; l--) {
-        int h = p->dims[2 * (l + 1)], w = p->dims[2 * (l + 1) + 1];
-        int ho = p->dims[2 * l], wo = p->dims[2 * l + 1];
-        if (l == L - 2) {
-            // the finest level is the caller's frames (image.copy() at :40 is a no-op here):
-            // prev and curr in one launch, images 0..B-1 from d_prev, B..2B-1 from d_curr;
-            // a sequence's B+1 frames are one buffer (in2 unused)
-            first.in2 = seq ? nullptr : d_curr;
-            first.nsplit = seq ? 0 : B;
-            first.u8 = u8;
-            rc = launch_pyr_down(p, p->gauss, s, d_prev, p->pyr[l], p->tmpA, p->tmpB, nimg, h, w, ho, wo, &first);
-            if (rc) return rc;
-        } else {
-            rc = launch_pyr_down(p, p->gauss, s, p->pyr[l + 1], p->pyr[l], p->tmpA, p->tmpB, nimg, h, w, ho, wo);
-            if (rc) return rc;
-        }
-    }
+    first.u8 = u8;
+    if ((rc = build_pyramids(p, s, d_prev, d_curr, seq, first))) return rc;
 
     // pair b reads pyramid images b and B + b, or a sequence's frames b and b + 1
     if ((rc = iterate_levels(p, s, d_prev, d_curr, 0, seq ? 1 : B, u8, d_u, d_v)) || !fb) return rc;
@@ -1248,6 +1294,7 @@ int resolve_pair(oflk_plan *p, int b, const void *d_prev_in, const void *d_curr_
     const size_t N = (size_t)H * W;
     oflk_plan::Exact &x = p->exact;
     int rc;
+    if ((rc = ensure_dense_ws(p))) return rc;   // the blur temporaries and the level flows' slots
     if (!x.ready) {
         size_t tot = 0;
         for (int l = 0; l < L; l++) {
@@ -1438,6 +1485,7 @@ OFLK_API int oflk_plan_read_level_flow(oflk_plan *p, int level, int pair, float 
         return fail(OFLK_ERR_INVALID, "level must be in [0,%d): the finest level's flow is the call's result", p->L - 1);
     if (pair < 0 || pair >= p->B) return fail(OFLK_ERR_INVALID, "pair %d out of range [0,%d)", pair, p->B);
     HIP_TRY(hipSetDevice(p->device));
+    if (!p->flow[level]) return fail(OFLK_ERR_INVALID, "no pyramidal pass has run on this plan yet");
     hipStream_t s = (hipStream_t)stream;
     StateSwap sw(p, p->last_fb);   // after a bidirectional pass the slots hold the backward flows
     int executed = 0;
@@ -3015,6 +3063,233 @@ OFLK_API int oflk_pyramidal_sequence_klt_replenish_u8(const unsigned char *frame
 {
     return sequence_klt_replenish<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, quality_level,
                                                  min_distance, max_corners, detect_every, tracks, visible, born, detected);
+}
+
+// =============================================================================
+// sparse pyramidal LK: points in, points out, no dense flow
+// =============================================================================
+namespace {
+// The configuration's refusals, before any device call: levels, iterations (INVALID), the window (odd, 3..11) and the
+// level sizes (every dimension >= 2: a level's linspace geometry divides by size - 1) (UNSUPPORTED)
+int check_sparse_config(int H, int W, int levels, int window_size, int iters)
+{
+    if (H < 1 || W < 1) return fail(OFLK_ERR_INVALID, "H and W must be >= 1 (got %d x %d)", H, W);
+    if (levels < 1 || levels > OFLK_MAX_LEVELS)
+        return fail(OFLK_ERR_INVALID, "levels must be in [1,%d] (got %d)", OFLK_MAX_LEVELS, levels);
+    if (iters < 1) return fail(OFLK_ERR_INVALID, "the sparse tracker needs iters >= 1 (got %d)", iters);
+    if (window_size < 3 || window_size > 11 || window_size % 2 == 0)
+        return fail(OFLK_ERR_UNSUPPORTED, "the sparse tracker is built for the odd windows 3 ... 11 (got %d)", window_size);
+    int h = H, w = W;
+    for (int l = levels - 1; l >= 0; l--) {
+        if (h < 2 || w < 2)
+            return fail(OFLK_ERR_UNSUPPORTED, "pyramid level %d of %dx%d would be %dx%d: the sparse tracker needs 2 x 2", l, W, H, w, h);
+        h = (int)((double)h * 0.5);
+        w = (int)((double)w * 0.5);
+    }
+    return OFLK_OK;
+}
+
+int check_sparse_test(float alpha, float beta, float max_residual)
+{
+    if (int rc = check_alpha_beta(alpha, beta)) return rc;
+    if (!(max_residual >= 0.0f)) return fail(OFLK_ERR_INVALID, "max_residual must be >= 0 (+inf disables the test)");
+    return OFLK_OK;
+}
+
+// The plan's B+1 pyramids of d_frames [B+1][H][W] (build_pyramids, exact arithmetic always) and the kernel arguments
+// that describe them.  Device workspace of a sparse pass: the plan's pyramid levels below the frame, nothing of frame
+// size -- except where a level is too small for the fused pyramid kernel: then the blur temporaries for B+1 images and,
+// for uint8 frames, their float32 copies.
+int sparse_pyramids(oflk_plan *p, const void *d_frames, bool u8, hipStream_t s, SparseArgs *a)
+{
+    HIP_TRY(hipSetDevice(p->device));
+    int rc;
+    if (u8 && u8_needs_stage(p)) {
+        if ((rc = stage_u8(p, s, d_frames, nullptr, true))) return rc;
+        d_frames = p->u8_stage[0];
+        u8 = false;
+    }
+    bool unfused = false;
+    for (int l = p->L - 2; l >= 0; l--)
+        unfused = unfused || !pyr_fused_fits(p->dims[2 * (l + 1)], p->dims[2 * (l + 1) + 1], p->dims[2 * l], p->dims[2 * l + 1], p->gauss);
+    if (unfused && (rc = ensure_tmp(p, (size_t)p->B + 1))) return rc;
+    PyrExtra first;
+    first.u8 = u8;
+    const int arith = p->arith;
+    p->arith = OFLK_ARITH_EXACT;
+    rc = build_pyramids(p, s, static_cast<const float *>(d_frames), nullptr, true, first);   // one buffer: no second pointer
+    p->arith = arith;
+    if (rc) return rc;
+    *a = SparseArgs{};
+    a->frames = d_frames;
+    a->L = p->L; a->K = p->K; a->B = p->B; a->H = p->H; a->W = p->W;
+    for (int l = 0; l < p->L; l++) {
+        a->pyr[l] = p->pyr[l];
+        a->dims[2 * l] = p->dims[2 * l];
+        a->dims[2 * l + 1] = p->dims[2 * l + 1];
+        if (l > 0) {   // upsample_args' ratios
+            a->sx[l] = (float)((double)p->dims[2 * l + 1] / (double)p->dims[2 * l - 1]);
+            a->sy[l] = (float)((double)p->dims[2 * l] / (double)p->dims[2 * l - 2]);
+        }
+    }
+    return u8 ? 1 : 0;   // > 0: the kernels read the finest level as uint8
+}
+
+template <bool TRACK>
+int sparse_launch(const oflk_plan *p, const SparseArgs &a, bool u8, hipStream_t s)
+{
+    const dim3 grid((unsigned)a.N);
+    const bool built = with_half_window(p->hw, [&](auto HW) {
+        with_pix(u8, [&](auto PIX) {
+            using T = typename decltype(PIX)::type;
+            if constexpr (TRACK) hipLaunchKernelGGL((k_sparse_track<decltype(HW)::value, T>), grid, dim3(64), 0, s, a);
+            else hipLaunchKernelGGL((k_sparse_lk<decltype(HW)::value, T>), grid, dim3(64), 0, s, a);
+        });
+    });
+    if (!built) return fail(OFLK_ERR_UNSUPPORTED, "half window %d not built", p->hw);
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+
+int plan_sparse_tracks(oflk_plan *p, const void *d_frames, bool u8, float alpha, float beta, float max_residual, int t0,
+                       const int *d_qt, const float *d_qxy, int N, float *d_tracks, unsigned char *d_visible, hipStream_t s)
+{
+    if (!p || !d_frames) return fail(OFLK_ERR_INVALID, "NULL argument");
+    int rc = check_queries(nullptr, p->B + 1, d_qxy, N, d_tracks, d_visible);
+    if (rc || (rc = check_sparse_test(alpha, beta, max_residual)) || (rc = check_sparse_config(p->H, p->W, p->L, p->win, p->K)))
+        return rc;
+    if (t0 < 0) return fail(OFLK_ERR_INVALID, "t0 must be >= 0 (got %d)", t0);
+    SparseArgs a;
+    if ((rc = sparse_pyramids(p, d_frames, u8, s, &a)) < 0) return rc;
+    a.qt = d_qt; a.qxy = d_qxy; a.tracks = d_tracks; a.visible = d_visible;
+    a.N = N; a.t0 = t0;
+    a.alpha = alpha; a.beta = beta; a.max_residual = max_residual;
+    return sparse_launch<true>(p, a, rc > 0, s);
+}
+
+template <class PIXELS>
+int sparse_lk_host(const PIXELS *prev, const PIXELS *curr, int H, int W, int levels, int window_size, int iters, const float *pts,
+                   int N, float *next_pts, unsigned char *status, float *residual)
+{
+    int rc = check_hw(prev, curr, H, W);
+    if (rc) return rc;
+    if (!pts || !next_pts || !status || !residual) return fail(OFLK_ERR_INVALID, "NULL point or output argument");
+    if (N < 1) return fail(OFLK_ERR_INVALID, "N must be >= 1 (got %d)", N);
+    if ((rc = check_sparse_config(H, W, levels, window_size, iters))) return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const size_t plane = (size_t)H * W, row = (size_t)N;
+    PIXELS *d_frames;
+    float *d_pts, *d_next, *d_res;
+    unsigned char *d_st;
+    oflk_plan *p = nullptr;
+    if ((rc = call.alloc(&d_frames, 2 * plane)) || (rc = call.to_device(d_frames, prev, plane)) ||
+        (rc = call.to_device(d_frames + plane, curr, plane)) || (rc = call.upload(&d_pts, pts, 2 * row)) ||
+        (rc = call.alloc(&d_next, 2 * row)) || (rc = call.alloc(&d_st, row)) || (rc = call.alloc(&d_res, row)) ||
+        (rc = host_plan(*call.c, call.dev, 1, H, W, levels, window_size, iters, &p)))
+        return rc;
+    SparseArgs a;
+    if ((rc = sparse_pyramids(p, d_frames, sizeof(PIXELS) == 1, nullptr, &a)) < 0) return rc;
+    a.pts = d_pts; a.next_pts = d_next; a.status = d_st; a.residual = d_res;
+    a.N = N;
+    if ((rc = sparse_launch<false>(p, a, rc > 0, nullptr))) return rc;
+    if ((rc = call.to_host(next_pts, d_next, 2 * row)) || (rc = call.to_host(status, d_st, row)) ||
+        (rc = call.to_host(residual, d_res, row)))
+        return rc;
+    return call.sync();
+}
+
+// Pairs per chunk of the sparse sequence call: a chunk holds C+1 frames and their pyramids and no flow, so it is sized by
+// the frames alone (~128 MB of float32 frames: sixteen 1080p pairs, four times chunk_pairs' four), and capped at 64 pairs,
+// which bounds a track launch's serial chain.  Below B exactly when the call is chunked.
+int sparse_chunk_pairs(int B, int H, int W)
+{
+    const size_t frame = (size_t)H * W * sizeof(float);
+    const int C = (int)std::min<size_t>(64, std::max<size_t>(1, ((size_t)128 << 20) / std::max<size_t>(frame, 1)));
+    return std::min(B, C);
+}
+
+// Sparse tracks of a whole sequence, host pointers.  Chunks as run_sequence_bidir's: C+1 frames go up (the boundary frame
+// is shared), one sparse pass (pyramids + one track launch, t0 = the chunk's first frame) continues from the previous
+// chunk's last row, only the rows come down.
+template <class PIXELS>
+int sequence_sparse_tracks(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
+                           float beta, float max_residual, const int *qt, const float *qxy, int N, float *tracks,
+                           unsigned char *visible)
+{
+    int rc = check_hw(frames, frames, H, W);
+    if (rc) return rc;
+    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
+    if ((rc = check_queries(qt, T, qxy, N, tracks, visible)) || (rc = check_sparse_test(alpha, beta, max_residual)) ||
+        (rc = check_sparse_config(H, W, levels, window_size, iters)))
+        return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const int B = T - 1, C = sparse_chunk_pairs(B, H, W);
+    const size_t plane = (size_t)H * W, row = (size_t)N;
+    PIXELS *d_frames = nullptr;
+    TrackRows R;
+    if ((rc = call.alloc(&d_frames, (size_t)(C + 1) * plane)) || (rc = call.alloc(&R.tr, (size_t)(C + 1) * 2 * row)) ||
+        (rc = call.alloc(&R.vis, (size_t)(C + 1) * row)) || (rc = call.upload(&R.qxy, qxy, 2 * row)) ||
+        (qt && (rc = call.upload(&R.qt, qt, row))))
+        return rc;
+    for (int b0 = 0; b0 < B; b0 += C) {
+        const int nb = std::min(C, B - b0);
+        oflk_plan *p = nullptr;
+        if ((rc = host_plan(*call.c, call.dev, nb, H, W, levels, window_size, iters, &p))) return rc;
+        if ((rc = call.to_device(d_frames, frames + (size_t)b0 * plane, (size_t)(nb + 1) * plane))) return rc;
+        if (b0 > 0) {   // row 0 of this chunk is the previous (full, C-pair) chunk's last row
+            HIP_TRY(hipMemcpyAsync(R.tr, R.tr + (size_t)C * 2 * row, 2 * row * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(R.vis, R.vis + (size_t)C * row, row, hipMemcpyDeviceToDevice, nullptr));
+        }
+        if ((rc = plan_sparse_tracks(p, d_frames, sizeof(PIXELS) == 1, alpha, beta, max_residual, b0, R.qt, R.qxy, N, R.tr, R.vis,
+                                     nullptr)))
+            return rc;
+        const int r0 = b0 > 0 ? 1 : 0;   // row 0 of a later chunk is already on the host
+        const size_t nr = (size_t)(nb + 1 - r0);
+        if ((rc = call.to_host(tracks + (size_t)(b0 + r0) * 2 * row, R.tr + (size_t)r0 * 2 * row, nr * 2 * row)) ||
+            (rc = call.to_host(visible + (size_t)(b0 + r0) * row, R.vis + (size_t)r0 * row, nr * row)) || (rc = call.sync()))
+            return rc;
+    }
+    return OFLK_OK;
+}
+}  // namespace
+
+OFLK_API int oflk_sparse_lk(const float *prev, const float *curr, int H, int W, int levels, int window_size, int iters,
+                            const float *pts, int N, float *next_pts, unsigned char *status, float *residual)
+{
+    return sparse_lk_host<float>(prev, curr, H, W, levels, window_size, iters, pts, N, next_pts, status, residual);
+}
+
+OFLK_API int oflk_sparse_lk_u8(const unsigned char *prev, const unsigned char *curr, int H, int W, int levels, int window_size,
+                               int iters, const float *pts, int N, float *next_pts, unsigned char *status, float *residual)
+{
+    return sparse_lk_host<unsigned char>(prev, curr, H, W, levels, window_size, iters, pts, N, next_pts, status, residual);
+}
+
+OFLK_API int oflk_plan_sparse_tracks(oflk_plan *plan, const void *d_frames, int u8, float alpha, float beta, float max_residual,
+                                     int t0, const int *d_qt, const float *d_qxy, int N, float *d_tracks,
+                                     unsigned char *d_visible, void *stream)
+{
+    return plan_sparse_tracks(plan, d_frames, u8 != 0, alpha, beta, max_residual, t0, d_qt, d_qxy, N, d_tracks, d_visible,
+                              (hipStream_t)stream);
+}
+
+OFLK_API int oflk_pyramidal_sequence_sparse_tracks(const float *frames, int T, int H, int W, int levels, int window_size,
+                                                   int iters, float alpha, float beta, float max_residual, const int *qt,
+                                                   const float *qxy, int N, float *tracks, unsigned char *visible)
+{
+    return sequence_sparse_tracks<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, qt, qxy, N, tracks,
+                                         visible);
+}
+
+OFLK_API int oflk_pyramidal_sequence_sparse_tracks_u8(const unsigned char *frames, int T, int H, int W, int levels,
+                                                      int window_size, int iters, float alpha, float beta, float max_residual,
+                                                      const int *qt, const float *qxy, int N, float *tracks,
+                                                      unsigned char *visible)
+{
+    return sequence_sparse_tracks<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, qt, qxy, N,
+                                                 tracks, visible);
 }
 
 OFLK_API int oflk_pyramidal_last_level_flow(int B, int H, int W, int levels, int window_size, int iters, int level,

@@ -81,6 +81,11 @@ SIGNATURES = {
     "oflk_track_points_host": (ctypes.c_int, [_f32p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
     "oflk_pyramidal_sequence_tracks": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 2 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
     "oflk_pyramidal_sequence_tracks_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 2 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
+    "oflk_sparse_lk": (ctypes.c_int, [_f32p, _f32p] + [ctypes.c_int] * 5 + [_f32p, ctypes.c_int, _f32p, _vp, _f32p]),
+    "oflk_sparse_lk_u8": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 5 + [_f32p, ctypes.c_int, _f32p, _vp, _f32p]),
+    "oflk_plan_sparse_tracks": (ctypes.c_int, [_vp, _vp, ctypes.c_int] + [ctypes.c_float] * 3 + [ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, _vp]),
+    "oflk_pyramidal_sequence_sparse_tracks": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 3 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
+    "oflk_pyramidal_sequence_sparse_tracks_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 3 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
     "oflk_corner_score": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_vp, _vp]),
     "oflk_corner_score_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 4 + [_f32p]),
     "oflk_corner_score_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_f32p]),
@@ -402,6 +407,36 @@ def track_points(d_uf: int, d_vf: int, d_ub: int, d_vb: int, B: int, H: int, W: 
 
 
 CORNER_WINDOWS = (3, 5, 7, 9, 11)
+
+
+def check_sparse_params(shape, num_levels, window_size, num_iterations, max_residual: float = 0.0) -> Tuple[int, int, int, float]:
+    """The sparse tracker's configuration as the C ABI takes it: (levels, window, iterations, max_residual as float32).
+    ValueError unless levels >= 1, iterations >= 1, the window is odd in [3, 11], every pyramid level of `shape` = (H, W)
+    is at least 2 x 2 and max_residual is >= 0 (inf allowed: no residual test).  Nothing here touches a device."""
+    for name, v in (("num_levels", num_levels), ("num_iterations", num_iterations)):
+        if isinstance(v, bool) or int(v) != v or int(v) < 1:
+            raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+    if window_size not in CORNER_WINDOWS:
+        raise ValueError(f"window_size must be one of {CORNER_WINDOWS}, got {window_size!r}")
+    h, w = int(shape[0]), int(shape[1])
+    for l in range(int(num_levels) - 1, -1, -1):
+        if h < 2 or w < 2:
+            raise ValueError(f"pyramid level {l} of {shape[0]} x {shape[1]} frames would be {h} x {w}: the sparse tracker needs 2 x 2")
+        h, w = int(h * 0.5), int(w * 0.5)
+    with np.errstate(over="ignore"):
+        r = np.float32(max_residual)
+    if not r >= 0:
+        raise ValueError(f"max_residual must be >= 0 (inf: no residual test), got {max_residual!r}")
+    return int(num_levels), int(window_size), int(num_iterations), float(r)
+
+
+def sparse_tracks(plan: "Plan", d_frames: int, d_qxy: int, N: int, d_tracks: int, d_visible: int, alpha: float = 0.01,
+                  beta: float = 0.5, max_residual: float = 4.0, t0: int = 0, d_qt: int = 0, u8: bool = False,
+                  stream: int = 0) -> None:
+    """oflk_plan_sparse_tracks on device pointers: d_frames [B+1][H][W] (float32, or uint8 with u8) are frames t0 .. t0+B of
+    the plan's B pairs; queries, rows and row 0 as track_points.  No flow field is computed or stored."""
+    check(lib().oflk_plan_sparse_tracks(plan._h, d_frames, int(bool(u8)), float(alpha), float(beta), float(max_residual), int(t0),
+                                        d_qt or None, d_qxy, int(N), d_tracks, d_visible, stream))
 
 
 def check_feature_params(max_corners, quality_level: float, min_distance: float, window_size: int) -> Tuple[int, float, float, int]:

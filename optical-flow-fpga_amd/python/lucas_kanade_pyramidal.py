@@ -30,7 +30,7 @@ import numpy as np
 import numpy.typing as npt
 
 import _oflk
-from lucas_kanade_core import lucas_kanade_single_scale
+from lucas_kanade_core import good_features_to_track, lucas_kanade_single_scale
 
 SCRIPT_DIR = Path(__file__).resolve().parent
 PROJECT_ROOT = SCRIPT_DIR.parent
@@ -312,6 +312,73 @@ def lucas_kanade_pyramidal_sequence_klt(frames, max_corners: int, quality_level:
                    _oflk.ptr(xy), _oflk.ptr(score), _oflk.ptr(tracks), visible.ctypes.data))
     n = int(count[0])
     return SequenceKLT(xy[:n], tracks[:, :n], visible[:, :n].astype(bool))
+
+
+def lucas_kanade_sparse(frame_prev, frame_curr, points, num_levels: int = 3, window_size: int = 5, num_iterations: int = 3):
+    """Sparse pyramidal Lucas-Kanade of one pair (the shape of calcOpticalFlowPyrLK): points (N, 2) (x, y) of frame_prev ->
+    (next_points (N, 2) float32, status (N,) bool, residual (N,) float32: the mean absolute difference of the two windows).
+
+    Per point and pyramid level a (window_size + 2)^2 template patch and, per iteration, the patch around the displaced
+    point are sampled bilinearly and solved with the reference's single-scale operations; the cost is proportional to
+    N * window_size^2 * num_levels * num_iterations, and no flow field exists anywhere.  status is False where the last
+    2x2 system had no solution or the point left the frame; a point outside the frame gives NaN.  Both frames uint8: the
+    uint8 path."""
+    u8 = _oflk.both_u8(frame_prev, frame_curr)
+    p, c = (np.ascontiguousarray(frame_prev), np.ascontiguousarray(frame_curr)) if u8 else (_oflk.as_f32(frame_prev),
+                                                                                            _oflk.as_f32(frame_curr))
+    H, W = _oflk.same_shape(p, c)
+    L, win, K, _ = _oflk.check_sparse_params((H, W), num_levels, window_size, num_iterations)
+    pts = np.asarray(points)
+    if pts.ndim != 2 or pts.shape[1] != 2 or pts.shape[0] < 1:
+        raise ValueError(f"points must be an (N, 2) (x, y) array with N >= 1, got shape {pts.shape}")
+    pts = np.ascontiguousarray(pts, np.float32)
+    N = pts.shape[0]
+    nxt, status, res = np.empty((N, 2), np.float32), np.empty(N, np.uint8), np.empty(N, np.float32)
+    if u8:
+        _oflk.check(_oflk.lib().oflk_sparse_lk_u8(p.ctypes.data, c.ctypes.data, H, W, L, win, K, _oflk.ptr(pts), N, _oflk.ptr(nxt),
+                                                  status.ctypes.data, _oflk.ptr(res)))
+    else:
+        _oflk.check(_oflk.lib().oflk_sparse_lk(_oflk.ptr(p), _oflk.ptr(c), H, W, L, win, K, _oflk.ptr(pts), N, _oflk.ptr(nxt),
+                                               status.ctypes.data, _oflk.ptr(res)))
+    return nxt, status.astype(bool), res
+
+
+def lucas_kanade_pyramidal_sequence_sparse_tracks(frames, queries, num_levels: int = 3, window_size: int = 5,
+                                                  num_iterations: int = 3, alpha: float = 0.01, beta: float = 0.5,
+                                                  max_residual: float = 4.0) -> SequenceTracks:
+    """lucas_kanade_pyramidal_sequence_tracks with the sparse tracker: every step of a point is lucas_kanade_sparse forward,
+    then backward from where it landed, and the point stays alive while both succeed, the two displacements pass the
+    forward-backward test (alpha, beta) and the forward residual is at most max_residual (grey levels; inf: no such test).
+    No dense flow is computed: only frames go up and rows come down.  frames, queries and the result as
+    lucas_kanade_pyramidal_sequence_tracks."""
+    a, b = _oflk.check_fb_params(alpha, beta)
+    arr, u8 = _oflk.as_sequence(frames)
+    T, H, W = arr.shape
+    L, win, K, r = _oflk.check_sparse_params((H, W), num_levels, window_size, num_iterations, max_residual)
+    qt, qxy = _oflk.as_queries(queries, T)
+    N = qxy.shape[0]
+    tracks, visible = np.empty((T, N, 2), np.float32), np.empty((T, N), np.uint8)
+    fn = _oflk.lib().oflk_pyramidal_sequence_sparse_tracks_u8 if u8 else _oflk.lib().oflk_pyramidal_sequence_sparse_tracks
+    src = arr.ctypes.data if u8 else _oflk.ptr(arr)
+    _oflk.check(fn(src, T, H, W, L, win, K, a, b, r, None if qt is None else qt.ctypes.data_as(_oflk._i32p), _oflk.ptr(qxy), N,
+                   _oflk.ptr(tracks), visible.ctypes.data))
+    return SequenceTracks(tracks, visible.astype(bool))
+
+
+def lucas_kanade_pyramidal_sequence_klt_sparse(frames, max_corners: int, quality_level: float = 0.01, min_distance: float = 10.0,
+                                               num_levels: int = 3, window_size: int = 5, num_iterations: int = 3,
+                                               alpha: float = 0.01, beta: float = 0.5, max_residual: float = 4.0) -> SequenceKLT:
+    """Detect, then track, sparsely: good_features_to_track on frame 0 (the LK window is the detection window), then
+    lucas_kanade_pyramidal_sequence_sparse_tracks on those points.  The features make one round trip through the host (at
+    most max_corners points).  Result as lucas_kanade_pyramidal_sequence_klt."""
+    a, b = _oflk.check_fb_params(alpha, beta)
+    arr, _ = _oflk.as_sequence(frames)
+    _oflk.check_sparse_params(arr.shape[1:], num_levels, window_size, num_iterations, max_residual)
+    xy, _ = good_features_to_track(arr[0], max_corners, quality_level, min_distance, window_size)
+    if xy.shape[0] == 0:
+        return SequenceKLT(xy, np.empty((arr.shape[0], 0, 2), np.float32), np.empty((arr.shape[0], 0), bool))
+    r = lucas_kanade_pyramidal_sequence_sparse_tracks(arr, xy, num_levels, window_size, num_iterations, a, b, max_residual)
+    return SequenceKLT(xy, r.tracks, r.visible)
 
 
 class SequenceKLTReplenish(NamedTuple):

@@ -566,9 +566,12 @@ int oflk_last_resolved(void);
  * backward pass's level flows (pair b: frames b+1 -> b).  Synchronises. */
 int oflk_plan_read_level_flow(oflk_plan *plan, int level, int pair, float *u, float *v, void *stream);
 
-/* Arithmetic of the plan's fp64 stages.  OFLK_ARITH_EXACT (the default of plans and of the host entry points): SciPy's
- * operation sequence, every operation rounded on its own -- results equal the reference's value for value.
- * OFLK_ARITH_CONTRACTED (opt-in): the Gaussian pyramid (python/lucas_kanade_pyramidal.py:46-59) accumulates with fused
+/* Arithmetic of the plan's fp64 stages.  OFLK_ARITH_EXACT (the default of plans and of the host entry points): results
+ * equal the reference's value for value.  Every stage executes SciPy's operation sequence, each operation rounded on its
+ * own, with one exception that keeps the results: the fused pyramid kernel forms each blurred value with fused
+ * multiply-adds, proves on the device that it rounds to the float32 SciPy's sequence rounds to, and executes SciPy's
+ * sequence where the proof fails.
+ * OFLK_ARITH_CONTRACTED (opt-in): the same fused sums without that proof, in the sampling as well: the Gaussian pyramid (python/lucas_kanade_pyramidal.py:46-59) accumulates with fused
  * multiply-adds, 17 instead of 25 fp64 operations per blurred value on a kernel the fp64 pipe binds.  Intermediates
  * differ from SciPy's by a few 1e-16 relative before they are rounded to float32 where SciPy rounds, so a pyramid value
  * differs from the reference's only where the fp64 value lies that close to a float32 rounding boundary (about one in

@@ -660,10 +660,13 @@ int launch_pyr_down(oflk_plan *plan, const GaussW &gauss, hipStream_t s, const f
         for (int k = 0; k <= 8; k++) a.w[k] = gauss.w[k];
         dim3 grid((wo + kPTW - 1) / kPTW, (ho + kPTH - 1) / kPTH, nimg);
         Prof pr(plan, s, KC_PYR_FUSED);
-        const bool fma = contracted_pyramid(plan);   // opt-in (contracted / tolerant); never the default
+        // contracted / tolerant plans: the opt-in fused sums as they are.  The exact arithmetic (every other plan, and no
+        // plan at all) runs them behind the rounding certificate, which leaves SciPy's results
+        constexpr int kExactForm = OFLK_PYR_CERT ? PYR_CERTIFIED : PYR_EXACT;
+        const int arith = contracted_pyramid(plan) ? PYR_CONTRACTED : kExactForm;
         with_pix(extra && extra->u8, [&](auto PIX) {
-            with_bool(fma, [&](auto FMA) {
-                hipLaunchKernelGGL((k_pyr_down<typename decltype(PIX)::type, decltype(FMA)::value>), grid, dim3(256), 0, s, a);
+            with_int<PYR_CONTRACTED, kExactForm>(arith, [&](auto ARITH) {
+                hipLaunchKernelGGL((k_pyr_down<typename decltype(PIX)::type, decltype(ARITH)::value>), grid, dim3(256), 0, s, a);
             });
         });
         HIP_TRY(hipGetLastError());
@@ -1239,6 +1242,21 @@ OFLK_API int oflk_plan_read_log(oflk_plan *p, float *residual_log, int *iters_ru
     HIP_TRY(hipStreamSynchronize(s));
     return OFLK_OK;
 }
+
+#ifdef OFLK_DIAG
+// diagnostic build only (tools/pyr_redo.py): waves of k_pyr_down's passes B and C on the current device since the last
+// reset, [B ran, B redone, C ran, C redone]
+OFLK_API int oflk_debug_pyr_cert_waves(unsigned long long *out, int reset)
+{
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pyr_cert_waves), 4 * sizeof(unsigned long long)) != hipSuccess) return -1;
+    if (reset) {
+        const unsigned long long z[4] = {0, 0, 0, 0};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_pyr_cert_waves), z, sizeof(z)) != hipSuccess) return -1;
+    }
+    return 0;
+}
+#endif
 
 #ifdef OFLK_STAMPS
 // diagnostic build only (tools/stamps.py): [blocks][4 waves][8 tiles][16] s_memtime stamps of the last

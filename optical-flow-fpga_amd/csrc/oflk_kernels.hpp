@@ -24,6 +24,9 @@
 #ifndef OFLK_PYR_PAIRS
 #define OFLK_PYR_PAIRS 1   // k_pyr_down: interior float32 tiles staged as column pairs (8-byte loads)
 #endif
+#ifndef OFLK_PYR_CERT
+#define OFLK_PYR_CERT 1    // k_pyr_down: the exact arithmetic runs the certified form (0: SciPy's sequence throughout)
+#endif
 #ifndef OFLK_LK16_PF
 #define OFLK_LK16_PF 2   // rows of frame loads in flight per wave (k_lk16d)
 #endif
@@ -1881,13 +1884,79 @@ struct PyrArgs {
     double w[9];       // gaussian weights, w[k] at distance k
 };
 
-// FMA = false: SciPy's operation sequence, every fp64 operation rounded on its own (the default; results equal to
-// the reference's).  FMA = true (opt-in, oflk_plan_set_arithmetic): the same sums with the multiply and the add of a
-// tap fused -- 17 instead of 25 fp64 operations per blurred value, on a kernel the fp64 pipe binds.  Every
-// intermediate then differs from SciPy's by at most a few 1e-16 relative BEFORE it is rounded to float32 exactly where
-// SciPy rounds (after each axis, after the sampling), so a float32 value differs from the reference's only where the
-// fp64 value lies within that distance of a float32 rounding boundary: about one value in 10^7, by one float32 ulp.
-template <class PIX, bool FMA = false>
+// The arithmetic of passes B and C (and, for the contracted form, of stage D):
+//   PYR_EXACT       SciPy's operation sequence, every fp64 operation rounded on its own: results equal to the reference's.
+//   PYR_CONTRACTED  (opt-in, oflk_plan_set_arithmetic) the same sums with the multiply and the add of a tap fused -- 17
+//                   instead of 25 fp64 operations per blurred value, on a kernel the fp64 pipe binds.  Every
+//                   intermediate then differs from SciPy's by at most a few 1e-16 relative BEFORE it is rounded to float32
+//                   exactly where SciPy rounds (after each axis, after the sampling), so a float32 value differs from the
+//                   reference's only where the fp64 value lies within that distance of a float32 rounding boundary: about
+//                   one value in 10^7, by one float32 ulp.
+//   PYR_CERTIFIED   what the exact arithmetic runs: passes B and C compute the fused sum t' and prove, per value, that it
+//                   rounds to the float32 SciPy's sum t rounds to (PyrCert below; the proof is DESIGN.md section 2).  A
+//                   wave in which any value is left unproven recomputes its outputs with SciPy's sequence, so the
+//                   results are PYR_EXACT's in every case.  Stage D is PYR_EXACT's.
+enum { PYR_EXACT = 0, PYR_CONTRACTED = 1, PYR_CERTIFIED = 2 };
+
+// one blurred value: x[8] w[0], then the eight symmetric pairs from the outside in (scipy.ndimage.correlate1d)
+template <bool FMA>
+__device__ __forceinline__ double pyr_tap_sum(const float *x, const double *w)
+{
+    double t = (double)x[8] * w[0];
+#pragma unroll
+    for (int k = 8; k >= 1; k--) {
+        double sgm = (double)x[8 - k] + (double)x[8 + k];
+        if constexpr (FMA) {
+            t = __builtin_fma(sgm, w[k], t);
+        } else {
+            double m = sgm * w[k];
+            t = t + m;
+        }
+    }
+    return t;
+}
+
+// The certificate of PYR_CERTIFIED.  |t - t'| <= c u M with u = 2^-53, M the largest |input| of
+// the window and c = 32 (derived: 18.0...).  float32(t') == float32(t) is proven when, with R = 64 and
+// delta = 2^11 = c R fp64 ulps,
+//   (1) t' is finite (then so is every input: the weights are positive),
+//   (2) 2^-126 <= |t'| < 2^127 (float32's normal range, one binade short of overflow), or M == 0 and t' == 0,
+//   (3) |t'| >= M / R, so that c u M is at most c R ulps of t',
+//   (4) the low 29 mantissa bits of t' are more than delta away from 2^28, the float32 rounding boundary.
+// A thread accumulates over its outputs and tests once: M is the largest |value| of ALL its window registers (never
+// smaller than a value's own M), (2) and (3) are tested on tf = float32(t') with thresholds that imply them
+// (|tf| >= max(M / 32, 2^-125) gives |t'| >= |tf| (1 - 2^-24) >= max(M / 64, 2^-126); |tf| < 2^127 gives |t'| < 2^127),
+// and on bit patterns, so that a NaN or an infinity compares as too large.  Everything is phrased so that it is true
+// only when the value is proven safe.
+constexpr unsigned kCertDelta = 1u << 11;
+struct PyrCert {
+    unsigned ymin = ~0u, amin = ~0u, amax = 0u;
+    __device__ __forceinline__ void add(double t, float tf)
+    {
+        // y = (low29 - 2^28 + delta) mod 2^29, kept as y << 3: |low29 - 2^28| > delta  <=>  y > 2 delta
+        ymin = min(ymin, ((unsigned)__double2loint(t) + (kCertDelta - (1u << 28))) << 3);
+        const unsigned ab = __float_as_uint(tf) & 0x7fffffffu;
+        amin = min(amin, ab);
+        amax = max(amax, ab);
+    }
+    __device__ __forceinline__ bool safe(float M) const
+    {
+        const unsigned thr = __float_as_uint(fmaxf(M * 0.03125f, 0x1p-125f));   // M = inf: no |tf| reaches it
+        const bool magnitude = (amin >= thr && amax < 0x7f000000u) || (M == 0.0f && amax == 0u);
+        return ymin > ((2u * kCertDelta) << 3) && magnitude;
+    }
+};
+
+#ifdef OFLK_DIAG
+// diagnostic build only: waves of passes B and C that ran, and that took the exact redo ([B ran, B redo, C ran, C redo])
+__device__ unsigned long long g_pyr_cert_waves[4];
+__device__ __forceinline__ void pyr_cert_count(int slot)
+{
+    if (__ffsll((long long)__ballot(1)) - 1 == (int)(threadIdx.x & 63)) atomicAdd(&g_pyr_cert_waves[slot], 1ull);
+}
+#endif
+
+template <class PIX, int ARITH = PYR_EXACT>
 __global__ __launch_bounds__(256) void k_pyr_down(PyrArgs a)
 {
     __shared__ __attribute__((aligned(16))) float s_in[kPIH * kPIW];   // stage A (8-byte column-pair writes); reused for the blurred tile (stage C output)
@@ -2008,22 +2077,37 @@ __global__ __launch_bounds__(256) void k_pyr_down(PyrArgs a)
             float win[RS + 16];
 #pragma unroll
             for (int k = 0; k < RS + 16; k++) win[k] = k < KSAFE ? wb[k * kPIW] : wb[min(k, kPIH - 1 - seg * RS) * kPIW];
-#pragma unroll
-            for (int o = 0; o < RS; o++) {
-                using AccB = double;
-                AccB t = (AccB)win[o + 8] * (AccB)a.w[0];
-#pragma unroll
-                for (int k = 8; k >= 1; k--) {
-                    AccB sgm = (AccB)win[o + 8 - k] + (AccB)win[o + 8 + k];
-                    if constexpr (FMA) {
-                        t = __builtin_fma(sgm, (AccB)a.w[k], t);
-                    } else {
-                        AccB m = sgm * (AccB)a.w[k];
-                        t = t + m;
-                    }
-                }
+            auto store = [&](int o, double t) {
                 int r = seg * RS + o;
                 if (r < kPBH) s_v[r * kPVS + col] = (float)t;
+            };
+            if constexpr (ARITH == PYR_CERTIFIED) {
+                float M = 0.0f;
+#pragma unroll
+                for (int k = 0; k < RS + 16; k++) M = fmaxf(M, fabsf(win[k]));
+                PyrCert cert;
+#pragma unroll
+                for (int o = 0; o < RS; o++) {
+                    double t = pyr_tap_sum<true>(&win[o], a.w);
+                    cert.add(t, (float)t);
+                    store(o, t);
+                }
+#ifdef OFLK_DIAG
+                pyr_cert_count(0);
+#endif
+                if (__any(!cert.safe(M))) {   // wave-uniform: SciPy's sequence for this wave's outputs
+#ifdef OFLK_DIAG
+                    pyr_cert_count(1);
+#endif
+                    // the window made opaque: shared with the fast path, the pair sums of all outputs would stay live
+#pragma unroll
+                    for (int k = 0; k < RS + 16; k++) asm volatile("" : "+v"(win[k]));
+#pragma unroll
+                    for (int o = 0; o < RS; o++) store(o, pyr_tap_sum<false>(&win[o], a.w));
+                }
+            } else {
+#pragma unroll
+                for (int o = 0; o < RS; o++) store(o, pyr_tap_sum<ARITH == PYR_CONTRACTED>(&win[o], a.w));
             }
         }
     }
@@ -2042,21 +2126,36 @@ __global__ __launch_bounds__(256) void k_pyr_down(PyrArgs a)
             float win[CS + 16];
 #pragma unroll
             for (int k = 0; k < CS + 16; k++) win[k] = k < KSAFE ? wb[k] : wb[min(k, kPIW - 1 - seg * CS)];
-#pragma unroll
-            for (int o = 0; o < CS; o++) {
-                using AccC = double;
-                AccC t = (AccC)win[o + 8] * (AccC)a.w[0];
-#pragma unroll
-                for (int k = 8; k >= 1; k--) {
-                    AccC sgm = (AccC)win[o + 8 - k] + (AccC)win[o + 8 + k];
-                    if constexpr (FMA) {
-                        t = __builtin_fma(sgm, (AccC)a.w[k], t);
-                    } else {
-                        AccC m = sgm * (AccC)a.w[k];
-                        t = t + m;
-                    }
-                }
+            auto store = [&](int o, double t) {
                 if (seg * CS + o < kPBW) s_h[row * kPHS + seg * CS + o] = (float)t;
+            };
+            if constexpr (ARITH == PYR_CERTIFIED) {
+                float M = 0.0f;
+#pragma unroll
+                for (int k = 0; k < CS + 16; k++) M = fmaxf(M, fabsf(win[k]));
+                PyrCert cert;
+#pragma unroll
+                for (int o = 0; o < CS; o++) {
+                    double t = pyr_tap_sum<true>(&win[o], a.w);
+                    cert.add(t, (float)t);
+                    store(o, t);
+                }
+#ifdef OFLK_DIAG
+                pyr_cert_count(2);
+#endif
+                if (__any(!cert.safe(M))) {
+#ifdef OFLK_DIAG
+                    pyr_cert_count(3);
+#endif
+                    // the window made opaque: shared with the fast path, the pair sums of all outputs would stay live
+#pragma unroll
+                    for (int k = 0; k < CS + 16; k++) asm volatile("" : "+v"(win[k]));
+#pragma unroll
+                    for (int o = 0; o < CS; o++) store(o, pyr_tap_sum<false>(&win[o], a.w));
+                }
+            } else {
+#pragma unroll
+                for (int o = 0; o < CS; o++) store(o, pyr_tap_sum<ARITH == PYR_CONTRACTED>(&win[o], a.w));
             }
         }
     }
@@ -2081,7 +2180,7 @@ __global__ __launch_bounds__(256) void k_pyr_down(PyrArgs a)
             const float *r0 = s_h + (y0 - ylo) * kPHS - xlo;
             const float *r1 = s_h + (y1 - ylo) * kPHS - xlo;
             double acc = 0.0, c;
-            if constexpr (FMA) {
+            if constexpr (ARITH == PYR_CONTRACTED) {
                 c = (double)r0[x0]; c = c * wy0; acc = c * wx0;
                 c = (double)r0[x1]; c = c * wy0; acc = __builtin_fma(c, wx1, acc);
                 c = (double)r1[x0]; c = c * wy1; acc = __builtin_fma(c, wx0, acc);

@@ -369,6 +369,58 @@ int oflk_replenish_features_host_u8(const unsigned char *frame, int H, int W, in
                                     float min_distance, int max_corners, int t, const float *xy, const unsigned char *visible,
                                     int *qt, float *qxy, unsigned char *born, int *detected);
 
+/* ---- replenished KLT on the sparse tracker ------------------------------------------------------------------------- */
+/* The statement (tests/sparse_replenish_model.py): the replenished-KLT statement above with the step of the sparse tracks
+ * (statement at oflk_pyramidal_sequence_sparse_tracks) in the place of the dense one, and one more output.  K = max_corners
+ * slots, each holding at most one live track, every slot dead at first; D = detect_every >= 1; the LK window is the
+ * detection window.  For t = 0 .. T-1:
+ *   step (t > 0):  every alive slot takes the step of pair t-1 of the sparse tracks: step forward, then step backward from
+ *                  f32(q) if the forward step is ok;  alive = ok and ok' and e2 <= alpha*m2 + beta and r <= max_residual;
+ *                  the position becomes (f32(qx), f32(qy))
+ *                  residual[t][n] = the forward step's r where that step was ok, for every slot alive on row t-1, whether
+ *                  or not the track survives the step.  Every other entry is NaN: a slot dead on row t-1 (one born on row t
+ *                  in a slot that was dead keeps its NaN), a forward step that was not ok, and all of row 0.  A slot whose
+ *                  track ends on row t and that is filled again on row t holds the ended track's residual there.
+ *   detect (t % D == 0 and t < T-1):  exactly the detection of the replenished-KLT statement on frame t: the free slots
+ *                  ascending, the seeds rint of the alive slots' positions after the step, the greedy stopped after
+ *                  len(free) acceptances, the i-th accepted point into slot free[i] (alive, born[t][slot] = 1),
+ *                  detected[t] = the number accepted
+ *   row t:         tracks[t][n] = (x, y) if alive, else (NaN, NaN);  visible[t][n] = alive
+ * With D >= T tracks and visible are those of the detection on frame 0 followed by the sparse tracks.  Positions are
+ * float32 between steps and a call's last row is never a detection row of that call, so the result does not depend on how
+ * the sequence is cut into calls or chunks.
+ *
+ * oflk_pyramidal_sequence_klt_sparse: detect once, then the sparse tracks.  Equals oflk_good_features_host on frame 0
+ * followed by oflk_pyramidal_sequence_sparse_tracks on its xy (N = K, every query at frame 0, the NaN rows never-visible
+ * tracks), byte for byte; the features are born on the device, straight into the query buffer.  Outputs as
+ * oflk_pyramidal_sequence_klt.
+ * oflk_pyramidal_sequence_klt_sparse_replenish: the statement.  tracks [T][K][2], visible, born [T][K], detected [T],
+ * residual [T][K] (may be NULL).  Chunks as oflk_pyramidal_sequence_sparse_tracks (at most 64 pairs, sized by the frames
+ * alone; the boundary frame shared, the last row carried); a chunk holds its frames and their pyramids, the rows and the
+ * detection's workspace of one frame, and no flow.  Its pyramids are built once and its pairs tracked in segments cut at
+ * the detection frames, the seven launches of a detection ahead of the segment that begins on one.  Only rows, born,
+ * detected and residual come down.
+ * Checks: those of oflk_pyramidal_sequence_sparse_tracks and of oflk_pyramidal_sequence_klt_replenish, with their codes,
+ * before any device call. */
+int oflk_pyramidal_sequence_klt_sparse(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                       float alpha, float beta, float max_residual, float quality_level, float min_distance,
+                                       int max_corners, int *count, float *xy, float *score, float *tracks,
+                                       unsigned char *visible);
+int oflk_pyramidal_sequence_klt_sparse_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size,
+                                          int iters, float alpha, float beta, float max_residual, float quality_level,
+                                          float min_distance, int max_corners, int *count, float *xy, float *score,
+                                          float *tracks, unsigned char *visible);
+int oflk_pyramidal_sequence_klt_sparse_replenish(const float *frames, int T, int H, int W, int levels, int window_size,
+                                                 int iters, float alpha, float beta, float max_residual, float quality_level,
+                                                 float min_distance, int max_corners, int detect_every, float *tracks,
+                                                 unsigned char *visible, unsigned char *born, int *detected,
+                                                 float *residual /* [T][K], may be NULL */);
+int oflk_pyramidal_sequence_klt_sparse_replenish_u8(const unsigned char *frames, int T, int H, int W, int levels,
+                                                    int window_size, int iters, float alpha, float beta, float max_residual,
+                                                    float quality_level, float min_distance, int max_corners, int detect_every,
+                                                    float *tracks, unsigned char *visible, unsigned char *born, int *detected,
+                                                    float *residual /* [T][K], may be NULL */);
+
 /* Rehearsal of the chunk queue above on a box with fewer GPUs than workers (tests): `workers` > 0 makes the *_multi entry
  * points run that many queue workers, worker i on device i % n_gpus (workers of one device take turns on it); 0 restores
  * one worker per device.  Results do not change. */
@@ -493,6 +545,22 @@ int oflk_track_points(const float *d_uf, const float *d_vf, const float *d_ub, c
 int oflk_plan_sparse_tracks(oflk_plan *plan, const void *d_frames, int u8, float alpha, float beta, float max_residual,
                             int t0, const int *d_qt, const float *d_qxy, int N, float *d_tracks, unsigned char *d_visible,
                             void *stream);
+/* Replenished KLT on the sparse tracker (statement at oflk_pyramidal_sequence_klt_sparse_replenish) through the plan's B
+ * pairs, device pointers: d_frames [B+1][H][W] (uint8 with u8 != 0) are frames t0 .. t0+B of the sequence.  t0 == 0: the
+ * call makes every slot dead itself.  t0 > 0: d_qt [K], d_qxy [K][2] and row 0 of d_tracks [B+1][K][2] / d_visible [B+1][K]
+ * are the previous call's (row 0 is its last row).  It detects on the rows r < B whose frame t0 + r is a multiple of
+ * detect_every, never on its last row; it writes d_born [B+1][K] and d_detected [B+1] completely and d_residual (may be
+ * NULL) rows 1 .. B, row 0 only when t0 == 0.  The B+1 pyramids are built once; then one track launch per segment of pairs
+ * between detection frames, on the buffers offset to the segment's first frame, the detection's seven launches ahead of
+ * it.  d_workspace: oflk_replenish_features_workspace bytes, 256-byte aligned; d_qxy and d_tracks 8-byte aligned.  Checks as
+ * oflk_plan_sparse_tracks and oflk_replenish_features, detect_every < 1 and t0 < 0: OFLK_ERR_INVALID, before any device
+ * call.  Asynchronous, no synchronisation, no host round trip; a single chain on the one stream, which can be captured into
+ * a graph after one eager call. */
+int oflk_plan_sparse_klt_replenish(oflk_plan *plan, const void *d_frames, int u8, float alpha, float beta, float max_residual,
+                                   float quality_level, float min_distance, int max_corners, int detect_every, int t0,
+                                   void *d_workspace, size_t workspace_bytes, int *d_qt, float *d_qxy, float *d_tracks,
+                                   unsigned char *d_visible, unsigned char *d_born, int *d_detected,
+                                   float *d_residual /* may be NULL */, void *stream);
 /* Shi-Tomasi scores (statement above) of F frames, device pointers: d_frames [F][H][W] float32, or uint8 with u8 != 0;
  * d_score [F][H][W].  Asynchronous; one launch. */
 int oflk_corner_score(const void *d_frames, int u8, int F, int H, int W, int window_size, float *d_score, void *stream);

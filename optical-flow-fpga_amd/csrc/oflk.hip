@@ -11,6 +11,7 @@
 #include "oflk_sparse.hpp"
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -3153,15 +3154,18 @@ int sparse_pyramids(oflk_plan *p, const void *d_frames, bool u8, hipStream_t s, 
     return u8 ? 1 : 0;   // > 0: the kernels read the finest level as uint8
 }
 
+// step_residual != NULL: the track kernel that also writes those rows
 template <bool TRACK>
-int sparse_launch(const oflk_plan *p, const SparseArgs &a, bool u8, hipStream_t s)
+int sparse_launch(const oflk_plan *p, const SparseArgs &a, bool u8, hipStream_t s, float *step_residual = nullptr)
 {
     const dim3 grid((unsigned)a.N);
     const bool built = with_half_window(p->hw, [&](auto HW) {
         with_pix(u8, [&](auto PIX) {
             using T = typename decltype(PIX)::type;
-            if constexpr (TRACK) hipLaunchKernelGGL((k_sparse_track<decltype(HW)::value, T>), grid, dim3(64), 0, s, a);
-            else hipLaunchKernelGGL((k_sparse_lk<decltype(HW)::value, T>), grid, dim3(64), 0, s, a);
+            constexpr int hw = decltype(HW)::value;
+            if constexpr (!TRACK) hipLaunchKernelGGL((k_sparse_lk<hw, T>), grid, dim3(64), 0, s, a);
+            else if (step_residual) hipLaunchKernelGGL((k_sparse_track_residual<hw, T>), grid, dim3(64), 0, s, a, step_residual);
+            else hipLaunchKernelGGL((k_sparse_track<hw, T>), grid, dim3(64), 0, s, a);
         });
     });
     if (!built) return fail(OFLK_ERR_UNSUPPORTED, "half window %d not built", p->hw);
@@ -3183,6 +3187,66 @@ int plan_sparse_tracks(oflk_plan *p, const void *d_frames, bool u8, float alpha,
     a.N = N; a.t0 = t0;
     a.alpha = alpha; a.beta = beta; a.max_residual = max_residual;
     return sparse_launch<true>(p, a, rc > 0, s);
+}
+
+// The slot side of a replenished sparse pass: the selection's parameters, its workspace (feat_ws(.., 1, .., K)), the slots'
+// queries and the per-row outputs of the pass's B+1 rows
+struct SparseKlt {
+    float q, md;
+    int K, every;
+    void *ws;
+    int *qt;                   // [K]
+    float *qxy;                // [K][2]
+    unsigned char *born;       // [B+1][K]
+    int *detected;             // [B+1]
+    float *residual;           // [B+1][K] or NULL
+};
+
+// oflk_plan_sparse_klt_replenish on checked arguments: the plan's B+1 pyramids once, then the pairs t0 .. t0+B-1 in
+// segments [s0, e) cut at the multiples of `every`, one track launch each on the buffers offset to frame s0 - t0 (the
+// kernel's frame 0, row 0 and t0 = s0).  Ahead of a segment that begins on such a multiple, the detection on that frame
+// fills free slots from the slots' row of it; the launch starts them (qt = s0) and continues the others.  The last row is
+// never a detection row.  One chain of launches on stream s; nothing is synchronized.
+int sparse_klt_pass(oflk_plan *p, const void *d_frames, bool u8, float alpha, float beta, float max_residual, int t0,
+                    const SparseKlt &k, float *d_tracks, unsigned char *d_visible, hipStream_t s)
+{
+    SparseArgs base;
+    int rc = sparse_pyramids(p, d_frames, u8, s, &base);
+    if (rc < 0) return rc;
+    const bool fine_u8 = rc > 0;
+    const int B = p->B, H = p->H, W = p->W;
+    const size_t row = (size_t)k.K, plane = (size_t)H * W;
+    if (t0 == 0) {
+        hipLaunchKernelGGL(k_slots_init, dim3((unsigned)((k.K + 255) / 256)), dim3(256), 0, s, k.qt,
+                           reinterpret_cast<float2 *>(k.qxy), reinterpret_cast<float2 *>(d_tracks), d_visible, k.K);
+        HIP_TRY(hipGetLastError());
+    }
+    const size_t nborn = (size_t)(B + 1) * row;
+    hipLaunchKernelGGL(k_sparse_rows_clear, dim3((unsigned)std::min<size_t>((nborn + 255) / 256, 1024)), dim3(256), 0, s, k.born, nborn,
+                       k.detected, (size_t)B + 1);
+    HIP_TRY(hipGetLastError());
+    const FeatWs ws = feat_ws(k.ws, 1, H, W, k.md, k.K);
+    const long long end = (long long)t0 + B;
+    for (long long s0 = t0; s0 < end;) {
+        const long long e = std::min(end, (s0 / k.every + 1) * k.every);
+        const size_t r = (size_t)(s0 - t0);
+        float *tr = d_tracks + r * 2 * row;
+        unsigned char *vis = d_visible + r * row;
+        if (s0 % k.every == 0) {
+            const SlotSide slots{tr, vis, k.qt, k.born + r * row, k.detected + r, (int)s0};
+            const void *frame = static_cast<const char *>(d_frames) + r * plane * (u8 ? 1 : sizeof(float));
+            if ((rc = detect_launch(frame, u8, 1, H, W, p->win, k.q, k.md, k.K, ws, nullptr, k.qxy, nullptr, &slots, s))) return rc;
+        }
+        SparseArgs a = base;
+        a.frames = static_cast<const char *>(base.frames) + r * plane * (fine_u8 ? 1 : sizeof(float));
+        for (int l = 0; l < p->L - 1; l++) a.pyr[l] = base.pyr[l] + r * (size_t)p->dims[2 * l] * (size_t)p->dims[2 * l + 1];
+        a.B = (int)(e - s0); a.N = k.K; a.t0 = (int)s0;
+        a.qt = k.qt; a.qxy = k.qxy; a.tracks = tr; a.visible = vis;
+        a.alpha = alpha; a.beta = beta; a.max_residual = max_residual;
+        if ((rc = sparse_launch<true>(p, a, fine_u8, s, k.residual ? k.residual + r * row : nullptr))) return rc;
+        s0 = e;
+    }
+    return OFLK_OK;
 }
 
 template <class PIXELS>
@@ -3228,17 +3292,19 @@ int sparse_chunk_pairs(int B, int H, int W)
 }
 
 // Sparse tracks of a whole sequence, host pointers.  Chunks as run_sequence_bidir's: C+1 frames go up (the boundary frame
-// is shared), one sparse pass (pyramids + one track launch, t0 = the chunk's first frame) continues from the previous
-// chunk's last row, only the rows come down.
-template <class PIXELS>
-int sequence_sparse_tracks(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
-                           float beta, float max_residual, const int *qt, const float *qxy, int N, float *tracks,
-                           unsigned char *visible)
+// is shared), pass(call, p, d_frames, b0, nb, R) enqueues the chunk's sparse pass on its plan (rows of frames b0 .. b0+nb
+// into R, continued from the previous chunk's last row, which is R's row 0), only the rows come down.  `every` > 0: the
+// multiples of it are detection frames, as in run_sequence_tracks: a chunk that begins on one sends its row 0 down again.
+// A call's other parts: checks(), setup(call, R, C) and extras(call, b0, nb, r0) after rows r0 .. nb have gone down.
+template <class PIXELS, class Checks, class Setup, class Pass, class Extras>
+int run_sequence_sparse(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
+                        float max_residual, int N, float *tracks, unsigned char *visible, int every, Checks checks, Setup setup,
+                        Pass pass, Extras extras)
 {
     int rc = check_hw(frames, frames, H, W);
     if (rc) return rc;
     if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
-    if ((rc = check_queries(qt, T, qxy, N, tracks, visible)) || (rc = check_sparse_test(alpha, beta, max_residual)) ||
+    if ((rc = checks()) || (rc = check_sparse_test(alpha, beta, max_residual)) ||
         (rc = check_sparse_config(H, W, levels, window_size, iters)))
         return rc;
     HostCall call;
@@ -3248,8 +3314,7 @@ int sequence_sparse_tracks(const PIXELS *frames, int T, int H, int W, int levels
     PIXELS *d_frames = nullptr;
     TrackRows R;
     if ((rc = call.alloc(&d_frames, (size_t)(C + 1) * plane)) || (rc = call.alloc(&R.tr, (size_t)(C + 1) * 2 * row)) ||
-        (rc = call.alloc(&R.vis, (size_t)(C + 1) * row)) || (rc = call.upload(&R.qxy, qxy, 2 * row)) ||
-        (qt && (rc = call.upload(&R.qt, qt, row))))
+        (rc = call.alloc(&R.vis, (size_t)(C + 1) * row)) || (rc = setup(call, R, C)))
         return rc;
     for (int b0 = 0; b0 < B; b0 += C) {
         const int nb = std::min(C, B - b0);
@@ -3260,16 +3325,115 @@ int sequence_sparse_tracks(const PIXELS *frames, int T, int H, int W, int levels
             HIP_TRY(hipMemcpyAsync(R.tr, R.tr + (size_t)C * 2 * row, 2 * row * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
             HIP_TRY(hipMemcpyAsync(R.vis, R.vis + (size_t)C * row, row, hipMemcpyDeviceToDevice, nullptr));
         }
-        if ((rc = plan_sparse_tracks(p, d_frames, sizeof(PIXELS) == 1, alpha, beta, max_residual, b0, R.qt, R.qxy, N, R.tr, R.vis,
-                                     nullptr)))
-            return rc;
-        const int r0 = b0 > 0 ? 1 : 0;   // row 0 of a later chunk is already on the host
+        if ((rc = pass(call, p, d_frames, b0, nb, R))) return rc;
+        // row 0 of a later chunk is already on the host, unless the chunk begins at a detection frame
+        const int r0 = b0 > 0 && !(every && b0 % every == 0) ? 1 : 0;
         const size_t nr = (size_t)(nb + 1 - r0);
         if ((rc = call.to_host(tracks + (size_t)(b0 + r0) * 2 * row, R.tr + (size_t)r0 * 2 * row, nr * 2 * row)) ||
-            (rc = call.to_host(visible + (size_t)(b0 + r0) * row, R.vis + (size_t)r0 * row, nr * row)) || (rc = call.sync()))
+            (rc = call.to_host(visible + (size_t)(b0 + r0) * row, R.vis + (size_t)r0 * row, nr * row)) ||
+            (rc = extras(call, b0, nb, r0)) || (rc = call.sync()))
             return rc;
     }
     return OFLK_OK;
+}
+
+// oflk_pyramidal_sequence_sparse_tracks: the caller's queries go up; one track launch per chunk, t0 = its first frame
+template <class PIXELS>
+int sequence_sparse_tracks(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
+                           float beta, float max_residual, const int *qt, const float *qxy, int N, float *tracks,
+                           unsigned char *visible)
+{
+    auto checks = [&]() -> int { return check_queries(qt, T, qxy, N, tracks, visible); };
+    auto setup = [&](HostCall &call, TrackRows &R, int) -> int {
+        const int rc = call.upload(&R.qxy, qxy, 2 * (size_t)N);
+        return rc || !qt ? rc : call.upload(&R.qt, qt, (size_t)N);
+    };
+    auto pass = [&](HostCall &, oflk_plan *p, const PIXELS *d_frames, int b0, int, TrackRows &R) -> int {
+        return plan_sparse_tracks(p, d_frames, sizeof(PIXELS) == 1, alpha, beta, max_residual, b0, R.qt, R.qxy, N, R.tr, R.vis, nullptr);
+    };
+    return run_sequence_sparse<PIXELS>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, N, tracks, visible, 0,
+                                       checks, setup, pass, no_part);
+}
+
+// oflk_pyramidal_sequence_klt_sparse: sequence_klt's detection on frame 0 (ahead of chunk 0's pass, straight into the query
+// buffer: N = K, the NaN rows are never-visible tracks), then sequence_sparse_tracks; count, xy and score come down with
+// chunk 0
+template <class PIXELS>
+int sequence_klt_sparse(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
+                        float max_residual, float q, float md, int K, int *count, float *xy, float *score, float *tracks,
+                        unsigned char *visible)
+{
+    const size_t row = (size_t)K;
+    char *d_ws = nullptr;
+    int *d_cnt = nullptr;
+    float *d_sc = nullptr;
+    auto checks = [&]() -> int {
+        if (!count || !xy || !score || !tracks || !visible) return fail(OFLK_ERR_INVALID, "NULL output argument");
+        return check_select(q, md, K);
+    };
+    auto setup = [&](HostCall &call, TrackRows &R, int) -> int {
+        int rc;
+        if ((rc = call.alloc(&R.qxy, 2 * row)) || (rc = call.alloc(&d_ws, feat_ws(nullptr, 1, H, W, md, 0).bytes)) ||
+            (rc = call.alloc(&d_cnt, 1)) || (rc = call.alloc(&d_sc, row)))
+            return rc;
+        return OFLK_OK;
+    };
+    auto pass = [&](HostCall &call, oflk_plan *p, const PIXELS *d_frames, int b0, int, TrackRows &R) -> int {
+        int rc;
+        if (b0 == 0) {
+            if ((rc = detect_launch(d_frames, sizeof(PIXELS) == 1, 1, H, W, window_size, q, md, K, feat_ws(d_ws, 1, H, W, md, 0),
+                                    d_cnt, R.qxy, d_sc, nullptr, nullptr)) ||
+                (rc = call.to_host(count, d_cnt, 1)) || (rc = call.to_host(xy, R.qxy, 2 * row)) ||
+                (rc = call.to_host(score, d_sc, row)))
+                return rc;
+        }
+        return plan_sparse_tracks(p, d_frames, sizeof(PIXELS) == 1, alpha, beta, max_residual, b0, nullptr, R.qxy, K, R.tr, R.vis,
+                                  nullptr);
+    };
+    return run_sequence_sparse<PIXELS>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, K, tracks, visible, 0,
+                                       checks, setup, pass, no_part);
+}
+
+// oflk_pyramidal_sequence_klt_sparse_replenish: K slots, one replenished sparse pass (sparse_klt_pass, t0 = the chunk's
+// first frame) per chunk; rows, born, detected and residual come down.  Residual row 0 of a later chunk is the previous
+// chunk's last row, which is already on the host.
+template <class PIXELS>
+int sequence_klt_sparse_replenish(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
+                                  float beta, float max_residual, float q, float md, int K, int detect_every, float *tracks,
+                                  unsigned char *visible, unsigned char *born, int *detected, float *residual)
+{
+    const size_t row = (size_t)K;
+    SparseKlt k{q, md, K, detect_every, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    auto checks = [&]() -> int {
+        if (!tracks || !visible || !born || !detected) return fail(OFLK_ERR_INVALID, "NULL output argument");
+        if (detect_every < 1) return fail(OFLK_ERR_INVALID, "detect_every must be >= 1 (got %d)", detect_every);
+        return check_select(q, md, K);
+    };
+    auto setup = [&](HostCall &call, TrackRows &R, int C) -> int {
+        int rc;
+        char *d_ws = nullptr;
+        if ((rc = call.alloc(&R.qxy, 2 * row)) || (rc = call.alloc(&R.qt, row)) ||
+            (rc = call.alloc(&d_ws, feat_ws(nullptr, 1, H, W, md, K).bytes)) || (rc = call.alloc(&k.born, (size_t)(C + 1) * row)) ||
+            (rc = call.alloc(&k.detected, (size_t)C + 1)) || (rc = call.alloc(&k.residual, (size_t)(C + 1) * row, residual != nullptr)))
+            return rc;
+        k.ws = d_ws; k.qt = R.qt; k.qxy = R.qxy;
+        return OFLK_OK;
+    };
+    auto pass = [&](HostCall &, oflk_plan *p, const PIXELS *d_frames, int b0, int, TrackRows &R) -> int {
+        return sparse_klt_pass(p, d_frames, sizeof(PIXELS) == 1, alpha, beta, max_residual, b0, k, R.tr, R.vis, nullptr);
+    };
+    auto extras = [&](HostCall &call, int b0, int nb, int r0) -> int {
+        const size_t nr = (size_t)(nb + 1 - r0);
+        int rc;
+        if ((rc = call.to_host(born + (size_t)(b0 + r0) * row, k.born + (size_t)r0 * row, nr * row)) ||
+            (rc = call.to_host(detected + b0 + r0, k.detected + r0, nr)))
+            return rc;
+        const int q0 = b0 > 0 ? 1 : 0;
+        return residual ? call.to_host(residual + (size_t)(b0 + q0) * row, k.residual + (size_t)q0 * row, (size_t)(nb + 1 - q0) * row)
+                        : OFLK_OK;
+    };
+    return run_sequence_sparse<PIXELS>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, K, tracks, visible,
+                                       detect_every, checks, setup, pass, extras);
 }
 }  // namespace
 
@@ -3308,6 +3472,74 @@ OFLK_API int oflk_pyramidal_sequence_sparse_tracks_u8(const unsigned char *frame
 {
     return sequence_sparse_tracks<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, qt, qxy, N,
                                                  tracks, visible);
+}
+
+OFLK_API int oflk_pyramidal_sequence_klt_sparse(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                                float alpha, float beta, float max_residual, float quality_level,
+                                                float min_distance, int max_corners, int *count, float *xy, float *score,
+                                                float *tracks, unsigned char *visible)
+{
+    return sequence_klt_sparse<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, quality_level,
+                                      min_distance, max_corners, count, xy, score, tracks, visible);
+}
+
+OFLK_API int oflk_pyramidal_sequence_klt_sparse_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size,
+                                                   int iters, float alpha, float beta, float max_residual, float quality_level,
+                                                   float min_distance, int max_corners, int *count, float *xy, float *score,
+                                                   float *tracks, unsigned char *visible)
+{
+    return sequence_klt_sparse<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, quality_level,
+                                              min_distance, max_corners, count, xy, score, tracks, visible);
+}
+
+OFLK_API int oflk_pyramidal_sequence_klt_sparse_replenish(const float *frames, int T, int H, int W, int levels, int window_size,
+                                                          int iters, float alpha, float beta, float max_residual,
+                                                          float quality_level, float min_distance, int max_corners,
+                                                          int detect_every, float *tracks, unsigned char *visible,
+                                                          unsigned char *born, int *detected, float *residual)
+{
+    return sequence_klt_sparse_replenish<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual,
+                                                quality_level, min_distance, max_corners, detect_every, tracks, visible, born,
+                                                detected, residual);
+}
+
+OFLK_API int oflk_pyramidal_sequence_klt_sparse_replenish_u8(const unsigned char *frames, int T, int H, int W, int levels,
+                                                             int window_size, int iters, float alpha, float beta,
+                                                             float max_residual, float quality_level, float min_distance,
+                                                             int max_corners, int detect_every, float *tracks,
+                                                             unsigned char *visible, unsigned char *born, int *detected,
+                                                             float *residual)
+{
+    return sequence_klt_sparse_replenish<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual,
+                                                        quality_level, min_distance, max_corners, detect_every, tracks, visible,
+                                                        born, detected, residual);
+}
+
+OFLK_API int oflk_plan_sparse_klt_replenish(oflk_plan *plan, const void *d_frames, int u8, float alpha, float beta,
+                                            float max_residual, float quality_level, float min_distance, int max_corners,
+                                            int detect_every, int t0, void *d_workspace, size_t workspace_bytes, int *d_qt,
+                                            float *d_qxy, float *d_tracks, unsigned char *d_visible, unsigned char *d_born,
+                                            int *d_detected, float *d_residual, void *stream)
+{
+    if (!plan || !d_frames) return fail(OFLK_ERR_INVALID, "NULL argument");
+    if (!d_workspace || !d_qt || !d_qxy || !d_tracks || !d_visible || !d_born || !d_detected)
+        return fail(OFLK_ERR_INVALID, "NULL workspace, slot state or output argument");
+    int rc = check_sparse_test(alpha, beta, max_residual);
+    if (rc || (rc = check_sparse_config(plan->H, plan->W, plan->L, plan->win, plan->K)) ||
+        (rc = check_select(quality_level, min_distance, max_corners)))
+        return rc;
+    if (detect_every < 1) return fail(OFLK_ERR_INVALID, "detect_every must be >= 1 (got %d)", detect_every);
+    if (t0 < 0 || t0 > INT_MAX - plan->B) return fail(OFLK_ERR_INVALID, "t0 must be in [0, INT_MAX - B] (got %d)", t0);
+    const size_t need = feat_ws(nullptr, 1, plan->H, plan->W, min_distance, max_corners).bytes;
+    if (workspace_bytes < need)
+        return fail(OFLK_ERR_INVALID, "workspace of %zu bytes, %zu needed (oflk_replenish_features_workspace)", workspace_bytes,
+                    need);
+    if (reinterpret_cast<uintptr_t>(d_workspace) % 256 != 0 || reinterpret_cast<uintptr_t>(d_qxy) % 8 != 0 ||
+        reinterpret_cast<uintptr_t>(d_tracks) % 8 != 0)
+        return fail(OFLK_ERR_INVALID, "d_workspace must be 256-byte aligned, d_qxy and d_tracks 8-byte aligned");
+    const SparseKlt k{quality_level, min_distance, max_corners, detect_every, d_workspace, d_qt, d_qxy, d_born, d_detected,
+                      d_residual};
+    return sparse_klt_pass(plan, d_frames, u8 != 0, alpha, beta, max_residual, t0, k, d_tracks, d_visible, (hipStream_t)stream);
 }
 
 OFLK_API int oflk_pyramidal_last_level_flow(int B, int H, int W, int levels, int window_size, int iters, int level,

@@ -239,10 +239,12 @@ __global__ __launch_bounds__(64) void k_sparse_lk(SparseArgs a)
 // oflk_plan_sparse_tracks: grid (N), one wave per query, looping over the launch's pairs as k_track does.  A step of an
 // alive point is the forward step, then (if it is ok) the backward step from the rounded target, the forward-backward
 // test on the two displacements (fb_finish's expressions) and the residual test.
-template <int HW, class PIX>
-__global__ __launch_bounds__(64) void k_sparse_track(SparseArgs a)
+// RES (oflk_plan_sparse_klt_replenish): step_residual [B+1][N], row r of query n = the forward step's residual of pair r - 1
+// where the point was alive on row r - 1 and that step was ok, whether or not the track survives it; NaN otherwise.  Row 0
+// is written (NaN) by the launch with t0 == 0 only: in a later launch it is the earlier launch's last row.
+template <int HW, class PIX, bool RES>
+__device__ __forceinline__ void sparse_track(const SparseArgs &a, SparseLds<HW> &m, float *step_residual)
 {
-    __shared__ SparseLds<HW> m;
     const size_t n = blockIdx.x, N = (size_t)a.N;
     const int lane = threadIdx.x;
     const int qt = a.qt ? a.qt[n] : 0;
@@ -278,9 +280,13 @@ __global__ __launch_bounds__(64) void k_sparse_track(SparseArgs a)
                     keep = s.ok && e2 <= a.alpha * m2 + a.beta && f.residual <= a.max_residual;
                 }
             }
+            if constexpr (RES)
+                if (lane == 0) step_residual[(size_t)r * N + n] = f.ok ? f.residual : nan;
             alive = keep;
             x = nx;
             y = ny;
+        } else if constexpr (RES) {
+            if (lane == 0 && (r > 0 || a.t0 == 0)) step_residual[(size_t)r * N + n] = nan;
         }
         if (r == r_q) {
             alive = q_in;
@@ -295,6 +301,30 @@ __global__ __launch_bounds__(64) void k_sparse_track(SparseArgs a)
             a.visible[i] = alive ? 1 : 0;
         }
     }
+}
+
+template <int HW, class PIX>
+__global__ __launch_bounds__(64) void k_sparse_track(SparseArgs a)
+{
+    __shared__ SparseLds<HW> m;
+    sparse_track<HW, PIX, false>(a, m, nullptr);
+}
+
+// the same with the residual rows: a kernel of its own, so that the launches without them keep their arguments and code
+template <int HW, class PIX>
+__global__ __launch_bounds__(64) void k_sparse_track_residual(SparseArgs a, float *step_residual)
+{
+    __shared__ SparseLds<HW> m;
+    sparse_track<HW, PIX, true>(a, m, step_residual);
+}
+
+// oflk_plan_sparse_klt_replenish: born [nb] and detected [nd] zeroed ahead of the pass's detections.  A launch, so that a
+// captured pass is a chain of kernels only.
+__global__ __launch_bounds__(256) void k_sparse_rows_clear(unsigned char *born, size_t nb, int *detected, size_t nd)
+{
+    const size_t first = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    for (size_t i = first; i < nb; i += stride) born[i] = 0;
+    for (size_t i = first; i < nd; i += stride) detected[i] = 0;
 }
 
 }  // namespace oflk

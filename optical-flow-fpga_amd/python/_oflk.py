@@ -86,6 +86,11 @@ SIGNATURES = {
     "oflk_plan_sparse_tracks": (ctypes.c_int, [_vp, _vp, ctypes.c_int] + [ctypes.c_float] * 3 + [ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, _vp]),
     "oflk_pyramidal_sequence_sparse_tracks": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 3 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
     "oflk_pyramidal_sequence_sparse_tracks_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 3 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
+    "oflk_pyramidal_sequence_klt_sparse": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int, _i32p, _f32p, _f32p, _f32p, _vp]),
+    "oflk_pyramidal_sequence_klt_sparse_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int, _i32p, _f32p, _f32p, _f32p, _vp]),
+    "oflk_pyramidal_sequence_klt_sparse_replenish": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 2 + [_f32p, _vp, _vp, _i32p, _f32p]),
+    "oflk_pyramidal_sequence_klt_sparse_replenish_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 2 + [_f32p, _vp, _vp, _i32p, _f32p]),
+    "oflk_plan_sparse_klt_replenish": (ctypes.c_int, [_vp, _vp, ctypes.c_int] + [ctypes.c_float] * 5 + [ctypes.c_int] * 3 + [_vp, ctypes.c_size_t] + [_vp] * 8),
     "oflk_corner_score": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_vp, _vp]),
     "oflk_corner_score_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 4 + [_f32p]),
     "oflk_corner_score_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_f32p]),
@@ -437,6 +442,22 @@ def sparse_tracks(plan: "Plan", d_frames: int, d_qxy: int, N: int, d_tracks: int
     the plan's B pairs; queries, rows and row 0 as track_points.  No flow field is computed or stored."""
     check(lib().oflk_plan_sparse_tracks(plan._h, d_frames, int(bool(u8)), float(alpha), float(beta), float(max_residual), int(t0),
                                         d_qt or None, d_qxy, int(N), d_tracks, d_visible, stream))
+
+
+def sparse_klt_replenish(plan: "Plan", d_frames: int, d_workspace: int, workspace_bytes: int, d_qt: int, d_qxy: int,
+                         d_tracks: int, d_visible: int, d_born: int, d_detected: int, max_corners: int, detect_every: int,
+                         quality_level: float = 0.01, min_distance: float = 10.0, alpha: float = 0.01, beta: float = 0.5,
+                         max_residual: float = 4.0, t0: int = 0, d_residual: int = 0, u8: bool = False, stream: int = 0) -> None:
+    """oflk_plan_sparse_klt_replenish on device pointers: d_frames [B+1][H][W] (float32, or uint8 with u8) are frames
+    t0 .. t0+B of the plan's B pairs; K = max_corners slots in d_qt [K] int32 / d_qxy [K][2]; rows into d_tracks [B+1][K][2],
+    d_visible, d_born [B+1][K] uint8, d_detected [B+1] int32 and d_residual [B+1][K] float32 (0: none).  t0 > 0 continues
+    from the previous call's d_qt, d_qxy and last row (this call's row 0).  d_workspace of at least
+    replenish_features_workspace bytes."""
+    check(lib().oflk_plan_sparse_klt_replenish(plan._h, d_frames, int(bool(u8)), float(alpha), float(beta), float(max_residual),
+                                               float(quality_level), float(min_distance), int(max_corners), int(detect_every),
+                                               int(t0), d_workspace or None, int(workspace_bytes), d_qt or None, d_qxy or None,
+                                               d_tracks or None, d_visible or None, d_born or None, d_detected or None,
+                                               d_residual or None, stream))
 
 
 def check_feature_params(max_corners, quality_level: float, min_distance: float, window_size: int) -> Tuple[int, float, float, int]:

@@ -30,7 +30,7 @@ import numpy as np
 import numpy.typing as npt
 
 import _oflk
-from lucas_kanade_core import good_features_to_track, lucas_kanade_single_scale
+from lucas_kanade_core import lucas_kanade_single_scale
 
 SCRIPT_DIR = Path(__file__).resolve().parent
 PROJECT_ROOT = SCRIPT_DIR.parent
@@ -369,16 +369,22 @@ def lucas_kanade_pyramidal_sequence_klt_sparse(frames, max_corners: int, quality
                                                num_levels: int = 3, window_size: int = 5, num_iterations: int = 3,
                                                alpha: float = 0.01, beta: float = 0.5, max_residual: float = 4.0) -> SequenceKLT:
     """Detect, then track, sparsely: good_features_to_track on frame 0 (the LK window is the detection window), then
-    lucas_kanade_pyramidal_sequence_sparse_tracks on those points.  The features make one round trip through the host (at
-    most max_corners points).  Result as lucas_kanade_pyramidal_sequence_klt."""
+    lucas_kanade_pyramidal_sequence_sparse_tracks on those points, in one call: the features are born on the device,
+    straight into the tracker's query buffer.  Result as lucas_kanade_pyramidal_sequence_klt."""
     a, b = _oflk.check_fb_params(alpha, beta)
-    arr, _ = _oflk.as_sequence(frames)
-    _oflk.check_sparse_params(arr.shape[1:], num_levels, window_size, num_iterations, max_residual)
-    xy, _ = good_features_to_track(arr[0], max_corners, quality_level, min_distance, window_size)
-    if xy.shape[0] == 0:
-        return SequenceKLT(xy, np.empty((arr.shape[0], 0, 2), np.float32), np.empty((arr.shape[0], 0), bool))
-    r = lucas_kanade_pyramidal_sequence_sparse_tracks(arr, xy, num_levels, window_size, num_iterations, a, b, max_residual)
-    return SequenceKLT(xy, r.tracks, r.visible)
+    arr, u8 = _oflk.as_sequence(frames)
+    T, H, W = arr.shape
+    L, win, it, r = _oflk.check_sparse_params((H, W), num_levels, window_size, num_iterations, max_residual)
+    K, q, md, win = _oflk.check_feature_params(max_corners, quality_level, min_distance, win)
+    count = np.zeros(1, np.int32)
+    xy, score = np.empty((K, 2), np.float32), np.empty(K, np.float32)
+    tracks, visible = np.empty((T, K, 2), np.float32), np.empty((T, K), np.uint8)
+    fn = _oflk.lib().oflk_pyramidal_sequence_klt_sparse_u8 if u8 else _oflk.lib().oflk_pyramidal_sequence_klt_sparse
+    src = arr.ctypes.data if u8 else _oflk.ptr(arr)
+    _oflk.check(fn(src, T, H, W, L, win, it, a, b, r, q, md, K, count.ctypes.data_as(_oflk._i32p), _oflk.ptr(xy),
+                   _oflk.ptr(score), _oflk.ptr(tracks), visible.ctypes.data))
+    n = int(count[0])
+    return SequenceKLT(xy[:n], tracks[:, :n], visible[:, :n].astype(bool))
 
 
 class SequenceKLTReplenish(NamedTuple):
@@ -413,6 +419,44 @@ def lucas_kanade_pyramidal_sequence_klt_replenish(frames, max_corners: int, dete
     _oflk.check(fn(src, T, H, W, int(num_levels), win, int(num_iterations), a, b, q, md, K, min(int(detect_every), 2 ** 31 - 1),
                    _oflk.ptr(tracks), visible.ctypes.data, born.ctypes.data, detected.ctypes.data_as(_oflk._i32p)))
     return SequenceKLTReplenish(tracks, visible.astype(bool), born.astype(bool), detected)
+
+
+class SequenceKLTSparseReplenish(NamedTuple):
+    """Result of lucas_kanade_pyramidal_sequence_klt_sparse_replenish: SequenceKLTReplenish's fields and the steps' residuals."""
+    tracks: np.ndarray     # (T, K, 2) float32 (x, y); NaN where not visible
+    visible: np.ndarray    # (T, K) bool
+    born: np.ndarray       # (T, K) bool: a new track begins in this slot on this frame
+    detected: np.ndarray   # (T,) int32: points born on each frame
+    residual: np.ndarray   # (T, K) float32: the forward residual of the step into row t of a slot alive on row t-1; else NaN
+
+
+def lucas_kanade_pyramidal_sequence_klt_sparse_replenish(frames, max_corners: int, detect_every: int,
+                                                         quality_level: float = 0.01, min_distance: float = 10.0,
+                                                         num_levels: int = 3, window_size: int = 5, num_iterations: int = 3,
+                                                         alpha: float = 0.01, beta: float = 0.5,
+                                                         max_residual: float = 4.0) -> SequenceKLTSparseReplenish:
+    """lucas_kanade_pyramidal_sequence_klt_replenish on the sparse tracker: max_corners slots, a detection on every
+    detect_every-th frame away from the live tracks, and between them the steps of
+    lucas_kanade_pyramidal_sequence_sparse_tracks -- no flow field anywhere.  residual[t, n] is the forward step's mean
+    absolute window difference (what max_residual is compared with) for every slot that was alive on frame t-1 and whose
+    forward step succeeded, also where the track ends on that step; NaN elsewhere.  lucas_kanade_core.split_tracks(visible,
+    born) lists the tracks.  Frames go up; the rows come down."""
+    a, b = _oflk.check_fb_params(alpha, beta)
+    arr, u8 = _oflk.as_sequence(frames)
+    T, H, W = arr.shape
+    L, win, it, r = _oflk.check_sparse_params((H, W), num_levels, window_size, num_iterations, max_residual)
+    K, q, md, win = _oflk.check_feature_params(max_corners, quality_level, min_distance, win)
+    if isinstance(detect_every, bool) or int(detect_every) != detect_every or int(detect_every) < 1:
+        raise ValueError(f"detect_every must be an integer >= 1, got {detect_every!r}")
+    tracks, visible = np.empty((T, K, 2), np.float32), np.empty((T, K), np.uint8)
+    born, detected = np.empty((T, K), np.uint8), np.empty(T, np.int32)
+    residual = np.empty((T, K), np.float32)
+    fn = (_oflk.lib().oflk_pyramidal_sequence_klt_sparse_replenish_u8 if u8
+          else _oflk.lib().oflk_pyramidal_sequence_klt_sparse_replenish)
+    src = arr.ctypes.data if u8 else _oflk.ptr(arr)
+    _oflk.check(fn(src, T, H, W, L, win, it, a, b, r, q, md, K, min(int(detect_every), 2 ** 31 - 1), _oflk.ptr(tracks),
+                   visible.ctypes.data, born.ctypes.data, detected.ctypes.data_as(_oflk._i32p), _oflk.ptr(residual)))
+    return SequenceKLTSparseReplenish(tracks, visible.astype(bool), born.astype(bool), detected, residual)
 
 
 def _dump_levels(key, shapes, u, v) -> None:

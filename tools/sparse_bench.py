@@ -13,7 +13,15 @@ plan's workspace as oflk_plan_workspace_bytes reports it for a plan of the chunk
 the call's own frame, flow and row buffers, computed from the shapes).  Kernel times come from a separate run under
 `rocprofv3 --kernel-trace --stats` (--only sparse keeps the trace short).
 
-    python tools/sparse_bench.py [--frames 129] [--steps 5] [--warmup 1] [--only sparse|dense]
+--replenish times the replenished KLT instead, on the same frames: K = max_corners in (1 000, 10 000) and detect_every in
+(1, 4, 16), alternating which goes first:
+  (a) oflk_pyramidal_sequence_klt_replenish_u8         dense flows, track kernel, detections
+  (b) oflk_pyramidal_sequence_klt_sparse_replenish_u8  pyramids, one sparse track launch per segment, detections
+One JSON line per (K, detect_every): ms per call (median, min, max), the points detected and the share of slots alive on the
+last frame for both.  --only sparse under rocprofv3 gives the split into pyramid, track and detection kernels.
+
+    python tools/sparse_bench.py [--frames 129] [--steps 5] [--warmup 1] [--only sparse|dense] [--replenish]
+                                 [--budgets 1000,10000] [--every 1,4,16]
 """
 import argparse
 import json
@@ -52,6 +60,53 @@ def plan_bytes(C, H, W, sparse):
         plan.close()
 
 
+def replenish_leg(args, frames, forms, steps):
+    """the replenished KLT, dense against sparse, host to host"""
+    import numpy as np
+
+    import _oflk
+
+    L = _oflk.lib()
+    T, H, W = frames.shape
+    for K, md in zip(args.budgets, (10.0, 4.0) if len(args.budgets) == 2 else [4.0] * len(args.budgets)):
+        for D in args.every:
+            out = {f: (np.empty((T, K, 2), np.float32), np.empty((T, K), np.uint8), np.empty((T, K), np.uint8), np.empty(T, np.int32))
+                   for f in forms}
+            res = np.empty((T, K), np.float32)
+
+            def call(form):
+                tr, vis, born, det = out[form]
+                if form == "dense":
+                    _oflk.check(L.oflk_pyramidal_sequence_klt_replenish_u8(frames.ctypes.data, T, H, W, 3, 5, 3, 0.01, 0.5, 0.01, md, K,
+                                                                           D, _oflk.ptr(tr), vis.ctypes.data, born.ctypes.data,
+                                                                           det.ctypes.data_as(_oflk._i32p)))
+                else:
+                    _oflk.check(L.oflk_pyramidal_sequence_klt_sparse_replenish_u8(frames.ctypes.data, T, H, W, 3, 5, 3, 0.01, 0.5, 4.0,
+                                                                                  0.01, md, K, D, _oflk.ptr(tr), vis.ctypes.data,
+                                                                                  born.ctypes.data, det.ctypes.data_as(_oflk._i32p),
+                                                                                  _oflk.ptr(res)))
+
+            for _ in range(args.warmup):
+                for f in forms:
+                    call(f)
+            ms = {f: [] for f in forms}
+            for i in range(steps):
+                for f in (forms if i % 2 == 0 else forms[::-1]):
+                    t0 = time.perf_counter()
+                    call(f)
+                    ms[f].append((time.perf_counter() - t0) * 1e3)
+            line = {"tool": "sparse_bench", "leg": "replenish", "pixels": "u8", "frames": T, "height": H, "width": W, "levels": 3,
+                    "window": 5, "iters": 3, "steps": steps, "K": K, "min_distance": md, "detect_every": D}
+            for f in forms:
+                line[f"{f}_ms"] = round(statistics.median(ms[f]), 3)
+                line[f"{f}_ms_min_max"] = [round(min(ms[f]), 3), round(max(ms[f]), 3)]
+                line[f"{f}_detected"] = int(out[f][3].sum())
+                line[f"{f}_alive_last"] = round(float(out[f][1][-1].mean()), 4)
+            if len(forms) == 2:
+                line["speedup"] = round(line["dense_ms"] / line["sparse_ms"], 3)
+            print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=129)
@@ -61,6 +116,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--only", choices=["sparse", "dense"], default=None)
+    ap.add_argument("--replenish", action="store_true", help="time the replenished KLT calls instead of the plain tracks")
+    ap.add_argument("--budgets", type=lambda v: [int(x) for x in v.split(",")], default=[1000, 10000], help="--replenish: max_corners")
+    ap.add_argument("--every", type=lambda v: [int(x) for x in v.split(",")], default=[1, 4, 16], help="--replenish: detect_every")
     args = ap.parse_args()
     steps = max(1, min(args.steps, 20))
     import numpy as np
@@ -80,6 +138,9 @@ def main():
         frames[t] = np.rint(np.clip(f, 0.0, 255.0)).astype(np.uint8)
     L = _oflk.lib()
     forms = [f for f in ("dense", "sparse") if args.only in (None, f)]
+    if args.replenish:
+        replenish_leg(args, frames, forms, steps)
+        return
     # chunk sizes of the two host calls at this frame size (chunk_pairs / sparse_chunk_pairs in oflk.hip)
     c_dense = max(1, (32 << 20) // (H * W * 4))
     c_dense = c_dense if B >= 4 * c_dense and B * H * W * 4 >= (64 << 20) else B

@@ -421,6 +421,67 @@ int oflk_pyramidal_sequence_klt_sparse_replenish_u8(const unsigned char *frames,
                                                     float *tracks, unsigned char *visible, unsigned char *born, int *detected,
                                                     float *residual /* [T][K], may be NULL */);
 
+/* ---- online sparse KLT tracker: frames pushed one at a time ------------------------------------------------------------ */
+/* The statement (tests/tracker_model.py): the sparse-replenish statement above for video that arrives frame by frame and
+ * has no known end.  A tracker keeps K = max_corners slots on the device (every slot dead at first) and takes one frame
+ * per push.  D = detect_every >= 0.  Push of frame t (t = 0, 1, ...):
+ *   step (t > 0):  every alive slot takes the step of pair t-1 of the sparse-replenish statement, unchanged: forward,
+ *                  backward, the forward-backward test, r <= max_residual, the position f32(q), residual[n] as there
+ *   detect (D > 0 and t % D == 0):  the detection of that statement on frame t with the rows after the step -- now, not when
+ *                  the next frame arrives: a tracker knows no last frame, so that statement's t < T-1 falls away
+ *   row t:         xy[n] = the position, or (NaN, NaN);  visible[n];  born[n] = 1 where a track began in slot n on this frame;
+ *                  birth[n] = the index of the frame on which the slot's current track began (defined where visible[n]);
+ *                  residual[n], all NaN on frame 0;  detected = the points accepted on this frame
+ * So the rows of T pushes are rows 0 .. T-1 of oflk_pyramidal_sequence_klt_sparse_replenish on those frames followed by any
+ * one more frame, byte for byte.  With D = 0 nothing is ever detected.
+ * oflk_tracker_add_points after the push of frame t: points that are not finite or lie outside [0, W-1] x [0, H-1] are dropped
+ * on the host; the i-th remaining point goes to the i-th dead slot, ascending, while dead slots last, and the rest are
+ * dropped.  Such a slot gets position (x + 0, y + 0), visible = 1, born = 1, birth = t; a later read_row shows it, and from
+ * the next push on it is an ordinary track that seeds later detections like any other.  With D = 0 a slot's track equals
+ * the track of the query (t, x, y) in oflk_pyramidal_sequence_sparse_tracks.
+ *
+ * State: a ring of two frames in the input pixel type, their two pyramids, two rows, birth / the detection's queries / born /
+ * residual / detected, the points of add_points and the oflk_replenish_features workspace of one frame.  Every pyramid step
+ * runs the fused kernel, which at the pyramid's scale of 0.5 fits every admissible frame (a step that does not cannot occur at
+ * that scale), so there are no blur temporaries and no float32 copy of uint8 frames.  Creation checks the configuration and
+ * makes no device call; the first push allocates all of it, no later push allocates.  A push is enqueued from host-side state
+ * -- the ring slot t & 1, the birth index t, whether t % D == 0 -- so a captured push replayed would repeat one frame's role:
+ * pushes are not made for graph capture.  A push copies the frame into the free ring slot, builds that one frame's pyramid
+ * (the previous frame's is kept), and runs one launch for the step of all slots; a detecting push adds the seven launches of a
+ * detection and one that completes the rows of the newborn.  A push that fails part-way leaves the frame index and the
+ * previous row as they were, and every later push is refused with OFLK_ERR_INVALID until oflk_tracker_reset.
+ * A tracker is single-stream, like a plan: every call on it is ordered by the caller.
+ * Refusals, before any device call: everything oflk_pyramidal_sequence_klt_sparse_replenish refuses about shape, window,
+ * levels, iterations, alpha, beta, max_residual, quality_level, min_distance and max_corners, with its codes;
+ * detect_every < 0: OFLK_ERR_INVALID;  row_device / read_row / add_points before the first push, n < 1 or a NULL tracker,
+ * frame or points: OFLK_ERR_INVALID;  a push after frame index 2^31 - 2: OFLK_ERR_UNSUPPORTED (oflk_tracker_reset starts
+ * again at frame 0). */
+typedef struct oflk_tracker oflk_tracker;
+int oflk_tracker_create(oflk_tracker **tr, int device, int H, int W, int u8, int levels, int window_size, int iters,
+                        float alpha, float beta, float max_residual, float quality_level, float min_distance,
+                        int max_corners /* K slots */, int detect_every /* D >= 1; 0: never detect */);
+int oflk_tracker_destroy(oflk_tracker *tr);
+int oflk_tracker_reset(oflk_tracker *tr, void *stream);      /* every slot dead, next push is frame 0 */
+size_t oflk_tracker_workspace_bytes(const oflk_tracker *tr); /* what is allocated at the moment (0 before the first push) */
+int oflk_tracker_frame_index(const oflk_tracker *tr);        /* index of the last pushed frame, -1 before the first */
+/* device frame [H][W] (uint8 when created with u8); asynchronous on `stream`, no host synchronisation */
+int oflk_tracker_push_device(oflk_tracker *tr, const void *d_frame, void *stream);
+/* device pointers to the row of the last pushed frame (each may be NULL), valid until the next push / add / reset:
+ * xy [K][2], visible [K], born [K], birth [K], residual [K], detected [1] */
+int oflk_tracker_row_device(const oflk_tracker *tr, const float **d_xy, const unsigned char **d_visible,
+                            const unsigned char **d_born, const int **d_birth, const float **d_residual,
+                            const int **d_detected);
+/* copy that row to host arrays (each may be NULL); synchronises `stream` */
+int oflk_tracker_read_row(oflk_tracker *tr, float *xy, unsigned char *visible, unsigned char *born, int *birth,
+                          float *residual, int *detected, void *stream);
+/* host frame in, the row out: push_device + read_row on the null stream, the frame copied straight into the ring;
+ * synchronous */
+int oflk_tracker_push(oflk_tracker *tr, const void *frame, float *xy, unsigned char *visible, unsigned char *born,
+                      int *birth, float *residual, int *detected);
+/* n host points (x, y) start tracks on the last pushed frame, in the dead slots, ascending; the points are on the device
+ * when the call returns (it synchronises `stream` once), the slots are filled in stream order */
+int oflk_tracker_add_points(oflk_tracker *tr, const float *pts, int n, void *stream);
+
 /* Rehearsal of the chunk queue above on a box with fewer GPUs than workers (tests): `workers` > 0 makes the *_multi entry
  * points run that many queue workers, worker i on device i % n_gpus (workers of one device take turns on it); 0 restores
  * one worker per device.  Results do not change. */

@@ -9,6 +9,7 @@
 #include "oflk_kernels.hpp"
 #include "oflk_stream.hpp"
 #include "oflk_sparse.hpp"
+#include "oflk_tracker.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -3540,6 +3541,322 @@ OFLK_API int oflk_plan_sparse_klt_replenish(oflk_plan *plan, const void *d_frame
     const SparseKlt k{quality_level, min_distance, max_corners, detect_every, d_workspace, d_qt, d_qxy, d_born, d_detected,
                       d_residual};
     return sparse_klt_pass(plan, d_frames, u8 != 0, alpha, beta, max_residual, t0, k, d_tracks, d_visible, (hipStream_t)stream);
+}
+
+// =============================================================================
+// online sparse KLT tracker: one frame per push
+// =============================================================================
+// The state of a tracker.  Creation checks and records the configuration and makes no device call; the first push
+// allocates everything (ensure_state), and no later push allocates.  Frame t lives in ring slot t & 1, and so do its
+// pyramid levels and its row.
+struct oflk_tracker {
+    int device = 0, H = 0, W = 0, L = 0, win = 0, hw = 0, iters = 0, K = 0, every = 0;
+    bool u8 = false;
+    float alpha = 0, beta = 0, max_residual = 0, q = 0, md = 0;
+    int dims[2 * OFLK_MAX_LEVELS] = {0};
+    GaussW gauss;
+    long long t = -1;                 // index of the last pushed frame
+    bool ready = false;               // the device state exists
+    bool failed = false;              // a push failed part-way: pushes are refused until reset
+    size_t ws_bytes = 0;
+    void *ring = nullptr;             // [2][H][W], the input pixel type
+    float *pyr[OFLK_MAX_LEVELS] = {nullptr};   // l < L-1: [2][h_l][w_l]
+    float *xy = nullptr;              // [2][K][2]
+    unsigned char *vis = nullptr;     // [2][K]
+    int *qt = nullptr;                // [K]: birth
+    float *qxy = nullptr, *pts = nullptr;   // [K][2] the detection's queries; the points of add_points
+    unsigned char *born = nullptr;    // [K]
+    float *residual = nullptr;        // [K]
+    int *detected = nullptr;          // [1]
+    char *feat = nullptr;             // the oflk_replenish_features workspace of one frame
+
+    size_t npix(int l) const { return (size_t)dims[2 * l] * (size_t)dims[2 * l + 1]; }
+    size_t pix_bytes() const { return u8 ? 1 : sizeof(float); }
+    float *row_xy(long long f) const { return xy + (size_t)(f & 1) * 2 * (size_t)K; }
+    unsigned char *row_vis(long long f) const { return vis + (size_t)(f & 1) * (size_t)K; }
+    char *frame(long long f) const { return static_cast<char *>(ring) + (size_t)(f & 1) * (size_t)H * W * pix_bytes(); }
+};
+
+namespace {
+void tracker_free(oflk_tracker *tr)
+{
+    if (!tr) return;
+    if (tr->ready || tr->ws_bytes) (void)hipSetDevice(tr->device);
+    for (float *q : tr->pyr)
+        if (q) (void)hipFree(q);
+    for (void *q : {(void *)tr->ring, (void *)tr->xy, (void *)tr->vis, (void *)tr->qt, (void *)tr->qxy, (void *)tr->pts, (void *)tr->born,
+                    (void *)tr->residual, (void *)tr->detected, (void *)tr->feat})
+        if (q) (void)hipFree(q);
+    delete tr;
+}
+
+// the device state, on the first push
+int tracker_ensure_state(oflk_tracker *tr)
+{
+    int rc = ensure_device(tr->device);
+    if (rc || tr->ready) return rc;
+    if (tr->ws_bytes) return fail(OFLK_ERR_NOMEM, "the tracker's state could not be allocated by an earlier push");
+    const size_t plane = (size_t)tr->H * tr->W, row = (size_t)tr->K;
+    unsigned char *ring = nullptr;
+    if ((rc = dmalloc(&ring, 2 * plane * tr->pix_bytes(), &tr->ws_bytes))) return rc;
+    tr->ring = ring;
+    for (int l = 0; l < tr->L - 1; l++)
+        if ((rc = dmalloc(&tr->pyr[l], 2 * tr->npix(l), &tr->ws_bytes))) return rc;
+    if ((rc = dmalloc(&tr->xy, 2 * 2 * row, &tr->ws_bytes)) || (rc = dmalloc(&tr->vis, 2 * row, &tr->ws_bytes)) ||
+        (rc = dmalloc(&tr->qt, row, &tr->ws_bytes)) || (rc = dmalloc(&tr->qxy, 2 * row, &tr->ws_bytes)) ||
+        (rc = dmalloc(&tr->pts, 2 * row, &tr->ws_bytes)) || (rc = dmalloc(&tr->born, row, &tr->ws_bytes)) ||
+        (rc = dmalloc(&tr->residual, row, &tr->ws_bytes)) || (rc = dmalloc(&tr->detected, 1, &tr->ws_bytes)) ||
+        (rc = dmalloc(&tr->feat, feat_ws(nullptr, 1, tr->H, tr->W, tr->md, tr->K).bytes, &tr->ws_bytes)))
+        return rc;
+    tr->ready = true;
+    return OFLK_OK;
+}
+
+// the kernel arguments that describe the ring (sparse_pyramids' for a plan)
+SparseArgs tracker_args(const oflk_tracker *tr)
+{
+    SparseArgs a{};
+    a.frames = tr->ring;
+    a.L = tr->L; a.K = tr->iters; a.B = 1; a.H = tr->H; a.W = tr->W; a.N = tr->K;
+    for (int l = 0; l < tr->L; l++) {
+        a.pyr[l] = tr->pyr[l];
+        a.dims[2 * l] = tr->dims[2 * l];
+        a.dims[2 * l + 1] = tr->dims[2 * l + 1];
+        if (l > 0) {   // upsample_args' ratios
+            a.sx[l] = (float)((double)tr->dims[2 * l + 1] / (double)tr->dims[2 * l - 1]);
+            a.sy[l] = (float)((double)tr->dims[2 * l] / (double)tr->dims[2 * l - 2]);
+        }
+    }
+    a.alpha = tr->alpha; a.beta = tr->beta; a.max_residual = tr->max_residual;
+    return a;
+}
+
+int tracker_newborn(const oflk_tracker *tr, long long t, const float *qxy, const int *free, const int *nfree, int n, hipStream_t s)
+{
+    NewbornArgs b{};
+    b.row = reinterpret_cast<float2 *>(tr->row_xy(t));
+    b.visible = tr->row_vis(t);
+    b.born = tr->born; b.qt = tr->qt;
+    b.qxy = reinterpret_cast<const float2 *>(qxy);
+    b.free = free; b.nfree = nfree;
+    b.n = n; b.K = tr->K; b.t = (int)t;
+    const int threads = free ? std::min(n, tr->K) : tr->K;
+    hipLaunchKernelGGL(k_tracker_newborn, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, b);
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+
+// One push: the frame (host or device memory) into the free ring slot, that one frame's pyramid into the same slot
+// (launch_pyr_down on one image; the previous frame's is kept), the step of every alive slot (k_sparse_push) and, on a
+// detection frame, detect_launch on the new row and the rows of the newborn.  All on stream s; nothing is synchronized.
+// A push that fails leaves the frame index where it was, but the free ring slot, its pyramid and the other row may have
+// been written: the previous row stays readable, and tracker_push refuses further pushes until the tracker is reset.
+int tracker_enqueue(oflk_tracker *tr, const void *src, hipMemcpyKind kind, hipStream_t s)
+{
+    int rc = OFLK_OK;
+    const long long t = tr->t + 1;
+    const int c = (int)(t & 1);
+    const size_t plane = (size_t)tr->H * tr->W;
+    char *frame = tr->frame(t);
+    HIP_TRY(hipMemcpyAsync(frame, src, plane * tr->pix_bytes(), kind, s));
+    if (tr->L > 1) {
+        const float *in = reinterpret_cast<const float *>(frame);
+        PyrExtra first;
+        first.u8 = tr->u8;
+        for (int l = tr->L - 2; l >= 0; l--) {   // every step is the fused kernel's (oflk_tracker_create), so no temporaries
+            float *out = tr->pyr[l] + (size_t)c * tr->npix(l);
+            if ((rc = launch_pyr_down(nullptr, tr->gauss, s, in, out, nullptr, nullptr, 1, tr->dims[2 * (l + 1)], tr->dims[2 * (l + 1) + 1],
+                                      tr->dims[2 * l], tr->dims[2 * l + 1], l == tr->L - 2 ? &first : nullptr)))
+                return rc;
+            in = out;
+        }
+    }
+    const SparseArgs a = tracker_args(tr);
+    PushArgs r{};
+    if (t > 0) {
+        r.xy_in = tr->row_xy(t - 1);
+        r.vis_in = tr->row_vis(t - 1);
+    }
+    r.xy_out = tr->row_xy(t); r.vis_out = tr->row_vis(t);
+    r.residual = tr->residual; r.born = tr->born; r.detected = tr->detected;
+    r.ib = c;
+    const bool built = with_half_window(tr->hw, [&](auto HW) {
+        with_pix(tr->u8, [&](auto PIX) {
+            hipLaunchKernelGGL((k_sparse_push<decltype(HW)::value, typename decltype(PIX)::type>), dim3((unsigned)tr->K), dim3(64), 0, s, a, r);
+        });
+    });
+    if (!built) return fail(OFLK_ERR_UNSUPPORTED, "half window %d not built", tr->hw);
+    HIP_TRY(hipGetLastError());
+    if (tr->every > 0 && t % tr->every == 0) {
+        const SlotSide slots{tr->row_xy(t), tr->row_vis(t), tr->qt, tr->born, tr->detected, (int)t};
+        if ((rc = detect_launch(frame, tr->u8, 1, tr->H, tr->W, tr->win, tr->q, tr->md, tr->K,
+                                feat_ws(tr->feat, 1, tr->H, tr->W, tr->md, tr->K), nullptr, tr->qxy, nullptr, &slots, s)) ||
+            (rc = tracker_newborn(tr, t, tr->qxy, nullptr, nullptr, 0, s)))
+            return rc;
+    }
+    tr->t = t;   // only a push whose every launch was accepted counts
+    return OFLK_OK;
+}
+
+int tracker_push(oflk_tracker *tr, const void *src, hipMemcpyKind kind, hipStream_t s)
+{
+    if (!tr || !src) return fail(OFLK_ERR_INVALID, "NULL argument");
+    if (tr->failed) return fail(OFLK_ERR_INVALID, "an earlier push failed part-way: reset the tracker before it is pushed again");
+    if (tr->t >= (long long)INT_MAX - 1)
+        return fail(OFLK_ERR_UNSUPPORTED, "frame index %lld is the last one a tracker takes (reset it)", tr->t);
+    int rc = tracker_ensure_state(tr);   // a refusal here has written nothing
+    if (rc) return rc;
+    if ((rc = tracker_enqueue(tr, src, kind, s))) tr->failed = true;
+    return rc;
+}
+
+// add_points' host side: the points inside [0, W-1] x [0, H-1] (float32 compares, as the kernels'; NaN: outside) in their
+// order, at most one per slot
+std::vector<float> tracker_filter_points(const oflk_tracker *tr, const float *pts, int n)
+{
+    std::vector<float> keep;
+    const float xmax = (float)(tr->W - 1), ymax = (float)(tr->H - 1);
+    for (int i = 0; i < n && keep.size() < 2 * (size_t)tr->K; i++) {
+        const float x = pts[2 * (size_t)i], y = pts[2 * (size_t)i + 1];
+        if (x >= 0.0f && x <= xmax && y >= 0.0f && y <= ymax) {
+            keep.push_back(x);
+            keep.push_back(y);
+        }
+    }
+    return keep;
+}
+
+// the frame sizes a plan takes (oflk_plan_create's bounds, which the sequence call meets there)
+int check_frame_size(int H, int W)
+{
+    if (H < 1 || W < 1) return fail(OFLK_ERR_INVALID, "H and W must be >= 1 (got %d x %d)", H, W);
+    if ((size_t)H * (size_t)W >= ((size_t)1 << 29)) return fail(OFLK_ERR_UNSUPPORTED, "frames of 2^29 pixels or more are not supported");
+    if (H >= kMaxDim || W >= kMaxDim)
+        return fail(OFLK_ERR_UNSUPPORTED, "frames of 2^23 rows or columns or more are not supported (got %d x %d)", H, W);
+    return OFLK_OK;
+}
+
+int tracker_pushed(const oflk_tracker *tr)
+{
+    if (!tr) return fail(OFLK_ERR_INVALID, "NULL tracker");
+    if (tr->t < 0) return fail(OFLK_ERR_INVALID, "no frame has been pushed yet");
+    return OFLK_OK;
+}
+}  // namespace
+
+OFLK_API int oflk_tracker_create(oflk_tracker **out, int device, int H, int W, int u8, int levels, int window_size, int iters,
+                                 float alpha, float beta, float max_residual, float quality_level, float min_distance,
+                                 int max_corners, int detect_every)
+{
+    if (!out) return fail(OFLK_ERR_INVALID, "tracker pointer is NULL");
+    *out = nullptr;
+    int rc = check_frame_size(H, W);
+    if (rc || (rc = check_sparse_test(alpha, beta, max_residual)) || (rc = check_sparse_config(H, W, levels, window_size, iters)) ||
+        (rc = check_select(quality_level, min_distance, max_corners)))
+        return rc;
+    if (detect_every < 0) return fail(OFLK_ERR_INVALID, "detect_every must be >= 0 (0: never detect; got %d)", detect_every);
+    if (device < 0 || device >= kMaxDevices) return fail(OFLK_ERR_INVALID, "device %d out of range", device);
+    oflk_tracker *tr = new oflk_tracker();
+    tr->device = device; tr->H = H; tr->W = W; tr->L = levels; tr->win = window_size; tr->hw = window_size / 2; tr->iters = iters;
+    tr->K = max_corners; tr->every = detect_every; tr->u8 = u8 != 0;
+    tr->alpha = alpha; tr->beta = beta; tr->max_residual = max_residual; tr->q = quality_level; tr->md = min_distance;
+    if ((rc = level_dims(H, W, levels, 0.5, tr->dims)) || (rc = make_gauss(2.0, &tr->gauss))) {
+        delete tr;
+        return rc;
+    }
+    // At the pyramid's scale of 0.5 every step fits the fused kernel: a finer size is 2m or 2m + 1 for the coarser m, so a 32 x
+    // 16 coarse tile spans at most 66 x 34 source elements.  The tracker therefore holds neither the unfused chain's
+    // temporaries nor a float32 stage for uint8 frames, and this guard cannot fire at that scale; it is here so that
+    // launch_pyr_down below is never handed NULL temporaries it would use
+    for (int l = levels - 2; l >= 0; l--)
+        if (!pyr_fused_fits(tr->dims[2 * (l + 1)], tr->dims[2 * (l + 1) + 1], tr->dims[2 * l], tr->dims[2 * l + 1], tr->gauss)) {
+            delete tr;
+            return fail(OFLK_ERR_UNSUPPORTED, "pyramid level %d of %dx%d does not fit the fused pyramid kernel", l, W, H);
+        }
+    *out = tr;
+    return OFLK_OK;
+}
+
+OFLK_API int oflk_tracker_destroy(oflk_tracker *tr)
+{
+    tracker_free(tr);
+    return OFLK_OK;
+}
+
+OFLK_API int oflk_tracker_reset(oflk_tracker *tr, void *)
+{
+    if (!tr) return fail(OFLK_ERR_INVALID, "NULL tracker");
+    tr->t = -1;   // frame 0's push reads no row: every slot is dead
+    tr->failed = false;
+    return OFLK_OK;
+}
+
+OFLK_API size_t oflk_tracker_workspace_bytes(const oflk_tracker *tr) { return tr ? tr->ws_bytes : 0; }
+
+OFLK_API int oflk_tracker_frame_index(const oflk_tracker *tr) { return tr ? (int)tr->t : -1; }
+
+OFLK_API int oflk_tracker_push_device(oflk_tracker *tr, const void *d_frame, void *stream)
+{
+    return tracker_push(tr, d_frame, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_tracker_row_device(const oflk_tracker *tr, const float **d_xy, const unsigned char **d_visible,
+                                     const unsigned char **d_born, const int **d_birth, const float **d_residual,
+                                     const int **d_detected)
+{
+    if (int rc = tracker_pushed(tr)) return rc;
+    if (d_xy) *d_xy = tr->row_xy(tr->t);
+    if (d_visible) *d_visible = tr->row_vis(tr->t);
+    if (d_born) *d_born = tr->born;
+    if (d_birth) *d_birth = tr->qt;
+    if (d_residual) *d_residual = tr->residual;
+    if (d_detected) *d_detected = tr->detected;
+    return OFLK_OK;
+}
+
+OFLK_API int oflk_tracker_read_row(oflk_tracker *tr, float *xy, unsigned char *visible, unsigned char *born, int *birth,
+                                   float *residual, int *detected, void *stream)
+{
+    if (int rc = tracker_pushed(tr)) return rc;
+    HIP_TRY(hipSetDevice(tr->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t row = (size_t)tr->K;
+    if (xy) HIP_TRY(hipMemcpyAsync(xy, tr->row_xy(tr->t), 2 * row * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (visible) HIP_TRY(hipMemcpyAsync(visible, tr->row_vis(tr->t), row, hipMemcpyDeviceToHost, s));
+    if (born) HIP_TRY(hipMemcpyAsync(born, tr->born, row, hipMemcpyDeviceToHost, s));
+    if (birth) HIP_TRY(hipMemcpyAsync(birth, tr->qt, row * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (residual) HIP_TRY(hipMemcpyAsync(residual, tr->residual, row * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (detected) HIP_TRY(hipMemcpyAsync(detected, tr->detected, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return OFLK_OK;
+}
+
+OFLK_API int oflk_tracker_push(oflk_tracker *tr, const void *frame, float *xy, unsigned char *visible, unsigned char *born,
+                               int *birth, float *residual, int *detected)
+{
+    int rc = tracker_push(tr, frame, hipMemcpyHostToDevice, nullptr);
+    if (rc) {
+        if (tr && tr->ready) (void)hipStreamSynchronize(nullptr);   // a copy from the caller's frame may be queued
+        return rc;
+    }
+    return oflk_tracker_read_row(tr, xy, visible, born, birth, residual, detected, nullptr);
+}
+
+OFLK_API int oflk_tracker_add_points(oflk_tracker *tr, const float *pts, int n, void *stream)
+{
+    if (int rc = tracker_pushed(tr)) return rc;
+    if (!pts) return fail(OFLK_ERR_INVALID, "NULL points");
+    if (n < 1) return fail(OFLK_ERR_INVALID, "n must be >= 1 (got %d)", n);
+    const std::vector<float> keep = tracker_filter_points(tr, pts, n);
+    if (keep.empty()) return OFLK_OK;
+    HIP_TRY(hipSetDevice(tr->device));
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(tr->pts, keep.data(), keep.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));   // `keep` is this call's
+    const FeatWs ws = feat_ws(tr->feat, 1, tr->H, tr->W, tr->md, tr->K);
+    hipLaunchKernelGGL(k_free_list, dim3(1), dim3(256), 0, s, (const unsigned char *)tr->row_vis(tr->t), tr->K, ws.free, ws.nfree);
+    HIP_TRY(hipGetLastError());
+    return tracker_newborn(tr, tr->t, tr->pts, ws.free, ws.nfree, (int)(keep.size() / 2), s);
 }
 
 OFLK_API int oflk_pyramidal_last_level_flow(int B, int H, int W, int levels, int window_size, int iters, int level,

@@ -106,6 +106,16 @@ SIGNATURES = {
     "oflk_replenish_features_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [ctypes.c_int] * 2 + [_f32p, _vp, _i32p, _f32p, _vp, _i32p]),
     "oflk_replenish_features_workspace": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
     "oflk_replenish_features": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [ctypes.c_float] * 2 + [ctypes.c_int] * 2 + [_vp, _vp, _vp, ctypes.c_size_t] + [_vp] * 5),
+    "oflk_tracker_create": (ctypes.c_int, [ctypes.POINTER(_vp)] + [ctypes.c_int] * 7 + [ctypes.c_float] * 5 + [ctypes.c_int] * 2),
+    "oflk_tracker_destroy": (ctypes.c_int, [_vp]),
+    "oflk_tracker_reset": (ctypes.c_int, [_vp, _vp]),
+    "oflk_tracker_workspace_bytes": (ctypes.c_size_t, [_vp]),
+    "oflk_tracker_frame_index": (ctypes.c_int, [_vp]),
+    "oflk_tracker_push_device": (ctypes.c_int, [_vp, _vp, _vp]),
+    "oflk_tracker_row_device": (ctypes.c_int, [_vp] + [ctypes.POINTER(_vp)] * 6),
+    "oflk_tracker_read_row": (ctypes.c_int, [_vp, _f32p, _vp, _vp, _i32p, _f32p, _i32p, _vp]),
+    "oflk_tracker_push": (ctypes.c_int, [_vp, _vp, _f32p, _vp, _vp, _i32p, _f32p, _i32p]),
+    "oflk_tracker_add_points": (ctypes.c_int, [_vp, _f32p, ctypes.c_int, _vp]),
     "oflk_shard_range": (None, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, _i32p]),
     "oflk_single_scale_fp16": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, _f32p, _f32p]),
     "oflk_rtl_stream_length": (ctypes.c_long, [ctypes.c_int, ctypes.c_int]),
@@ -538,3 +548,81 @@ def replenish_features(d_frame: int, H: int, W: int, t: int, d_xy: int, d_visibl
     check(lib().oflk_replenish_features(d_frame, int(bool(u8)), int(H), int(W), int(window_size), float(quality_level),
                                         float(min_distance), int(max_corners), int(t), d_xy, d_visible, d_workspace,
                                         int(workspace_bytes), d_qt, d_qxy, d_born, d_detected, stream))
+
+
+class Tracker:
+    """Online sparse KLT tracker (oflk_tracker_*): K = max_corners slots on `device`, one frame per push.  Pointers are raw
+    device addresses, stream a hipStream_t handle; the rows are those of the statement in include/oflk.h.  The arguments
+    are the C ABI's and are checked there; creation makes no device call."""
+
+    def __init__(self, device: int, H: int, W: int, u8: bool, max_corners: int, detect_every: int, levels: int = 3,
+                 window_size: int = 5, iters: int = 3, alpha: float = 0.01, beta: float = 0.5, max_residual: float = 4.0,
+                 quality_level: float = 0.01, min_distance: float = 10.0):
+        self._h = _vp()
+        self.H, self.W, self.u8, self.K = int(H), int(W), bool(u8), int(max_corners)
+        check(lib().oflk_tracker_create(ctypes.byref(self._h), int(device), int(H), int(W), int(bool(u8)), int(levels),
+                                        int(window_size), int(iters), float(alpha), float(beta), float(max_residual),
+                                        float(quality_level), float(min_distance), int(max_corners), int(detect_every)))
+
+    def close(self) -> None:
+        if self._h:
+            lib().oflk_tracker_destroy(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def workspace_bytes(self) -> int:
+        return int(lib().oflk_tracker_workspace_bytes(self._h))
+
+    @property
+    def frame_index(self) -> int:
+        return int(lib().oflk_tracker_frame_index(self._h))
+
+    def reset(self, stream: int = 0) -> None:
+        check(lib().oflk_tracker_reset(self._h, stream))
+
+    def push_device(self, d_frame: int, stream: int = 0) -> None:
+        check(lib().oflk_tracker_push_device(self._h, d_frame or None, stream))
+
+    def row_device(self) -> Tuple[int, int, int, int, int, int]:
+        """device addresses of xy, visible, born, birth, residual, detected of the last pushed frame"""
+        p = [_vp() for _ in range(6)]
+        check(lib().oflk_tracker_row_device(self._h, *[ctypes.byref(q) for q in p]))
+        return tuple(int(q.value) for q in p)
+
+    def _row(self):
+        K = self.K
+        return (np.empty((K, 2), np.float32), np.empty(K, np.uint8), np.empty(K, np.uint8), np.empty(K, np.int32),
+                np.empty(K, np.float32), np.empty(1, np.int32))
+
+    @staticmethod
+    def _row_args(r):
+        return ptr(r[0]), r[1].ctypes.data, r[2].ctypes.data, r[3].ctypes.data_as(_i32p), ptr(r[4]), r[5].ctypes.data_as(_i32p)
+
+    def read_row(self, stream: int = 0):
+        """(xy (K, 2) float32, visible (K,) uint8, born (K,) uint8, birth (K,) int32, residual (K,) float32, detected int)"""
+        r = self._row()
+        check(lib().oflk_tracker_read_row(self._h, *self._row_args(r), stream))
+        return r[:5] + (int(r[5][0]),)
+
+    def push(self, frame: np.ndarray):
+        """a contiguous host frame (H, W) of the tracker's element type in, the row (as read_row) out"""
+        want = np.uint8 if self.u8 else np.float32
+        if not (isinstance(frame, np.ndarray) and frame.dtype == want and frame.shape == (self.H, self.W)
+                and frame.flags["C_CONTIGUOUS"]):
+            raise ValueError(f"expected a contiguous {np.dtype(want).name} frame of shape {(self.H, self.W)}")
+        r = self._row()
+        check(lib().oflk_tracker_push(self._h, frame.ctypes.data, *self._row_args(r)))
+        return r[:5] + (int(r[5][0]),)
+
+    def add_points(self, pts, stream: int = 0) -> None:
+        """(n, 2) host points (x, y), n >= 1"""
+        p = np.ascontiguousarray(pts, np.float32)
+        if p.ndim != 2 or p.shape[1] != 2:
+            raise ValueError(f"points must be an (n, 2) array of (x, y), got shape {p.shape}")
+        check(lib().oflk_tracker_add_points(self._h, ptr(p), int(p.shape[0]), stream))

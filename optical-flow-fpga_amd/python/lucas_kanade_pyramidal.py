@@ -459,6 +459,93 @@ def lucas_kanade_pyramidal_sequence_klt_sparse_replenish(frames, max_corners: in
     return SequenceKLTSparseReplenish(tracks, visible.astype(bool), born.astype(bool), detected, residual)
 
 
+class TrackerRow(NamedTuple):
+    """One frame's row of a SparseKltTracker: K slots."""
+    xy: np.ndarray         # (K, 2) float32 (x, y); NaN where not visible
+    visible: np.ndarray    # (K,) bool
+    born: np.ndarray       # (K,) bool: a new track began in this slot on this frame
+    birth: np.ndarray      # (K,) int32: the frame on which the slot's current track began (meaningful where visible)
+    residual: np.ndarray   # (K,) float32: the forward residual of the step into this frame of a slot alive before it; else NaN
+    detected: int          # points accepted by this frame's detection
+
+
+class SparseKltTracker:
+    """lucas_kanade_pyramidal_sequence_klt_sparse_replenish for video that arrives frame by frame: the state stays on the
+    device and push(frame) returns that frame's row.  Frame t detects when t % detect_every == 0 (0: never; hand it points
+    with add_points), at once, so a point born on frame t is in row t.  The rows of T pushes are rows 0 .. T-1 of the
+    sequence call on those frames followed by any one more.
+
+        with SparseKltTracker(frame.shape, 1000) as tracker:
+            for frame in video:                     # uint8 (H, W)
+                row = tracker.push(frame)
+    """
+
+    def __init__(self, shape, max_corners: int, detect_every: int = 4, quality_level: float = 0.01, min_distance: float = 10.0,
+                 num_levels: int = 3, window_size: int = 5, num_iterations: int = 3, alpha: float = 0.01, beta: float = 0.5,
+                 max_residual: float = 4.0, dtype=np.uint8, device: int = 0):
+        if len(shape) != 2 or int(shape[0]) < 1 or int(shape[1]) < 1:
+            raise ValueError(f"shape must be (H, W), got {shape!r}")
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.uint8), np.dtype(np.float32)):
+            raise ValueError(f"dtype must be uint8 or float32, got {dtype!r}")
+        a, b = _oflk.check_fb_params(alpha, beta)
+        H, W = int(shape[0]), int(shape[1])
+        L, win, it, r = _oflk.check_sparse_params((H, W), num_levels, window_size, num_iterations, max_residual)
+        K, q, md, win = _oflk.check_feature_params(max_corners, quality_level, min_distance, win)
+        if isinstance(detect_every, bool) or int(detect_every) != detect_every or int(detect_every) < 0:
+            raise ValueError(f"detect_every must be an integer >= 0, got {detect_every!r}")
+        self.shape, self.max_corners, self.detect_every = (H, W), K, min(int(detect_every), 2 ** 31 - 1)
+        self._t = _oflk.Tracker(device, H, W, self.dtype == np.uint8, K, self.detect_every, L, win, it, a, b, r, q, md)
+
+    @staticmethod
+    def _row(r) -> TrackerRow:
+        return TrackerRow(r[0], r[1].astype(bool), r[2].astype(bool), r[3], r[4], r[5])
+
+    def push(self, frame) -> TrackerRow:
+        """the next frame (H, W) in, its row out (synchronous)"""
+        f = np.ascontiguousarray(frame, self.dtype)
+        if f.shape != self.shape:
+            raise ValueError(f"expected a frame of shape {self.shape}, got {f.shape}")
+        return self._row(self._t.push(f))
+
+    def push_device(self, ptr: int, stream: int = 0) -> None:
+        """the next frame at a device address, asynchronous on `stream`; read_row or row_device gives its row"""
+        self._t.push_device(ptr, stream)
+
+    def read_row(self, stream: int = 0) -> TrackerRow:
+        """the row of the last pushed frame, points of add_points included (synchronises `stream`)"""
+        return self._row(self._t.read_row(stream))
+
+    def row_device(self):
+        """device addresses (xy, visible, born, birth, residual, detected) of the last pushed frame's row, valid until the
+        next push, add_points or reset"""
+        return self._t.row_device()
+
+    def add_points(self, pts, stream: int = 0) -> None:
+        """(n, 2) points (x, y) start tracks on the last pushed frame in the dead slots, ascending; points outside the frame
+        or not finite, and those for which no dead slot is left, are dropped"""
+        self._t.add_points(pts, stream)
+
+    def reset(self) -> None:
+        """every slot dead; the next push is frame 0"""
+        self._t.reset()
+
+    @property
+    def frame_index(self) -> int:
+        """index of the last pushed frame, -1 before the first"""
+        return self._t.frame_index
+
+    def close(self) -> None:
+        self._t.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
 def _dump_levels(key, shapes, u, v) -> None:
     """The reference's per-level PNG side effect (:226), after the call, best-effort."""
     num_levels = key[3]

@@ -20,7 +20,15 @@ the call's own frame, flow and row buffers, computed from the shapes).  Kernel t
 One JSON line per (K, detect_every): ms per call (median, min, max), the points detected and the share of slots alive on the
 last frame for both.  --only sparse under rocprofv3 gives the split into pyramid, track and detection kernels.
 
-    python tools/sparse_bench.py [--frames 129] [--steps 5] [--warmup 1] [--only sparse|dense] [--replenish]
+--online times the online tracker on the same frames and (K, detect_every) grid, alternating which goes first:
+  (a) oflk_pyramidal_sequence_klt_sparse_replenish_u8  one call on the T host frames
+  (b) oflk_tracker_push                                T synchronous host pushes on one tracker (reset before each round)
+and, from events around single calls on the T frames already on the device, the device time of a non-detecting and of a
+detecting oflk_tracker_push_device in the steady state (frames 8 .. T-1; the JSON line gives each median's sample count, and
+with detect_every 1 there is no non-detecting push).  One JSON line per (K, detect_every); it also checks that the pushes' rows
+are the call's.
+
+    python tools/sparse_bench.py [--frames 129] [--steps 5] [--warmup 1] [--only sparse|dense] [--replenish | --online]
                                  [--budgets 1000,10000] [--every 1,4,16]
 """
 import argparse
@@ -107,6 +115,79 @@ def replenish_leg(args, frames, forms, steps):
             print(json.dumps(line), flush=True)
 
 
+def online_leg(args, frames, steps):
+    """the online tracker against the sequence call, host to host, and the device time of single pushes"""
+    import numpy as np
+    import torch
+
+    import _oflk
+
+    L = _oflk.lib()
+    T, H, W = frames.shape
+    d_frames = torch.from_numpy(frames).to("cuda:0")   # every frame: each device median below states its count
+    st = torch.cuda.current_stream().cuda_stream
+    for K, md in zip(args.budgets, (10.0, 4.0) if len(args.budgets) == 2 else [4.0] * len(args.budgets)):
+        for D in args.every:
+            tr, vis, born = np.empty((T, K, 2), np.float32), np.empty((T, K), np.uint8), np.empty((T, K), np.uint8)
+            det, res = np.empty(T, np.int32), np.empty((T, K), np.float32)
+            ptr, pvis, pborn = np.empty((T, K, 2), np.float32), np.empty((T, K), np.uint8), np.empty((T, K), np.uint8)
+            pdet, pres, birth = np.empty(T, np.int32), np.empty((T, K), np.float32), np.empty(K, np.int32)
+            tk = _oflk.Tracker(0, H, W, True, K, D, 3, 5, 3, 0.01, 0.5, 4.0, 0.01, md)
+
+            def call(form):
+                if form == "sequence":
+                    _oflk.check(L.oflk_pyramidal_sequence_klt_sparse_replenish_u8(frames.ctypes.data, T, H, W, 3, 5, 3, 0.01, 0.5, 4.0,
+                                                                                  0.01, md, K, D, _oflk.ptr(tr), vis.ctypes.data,
+                                                                                  born.ctypes.data, det.ctypes.data_as(_oflk._i32p),
+                                                                                  _oflk.ptr(res)))
+                    return
+                tk.reset()
+                for t in range(T):
+                    _oflk.check(L.oflk_tracker_push(tk._h, frames[t].ctypes.data, _oflk.ptr(ptr[t]), pvis[t].ctypes.data,
+                                                    pborn[t].ctypes.data, birth.ctypes.data_as(_oflk._i32p), _oflk.ptr(pres[t]),
+                                                    pdet[t:].ctypes.data_as(_oflk._i32p)))
+
+            forms = ["sequence", "pushes"]
+            try:
+                for _ in range(args.warmup):
+                    for f in forms:
+                        call(f)
+                ms = {f: [] for f in forms}
+                for i in range(steps):
+                    for f in (forms if i % 2 == 0 else forms[::-1]):
+                        t0 = time.perf_counter()
+                        call(f)
+                        ms[f].append((time.perf_counter() - t0) * 1e3)
+                same = all(np.array_equal(a[:T - 1], b[:T - 1], equal_nan=a.dtype == np.float32)
+                           for a, b in ((ptr, tr), (pvis, vis), (pborn, born), (pdet, det), (pres, res)))
+                # device time of single pushes in the steady state: events around one push_device each
+                tk.reset()
+                dev_ms = {"detecting": [], "plain": []}
+                for t in range(d_frames.shape[0]):
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    tk.push_device(d_frames[t].data_ptr(), st)
+                    b.record()
+                    b.synchronize()
+                    if t >= 8:   # past frame 0's detection, where every slot is free
+                        dev_ms["detecting" if D > 0 and t % D == 0 else "plain"].append(a.elapsed_time(b))
+            finally:
+                tk.close()
+            line = {"tool": "sparse_bench", "leg": "online", "pixels": "u8", "frames": T, "height": H, "width": W, "levels": 3,
+                    "window": 5, "iters": 3, "steps": steps, "K": K, "min_distance": md, "detect_every": D,
+                    "rows_equal_the_call": bool(same)}
+            for f in forms:
+                line[f"{f}_ms"] = round(statistics.median(ms[f]), 3)
+                line[f"{f}_ms_min_max"] = [round(min(ms[f]), 3), round(max(ms[f]), 3)]
+            line["pushes_over_sequence"] = round(line["pushes_ms"] / line["sequence_ms"], 3)
+            line["push_ms_per_frame"] = round(line["pushes_ms"] / T, 4)
+            for k, v in dev_ms.items():
+                line[f"push_device_{k}_ms"] = round(statistics.median(v), 4) if v else None
+                line[f"push_device_{k}_ms_min_max"] = [round(min(v), 4), round(max(v), 4)] if v else None
+                line[f"push_device_{k}_samples"] = len(v)
+            print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=129)
@@ -117,6 +198,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--only", choices=["sparse", "dense"], default=None)
     ap.add_argument("--replenish", action="store_true", help="time the replenished KLT calls instead of the plain tracks")
+    ap.add_argument("--online", action="store_true", help="time the online tracker's pushes against the replenished sparse call")
     ap.add_argument("--budgets", type=lambda v: [int(x) for x in v.split(",")], default=[1000, 10000], help="--replenish: max_corners")
     ap.add_argument("--every", type=lambda v: [int(x) for x in v.split(",")], default=[1, 4, 16], help="--replenish: detect_every")
     args = ap.parse_args()
@@ -138,6 +220,9 @@ def main():
         frames[t] = np.rint(np.clip(f, 0.0, 255.0)).astype(np.uint8)
     L = _oflk.lib()
     forms = [f for f in ("dense", "sparse") if args.only in (None, f)]
+    if args.online:
+        online_leg(args, frames, steps)
+        return
     if args.replenish:
         replenish_leg(args, frames, forms, steps)
         return

@@ -482,6 +482,71 @@ int oflk_tracker_push(oflk_tracker *tr, const void *frame, float *xy, unsigned c
  * when the call returns (it synchronises `stream` once), the slots are filled in stream order */
 int oflk_tracker_add_points(oflk_tracker *tr, const float *pts, int n, void *stream);
 
+/* ---- global motion from point correspondences: deterministic RANSAC and a least-squares refit ------------------------- */
+/* The statement (tests/motion_model.py), per step with hash index i: correspondences src[n] -> dst[n], a validity mask, a
+ * model family, Hn hypotheses, a threshold (px) and a seed.
+ *   families       OFLK_MOTION_TRANSLATION (sample m = 1), OFLK_MOTION_SIMILARITY (m = 2: x' = a x - b y + tx, y' = b x + a y
+ *                  + ty), OFLK_MOTION_AFFINE (m = 3); a model is six float32 [a00 a01 tx; a10 a11 ty]
+ *   compaction     valid: the mask byte non-zero (no mask: always) and the four coordinates finite; the M valid ones keep
+ *                  their slot order.  M < m: the failure result -- six NaNs, mask all 0, counts (0, M, 0)
+ *   sampling       draw(seed, i, h, j): x = fmix(seed ^ 0x9E3779B9); x = fmix(x + i); x = fmix(x + h); x = fmix(x + j) on
+ *                  uint32 with murmur3's finaliser fmix.  Pick j of hypothesis h is r = draw % (M - j), the r-th position not
+ *                  yet picked, ascending.  A step depends on its own inputs and its index only
+ *   minimal solve  float64 on the points converted to double, each operation rounded on its own, differences taken from
+ *                  the first point; the six coefficients rounded to float32.  Coincident points (similarity), a zero
+ *                  determinant (affine) or a coefficient that is not finite: degenerate, score -1
+ *   score          float32, one operation at a time: ex = ((a00 x + a01 y) + tx) - qx, ey likewise, r2 = ex ex + ey ey;
+ *                  inlier: r2 <= threshold * threshold.  Score = inliers among the valid; best = largest, ties to the
+ *                  lowest h; every hypothesis degenerate: the failure result
+ *   refit          least squares of the family over the best hypothesis's inliers, centred on their centroids, float64
+ *                  sums of the float32 inputs in a stated order: 256 partials, partial l adds positions l, l + 256, ...
+ *                  ascending from +0.0, then partial[l] += partial[l + stride] for stride 128, 64, ..., 1.  No inlier, a
+ *                  zero determinant / spread or a result not finite in float32: the best hypothesis's model is kept
+ *   outputs        model [6];  inlier [N]: the score's test with the returned model on the valid correspondences, 0
+ *                  elsewhere;  counts [3] = (n_inliers = the mask's sum, n_valid = M, status = 1)
+ * Homographies and iterative re-estimation are not offered.
+ * Three kernel launches on `stream` (compaction, scoring with one wave per hypothesis, select-and-refit), no memset, no
+ * atomics, nothing synchronised: the chain can be captured into a graph after one eager call.
+ * Refusals, before any device call: an unknown model, hypotheses < 1 or > OFLK_MOTION_MAX_HYPOTHESES, a threshold that is
+ * not finite and positive, S or N < 1 (T < 2, K < 1), NULL pointers (d_valid and d_born may be NULL), d_src / d_dst /
+ * d_tracks not 8-byte aligned, a workspace that is too small or not 256-byte aligned: OFLK_ERR_INVALID. */
+#define OFLK_MOTION_TRANSLATION 0
+#define OFLK_MOTION_SIMILARITY 1
+#define OFLK_MOTION_AFFINE 2
+#define OFLK_MOTION_MAX_HYPOTHESES 65536
+/* bytes of the caller's workspace for S steps of N correspondences */
+int oflk_motion_workspace(int S, int N, int hypotheses, size_t *bytes);
+/* device form: d_src, d_dst [S][N][2], d_valid [S][N] or NULL (finiteness alone decides); step s draws with index step0 + s
+ * (uint32, wrapping).  d_model [S][6], d_inlier [S][N], d_counts [S][3].  Asynchronous on `stream`. */
+int oflk_estimate_motion(const float *d_src, const float *d_dst, const unsigned char *d_valid, int S, int N, int step0,
+                         int model, int hypotheses, float threshold, unsigned seed, void *d_workspace, size_t workspace_bytes,
+                         float *d_model, unsigned char *d_inlier, int *d_counts, void *stream);
+/* device form on rows as the track calls write them: d_tracks [T][K][2], d_visible [T][K], d_born [T][K] or NULL.  Step t
+ * (0 <= t < T-1) runs from row t to row t+1 with index t0 + t; slot n is valid on it when it is visible on both rows and
+ * not born on row t+1 (a slot that died and was refilled on one row is two different tracks).  The workspace is that of
+ * S = T-1, N = K; d_model [T-1][6], d_inlier [T-1][K], d_counts [T-1][3]. */
+int oflk_tracks_motion(const float *d_tracks, const unsigned char *d_visible, const unsigned char *d_born, int T, int K, int t0,
+                       int model, int hypotheses, float threshold, unsigned seed, void *d_workspace, size_t workspace_bytes,
+                       float *d_model, unsigned char *d_inlier, int *d_counts, void *stream);
+/* host arrays in and out (valid may be NULL); synchronous */
+int oflk_estimate_motion_host(const float *src, const float *dst, const unsigned char *valid, int S, int N, int step0, int model,
+                              int hypotheses, float threshold, unsigned seed, float *model_out, unsigned char *inlier,
+                              int *counts);
+/* The tracker's motion row.  model = -1 turns it off (the default; the other arguments are then ignored), and a push
+ * enqueues exactly what it does without this call.  With a model set, the push of frame t >= 1 enqueues, after its step and
+ * any detection, the fit of step t-1 -> t on the tracker's two rows: slot n is valid when visible on both and not born on
+ * frame t; the index is t-1.  Frame 0 (also after a reset) gets the failure result with M = 0.  So the motion rows of T
+ * pushes are steps 0 .. T-2 of oflk_tracks_motion on the rows of those pushes.  May be called between pushes; it takes
+ * effect on the next push, which (re)allocates the fit's buffers when they are missing or too small -- the one exception
+ * to "no later push allocates"; oflk_tracker_workspace_bytes counts them.  Points of oflk_tracker_add_points join the fit
+ * from the next step on.  motion_device / read_motion before a push with motion on: OFLK_ERR_INVALID. */
+int oflk_tracker_set_motion(oflk_tracker *tr, int model, int hypotheses, float threshold, unsigned seed);
+/* device pointers (each may be NULL) to the last push's motion row: model [6], inlier [K], counts [3] */
+int oflk_tracker_motion_device(const oflk_tracker *tr, const float **d_model, const unsigned char **d_inlier,
+                               const int **d_counts);
+/* copy it to host arrays (each may be NULL); synchronises `stream` */
+int oflk_tracker_read_motion(oflk_tracker *tr, float *model, unsigned char *inlier, int *counts, void *stream);
+
 /* Rehearsal of the chunk queue above on a box with fewer GPUs than workers (tests): `workers` > 0 makes the *_multi entry
  * points run that many queue workers, worker i on device i % n_gpus (workers of one device take turns on it); 0 restores
  * one worker per device.  Results do not change. */

@@ -10,6 +10,7 @@
 #include "oflk_stream.hpp"
 #include "oflk_sparse.hpp"
 #include "oflk_tracker.hpp"
+#include "oflk_motion.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -3544,6 +3545,160 @@ OFLK_API int oflk_plan_sparse_klt_replenish(oflk_plan *plan, const void *d_frame
 }
 
 // =============================================================================
+// global motion from correspondences: RANSAC and refit (oflk_motion.hpp)
+// =============================================================================
+namespace {
+// The workspace of the fit, 256-byte aligned pieces: M [S], the compacted correspondences [S][N], score [S][Hn] and the
+// hypotheses' models [S][Hn][6]
+struct MotionWs {
+    int *M;
+    float4 *pts;
+    int *score;
+    float *hmodel;
+    size_t bytes;
+};
+
+MotionWs motion_ws(void *base, int S, int N, int Hn)
+{
+    MotionWs v{};
+    auto take = [&](auto *&p, size_t n) {
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(reinterpret_cast<uintptr_t>(base) + v.bytes);
+        v.bytes += align256(n * sizeof(*p));
+    };
+    const size_t nS = (size_t)S;
+    take(v.M, nS);
+    take(v.pts, nS * (size_t)N);
+    take(v.score, nS * (size_t)Hn);
+    take(v.hmodel, nS * (size_t)Hn * 6);
+    return v;
+}
+
+// what every form of the fit refuses about its parameters
+int check_motion(int model, int hypotheses, float threshold)
+{
+    if (model != OFLK_MOTION_TRANSLATION && model != OFLK_MOTION_SIMILARITY && model != OFLK_MOTION_AFFINE)
+        return fail(OFLK_ERR_INVALID, "unknown motion model %d", model);
+    if (hypotheses < 1 || hypotheses > OFLK_MOTION_MAX_HYPOTHESES)
+        return fail(OFLK_ERR_INVALID, "hypotheses must be in [1, %d] (got %d)", OFLK_MOTION_MAX_HYPOTHESES, hypotheses);
+    if (!(std::isfinite(threshold) && threshold > 0.0f))
+        return fail(OFLK_ERR_INVALID, "threshold must be finite and > 0 (got %g)", (double)threshold);
+    return OFLK_OK;
+}
+
+int check_motion_shape(int S, int N)
+{
+    if (S < 1 || N < 1) return fail(OFLK_ERR_INVALID, "steps and correspondences must be >= 1 (got %d steps of %d)", S, N);
+    return OFLK_OK;
+}
+
+int check_motion_workspace(const void *ws, size_t bytes, int S, int N, int Hn)
+{
+    if (!ws) return fail(OFLK_ERR_INVALID, "NULL workspace");
+    const size_t need = motion_ws(nullptr, S, N, Hn).bytes;
+    if (bytes < need) return fail(OFLK_ERR_INVALID, "workspace of %zu bytes, %zu needed (oflk_motion_workspace)", bytes, need);
+    if (!aligned(ws, 256)) return fail(OFLK_ERR_INVALID, "d_workspace must be 256-byte aligned");
+    return OFLK_OK;
+}
+
+// The three launches of S steps on stream s; the arguments are checked.  Step s reads src / dst / va / vb / born at
+// [s][N]: NULL masks do not decide.
+struct MotionIn {
+    const float *src, *dst;
+    const unsigned char *va, *vb, *born;
+};
+
+int motion_launch(const MotionIn &in, int S, int N, unsigned index0, int model, int Hn, float threshold, unsigned seed,
+                  const MotionWs &ws, float *d_model, unsigned char *d_inlier, int *d_counts, hipStream_t s)
+{
+    MotionArgs a{};
+    a.src = reinterpret_cast<const float2 *>(in.src);
+    a.dst = reinterpret_cast<const float2 *>(in.dst);
+    a.va = in.va; a.vb = in.vb; a.born = in.born;
+    a.S = S; a.N = N; a.Hn = Hn;
+    a.index0 = index0; a.seed = seed;
+    a.thr2 = threshold * threshold;
+    a.M = ws.M; a.pts = ws.pts; a.score = ws.score; a.hmodel = ws.hmodel;
+    a.model = d_model; a.inlier = d_inlier; a.counts = d_counts;
+    const unsigned steps = (unsigned)std::min(S, 65535);
+    hipLaunchKernelGGL(k_motion_compact, dim3(steps), dim3(kMotionCompact), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    const dim3 grid((unsigned)((Hn + kMotionWaves - 1) / kMotionWaves), steps);
+    const bool built = with_int<kMotionTranslation, kMotionSimilarity, kMotionAffine>(model, [&](auto MODEL) {
+        hipLaunchKernelGGL(k_motion_score<decltype(MODEL)::value>, grid, dim3(64 * kMotionWaves), 0, s, a);
+        hipLaunchKernelGGL(k_motion_refit<decltype(MODEL)::value>, dim3(steps), dim3(kMotionLanes), 0, s, a);
+    });
+    if (!built) return fail(OFLK_ERR_INVALID, "unknown motion model %d", model);
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+}  // namespace
+
+OFLK_API int oflk_motion_workspace(int S, int N, int hypotheses, size_t *bytes)
+{
+    if (!bytes) return fail(OFLK_ERR_INVALID, "NULL bytes");
+    int rc = check_motion_shape(S, N);
+    if (rc || (rc = check_motion(OFLK_MOTION_AFFINE, hypotheses, 1.0f))) return rc;
+    *bytes = motion_ws(nullptr, S, N, hypotheses).bytes;
+    return OFLK_OK;
+}
+
+OFLK_API int oflk_estimate_motion(const float *d_src, const float *d_dst, const unsigned char *d_valid, int S, int N, int step0,
+                                  int model, int hypotheses, float threshold, unsigned seed, void *d_workspace,
+                                  size_t workspace_bytes, float *d_model, unsigned char *d_inlier, int *d_counts, void *stream)
+{
+    int rc = check_motion_shape(S, N);
+    if (rc || (rc = check_motion(model, hypotheses, threshold))) return rc;
+    if (!d_src || !d_dst || !d_model || !d_inlier || !d_counts) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    if (!aligned(d_src, 8) || !aligned(d_dst, 8)) return fail(OFLK_ERR_INVALID, "d_src and d_dst must be 8-byte aligned");
+    if ((rc = check_motion_workspace(d_workspace, workspace_bytes, S, N, hypotheses))) return rc;
+    return motion_launch({d_src, d_dst, d_valid, nullptr, nullptr}, S, N, (unsigned)step0, model, hypotheses, threshold, seed,
+                         motion_ws(d_workspace, S, N, hypotheses), d_model, d_inlier, d_counts, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_tracks_motion(const float *d_tracks, const unsigned char *d_visible, const unsigned char *d_born, int T, int K,
+                                int t0, int model, int hypotheses, float threshold, unsigned seed, void *d_workspace,
+                                size_t workspace_bytes, float *d_model, unsigned char *d_inlier, int *d_counts, void *stream)
+{
+    if (T < 2) return fail(OFLK_ERR_INVALID, "T must be >= 2 (got %d)", T);
+    int rc = check_motion_shape(T - 1, K);
+    if (rc || (rc = check_motion(model, hypotheses, threshold))) return rc;
+    if (!d_tracks || !d_visible || !d_model || !d_inlier || !d_counts) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    if (!aligned(d_tracks, 8)) return fail(OFLK_ERR_INVALID, "d_tracks must be 8-byte aligned");
+    if ((rc = check_motion_workspace(d_workspace, workspace_bytes, T - 1, K, hypotheses))) return rc;
+    // row t+1 of a [T][K] array is row t of the array that begins K elements later: one stride for every input
+    const MotionIn in{d_tracks, d_tracks + 2 * (size_t)K, d_visible, d_visible + (size_t)K, d_born ? d_born + (size_t)K : nullptr};
+    return motion_launch(in, T - 1, K, (unsigned)t0, model, hypotheses, threshold, seed, motion_ws(d_workspace, T - 1, K, hypotheses),
+                         d_model, d_inlier, d_counts, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_estimate_motion_host(const float *src, const float *dst, const unsigned char *valid, int S, int N, int step0,
+                                       int model, int hypotheses, float threshold, unsigned seed, float *model_out,
+                                       unsigned char *inlier, int *counts)
+{
+    int rc = check_motion_shape(S, N);
+    if (rc || (rc = check_motion(model, hypotheses, threshold))) return rc;
+    if (!src || !dst || !model_out || !inlier || !counts) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const size_t n = (size_t)S * (size_t)N;
+    float *d_src, *d_dst, *d_model;
+    unsigned char *d_valid = nullptr, *d_inl;
+    char *d_ws;
+    int *d_cnt;
+    if ((rc = call.upload(&d_src, src, 2 * n)) || (rc = call.upload(&d_dst, dst, 2 * n)) ||
+        (valid && (rc = call.upload(&d_valid, valid, n))) || (rc = call.alloc(&d_ws, motion_ws(nullptr, S, N, hypotheses).bytes)) ||
+        (rc = call.alloc(&d_model, 6 * (size_t)S)) || (rc = call.alloc(&d_inl, n)) || (rc = call.alloc(&d_cnt, 3 * (size_t)S)))
+        return rc;
+    if ((rc = motion_launch({d_src, d_dst, d_valid, nullptr, nullptr}, S, N, (unsigned)step0, model, hypotheses, threshold, seed,
+                            motion_ws(d_ws, S, N, hypotheses), d_model, d_inl, d_cnt, nullptr)))
+        return rc;
+    if ((rc = call.to_host(model_out, d_model, 6 * (size_t)S)) || (rc = call.to_host(inlier, d_inl, n)) ||
+        (rc = call.to_host(counts, d_cnt, 3 * (size_t)S)))
+        return rc;
+    return call.sync();
+}
+
+// =============================================================================
 // online sparse KLT tracker: one frame per push
 // =============================================================================
 // The state of a tracker.  Creation checks and records the configuration and makes no device call; the first push
@@ -3569,6 +3724,17 @@ struct oflk_tracker {
     float *residual = nullptr;        // [K]
     int *detected = nullptr;          // [1]
     char *feat = nullptr;             // the oflk_replenish_features workspace of one frame
+    // the motion row (oflk_tracker_set_motion): off while m_model < 0; the buffers come with the first push that needs them
+    int m_model = -1, m_hyps = 0;
+    float m_thr = 0;
+    unsigned m_seed = 0;
+    long long m_t = -2;               // the frame whose motion row the buffers hold
+    float *m_out = nullptr;           // [6]
+    unsigned char *m_inlier = nullptr;   // [K]
+    int *m_counts = nullptr;          // [3]
+    char *m_ws = nullptr;             // the fit's workspace of one step, for m_ws_hyps hypotheses
+    int m_ws_hyps = 0;
+    size_t m_ws_bytes = 0;
 
     size_t npix(int l) const { return (size_t)dims[2 * l] * (size_t)dims[2 * l + 1]; }
     size_t pix_bytes() const { return u8 ? 1 : sizeof(float); }
@@ -3585,7 +3751,8 @@ void tracker_free(oflk_tracker *tr)
     for (float *q : tr->pyr)
         if (q) (void)hipFree(q);
     for (void *q : {(void *)tr->ring, (void *)tr->xy, (void *)tr->vis, (void *)tr->qt, (void *)tr->qxy, (void *)tr->pts, (void *)tr->born,
-                    (void *)tr->residual, (void *)tr->detected, (void *)tr->feat})
+                    (void *)tr->residual, (void *)tr->detected, (void *)tr->feat, (void *)tr->m_out, (void *)tr->m_inlier,
+                    (void *)tr->m_counts, (void *)tr->m_ws})
         if (q) (void)hipFree(q);
     delete tr;
 }
@@ -3609,6 +3776,27 @@ int tracker_ensure_state(oflk_tracker *tr)
         (rc = dmalloc(&tr->feat, feat_ws(nullptr, 1, tr->H, tr->W, tr->md, tr->K).bytes, &tr->ws_bytes)))
         return rc;
     tr->ready = true;
+    return OFLK_OK;
+}
+
+// the motion row's buffers, before the first push that fits (and again when the hypotheses outgrow the workspace)
+int tracker_ensure_motion(oflk_tracker *tr)
+{
+    int rc = OFLK_OK;
+    if (!tr->m_out && ((rc = dmalloc(&tr->m_out, 6, &tr->ws_bytes)) || (rc = dmalloc(&tr->m_inlier, (size_t)tr->K, &tr->ws_bytes)) ||
+                       (rc = dmalloc(&tr->m_counts, 3, &tr->ws_bytes))))
+        return rc;
+    if (tr->m_ws_hyps >= tr->m_hyps) return OFLK_OK;
+    if (tr->m_ws) {
+        HIP_TRY(hipFree(tr->m_ws));   // waits for the work that uses it
+        tr->m_ws = nullptr;
+        tr->ws_bytes -= tr->m_ws_bytes;
+        tr->m_ws_hyps = 0;
+    }
+    const size_t before = tr->ws_bytes;
+    if ((rc = dmalloc(&tr->m_ws, motion_ws(nullptr, 1, tr->K, tr->m_hyps).bytes, &tr->ws_bytes))) return rc;
+    tr->m_ws_bytes = tr->ws_bytes - before;
+    tr->m_ws_hyps = tr->m_hyps;
     return OFLK_OK;
 }
 
@@ -3694,6 +3882,18 @@ int tracker_enqueue(oflk_tracker *tr, const void *src, hipMemcpyKind kind, hipSt
             (rc = tracker_newborn(tr, t, tr->qxy, nullptr, nullptr, 0, s)))
             return rc;
     }
+    if (tr->m_model >= 0) {   // the motion row: step t-1 -> t on the two rows and this frame's born
+        if (t == 0) {
+            hipLaunchKernelGGL(k_motion_none, dim3((unsigned)((std::max(tr->K, 6) + 255) / 256)), dim3(256), 0, s, tr->m_out,
+                               tr->m_inlier, tr->m_counts, tr->K);
+            HIP_TRY(hipGetLastError());
+        } else if ((rc = motion_launch({tr->row_xy(t - 1), tr->row_xy(t), tr->row_vis(t - 1), tr->row_vis(t), tr->born}, 1, tr->K,
+                                       (unsigned)(t - 1), tr->m_model, tr->m_hyps, tr->m_thr, tr->m_seed,
+                                       motion_ws(tr->m_ws, 1, tr->K, tr->m_hyps), tr->m_out, tr->m_inlier, tr->m_counts, s))) {
+            return rc;
+        }
+        tr->m_t = t;
+    }
     tr->t = t;   // only a push whose every launch was accepted counts
     return OFLK_OK;
 }
@@ -3705,7 +3905,7 @@ int tracker_push(oflk_tracker *tr, const void *src, hipMemcpyKind kind, hipStrea
     if (tr->t >= (long long)INT_MAX - 1)
         return fail(OFLK_ERR_UNSUPPORTED, "frame index %lld is the last one a tracker takes (reset it)", tr->t);
     int rc = tracker_ensure_state(tr);   // a refusal here has written nothing
-    if (rc) return rc;
+    if (rc || (tr->m_model >= 0 && (rc = tracker_ensure_motion(tr)))) return rc;
     if ((rc = tracker_enqueue(tr, src, kind, s))) tr->failed = true;
     return rc;
 }
@@ -3787,6 +3987,7 @@ OFLK_API int oflk_tracker_reset(oflk_tracker *tr, void *)
 {
     if (!tr) return fail(OFLK_ERR_INVALID, "NULL tracker");
     tr->t = -1;   // frame 0's push reads no row: every slot is dead
+    tr->m_t = -2;
     tr->failed = false;
     return OFLK_OK;
 }
@@ -3857,6 +4058,49 @@ OFLK_API int oflk_tracker_add_points(oflk_tracker *tr, const float *pts, int n, 
     hipLaunchKernelGGL(k_free_list, dim3(1), dim3(256), 0, s, (const unsigned char *)tr->row_vis(tr->t), tr->K, ws.free, ws.nfree);
     HIP_TRY(hipGetLastError());
     return tracker_newborn(tr, tr->t, tr->pts, ws.free, ws.nfree, (int)(keep.size() / 2), s);
+}
+
+OFLK_API int oflk_tracker_set_motion(oflk_tracker *tr, int model, int hypotheses, float threshold, unsigned seed)
+{
+    if (!tr) return fail(OFLK_ERR_INVALID, "NULL tracker");
+    if (model == -1) {
+        tr->m_model = -1;
+        return OFLK_OK;
+    }
+    if (int rc = check_motion(model, hypotheses, threshold)) return rc;
+    tr->m_model = model; tr->m_hyps = hypotheses; tr->m_thr = threshold; tr->m_seed = seed;
+    return OFLK_OK;
+}
+
+namespace {
+int tracker_has_motion(const oflk_tracker *tr)
+{
+    if (int rc = tracker_pushed(tr)) return rc;
+    if (tr->m_t != tr->t) return fail(OFLK_ERR_INVALID, "the last push had no motion model set (oflk_tracker_set_motion)");
+    return OFLK_OK;
+}
+}  // namespace
+
+OFLK_API int oflk_tracker_motion_device(const oflk_tracker *tr, const float **d_model, const unsigned char **d_inlier,
+                                        const int **d_counts)
+{
+    if (int rc = tracker_has_motion(tr)) return rc;
+    if (d_model) *d_model = tr->m_out;
+    if (d_inlier) *d_inlier = tr->m_inlier;
+    if (d_counts) *d_counts = tr->m_counts;
+    return OFLK_OK;
+}
+
+OFLK_API int oflk_tracker_read_motion(oflk_tracker *tr, float *model, unsigned char *inlier, int *counts, void *stream)
+{
+    if (int rc = tracker_has_motion(tr)) return rc;
+    HIP_TRY(hipSetDevice(tr->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (model) HIP_TRY(hipMemcpyAsync(model, tr->m_out, 6 * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (inlier) HIP_TRY(hipMemcpyAsync(inlier, tr->m_inlier, (size_t)tr->K, hipMemcpyDeviceToHost, s));
+    if (counts) HIP_TRY(hipMemcpyAsync(counts, tr->m_counts, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return OFLK_OK;
 }
 
 OFLK_API int oflk_pyramidal_last_level_flow(int B, int H, int W, int levels, int window_size, int iters, int level,

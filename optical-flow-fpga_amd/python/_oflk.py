@@ -116,6 +116,13 @@ SIGNATURES = {
     "oflk_tracker_read_row": (ctypes.c_int, [_vp, _f32p, _vp, _vp, _i32p, _f32p, _i32p, _vp]),
     "oflk_tracker_push": (ctypes.c_int, [_vp, _vp, _f32p, _vp, _vp, _i32p, _f32p, _i32p]),
     "oflk_tracker_add_points": (ctypes.c_int, [_vp, _f32p, ctypes.c_int, _vp]),
+    "oflk_motion_workspace": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)]),
+    "oflk_estimate_motion": (ctypes.c_int, [_vp] * 3 + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_uint, _vp, ctypes.c_size_t] + [_vp] * 4),
+    "oflk_tracks_motion": (ctypes.c_int, [_vp] * 3 + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_uint, _vp, ctypes.c_size_t] + [_vp] * 4),
+    "oflk_estimate_motion_host": (ctypes.c_int, [_f32p, _f32p, _vp] + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_uint, _f32p, _vp, _i32p]),
+    "oflk_tracker_set_motion": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_uint]),
+    "oflk_tracker_motion_device": (ctypes.c_int, [_vp] + [ctypes.POINTER(_vp)] * 3),
+    "oflk_tracker_read_motion": (ctypes.c_int, [_vp, _f32p, _vp, _i32p, _vp]),
     "oflk_shard_range": (None, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, _i32p]),
     "oflk_single_scale_fp16": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, _f32p, _f32p]),
     "oflk_rtl_stream_length": (ctypes.c_long, [ctypes.c_int, ctypes.c_int]),
@@ -550,6 +557,67 @@ def replenish_features(d_frame: int, H: int, W: int, t: int, d_xy: int, d_visibl
                                         int(workspace_bytes), d_qt, d_qxy, d_born, d_detected, stream))
 
 
+MOTION_MODELS = {"translation": 0, "similarity": 1, "affine": 2}
+MOTION_MAX_HYPOTHESES = 65536
+
+
+def check_motion_params(model, hypotheses, threshold: float, seed) -> Tuple[int, int, float, int]:
+    """The fit's parameters as the C ABI takes them: (model code, hypotheses, threshold as float32, seed as uint32);
+    ValueError for an unknown model, hypotheses outside [1, MOTION_MAX_HYPOTHESES], a threshold that is not finite and
+    positive or a seed outside uint32.  Nothing here touches a device."""
+    code = MOTION_MODELS.get(model) if isinstance(model, str) else (model if model in (0, 1, 2) and not isinstance(model, bool) else None)
+    if code is None:
+        raise ValueError(f"model must be one of {sorted(MOTION_MODELS)}, got {model!r}")
+    if isinstance(hypotheses, bool) or int(hypotheses) != hypotheses or not 1 <= int(hypotheses) <= MOTION_MAX_HYPOTHESES:
+        raise ValueError(f"hypotheses must be an integer in [1, {MOTION_MAX_HYPOTHESES}], got {hypotheses!r}")
+    with np.errstate(over="ignore"):
+        thr = np.float32(threshold)
+    if not (np.isfinite(thr) and thr > 0):
+        raise ValueError(f"threshold must be finite and > 0, got {threshold!r}")
+    if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 32:
+        raise ValueError(f"seed must be an integer in [0, 2^32), got {seed!r}")
+    return int(code), int(hypotheses), float(thr), int(seed)
+
+
+def motion_workspace(S: int, N: int, hypotheses: int) -> int:
+    """bytes of the workspace of oflk_estimate_motion (S steps of N correspondences) and oflk_tracks_motion (S = T-1, N = K)"""
+    n = ctypes.c_size_t(0)
+    check(lib().oflk_motion_workspace(int(S), int(N), int(hypotheses), ctypes.byref(n)))
+    return int(n.value)
+
+
+def estimate_motion(d_src: int, d_dst: int, d_valid: int, S: int, N: int, d_workspace: int, workspace_bytes: int, d_model: int,
+                    d_inlier: int, d_counts: int, model: int = 1, hypotheses: int = 256, threshold: float = 1.0, seed: int = 0,
+                    step0: int = 0, stream: int = 0) -> None:
+    """oflk_estimate_motion on device pointers: d_src, d_dst [S][N][2] float32, d_valid [S][N] uint8 or 0 -> d_model [S][6]
+    float32, d_inlier [S][N] uint8, d_counts [S][3] int32 (n_inliers, n_valid, status); asynchronous on `stream`."""
+    check(lib().oflk_estimate_motion(d_src or None, d_dst or None, d_valid or None, int(S), int(N), int(step0), int(model),
+                                     int(hypotheses), float(threshold), int(seed), d_workspace or None, int(workspace_bytes),
+                                     d_model or None, d_inlier or None, d_counts or None, stream))
+
+
+def tracks_motion(d_tracks: int, d_visible: int, d_born: int, T: int, K: int, d_workspace: int, workspace_bytes: int,
+                  d_model: int, d_inlier: int, d_counts: int, model: int = 1, hypotheses: int = 256, threshold: float = 1.0,
+                  seed: int = 0, t0: int = 0, stream: int = 0) -> None:
+    """oflk_tracks_motion on device pointers: rows d_tracks [T][K][2], d_visible [T][K], d_born [T][K] or 0 -> the T-1 steps'
+    d_model [T-1][6], d_inlier [T-1][K], d_counts [T-1][3]; the workspace is motion_workspace(T-1, K, hypotheses)."""
+    check(lib().oflk_tracks_motion(d_tracks or None, d_visible or None, d_born or None, int(T), int(K), int(t0), int(model),
+                                   int(hypotheses), float(threshold), int(seed), d_workspace or None, int(workspace_bytes),
+                                   d_model or None, d_inlier or None, d_counts or None, stream))
+
+
+def estimate_motion_host(src: np.ndarray, dst: np.ndarray, valid: Optional[np.ndarray], model: int, hypotheses: int,
+                         threshold: float, seed: int, step0: int = 0):
+    """oflk_estimate_motion_host: contiguous float32 (S, N, 2) arrays and an optional uint8 (S, N) mask in; (model (S, 6)
+    float32, inlier (S, N) uint8, counts (S, 3) int32) out"""
+    S, N = src.shape[:2]
+    out, inl, cnt = np.empty((S, 6), np.float32), np.empty((S, N), np.uint8), np.empty((S, 3), np.int32)
+    check(lib().oflk_estimate_motion_host(ptr(src), ptr(dst), None if valid is None else valid.ctypes.data, S, N, int(step0),
+                                          int(model), int(hypotheses), float(threshold), int(seed), ptr(out), inl.ctypes.data,
+                                          cnt.ctypes.data_as(_i32p)))
+    return out, inl, cnt
+
+
 class Tracker:
     """Online sparse KLT tracker (oflk_tracker_*): K = max_corners slots on `device`, one frame per push.  Pointers are raw
     device addresses, stream a hipStream_t handle; the rows are those of the statement in include/oflk.h.  The arguments
@@ -626,3 +694,19 @@ class Tracker:
         if p.ndim != 2 or p.shape[1] != 2:
             raise ValueError(f"points must be an (n, 2) array of (x, y), got shape {p.shape}")
         check(lib().oflk_tracker_add_points(self._h, ptr(p), int(p.shape[0]), stream))
+
+    def set_motion(self, model: int, hypotheses: int = 256, threshold: float = 1.0, seed: int = 0) -> None:
+        """the motion row of the pushes from the next one on; model -1: off"""
+        check(lib().oflk_tracker_set_motion(self._h, int(model), int(hypotheses), float(threshold), int(seed)))
+
+    def motion_device(self) -> Tuple[int, int, int]:
+        """device addresses of model [6], inlier [K], counts [3] of the last push's motion row"""
+        p = [_vp() for _ in range(3)]
+        check(lib().oflk_tracker_motion_device(self._h, *[ctypes.byref(q) for q in p]))
+        return tuple(int(q.value) for q in p)
+
+    def read_motion(self, stream: int = 0):
+        """(model (6,) float32, inlier (K,) uint8, counts (3,) int32) of the last push's motion row"""
+        m, inl, cnt = np.empty(6, np.float32), np.empty(self.K, np.uint8), np.empty(3, np.int32)
+        check(lib().oflk_tracker_read_motion(self._h, ptr(m), inl.ctypes.data, cnt.ctypes.data_as(_i32p), stream))
+        return m, inl, cnt

@@ -12,7 +12,7 @@ No CPU fallback exists: without the built library or a GPU the calls raise.
 """
 from __future__ import annotations
 
-from typing import Tuple
+from typing import NamedTuple, Tuple
 
 import numpy as np
 import numpy.typing as npt
@@ -230,3 +230,64 @@ def split_tracks(visible, born):
             gone = np.flatnonzero(~vis[t0:stop, n])
             out.append((n, t0, t0 + int(gone[0]) - 1 if len(gone) else stop - 1))
     return out
+
+
+class Motion(NamedTuple):
+    """A global 2-D motion model fitted to point correspondences (estimate_motion)."""
+    model: np.ndarray      # (2, 3) float32 [a00 a01 tx; a10 a11 ty]: dst = A src + t; NaN when status is 0.  Batched: (S, 2, 3)
+    inlier: np.ndarray     # (N,) bool: the correspondences within the threshold of the returned model.  Batched: (S, N)
+    n_inliers: int         # the mask's sum.  Batched: (S,) int32
+    n_valid: int           # correspondences that entered the fit
+    status: int            # 1: a model was found; 0: fewer valid correspondences than the sample, or every sample degenerate
+
+
+def _motion(out, inl, cnt, batched: bool) -> Motion:
+    m = Motion(out.reshape(-1, 2, 3), inl.astype(bool), cnt[:, 0].copy(), cnt[:, 1].copy(), cnt[:, 2].copy())
+    return m if batched else Motion(m.model[0], m.inlier[0], int(m.n_inliers[0]), int(m.n_valid[0]), int(m.status[0]))
+
+
+def estimate_motion(src, dst, valid=None, model: str = "similarity", hypotheses: int = 256, threshold: float = 1.0, seed: int = 0,
+                    step0: int = 0) -> Motion:
+    """A robust global motion model between point sets, on the GPU: a deterministic RANSAC and a least-squares refit.
+
+    src, dst: (N, 2) float32 (x, y), or a batch of steps (S, N, 2) fitted independently; valid: (N,) / (S, N) or None.  A
+    correspondence enters the fit when its mask is set and its coordinates are finite.  model: "translation",
+    "similarity" (rotation, uniform scale, translation) or "affine".  `hypotheses` minimal samples are drawn from a
+    counter-based hash of (seed, step0 + s, hypothesis), scored by the number of correspondences within `threshold` pixels,
+    and the best one (ties to the lowest) is refitted over its inliers.  The same inputs give the same bytes.  The statement
+    is in include/oflk.h; homographies and iterative re-estimation are not offered.
+    """
+    code, hn, thr, sd = _oflk.check_motion_params(model, hypotheses, threshold, seed)
+    a, b = np.ascontiguousarray(src, np.float32), np.ascontiguousarray(dst, np.float32)
+    if a.ndim not in (2, 3) or a.shape[-1] != 2 or a.shape != b.shape or a.size == 0:
+        raise ValueError(f"expected src and dst of one shape (N, 2) or (S, N, 2), got {a.shape} and {b.shape}")
+    batched = a.ndim == 3
+    if not batched:
+        a, b = a[None], b[None]
+    v = None
+    if valid is not None:
+        v = np.ascontiguousarray(np.asarray(valid) != 0, np.uint8)
+        v = v if batched else v[None]
+        if v.shape != a.shape[:2]:
+            raise ValueError(f"valid must have shape {a.shape[:2] if batched else a.shape[1:2]}, got {np.shape(valid)}")
+    if isinstance(step0, bool) or int(step0) != step0 or not 0 <= int(step0) < 2 ** 31:
+        raise ValueError(f"step0 must be an integer in [0, 2^31), got {step0!r}")
+    return _motion(*_oflk.estimate_motion_host(a, b, v, code, hn, thr, sd, int(step0)), batched)
+
+
+def tracks_motion(tracks, visible, born=None, model: str = "similarity", hypotheses: int = 256, threshold: float = 1.0,
+                  seed: int = 0, t0: int = 0) -> Motion:
+    """The T-1 motions between consecutive rows of any of the track calls: tracks (T, K, 2), visible (T, K), born (T, K) or
+    None.  Step t runs from row t to row t+1 with hash index t0 + t; a slot is valid on it when it is visible on both rows
+    and not born on row t+1 (a slot that died and was refilled on one row is two different tracks).  Returns a batched
+    Motion of T-1 steps."""
+    tr, vis = np.asarray(tracks, np.float32), np.asarray(visible) != 0
+    if tr.ndim != 3 or tr.shape[2] != 2 or tr.shape[0] < 2 or vis.shape != tr.shape[:2]:
+        raise ValueError(f"expected tracks (T, K, 2) with T >= 2 and visible (T, K), got {tr.shape} and {vis.shape}")
+    ok = vis[:-1] & vis[1:]
+    if born is not None:
+        b = np.asarray(born) != 0
+        if b.shape != vis.shape:
+            raise ValueError(f"born must have shape {vis.shape}, got {b.shape}")
+        ok &= ~b[1:]
+    return estimate_motion(tr[:-1], tr[1:], ok, model, hypotheses, threshold, seed, t0)

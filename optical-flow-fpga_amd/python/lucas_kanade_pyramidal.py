@@ -30,7 +30,7 @@ import numpy as np
 import numpy.typing as npt
 
 import _oflk
-from lucas_kanade_core import lucas_kanade_single_scale
+from lucas_kanade_core import Motion, estimate_motion, lucas_kanade_single_scale, tracks_motion  # noqa: F401
 
 SCRIPT_DIR = Path(__file__).resolve().parent
 PROJECT_ROOT = SCRIPT_DIR.parent
@@ -471,7 +471,7 @@ class TrackerRow(NamedTuple):
 
 class SparseKltTracker:
     """lucas_kanade_pyramidal_sequence_klt_sparse_replenish for video that arrives frame by frame: the state stays on the
-    device and push(frame) returns that frame's row.  Frame t detects when t % detect_every == 0 (0: never; hand it points
+    device and push(frame) returns that frame's row (with motion=, also that step's global motion: motion()).  Frame t detects when t % detect_every == 0 (0: never; hand it points
     with add_points), at once, so a point born on frame t is in row t.  The rows of T pushes are rows 0 .. T-1 of the
     sequence call on those frames followed by any one more.
 
@@ -482,7 +482,7 @@ class SparseKltTracker:
 
     def __init__(self, shape, max_corners: int, detect_every: int = 4, quality_level: float = 0.01, min_distance: float = 10.0,
                  num_levels: int = 3, window_size: int = 5, num_iterations: int = 3, alpha: float = 0.01, beta: float = 0.5,
-                 max_residual: float = 4.0, dtype=np.uint8, device: int = 0):
+                 max_residual: float = 4.0, dtype=np.uint8, device: int = 0, motion=None):
         if len(shape) != 2 or int(shape[0]) < 1 or int(shape[1]) < 1:
             raise ValueError(f"shape must be (H, W), got {shape!r}")
         self.dtype = np.dtype(dtype)
@@ -496,6 +496,8 @@ class SparseKltTracker:
             raise ValueError(f"detect_every must be an integer >= 0, got {detect_every!r}")
         self.shape, self.max_corners, self.detect_every = (H, W), K, min(int(detect_every), 2 ** 31 - 1)
         self._t = _oflk.Tracker(device, H, W, self.dtype == np.uint8, K, self.detect_every, L, win, it, a, b, r, q, md)
+        if motion is not None:
+            self.set_motion(**motion) if isinstance(motion, dict) else self.set_motion(motion)
 
     @staticmethod
     def _row(r) -> TrackerRow:
@@ -529,6 +531,25 @@ class SparseKltTracker:
     def reset(self) -> None:
         """every slot dead; the next push is frame 0"""
         self._t.reset()
+
+    def set_motion(self, model="similarity", hypotheses: int = 256, threshold: float = 1.0, seed: int = 0) -> None:
+        """From the next push on, every push also fits the global motion of its step (lucas_kanade_core.estimate_motion on
+        the slots visible on both frames and not born on the new one, hash index t-1 for the push of frame t) on the
+        device; motion() returns it.  model None turns it off.  The constructor's motion= takes a model name or a dict of
+        these arguments."""
+        if model is None:
+            self._t.set_motion(-1)
+        else:
+            self._t.set_motion(*_oflk.check_motion_params(model, hypotheses, threshold, seed))
+
+    def motion(self, stream: int = 0) -> Motion:
+        """the last push's Motion: rows t-1 -> t; status 0 after frame 0 (synchronises `stream`)"""
+        m, inl, cnt = self._t.read_motion(stream)
+        return Motion(m.reshape(2, 3), inl.astype(bool), int(cnt[0]), int(cnt[1]), int(cnt[2]))
+
+    def motion_device(self):
+        """device addresses (model [6], inlier [K], counts [3]) of the last push's motion, valid until the next push"""
+        return self._t.motion_device()
 
     @property
     def frame_index(self) -> int:

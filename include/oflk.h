@@ -547,6 +547,77 @@ int oflk_tracker_motion_device(const oflk_tracker *tr, const float **d_model, co
 /* copy it to host arrays (each may be NULL); synchronises `stream` */
 int oflk_tracker_read_motion(oflk_tracker *tr, float *model, unsigned char *inlier, int *counts, void *stream);
 
+/* ---- video stabilisation: a smoothed trajectory of the step models and an affine warp of whole frames ------------------ */
+/* The statement (tests/stabilize_model.py).  Every operation is float64 unless stated and rounded on its own, in the order
+ * written; nothing is contracted and the device computes no transcendental.
+ * Trajectory: one correction per frame from the T-1 step models.
+ *   inputs         model [T-1][6] float32 [a00 a01 tx; a10 a11 ty], step s mapping frame s to frame s+1, as
+ *                  oflk_tracks_motion writes it;  counts [T-1][3] or NULL;  weights[0 .. r] float64, finite and positive,
+ *                  formed by the caller on the host (as oflk_build_pyramid_w takes its Gaussian table);  the radius r,
+ *                  0 <= r <= OFLK_STABILIZE_MAX_RADIUS;  T >= 1 (T == 1: model may be NULL)
+ *   inverse        of [a00 a01 tx; a10 a11 ty]:  det = a00 a11 - a01 a10;  i00 = a11 / det, i01 = -a01 / det,
+ *                  i10 = -a10 / det, i11 = a00 / det;  itx = -(i00 tx + i01 ty), ity = -(i10 tx + i11 ty)
+ *   step s         A_s = the six coefficients as double, B_s = its inverse.  The step is held when counts[s][2] == 0, a
+ *                  coefficient is not finite, det == 0 or a coefficient of B_s is not finite: then A_s = B_s = identity (the
+ *                  camera is taken to stand still across a step that could not be fitted) and held[s] = 1, else 0
+ *   composition    C = A o F (F first):  c00 = A00 F00 + A01 F10, c01 = A00 F01 + A01 F11, ctx = (A00 Ftx + A01 Fty) + Atx,
+ *                  and the second row likewise
+ *   frame t        r_t = min(r, t, T-1-t): the window is always symmetric, so frames 0 and T-1 are never moved and a
+ *                  uniform camera motion is left alone on every frame.  acc = weights[0] I (six products),
+ *                  ws = weights[0], F = G = I;  for i = 1 .. r_t:  F = A_{t+i-1} o F;  acc += weights[i] F;
+ *                  ws += weights[i];  G = B_{t-i} o G;  acc += weights[i] G;  ws += weights[i].  Forward, then backward,
+ *                  inside each i: that order makes a constant integer pan cancel exactly.
+ *                  correction[t] = f32(acc / ws), six quotients;  map[t] = the inverse, by the formula above, of
+ *                  correction[t] converted back to double.  det == 0 or anything not finite: both are the identity
+ *   outputs        correction [T][6] float32 (where frame t's content is moved to), map [T][6] float64 (the output pixel's
+ *                  source position: what oflk_warp_affine takes), held [T-1] bytes (may be NULL)
+ * This is the relative-motion average of Gaussian motion filtering: a scene point's steadied path is the weighted mean of its
+ * path over the window, and the mean of translations is a translation, of similarities a similarity.
+ * Warp: out[f][y][x] = sample(frame f, xs, ys) with xs = (m0 f64(x) + m1 f64(y)) + m2, ys = (m3 f64(x) + m4 f64(y)) + m5,
+ * m = map[f];  sample is the bilinear sample stated above (the reference's warp_image at one float64 point:
+ * map_coordinates, order 1, cval 0, float32 result).  inside[f][y][x] = 1 where 0 <= xs <= W-1 and 0 <= ys <= H-1 (float64,
+ * closed; the taps were read), else 0, and there the sample is 0.  float32 frames give float32; uint8 frames give
+ * (unsigned char) rintf(sample), half to even (a sample of bytes lies in [0, 255]).  Frames are finite, H, W >= 2, and out
+ * does not overlap the frames.  Cropping or zooming the border away (inside is what a caller needs for it), rolling-shutter
+ * correction and homographies are not offered.
+ * Refusals, before any device call: T < 1 (the sequence call: T < 2), F < 1, H or W < 2, a radius outside
+ * [0, OFLK_STABILIZE_MAX_RADIUS], a weight that is not finite and positive, NULL pointers (d_counts, d_held, d_inside and
+ * the sequence call's last four outputs may be NULL; d_model when T == 1), d_map not 8-byte aligned: OFLK_ERR_INVALID;
+ * frames of 2^30 pixels or more: OFLK_ERR_UNSUPPORTED.  The sequence call also refuses whatever
+ * oflk_pyramidal_sequence_klt_sparse_replenish and oflk_tracks_motion refuse, with their codes. */
+#define OFLK_STABILIZE_MAX_RADIUS 64
+/* device form, one launch (one thread per frame, the weights in the launch arguments), asynchronous on `stream`; can be
+ * captured into a graph */
+int oflk_stabilize_trajectory(const float *d_model, const int *d_counts, int T, const double *weights /* host, [radius + 1] */,
+                              int radius, float *d_correction, double *d_map, unsigned char *d_held, void *stream);
+/* device form, one launch for the F frames: d_frames, d_out [F][H][W] (uint8 when u8), d_map [F][6] float64, d_inside
+ * [F][H][W] bytes or NULL.  Asynchronous on `stream`. */
+int oflk_warp_affine(const void *d_frames, int u8, int F, int H, int W, const double *d_map, void *d_out,
+                     unsigned char *d_inside, void *stream);
+/* host arrays, synchronous.  The warp goes in chunks of at most 64 frames; frames are independent, so the result does not
+ * depend on the cut. */
+int oflk_stabilize_trajectory_host(const float *model, const int *counts, int T, const double *weights, int radius,
+                                   float *correction, double *map, unsigned char *held);
+int oflk_warp_affine_host(const float *frames, int F, int H, int W, const double *map, float *out, unsigned char *inside);
+int oflk_warp_affine_host_u8(const unsigned char *frames, int F, int H, int W, const double *map, unsigned char *out,
+                             unsigned char *inside);
+/* Frames in, steadied frames out.  By statement, byte for byte: oflk_pyramidal_sequence_klt_sparse_replenish on the frames,
+ * oflk_tracks_motion on its rows with t0 = 0, oflk_stabilize_trajectory on the models and counts, oflk_warp_affine of the
+ * frames under its maps.  Pass 1 is the replenish call's chunk loop, from which only rows come down; then the fit and the
+ * trajectory of all T frames run at once on the rows (a few KB per frame); pass 2 sends the frames up again in chunks and
+ * the steadied frames come down.  Nothing of the sequence's size is ever on the device.
+ * out [T][H][W] in the input type;  correction [T][6], model_out [T-1][6], counts_out [T-1][3], held [T-1]: each may be
+ * NULL. */
+int oflk_stabilize_sequence(const float *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
+                            float beta, float max_residual, float quality_level, float min_distance, int max_corners,
+                            int detect_every, int model, int hypotheses, float threshold, unsigned seed, const double *weights,
+                            int radius, float *out, float *correction, float *model_out, int *counts_out, unsigned char *held);
+int oflk_stabilize_sequence_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size, int iters,
+                               float alpha, float beta, float max_residual, float quality_level, float min_distance,
+                               int max_corners, int detect_every, int model, int hypotheses, float threshold, unsigned seed,
+                               const double *weights, int radius, unsigned char *out, float *correction, float *model_out,
+                               int *counts_out, unsigned char *held);
+
 /* Rehearsal of the chunk queue above on a box with fewer GPUs than workers (tests): `workers` > 0 makes the *_multi entry
  * points run that many queue workers, worker i on device i % n_gpus (workers of one device take turns on it); 0 restores
  * one worker per device.  Results do not change. */

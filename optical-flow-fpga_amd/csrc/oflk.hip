@@ -11,6 +11,7 @@
 #include "oflk_sparse.hpp"
 #include "oflk_tracker.hpp"
 #include "oflk_motion.hpp"
+#include "oflk_stabilize.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -3696,6 +3697,236 @@ OFLK_API int oflk_estimate_motion_host(const float *src, const float *dst, const
         (rc = call.to_host(counts, d_cnt, 3 * (size_t)S)))
         return rc;
     return call.sync();
+}
+
+// =============================================================================
+// video stabilisation: the smoothed trajectory and the affine warp (oflk_stabilize.hpp)
+// =============================================================================
+namespace {
+int check_stab_window(const double *weights, int radius)
+{
+    if (radius < 0 || radius > OFLK_STABILIZE_MAX_RADIUS)
+        return fail(OFLK_ERR_INVALID, "radius must be in [0, %d] (got %d)", OFLK_STABILIZE_MAX_RADIUS, radius);
+    if (!weights) return fail(OFLK_ERR_INVALID, "NULL weights");
+    for (int i = 0; i <= radius; i++)
+        if (!(std::isfinite(weights[i]) && weights[i] > 0.0))
+            return fail(OFLK_ERR_INVALID, "weights[%d] must be finite and > 0 (got %g)", i, weights[i]);
+    return OFLK_OK;
+}
+
+int check_trajectory(const void *model, int T, const double *weights, int radius, const void *correction, const void *map)
+{
+    if (T < 1) return fail(OFLK_ERR_INVALID, "T must be >= 1 (got %d)", T);
+    if (int rc = check_stab_window(weights, radius)) return rc;
+    if ((T > 1 && !model) || !correction || !map) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    return OFLK_OK;
+}
+
+// the one launch of the trajectory on stream s; the arguments are checked
+int trajectory_launch(const float *d_model, const int *d_counts, int T, const double *weights, int radius, float *d_correction,
+                      double *d_map, unsigned char *d_held, hipStream_t s)
+{
+    StabWeights wt{};
+    for (int i = 0; i <= radius; i++) wt.w[i] = weights[i];
+    hipLaunchKernelGGL(k_stab_trajectory, dim3((unsigned)((T + kStabBlock - 1) / kStabBlock)), dim3(kStabBlock), 0, s, d_model,
+                       d_counts, T, radius, wt, d_correction, d_map, d_held);
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+
+int check_warp_affine(const void *frames, int F, int H, int W, const void *map, const void *out)
+{
+    if (F < 1) return fail(OFLK_ERR_INVALID, "F must be >= 1 (got %d)", F);
+    if (H < 2 || W < 2) return fail(OFLK_ERR_INVALID, "H and W must be >= 2 (got %d x %d)", H, W);
+    if (!frames || !map || !out) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    return check_hw(frames, out, H, W);
+}
+
+// the one launch of the warp of F frames on stream s; the arguments are checked
+template <class PIX>
+int warp_affine_launch(const PIX *d_frames, int F, int H, int W, const double *d_map, PIX *d_out, unsigned char *d_inside,
+                       hipStream_t s)
+{
+    WarpAffineArgs<PIX> a{};
+    a.in = d_frames; a.map = d_map; a.out = d_out; a.inside = d_inside;
+    a.F = F; a.H = H; a.W = W;
+    const bool vec = W % kWarpPx == 0 && aligned(d_out, (unsigned)(kWarpPx * sizeof(PIX))) && (!d_inside || aligned(d_inside, kWarpPx));
+    const dim3 grid((unsigned)((H + 3) / 4), (unsigned)((W + 64 * kWarpPx - 1) / (64 * kWarpPx)), (unsigned)std::min(F, 65535));
+    if (vec)
+        hipLaunchKernelGGL((k_warp_affine<PIX, true>), grid, dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL((k_warp_affine<PIX, false>), grid, dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+
+// F host frames under the device maps d_map [F][6], in chunks of frames through one pair of device buffers: a chunk goes up,
+// is warped and comes down.  Frames are independent, so the result does not depend on the cut.
+template <class PIX>
+int warp_affine_chunks(HostCall &call, const PIX *frames, int F, int H, int W, const double *d_map, PIX *out, unsigned char *inside)
+{
+    const int C = sparse_chunk_pairs(F, H, W);
+    const size_t plane = (size_t)H * W;
+    PIX *d_in = nullptr, *d_out = nullptr;
+    unsigned char *d_inside = nullptr;
+    int rc;
+    if ((rc = call.alloc(&d_in, (size_t)C * plane)) || (rc = call.alloc(&d_out, (size_t)C * plane)) ||
+        (rc = call.alloc(&d_inside, (size_t)C * plane, inside != nullptr)))
+        return rc;
+    for (int f0 = 0; f0 < F; f0 += C) {
+        const int n = std::min(C, F - f0);
+        const size_t o = (size_t)f0 * plane, len = (size_t)n * plane;
+        if ((rc = call.to_device(d_in, frames + o, len)) ||
+            (rc = warp_affine_launch<PIX>(d_in, n, H, W, d_map + 6 * (size_t)f0, d_out, d_inside, nullptr)) ||
+            (rc = call.to_host(out + o, d_out, len)) || (inside && (rc = call.to_host(inside + o, d_inside, len))) ||
+            (rc = call.sync()))
+            return rc;
+    }
+    return OFLK_OK;
+}
+
+template <class PIX>
+int warp_affine_host(const PIX *frames, int F, int H, int W, const double *map, PIX *out, unsigned char *inside)
+{
+    int rc = check_warp_affine(frames, F, H, W, map, out);
+    if (rc) return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    double *d_map = nullptr;
+    if ((rc = call.upload(&d_map, map, 6 * (size_t)F))) return rc;
+    return warp_affine_chunks<PIX>(call, frames, F, H, W, d_map, out, inside);
+}
+
+// oflk_stabilize_sequence: pass 1 is the replenish call itself (its chunk loop; only rows come down, into this call's own
+// arrays); the rows go up again for the fit and the trajectory of all T frames, and pass 2 warps the frames chunk by chunk
+template <class PIX>
+int stabilize_sequence(const PIX *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
+                       float max_residual, float q, float md, int K, int detect_every, int model, int hypotheses, float threshold,
+                       unsigned seed, const double *weights, int radius, PIX *out, float *correction, float *model_out,
+                       int *counts_out, unsigned char *held)
+{
+    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
+    int rc = check_warp_affine(frames, T, H, W, frames, out);
+    if (rc || (rc = check_motion(model, hypotheses, threshold)) || (rc = check_stab_window(weights, radius))) return rc;
+    // the replenish call's own refusals, ahead of this call's arrays (it repeats them)
+    if (detect_every < 1) return fail(OFLK_ERR_INVALID, "detect_every must be >= 1 (got %d)", detect_every);
+    if ((rc = check_select(q, md, K)) || (rc = check_sparse_test(alpha, beta, max_residual)) ||
+        (rc = check_sparse_config(H, W, levels, window_size, iters)))
+        return rc;
+    const size_t row = (size_t)K, nT = (size_t)T, S = nT - 1;
+    std::vector<float> tracks;
+    std::vector<unsigned char> visible, born;
+    std::vector<int> detected;
+    try {
+        tracks.resize(nT * 2 * row);
+        visible.resize(nT * row);
+        born.resize(nT * row);
+        detected.resize(nT);
+    } catch (const std::exception &) {
+        return fail(OFLK_ERR_NOMEM, "no host memory for the rows of %d frames of %d slots", T, K);
+    }
+    if ((rc = sequence_klt_sparse_replenish<PIX>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, q, md, K,
+                                                 detect_every, tracks.data(), visible.data(), born.data(), detected.data(),
+                                                 nullptr)))
+        return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    float *d_tr, *d_model, *d_corr;
+    unsigned char *d_vis, *d_born, *d_inl, *d_held;
+    char *d_ws;
+    int *d_cnt;
+    double *d_map;
+    if ((rc = call.upload(&d_tr, (const float *)tracks.data(), nT * 2 * row)) ||
+        (rc = call.upload(&d_vis, (const unsigned char *)visible.data(), nT * row)) ||
+        (rc = call.upload(&d_born, (const unsigned char *)born.data(), nT * row)) ||
+        (rc = call.alloc(&d_ws, motion_ws(nullptr, T - 1, K, hypotheses).bytes)) || (rc = call.alloc(&d_model, 6 * S)) ||
+        (rc = call.alloc(&d_inl, S * row)) || (rc = call.alloc(&d_cnt, 3 * S)) || (rc = call.alloc(&d_corr, 6 * nT)) ||
+        (rc = call.alloc(&d_map, 6 * nT)) || (rc = call.alloc(&d_held, S)))
+        return rc;
+    const MotionIn in{d_tr, d_tr + 2 * row, d_vis, d_vis + row, d_born + row};
+    if ((rc = motion_launch(in, T - 1, K, 0u, model, hypotheses, threshold, seed, motion_ws(d_ws, T - 1, K, hypotheses), d_model,
+                            d_inl, d_cnt, nullptr)) ||
+        (rc = trajectory_launch(d_model, d_cnt, T, weights, radius, d_corr, d_map, d_held, nullptr)))
+        return rc;
+    if ((correction && (rc = call.to_host(correction, d_corr, 6 * nT))) || (model_out && (rc = call.to_host(model_out, d_model, 6 * S))) ||
+        (counts_out && (rc = call.to_host(counts_out, d_cnt, 3 * S))) || (held && (rc = call.to_host(held, d_held, S))))
+        return rc;
+    return warp_affine_chunks<PIX>(call, frames, T, H, W, d_map, out, nullptr);
+}
+}  // namespace
+
+OFLK_API int oflk_stabilize_trajectory(const float *d_model, const int *d_counts, int T, const double *weights, int radius,
+                                       float *d_correction, double *d_map, unsigned char *d_held, void *stream)
+{
+    if (int rc = check_trajectory(d_model, T, weights, radius, d_correction, d_map)) return rc;
+    if (!aligned(d_map, 8)) return fail(OFLK_ERR_INVALID, "d_map must be 8-byte aligned");
+    return trajectory_launch(d_model, d_counts, T, weights, radius, d_correction, d_map, d_held, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_warp_affine(const void *d_frames, int u8, int F, int H, int W, const double *d_map, void *d_out,
+                              unsigned char *d_inside, void *stream)
+{
+    if (int rc = check_warp_affine(d_frames, F, H, W, d_map, d_out)) return rc;
+    if (!aligned(d_map, 8)) return fail(OFLK_ERR_INVALID, "d_map must be 8-byte aligned");
+    if (!u8 && (!aligned(d_frames, 4) || !aligned(d_out, 4))) return fail(OFLK_ERR_INVALID, "float32 frames must be 4-byte aligned");
+    return u8 ? warp_affine_launch<unsigned char>((const unsigned char *)d_frames, F, H, W, d_map, (unsigned char *)d_out, d_inside,
+                                                  (hipStream_t)stream)
+              : warp_affine_launch<float>((const float *)d_frames, F, H, W, d_map, (float *)d_out, d_inside, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_stabilize_trajectory_host(const float *model, const int *counts, int T, const double *weights, int radius,
+                                            float *correction, double *map, unsigned char *held)
+{
+    int rc = check_trajectory(model, T, weights, radius, correction, map);
+    if (rc) return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const size_t nT = (size_t)T, S = nT - 1;
+    float *d_model = nullptr, *d_corr;
+    int *d_cnt = nullptr;
+    double *d_map;
+    unsigned char *d_held;
+    if ((S && (rc = call.upload(&d_model, model, 6 * S))) || (S && counts && (rc = call.upload(&d_cnt, counts, 3 * S))) ||
+        (rc = call.alloc(&d_corr, 6 * nT)) || (rc = call.alloc(&d_map, 6 * nT)) || (rc = call.alloc(&d_held, S, held && S)))
+        return rc;
+    if ((rc = trajectory_launch(d_model, d_cnt, T, weights, radius, d_corr, d_map, d_held, nullptr))) return rc;
+    if ((rc = call.to_host(correction, d_corr, 6 * nT)) || (rc = call.to_host(map, d_map, 6 * nT)) ||
+        (d_held && (rc = call.to_host(held, d_held, S))))
+        return rc;
+    return call.sync();
+}
+
+OFLK_API int oflk_warp_affine_host(const float *frames, int F, int H, int W, const double *map, float *out, unsigned char *inside)
+{
+    return warp_affine_host<float>(frames, F, H, W, map, out, inside);
+}
+
+OFLK_API int oflk_warp_affine_host_u8(const unsigned char *frames, int F, int H, int W, const double *map, unsigned char *out,
+                                      unsigned char *inside)
+{
+    return warp_affine_host<unsigned char>(frames, F, H, W, map, out, inside);
+}
+
+OFLK_API int oflk_stabilize_sequence(const float *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
+                                     float beta, float max_residual, float quality_level, float min_distance, int max_corners,
+                                     int detect_every, int model, int hypotheses, float threshold, unsigned seed,
+                                     const double *weights, int radius, float *out, float *correction, float *model_out,
+                                     int *counts_out, unsigned char *held)
+{
+    return stabilize_sequence<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, quality_level,
+                                     min_distance, max_corners, detect_every, model, hypotheses, threshold, seed, weights, radius, out,
+                                     correction, model_out, counts_out, held);
+}
+
+OFLK_API int oflk_stabilize_sequence_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                        float alpha, float beta, float max_residual, float quality_level, float min_distance,
+                                        int max_corners, int detect_every, int model, int hypotheses, float threshold,
+                                        unsigned seed, const double *weights, int radius, unsigned char *out, float *correction,
+                                        float *model_out, int *counts_out, unsigned char *held)
+{
+    return stabilize_sequence<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, quality_level,
+                                             min_distance, max_corners, detect_every, model, hypotheses, threshold, seed, weights,
+                                             radius, out, correction, model_out, counts_out, held);
 }
 
 // =============================================================================

@@ -1,0 +1,201 @@
+// oflk_stabilize.hpp -- gfx950 device code of video stabilisation (oflk_stabilize_trajectory, oflk_warp_affine and the
+// sequence call made of them): the smoothed trajectory of the global motion's step models, and the resampling of whole
+// frames under one 2 x 3 map each.
+//
+// The statement is tests/stabilize_model.py (include/oflk.h repeats it).  Everything here is float64 in that file's
+// operation order, every operation rounded on its own; nothing is contracted and there is no transcendental: the window's
+// weights come from the host.
+//
+//   k_stab_trajectory   one thread per frame: the serial chain of at most 2 x 64 compositions of its window.  A thread
+//                       inverts the steps it needs itself, so there is no workspace, no atomics and nothing passes
+//                       between threads; the weights travel by value in the launch arguments, so the launch needs no
+//                       upload and can be captured
+//   k_warp_affine<PIX, VEC>  one launch for F frames.  A lane owns kWarpPx consecutive output pixels of a row.  VEC (the row
+//                       length a multiple of kWarpPx and the bases aligned to a lane's store) stores them as one float4
+//                       (float) or one dword (bytes, and the inside mask); every other shape and alignment runs the
+//                       other instantiation, which stores element by element.  The four taps of a pixel are
+//                       bilinear_taps / bilinear_finish, gathered through the cache as k_warp's: an affine image of a
+//                       row segment is a row segment
+#pragma once
+#include "oflk_kernels.hpp"
+
+#pragma clang fp contract(off)
+
+namespace oflk {
+
+constexpr int kStabBlock = 64;   // k_stab_trajectory's block
+constexpr int kWarpPx = 4;       // consecutive output pixels of a lane of k_warp_affine
+
+struct StabWeights {
+    double w[OFLK_STABILIZE_MAX_RADIUS + 1];
+};
+
+__device__ __forceinline__ void stab_identity(double (&a)[6])
+{
+    a[0] = 1.0; a[1] = 0.0; a[2] = 0.0;
+    a[3] = 0.0; a[4] = 1.0; a[5] = 0.0;
+}
+
+// b = the inverse of [a00 a01 tx; a10 a11 ty]; false: a zero determinant or a coefficient that is not finite
+__device__ __forceinline__ bool stab_invert(const double (&a)[6], double (&b)[6])
+{
+    const double det = a[0] * a[4] - a[1] * a[3];
+    b[0] = a[4] / det;
+    b[1] = -a[1] / det;
+    b[3] = -a[3] / det;
+    b[4] = a[0] / det;
+    b[2] = -(b[0] * a[2] + b[1] * a[5]);
+    b[5] = -(b[3] * a[2] + b[4] * a[5]);
+    bool ok = !(det == 0.0);
+    for (int k = 0; k < 6; k++) ok = ok && __builtin_isfinite(b[k]);
+    return ok;
+}
+
+// step s and its inverse, both the identity when the step is held; returns held
+__device__ __forceinline__ bool stab_step(const float *__restrict__ model, const int *__restrict__ counts, size_t s, double (&a)[6],
+                                          double (&b)[6])
+{
+    bool ok = !counts || counts[3 * s + 2] != 0;
+    for (int k = 0; k < 6; k++) {
+        a[k] = (double)model[6 * s + k];
+        ok = ok && __builtin_isfinite(a[k]);
+    }
+    ok = stab_invert(a, b) && ok;
+    if (!ok) {
+        stab_identity(a);
+        stab_identity(b);
+    }
+    return !ok;
+}
+
+// f = a o f: apply f, then a
+__device__ __forceinline__ void stab_compose(const double (&a)[6], double (&f)[6])
+{
+    const double c0 = a[0] * f[0] + a[1] * f[3];
+    const double c1 = a[0] * f[1] + a[1] * f[4];
+    const double c2 = (a[0] * f[2] + a[1] * f[5]) + a[2];
+    const double c3 = a[3] * f[0] + a[4] * f[3];
+    const double c4 = a[3] * f[1] + a[4] * f[4];
+    const double c5 = (a[3] * f[2] + a[4] * f[5]) + a[5];
+    f[0] = c0; f[1] = c1; f[2] = c2;
+    f[3] = c3; f[4] = c4; f[5] = c5;
+}
+
+// ---- the trajectory: grid (ceil(T / kStabBlock)), block kStabBlock ----
+__global__ __launch_bounds__(kStabBlock) void k_stab_trajectory(const float *__restrict__ model, const int *__restrict__ counts,
+                                                                int T, int radius, StabWeights wt, float *__restrict__ correction,
+                                                                double *__restrict__ map, unsigned char *__restrict__ held)
+{
+    const unsigned t = blockIdx.x * (unsigned)kStabBlock + threadIdx.x;
+    if (t >= (unsigned)T) return;
+    double a[6], b[6];
+    if (t + 1 < (unsigned)T) {
+        const bool h = stab_step(model, counts, t, a, b);
+        if (held) held[t] = h ? 1 : 0;
+    }
+    const int rt = min(radius, (int)min(t, (unsigned)T - 1u - t));
+    const double w0 = wt.w[0];
+    double acc[6] = {w0 * 1.0, w0 * 0.0, w0 * 0.0, w0 * 0.0, w0 * 1.0, w0 * 0.0};
+    double ws = w0;
+    double f[6], g[6];
+    stab_identity(f);
+    stab_identity(g);
+    for (int i = 1; i <= rt; i++) {
+        const double w = wt.w[i];
+        stab_step(model, counts, (size_t)t + (size_t)i - 1, a, b);   // frame t to frame t + i
+        stab_compose(a, f);
+        for (int k = 0; k < 6; k++) acc[k] = acc[k] + w * f[k];
+        ws = ws + w;
+        stab_step(model, counts, (size_t)t - (size_t)i, a, b);       // frame t to frame t - i
+        stab_compose(b, g);
+        for (int k = 0; k < 6; k++) acc[k] = acc[k] + w * g[k];
+        ws = ws + w;
+    }
+    float c[6];
+    double cd[6], m[6];
+    bool ok = true;
+    for (int k = 0; k < 6; k++) {
+        c[k] = __double2float_rn(acc[k] / ws);
+        ok = ok && __builtin_isfinite(c[k]);
+        cd[k] = (double)c[k];
+    }
+    ok = stab_invert(cd, m) && ok;
+    if (!ok) {
+        stab_identity(cd);
+        stab_identity(m);
+    }
+    for (int k = 0; k < 6; k++) {
+        correction[6 * (size_t)t + k] = (float)cd[k];
+        map[6 * (size_t)t + k] = m[k];
+    }
+}
+
+// ---- the warp: grid (ceil(H / 4), ceil(W / (64 kWarpPx)), min(F, 65535)), block 256 = 4 rows of 64 lanes ----
+template <class PIX>
+struct WarpAffineArgs {
+    const PIX *in;            // [F][H][W]
+    const double *map;        // [F][6]
+    PIX *out;                 // [F][H][W]
+    unsigned char *inside;    // [F][H][W] or NULL
+    int F, H, W;
+};
+
+__device__ __forceinline__ float warp_store_value(float v, float) { return v; }
+__device__ __forceinline__ unsigned char warp_store_value(float v, unsigned char) { return (unsigned char)rintf(v); }
+
+// VEC: W % kWarpPx == 0 and out (and inside, when given) aligned to a lane's store, so every lane owns kWarpPx whole pixels
+// and stores them at once.  The two forms are two kernels: in one, the compiler folds the wide store into the tail's.
+template <class PIX, bool VEC>
+__global__ __launch_bounds__(256) void k_warp_affine(WarpAffineArgs<PIX> a)
+{
+    const int x0 = ((int)blockIdx.y * 64 + (int)(threadIdx.x & 63)) * kWarpPx;
+    const int y = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (x0 >= a.W || y >= a.H) return;
+    const size_t plane = (size_t)a.H * (size_t)a.W;
+    const size_t row = (size_t)y * (size_t)a.W + (size_t)x0;
+    const double fy = (double)y, Wm1 = (double)(a.W - 1), Hm1 = (double)(a.H - 1);
+    for (int f = blockIdx.z; f < a.F; f += gridDim.z) {
+        const double *__restrict__ m = a.map + 6 * (size_t)f;
+        const double m0 = m[0], m2 = m[2], m3 = m[3], m5 = m[5];
+        const double bx = m[1] * fy, by = m[4] * fy;
+        const PIX *__restrict__ img = a.in + (size_t)f * plane;
+        PIX v[kWarpPx];
+        unsigned char in[kWarpPx];
+#pragma unroll
+        for (int k = 0; k < kWarpPx; k++) {   // a pixel past the row's end is computed (its taps are clamped) and not stored
+            const double fx = (double)(x0 + k);
+            const double xs = (m0 * fx + bx) + m2;
+            const double ys = (m3 * fx + by) + m5;
+            const bool ok = xs >= 0.0 && xs <= Wm1 && ys >= 0.0 && ys <= Hm1;
+            const BilinearTaps t = bilinear_taps(a.H, a.W, ys, xs);
+            const float s = bilinear_finish(t, ld_pix<PIX>(img, (unsigned)t.i00), ld_pix<PIX>(img, (unsigned)t.i01),
+                                            ld_pix<PIX>(img, (unsigned)t.i10), ld_pix<PIX>(img, (unsigned)t.i11));
+            v[k] = warp_store_value(ok ? s : 0.0f, PIX());
+            in[k] = ok ? 1 : 0;
+        }
+        PIX *__restrict__ dst = a.out + (size_t)f * plane + row;
+        if constexpr (VEC) {
+            if constexpr (sizeof(PIX) == 4) {
+                *reinterpret_cast<float4 *>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+            } else {
+                *reinterpret_cast<unsigned *>(dst) = (unsigned)v[0] | ((unsigned)v[1] << 8) | ((unsigned)v[2] << 16) | ((unsigned)v[3] << 24);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < kWarpPx; k++)
+                if (x0 + k < a.W) dst[k] = v[k];
+        }
+        if (a.inside) {
+            unsigned char *__restrict__ di = a.inside + (size_t)f * plane + row;
+            if constexpr (VEC) {
+                *reinterpret_cast<unsigned *>(di) = (unsigned)in[0] | ((unsigned)in[1] << 8) | ((unsigned)in[2] << 16) | ((unsigned)in[3] << 24);
+            } else {
+#pragma unroll
+                for (int k = 0; k < kWarpPx; k++)
+                    if (x0 + k < a.W) di[k] = in[k];
+            }
+        }
+    }
+}
+
+}  // namespace oflk

@@ -26,6 +26,7 @@ OFLK_ERR_NOMEM = -5
 
 _f32p = ctypes.POINTER(ctypes.c_float)
 _i32p = ctypes.POINTER(ctypes.c_int)
+_f64p = ctypes.POINTER(ctypes.c_double)
 _vp = ctypes.c_void_p
 
 # every exported symbol of include/oflk.h: name -> (restype, argtypes)
@@ -123,6 +124,13 @@ SIGNATURES = {
     "oflk_tracker_set_motion": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_uint]),
     "oflk_tracker_motion_device": (ctypes.c_int, [_vp] + [ctypes.POINTER(_vp)] * 3),
     "oflk_tracker_read_motion": (ctypes.c_int, [_vp, _f32p, _vp, _i32p, _vp]),
+    "oflk_stabilize_trajectory": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _f64p, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "oflk_warp_affine": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_vp] * 4),
+    "oflk_stabilize_trajectory_host": (ctypes.c_int, [_f32p, _i32p, ctypes.c_int, _f64p, ctypes.c_int, _f32p, _f64p, _vp]),
+    "oflk_warp_affine_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 3 + [_f64p, _f32p, _vp]),
+    "oflk_warp_affine_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [_f64p, _vp, _vp]),
+    "oflk_stabilize_sequence": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int, _f32p, _f32p, _f32p, _i32p, _vp]),
+    "oflk_stabilize_sequence_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int, _vp, _f32p, _f32p, _i32p, _vp]),
     "oflk_shard_range": (None, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, _i32p]),
     "oflk_single_scale_fp16": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, _f32p, _f32p]),
     "oflk_rtl_stream_length": (ctypes.c_long, [ctypes.c_int, ctypes.c_int]),
@@ -616,6 +624,71 @@ def estimate_motion_host(src: np.ndarray, dst: np.ndarray, valid: Optional[np.nd
                                           int(model), int(hypotheses), float(threshold), int(seed), ptr(out), inl.ctypes.data,
                                           cnt.ctypes.data_as(_i32p)))
     return out, inl, cnt
+
+
+STABILIZE_MAX_RADIUS = 64
+
+
+def stabilize_weights(radius, sigma=None) -> np.ndarray:
+    """The window of the trajectory filter as the C ABI takes it: radius + 1 float64 Gaussian weights
+    exp(-0.5 (i / sigma)^2), sigma defaulting to radius / 2 (1.0 for radius 0), formed here on the host.  ValueError for a
+    radius outside [0, STABILIZE_MAX_RADIUS], a sigma that is not finite and positive, or a weight that underflows to 0."""
+    if isinstance(radius, bool) or int(radius) != radius or not 0 <= int(radius) <= STABILIZE_MAX_RADIUS:
+        raise ValueError(f"radius must be an integer in [0, {STABILIZE_MAX_RADIUS}], got {radius!r}")
+    radius = int(radius)
+    if sigma is None:
+        sigma = radius / 2 if radius > 0 else 1.0
+    sigma = float(sigma)
+    if not (np.isfinite(sigma) and sigma > 0):
+        raise ValueError(f"sigma must be finite and > 0, got {sigma!r}")
+    w = np.exp(-0.5 * (np.arange(radius + 1) / sigma) ** 2)
+    if not (np.isfinite(w).all() and (w > 0).all()):
+        raise ValueError(f"sigma {sigma!r} is too small for radius {radius}: a weight underflows to 0")
+    return np.ascontiguousarray(w, np.float64)
+
+
+def _f64(a: np.ndarray):
+    return a.ctypes.data_as(_f64p)
+
+
+def stabilize_trajectory(d_model: int, d_counts: int, T: int, weights: np.ndarray, d_correction: int, d_map: int, d_held: int = 0,
+                         stream: int = 0) -> None:
+    """oflk_stabilize_trajectory on device pointers: d_model [T-1][6] float32, d_counts [T-1][3] int32 or 0, the host weights
+    (radius = len - 1) -> d_correction [T][6] float32, d_map [T][6] float64, d_held [T-1] uint8 or 0; asynchronous."""
+    w = np.ascontiguousarray(weights, np.float64)
+    check(lib().oflk_stabilize_trajectory(d_model or None, d_counts or None, int(T), _f64(w), int(w.size) - 1, d_correction or None,
+                                          d_map or None, d_held or None, stream))
+
+
+def warp_affine(d_frames: int, F: int, H: int, W: int, d_map: int, d_out: int, d_inside: int = 0, u8: bool = False,
+                stream: int = 0) -> None:
+    """oflk_warp_affine on device pointers: frames and d_out [F][H][W] (float32, or uint8 with u8), d_map [F][6] float64,
+    d_inside [F][H][W] uint8 or 0; asynchronous."""
+    check(lib().oflk_warp_affine(d_frames or None, int(bool(u8)), int(F), int(H), int(W), d_map or None, d_out or None,
+                                 d_inside or None, stream))
+
+
+def stabilize_trajectory_host(model: np.ndarray, counts: Optional[np.ndarray], T: int, weights: np.ndarray):
+    """oflk_stabilize_trajectory_host: contiguous float32 (T-1, 6) models and optional int32 (T-1, 3) counts in;
+    (correction (T, 6) float32, map (T, 6) float64, held (T-1,) uint8) out"""
+    corr, mp, held = np.empty((T, 6), np.float32), np.empty((T, 6), np.float64), np.empty(max(T - 1, 0), np.uint8)
+    check(lib().oflk_stabilize_trajectory_host(ptr(model) if T > 1 else None, None if counts is None or T < 2 else counts.ctypes.data_as(_i32p),
+                                               int(T), _f64(weights), int(weights.size) - 1, ptr(corr), _f64(mp),
+                                               held.ctypes.data if T > 1 else None))
+    return corr, mp, held
+
+
+def warp_affine_host(frames: np.ndarray, maps: np.ndarray, inside: bool = False):
+    """oflk_warp_affine_host[_u8]: contiguous (F, H, W) float32 or uint8 frames and (F, 6) float64 maps in; the warped
+    frames and, when asked for, the inside mask (else None) out"""
+    F, H, W = frames.shape
+    u8 = frames.dtype == np.uint8
+    out = np.empty_like(frames)
+    ins = np.empty((F, H, W), np.uint8) if inside else None
+    fn = lib().oflk_warp_affine_host_u8 if u8 else lib().oflk_warp_affine_host
+    check(fn(frames.ctypes.data if u8 else ptr(frames), F, H, W, _f64(maps), out.ctypes.data if u8 else ptr(out),
+             None if ins is None else ins.ctypes.data))
+    return out, ins
 
 
 class Tracker:

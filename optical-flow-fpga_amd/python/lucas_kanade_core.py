@@ -291,3 +291,60 @@ def tracks_motion(tracks, visible, born=None, model: str = "similarity", hypothe
             raise ValueError(f"born must have shape {vis.shape}, got {b.shape}")
         ok &= ~b[1:]
     return estimate_motion(tr[:-1], tr[1:], ok, model, hypotheses, threshold, seed, t0)
+
+
+class Trajectory(NamedTuple):
+    """The smoothed camera trajectory of a sequence (stabilize_trajectory)."""
+    correction: np.ndarray  # (T, 2, 3) float32: where frame t's content is moved to; the identity on frames 0 and T-1
+    map: np.ndarray         # (T, 2, 3) float64: its inverse, the source position of an output pixel: what warp_affine takes
+    held: np.ndarray        # (T-1,) bool: the step could not be used (status 0, not finite, singular) and counts as no motion
+
+
+def stabilize_trajectory(models, status=None, radius: int = 15, sigma=None) -> Trajectory:
+    """One steadying correction per frame from the T-1 step models of tracks_motion, on the GPU.
+
+    models: (T-1, 2, 3) or (T-1, 6) float32, step s mapping frame s to frame s+1 (an empty array: T = 1); status: (T-1,) or
+    None -- a step with status 0 is held, like one whose model is not finite or singular: the camera is taken to stand still
+    across it.  Frame t's correction is the Gaussian-weighted mean (weights exp(-0.5 (i / sigma)^2), sigma = radius / 2 by
+    default, formed here with NumPy) of the motions from frame t to frames t-r_t .. t+r_t, with r_t = min(radius, t, T-1-t):
+    the window is always symmetric, so the first and last frame are never moved and a uniform camera motion is left alone.
+    The same inputs give the same bytes; the statement is in include/oflk.h.
+    """
+    w = _oflk.stabilize_weights(radius, sigma)
+    m = np.ascontiguousarray(models, np.float32)
+    if m.ndim == 3 and m.shape[1:] == (2, 3):
+        m = m.reshape(-1, 6)
+    if m.ndim != 2 or m.shape[1] != 6:
+        if m.size:
+            raise ValueError(f"expected models of shape (T-1, 2, 3) or (T-1, 6), got {np.shape(models)}")
+        m = m.reshape(0, 6)
+    S = m.shape[0]
+    counts = None
+    if status is not None:
+        st = np.asarray(status)
+        if st.shape != (S,):
+            raise ValueError(f"status must have shape {(S,)}, got {st.shape}")
+        counts = np.zeros((S, 3), np.int32)
+        counts[:, 2] = st != 0
+    corr, mp, held = _oflk.stabilize_trajectory_host(m, counts, S + 1, w)
+    return Trajectory(corr.reshape(-1, 2, 3), mp.reshape(-1, 2, 3), held.astype(bool))
+
+
+def warp_affine(frames, maps, return_inside: bool = False):
+    """Resample frames under one 2 x 3 map each, on the GPU: out[f, y, x] is the bilinear sample (zero outside) of frame f at
+    (xs, ys) = maps[f] applied to (x, y) in float64.  frames: (H, W) or (F, H, W), float32 or uint8 (uint8 out: rounded half
+    to even); maps: (2, 3) / (6,) for one frame, (F, 2, 3) / (F, 6) for a batch, e.g. Trajectory.map.  With return_inside
+    also the (F, H, W) bool mask of the pixels whose source position lies inside the frame."""
+    single = isinstance(frames, np.ndarray) and frames.ndim == 2
+    arr, _ = _oflk.as_frames(frames)
+    F, H, W = arr.shape
+    if H < 2 or W < 2:
+        raise ValueError(f"frames must be at least 2 x 2, got {H} x {W}")
+    m = np.ascontiguousarray(maps, np.float64)
+    if m.size != 6 * F or m.ndim not in (1, 2, 3) or m.shape[-1] not in (3, 6):
+        raise ValueError(f"expected {F} maps of shape (2, 3) or (6,), got {np.shape(maps)}")
+    out, ins = _oflk.warp_affine_host(arr, m.reshape(F, 6), bool(return_inside))
+    out = out[0] if single else out
+    if not return_inside:
+        return out
+    return out, (ins[0] if single else ins).astype(bool)

@@ -30,7 +30,8 @@ import numpy as np
 import numpy.typing as npt
 
 import _oflk
-from lucas_kanade_core import Motion, estimate_motion, lucas_kanade_single_scale, tracks_motion  # noqa: F401
+from lucas_kanade_core import (Motion, Trajectory, estimate_motion, lucas_kanade_single_scale, stabilize_trajectory,  # noqa: F401
+                               tracks_motion, warp_affine)
 
 SCRIPT_DIR = Path(__file__).resolve().parent
 PROJECT_ROOT = SCRIPT_DIR.parent
@@ -457,6 +458,46 @@ def lucas_kanade_pyramidal_sequence_klt_sparse_replenish(frames, max_corners: in
     _oflk.check(fn(src, T, H, W, L, win, it, a, b, r, q, md, K, min(int(detect_every), 2 ** 31 - 1), _oflk.ptr(tracks),
                    visible.ctypes.data, born.ctypes.data, detected.ctypes.data_as(_oflk._i32p), _oflk.ptr(residual)))
     return SequenceKLTSparseReplenish(tracks, visible.astype(bool), born.astype(bool), detected, residual)
+
+
+class SequenceStabilized(NamedTuple):
+    """Result of lucas_kanade_pyramidal_sequence_stabilize."""
+    frames: np.ndarray      # (T, H, W), the input's type: the steadied frames, zero where the source lies outside the frame
+    correction: np.ndarray  # (T, 2, 3) float32: where frame t's content was moved to (Trajectory.correction)
+    model: np.ndarray       # (T-1, 2, 3) float32: the fitted motion of step t -> t+1; NaN where status is 0
+    status: np.ndarray      # (T-1,) int32: 1 where a model was found
+    held: np.ndarray        # (T-1,) bool: the step counted as no motion
+
+
+def lucas_kanade_pyramidal_sequence_stabilize(frames, max_corners: int, detect_every: int, model: str = "similarity",
+                                              radius: int = 15, sigma=None, hypotheses: int = 256, threshold: float = 1.0,
+                                              seed: int = 0, quality_level: float = 0.01, min_distance: float = 10.0,
+                                              num_levels: int = 3, window_size: int = 5, num_iterations: int = 3,
+                                              alpha: float = 0.01, beta: float = 0.5,
+                                              max_residual: float = 4.0) -> SequenceStabilized:
+    """Frames in, steadied frames out: lucas_kanade_pyramidal_sequence_klt_sparse_replenish on the frames, tracks_motion on
+    its rows, stabilize_trajectory on the models and warp_affine of the frames under its maps, in one call whose
+    intermediate rows stay in the library.  The frames go up twice, chunk by chunk (once to track, once to warp); nothing
+    of the sequence's size is ever on the device.  The black border is not cropped (warp_affine's inside mask tells where
+    it is)."""
+    a, b = _oflk.check_fb_params(alpha, beta)
+    arr, u8 = _oflk.as_sequence(frames)
+    T, H, W = arr.shape
+    L, win, it, r = _oflk.check_sparse_params((H, W), num_levels, window_size, num_iterations, max_residual)
+    K, q, md, win = _oflk.check_feature_params(max_corners, quality_level, min_distance, win)
+    if isinstance(detect_every, bool) or int(detect_every) != detect_every or int(detect_every) < 1:
+        raise ValueError(f"detect_every must be an integer >= 1, got {detect_every!r}")
+    code, hn, thr, sd = _oflk.check_motion_params(model, hypotheses, threshold, seed)
+    w = _oflk.stabilize_weights(radius, sigma)
+    out = np.empty_like(arr)
+    corr, mod = np.empty((T, 6), np.float32), np.empty((T - 1, 6), np.float32)
+    cnt, held = np.empty((T - 1, 3), np.int32), np.empty(T - 1, np.uint8)
+    fn = _oflk.lib().oflk_stabilize_sequence_u8 if u8 else _oflk.lib().oflk_stabilize_sequence
+    _oflk.check(fn(arr.ctypes.data if u8 else _oflk.ptr(arr), T, H, W, L, win, it, a, b, r, q, md, K,
+                   min(int(detect_every), 2 ** 31 - 1), code, hn, thr, sd, _oflk._f64(w), int(w.size) - 1,
+                   out.ctypes.data if u8 else _oflk.ptr(out), _oflk.ptr(corr), _oflk.ptr(mod), cnt.ctypes.data_as(_oflk._i32p),
+                   held.ctypes.data))
+    return SequenceStabilized(out, corr.reshape(T, 2, 3), mod.reshape(T - 1, 2, 3), cnt[:, 2].copy(), held.astype(bool))
 
 
 class TrackerRow(NamedTuple):

@@ -595,7 +595,9 @@ int launch_upsample(oflk_plan *plan, hipStream_t s, const ResampleArgs &r_in, in
     Prof pr(plan, s, KC_UPSAMPLE);
     if (upsample_fits(r.H, r.W, r.Ho, r.Wo)) {
         dim3 grid((r.Wo + kUTW - 1) / kUTW, (r.Ho + kUTH - 1) / kUTH, nimg);
-        hipLaunchKernelGGL(k_upsample, grid, dim3(256), 0, s, r);
+        // a one-row or one-column coarse field keeps run-time tap strides; every other one has them at compile time
+        if (r.H == 1 || r.W == 1) hipLaunchKernelGGL(k_upsample<true>, grid, dim3(256), 0, s, r);
+        else hipLaunchKernelGGL(k_upsample<false>, grid, dim3(256), 0, s, r);
     } else {
         hipLaunchKernelGGL(k_resample<2>, grid_resample(r.Wo, r.Ho, nimg), dim3(256), 0, s, r);
     }

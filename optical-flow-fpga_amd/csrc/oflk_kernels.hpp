@@ -2201,17 +2201,32 @@ __global__ __launch_bounds__(256) void k_pyr_down(PyrArgs a)
 // K4: upsample_flow (lucas_kanade_pyramidal.py:100-138) with the coarse tile staged in
 // LDS.  A block produces 256 x 16 fine outputs of both planes; the coarse cells it
 // samples (at most kUSW columns x kUSH rows per plane) are fetched with coalesced
-// loads once, and the 16 taps per plane of each thread come from LDS (gathering them
-// from global memory made the kernel L1-throughput bound).  Same arithmetic as
+// loads once, and the four taps of an output come from LDS (gathering them from
+// global memory made the kernel L1-throughput bound).  Same arithmetic as
 // k_resample<2> with scaling; the host checks that every block's source span fits
 // (upsample_fits) and falls back to k_resample<2> otherwise.
+// A wave covers one 128-column half of the tile over 8 rows, a lane 2 columns of it: the
+// lanes of a wave read adjacent LDS cells (no bank conflict at a ratio of 2), a row's
+// stores of a wave are one contiguous run, and in a last block column that ends in the
+// left half the waves of the right half leave after the barrier.
 // ---------------------------------------------------------------------------
-constexpr int kUTW = 256, kUTH = 16;  // fine outputs per block: a thread owns 4 (x) by 4 (y) of them
+constexpr int kUTW = 256, kUTH = 16;  // fine outputs per block: a wave owns 128 (x) by 8 (y) of them, a lane 2 (x) by 8 (y)
 constexpr int kUSW = 136, kUSH = 10;  // coarse columns / rows staged per plane
 
+// DEGEN: a coarse field of one row or one column, whose second tap of that axis is the first one again (run-time tap
+// strides); every other field has its four taps at compile-time offsets of one LDS address.
+template <bool DEGEN>
 __global__ __launch_bounds__(256) void k_upsample(ResampleArgs a)
 {
-    __shared__ float s_src[2][kUSH][kUSW];
+    constexpr int TX = 2, TY = 8;               // outputs per lane
+    constexpr int WX = kUTW / (64 * TX);        // waves side by side in the tile
+    constexpr int NC = kUSH * kUSW;             // staged cells
+    static_assert(WX * TX * 64 == kUTW && (256 / 64 / WX) * TY == kUTH, "four waves cover the tile");
+    // the tile as fp64, {u, v} of a cell side by side: a cell is converted once, while staging, and a tap of both
+    // planes is one 16-byte LDS read
+    __shared__ double2 s_cell[NC];
+    __shared__ double s_wy[kUTH][2];            // the y side of the tile's rows, the same for every lane: (wy0, wy1)
+    __shared__ int s_row[kUTH];                 // ... and the LDS cell of tap row 0, or -1 outside
     const int tid = threadIdx.x;
     const int jb = blockIdx.x * kUTW, ib = blockIdx.y * kUTH;
     const int img = blockIdx.z;
@@ -2228,8 +2243,8 @@ __global__ __launch_bounds__(256) void k_upsample(ResampleArgs a)
     if (ib + kUTH >= a.Ho) ylo = min(ylo, max(H - 2, 0));
     if (jb + kUTW >= a.Wo) xlo = min(xlo, max(W - 2, 0));
     if (a.interleaved) {
-        // interleaved {u, v} source: one 8-byte load per cell, split into the two LDS planes
-        constexpr int NL = (kUSH * kUSW + 255) / 256;      // 6 staged cells per thread
+        // interleaved {u, v} source: one 8-byte load per cell, one 16-byte LDS write
+        constexpr int NL = (NC + 255) / 256;               // 6 staged cells per thread
         constexpr int QS = 256 / kUSW, RS = 256 % kUSW;    // (row, column) advance per 256 cells
         const float2 *__restrict__ src = reinterpret_cast<const float2 *>(a.in[0]) + selofs + (size_t)img * ip;
         float2 vals[NL];
@@ -2244,14 +2259,11 @@ __global__ __launch_bounds__(256) void k_upsample(ResampleArgs a)
 #pragma unroll
         for (int k = 0; k < NL; k++) {
             const int e = tid + k * 256;
-            if ((k + 1) * 256 <= kUSH * kUSW || e < kUSH * kUSW) {
-                (&s_src[0][0][0])[e] = vals[k].x;
-                (&s_src[1][0][0])[e] = vals[k].y;
-            }
+            if ((k + 1) * 256 <= NC || e < NC) s_cell[e] = make_double2((double)vals[k].x, (double)vals[k].y);
         }
     } else {
         // coalesced staging: all loads of a thread are issued before the first LDS write
-        constexpr int NL = (2 * kUSH * kUSW + 255) / 256;  // 11 staged cells per thread
+        constexpr int NL = (2 * NC + 255) / 256;           // 11 staged cells per thread
         constexpr int QS = 256 / kUSW, RS = 256 % kUSW;    // (row, column) advance per 256 cells
         float vals[NL];
         int r = tid / kUSW, c = tid - r * kUSW;            // row runs over both planes: 2 * kUSH rows
@@ -2267,26 +2279,40 @@ __global__ __launch_bounds__(256) void k_upsample(ResampleArgs a)
 #pragma unroll
         for (int k = 0; k < NL; k++) {
             const int e = tid + k * 256;
-            if ((k + 1) * 256 <= 2 * kUSH * kUSW || e < 2 * kUSH * kUSW) (&s_src[0][0][0])[e] = vals[k];
+            if ((k + 1) * 256 <= 2 * NC || e < 2 * NC) {
+                const int p = e >= NC ? 1 : 0;
+                (&s_cell[0].x)[2 * (e - p * NC) + p] = (double)vals[k];
+            }
         }
     }
-    __syncthreads();
-
-    const int j0 = jb + (tid & 63) * 4;
-    const int i0 = ib + (tid >> 6) * 4;
-    if (j0 >= a.Wo || i0 >= a.Ho) return;
     // Same sampling as lean_taps (see there): one unsigned compare per axis for the range test,
     // and a sample exactly on the last index is expressed from the cell before it (floor capped at
     // N-2, fraction exactly 1), so the two taps of an axis are always adjacent cells of the staged
-    // tile.  The x side is computed once per thread and reused by its four rows.
+    // tile.  The y side is formed once per block, the x side once per thread and reused by its eight rows.
     const LeanGeom lg = lean_geom(H, W);
-    const int rstep = H > 1 ? kUSW : 0;           // LDS words from tap row 0 to tap row 1
-    const int cstep = W > 1 ? 1 : 0;
-    double wx0[4], wx1[4];
-    int xo[4];
-    bool x_in[4];
+    if (tid < kUTH) {
+        const double y = linspace_at(a.ly, min(ib + tid, a.Ho - 1));
+        const bool y_in = (unsigned long long)__double_as_longlong(y) <= (unsigned long long)__double_as_longlong(lg.Hm1);
+        const double fy = fmin(floor(y), lg.Hm2);
+        const double wy0 = 1.0 - (y - fy);
+        s_wy[tid][0] = wy0;
+        s_wy[tid][1] = 1.0 - wy0;
+        s_row[tid] = y_in ? ((int)fy - ylo) * kUSW : -1;
+    }
+    __syncthreads();
+
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int j0 = jb + (wave % WX * 64 + (tid & 63)) * TX;
+    const int r0 = wave / WX * TY;
+    const int i0 = ib + r0;
+    if (j0 >= a.Wo || i0 >= a.Ho) return;              // at the right edge whole waves leave
+    const int rstep = DEGEN ? (H > 1 ? kUSW : 0) : kUSW;   // LDS cells from tap row 0 to tap row 1
+    const int cstep = DEGEN ? (W > 1 ? 1 : 0) : 1;
+    double wx0[TX], wx1[TX];
+    int xo[TX];
+    bool x_in[TX];
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
+    for (int k = 0; k < TX; k++) {
         const int j = min(j0 + k, a.Wo - 1);
         const double x = linspace_at(a.lx, j);
         x_in[k] = (unsigned long long)__double_as_longlong(x) <= (unsigned long long)__double_as_longlong(lg.Wm1);
@@ -2295,54 +2321,50 @@ __global__ __launch_bounds__(256) void k_upsample(ResampleArgs a)
         wx1[k] = 1.0 - wx0[k];
         xo[k] = x_in[k] ? (int)fx - xlo : 0;
     }
-    const float *__restrict__ tile = &s_src[0][0][0];
     const bool vec = a.vec_store != 0;
 #pragma unroll
-    for (int o = 0; o < 4; o++) {
+    for (int o = 0; o < TY; o++) {
         const int i = i0 + o;
         if (i >= a.Ho) break;
-        const double y = linspace_at(a.ly, i);
-        const bool y_in = (unsigned long long)__double_as_longlong(y) <= (unsigned long long)__double_as_longlong(lg.Hm1);
-        const double fy = fmin(floor(y), lg.Hm2);
-        const double wy0 = 1.0 - (y - fy), wy1 = 1.0 - wy0;
-        const int row0 = y_in ? ((int)fy - ylo) * kUSW : 0;
-        float res[2][4];
+        const double wy0 = s_wy[r0 + o][0], wy1 = s_wy[r0 + o][1];
+        const int row0 = s_row[r0 + o];
+        float res[2][TX];
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const bool inside = y_in & x_in[k];
-            const int o00 = inside ? row0 + xo[k] : 0;
+        for (int k = 0; k < TX; k++) {
+            const bool inside = (row0 >= 0) & x_in[k];
+            const double2 *t = s_cell + (inside ? row0 + xo[k] : 0);
+            const double2 t00 = t[0], t01 = t[cstep], t10 = t[rstep], t11 = t[rstep + cstep];
 #pragma unroll
             for (int p = 0; p < 2; p++) {
-                const float *t = tile + p * (kUSH * kUSW) + o00;
                 double acc, c;
-                c = (double)t[0]; c = c * wy0; acc = c * wx0[k];
-                c = (double)t[cstep]; c = c * wy0; c = c * wx1[k]; acc = acc + c;
-                c = (double)t[rstep]; c = c * wy1; c = c * wx0[k]; acc = acc + c;
-                c = (double)t[rstep + cstep]; c = c * wy1; c = c * wx1[k]; acc = acc + c;
+                c = p ? t00.y : t00.x; c = c * wy0; acc = c * wx0[k];
+                c = p ? t01.y : t01.x; c = c * wy0; c = c * wx1[k]; acc = acc + c;
+                c = p ? t10.y : t10.x; c = c * wy1; c = c * wx0[k]; acc = acc + c;
+                c = p ? t11.y : t11.x; c = c * wy1; c = c * wx1[k]; acc = acc + c;
                 const float r = inside ? (float)acc : 0.0f;
                 res[p][k] = r * a.scale[p];   // fp32 multiply by float32(scale), :135-136
             }
         }
+        // a wave's stores of a row are one contiguous run: 1 KB interleaved, 512 B per plane
         if (a.interleaved) {
-            float2 *__restrict__ dst = reinterpret_cast<float2 *>(a.out[0]) + (size_t)img * op + (size_t)i * a.Wo + j0;
-            if (vec) {   // (i * Wo + j0) * 8 bytes is a multiple of 32
-                reinterpret_cast<float4 *>(dst)[0] = make_float4(res[0][0], res[1][0], res[0][1], res[1][1]);
-                reinterpret_cast<float4 *>(dst)[1] = make_float4(res[0][2], res[1][2], res[0][3], res[1][3]);
+            float2 *__restrict__ dst = reinterpret_cast<float2 *>(a.out[0]) + ((size_t)img * op + (size_t)i * a.Wo) + j0;
+            if (vec) {   // (i * Wo + j0) * 8 bytes is a multiple of 16
+                *reinterpret_cast<float4 *>(dst) = make_float4(res[0][0], res[1][0], res[0][1], res[1][1]);
             } else {
 #pragma unroll
-                for (int k = 0; k < 4; k++)
+                for (int k = 0; k < TX; k++)
                     if (j0 + k < a.Wo) dst[k] = make_float2(res[0][k], res[1][k]);
             }
             continue;
         }
 #pragma unroll
         for (int p = 0; p < 2; p++) {
-            float *__restrict__ dst = a.out[p] + (size_t)img * op + (size_t)i * a.Wo + j0;
+            float *__restrict__ dst = a.out[p] + ((size_t)img * op + (size_t)i * a.Wo) + j0;
             if (vec) {
-                *reinterpret_cast<float4 *>(dst) = make_float4(res[p][0], res[p][1], res[p][2], res[p][3]);
+                *reinterpret_cast<float2 *>(dst) = make_float2(res[p][0], res[p][1]);
             } else {
 #pragma unroll
-                for (int k = 0; k < 4; k++)
+                for (int k = 0; k < TX; k++)
                     if (j0 + k < a.Wo) dst[k] = res[p][k];
             }
         }

@@ -834,6 +834,16 @@ OFLK_API int oflk_pyramid_level_dims(int H, int W, int levels, double scale_fact
 // =============================================================================
 // plan API
 // =============================================================================
+// the largest frames a plan or a tracker takes
+static int check_frame_bounds(int H, int W)
+{
+    if ((size_t)H * (size_t)W >= ((size_t)1 << 29))
+        return fail(OFLK_ERR_UNSUPPORTED, "frames of 2^29 pixels or more are not supported");  // 32-bit byte offsets into float2 planes
+    if (H >= kMaxDim || W >= kMaxDim)
+        return fail(OFLK_ERR_UNSUPPORTED, "frames of 2^23 rows or columns or more are not supported (got %d x %d)", H, W);
+    return OFLK_OK;
+}
+
 OFLK_API int oflk_plan_create(oflk_plan **out, int device, int B, int H, int W, int levels,
                               int window_size, int iters)
 {
@@ -841,13 +851,9 @@ OFLK_API int oflk_plan_create(oflk_plan **out, int device, int B, int H, int W, 
     *out = nullptr;
     if (B < 1) return fail(OFLK_ERR_INVALID, "B must be >= 1");
     if (iters < 0) return fail(OFLK_ERR_INVALID, "iters must be >= 0");
-    if ((size_t)H * (size_t)W >= ((size_t)1 << 29))
-        return fail(OFLK_ERR_UNSUPPORTED, "frames of 2^29 pixels or more are not supported");  // 32-bit byte offsets into float2 planes
-    if (H >= kMaxDim || W >= kMaxDim)
-        return fail(OFLK_ERR_UNSUPPORTED, "frames of 2^23 rows or columns or more are not supported (got %d x %d)", H, W);
     int hw = 0;
-    int rc = window_hw(window_size, &hw);
-    if (rc) return rc;
+    int rc = check_frame_bounds(H, W);
+    if (rc || (rc = window_hw(window_size, &hw))) return rc;
     int dims[2 * OFLK_MAX_LEVELS];
     rc = level_dims(H, W, levels, 0.5, dims);
     if (rc) return rc;
@@ -2341,88 +2347,95 @@ int fb_launch(const float *uf, const float *vf, const float *ub, const float *vb
     return OFLK_OK;
 }
 
-// Both directions of a sequence, host pointers.  Chunks of C pairs (C+1 frames, chunk_pairs) run one after the other on the
-// null stream: the chunk's frames go up, one bidirectional plan pass writes d[0..3] (uf, vf, ub, vb), the flagged pairs of both
-// directions are resolved (counted into t_resolved), the caller's own work on the chunk runs, and the stream is synchronized,
-// as the next chunk reuses the buffers.  The caller's parts:
-//   check()                            its own arguments, after the sequence's and before any device call
-//   setup(call, C)                     its per-call buffers and uploads
-//   chunk(call, b0, nb, d_frames, d)   its work on pairs b0 .. b0+nb-1, whose frames b0 .. b0+nb are in d_frames
-template <class PIXELS, class Check, class Setup, class Chunk>
-int run_sequence_bidir(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, Check check, Setup setup,
-                       Chunk chunk)
+// The frames and the flow configuration of a host sequence call
+struct Seq {
+    const void *frames;   // [T][H][W], uint8 or float32
+    bool u8;
+    int T, H, W, levels, window_size, iters;
+    size_t frame_bytes() const { return (size_t)H * W * (u8 ? 1 : sizeof(float)); }
+};
+
+int check_seq(const Seq &seq)
 {
-    constexpr bool U8 = sizeof(PIXELS) == 1;
-    t_resolved = 0;
-    int rc = check_hw(frames, frames, H, W);
-    if (rc) return rc;
-    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
-    if (levels < 1) return fail(OFLK_ERR_INVALID, "levels must be in [1,%d] (got %d)", OFLK_MAX_LEVELS, levels);
-    if ((rc = check())) return rc;
-    HostCall call;
-    if ((rc = call.begin())) return rc;
-    const int B = T - 1;
-    const size_t plane = (size_t)H * W;
-    const int C = chunk_pairs(B, H, W);
-    PIXELS *d_frames = nullptr;
-    float *d[4];
-    if ((rc = call.alloc(&d_frames, (size_t)(C + 1) * plane))) return rc;
-    for (auto &q : d)
-        if ((rc = call.alloc(&q, (size_t)C * plane))) return rc;
-    if ((rc = setup(call, C))) return rc;
-    for (int b0 = 0; b0 < B; b0 += C) {
-        const int nb = std::min(C, B - b0);
-        oflk_plan *p = nullptr;
-        if ((rc = host_plan(*call.c, call.dev, nb, H, W, levels, window_size, iters, &p))) return rc;
-        if ((rc = call.to_device(d_frames, frames + (size_t)b0 * plane, (size_t)(nb + 1) * plane))) return rc;
-        if ((rc = plan_pyramidal(p, d_frames, d_frames + plane, U8, d[0], d[1], nullptr, true, d[2], d[3]))) return rc;
-        if (iters > 0) {
-            int n_res = 0;
-            if ((rc = resolve_uncertain_fb(p, d_frames, U8, d[0], d[1], d[2], d[3], nullptr, &n_res))) return rc;
-            t_resolved += n_res;
-        }
-        if ((rc = chunk(call, b0, nb, d_frames, d)) || (rc = call.sync())) return rc;
-    }
+    if (int rc = check_hw(seq.frames, seq.frames, seq.H, seq.W)) return rc;
+    if (seq.T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", seq.T);
     return OFLK_OK;
 }
 
-// Both directions of a sequence and their consistency, host pointers: run_sequence_bidir's chunks, one check launch each
+// One chunk of both directions of a sequence on the null stream: the device buffers of C+1 frames and of the four flows
+// of C pairs (chunk_pairs), and what fills them
+struct BidirChunk {
+    char *frames = nullptr;   // [C+1][H][W] of the call's pixels
+    float *d[4] = {};         // uf, vf, ub, vb: [C][H][W] each
+
+    static int check(const Seq &seq)   // what both directions refuse before any device call; t_resolved starts at 0
+    {
+        t_resolved = 0;
+        if (int rc = check_seq(seq)) return rc;
+        if (seq.levels < 1) return fail(OFLK_ERR_INVALID, "levels must be in [1,%d] (got %d)", OFLK_MAX_LEVELS, seq.levels);
+        return OFLK_OK;
+    }
+    int alloc(HostCall &call, const Seq &seq, int C)
+    {
+        int rc = call.alloc(&frames, (size_t)(C + 1) * seq.frame_bytes());
+        for (auto &q : d)
+            if (!rc) rc = call.alloc(&q, (size_t)C * seq.H * seq.W);
+        return rc;
+    }
+    // pairs b0 .. b0+nb-1: their nb+1 frames go up, one bidirectional plan pass writes d, and the flagged pairs of both
+    // directions are resolved (counted into t_resolved)
+    int run(HostCall &call, const Seq &seq, int b0, int nb)
+    {
+        const size_t fb = seq.frame_bytes();
+        oflk_plan *p = nullptr;
+        int rc = host_plan(*call.c, call.dev, nb, seq.H, seq.W, seq.levels, seq.window_size, seq.iters, &p);
+        if (rc || (rc = call.to_device(frames, static_cast<const char *>(seq.frames) + (size_t)b0 * fb, (size_t)(nb + 1) * fb)) ||
+            (rc = plan_pyramidal(p, frames, frames + fb, seq.u8, d[0], d[1], nullptr, true, d[2], d[3])))
+            return rc;
+        int n_res = 0;
+        if (seq.iters > 0 && (rc = resolve_uncertain_fb(p, frames, seq.u8, d[0], d[1], d[2], d[3], nullptr, &n_res))) return rc;
+        t_resolved += n_res;
+        return OFLK_OK;
+    }
+};
+
+// Both directions of a sequence and their consistency, host pointers.  Chunks of C pairs run one after the other on the
+// null stream: BidirChunk fills d[0..3], one check launch follows, everything comes down, and the stream is synchronized,
+// as the next chunk reuses the buffers.
 template <class PIXELS>
 int run_sequence_fb(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
                     float *uf, float *vf, float *ub, float *vb, float *ef, float *eb, unsigned char *qf, unsigned char *qb)
 {
+    const Seq seq{frames, sizeof(PIXELS) == 1, T, H, W, levels, window_size, iters};
     const bool check = ef || eb || qf || qb;
+    int rc = BidirChunk::check(seq);
+    if (rc || (check && (rc = check_fb(uf, vf, ub, vb, T - 1, H, W, alpha, beta, ef, eb, qf, qb)))) return rc;
+    if (!uf || !vf || !ub || !vb) return fail(OFLK_ERR_INVALID, "NULL flow argument");
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const int B = T - 1, C = chunk_pairs(B, H, W);
     const size_t plane = (size_t)H * W;
-    float *d_e[2] = {nullptr, nullptr};
-    unsigned char *d_q[2] = {nullptr, nullptr};
-    auto checks = [&]() -> int {
-        int rc;
-        if (check && (rc = check_fb(uf, vf, ub, vb, T - 1, H, W, alpha, beta, ef, eb, qf, qb))) return rc;
-        if (!uf || !vf || !ub || !vb) return fail(OFLK_ERR_INVALID, "NULL flow argument");
-        return OFLK_OK;
-    };
-    auto setup = [&](HostCall &call, int C) -> int {
-        const size_t n = (size_t)C * plane;
-        int rc;
-        if ((rc = call.alloc(&d_e[0], n, ef)) || (rc = call.alloc(&d_e[1], n, eb)) || (rc = call.alloc(&d_q[0], n, qf)) ||
-            (rc = call.alloc(&d_q[1], n, qb)))
-            return rc;
-        return OFLK_OK;
-    };
-    auto chunk = [&](HostCall &call, int b0, int nb, const PIXELS *, float *const *d) -> int {
+    BidirChunk k{};
+    float *d_e[2];
+    float *const outs[4] = {uf, vf, ub, vb};
+    unsigned char *d_q[2];
+    if ((rc = k.alloc(call, seq, C)) || (rc = call.alloc(&d_e[0], C * plane, ef)) || (rc = call.alloc(&d_e[1], C * plane, eb)) ||
+        (rc = call.alloc(&d_q[0], C * plane, qf)) || (rc = call.alloc(&d_q[1], C * plane, qb)))
+        return rc;
+    for (int b0 = 0; b0 < B; b0 += C) {
+        const int nb = std::min(C, B - b0);
         const size_t off = (size_t)b0 * plane, n = (size_t)nb * plane;
-        int rc;
-        if (check && (rc = fb_launch(d[0], d[1], d[2], d[3], nb, H, W, alpha, beta, d_e[0], d_e[1], d_q[0], d_q[1], nullptr)))
+        if ((rc = k.run(call, seq, b0, nb))) return rc;
+        if (check && (rc = fb_launch(k.d[0], k.d[1], k.d[2], k.d[3], nb, H, W, alpha, beta, d_e[0], d_e[1], d_q[0], d_q[1], nullptr)))
             return rc;
-        float *outs[4] = {uf, vf, ub, vb};
         for (int i = 0; i < 4; i++)
-            if ((rc = call.to_host(outs[i] + off, d[i], n))) return rc;
+            if ((rc = call.to_host(outs[i] + off, k.d[i], n))) return rc;
         if ((ef && (rc = call.to_host(ef + off, d_e[0], n))) || (eb && (rc = call.to_host(eb + off, d_e[1], n))) ||
-            (qf && (rc = call.to_host(qf + off, d_q[0], n))) || (qb && (rc = call.to_host(qb + off, d_q[1], n))))
+            (qf && (rc = call.to_host(qf + off, d_q[0], n))) || (qb && (rc = call.to_host(qb + off, d_q[1], n))) ||
+            (rc = call.sync()))
             return rc;
-        return OFLK_OK;
-    };
-    return run_sequence_bidir<PIXELS>(frames, T, H, W, levels, window_size, iters, checks, setup, chunk);
+    }
+    return OFLK_OK;
 }
 }  // namespace
 
@@ -2857,152 +2870,249 @@ struct TrackRows {   // the device side of every sequence track call: the querie
     int *qt = nullptr;                     // [N]; NULL: every query starts on frame 0
     float *qxy = nullptr, *tr = nullptr;   // [N][2] and [C+1][N][2]
     unsigned char *vis = nullptr;          // [C+1][N]
+    float *res = nullptr;                  // [C+1][N] step residuals, which only the sparse engine writes; NULL: none
 };
 
-// Tracks of a whole sequence, host pointers: run_sequence_bidir's chunks; only the tracks come down.  The calls differ in
-// the frames on which queries come into existence, the detection frames: the multiples of `every` (0: none).  A chunk's
-// pairs are walked in segments cut there.  Before the segment that begins at such a frame s, detect(call, R, s, r, frame)
-// puts new queries (qt, qxy) into R from row r of the chunk; the segment's launch (t0 = s) starts them on its row 0 and
-// continues the others.  A call's other parts: checks(), setup(call, R, C), begin(nb) ahead of a chunk's segments and
-// extras(call, b0, nb, r0) after its rows r0 .. nb have gone down.
-template <class PIXELS, class Checks, class Setup, class Begin, class Detect, class Extras>
-int run_sequence_tracks(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
-                        float beta, int N, float *tracks, unsigned char *visible, int every, Checks checks, Setup setup,
-                        Begin begin, Detect detect, Extras extras)
+// The pairs t0 .. t0+B-1 in segments [s0, e) cut at the multiples of `every`, the detection frames (0: none, one segment):
+// detect(s0, r) ahead of a segment that begins on one, then step(s0, e, r) for every segment; r = s0 - t0 is the segment's
+// first row.  The last row is never a detection row.  64-bit: t0 + B may reach INT_MAX.
+template <class Detect, class Step>
+int walk_segments(int t0, int B, int every, Detect detect, Step step)
 {
-    const size_t row = (size_t)N, plane = (size_t)H * W;
-    int C = 0;   // pairs per chunk (setup)
+    const long long end = (long long)t0 + B;
+    for (long long s0 = t0; s0 < end;) {
+        const long long e = every ? std::min(end, (s0 / every + 1) * every) : end;
+        const int r = (int)(s0 - t0);
+        int rc;
+        if (every && s0 % every == 0 && (rc = detect((int)s0, r))) return rc;
+        if ((rc = step((int)s0, (int)e, r))) return rc;
+        s0 = e;
+    }
+    return OFLK_OK;
+}
+
+// Tracks of a whole sequence, host pointers: the one driver of the six sequence track calls.  Chunks of C pairs run one after
+// the other on the null stream.  The chunk's frames go up (the dense engine's flows follow them at once); row 0 of a later
+// chunk is the previous chunk's last row; a source that detects once does so now, on the first chunk's frame 0; the engine
+// readies the chunk (the sparse engine's pyramids); its pairs are walked in segments (walk_segments): before the segment
+// that begins at a detection frame s, the source puts new queries (qt, qxy) into R from row r of the chunk, and the segment's
+// launch (t0 = s) starts them on its row 0 and continues the others; the rows come down and the stream is synchronized, as
+// the next chunk reuses the buffers.
+//   Engine: how tracks are made.  check(seq) its refusals, pairs(B, H, W) a chunk's size, alloc(call, seq, C),
+//           upload(call, seq, b0, nb) the chunk's frames up, ready(seq) what else a chunk needs before its segments,
+//           frame(seq, r) the chunk's device frame r, step(seq, R, N, s0, e, r) one segment's launch.  DenseTracks, SparseTracks.
+//   Source: where queries come from.  check(seq, tracks, visible), detect_every(T), setup(call, seq, R, C) its buffers,
+//           first(call, seq, R, frame, b0) on an uploaded chunk's frame 0, begin(R, b0, nb) ahead of a chunk's segments,
+//           detect(call, seq, R, frame, s, r) and down(call, seq, R, b0, nb, r0): what comes down beside rows r0 .. nb.
+//           GivenQueries, DetectOnce and Replenished.
+template <class Engine, class Source>
+int run_sequence_tracks(const Seq &seq, Engine eng, Source src, int N, float *tracks, unsigned char *visible)
+{
+    int rc = eng.check(seq);
+    if (rc || (rc = src.check(seq, tracks, visible))) return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const int B = seq.T - 1, C = eng.pairs(B, seq.H, seq.W), every = src.detect_every(seq.T);
+    const size_t row = (size_t)N;
     TrackRows R;
-    auto detection_frame = [&](int s) { return every && s % every == 0; };
-    auto all_checks = [&]() -> int { const int rc = check_alpha_beta(alpha, beta); return rc ? rc : checks(); };
-    auto all_setup = [&](HostCall &call, int pairs) -> int {
-        int rc;
-        C = pairs;
-        if ((rc = call.alloc(&R.tr, (size_t)(C + 1) * 2 * row)) || (rc = call.alloc(&R.vis, (size_t)(C + 1) * row))) return rc;
-        return setup(call, R, C);
-    };
-    auto chunk = [&](HostCall &call, int b0, int nb, const PIXELS *d_frames, float *const *d) -> int {
-        int rc;
+    if ((rc = eng.alloc(call, seq, C)) || (rc = call.alloc(&R.tr, (size_t)(C + 1) * 2 * row)) ||
+        (rc = call.alloc(&R.vis, (size_t)(C + 1) * row)) || (rc = src.setup(call, seq, R, C)))
+        return rc;
+    for (int b0 = 0; b0 < B; b0 += C) {
+        const int nb = std::min(C, B - b0);
+        if ((rc = eng.upload(call, seq, b0, nb))) return rc;
         if (b0 > 0) {   // row 0 of this chunk is the previous (full, C-pair) chunk's last row
             HIP_TRY(hipMemcpyAsync(R.tr, R.tr + (size_t)C * 2 * row, 2 * row * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
             HIP_TRY(hipMemcpyAsync(R.vis, R.vis + (size_t)C * row, row, hipMemcpyDeviceToDevice, nullptr));
         }
-        if ((rc = begin(nb))) return rc;
-        for (int s0 = b0; s0 < b0 + nb;) {   // segments [s0, e) of pairs; s0 <= T-2
-            const int e = every ? (int)std::min<long long>(b0 + nb, ((long long)s0 / every + 1) * every) : b0 + nb, r = s0 - b0;
-            const size_t fo = (size_t)r * plane;
-            if (detection_frame(s0) && (rc = detect(call, R, s0, r, d_frames + fo))) return rc;
-            if ((rc = track_launch(d[0] + fo, d[1] + fo, d[2] + fo, d[3] + fo, e - s0, H, W, alpha, beta, s0, R.qt, R.qxy, N,
-                                   R.tr + (size_t)r * 2 * row, R.vis + (size_t)r * row, nullptr)))
-                return rc;
-            s0 = e;
-        }
+        if ((rc = src.first(call, seq, R, eng.frame(seq, 0), b0)) || (rc = eng.ready(seq)) || (rc = src.begin(R, b0, nb))) return rc;
+        rc = walk_segments(b0, nb, every, [&](int s, int r) { return src.detect(call, seq, R, eng.frame(seq, r), s, r); },
+                           [&](int s0, int e, int r) { return eng.step(seq, R, N, s0, e, r); });
+        if (rc) return rc;
         // row 0 of a later chunk is already on the host, unless the chunk begins at a detection frame: that segment's
         // launch is what makes the row final, so it goes again
-        const int r0 = b0 > 0 && !detection_frame(b0) ? 1 : 0;
+        const int r0 = b0 > 0 && !(every && b0 % every == 0) ? 1 : 0;
         const size_t nr = (size_t)(nb + 1 - r0);
         if ((rc = call.to_host(tracks + (size_t)(b0 + r0) * 2 * row, R.tr + (size_t)r0 * 2 * row, nr * 2 * row)) ||
-            (rc = call.to_host(visible + (size_t)(b0 + r0) * row, R.vis + (size_t)r0 * row, nr * row)))
+            (rc = call.to_host(visible + (size_t)(b0 + r0) * row, R.vis + (size_t)r0 * row, nr * row)) ||
+            (rc = src.down(call, seq, R, b0, nb, r0)) || (rc = call.sync()))
             return rc;
-        return extras(call, b0, nb, r0);
-    };
-    return run_sequence_bidir<PIXELS>(frames, T, H, W, levels, window_size, iters, all_checks, all_setup, chunk);
+    }
+    return OFLK_OK;
 }
 
-constexpr auto no_part = [](auto &&...) -> int { return OFLK_OK; };   // a part that a call does not have
+// The dense engine: a chunk is BidirChunk's (run_sequence_fb's), a segment one k_track launch on its flows
+struct DenseTracks {
+    float alpha, beta;
+    BidirChunk k{};
 
-// oflk_pyramidal_sequence_tracks: no detection frame; only the queries go up
-template <class PIXELS>
-int sequence_tracks(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
-                    const int *qt, const float *qxy, int N, float *tracks, unsigned char *visible)
-{
-    auto checks = [&]() -> int { return check_queries(qt, T, qxy, N, tracks, visible); };
-    auto setup = [&](HostCall &call, TrackRows &R, int) -> int {
+    int check(const Seq &seq) const
+    {
+        const int rc = BidirChunk::check(seq);
+        return rc ? rc : check_alpha_beta(alpha, beta);
+    }
+    static int pairs(int B, int H, int W) { return chunk_pairs(B, H, W); }
+    int alloc(HostCall &call, const Seq &seq, int C) { return k.alloc(call, seq, C); }
+    int upload(HostCall &call, const Seq &seq, int b0, int nb) { return k.run(call, seq, b0, nb); }   // and both flows
+    static int ready(const Seq &) { return OFLK_OK; }
+    const void *frame(const Seq &seq, int r) const { return k.frames + (size_t)r * seq.frame_bytes(); }
+    int step(const Seq &seq, const TrackRows &R, int N, int s0, int e, int r) const
+    {
+        const size_t fo = (size_t)r * seq.H * seq.W, row = (size_t)N;
+        return track_launch(k.d[0] + fo, k.d[1] + fo, k.d[2] + fo, k.d[3] + fo, e - s0, seq.H, seq.W, alpha, beta, s0, R.qt, R.qxy, N,
+                            R.tr + (size_t)r * 2 * row, R.vis + (size_t)r * row, nullptr);
+    }
+};
+
+constexpr auto no_part = [](auto &&...) -> int { return OFLK_OK; };   // a part that a source does not have
+
+// The caller's queries: they go up, and no frame is a detection frame
+struct GivenQueries {
+    const int *qt;      // [N] or NULL
+    const float *qxy;   // [N][2]
+    int N;
+
+    int check(const Seq &seq, const void *tracks, const void *visible) const
+    {
+        return check_queries(qt, seq.T, qxy, N, tracks, visible);
+    }
+    static int detect_every(int) { return 0; }
+    int setup(HostCall &call, const Seq &, TrackRows &R, int) const
+    {
         const int rc = call.upload(&R.qxy, qxy, 2 * (size_t)N);
         return rc || !qt ? rc : call.upload(&R.qt, qt, (size_t)N);
-    };
-    return run_sequence_tracks<PIXELS>(frames, T, H, W, levels, window_size, iters, alpha, beta, N, tracks, visible, 0, checks,
-                                       setup, no_part, no_part, no_part);
-}
+    }
+    static constexpr auto first = no_part, begin = no_part, detect = no_part, down = no_part;
+};
 
-// oflk_pyramidal_sequence_klt: frame 0, the only multiple of T, is the detection frame.  Its xy go straight into the query
-// buffer (N = K; the NaN rows are never-visible tracks), and count, xy and score come down with chunk 0.
-template <class PIXELS>
-int sequence_klt(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
-                 float q, float md, int K, int *count, float *xy, float *score, float *tracks, unsigned char *visible)
-{
-    const size_t row = (size_t)K;
+// One detection, on frame 0 as soon as the first chunk's frames are up; no frame of the walk is a detection frame.  Its xy
+// go straight into the query buffer (N = K; the NaN rows are never-visible tracks), and count, xy and score come down with
+// chunk 0.
+struct DetectOnce {
+    float q, md;
+    int K;
+    int *count;          // the caller's [1], [K][2] and [K]
+    float *xy, *score;
     char *d_ws = nullptr;
     int *d_cnt = nullptr;
     float *d_sc = nullptr;
-    auto checks = [&]() -> int {
+
+    int check(const Seq &seq, const void *tracks, const void *visible) const
+    {
         if (!count || !xy || !score || !tracks || !visible) return fail(OFLK_ERR_INVALID, "NULL output argument");
         const int rc = check_select(q, md, K);
-        return rc ? rc : check_corner_window(window_size);
-    };
-    auto setup = [&](HostCall &call, TrackRows &R, int) -> int {
+        // never a second text for a window on the sparse engine, whose own check of the same odd sizes 3 .. 11 comes first
+        return rc ? rc : check_corner_window(seq.window_size);
+    }
+    static int detect_every(int) { return 0; }
+    int setup(HostCall &call, const Seq &seq, TrackRows &R, int)
+    {
         int rc;
-        if ((rc = call.alloc(&R.qxy, 2 * row)) || (rc = call.alloc(&d_ws, feat_ws(nullptr, 1, H, W, md, 0).bytes)) ||
-            (rc = call.alloc(&d_cnt, 1)) || (rc = call.alloc(&d_sc, row)))
+        if ((rc = call.alloc(&R.qxy, 2 * (size_t)K)) || (rc = call.alloc(&d_ws, feat_ws(nullptr, 1, seq.H, seq.W, md, 0).bytes)) ||
+            (rc = call.alloc(&d_cnt, 1)) || (rc = call.alloc(&d_sc, (size_t)K)))
             return rc;
         return OFLK_OK;
-    };
-    auto detect = [&](HostCall &call, TrackRows &R, int, int, const PIXELS *d_frame) -> int {
-        int rc = detect_launch(d_frame, sizeof(PIXELS) == 1, 1, H, W, window_size, q, md, K, feat_ws(d_ws, 1, H, W, md, 0), d_cnt,
-                               R.qxy, d_sc, nullptr, nullptr);
-        if (rc || (rc = call.to_host(count, d_cnt, 1)) || (rc = call.to_host(xy, R.qxy, 2 * row)) ||
-            (rc = call.to_host(score, d_sc, row)))
+    }
+    int first(HostCall &call, const Seq &seq, const TrackRows &R, const void *d_frame, int b0) const
+    {
+        if (b0 > 0) return OFLK_OK;
+        int rc = detect_launch(d_frame, seq.u8, 1, seq.H, seq.W, seq.window_size, q, md, K, feat_ws(d_ws, 1, seq.H, seq.W, md, 0),
+                               d_cnt, R.qxy, d_sc, nullptr, nullptr);
+        if (rc || (rc = call.to_host(count, d_cnt, 1)) || (rc = call.to_host(xy, R.qxy, 2 * (size_t)K)) ||
+            (rc = call.to_host(score, d_sc, (size_t)K)))
             return rc;
         return OFLK_OK;
-    };
-    return run_sequence_tracks<PIXELS>(frames, T, H, W, levels, window_size, iters, alpha, beta, K, tracks, visible, T, checks,
-                                       setup, no_part, detect, no_part);
+    }
+    static constexpr auto begin = no_part, detect = no_part, down = no_part;
+};
+
+// The slot side of replenished KLT: the K queries are slots, every one dead at first.  On every `every`-th frame s the
+// detection fills free slots (qt = s, qxy) from the slots' row of s, born with them.  The selection's parameters, its
+// workspace (feat_ws(.., 1, .., K)) and the per-row outputs of a pass of B+1 rows
+struct Slots {
+    float q, md;
+    int K, every;
+    void *ws = nullptr;
+    unsigned char *born = nullptr;   // [B+1][K]
+    int *detected = nullptr;         // [B+1]
+};
+
+// ahead of a pass of B+1 rows that begins on frame t0: the slots' first state (t0 = 0) and the pass's born and detected rows
+// cleared, by kernels on stream s (a pass is captured into graphs: no memset)
+int slots_begin(const Slots &k, const TrackRows &R, int t0, int B, hipStream_t s)
+{
+    if (t0 == 0) {
+        hipLaunchKernelGGL(k_slots_init, dim3((unsigned)((k.K + 255) / 256)), dim3(256), 0, s, R.qt, reinterpret_cast<float2 *>(R.qxy),
+                           reinterpret_cast<float2 *>(R.tr), R.vis, k.K);
+        HIP_TRY(hipGetLastError());
+    }
+    const size_t nborn = (size_t)(B + 1) * k.K;
+    hipLaunchKernelGGL(k_sparse_rows_clear, dim3((unsigned)std::min<size_t>((nborn + 255) / 256, 1024)), dim3(256), 0, s, k.born, nborn,
+                       k.detected, (size_t)B + 1);
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
 }
 
-// oflk_pyramidal_sequence_klt_replenish: the K queries are slots, every one dead at first (k_slots_init).  On every
-// detect_every-th frame s the detection fills free slots (qt = s, qxy) from the slots' row of s, born with them.
-template <class PIXELS>
-int sequence_klt_replenish(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
-                           float beta, float q, float md, int K, int detect_every, float *tracks, unsigned char *visible,
-                           unsigned char *born, int *detected)
+// the detection on `frame`, which is frame s0 and row r of the pass
+int slots_detect(const Slots &k, const TrackRows &R, const void *frame, bool u8, int H, int W, int window_size, int s0, int r,
+                 hipStream_t s)
 {
-    if (!born) return fail(OFLK_ERR_INVALID, "NULL output argument");
-    const size_t row = (size_t)K;
-    char *d_ws = nullptr;
-    unsigned char *d_born = nullptr;
-    int *d_det = nullptr;
-    auto checks = [&]() -> int {
-        if (!detected || !tracks || !visible) return fail(OFLK_ERR_INVALID, "NULL output argument");
-        if (detect_every < 1) return fail(OFLK_ERR_INVALID, "detect_every must be >= 1 (got %d)", detect_every);
-        const int rc = check_select(q, md, K);
-        return rc ? rc : check_corner_window(window_size);
-    };
-    auto setup = [&](HostCall &call, TrackRows &R, int C) -> int {
-        int rc;
-        if ((rc = call.alloc(&R.qxy, 2 * row)) || (rc = call.alloc(&d_ws, feat_ws(nullptr, 1, H, W, md, K).bytes)) ||
-            (rc = call.alloc(&R.qt, row)) || (rc = call.alloc(&d_born, (size_t)(C + 1) * row)) ||
-            (rc = call.alloc(&d_det, (size_t)T)))
-            return rc;
-        hipLaunchKernelGGL(k_slots_init, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, nullptr, R.qt,
-                           reinterpret_cast<float2 *>(R.qxy), reinterpret_cast<float2 *>(R.tr), R.vis, K);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemsetAsync(d_det, 0, (size_t)T * sizeof(int), nullptr));
-        return OFLK_OK;
-    };
-    auto begin = [&](int nb) -> int { HIP_TRY(hipMemsetAsync(d_born, 0, (size_t)(nb + 1) * row, nullptr)); return OFLK_OK; };
-    auto detect = [&](HostCall &, TrackRows &R, int s, int r, const PIXELS *d_frame) -> int {
-        const SlotSide slots{R.tr + (size_t)r * 2 * row, R.vis + (size_t)r * row, R.qt, d_born + (size_t)r * row, d_det + s, s};
-        return detect_launch(d_frame, sizeof(PIXELS) == 1, 1, H, W, window_size, q, md, K, feat_ws(d_ws, 1, H, W, md, K), nullptr,
-                             R.qxy, nullptr, &slots, nullptr);
-    };
-    auto extras = [&](HostCall &call, int b0, int nb, int r0) -> int {
-        int rc = call.to_host(born + (size_t)(b0 + r0) * row, d_born + (size_t)r0 * row, (size_t)(nb + 1 - r0) * row);
-        if (!rc && b0 + nb == T - 1) rc = call.to_host(detected, d_det, (size_t)T);
-        return rc;
-    };
-    return run_sequence_tracks<PIXELS>(frames, T, H, W, levels, window_size, iters, alpha, beta, K, tracks, visible, detect_every,
-                                       checks, setup, begin, detect, extras);
+    const size_t row = (size_t)k.K;
+    const SlotSide slots{R.tr + (size_t)r * 2 * row, R.vis + (size_t)r * row, R.qt, k.born + (size_t)r * row, k.detected + r, s0};
+    return detect_launch(frame, u8, 1, H, W, window_size, k.q, k.md, k.K, feat_ws(k.ws, 1, H, W, k.md, k.K), nullptr, R.qxy, nullptr,
+                         &slots, s);
 }
+
+// Replenished slots: a chunk is one pass of Slots; born and (the sparse engine's) residual rows come down beside the tracks.
+// Residual row 0 of a later chunk is the previous chunk's last row, which is already on the host.  The chunks' detected
+// rows are pieces of one [T] array that comes down once, with the last chunk: a download per chunk costs the dense engine's
+// many small chunks a millisecond in all.
+struct Replenished : Slots {
+    unsigned char *h_born;   // the caller's [T][K], [T] and [T][K] or NULL
+    int *h_detected;
+    float *h_residual;
+    int *d_det = nullptr;    // [T]
+
+    int check(const Seq &seq, const void *tracks, const void *visible) const
+    {
+        if (!tracks || !visible || !h_born || !h_detected) return fail(OFLK_ERR_INVALID, "NULL output argument");
+        if (every < 1) return fail(OFLK_ERR_INVALID, "detect_every must be >= 1 (got %d)", every);
+        const int rc = check_select(q, md, K);
+        return rc ? rc : check_corner_window(seq.window_size);
+    }
+    int detect_every(int) const { return every; }
+    static constexpr auto first = no_part;
+    int setup(HostCall &call, const Seq &seq, TrackRows &R, int C)
+    {
+        const size_t row = (size_t)K, rows = (size_t)(C + 1) * row;
+        char *d_ws = nullptr;
+        int rc;
+        if ((rc = call.alloc(&R.qxy, 2 * row)) || (rc = call.alloc(&R.qt, row)) ||
+            (rc = call.alloc(&d_ws, feat_ws(nullptr, 1, seq.H, seq.W, md, K).bytes)) || (rc = call.alloc(&born, rows)) ||
+            (rc = call.alloc(&d_det, (size_t)seq.T)) || (rc = call.alloc(&R.res, rows, h_residual != nullptr)))
+            return rc;
+        ws = d_ws;
+        return OFLK_OK;
+    }
+    int begin(const TrackRows &R, int b0, int nb)
+    {
+        detected = d_det + b0;   // row b0 was the previous chunk's last row, which is no detection row: cleared again
+        return slots_begin(*this, R, b0, nb, nullptr);
+    }
+    int detect(HostCall &, const Seq &seq, const TrackRows &R, const void *d_frame, int s, int r) const
+    {
+        return slots_detect(*this, R, d_frame, seq.u8, seq.H, seq.W, seq.window_size, s, r, nullptr);
+    }
+    int down(HostCall &call, const Seq &seq, const TrackRows &R, int b0, int nb, int r0) const
+    {
+        const size_t row = (size_t)K;
+        int rc = call.to_host(h_born + (size_t)(b0 + r0) * row, born + (size_t)r0 * row, (size_t)(nb + 1 - r0) * row);
+        if (!rc && b0 + nb == seq.T - 1) rc = call.to_host(h_detected, d_det, (size_t)seq.T);
+        if (rc || !R.res) return rc;
+        const int q0 = b0 > 0 ? 1 : 0;
+        return call.to_host(h_residual + (size_t)(b0 + q0) * row, R.res + (size_t)q0 * row, (size_t)(nb + 1 - q0) * row);
+    }
+};
 }  // namespace
 
 
@@ -3044,22 +3154,24 @@ OFLK_API int oflk_pyramidal_sequence_tracks(const float *frames, int T, int H, i
                                             float alpha, float beta, const int *qt, const float *qxy, int N, float *tracks,
                                             unsigned char *visible)
 {
-    return sequence_tracks<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, qt, qxy, N, tracks, visible);
+    return run_sequence_tracks(Seq{frames, false, T, H, W, levels, window_size, iters}, DenseTracks{alpha, beta},
+                               GivenQueries{qt, qxy, N}, N, tracks, visible);
 }
 
 OFLK_API int oflk_pyramidal_sequence_tracks_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size,
                                                int iters, float alpha, float beta, const int *qt, const float *qxy, int N,
                                                float *tracks, unsigned char *visible)
 {
-    return sequence_tracks<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, qt, qxy, N, tracks, visible);
+    return run_sequence_tracks(Seq{frames, true, T, H, W, levels, window_size, iters}, DenseTracks{alpha, beta},
+                               GivenQueries{qt, qxy, N}, N, tracks, visible);
 }
 
 OFLK_API int oflk_pyramidal_sequence_klt(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
                                          float alpha, float beta, float quality_level, float min_distance, int max_corners,
                                          int *count, float *xy, float *score, float *tracks, unsigned char *visible)
 {
-    return sequence_klt<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, quality_level, min_distance, max_corners,
-                               count, xy, score, tracks, visible);
+    return run_sequence_tracks(Seq{frames, false, T, H, W, levels, window_size, iters}, DenseTracks{alpha, beta},
+                               DetectOnce{quality_level, min_distance, max_corners, count, xy, score}, max_corners, tracks, visible);
 }
 
 OFLK_API int oflk_pyramidal_sequence_klt_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size,
@@ -3067,8 +3179,8 @@ OFLK_API int oflk_pyramidal_sequence_klt_u8(const unsigned char *frames, int T, 
                                             int max_corners, int *count, float *xy, float *score, float *tracks,
                                             unsigned char *visible)
 {
-    return sequence_klt<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, quality_level, min_distance,
-                                       max_corners, count, xy, score, tracks, visible);
+    return run_sequence_tracks(Seq{frames, true, T, H, W, levels, window_size, iters}, DenseTracks{alpha, beta},
+                               DetectOnce{quality_level, min_distance, max_corners, count, xy, score}, max_corners, tracks, visible);
 }
 
 OFLK_API int oflk_pyramidal_sequence_klt_replenish(const float *frames, int T, int H, int W, int levels, int window_size,
@@ -3076,8 +3188,9 @@ OFLK_API int oflk_pyramidal_sequence_klt_replenish(const float *frames, int T, i
                                                    int max_corners, int detect_every, float *tracks, unsigned char *visible,
                                                    unsigned char *born, int *detected)
 {
-    return sequence_klt_replenish<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, quality_level, min_distance,
-                                         max_corners, detect_every, tracks, visible, born, detected);
+    return run_sequence_tracks(Seq{frames, false, T, H, W, levels, window_size, iters}, DenseTracks{alpha, beta},
+                               Replenished{{quality_level, min_distance, max_corners, detect_every}, born, detected, nullptr},
+                               max_corners, tracks, visible);
 }
 
 OFLK_API int oflk_pyramidal_sequence_klt_replenish_u8(const unsigned char *frames, int T, int H, int W, int levels,
@@ -3085,8 +3198,9 @@ OFLK_API int oflk_pyramidal_sequence_klt_replenish_u8(const unsigned char *frame
                                                       float min_distance, int max_corners, int detect_every, float *tracks,
                                                       unsigned char *visible, unsigned char *born, int *detected)
 {
-    return sequence_klt_replenish<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, quality_level,
-                                                 min_distance, max_corners, detect_every, tracks, visible, born, detected);
+    return run_sequence_tracks(Seq{frames, true, T, H, W, levels, window_size, iters}, DenseTracks{alpha, beta},
+                               Replenished{{quality_level, min_distance, max_corners, detect_every}, born, detected, nullptr},
+                               max_corners, tracks, visible);
 }
 
 // =============================================================================
@@ -3120,6 +3234,20 @@ int check_sparse_test(float alpha, float beta, float max_residual)
     return OFLK_OK;
 }
 
+// a pyramid's L levels as the sparse kernels take them: pointers, sizes and upsample_args' ratios
+void sparse_levels(SparseArgs *a, int L, float *const *pyr, const int *dims)
+{
+    for (int l = 0; l < L; l++) {
+        a->pyr[l] = pyr[l];
+        a->dims[2 * l] = dims[2 * l];
+        a->dims[2 * l + 1] = dims[2 * l + 1];
+        if (l > 0) {
+            a->sx[l] = (float)((double)dims[2 * l + 1] / (double)dims[2 * l - 1]);
+            a->sy[l] = (float)((double)dims[2 * l] / (double)dims[2 * l - 2]);
+        }
+    }
+}
+
 // The plan's B+1 pyramids of d_frames [B+1][H][W] (build_pyramids, exact arithmetic always) and the kernel arguments
 // that describe them.  Device workspace of a sparse pass: the plan's pyramid levels below the frame, nothing of frame
 // size -- except where a level is too small for the fused pyramid kernel: then the blur temporaries for B+1 images and,
@@ -3147,15 +3275,7 @@ int sparse_pyramids(oflk_plan *p, const void *d_frames, bool u8, hipStream_t s, 
     *a = SparseArgs{};
     a->frames = d_frames;
     a->L = p->L; a->K = p->K; a->B = p->B; a->H = p->H; a->W = p->W;
-    for (int l = 0; l < p->L; l++) {
-        a->pyr[l] = p->pyr[l];
-        a->dims[2 * l] = p->dims[2 * l];
-        a->dims[2 * l + 1] = p->dims[2 * l + 1];
-        if (l > 0) {   // upsample_args' ratios
-            a->sx[l] = (float)((double)p->dims[2 * l + 1] / (double)p->dims[2 * l - 1]);
-            a->sy[l] = (float)((double)p->dims[2 * l] / (double)p->dims[2 * l - 2]);
-        }
-    }
+    sparse_levels(a, p->L, p->pyr, p->dims);
     return u8 ? 1 : 0;   // > 0: the kernels read the finest level as uint8
 }
 
@@ -3194,65 +3314,37 @@ int plan_sparse_tracks(oflk_plan *p, const void *d_frames, bool u8, float alpha,
     return sparse_launch<true>(p, a, rc > 0, s);
 }
 
-// The slot side of a replenished sparse pass: the selection's parameters, its workspace (feat_ws(.., 1, .., K)), the slots'
-// queries and the per-row outputs of the pass's B+1 rows
-struct SparseKlt {
-    float q, md;
-    int K, every;
-    void *ws;
-    int *qt;                   // [K]
-    float *qxy;                // [K][2]
-    unsigned char *born;       // [B+1][K]
-    int *detected;             // [B+1]
-    float *residual;           // [B+1][K] or NULL
-};
+// A sparse pass on a plan, one chain of launches on stream s with nothing synchronized: the plan's B+1 pyramids once
+// (begin), then one track launch per segment (step).  The host driver's sparse engine and oflk_plan_sparse_klt_replenish.
+struct SparsePass {
+    float alpha, beta, max_residual;
+    oflk_plan *p = nullptr;
+    hipStream_t s = nullptr;
+    SparseArgs base{};      // the whole pass's
+    bool fine_u8 = false;   // the kernels read the finest level as uint8
 
-// oflk_plan_sparse_klt_replenish on checked arguments: the plan's B+1 pyramids once, then the pairs t0 .. t0+B-1 in
-// segments [s0, e) cut at the multiples of `every`, one track launch each on the buffers offset to frame s0 - t0 (the
-// kernel's frame 0, row 0 and t0 = s0).  Ahead of a segment that begins on such a multiple, the detection on that frame
-// fills free slots from the slots' row of it; the launch starts them (qt = s0) and continues the others.  The last row is
-// never a detection row.  One chain of launches on stream s; nothing is synchronized.
-int sparse_klt_pass(oflk_plan *p, const void *d_frames, bool u8, float alpha, float beta, float max_residual, int t0,
-                    const SparseKlt &k, float *d_tracks, unsigned char *d_visible, hipStream_t s)
-{
-    SparseArgs base;
-    int rc = sparse_pyramids(p, d_frames, u8, s, &base);
-    if (rc < 0) return rc;
-    const bool fine_u8 = rc > 0;
-    const int B = p->B, H = p->H, W = p->W;
-    const size_t row = (size_t)k.K, plane = (size_t)H * W;
-    if (t0 == 0) {
-        hipLaunchKernelGGL(k_slots_init, dim3((unsigned)((k.K + 255) / 256)), dim3(256), 0, s, k.qt,
-                           reinterpret_cast<float2 *>(k.qxy), reinterpret_cast<float2 *>(d_tracks), d_visible, k.K);
-        HIP_TRY(hipGetLastError());
+    int begin(oflk_plan *plan, const void *d_frames, bool u8, hipStream_t stream)
+    {
+        p = plan;
+        s = stream;
+        const int rc = sparse_pyramids(p, d_frames, u8, s, &base);
+        fine_u8 = rc > 0;
+        return std::min(rc, 0);
     }
-    const size_t nborn = (size_t)(B + 1) * row;
-    hipLaunchKernelGGL(k_sparse_rows_clear, dim3((unsigned)std::min<size_t>((nborn + 255) / 256, 1024)), dim3(256), 0, s, k.born, nborn,
-                       k.detected, (size_t)B + 1);
-    HIP_TRY(hipGetLastError());
-    const FeatWs ws = feat_ws(k.ws, 1, H, W, k.md, k.K);
-    const long long end = (long long)t0 + B;
-    for (long long s0 = t0; s0 < end;) {
-        const long long e = std::min(end, (s0 / k.every + 1) * k.every);
-        const size_t r = (size_t)(s0 - t0);
-        float *tr = d_tracks + r * 2 * row;
-        unsigned char *vis = d_visible + r * row;
-        if (s0 % k.every == 0) {
-            const SlotSide slots{tr, vis, k.qt, k.born + r * row, k.detected + r, (int)s0};
-            const void *frame = static_cast<const char *>(d_frames) + r * plane * (u8 ? 1 : sizeof(float));
-            if ((rc = detect_launch(frame, u8, 1, H, W, p->win, k.q, k.md, k.K, ws, nullptr, k.qxy, nullptr, &slots, s))) return rc;
-        }
+    // the segment of pairs s0 .. e-1 that begins on row r of the pass: one launch on the buffers offset to frame r (the
+    // kernel's frame 0, row 0 and t0 = s0); with R.res, the kernel that also writes those rows
+    int step(const TrackRows &R, int N, int s0, int e, int r) const
+    {
+        const size_t row = (size_t)N, fo = (size_t)r * p->H * p->W;
         SparseArgs a = base;
-        a.frames = static_cast<const char *>(base.frames) + r * plane * (fine_u8 ? 1 : sizeof(float));
-        for (int l = 0; l < p->L - 1; l++) a.pyr[l] = base.pyr[l] + r * (size_t)p->dims[2 * l] * (size_t)p->dims[2 * l + 1];
-        a.B = (int)(e - s0); a.N = k.K; a.t0 = (int)s0;
-        a.qt = k.qt; a.qxy = k.qxy; a.tracks = tr; a.visible = vis;
+        a.frames = static_cast<const char *>(base.frames) + fo * (fine_u8 ? 1 : sizeof(float));
+        for (int l = 0; l < p->L - 1; l++) a.pyr[l] = base.pyr[l] + (size_t)r * p->dims[2 * l] * (size_t)p->dims[2 * l + 1];
+        a.B = e - s0; a.N = N; a.t0 = s0;
+        a.qt = R.qt; a.qxy = R.qxy; a.tracks = R.tr + (size_t)r * 2 * row; a.visible = R.vis + (size_t)r * row;
         a.alpha = alpha; a.beta = beta; a.max_residual = max_residual;
-        if ((rc = sparse_launch<true>(p, a, fine_u8, s, k.residual ? k.residual + r * row : nullptr))) return rc;
-        s0 = e;
+        return sparse_launch<true>(p, a, fine_u8, s, R.res ? R.res + (size_t)r * row : nullptr);
     }
-    return OFLK_OK;
-}
+};
 
 template <class PIXELS>
 int sparse_lk_host(const PIXELS *prev, const PIXELS *curr, int H, int W, int levels, int window_size, int iters, const float *pts,
@@ -3296,150 +3388,30 @@ int sparse_chunk_pairs(int B, int H, int W)
     return std::min(B, C);
 }
 
-// Sparse tracks of a whole sequence, host pointers.  Chunks as run_sequence_bidir's: C+1 frames go up (the boundary frame
-// is shared), pass(call, p, d_frames, b0, nb, R) enqueues the chunk's sparse pass on its plan (rows of frames b0 .. b0+nb
-// into R, continued from the previous chunk's last row, which is R's row 0), only the rows come down.  `every` > 0: the
-// multiples of it are detection frames, as in run_sequence_tracks: a chunk that begins on one sends its row 0 down again.
-// A call's other parts: checks(), setup(call, R, C) and extras(call, b0, nb, r0) after rows r0 .. nb have gone down.
-template <class PIXELS, class Checks, class Setup, class Pass, class Extras>
-int run_sequence_sparse(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
-                        float max_residual, int N, float *tracks, unsigned char *visible, int every, Checks checks, Setup setup,
-                        Pass pass, Extras extras)
-{
-    int rc = check_hw(frames, frames, H, W);
-    if (rc) return rc;
-    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
-    if ((rc = checks()) || (rc = check_sparse_test(alpha, beta, max_residual)) ||
-        (rc = check_sparse_config(H, W, levels, window_size, iters)))
-        return rc;
-    HostCall call;
-    if ((rc = call.begin())) return rc;
-    const int B = T - 1, C = sparse_chunk_pairs(B, H, W);
-    const size_t plane = (size_t)H * W, row = (size_t)N;
-    PIXELS *d_frames = nullptr;
-    TrackRows R;
-    if ((rc = call.alloc(&d_frames, (size_t)(C + 1) * plane)) || (rc = call.alloc(&R.tr, (size_t)(C + 1) * 2 * row)) ||
-        (rc = call.alloc(&R.vis, (size_t)(C + 1) * row)) || (rc = setup(call, R, C)))
-        return rc;
-    for (int b0 = 0; b0 < B; b0 += C) {
-        const int nb = std::min(C, B - b0);
-        oflk_plan *p = nullptr;
-        if ((rc = host_plan(*call.c, call.dev, nb, H, W, levels, window_size, iters, &p))) return rc;
-        if ((rc = call.to_device(d_frames, frames + (size_t)b0 * plane, (size_t)(nb + 1) * plane))) return rc;
-        if (b0 > 0) {   // row 0 of this chunk is the previous (full, C-pair) chunk's last row
-            HIP_TRY(hipMemcpyAsync(R.tr, R.tr + (size_t)C * 2 * row, 2 * row * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
-            HIP_TRY(hipMemcpyAsync(R.vis, R.vis + (size_t)C * row, row, hipMemcpyDeviceToDevice, nullptr));
-        }
-        if ((rc = pass(call, p, d_frames, b0, nb, R))) return rc;
-        // row 0 of a later chunk is already on the host, unless the chunk begins at a detection frame
-        const int r0 = b0 > 0 && !(every && b0 % every == 0) ? 1 : 0;
-        const size_t nr = (size_t)(nb + 1 - r0);
-        if ((rc = call.to_host(tracks + (size_t)(b0 + r0) * 2 * row, R.tr + (size_t)r0 * 2 * row, nr * 2 * row)) ||
-            (rc = call.to_host(visible + (size_t)(b0 + r0) * row, R.vis + (size_t)r0 * row, nr * row)) ||
-            (rc = extras(call, b0, nb, r0)) || (rc = call.sync()))
-            return rc;
+// The sparse engine of run_sequence_tracks: a chunk is its C+1 frames and their pyramids and no flow, a segment one
+// SparsePass step
+struct SparseTracks {
+    SparsePass pass;
+    char *frames = nullptr;   // [C+1][H][W] of the call's pixels
+
+    int check(const Seq &seq) const
+    {
+        int rc = check_seq(seq);
+        if (rc || (rc = check_sparse_test(pass.alpha, pass.beta, pass.max_residual))) return rc;
+        return check_sparse_config(seq.H, seq.W, seq.levels, seq.window_size, seq.iters);
     }
-    return OFLK_OK;
-}
-
-// oflk_pyramidal_sequence_sparse_tracks: the caller's queries go up; one track launch per chunk, t0 = its first frame
-template <class PIXELS>
-int sequence_sparse_tracks(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
-                           float beta, float max_residual, const int *qt, const float *qxy, int N, float *tracks,
-                           unsigned char *visible)
-{
-    auto checks = [&]() -> int { return check_queries(qt, T, qxy, N, tracks, visible); };
-    auto setup = [&](HostCall &call, TrackRows &R, int) -> int {
-        const int rc = call.upload(&R.qxy, qxy, 2 * (size_t)N);
-        return rc || !qt ? rc : call.upload(&R.qt, qt, (size_t)N);
-    };
-    auto pass = [&](HostCall &, oflk_plan *p, const PIXELS *d_frames, int b0, int, TrackRows &R) -> int {
-        return plan_sparse_tracks(p, d_frames, sizeof(PIXELS) == 1, alpha, beta, max_residual, b0, R.qt, R.qxy, N, R.tr, R.vis, nullptr);
-    };
-    return run_sequence_sparse<PIXELS>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, N, tracks, visible, 0,
-                                       checks, setup, pass, no_part);
-}
-
-// oflk_pyramidal_sequence_klt_sparse: sequence_klt's detection on frame 0 (ahead of chunk 0's pass, straight into the query
-// buffer: N = K, the NaN rows are never-visible tracks), then sequence_sparse_tracks; count, xy and score come down with
-// chunk 0
-template <class PIXELS>
-int sequence_klt_sparse(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
-                        float max_residual, float q, float md, int K, int *count, float *xy, float *score, float *tracks,
-                        unsigned char *visible)
-{
-    const size_t row = (size_t)K;
-    char *d_ws = nullptr;
-    int *d_cnt = nullptr;
-    float *d_sc = nullptr;
-    auto checks = [&]() -> int {
-        if (!count || !xy || !score || !tracks || !visible) return fail(OFLK_ERR_INVALID, "NULL output argument");
-        return check_select(q, md, K);
-    };
-    auto setup = [&](HostCall &call, TrackRows &R, int) -> int {
-        int rc;
-        if ((rc = call.alloc(&R.qxy, 2 * row)) || (rc = call.alloc(&d_ws, feat_ws(nullptr, 1, H, W, md, 0).bytes)) ||
-            (rc = call.alloc(&d_cnt, 1)) || (rc = call.alloc(&d_sc, row)))
-            return rc;
-        return OFLK_OK;
-    };
-    auto pass = [&](HostCall &call, oflk_plan *p, const PIXELS *d_frames, int b0, int, TrackRows &R) -> int {
-        int rc;
-        if (b0 == 0) {
-            if ((rc = detect_launch(d_frames, sizeof(PIXELS) == 1, 1, H, W, window_size, q, md, K, feat_ws(d_ws, 1, H, W, md, 0),
-                                    d_cnt, R.qxy, d_sc, nullptr, nullptr)) ||
-                (rc = call.to_host(count, d_cnt, 1)) || (rc = call.to_host(xy, R.qxy, 2 * row)) ||
-                (rc = call.to_host(score, d_sc, row)))
-                return rc;
-        }
-        return plan_sparse_tracks(p, d_frames, sizeof(PIXELS) == 1, alpha, beta, max_residual, b0, nullptr, R.qxy, K, R.tr, R.vis,
-                                  nullptr);
-    };
-    return run_sequence_sparse<PIXELS>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, K, tracks, visible, 0,
-                                       checks, setup, pass, no_part);
-}
-
-// oflk_pyramidal_sequence_klt_sparse_replenish: K slots, one replenished sparse pass (sparse_klt_pass, t0 = the chunk's
-// first frame) per chunk; rows, born, detected and residual come down.  Residual row 0 of a later chunk is the previous
-// chunk's last row, which is already on the host.
-template <class PIXELS>
-int sequence_klt_sparse_replenish(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
-                                  float beta, float max_residual, float q, float md, int K, int detect_every, float *tracks,
-                                  unsigned char *visible, unsigned char *born, int *detected, float *residual)
-{
-    const size_t row = (size_t)K;
-    SparseKlt k{q, md, K, detect_every, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    auto checks = [&]() -> int {
-        if (!tracks || !visible || !born || !detected) return fail(OFLK_ERR_INVALID, "NULL output argument");
-        if (detect_every < 1) return fail(OFLK_ERR_INVALID, "detect_every must be >= 1 (got %d)", detect_every);
-        return check_select(q, md, K);
-    };
-    auto setup = [&](HostCall &call, TrackRows &R, int C) -> int {
-        int rc;
-        char *d_ws = nullptr;
-        if ((rc = call.alloc(&R.qxy, 2 * row)) || (rc = call.alloc(&R.qt, row)) ||
-            (rc = call.alloc(&d_ws, feat_ws(nullptr, 1, H, W, md, K).bytes)) || (rc = call.alloc(&k.born, (size_t)(C + 1) * row)) ||
-            (rc = call.alloc(&k.detected, (size_t)C + 1)) || (rc = call.alloc(&k.residual, (size_t)(C + 1) * row, residual != nullptr)))
-            return rc;
-        k.ws = d_ws; k.qt = R.qt; k.qxy = R.qxy;
-        return OFLK_OK;
-    };
-    auto pass = [&](HostCall &, oflk_plan *p, const PIXELS *d_frames, int b0, int, TrackRows &R) -> int {
-        return sparse_klt_pass(p, d_frames, sizeof(PIXELS) == 1, alpha, beta, max_residual, b0, k, R.tr, R.vis, nullptr);
-    };
-    auto extras = [&](HostCall &call, int b0, int nb, int r0) -> int {
-        const size_t nr = (size_t)(nb + 1 - r0);
-        int rc;
-        if ((rc = call.to_host(born + (size_t)(b0 + r0) * row, k.born + (size_t)r0 * row, nr * row)) ||
-            (rc = call.to_host(detected + b0 + r0, k.detected + r0, nr)))
-            return rc;
-        const int q0 = b0 > 0 ? 1 : 0;
-        return residual ? call.to_host(residual + (size_t)(b0 + q0) * row, k.residual + (size_t)q0 * row, (size_t)(nb + 1 - q0) * row)
-                        : OFLK_OK;
-    };
-    return run_sequence_sparse<PIXELS>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, K, tracks, visible,
-                                       detect_every, checks, setup, pass, extras);
-}
+    static int pairs(int B, int H, int W) { return sparse_chunk_pairs(B, H, W); }
+    int alloc(HostCall &call, const Seq &seq, int C) { return call.alloc(&frames, (size_t)(C + 1) * seq.frame_bytes()); }
+    int upload(HostCall &call, const Seq &seq, int b0, int nb)
+    {
+        const size_t fb = seq.frame_bytes();
+        const int rc = host_plan(*call.c, call.dev, nb, seq.H, seq.W, seq.levels, seq.window_size, seq.iters, &pass.p);
+        return rc ? rc : call.to_device(frames, static_cast<const char *>(seq.frames) + (size_t)b0 * fb, (size_t)(nb + 1) * fb);
+    }
+    int ready(const Seq &seq) { return pass.begin(pass.p, frames, seq.u8, nullptr); }
+    const void *frame(const Seq &seq, int r) const { return frames + (size_t)r * seq.frame_bytes(); }
+    int step(const Seq &, const TrackRows &R, int N, int s0, int e, int r) const { return pass.step(R, N, s0, e, r); }
+};
 }  // namespace
 
 OFLK_API int oflk_sparse_lk(const float *prev, const float *curr, int H, int W, int levels, int window_size, int iters,
@@ -3466,8 +3438,8 @@ OFLK_API int oflk_pyramidal_sequence_sparse_tracks(const float *frames, int T, i
                                                    int iters, float alpha, float beta, float max_residual, const int *qt,
                                                    const float *qxy, int N, float *tracks, unsigned char *visible)
 {
-    return sequence_sparse_tracks<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, qt, qxy, N, tracks,
-                                         visible);
+    return run_sequence_tracks(Seq{frames, false, T, H, W, levels, window_size, iters}, SparseTracks{{alpha, beta, max_residual}},
+                               GivenQueries{qt, qxy, N}, N, tracks, visible);
 }
 
 OFLK_API int oflk_pyramidal_sequence_sparse_tracks_u8(const unsigned char *frames, int T, int H, int W, int levels,
@@ -3475,8 +3447,8 @@ OFLK_API int oflk_pyramidal_sequence_sparse_tracks_u8(const unsigned char *frame
                                                       const int *qt, const float *qxy, int N, float *tracks,
                                                       unsigned char *visible)
 {
-    return sequence_sparse_tracks<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, qt, qxy, N,
-                                                 tracks, visible);
+    return run_sequence_tracks(Seq{frames, true, T, H, W, levels, window_size, iters}, SparseTracks{{alpha, beta, max_residual}},
+                               GivenQueries{qt, qxy, N}, N, tracks, visible);
 }
 
 OFLK_API int oflk_pyramidal_sequence_klt_sparse(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
@@ -3484,8 +3456,8 @@ OFLK_API int oflk_pyramidal_sequence_klt_sparse(const float *frames, int T, int 
                                                 float min_distance, int max_corners, int *count, float *xy, float *score,
                                                 float *tracks, unsigned char *visible)
 {
-    return sequence_klt_sparse<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, quality_level,
-                                      min_distance, max_corners, count, xy, score, tracks, visible);
+    return run_sequence_tracks(Seq{frames, false, T, H, W, levels, window_size, iters}, SparseTracks{{alpha, beta, max_residual}},
+                               DetectOnce{quality_level, min_distance, max_corners, count, xy, score}, max_corners, tracks, visible);
 }
 
 OFLK_API int oflk_pyramidal_sequence_klt_sparse_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size,
@@ -3493,8 +3465,8 @@ OFLK_API int oflk_pyramidal_sequence_klt_sparse_u8(const unsigned char *frames, 
                                                    float min_distance, int max_corners, int *count, float *xy, float *score,
                                                    float *tracks, unsigned char *visible)
 {
-    return sequence_klt_sparse<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, quality_level,
-                                              min_distance, max_corners, count, xy, score, tracks, visible);
+    return run_sequence_tracks(Seq{frames, true, T, H, W, levels, window_size, iters}, SparseTracks{{alpha, beta, max_residual}},
+                               DetectOnce{quality_level, min_distance, max_corners, count, xy, score}, max_corners, tracks, visible);
 }
 
 OFLK_API int oflk_pyramidal_sequence_klt_sparse_replenish(const float *frames, int T, int H, int W, int levels, int window_size,
@@ -3503,9 +3475,9 @@ OFLK_API int oflk_pyramidal_sequence_klt_sparse_replenish(const float *frames, i
                                                           int detect_every, float *tracks, unsigned char *visible,
                                                           unsigned char *born, int *detected, float *residual)
 {
-    return sequence_klt_sparse_replenish<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual,
-                                                quality_level, min_distance, max_corners, detect_every, tracks, visible, born,
-                                                detected, residual);
+    return run_sequence_tracks(Seq{frames, false, T, H, W, levels, window_size, iters}, SparseTracks{{alpha, beta, max_residual}},
+                               Replenished{{quality_level, min_distance, max_corners, detect_every}, born, detected, residual},
+                               max_corners, tracks, visible);
 }
 
 OFLK_API int oflk_pyramidal_sequence_klt_sparse_replenish_u8(const unsigned char *frames, int T, int H, int W, int levels,
@@ -3515,9 +3487,9 @@ OFLK_API int oflk_pyramidal_sequence_klt_sparse_replenish_u8(const unsigned char
                                                              unsigned char *visible, unsigned char *born, int *detected,
                                                              float *residual)
 {
-    return sequence_klt_sparse_replenish<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual,
-                                                        quality_level, min_distance, max_corners, detect_every, tracks, visible,
-                                                        born, detected, residual);
+    return run_sequence_tracks(Seq{frames, true, T, H, W, levels, window_size, iters}, SparseTracks{{alpha, beta, max_residual}},
+                               Replenished{{quality_level, min_distance, max_corners, detect_every}, born, detected, residual},
+                               max_corners, tracks, visible);
 }
 
 OFLK_API int oflk_plan_sparse_klt_replenish(oflk_plan *plan, const void *d_frames, int u8, float alpha, float beta,
@@ -3542,9 +3514,19 @@ OFLK_API int oflk_plan_sparse_klt_replenish(oflk_plan *plan, const void *d_frame
     if (reinterpret_cast<uintptr_t>(d_workspace) % 256 != 0 || reinterpret_cast<uintptr_t>(d_qxy) % 8 != 0 ||
         reinterpret_cast<uintptr_t>(d_tracks) % 8 != 0)
         return fail(OFLK_ERR_INVALID, "d_workspace must be 256-byte aligned, d_qxy and d_tracks 8-byte aligned");
-    const SparseKlt k{quality_level, min_distance, max_corners, detect_every, d_workspace, d_qt, d_qxy, d_born, d_detected,
-                      d_residual};
-    return sparse_klt_pass(plan, d_frames, u8 != 0, alpha, beta, max_residual, t0, k, d_tracks, d_visible, (hipStream_t)stream);
+    // the plan's B+1 pyramids once, then the pairs t0 .. t0+B-1 as the host driver walks a chunk's: one chain of launches
+    const hipStream_t s = (hipStream_t)stream;
+    const Slots k{quality_level, min_distance, max_corners, detect_every, d_workspace, d_born, d_detected};
+    const TrackRows R{d_qt, d_qxy, d_tracks, d_visible, d_residual};
+    const size_t fb = (size_t)plan->H * plan->W * (u8 ? 1 : sizeof(float));
+    SparsePass pass{alpha, beta, max_residual};
+    if ((rc = pass.begin(plan, d_frames, u8 != 0, s)) || (rc = slots_begin(k, R, t0, plan->B, s))) return rc;
+    return walk_segments(
+        t0, plan->B, detect_every,
+        [&](int s0, int r) {
+            return slots_detect(k, R, static_cast<const char *>(d_frames) + r * fb, u8 != 0, plan->H, plan->W, plan->win, s0, r, s);
+        },
+        [&](int s0, int e, int r) { return pass.step(R, max_corners, s0, e, r); });
 }
 
 // =============================================================================
@@ -3827,9 +3809,10 @@ int stabilize_sequence(const PIX *frames, int T, int H, int W, int levels, int w
     } catch (const std::exception &) {
         return fail(OFLK_ERR_NOMEM, "no host memory for the rows of %d frames of %d slots", T, K);
     }
-    if ((rc = sequence_klt_sparse_replenish<PIX>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, q, md, K,
-                                                 detect_every, tracks.data(), visible.data(), born.data(), detected.data(),
-                                                 nullptr)))
+    if ((rc = run_sequence_tracks(Seq{frames, sizeof(PIX) == 1, T, H, W, levels, window_size, iters},
+                                  SparseTracks{{alpha, beta, max_residual}},
+                                  Replenished{{q, md, K, detect_every}, born.data(), detected.data(), nullptr}, K, tracks.data(),
+                                  visible.data())))
         return rc;
     HostCall call;
     if ((rc = call.begin())) return rc;
@@ -4039,15 +4022,7 @@ SparseArgs tracker_args(const oflk_tracker *tr)
     SparseArgs a{};
     a.frames = tr->ring;
     a.L = tr->L; a.K = tr->iters; a.B = 1; a.H = tr->H; a.W = tr->W; a.N = tr->K;
-    for (int l = 0; l < tr->L; l++) {
-        a.pyr[l] = tr->pyr[l];
-        a.dims[2 * l] = tr->dims[2 * l];
-        a.dims[2 * l + 1] = tr->dims[2 * l + 1];
-        if (l > 0) {   // upsample_args' ratios
-            a.sx[l] = (float)((double)tr->dims[2 * l + 1] / (double)tr->dims[2 * l - 1]);
-            a.sy[l] = (float)((double)tr->dims[2 * l] / (double)tr->dims[2 * l - 2]);
-        }
-    }
+    sparse_levels(&a, tr->L, tr->pyr, tr->dims);
     a.alpha = tr->alpha; a.beta = tr->beta; a.max_residual = tr->max_residual;
     return a;
 }
@@ -4159,16 +4134,6 @@ std::vector<float> tracker_filter_points(const oflk_tracker *tr, const float *pt
     return keep;
 }
 
-// the frame sizes a plan takes (oflk_plan_create's bounds, which the sequence call meets there)
-int check_frame_size(int H, int W)
-{
-    if (H < 1 || W < 1) return fail(OFLK_ERR_INVALID, "H and W must be >= 1 (got %d x %d)", H, W);
-    if ((size_t)H * (size_t)W >= ((size_t)1 << 29)) return fail(OFLK_ERR_UNSUPPORTED, "frames of 2^29 pixels or more are not supported");
-    if (H >= kMaxDim || W >= kMaxDim)
-        return fail(OFLK_ERR_UNSUPPORTED, "frames of 2^23 rows or columns or more are not supported (got %d x %d)", H, W);
-    return OFLK_OK;
-}
-
 int tracker_pushed(const oflk_tracker *tr)
 {
     if (!tr) return fail(OFLK_ERR_INVALID, "NULL tracker");
@@ -4183,7 +4148,8 @@ OFLK_API int oflk_tracker_create(oflk_tracker **out, int device, int H, int W, i
 {
     if (!out) return fail(OFLK_ERR_INVALID, "tracker pointer is NULL");
     *out = nullptr;
-    int rc = check_frame_size(H, W);
+    if (H < 1 || W < 1) return fail(OFLK_ERR_INVALID, "H and W must be >= 1 (got %d x %d)", H, W);
+    int rc = check_frame_bounds(H, W);   // oflk_plan_create's, which the sequence call meets there
     if (rc || (rc = check_sparse_test(alpha, beta, max_residual)) || (rc = check_sparse_config(H, W, levels, window_size, iters)) ||
         (rc = check_select(quality_level, min_distance, max_corners)))
         return rc;

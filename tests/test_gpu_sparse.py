@@ -229,6 +229,15 @@ def test_a_long_sequence_is_cut_into_chunks():
     want = S.track(frames, qt, qxy, 3, 5, 3)
     assert want[1][65:].sum() > 20   # tracks live across the cut
     _same_tracks(P.lucas_kanade_pyramidal_sequence_sparse_tracks(frames, queries), want, "70 frames")
+    # The detect-then-track form across the same cut: its detection runs once, ahead of chunk 0, and chunk 1 continues
+    # the carried row.  It must equal the given-queries form on its own corners (which the line above ties to the
+    # statement).  Live marks are counted as above, over rows 65 .. 69: tests/sparse_model.py on these frames with
+    # min_distance = 3 gives 31 (float32: 16 corners, 7 alive on frame 65) and 21 (uint8: 16 corners, 5 alive).  The
+    # 24 x 32 scene has no more than 19 corners at any min_distance, so the count cannot be of distinct tracks.
+    for name, f in (("float32", frames), ("uint8", np.rint(frames).astype(np.uint8))):
+        r = P.lucas_kanade_pyramidal_sequence_klt_sparse(f, 96, 0.01, 3.0)
+        assert r.visible[65:].sum() >= 20 and r.visible[65].sum() >= 5, name   # marks after the cut; tracks that cross it
+        _same_tracks((r.tracks, r.visible), P.lucas_kanade_pyramidal_sequence_sparse_tracks(f, r.xy), f"klt_sparse, {name}")
 
 
 def _scene():

@@ -618,6 +618,83 @@ int oflk_stabilize_sequence_u8(const unsigned char *frames, int T, int H, int W,
                                const double *weights, int radius, unsigned char *out, float *correction, float *model_out,
                                int *counts_out, unsigned char *held);
 
+/* ---- online video stabilisation: a fixed-lag stabiliser on the tracker --------------------------------------------------- */
+/* The statement (tests/stabilize_online_model.py) is the trajectory above, read in the order in which a stream delivers its
+ * steps.  The window of frame f is r_f = min(r, f, T-1-f) and reads steps f - r_f .. f + r_f - 1 only, so frame f is final
+ * once frame f + r has been pushed, and the last r frames are final once the stream is known to have ended.  A stabiliser
+ * of radius r therefore emits frame t - r on the push of frame t >= r (lag = r frames) and the remaining min(r, T) frames,
+ * ascending, on a flush, which supplies the true T.  By statement, byte for byte: the frames and corrections of T pushes
+ * and a flush are `out` and `correction` of oflk_stabilize_sequence[_u8] on the same T frames with the same arguments
+ * (that call wants T >= 2 and detect_every >= 1; the stabiliser also takes one frame, and detect_every = 0).  A slot filled
+ * by a detection on the last pushed frame does not count: its born mark keeps it out of the step into that frame, which is
+ * what the sequence call, which never detects on its last frame, sees as a dead slot.  With r = 0 every push emits its own
+ * frame under the identity.
+ * oflk_stabilize_trajectory_ring is the trajectory of n consecutive frames f0 .. f0 + n - 1 whose steps lie in a ring: step
+ * s at slot s % cap of d_model_ring [cap][6] float32 and d_counts_ring [cap][3] int32 (or NULL), cap >= max(2 r, 1).
+ * T = -1: the stream is open, r_f = min(r, f) and n = 1; T >= 0: r_f = min(r, f, T-1-f) and f0 + n <= T.  Only the slots of
+ * steps f - r_f .. f + r_f - 1 are read.  d_correction [n][6], d_map [n][6] as oflk_stabilize_trajectory's rows f0 ..
+ * f0 + n - 1, every value formed by the same operations in the same order.  One launch, one block per frame (the window's
+ * inversions side by side, the two chains on two lanes), the weights in the launch arguments; asynchronous; can be captured.
+ *
+ * State of a stabiliser: a tracker with its motion row on (its state is listed there), a delay line of r + 1 frames in the
+ * input pixel type -- (r + 1) H W pixels, 33 MB for 1080p bytes at r = 15 --, the ring of 2 r step models and counts, and r
+ * rows of correction and map.  Creation checks the configuration and makes no device call; the first push allocates all of
+ * it and no later push allocates.  The host forms stage one frame and one mask on the device; those two planes come with
+ * the first host call.  oflk_stabilizer_workspace_bytes counts everything, the inner tracker included.
+ * A push of frame t enqueues on the one stream: the frame copied into delay slot t % (r + 1); the tracker's push of that
+ * slot, whose fit (t >= 1) writes step t-1 straight into ring slot (t-1) % cap; and for t >= r the trajectory of frame
+ * t - r (one launch) and one oflk_warp_affine launch of its delay slot into d_out.  A flush enqueues one trajectory launch
+ * for its frames and at most two warp launches (the delay line wraps once).  Nothing synchronises in the device forms.
+ * Pushes are enqueued from host-side state, so they are not made for graph capture (as the tracker's).  A push or flush
+ * that fails part-way leaves the frame index as it was, and every later push is refused with OFLK_ERR_INVALID until
+ * oflk_stabilizer_reset.  After a flush (also one that had nothing to emit) every push is refused with OFLK_ERR_INVALID
+ * until oflk_stabilizer_reset; a second flush emits nothing.  A stabiliser is single-stream: every call on it is ordered by
+ * the caller.
+ * Refusals, before any device call: what oflk_tracker_create refuses about device, shape, window, levels, iterations,
+ * alpha, beta, max_residual, quality_level, min_distance, max_corners and detect_every, what oflk_tracker_set_motion refuses
+ * about model (a model is required: model < 0 is OFLK_ERR_INVALID), hypotheses and threshold, and what
+ * oflk_stabilize_trajectory refuses about weights and radius, with their codes; H or W < 2: OFLK_ERR_INVALID.  A NULL
+ * stabiliser, frame, output, `emitted`, `first` or `count` (d_inside, inside and correction may be NULL; the flush's output
+ * when nothing is left), float32 device frames not 4-byte aligned, correction_device before the first emission:
+ * OFLK_ERR_INVALID.  oflk_stabilize_trajectory_ring: the window's refusals, cap < max(2 radius, 1), n < 1 or n > 128,
+ * f0 < 0, T < -1, T >= 0 with f0 + n > T, T = -1 with n != 1, NULL pointers (d_counts_ring may be NULL), d_map not 8-byte
+ * aligned: OFLK_ERR_INVALID. */
+typedef struct oflk_stabilizer oflk_stabilizer;
+int oflk_stabilize_trajectory_ring(const float *d_model_ring, const int *d_counts_ring /* may be NULL */, int cap, int f0, int n,
+                                   int T /* -1: the stream is open */, const double *weights /* host, [radius + 1] */, int radius,
+                                   float *d_correction /* [n][6] */, double *d_map /* [n][6] */, void *stream);
+int oflk_stabilizer_create(oflk_stabilizer **st, int device, int H, int W, int u8, int levels, int window_size, int iters,
+                           float alpha, float beta, float max_residual, float quality_level, float min_distance,
+                           int max_corners, int detect_every, int model, int hypotheses, float threshold, unsigned seed,
+                           const double *weights /* host, [radius + 1], copied */, int radius);
+int oflk_stabilizer_destroy(oflk_stabilizer *st);
+int oflk_stabilizer_reset(oflk_stabilizer *st, void *stream);      /* frame index -1, the inner tracker reset, pushes taken again */
+size_t oflk_stabilizer_workspace_bytes(const oflk_stabilizer *st); /* what is allocated at the moment, the tracker's included */
+int oflk_stabilizer_lag(const oflk_stabilizer *st);                /* = radius: frame t - lag comes out of the push of frame t */
+int oflk_stabilizer_frame_index(const oflk_stabilizer *st);        /* index of the last pushed frame, -1 before the first */
+/* device frame [H][W] in, the steadied frame *emitted = t - r into d_out [H][W] (and d_inside [H][W] bytes, may be NULL) when
+ * t >= r; else *emitted = -1 and neither is written.  *emitted is known on the host when the call returns.  Asynchronous
+ * on `stream`, no host synchronisation */
+int oflk_stabilizer_push_device(oflk_stabilizer *st, const void *d_frame, void *d_out, unsigned char *d_inside, int *emitted,
+                                void *stream);
+/* host frame in, host frame out (and inside, and the emitted frame's correction [6]; both may be NULL), through the staged
+ * planes on the null stream; synchronous */
+int oflk_stabilizer_push(oflk_stabilizer *st, const void *frame, void *out, unsigned char *inside, float *correction,
+                         int *emitted);
+/* the stream has ended: the *count = min(r, T) frames not yet emitted, *first .. *first + *count - 1, into d_out
+ * [radius][H][W] (and d_inside, may be NULL) with the true T.  *count is 0 before any push and after a flush */
+int oflk_stabilizer_flush_device(oflk_stabilizer *st, void *d_out, unsigned char *d_inside, int *first, int *count, void *stream);
+/* host arrays: out [radius][H][W], inside (may be NULL), correction [radius][6] (may be NULL); synchronous */
+int oflk_stabilizer_flush(oflk_stabilizer *st, void *out, unsigned char *inside, float *correction, int *first, int *count);
+/* device pointers (each may be NULL) to the rows of the last emission -- one row after a push, *count after a flush --,
+ * valid until the next push, flush or reset: correction [rows][6] float32, map [rows][6] float64 */
+int oflk_stabilizer_correction_device(const oflk_stabilizer *st, const float **d_correction, const double **d_map);
+/* The inner tracker, owned by the stabiliser, for oflk_tracker_row_device / read_row / motion_device / read_motion /
+ * add_points / frame_index: the row and the step's motion of the last pushed frame (not of the emitted one).  Pushing it,
+ * resetting it, destroying it or changing its motion directly is the caller's error: the stabiliser's frames and steps
+ * would no longer be the tracker's. */
+oflk_tracker *oflk_stabilizer_tracker(oflk_stabilizer *st);
+
 /* Rehearsal of the chunk queue above on a box with fewer GPUs than workers (tests): `workers` > 0 makes the *_multi entry
  * points run that many queue workers, worker i on device i % n_gpus (workers of one device take turns on it); 0 restores
  * one worker per device.  Results do not change. */

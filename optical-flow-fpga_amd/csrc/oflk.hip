@@ -4302,6 +4302,335 @@ OFLK_API int oflk_tracker_read_motion(oflk_tracker *tr, float *model, unsigned c
     return OFLK_OK;
 }
 
+// =============================================================================
+// online video stabilisation: a fixed-lag stabiliser on the tracker
+// =============================================================================
+// The state of a stabiliser: a tracker with its motion row on, and what the trajectory's window needs of the past -- the
+// last r + 1 frames (frame t in delay slot t % (r + 1)) and the last cap = max(2 r, 1) step models (step s in ring slot
+// s % cap).  The fit of the push of frame t writes step t-1 straight into its ring slot: the tracker's motion-row pointers
+// are aimed there before the push (frame 0's failure row goes to the tracker's own buffers), so the inner tracker's
+// motion_device / read_motion show the step as on a plain tracker.  Creation makes no device call; the first push
+// allocates everything but the one-frame staging of the host forms, which comes with their first call.
+struct oflk_stabilizer {
+    oflk_tracker *tr = nullptr;
+    int r = 0, cap = 1;
+    StabWeights wt{};
+    long long t = -1;                 // index of the last pushed frame
+    bool ready = false;               // the device state exists
+    bool failed = false;              // a push or flush failed part-way: refused until reset
+    bool flushed = false;             // the stream has ended: pushes are refused until reset
+    int rows = 0;                     // rows of corr / map the last emission wrote
+    size_t ws_bytes = 0;
+    char *delay = nullptr;            // [r + 1][H][W], the input pixel type
+    float *ring_model = nullptr;      // [cap][6]
+    int *ring_counts = nullptr;       // [cap][3]
+    float *corr = nullptr;            // [max(r, 1)][6]
+    double *map = nullptr;            // [max(r, 1)][6]
+    float *own_model = nullptr;       // the tracker's own motion row, put back before it is freed
+    int *own_counts = nullptr;
+    char *stage_out = nullptr;        // [H][W] in the pixel type and [H][W] bytes: the host forms' staging
+    unsigned char *stage_inside = nullptr;
+
+    size_t plane_bytes() const { return (size_t)tr->H * tr->W * tr->pix_bytes(); }
+    char *slot(long long f) const { return delay + (size_t)(f % (r + 1)) * plane_bytes(); }
+};
+
+namespace {
+int check_trajectory_ring(const void *model, int cap, int f0, int n, int T, const double *weights, int radius, const void *correction,
+                          const void *map)
+{
+    if (int rc = check_stab_window(weights, radius)) return rc;
+    if (cap < std::max(2 * radius, 1))
+        return fail(OFLK_ERR_INVALID, "cap must be >= max(2 radius, 1) = %d (got %d)", std::max(2 * radius, 1), cap);
+    if (n < 1 || n > kStabOnlineBlock) return fail(OFLK_ERR_INVALID, "n must be in [1, %d] (got %d)", kStabOnlineBlock, n);
+    if (f0 < 0) return fail(OFLK_ERR_INVALID, "f0 must be >= 0 (got %d)", f0);
+    if (T < -1) return fail(OFLK_ERR_INVALID, "T must be >= 0, or -1 while the stream is open (got %d)", T);
+    if (T >= 0 && (long long)f0 + n > (long long)T)
+        return fail(OFLK_ERR_INVALID, "frames %d .. %lld of a stream of %d", f0, (long long)f0 + n - 1, T);
+    if (T < 0 && n != 1) return fail(OFLK_ERR_INVALID, "an open stream has one final frame at a time (n = %d)", n);
+    if (!model || !correction || !map) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    if (!aligned(map, 8)) return fail(OFLK_ERR_INVALID, "d_map must be 8-byte aligned");
+    return OFLK_OK;
+}
+
+// the one launch of k_stab_online on stream s; the arguments are checked
+int trajectory_ring_launch(const float *d_model, const int *d_counts, int cap, int f0, int n, int T, const StabWeights &wt, int radius,
+                           float *d_correction, double *d_map, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_stab_online, dim3((unsigned)n), dim3(kStabOnlineBlock), 0, s, d_model, d_counts, cap, f0, T, radius, wt,
+                       d_correction, d_map);
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+
+int stabilizer_warp(const oflk_stabilizer *st, const void *d_frames, int F, const double *d_map, void *d_out, unsigned char *d_inside,
+                    hipStream_t s)
+{
+    const oflk_tracker *tr = st->tr;
+    int rc = OFLK_OK;
+    with_pix(tr->u8, [&](auto PIX) {
+        using P = typename decltype(PIX)::type;
+        rc = warp_affine_launch<P>((const P *)d_frames, F, tr->H, tr->W, d_map, (P *)d_out, d_inside, s);
+    });
+    return rc;
+}
+
+// the device state, on the first push
+int stabilizer_ensure_state(oflk_stabilizer *st)
+{
+    oflk_tracker *tr = st->tr;
+    int rc = tracker_ensure_state(tr);
+    if (rc || st->ready) return rc;
+    if (st->ws_bytes) return fail(OFLK_ERR_NOMEM, "the stabiliser's state could not be allocated by an earlier push");
+    if ((rc = tracker_ensure_motion(tr))) return rc;
+    const size_t rows = (size_t)std::max(st->r, 1);
+    if ((rc = dmalloc(&st->delay, (size_t)(st->r + 1) * st->plane_bytes(), &st->ws_bytes)) ||
+        (rc = dmalloc(&st->ring_model, 6 * (size_t)st->cap, &st->ws_bytes)) ||
+        (rc = dmalloc(&st->ring_counts, 3 * (size_t)st->cap, &st->ws_bytes)) || (rc = dmalloc(&st->corr, 6 * rows, &st->ws_bytes)) ||
+        (rc = dmalloc(&st->map, 6 * rows, &st->ws_bytes)))
+        return rc;
+    st->own_model = tr->m_out;
+    st->own_counts = tr->m_counts;
+    st->ready = true;
+    return OFLK_OK;
+}
+
+// the staging of the host forms, on their first call
+int stabilizer_ensure_stage(oflk_stabilizer *st)
+{
+    if (st->stage_out) return OFLK_OK;
+    int rc = dmalloc(&st->stage_out, st->plane_bytes(), &st->ws_bytes);
+    if (!rc) rc = dmalloc(&st->stage_inside, (size_t)st->tr->H * st->tr->W, &st->ws_bytes);
+    return rc;
+}
+
+// what every push and flush is refused for
+int stabilizer_open(const oflk_stabilizer *st, const char *what)
+{
+    if (st->flushed) return fail(OFLK_ERR_INVALID, "the stabiliser has been flushed: reset it before %s", what);
+    if (st->failed) return fail(OFLK_ERR_INVALID, "an earlier push or flush failed part-way: reset the stabiliser before %s", what);
+    return OFLK_OK;
+}
+
+// One push on stream s: the frame (host or device memory) into its delay slot, the tracker's push of that slot with the fit
+// aimed at the step's ring slot, and for t >= r the trajectory of frame t - r and its warp into d_out.  Nothing is
+// synchronised.  The frame index moves only when every launch was accepted.
+int stabilizer_enqueue(oflk_stabilizer *st, const void *src, hipMemcpyKind kind, void *d_out, unsigned char *d_inside, hipStream_t s)
+{
+    oflk_tracker *tr = st->tr;
+    const long long t = st->t + 1;
+    char *frame = st->slot(t);
+    HIP_TRY(hipMemcpyAsync(frame, src, st->plane_bytes(), kind, s));
+    const size_t k = t >= 1 ? (size_t)((t - 1) % st->cap) : 0;
+    tr->m_out = t >= 1 ? st->ring_model + 6 * k : st->own_model;
+    tr->m_counts = t >= 1 ? st->ring_counts + 3 * k : st->own_counts;
+    int rc = tracker_push(tr, frame, hipMemcpyDeviceToDevice, s);
+    if (rc) return rc;
+    if (t >= st->r) {
+        const long long e = t - st->r;
+        if ((rc = trajectory_ring_launch(st->ring_model, st->ring_counts, st->cap, (int)e, 1, -1, st->wt, st->r, st->corr, st->map, s)) ||
+            (rc = stabilizer_warp(st, st->slot(e), 1, st->map, d_out, d_inside, s)))
+            return rc;
+        st->rows = 1;
+    }
+    st->t = t;
+    return OFLK_OK;
+}
+
+int stabilizer_push(oflk_stabilizer *st, const void *src, hipMemcpyKind kind, void *d_out, unsigned char *d_inside, int *emitted,
+                    hipStream_t s)
+{
+    if (emitted) *emitted = -1;
+    if (!st || !src || !d_out || !emitted) return fail(OFLK_ERR_INVALID, "NULL argument");
+    int rc = stabilizer_open(st, "it is pushed again");
+    if (rc || (rc = stabilizer_ensure_state(st))) return rc;   // a refusal here has written nothing
+    if ((rc = stabilizer_enqueue(st, src, kind, d_out, d_inside, s))) {
+        st->failed = true;
+        return rc;
+    }
+    if (st->t >= st->r) *emitted = (int)(st->t - st->r);
+    return OFLK_OK;
+}
+
+// A flush up to the trajectory: the refusals, the frames that are left (first, n) and their rows of corr / map on stream s
+int stabilizer_flush_begin(oflk_stabilizer *st, const void *out, int *first, int *count, hipStream_t s)
+{
+    if (first) *first = 0;
+    if (count) *count = 0;
+    if (!st || !first || !count) return fail(OFLK_ERR_INVALID, "NULL argument");
+    if (st->failed) return fail(OFLK_ERR_INVALID, "an earlier push or flush failed part-way: reset the stabiliser");
+    const long long T = st->t + 1;
+    const int n = st->flushed ? 0 : (int)std::min<long long>(st->r, T);
+    *first = (int)(T - n);
+    if (n == 0) {
+        st->flushed = true;
+        return OFLK_OK;
+    }
+    if (!out) return fail(OFLK_ERR_INVALID, "NULL output for the %d frames that are left", n);
+    HIP_TRY(hipSetDevice(st->tr->device));
+    st->flushed = true;
+    if (int rc = trajectory_ring_launch(st->ring_model, st->ring_counts, st->cap, *first, n, (int)T, st->wt, st->r, st->corr, st->map, s)) {
+        st->failed = true;
+        return rc;
+    }
+    st->rows = n;
+    *count = n;
+    return OFLK_OK;
+}
+}  // namespace
+
+OFLK_API int oflk_stabilize_trajectory_ring(const float *d_model_ring, const int *d_counts_ring, int cap, int f0, int n, int T,
+                                            const double *weights, int radius, float *d_correction, double *d_map, void *stream)
+{
+    if (int rc = check_trajectory_ring(d_model_ring, cap, f0, n, T, weights, radius, d_correction, d_map)) return rc;
+    StabWeights wt{};
+    for (int i = 0; i <= radius; i++) wt.w[i] = weights[i];
+    return trajectory_ring_launch(d_model_ring, d_counts_ring, cap, f0, n, T, wt, radius, d_correction, d_map, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_stabilizer_create(oflk_stabilizer **out, int device, int H, int W, int u8, int levels, int window_size, int iters,
+                                    float alpha, float beta, float max_residual, float quality_level, float min_distance,
+                                    int max_corners, int detect_every, int model, int hypotheses, float threshold, unsigned seed,
+                                    const double *weights, int radius)
+{
+    if (!out) return fail(OFLK_ERR_INVALID, "stabiliser pointer is NULL");
+    *out = nullptr;
+    if (H < 2 || W < 2) return fail(OFLK_ERR_INVALID, "H and W must be >= 2 (got %d x %d)", H, W);
+    int rc = check_motion(model, hypotheses, threshold);
+    if (rc || (rc = check_stab_window(weights, radius))) return rc;
+    oflk_tracker *tr = nullptr;
+    if ((rc = oflk_tracker_create(&tr, device, H, W, u8, levels, window_size, iters, alpha, beta, max_residual, quality_level,
+                                  min_distance, max_corners, detect_every)) ||
+        (rc = oflk_tracker_set_motion(tr, model, hypotheses, threshold, seed))) {
+        tracker_free(tr);
+        return rc;
+    }
+    oflk_stabilizer *st = new oflk_stabilizer();
+    st->tr = tr;
+    st->r = radius;
+    st->cap = std::max(2 * radius, 1);
+    for (int i = 0; i <= radius; i++) st->wt.w[i] = weights[i];
+    *out = st;
+    return OFLK_OK;
+}
+
+OFLK_API int oflk_stabilizer_destroy(oflk_stabilizer *st)
+{
+    if (!st) return OFLK_OK;
+    if (st->ready) {   // the tracker frees its own motion row
+        st->tr->m_out = st->own_model;
+        st->tr->m_counts = st->own_counts;
+    }
+    if (st->ws_bytes) (void)hipSetDevice(st->tr->device);
+    for (void *q : {(void *)st->delay, (void *)st->ring_model, (void *)st->ring_counts, (void *)st->corr, (void *)st->map,
+                    (void *)st->stage_out, (void *)st->stage_inside})
+        if (q) (void)hipFree(q);
+    tracker_free(st->tr);
+    delete st;
+    return OFLK_OK;
+}
+
+OFLK_API int oflk_stabilizer_reset(oflk_stabilizer *st, void *stream)
+{
+    if (!st) return fail(OFLK_ERR_INVALID, "NULL stabiliser");
+    st->t = -1;
+    st->rows = 0;
+    st->failed = st->flushed = false;
+    return oflk_tracker_reset(st->tr, stream);
+}
+
+OFLK_API size_t oflk_stabilizer_workspace_bytes(const oflk_stabilizer *st) { return st ? st->ws_bytes + st->tr->ws_bytes : 0; }
+
+OFLK_API int oflk_stabilizer_lag(const oflk_stabilizer *st) { return st ? st->r : -1; }
+
+OFLK_API int oflk_stabilizer_frame_index(const oflk_stabilizer *st) { return st ? (int)st->t : -1; }
+
+OFLK_API oflk_tracker *oflk_stabilizer_tracker(oflk_stabilizer *st) { return st ? st->tr : nullptr; }
+
+OFLK_API int oflk_stabilizer_push_device(oflk_stabilizer *st, const void *d_frame, void *d_out, unsigned char *d_inside, int *emitted,
+                                         void *stream)
+{
+    if (st && !st->tr->u8 && (!aligned(d_frame, 4) || !aligned(d_out, 4))) {
+        if (emitted) *emitted = -1;
+        return fail(OFLK_ERR_INVALID, "float32 frames must be 4-byte aligned");
+    }
+    return stabilizer_push(st, d_frame, hipMemcpyDeviceToDevice, d_out, d_inside, emitted, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_stabilizer_correction_device(const oflk_stabilizer *st, const float **d_correction, const double **d_map)
+{
+    if (!st) return fail(OFLK_ERR_INVALID, "NULL stabiliser");
+    if (st->rows < 1) return fail(OFLK_ERR_INVALID, "no frame has been emitted yet");
+    if (d_correction) *d_correction = st->corr;
+    if (d_map) *d_map = st->map;
+    return OFLK_OK;
+}
+
+OFLK_API int oflk_stabilizer_push(oflk_stabilizer *st, const void *frame, void *out, unsigned char *inside, float *correction,
+                                  int *emitted)
+{
+    if (emitted) *emitted = -1;
+    if (!st || !frame || !out || !emitted) return fail(OFLK_ERR_INVALID, "NULL argument");
+    int rc = stabilizer_open(st, "it is pushed again");
+    if (rc || (rc = stabilizer_ensure_state(st)) || (rc = stabilizer_ensure_stage(st))) return rc;
+    if ((rc = stabilizer_push(st, frame, hipMemcpyHostToDevice, st->stage_out, inside ? st->stage_inside : nullptr, emitted, nullptr))) {
+        if (st->ready) (void)hipStreamSynchronize(nullptr);   // a copy from the caller's frame may be queued
+        return rc;
+    }
+    if (*emitted >= 0) {
+        HIP_TRY(hipMemcpyAsync(out, st->stage_out, st->plane_bytes(), hipMemcpyDeviceToHost, nullptr));
+        if (inside) HIP_TRY(hipMemcpyAsync(inside, st->stage_inside, (size_t)st->tr->H * st->tr->W, hipMemcpyDeviceToHost, nullptr));
+        if (correction) HIP_TRY(hipMemcpyAsync(correction, st->corr, 6 * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    }
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return OFLK_OK;
+}
+
+OFLK_API int oflk_stabilizer_flush_device(oflk_stabilizer *st, void *d_out, unsigned char *d_inside, int *first, int *count, void *stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    int rc = stabilizer_flush_begin(st, d_out, first, count, s);
+    if (rc || *count == 0) return rc;
+    // frames first .. first + n - 1 lie in consecutive delay slots that wrap at most once: two launches at the most
+    const int n = *count, slots = st->r + 1, s0 = *first % slots, n0 = std::min(n, slots - s0);
+    const size_t pb = st->plane_bytes(), plane = (size_t)st->tr->H * st->tr->W;
+    if ((rc = stabilizer_warp(st, st->delay + (size_t)s0 * pb, n0, st->map, d_out, d_inside, s)) ||
+        (n > n0 && (rc = stabilizer_warp(st, st->delay, n - n0, st->map + 6 * (size_t)n0, static_cast<char *>(d_out) + (size_t)n0 * pb,
+                                         d_inside ? d_inside + (size_t)n0 * plane : nullptr, s)))) {
+        st->failed = true;
+        *count = 0;
+    }
+    return rc;
+}
+
+OFLK_API int oflk_stabilizer_flush(oflk_stabilizer *st, void *out, unsigned char *inside, float *correction, int *first, int *count)
+{
+    int rc = stabilizer_flush_begin(st, out, first, count, nullptr);
+    if (rc || *count == 0) return rc;
+    const int n = *count;
+    *count = 0;
+    if ((rc = stabilizer_ensure_stage(st))) {
+        st->failed = true;
+        return rc;
+    }
+    // frame by frame through the one staged frame; the null stream orders a frame's copies ahead of the next warp
+    const size_t pb = st->plane_bytes(), plane = (size_t)st->tr->H * st->tr->W;
+    for (int i = 0; i < n; i++) {
+        if ((rc = stabilizer_warp(st, st->slot((long long)*first + i), 1, st->map + 6 * (size_t)i, st->stage_out,
+                                  inside ? st->stage_inside : nullptr, nullptr))) {
+            st->failed = true;
+            (void)hipStreamSynchronize(nullptr);
+            return rc;
+        }
+        HIP_TRY(hipMemcpyAsync(static_cast<char *>(out) + (size_t)i * pb, st->stage_out, pb, hipMemcpyDeviceToHost, nullptr));
+        if (inside) HIP_TRY(hipMemcpyAsync(inside + (size_t)i * plane, st->stage_inside, plane, hipMemcpyDeviceToHost, nullptr));
+    }
+    if (correction) HIP_TRY(hipMemcpyAsync(correction, st->corr, 6 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    *count = n;
+    return OFLK_OK;
+}
+
 OFLK_API int oflk_pyramidal_last_level_flow(int B, int H, int W, int levels, int window_size, int iters, int level,
                                             int pair, float *u, float *v)
 {

@@ -1,6 +1,6 @@
-// oflk_stabilize.hpp -- gfx950 device code of video stabilisation (oflk_stabilize_trajectory, oflk_warp_affine and the
-// sequence call made of them): the smoothed trajectory of the global motion's step models, and the resampling of whole
-// frames under one 2 x 3 map each.
+// oflk_stabilize.hpp -- gfx950 device code of video stabilisation (oflk_stabilize_trajectory, oflk_warp_affine, the
+// sequence call and the online stabiliser made of them): the smoothed trajectory of the global motion's step models, and
+// the resampling of whole frames under one 2 x 3 map each.
 //
 // The statement is tests/stabilize_model.py (include/oflk.h repeats it).  Everything here is float64 in that file's
 // operation order, every operation rounded on its own; nothing is contracted and there is no transcendental: the window's
@@ -10,6 +10,9 @@
 //                       inverts the steps it needs itself, so there is no workspace, no atomics and nothing passes
 //                       between threads; the weights travel by value in the launch arguments, so the launch needs no
 //                       upload and can be captured
+//   k_stab_online       the same trajectory for n consecutive frames whose steps lie in a ring (the online stabiliser's,
+//                       oflk_stabilize_trajectory_ring): one block per frame, the inversions of its window side by side,
+//                       the two chains on two lanes, the six weighted sums on six
 //   k_warp_affine<PIX, VEC>  one launch for F frames.  A lane owns kWarpPx consecutive output pixels of a row.  VEC (the row
 //                       length a multiple of kWarpPx and the bases aligned to a lane's store) stores them as one float4
 //                       (float) or one dword (bytes, and the inside mask); every other shape and alignment runs the
@@ -24,6 +27,7 @@
 namespace oflk {
 
 constexpr int kStabBlock = 64;   // k_stab_trajectory's block
+constexpr int kStabOnlineBlock = 2 * OFLK_STABILIZE_MAX_RADIUS;   // k_stab_online's: one lane per step of the widest window
 constexpr int kWarpPx = 4;       // consecutive output pixels of a lane of k_warp_affine
 
 struct StabWeights {
@@ -127,6 +131,80 @@ __global__ __launch_bounds__(kStabBlock) void k_stab_trajectory(const float *__r
     for (int k = 0; k < 6; k++) {
         correction[6 * (size_t)t + k] = (float)cd[k];
         map[6 * (size_t)t + k] = m[k];
+    }
+}
+
+// ---- the trajectory of n consecutive frames from a ring of steps: grid (n), block kStabOnlineBlock ----
+// Block b owns frame f = f0 + b.  T < 0: the stream is open and the window is min(radius, f); else min(radius, f, T-1-f).
+// Step s lives at ring slot s % cap.  The values are k_stab_trajectory's, each formed by the same operations in the same
+// order; what does not depend on the chain's order runs side by side:
+//   lanes j < 2 r_f   load and invert step f - r_f + j: A and B into LDS
+//   lanes 0 and 1     the forward chain F_i = A_{f+i-1} o F_{i-1} and the backward chain G_i = B_{f-i} o G_{i-1}: one
+//                     instruction stream on two LDS addresses, every F_i and G_i kept
+//   lanes k < 6       coefficient k: acc += w_i F_i[k]; acc += w_i G_i[k] in i's order, ws likewise, the quotient, float32
+//   lane 0            the inverse of the correction, or the identity for both
+__global__ __launch_bounds__(kStabOnlineBlock) void k_stab_online(const float *__restrict__ model, const int *__restrict__ counts,
+                                                                  int cap, int f0, int T, int radius, StabWeights wt,
+                                                                  float *__restrict__ correction, double *__restrict__ map)
+{
+    __shared__ double step[2][kStabOnlineBlock][6];                   // [0]: A, [1]: B, of step f - r_f + j
+    __shared__ double chain[2][OFLK_STABILIZE_MAX_RADIUS + 1][6];     // [0][i]: F_i, [1][i]: G_i
+    __shared__ float corr[6];
+    const int j = (int)threadIdx.x;
+    const unsigned f = (unsigned)f0 + blockIdx.x;
+    int rf = (int)min((unsigned)radius, f);
+    if (T >= 0) rf = (int)min((unsigned)rf, (unsigned)T - 1u - f);
+    if (j < 2 * rf) {
+        const unsigned s = f - (unsigned)rf + (unsigned)j;
+        double a[6], b[6];
+        stab_step(model, counts, (size_t)(s % (unsigned)cap), a, b);
+        for (int k = 0; k < 6; k++) {
+            step[0][j][k] = a[k];
+            step[1][j][k] = b[k];
+        }
+    }
+    __syncthreads();
+    if (j < 2) {   // lane 0 forward over A at rf + i - 1, lane 1 backward over B at rf - i
+        double c[6], a[6];
+        stab_identity(c);
+        for (int i = 1; i <= rf; i++) {
+            const int at = j == 0 ? rf + i - 1 : rf - i;
+            for (int k = 0; k < 6; k++) a[k] = step[j][at][k];
+            stab_compose(a, c);
+            for (int k = 0; k < 6; k++) chain[j][i][k] = c[k];
+        }
+    }
+    __syncthreads();
+    if (j < 6) {
+        const double w0 = wt.w[0];
+        double acc = w0 * ((j == 0 || j == 4) ? 1.0 : 0.0);
+        double ws = w0;
+        for (int i = 1; i <= rf; i++) {
+            const double w = wt.w[i];
+            acc = acc + w * chain[0][i][j];
+            ws = ws + w;
+            acc = acc + w * chain[1][i][j];
+            ws = ws + w;
+        }
+        corr[j] = __double2float_rn(acc / ws);
+    }
+    __syncthreads();
+    if (j == 0) {
+        double cd[6], m[6];
+        bool ok = true;
+        for (int k = 0; k < 6; k++) {
+            ok = ok && __builtin_isfinite(corr[k]);
+            cd[k] = (double)corr[k];
+        }
+        ok = stab_invert(cd, m) && ok;
+        if (!ok) {
+            stab_identity(cd);
+            stab_identity(m);
+        }
+        for (int k = 0; k < 6; k++) {
+            correction[6 * (size_t)blockIdx.x + k] = (float)cd[k];
+            map[6 * (size_t)blockIdx.x + k] = m[k];
+        }
     }
 }
 

@@ -131,6 +131,19 @@ SIGNATURES = {
     "oflk_warp_affine_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [_f64p, _vp, _vp]),
     "oflk_stabilize_sequence": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int, _f32p, _f32p, _f32p, _i32p, _vp]),
     "oflk_stabilize_sequence_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int, _vp, _f32p, _f32p, _i32p, _vp]),
+    "oflk_stabilize_trajectory_ring": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 4 + [_f64p, ctypes.c_int, _vp, _vp, _vp]),
+    "oflk_stabilizer_create": (ctypes.c_int, [ctypes.POINTER(_vp)] + [ctypes.c_int] * 7 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int]),
+    "oflk_stabilizer_destroy": (ctypes.c_int, [_vp]),
+    "oflk_stabilizer_reset": (ctypes.c_int, [_vp, _vp]),
+    "oflk_stabilizer_workspace_bytes": (ctypes.c_size_t, [_vp]),
+    "oflk_stabilizer_lag": (ctypes.c_int, [_vp]),
+    "oflk_stabilizer_frame_index": (ctypes.c_int, [_vp]),
+    "oflk_stabilizer_push_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32p, _vp]),
+    "oflk_stabilizer_push": (ctypes.c_int, [_vp, _vp, _vp, _vp, _f32p, _i32p]),
+    "oflk_stabilizer_flush_device": (ctypes.c_int, [_vp, _vp, _vp, _i32p, _i32p, _vp]),
+    "oflk_stabilizer_flush": (ctypes.c_int, [_vp, _vp, _vp, _f32p, _i32p, _i32p]),
+    "oflk_stabilizer_correction_device": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
+    "oflk_stabilizer_tracker": (_vp, [_vp]),
     "oflk_shard_range": (None, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, _i32p]),
     "oflk_single_scale_fp16": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, _f32p, _f32p]),
     "oflk_rtl_stream_length": (ctypes.c_long, [ctypes.c_int, ctypes.c_int]),
@@ -660,6 +673,16 @@ def stabilize_trajectory(d_model: int, d_counts: int, T: int, weights: np.ndarra
                                           d_map or None, d_held or None, stream))
 
 
+def stabilize_trajectory_ring(d_model_ring: int, d_counts_ring: int, cap: int, f0: int, n: int, T: int, weights: np.ndarray,
+                              d_correction: int, d_map: int, stream: int = 0) -> None:
+    """oflk_stabilize_trajectory_ring on device pointers: step s at slot s % cap of d_model_ring [cap][6] float32 and
+    d_counts_ring [cap][3] int32 (or 0); frames f0 .. f0 + n - 1 of a stream of T frames (T = -1: open, n = 1) ->
+    d_correction [n][6] float32, d_map [n][6] float64; asynchronous."""
+    w = np.ascontiguousarray(weights, np.float64)
+    check(lib().oflk_stabilize_trajectory_ring(d_model_ring or None, d_counts_ring or None, int(cap), int(f0), int(n), int(T), _f64(w),
+                                               int(w.size) - 1, d_correction or None, d_map or None, stream))
+
+
 def warp_affine(d_frames: int, F: int, H: int, W: int, d_map: int, d_out: int, d_inside: int = 0, u8: bool = False,
                 stream: int = 0) -> None:
     """oflk_warp_affine on device pointers: frames and d_out [F][H][W] (float32, or uint8 with u8), d_map [F][6] float64,
@@ -705,10 +728,19 @@ class Tracker:
                                         int(window_size), int(iters), float(alpha), float(beta), float(max_residual),
                                         float(quality_level), float(min_distance), int(max_corners), int(detect_every)))
 
+    _owned = True   # False: the handle belongs to a Stabilizer
+
+    @classmethod
+    def _borrowed(cls, handle, H: int, W: int, u8: bool, max_corners: int) -> "Tracker":
+        t = cls.__new__(cls)
+        t._h, t._owned = handle, False
+        t.H, t.W, t.u8, t.K = int(H), int(W), bool(u8), int(max_corners)
+        return t
+
     def close(self) -> None:
-        if self._h:
+        if self._h and self._owned:
             lib().oflk_tracker_destroy(self._h)
-            self._h = _vp()
+        self._h = _vp()
 
     def __del__(self):
         try:
@@ -783,3 +815,99 @@ class Tracker:
         m, inl, cnt = np.empty(6, np.float32), np.empty(self.K, np.uint8), np.empty(3, np.int32)
         check(lib().oflk_tracker_read_motion(self._h, ptr(m), inl.ctypes.data, cnt.ctypes.data_as(_i32p), stream))
         return m, inl, cnt
+
+
+class Stabilizer:
+    """Online fixed-lag stabiliser (oflk_stabilizer_*): a Tracker with its motion row on, a delay line of radius + 1 frames
+    and a ring of step models on `device`; the push of frame t emits frame t - radius, flush() the rest.  Pointers are raw
+    device addresses, stream a hipStream_t handle.  The arguments are the C ABI's and are checked there; creation makes no
+    device call.  `tracker` is the inner Tracker (owned by the stabiliser): its rows and motion, add_points."""
+
+    def __init__(self, device: int, H: int, W: int, u8: bool, max_corners: int, detect_every: int, model: int, weights: np.ndarray,
+                 hypotheses: int = 256, threshold: float = 1.0, seed: int = 0, levels: int = 3, window_size: int = 5, iters: int = 3,
+                 alpha: float = 0.01, beta: float = 0.5, max_residual: float = 4.0, quality_level: float = 0.01,
+                 min_distance: float = 10.0):
+        self._h = _vp()
+        self.H, self.W, self.u8, self.K = int(H), int(W), bool(u8), int(max_corners)
+        w = np.ascontiguousarray(weights, np.float64)
+        self.radius = int(w.size) - 1
+        check(lib().oflk_stabilizer_create(ctypes.byref(self._h), int(device), int(H), int(W), int(bool(u8)), int(levels),
+                                           int(window_size), int(iters), float(alpha), float(beta), float(max_residual),
+                                           float(quality_level), float(min_distance), int(max_corners), int(detect_every), int(model),
+                                           int(hypotheses), float(threshold), int(seed), _f64(w), self.radius))
+        self.tracker = Tracker._borrowed(_vp(lib().oflk_stabilizer_tracker(self._h)), H, W, u8, max_corners)
+
+    def close(self) -> None:
+        if self._h:
+            self.tracker.close()
+            lib().oflk_stabilizer_destroy(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def workspace_bytes(self) -> int:
+        return int(lib().oflk_stabilizer_workspace_bytes(self._h))
+
+    @property
+    def lag(self) -> int:
+        return int(lib().oflk_stabilizer_lag(self._h))
+
+    @property
+    def frame_index(self) -> int:
+        return int(lib().oflk_stabilizer_frame_index(self._h))
+
+    def reset(self, stream: int = 0) -> None:
+        check(lib().oflk_stabilizer_reset(self._h, stream))
+
+    def push_device(self, d_frame: int, d_out: int, d_inside: int = 0, stream: int = 0) -> int:
+        """the index of the frame written to d_out (and d_inside), or -1 when nothing was"""
+        e = ctypes.c_int(-1)
+        check(lib().oflk_stabilizer_push_device(self._h, d_frame or None, d_out or None, d_inside or None, ctypes.byref(e), stream))
+        return int(e.value)
+
+    def flush_device(self, d_out: int, d_inside: int = 0, stream: int = 0) -> Tuple[int, int]:
+        """(first, count) of the frames written to d_out [radius][H][W] (and d_inside)"""
+        first, count = ctypes.c_int(0), ctypes.c_int(0)
+        check(lib().oflk_stabilizer_flush_device(self._h, d_out or None, d_inside or None, ctypes.byref(first), ctypes.byref(count),
+                                                 stream))
+        return int(first.value), int(count.value)
+
+    def correction_device(self) -> Tuple[int, int]:
+        """device addresses of correction [rows][6] float32 and map [rows][6] float64 of the last emission"""
+        c, m = _vp(), _vp()
+        check(lib().oflk_stabilizer_correction_device(self._h, ctypes.byref(c), ctypes.byref(m)))
+        return int(c.value), int(m.value)
+
+    def _dtype(self):
+        return np.uint8 if self.u8 else np.float32
+
+    def push(self, frame: np.ndarray, inside: bool = False):
+        """a contiguous host frame (H, W) of the stabiliser's element type in; (emitted index or -1, frame (H, W) or None,
+        correction (6,) float32 or None, inside (H, W) uint8 or None) out"""
+        if not (isinstance(frame, np.ndarray) and frame.dtype == self._dtype() and frame.shape == (self.H, self.W)
+                and frame.flags["C_CONTIGUOUS"]):
+            raise ValueError(f"expected a contiguous {np.dtype(self._dtype()).name} frame of shape {(self.H, self.W)}")
+        out, corr = np.empty((self.H, self.W), self._dtype()), np.empty(6, np.float32)
+        ins = np.empty((self.H, self.W), np.uint8) if inside else None
+        e = ctypes.c_int(-1)
+        check(lib().oflk_stabilizer_push(self._h, frame.ctypes.data, out.ctypes.data, None if ins is None else ins.ctypes.data,
+                                         ptr(corr), ctypes.byref(e)))
+        if e.value < 0:
+            return -1, None, None, None
+        return int(e.value), out, corr, ins
+
+    def flush(self, inside: bool = False):
+        """(first, frames (count, H, W), correction (count, 6) float32, inside (count, H, W) uint8 or None)"""
+        n = max(self.radius, 1)
+        out, corr = np.empty((n, self.H, self.W), self._dtype()), np.empty((n, 6), np.float32)
+        ins = np.empty((n, self.H, self.W), np.uint8) if inside else None
+        first, count = ctypes.c_int(0), ctypes.c_int(0)
+        check(lib().oflk_stabilizer_flush(self._h, out.ctypes.data, None if ins is None else ins.ctypes.data, ptr(corr),
+                                          ctypes.byref(first), ctypes.byref(count)))
+        c = int(count.value)
+        return int(first.value), out[:c], corr[:c], None if ins is None else ins[:c]

@@ -24,7 +24,7 @@ import argparse
 import ctypes
 import os
 from pathlib import Path
-from typing import List, NamedTuple, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import numpy.typing as npt
@@ -599,6 +599,121 @@ class SparseKltTracker:
 
     def close(self) -> None:
         self._t.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class StabilizedFrame(NamedTuple):
+    """One steadied frame of an OnlineStabilizer."""
+    index: int                     # the frame's index in the stream
+    frame: np.ndarray              # (H, W), the input's type; zero where the source lies outside the frame
+    correction: np.ndarray         # (2, 3) float32: where the frame's content was moved to
+    inside: Optional[np.ndarray]   # (H, W) bool: the source lay inside the frame; None unless asked for
+
+
+class OnlineStabilizer:
+    """lucas_kanade_pyramidal_sequence_stabilize for video that arrives frame by frame: a SparseKltTracker with its motion on,
+    a delay line of radius + 1 frames and the last 2 radius step models stay on the device.  The window of frame f reaches
+    radius frames ahead, so push(frame t) returns frame t - radius (None while t < radius) and flush() returns the last
+    radius frames once the stream has ended.  The frames and corrections of T pushes and a flush are those of the sequence
+    call on the same T frames, byte for byte.  After flush() the stabiliser takes no frame until reset().  The black border
+    is not cropped (inside=True returns the mask).
+
+        with OnlineStabilizer(frame.shape, 1000, radius=15) as stab:
+            for frame in video:                     # uint8 (H, W)
+                s = stab.push(frame)
+                if s is not None:
+                    show(s.index, s.frame)
+            for s in stab.flush():
+                show(s.index, s.frame)
+    """
+
+    def __init__(self, shape, max_corners: int, detect_every: int = 4, model="similarity", radius: int = 15, sigma=None,
+                 hypotheses: int = 256, threshold: float = 1.0, seed: int = 0, quality_level: float = 0.01,
+                 min_distance: float = 10.0, num_levels: int = 3, window_size: int = 5, num_iterations: int = 3, alpha: float = 0.01,
+                 beta: float = 0.5, max_residual: float = 4.0, dtype=np.uint8, device: int = 0, inside: bool = False):
+        if len(shape) != 2 or int(shape[0]) < 2 or int(shape[1]) < 2:
+            raise ValueError(f"shape must be (H, W) with H, W >= 2, got {shape!r}")
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.uint8), np.dtype(np.float32)):
+            raise ValueError(f"dtype must be uint8 or float32, got {dtype!r}")
+        a, b = _oflk.check_fb_params(alpha, beta)
+        H, W = int(shape[0]), int(shape[1])
+        L, win, it, r = _oflk.check_sparse_params((H, W), num_levels, window_size, num_iterations, max_residual)
+        K, q, md, win = _oflk.check_feature_params(max_corners, quality_level, min_distance, win)
+        if isinstance(detect_every, bool) or int(detect_every) != detect_every or int(detect_every) < 0:
+            raise ValueError(f"detect_every must be an integer >= 0, got {detect_every!r}")
+        code, hn, thr, sd = _oflk.check_motion_params(model, hypotheses, threshold, seed)
+        w = _oflk.stabilize_weights(radius, sigma)
+        self.shape, self.max_corners, self.detect_every = (H, W), K, min(int(detect_every), 2 ** 31 - 1)
+        self.radius, self.inside = int(w.size) - 1, bool(inside)
+        self._s = _oflk.Stabilizer(device, H, W, self.dtype == np.uint8, K, self.detect_every, code, w, hn, thr, sd, L, win, it, a, b, r,
+                                   q, md)
+
+    def _frame(self, index, frame, corr, ins) -> StabilizedFrame:
+        return StabilizedFrame(int(index), frame, corr.reshape(2, 3), None if ins is None else ins.astype(bool))
+
+    def push(self, frame) -> Optional[StabilizedFrame]:
+        """the next frame (H, W) in; frame t - radius steadied, or None while t < radius (synchronous)"""
+        f = np.ascontiguousarray(frame, self.dtype)
+        if f.shape != self.shape:
+            raise ValueError(f"expected a frame of shape {self.shape}, got {f.shape}")
+        e, out, corr, ins = self._s.push(f, self.inside)
+        return None if e < 0 else self._frame(e, out, corr, ins)
+
+    def flush(self) -> List[StabilizedFrame]:
+        """the stream has ended: the min(radius, T) frames not yet returned, ascending (synchronous)"""
+        first, out, corr, ins = self._s.flush(self.inside)
+        return [self._frame(first + i, out[i], corr[i], None if ins is None else ins[i]) for i in range(len(out))]
+
+    def push_device(self, ptr: int, out_ptr: int, inside_ptr: int = 0, stream: int = 0) -> int:
+        """the next frame at a device address, asynchronous on `stream`: returns the index of the frame written to out_ptr
+        [H][W] (and inside_ptr [H][W] uint8), or -1 when nothing was written"""
+        return self._s.push_device(ptr, out_ptr, inside_ptr, stream)
+
+    def flush_device(self, out_ptr: int, inside_ptr: int = 0, stream: int = 0) -> Tuple[int, int]:
+        """the stream has ended: (first, count) of the frames written to out_ptr [radius][H][W] (and inside_ptr)"""
+        return self._s.flush_device(out_ptr, inside_ptr, stream)
+
+    def correction_device(self) -> Tuple[int, int]:
+        """device addresses (correction [rows][6] float32, map [rows][6] float64) of the last emission, valid until the next
+        push, flush or reset"""
+        return self._s.correction_device()
+
+    def row(self, stream: int = 0) -> TrackerRow:
+        """the tracker's row of the last pushed frame (not of the returned one; synchronises `stream`)"""
+        return SparseKltTracker._row(self._s.tracker.read_row(stream))
+
+    def motion(self, stream: int = 0) -> Motion:
+        """the fitted motion of the step into the last pushed frame; status 0 after frame 0 (synchronises `stream`)"""
+        m, inl, cnt = self._s.tracker.read_motion(stream)
+        return Motion(m.reshape(2, 3), inl.astype(bool), int(cnt[0]), int(cnt[1]), int(cnt[2]))
+
+    def add_points(self, pts, stream: int = 0) -> None:
+        """SparseKltTracker.add_points on the last pushed frame"""
+        self._s.tracker.add_points(pts, stream)
+
+    @property
+    def lag(self) -> int:
+        """frames between a push and the frame it returns: the radius"""
+        return self._s.lag
+
+    @property
+    def frame_index(self) -> int:
+        """index of the last pushed frame, -1 before the first"""
+        return self._s.frame_index
+
+    def reset(self) -> None:
+        """forget the stream: the next push is frame 0"""
+        self._s.reset()
+
+    def close(self) -> None:
+        self._s.close()
 
     def __enter__(self):
         return self

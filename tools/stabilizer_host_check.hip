@@ -1,0 +1,103 @@
+// Host-side check of the online stabiliser for a sanitizer build (make -C optical-flow-fpga_amd/csrc stabilizer-host-check):
+// create, every refusal that needs no device, the getters, a flush with nothing to emit, the refused push after it, reset
+// and destroy, and the refusals of oflk_stabilize_trajectory_ring.  It includes the library's translation unit and runs on
+// a machine without a GPU.  Exit status 0: every expectation held (and the sanitizers found nothing).
+#include "../optical-flow-fpga_amd/csrc/oflk.hip"
+
+#include <cstdio>
+#include <limits>
+
+static int g_failed = 0;
+#define EXPECT(cond)                                                        \
+    do {                                                                    \
+        if (!(cond)) {                                                      \
+            std::printf("%s:%d: %s\n", __FILE__, __LINE__, #cond);          \
+            g_failed++;                                                     \
+        }                                                                   \
+    } while (0)
+
+static double g_w[OFLK_STABILIZE_MAX_RADIUS + 1];
+
+static int create(oflk_stabilizer **st, int H, int W, int u8, int win, int K, int D, int model, int hyps, float thr, const double *w,
+                  int radius)
+{
+    return oflk_stabilizer_create(st, 0, H, W, u8, 3, win, 3, 0.01f, 0.5f, 4.0f, 0.01f, 3.0f, K, D, model, hyps, thr, 7u, w, radius);
+}
+
+int main()
+{
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    for (double &v : g_w) v = 1.0;
+    double bad[4] = {1.0, 1.0, 0.0, 1.0};
+    oflk_stabilizer *st = nullptr;
+    // refusals of creation
+    EXPECT(create(nullptr, 24, 32, 1, 5, 8, 2, 1, 16, 1.0f, g_w, 3) == OFLK_ERR_INVALID);
+    EXPECT(create(&st, 1, 32, 1, 5, 8, 2, 1, 16, 1.0f, g_w, 3) == OFLK_ERR_INVALID && !st);
+    EXPECT(create(&st, 24, 1, 0, 5, 8, 2, 1, 16, 1.0f, g_w, 3) == OFLK_ERR_INVALID && !st);
+    EXPECT(create(&st, 24, 32, 1, 4, 8, 2, 1, 16, 1.0f, g_w, 3) == OFLK_ERR_UNSUPPORTED && !st);
+    EXPECT(create(&st, 7, 9, 1, 5, 8, 2, 1, 16, 1.0f, g_w, 3) == OFLK_ERR_UNSUPPORTED && !st);
+    EXPECT(create(&st, 24, 32, 1, 5, 0, 2, 1, 16, 1.0f, g_w, 3) == OFLK_ERR_INVALID && !st);
+    EXPECT(create(&st, 24, 32, 1, 5, 8, -1, 1, 16, 1.0f, g_w, 3) == OFLK_ERR_INVALID && !st);
+    EXPECT(create(&st, 24, 32, 1, 5, 8, 2, -1, 16, 1.0f, g_w, 3) == OFLK_ERR_INVALID && !st);
+    EXPECT(create(&st, 24, 32, 1, 5, 8, 2, 3, 16, 1.0f, g_w, 3) == OFLK_ERR_INVALID && !st);
+    EXPECT(create(&st, 24, 32, 1, 5, 8, 2, 1, 0, 1.0f, g_w, 3) == OFLK_ERR_INVALID && !st);
+    EXPECT(create(&st, 24, 32, 1, 5, 8, 2, 1, 16, nan, g_w, 3) == OFLK_ERR_INVALID && !st);
+    EXPECT(create(&st, 24, 32, 1, 5, 8, 2, 1, 16, 1.0f, nullptr, 3) == OFLK_ERR_INVALID && !st);
+    EXPECT(create(&st, 24, 32, 1, 5, 8, 2, 1, 16, 1.0f, bad, 3) == OFLK_ERR_INVALID && !st);
+    EXPECT(create(&st, 24, 32, 1, 5, 8, 2, 1, 16, 1.0f, g_w, -1) == OFLK_ERR_INVALID && !st);
+    EXPECT(create(&st, 24, 32, 1, 5, 8, 2, 1, 16, 1.0f, g_w, OFLK_STABILIZE_MAX_RADIUS + 1) == OFLK_ERR_INVALID && !st);
+    // a stabiliser, and what it answers and refuses before the first push
+    alignas(4) unsigned char frame[8] = {0}, out[8] = {0};
+    for (int u8 = 0; u8 < 2; u8++)
+        for (int r : {0, 1, 3, OFLK_STABILIZE_MAX_RADIUS}) {
+            EXPECT(create(&st, 24, 32, u8, 5, 5, r & 1, OFLK_MOTION_AFFINE, 16, 1.0f, g_w, r) == OFLK_OK && st);
+            if (!st) continue;
+            EXPECT(oflk_stabilizer_lag(st) == r && oflk_stabilizer_frame_index(st) == -1 && oflk_stabilizer_workspace_bytes(st) == 0);
+            oflk_tracker *tr = oflk_stabilizer_tracker(st);
+            EXPECT(tr && oflk_tracker_frame_index(tr) == -1);
+            const float *c = nullptr;
+            const double *m = nullptr;
+            EXPECT(oflk_stabilizer_correction_device(st, &c, &m) == OFLK_ERR_INVALID && !c && !m);
+            int e = 5, first = 5, count = 5;
+            EXPECT(oflk_stabilizer_push_device(st, nullptr, out, nullptr, &e, nullptr) == OFLK_ERR_INVALID && e == -1);
+            EXPECT(oflk_stabilizer_push_device(st, frame, nullptr, nullptr, &e, nullptr) == OFLK_ERR_INVALID);
+            EXPECT(oflk_stabilizer_push_device(st, frame, out, nullptr, nullptr, nullptr) == OFLK_ERR_INVALID);
+            EXPECT(oflk_stabilizer_push(st, nullptr, out, nullptr, nullptr, &e) == OFLK_ERR_INVALID);
+            if (!u8) EXPECT(oflk_stabilizer_push_device(st, frame + 1, out, nullptr, &e, nullptr) == OFLK_ERR_INVALID);
+            EXPECT(oflk_stabilizer_flush_device(st, nullptr, nullptr, nullptr, &count, nullptr) == OFLK_ERR_INVALID && count == 0);
+            EXPECT(oflk_stabilizer_flush_device(st, nullptr, nullptr, &first, &count, nullptr) == OFLK_OK && first == 0 && count == 0);
+            e = 5;
+            EXPECT(oflk_stabilizer_push_device(st, frame, out, nullptr, &e, nullptr) == OFLK_ERR_INVALID && e == -1);   // flushed
+            EXPECT(oflk_stabilizer_push(st, frame, out, nullptr, nullptr, &e) == OFLK_ERR_INVALID);
+            EXPECT(oflk_stabilizer_flush(st, nullptr, nullptr, nullptr, &first, &count) == OFLK_OK && count == 0);
+            EXPECT(oflk_stabilizer_reset(st, nullptr) == OFLK_OK && oflk_stabilizer_frame_index(st) == -1);
+            EXPECT(oflk_stabilizer_destroy(st) == OFLK_OK);
+            st = nullptr;
+        }
+    EXPECT(oflk_stabilizer_destroy(nullptr) == OFLK_OK && oflk_stabilizer_reset(nullptr, nullptr) == OFLK_ERR_INVALID);
+    EXPECT(oflk_stabilizer_lag(nullptr) == -1 && oflk_stabilizer_frame_index(nullptr) == -1 && !oflk_stabilizer_tracker(nullptr));
+    // the ring form
+    alignas(8) static float ring[6 * 8];
+    alignas(8) static double map[6 * 4];
+    float *corr = ring;   // never written: every call below is refused
+    auto traj_at = [&](int cap, int f0, int n, int T, const double *w, int radius, double *mp) {
+        return oflk_stabilize_trajectory_ring(ring, nullptr, cap, f0, n, T, w, radius, corr, mp, nullptr);
+    };
+    auto traj = [&](int cap, int f0, int n, int T, const double *w, int radius) { return traj_at(cap, f0, n, T, w, radius, map); };
+    EXPECT(traj(5, 10, 1, -1, g_w, 3) == OFLK_ERR_INVALID);
+    EXPECT(traj(0, 10, 1, -1, g_w, 0) == OFLK_ERR_INVALID);
+    EXPECT(traj(6, -1, 1, -1, g_w, 3) == OFLK_ERR_INVALID);
+    EXPECT(traj(6, 10, 0, -1, g_w, 3) == OFLK_ERR_INVALID);
+    EXPECT(traj(6, 10, 2, -1, g_w, 3) == OFLK_ERR_INVALID);
+    EXPECT(traj(6, 10, 129, 1000, g_w, 3) == OFLK_ERR_INVALID);
+    EXPECT(traj(6, 10, 3, 12, g_w, 3) == OFLK_ERR_INVALID);
+    EXPECT(traj(6, INT_MAX, 2, INT_MAX, g_w, 3) == OFLK_ERR_INVALID);
+    EXPECT(traj(6, 10, 1, -2, g_w, 3) == OFLK_ERR_INVALID);
+    EXPECT(traj(6, 10, 1, -1, bad, 3) == OFLK_ERR_INVALID);
+    EXPECT(traj(6, 10, 1, -1, nullptr, 3) == OFLK_ERR_INVALID);
+    EXPECT(traj(6, 10, 1, -1, g_w, 65) == OFLK_ERR_INVALID);
+    EXPECT(traj_at(6, 10, 1, -1, g_w, 3, reinterpret_cast<double *>(reinterpret_cast<char *>(map) + 4)) == OFLK_ERR_INVALID);
+    EXPECT(oflk_stabilize_trajectory_ring(nullptr, nullptr, 6, 10, 1, -1, g_w, 3, corr, map, nullptr) == OFLK_ERR_INVALID);
+    std::printf(g_failed ? "stabiliser host check: %d expectation(s) failed\n" : "stabiliser host check: ok\n", g_failed);
+    return g_failed ? 1 : 0;
+}

@@ -504,7 +504,7 @@ int oflk_tracker_add_points(oflk_tracker *tr, const float *pts, int n, void *str
  *                  zero determinant / spread or a result not finite in float32: the best hypothesis's model is kept
  *   outputs        model [6];  inlier [N]: the score's test with the returned model on the valid correspondences, 0
  *                  elsewhere;  counts [3] = (n_inliers = the mask's sum, n_valid = M, status = 1)
- * Homographies and iterative re-estimation are not offered.
+ * These calls fit six coefficients: homographies have their own calls below, and iterative re-estimation is not offered.
  * Three kernel launches on `stream` (compaction, scoring with one wave per hypothesis, select-and-refit), no memset, no
  * atomics, nothing synchronised: the chain can be captured into a graph after one eager call.
  * Refusals, before any device call: an unknown model, hypotheses < 1 or > OFLK_MOTION_MAX_HYPOTHESES, a threshold that is
@@ -547,6 +547,65 @@ int oflk_tracker_motion_device(const oflk_tracker *tr, const float **d_model, co
 /* copy it to host arrays (each may be NULL); synchronises `stream` */
 int oflk_tracker_read_motion(oflk_tracker *tr, float *model, unsigned char *inlier, int *counts, void *stream);
 
+/* ---- homography from point correspondences: a four-point RANSAC and a normalised linear refit ------------------------- */
+/* The statement (tests/homography_model.py), per step with hash index i: correspondences src[n] -> dst[n], a validity mask,
+ * Hn hypotheses, a threshold (px) and a seed.  A model is nine float32, row-major [h00 h01 h02; h10 h11 h12; h20 h21 h22]
+ * with h22 == 1.0f exactly: dst = (h00 x + h01 y + h02, h10 x + h11 y + h12) / (h20 x + h21 y + h22).
+ *   compaction     as the motion fit's.  M < 4: the failure result -- nine NaNs, mask all 0, counts (0, M, 0)
+ *   sampling       the motion fit's draw and rule with m = 4 picks: pick j is r = draw % (M - j), bumped once for each
+ *                  earlier pick, taken in ascending order, that is <= it
+ *   minimal solve  float64 on the points converted to double, each operation rounded on its own.  Q(x0, y0 .. x3, y3), the
+ *                  map of the unit square onto a quadrilateral in pick order:  sx = (x0 - x1) + (x2 - x3), sy likewise;
+ *                  dx1 = x1 - x2, dx2 = x3 - x2, dy1, dy2 likewise;  den = dx1 dy2 - dy1 dx2;  g = (sx dy2 - sy dx2) / den;
+ *                  h = (dx1 sy - dy1 sx) / den;  Q = [(x1 - x0) + g x1, (x3 - x0) + h x3, x0;  (y1 - y0) + g y1,
+ *                  (y3 - y0) + h y3, y0;  g, h, 1].  S = Q of the source points, D = Q of the destination points,
+ *                  Hm = D adj(S) with adj(S), for S = [a b c; d e f; g h i], = [e i - f h, c h - b i, b f - c e;
+ *                  f g - d i, a i - c g, c d - a f;  d h - e g, b g - a h, a e - b d] and the product's entries
+ *                  (r0 c0 + r1 c1) + r2 c2;  the nine entries divided by Hm[2][2] and rounded to float32.  den == 0 on either
+ *                  side, Hm[2][2] == 0 or a coefficient that is not finite: degenerate, score -1
+ *   score          float32, one operation at a time:  w = (h20 x + h21 y) + h22;  ex = ((h00 x + h01 y) + h02) / w - qx, ey
+ *                  likewise (IEEE division);  r2 = ex ex + ey ey;  inlier: w > 0 and r2 <= threshold * threshold.  Best =
+ *                  largest count, ties to the lowest h; every hypothesis degenerate: the failure result
+ *   refit          over the best hypothesis's inliers, float64, every sum in the motion fit's stated order.  (a) the count n
+ *                  and the four coordinate sums give the centroids cpx, cpy, cqx, cqy.  (b) lp = sum(|X - cpx| + |Y - cpy|),
+ *                  lq likewise;  sp = n / lp, sq = n / lq (no square root).  (c) x = (X - cpx) sp, y = (Y - cpy) sp,
+ *                  u = (U - cqx) sq, v = (V - cqy) sq.  (d) the normal equations G h = b of the rows
+ *                  [x y 1 0 0 0 -xu -yu | u] and [0 0 0 x y 1 -xv -yv | v]: with xx = x x, xy = x y, yy = y y,
+ *                  r = u u + v v, the 22 sums of xx, xy, yy, x, y;  xx u, xy u, yy u, x u, y u;  the same five with v;
+ *                  xx r, xy r, yy r;  u, v, x r, y r (a three-factor term is the two-factor product times the third), n
+ *                  in G[2][2] and G[5][5].  (e) elimination without pivoting on [G | b]: for k = 0 .. 7, for i = k+1 .. 7,
+ *                  f = G[i][k] / G[k][k], G[i][j] -= f G[k][j] for j = k+1 .. 8 ascending;  then for i = 7 .. 0,
+ *                  h[i] = (b[i] - G[i][j] h[j], j = i+1 .. 7 ascending, one by one) / G[i][i].  (f) with Hn = [h0 .. h7, 1],
+ *                  tx = sp cpx, ty = sp cpy:  A[r][0] = Hn[r][0] sp, A[r][1] = Hn[r][1] sp,
+ *                  A[r][2] = Hn[r][2] - (Hn[r][0] tx + Hn[r][1] ty);  B[0][c] = A[0][c] / sq + cqx A[2][c],
+ *                  B[1][c] = A[1][c] / sq + cqy A[2][c], B[2][c] = A[2][c];  the nine entries divided by B[2][2] and rounded
+ *                  to float32.  No inlier, lp or lq zero, a pivot zero or not finite, B[2][2] zero or a result not finite
+ *                  in float32: the best hypothesis's model is kept
+ *   outputs        model [9];  inlier [N]: the score's test with the returned model on the valid correspondences, 0
+ *                  elsewhere;  counts [3] = (n_inliers, n_valid = M, status = 1)
+ * model[t] of oflk_tracks_homography maps row t to row t+1, so oflk_warp_perspective of frame t+1 under model[t] (converted
+ * to double) registers frame t+1 onto frame t.  The tracker's motion row and the stabiliser keep six coefficients.
+ * Three kernel launches on `stream` (the motion fit's compaction, scoring with one wave per hypothesis, select-and-refit), no
+ * memset, no atomics, nothing synchronised: the chain can be captured into a graph after one eager call.
+ * Refusals, before any device call: hypotheses < 1 or > OFLK_MOTION_MAX_HYPOTHESES, a threshold that is not finite and
+ * positive, S or N < 1 (T < 2, K < 1), NULL pointers (d_valid and d_born may be NULL), d_src / d_dst / d_tracks not 8-byte
+ * aligned, a workspace that is too small or not 256-byte aligned: OFLK_ERR_INVALID. */
+/* bytes of the caller's workspace for S steps of N correspondences */
+int oflk_homography_workspace(int S, int N, int hypotheses, size_t *bytes);
+/* device form, as oflk_estimate_motion's: d_model [S][9], d_inlier [S][N], d_counts [S][3].  Asynchronous on `stream`. */
+int oflk_estimate_homography(const float *d_src, const float *d_dst, const unsigned char *d_valid, int S, int N, int step0,
+                             int hypotheses, float threshold, unsigned seed, void *d_workspace, size_t workspace_bytes,
+                             float *d_model, unsigned char *d_inlier, int *d_counts, void *stream);
+/* device form on rows, with oflk_tracks_motion's validity rule: the workspace is that of S = T-1, N = K; d_model [T-1][9],
+ * d_inlier [T-1][K], d_counts [T-1][3] */
+int oflk_tracks_homography(const float *d_tracks, const unsigned char *d_visible, const unsigned char *d_born, int T, int K, int t0,
+                           int hypotheses, float threshold, unsigned seed, void *d_workspace, size_t workspace_bytes,
+                           float *d_model, unsigned char *d_inlier, int *d_counts, void *stream);
+/* host arrays in and out (valid may be NULL); synchronous */
+int oflk_estimate_homography_host(const float *src, const float *dst, const unsigned char *valid, int S, int N, int step0,
+                                  int hypotheses, float threshold, unsigned seed, float *model_out, unsigned char *inlier,
+                                  int *counts);
+
 /* ---- video stabilisation: a smoothed trajectory of the step models and an affine warp of whole frames ------------------ */
 /* The statement (tests/stabilize_model.py).  Every operation is float64 unless stated and rounded on its own, in the order
  * written; nothing is contracted and the device computes no transcendental.
@@ -578,8 +637,12 @@ int oflk_tracker_read_motion(oflk_tracker *tr, float *model, unsigned char *inli
  * map_coordinates, order 1, cval 0, float32 result).  inside[f][y][x] = 1 where 0 <= xs <= W-1 and 0 <= ys <= H-1 (float64,
  * closed; the taps were read), else 0, and there the sample is 0.  float32 frames give float32; uint8 frames give
  * (unsigned char) rintf(sample), half to even (a sample of bytes lies in [0, 255]).  Frames are finite, H, W >= 2, and out
- * does not overlap the frames.  Cropping or zooming the border away (inside is what a caller needs for it), rolling-shutter
- * correction and homographies are not offered.
+ * does not overlap the frames.  Cropping or zooming the border away (inside is what a caller needs for it) and
+ * rolling-shutter correction are not offered; the trajectory and the sequence calls smooth six coefficients, not homographies.
+ * Perspective warp (tests/homography_model.py): m = map[f] has nine coefficients;  w = (m6 f64(x) + m7 f64(y)) + m8;
+ * xs = ((m0 x + m1 y) + m2) / w, ys = ((m3 x + m4 y) + m5) / w -- two IEEE float64 divisions, not one reciprocal;
+ * inside = w > 0 and 0 <= xs <= W-1 and 0 <= ys <= H-1, a NaN anywhere meaning outside;  everything else as above.  A map
+ * whose third row is (0, 0, 1) therefore gives oflk_warp_affine's bytes under its first two rows.
  * Refusals, before any device call: T < 1 (the sequence call: T < 2), F < 1, H or W < 2, a radius outside
  * [0, OFLK_STABILIZE_MAX_RADIUS], a weight that is not finite and positive, NULL pointers (d_counts, d_held, d_inside and
  * the sequence call's last four outputs may be NULL; d_model when T == 1), d_map not 8-byte aligned: OFLK_ERR_INVALID;
@@ -601,6 +664,12 @@ int oflk_stabilize_trajectory_host(const float *model, const int *counts, int T,
 int oflk_warp_affine_host(const float *frames, int F, int H, int W, const double *map, float *out, unsigned char *inside);
 int oflk_warp_affine_host_u8(const unsigned char *frames, int F, int H, int W, const double *map, unsigned char *out,
                              unsigned char *inside);
+/* the perspective warp, with oflk_warp_affine's forms, refusals and chunks: d_map / map [F][9] float64 */
+int oflk_warp_perspective(const void *d_frames, int u8, int F, int H, int W, const double *d_map, void *d_out,
+                          unsigned char *d_inside, void *stream);
+int oflk_warp_perspective_host(const float *frames, int F, int H, int W, const double *map, float *out, unsigned char *inside);
+int oflk_warp_perspective_host_u8(const unsigned char *frames, int F, int H, int W, const double *map, unsigned char *out,
+                                  unsigned char *inside);
 /* Frames in, steadied frames out.  By statement, byte for byte: oflk_pyramidal_sequence_klt_sparse_replenish on the frames,
  * oflk_tracks_motion on its rows with t0 = 0, oflk_stabilize_trajectory on the models and counts, oflk_warp_affine of the
  * frames under its maps.  Pass 1 is the replenish call's chunk loop, from which only rows come down; then the fit and the

@@ -11,6 +11,7 @@
 #include "oflk_sparse.hpp"
 #include "oflk_tracker.hpp"
 #include "oflk_motion.hpp"
+#include "oflk_homography.hpp"
 #include "oflk_stabilize.hpp"
 
 #include <algorithm>
@@ -3534,7 +3535,7 @@ OFLK_API int oflk_plan_sparse_klt_replenish(oflk_plan *plan, const void *d_frame
 // =============================================================================
 namespace {
 // The workspace of the fit, 256-byte aligned pieces: M [S], the compacted correspondences [S][N], score [S][Hn] and the
-// hypotheses' models [S][Hn][6]
+// hypotheses' models [S][Hn][nc] -- nc = 6 coefficients, 9 for the homography fit
 struct MotionWs {
     int *M;
     float4 *pts;
@@ -3543,7 +3544,7 @@ struct MotionWs {
     size_t bytes;
 };
 
-MotionWs motion_ws(void *base, int S, int N, int Hn)
+MotionWs motion_ws(void *base, int S, int N, int Hn, int nc = 6)
 {
     MotionWs v{};
     auto take = [&](auto *&p, size_t n) {
@@ -3554,20 +3555,26 @@ MotionWs motion_ws(void *base, int S, int N, int Hn)
     take(v.M, nS);
     take(v.pts, nS * (size_t)N);
     take(v.score, nS * (size_t)Hn);
-    take(v.hmodel, nS * (size_t)Hn * 6);
+    take(v.hmodel, nS * (size_t)Hn * (size_t)nc);
     return v;
 }
 
-// what every form of the fit refuses about its parameters
-int check_motion(int model, int hypotheses, float threshold)
+// what every form of a fit refuses about its RANSAC parameters
+int check_ransac(int hypotheses, float threshold)
 {
-    if (model != OFLK_MOTION_TRANSLATION && model != OFLK_MOTION_SIMILARITY && model != OFLK_MOTION_AFFINE)
-        return fail(OFLK_ERR_INVALID, "unknown motion model %d", model);
     if (hypotheses < 1 || hypotheses > OFLK_MOTION_MAX_HYPOTHESES)
         return fail(OFLK_ERR_INVALID, "hypotheses must be in [1, %d] (got %d)", OFLK_MOTION_MAX_HYPOTHESES, hypotheses);
     if (!(std::isfinite(threshold) && threshold > 0.0f))
         return fail(OFLK_ERR_INVALID, "threshold must be finite and > 0 (got %g)", (double)threshold);
     return OFLK_OK;
+}
+
+// what every form of the motion fit refuses about its parameters
+int check_motion(int model, int hypotheses, float threshold)
+{
+    if (model != OFLK_MOTION_TRANSLATION && model != OFLK_MOTION_SIMILARITY && model != OFLK_MOTION_AFFINE)
+        return fail(OFLK_ERR_INVALID, "unknown motion model %d", model);
+    return check_ransac(hypotheses, threshold);
 }
 
 int check_motion_shape(int S, int N)
@@ -3576,11 +3583,13 @@ int check_motion_shape(int S, int N)
     return OFLK_OK;
 }
 
-int check_motion_workspace(const void *ws, size_t bytes, int S, int N, int Hn)
+int check_motion_workspace(const void *ws, size_t bytes, int S, int N, int Hn, int nc = 6)
 {
     if (!ws) return fail(OFLK_ERR_INVALID, "NULL workspace");
-    const size_t need = motion_ws(nullptr, S, N, Hn).bytes;
-    if (bytes < need) return fail(OFLK_ERR_INVALID, "workspace of %zu bytes, %zu needed (oflk_motion_workspace)", bytes, need);
+    const size_t need = motion_ws(nullptr, S, N, Hn, nc).bytes;
+    if (bytes < need)
+        return fail(OFLK_ERR_INVALID, "workspace of %zu bytes, %zu needed (%s)", bytes, need,
+                    nc == 6 ? "oflk_motion_workspace" : "oflk_homography_workspace");
     if (!aligned(ws, 256)) return fail(OFLK_ERR_INVALID, "d_workspace must be 256-byte aligned");
     return OFLK_OK;
 }
@@ -3592,8 +3601,8 @@ struct MotionIn {
     const unsigned char *va, *vb, *born;
 };
 
-int motion_launch(const MotionIn &in, int S, int N, unsigned index0, int model, int Hn, float threshold, unsigned seed,
-                  const MotionWs &ws, float *d_model, unsigned char *d_inlier, int *d_counts, hipStream_t s)
+MotionArgs motion_args(const MotionIn &in, int S, int N, unsigned index0, int Hn, float threshold, unsigned seed, const MotionWs &ws,
+                       float *d_model, unsigned char *d_inlier, int *d_counts)
 {
     MotionArgs a{};
     a.src = reinterpret_cast<const float2 *>(in.src);
@@ -3604,6 +3613,13 @@ int motion_launch(const MotionIn &in, int S, int N, unsigned index0, int model, 
     a.thr2 = threshold * threshold;
     a.M = ws.M; a.pts = ws.pts; a.score = ws.score; a.hmodel = ws.hmodel;
     a.model = d_model; a.inlier = d_inlier; a.counts = d_counts;
+    return a;
+}
+
+int motion_launch(const MotionIn &in, int S, int N, unsigned index0, int model, int Hn, float threshold, unsigned seed,
+                  const MotionWs &ws, float *d_model, unsigned char *d_inlier, int *d_counts, hipStream_t s)
+{
+    const MotionArgs a = motion_args(in, S, N, index0, Hn, threshold, seed, ws, d_model, d_inlier, d_counts);
     const unsigned steps = (unsigned)std::min(S, 65535);
     hipLaunchKernelGGL(k_motion_compact, dim3(steps), dim3(kMotionCompact), 0, s, a);
     HIP_TRY(hipGetLastError());
@@ -3613,6 +3629,21 @@ int motion_launch(const MotionIn &in, int S, int N, unsigned index0, int model, 
         hipLaunchKernelGGL(k_motion_refit<decltype(MODEL)::value>, dim3(steps), dim3(kMotionLanes), 0, s, a);
     });
     if (!built) return fail(OFLK_ERR_INVALID, "unknown motion model %d", model);
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+
+// The homography fit's three launches (oflk_homography.hpp): the motion fit's compaction, then nine coefficients per model
+// in ws (motion_ws with nc = 9) and in d_model [S][9]
+int homography_launch(const MotionIn &in, int S, int N, unsigned index0, int Hn, float threshold, unsigned seed, const MotionWs &ws,
+                      float *d_model, unsigned char *d_inlier, int *d_counts, hipStream_t s)
+{
+    const MotionArgs a = motion_args(in, S, N, index0, Hn, threshold, seed, ws, d_model, d_inlier, d_counts);
+    const unsigned steps = (unsigned)std::min(S, 65535);
+    hipLaunchKernelGGL(k_motion_compact, dim3(steps), dim3(kMotionCompact), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_homog_score, dim3((unsigned)((Hn + kMotionWaves - 1) / kMotionWaves), steps), dim3(64 * kMotionWaves), 0, s, a);
+    hipLaunchKernelGGL(k_homog_refit, dim3(steps), dim3(kMotionLanes), 0, s, a);
     HIP_TRY(hipGetLastError());
     return OFLK_OK;
 }
@@ -3656,12 +3687,14 @@ OFLK_API int oflk_tracks_motion(const float *d_tracks, const unsigned char *d_vi
                          d_model, d_inlier, d_counts, (hipStream_t)stream);
 }
 
-OFLK_API int oflk_estimate_motion_host(const float *src, const float *dst, const unsigned char *valid, int S, int N, int step0,
-                                       int model, int hypotheses, float threshold, unsigned seed, float *model_out,
-                                       unsigned char *inlier, int *counts)
+namespace {
+// the host form of both fits: model < 0 is the homography fit, nine coefficients per model
+int estimate_host(const float *src, const float *dst, const unsigned char *valid, int S, int N, int step0, int model, int hypotheses,
+                  float threshold, unsigned seed, float *model_out, unsigned char *inlier, int *counts)
 {
-    int rc = check_motion_shape(S, N);
-    if (rc || (rc = check_motion(model, hypotheses, threshold))) return rc;
+    const bool homography = model < 0;
+    const size_t nc = homography ? 9 : 6;
+    int rc;
     if (!src || !dst || !model_out || !inlier || !counts) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
     HostCall call;
     if ((rc = call.begin())) return rc;
@@ -3671,16 +3704,78 @@ OFLK_API int oflk_estimate_motion_host(const float *src, const float *dst, const
     char *d_ws;
     int *d_cnt;
     if ((rc = call.upload(&d_src, src, 2 * n)) || (rc = call.upload(&d_dst, dst, 2 * n)) ||
-        (valid && (rc = call.upload(&d_valid, valid, n))) || (rc = call.alloc(&d_ws, motion_ws(nullptr, S, N, hypotheses).bytes)) ||
-        (rc = call.alloc(&d_model, 6 * (size_t)S)) || (rc = call.alloc(&d_inl, n)) || (rc = call.alloc(&d_cnt, 3 * (size_t)S)))
+        (valid && (rc = call.upload(&d_valid, valid, n))) ||
+        (rc = call.alloc(&d_ws, motion_ws(nullptr, S, N, hypotheses, (int)nc).bytes)) || (rc = call.alloc(&d_model, nc * (size_t)S)) ||
+        (rc = call.alloc(&d_inl, n)) || (rc = call.alloc(&d_cnt, 3 * (size_t)S)))
         return rc;
-    if ((rc = motion_launch({d_src, d_dst, d_valid, nullptr, nullptr}, S, N, (unsigned)step0, model, hypotheses, threshold, seed,
-                            motion_ws(d_ws, S, N, hypotheses), d_model, d_inl, d_cnt, nullptr)))
+    const MotionIn in{d_src, d_dst, d_valid, nullptr, nullptr};
+    const MotionWs ws = motion_ws(d_ws, S, N, hypotheses, (int)nc);
+    if ((rc = homography ? homography_launch(in, S, N, (unsigned)step0, hypotheses, threshold, seed, ws, d_model, d_inl, d_cnt, nullptr)
+                         : motion_launch(in, S, N, (unsigned)step0, model, hypotheses, threshold, seed, ws, d_model, d_inl, d_cnt,
+                                         nullptr)))
         return rc;
-    if ((rc = call.to_host(model_out, d_model, 6 * (size_t)S)) || (rc = call.to_host(inlier, d_inl, n)) ||
+    if ((rc = call.to_host(model_out, d_model, nc * (size_t)S)) || (rc = call.to_host(inlier, d_inl, n)) ||
         (rc = call.to_host(counts, d_cnt, 3 * (size_t)S)))
         return rc;
     return call.sync();
+}
+}  // namespace
+
+OFLK_API int oflk_estimate_motion_host(const float *src, const float *dst, const unsigned char *valid, int S, int N, int step0,
+                                       int model, int hypotheses, float threshold, unsigned seed, float *model_out,
+                                       unsigned char *inlier, int *counts)
+{
+    int rc = check_motion_shape(S, N);
+    if (rc || (rc = check_motion(model, hypotheses, threshold))) return rc;
+    return estimate_host(src, dst, valid, S, N, step0, model, hypotheses, threshold, seed, model_out, inlier, counts);
+}
+
+// ---- the homography fit: the same three forms with nine coefficients per model (oflk_homography.hpp) ----
+OFLK_API int oflk_homography_workspace(int S, int N, int hypotheses, size_t *bytes)
+{
+    if (!bytes) return fail(OFLK_ERR_INVALID, "NULL bytes");
+    int rc = check_motion_shape(S, N);
+    if (rc || (rc = check_ransac(hypotheses, 1.0f))) return rc;
+    *bytes = motion_ws(nullptr, S, N, hypotheses, 9).bytes;
+    return OFLK_OK;
+}
+
+OFLK_API int oflk_estimate_homography(const float *d_src, const float *d_dst, const unsigned char *d_valid, int S, int N, int step0,
+                                      int hypotheses, float threshold, unsigned seed, void *d_workspace, size_t workspace_bytes,
+                                      float *d_model, unsigned char *d_inlier, int *d_counts, void *stream)
+{
+    int rc = check_motion_shape(S, N);
+    if (rc || (rc = check_ransac(hypotheses, threshold))) return rc;
+    if (!d_src || !d_dst || !d_model || !d_inlier || !d_counts) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    if (!aligned(d_src, 8) || !aligned(d_dst, 8)) return fail(OFLK_ERR_INVALID, "d_src and d_dst must be 8-byte aligned");
+    if ((rc = check_motion_workspace(d_workspace, workspace_bytes, S, N, hypotheses, 9))) return rc;
+    return homography_launch({d_src, d_dst, d_valid, nullptr, nullptr}, S, N, (unsigned)step0, hypotheses, threshold, seed,
+                             motion_ws(d_workspace, S, N, hypotheses, 9), d_model, d_inlier, d_counts, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_tracks_homography(const float *d_tracks, const unsigned char *d_visible, const unsigned char *d_born, int T, int K,
+                                    int t0, int hypotheses, float threshold, unsigned seed, void *d_workspace,
+                                    size_t workspace_bytes, float *d_model, unsigned char *d_inlier, int *d_counts, void *stream)
+{
+    if (T < 2) return fail(OFLK_ERR_INVALID, "T must be >= 2 (got %d)", T);
+    int rc = check_motion_shape(T - 1, K);
+    if (rc || (rc = check_ransac(hypotheses, threshold))) return rc;
+    if (!d_tracks || !d_visible || !d_model || !d_inlier || !d_counts) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    if (!aligned(d_tracks, 8)) return fail(OFLK_ERR_INVALID, "d_tracks must be 8-byte aligned");
+    if ((rc = check_motion_workspace(d_workspace, workspace_bytes, T - 1, K, hypotheses, 9))) return rc;
+    // the rows as oflk_tracks_motion cuts them
+    const MotionIn in{d_tracks, d_tracks + 2 * (size_t)K, d_visible, d_visible + (size_t)K, d_born ? d_born + (size_t)K : nullptr};
+    return homography_launch(in, T - 1, K, (unsigned)t0, hypotheses, threshold, seed, motion_ws(d_workspace, T - 1, K, hypotheses, 9),
+                             d_model, d_inlier, d_counts, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_estimate_homography_host(const float *src, const float *dst, const unsigned char *valid, int S, int N, int step0,
+                                           int hypotheses, float threshold, unsigned seed, float *model_out, unsigned char *inlier,
+                                           int *counts)
+{
+    int rc = check_motion_shape(S, N);
+    if (rc || (rc = check_ransac(hypotheses, threshold))) return rc;
+    return estimate_host(src, dst, valid, S, N, step0, -1, hypotheses, threshold, seed, model_out, inlier, counts);
 }
 
 // =============================================================================
@@ -3726,8 +3821,9 @@ int check_warp_affine(const void *frames, int F, int H, int W, const void *map, 
     return check_hw(frames, out, H, W);
 }
 
-// the one launch of the warp of F frames on stream s; the arguments are checked
-template <class PIX>
+// the one launch of the warp of F frames on stream s; the arguments are checked.  PERSP: d_map is [F][9] and the kernel
+// k_warp_perspective
+template <class PIX, bool PERSP = false>
 int warp_affine_launch(const PIX *d_frames, int F, int H, int W, const double *d_map, PIX *d_out, unsigned char *d_inside,
                        hipStream_t s)
 {
@@ -3736,17 +3832,24 @@ int warp_affine_launch(const PIX *d_frames, int F, int H, int W, const double *d
     a.F = F; a.H = H; a.W = W;
     const bool vec = W % kWarpPx == 0 && aligned(d_out, (unsigned)(kWarpPx * sizeof(PIX))) && (!d_inside || aligned(d_inside, kWarpPx));
     const dim3 grid((unsigned)((H + 3) / 4), (unsigned)((W + 64 * kWarpPx - 1) / (64 * kWarpPx)), (unsigned)std::min(F, 65535));
-    if (vec)
-        hipLaunchKernelGGL((k_warp_affine<PIX, true>), grid, dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL((k_warp_affine<PIX, false>), grid, dim3(256), 0, s, a);
+    if constexpr (PERSP) {
+        if (vec)
+            hipLaunchKernelGGL((k_warp_perspective<PIX, true>), grid, dim3(256), 0, s, a);
+        else
+            hipLaunchKernelGGL((k_warp_perspective<PIX, false>), grid, dim3(256), 0, s, a);
+    } else {
+        if (vec)
+            hipLaunchKernelGGL((k_warp_affine<PIX, true>), grid, dim3(256), 0, s, a);
+        else
+            hipLaunchKernelGGL((k_warp_affine<PIX, false>), grid, dim3(256), 0, s, a);
+    }
     HIP_TRY(hipGetLastError());
     return OFLK_OK;
 }
 
-// F host frames under the device maps d_map [F][6], in chunks of frames through one pair of device buffers: a chunk goes up,
-// is warped and comes down.  Frames are independent, so the result does not depend on the cut.
-template <class PIX>
+// F host frames under the device maps d_map [F][6] (PERSP: [F][9]), in chunks of frames through one pair of device buffers: a
+// chunk goes up, is warped and comes down.  Frames are independent, so the result does not depend on the cut.
+template <class PIX, bool PERSP = false>
 int warp_affine_chunks(HostCall &call, const PIX *frames, int F, int H, int W, const double *d_map, PIX *out, unsigned char *inside)
 {
     const int C = sparse_chunk_pairs(F, H, W);
@@ -3761,7 +3864,7 @@ int warp_affine_chunks(HostCall &call, const PIX *frames, int F, int H, int W, c
         const int n = std::min(C, F - f0);
         const size_t o = (size_t)f0 * plane, len = (size_t)n * plane;
         if ((rc = call.to_device(d_in, frames + o, len)) ||
-            (rc = warp_affine_launch<PIX>(d_in, n, H, W, d_map + 6 * (size_t)f0, d_out, d_inside, nullptr)) ||
+            (rc = warp_affine_launch<PIX, PERSP>(d_in, n, H, W, d_map + (PERSP ? 9 : 6) * (size_t)f0, d_out, d_inside, nullptr)) ||
             (rc = call.to_host(out + o, d_out, len)) || (inside && (rc = call.to_host(inside + o, d_inside, len))) ||
             (rc = call.sync()))
             return rc;
@@ -3769,7 +3872,7 @@ int warp_affine_chunks(HostCall &call, const PIX *frames, int F, int H, int W, c
     return OFLK_OK;
 }
 
-template <class PIX>
+template <class PIX, bool PERSP = false>
 int warp_affine_host(const PIX *frames, int F, int H, int W, const double *map, PIX *out, unsigned char *inside)
 {
     int rc = check_warp_affine(frames, F, H, W, map, out);
@@ -3777,8 +3880,8 @@ int warp_affine_host(const PIX *frames, int F, int H, int W, const double *map, 
     HostCall call;
     if ((rc = call.begin())) return rc;
     double *d_map = nullptr;
-    if ((rc = call.upload(&d_map, map, 6 * (size_t)F))) return rc;
-    return warp_affine_chunks<PIX>(call, frames, F, H, W, d_map, out, inside);
+    if ((rc = call.upload(&d_map, map, (PERSP ? 9 : 6) * (size_t)F))) return rc;
+    return warp_affine_chunks<PIX, PERSP>(call, frames, F, H, W, d_map, out, inside);
 }
 
 // oflk_stabilize_sequence: pass 1 is the replenish call itself (its chunk loop; only rows come down, into this call's own
@@ -3890,6 +3993,29 @@ OFLK_API int oflk_warp_affine_host_u8(const unsigned char *frames, int F, int H,
                                       unsigned char *inside)
 {
     return warp_affine_host<unsigned char>(frames, F, H, W, map, out, inside);
+}
+
+// ---- the perspective warp: the affine warp's forms under 3 x 3 maps ----
+OFLK_API int oflk_warp_perspective(const void *d_frames, int u8, int F, int H, int W, const double *d_map, void *d_out,
+                                   unsigned char *d_inside, void *stream)
+{
+    if (int rc = check_warp_affine(d_frames, F, H, W, d_map, d_out)) return rc;
+    if (!aligned(d_map, 8)) return fail(OFLK_ERR_INVALID, "d_map must be 8-byte aligned");
+    if (!u8 && (!aligned(d_frames, 4) || !aligned(d_out, 4))) return fail(OFLK_ERR_INVALID, "float32 frames must be 4-byte aligned");
+    return u8 ? warp_affine_launch<unsigned char, true>((const unsigned char *)d_frames, F, H, W, d_map, (unsigned char *)d_out,
+                                                        d_inside, (hipStream_t)stream)
+              : warp_affine_launch<float, true>((const float *)d_frames, F, H, W, d_map, (float *)d_out, d_inside, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_warp_perspective_host(const float *frames, int F, int H, int W, const double *map, float *out, unsigned char *inside)
+{
+    return warp_affine_host<float, true>(frames, F, H, W, map, out, inside);
+}
+
+OFLK_API int oflk_warp_perspective_host_u8(const unsigned char *frames, int F, int H, int W, const double *map, unsigned char *out,
+                                           unsigned char *inside)
+{
+    return warp_affine_host<unsigned char, true>(frames, F, H, W, map, out, inside);
 }
 
 OFLK_API int oflk_stabilize_sequence(const float *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,

@@ -37,8 +37,8 @@ struct MotionArgs {
     int *M;                                 // [S]          workspace
     float4 *pts;                            // [S][N]       (the first M[s] of a step are written and read)
     int *score;                             // [S][Hn]
-    float *hmodel;                          // [S][Hn][6]
-    float *model;                           // [S][6]       outputs
+    float *hmodel;                          // [S][Hn][6]; the homography fit (oflk_homography.hpp): [S][Hn][9]
+    float *model;                           // [S][6]       outputs; the homography fit: [S][9]
     unsigned char *inlier;                  // [S][N]
     int *counts;                            // [S][3]
 };
@@ -213,8 +213,8 @@ __global__ __launch_bounds__(64 * kMotionWaves) void k_motion_score(MotionArgs a
 }
 
 // the fixed tree of the statement over `rows` arrays of kMotionLanes doubles; all threads call it, the sums end in red[k][0]
-template <int ROWS>
-__device__ __forceinline__ void motion_tree(double (&red)[7][kMotionLanes], int tid)
+template <int ROWS, int CAP>
+__device__ __forceinline__ void motion_tree(double (&red)[CAP][kMotionLanes], int tid)
 {
     __syncthreads();
     for (int st = kMotionLanes / 2; st >= 1; st >>= 1) {
@@ -236,6 +236,38 @@ __device__ __forceinline__ int motion_int_sum(int (&ired)[kMotionLanes], int tid
     return ired[0];
 }
 
+// the largest of a step's Hn scores into bs and its hypothesis into bh, ties to the lowest h: a thread meets its h
+// ascending, the tree compares (score, h).  All threads call it
+__device__ __forceinline__ void motion_argmax(const int *score, int Hn, int (&ired)[kMotionLanes], int (&ibest)[kMotionLanes], int tid,
+                                              int &bs, int &bh)
+{
+    bs = -1;
+    bh = 0x7fffffff;
+    for (int h = tid; h < Hn; h += kMotionLanes) {
+        const int sc = score[h];
+        if (sc > bs) {
+            bs = sc;
+            bh = h;
+        }
+    }
+    __syncthreads();   // the previous step's readers of ired are done
+    ired[tid] = bs;
+    ibest[tid] = bh;
+    __syncthreads();
+    for (int st = kMotionLanes / 2; st >= 1; st >>= 1) {
+        if (tid < st) {
+            const int os = ired[tid + st], oh = ibest[tid + st];
+            if (os > ired[tid] || (os == ired[tid] && oh < ibest[tid])) {
+                ired[tid] = os;
+                ibest[tid] = oh;
+            }
+        }
+        __syncthreads();
+    }
+    bs = ired[0];
+    bh = ibest[0];
+}
+
 // ---- 3. select and refit: grid (min(S, 65535)), block kMotionLanes ----
 template <int MODEL>
 __global__ __launch_bounds__(kMotionLanes) void k_motion_refit(MotionArgs a)
@@ -248,31 +280,8 @@ __global__ __launch_bounds__(kMotionLanes) void k_motion_refit(MotionArgs a)
         const size_t row = (size_t)s * (size_t)a.N;
         const int M = a.M[s];
         const float4 *pts = a.pts + row;
-        // the largest score, ties to the lowest h: a thread meets its h ascending, the tree compares (score, h)
-        int bs = -1, bh = 0x7fffffff;
-        for (int h = tid; h < a.Hn; h += kMotionLanes) {
-            const int sc = a.score[(size_t)s * (size_t)a.Hn + (size_t)h];
-            if (sc > bs) {
-                bs = sc;
-                bh = h;
-            }
-        }
-        __syncthreads();   // the previous step's readers of ired are done
-        ired[tid] = bs;
-        ibest[tid] = bh;
-        __syncthreads();
-        for (int st = kMotionLanes / 2; st >= 1; st >>= 1) {
-            if (tid < st) {
-                const int os = ired[tid + st], oh = ibest[tid + st];
-                if (os > ired[tid] || (os == ired[tid] && oh < ibest[tid])) {
-                    ired[tid] = os;
-                    ibest[tid] = oh;
-                }
-            }
-            __syncthreads();
-        }
-        bs = ired[0];
-        bh = ibest[0];
+        int bs, bh;
+        motion_argmax(a.score + (size_t)s * (size_t)a.Hn, a.Hn, ired, ibest, tid, bs, bh);
         if (bs < 0) {   // M < m, or every hypothesis degenerate (uniform over the block)
             for (long n = tid; n < (long)a.N; n += kMotionLanes) a.inlier[row + (size_t)n] = 0;
             if (tid < 6) a.model[6 * (size_t)s + tid] = nan;

@@ -19,6 +19,8 @@
 //                       other instantiation, which stores element by element.  The four taps of a pixel are
 //                       bilinear_taps / bilinear_finish, gathered through the cache as k_warp's: an affine image of a
 //                       row segment is a row segment
+//   k_warp_perspective<PIX, VEC>  the same body under a 3 x 3 map (oflk_warp_perspective, tests/homography_model.py): the
+//                       source position divided by w, two float64 divisions per pixel, outside where w <= 0
 #pragma once
 #include "oflk_kernels.hpp"
 
@@ -212,7 +214,7 @@ __global__ __launch_bounds__(kStabOnlineBlock) void k_stab_online(const float *_
 template <class PIX>
 struct WarpAffineArgs {
     const PIX *in;            // [F][H][W]
-    const double *map;        // [F][6]
+    const double *map;        // [F][6]; k_warp_perspective: [F][9]
     PIX *out;                 // [F][H][W]
     unsigned char *inside;    // [F][H][W] or NULL
     int F, H, W;
@@ -223,9 +225,12 @@ __device__ __forceinline__ unsigned char warp_store_value(float v, unsigned char
 
 // VEC: W % kWarpPx == 0 and out (and inside, when given) aligned to a lane's store, so every lane owns kWarpPx whole pixels
 // and stores them at once.  The two forms are two kernels: in one, the compiler folds the wide store into the tail's.
-template <class PIX, bool VEC>
-__global__ __launch_bounds__(256) void k_warp_affine(WarpAffineArgs<PIX> a)
+// PERSP: the map has a third row and the source position is divided by w = (m6 x + m7 y) + m8, two IEEE divisions per pixel
+// (tests/homography_model.py); w <= 0 or a NaN anywhere is outside.
+template <class PIX, bool VEC, bool PERSP>
+__device__ __forceinline__ void warp_frames(const WarpAffineArgs<PIX> a)
 {
+    constexpr int NC = PERSP ? 9 : 6;
     const int x0 = ((int)blockIdx.y * 64 + (int)(threadIdx.x & 63)) * kWarpPx;
     const int y = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
     if (x0 >= a.W || y >= a.H) return;
@@ -233,18 +238,28 @@ __global__ __launch_bounds__(256) void k_warp_affine(WarpAffineArgs<PIX> a)
     const size_t row = (size_t)y * (size_t)a.W + (size_t)x0;
     const double fy = (double)y, Wm1 = (double)(a.W - 1), Hm1 = (double)(a.H - 1);
     for (int f = blockIdx.z; f < a.F; f += gridDim.z) {
-        const double *__restrict__ m = a.map + 6 * (size_t)f;
+        const double *__restrict__ m = a.map + NC * (size_t)f;
         const double m0 = m[0], m2 = m[2], m3 = m[3], m5 = m[5];
         const double bx = m[1] * fy, by = m[4] * fy;
+        [[maybe_unused]] double m6 = 0.0, m8 = 1.0, bw = 0.0;
+        if constexpr (PERSP) {
+            m6 = m[6];
+            m8 = m[8];
+            bw = m[7] * fy;
+        }
         const PIX *__restrict__ img = a.in + (size_t)f * plane;
         PIX v[kWarpPx];
         unsigned char in[kWarpPx];
 #pragma unroll
         for (int k = 0; k < kWarpPx; k++) {   // a pixel past the row's end is computed (its taps are clamped) and not stored
             const double fx = (double)(x0 + k);
-            const double xs = (m0 * fx + bx) + m2;
-            const double ys = (m3 * fx + by) + m5;
-            const bool ok = xs >= 0.0 && xs <= Wm1 && ys >= 0.0 && ys <= Hm1;
+            [[maybe_unused]] const double w = (m6 * fx + bw) + m8;
+            const double xa = (m0 * fx + bx) + m2;
+            const double ya = (m3 * fx + by) + m5;
+            const double xs = PERSP ? xa / w : xa;
+            const double ys = PERSP ? ya / w : ya;
+            const bool within = xs >= 0.0 && xs <= Wm1 && ys >= 0.0 && ys <= Hm1;
+            const bool ok = PERSP ? w > 0.0 && within : within;
             const BilinearTaps t = bilinear_taps(a.H, a.W, ys, xs);
             const float s = bilinear_finish(t, ld_pix<PIX>(img, (unsigned)t.i00), ld_pix<PIX>(img, (unsigned)t.i01),
                                             ld_pix<PIX>(img, (unsigned)t.i10), ld_pix<PIX>(img, (unsigned)t.i11));
@@ -274,6 +289,18 @@ __global__ __launch_bounds__(256) void k_warp_affine(WarpAffineArgs<PIX> a)
             }
         }
     }
+}
+
+template <class PIX, bool VEC>
+__global__ __launch_bounds__(256) void k_warp_affine(WarpAffineArgs<PIX> a)
+{
+    warp_frames<PIX, VEC, false>(a);
+}
+
+template <class PIX, bool VEC>
+__global__ __launch_bounds__(256) void k_warp_perspective(WarpAffineArgs<PIX> a)
+{
+    warp_frames<PIX, VEC, true>(a);
 }
 
 }  // namespace oflk

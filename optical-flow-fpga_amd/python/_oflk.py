@@ -121,6 +121,10 @@ SIGNATURES = {
     "oflk_estimate_motion": (ctypes.c_int, [_vp] * 3 + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_uint, _vp, ctypes.c_size_t] + [_vp] * 4),
     "oflk_tracks_motion": (ctypes.c_int, [_vp] * 3 + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_uint, _vp, ctypes.c_size_t] + [_vp] * 4),
     "oflk_estimate_motion_host": (ctypes.c_int, [_f32p, _f32p, _vp] + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_uint, _f32p, _vp, _i32p]),
+    "oflk_homography_workspace": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)]),
+    "oflk_estimate_homography": (ctypes.c_int, [_vp] * 3 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _vp, ctypes.c_size_t] + [_vp] * 4),
+    "oflk_tracks_homography": (ctypes.c_int, [_vp] * 3 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _vp, ctypes.c_size_t] + [_vp] * 4),
+    "oflk_estimate_homography_host": (ctypes.c_int, [_f32p, _f32p, _vp] + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f32p, _vp, _i32p]),
     "oflk_tracker_set_motion": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_uint]),
     "oflk_tracker_motion_device": (ctypes.c_int, [_vp] + [ctypes.POINTER(_vp)] * 3),
     "oflk_tracker_read_motion": (ctypes.c_int, [_vp, _f32p, _vp, _i32p, _vp]),
@@ -129,6 +133,9 @@ SIGNATURES = {
     "oflk_stabilize_trajectory_host": (ctypes.c_int, [_f32p, _i32p, ctypes.c_int, _f64p, ctypes.c_int, _f32p, _f64p, _vp]),
     "oflk_warp_affine_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 3 + [_f64p, _f32p, _vp]),
     "oflk_warp_affine_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [_f64p, _vp, _vp]),
+    "oflk_warp_perspective": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_vp] * 4),
+    "oflk_warp_perspective_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 3 + [_f64p, _f32p, _vp]),
+    "oflk_warp_perspective_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [_f64p, _vp, _vp]),
     "oflk_stabilize_sequence": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int, _f32p, _f32p, _f32p, _i32p, _vp]),
     "oflk_stabilize_sequence_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int, _vp, _f32p, _f32p, _i32p, _vp]),
     "oflk_stabilize_trajectory_ring": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 4 + [_f64p, ctypes.c_int, _vp, _vp, _vp]),
@@ -589,6 +596,12 @@ def check_motion_params(model, hypotheses, threshold: float, seed) -> Tuple[int,
     code = MOTION_MODELS.get(model) if isinstance(model, str) else (model if model in (0, 1, 2) and not isinstance(model, bool) else None)
     if code is None:
         raise ValueError(f"model must be one of {sorted(MOTION_MODELS)}, got {model!r}")
+    return (int(code),) + check_ransac_params(hypotheses, threshold, seed)
+
+
+def check_ransac_params(hypotheses, threshold: float, seed) -> Tuple[int, float, int]:
+    """What the motion and the homography fit share of check_motion_params: (hypotheses, threshold as float32, seed as
+    uint32), with its ValueErrors"""
     if isinstance(hypotheses, bool) or int(hypotheses) != hypotheses or not 1 <= int(hypotheses) <= MOTION_MAX_HYPOTHESES:
         raise ValueError(f"hypotheses must be an integer in [1, {MOTION_MAX_HYPOTHESES}], got {hypotheses!r}")
     with np.errstate(over="ignore"):
@@ -597,7 +610,7 @@ def check_motion_params(model, hypotheses, threshold: float, seed) -> Tuple[int,
         raise ValueError(f"threshold must be finite and > 0, got {threshold!r}")
     if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 32:
         raise ValueError(f"seed must be an integer in [0, 2^32), got {seed!r}")
-    return int(code), int(hypotheses), float(thr), int(seed)
+    return int(hypotheses), float(thr), int(seed)
 
 
 def motion_workspace(S: int, N: int, hypotheses: int) -> int:
@@ -636,6 +649,46 @@ def estimate_motion_host(src: np.ndarray, dst: np.ndarray, valid: Optional[np.nd
     check(lib().oflk_estimate_motion_host(ptr(src), ptr(dst), None if valid is None else valid.ctypes.data, S, N, int(step0),
                                           int(model), int(hypotheses), float(threshold), int(seed), ptr(out), inl.ctypes.data,
                                           cnt.ctypes.data_as(_i32p)))
+    return out, inl, cnt
+
+
+def homography_workspace(S: int, N: int, hypotheses: int) -> int:
+    """bytes of the workspace of oflk_estimate_homography (S steps of N correspondences) and oflk_tracks_homography (S = T-1,
+    N = K)"""
+    n = ctypes.c_size_t(0)
+    check(lib().oflk_homography_workspace(int(S), int(N), int(hypotheses), ctypes.byref(n)))
+    return int(n.value)
+
+
+def estimate_homography(d_src: int, d_dst: int, d_valid: int, S: int, N: int, d_workspace: int, workspace_bytes: int, d_model: int,
+                        d_inlier: int, d_counts: int, hypotheses: int = 256, threshold: float = 1.0, seed: int = 0, step0: int = 0,
+                        stream: int = 0) -> None:
+    """oflk_estimate_homography on device pointers: d_src, d_dst [S][N][2] float32, d_valid [S][N] uint8 or 0 -> d_model
+    [S][9] float32, d_inlier [S][N] uint8, d_counts [S][3] int32 (n_inliers, n_valid, status); asynchronous on `stream`."""
+    check(lib().oflk_estimate_homography(d_src or None, d_dst or None, d_valid or None, int(S), int(N), int(step0), int(hypotheses),
+                                         float(threshold), int(seed), d_workspace or None, int(workspace_bytes), d_model or None,
+                                         d_inlier or None, d_counts or None, stream))
+
+
+def tracks_homography(d_tracks: int, d_visible: int, d_born: int, T: int, K: int, d_workspace: int, workspace_bytes: int,
+                      d_model: int, d_inlier: int, d_counts: int, hypotheses: int = 256, threshold: float = 1.0, seed: int = 0,
+                      t0: int = 0, stream: int = 0) -> None:
+    """oflk_tracks_homography on device pointers: rows d_tracks [T][K][2], d_visible [T][K], d_born [T][K] or 0 -> the T-1
+    steps' d_model [T-1][9], d_inlier [T-1][K], d_counts [T-1][3]; the workspace is homography_workspace(T-1, K, hypotheses)."""
+    check(lib().oflk_tracks_homography(d_tracks or None, d_visible or None, d_born or None, int(T), int(K), int(t0), int(hypotheses),
+                                       float(threshold), int(seed), d_workspace or None, int(workspace_bytes), d_model or None,
+                                       d_inlier or None, d_counts or None, stream))
+
+
+def estimate_homography_host(src: np.ndarray, dst: np.ndarray, valid: Optional[np.ndarray], hypotheses: int, threshold: float,
+                             seed: int, step0: int = 0):
+    """oflk_estimate_homography_host: contiguous float32 (S, N, 2) arrays and an optional uint8 (S, N) mask in; (model (S, 9)
+    float32, inlier (S, N) uint8, counts (S, 3) int32) out"""
+    S, N = src.shape[:2]
+    out, inl, cnt = np.empty((S, 9), np.float32), np.empty((S, N), np.uint8), np.empty((S, 3), np.int32)
+    check(lib().oflk_estimate_homography_host(ptr(src), ptr(dst), None if valid is None else valid.ctypes.data, S, N, int(step0),
+                                              int(hypotheses), float(threshold), int(seed), ptr(out), inl.ctypes.data,
+                                              cnt.ctypes.data_as(_i32p)))
     return out, inl, cnt
 
 
@@ -691,6 +744,13 @@ def warp_affine(d_frames: int, F: int, H: int, W: int, d_map: int, d_out: int, d
                                  d_inside or None, stream))
 
 
+def warp_perspective(d_frames: int, F: int, H: int, W: int, d_map: int, d_out: int, d_inside: int = 0, u8: bool = False,
+                     stream: int = 0) -> None:
+    """oflk_warp_perspective on device pointers: oflk_warp_affine's arguments with d_map [F][9] float64; asynchronous."""
+    check(lib().oflk_warp_perspective(d_frames or None, int(bool(u8)), int(F), int(H), int(W), d_map or None, d_out or None,
+                                      d_inside or None, stream))
+
+
 def stabilize_trajectory_host(model: np.ndarray, counts: Optional[np.ndarray], T: int, weights: np.ndarray):
     """oflk_stabilize_trajectory_host: contiguous float32 (T-1, 6) models and optional int32 (T-1, 3) counts in;
     (correction (T, 6) float32, map (T, 6) float64, held (T-1,) uint8) out"""
@@ -702,13 +762,15 @@ def stabilize_trajectory_host(model: np.ndarray, counts: Optional[np.ndarray], T
 
 
 def warp_affine_host(frames: np.ndarray, maps: np.ndarray, inside: bool = False):
-    """oflk_warp_affine_host[_u8]: contiguous (F, H, W) float32 or uint8 frames and (F, 6) float64 maps in; the warped
-    frames and, when asked for, the inside mask (else None) out"""
+    """oflk_warp_affine_host[_u8] -- oflk_warp_perspective_host[_u8] for (F, 9) maps --: contiguous (F, H, W) float32 or uint8
+    frames and (F, 6) float64 maps in; the warped frames and, when asked for, the inside mask (else None) out"""
     F, H, W = frames.shape
     u8 = frames.dtype == np.uint8
     out = np.empty_like(frames)
     ins = np.empty((F, H, W), np.uint8) if inside else None
     fn = lib().oflk_warp_affine_host_u8 if u8 else lib().oflk_warp_affine_host
+    if maps.shape[-1] == 9:
+        fn = lib().oflk_warp_perspective_host_u8 if u8 else lib().oflk_warp_perspective_host
     check(fn(frames.ctypes.data if u8 else ptr(frames), F, H, W, _f64(maps), out.ctypes.data if u8 else ptr(out),
              None if ins is None else ins.ctypes.data))
     return out, ins

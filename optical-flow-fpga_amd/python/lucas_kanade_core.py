@@ -255,9 +255,17 @@ def estimate_motion(src, dst, valid=None, model: str = "similarity", hypotheses:
     "similarity" (rotation, uniform scale, translation) or "affine".  `hypotheses` minimal samples are drawn from a
     counter-based hash of (seed, step0 + s, hypothesis), scored by the number of correspondences within `threshold` pixels,
     and the best one (ties to the lowest) is refitted over its inliers.  The same inputs give the same bytes.  The statement
-    is in include/oflk.h; homographies and iterative re-estimation are not offered.
+    is in include/oflk.h; this call fits six coefficients (estimate_homography fits nine) and iterative re-estimation is not
+    offered.
     """
     code, hn, thr, sd = _oflk.check_motion_params(model, hypotheses, threshold, seed)
+    a, b, v, batched = _correspondences(src, dst, valid, step0)
+    return _motion(*_oflk.estimate_motion_host(a, b, v, code, hn, thr, sd, int(step0)), batched)
+
+
+def _correspondences(src, dst, valid, step0):
+    """the arrays of estimate_motion / estimate_homography as the host forms take them: (src, dst (S, N, 2) float32, valid
+    (S, N) uint8 or None, batched)"""
     a, b = np.ascontiguousarray(src, np.float32), np.ascontiguousarray(dst, np.float32)
     if a.ndim not in (2, 3) or a.shape[-1] != 2 or a.shape != b.shape or a.size == 0:
         raise ValueError(f"expected src and dst of one shape (N, 2) or (S, N, 2), got {a.shape} and {b.shape}")
@@ -272,7 +280,7 @@ def estimate_motion(src, dst, valid=None, model: str = "similarity", hypotheses:
             raise ValueError(f"valid must have shape {a.shape[:2] if batched else a.shape[1:2]}, got {np.shape(valid)}")
     if isinstance(step0, bool) or int(step0) != step0 or not 0 <= int(step0) < 2 ** 31:
         raise ValueError(f"step0 must be an integer in [0, 2^31), got {step0!r}")
-    return _motion(*_oflk.estimate_motion_host(a, b, v, code, hn, thr, sd, int(step0)), batched)
+    return a, b, v, batched
 
 
 def tracks_motion(tracks, visible, born=None, model: str = "similarity", hypotheses: int = 256, threshold: float = 1.0,
@@ -281,6 +289,13 @@ def tracks_motion(tracks, visible, born=None, model: str = "similarity", hypothe
     None.  Step t runs from row t to row t+1 with hash index t0 + t; a slot is valid on it when it is visible on both rows
     and not born on row t+1 (a slot that died and was refilled on one row is two different tracks).  Returns a batched
     Motion of T-1 steps."""
+    tr, ok = _track_steps(tracks, visible, born)
+    return estimate_motion(tr[:-1], tr[1:], ok, model, hypotheses, threshold, seed, t0)
+
+
+def _track_steps(tracks, visible, born):
+    """(tracks (T, K, 2) float32, valid (T-1, K)): a slot is valid on step t when visible on rows t and t+1 and not born on
+    row t+1"""
     tr, vis = np.asarray(tracks, np.float32), np.asarray(visible) != 0
     if tr.ndim != 3 or tr.shape[2] != 2 or tr.shape[0] < 2 or vis.shape != tr.shape[:2]:
         raise ValueError(f"expected tracks (T, K, 2) with T >= 2 and visible (T, K), got {tr.shape} and {vis.shape}")
@@ -290,7 +305,42 @@ def tracks_motion(tracks, visible, born=None, model: str = "similarity", hypothe
         if b.shape != vis.shape:
             raise ValueError(f"born must have shape {vis.shape}, got {b.shape}")
         ok &= ~b[1:]
-    return estimate_motion(tr[:-1], tr[1:], ok, model, hypotheses, threshold, seed, t0)
+    return tr, ok
+
+
+class Homography(NamedTuple):
+    """A homography fitted to point correspondences (estimate_homography)."""
+    model: np.ndarray      # (3, 3) float32, model[2, 2] == 1: dst ~ model @ (x, y, 1); NaN when status is 0.  Batched: (S, 3, 3)
+    inlier: np.ndarray     # (N,) bool: the correspondences within the threshold of the returned model.  Batched: (S, N)
+    n_inliers: int         # the mask's sum.  Batched: (S,) int32
+    n_valid: int           # correspondences that entered the fit
+    status: int            # 1: a model was found; 0: fewer than four valid correspondences, or every sample degenerate
+
+
+def estimate_homography(src, dst, valid=None, hypotheses: int = 256, threshold: float = 1.0, seed: int = 0,
+                        step0: int = 0) -> Homography:
+    """A robust homography between point sets, on the GPU: a deterministic four-point RANSAC and a normalised linear refit.
+
+    src, dst, valid, hypotheses, threshold, seed and step0 are estimate_motion's.  A hypothesis is the closed-form
+    homography of four correspondences; a correspondence is an inlier of it when it lies in front of the camera
+    (h20 x + h21 y + 1 > 0) and reprojects within `threshold` pixels; the best hypothesis (ties to the lowest) is refitted
+    over its inliers by the normalised direct linear transform.  The same inputs give the same bytes.  The statement is in
+    include/oflk.h.
+    """
+    hn, thr, sd = _oflk.check_ransac_params(hypotheses, threshold, seed)
+    a, b, v, batched = _correspondences(src, dst, valid, step0)
+    out, inl, cnt = _oflk.estimate_homography_host(a, b, v, hn, thr, sd, int(step0))
+    m = Homography(out.reshape(-1, 3, 3), inl.astype(bool), cnt[:, 0].copy(), cnt[:, 1].copy(), cnt[:, 2].copy())
+    return m if batched else Homography(m.model[0], m.inlier[0], int(m.n_inliers[0]), int(m.n_valid[0]), int(m.status[0]))
+
+
+def tracks_homography(tracks, visible, born=None, hypotheses: int = 256, threshold: float = 1.0, seed: int = 0,
+                      t0: int = 0) -> Homography:
+    """The T-1 homographies between consecutive rows of any of the track calls, with tracks_motion's arguments and validity
+    rule.  Returns a batched Homography of T-1 steps, model (T-1, 3, 3), NaN where status is 0.  model[t] maps row t to row
+    t+1, so warp_perspective(frames[t+1], model[t]) registers frame t+1 onto frame t."""
+    tr, ok = _track_steps(tracks, visible, born)
+    return estimate_homography(tr[:-1], tr[1:], ok, hypotheses, threshold, seed, t0)
 
 
 class Trajectory(NamedTuple):
@@ -344,6 +394,28 @@ def warp_affine(frames, maps, return_inside: bool = False):
     if m.size != 6 * F or m.ndim not in (1, 2, 3) or m.shape[-1] not in (3, 6):
         raise ValueError(f"expected {F} maps of shape (2, 3) or (6,), got {np.shape(maps)}")
     out, ins = _oflk.warp_affine_host(arr, m.reshape(F, 6), bool(return_inside))
+    out = out[0] if single else out
+    if not return_inside:
+        return out
+    return out, (ins[0] if single else ins).astype(bool)
+
+
+def warp_perspective(frames, maps, return_inside: bool = False):
+    """Resample frames under one 3 x 3 map each, on the GPU: out[f, y, x] is the bilinear sample (zero outside) of frame f at
+    (xs, ys) = the first two rows of maps[f] applied to (x, y, 1) and divided by the third, in float64.  A pixel is outside
+    where the divisor is not positive or the source position leaves the frame.  frames: (H, W) or (F, H, W), float32 or
+    uint8 (uint8 out: rounded half to even); maps: (3, 3) / (9,) for one frame, (F, 3, 3) / (F, 9) for a batch, e.g.
+    Homography.model: the map takes an output pixel to its source, so warp_perspective(frames[t+1], model[t]) registers
+    frame t+1 onto frame t.  With return_inside also the (F, H, W) bool mask of the pixels that were sampled."""
+    single = isinstance(frames, np.ndarray) and frames.ndim == 2
+    arr, _ = _oflk.as_frames(frames)
+    F, H, W = arr.shape
+    if H < 2 or W < 2:
+        raise ValueError(f"frames must be at least 2 x 2, got {H} x {W}")
+    m = np.ascontiguousarray(maps, np.float64)
+    if m.size != 9 * F or m.ndim not in (1, 2, 3) or m.shape[-1] not in (3, 9) or (m.shape[-1] == 3 and (m.ndim < 2 or m.shape[-2] != 3)):
+        raise ValueError(f"expected {F} maps of shape (3, 3) or (9,), got {np.shape(maps)}")
+    out, ins = _oflk.warp_affine_host(arr, m.reshape(F, 9), bool(return_inside))
     out = out[0] if single else out
     if not return_inside:
         return out

@@ -30,8 +30,9 @@ import numpy as np
 import numpy.typing as npt
 
 import _oflk
-from lucas_kanade_core import (Motion, Trajectory, estimate_motion, lucas_kanade_single_scale, stabilize_trajectory,  # noqa: F401
-                               tracks_motion, warp_affine)
+from lucas_kanade_core import (Homography, Motion, Trajectory, estimate_homography, estimate_motion,  # noqa: F401
+                               lucas_kanade_single_scale, stabilize_trajectory, tracks_homography, tracks_motion, warp_affine,
+                               warp_perspective)
 
 SCRIPT_DIR = Path(__file__).resolve().parent
 PROJECT_ROOT = SCRIPT_DIR.parent

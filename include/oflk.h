@@ -687,6 +687,103 @@ int oflk_stabilize_sequence_u8(const unsigned char *frames, int T, int H, int W,
                                const double *weights, int radius, unsigned char *out, float *correction, float *model_out,
                                int *counts_out, unsigned char *held);
 
+/* ---- video mosaics: chained homographies, every frame blended onto one canvas ------------------------------------------- */
+/* The statement (tests/mosaic_model.py).  Every operation is float64 unless stated and rounded on its own, in the order
+ * written; nothing is contracted, there is no transcendental and no atomic, and no result depends on the launch geometry or on
+ * how the frames are cut into calls.  The device equals it byte for byte, a NaN equal to a NaN.
+ * Chain: the step models composed from an anchor frame.
+ *   inputs         model [T-1][9] float32 and counts [T-1][3] (or NULL) as oflk_tracks_homography writes them;  the anchor a
+ *                  in [0, T-1];  the frame size H, W >= 2;  extent, finite and positive;  T >= 1 (T == 1: model may be NULL)
+ *   step s         A_s = the nine coefficients as double;  B_s = adj(A_s) / adj(A_s)[2][2]: the adjugate's nine cofactors
+ *                  (each a b - c d, as the homography fit writes them: e i - f h, c h - b i, b f - c e;  f g - d i, a i - c g,
+ *                  c d - a f;  d h - e g, b g - a h, a e - b d for the rows [a b c; d e f; g h i]) and nine divisions.  The
+ *                  step is held when counts[s][2] == 0, a coefficient of A_s is not finite, adj[2][2] == 0 or a coefficient of
+ *                  B_s is not finite: then A_s = B_s = I and held[s] = 1, else 0 (the stabiliser's rule)
+ *   composition    C = X o Y (Y first):  C[r][c] = (X[r][0] Y[0][c] + X[r][1] Y[1][c]) + X[r][2] Y[2][c], then all nine
+ *                  divided by C[2][2]
+ *   chains         P_t maps anchor coordinates to frame t's:  P_a = I;  P_t = A_{t-1} o P_{t-1} for t > a;
+ *                  P_t = B_t o P_{t+1} for t < a.  Q_t maps frame t's to the anchor's:  Q_a = I;  Q_t = Q_{t-1} o B_{t-1} for
+ *                  t > a;  Q_t = Q_{t+1} o A_t for t < a.  Q is a chain of its own, not an inversion of P
+ *   box            the corners (0,0), (W-1,0), (W-1,H-1), (0,H-1) under Q_t by the perspective warp's formula, divisions
+ *                  included:  w = (q6 x + q7 y) + q8, X = ((q0 x + q1 y) + q2) / w, Y likewise;
+ *                  box[t] = (xmin, ymin, xmax, ymax), each taken as min(min(c0, c1), min(c2, c3))
+ *   dropped[t]     1 when a corner's w <= 0, anything in P_t, Q_t or the corners is not finite, or a corner coordinate
+ *                  exceeds extent in absolute value;  and for every frame further from the anchor on that side, whose chain
+ *                  runs through the dropped one.  The anchor is never dropped.  box of a dropped frame is four NaNs;  its
+ *                  from_anchor and to_anchor hold what the chain computed
+ *   outputs        from_anchor [T][9] = P (what oflk_mosaic_accumulate takes), to_anchor [T][9] = Q, box [T][4] float64;
+ *                  held [T-1] (may be NULL) and dropped [T] bytes
+ * Canvas (host integers): x0 = floor(min xmin), y0 = floor(min ymin) over the frames not dropped,
+ * Wc = ceil(max xmax) - x0 + 1, Hc likewise.
+ * Accumulate.  The state represents, per canvas pixel, a float64 sum, a float64 wsum and an int32 count; all-zero bytes are
+ * the empty canvas (clear it with a memset); its layout is private.  Canvas pixel (x, y) has fx = f64(x0 + x),
+ * fy = f64(y0 + y), the sums formed in integers.  For f = 0 .. F-1 ascending with skip[f] == 0, m = map[f]:
+ *   w = (m6 fx + m7 fy) + m8;  xs = ((m0 fx + m1 fy) + m2) / w;  ys = ((m3 fx + m4 fy) + m5) / w;
+ *   inside = w > 0 and 0 <= xs <= W-1 and 0 <= ys <= H-1, a NaN anywhere meaning outside
+ * -- oflk_warp_perspective's, with (fx, fy) for the pixel indices.  Where inside, s = the float32 bilinear sample of frame f
+ * at (xs, ys), and
+ *   OFLK_MOSAIC_MEAN      sum += f64(s);  wsum += 1.0
+ *   OFLK_MOSAIC_FEATHER   g = min(min(xs, (W-1) - xs), min(ys, (H-1) - ys)) + 1.0;  sum += g * f64(s) (the product rounded,
+ *                         then the sum);  wsum += g
+ *   OFLK_MOSAIC_FIRST     only when count == 0:  sum = f64(s), wsum = 1.0
+ *   OFLK_MOSAIC_LAST      sum = f64(s), wsum = 1.0
+ * and count += 1 in every mode.  A pixel's samples are added one by one in frame order, so a canvas accumulated in several
+ * calls (frames 0 .. k, then k+1 .. F-1) holds the bytes of one call: a video may be fed as it arrives.
+ * Resolve: where count > 0, out = f32(sum / wsum), for uint8 output (unsigned char) rintf of that;  elsewhere 0.  The state
+ * is not changed.
+ * Refusals, before any device call: T < 1 (the sequence call: T < 2), an anchor outside [0, T-1], an extent that is not finite
+ * and positive, F < 1, H or W < 2, Hc or Wc < 1, an unknown blend, NULL pointers (d_counts, d_held, d_skip, d_count and the
+ * sequence call's outputs after `canvas` may be NULL; d_model when T == 1), a map or chain output that is not 8-byte aligned, a
+ * state that is too small or not 256-byte aligned: OFLK_ERR_INVALID;  a frame or a canvas of 2^30 pixels or more, a canvas
+ * that reaches 2^30 from the origin: OFLK_ERR_UNSUPPORTED.  A temporal median, exposure compensation and bundle adjustment of
+ * the chain (its drift grows with the distance from the anchor) are not offered. */
+#define OFLK_MOSAIC_MEAN 0
+#define OFLK_MOSAIC_FEATHER 1
+#define OFLK_MOSAIC_FIRST 2
+#define OFLK_MOSAIC_LAST 3
+/* device form, one launch (one block, a lane for each side of the anchor), no workspace, asynchronous on `stream`; can be
+ * captured into a graph */
+int oflk_mosaic_chain(const float *d_model, const int *d_counts, int T, int anchor, int H, int W, double extent,
+                      double *d_from_anchor, double *d_to_anchor, double *d_box, unsigned char *d_held, unsigned char *d_dropped,
+                      void *stream);
+/* host arrays, synchronous */
+int oflk_mosaic_chain_host(const float *model, const int *counts, int T, int anchor, int H, int W, double extent,
+                           double *from_anchor, double *to_anchor, double *box, unsigned char *held, unsigned char *dropped);
+/* host only, no device call: the canvas of the boxes that are not dropped.  A box that is not finite: OFLK_ERR_INVALID */
+int oflk_mosaic_canvas(const double *box, const unsigned char *dropped, int T, int *x0, int *y0, int *Wc, int *Hc);
+/* bytes of the state of an Hc x Wc canvas; 0 for a canvas that is refused.  Host only */
+size_t oflk_mosaic_state_bytes(int Hc, int Wc);
+/* device form, one launch: adds the F frames d_frames [F][H][W] (uint8 when u8) under d_map [F][9] float64 to d_state
+ * (256-byte aligned, state_bytes >= oflk_mosaic_state_bytes);  d_skip [F] bytes or NULL.  Asynchronous on `stream`. */
+int oflk_mosaic_accumulate(const void *d_frames, int u8, int F, int H, int W, const double *d_map, const unsigned char *d_skip,
+                           int x0, int y0, int Hc, int Wc, int blend, void *d_state, size_t state_bytes, void *stream);
+/* device form, one launch: d_out [Hc][Wc] (uint8 when u8), d_count [Hc][Wc] int32 or NULL.  Asynchronous on `stream`. */
+int oflk_mosaic_resolve(const void *d_state, int Hc, int Wc, int u8, void *d_out, int *d_count, void *stream);
+/* host arrays, synchronous: the frames go up in chunks of at most 64 and are added to one state, which is then resolved;  the
+ * cut does not show.  skip and count may be NULL */
+int oflk_mosaic_composite_host(const float *frames, int F, int H, int W, const double *map, const unsigned char *skip, int x0,
+                               int y0, int Hc, int Wc, int blend, float *out, int *count);
+int oflk_mosaic_composite_host_u8(const unsigned char *frames, int F, int H, int W, const double *map, const unsigned char *skip,
+                                  int x0, int y0, int Hc, int Wc, int blend, unsigned char *out, int *count);
+/* Frames in, mosaic out.  By statement, byte for byte: oflk_pyramidal_sequence_klt_sparse_replenish on the frames,
+ * oflk_tracks_homography on its rows with t0 = 0, oflk_mosaic_chain and oflk_mosaic_canvas, then oflk_mosaic_accumulate of all
+ * frames under from_anchor with skip = dropped and the canvas's x0, y0, and oflk_mosaic_resolve.  Pass 1 is the replenish
+ * call's chunk loop; the fit and the chain run on the rows; the boxes and flags come down for the canvas; pass 2 sends the
+ * frames up again in chunks.  canvas [4] receives x0, y0, Wc, Hc;  out has room for `capacity` pixels: when Wc * Hc exceeds it
+ * the call returns OFLK_ERR_UNSUPPORTED with canvas written, else out (and count) hold [Hc][Wc] packed.  count [capacity],
+ * to_anchor [T][9], held [T-1], dropped [T], model_out [T-1][9], counts_out [T-1][3]: each may be NULL.  The call refuses
+ * whatever its parts refuse, with their codes. */
+int oflk_mosaic_sequence(const float *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
+                         float max_residual, float quality_level, float min_distance, int max_corners, int detect_every,
+                         int hypotheses, float threshold, unsigned seed, int anchor, double extent, int blend, float *out,
+                         size_t capacity, int *canvas, int *count, double *to_anchor, unsigned char *held, unsigned char *dropped,
+                         float *model_out, int *counts_out);
+int oflk_mosaic_sequence_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
+                            float beta, float max_residual, float quality_level, float min_distance, int max_corners,
+                            int detect_every, int hypotheses, float threshold, unsigned seed, int anchor, double extent, int blend,
+                            unsigned char *out, size_t capacity, int *canvas, int *count, double *to_anchor, unsigned char *held,
+                            unsigned char *dropped, float *model_out, int *counts_out);
+
 /* ---- online video stabilisation: a fixed-lag stabiliser on the tracker --------------------------------------------------- */
 /* The statement (tests/stabilize_online_model.py) is the trajectory above, read in the order in which a stream delivers its
  * steps.  The window of frame f is r_f = min(r, f, T-1-f) and reads steps f - r_f .. f + r_f - 1 only, so frame f is final

@@ -13,6 +13,7 @@
 #include "oflk_motion.hpp"
 #include "oflk_homography.hpp"
 #include "oflk_stabilize.hpp"
+#include "oflk_mosaic.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -4038,6 +4039,369 @@ OFLK_API int oflk_stabilize_sequence_u8(const unsigned char *frames, int T, int 
     return stabilize_sequence<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, quality_level,
                                              min_distance, max_corners, detect_every, model, hypotheses, threshold, seed, weights,
                                              radius, out, correction, model_out, counts_out, held);
+}
+
+// =============================================================================
+// video mosaics: the chain of step homographies, the canvas, accumulate and resolve (oflk_mosaic.hpp)
+// =============================================================================
+namespace {
+size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// the three planes of a canvas state in a buffer at `base` (NULL: only the size is wanted)
+struct MosaicLayout {
+    MosaicState st;
+    size_t bytes;
+};
+
+MosaicLayout mosaic_state(void *base, int Hc, int Wc)
+{
+    const size_t Wp = ((size_t)Wc + kMosaicPx - 1) / kMosaicPx * kMosaicPx, n = (size_t)Hc * Wp;
+    const size_t plane64 = round256(n * sizeof(double)), plane32 = round256(n * sizeof(int));
+    char *b = static_cast<char *>(base);
+    MosaicLayout l{};
+    l.st.sum = reinterpret_cast<double *>(b);
+    l.st.wsum = reinterpret_cast<double *>(b + plane64);
+    l.st.count = reinterpret_cast<int *>(b + 2 * plane64);
+    l.st.Wp = (int)Wp;
+    l.bytes = 2 * plane64 + plane32;
+    return l;
+}
+
+int check_mosaic_canvas(int Hc, int Wc)
+{
+    if (Hc < 1 || Wc < 1) return fail(OFLK_ERR_INVALID, "Hc and Wc must be >= 1 (got %d x %d)", Hc, Wc);
+    if ((size_t)Hc * (size_t)Wc >= ((size_t)1 << 30)) return fail(OFLK_ERR_UNSUPPORTED, "a canvas of 2^30 pixels or more is not supported");
+    return OFLK_OK;
+}
+
+int check_mosaic_blend(int blend)
+{
+    if (blend < OFLK_MOSAIC_MEAN || blend > OFLK_MOSAIC_LAST) return fail(OFLK_ERR_INVALID, "unknown blend %d", blend);
+    return OFLK_OK;
+}
+
+int check_mosaic_frames(const void *frames, int F, int H, int W, const void *map, int Hc, int Wc, int blend)
+{
+    if (F < 1) return fail(OFLK_ERR_INVALID, "F must be >= 1 (got %d)", F);
+    if (H < 2 || W < 2) return fail(OFLK_ERR_INVALID, "H and W must be >= 2 (got %d x %d)", H, W);
+    int rc = check_mosaic_canvas(Hc, Wc);
+    if (rc || (rc = check_mosaic_blend(blend))) return rc;
+    if (!frames || !map) return fail(OFLK_ERR_INVALID, "NULL input argument");
+    return check_hw(frames, frames, H, W);
+}
+
+int check_mosaic_chain(const void *model, int T, int anchor, int H, int W, double extent, const void *from_anchor, const void *to_anchor,
+                       const void *box, const void *dropped)
+{
+    if (T < 1) return fail(OFLK_ERR_INVALID, "T must be >= 1 (got %d)", T);
+    if (anchor < 0 || anchor >= T) return fail(OFLK_ERR_INVALID, "anchor must be in [0, %d] (got %d)", T - 1, anchor);
+    if (H < 2 || W < 2) return fail(OFLK_ERR_INVALID, "H and W must be >= 2 (got %d x %d)", H, W);
+    if (!(std::isfinite(extent) && extent > 0.0)) return fail(OFLK_ERR_INVALID, "extent must be finite and > 0 (got %g)", extent);
+    if ((T > 1 && !model) || !from_anchor || !to_anchor || !box || !dropped) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    return OFLK_OK;
+}
+
+// the one launch of the chain on stream s; the arguments are checked
+int mosaic_chain_launch(const float *d_model, const int *d_counts, int T, int anchor, int H, int W, double extent, double *d_from,
+                        double *d_to, double *d_box, unsigned char *d_held, unsigned char *d_dropped, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_mosaic_chain, dim3(1), dim3(kMosaicChainBlock), 0, s, d_model, d_counts, T, anchor, H, W, extent, d_from, d_to,
+                       d_box, d_held, d_dropped);
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+
+// the one launch that adds F frames to the state on stream s; the arguments are checked
+template <class PIX>
+int mosaic_accumulate_launch(const PIX *d_frames, int F, int H, int W, const double *d_map, const unsigned char *d_skip, int x0, int y0,
+                             int Hc, int Wc, int blend, void *d_state, hipStream_t s)
+{
+    MosaicArgs<PIX> a{};
+    a.in = d_frames; a.map = d_map; a.skip = d_skip;
+    a.st = mosaic_state(d_state, Hc, Wc).st;
+    a.F = F; a.H = H; a.W = W;
+    a.x0 = x0; a.y0 = y0; a.Hc = Hc; a.Wc = Wc;
+    a.tiles_x = (Wc + kMosaicTileW - 1) / kMosaicTileW;
+    const dim3 grid((unsigned)a.tiles_x * (unsigned)((Hc + kMosaicBlockH - 1) / kMosaicBlockH));
+    const bool built = with_int<kMosaicMean, kMosaicFeather, kMosaicFirst, kMosaicLast>(blend, [&](auto BLEND) {
+        hipLaunchKernelGGL((k_mosaic_accumulate<PIX, decltype(BLEND)::value>), grid, dim3(256), 0, s, a);
+    });
+    if (!built) return fail(OFLK_ERR_INVALID, "unknown blend %d", blend);
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+
+template <class PIX>
+int mosaic_resolve_launch(void *d_state, int Hc, int Wc, PIX *d_out, int *d_count, hipStream_t s)
+{
+    MosaicResolveArgs<PIX> a{};
+    a.st = mosaic_state(d_state, Hc, Wc).st;
+    a.out = d_out; a.count = d_count; a.Hc = Hc; a.Wc = Wc;
+    const bool vec = Wc % kMosaicPx == 0 && aligned(d_out, (unsigned)(kMosaicPx * sizeof(PIX))) && (!d_count || aligned(d_count, 16));
+    const size_t quads = (size_t)Hc * (size_t)(a.st.Wp / kMosaicPx);
+    const dim3 grid((unsigned)((quads + 255) / 256));
+    if (vec)
+        hipLaunchKernelGGL((k_mosaic_resolve<PIX, true>), grid, dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL((k_mosaic_resolve<PIX, false>), grid, dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+
+// F host frames added to an empty state in chunks through one device buffer, then resolved into the host arrays.  A pixel's
+// samples are added in frame order whatever the cut, so the cut does not show.
+template <class PIX>
+int mosaic_composite_chunks(HostCall &call, const PIX *frames, int F, int H, int W, const double *d_map, const unsigned char *d_skip,
+                            int x0, int y0, int Hc, int Wc, int blend, PIX *out, int *count)
+{
+    const int C = sparse_chunk_pairs(F, H, W);
+    const size_t plane = (size_t)H * W, npix = (size_t)Hc * Wc;
+    const size_t bytes = mosaic_state(nullptr, Hc, Wc).bytes;
+    PIX *d_in = nullptr, *d_out = nullptr;
+    char *d_state = nullptr;
+    int *d_count = nullptr;
+    int rc;
+    if ((rc = call.alloc(&d_in, (size_t)C * plane)) || (rc = call.alloc(&d_state, bytes)) || (rc = call.alloc(&d_out, npix)) ||
+        (rc = call.alloc(&d_count, npix, count != nullptr)))
+        return rc;
+    HIP_TRY(hipMemsetAsync(d_state, 0, bytes, nullptr));
+    for (int f0 = 0; f0 < F; f0 += C) {
+        const int n = std::min(C, F - f0);
+        if ((rc = call.to_device(d_in, frames + (size_t)f0 * plane, (size_t)n * plane)) ||
+            (rc = mosaic_accumulate_launch<PIX>(d_in, n, H, W, d_map + 9 * (size_t)f0, d_skip ? d_skip + f0 : nullptr, x0, y0, Hc, Wc,
+                                                blend, d_state, nullptr)) ||
+            (rc = call.sync()))
+            return rc;
+    }
+    if ((rc = mosaic_resolve_launch<PIX>(d_state, Hc, Wc, d_out, d_count, nullptr)) || (rc = call.to_host(out, d_out, npix)) ||
+        (count && (rc = call.to_host(count, d_count, npix))))
+        return rc;
+    return call.sync();
+}
+
+template <class PIX>
+int mosaic_composite_host(const PIX *frames, int F, int H, int W, const double *map, const unsigned char *skip, int x0, int y0, int Hc,
+                          int Wc, int blend, PIX *out, int *count)
+{
+    int rc = check_mosaic_frames(frames, F, H, W, map, Hc, Wc, blend);
+    if (rc) return rc;
+    if (!out) return fail(OFLK_ERR_INVALID, "NULL output argument");
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    double *d_map = nullptr;
+    unsigned char *d_skip = nullptr;
+    if ((rc = call.upload(&d_map, map, 9 * (size_t)F)) || (skip && (rc = call.upload(&d_skip, skip, (size_t)F)))) return rc;
+    return mosaic_composite_chunks<PIX>(call, frames, F, H, W, d_map, d_skip, x0, y0, Hc, Wc, blend, out, count);
+}
+
+// oflk_mosaic_sequence: pass 1 is the replenish call itself, as in stabilize_sequence; the rows go up again for the
+// homography fit and the chain; the boxes and drop flags come down for the canvas; pass 2 adds the frames chunk by chunk
+template <class PIX>
+int mosaic_sequence(const PIX *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
+                    float max_residual, float q, float md, int K, int detect_every, int hypotheses, float threshold, unsigned seed,
+                    int anchor, double extent, int blend, PIX *out, size_t capacity, int *canvas, int *count, double *to_anchor,
+                    unsigned char *held, unsigned char *dropped, float *model_out, int *counts_out)
+{
+    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
+    if (!canvas) return fail(OFLK_ERR_INVALID, "NULL canvas");
+    int rc = check_warp_affine(frames, T, H, W, frames, out);
+    if (rc || (rc = check_ransac(hypotheses, threshold)) || (rc = check_mosaic_blend(blend)) ||
+        (rc = check_mosaic_chain(frames, T, anchor, H, W, extent, frames, frames, frames, frames)))
+        return rc;
+    if (detect_every < 1) return fail(OFLK_ERR_INVALID, "detect_every must be >= 1 (got %d)", detect_every);
+    if ((rc = check_select(q, md, K)) || (rc = check_sparse_test(alpha, beta, max_residual)) ||
+        (rc = check_sparse_config(H, W, levels, window_size, iters)) || (rc = check_motion_shape(T - 1, K)))
+        return rc;
+    const size_t row = (size_t)K, nT = (size_t)T, S = nT - 1;
+    std::vector<float> tracks;
+    std::vector<unsigned char> visible, born, h_dropped;
+    std::vector<int> detected;
+    std::vector<double> h_box;
+    try {
+        tracks.resize(nT * 2 * row);
+        visible.resize(nT * row);
+        born.resize(nT * row);
+        detected.resize(nT);
+        h_box.resize(4 * nT);
+        h_dropped.resize(nT);
+    } catch (const std::exception &) {
+        return fail(OFLK_ERR_NOMEM, "no host memory for the rows of %d frames of %d slots", T, K);
+    }
+    if ((rc = run_sequence_tracks(Seq{frames, sizeof(PIX) == 1, T, H, W, levels, window_size, iters},
+                                  SparseTracks{{alpha, beta, max_residual}},
+                                  Replenished{{q, md, K, detect_every}, born.data(), detected.data(), nullptr}, K, tracks.data(),
+                                  visible.data())))
+        return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    float *d_tr, *d_model;
+    unsigned char *d_vis, *d_born, *d_inl, *d_held, *d_drop;
+    char *d_ws;
+    int *d_cnt;
+    double *d_from, *d_to, *d_box;
+    if ((rc = call.upload(&d_tr, (const float *)tracks.data(), nT * 2 * row)) ||
+        (rc = call.upload(&d_vis, (const unsigned char *)visible.data(), nT * row)) ||
+        (rc = call.upload(&d_born, (const unsigned char *)born.data(), nT * row)) ||
+        (rc = call.alloc(&d_ws, motion_ws(nullptr, T - 1, K, hypotheses, 9).bytes)) || (rc = call.alloc(&d_model, 9 * S)) ||
+        (rc = call.alloc(&d_inl, S * row)) || (rc = call.alloc(&d_cnt, 3 * S)) || (rc = call.alloc(&d_from, 9 * nT)) ||
+        (rc = call.alloc(&d_to, 9 * nT)) || (rc = call.alloc(&d_box, 4 * nT)) || (rc = call.alloc(&d_held, S)) ||
+        (rc = call.alloc(&d_drop, nT)))
+        return rc;
+    const MotionIn in{d_tr, d_tr + 2 * row, d_vis, d_vis + row, d_born + row};
+    if ((rc = homography_launch(in, T - 1, K, 0u, hypotheses, threshold, seed, motion_ws(d_ws, T - 1, K, hypotheses, 9), d_model, d_inl,
+                                d_cnt, nullptr)) ||
+        (rc = mosaic_chain_launch(d_model, d_cnt, T, anchor, H, W, extent, d_from, d_to, d_box, d_held, d_drop, nullptr)))
+        return rc;
+    if ((rc = call.to_host(h_box.data(), d_box, 4 * nT)) || (rc = call.to_host(h_dropped.data(), d_drop, nT)) ||
+        (to_anchor && (rc = call.to_host(to_anchor, d_to, 9 * nT))) || (held && (rc = call.to_host(held, d_held, S))) ||
+        (model_out && (rc = call.to_host(model_out, d_model, 9 * S))) || (counts_out && (rc = call.to_host(counts_out, d_cnt, 3 * S))) ||
+        (rc = call.sync()))
+        return rc;
+    if (dropped) std::memcpy(dropped, h_dropped.data(), nT);
+    if ((rc = oflk_mosaic_canvas(h_box.data(), h_dropped.data(), T, &canvas[0], &canvas[1], &canvas[2], &canvas[3]))) return rc;
+    const int x0 = canvas[0], y0 = canvas[1], Wc = canvas[2], Hc = canvas[3];
+    if ((rc = check_mosaic_canvas(Hc, Wc))) return rc;
+    if ((size_t)Hc * (size_t)Wc > capacity)
+        return fail(OFLK_ERR_UNSUPPORTED, "the canvas of %d x %d pixels at (%d, %d) exceeds the capacity of %zu pixels", Wc, Hc, x0, y0,
+                    capacity);
+    return mosaic_composite_chunks<PIX>(call, frames, T, H, W, d_from, d_drop, x0, y0, Hc, Wc, blend, out, count);
+}
+}  // namespace
+
+OFLK_API size_t oflk_mosaic_state_bytes(int Hc, int Wc)
+{
+    if (Hc < 1 || Wc < 1 || (size_t)Hc * (size_t)Wc >= ((size_t)1 << 30)) return 0;
+    return mosaic_state(nullptr, Hc, Wc).bytes;
+}
+
+OFLK_API int oflk_mosaic_chain(const float *d_model, const int *d_counts, int T, int anchor, int H, int W, double extent,
+                               double *d_from_anchor, double *d_to_anchor, double *d_box, unsigned char *d_held,
+                               unsigned char *d_dropped, void *stream)
+{
+    if (int rc = check_mosaic_chain(d_model, T, anchor, H, W, extent, d_from_anchor, d_to_anchor, d_box, d_dropped)) return rc;
+    if (!aligned(d_from_anchor, 8) || !aligned(d_to_anchor, 8) || !aligned(d_box, 8))
+        return fail(OFLK_ERR_INVALID, "d_from_anchor, d_to_anchor and d_box must be 8-byte aligned");
+    return mosaic_chain_launch(d_model, d_counts, T, anchor, H, W, extent, d_from_anchor, d_to_anchor, d_box, d_held, d_dropped,
+                               (hipStream_t)stream);
+}
+
+OFLK_API int oflk_mosaic_chain_host(const float *model, const int *counts, int T, int anchor, int H, int W, double extent,
+                                    double *from_anchor, double *to_anchor, double *box, unsigned char *held, unsigned char *dropped)
+{
+    int rc = check_mosaic_chain(model, T, anchor, H, W, extent, from_anchor, to_anchor, box, dropped);
+    if (rc) return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const size_t nT = (size_t)T, S = nT - 1;
+    float *d_model = nullptr;
+    int *d_cnt = nullptr;
+    double *d_from, *d_to, *d_box;
+    unsigned char *d_held, *d_drop;
+    if ((S && (rc = call.upload(&d_model, model, 9 * S))) || (S && counts && (rc = call.upload(&d_cnt, counts, 3 * S))) ||
+        (rc = call.alloc(&d_from, 9 * nT)) || (rc = call.alloc(&d_to, 9 * nT)) || (rc = call.alloc(&d_box, 4 * nT)) ||
+        (rc = call.alloc(&d_held, S, held && S)) || (rc = call.alloc(&d_drop, nT)))
+        return rc;
+    if ((rc = mosaic_chain_launch(d_model, d_cnt, T, anchor, H, W, extent, d_from, d_to, d_box, d_held, d_drop, nullptr))) return rc;
+    if ((rc = call.to_host(from_anchor, d_from, 9 * nT)) || (rc = call.to_host(to_anchor, d_to, 9 * nT)) ||
+        (rc = call.to_host(box, d_box, 4 * nT)) || (d_held && (rc = call.to_host(held, d_held, S))) ||
+        (rc = call.to_host(dropped, d_drop, nT)))
+        return rc;
+    return call.sync();
+}
+
+OFLK_API int oflk_mosaic_canvas(const double *box, const unsigned char *dropped, int T, int *x0, int *y0, int *Wc, int *Hc)
+{
+    if (T < 1) return fail(OFLK_ERR_INVALID, "T must be >= 1 (got %d)", T);
+    if (!box || !dropped || !x0 || !y0 || !Wc || !Hc) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    double lo[2] = {INFINITY, INFINITY}, hi[2] = {-INFINITY, -INFINITY};
+    bool any = false;
+    for (int t = 0; t < T; t++) {
+        if (dropped[t]) continue;
+        const double *b = box + 4 * (size_t)t;
+        for (int k = 0; k < 4; k++)
+            if (!std::isfinite(b[k])) return fail(OFLK_ERR_INVALID, "box[%d] of a frame that is not dropped is not finite", t);
+        any = true;
+        for (int k = 0; k < 2; k++) {
+            lo[k] = std::min(lo[k], b[k]);
+            hi[k] = std::max(hi[k], b[2 + k]);
+        }
+    }
+    if (!any) return fail(OFLK_ERR_INVALID, "every frame is dropped");
+    const double lim = (double)(1 << 30);
+    for (int k = 0; k < 2; k++) {
+        lo[k] = std::floor(lo[k]);
+        hi[k] = std::ceil(hi[k]);
+        if (!(lo[k] > -lim && hi[k] < lim && hi[k] >= lo[k]))
+            return fail(OFLK_ERR_UNSUPPORTED, "a canvas from %g to %g is not supported", lo[k], hi[k]);
+    }
+    *x0 = (int)lo[0];
+    *y0 = (int)lo[1];
+    *Wc = (int)(hi[0] - lo[0]) + 1;
+    *Hc = (int)(hi[1] - lo[1]) + 1;
+    return OFLK_OK;
+}
+
+OFLK_API int oflk_mosaic_accumulate(const void *d_frames, int u8, int F, int H, int W, const double *d_map, const unsigned char *d_skip,
+                                    int x0, int y0, int Hc, int Wc, int blend, void *d_state, size_t state_bytes, void *stream)
+{
+    if (int rc = check_mosaic_frames(d_frames, F, H, W, d_map, Hc, Wc, blend)) return rc;
+    if (!d_state) return fail(OFLK_ERR_INVALID, "NULL d_state");
+    if (!aligned(d_map, 8)) return fail(OFLK_ERR_INVALID, "d_map must be 8-byte aligned");
+    if (!u8 && !aligned(d_frames, 4)) return fail(OFLK_ERR_INVALID, "float32 frames must be 4-byte aligned");
+    const size_t need = mosaic_state(nullptr, Hc, Wc).bytes;
+    if (state_bytes < need) return fail(OFLK_ERR_INVALID, "state of %zu bytes, %zu needed (oflk_mosaic_state_bytes)", state_bytes, need);
+    if (!aligned(d_state, 256)) return fail(OFLK_ERR_INVALID, "d_state must be 256-byte aligned");
+    return u8 ? mosaic_accumulate_launch<unsigned char>((const unsigned char *)d_frames, F, H, W, d_map, d_skip, x0, y0, Hc, Wc, blend,
+                                                        d_state, (hipStream_t)stream)
+              : mosaic_accumulate_launch<float>((const float *)d_frames, F, H, W, d_map, d_skip, x0, y0, Hc, Wc, blend, d_state,
+                                                (hipStream_t)stream);
+}
+
+OFLK_API int oflk_mosaic_resolve(const void *d_state, int Hc, int Wc, int u8, void *d_out, int *d_count, void *stream)
+{
+    if (int rc = check_mosaic_canvas(Hc, Wc)) return rc;
+    if (!d_state || !d_out) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    if (!aligned(d_state, 256)) return fail(OFLK_ERR_INVALID, "d_state must be 256-byte aligned");
+    if ((!u8 && !aligned(d_out, 4)) || (d_count && !aligned(d_count, 4)))
+        return fail(OFLK_ERR_INVALID, "float32 output and d_count must be 4-byte aligned");
+    void *st = const_cast<void *>(d_state);   // read only
+    return u8 ? mosaic_resolve_launch<unsigned char>(st, Hc, Wc, (unsigned char *)d_out, d_count, (hipStream_t)stream)
+              : mosaic_resolve_launch<float>(st, Hc, Wc, (float *)d_out, d_count, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_mosaic_composite_host(const float *frames, int F, int H, int W, const double *map, const unsigned char *skip, int x0,
+                                        int y0, int Hc, int Wc, int blend, float *out, int *count)
+{
+    return mosaic_composite_host<float>(frames, F, H, W, map, skip, x0, y0, Hc, Wc, blend, out, count);
+}
+
+OFLK_API int oflk_mosaic_composite_host_u8(const unsigned char *frames, int F, int H, int W, const double *map,
+                                           const unsigned char *skip, int x0, int y0, int Hc, int Wc, int blend, unsigned char *out,
+                                           int *count)
+{
+    return mosaic_composite_host<unsigned char>(frames, F, H, W, map, skip, x0, y0, Hc, Wc, blend, out, count);
+}
+
+OFLK_API int oflk_mosaic_sequence(const float *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
+                                  float beta, float max_residual, float quality_level, float min_distance, int max_corners,
+                                  int detect_every, int hypotheses, float threshold, unsigned seed, int anchor, double extent,
+                                  int blend, float *out, size_t capacity, int *canvas, int *count, double *to_anchor,
+                                  unsigned char *held, unsigned char *dropped, float *model_out, int *counts_out)
+{
+    return mosaic_sequence<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, quality_level, min_distance,
+                                  max_corners, detect_every, hypotheses, threshold, seed, anchor, extent, blend, out, capacity, canvas,
+                                  count, to_anchor, held, dropped, model_out, counts_out);
+}
+
+OFLK_API int oflk_mosaic_sequence_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                     float alpha, float beta, float max_residual, float quality_level, float min_distance,
+                                     int max_corners, int detect_every, int hypotheses, float threshold, unsigned seed, int anchor,
+                                     double extent, int blend, unsigned char *out, size_t capacity, int *canvas, int *count,
+                                     double *to_anchor, unsigned char *held, unsigned char *dropped, float *model_out, int *counts_out)
+{
+    return mosaic_sequence<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, quality_level,
+                                          min_distance, max_corners, detect_every, hypotheses, threshold, seed, anchor, extent, blend,
+                                          out, capacity, canvas, count, to_anchor, held, dropped, model_out, counts_out);
 }
 
 // =============================================================================

@@ -138,6 +138,16 @@ SIGNATURES = {
     "oflk_warp_perspective_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [_f64p, _vp, _vp]),
     "oflk_stabilize_sequence": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int, _f32p, _f32p, _f32p, _i32p, _vp]),
     "oflk_stabilize_sequence_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int, _vp, _f32p, _f32p, _i32p, _vp]),
+    "oflk_mosaic_chain": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 4 + [ctypes.c_double] + [_vp] * 6),
+    "oflk_mosaic_chain_host": (ctypes.c_int, [_f32p, _i32p] + [ctypes.c_int] * 4 + [ctypes.c_double, _f64p, _f64p, _f64p, _vp, _vp]),
+    "oflk_mosaic_canvas": (ctypes.c_int, [_f64p, _vp, ctypes.c_int] + [_i32p] * 4),
+    "oflk_mosaic_state_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
+    "oflk_mosaic_accumulate": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_vp, _vp] + [ctypes.c_int] * 5 + [_vp, ctypes.c_size_t, _vp]),
+    "oflk_mosaic_resolve": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [_vp] * 3),
+    "oflk_mosaic_composite_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 3 + [_f64p, _vp] + [ctypes.c_int] * 5 + [_f32p, _i32p]),
+    "oflk_mosaic_composite_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [_f64p, _vp] + [ctypes.c_int] * 5 + [_vp, _i32p]),
+    "oflk_mosaic_sequence": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_uint, ctypes.c_int, ctypes.c_double, ctypes.c_int, _f32p, ctypes.c_size_t, _i32p, _i32p, _f64p, _vp, _vp, _f32p, _i32p]),
+    "oflk_mosaic_sequence_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_uint, ctypes.c_int, ctypes.c_double, ctypes.c_int, _vp, ctypes.c_size_t, _i32p, _i32p, _f64p, _vp, _vp, _f32p, _i32p]),
     "oflk_stabilize_trajectory_ring": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 4 + [_f64p, ctypes.c_int, _vp, _vp, _vp]),
     "oflk_stabilizer_create": (ctypes.c_int, [ctypes.POINTER(_vp)] + [ctypes.c_int] * 7 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int]),
     "oflk_stabilizer_destroy": (ctypes.c_int, [_vp]),
@@ -774,6 +784,76 @@ def warp_affine_host(frames: np.ndarray, maps: np.ndarray, inside: bool = False)
     check(fn(frames.ctypes.data if u8 else ptr(frames), F, H, W, _f64(maps), out.ctypes.data if u8 else ptr(out),
              None if ins is None else ins.ctypes.data))
     return out, ins
+
+
+MOSAIC_BLENDS = {"mean": 0, "feather": 1, "first": 2, "last": 3}
+
+
+def check_mosaic_blend(blend) -> int:
+    """the C ABI's code of a blend given by name; ValueError for anything else"""
+    if not isinstance(blend, str) or blend not in MOSAIC_BLENDS:
+        raise ValueError(f"blend must be one of {sorted(MOSAIC_BLENDS)}, got {blend!r}")
+    return MOSAIC_BLENDS[blend]
+
+
+def mosaic_state_bytes(Hc: int, Wc: int) -> int:
+    """bytes of the canvas state of oflk_mosaic_accumulate / oflk_mosaic_resolve (0: the canvas is refused)"""
+    return int(lib().oflk_mosaic_state_bytes(int(Hc), int(Wc)))
+
+
+def mosaic_chain(d_model: int, d_counts: int, T: int, anchor: int, H: int, W: int, extent: float, d_from_anchor: int, d_to_anchor: int,
+                 d_box: int, d_held: int, d_dropped: int, stream: int = 0) -> None:
+    """oflk_mosaic_chain on device pointers: d_model [T-1][9] float32, d_counts [T-1][3] int32 or 0 -> d_from_anchor, d_to_anchor
+    [T][9] float64, d_box [T][4] float64, d_held [T-1] uint8 or 0, d_dropped [T] uint8; asynchronous."""
+    check(lib().oflk_mosaic_chain(d_model or None, d_counts or None, int(T), int(anchor), int(H), int(W), float(extent),
+                                  d_from_anchor or None, d_to_anchor or None, d_box or None, d_held or None, d_dropped or None, stream))
+
+
+def mosaic_chain_host(model: np.ndarray, counts: Optional[np.ndarray], T: int, anchor: int, H: int, W: int, extent: float):
+    """oflk_mosaic_chain_host: contiguous float32 (T-1, 9) models and optional int32 (T-1, 3) counts in; (from_anchor (T, 9),
+    to_anchor (T, 9), box (T, 4) float64, held (T-1,), dropped (T,) uint8) out"""
+    fr, to, box = np.empty((T, 9), np.float64), np.empty((T, 9), np.float64), np.empty((T, 4), np.float64)
+    held, drop = np.empty(max(T - 1, 0), np.uint8), np.empty(T, np.uint8)
+    check(lib().oflk_mosaic_chain_host(ptr(model) if T > 1 else None, None if counts is None or T < 2 else counts.ctypes.data_as(_i32p),
+                                       int(T), int(anchor), int(H), int(W), float(extent), _f64(fr), _f64(to), _f64(box),
+                                       held.ctypes.data if T > 1 else None, drop.ctypes.data))
+    return fr, to, box, held, drop
+
+
+def mosaic_canvas(box: np.ndarray, dropped: np.ndarray):
+    """oflk_mosaic_canvas (host only): (x0, y0, Wc, Hc) of the boxes that are not dropped"""
+    box, dropped = np.ascontiguousarray(box, np.float64), np.ascontiguousarray(dropped, np.uint8)
+    v = [ctypes.c_int() for _ in range(4)]
+    check(lib().oflk_mosaic_canvas(_f64(box), dropped.ctypes.data, int(dropped.size), *[ctypes.byref(c) for c in v]))
+    return tuple(int(c.value) for c in v)
+
+
+def mosaic_accumulate(d_frames: int, F: int, H: int, W: int, d_map: int, d_skip: int, x0: int, y0: int, Hc: int, Wc: int, blend: int,
+                      d_state: int, state_bytes: int, u8: bool = False, stream: int = 0) -> None:
+    """oflk_mosaic_accumulate on device pointers: adds d_frames [F][H][W] (float32, or uint8 with u8) under d_map [F][9] float64
+    (d_skip [F] uint8 or 0) to the canvas state d_state; asynchronous."""
+    check(lib().oflk_mosaic_accumulate(d_frames or None, int(bool(u8)), int(F), int(H), int(W), d_map or None, d_skip or None, int(x0),
+                                       int(y0), int(Hc), int(Wc), int(blend), d_state or None, int(state_bytes), stream))
+
+
+def mosaic_resolve(d_state: int, Hc: int, Wc: int, d_out: int, d_count: int = 0, u8: bool = False, stream: int = 0) -> None:
+    """oflk_mosaic_resolve on device pointers: d_out [Hc][Wc] (float32, or uint8 with u8), d_count [Hc][Wc] int32 or 0;
+    asynchronous."""
+    check(lib().oflk_mosaic_resolve(d_state or None, int(Hc), int(Wc), int(bool(u8)), d_out or None, d_count or None, stream))
+
+
+def mosaic_composite_host(frames: np.ndarray, maps: np.ndarray, skip: Optional[np.ndarray], x0: int, y0: int, Hc: int, Wc: int,
+                          blend: int, count: bool = False):
+    """oflk_mosaic_composite_host[_u8]: contiguous (F, H, W) float32 or uint8 frames, (F, 9) float64 maps and optional (F,) uint8
+    skip flags in; the (Hc, Wc) mosaic and, when asked for, the int32 count (else None) out"""
+    F, H, W = frames.shape
+    u8 = frames.dtype == np.uint8
+    out = np.empty((Hc, Wc), frames.dtype)
+    cnt = np.empty((Hc, Wc), np.int32) if count else None
+    fn = lib().oflk_mosaic_composite_host_u8 if u8 else lib().oflk_mosaic_composite_host
+    check(fn(frames.ctypes.data if u8 else ptr(frames), F, H, W, _f64(maps), None if skip is None else skip.ctypes.data, int(x0), int(y0),
+             int(Hc), int(Wc), int(blend), out.ctypes.data if u8 else ptr(out), None if cnt is None else cnt.ctypes.data_as(_i32p)))
+    return out, cnt
 
 
 class Tracker:

@@ -420,3 +420,84 @@ def warp_perspective(frames, maps, return_inside: bool = False):
     if not return_inside:
         return out
     return out, (ins[0] if single else ins).astype(bool)
+
+
+class MosaicChain(NamedTuple):
+    """The step homographies of a sequence composed from an anchor frame (mosaic_chain)."""
+    from_anchor: np.ndarray   # (T, 3, 3) float64: anchor coordinates to frame t's: what mosaic_composite takes
+    to_anchor: np.ndarray     # (T, 3, 3) float64: frame t's coordinates to the anchor's; a chain of its own, not an inversion
+    box: np.ndarray           # (T, 4) float64 (xmin, ymin, xmax, ymax) of frame t's corners in anchor coordinates; NaN where dropped
+    held: np.ndarray          # (T-1,) bool: the step could not be used and counts as no motion
+    dropped: np.ndarray       # (T,) bool: the frame cannot be placed (behind the camera, not finite, beyond extent), or lies past one
+    origin: tuple             # (x0, y0): the anchor coordinates of canvas pixel (0, 0)
+    canvas_shape: tuple       # (Hc, Wc): the canvas that holds every frame that is not dropped
+
+
+def mosaic_chain(model, status, shape, anchor: int = 0, extent=None) -> MosaicChain:
+    """Every frame of a sequence placed in the coordinates of one anchor frame, on the GPU: the T-1 step models of
+    tracks_homography composed forwards and backwards from frame `anchor`.
+
+    model: (T-1, 3, 3) or (T-1, 9) float32, step s mapping frame s to frame s+1 (an empty array: T = 1); status: (T-1,) or None
+    -- a step with status 0 is held (taken as no motion), like one that is not finite or singular; shape: (H, W) of the frames.
+    A frame whose corners land behind the camera, are not finite or lie more than `extent` (default 8 max(H, W)) from the
+    anchor's origin is dropped, and so is every frame beyond it; the anchor never is.  The same inputs give the same bytes;
+    the statement is in include/oflk.h."""
+    if len(shape) != 2 or int(shape[0]) < 2 or int(shape[1]) < 2:
+        raise ValueError(f"shape must be (H, W) with H, W >= 2, got {shape!r}")
+    H, W = int(shape[0]), int(shape[1])
+    m = np.ascontiguousarray(model, np.float32)
+    if m.ndim == 3 and m.shape[1:] == (3, 3):
+        m = m.reshape(-1, 9)
+    if m.ndim != 2 or m.shape[1] != 9:
+        if m.size:
+            raise ValueError(f"expected models of shape (T-1, 3, 3) or (T-1, 9), got {np.shape(model)}")
+        m = m.reshape(0, 9)
+    S = m.shape[0]
+    if isinstance(anchor, bool) or int(anchor) != anchor or not 0 <= int(anchor) <= S:
+        raise ValueError(f"anchor must be an integer in [0, {S}], got {anchor!r}")
+    extent = 8.0 * max(H, W) if extent is None else float(extent)
+    if not (np.isfinite(extent) and extent > 0):
+        raise ValueError(f"extent must be finite and > 0, got {extent!r}")
+    counts = None
+    if status is not None:
+        st = np.asarray(status)
+        if st.shape != (S,):
+            raise ValueError(f"status must have shape {(S,)}, got {st.shape}")
+        counts = np.zeros((S, 3), np.int32)
+        counts[:, 2] = st != 0
+    fr, to, box, held, drop = _oflk.mosaic_chain_host(m, counts, S + 1, int(anchor), H, W, extent)
+    x0, y0, Wc, Hc = _oflk.mosaic_canvas(box, drop)
+    return MosaicChain(fr.reshape(-1, 3, 3), to.reshape(-1, 3, 3), box, held.astype(bool), drop.astype(bool), (x0, y0), (Hc, Wc))
+
+
+def mosaic_composite(frames, maps, canvas_shape, origin=(0, 0), skip=None, blend: str = "mean", return_count: bool = False):
+    """Blend frames onto one canvas, on the GPU.  Canvas pixel (x, y) has the coordinates (origin[0] + x, origin[1] + y); frame
+    f covers it where maps[f] (3 x 3, canvas coordinates to frame f's, e.g. MosaicChain.from_anchor) takes it inside the
+    frame, and contributes its bilinear sample there.  blend: "mean"; "feather" (each sample weighted by one plus its distance
+    from the frame's nearest edge); "first" / "last" (the lowest / highest frame that covers the pixel).  frames: (F, H, W)
+    float32 or uint8 (uint8 out: rounded half to even); skip: (F,) flags of frames to leave out, e.g. MosaicChain.dropped.
+    Returns the (Hc, Wc) canvas, zero where no frame reaches; with return_count also the (Hc, Wc) int32 number of frames that
+    cover each pixel."""
+    arr, _ = _oflk.as_frames(frames)
+    F, H, W = arr.shape
+    if H < 2 or W < 2:
+        raise ValueError(f"frames must be at least 2 x 2, got {H} x {W}")
+    code = _oflk.check_mosaic_blend(blend)
+    if len(canvas_shape) != 2 or int(canvas_shape[0]) < 1 or int(canvas_shape[1]) < 1:
+        raise ValueError(f"canvas_shape must be (Hc, Wc) with Hc, Wc >= 1, got {canvas_shape!r}")
+    Hc, Wc = int(canvas_shape[0]), int(canvas_shape[1])
+    if Hc * Wc >= 2 ** 30:
+        raise ValueError(f"a canvas of 2^30 pixels or more is not supported, got {Hc} x {Wc}")
+    if len(origin) != 2 or any(isinstance(v, bool) or int(v) != v or abs(int(v)) >= 2 ** 31 for v in origin):
+        raise ValueError(f"origin must be two integers (x0, y0), got {origin!r}")
+    m = np.ascontiguousarray(maps, np.float64)
+    if m.size != 9 * F or m.ndim not in (1, 2, 3) or m.shape[-1] not in (3, 9) or (m.shape[-1] == 3 and (m.ndim < 2 or m.shape[-2] != 3)):
+        raise ValueError(f"expected {F} maps of shape (3, 3) or (9,), got {np.shape(maps)}")
+    sk = None
+    if skip is not None:
+        sk = np.asarray(skip)
+        if sk.shape != (F,):
+            raise ValueError(f"skip must have shape {(F,)}, got {sk.shape}")
+        sk = np.ascontiguousarray(sk != 0, np.uint8)
+    out, cnt = _oflk.mosaic_composite_host(arr, m.reshape(F, 9), sk, int(origin[0]), int(origin[1]), Hc, Wc, code, bool(return_count))
+    return (out, cnt) if return_count else out

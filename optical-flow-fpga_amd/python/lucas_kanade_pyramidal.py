@@ -30,9 +30,9 @@ import numpy as np
 import numpy.typing as npt
 
 import _oflk
-from lucas_kanade_core import (Homography, Motion, Trajectory, estimate_homography, estimate_motion,  # noqa: F401
-                               lucas_kanade_single_scale, stabilize_trajectory, tracks_homography, tracks_motion, warp_affine,
-                               warp_perspective)
+from lucas_kanade_core import (Homography, MosaicChain, Motion, Trajectory, estimate_homography, estimate_motion,  # noqa: F401
+                               lucas_kanade_single_scale, mosaic_chain, mosaic_composite, stabilize_trajectory, tracks_homography,
+                               tracks_motion, warp_affine, warp_perspective)
 
 SCRIPT_DIR = Path(__file__).resolve().parent
 PROJECT_ROOT = SCRIPT_DIR.parent
@@ -499,6 +499,62 @@ def lucas_kanade_pyramidal_sequence_stabilize(frames, max_corners: int, detect_e
                    out.ctypes.data if u8 else _oflk.ptr(out), _oflk.ptr(corr), _oflk.ptr(mod), cnt.ctypes.data_as(_oflk._i32p),
                    held.ctypes.data))
     return SequenceStabilized(out, corr.reshape(T, 2, 3), mod.reshape(T - 1, 2, 3), cnt[:, 2].copy(), held.astype(bool))
+
+
+class Mosaic(NamedTuple):
+    """Result of lucas_kanade_pyramidal_sequence_mosaic."""
+    canvas: np.ndarray      # (Hc, Wc), the input's type: the blended frames in the anchor's coordinates, zero where none reaches
+    count: np.ndarray       # (Hc, Wc) int32: the number of frames that cover each pixel
+    origin: tuple           # (x0, y0): the anchor coordinates of canvas pixel (0, 0)
+    to_anchor: np.ndarray   # (T, 3, 3) float64: frame t's coordinates to the anchor's (MosaicChain.to_anchor)
+    held: np.ndarray        # (T-1,) bool: the step counted as no motion
+    dropped: np.ndarray     # (T,) bool: the frame was left out
+    model: np.ndarray       # (T-1, 3, 3) float32: the fitted homography of step t -> t+1; NaN where status is 0
+    status: np.ndarray      # (T-1,) int32: 1 where a model was found
+
+
+def lucas_kanade_pyramidal_sequence_mosaic(frames, max_corners: int = 1000, detect_every: int = 4, hypotheses: int = 256,
+                                           threshold: float = 1.0, seed: int = 0, quality_level: float = 0.01,
+                                           min_distance: float = 10.0, num_levels: int = 3, window_size: int = 5,
+                                           num_iterations: int = 3, alpha: float = 0.01, beta: float = 0.5, max_residual: float = 4.0,
+                                           anchor: int = 0, extent=None, blend: str = "feather", max_pixels=None) -> Mosaic:
+    """Frames in, one picture out: lucas_kanade_pyramidal_sequence_klt_sparse_replenish on the frames, tracks_homography on its
+    rows, mosaic_chain from frame `anchor`, and mosaic_composite of every frame that is not dropped, in one call whose
+    intermediate rows stay in the library.  The frames go up twice, chunk by chunk (once to track, once to blend).  The canvas
+    is as large as the camera's path makes it; a canvas of more than max_pixels (default 16 H W) pixels raises OflkError with
+    the size it needed in the message."""
+    a, b = _oflk.check_fb_params(alpha, beta)
+    arr, u8 = _oflk.as_sequence(frames)
+    T, H, W = arr.shape
+    if H < 2 or W < 2:
+        raise ValueError(f"frames must be at least 2 x 2, got {H} x {W}")
+    L, win, it, r = _oflk.check_sparse_params((H, W), num_levels, window_size, num_iterations, max_residual)
+    K, q, md, win = _oflk.check_feature_params(max_corners, quality_level, min_distance, win)
+    if isinstance(detect_every, bool) or int(detect_every) != detect_every or int(detect_every) < 1:
+        raise ValueError(f"detect_every must be an integer >= 1, got {detect_every!r}")
+    hn, thr, sd = _oflk.check_ransac_params(hypotheses, threshold, seed)
+    code = _oflk.check_mosaic_blend(blend)
+    if isinstance(anchor, bool) or int(anchor) != anchor or not 0 <= int(anchor) < T:
+        raise ValueError(f"anchor must be an integer in [0, {T - 1}], got {anchor!r}")
+    extent = 8.0 * max(H, W) if extent is None else float(extent)
+    if not (np.isfinite(extent) and extent > 0):
+        raise ValueError(f"extent must be finite and > 0, got {extent!r}")
+    cap = 16 * H * W if max_pixels is None else max_pixels
+    if isinstance(cap, bool) or int(cap) != cap or int(cap) < 1:
+        raise ValueError(f"max_pixels must be an integer >= 1, got {max_pixels!r}")
+    cap = min(int(cap), 2 ** 30 - 1)
+    out, cnt = np.empty(cap, arr.dtype), np.empty(cap, np.int32)
+    canvas = np.zeros(4, np.int32)
+    to, mod = np.empty((T, 9), np.float64), np.empty((T - 1, 9), np.float32)
+    counts, held, drop = np.empty((T - 1, 3), np.int32), np.empty(T - 1, np.uint8), np.empty(T, np.uint8)
+    fn = _oflk.lib().oflk_mosaic_sequence_u8 if u8 else _oflk.lib().oflk_mosaic_sequence
+    _oflk.check(fn(arr.ctypes.data if u8 else _oflk.ptr(arr), T, H, W, L, win, it, a, b, r, q, md, K,
+                   min(int(detect_every), 2 ** 31 - 1), hn, thr, sd, int(anchor), extent, code,
+                   out.ctypes.data if u8 else _oflk.ptr(out), cap, canvas.ctypes.data_as(_oflk._i32p), cnt.ctypes.data_as(_oflk._i32p),
+                   _oflk._f64(to), held.ctypes.data, drop.ctypes.data, _oflk.ptr(mod), counts.ctypes.data_as(_oflk._i32p)))
+    x0, y0, Wc, Hc = (int(v) for v in canvas)
+    return Mosaic(out[:Hc * Wc].reshape(Hc, Wc).copy(), cnt[:Hc * Wc].reshape(Hc, Wc).copy(), (x0, y0), to.reshape(T, 3, 3),
+                  held.astype(bool), drop.astype(bool), mod.reshape(T - 1, 3, 3), counts[:, 2].copy())
 
 
 class TrackerRow(NamedTuple):

@@ -784,6 +784,83 @@ int oflk_mosaic_sequence_u8(const unsigned char *frames, int T, int H, int W, in
                             unsigned char *out, size_t capacity, int *canvas, int *count, double *to_anchor, unsigned char *held,
                             unsigned char *dropped, float *model_out, int *counts_out);
 
+/* ---- direct image alignment: step models refined on pixel intensities -------------------------------------------------- */
+/* The statement (tests/align_model.py).  Inverse-compositional Lucas-Kanade registration of frame B to the template A over the
+ * whole frame, coarse to fine, from a given step model (the RANSAC fits': model[t] maps frame t's coordinates to frame t+1's,
+ * as oflk_warp_perspective(frames[t+1], model[t]) reads it).  The residual at pixel x of A is r(x) = B(M x) - A(x).  Every
+ * operation is float64 unless stated and rounded on its own, in the order written; nothing is contracted, there is no atomic
+ * and no result depends on the launch geometry or on how the steps are cut into calls.  The device equals it byte for byte, a
+ * NaN equal to a NaN.  L = levels, n = iterations, NP = 6 parameters (OFLK_ALIGN_AFFINE, six float32 [a00 a01 tx; a10 a11 ty])
+ * or 8 (OFLK_ALIGN_HOMOGRAPHY, nine float32 with [2][2] == 1);  both are carried as nine float64, an affine model with the
+ * third row (0, 0, 1).
+ *   refused step   status_in[s] == 0 or a model entry that is not finite: the model's bytes, status 0, stats four zeros
+ *   pyramids       oflk_build_pyramid's levels (scale 0.5) of A and B as float32, uint8 frames converted first;  level 0 is
+ *                  the coarsest, level L-1 the frame;  level l has H_l x W_l pixels
+ *   sums(l, M)     for every pixel (x, y) of level l:  w = (m6 x + m7 y) + m8;  xs = ((m0 x + m1 y) + m2) / w;
+ *                  ys = ((m3 x + m4 y) + m5) / w (the perspective warp's);  counted = w > 0 and 0 <= xs <= W_l - 1 and
+ *                  0 <= ys <= H_l - 1, a NaN anywhere meaning not counted;  r = f64(sample(B_l, xs, ys) - A_l[y][x]), the
+ *                  difference in float32;  Gx, Gy = oflk_compute_gradients(A_l, A_l)'s Ix, Iy as float64 (Sobel / 8, the
+ *                  border clamped; a true convolution, so minus the derivatives);  xh = (x - cx) / s, yh = (y - cy) / s with
+ *                  cx = (W_l - 1) / 2, cy = (H_l - 1) / 2, s = max(W_l, H_l) / 2;
+ *                  sd = [Gx xh, Gx yh, Gx, Gy xh, Gy yh, Gy, -(t xh), -(t yh)], t = sd[0] + sd[4] (affine: the first six).
+ *                  The NS = NP (NP + 1) / 2 + NP + 2 sums over the counted pixels (46 or 29):  sd[i] sd[j] for i = 0 .. NP-1,
+ *                  j = i .. NP-1;  sd[i] r;  r r;  1.0 (the count)
+ *   order          the level is cut into tiles of 64 columns by 32 rows from the origin.  In a tile, a column's partial starts
+ *                  at +0.0 and adds its counted pixels top to bottom;  the 64 partials are combined by the motion fit's tree
+ *                  (for stride 32, 16, .., 1: partial[c] += partial[c + stride] for c < stride);  the total starts at +0.0
+ *                  and adds the tile sums one after another in raster order
+ *   before         e0 / c0, the r r sum and the count of sums(L-1, M) under the input model
+ *   level l        for l = 0 .. L-1, unless the step is frozen:  sx = W_l / W, sy = H_l / H;  M_l = D M D^-1:
+ *                  [m0, (m1 sx) / sy, m2 sx;  (m3 sy) / sx, m4, m5 sy;  m6 / sx, m7 / sy, m8];  then n iterations;  then back:
+ *                  [m0, (m1 sy) / sx, m2 / sx;  (m3 sx) / sy, m4, m5 / sy;  m6 sx, m7 sy, m8]
+ *   iteration      S = sums(l, M_l).  [G | b]: G the symmetric matrix of the sd sd sums, b the sd r sums, eliminated without
+ *                  pivoting by the homography refit's procedure on NP rows: q.  p = -(q / s) (the gradients' sign).
+ *                  P = [p0 p1 p2; p3 p4 p5; p6 p7 0] (affine: p6 = p7 = 0);  A[r][0] = P[r][0] / s, A[r][1] = P[r][1] / s,
+ *                  A[r][2] = P[r][2] - (A[r][0] cx + A[r][1] cy);  D[0][c] = s A[0][c] + cx A[2][c],
+ *                  D[1][c] = s A[1][c] + cy A[2][c], D[2][c] = A[2][c];  dM = D with 1.0 added to the diagonal;
+ *                  I = adj(dM) / adj(dM)[2][2] (the mosaic chain's cofactors, nine divisions);
+ *                  N[r][c] = (M_l[r][0] I[0][c] + M_l[r][1] I[1][c]) + M_l[r][2] I[2][c];  M_l = N, one more accepted update
+ *   freezing       the iteration is skipped and the step freezes with its M_l, which goes back to the frame at once and is
+ *                  not touched again, when the count < f64(min_share) * f64(W_l H_l), a pivot is zero or not finite, an
+ *                  entry of N is not finite, or (n6 x + n7 y) + n8 > 0 fails at a corner (0,0), (W_l-1,0), (W_l-1,H_l-1),
+ *                  (0,H_l-1) of the level
+ *   outputs        e1, c1 of sums(L-1, M) under the final model;  stats[s] = [e0 / c0, e1 / c1, c1 / f64(W H), accepted];
+ *                  no accepted update: the input model's bytes, status 0;  not e1 / c1 <= e0 / c0 (a NaN on either side
+ *                  included): the input model's bytes, status 2 (rejected);  else status 1 and the model as float32: affine m0 .. m5, homography m_k / m8
+ * Refusals, before any device call: S < 1 (the sequence calls: T < 2), H or W < 1, iterations < 1, min_share outside (0, 1],
+ * an unknown model, levels outside [1, OFLK_MAX_LEVELS], NULL pointers (d_status_in / status_in may be NULL: every step
+ * refined), a workspace that is too small or not 256-byte aligned, d_stats not 8-byte aligned: OFLK_ERR_INVALID;  frames of
+ * 2^30 pixels or more, levels whose coarsest would be smaller than 8 x 8: OFLK_ERR_UNSUPPORTED.  Early exit on a small
+ * update, the ECC normalisation, photometric gain and bias, translation and similarity models and robust weights are not
+ * offered. */
+#define OFLK_ALIGN_AFFINE 0
+#define OFLK_ALIGN_HOMOGRAPHY 1
+/* bytes of the workspace of S steps (the sequence call: S = T - 1).  Host only */
+int oflk_align_workspace(int S, int H, int W, int levels, int model, size_t *bytes);
+/* device form: d_a, d_b [S][H][W] (uint8 when u8), d_model_in, d_model_out [S][6 | 9] float32, d_status_in [S] int32 or NULL,
+ * d_status_out [S] int32, d_stats [S][4] float64.  The pyramids, then two launches per iteration and per residual, all
+ * asynchronous on `stream` with no host round trip; can be captured into a graph (one chain, no parallel branches) */
+int oflk_align_refine(const void *d_a, const void *d_b, int u8, int S, int H, int W, int levels, int iterations, int model,
+                      float min_share, const float *d_model_in, const int *d_status_in, void *d_workspace, size_t workspace_bytes,
+                      float *d_model_out, int *d_status_out, double *d_stats, void *stream);
+/* the same on the T-1 steps t -> t+1 of d_frames [T][H][W]; every frame's pyramid is built once */
+int oflk_align_sequence(const void *d_frames, int u8, int T, int H, int W, int levels, int iterations, int model, float min_share,
+                        const float *d_model_in, const int *d_status_in, void *d_workspace, size_t workspace_bytes,
+                        float *d_model_out, int *d_status_out, double *d_stats, void *stream);
+/* host arrays, synchronous.  The steps go up in chunks of at most 64; steps are independent and a frame's pyramid depends on
+ * the frame alone, so the cut does not show */
+int oflk_align_refine_host(const float *a, const float *b, int S, int H, int W, int levels, int iterations, int model,
+                           float min_share, const float *model_in, const int *status_in, float *model_out, int *status_out,
+                           double *stats);
+int oflk_align_refine_host_u8(const unsigned char *a, const unsigned char *b, int S, int H, int W, int levels, int iterations,
+                              int model, float min_share, const float *model_in, const int *status_in, float *model_out,
+                              int *status_out, double *stats);
+int oflk_align_sequence_host(const float *frames, int T, int H, int W, int levels, int iterations, int model, float min_share,
+                             const float *model_in, const int *status_in, float *model_out, int *status_out, double *stats);
+int oflk_align_sequence_host_u8(const unsigned char *frames, int T, int H, int W, int levels, int iterations, int model,
+                                float min_share, const float *model_in, const int *status_in, float *model_out, int *status_out,
+                                double *stats);
+
 /* ---- online video stabilisation: a fixed-lag stabiliser on the tracker --------------------------------------------------- */
 /* The statement (tests/stabilize_online_model.py) is the trajectory above, read in the order in which a stream delivers its
  * steps.  The window of frame f is r_f = min(r, f, T-1-f) and reads steps f - r_f .. f + r_f - 1 only, so frame f is final

@@ -14,6 +14,7 @@
 #include "oflk_homography.hpp"
 #include "oflk_stabilize.hpp"
 #include "oflk_mosaic.hpp"
+#include "oflk_align.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -4402,6 +4403,303 @@ OFLK_API int oflk_mosaic_sequence_u8(const unsigned char *frames, int T, int H, 
     return mosaic_sequence<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, quality_level,
                                           min_distance, max_corners, detect_every, hypotheses, threshold, seed, anchor, extent, blend,
                                           out, capacity, canvas, count, to_anchor, held, dropped, model_out, counts_out);
+}
+
+// =============================================================================
+// direct image alignment: step models refined on pixel intensities (oflk_align.hpp)
+// =============================================================================
+namespace {
+int align_coefficients(int model) { return model == OFLK_ALIGN_HOMOGRAPHY ? 9 : 6; }
+int align_nsums(int model) { return align_sums(model == OFLK_ALIGN_HOMOGRAPHY ? 8 : 6); }
+int align_tiles(int h, int w) { return ((w + kAlignTileW - 1) / kAlignTileW) * ((h + kAlignTileH - 1) / kAlignTileH); }
+
+// The refusals of the configuration, before any device call; dims receives the level sizes
+int check_align(int S, int H, int W, int levels, int iterations, int model, float min_share, int *dims)
+{
+    if (S < 1) return fail(OFLK_ERR_INVALID, "S must be >= 1 (got %d)", S);
+    if (H < 1 || W < 1) return fail(OFLK_ERR_INVALID, "H and W must be >= 1 (got %d x %d)", H, W);
+    if ((size_t)H * (size_t)W >= ((size_t)1 << 30)) return fail(OFLK_ERR_UNSUPPORTED, "frames of 2^30 pixels or more are not supported");
+    if (H >= kMaxDim || W >= kMaxDim)
+        return fail(OFLK_ERR_UNSUPPORTED, "frames of 2^23 rows or columns or more are not supported (got %d x %d)", H, W);
+    if (model != OFLK_ALIGN_AFFINE && model != OFLK_ALIGN_HOMOGRAPHY) return fail(OFLK_ERR_INVALID, "unknown model %d", model);
+    if (iterations < 1) return fail(OFLK_ERR_INVALID, "iterations must be >= 1 (got %d)", iterations);
+    if (!(min_share > 0.0f && min_share <= 1.0f)) return fail(OFLK_ERR_INVALID, "min_share must be in (0, 1] (got %g)", (double)min_share);
+    if (levels < 1 || levels > OFLK_MAX_LEVELS) return fail(OFLK_ERR_INVALID, "levels must be in [1,%d] (got %d)", OFLK_MAX_LEVELS, levels);
+    int h = H, w = W;
+    for (int l = levels - 1; l >= 0; l--) {
+        if (h < 8 || w < 8)
+            return fail(OFLK_ERR_UNSUPPORTED, "pyramid level %d of %dx%d would be %dx%d: the alignment needs 8 x 8", l, W, H, w, h);
+        dims[2 * l] = h;
+        dims[2 * l + 1] = w;
+        h = (int)((double)h * 0.5);
+        w = (int)((double)w * 0.5);
+    }
+    return OFLK_OK;
+}
+
+// The workspace, 256-byte aligned pieces: the steps' states [S], the tile sums [S][tiles of the frame][NS], and per level
+// below the frame 2 S images (the pair form: S of A, then S of B; the sequence form: the first S + 1 hold its frames')
+struct AlignWs {
+    AlignState *state;
+    double *partial;
+    float *pyr[OFLK_MAX_LEVELS];
+    size_t pstride, bytes;
+};
+
+AlignWs align_ws(void *base, int S, int levels, const int *dims, int model)
+{
+    char *b = static_cast<char *>(base);
+    auto at = [&](size_t o) { return b ? b + o : nullptr; };   // NULL: only the size is wanted
+    AlignWs ws{};
+    size_t o = 0;
+    ws.state = reinterpret_cast<AlignState *>(at(o));
+    o += round256((size_t)S * sizeof(AlignState));
+    ws.pstride = (size_t)align_tiles(dims[2 * (levels - 1)], dims[2 * (levels - 1) + 1]) * (size_t)align_nsums(model);
+    ws.partial = reinterpret_cast<double *>(at(o));
+    o += round256((size_t)S * ws.pstride * sizeof(double));
+    for (int l = 0; l < levels - 1; l++) {
+        ws.pyr[l] = reinterpret_cast<float *>(at(o));
+        o += round256(2 * (size_t)S * (size_t)dims[2 * l] * (size_t)dims[2 * l + 1] * sizeof(float));
+    }
+    ws.bytes = o;
+    return ws;
+}
+
+int check_align_device(const void *d_a, const void *d_b, int u8, const void *d_model_in, const void *d_ws, size_t bytes, size_t need,
+                       const void *d_model_out, const void *d_status_out, const void *d_stats)
+{
+    if (!d_a || !d_b || !d_model_in || !d_ws || !d_model_out || !d_status_out || !d_stats)
+        return fail(OFLK_ERR_INVALID, "NULL input, workspace or output argument");
+    if (bytes < need) return fail(OFLK_ERR_INVALID, "workspace of %zu bytes, %zu needed (oflk_align_workspace)", bytes, need);
+    if (!aligned(d_ws, 256) || !aligned(d_stats, 8)) return fail(OFLK_ERR_INVALID, "d_workspace must be 256-byte aligned, d_stats 8-byte aligned");
+    if (!u8 && (!aligned(d_a, 4) || !aligned(d_b, 4))) return fail(OFLK_ERR_INVALID, "float32 frames must be 4-byte aligned");
+    return OFLK_OK;
+}
+
+template <class PIX, int NP>
+int align_reduce_launch(const AlignReduceArgs &r, int tiles, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_align_reduce<PIX, NP>), dim3((unsigned)tiles, (unsigned)std::min(r.S, 65535)), dim3(64), 0, s, r);
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+
+// The whole chain of one call on stream s; the arguments are checked.  d_a, d_b: the S templates and images, `step` elements
+// apart (the pair form: two arrays of S frames; the sequence form: d_b = d_a + one frame).  nimg > 0: the sequence form's
+// nimg = S + 1 frames, whose pyramids are built once.
+template <class PIX, int NP>
+int align_launch(const PIX *d_a, const PIX *d_b, int nimg, int S, int H, int W, int levels, const int *dims, int iterations,
+                 float min_share, const float *d_model_in, const int *d_status_in, const AlignWs &ws, float *d_model_out,
+                 int *d_status_out, double *d_stats, hipStream_t s)
+{
+    constexpr int NC = NP == 8 ? 9 : 6;
+    const bool seq = nimg > 0;
+    const int n = seq ? nimg : 2 * S;
+    int rc;
+    if (levels > 1) {
+        GaussW gauss;
+        if ((rc = make_gauss(2.0, &gauss))) return rc;
+        for (int l = levels - 2; l >= 0; l--)
+            if (!pyr_fused_fits(dims[2 * (l + 1)], dims[2 * (l + 1) + 1], dims[2 * l], dims[2 * l + 1], gauss))
+                return fail(OFLK_ERR_UNSUPPORTED, "pyramid level %d of %dx%d does not fit the fused pyramid kernel", l, W, H);
+        PyrExtra first;
+        first.u8 = sizeof(PIX) == 1;
+        if (!seq) {
+            first.in2 = reinterpret_cast<const float *>(d_b);
+            first.nsplit = S;
+        }
+        const float *in = reinterpret_cast<const float *>(d_a);
+        for (int l = levels - 2; l >= 0; l--) {
+            if ((rc = launch_pyr_down(nullptr, gauss, s, in, ws.pyr[l], nullptr, nullptr, n, dims[2 * (l + 1)], dims[2 * (l + 1) + 1],
+                                      dims[2 * l], dims[2 * l + 1], l == levels - 2 ? &first : nullptr)))
+                return rc;
+            in = ws.pyr[l];
+        }
+    }
+    hipLaunchKernelGGL(k_align_begin, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, s, d_model_in, d_status_in, S, NC, ws.state);
+    HIP_TRY(hipGetLastError());
+
+    // the sums of level l under the steps' current models, then the update of the given mode
+    auto pass = [&](int l, int mode, int last, int next) -> int {
+        const int h = dims[2 * l], w = dims[2 * l + 1];
+        AlignReduceArgs r{};
+        r.stride = (size_t)h * (size_t)w;
+        r.H = h; r.W = w; r.tiles_x = (w + kAlignTileW - 1) / kAlignTileW; r.S = S;
+        r.skip_frozen = mode == kAlignIterate;
+        r.state = ws.state; r.partial = ws.partial; r.pstride = ws.pstride;
+        const int tiles = align_tiles(h, w);
+        int rc2;
+        if (l == levels - 1) {
+            r.a = d_a;
+            r.b = d_b;
+            rc2 = align_reduce_launch<PIX, NP>(r, tiles, s);
+        } else {
+            r.a = ws.pyr[l];
+            r.b = ws.pyr[l] + (seq ? 1 : (size_t)S) * r.stride;
+            rc2 = align_reduce_launch<float, NP>(r, tiles, s);
+        }
+        if (rc2) return rc2;
+        AlignUpdateArgs u{};
+        u.state = ws.state; u.partial = ws.partial; u.pstride = ws.pstride;
+        u.tiles = tiles; u.S = S; u.mode = mode;
+        u.H = H; u.W = W; u.h = h; u.w = w;
+        u.last = last;
+        if (next >= 0) {
+            u.nh = dims[2 * next];
+            u.nw = dims[2 * next + 1];
+        }
+        u.min_count = (double)min_share * (double)((long long)w * (long long)h);
+        u.model_in = d_model_in; u.model_out = d_model_out; u.status_out = d_status_out; u.stats = d_stats;
+        hipLaunchKernelGGL((k_align_update<NP>), dim3((unsigned)std::min(S, 65535)), dim3(64), 0, s, u);
+        HIP_TRY(hipGetLastError());
+        return OFLK_OK;
+    };
+    if ((rc = pass(levels - 1, kAlignFirst, 0, 0))) return rc;
+    for (int l = 0; l < levels; l++)
+        for (int k = 0; k < iterations; k++) {
+            const bool last = k == iterations - 1;
+            if ((rc = pass(l, kAlignIterate, last, last ? (l + 1 < levels ? l + 1 : -1) : -1))) return rc;
+        }
+    return pass(levels - 1, kAlignLast, 0, -1);
+}
+
+template <class PIX>
+int align_dispatch(const PIX *d_a, const PIX *d_b, int nimg, int S, int H, int W, int levels, const int *dims, int iterations,
+                   int model, float min_share, const float *d_model_in, const int *d_status_in, const AlignWs &ws,
+                   float *d_model_out, int *d_status_out, double *d_stats, hipStream_t s)
+{
+    return model == OFLK_ALIGN_HOMOGRAPHY
+               ? align_launch<PIX, 8>(d_a, d_b, nimg, S, H, W, levels, dims, iterations, min_share, d_model_in, d_status_in, ws,
+                                      d_model_out, d_status_out, d_stats, s)
+               : align_launch<PIX, 6>(d_a, d_b, nimg, S, H, W, levels, dims, iterations, min_share, d_model_in, d_status_in, ws,
+                                      d_model_out, d_status_out, d_stats, s);
+}
+
+int align_device(const void *d_a, const void *d_b, int u8, int nimg, int S, int H, int W, int levels, int iterations, int model,
+                 float min_share, const float *d_model_in, const int *d_status_in, void *d_workspace, size_t bytes,
+                 float *d_model_out, int *d_status_out, double *d_stats, hipStream_t s)
+{
+    int dims[2 * OFLK_MAX_LEVELS];
+    int rc = check_align(S, H, W, levels, iterations, model, min_share, dims);
+    if (rc) return rc;
+    const size_t need = align_ws(nullptr, S, levels, dims, model).bytes;
+    if ((rc = check_align_device(d_a, d_b, u8, d_model_in, d_workspace, bytes, need, d_model_out, d_status_out, d_stats))) return rc;
+    const AlignWs ws = align_ws(d_workspace, S, levels, dims, model);
+    return u8 ? align_dispatch<unsigned char>((const unsigned char *)d_a, (const unsigned char *)d_b, nimg, S, H, W, levels, dims,
+                                              iterations, model, min_share, d_model_in, d_status_in, ws, d_model_out, d_status_out,
+                                              d_stats, s)
+              : align_dispatch<float>((const float *)d_a, (const float *)d_b, nimg, S, H, W, levels, dims, iterations, model, min_share,
+                                      d_model_in, d_status_in, ws, d_model_out, d_status_out, d_stats, s);
+}
+
+// S host steps in chunks of steps through one set of device buffers: a chunk's frames go up, its steps are refined and the
+// models, statuses and stats of all steps come down at the end.  Steps are independent and a frame's pyramid depends on the
+// frame alone, so the cut does not show.  seq: frames [S + 1][H][W], a chunk of n steps takes its n + 1 frames (b is unused)
+template <class PIX>
+int align_host(const PIX *a, const PIX *b, bool seq, int S, int H, int W, int levels, int iterations, int model, float min_share,
+               const float *model_in, const int *status_in, float *model_out, int *status_out, double *stats)
+{
+    int dims[2 * OFLK_MAX_LEVELS];
+    int rc = check_align(S, H, W, levels, iterations, model, min_share, dims);
+    if (rc) return rc;
+    if (!a || (!seq && !b) || !model_in || !model_out || !status_out || !stats)
+        return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const int C = sparse_chunk_pairs(S, H, W), nc = align_coefficients(model);
+    const size_t plane = (size_t)H * W, nS = (size_t)S;
+    PIX *d_a = nullptr, *d_b = nullptr;
+    float *d_min = nullptr, *d_mout = nullptr;
+    int *d_sin = nullptr, *d_sout = nullptr;
+    double *d_stats = nullptr;
+    char *d_ws = nullptr;
+    const size_t bytes = align_ws(nullptr, C, levels, dims, model).bytes;
+    if ((rc = call.alloc(&d_a, (size_t)(C + (seq ? 1 : 0)) * plane)) || (rc = call.alloc(&d_b, (size_t)C * plane, !seq)) ||
+        (rc = call.upload(&d_min, model_in, nc * nS)) || (status_in && (rc = call.upload(&d_sin, status_in, nS))) ||
+        (rc = call.alloc(&d_mout, nc * nS)) || (rc = call.alloc(&d_sout, nS)) || (rc = call.alloc(&d_stats, 4 * nS)) ||
+        (rc = call.alloc(&d_ws, bytes)))
+        return rc;
+    for (int s0 = 0; s0 < S; s0 += C) {
+        const int n = std::min(C, S - s0);
+        const size_t o = (size_t)s0 * plane;
+        if ((rc = call.to_device(d_a, a + o, (size_t)(n + (seq ? 1 : 0)) * plane)) ||
+            (!seq && (rc = call.to_device(d_b, b + o, (size_t)n * plane))))
+            return rc;
+        const AlignWs ws = align_ws(d_ws, n, levels, dims, model);
+        if ((rc = align_dispatch<PIX>(d_a, seq ? d_a + plane : d_b, seq ? n + 1 : 0, n, H, W, levels, dims, iterations, model, min_share,
+                                      d_min + (size_t)nc * s0, d_sin ? d_sin + s0 : nullptr, ws, d_mout + (size_t)nc * s0, d_sout + s0,
+                                      d_stats + 4 * (size_t)s0, nullptr)) ||
+            (rc = call.sync()))
+            return rc;
+    }
+    if ((rc = call.to_host(model_out, d_mout, nc * nS)) || (rc = call.to_host(status_out, d_sout, nS)) ||
+        (rc = call.to_host(stats, d_stats, 4 * nS)))
+        return rc;
+    return call.sync();
+}
+}  // namespace
+
+OFLK_API int oflk_align_workspace(int S, int H, int W, int levels, int model, size_t *bytes)
+{
+    if (!bytes) return fail(OFLK_ERR_INVALID, "bytes is NULL");
+    *bytes = 0;
+    int dims[2 * OFLK_MAX_LEVELS];
+    if (int rc = check_align(S, H, W, levels, 1, model, 1.0f, dims)) return rc;
+    *bytes = align_ws(nullptr, S, levels, dims, model).bytes;
+    return OFLK_OK;
+}
+
+OFLK_API int oflk_align_refine(const void *d_a, const void *d_b, int u8, int S, int H, int W, int levels, int iterations, int model,
+                               float min_share, const float *d_model_in, const int *d_status_in, void *d_workspace,
+                               size_t workspace_bytes, float *d_model_out, int *d_status_out, double *d_stats, void *stream)
+{
+    return align_device(d_a, d_b, u8, 0, S, H, W, levels, iterations, model, min_share, d_model_in, d_status_in, d_workspace,
+                        workspace_bytes, d_model_out, d_status_out, d_stats, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_align_sequence(const void *d_frames, int u8, int T, int H, int W, int levels, int iterations, int model,
+                                 float min_share, const float *d_model_in, const int *d_status_in, void *d_workspace,
+                                 size_t workspace_bytes, float *d_model_out, int *d_status_out, double *d_stats, void *stream)
+{
+    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
+    const void *d_b = d_frames && H > 0 && W > 0 ? static_cast<const char *>(d_frames) + (size_t)H * (size_t)W * (u8 ? 1 : sizeof(float))
+                                                 : d_frames;
+    return align_device(d_frames, d_b, u8, T, T - 1, H, W, levels, iterations, model, min_share, d_model_in, d_status_in, d_workspace,
+                        workspace_bytes, d_model_out, d_status_out, d_stats, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_align_refine_host(const float *a, const float *b, int S, int H, int W, int levels, int iterations, int model,
+                                    float min_share, const float *model_in, const int *status_in, float *model_out,
+                                    int *status_out, double *stats)
+{
+    return align_host<float>(a, b, false, S, H, W, levels, iterations, model, min_share, model_in, status_in, model_out, status_out,
+                             stats);
+}
+
+OFLK_API int oflk_align_refine_host_u8(const unsigned char *a, const unsigned char *b, int S, int H, int W, int levels,
+                                       int iterations, int model, float min_share, const float *model_in, const int *status_in,
+                                       float *model_out, int *status_out, double *stats)
+{
+    return align_host<unsigned char>(a, b, false, S, H, W, levels, iterations, model, min_share, model_in, status_in, model_out,
+                                     status_out, stats);
+}
+
+OFLK_API int oflk_align_sequence_host(const float *frames, int T, int H, int W, int levels, int iterations, int model,
+                                      float min_share, const float *model_in, const int *status_in, float *model_out,
+                                      int *status_out, double *stats)
+{
+    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
+    return align_host<float>(frames, nullptr, true, T - 1, H, W, levels, iterations, model, min_share, model_in, status_in, model_out,
+                             status_out, stats);
+}
+
+OFLK_API int oflk_align_sequence_host_u8(const unsigned char *frames, int T, int H, int W, int levels, int iterations, int model,
+                                         float min_share, const float *model_in, const int *status_in, float *model_out,
+                                         int *status_out, double *stats)
+{
+    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
+    return align_host<unsigned char>(frames, nullptr, true, T - 1, H, W, levels, iterations, model, min_share, model_in, status_in,
+                                     model_out, status_out, stats);
 }
 
 // =============================================================================

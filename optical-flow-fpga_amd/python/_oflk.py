@@ -148,6 +148,13 @@ SIGNATURES = {
     "oflk_mosaic_composite_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [_f64p, _vp] + [ctypes.c_int] * 5 + [_vp, _i32p]),
     "oflk_mosaic_sequence": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_uint, ctypes.c_int, ctypes.c_double, ctypes.c_int, _f32p, ctypes.c_size_t, _i32p, _i32p, _f64p, _vp, _vp, _f32p, _i32p]),
     "oflk_mosaic_sequence_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_uint, ctypes.c_int, ctypes.c_double, ctypes.c_int, _vp, ctypes.c_size_t, _i32p, _i32p, _f64p, _vp, _vp, _f32p, _i32p]),
+    "oflk_align_workspace": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_size_t)]),
+    "oflk_align_refine": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 7 + [ctypes.c_float, _vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp]),
+    "oflk_align_sequence": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [ctypes.c_float, _vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp]),
+    "oflk_align_refine_host": (ctypes.c_int, [_f32p, _f32p] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p]),
+    "oflk_align_refine_host_u8": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p]),
+    "oflk_align_sequence_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p]),
+    "oflk_align_sequence_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p]),
     "oflk_stabilize_trajectory_ring": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 4 + [_f64p, ctypes.c_int, _vp, _vp, _vp]),
     "oflk_stabilizer_create": (ctypes.c_int, [ctypes.POINTER(_vp)] + [ctypes.c_int] * 7 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int]),
     "oflk_stabilizer_destroy": (ctypes.c_int, [_vp]),
@@ -854,6 +861,71 @@ def mosaic_composite_host(frames: np.ndarray, maps: np.ndarray, skip: Optional[n
     check(fn(frames.ctypes.data if u8 else ptr(frames), F, H, W, _f64(maps), None if skip is None else skip.ctypes.data, int(x0), int(y0),
              int(Hc), int(Wc), int(blend), out.ctypes.data if u8 else ptr(out), None if cnt is None else cnt.ctypes.data_as(_i32p)))
     return out, cnt
+
+
+ALIGN_KINDS = {"affine": 0, "homography": 1}
+
+
+def check_align_params(kind, levels, iterations, min_share: float) -> Tuple[int, int, int, float]:
+    """the C ABI's model code and the checked levels, iterations and min_share of the alignment calls; ValueError otherwise"""
+    if not isinstance(kind, str) or kind not in ALIGN_KINDS:
+        raise ValueError(f"kind must be one of {sorted(ALIGN_KINDS)}, got {kind!r}")
+    for name, v in (("levels", levels), ("iterations", iterations)):
+        if isinstance(v, bool) or int(v) != v or int(v) < 1:
+            raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+    ms = float(min_share)
+    if not 0.0 < ms <= 1.0:
+        raise ValueError(f"min_share must be in (0, 1], got {min_share!r}")
+    return ALIGN_KINDS[kind], int(levels), int(iterations), ms
+
+
+def align_workspace(S: int, H: int, W: int, levels: int, model: int) -> int:
+    """bytes of the workspace of oflk_align_refine for S steps (oflk_align_sequence: S = T - 1)"""
+    n = ctypes.c_size_t(0)
+    check(lib().oflk_align_workspace(int(S), int(H), int(W), int(levels), int(model), ctypes.byref(n)))
+    return int(n.value)
+
+
+def align_refine(d_a: int, d_b: int, S: int, H: int, W: int, levels: int, iterations: int, model: int, min_share: float,
+                 d_model_in: int, d_status_in: int, d_workspace: int, workspace_bytes: int, d_model_out: int, d_status_out: int,
+                 d_stats: int, u8: bool = False, stream: int = 0) -> None:
+    """oflk_align_refine on device pointers: d_a, d_b [S][H][W] (float32, or uint8 with u8), d_model_in / d_model_out [S][6 | 9]
+    float32, d_status_in [S] int32 or 0, d_status_out [S] int32, d_stats [S][4] float64; asynchronous."""
+    check(lib().oflk_align_refine(d_a or None, d_b or None, int(bool(u8)), int(S), int(H), int(W), int(levels), int(iterations),
+                                  int(model), float(min_share), d_model_in or None, d_status_in or None, d_workspace or None,
+                                  int(workspace_bytes), d_model_out or None, d_status_out or None, d_stats or None, stream))
+
+
+def align_sequence(d_frames: int, T: int, H: int, W: int, levels: int, iterations: int, model: int, min_share: float,
+                   d_model_in: int, d_status_in: int, d_workspace: int, workspace_bytes: int, d_model_out: int, d_status_out: int,
+                   d_stats: int, u8: bool = False, stream: int = 0) -> None:
+    """oflk_align_sequence on device pointers: the T-1 steps t -> t+1 of d_frames [T][H][W], with align_refine's other
+    arguments for S = T - 1; asynchronous."""
+    check(lib().oflk_align_sequence(d_frames or None, int(bool(u8)), int(T), int(H), int(W), int(levels), int(iterations), int(model),
+                                    float(min_share), d_model_in or None, d_status_in or None, d_workspace or None,
+                                    int(workspace_bytes), d_model_out or None, d_status_out or None, d_stats or None, stream))
+
+
+def align_host(a: np.ndarray, b: Optional[np.ndarray], model_in: np.ndarray, status_in: Optional[np.ndarray], levels: int,
+               iterations: int, model: int, min_share: float):
+    """oflk_align_refine_host[_u8] (b given: contiguous (S, H, W) arrays of one type) or oflk_align_sequence_host[_u8] (b None:
+    a holds the S + 1 frames); contiguous float32 (S, 6 | 9) models and optional int32 (S,) statuses in; (model (S, nc) float32,
+    status (S,) int32, stats (S, 4) float64) out"""
+    F, H, W = a.shape
+    S = F if b is not None else F - 1
+    u8 = a.dtype == np.uint8
+    out = np.empty_like(model_in)
+    st, stats = np.empty(S, np.int32), np.empty((S, 4), np.float64)
+    pix = (lambda x: x.ctypes.data) if u8 else ptr
+    tail = (int(H), int(W), int(levels), int(iterations), int(model), float(min_share), ptr(model_in),
+            None if status_in is None else status_in.ctypes.data_as(_i32p), ptr(out), st.ctypes.data_as(_i32p), _f64(stats))
+    if b is not None:
+        fn = lib().oflk_align_refine_host_u8 if u8 else lib().oflk_align_refine_host
+        check(fn(pix(a), pix(b), S, *tail))
+    else:
+        fn = lib().oflk_align_sequence_host_u8 if u8 else lib().oflk_align_sequence_host
+        check(fn(pix(a), F, *tail))
+    return out, st, stats
 
 
 class Tracker:

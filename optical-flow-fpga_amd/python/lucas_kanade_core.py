@@ -501,3 +501,63 @@ def mosaic_composite(frames, maps, canvas_shape, origin=(0, 0), skip=None, blend
         sk = np.ascontiguousarray(sk != 0, np.uint8)
     out, cnt = _oflk.mosaic_composite_host(arr, m.reshape(F, 9), sk, int(origin[0]), int(origin[1]), Hc, Wc, code, bool(return_count))
     return (out, cnt) if return_count else out
+
+
+class Alignment(NamedTuple):
+    """Step models refined on pixel intensities (refine_alignment, sequence_refine_alignment)."""
+    model: np.ndarray    # (S, 3, 3) (homography, model[2, 2] == 1) or (S, 2, 3) (affine) float32; the input model where status != 1
+    status: np.ndarray   # (S,) int32: 1 refined; 0 not refined (input status 0, not finite, or frozen before an update); 2 rejected
+    stats: np.ndarray    # (S, 4) float64: mean squared residual before and after, counted share of the frame, accepted updates
+
+
+def _align_models(model, status, S: int, kind: str):
+    nc = 9 if kind == "homography" else 6
+    m = np.ascontiguousarray(model, np.float32)
+    if m.size != nc * S:
+        raise ValueError(f"expected {S} {kind} models of {nc} coefficients, got {np.shape(model)}")
+    st = None
+    if status is not None:
+        st = np.asarray(status)
+        if st.shape != (S,):
+            raise ValueError(f"status must have shape {(S,)}, got {st.shape}")
+        st = np.ascontiguousarray(st != 0, np.int32)
+    return m.reshape(S, nc), st
+
+
+def _alignment(out, st, stats, kind: str, single: bool) -> Alignment:
+    out = out.reshape((-1, 3, 3) if kind == "homography" else (-1, 2, 3))
+    return Alignment(out[0], int(st[0]), stats[0]) if single else Alignment(out, st, stats)
+
+
+def refine_alignment(a, b, model, status=None, kind: str = "homography", levels: int = 3, iterations: int = 5,
+                     min_share: float = 0.25) -> Alignment:
+    """Refine step models on the pixels themselves, on the GPU: inverse-compositional Lucas-Kanade registration of frame b to
+    the template a over the whole frame, coarse to fine, `iterations` Gauss-Newton updates on each of `levels` pyramid levels.
+
+    a, b: (H, W) or (S, H, W), float32 or uint8, of one type; model: the (3, 3) / (S, 3, 3) homographies of
+    estimate_homography (kind "homography") or the (2, 3) / (S, 2, 3) models of estimate_motion (kind "affine"), mapping a's
+    coordinates to b's; status: (S,) or None -- a step with status 0 comes back as it went in.  A step that cannot be
+    refined (fewer than `min_share` of the pixels land inside b, a flat template, a singular system) keeps its input model
+    with status 0, and one whose mean squared residual grew keeps it with status 2.  The same inputs give the same bytes; the
+    statement is in include/oflk.h.
+    """
+    code, L, n, ms = _oflk.check_align_params(kind, levels, iterations, min_share)
+    single = isinstance(a, np.ndarray) and a.ndim == 2
+    fa, ua = _oflk.as_frames(a)
+    fb, ub = _oflk.as_frames(b)
+    if fa.shape != fb.shape or ua != ub:
+        raise ValueError(f"a and b must have one shape and type, got {fa.shape} {fa.dtype} and {fb.shape} {fb.dtype}")
+    m, st = _align_models(model, status, fa.shape[0], kind)
+    return _alignment(*_oflk.align_host(fa, fb, m, st, L, n, code, ms), kind, single)
+
+
+def sequence_refine_alignment(frames, model, status=None, kind: str = "homography", levels: int = 3, iterations: int = 5,
+                              min_share: float = 0.25) -> Alignment:
+    """refine_alignment on the T-1 steps t -> t+1 of frames (T, H, W): model[t] (e.g. of tracks_homography or tracks_motion)
+    maps frame t's coordinates to frame t+1's.  Every frame's pyramid is built once.  Returns a batched Alignment."""
+    code, L, n, ms = _oflk.check_align_params(kind, levels, iterations, min_share)
+    arr, _ = _oflk.as_frames(frames)
+    if arr.shape[0] < 2:
+        raise ValueError(f"a sequence needs at least two frames, got {arr.shape[0]}")
+    m, st = _align_models(model, status, arr.shape[0] - 1, kind)
+    return _alignment(*_oflk.align_host(arr, None, m, st, L, n, code, ms), kind, False)

@@ -30,9 +30,10 @@ import numpy as np
 import numpy.typing as npt
 
 import _oflk
-from lucas_kanade_core import (Homography, MosaicChain, Motion, Trajectory, estimate_homography, estimate_motion,  # noqa: F401
-                               lucas_kanade_single_scale, mosaic_chain, mosaic_composite, stabilize_trajectory, tracks_homography,
-                               tracks_motion, warp_affine, warp_perspective)
+from lucas_kanade_core import (Alignment, Homography, MosaicChain, Motion, Trajectory, estimate_homography,  # noqa: F401
+                               estimate_motion, lucas_kanade_single_scale, mosaic_chain, mosaic_composite, refine_alignment,
+                               sequence_refine_alignment, stabilize_trajectory, tracks_homography, tracks_motion, warp_affine,
+                               warp_perspective)
 
 SCRIPT_DIR = Path(__file__).resolve().parent
 PROJECT_ROOT = SCRIPT_DIR.parent
@@ -474,13 +475,27 @@ def lucas_kanade_pyramidal_sequence_stabilize(frames, max_corners: int, detect_e
                                               radius: int = 15, sigma=None, hypotheses: int = 256, threshold: float = 1.0,
                                               seed: int = 0, quality_level: float = 0.01, min_distance: float = 10.0,
                                               num_levels: int = 3, window_size: int = 5, num_iterations: int = 3,
-                                              alpha: float = 0.01, beta: float = 0.5,
-                                              max_residual: float = 4.0) -> SequenceStabilized:
+                                              alpha: float = 0.01, beta: float = 0.5, max_residual: float = 4.0,
+                                              refine_iterations: int = 0, refine_levels: int = 3) -> SequenceStabilized:
     """Frames in, steadied frames out: lucas_kanade_pyramidal_sequence_klt_sparse_replenish on the frames, tracks_motion on
     its rows, stabilize_trajectory on the models and warp_affine of the frames under its maps, in one call whose
     intermediate rows stay in the library.  The frames go up twice, chunk by chunk (once to track, once to warp); nothing
     of the sequence's size is ever on the device.  The black border is not cropped (warp_affine's inside mask tells where
-    it is)."""
+    it is).
+
+    refine_iterations > 0: the same chain made of its public parts, with sequence_refine_alignment (kind "affine",
+    refine_levels levels, refine_iterations iterations each) between the fit and the trajectory: every fitted step is refined
+    on the pixels of its two frames, and a step that cannot be refined keeps the fitted model."""
+    if isinstance(refine_iterations, bool) or int(refine_iterations) != refine_iterations or int(refine_iterations) < 0:
+        raise ValueError(f"refine_iterations must be an integer >= 0, got {refine_iterations!r}")
+    if int(refine_iterations) > 0:
+        rows = lucas_kanade_pyramidal_sequence_klt_sparse_replenish(frames, max_corners, detect_every, quality_level, min_distance,
+                                                                    num_levels, window_size, num_iterations, alpha, beta, max_residual)
+        fit = tracks_motion(rows.tracks, rows.visible, rows.born, model, hypotheses, threshold, seed)
+        arr, _ = _oflk.as_sequence(frames)
+        al = sequence_refine_alignment(arr, fit.model, fit.status, "affine", refine_levels, int(refine_iterations))
+        tr = stabilize_trajectory(al.model, fit.status, radius, sigma)
+        return SequenceStabilized(warp_affine(arr, tr.map), tr.correction, al.model, fit.status, tr.held)
     a, b = _oflk.check_fb_params(alpha, beta)
     arr, u8 = _oflk.as_sequence(frames)
     T, H, W = arr.shape
@@ -517,12 +532,35 @@ def lucas_kanade_pyramidal_sequence_mosaic(frames, max_corners: int = 1000, dete
                                            threshold: float = 1.0, seed: int = 0, quality_level: float = 0.01,
                                            min_distance: float = 10.0, num_levels: int = 3, window_size: int = 5,
                                            num_iterations: int = 3, alpha: float = 0.01, beta: float = 0.5, max_residual: float = 4.0,
-                                           anchor: int = 0, extent=None, blend: str = "feather", max_pixels=None) -> Mosaic:
+                                           anchor: int = 0, extent=None, blend: str = "feather", max_pixels=None,
+                                           refine_iterations: int = 0, refine_levels: int = 3) -> Mosaic:
     """Frames in, one picture out: lucas_kanade_pyramidal_sequence_klt_sparse_replenish on the frames, tracks_homography on its
     rows, mosaic_chain from frame `anchor`, and mosaic_composite of every frame that is not dropped, in one call whose
     intermediate rows stay in the library.  The frames go up twice, chunk by chunk (once to track, once to blend).  The canvas
     is as large as the camera's path makes it; a canvas of more than max_pixels (default 16 H W) pixels raises OflkError with
-    the size it needed in the message."""
+    the size it needed in the message.
+
+    refine_iterations > 0: the same chain made of its public parts, with sequence_refine_alignment (kind "homography",
+    refine_levels levels, refine_iterations iterations each) between the fit and the chain, which answers the chain's drift: a
+    product of steps fitted to at most max_corners tracks each."""
+    if isinstance(refine_iterations, bool) or int(refine_iterations) != refine_iterations or int(refine_iterations) < 0:
+        raise ValueError(f"refine_iterations must be an integer >= 0, got {refine_iterations!r}")
+    if int(refine_iterations) > 0:
+        rows = lucas_kanade_pyramidal_sequence_klt_sparse_replenish(frames, max_corners, detect_every, quality_level, min_distance,
+                                                                    num_levels, window_size, num_iterations, alpha, beta, max_residual)
+        fit = tracks_homography(rows.tracks, rows.visible, rows.born, hypotheses, threshold, seed)
+        arr, _ = _oflk.as_sequence(frames)
+        al = sequence_refine_alignment(arr, fit.model, fit.status, "homography", refine_levels, int(refine_iterations))
+        ch = mosaic_chain(al.model, fit.status, arr.shape[1:], anchor, extent)
+        Hc, Wc = ch.canvas_shape
+        cap = 16 * arr.shape[1] * arr.shape[2] if max_pixels is None else max_pixels
+        if isinstance(cap, bool) or int(cap) != cap or int(cap) < 1:
+            raise ValueError(f"max_pixels must be an integer >= 1, got {max_pixels!r}")
+        if Hc * Wc > int(cap):
+            raise _oflk.OflkError(_oflk.OFLK_ERR_UNSUPPORTED,
+                                  f"the canvas of {Wc} x {Hc} pixels at {ch.origin} exceeds the capacity of {int(cap)} pixels")
+        canvas, cnt = mosaic_composite(arr, ch.from_anchor, (Hc, Wc), ch.origin, ch.dropped, blend, True)
+        return Mosaic(canvas, cnt, ch.origin, ch.to_anchor, ch.held, ch.dropped, al.model, fit.status)
     a, b = _oflk.check_fb_params(alpha, beta)
     arr, u8 = _oflk.as_sequence(frames)
     T, H, W = arr.shape

@@ -1,0 +1,119 @@
+// Host-side check of direct image alignment for a sanitizer build (make -C optical-flow-fpga_amd/csrc align-host-check): the
+// workspace sizing and layout and every refusal that needs no device, of the device forms and of the host forms.  It includes
+// the library's translation unit and runs on a machine without a GPU.  Exit status 0: every expectation held (and the
+// sanitizers found nothing).
+#include "../optical-flow-fpga_amd/csrc/oflk.hip"
+
+#include <cstdio>
+#include <limits>
+
+static int g_failed = 0;
+#define EXPECT(cond)                                                        \
+    do {                                                                    \
+        if (!(cond)) {                                                      \
+            std::printf("%s:%d: %s\n", __FILE__, __LINE__, #cond);          \
+            g_failed++;                                                     \
+        }                                                                   \
+    } while (0)
+
+alignas(256) static unsigned char g_buf[1024];   // stands for device memory: every call below is refused before it is touched
+
+int main()
+{
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    const int A = OFLK_ALIGN_AFFINE, P = OFLK_ALIGN_HOMOGRAPHY;
+    size_t n = 7;
+    // the workspace: refusals and sizes
+    EXPECT(oflk_align_workspace(1, 32, 32, 1, P, nullptr) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_workspace(0, 32, 32, 1, P, &n) == OFLK_ERR_INVALID && n == 0);
+    EXPECT(oflk_align_workspace(1, 0, 32, 1, P, &n) == OFLK_ERR_INVALID && n == 0);
+    EXPECT(oflk_align_workspace(1, 32, 32, 0, P, &n) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_workspace(1, 32, 32, OFLK_MAX_LEVELS + 1, P, &n) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_workspace(1, 32, 32, 1, 2, &n) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_workspace(1, 32, 32, 1, -1, &n) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_workspace(1, 7, 32, 1, P, &n) == OFLK_ERR_UNSUPPORTED);        // the frame itself under 8 x 8
+    EXPECT(oflk_align_workspace(1, 32, 31, 3, P, &n) == OFLK_ERR_UNSUPPORTED);       // 31 -> 15 -> 7
+    EXPECT(oflk_align_workspace(1, 32, 32, 3, P, &n) == OFLK_OK && n > 0);           // 32 -> 16 -> 8
+    EXPECT(oflk_align_workspace(1, 1 << 15, 1 << 15, 1, P, &n) == OFLK_ERR_UNSUPPORTED && n == 0);
+    EXPECT(std::string(oflk_last_error()).find("2^30") != std::string::npos);
+    for (int model : {A, P})
+        for (int L : {1, 3})
+            for (int S : {1, 5}) {
+                int dims[2 * OFLK_MAX_LEVELS];
+                EXPECT(check_align(S, 70, 257, L, 1, model, 0.25f, dims) == OFLK_OK);
+                EXPECT(dims[2 * (L - 1)] == 70 && dims[2 * (L - 1) + 1] == 257);
+                const AlignWs ws = align_ws(g_buf, S, L, dims, model);
+                EXPECT(oflk_align_workspace(S, 70, 257, L, model, &n) == OFLK_OK && n == ws.bytes);
+                // the pieces follow each other on 256-byte boundaries and end inside the size
+                const size_t ns = model == P ? 46 : 29, tiles = 5 * 3;
+                EXPECT(ws.pstride == tiles * ns && align_nsums(model) == (int)ns && align_tiles(70, 257) == (int)tiles);
+                const char *b = reinterpret_cast<const char *>(g_buf);
+                EXPECT(reinterpret_cast<const char *>(ws.state) == b);
+                EXPECT(reinterpret_cast<const char *>(ws.partial) >= b + S * sizeof(AlignState) && aligned(ws.partial, 256));
+                const char *end = reinterpret_cast<const char *>(ws.partial) + S * ws.pstride * sizeof(double);
+                for (int l = 0; l < L - 1; l++) {
+                    EXPECT(reinterpret_cast<const char *>(ws.pyr[l]) >= end && aligned(ws.pyr[l], 256));
+                    end = reinterpret_cast<const char *>(ws.pyr[l]) + 2 * (size_t)S * dims[2 * l] * dims[2 * l + 1] * sizeof(float);
+                }
+                EXPECT(end <= b + ws.bytes && ws.bytes % 256 == 0);
+            }
+    // the device forms: every refusal comes before the pointers are used
+    EXPECT(oflk_align_workspace(2, 32, 40, 2, P, &n) == OFLK_OK);
+    void *d = g_buf;
+    float *fm = reinterpret_cast<float *>(g_buf);
+    int *im = reinterpret_cast<int *>(g_buf);
+    double *dm = reinterpret_cast<double *>(g_buf);
+    auto refine = [&](const void *a, const void *b, int u8, int S, int H, int W, int L, int it, int model, float share, const float *mi,
+                      void *ws, size_t bytes, float *mo, int *so, double *st) {
+        return oflk_align_refine(a, b, u8, S, H, W, L, it, model, share, mi, nullptr, ws, bytes, mo, so, st, nullptr);
+    };
+    EXPECT(refine(d, d, 0, 0, 32, 40, 2, 1, P, 0.25f, fm, d, n, fm, im, dm) == OFLK_ERR_INVALID);
+    EXPECT(refine(d, d, 0, 2, 32, 40, 2, 0, P, 0.25f, fm, d, n, fm, im, dm) == OFLK_ERR_INVALID);
+    EXPECT(std::string(oflk_last_error()).find("iterations") != std::string::npos);
+    EXPECT(refine(d, d, 0, 2, 32, 40, 2, 1, 5, 0.25f, fm, d, n, fm, im, dm) == OFLK_ERR_INVALID);
+    EXPECT(std::string(oflk_last_error()).find("model") != std::string::npos);
+    for (float share : {0.0f, -0.5f, 1.5f, nan}) {
+        EXPECT(refine(d, d, 0, 2, 32, 40, 2, 1, P, share, fm, d, n, fm, im, dm) == OFLK_ERR_INVALID);
+        EXPECT(std::string(oflk_last_error()).find("min_share") != std::string::npos);
+    }
+    EXPECT(refine(d, d, 0, 2, 31, 40, 3, 1, P, 0.25f, fm, d, n, fm, im, dm) == OFLK_ERR_UNSUPPORTED);   // 31 -> 15 -> 7 rows
+    EXPECT(refine(nullptr, d, 0, 2, 32, 40, 2, 1, P, 0.25f, fm, d, n, fm, im, dm) == OFLK_ERR_INVALID);
+    EXPECT(refine(d, nullptr, 0, 2, 32, 40, 2, 1, P, 0.25f, fm, d, n, fm, im, dm) == OFLK_ERR_INVALID);
+    EXPECT(refine(d, d, 0, 2, 32, 40, 2, 1, P, 0.25f, nullptr, d, n, fm, im, dm) == OFLK_ERR_INVALID);
+    EXPECT(refine(d, d, 0, 2, 32, 40, 2, 1, P, 0.25f, fm, nullptr, n, fm, im, dm) == OFLK_ERR_INVALID);
+    EXPECT(refine(d, d, 0, 2, 32, 40, 2, 1, P, 0.25f, fm, d, n, nullptr, im, dm) == OFLK_ERR_INVALID);
+    EXPECT(refine(d, d, 0, 2, 32, 40, 2, 1, P, 0.25f, fm, d, n, fm, nullptr, dm) == OFLK_ERR_INVALID);
+    EXPECT(refine(d, d, 0, 2, 32, 40, 2, 1, P, 0.25f, fm, d, n, fm, im, nullptr) == OFLK_ERR_INVALID);
+    EXPECT(refine(d, d, 0, 2, 32, 40, 2, 1, P, 0.25f, fm, d, n - 1, fm, im, dm) == OFLK_ERR_INVALID);
+    EXPECT(std::string(oflk_last_error()).find("oflk_align_workspace") != std::string::npos);
+    EXPECT(refine(d, d, 0, 2, 32, 40, 2, 1, P, 0.25f, fm, g_buf + 128, n, fm, im, dm) == OFLK_ERR_INVALID);
+    EXPECT(refine(d, d, 0, 2, 32, 40, 2, 1, P, 0.25f, fm, d, n, fm, im, reinterpret_cast<double *>(g_buf + 4)) == OFLK_ERR_INVALID);
+    EXPECT(refine(g_buf + 1, d, 0, 2, 32, 40, 2, 1, P, 0.25f, fm, d, n, fm, im, dm) == OFLK_ERR_INVALID);   // float32 frames off a 4-byte boundary
+    auto sequence = [&](const void *f, int T, int L, int it, int model) {
+        return oflk_align_sequence(f, 1, T, 32, 40, L, it, model, 0.25f, fm, nullptr, d, n, fm, im, dm, nullptr);
+    };
+    EXPECT(sequence(d, 1, 2, 1, P) == OFLK_ERR_INVALID);
+    EXPECT(sequence(nullptr, 3, 2, 1, P) == OFLK_ERR_INVALID);
+    EXPECT(sequence(d, 3, 2, 0, A) == OFLK_ERR_INVALID);
+    EXPECT(sequence(d, 3, 2, 1, 9) == OFLK_ERR_INVALID);
+    EXPECT(sequence(d, 3, 4, 1, A) == OFLK_ERR_UNSUPPORTED);
+    // the host forms refuse the same before they look for a device
+    const unsigned char *u = g_buf;
+    EXPECT(oflk_align_refine_host(fm, fm, 0, 32, 40, 2, 1, P, 0.25f, fm, nullptr, fm, im, dm) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_refine_host(fm, fm, 1, 32, 40, 2, 0, P, 0.25f, fm, nullptr, fm, im, dm) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_refine_host(fm, fm, 1, 32, 40, 2, 1, P, 2.0f, fm, nullptr, fm, im, dm) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_refine_host(fm, fm, 1, 32, 40, 4, 1, P, 0.25f, fm, nullptr, fm, im, dm) == OFLK_ERR_UNSUPPORTED);
+    EXPECT(oflk_align_refine_host(nullptr, fm, 1, 32, 40, 2, 1, P, 0.25f, fm, nullptr, fm, im, dm) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_refine_host(fm, nullptr, 1, 32, 40, 2, 1, P, 0.25f, fm, nullptr, fm, im, dm) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_refine_host_u8(u, u, 1, 32, 40, 2, 1, 3, 0.25f, fm, nullptr, fm, im, dm) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_refine_host_u8(u, u, 1, 32, 40, 2, 1, A, 0.25f, nullptr, nullptr, fm, im, dm) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_refine_host_u8(u, u, 1, 32, 40, 2, 1, A, 0.25f, fm, nullptr, nullptr, im, dm) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_refine_host_u8(u, u, 1, 32, 40, 2, 1, A, 0.25f, fm, nullptr, fm, nullptr, dm) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_refine_host_u8(u, u, 1, 32, 40, 2, 1, A, 0.25f, fm, nullptr, fm, im, nullptr) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_sequence_host(fm, 1, 32, 40, 2, 1, P, 0.25f, fm, nullptr, fm, im, dm) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_sequence_host(nullptr, 2, 32, 40, 2, 1, P, 0.25f, fm, nullptr, fm, im, dm) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_sequence_host_u8(u, 2, 32, 40, 2, -3, P, 0.25f, fm, nullptr, fm, im, dm) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_sequence_host_u8(u, 2, 6, 40, 1, 1, P, 0.25f, fm, nullptr, fm, im, dm) == OFLK_ERR_UNSUPPORTED);
+    std::printf(g_failed ? "align host check: %d expectation(s) failed\n" : "align host check: ok\n", g_failed);
+    return g_failed ? 1 : 0;
+}

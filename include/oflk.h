@@ -938,6 +938,64 @@ int oflk_stabilizer_correction_device(const oflk_stabilizer *st, const float **d
  * would no longer be the tracker's. */
 oflk_tracker *oflk_stabilizer_tracker(oflk_stabilizer *st);
 
+/* ---- colour video: luma, warps of interleaved frames, colour stabilisers ------------------------------------------------- */
+/* The statement (tests/colour_model.py).
+ * Layout: colour frames are interleaved uint8, [F][H][W][C] with C = channels = 3 or 4 ("packed" below).  float32 colour is
+ * not offered.  `order` says where R, G and B sit: OFLK_ORDER_RGB = R, G, B at bytes 0, 1, 2; OFLK_ORDER_BGR = B, G, R.
+ * The byte at index 3 when C = 4 is a fourth channel: luma ignores it, every warp resamples it like the others.
+ * Luma: Y = (77 R + 150 G + 29 B + 128) >> 8 in integers.  The weights sum to 256, so grey input (R = G = B = g) gives
+ * Y = g and Y never leaves [0, 255]; there is no float arithmetic and nothing to round.
+ * Packed warps: for every channel c, out[f][y][x][c] is the byte that oflk_warp_affine / oflk_warp_perspective writes at
+ * [f][y][x] for the plane frames[f][:, :, c] under map[f] -- (unsigned char) rintf(sample), 0 outside the frame -- and
+ * inside[f][y][x] is that call's inside: one byte per pixel, not per channel.  The kernels form the source position, the
+ * test and the four weights once per pixel and finish C channels on them, by the planar kernels' operations in their order.
+ * No load touches a byte outside [F][H][W][C].
+ * Colour stabilisation, by statement, byte for byte: (1) the luma of every frame; (2) oflk_stabilize_sequence_u8 on the
+ * luma frames for correction, model_out, counts_out and held; (3) the packed affine warp of the colour frames under the
+ * maps of that trajectory.  The sequence call takes the luma in a chunked pass of its own (a chunk of packed frames goes
+ * up, its luma comes down into a host array of T H W bytes), runs the grey call's pass 1 and trajectory on that array and
+ * warps the packed frames chunk by chunk: nothing of the sequence's size is ever on the device.
+ * The online form: a stabiliser made by oflk_stabilizer_create_packed holds packed frames in its delay line --
+ * (r + 1) H W C bytes, counted by oflk_stabilizer_workspace_bytes with one more plane for the luma -- and its tracker is
+ * pushed the luma of each frame, computed on the device inside the push (one more launch).  oflk_stabilizer_push, flush,
+ * their _device forms, correction_device, lag, reset and destroy then take and return [H][W][C] frames for such an
+ * object; d_inside / inside stays [H][W].  The frames and corrections of T pushes and a flush equal
+ * oflk_stabilize_sequence_packed on the same T frames.  A stabiliser made by oflk_stabilizer_create is what it was.
+ * Refusals, before any device call: channels not 3 or 4, an order outside the two values, NULL pointers (d_inside, inside
+ * and the sequence call's last four outputs may be NULL), H or W < 2, F < 1 (the sequence call: T < 2), d_map not 8-byte
+ * aligned: OFLK_ERR_INVALID;  frames of 2^30 pixels or more: OFLK_ERR_UNSUPPORTED.  Byte offsets inside a frame are 32-bit,
+ * so frames of H W C >= 2^31 bytes are refused as well, with OFLK_ERR_UNSUPPORTED; offsets across frames are 64-bit.  The
+ * sequence call and the stabiliser also refuse what their grey forms refuse, with their codes.  Frames and outputs may
+ * have any alignment (an unaligned base or W % 4 != 0 runs the element-wise kernels). */
+#define OFLK_ORDER_RGB 0
+#define OFLK_ORDER_BGR 1
+/* device form, one launch: d_frames [F][H][W][C] -> d_luma [F][H][W].  Asynchronous on `stream`. */
+int oflk_luma_u8(const unsigned char *d_frames, int F, int H, int W, int channels, int order, unsigned char *d_luma, void *stream);
+/* host arrays, synchronous, in chunks of at most 64 frames */
+int oflk_luma_u8_host(const unsigned char *frames, int F, int H, int W, int channels, int order, unsigned char *luma);
+/* device forms, one launch for the F frames: d_frames, d_out [F][H][W][C], d_map [F][6] (perspective: [F][9]) float64,
+ * d_inside [F][H][W] bytes or NULL.  Asynchronous on `stream`. */
+int oflk_warp_affine_packed(const unsigned char *d_frames, int F, int H, int W, int channels, const double *d_map,
+                            unsigned char *d_out, unsigned char *d_inside, void *stream);
+int oflk_warp_perspective_packed(const unsigned char *d_frames, int F, int H, int W, int channels, const double *d_map,
+                                 unsigned char *d_out, unsigned char *d_inside, void *stream);
+/* host arrays, synchronous, in chunks of at most 64 frames; the result does not depend on the cut */
+int oflk_warp_affine_packed_host(const unsigned char *frames, int F, int H, int W, int channels, const double *map,
+                                 unsigned char *out, unsigned char *inside);
+int oflk_warp_perspective_packed_host(const unsigned char *frames, int F, int H, int W, int channels, const double *map,
+                                      unsigned char *out, unsigned char *inside);
+/* oflk_stabilize_sequence_u8's arguments with packed frames in and out: frames, out [T][H][W][C] */
+int oflk_stabilize_sequence_packed(const unsigned char *frames, int T, int H, int W, int channels, int order, int levels,
+                                   int window_size, int iters, float alpha, float beta, float max_residual, float quality_level,
+                                   float min_distance, int max_corners, int detect_every, int model, int hypotheses,
+                                   float threshold, unsigned seed, const double *weights, int radius, unsigned char *out,
+                                   float *correction, float *model_out, int *counts_out, unsigned char *held);
+/* oflk_stabilizer_create's arguments with channels and order in place of u8 */
+int oflk_stabilizer_create_packed(oflk_stabilizer **st, int device, int H, int W, int channels, int order, int levels,
+                                  int window_size, int iters, float alpha, float beta, float max_residual, float quality_level,
+                                  float min_distance, int max_corners, int detect_every, int model, int hypotheses, float threshold,
+                                  unsigned seed, const double *weights /* host, [radius + 1], copied */, int radius);
+
 /* Rehearsal of the chunk queue above on a box with fewer GPUs than workers (tests): `workers` > 0 makes the *_multi entry
  * points run that many queue workers, worker i on device i % n_gpus (workers of one device take turns on it); 0 restores
  * one worker per device.  Results do not change. */

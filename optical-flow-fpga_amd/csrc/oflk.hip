@@ -15,6 +15,7 @@
 #include "oflk_stabilize.hpp"
 #include "oflk_mosaic.hpp"
 #include "oflk_align.hpp"
+#include "oflk_colour.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -3888,11 +3889,10 @@ int warp_affine_host(const PIX *frames, int F, int H, int W, const double *map, 
 
 // oflk_stabilize_sequence: pass 1 is the replenish call itself (its chunk loop; only rows come down, into this call's own
 // arrays); the rows go up again for the fit and the trajectory of all T frames, and pass 2 warps the frames chunk by chunk
-template <class PIX>
-int stabilize_sequence(const PIX *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
-                       float max_residual, float q, float md, int K, int detect_every, int model, int hypotheses, float threshold,
-                       unsigned seed, const double *weights, int radius, PIX *out, float *correction, float *model_out,
-                       int *counts_out, unsigned char *held)
+// what the sequence calls refuse, before any device call (frames and out: the call's own pixels, grey or packed)
+int check_stabilize_sequence(const void *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
+                             float max_residual, float q, float md, int K, int detect_every, int model, int hypotheses,
+                             float threshold, const double *weights, int radius, const void *out)
 {
     if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
     int rc = check_warp_affine(frames, T, H, W, frames, out);
@@ -3902,6 +3902,18 @@ int stabilize_sequence(const PIX *frames, int T, int H, int W, int levels, int w
     if ((rc = check_select(q, md, K)) || (rc = check_sparse_test(alpha, beta, max_residual)) ||
         (rc = check_sparse_config(H, W, levels, window_size, iters)))
         return rc;
+    return OFLK_OK;
+}
+
+// Pass 1 and the trajectory of a sequence call on the checked grey frames: begins `call`, leaves the maps of all T frames in
+// its *d_map_out [T][6] and sends the four small outputs on their way (the caller's last chunk synchronises)
+template <class PIX>
+int stabilize_maps(HostCall &call, const PIX *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
+                   float beta, float max_residual, float q, float md, int K, int detect_every, int model, int hypotheses,
+                   float threshold, unsigned seed, const double *weights, int radius, float *correction, float *model_out,
+                   int *counts_out, unsigned char *held, double **d_map_out)
+{
+    int rc;
     const size_t row = (size_t)K, nT = (size_t)T, S = nT - 1;
     std::vector<float> tracks;
     std::vector<unsigned char> visible, born;
@@ -3919,7 +3931,6 @@ int stabilize_sequence(const PIX *frames, int T, int H, int W, int levels, int w
                                   Replenished{{q, md, K, detect_every}, born.data(), detected.data(), nullptr}, K, tracks.data(),
                                   visible.data())))
         return rc;
-    HostCall call;
     if ((rc = call.begin())) return rc;
     float *d_tr, *d_model, *d_corr;
     unsigned char *d_vis, *d_born, *d_inl, *d_held;
@@ -3940,6 +3951,25 @@ int stabilize_sequence(const PIX *frames, int T, int H, int W, int levels, int w
         return rc;
     if ((correction && (rc = call.to_host(correction, d_corr, 6 * nT))) || (model_out && (rc = call.to_host(model_out, d_model, 6 * S))) ||
         (counts_out && (rc = call.to_host(counts_out, d_cnt, 3 * S))) || (held && (rc = call.to_host(held, d_held, S))))
+        return rc;
+    *d_map_out = d_map;
+    return OFLK_OK;
+}
+
+template <class PIX>
+int stabilize_sequence(const PIX *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
+                       float max_residual, float q, float md, int K, int detect_every, int model, int hypotheses, float threshold,
+                       unsigned seed, const double *weights, int radius, PIX *out, float *correction, float *model_out,
+                       int *counts_out, unsigned char *held)
+{
+    int rc = check_stabilize_sequence(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, q, md, K, detect_every,
+                                      model, hypotheses, threshold, weights, radius, out);
+    if (rc) return rc;
+    HostCall call;
+    double *d_map = nullptr;
+    if ((rc = stabilize_maps<PIX>(call, frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, q, md, K, detect_every,
+                                  model, hypotheses, threshold, seed, weights, radius, correction, model_out, counts_out, held,
+                                  &d_map)))
         return rc;
     return warp_affine_chunks<PIX>(call, frames, T, H, W, d_map, out, nullptr);
 }
@@ -4040,6 +4070,230 @@ OFLK_API int oflk_stabilize_sequence_u8(const unsigned char *frames, int T, int 
     return stabilize_sequence<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, quality_level,
                                              min_distance, max_corners, detect_every, model, hypotheses, threshold, seed, weights,
                                              radius, out, correction, model_out, counts_out, held);
+}
+
+// =============================================================================
+// colour video: interleaved bytes [F][H][W][C] -- luma, the packed warps and the packed sequence call (oflk_colour.hpp)
+// =============================================================================
+namespace {
+int check_channels(int channels)
+{
+    if (channels != 3 && channels != 4) return fail(OFLK_ERR_INVALID, "channels must be 3 or 4 (got %d)", channels);
+    return OFLK_OK;
+}
+
+int check_order(int order)
+{
+    if (order != OFLK_ORDER_RGB && order != OFLK_ORDER_BGR)
+        return fail(OFLK_ERR_INVALID, "order must be OFLK_ORDER_RGB or OFLK_ORDER_BGR (got %d)", order);
+    return OFLK_OK;
+}
+
+// the refusals every packed call shares: the planar warp's, and a frame whose bytes a 32-bit offset cannot count
+int check_packed(const void *frames, int F, int H, int W, int channels, const void *out)
+{
+    if (int rc = check_channels(channels)) return rc;
+    if (F < 1) return fail(OFLK_ERR_INVALID, "F must be >= 1 (got %d)", F);
+    if (H < 2 || W < 2) return fail(OFLK_ERR_INVALID, "H and W must be >= 2 (got %d x %d)", H, W);
+    if (!frames || !out) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    if (int rc = check_hw(frames, out, H, W)) return rc;
+    if ((size_t)H * (size_t)W * (size_t)channels >= ((size_t)1 << 31))
+        return fail(OFLK_ERR_UNSUPPORTED, "packed frames of 2^31 bytes or more are not supported");   // 32-bit byte offsets
+    return OFLK_OK;
+}
+
+// the one launch of the luma of F frames on stream s; the arguments are checked
+int luma_launch(const unsigned char *d_frames, int F, int H, int W, int channels, int order, unsigned char *d_luma, hipStream_t s)
+{
+    LumaArgs a{};
+    a.in = d_frames; a.out = d_luma;
+    a.n = (size_t)F * (size_t)H * (size_t)W;
+    a.bgr = order == OFLK_ORDER_BGR;
+    const bool vec = W % kLumaPx == 0 && aligned(d_frames, channels == 4 ? 16 : 4) && aligned(d_luma, 4);
+    const size_t work = vec ? a.n / kLumaPx : a.n;
+    const dim3 grid((unsigned)std::min<size_t>((work + kLumaBlock - 1) / kLumaBlock, (size_t)65535 * 16));
+    if (channels == 3) {
+        if (vec)
+            hipLaunchKernelGGL((k_luma<3, true>), grid, dim3(kLumaBlock), 0, s, a);
+        else
+            hipLaunchKernelGGL((k_luma<3, false>), grid, dim3(kLumaBlock), 0, s, a);
+    } else {
+        if (vec)
+            hipLaunchKernelGGL((k_luma<4, true>), grid, dim3(kLumaBlock), 0, s, a);
+        else
+            hipLaunchKernelGGL((k_luma<4, false>), grid, dim3(kLumaBlock), 0, s, a);
+    }
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+
+// the one launch of the packed warp of F frames on stream s; the arguments are checked
+template <int C, bool PERSP>
+int warp_packed_launch_c(const WarpPackedArgs &a, bool vec, const dim3 grid, hipStream_t s)
+{
+    if (vec)
+        hipLaunchKernelGGL((k_warp_packed<C, PERSP, true>), grid, dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL((k_warp_packed<C, PERSP, false>), grid, dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+
+template <bool PERSP>
+int warp_packed_launch(const unsigned char *d_frames, int F, int H, int W, int channels, const double *d_map, unsigned char *d_out,
+                       unsigned char *d_inside, hipStream_t s)
+{
+    WarpPackedArgs a{};
+    a.in = d_frames; a.map = d_map; a.out = d_out; a.inside = d_inside;
+    a.F = F; a.H = H; a.W = W;
+    // a lane's store: three dwords (C = 3) or one dwordx4 (C = 4), and the inside dword
+    const bool vec = W % kWarpPx == 0 && aligned(d_out, channels == 4 ? 16 : 4) &&
+                     (!d_inside || aligned(d_inside, kWarpPx));
+    const dim3 grid((unsigned)((H + 3) / 4), (unsigned)((W + 64 * kWarpPx - 1) / (64 * kWarpPx)), (unsigned)std::min(F, 65535));
+    return channels == 3 ? warp_packed_launch_c<3, PERSP>(a, vec, grid, s) : warp_packed_launch_c<4, PERSP>(a, vec, grid, s);
+}
+
+// F packed host frames under the device maps d_map, in warp_affine_chunks' chunks through one pair of device buffers
+template <bool PERSP>
+int warp_packed_chunks(HostCall &call, const unsigned char *frames, int F, int H, int W, int channels, const double *d_map,
+                       unsigned char *out, unsigned char *inside)
+{
+    const int C = sparse_chunk_pairs(F, H, W);
+    const size_t plane = (size_t)H * W, fb = plane * (size_t)channels;
+    unsigned char *d_in = nullptr, *d_out = nullptr, *d_inside = nullptr;
+    int rc;
+    if ((rc = call.alloc(&d_in, (size_t)C * fb)) || (rc = call.alloc(&d_out, (size_t)C * fb)) ||
+        (rc = call.alloc(&d_inside, (size_t)C * plane, inside != nullptr)))
+        return rc;
+    for (int f0 = 0; f0 < F; f0 += C) {
+        const int n = std::min(C, F - f0);
+        const size_t o = (size_t)f0 * fb, len = (size_t)n * fb;
+        if ((rc = call.to_device(d_in, frames + o, len)) ||
+            (rc = warp_packed_launch<PERSP>(d_in, n, H, W, channels, d_map + (PERSP ? 9 : 6) * (size_t)f0, d_out, d_inside, nullptr)) ||
+            (rc = call.to_host(out + o, d_out, len)) ||
+            (inside && (rc = call.to_host(inside + (size_t)f0 * plane, d_inside, (size_t)n * plane))) || (rc = call.sync()))
+            return rc;
+    }
+    return OFLK_OK;
+}
+
+template <bool PERSP>
+int warp_packed_host(const unsigned char *frames, int F, int H, int W, int channels, const double *map, unsigned char *out,
+                     unsigned char *inside)
+{
+    int rc = check_packed(frames, F, H, W, channels, out);
+    if (rc) return rc;
+    if (!map) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    double *d_map = nullptr;
+    if ((rc = call.upload(&d_map, map, (PERSP ? 9 : 6) * (size_t)F))) return rc;
+    return warp_packed_chunks<PERSP>(call, frames, F, H, W, channels, d_map, out, inside);
+}
+
+template <bool PERSP>
+int warp_packed_device(const unsigned char *d_frames, int F, int H, int W, int channels, const double *d_map, unsigned char *d_out,
+                       unsigned char *d_inside, void *stream)
+{
+    if (int rc = check_packed(d_frames, F, H, W, channels, d_out)) return rc;
+    if (!d_map) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    if (!aligned(d_map, 8)) return fail(OFLK_ERR_INVALID, "d_map must be 8-byte aligned");
+    return warp_packed_launch<PERSP>(d_frames, F, H, W, channels, d_map, d_out, d_inside, (hipStream_t)stream);
+}
+
+// the luma of F packed host frames in the warp's chunks: a chunk goes up, is converted and its luma comes down
+int luma_chunks(HostCall &call, const unsigned char *frames, int F, int H, int W, int channels, int order, unsigned char *luma)
+{
+    const int C = sparse_chunk_pairs(F, H, W);
+    const size_t plane = (size_t)H * W, fb = plane * (size_t)channels;
+    unsigned char *d_in = nullptr, *d_out = nullptr;
+    int rc;
+    if ((rc = call.alloc(&d_in, (size_t)C * fb)) || (rc = call.alloc(&d_out, (size_t)C * plane))) return rc;
+    for (int f0 = 0; f0 < F; f0 += C) {
+        const int n = std::min(C, F - f0);
+        if ((rc = call.to_device(d_in, frames + (size_t)f0 * fb, (size_t)n * fb)) ||
+            (rc = luma_launch(d_in, n, H, W, channels, order, d_out, nullptr)) ||
+            (rc = call.to_host(luma + (size_t)f0 * plane, d_out, (size_t)n * plane)) || (rc = call.sync()))
+            return rc;
+    }
+    return OFLK_OK;
+}
+}  // namespace
+
+OFLK_API int oflk_luma_u8(const unsigned char *d_frames, int F, int H, int W, int channels, int order, unsigned char *d_luma,
+                          void *stream)
+{
+    int rc = check_packed(d_frames, F, H, W, channels, d_luma);
+    if (rc || (rc = check_order(order))) return rc;
+    return luma_launch(d_frames, F, H, W, channels, order, d_luma, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_luma_u8_host(const unsigned char *frames, int F, int H, int W, int channels, int order, unsigned char *luma)
+{
+    int rc = check_packed(frames, F, H, W, channels, luma);
+    if (rc || (rc = check_order(order))) return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    return luma_chunks(call, frames, F, H, W, channels, order, luma);
+}
+
+OFLK_API int oflk_warp_affine_packed(const unsigned char *d_frames, int F, int H, int W, int channels, const double *d_map,
+                                     unsigned char *d_out, unsigned char *d_inside, void *stream)
+{
+    return warp_packed_device<false>(d_frames, F, H, W, channels, d_map, d_out, d_inside, stream);
+}
+
+OFLK_API int oflk_warp_perspective_packed(const unsigned char *d_frames, int F, int H, int W, int channels, const double *d_map,
+                                          unsigned char *d_out, unsigned char *d_inside, void *stream)
+{
+    return warp_packed_device<true>(d_frames, F, H, W, channels, d_map, d_out, d_inside, stream);
+}
+
+OFLK_API int oflk_warp_affine_packed_host(const unsigned char *frames, int F, int H, int W, int channels, const double *map,
+                                          unsigned char *out, unsigned char *inside)
+{
+    return warp_packed_host<false>(frames, F, H, W, channels, map, out, inside);
+}
+
+OFLK_API int oflk_warp_perspective_packed_host(const unsigned char *frames, int F, int H, int W, int channels, const double *map,
+                                               unsigned char *out, unsigned char *inside)
+{
+    return warp_packed_host<true>(frames, F, H, W, channels, map, out, inside);
+}
+
+// The luma of all T frames comes down into a host array of its own (one byte per pixel: a third or a quarter of the caller's
+// frames) in a chunked pass ahead of pass 1, which then is the grey call's on that array; pass 2 warps the packed frames
+OFLK_API int oflk_stabilize_sequence_packed(const unsigned char *frames, int T, int H, int W, int channels, int order, int levels,
+                                            int window_size, int iters, float alpha, float beta, float max_residual,
+                                            float quality_level, float min_distance, int max_corners, int detect_every, int model,
+                                            int hypotheses, float threshold, unsigned seed, const double *weights, int radius,
+                                            unsigned char *out, float *correction, float *model_out, int *counts_out,
+                                            unsigned char *held)
+{
+    int rc = check_channels(channels);
+    if (rc || (rc = check_order(order))) return rc;
+    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
+    if ((rc = check_packed(frames, T, H, W, channels, out)) ||
+        (rc = check_stabilize_sequence(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, quality_level,
+                                       min_distance, max_corners, detect_every, model, hypotheses, threshold, weights, radius, out)))
+        return rc;
+    std::vector<unsigned char> luma;
+    try {
+        luma.resize((size_t)T * H * W);
+    } catch (const std::exception &) {
+        return fail(OFLK_ERR_NOMEM, "no host memory for the luma of %d frames of %d x %d", T, W, H);
+    }
+    {
+        HostCall call;
+        if ((rc = call.begin()) || (rc = luma_chunks(call, frames, T, H, W, channels, order, luma.data()))) return rc;
+    }
+    HostCall call;
+    double *d_map = nullptr;
+    if ((rc = stabilize_maps<unsigned char>(call, luma.data(), T, H, W, levels, window_size, iters, alpha, beta, max_residual,
+                                            quality_level, min_distance, max_corners, detect_every, model, hypotheses, threshold, seed,
+                                            weights, radius, correction, model_out, counts_out, held, &d_map)))
+        return rc;
+    return warp_packed_chunks<false>(call, frames, T, H, W, channels, d_map, out, nullptr);
 }
 
 // =============================================================================
@@ -5118,8 +5372,12 @@ struct oflk_stabilizer {
     int *own_counts = nullptr;
     char *stage_out = nullptr;        // [H][W] in the pixel type and [H][W] bytes: the host forms' staging
     unsigned char *stage_inside = nullptr;
+    // oflk_stabilizer_create_packed: the delay line and every frame in and out are [H][W][channels] bytes, and the tracker
+    // (uint8) is pushed the luma of the frame, formed in `luma` by the push
+    int channels = 0, order = 0;      // 0 channels: a grey stabiliser
+    unsigned char *luma = nullptr;    // [H][W]
 
-    size_t plane_bytes() const { return (size_t)tr->H * tr->W * tr->pix_bytes(); }
+    size_t plane_bytes() const { return (size_t)tr->H * tr->W * (channels ? (size_t)channels : tr->pix_bytes()); }
     char *slot(long long f) const { return delay + (size_t)(f % (r + 1)) * plane_bytes(); }
 };
 
@@ -5155,6 +5413,9 @@ int stabilizer_warp(const oflk_stabilizer *st, const void *d_frames, int F, cons
                     hipStream_t s)
 {
     const oflk_tracker *tr = st->tr;
+    if (st->channels)
+        return warp_packed_launch<false>((const unsigned char *)d_frames, F, tr->H, tr->W, st->channels, d_map, (unsigned char *)d_out,
+                                         d_inside, s);
     int rc = OFLK_OK;
     with_pix(tr->u8, [&](auto PIX) {
         using P = typename decltype(PIX)::type;
@@ -5175,7 +5436,8 @@ int stabilizer_ensure_state(oflk_stabilizer *st)
     if ((rc = dmalloc(&st->delay, (size_t)(st->r + 1) * st->plane_bytes(), &st->ws_bytes)) ||
         (rc = dmalloc(&st->ring_model, 6 * (size_t)st->cap, &st->ws_bytes)) ||
         (rc = dmalloc(&st->ring_counts, 3 * (size_t)st->cap, &st->ws_bytes)) || (rc = dmalloc(&st->corr, 6 * rows, &st->ws_bytes)) ||
-        (rc = dmalloc(&st->map, 6 * rows, &st->ws_bytes)))
+        (rc = dmalloc(&st->map, 6 * rows, &st->ws_bytes)) ||
+        (st->channels && (rc = dmalloc(&st->luma, (size_t)tr->H * tr->W, &st->ws_bytes))))
         return rc;
     st->own_model = tr->m_out;
     st->own_counts = tr->m_counts;
@@ -5212,8 +5474,11 @@ int stabilizer_enqueue(oflk_stabilizer *st, const void *src, hipMemcpyKind kind,
     const size_t k = t >= 1 ? (size_t)((t - 1) % st->cap) : 0;
     tr->m_out = t >= 1 ? st->ring_model + 6 * k : st->own_model;
     tr->m_counts = t >= 1 ? st->ring_counts + 3 * k : st->own_counts;
-    int rc = tracker_push(tr, frame, hipMemcpyDeviceToDevice, s);
-    if (rc) return rc;
+    int rc = OFLK_OK;
+    if (st->channels &&
+        (rc = luma_launch((const unsigned char *)frame, 1, tr->H, tr->W, st->channels, st->order, st->luma, s)))
+        return rc;
+    if ((rc = tracker_push(tr, st->channels ? (const void *)st->luma : (const void *)frame, hipMemcpyDeviceToDevice, s))) return rc;
     if (t >= st->r) {
         const long long e = t - st->r;
         if ((rc = trajectory_ring_launch(st->ring_model, st->ring_counts, st->cap, (int)e, 1, -1, st->wt, st->r, st->corr, st->map, s)) ||
@@ -5302,6 +5567,25 @@ OFLK_API int oflk_stabilizer_create(oflk_stabilizer **out, int device, int H, in
     return OFLK_OK;
 }
 
+OFLK_API int oflk_stabilizer_create_packed(oflk_stabilizer **out, int device, int H, int W, int channels, int order, int levels,
+                                           int window_size, int iters, float alpha, float beta, float max_residual,
+                                           float quality_level, float min_distance, int max_corners, int detect_every, int model,
+                                           int hypotheses, float threshold, unsigned seed, const double *weights, int radius)
+{
+    if (!out) return fail(OFLK_ERR_INVALID, "stabiliser pointer is NULL");
+    *out = nullptr;
+    int rc = check_channels(channels);
+    if (rc || (rc = check_order(order))) return rc;
+    if (H >= 2 && W >= 2 && (size_t)H * (size_t)W * (size_t)channels >= ((size_t)1 << 31))
+        return fail(OFLK_ERR_UNSUPPORTED, "packed frames of 2^31 bytes or more are not supported");
+    if ((rc = oflk_stabilizer_create(out, device, H, W, 1, levels, window_size, iters, alpha, beta, max_residual, quality_level,
+                                     min_distance, max_corners, detect_every, model, hypotheses, threshold, seed, weights, radius)))
+        return rc;
+    (*out)->channels = channels;
+    (*out)->order = order;
+    return OFLK_OK;
+}
+
 OFLK_API int oflk_stabilizer_destroy(oflk_stabilizer *st)
 {
     if (!st) return OFLK_OK;
@@ -5311,7 +5595,7 @@ OFLK_API int oflk_stabilizer_destroy(oflk_stabilizer *st)
     }
     if (st->ws_bytes) (void)hipSetDevice(st->tr->device);
     for (void *q : {(void *)st->delay, (void *)st->ring_model, (void *)st->ring_counts, (void *)st->corr, (void *)st->map,
-                    (void *)st->stage_out, (void *)st->stage_inside})
+                    (void *)st->stage_out, (void *)st->stage_inside, (void *)st->luma})
         if (q) (void)hipFree(q);
     tracker_free(st->tr);
     delete st;

@@ -168,6 +168,14 @@ SIGNATURES = {
     "oflk_stabilizer_flush": (ctypes.c_int, [_vp, _vp, _vp, _f32p, _i32p, _i32p]),
     "oflk_stabilizer_correction_device": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     "oflk_stabilizer_tracker": (_vp, [_vp]),
+    "oflk_luma_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_vp, _vp]),
+    "oflk_luma_u8_host": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_vp]),
+    "oflk_warp_affine_packed": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_vp] * 4),
+    "oflk_warp_perspective_packed": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_vp] * 4),
+    "oflk_warp_affine_packed_host": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_f64p, _vp, _vp]),
+    "oflk_warp_perspective_packed_host": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_f64p, _vp, _vp]),
+    "oflk_stabilize_sequence_packed": (ctypes.c_int, [_vp] + [ctypes.c_int] * 8 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int, _vp, _f32p, _f32p, _i32p, _vp]),
+    "oflk_stabilizer_create_packed": (ctypes.c_int, [ctypes.POINTER(_vp)] + [ctypes.c_int] * 8 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int]),
     "oflk_shard_range": (None, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, _i32p]),
     "oflk_single_scale_fp16": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, _f32p, _f32p]),
     "oflk_rtl_stream_length": (ctypes.c_long, [ctypes.c_int, ctypes.c_int]),
@@ -793,6 +801,75 @@ def warp_affine_host(frames: np.ndarray, maps: np.ndarray, inside: bool = False)
     return out, ins
 
 
+COLOUR_ORDERS = {"rgb": 0, "bgr": 1}
+
+
+def check_colour_order(order) -> int:
+    """the C ABI's code of a channel order given by name; ValueError for anything else"""
+    if not isinstance(order, str) or order not in COLOUR_ORDERS:
+        raise ValueError(f"order must be one of {sorted(COLOUR_ORDERS)}, got {order!r}")
+    return COLOUR_ORDERS[order]
+
+
+def is_packed(frames, ndim: int = 4) -> bool:
+    """True for an array with a trailing channel axis: `ndim` dimensions where the grey form has ndim - 1"""
+    return isinstance(frames, np.ndarray) and frames.ndim == ndim
+
+
+def as_packed(frames, what: str = "(F, H, W, C)") -> np.ndarray:
+    """Interleaved colour frames as one contiguous uint8 (F, H, W, C) array, C in {3, 4} and H, W >= 2.  ValueError for
+    anything else, float32 colour included; no device call."""
+    if not isinstance(frames, np.ndarray) or frames.ndim != 4:
+        raise ValueError(f"expected a {what} array of colour frames, got shape {np.shape(frames)}")
+    if frames.dtype != np.uint8:
+        raise ValueError(f"colour frames must be uint8 (float32 colour is not offered), got {frames.dtype}")
+    F, H, W, C = frames.shape
+    if C not in (3, 4):
+        raise ValueError(f"colour frames must have 3 or 4 interleaved channels, got {C}")
+    if F < 1 or H < 2 or W < 2:
+        raise ValueError(f"expected at least one frame of at least 2 x 2 pixels, got shape {frames.shape}")
+    return np.ascontiguousarray(frames)
+
+
+def luma(d_frames: int, F: int, H: int, W: int, channels: int, d_luma: int, order: int = 0, stream: int = 0) -> None:
+    """oflk_luma_u8 on device pointers: d_frames [F][H][W][channels] uint8 -> d_luma [F][H][W] uint8; asynchronous."""
+    check(lib().oflk_luma_u8(d_frames or None, int(F), int(H), int(W), int(channels), int(order), d_luma or None, stream))
+
+
+def luma_host(frames: np.ndarray, order: int = 0) -> np.ndarray:
+    """oflk_luma_u8_host: contiguous uint8 (F, H, W, C) frames in, their (F, H, W) uint8 luma out"""
+    F, H, W, C = frames.shape
+    out = np.empty((F, H, W), np.uint8)
+    check(lib().oflk_luma_u8_host(frames.ctypes.data, F, H, W, C, int(order), out.ctypes.data))
+    return out
+
+
+def warp_affine_packed(d_frames: int, F: int, H: int, W: int, channels: int, d_map: int, d_out: int, d_inside: int = 0,
+                       stream: int = 0) -> None:
+    """oflk_warp_affine_packed on device pointers: frames and d_out [F][H][W][channels] uint8, d_map [F][6] float64, d_inside
+    [F][H][W] uint8 or 0; asynchronous."""
+    check(lib().oflk_warp_affine_packed(d_frames or None, int(F), int(H), int(W), int(channels), d_map or None, d_out or None,
+                                        d_inside or None, stream))
+
+
+def warp_perspective_packed(d_frames: int, F: int, H: int, W: int, channels: int, d_map: int, d_out: int, d_inside: int = 0,
+                            stream: int = 0) -> None:
+    """oflk_warp_perspective_packed on device pointers: oflk_warp_affine_packed's arguments with d_map [F][9]; asynchronous."""
+    check(lib().oflk_warp_perspective_packed(d_frames or None, int(F), int(H), int(W), int(channels), d_map or None, d_out or None,
+                                             d_inside or None, stream))
+
+
+def warp_packed_host(frames: np.ndarray, maps: np.ndarray, inside: bool = False):
+    """oflk_warp_affine_packed_host -- oflk_warp_perspective_packed_host for (F, 9) maps --: contiguous uint8 (F, H, W, C) frames
+    and float64 maps in; the warped frames and, when asked for, the (F, H, W) inside mask (else None) out"""
+    F, H, W, C = frames.shape
+    out = np.empty_like(frames)
+    ins = np.empty((F, H, W), np.uint8) if inside else None
+    fn = lib().oflk_warp_perspective_packed_host if maps.shape[-1] == 9 else lib().oflk_warp_affine_packed_host
+    check(fn(frames.ctypes.data, F, H, W, C, _f64(maps), out.ctypes.data, None if ins is None else ins.ctypes.data))
+    return out, ins
+
+
 MOSAIC_BLENDS = {"mean": 0, "feather": 1, "first": 2, "last": 3}
 
 
@@ -1040,15 +1117,22 @@ class Stabilizer:
     def __init__(self, device: int, H: int, W: int, u8: bool, max_corners: int, detect_every: int, model: int, weights: np.ndarray,
                  hypotheses: int = 256, threshold: float = 1.0, seed: int = 0, levels: int = 3, window_size: int = 5, iters: int = 3,
                  alpha: float = 0.01, beta: float = 0.5, max_residual: float = 4.0, quality_level: float = 0.01,
-                 min_distance: float = 10.0):
+                 min_distance: float = 10.0, channels: int = 0, order: int = 0):
         self._h = _vp()
         self.H, self.W, self.u8, self.K = int(H), int(W), bool(u8), int(max_corners)
+        self.channels = int(channels)   # 0: grey frames (H, W); 3 or 4: packed uint8 frames (H, W, channels), luma to the tracker
         w = np.ascontiguousarray(weights, np.float64)
         self.radius = int(w.size) - 1
-        check(lib().oflk_stabilizer_create(ctypes.byref(self._h), int(device), int(H), int(W), int(bool(u8)), int(levels),
-                                           int(window_size), int(iters), float(alpha), float(beta), float(max_residual),
-                                           float(quality_level), float(min_distance), int(max_corners), int(detect_every), int(model),
-                                           int(hypotheses), float(threshold), int(seed), _f64(w), self.radius))
+        tail = (int(levels), int(window_size), int(iters), float(alpha), float(beta), float(max_residual), float(quality_level),
+                float(min_distance), int(max_corners), int(detect_every), int(model), int(hypotheses), float(threshold), int(seed),
+                _f64(w), self.radius)
+        if self.channels:
+            if not self.u8:
+                raise ValueError("colour frames must be uint8 (float32 colour is not offered)")
+            check(lib().oflk_stabilizer_create_packed(ctypes.byref(self._h), int(device), int(H), int(W), self.channels, int(order),
+                                                      *tail))
+        else:
+            check(lib().oflk_stabilizer_create(ctypes.byref(self._h), int(device), int(H), int(W), int(bool(u8)), *tail))
         self.tracker = Tracker._borrowed(_vp(lib().oflk_stabilizer_tracker(self._h)), H, W, u8, max_corners)
 
     def close(self) -> None:
@@ -1100,13 +1184,16 @@ class Stabilizer:
     def _dtype(self):
         return np.uint8 if self.u8 else np.float32
 
+    def _shape(self):
+        return (self.H, self.W, self.channels) if self.channels else (self.H, self.W)
+
     def push(self, frame: np.ndarray, inside: bool = False):
-        """a contiguous host frame (H, W) of the stabiliser's element type in; (emitted index or -1, frame (H, W) or None,
-        correction (6,) float32 or None, inside (H, W) uint8 or None) out"""
-        if not (isinstance(frame, np.ndarray) and frame.dtype == self._dtype() and frame.shape == (self.H, self.W)
+        """a contiguous host frame (H, W) -- (H, W, channels) for a colour stabiliser -- of the stabiliser's element type in;
+        (emitted index or -1, frame of that shape or None, correction (6,) float32 or None, inside (H, W) uint8 or None) out"""
+        if not (isinstance(frame, np.ndarray) and frame.dtype == self._dtype() and frame.shape == self._shape()
                 and frame.flags["C_CONTIGUOUS"]):
-            raise ValueError(f"expected a contiguous {np.dtype(self._dtype()).name} frame of shape {(self.H, self.W)}")
-        out, corr = np.empty((self.H, self.W), self._dtype()), np.empty(6, np.float32)
+            raise ValueError(f"expected a contiguous {np.dtype(self._dtype()).name} frame of shape {self._shape()}")
+        out, corr = np.empty(self._shape(), self._dtype()), np.empty(6, np.float32)
         ins = np.empty((self.H, self.W), np.uint8) if inside else None
         e = ctypes.c_int(-1)
         check(lib().oflk_stabilizer_push(self._h, frame.ctypes.data, out.ctypes.data, None if ins is None else ins.ctypes.data,
@@ -1116,9 +1203,10 @@ class Stabilizer:
         return int(e.value), out, corr, ins
 
     def flush(self, inside: bool = False):
-        """(first, frames (count, H, W), correction (count, 6) float32, inside (count, H, W) uint8 or None)"""
+        """(first, frames (count, H, W) or (count, H, W, channels), correction (count, 6) float32, inside (count, H, W) uint8
+        or None)"""
         n = max(self.radius, 1)
-        out, corr = np.empty((n, self.H, self.W), self._dtype()), np.empty((n, 6), np.float32)
+        out, corr = np.empty((n,) + self._shape(), self._dtype()), np.empty((n, 6), np.float32)
         ins = np.empty((n, self.H, self.W), np.uint8) if inside else None
         first, count = ctypes.c_int(0), ctypes.c_int(0)
         check(lib().oflk_stabilizer_flush(self._h, out.ctypes.data, None if ins is None else ins.ctypes.data, ptr(corr),

@@ -380,11 +380,42 @@ def stabilize_trajectory(models, status=None, radius: int = 15, sigma=None) -> T
     return Trajectory(corr.reshape(-1, 2, 3), mp.reshape(-1, 2, 3), held.astype(bool))
 
 
+def rgb_to_luma(frames, order: str = "rgb"):
+    """The luma of interleaved colour frames, on the GPU: Y = (77 R + 150 G + 29 B + 128) >> 8 in integers, so grey input
+    returns itself.  frames: (H, W, C) or (F, H, W, C) uint8 with C = 3 or 4 (a fourth channel is ignored); order: "rgb" or
+    "bgr", where R, G and B sit among the first three bytes.  Returns (H, W) or (F, H, W) uint8: what the tracking and flow
+    calls, which take one plane, are given for colour video."""
+    code = _oflk.check_colour_order(order)
+    single = isinstance(frames, np.ndarray) and frames.ndim == 3
+    arr = _oflk.as_packed(frames[None] if single else frames, "(H, W, C) or (F, H, W, C)")
+    out = _oflk.luma_host(arr, code)
+    return out[0] if single else out
+
+
+def _warp_packed(frames, maps, return_inside: bool, n: int):
+    """warp_affine (n = 6) / warp_perspective (n = 9) of a 4-D array: interleaved colour frames"""
+    arr = _oflk.as_packed(frames)
+    F = arr.shape[0]
+    m = np.ascontiguousarray(maps, np.float64)
+    rows = (3, 6) if n == 6 else (3, 9)
+    if m.size != n * F or m.ndim not in (1, 2, 3) or m.shape[-1] not in rows or (n == 9 and m.shape[-1] == 3 and (m.ndim < 2 or m.shape[-2] != 3)):
+        raise ValueError(f"expected {F} maps of shape {(2, 3) if n == 6 else (3, 3)} or ({n},), got {np.shape(maps)}")
+    out, ins = _oflk.warp_packed_host(arr, m.reshape(F, n), bool(return_inside))
+    return (out, ins.astype(bool)) if return_inside else out
+
+
 def warp_affine(frames, maps, return_inside: bool = False):
     """Resample frames under one 2 x 3 map each, on the GPU: out[f, y, x] is the bilinear sample (zero outside) of frame f at
     (xs, ys) = maps[f] applied to (x, y) in float64.  frames: (H, W) or (F, H, W), float32 or uint8 (uint8 out: rounded half
     to even); maps: (2, 3) / (6,) for one frame, (F, 2, 3) / (F, 6) for a batch, e.g. Trajectory.map.  With return_inside
-    also the (F, H, W) bool mask of the pixels whose source position lies inside the frame."""
+    also the (F, H, W) bool mask of the pixels whose source position lies inside the frame.
+
+    A 4-D uint8 array (F, H, W, C), C = 3 or 4, is a batch of interleaved colour frames: the source position is formed once
+    per pixel and every channel is sampled there, each channel's bytes being those of this call on its plane; the result has
+    the same shape and the mask stays (F, H, W).  A 3-D array keeps meaning (F, H, W) grey frames, so one colour frame is
+    passed as frame[None]; float32 colour is refused."""
+    if _oflk.is_packed(frames):
+        return _warp_packed(frames, maps, return_inside, 6)
     single = isinstance(frames, np.ndarray) and frames.ndim == 2
     arr, _ = _oflk.as_frames(frames)
     F, H, W = arr.shape
@@ -406,7 +437,12 @@ def warp_perspective(frames, maps, return_inside: bool = False):
     where the divisor is not positive or the source position leaves the frame.  frames: (H, W) or (F, H, W), float32 or
     uint8 (uint8 out: rounded half to even); maps: (3, 3) / (9,) for one frame, (F, 3, 3) / (F, 9) for a batch, e.g.
     Homography.model: the map takes an output pixel to its source, so warp_perspective(frames[t+1], model[t]) registers
-    frame t+1 onto frame t.  With return_inside also the (F, H, W) bool mask of the pixels that were sampled."""
+    frame t+1 onto frame t.  With return_inside also the (F, H, W) bool mask of the pixels that were sampled.
+
+    A 4-D uint8 array (F, H, W, C), C = 3 or 4, is a batch of interleaved colour frames, as in warp_affine: the same shape
+    comes back, the mask stays (F, H, W), a 3-D array keeps meaning (F, H, W) grey frames and float32 colour is refused."""
+    if _oflk.is_packed(frames):
+        return _warp_packed(frames, maps, return_inside, 9)
     single = isinstance(frames, np.ndarray) and frames.ndim == 2
     arr, _ = _oflk.as_frames(frames)
     F, H, W = arr.shape
@@ -477,7 +513,16 @@ def mosaic_composite(frames, maps, canvas_shape, origin=(0, 0), skip=None, blend
     from the frame's nearest edge); "first" / "last" (the lowest / highest frame that covers the pixel).  frames: (F, H, W)
     float32 or uint8 (uint8 out: rounded half to even); skip: (F,) flags of frames to leave out, e.g. MosaicChain.dropped.
     Returns the (Hc, Wc) canvas, zero where no frame reaches; with return_count also the (Hc, Wc) int32 number of frames that
-    cover each pixel."""
+    cover each pixel.
+
+    A 4-D uint8 array (F, H, W, C), C = 3 or 4, is a batch of interleaved colour frames: every channel's plane is blended by a
+    call of its own under the same maps and the canvases are stacked to (Hc, Wc, C); the count is the one count of them all."""
+    if _oflk.is_packed(frames):
+        arr = _oflk.as_packed(frames)
+        planes = [mosaic_composite(np.ascontiguousarray(arr[..., c]), maps, canvas_shape, origin, skip, blend, True)
+                  for c in range(arr.shape[-1])]
+        canvas = np.stack([p[0] for p in planes], axis=-1)
+        return (canvas, planes[0][1]) if return_count else canvas
     arr, _ = _oflk.as_frames(frames)
     F, H, W = arr.shape
     if H < 2 or W < 2:

@@ -32,7 +32,7 @@ import numpy.typing as npt
 import _oflk
 from lucas_kanade_core import (Alignment, Homography, MosaicChain, Motion, Trajectory, estimate_homography,  # noqa: F401
                                estimate_motion, lucas_kanade_single_scale, mosaic_chain, mosaic_composite, refine_alignment,
-                               sequence_refine_alignment, stabilize_trajectory, tracks_homography, tracks_motion, warp_affine,
+                               rgb_to_luma, sequence_refine_alignment, stabilize_trajectory, tracks_homography, tracks_motion, warp_affine,
                                warp_perspective)
 
 SCRIPT_DIR = Path(__file__).resolve().parent
@@ -464,7 +464,7 @@ def lucas_kanade_pyramidal_sequence_klt_sparse_replenish(frames, max_corners: in
 
 class SequenceStabilized(NamedTuple):
     """Result of lucas_kanade_pyramidal_sequence_stabilize."""
-    frames: np.ndarray      # (T, H, W), the input's type: the steadied frames, zero where the source lies outside the frame
+    frames: np.ndarray      # (T, H, W) -- (T, H, W, C) for colour --, the input's type: the steadied frames, zero outside
     correction: np.ndarray  # (T, 2, 3) float32: where frame t's content was moved to (Trajectory.correction)
     model: np.ndarray       # (T-1, 2, 3) float32: the fitted motion of step t -> t+1; NaN where status is 0
     status: np.ndarray      # (T-1,) int32: 1 where a model was found
@@ -476,7 +476,8 @@ def lucas_kanade_pyramidal_sequence_stabilize(frames, max_corners: int, detect_e
                                               seed: int = 0, quality_level: float = 0.01, min_distance: float = 10.0,
                                               num_levels: int = 3, window_size: int = 5, num_iterations: int = 3,
                                               alpha: float = 0.01, beta: float = 0.5, max_residual: float = 4.0,
-                                              refine_iterations: int = 0, refine_levels: int = 3) -> SequenceStabilized:
+                                              refine_iterations: int = 0, refine_levels: int = 3,
+                                              order: str = "rgb") -> SequenceStabilized:
     """Frames in, steadied frames out: lucas_kanade_pyramidal_sequence_klt_sparse_replenish on the frames, tracks_motion on
     its rows, stabilize_trajectory on the models and warp_affine of the frames under its maps, in one call whose
     intermediate rows stay in the library.  The frames go up twice, chunk by chunk (once to track, once to warp); nothing
@@ -485,20 +486,36 @@ def lucas_kanade_pyramidal_sequence_stabilize(frames, max_corners: int, detect_e
 
     refine_iterations > 0: the same chain made of its public parts, with sequence_refine_alignment (kind "affine",
     refine_levels levels, refine_iterations iterations each) between the fit and the trajectory: every fitted step is refined
-    on the pixels of its two frames, and a step that cannot be refined keeps the fitted model."""
+    on the pixels of its two frames, and a step that cannot be refined keeps the fitted model.
+
+    A 4-D uint8 array (T, H, W, C), C = 3 or 4, is interleaved colour video with R, G and B where `order` ("rgb" or "bgr")
+    says: the motion is tracked, fitted and (with refine_iterations) refined on rgb_to_luma of the frames, exactly as this
+    call does on that luma, and the colour frames are warped under the maps of that trajectory, every channel at one source
+    position; .frames then has the input's shape."""
     if isinstance(refine_iterations, bool) or int(refine_iterations) != refine_iterations or int(refine_iterations) < 0:
         raise ValueError(f"refine_iterations must be an integer >= 0, got {refine_iterations!r}")
+    colour = _oflk.is_packed(frames)
+    code_order = _oflk.check_colour_order(order)
+    if colour:
+        packed = _oflk.as_packed(frames, "(T, H, W, C)")
     if int(refine_iterations) > 0:
-        rows = lucas_kanade_pyramidal_sequence_klt_sparse_replenish(frames, max_corners, detect_every, quality_level, min_distance,
+        grey = rgb_to_luma(packed, order) if colour else frames
+        rows = lucas_kanade_pyramidal_sequence_klt_sparse_replenish(grey, max_corners, detect_every, quality_level, min_distance,
                                                                     num_levels, window_size, num_iterations, alpha, beta, max_residual)
         fit = tracks_motion(rows.tracks, rows.visible, rows.born, model, hypotheses, threshold, seed)
-        arr, _ = _oflk.as_sequence(frames)
+        arr, _ = _oflk.as_sequence(grey)
         al = sequence_refine_alignment(arr, fit.model, fit.status, "affine", refine_levels, int(refine_iterations))
         tr = stabilize_trajectory(al.model, fit.status, radius, sigma)
-        return SequenceStabilized(warp_affine(arr, tr.map), tr.correction, al.model, fit.status, tr.held)
+        return SequenceStabilized(warp_affine(packed if colour else arr, tr.map), tr.correction, al.model, fit.status, tr.held)
     a, b = _oflk.check_fb_params(alpha, beta)
-    arr, u8 = _oflk.as_sequence(frames)
-    T, H, W = arr.shape
+    if colour:
+        if packed.shape[0] < 2:
+            raise ValueError(f"a sequence needs at least 2 frames, got {packed.shape[0]}")
+        arr, u8 = packed, True
+        T, H, W, C = arr.shape
+    else:
+        arr, u8 = _oflk.as_sequence(frames)
+        T, H, W = arr.shape
     L, win, it, r = _oflk.check_sparse_params((H, W), num_levels, window_size, num_iterations, max_residual)
     K, q, md, win = _oflk.check_feature_params(max_corners, quality_level, min_distance, win)
     if isinstance(detect_every, bool) or int(detect_every) != detect_every or int(detect_every) < 1:
@@ -508,6 +525,12 @@ def lucas_kanade_pyramidal_sequence_stabilize(frames, max_corners: int, detect_e
     out = np.empty_like(arr)
     corr, mod = np.empty((T, 6), np.float32), np.empty((T - 1, 6), np.float32)
     cnt, held = np.empty((T - 1, 3), np.int32), np.empty(T - 1, np.uint8)
+    if colour:
+        _oflk.check(_oflk.lib().oflk_stabilize_sequence_packed(
+            arr.ctypes.data, T, H, W, C, code_order, L, win, it, a, b, r, q, md, K, min(int(detect_every), 2 ** 31 - 1), code, hn, thr,
+            sd, _oflk._f64(w), int(w.size) - 1, out.ctypes.data, _oflk.ptr(corr), _oflk.ptr(mod), cnt.ctypes.data_as(_oflk._i32p),
+            held.ctypes.data))
+        return SequenceStabilized(out, corr.reshape(T, 2, 3), mod.reshape(T - 1, 2, 3), cnt[:, 2].copy(), held.astype(bool))
     fn = _oflk.lib().oflk_stabilize_sequence_u8 if u8 else _oflk.lib().oflk_stabilize_sequence
     _oflk.check(fn(arr.ctypes.data if u8 else _oflk.ptr(arr), T, H, W, L, win, it, a, b, r, q, md, K,
                    min(int(detect_every), 2 ** 31 - 1), code, hn, thr, sd, _oflk._f64(w), int(w.size) - 1,
@@ -518,7 +541,7 @@ def lucas_kanade_pyramidal_sequence_stabilize(frames, max_corners: int, detect_e
 
 class Mosaic(NamedTuple):
     """Result of lucas_kanade_pyramidal_sequence_mosaic."""
-    canvas: np.ndarray      # (Hc, Wc), the input's type: the blended frames in the anchor's coordinates, zero where none reaches
+    canvas: np.ndarray      # (Hc, Wc) -- (Hc, Wc, C) for colour --, the input's type: the blended frames in the anchor's coordinates
     count: np.ndarray       # (Hc, Wc) int32: the number of frames that cover each pixel
     origin: tuple           # (x0, y0): the anchor coordinates of canvas pixel (0, 0)
     to_anchor: np.ndarray   # (T, 3, 3) float64: frame t's coordinates to the anchor's (MosaicChain.to_anchor)
@@ -533,7 +556,7 @@ def lucas_kanade_pyramidal_sequence_mosaic(frames, max_corners: int = 1000, dete
                                            min_distance: float = 10.0, num_levels: int = 3, window_size: int = 5,
                                            num_iterations: int = 3, alpha: float = 0.01, beta: float = 0.5, max_residual: float = 4.0,
                                            anchor: int = 0, extent=None, blend: str = "feather", max_pixels=None,
-                                           refine_iterations: int = 0, refine_levels: int = 3) -> Mosaic:
+                                           refine_iterations: int = 0, refine_levels: int = 3, order: str = "rgb") -> Mosaic:
     """Frames in, one picture out: lucas_kanade_pyramidal_sequence_klt_sparse_replenish on the frames, tracks_homography on its
     rows, mosaic_chain from frame `anchor`, and mosaic_composite of every frame that is not dropped, in one call whose
     intermediate rows stay in the library.  The frames go up twice, chunk by chunk (once to track, once to blend).  The canvas
@@ -542,9 +565,22 @@ def lucas_kanade_pyramidal_sequence_mosaic(frames, max_corners: int = 1000, dete
 
     refine_iterations > 0: the same chain made of its public parts, with sequence_refine_alignment (kind "homography",
     refine_levels levels, refine_iterations iterations each) between the fit and the chain, which answers the chain's drift: a
-    product of steps fitted to at most max_corners tracks each."""
+    product of steps fitted to at most max_corners tracks each.
+
+    A 4-D uint8 array (T, H, W, C), C = 3 or 4, is interleaved colour video (`order`: "rgb" or "bgr"): this call runs on
+    rgb_to_luma of the frames for everything but the canvas, and every channel's plane is then blended by mosaic_composite
+    under the chain fitted on the luma; .canvas is (Hc, Wc, C), .count the grey call's."""
     if isinstance(refine_iterations, bool) or int(refine_iterations) != refine_iterations or int(refine_iterations) < 0:
         raise ValueError(f"refine_iterations must be an integer >= 0, got {refine_iterations!r}")
+    _oflk.check_colour_order(order)
+    if _oflk.is_packed(frames):
+        packed = _oflk.as_packed(frames, "(T, H, W, C)")
+        m = lucas_kanade_pyramidal_sequence_mosaic(rgb_to_luma(packed, order), max_corners, detect_every, hypotheses, threshold, seed,
+                                                   quality_level, min_distance, num_levels, window_size, num_iterations, alpha, beta,
+                                                   max_residual, anchor, extent, blend, max_pixels, refine_iterations, refine_levels)
+        ch = mosaic_chain(m.model, m.status, packed.shape[1:3], anchor, extent)
+        canvas = mosaic_composite(packed, ch.from_anchor, m.canvas.shape, m.origin, ch.dropped, blend)
+        return m._replace(canvas=canvas)
     if int(refine_iterations) > 0:
         rows = lucas_kanade_pyramidal_sequence_klt_sparse_replenish(frames, max_corners, detect_every, quality_level, min_distance,
                                                                     num_levels, window_size, num_iterations, alpha, beta, max_residual)
@@ -706,7 +742,7 @@ class SparseKltTracker:
 class StabilizedFrame(NamedTuple):
     """One steadied frame of an OnlineStabilizer."""
     index: int                     # the frame's index in the stream
-    frame: np.ndarray              # (H, W), the input's type; zero where the source lies outside the frame
+    frame: np.ndarray              # (H, W) -- (H, W, C) for colour --, the input's type; zero where the source lies outside
     correction: np.ndarray         # (2, 3) float32: where the frame's content was moved to
     inside: Optional[np.ndarray]   # (H, W) bool: the source lay inside the frame; None unless asked for
 
@@ -717,7 +753,10 @@ class OnlineStabilizer:
     radius frames ahead, so push(frame t) returns frame t - radius (None while t < radius) and flush() returns the last
     radius frames once the stream has ended.  The frames and corrections of T pushes and a flush are those of the sequence
     call on the same T frames, byte for byte.  After flush() the stabiliser takes no frame until reset().  The black border
-    is not cropped (inside=True returns the mask).
+    is not cropped (inside=True returns the mask).  shape = (H, W, C) with C = 3 or 4 and order = "rgb" or "bgr" (required:
+    without it a three-entry shape is refused, as it always was) makes a colour stabiliser: it takes and returns interleaved
+    uint8 frames (H, W, C), tracks their luma, which the push forms on the device, and equals the sequence call on the same
+    colour frames; the device forms then take [H][W][C] frames too.
 
         with OnlineStabilizer(frame.shape, 1000, radius=15) as stab:
             for frame in video:                     # uint8 (H, W)
@@ -731,12 +770,23 @@ class OnlineStabilizer:
     def __init__(self, shape, max_corners: int, detect_every: int = 4, model="similarity", radius: int = 15, sigma=None,
                  hypotheses: int = 256, threshold: float = 1.0, seed: int = 0, quality_level: float = 0.01,
                  min_distance: float = 10.0, num_levels: int = 3, window_size: int = 5, num_iterations: int = 3, alpha: float = 0.01,
-                 beta: float = 0.5, max_residual: float = 4.0, dtype=np.uint8, device: int = 0, inside: bool = False):
-        if len(shape) != 2 or int(shape[0]) < 2 or int(shape[1]) < 2:
-            raise ValueError(f"shape must be (H, W) with H, W >= 2, got {shape!r}")
+                 beta: float = 0.5, max_residual: float = 4.0, dtype=np.uint8, device: int = 0, inside: bool = False,
+                 order: Optional[str] = None):
+        if len(shape) not in (2, 3) or int(shape[0]) < 2 or int(shape[1]) < 2:
+            raise ValueError(f"shape must be (H, W) or (H, W, C) with H, W >= 2, got {shape!r}")
+        channels = 0
+        if len(shape) == 3:   # interleaved colour frames: the tracker sees their luma
+            channels = int(shape[2])
+            if channels not in (3, 4):
+                raise ValueError(f"colour frames must have 3 or 4 interleaved channels, got shape {shape!r}")
+            if order is None:   # a decoder hands over RGB or BGR: there is no safe guess, and (H, W, 3) was refused before colour
+                raise ValueError(f"a colour stabiliser (shape {shape!r}) needs order='rgb' or order='bgr'")
+        code_order = 0 if order is None else _oflk.check_colour_order(order)
         self.dtype = np.dtype(dtype)
         if self.dtype not in (np.dtype(np.uint8), np.dtype(np.float32)):
             raise ValueError(f"dtype must be uint8 or float32, got {dtype!r}")
+        if channels and self.dtype != np.dtype(np.uint8):
+            raise ValueError("colour frames must be uint8 (float32 colour is not offered)")
         a, b = _oflk.check_fb_params(alpha, beta)
         H, W = int(shape[0]), int(shape[1])
         L, win, it, r = _oflk.check_sparse_params((H, W), num_levels, window_size, num_iterations, max_residual)
@@ -745,16 +795,17 @@ class OnlineStabilizer:
             raise ValueError(f"detect_every must be an integer >= 0, got {detect_every!r}")
         code, hn, thr, sd = _oflk.check_motion_params(model, hypotheses, threshold, seed)
         w = _oflk.stabilize_weights(radius, sigma)
-        self.shape, self.max_corners, self.detect_every = (H, W), K, min(int(detect_every), 2 ** 31 - 1)
+        self.shape, self.max_corners, self.detect_every = (H, W, channels) if channels else (H, W), K, min(int(detect_every), 2 ** 31 - 1)
         self.radius, self.inside = int(w.size) - 1, bool(inside)
         self._s = _oflk.Stabilizer(device, H, W, self.dtype == np.uint8, K, self.detect_every, code, w, hn, thr, sd, L, win, it, a, b, r,
-                                   q, md)
+                                   q, md, channels, code_order)
 
     def _frame(self, index, frame, corr, ins) -> StabilizedFrame:
         return StabilizedFrame(int(index), frame, corr.reshape(2, 3), None if ins is None else ins.astype(bool))
 
     def push(self, frame) -> Optional[StabilizedFrame]:
-        """the next frame (H, W) in; frame t - radius steadied, or None while t < radius (synchronous)"""
+        """the next frame (H, W) -- (H, W, C) for a colour stabiliser -- in; frame t - radius steadied, or None while
+        t < radius (synchronous)"""
         f = np.ascontiguousarray(frame, self.dtype)
         if f.shape != self.shape:
             raise ValueError(f"expected a frame of shape {self.shape}, got {f.shape}")

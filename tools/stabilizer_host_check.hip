@@ -74,6 +74,60 @@ int main()
             EXPECT(oflk_stabilizer_destroy(st) == OFLK_OK);
             st = nullptr;
         }
+    // a packed stabiliser (colour frames): creation's own refusals, then the same answers before the first push
+    auto create_packed = [&](oflk_stabilizer **s, int H, int W, int channels, int order, int radius) {
+        return oflk_stabilizer_create_packed(s, 0, H, W, channels, order, 3, 5, 3, 0.01f, 0.5f, 4.0f, 0.01f, 3.0f, 8, 2,
+                                             OFLK_MOTION_SIMILARITY, 16, 1.0f, 7u, g_w, radius);
+    };
+    EXPECT(create_packed(nullptr, 24, 32, 3, OFLK_ORDER_RGB, 3) == OFLK_ERR_INVALID);
+    for (int channels : {0, 1, 2, 5})
+        EXPECT(create_packed(&st, 24, 32, channels, OFLK_ORDER_RGB, 3) == OFLK_ERR_INVALID && !st);
+    for (int order : {-1, 2})
+        EXPECT(create_packed(&st, 24, 32, 3, order, 3) == OFLK_ERR_INVALID && !st);
+    EXPECT(create_packed(&st, 1, 32, 3, OFLK_ORDER_RGB, 3) == OFLK_ERR_INVALID && !st);
+    EXPECT(create_packed(&st, 30000, 30000, 3, OFLK_ORDER_RGB, 3) == OFLK_ERR_UNSUPPORTED && !st);
+    EXPECT(create_packed(&st, 24, 32, 3, OFLK_ORDER_RGB, -1) == OFLK_ERR_INVALID && !st);
+    for (int channels : {3, 4})
+        for (int order : {OFLK_ORDER_RGB, OFLK_ORDER_BGR}) {
+            EXPECT(create_packed(&st, 24, 32, channels, order, 3) == OFLK_OK && st);
+            if (!st) continue;
+            EXPECT(st->channels == channels && st->order == order && st->tr->u8);
+            EXPECT(st->plane_bytes() == (size_t)24 * 32 * channels);
+            EXPECT(oflk_stabilizer_lag(st) == 3 && oflk_stabilizer_frame_index(st) == -1 && oflk_stabilizer_workspace_bytes(st) == 0);
+            int e = 5, first = 5, count = 5;
+            EXPECT(oflk_stabilizer_push_device(st, nullptr, out, nullptr, &e, nullptr) == OFLK_ERR_INVALID && e == -1);
+            EXPECT(oflk_stabilizer_push_device(st, frame + 1, nullptr, nullptr, &e, nullptr) == OFLK_ERR_INVALID);
+            EXPECT(oflk_stabilizer_push(st, nullptr, out, nullptr, nullptr, &e) == OFLK_ERR_INVALID);
+            EXPECT(oflk_stabilizer_flush_device(st, nullptr, nullptr, &first, &count, nullptr) == OFLK_OK && first == 0 && count == 0);
+            EXPECT(oflk_stabilizer_push_device(st, frame, out, nullptr, &e, nullptr) == OFLK_ERR_INVALID && e == -1);   // flushed
+            EXPECT(oflk_stabilizer_reset(st, nullptr) == OFLK_OK && oflk_stabilizer_frame_index(st) == -1);
+            EXPECT(oflk_stabilizer_destroy(st) == OFLK_OK);
+            st = nullptr;
+        }
+    // the packed calls' refusals that need no device
+    {
+        alignas(8) static double m9[9 * 2];
+        static unsigned char px[2 * 4 * 4 * 4], po[2 * 4 * 4 * 4];
+        EXPECT(oflk_luma_u8(px, 2, 4, 4, 2, OFLK_ORDER_RGB, po, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_luma_u8(px, 2, 4, 4, 3, 2, po, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_luma_u8_host(px, 0, 4, 4, 3, OFLK_ORDER_BGR, po) == OFLK_ERR_INVALID);
+        EXPECT(oflk_luma_u8_host(px, 2, 4, 1, 3, OFLK_ORDER_BGR, po) == OFLK_ERR_INVALID);
+        EXPECT(oflk_luma_u8_host(nullptr, 2, 4, 4, 3, OFLK_ORDER_BGR, po) == OFLK_ERR_INVALID);
+        EXPECT(oflk_luma_u8_host(px, 1, 32768, 32768, 3, OFLK_ORDER_BGR, po) == OFLK_ERR_UNSUPPORTED);
+        EXPECT(oflk_luma_u8_host(px, 1, 30000, 30000, 3, OFLK_ORDER_BGR, po) == OFLK_ERR_UNSUPPORTED);
+        EXPECT(oflk_warp_affine_packed(px, 2, 4, 4, 5, m9, po, nullptr, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_warp_affine_packed(px, 2, 4, 4, 3, nullptr, po, nullptr, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_warp_perspective_packed(px, 2, 4, 4, 4, reinterpret_cast<double *>(reinterpret_cast<char *>(m9) + 4), po, nullptr,
+                                            nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_warp_affine_packed_host(px, 2, 1, 4, 3, m9, po, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_warp_perspective_packed_host(px, 2, 4, 4, 3, m9, nullptr, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_warp_perspective_packed_host(px, 1, 30000, 30000, 3, m9, po, nullptr) == OFLK_ERR_UNSUPPORTED);
+        EXPECT(oflk_stabilize_sequence_packed(px, 1, 4, 4, 3, OFLK_ORDER_RGB, 1, 5, 3, 0.01f, 0.5f, 4.0f, 0.01f, 3.0f, 8, 2,
+                                              OFLK_MOTION_SIMILARITY, 16, 1.0f, 7u, g_w, 3, po, nullptr, nullptr, nullptr,
+                                              nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_stabilize_sequence_packed(px, 2, 4, 4, 3, 7, 1, 5, 3, 0.01f, 0.5f, 4.0f, 0.01f, 3.0f, 8, 2, OFLK_MOTION_SIMILARITY, 16,
+                                              1.0f, 7u, g_w, 3, po, nullptr, nullptr, nullptr, nullptr) == OFLK_ERR_INVALID);
+    }
     EXPECT(oflk_stabilizer_destroy(nullptr) == OFLK_OK && oflk_stabilizer_reset(nullptr, nullptr) == OFLK_ERR_INVALID);
     EXPECT(oflk_stabilizer_lag(nullptr) == -1 && oflk_stabilizer_frame_index(nullptr) == -1 && !oflk_stabilizer_tracker(nullptr));
     // the ring form

@@ -996,6 +996,66 @@ int oflk_stabilizer_create_packed(oflk_stabilizer **st, int device, int H, int W
                                   float min_distance, int max_corners, int detect_every, int model, int hypotheses, float threshold,
                                   unsigned seed, const double *weights /* host, [radius + 1], copied */, int radius);
 
+/* ---- NV12 video: one fused two-plane warp, NV12 stabilisers ---------------------------------------------------------------- */
+/* The statement (tests/nv12_model.py).
+ * Layout: an NV12 frame is H W 3 / 2 contiguous bytes: Y[H][W] first, then UV[H/2][W/2][2] with U at byte 0 and V at byte 1 of
+ * a pair; H and W are even and at least 4; frames are contiguous, [F][H W 3 / 2] (oflk_nv12_frame_bytes).  Pitched surfaces
+ * and separate plane pointers are not offered.
+ * Siting: `siting` says where chroma sample (column i, row j) sits in luma coordinates, x = 2 i + sx, y = 2 j + sy:
+ * OFLK_SITING_LEFT = (sx, sy) = (0, 0.5), the H.264 / HEVC default; OFLK_SITING_CENTER = (0.5, 0.5), as in JPEG and MPEG-1.
+ * The chroma map, float64, every operation rounded on its own, in this order:
+ *   c2 = (m0 sx + m1 sy) + m2,  c5 = (m3 sx + m4 sy) + m5,  perspective only: c8 = (m6 sx + m7 sy) + m8
+ *   affine:      mc = [m0, m1, 0.5 (c2 - sx);  m3, m4, 0.5 (c5 - sy)]
+ *   perspective: mc = [m0 - sx m6, m1 - sx m7, 0.5 (c2 - sx c8);  m3 - sy m6, m4 - sy m7, 0.5 (c5 - sy c8);  2 m6, 2 m7, c8]
+ * the luma map conjugated by the siting: a chroma sample is fetched from where its own luma position is fetched from.
+ * The warp: the Y plane of out[f] is the bytes oflk_warp_affine / oflk_warp_perspective (u8) writes for the plane Y[f] under
+ * map[f], and inside[f] [H][W] is that call's inside.  U and V of out[f] are, per channel, the bytes the same planar warp
+ * writes for the H/2 x W/2 plane UV[f][:, :, c] under mc, except that where that warp's own inside is 0 the chroma byte is
+ * 128, not 0: zero chroma is saturated green, and Y = 0 with U = V = 128 is black.  Nothing else differs from the planar
+ * statement.  Both planes of all F frames are one launch; no load touches a byte outside its own frame.
+ * NV12 stabilisation, by statement, byte for byte: (1) oflk_stabilize_sequence_u8 on the Y planes for correction, model_out,
+ * counts_out and held; (2) the NV12 affine warp of the frames under the maps of that trajectory.  The sequence call gathers
+ * the Y planes into a host array of T H W bytes (no device work), runs the grey call's pass 1 and trajectory on it and warps
+ * the NV12 frames chunk by chunk.
+ * The online form: a stabiliser made by oflk_stabilizer_create_nv12 holds (r + 1) NV12 frames in its delay line, and its
+ * tracker is pushed the frame's own first H W bytes: there is no luma launch and no luma plane.  oflk_stabilizer_push, flush,
+ * their _device forms, correction_device, lag, reset, workspace_bytes and destroy then take and return frames of H W 3 / 2
+ * bytes for such an object; d_inside / inside stays [H][W].  The frames and corrections of T pushes and a flush equal
+ * oflk_stabilize_sequence_nv12 on the same T frames.  Grey and packed stabilisers are what they were.
+ * Refusals, before any device call: H or W odd or below 4, a siting outside the two values, F < 1 (the sequence call: T < 2),
+ * NULL pointers (d_inside, inside and the sequence call's last four outputs may be NULL), d_map not 8-byte aligned:
+ * OFLK_ERR_INVALID;  H W >= 2^30: OFLK_ERR_UNSUPPORTED.  Byte offsets inside a frame are 32-bit, offsets across frames 64-bit.
+ * The sequence call and the stabiliser also refuse what their grey forms refuse, with their codes.  Frames and outputs may
+ * have any alignment: the Y plane and the mask are stored a dword a lane when W % 4 == 0 and d_out and d_inside are 4-byte
+ * aligned, the UV plane 8 bytes a lane when also W % 8 == 0 and d_out is 8-byte aligned; everything else runs the
+ * element-wise kernels. */
+#define OFLK_SITING_LEFT 0
+#define OFLK_SITING_CENTER 1
+/* H W 3 / 2, or 0 for a shape the NV12 calls refuse */
+size_t oflk_nv12_frame_bytes(int H, int W);
+/* device forms, one launch for both planes of the F frames: d_frames, d_out [F][H W 3 / 2], d_map [F][6] (perspective:
+ * [F][9]) float64, d_inside [F][H][W] bytes or NULL.  Asynchronous on `stream`, capturable. */
+int oflk_warp_affine_nv12(const unsigned char *d_frames, int F, int H, int W, int siting, const double *d_map,
+                          unsigned char *d_out, unsigned char *d_inside, void *stream);
+int oflk_warp_perspective_nv12(const unsigned char *d_frames, int F, int H, int W, int siting, const double *d_map,
+                               unsigned char *d_out, unsigned char *d_inside, void *stream);
+/* host arrays, synchronous, in chunks of at most 64 frames; the result does not depend on the cut */
+int oflk_warp_affine_nv12_host(const unsigned char *frames, int F, int H, int W, int siting, const double *map,
+                               unsigned char *out, unsigned char *inside);
+int oflk_warp_perspective_nv12_host(const unsigned char *frames, int F, int H, int W, int siting, const double *map,
+                                    unsigned char *out, unsigned char *inside);
+/* oflk_stabilize_sequence_u8's arguments with siting after W and NV12 frames in and out: frames, out [T][H W 3 / 2] */
+int oflk_stabilize_sequence_nv12(const unsigned char *frames, int T, int H, int W, int siting, int levels, int window_size,
+                                 int iters, float alpha, float beta, float max_residual, float quality_level, float min_distance,
+                                 int max_corners, int detect_every, int model, int hypotheses, float threshold, unsigned seed,
+                                 const double *weights, int radius, unsigned char *out, float *correction, float *model_out,
+                                 int *counts_out, unsigned char *held);
+/* oflk_stabilizer_create's arguments with siting in place of u8 */
+int oflk_stabilizer_create_nv12(oflk_stabilizer **st, int device, int H, int W, int siting, int levels, int window_size, int iters,
+                                float alpha, float beta, float max_residual, float quality_level, float min_distance,
+                                int max_corners, int detect_every, int model, int hypotheses, float threshold, unsigned seed,
+                                const double *weights /* host, [radius + 1], copied */, int radius);
+
 /* Rehearsal of the chunk queue above on a box with fewer GPUs than workers (tests): `workers` > 0 makes the *_multi entry
  * points run that many queue workers, worker i on device i % n_gpus (workers of one device take turns on it); 0 restores
  * one worker per device.  Results do not change. */

@@ -16,6 +16,7 @@
 #include "oflk_mosaic.hpp"
 #include "oflk_align.hpp"
 #include "oflk_colour.hpp"
+#include "oflk_nv12.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -4297,6 +4298,168 @@ OFLK_API int oflk_stabilize_sequence_packed(const unsigned char *frames, int T, 
 }
 
 // =============================================================================
+// NV12 video: Y[H][W] then UV[H/2][W/2][2] in H W 3 / 2 contiguous bytes -- the fused two-plane warps and the NV12 sequence
+// call (oflk_nv12.hpp)
+// =============================================================================
+namespace {
+int check_nv12_shape(int H, int W, int siting)
+{
+    if (H < 4 || W < 4 || H % 2 || W % 2) return fail(OFLK_ERR_INVALID, "NV12 frames need even H and W >= 4 (got %d x %d)", H, W);
+    if (siting != OFLK_SITING_LEFT && siting != OFLK_SITING_CENTER)
+        return fail(OFLK_ERR_INVALID, "siting must be OFLK_SITING_LEFT or OFLK_SITING_CENTER (got %d)", siting);
+    return OFLK_OK;
+}
+
+// the refusals every NV12 call shares: the shape's, and the planar warp's on the Y plane
+int check_nv12(const void *frames, int F, int H, int W, int siting, const void *out)
+{
+    if (int rc = check_nv12_shape(H, W, siting)) return rc;
+    if (F < 1) return fail(OFLK_ERR_INVALID, "F must be >= 1 (got %d)", F);
+    if (!frames || !out) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    return check_hw(frames, out, H, W);   // H W < 2^30, so a frame's H W 3 / 2 bytes are counted by 32-bit offsets
+}
+
+// the one launch of both planes of F frames on stream s; the arguments are checked
+template <bool PERSP>
+int warp_nv12_launch(const unsigned char *d_frames, int F, int H, int W, int siting, const double *d_map, unsigned char *d_out,
+                     unsigned char *d_inside, hipStream_t s)
+{
+    WarpNv12Args a{};
+    a.in = d_frames; a.map = d_map; a.out = d_out; a.inside = d_inside;
+    a.F = F; a.H = H; a.W = W;
+    a.sx = siting == OFLK_SITING_CENTER ? 0.5 : 0.0;
+    a.sy = 0.5;
+    const unsigned cols = (unsigned)((W + 64 * kWarpPx - 1) / (64 * kWarpPx));
+    a.luma_groups = (unsigned)((H + 3) / 4);
+    a.chroma_cols = (unsigned)((W / 2 + 64 * kWarpPx - 1) / (64 * kWarpPx));
+    const unsigned chroma_blocks = (unsigned)((H / 2 + 3) / 4) * a.chroma_cols;
+    // a luma lane's store: a dword of Y and the inside dword; a chroma lane's: one dwordx2.  W % 8 == 0 keeps H W and every
+    // frame's and row's offset a multiple of 8
+    const bool vec_luma = W % kWarpPx == 0 && aligned(d_out, kWarpPx) && (!d_inside || aligned(d_inside, kWarpPx));
+    const int vec = !vec_luma ? 0 : W % (2 * kWarpPx) == 0 && aligned(d_out, 2 * kWarpPx) ? 2 : 1;
+    const dim3 grid(a.luma_groups + (chroma_blocks + cols - 1) / cols, cols, (unsigned)std::min(F, 65535));
+    if (vec == 2)
+        hipLaunchKernelGGL((k_warp_nv12<PERSP, 2>), grid, dim3(256), 0, s, a);
+    else if (vec == 1)
+        hipLaunchKernelGGL((k_warp_nv12<PERSP, 1>), grid, dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL((k_warp_nv12<PERSP, 0>), grid, dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+
+// F NV12 host frames under the device maps d_map, in warp_affine_chunks' chunks through one pair of device buffers
+template <bool PERSP>
+int warp_nv12_chunks(HostCall &call, const unsigned char *frames, int F, int H, int W, int siting, const double *d_map,
+                     unsigned char *out, unsigned char *inside)
+{
+    const int C = sparse_chunk_pairs(F, H, W);
+    const size_t plane = (size_t)H * W, fb = plane + plane / 2;
+    unsigned char *d_in = nullptr, *d_out = nullptr, *d_inside = nullptr;
+    int rc;
+    if ((rc = call.alloc(&d_in, (size_t)C * fb)) || (rc = call.alloc(&d_out, (size_t)C * fb)) ||
+        (rc = call.alloc(&d_inside, (size_t)C * plane, inside != nullptr)))
+        return rc;
+    for (int f0 = 0; f0 < F; f0 += C) {
+        const int n = std::min(C, F - f0);
+        const size_t o = (size_t)f0 * fb, len = (size_t)n * fb;
+        if ((rc = call.to_device(d_in, frames + o, len)) ||
+            (rc = warp_nv12_launch<PERSP>(d_in, n, H, W, siting, d_map + (PERSP ? 9 : 6) * (size_t)f0, d_out, d_inside, nullptr)) ||
+            (rc = call.to_host(out + o, d_out, len)) ||
+            (inside && (rc = call.to_host(inside + (size_t)f0 * plane, d_inside, (size_t)n * plane))) || (rc = call.sync()))
+            return rc;
+    }
+    return OFLK_OK;
+}
+
+template <bool PERSP>
+int warp_nv12_host(const unsigned char *frames, int F, int H, int W, int siting, const double *map, unsigned char *out,
+                   unsigned char *inside)
+{
+    int rc = check_nv12(frames, F, H, W, siting, out);
+    if (rc) return rc;
+    if (!map) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    double *d_map = nullptr;
+    if ((rc = call.upload(&d_map, map, (PERSP ? 9 : 6) * (size_t)F))) return rc;
+    return warp_nv12_chunks<PERSP>(call, frames, F, H, W, siting, d_map, out, inside);
+}
+
+template <bool PERSP>
+int warp_nv12_device(const unsigned char *d_frames, int F, int H, int W, int siting, const double *d_map, unsigned char *d_out,
+                     unsigned char *d_inside, void *stream)
+{
+    if (int rc = check_nv12(d_frames, F, H, W, siting, d_out)) return rc;
+    if (!d_map) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    if (!aligned(d_map, 8)) return fail(OFLK_ERR_INVALID, "d_map must be 8-byte aligned");
+    return warp_nv12_launch<PERSP>(d_frames, F, H, W, siting, d_map, d_out, d_inside, (hipStream_t)stream);
+}
+}  // namespace
+
+OFLK_API size_t oflk_nv12_frame_bytes(int H, int W)
+{
+    if (H < 4 || W < 4 || H % 2 || W % 2 || (size_t)H * (size_t)W >= ((size_t)1 << 30) || H >= kMaxDim || W >= kMaxDim) return 0;
+    return (size_t)H * (size_t)W / 2 * 3;
+}
+
+OFLK_API int oflk_warp_affine_nv12(const unsigned char *d_frames, int F, int H, int W, int siting, const double *d_map,
+                                   unsigned char *d_out, unsigned char *d_inside, void *stream)
+{
+    return warp_nv12_device<false>(d_frames, F, H, W, siting, d_map, d_out, d_inside, stream);
+}
+
+OFLK_API int oflk_warp_perspective_nv12(const unsigned char *d_frames, int F, int H, int W, int siting, const double *d_map,
+                                        unsigned char *d_out, unsigned char *d_inside, void *stream)
+{
+    return warp_nv12_device<true>(d_frames, F, H, W, siting, d_map, d_out, d_inside, stream);
+}
+
+OFLK_API int oflk_warp_affine_nv12_host(const unsigned char *frames, int F, int H, int W, int siting, const double *map,
+                                        unsigned char *out, unsigned char *inside)
+{
+    return warp_nv12_host<false>(frames, F, H, W, siting, map, out, inside);
+}
+
+OFLK_API int oflk_warp_perspective_nv12_host(const unsigned char *frames, int F, int H, int W, int siting, const double *map,
+                                             unsigned char *out, unsigned char *inside)
+{
+    return warp_nv12_host<true>(frames, F, H, W, siting, map, out, inside);
+}
+
+// The Y planes of all T frames are gathered into a host array of their own (two thirds of the caller's frames, no device
+// work), pass 1 is the grey call's on that array, and pass 2 warps the NV12 frames
+OFLK_API int oflk_stabilize_sequence_nv12(const unsigned char *frames, int T, int H, int W, int siting, int levels, int window_size,
+                                          int iters, float alpha, float beta, float max_residual, float quality_level,
+                                          float min_distance, int max_corners, int detect_every, int model, int hypotheses,
+                                          float threshold, unsigned seed, const double *weights, int radius, unsigned char *out,
+                                          float *correction, float *model_out, int *counts_out, unsigned char *held)
+{
+    int rc = check_nv12_shape(H, W, siting);
+    if (rc) return rc;
+    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
+    if ((rc = check_nv12(frames, T, H, W, siting, out)) ||
+        (rc = check_stabilize_sequence(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, quality_level,
+                                       min_distance, max_corners, detect_every, model, hypotheses, threshold, weights, radius, out)))
+        return rc;
+    const size_t plane = (size_t)H * W, fb = plane + plane / 2;
+    std::vector<unsigned char> luma;
+    try {
+        luma.resize((size_t)T * plane);
+    } catch (const std::exception &) {
+        return fail(OFLK_ERR_NOMEM, "no host memory for the Y planes of %d frames of %d x %d", T, W, H);
+    }
+    for (int t = 0; t < T; t++) std::memcpy(luma.data() + (size_t)t * plane, frames + (size_t)t * fb, plane);
+    HostCall call;
+    double *d_map = nullptr;
+    if ((rc = stabilize_maps<unsigned char>(call, luma.data(), T, H, W, levels, window_size, iters, alpha, beta, max_residual,
+                                            quality_level, min_distance, max_corners, detect_every, model, hypotheses, threshold, seed,
+                                            weights, radius, correction, model_out, counts_out, held, &d_map)))
+        return rc;
+    return warp_nv12_chunks<false>(call, frames, T, H, W, siting, d_map, out, nullptr);
+}
+
+// =============================================================================
 // video mosaics: the chain of step homographies, the canvas, accumulate and resolve (oflk_mosaic.hpp)
 // =============================================================================
 namespace {
@@ -5376,8 +5539,16 @@ struct oflk_stabilizer {
     // (uint8) is pushed the luma of the frame, formed in `luma` by the push
     int channels = 0, order = 0;      // 0 channels: a grey stabiliser
     unsigned char *luma = nullptr;    // [H][W]
+    // oflk_stabilizer_create_nv12: the delay line and every frame in and out are H W 3 / 2 bytes, and the tracker (uint8) is
+    // pushed the frame's own first H W bytes, its Y plane: no luma launch and no luma plane
+    bool nv12 = false;
+    int siting = 0;
 
-    size_t plane_bytes() const { return (size_t)tr->H * tr->W * (channels ? (size_t)channels : tr->pix_bytes()); }
+    size_t plane_bytes() const
+    {
+        const size_t px = (size_t)tr->H * tr->W;
+        return nv12 ? px + px / 2 : px * (channels ? (size_t)channels : tr->pix_bytes());
+    }
     char *slot(long long f) const { return delay + (size_t)(f % (r + 1)) * plane_bytes(); }
 };
 
@@ -5413,6 +5584,9 @@ int stabilizer_warp(const oflk_stabilizer *st, const void *d_frames, int F, cons
                     hipStream_t s)
 {
     const oflk_tracker *tr = st->tr;
+    if (st->nv12)
+        return warp_nv12_launch<false>((const unsigned char *)d_frames, F, tr->H, tr->W, st->siting, d_map, (unsigned char *)d_out,
+                                       d_inside, s);
     if (st->channels)
         return warp_packed_launch<false>((const unsigned char *)d_frames, F, tr->H, tr->W, st->channels, d_map, (unsigned char *)d_out,
                                          d_inside, s);
@@ -5583,6 +5757,23 @@ OFLK_API int oflk_stabilizer_create_packed(oflk_stabilizer **out, int device, in
         return rc;
     (*out)->channels = channels;
     (*out)->order = order;
+    return OFLK_OK;
+}
+
+OFLK_API int oflk_stabilizer_create_nv12(oflk_stabilizer **out, int device, int H, int W, int siting, int levels, int window_size,
+                                         int iters, float alpha, float beta, float max_residual, float quality_level,
+                                         float min_distance, int max_corners, int detect_every, int model, int hypotheses,
+                                         float threshold, unsigned seed, const double *weights, int radius)
+{
+    if (!out) return fail(OFLK_ERR_INVALID, "stabiliser pointer is NULL");
+    *out = nullptr;
+    int rc = check_nv12_shape(H, W, siting);
+    if (rc) return rc;
+    if ((rc = oflk_stabilizer_create(out, device, H, W, 1, levels, window_size, iters, alpha, beta, max_residual, quality_level,
+                                     min_distance, max_corners, detect_every, model, hypotheses, threshold, seed, weights, radius)))
+        return rc;
+    (*out)->nv12 = true;
+    (*out)->siting = siting;
     return OFLK_OK;
 }
 

@@ -176,6 +176,13 @@ SIGNATURES = {
     "oflk_warp_perspective_packed_host": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_f64p, _vp, _vp]),
     "oflk_stabilize_sequence_packed": (ctypes.c_int, [_vp] + [ctypes.c_int] * 8 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int, _vp, _f32p, _f32p, _i32p, _vp]),
     "oflk_stabilizer_create_packed": (ctypes.c_int, [ctypes.POINTER(_vp)] + [ctypes.c_int] * 8 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int]),
+    "oflk_nv12_frame_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
+    "oflk_warp_affine_nv12": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_vp] * 4),
+    "oflk_warp_perspective_nv12": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_vp] * 4),
+    "oflk_warp_affine_nv12_host": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_f64p, _vp, _vp]),
+    "oflk_warp_perspective_nv12_host": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_f64p, _vp, _vp]),
+    "oflk_stabilize_sequence_nv12": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int, _vp, _f32p, _f32p, _i32p, _vp]),
+    "oflk_stabilizer_create_nv12": (ctypes.c_int, [ctypes.POINTER(_vp)] + [ctypes.c_int] * 7 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int]),
     "oflk_shard_range": (None, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, _i32p]),
     "oflk_single_scale_fp16": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, _f32p, _f32p]),
     "oflk_rtl_stream_length": (ctypes.c_long, [ctypes.c_int, ctypes.c_int]),
@@ -870,6 +877,61 @@ def warp_packed_host(frames: np.ndarray, maps: np.ndarray, inside: bool = False)
     return out, ins
 
 
+OFLK_SITING_LEFT, OFLK_SITING_CENTER = 0, 1
+NV12_SITINGS = {"left": OFLK_SITING_LEFT, "center": OFLK_SITING_CENTER}
+
+
+def check_nv12_siting(siting) -> int:
+    """the C ABI's code of a chroma siting given by name; ValueError for anything else"""
+    if not isinstance(siting, str) or siting not in NV12_SITINGS:
+        raise ValueError(f"siting must be one of {sorted(NV12_SITINGS)}, got {siting!r}")
+    return NV12_SITINGS[siting]
+
+
+def as_nv12(frames, what: str = "(F, 3H/2, W)") -> np.ndarray:
+    """NV12 frames as one contiguous uint8 (F, 3H/2, W) array: rows 0 .. H-1 of a frame are its Y plane, the H/2 rows behind
+    them its interleaved U, V pairs; H and W even and >= 4.  ValueError for anything else; no device call."""
+    if not isinstance(frames, np.ndarray) or frames.ndim != 3:
+        raise ValueError(f"expected a {what} array of NV12 frames, got shape {np.shape(frames)}")
+    if frames.dtype != np.uint8:
+        raise ValueError(f"NV12 frames must be uint8, got {frames.dtype}")
+    F, R, W = frames.shape
+    if R % 3 or (2 * R // 3) % 2:
+        raise ValueError(f"an NV12 frame has 3H/2 rows with H even, got {R} rows")
+    if W % 2:
+        raise ValueError(f"NV12 frames need an even W, got {W}")
+    if F < 1 or 2 * R // 3 < 4 or W < 4:
+        raise ValueError(f"expected at least one NV12 frame of at least 4 x 4 pixels, got shape {frames.shape}")
+    return np.ascontiguousarray(frames)
+
+
+def warp_affine_nv12(d_frames: int, F: int, H: int, W: int, d_map: int, d_out: int, d_inside: int = 0, siting: int = 0,
+                     stream: int = 0) -> None:
+    """oflk_warp_affine_nv12 on device pointers: frames and d_out [F][H W 3 / 2] uint8, d_map [F][6] float64, d_inside
+    [F][H][W] uint8 or 0; asynchronous."""
+    check(lib().oflk_warp_affine_nv12(d_frames or None, int(F), int(H), int(W), int(siting), d_map or None, d_out or None,
+                                      d_inside or None, stream))
+
+
+def warp_perspective_nv12(d_frames: int, F: int, H: int, W: int, d_map: int, d_out: int, d_inside: int = 0, siting: int = 0,
+                          stream: int = 0) -> None:
+    """oflk_warp_perspective_nv12 on device pointers: oflk_warp_affine_nv12's arguments with d_map [F][9]; asynchronous."""
+    check(lib().oflk_warp_perspective_nv12(d_frames or None, int(F), int(H), int(W), int(siting), d_map or None, d_out or None,
+                                           d_inside or None, stream))
+
+
+def warp_nv12_host(frames: np.ndarray, maps: np.ndarray, siting: int = 0, inside: bool = False):
+    """oflk_warp_affine_nv12_host -- oflk_warp_perspective_nv12_host for (F, 9) maps --: contiguous uint8 (F, 3H/2, W) frames
+    and float64 maps in; the warped frames and, when asked for, the (F, H, W) inside mask (else None) out"""
+    F, R, W = frames.shape
+    H = 2 * R // 3
+    out = np.empty_like(frames)
+    ins = np.empty((F, H, W), np.uint8) if inside else None
+    fn = lib().oflk_warp_perspective_nv12_host if maps.shape[-1] == 9 else lib().oflk_warp_affine_nv12_host
+    check(fn(frames.ctypes.data, F, H, W, int(siting), _f64(maps), out.ctypes.data, None if ins is None else ins.ctypes.data))
+    return out, ins
+
+
 MOSAIC_BLENDS = {"mean": 0, "feather": 1, "first": 2, "last": 3}
 
 
@@ -1117,16 +1179,21 @@ class Stabilizer:
     def __init__(self, device: int, H: int, W: int, u8: bool, max_corners: int, detect_every: int, model: int, weights: np.ndarray,
                  hypotheses: int = 256, threshold: float = 1.0, seed: int = 0, levels: int = 3, window_size: int = 5, iters: int = 3,
                  alpha: float = 0.01, beta: float = 0.5, max_residual: float = 4.0, quality_level: float = 0.01,
-                 min_distance: float = 10.0, channels: int = 0, order: int = 0):
+                 min_distance: float = 10.0, channels: int = 0, order: int = 0, nv12: bool = False, siting: int = 0):
         self._h = _vp()
         self.H, self.W, self.u8, self.K = int(H), int(W), bool(u8), int(max_corners)
         self.channels = int(channels)   # 0: grey frames (H, W); 3 or 4: packed uint8 frames (H, W, channels), luma to the tracker
+        self.nv12 = bool(nv12)          # NV12 uint8 frames (3H/2, W), their Y plane to the tracker
         w = np.ascontiguousarray(weights, np.float64)
         self.radius = int(w.size) - 1
         tail = (int(levels), int(window_size), int(iters), float(alpha), float(beta), float(max_residual), float(quality_level),
                 float(min_distance), int(max_corners), int(detect_every), int(model), int(hypotheses), float(threshold), int(seed),
                 _f64(w), self.radius)
-        if self.channels:
+        if self.nv12:
+            if not self.u8 or self.channels:
+                raise ValueError("NV12 frames are uint8 and have no channel axis")
+            check(lib().oflk_stabilizer_create_nv12(ctypes.byref(self._h), int(device), int(H), int(W), int(siting), *tail))
+        elif self.channels:
             if not self.u8:
                 raise ValueError("colour frames must be uint8 (float32 colour is not offered)")
             check(lib().oflk_stabilizer_create_packed(ctypes.byref(self._h), int(device), int(H), int(W), self.channels, int(order),
@@ -1185,6 +1252,8 @@ class Stabilizer:
         return np.uint8 if self.u8 else np.float32
 
     def _shape(self):
+        if self.nv12:
+            return (3 * self.H // 2, self.W)
         return (self.H, self.W, self.channels) if self.channels else (self.H, self.W)
 
     def push(self, frame: np.ndarray, inside: bool = False):

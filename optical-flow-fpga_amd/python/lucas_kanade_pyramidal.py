@@ -539,6 +539,111 @@ def lucas_kanade_pyramidal_sequence_stabilize(frames, max_corners: int, detect_e
     return SequenceStabilized(out, corr.reshape(T, 2, 3), mod.reshape(T - 1, 2, 3), cnt[:, 2].copy(), held.astype(bool))
 
 
+def nv12_planes(frames):
+    """Views of the two planes of NV12 frames: an (F, 3H/2, W) or (3H/2, W) uint8 array -- rows 0 .. H-1 of a frame are its Y
+    plane, the H/2 rows behind them its interleaved U, V pairs -- gives y (F, H, W) and uv (F, H/2, W/2, 2), or (H, W) and
+    (H/2, W/2, 2).  H and W must be even and >= 4."""
+    single = isinstance(frames, np.ndarray) and frames.ndim == 2
+    arr = _oflk.as_nv12(frames[None] if single else frames, "(F, 3H/2, W) or (3H/2, W)")
+    F, R, W = arr.shape
+    H = 2 * R // 3
+    y, uv = arr[:, :H, :], arr[:, H:, :].reshape(F, H // 2, W // 2, 2)
+    return (y[0], uv[0]) if single else (y, uv)
+
+
+def nv12_from_planes(y, uv):
+    """NV12 frames from their planes, nv12_planes' inverse: y (F, H, W) and uv (F, H/2, W/2, 2) uint8 give (F, 3H/2, W);
+    (H, W) and (H/2, W/2, 2) give (3H/2, W)."""
+    y, uv = np.asarray(y), np.asarray(uv)
+    if y.dtype != np.uint8 or uv.dtype != np.uint8:
+        raise ValueError(f"NV12 planes must be uint8, got {y.dtype} and {uv.dtype}")
+    single = y.ndim == 2
+    if single:
+        y, uv = y[None], uv[None]
+    if y.ndim != 3 or uv.ndim != 4:
+        raise ValueError(f"expected y (F, H, W) and uv (F, H/2, W/2, 2), got {y.shape} and {uv.shape}")
+    F, H, W = y.shape
+    if H % 2 or W % 2 or H < 4 or W < 4:
+        raise ValueError(f"NV12 frames need even H and W >= 4, got {H} x {W}")
+    if uv.shape != (F, H // 2, W // 2, 2):
+        raise ValueError(f"expected uv of shape {(F, H // 2, W // 2, 2)} for y of shape {y.shape}, got {uv.shape}")
+    out = np.concatenate([y, uv.reshape(F, H // 2, W)], axis=1)
+    return out[0] if single else out
+
+
+def _warp_nv12(frames, maps, siting, return_inside: bool, n: int):
+    code = _oflk.check_nv12_siting(siting)
+    single = isinstance(frames, np.ndarray) and frames.ndim == 2
+    arr = _oflk.as_nv12(frames[None] if single else frames, "(F, 3H/2, W) or (3H/2, W)")
+    F = arr.shape[0]
+    m = np.ascontiguousarray(maps, np.float64)
+    rows = (3, 6) if n == 6 else (3, 9)
+    if m.size != n * F or m.ndim not in (1, 2, 3) or m.shape[-1] not in rows or (n == 9 and m.shape[-1] == 3 and (m.ndim < 2 or m.shape[-2] != 3)):
+        raise ValueError(f"expected {F} maps of shape {(2, 3) if n == 6 else (3, 3)} or ({n},), got {np.shape(maps)}")
+    out, ins = _oflk.warp_nv12_host(arr, m.reshape(F, n), code, bool(return_inside))
+    if single:
+        out, ins = out[0], None if ins is None else ins[0]
+    return (out, ins.astype(bool)) if return_inside else out
+
+
+def warp_affine_nv12(frames, maps, siting: str = "left", return_inside: bool = False):
+    """warp_affine for NV12 frames, both planes in one launch: frames (F, 3H/2, W) or (3H/2, W) uint8 (nv12_from_planes), maps
+    as warp_affine's, in luma pixels.  The Y plane comes back as warp_affine returns it for that plane; U and V as
+    warp_affine returns them for their H/2 x W/2 planes under the map restated in chroma coordinates, where chroma sample
+    (i, j) sits at luma (2 i + sx, 2 j + sy): siting "left" is (0, 0.5), the H.264 / HEVC default, "center" (0.5, 0.5), as in
+    JPEG.  Outside the frame Y is 0 and U = V = 128: black.  With return_inside also the (F, H, W) bool mask of the Y plane."""
+    return _warp_nv12(frames, maps, siting, return_inside, 6)
+
+
+def warp_perspective_nv12(frames, maps, siting: str = "left", return_inside: bool = False):
+    """warp_perspective for NV12 frames, as warp_affine_nv12 under one 3 x 3 map each."""
+    return _warp_nv12(frames, maps, siting, return_inside, 9)
+
+
+def lucas_kanade_pyramidal_sequence_stabilize_nv12(frames, max_corners: int, detect_every: int, model: str = "similarity",
+                                                   radius: int = 15, sigma=None, hypotheses: int = 256, threshold: float = 1.0,
+                                                   seed: int = 0, quality_level: float = 0.01, min_distance: float = 10.0,
+                                                   num_levels: int = 3, window_size: int = 5, num_iterations: int = 3,
+                                                   alpha: float = 0.01, beta: float = 0.5, max_residual: float = 4.0,
+                                                   refine_iterations: int = 0, refine_levels: int = 3,
+                                                   siting: str = "left") -> SequenceStabilized:
+    """lucas_kanade_pyramidal_sequence_stabilize for NV12 video, frames (T, 3H/2, W) uint8 (nv12_from_planes): the motion is
+    tracked, fitted and (with refine_iterations) refined on the Y planes, exactly as that call does on them, and the NV12
+    frames are warped under the maps of that trajectory by warp_affine_nv12, the chroma sited as `siting` says.  .frames has
+    the input's shape.  No conversion and no luma pass: the Y plane is the frame's first H W bytes."""
+    if isinstance(refine_iterations, bool) or int(refine_iterations) != refine_iterations or int(refine_iterations) < 0:
+        raise ValueError(f"refine_iterations must be an integer >= 0, got {refine_iterations!r}")
+    code_siting = _oflk.check_nv12_siting(siting)
+    arr = _oflk.as_nv12(frames, "(T, 3H/2, W)")
+    T, R, W = arr.shape
+    H = 2 * R // 3
+    if T < 2:
+        raise ValueError(f"a sequence needs at least 2 frames, got {T}")
+    if int(refine_iterations) > 0:
+        grey = np.ascontiguousarray(arr[:, :H, :])
+        rows = lucas_kanade_pyramidal_sequence_klt_sparse_replenish(grey, max_corners, detect_every, quality_level, min_distance,
+                                                                    num_levels, window_size, num_iterations, alpha, beta, max_residual)
+        fit = tracks_motion(rows.tracks, rows.visible, rows.born, model, hypotheses, threshold, seed)
+        al = sequence_refine_alignment(grey, fit.model, fit.status, "affine", refine_levels, int(refine_iterations))
+        tr = stabilize_trajectory(al.model, fit.status, radius, sigma)
+        return SequenceStabilized(warp_affine_nv12(arr, tr.map, siting), tr.correction, al.model, fit.status, tr.held)
+    a, b = _oflk.check_fb_params(alpha, beta)
+    L, win, it, r = _oflk.check_sparse_params((H, W), num_levels, window_size, num_iterations, max_residual)
+    K, q, md, win = _oflk.check_feature_params(max_corners, quality_level, min_distance, win)
+    if isinstance(detect_every, bool) or int(detect_every) != detect_every or int(detect_every) < 1:
+        raise ValueError(f"detect_every must be an integer >= 1, got {detect_every!r}")
+    code, hn, thr, sd = _oflk.check_motion_params(model, hypotheses, threshold, seed)
+    w = _oflk.stabilize_weights(radius, sigma)
+    out = np.empty_like(arr)
+    corr, mod = np.empty((T, 6), np.float32), np.empty((T - 1, 6), np.float32)
+    cnt, held = np.empty((T - 1, 3), np.int32), np.empty(T - 1, np.uint8)
+    _oflk.check(_oflk.lib().oflk_stabilize_sequence_nv12(
+        arr.ctypes.data, T, H, W, code_siting, L, win, it, a, b, r, q, md, K, min(int(detect_every), 2 ** 31 - 1), code, hn, thr, sd,
+        _oflk._f64(w), int(w.size) - 1, out.ctypes.data, _oflk.ptr(corr), _oflk.ptr(mod), cnt.ctypes.data_as(_oflk._i32p),
+        held.ctypes.data))
+    return SequenceStabilized(out, corr.reshape(T, 2, 3), mod.reshape(T - 1, 2, 3), cnt[:, 2].copy(), held.astype(bool))
+
+
 class Mosaic(NamedTuple):
     """Result of lucas_kanade_pyramidal_sequence_mosaic."""
     canvas: np.ndarray      # (Hc, Wc) -- (Hc, Wc, C) for colour --, the input's type: the blended frames in the anchor's coordinates
@@ -756,7 +861,11 @@ class OnlineStabilizer:
     is not cropped (inside=True returns the mask).  shape = (H, W, C) with C = 3 or 4 and order = "rgb" or "bgr" (required:
     without it a three-entry shape is refused, as it always was) makes a colour stabiliser: it takes and returns interleaved
     uint8 frames (H, W, C), tracks their luma, which the push forms on the device, and equals the sequence call on the same
-    colour frames; the device forms then take [H][W][C] frames too.
+    colour frames; the device forms then take [H][W][C] frames too.  layout = "nv12" with shape = (H, W), H and W even, makes
+    an NV12 stabiliser: it takes and returns (3H/2, W) uint8 frames (nv12_from_planes), tracks their Y plane where it lies,
+    warps both planes in one launch with the chroma sited as `siting` says ("left" or "center"), and equals
+    lucas_kanade_pyramidal_sequence_stabilize_nv12 on the same frames; inside stays (H, W).  An NV12 frame is never guessed
+    from a shape.
 
         with OnlineStabilizer(frame.shape, 1000, radius=15) as stab:
             for frame in video:                     # uint8 (H, W)
@@ -771,7 +880,15 @@ class OnlineStabilizer:
                  hypotheses: int = 256, threshold: float = 1.0, seed: int = 0, quality_level: float = 0.01,
                  min_distance: float = 10.0, num_levels: int = 3, window_size: int = 5, num_iterations: int = 3, alpha: float = 0.01,
                  beta: float = 0.5, max_residual: float = 4.0, dtype=np.uint8, device: int = 0, inside: bool = False,
-                 order: Optional[str] = None):
+                 order: Optional[str] = None, layout: Optional[str] = None, siting: str = "left"):
+        if layout is not None and layout != "nv12":
+            raise ValueError(f"layout must be None or 'nv12', got {layout!r}")
+        nv12 = layout == "nv12"
+        code_siting = _oflk.check_nv12_siting(siting)
+        if nv12 and (len(shape) != 2 or int(shape[0]) < 4 or int(shape[1]) < 4 or int(shape[0]) % 2 or int(shape[1]) % 2):
+            raise ValueError(f"an NV12 stabiliser needs shape (H, W) with H, W even and >= 4, got {shape!r}")
+        if nv12 and order is not None:
+            raise ValueError("NV12 frames have no channel order")
         if len(shape) not in (2, 3) or int(shape[0]) < 2 or int(shape[1]) < 2:
             raise ValueError(f"shape must be (H, W) or (H, W, C) with H, W >= 2, got {shape!r}")
         channels = 0
@@ -787,6 +904,8 @@ class OnlineStabilizer:
             raise ValueError(f"dtype must be uint8 or float32, got {dtype!r}")
         if channels and self.dtype != np.dtype(np.uint8):
             raise ValueError("colour frames must be uint8 (float32 colour is not offered)")
+        if nv12 and self.dtype != np.dtype(np.uint8):
+            raise ValueError("NV12 frames must be uint8")
         a, b = _oflk.check_fb_params(alpha, beta)
         H, W = int(shape[0]), int(shape[1])
         L, win, it, r = _oflk.check_sparse_params((H, W), num_levels, window_size, num_iterations, max_residual)
@@ -796,16 +915,18 @@ class OnlineStabilizer:
         code, hn, thr, sd = _oflk.check_motion_params(model, hypotheses, threshold, seed)
         w = _oflk.stabilize_weights(radius, sigma)
         self.shape, self.max_corners, self.detect_every = (H, W, channels) if channels else (H, W), K, min(int(detect_every), 2 ** 31 - 1)
+        if nv12:
+            self.shape = (3 * H // 2, W)
         self.radius, self.inside = int(w.size) - 1, bool(inside)
         self._s = _oflk.Stabilizer(device, H, W, self.dtype == np.uint8, K, self.detect_every, code, w, hn, thr, sd, L, win, it, a, b, r,
-                                   q, md, channels, code_order)
+                                   q, md, channels, code_order, nv12, code_siting)
 
     def _frame(self, index, frame, corr, ins) -> StabilizedFrame:
         return StabilizedFrame(int(index), frame, corr.reshape(2, 3), None if ins is None else ins.astype(bool))
 
     def push(self, frame) -> Optional[StabilizedFrame]:
-        """the next frame (H, W) -- (H, W, C) for a colour stabiliser -- in; frame t - radius steadied, or None while
-        t < radius (synchronous)"""
+        """the next frame (H, W) -- (H, W, C) for a colour stabiliser, (3H/2, W) for an NV12 one -- in; frame t - radius
+        steadied, or None while t < radius (synchronous)"""
         f = np.ascontiguousarray(frame, self.dtype)
         if f.shape != self.shape:
             raise ValueError(f"expected a frame of shape {self.shape}, got {f.shape}")

@@ -128,6 +128,52 @@ int main()
         EXPECT(oflk_stabilize_sequence_packed(px, 2, 4, 4, 3, 7, 1, 5, 3, 0.01f, 0.5f, 4.0f, 0.01f, 3.0f, 8, 2, OFLK_MOTION_SIMILARITY, 16,
                                               1.0f, 7u, g_w, 3, po, nullptr, nullptr, nullptr, nullptr) == OFLK_ERR_INVALID);
     }
+    // an NV12 stabiliser: creation's own refusals, then the same answers before the first push
+    auto create_nv12 = [&](oflk_stabilizer **s, int H, int W, int siting, int radius) {
+        return oflk_stabilizer_create_nv12(s, 0, H, W, siting, 3, 5, 3, 0.01f, 0.5f, 4.0f, 0.01f, 3.0f, 8, 2, OFLK_MOTION_SIMILARITY, 16,
+                                           1.0f, 7u, g_w, radius);
+    };
+    EXPECT(create_nv12(nullptr, 24, 32, OFLK_SITING_LEFT, 3) == OFLK_ERR_INVALID);
+    for (int siting : {-1, 2}) EXPECT(create_nv12(&st, 24, 32, siting, 3) == OFLK_ERR_INVALID && !st);
+    EXPECT(create_nv12(&st, 23, 32, OFLK_SITING_LEFT, 3) == OFLK_ERR_INVALID && !st);
+    EXPECT(create_nv12(&st, 24, 31, OFLK_SITING_LEFT, 3) == OFLK_ERR_INVALID && !st);
+    EXPECT(create_nv12(&st, 2, 32, OFLK_SITING_LEFT, 3) == OFLK_ERR_INVALID && !st);
+    EXPECT(create_nv12(&st, 24, 32, OFLK_SITING_LEFT, -1) == OFLK_ERR_INVALID && !st);
+    for (int siting : {OFLK_SITING_LEFT, OFLK_SITING_CENTER}) {
+        EXPECT(create_nv12(&st, 24, 32, siting, 3) == OFLK_OK && st);
+        if (!st) continue;
+        EXPECT(st->nv12 && st->siting == siting && st->channels == 0 && st->tr->u8);
+        EXPECT(st->plane_bytes() == (size_t)24 * 32 * 3 / 2 && st->plane_bytes() == oflk_nv12_frame_bytes(24, 32));
+        EXPECT(oflk_stabilizer_lag(st) == 3 && oflk_stabilizer_frame_index(st) == -1 && oflk_stabilizer_workspace_bytes(st) == 0);
+        int e = 5, first = 5, count = 5;
+        EXPECT(oflk_stabilizer_push_device(st, nullptr, out, nullptr, &e, nullptr) == OFLK_ERR_INVALID && e == -1);
+        EXPECT(oflk_stabilizer_push(st, nullptr, out, nullptr, nullptr, &e) == OFLK_ERR_INVALID);
+        EXPECT(oflk_stabilizer_flush_device(st, nullptr, nullptr, &first, &count, nullptr) == OFLK_OK && first == 0 && count == 0);
+        EXPECT(oflk_stabilizer_push_device(st, frame, out, nullptr, &e, nullptr) == OFLK_ERR_INVALID && e == -1);   // flushed
+        EXPECT(oflk_stabilizer_reset(st, nullptr) == OFLK_OK && oflk_stabilizer_frame_index(st) == -1);
+        EXPECT(oflk_stabilizer_destroy(st) == OFLK_OK);
+        st = nullptr;
+    }
+    // the NV12 calls' refusals that need no device
+    {
+        alignas(8) static double m9[9 * 2];
+        static unsigned char px[2 * 4 * 4 * 3 / 2], po[2 * 4 * 4 * 3 / 2];
+        EXPECT(oflk_nv12_frame_bytes(4, 4) == 24 && oflk_nv12_frame_bytes(5, 4) == 0 && oflk_nv12_frame_bytes(4, 2) == 0);
+        EXPECT(oflk_nv12_frame_bytes(32768, 32768) == 0);
+        EXPECT(oflk_warp_affine_nv12(px, 2, 4, 4, 2, m9, po, nullptr, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_warp_affine_nv12(px, 2, 5, 4, OFLK_SITING_LEFT, m9, po, nullptr, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_warp_affine_nv12(px, 2, 4, 4, OFLK_SITING_LEFT, nullptr, po, nullptr, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_warp_perspective_nv12(px, 2, 4, 4, OFLK_SITING_CENTER, reinterpret_cast<double *>(reinterpret_cast<char *>(m9) + 4), po,
+                                          nullptr, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_warp_affine_nv12_host(px, 0, 4, 4, OFLK_SITING_LEFT, m9, po, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_warp_perspective_nv12_host(px, 2, 4, 4, OFLK_SITING_LEFT, m9, nullptr, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_warp_perspective_nv12_host(px, 1, 32768, 32768, OFLK_SITING_LEFT, m9, po, nullptr) == OFLK_ERR_UNSUPPORTED);
+        EXPECT(oflk_stabilize_sequence_nv12(px, 1, 4, 4, OFLK_SITING_LEFT, 1, 5, 3, 0.01f, 0.5f, 4.0f, 0.01f, 3.0f, 8, 2,
+                                            OFLK_MOTION_SIMILARITY, 16, 1.0f, 7u, g_w, 3, po, nullptr, nullptr, nullptr,
+                                            nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_stabilize_sequence_nv12(px, 2, 4, 4, 7, 1, 5, 3, 0.01f, 0.5f, 4.0f, 0.01f, 3.0f, 8, 2, OFLK_MOTION_SIMILARITY, 16, 1.0f,
+                                            7u, g_w, 3, po, nullptr, nullptr, nullptr, nullptr) == OFLK_ERR_INVALID);
+    }
     EXPECT(oflk_stabilizer_destroy(nullptr) == OFLK_OK && oflk_stabilizer_reset(nullptr, nullptr) == OFLK_ERR_INVALID);
     EXPECT(oflk_stabilizer_lag(nullptr) == -1 && oflk_stabilizer_frame_index(nullptr) == -1 && !oflk_stabilizer_tracker(nullptr));
     // the ring form

@@ -3817,87 +3817,124 @@ int trajectory_launch(const float *d_model, const int *d_counts, int T, const do
     return OFLK_OK;
 }
 
-int check_warp_affine(const void *frames, int F, int H, int W, const void *map, const void *out)
+// ---- frame layouts ----
+// How a frame of the warps, the sequence stabilisers and the online stabiliser lies in memory.  The layouts share one host
+// path (below the NV12 launcher: warp_launch, warp_chunks, warp_host, warp_device, stabilize_sequence), and every function
+// that tells them apart does so in one switch with one `case` a layout.
+enum class FrameKind { Planar, Packed, Nv12 };
+
+struct FrameLayout {
+    FrameKind kind;
+    int pix_bytes;   // Planar: 1 (uint8) or 4 (float32) bytes a pixel; Packed and Nv12 are bytes
+    int channels;    // Packed: 3 or 4 interleaved bytes a pixel; else 0
+    int order;       // Packed: OFLK_ORDER_*, what the luma weighs
+    int siting;      // Nv12: OFLK_SITING_*
+
+    static FrameLayout planar(bool u8) { return {FrameKind::Planar, u8 ? 1 : 4, 0, OFLK_ORDER_RGB, OFLK_SITING_LEFT}; }
+    static FrameLayout packed(int channels, int order) { return {FrameKind::Packed, 1, channels, order, OFLK_SITING_LEFT}; }
+    static FrameLayout nv12(int siting) { return {FrameKind::Nv12, 1, 0, OFLK_ORDER_RGB, siting}; }
+
+    size_t inside_bytes(int H, int W) const { return (size_t)H * (size_t)W; }   // the mask is a byte a pixel of every layout
+    size_t frame_bytes(int H, int W) const
+    {
+        const size_t px = (size_t)H * (size_t)W;
+        switch (kind) {
+        case FrameKind::Planar: return px * (size_t)pix_bytes;
+        case FrameKind::Packed: return px * (size_t)channels;
+        case FrameKind::Nv12: return px + px / 2;   // Y[H][W], then UV[H/2][W/2][2]
+        }
+        return 0;
+    }
+};
+
+int check_channels(int channels)
 {
-    if (F < 1) return fail(OFLK_ERR_INVALID, "F must be >= 1 (got %d)", F);
-    if (H < 2 || W < 2) return fail(OFLK_ERR_INVALID, "H and W must be >= 2 (got %d x %d)", H, W);
-    if (!frames || !map || !out) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
-    return check_hw(frames, out, H, W);
+    if (channels != 3 && channels != 4) return fail(OFLK_ERR_INVALID, "channels must be 3 or 4 (got %d)", channels);
+    return OFLK_OK;
 }
 
-// the one launch of the warp of F frames on stream s; the arguments are checked.  PERSP: d_map is [F][9] and the kernel
+int check_order(int order)
+{
+    if (order != OFLK_ORDER_RGB && order != OFLK_ORDER_BGR)
+        return fail(OFLK_ERR_INVALID, "order must be OFLK_ORDER_RGB or OFLK_ORDER_BGR (got %d)", order);
+    return OFLK_OK;
+}
+
+int check_nv12_shape(int H, int W, int siting)
+{
+    if (H < 4 || W < 4 || H % 2 || W % 2) return fail(OFLK_ERR_INVALID, "NV12 frames need even H and W >= 4 (got %d x %d)", H, W);
+    if (siting != OFLK_SITING_LEFT && siting != OFLK_SITING_CENTER)
+        return fail(OFLK_ERR_INVALID, "siting must be OFLK_SITING_LEFT or OFLK_SITING_CENTER (got %d)", siting);
+    return OFLK_OK;
+}
+
+// what a layout refuses of its own parameters and of the shape it needs: the first refusals of every call that names one
+int check_layout(const FrameLayout &L, int H, int W)
+{
+    switch (L.kind) {
+    case FrameKind::Planar: break;
+    case FrameKind::Packed:
+        if (int rc = check_channels(L.channels)) return rc;
+        return check_order(L.order);
+    case FrameKind::Nv12: return check_nv12_shape(H, W, L.siting);
+    }
+    return OFLK_OK;
+}
+
+// The frame refusals of a layout, in one order for every call that takes frames (tools/warp_host_check.hip holds the order and
+// the texts).  no_map: the call has a map and it is NULL (a call without one leaves it false): a planar call refuses that
+// with its other pointers, ahead of the size limits, a packed or NV12 call behind them.
+int check_frames(const FrameLayout &L, const void *frames, int F, int H, int W, const void *out, bool no_map = false)
+{
+    if (int rc = check_layout(L, H, W)) return rc;
+    if (F < 1) return fail(OFLK_ERR_INVALID, "F must be >= 1 (got %d)", F);
+    if (H < 2 || W < 2) return fail(OFLK_ERR_INVALID, "H and W must be >= 2 (got %d x %d)", H, W);
+    if (!frames || !out || (L.kind == FrameKind::Planar && no_map)) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    if (int rc = check_hw(frames, out, H, W)) return rc;   // H W < 2^30, so an NV12 frame's H W 3 / 2 bytes are counted by 32-bit offsets
+    if (L.kind == FrameKind::Packed && L.frame_bytes(H, W) >= ((size_t)1 << 31))
+        return fail(OFLK_ERR_UNSUPPORTED, "packed frames of 2^31 bytes or more are not supported");   // 32-bit byte offsets
+    if (no_map) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    return OFLK_OK;
+}
+
+// warp_frames' grid, which the packed warp shares: 4 rows of 64 lanes a block, kWarpPx pixels a lane, the frames in z
+dim3 warp_grid(int F, int H, int W)
+{
+    return dim3((unsigned)((H + 3) / 4), (unsigned)((W + 64 * kWarpPx - 1) / (64 * kWarpPx)), (unsigned)std::min(F, 65535));
+}
+
+// the one launch of the planar warp of F frames on stream s; the arguments are checked.  persp: d_map is [F][9] and the kernel
 // k_warp_perspective
-template <class PIX, bool PERSP = false>
-int warp_affine_launch(const PIX *d_frames, int F, int H, int W, const double *d_map, PIX *d_out, unsigned char *d_inside,
+template <class PIX>
+int warp_planar_launch(bool persp, const PIX *d_frames, int F, int H, int W, const double *d_map, PIX *d_out, unsigned char *d_inside,
                        hipStream_t s)
 {
     WarpAffineArgs<PIX> a{};
     a.in = d_frames; a.map = d_map; a.out = d_out; a.inside = d_inside;
     a.F = F; a.H = H; a.W = W;
     const bool vec = W % kWarpPx == 0 && aligned(d_out, (unsigned)(kWarpPx * sizeof(PIX))) && (!d_inside || aligned(d_inside, kWarpPx));
-    const dim3 grid((unsigned)((H + 3) / 4), (unsigned)((W + 64 * kWarpPx - 1) / (64 * kWarpPx)), (unsigned)std::min(F, 65535));
-    if constexpr (PERSP) {
-        if (vec)
-            hipLaunchKernelGGL((k_warp_perspective<PIX, true>), grid, dim3(256), 0, s, a);
-        else
-            hipLaunchKernelGGL((k_warp_perspective<PIX, false>), grid, dim3(256), 0, s, a);
-    } else {
-        if (vec)
-            hipLaunchKernelGGL((k_warp_affine<PIX, true>), grid, dim3(256), 0, s, a);
-        else
-            hipLaunchKernelGGL((k_warp_affine<PIX, false>), grid, dim3(256), 0, s, a);
-    }
+    with_bool(persp, [&](auto PERSP) {
+        with_bool(vec, [&](auto VEC) {
+            if constexpr (decltype(PERSP)::value)
+                hipLaunchKernelGGL((k_warp_perspective<PIX, decltype(VEC)::value>), warp_grid(F, H, W), dim3(256), 0, s, a);
+            else
+                hipLaunchKernelGGL((k_warp_affine<PIX, decltype(VEC)::value>), warp_grid(F, H, W), dim3(256), 0, s, a);
+        });
+    });
     HIP_TRY(hipGetLastError());
     return OFLK_OK;
 }
 
-// F host frames under the device maps d_map [F][6] (PERSP: [F][9]), in chunks of frames through one pair of device buffers: a
-// chunk goes up, is warped and comes down.  Frames are independent, so the result does not depend on the cut.
-template <class PIX, bool PERSP = false>
-int warp_affine_chunks(HostCall &call, const PIX *frames, int F, int H, int W, const double *d_map, PIX *out, unsigned char *inside)
+// oflk_stabilize_sequence and its packed and NV12 forms: pass 1 is the replenish call itself (its chunk loop; only rows come
+// down, into this call's own arrays); the rows go up again for the fit and the trajectory of all T frames, and pass 2 warps
+// the frames chunk by chunk.
+// What the sequence calls refuse behind their frames, before any device call
+int check_stabilize_config(int H, int W, int levels, int window_size, int iters, float alpha, float beta, float max_residual, float q,
+                           float md, int K, int detect_every, int model, int hypotheses, float threshold, const double *weights,
+                           int radius)
 {
-    const int C = sparse_chunk_pairs(F, H, W);
-    const size_t plane = (size_t)H * W;
-    PIX *d_in = nullptr, *d_out = nullptr;
-    unsigned char *d_inside = nullptr;
-    int rc;
-    if ((rc = call.alloc(&d_in, (size_t)C * plane)) || (rc = call.alloc(&d_out, (size_t)C * plane)) ||
-        (rc = call.alloc(&d_inside, (size_t)C * plane, inside != nullptr)))
-        return rc;
-    for (int f0 = 0; f0 < F; f0 += C) {
-        const int n = std::min(C, F - f0);
-        const size_t o = (size_t)f0 * plane, len = (size_t)n * plane;
-        if ((rc = call.to_device(d_in, frames + o, len)) ||
-            (rc = warp_affine_launch<PIX, PERSP>(d_in, n, H, W, d_map + (PERSP ? 9 : 6) * (size_t)f0, d_out, d_inside, nullptr)) ||
-            (rc = call.to_host(out + o, d_out, len)) || (inside && (rc = call.to_host(inside + o, d_inside, len))) ||
-            (rc = call.sync()))
-            return rc;
-    }
-    return OFLK_OK;
-}
-
-template <class PIX, bool PERSP = false>
-int warp_affine_host(const PIX *frames, int F, int H, int W, const double *map, PIX *out, unsigned char *inside)
-{
-    int rc = check_warp_affine(frames, F, H, W, map, out);
-    if (rc) return rc;
-    HostCall call;
-    if ((rc = call.begin())) return rc;
-    double *d_map = nullptr;
-    if ((rc = call.upload(&d_map, map, (PERSP ? 9 : 6) * (size_t)F))) return rc;
-    return warp_affine_chunks<PIX, PERSP>(call, frames, F, H, W, d_map, out, inside);
-}
-
-// oflk_stabilize_sequence: pass 1 is the replenish call itself (its chunk loop; only rows come down, into this call's own
-// arrays); the rows go up again for the fit and the trajectory of all T frames, and pass 2 warps the frames chunk by chunk
-// what the sequence calls refuse, before any device call (frames and out: the call's own pixels, grey or packed)
-int check_stabilize_sequence(const void *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
-                             float max_residual, float q, float md, int K, int detect_every, int model, int hypotheses,
-                             float threshold, const double *weights, int radius, const void *out)
-{
-    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
-    int rc = check_warp_affine(frames, T, H, W, frames, out);
-    if (rc || (rc = check_motion(model, hypotheses, threshold)) || (rc = check_stab_window(weights, radius))) return rc;
+    int rc = check_motion(model, hypotheses, threshold);
+    if (rc || (rc = check_stab_window(weights, radius))) return rc;
     // the replenish call's own refusals, ahead of this call's arrays (it repeats them)
     if (detect_every < 1) return fail(OFLK_ERR_INVALID, "detect_every must be >= 1 (got %d)", detect_every);
     if ((rc = check_select(q, md, K)) || (rc = check_sparse_test(alpha, beta, max_residual)) ||
@@ -3908,9 +3945,8 @@ int check_stabilize_sequence(const void *frames, int T, int H, int W, int levels
 
 // Pass 1 and the trajectory of a sequence call on the checked grey frames: begins `call`, leaves the maps of all T frames in
 // its *d_map_out [T][6] and sends the four small outputs on their way (the caller's last chunk synchronises)
-template <class PIX>
-int stabilize_maps(HostCall &call, const PIX *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
-                   float beta, float max_residual, float q, float md, int K, int detect_every, int model, int hypotheses,
+int stabilize_maps(HostCall &call, const void *frames, bool u8, int T, int H, int W, int levels, int window_size, int iters,
+                   float alpha, float beta, float max_residual, float q, float md, int K, int detect_every, int model, int hypotheses,
                    float threshold, unsigned seed, const double *weights, int radius, float *correction, float *model_out,
                    int *counts_out, unsigned char *held, double **d_map_out)
 {
@@ -3927,7 +3963,7 @@ int stabilize_maps(HostCall &call, const PIX *frames, int T, int H, int W, int l
     } catch (const std::exception &) {
         return fail(OFLK_ERR_NOMEM, "no host memory for the rows of %d frames of %d slots", T, K);
     }
-    if ((rc = run_sequence_tracks(Seq{frames, sizeof(PIX) == 1, T, H, W, levels, window_size, iters},
+    if ((rc = run_sequence_tracks(Seq{frames, u8, T, H, W, levels, window_size, iters},
                                   SparseTracks{{alpha, beta, max_residual}},
                                   Replenished{{q, md, K, detect_every}, born.data(), detected.data(), nullptr}, K, tracks.data(),
                                   visible.data())))
@@ -3956,24 +3992,6 @@ int stabilize_maps(HostCall &call, const PIX *frames, int T, int H, int W, int l
     *d_map_out = d_map;
     return OFLK_OK;
 }
-
-template <class PIX>
-int stabilize_sequence(const PIX *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
-                       float max_residual, float q, float md, int K, int detect_every, int model, int hypotheses, float threshold,
-                       unsigned seed, const double *weights, int radius, PIX *out, float *correction, float *model_out,
-                       int *counts_out, unsigned char *held)
-{
-    int rc = check_stabilize_sequence(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, q, md, K, detect_every,
-                                      model, hypotheses, threshold, weights, radius, out);
-    if (rc) return rc;
-    HostCall call;
-    double *d_map = nullptr;
-    if ((rc = stabilize_maps<PIX>(call, frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, q, md, K, detect_every,
-                                  model, hypotheses, threshold, seed, weights, radius, correction, model_out, counts_out, held,
-                                  &d_map)))
-        return rc;
-    return warp_affine_chunks<PIX>(call, frames, T, H, W, d_map, out, nullptr);
-}
 }  // namespace
 
 OFLK_API int oflk_stabilize_trajectory(const float *d_model, const int *d_counts, int T, const double *weights, int radius,
@@ -3984,16 +4002,6 @@ OFLK_API int oflk_stabilize_trajectory(const float *d_model, const int *d_counts
     return trajectory_launch(d_model, d_counts, T, weights, radius, d_correction, d_map, d_held, (hipStream_t)stream);
 }
 
-OFLK_API int oflk_warp_affine(const void *d_frames, int u8, int F, int H, int W, const double *d_map, void *d_out,
-                              unsigned char *d_inside, void *stream)
-{
-    if (int rc = check_warp_affine(d_frames, F, H, W, d_map, d_out)) return rc;
-    if (!aligned(d_map, 8)) return fail(OFLK_ERR_INVALID, "d_map must be 8-byte aligned");
-    if (!u8 && (!aligned(d_frames, 4) || !aligned(d_out, 4))) return fail(OFLK_ERR_INVALID, "float32 frames must be 4-byte aligned");
-    return u8 ? warp_affine_launch<unsigned char>((const unsigned char *)d_frames, F, H, W, d_map, (unsigned char *)d_out, d_inside,
-                                                  (hipStream_t)stream)
-              : warp_affine_launch<float>((const float *)d_frames, F, H, W, d_map, (float *)d_out, d_inside, (hipStream_t)stream);
-}
 
 OFLK_API int oflk_stabilize_trajectory_host(const float *model, const int *counts, int T, const double *weights, int radius,
                                             float *correction, double *map, unsigned char *held)
@@ -4017,92 +4025,10 @@ OFLK_API int oflk_stabilize_trajectory_host(const float *model, const int *count
     return call.sync();
 }
 
-OFLK_API int oflk_warp_affine_host(const float *frames, int F, int H, int W, const double *map, float *out, unsigned char *inside)
-{
-    return warp_affine_host<float>(frames, F, H, W, map, out, inside);
-}
-
-OFLK_API int oflk_warp_affine_host_u8(const unsigned char *frames, int F, int H, int W, const double *map, unsigned char *out,
-                                      unsigned char *inside)
-{
-    return warp_affine_host<unsigned char>(frames, F, H, W, map, out, inside);
-}
-
-// ---- the perspective warp: the affine warp's forms under 3 x 3 maps ----
-OFLK_API int oflk_warp_perspective(const void *d_frames, int u8, int F, int H, int W, const double *d_map, void *d_out,
-                                   unsigned char *d_inside, void *stream)
-{
-    if (int rc = check_warp_affine(d_frames, F, H, W, d_map, d_out)) return rc;
-    if (!aligned(d_map, 8)) return fail(OFLK_ERR_INVALID, "d_map must be 8-byte aligned");
-    if (!u8 && (!aligned(d_frames, 4) || !aligned(d_out, 4))) return fail(OFLK_ERR_INVALID, "float32 frames must be 4-byte aligned");
-    return u8 ? warp_affine_launch<unsigned char, true>((const unsigned char *)d_frames, F, H, W, d_map, (unsigned char *)d_out,
-                                                        d_inside, (hipStream_t)stream)
-              : warp_affine_launch<float, true>((const float *)d_frames, F, H, W, d_map, (float *)d_out, d_inside, (hipStream_t)stream);
-}
-
-OFLK_API int oflk_warp_perspective_host(const float *frames, int F, int H, int W, const double *map, float *out, unsigned char *inside)
-{
-    return warp_affine_host<float, true>(frames, F, H, W, map, out, inside);
-}
-
-OFLK_API int oflk_warp_perspective_host_u8(const unsigned char *frames, int F, int H, int W, const double *map, unsigned char *out,
-                                           unsigned char *inside)
-{
-    return warp_affine_host<unsigned char, true>(frames, F, H, W, map, out, inside);
-}
-
-OFLK_API int oflk_stabilize_sequence(const float *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
-                                     float beta, float max_residual, float quality_level, float min_distance, int max_corners,
-                                     int detect_every, int model, int hypotheses, float threshold, unsigned seed,
-                                     const double *weights, int radius, float *out, float *correction, float *model_out,
-                                     int *counts_out, unsigned char *held)
-{
-    return stabilize_sequence<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, quality_level,
-                                     min_distance, max_corners, detect_every, model, hypotheses, threshold, seed, weights, radius, out,
-                                     correction, model_out, counts_out, held);
-}
-
-OFLK_API int oflk_stabilize_sequence_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size, int iters,
-                                        float alpha, float beta, float max_residual, float quality_level, float min_distance,
-                                        int max_corners, int detect_every, int model, int hypotheses, float threshold,
-                                        unsigned seed, const double *weights, int radius, unsigned char *out, float *correction,
-                                        float *model_out, int *counts_out, unsigned char *held)
-{
-    return stabilize_sequence<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, quality_level,
-                                             min_distance, max_corners, detect_every, model, hypotheses, threshold, seed, weights,
-                                             radius, out, correction, model_out, counts_out, held);
-}
-
 // =============================================================================
-// colour video: interleaved bytes [F][H][W][C] -- luma, the packed warps and the packed sequence call (oflk_colour.hpp)
+// colour video: interleaved bytes [F][H][W][C] -- luma and the packed warp's launch (oflk_colour.hpp)
 // =============================================================================
 namespace {
-int check_channels(int channels)
-{
-    if (channels != 3 && channels != 4) return fail(OFLK_ERR_INVALID, "channels must be 3 or 4 (got %d)", channels);
-    return OFLK_OK;
-}
-
-int check_order(int order)
-{
-    if (order != OFLK_ORDER_RGB && order != OFLK_ORDER_BGR)
-        return fail(OFLK_ERR_INVALID, "order must be OFLK_ORDER_RGB or OFLK_ORDER_BGR (got %d)", order);
-    return OFLK_OK;
-}
-
-// the refusals every packed call shares: the planar warp's, and a frame whose bytes a 32-bit offset cannot count
-int check_packed(const void *frames, int F, int H, int W, int channels, const void *out)
-{
-    if (int rc = check_channels(channels)) return rc;
-    if (F < 1) return fail(OFLK_ERR_INVALID, "F must be >= 1 (got %d)", F);
-    if (H < 2 || W < 2) return fail(OFLK_ERR_INVALID, "H and W must be >= 2 (got %d x %d)", H, W);
-    if (!frames || !out) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
-    if (int rc = check_hw(frames, out, H, W)) return rc;
-    if ((size_t)H * (size_t)W * (size_t)channels >= ((size_t)1 << 31))
-        return fail(OFLK_ERR_UNSUPPORTED, "packed frames of 2^31 bytes or more are not supported");   // 32-bit byte offsets
-    return OFLK_OK;
-}
-
 // the one launch of the luma of F frames on stream s; the arguments are checked
 int luma_launch(const unsigned char *d_frames, int F, int H, int W, int channels, int order, unsigned char *d_luma, hipStream_t s)
 {
@@ -4113,36 +4039,18 @@ int luma_launch(const unsigned char *d_frames, int F, int H, int W, int channels
     const bool vec = W % kLumaPx == 0 && aligned(d_frames, channels == 4 ? 16 : 4) && aligned(d_luma, 4);
     const size_t work = vec ? a.n / kLumaPx : a.n;
     const dim3 grid((unsigned)std::min<size_t>((work + kLumaBlock - 1) / kLumaBlock, (size_t)65535 * 16));
-    if (channels == 3) {
-        if (vec)
-            hipLaunchKernelGGL((k_luma<3, true>), grid, dim3(kLumaBlock), 0, s, a);
-        else
-            hipLaunchKernelGGL((k_luma<3, false>), grid, dim3(kLumaBlock), 0, s, a);
-    } else {
-        if (vec)
-            hipLaunchKernelGGL((k_luma<4, true>), grid, dim3(kLumaBlock), 0, s, a);
-        else
-            hipLaunchKernelGGL((k_luma<4, false>), grid, dim3(kLumaBlock), 0, s, a);
-    }
+    with_int<3, 4>(channels, [&](auto C) {
+        with_bool(vec, [&](auto VEC) {
+            hipLaunchKernelGGL((k_luma<decltype(C)::value, decltype(VEC)::value>), grid, dim3(kLumaBlock), 0, s, a);
+        });
+    });
     HIP_TRY(hipGetLastError());
     return OFLK_OK;
 }
 
 // the one launch of the packed warp of F frames on stream s; the arguments are checked
-template <int C, bool PERSP>
-int warp_packed_launch_c(const WarpPackedArgs &a, bool vec, const dim3 grid, hipStream_t s)
-{
-    if (vec)
-        hipLaunchKernelGGL((k_warp_packed<C, PERSP, true>), grid, dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL((k_warp_packed<C, PERSP, false>), grid, dim3(256), 0, s, a);
-    HIP_TRY(hipGetLastError());
-    return OFLK_OK;
-}
-
-template <bool PERSP>
-int warp_packed_launch(const unsigned char *d_frames, int F, int H, int W, int channels, const double *d_map, unsigned char *d_out,
-                       unsigned char *d_inside, hipStream_t s)
+int warp_packed_launch(bool persp, const unsigned char *d_frames, int F, int H, int W, int channels, const double *d_map,
+                       unsigned char *d_out, unsigned char *d_inside, hipStream_t s)
 {
     WarpPackedArgs a{};
     a.in = d_frames; a.map = d_map; a.out = d_out; a.inside = d_inside;
@@ -4150,56 +4058,16 @@ int warp_packed_launch(const unsigned char *d_frames, int F, int H, int W, int c
     // a lane's store: three dwords (C = 3) or one dwordx4 (C = 4), and the inside dword
     const bool vec = W % kWarpPx == 0 && aligned(d_out, channels == 4 ? 16 : 4) &&
                      (!d_inside || aligned(d_inside, kWarpPx));
-    const dim3 grid((unsigned)((H + 3) / 4), (unsigned)((W + 64 * kWarpPx - 1) / (64 * kWarpPx)), (unsigned)std::min(F, 65535));
-    return channels == 3 ? warp_packed_launch_c<3, PERSP>(a, vec, grid, s) : warp_packed_launch_c<4, PERSP>(a, vec, grid, s);
-}
-
-// F packed host frames under the device maps d_map, in warp_affine_chunks' chunks through one pair of device buffers
-template <bool PERSP>
-int warp_packed_chunks(HostCall &call, const unsigned char *frames, int F, int H, int W, int channels, const double *d_map,
-                       unsigned char *out, unsigned char *inside)
-{
-    const int C = sparse_chunk_pairs(F, H, W);
-    const size_t plane = (size_t)H * W, fb = plane * (size_t)channels;
-    unsigned char *d_in = nullptr, *d_out = nullptr, *d_inside = nullptr;
-    int rc;
-    if ((rc = call.alloc(&d_in, (size_t)C * fb)) || (rc = call.alloc(&d_out, (size_t)C * fb)) ||
-        (rc = call.alloc(&d_inside, (size_t)C * plane, inside != nullptr)))
-        return rc;
-    for (int f0 = 0; f0 < F; f0 += C) {
-        const int n = std::min(C, F - f0);
-        const size_t o = (size_t)f0 * fb, len = (size_t)n * fb;
-        if ((rc = call.to_device(d_in, frames + o, len)) ||
-            (rc = warp_packed_launch<PERSP>(d_in, n, H, W, channels, d_map + (PERSP ? 9 : 6) * (size_t)f0, d_out, d_inside, nullptr)) ||
-            (rc = call.to_host(out + o, d_out, len)) ||
-            (inside && (rc = call.to_host(inside + (size_t)f0 * plane, d_inside, (size_t)n * plane))) || (rc = call.sync()))
-            return rc;
-    }
+    with_int<3, 4>(channels, [&](auto C) {
+        with_bool(persp, [&](auto PERSP) {
+            with_bool(vec, [&](auto VEC) {
+                hipLaunchKernelGGL((k_warp_packed<decltype(C)::value, decltype(PERSP)::value, decltype(VEC)::value>), warp_grid(F, H, W),
+                                   dim3(256), 0, s, a);
+            });
+        });
+    });
+    HIP_TRY(hipGetLastError());
     return OFLK_OK;
-}
-
-template <bool PERSP>
-int warp_packed_host(const unsigned char *frames, int F, int H, int W, int channels, const double *map, unsigned char *out,
-                     unsigned char *inside)
-{
-    int rc = check_packed(frames, F, H, W, channels, out);
-    if (rc) return rc;
-    if (!map) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
-    HostCall call;
-    if ((rc = call.begin())) return rc;
-    double *d_map = nullptr;
-    if ((rc = call.upload(&d_map, map, (PERSP ? 9 : 6) * (size_t)F))) return rc;
-    return warp_packed_chunks<PERSP>(call, frames, F, H, W, channels, d_map, out, inside);
-}
-
-template <bool PERSP>
-int warp_packed_device(const unsigned char *d_frames, int F, int H, int W, int channels, const double *d_map, unsigned char *d_out,
-                       unsigned char *d_inside, void *stream)
-{
-    if (int rc = check_packed(d_frames, F, H, W, channels, d_out)) return rc;
-    if (!d_map) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
-    if (!aligned(d_map, 8)) return fail(OFLK_ERR_INVALID, "d_map must be 8-byte aligned");
-    return warp_packed_launch<PERSP>(d_frames, F, H, W, channels, d_map, d_out, d_inside, (hipStream_t)stream);
 }
 
 // the luma of F packed host frames in the warp's chunks: a chunk goes up, is converted and its luma comes down
@@ -4224,105 +4092,27 @@ int luma_chunks(HostCall &call, const unsigned char *frames, int F, int H, int W
 OFLK_API int oflk_luma_u8(const unsigned char *d_frames, int F, int H, int W, int channels, int order, unsigned char *d_luma,
                           void *stream)
 {
-    int rc = check_packed(d_frames, F, H, W, channels, d_luma);
+    int rc = check_frames(FrameLayout::packed(channels, OFLK_ORDER_RGB), d_frames, F, H, W, d_luma);
     if (rc || (rc = check_order(order))) return rc;
     return luma_launch(d_frames, F, H, W, channels, order, d_luma, (hipStream_t)stream);
 }
 
 OFLK_API int oflk_luma_u8_host(const unsigned char *frames, int F, int H, int W, int channels, int order, unsigned char *luma)
 {
-    int rc = check_packed(frames, F, H, W, channels, luma);
+    int rc = check_frames(FrameLayout::packed(channels, OFLK_ORDER_RGB), frames, F, H, W, luma);
     if (rc || (rc = check_order(order))) return rc;
     HostCall call;
     if ((rc = call.begin())) return rc;
     return luma_chunks(call, frames, F, H, W, channels, order, luma);
 }
 
-OFLK_API int oflk_warp_affine_packed(const unsigned char *d_frames, int F, int H, int W, int channels, const double *d_map,
-                                     unsigned char *d_out, unsigned char *d_inside, void *stream)
-{
-    return warp_packed_device<false>(d_frames, F, H, W, channels, d_map, d_out, d_inside, stream);
-}
-
-OFLK_API int oflk_warp_perspective_packed(const unsigned char *d_frames, int F, int H, int W, int channels, const double *d_map,
-                                          unsigned char *d_out, unsigned char *d_inside, void *stream)
-{
-    return warp_packed_device<true>(d_frames, F, H, W, channels, d_map, d_out, d_inside, stream);
-}
-
-OFLK_API int oflk_warp_affine_packed_host(const unsigned char *frames, int F, int H, int W, int channels, const double *map,
-                                          unsigned char *out, unsigned char *inside)
-{
-    return warp_packed_host<false>(frames, F, H, W, channels, map, out, inside);
-}
-
-OFLK_API int oflk_warp_perspective_packed_host(const unsigned char *frames, int F, int H, int W, int channels, const double *map,
-                                               unsigned char *out, unsigned char *inside)
-{
-    return warp_packed_host<true>(frames, F, H, W, channels, map, out, inside);
-}
-
-// The luma of all T frames comes down into a host array of its own (one byte per pixel: a third or a quarter of the caller's
-// frames) in a chunked pass ahead of pass 1, which then is the grey call's on that array; pass 2 warps the packed frames
-OFLK_API int oflk_stabilize_sequence_packed(const unsigned char *frames, int T, int H, int W, int channels, int order, int levels,
-                                            int window_size, int iters, float alpha, float beta, float max_residual,
-                                            float quality_level, float min_distance, int max_corners, int detect_every, int model,
-                                            int hypotheses, float threshold, unsigned seed, const double *weights, int radius,
-                                            unsigned char *out, float *correction, float *model_out, int *counts_out,
-                                            unsigned char *held)
-{
-    int rc = check_channels(channels);
-    if (rc || (rc = check_order(order))) return rc;
-    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
-    if ((rc = check_packed(frames, T, H, W, channels, out)) ||
-        (rc = check_stabilize_sequence(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, quality_level,
-                                       min_distance, max_corners, detect_every, model, hypotheses, threshold, weights, radius, out)))
-        return rc;
-    std::vector<unsigned char> luma;
-    try {
-        luma.resize((size_t)T * H * W);
-    } catch (const std::exception &) {
-        return fail(OFLK_ERR_NOMEM, "no host memory for the luma of %d frames of %d x %d", T, W, H);
-    }
-    {
-        HostCall call;
-        if ((rc = call.begin()) || (rc = luma_chunks(call, frames, T, H, W, channels, order, luma.data()))) return rc;
-    }
-    HostCall call;
-    double *d_map = nullptr;
-    if ((rc = stabilize_maps<unsigned char>(call, luma.data(), T, H, W, levels, window_size, iters, alpha, beta, max_residual,
-                                            quality_level, min_distance, max_corners, detect_every, model, hypotheses, threshold, seed,
-                                            weights, radius, correction, model_out, counts_out, held, &d_map)))
-        return rc;
-    return warp_packed_chunks<false>(call, frames, T, H, W, channels, d_map, out, nullptr);
-}
-
 // =============================================================================
-// NV12 video: Y[H][W] then UV[H/2][W/2][2] in H W 3 / 2 contiguous bytes -- the fused two-plane warps and the NV12 sequence
-// call (oflk_nv12.hpp)
+// NV12 video: Y[H][W] then UV[H/2][W/2][2] in H W 3 / 2 contiguous bytes -- the fused two-plane warp's launch (oflk_nv12.hpp)
 // =============================================================================
 namespace {
-int check_nv12_shape(int H, int W, int siting)
-{
-    if (H < 4 || W < 4 || H % 2 || W % 2) return fail(OFLK_ERR_INVALID, "NV12 frames need even H and W >= 4 (got %d x %d)", H, W);
-    if (siting != OFLK_SITING_LEFT && siting != OFLK_SITING_CENTER)
-        return fail(OFLK_ERR_INVALID, "siting must be OFLK_SITING_LEFT or OFLK_SITING_CENTER (got %d)", siting);
-    return OFLK_OK;
-}
-
-// the refusals every NV12 call shares: the shape's, and the planar warp's on the Y plane
-int check_nv12(const void *frames, int F, int H, int W, int siting, const void *out)
-{
-    if (int rc = check_nv12_shape(H, W, siting)) return rc;
-    if (F < 1) return fail(OFLK_ERR_INVALID, "F must be >= 1 (got %d)", F);
-    if (!frames || !out) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
-    return check_hw(frames, out, H, W);   // H W < 2^30, so a frame's H W 3 / 2 bytes are counted by 32-bit offsets
-}
-
 // the one launch of both planes of F frames on stream s; the arguments are checked
-template <bool PERSP>
-int warp_nv12_launch(const unsigned char *d_frames, int F, int H, int W, int siting, const double *d_map, unsigned char *d_out,
-                     unsigned char *d_inside, hipStream_t s)
+int warp_nv12_launch(bool persp, const unsigned char *d_frames, int F, int H, int W, int siting, const double *d_map,
+                     unsigned char *d_out, unsigned char *d_inside, hipStream_t s)
 {
     WarpNv12Args a{};
     a.in = d_frames; a.map = d_map; a.out = d_out; a.inside = d_inside;
@@ -4338,62 +4128,13 @@ int warp_nv12_launch(const unsigned char *d_frames, int F, int H, int W, int sit
     const bool vec_luma = W % kWarpPx == 0 && aligned(d_out, kWarpPx) && (!d_inside || aligned(d_inside, kWarpPx));
     const int vec = !vec_luma ? 0 : W % (2 * kWarpPx) == 0 && aligned(d_out, 2 * kWarpPx) ? 2 : 1;
     const dim3 grid(a.luma_groups + (chroma_blocks + cols - 1) / cols, cols, (unsigned)std::min(F, 65535));
-    if (vec == 2)
-        hipLaunchKernelGGL((k_warp_nv12<PERSP, 2>), grid, dim3(256), 0, s, a);
-    else if (vec == 1)
-        hipLaunchKernelGGL((k_warp_nv12<PERSP, 1>), grid, dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL((k_warp_nv12<PERSP, 0>), grid, dim3(256), 0, s, a);
+    with_bool(persp, [&](auto PERSP) {
+        with_int<0, 1, 2>(vec, [&](auto VEC) {
+            hipLaunchKernelGGL((k_warp_nv12<decltype(PERSP)::value, decltype(VEC)::value>), grid, dim3(256), 0, s, a);
+        });
+    });
     HIP_TRY(hipGetLastError());
     return OFLK_OK;
-}
-
-// F NV12 host frames under the device maps d_map, in warp_affine_chunks' chunks through one pair of device buffers
-template <bool PERSP>
-int warp_nv12_chunks(HostCall &call, const unsigned char *frames, int F, int H, int W, int siting, const double *d_map,
-                     unsigned char *out, unsigned char *inside)
-{
-    const int C = sparse_chunk_pairs(F, H, W);
-    const size_t plane = (size_t)H * W, fb = plane + plane / 2;
-    unsigned char *d_in = nullptr, *d_out = nullptr, *d_inside = nullptr;
-    int rc;
-    if ((rc = call.alloc(&d_in, (size_t)C * fb)) || (rc = call.alloc(&d_out, (size_t)C * fb)) ||
-        (rc = call.alloc(&d_inside, (size_t)C * plane, inside != nullptr)))
-        return rc;
-    for (int f0 = 0; f0 < F; f0 += C) {
-        const int n = std::min(C, F - f0);
-        const size_t o = (size_t)f0 * fb, len = (size_t)n * fb;
-        if ((rc = call.to_device(d_in, frames + o, len)) ||
-            (rc = warp_nv12_launch<PERSP>(d_in, n, H, W, siting, d_map + (PERSP ? 9 : 6) * (size_t)f0, d_out, d_inside, nullptr)) ||
-            (rc = call.to_host(out + o, d_out, len)) ||
-            (inside && (rc = call.to_host(inside + (size_t)f0 * plane, d_inside, (size_t)n * plane))) || (rc = call.sync()))
-            return rc;
-    }
-    return OFLK_OK;
-}
-
-template <bool PERSP>
-int warp_nv12_host(const unsigned char *frames, int F, int H, int W, int siting, const double *map, unsigned char *out,
-                   unsigned char *inside)
-{
-    int rc = check_nv12(frames, F, H, W, siting, out);
-    if (rc) return rc;
-    if (!map) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
-    HostCall call;
-    if ((rc = call.begin())) return rc;
-    double *d_map = nullptr;
-    if ((rc = call.upload(&d_map, map, (PERSP ? 9 : 6) * (size_t)F))) return rc;
-    return warp_nv12_chunks<PERSP>(call, frames, F, H, W, siting, d_map, out, inside);
-}
-
-template <bool PERSP>
-int warp_nv12_device(const unsigned char *d_frames, int F, int H, int W, int siting, const double *d_map, unsigned char *d_out,
-                     unsigned char *d_inside, void *stream)
-{
-    if (int rc = check_nv12(d_frames, F, H, W, siting, d_out)) return rc;
-    if (!d_map) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
-    if (!aligned(d_map, 8)) return fail(OFLK_ERR_INVALID, "d_map must be 8-byte aligned");
-    return warp_nv12_launch<PERSP>(d_frames, F, H, W, siting, d_map, d_out, d_inside, (hipStream_t)stream);
 }
 }  // namespace
 
@@ -4403,60 +4144,257 @@ OFLK_API size_t oflk_nv12_frame_bytes(int H, int W)
     return (size_t)H * (size_t)W / 2 * 3;
 }
 
+// =============================================================================
+// frames of any layout: the one path of the warps and the sequence stabilisers
+// =============================================================================
+namespace {
+// the one launch of the warp of F frames of layout L on stream s: the single point that picks among the three launchers.  The
+// arguments are checked.  persp: d_map is [F][9]
+int warp_launch(const FrameLayout &L, bool persp, const void *d_frames, int F, int H, int W, const double *d_map, void *d_out,
+                unsigned char *d_inside, hipStream_t s)
+{
+    const unsigned char *in = static_cast<const unsigned char *>(d_frames);
+    unsigned char *out = static_cast<unsigned char *>(d_out);
+    switch (L.kind) {
+    case FrameKind::Planar: {
+        int rc = OFLK_OK;
+        with_pix(L.pix_bytes == 1, [&](auto PIX) {
+            using P = typename decltype(PIX)::type;
+            rc = warp_planar_launch<P>(persp, (const P *)d_frames, F, H, W, d_map, (P *)d_out, d_inside, s);
+        });
+        return rc;
+    }
+    case FrameKind::Packed: return warp_packed_launch(persp, in, F, H, W, L.channels, d_map, out, d_inside, s);
+    case FrameKind::Nv12: return warp_nv12_launch(persp, in, F, H, W, L.siting, d_map, out, d_inside, s);
+    }
+    return OFLK_OK;
+}
+
+// F host frames under the device maps d_map [F][6] (persp: [F][9]), in chunks of frames through one pair of device buffers: a
+// chunk goes up, is warped and comes down.  Frames are independent, so the result does not depend on the cut.
+int warp_chunks(HostCall &call, const FrameLayout &L, bool persp, const void *frames, int F, int H, int W, const double *d_map,
+                void *out, unsigned char *inside)
+{
+    const int C = sparse_chunk_pairs(F, H, W);
+    const size_t fb = L.frame_bytes(H, W), ib = L.inside_bytes(H, W);
+    const unsigned char *src = static_cast<const unsigned char *>(frames);
+    unsigned char *dst = static_cast<unsigned char *>(out), *d_in = nullptr, *d_out = nullptr, *d_inside = nullptr;
+    int rc;
+    if ((rc = call.alloc(&d_in, (size_t)C * fb)) || (rc = call.alloc(&d_out, (size_t)C * fb)) ||
+        (rc = call.alloc(&d_inside, (size_t)C * ib, inside != nullptr)))
+        return rc;
+    for (int f0 = 0; f0 < F; f0 += C) {
+        const int n = std::min(C, F - f0);
+        const size_t o = (size_t)f0 * fb, len = (size_t)n * fb;
+        if ((rc = call.to_device(d_in, src + o, len)) ||
+            (rc = warp_launch(L, persp, d_in, n, H, W, d_map + (persp ? 9 : 6) * (size_t)f0, d_out, d_inside, nullptr)) ||
+            (rc = call.to_host(dst + o, d_out, len)) ||
+            (inside && (rc = call.to_host(inside + (size_t)f0 * ib, d_inside, (size_t)n * ib))) || (rc = call.sync()))
+            return rc;
+    }
+    return OFLK_OK;
+}
+
+int warp_host(const FrameLayout &L, bool persp, const void *frames, int F, int H, int W, const double *map, void *out,
+              unsigned char *inside)
+{
+    int rc = check_frames(L, frames, F, H, W, out, !map);
+    if (rc) return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    double *d_map = nullptr;
+    if ((rc = call.upload(&d_map, map, (persp ? 9 : 6) * (size_t)F))) return rc;
+    return warp_chunks(call, L, persp, frames, F, H, W, d_map, out, inside);
+}
+
+int warp_device(const FrameLayout &L, bool persp, const void *d_frames, int F, int H, int W, const double *d_map, void *d_out,
+                unsigned char *d_inside, void *stream)
+{
+    if (int rc = check_frames(L, d_frames, F, H, W, d_out, !d_map)) return rc;
+    if (!aligned(d_map, 8)) return fail(OFLK_ERR_INVALID, "d_map must be 8-byte aligned");
+    if (L.kind == FrameKind::Planar && L.pix_bytes == 4 && (!aligned(d_frames, 4) || !aligned(d_out, 4)))
+        return fail(OFLK_ERR_INVALID, "float32 frames must be 4-byte aligned");
+    return warp_launch(L, persp, d_frames, F, H, W, d_map, d_out, d_inside, (hipStream_t)stream);
+}
+
+// The sequence stabiliser of every layout.  Pass 1 is the grey call's, on the frames themselves (planar) or on a host array
+// of luma of this call's own, one byte a pixel: the packed frames' luma comes down in a chunked pass ahead of pass 1 (a
+// third or a quarter of the caller's frames), the NV12 frames' Y planes are gathered with no device work (two thirds).
+// Pass 2 warps the caller's frames in their own layout.
+int stabilize_sequence(const FrameLayout &L, const void *frames, int T, int H, int W, int levels, int window_size, int iters,
+                       float alpha, float beta, float max_residual, float q, float md, int K, int detect_every, int model,
+                       int hypotheses, float threshold, unsigned seed, const double *weights, int radius, void *out,
+                       float *correction, float *model_out, int *counts_out, unsigned char *held)
+{
+    int rc = check_layout(L, H, W);
+    if (rc) return rc;
+    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
+    if ((rc = check_frames(L, frames, T, H, W, out)) ||
+        (rc = check_stabilize_config(H, W, levels, window_size, iters, alpha, beta, max_residual, q, md, K, detect_every, model,
+                                     hypotheses, threshold, weights, radius)))
+        return rc;
+    const unsigned char *bytes = static_cast<const unsigned char *>(frames);
+    const size_t plane = (size_t)H * W;
+    std::vector<unsigned char> luma;
+    switch (L.kind) {
+    case FrameKind::Planar: break;
+    case FrameKind::Packed: {
+        try {
+            luma.resize((size_t)T * plane);
+        } catch (const std::exception &) {
+            return fail(OFLK_ERR_NOMEM, "no host memory for the luma of %d frames of %d x %d", T, W, H);
+        }
+        HostCall call;
+        if ((rc = call.begin()) || (rc = luma_chunks(call, bytes, T, H, W, L.channels, L.order, luma.data()))) return rc;
+        break;
+    }
+    case FrameKind::Nv12:
+        try {
+            luma.resize((size_t)T * plane);
+        } catch (const std::exception &) {
+            return fail(OFLK_ERR_NOMEM, "no host memory for the Y planes of %d frames of %d x %d", T, W, H);
+        }
+        for (int t = 0; t < T; t++) std::memcpy(luma.data() + (size_t)t * plane, bytes + (size_t)t * L.frame_bytes(H, W), plane);
+        break;
+    }
+    const bool planar = L.kind == FrameKind::Planar;
+    HostCall call;
+    double *d_map = nullptr;
+    if ((rc = stabilize_maps(call, planar ? frames : luma.data(), planar ? L.pix_bytes == 1 : true, T, H, W, levels, window_size, iters,
+                             alpha, beta, max_residual, q, md, K, detect_every, model, hypotheses, threshold, seed, weights, radius,
+                             correction, model_out, counts_out, held, &d_map)))
+        return rc;
+    return warp_chunks(call, L, false, frames, T, H, W, d_map, out, nullptr);
+}
+}  // namespace
+
+// ---- the twelve warps: affine and perspective, device and host, of the four layouts ----
+OFLK_API int oflk_warp_affine(const void *d_frames, int u8, int F, int H, int W, const double *d_map, void *d_out,
+                              unsigned char *d_inside, void *stream)
+{
+    return warp_device(FrameLayout::planar(u8 != 0), false, d_frames, F, H, W, d_map, d_out, d_inside, stream);
+}
+
+OFLK_API int oflk_warp_perspective(const void *d_frames, int u8, int F, int H, int W, const double *d_map, void *d_out,
+                                   unsigned char *d_inside, void *stream)
+{
+    return warp_device(FrameLayout::planar(u8 != 0), true, d_frames, F, H, W, d_map, d_out, d_inside, stream);
+}
+
+OFLK_API int oflk_warp_affine_host(const float *frames, int F, int H, int W, const double *map, float *out, unsigned char *inside)
+{
+    return warp_host(FrameLayout::planar(false), false, frames, F, H, W, map, out, inside);
+}
+
+OFLK_API int oflk_warp_affine_host_u8(const unsigned char *frames, int F, int H, int W, const double *map, unsigned char *out,
+                                      unsigned char *inside)
+{
+    return warp_host(FrameLayout::planar(true), false, frames, F, H, W, map, out, inside);
+}
+
+OFLK_API int oflk_warp_perspective_host(const float *frames, int F, int H, int W, const double *map, float *out, unsigned char *inside)
+{
+    return warp_host(FrameLayout::planar(false), true, frames, F, H, W, map, out, inside);
+}
+
+OFLK_API int oflk_warp_perspective_host_u8(const unsigned char *frames, int F, int H, int W, const double *map, unsigned char *out,
+                                           unsigned char *inside)
+{
+    return warp_host(FrameLayout::planar(true), true, frames, F, H, W, map, out, inside);
+}
+
+OFLK_API int oflk_warp_affine_packed(const unsigned char *d_frames, int F, int H, int W, int channels, const double *d_map,
+                                     unsigned char *d_out, unsigned char *d_inside, void *stream)
+{
+    return warp_device(FrameLayout::packed(channels, OFLK_ORDER_RGB), false, d_frames, F, H, W, d_map, d_out, d_inside, stream);
+}
+
+OFLK_API int oflk_warp_perspective_packed(const unsigned char *d_frames, int F, int H, int W, int channels, const double *d_map,
+                                          unsigned char *d_out, unsigned char *d_inside, void *stream)
+{
+    return warp_device(FrameLayout::packed(channels, OFLK_ORDER_RGB), true, d_frames, F, H, W, d_map, d_out, d_inside, stream);
+}
+
+OFLK_API int oflk_warp_affine_packed_host(const unsigned char *frames, int F, int H, int W, int channels, const double *map,
+                                          unsigned char *out, unsigned char *inside)
+{
+    return warp_host(FrameLayout::packed(channels, OFLK_ORDER_RGB), false, frames, F, H, W, map, out, inside);
+}
+
+OFLK_API int oflk_warp_perspective_packed_host(const unsigned char *frames, int F, int H, int W, int channels, const double *map,
+                                               unsigned char *out, unsigned char *inside)
+{
+    return warp_host(FrameLayout::packed(channels, OFLK_ORDER_RGB), true, frames, F, H, W, map, out, inside);
+}
+
 OFLK_API int oflk_warp_affine_nv12(const unsigned char *d_frames, int F, int H, int W, int siting, const double *d_map,
                                    unsigned char *d_out, unsigned char *d_inside, void *stream)
 {
-    return warp_nv12_device<false>(d_frames, F, H, W, siting, d_map, d_out, d_inside, stream);
+    return warp_device(FrameLayout::nv12(siting), false, d_frames, F, H, W, d_map, d_out, d_inside, stream);
 }
 
 OFLK_API int oflk_warp_perspective_nv12(const unsigned char *d_frames, int F, int H, int W, int siting, const double *d_map,
                                         unsigned char *d_out, unsigned char *d_inside, void *stream)
 {
-    return warp_nv12_device<true>(d_frames, F, H, W, siting, d_map, d_out, d_inside, stream);
+    return warp_device(FrameLayout::nv12(siting), true, d_frames, F, H, W, d_map, d_out, d_inside, stream);
 }
 
 OFLK_API int oflk_warp_affine_nv12_host(const unsigned char *frames, int F, int H, int W, int siting, const double *map,
                                         unsigned char *out, unsigned char *inside)
 {
-    return warp_nv12_host<false>(frames, F, H, W, siting, map, out, inside);
+    return warp_host(FrameLayout::nv12(siting), false, frames, F, H, W, map, out, inside);
 }
 
 OFLK_API int oflk_warp_perspective_nv12_host(const unsigned char *frames, int F, int H, int W, int siting, const double *map,
                                              unsigned char *out, unsigned char *inside)
 {
-    return warp_nv12_host<true>(frames, F, H, W, siting, map, out, inside);
+    return warp_host(FrameLayout::nv12(siting), true, frames, F, H, W, map, out, inside);
 }
 
-// The Y planes of all T frames are gathered into a host array of their own (two thirds of the caller's frames, no device
-// work), pass 1 is the grey call's on that array, and pass 2 warps the NV12 frames
+// ---- the four sequence stabilisers ----
+OFLK_API int oflk_stabilize_sequence(const float *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
+                                     float beta, float max_residual, float quality_level, float min_distance, int max_corners,
+                                     int detect_every, int model, int hypotheses, float threshold, unsigned seed,
+                                     const double *weights, int radius, float *out, float *correction, float *model_out,
+                                     int *counts_out, unsigned char *held)
+{
+    return stabilize_sequence(FrameLayout::planar(false), frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual,
+                              quality_level, min_distance, max_corners, detect_every, model, hypotheses, threshold, seed, weights, radius,
+                              out, correction, model_out, counts_out, held);
+}
+
+OFLK_API int oflk_stabilize_sequence_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                        float alpha, float beta, float max_residual, float quality_level, float min_distance,
+                                        int max_corners, int detect_every, int model, int hypotheses, float threshold,
+                                        unsigned seed, const double *weights, int radius, unsigned char *out, float *correction,
+                                        float *model_out, int *counts_out, unsigned char *held)
+{
+    return stabilize_sequence(FrameLayout::planar(true), frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual,
+                              quality_level, min_distance, max_corners, detect_every, model, hypotheses, threshold, seed, weights, radius,
+                              out, correction, model_out, counts_out, held);
+}
+
+OFLK_API int oflk_stabilize_sequence_packed(const unsigned char *frames, int T, int H, int W, int channels, int order, int levels,
+                                            int window_size, int iters, float alpha, float beta, float max_residual,
+                                            float quality_level, float min_distance, int max_corners, int detect_every, int model,
+                                            int hypotheses, float threshold, unsigned seed, const double *weights, int radius,
+                                            unsigned char *out, float *correction, float *model_out, int *counts_out,
+                                            unsigned char *held)
+{
+    return stabilize_sequence(FrameLayout::packed(channels, order), frames, T, H, W, levels, window_size, iters, alpha, beta,
+                              max_residual, quality_level, min_distance, max_corners, detect_every, model, hypotheses, threshold, seed,
+                              weights, radius, out, correction, model_out, counts_out, held);
+}
+
 OFLK_API int oflk_stabilize_sequence_nv12(const unsigned char *frames, int T, int H, int W, int siting, int levels, int window_size,
                                           int iters, float alpha, float beta, float max_residual, float quality_level,
                                           float min_distance, int max_corners, int detect_every, int model, int hypotheses,
                                           float threshold, unsigned seed, const double *weights, int radius, unsigned char *out,
                                           float *correction, float *model_out, int *counts_out, unsigned char *held)
 {
-    int rc = check_nv12_shape(H, W, siting);
-    if (rc) return rc;
-    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
-    if ((rc = check_nv12(frames, T, H, W, siting, out)) ||
-        (rc = check_stabilize_sequence(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, quality_level,
-                                       min_distance, max_corners, detect_every, model, hypotheses, threshold, weights, radius, out)))
-        return rc;
-    const size_t plane = (size_t)H * W, fb = plane + plane / 2;
-    std::vector<unsigned char> luma;
-    try {
-        luma.resize((size_t)T * plane);
-    } catch (const std::exception &) {
-        return fail(OFLK_ERR_NOMEM, "no host memory for the Y planes of %d frames of %d x %d", T, W, H);
-    }
-    for (int t = 0; t < T; t++) std::memcpy(luma.data() + (size_t)t * plane, frames + (size_t)t * fb, plane);
-    HostCall call;
-    double *d_map = nullptr;
-    if ((rc = stabilize_maps<unsigned char>(call, luma.data(), T, H, W, levels, window_size, iters, alpha, beta, max_residual,
-                                            quality_level, min_distance, max_corners, detect_every, model, hypotheses, threshold, seed,
-                                            weights, radius, correction, model_out, counts_out, held, &d_map)))
-        return rc;
-    return warp_nv12_chunks<false>(call, frames, T, H, W, siting, d_map, out, nullptr);
+    return stabilize_sequence(FrameLayout::nv12(siting), frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual,
+                              quality_level, min_distance, max_corners, detect_every, model, hypotheses, threshold, seed, weights, radius,
+                              out, correction, model_out, counts_out, held);
 }
 
 // =============================================================================
@@ -4622,7 +4560,7 @@ int mosaic_sequence(const PIX *frames, int T, int H, int W, int levels, int wind
 {
     if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
     if (!canvas) return fail(OFLK_ERR_INVALID, "NULL canvas");
-    int rc = check_warp_affine(frames, T, H, W, frames, out);
+    int rc = check_frames(FrameLayout::planar(sizeof(PIX) == 1), frames, T, H, W, out);
     if (rc || (rc = check_ransac(hypotheses, threshold)) || (rc = check_mosaic_blend(blend)) ||
         (rc = check_mosaic_chain(frames, T, anchor, H, W, extent, frames, frames, frames, frames)))
         return rc;
@@ -5526,29 +5464,22 @@ struct oflk_stabilizer {
     bool flushed = false;             // the stream has ended: pushes are refused until reset
     int rows = 0;                     // rows of corr / map the last emission wrote
     size_t ws_bytes = 0;
-    char *delay = nullptr;            // [r + 1][H][W], the input pixel type
+    char *delay = nullptr;            // [r + 1] frames of the layout
     float *ring_model = nullptr;      // [cap][6]
     int *ring_counts = nullptr;       // [cap][3]
     float *corr = nullptr;            // [max(r, 1)][6]
     double *map = nullptr;            // [max(r, 1)][6]
     float *own_model = nullptr;       // the tracker's own motion row, put back before it is freed
     int *own_counts = nullptr;
-    char *stage_out = nullptr;        // [H][W] in the pixel type and [H][W] bytes: the host forms' staging
+    char *stage_out = nullptr;        // a frame of the layout and [H][W] bytes: the host forms' staging
     unsigned char *stage_inside = nullptr;
-    // oflk_stabilizer_create_packed: the delay line and every frame in and out are [H][W][channels] bytes, and the tracker
-    // (uint8) is pushed the luma of the frame, formed in `luma` by the push
-    int channels = 0, order = 0;      // 0 channels: a grey stabiliser
-    unsigned char *luma = nullptr;    // [H][W]
-    // oflk_stabilizer_create_nv12: the delay line and every frame in and out are H W 3 / 2 bytes, and the tracker (uint8) is
-    // pushed the frame's own first H W bytes, its Y plane: no luma launch and no luma plane
-    bool nv12 = false;
-    int siting = 0;
+    // The delay line and every frame in and out are the layout's.  Planar: the tracker is pushed the frame.  Packed: the
+    // tracker (uint8) is pushed the luma of the frame, formed in `luma` by the push.  NV12: the tracker (uint8) is pushed the
+    // frame's own first H W bytes, its Y plane: no luma launch and no luma plane
+    FrameLayout layout = FrameLayout::planar(false);
+    unsigned char *luma = nullptr;    // [H][W], packed only
 
-    size_t plane_bytes() const
-    {
-        const size_t px = (size_t)tr->H * tr->W;
-        return nv12 ? px + px / 2 : px * (channels ? (size_t)channels : tr->pix_bytes());
-    }
+    size_t plane_bytes() const { return layout.frame_bytes(tr->H, tr->W); }
     char *slot(long long f) const { return delay + (size_t)(f % (r + 1)) * plane_bytes(); }
 };
 
@@ -5580,24 +5511,6 @@ int trajectory_ring_launch(const float *d_model, const int *d_counts, int cap, i
     return OFLK_OK;
 }
 
-int stabilizer_warp(const oflk_stabilizer *st, const void *d_frames, int F, const double *d_map, void *d_out, unsigned char *d_inside,
-                    hipStream_t s)
-{
-    const oflk_tracker *tr = st->tr;
-    if (st->nv12)
-        return warp_nv12_launch<false>((const unsigned char *)d_frames, F, tr->H, tr->W, st->siting, d_map, (unsigned char *)d_out,
-                                       d_inside, s);
-    if (st->channels)
-        return warp_packed_launch<false>((const unsigned char *)d_frames, F, tr->H, tr->W, st->channels, d_map, (unsigned char *)d_out,
-                                         d_inside, s);
-    int rc = OFLK_OK;
-    with_pix(tr->u8, [&](auto PIX) {
-        using P = typename decltype(PIX)::type;
-        rc = warp_affine_launch<P>((const P *)d_frames, F, tr->H, tr->W, d_map, (P *)d_out, d_inside, s);
-    });
-    return rc;
-}
-
 // the device state, on the first push
 int stabilizer_ensure_state(oflk_stabilizer *st)
 {
@@ -5611,7 +5524,7 @@ int stabilizer_ensure_state(oflk_stabilizer *st)
         (rc = dmalloc(&st->ring_model, 6 * (size_t)st->cap, &st->ws_bytes)) ||
         (rc = dmalloc(&st->ring_counts, 3 * (size_t)st->cap, &st->ws_bytes)) || (rc = dmalloc(&st->corr, 6 * rows, &st->ws_bytes)) ||
         (rc = dmalloc(&st->map, 6 * rows, &st->ws_bytes)) ||
-        (st->channels && (rc = dmalloc(&st->luma, (size_t)tr->H * tr->W, &st->ws_bytes))))
+        (st->layout.kind == FrameKind::Packed && (rc = dmalloc(&st->luma, (size_t)tr->H * tr->W, &st->ws_bytes))))
         return rc;
     st->own_model = tr->m_out;
     st->own_counts = tr->m_counts;
@@ -5648,15 +5561,19 @@ int stabilizer_enqueue(oflk_stabilizer *st, const void *src, hipMemcpyKind kind,
     const size_t k = t >= 1 ? (size_t)((t - 1) % st->cap) : 0;
     tr->m_out = t >= 1 ? st->ring_model + 6 * k : st->own_model;
     tr->m_counts = t >= 1 ? st->ring_counts + 3 * k : st->own_counts;
+    // what the tracker is pushed: the frame, the packed frame's luma, or the NV12 frame's leading Y plane
+    const FrameLayout &L = st->layout;
+    const void *grey = frame;
     int rc = OFLK_OK;
-    if (st->channels &&
-        (rc = luma_launch((const unsigned char *)frame, 1, tr->H, tr->W, st->channels, st->order, st->luma, s)))
-        return rc;
-    if ((rc = tracker_push(tr, st->channels ? (const void *)st->luma : (const void *)frame, hipMemcpyDeviceToDevice, s))) return rc;
+    if (L.kind == FrameKind::Packed) {
+        if ((rc = luma_launch((const unsigned char *)frame, 1, tr->H, tr->W, L.channels, L.order, st->luma, s))) return rc;
+        grey = st->luma;
+    }
+    if ((rc = tracker_push(tr, grey, hipMemcpyDeviceToDevice, s))) return rc;
     if (t >= st->r) {
         const long long e = t - st->r;
         if ((rc = trajectory_ring_launch(st->ring_model, st->ring_counts, st->cap, (int)e, 1, -1, st->wt, st->r, st->corr, st->map, s)) ||
-            (rc = stabilizer_warp(st, st->slot(e), 1, st->map, d_out, d_inside, s)))
+            (rc = warp_launch(L, false, st->slot(e), 1, tr->H, tr->W, st->map, d_out, d_inside, s)))
             return rc;
         st->rows = 1;
     }
@@ -5715,30 +5632,45 @@ OFLK_API int oflk_stabilize_trajectory_ring(const float *d_model_ring, const int
     return trajectory_ring_launch(d_model_ring, d_counts_ring, cap, f0, n, T, wt, radius, d_correction, d_map, (hipStream_t)stream);
 }
 
-OFLK_API int oflk_stabilizer_create(oflk_stabilizer **out, int device, int H, int W, int u8, int levels, int window_size, int iters,
-                                    float alpha, float beta, float max_residual, float quality_level, float min_distance,
-                                    int max_corners, int detect_every, int model, int hypotheses, float threshold, unsigned seed,
-                                    const double *weights, int radius)
+namespace {
+// the creation of every layout: the layout's own refusals, the shape, the byte count of a packed frame, then the tracker's
+int stabilizer_create(oflk_stabilizer **out, int device, int H, int W, const FrameLayout &L, int levels, int window_size, int iters,
+                      float alpha, float beta, float max_residual, float q, float md, int K, int detect_every, int model,
+                      int hypotheses, float threshold, unsigned seed, const double *weights, int radius)
 {
     if (!out) return fail(OFLK_ERR_INVALID, "stabiliser pointer is NULL");
     *out = nullptr;
+    int rc = check_layout(L, H, W);
+    if (rc) return rc;
     if (H < 2 || W < 2) return fail(OFLK_ERR_INVALID, "H and W must be >= 2 (got %d x %d)", H, W);
-    int rc = check_motion(model, hypotheses, threshold);
-    if (rc || (rc = check_stab_window(weights, radius))) return rc;
+    if (L.kind == FrameKind::Packed && L.frame_bytes(H, W) >= ((size_t)1 << 31))
+        return fail(OFLK_ERR_UNSUPPORTED, "packed frames of 2^31 bytes or more are not supported");
+    if ((rc = check_motion(model, hypotheses, threshold)) || (rc = check_stab_window(weights, radius))) return rc;
     oflk_tracker *tr = nullptr;
-    if ((rc = oflk_tracker_create(&tr, device, H, W, u8, levels, window_size, iters, alpha, beta, max_residual, quality_level,
-                                  min_distance, max_corners, detect_every)) ||
+    if ((rc = oflk_tracker_create(&tr, device, H, W, L.pix_bytes == 1, levels, window_size, iters, alpha, beta, max_residual, q, md, K,
+                                  detect_every)) ||
         (rc = oflk_tracker_set_motion(tr, model, hypotheses, threshold, seed))) {
         tracker_free(tr);
         return rc;
     }
     oflk_stabilizer *st = new oflk_stabilizer();
     st->tr = tr;
+    st->layout = L;
     st->r = radius;
     st->cap = std::max(2 * radius, 1);
     for (int i = 0; i <= radius; i++) st->wt.w[i] = weights[i];
     *out = st;
     return OFLK_OK;
+}
+}  // namespace
+
+OFLK_API int oflk_stabilizer_create(oflk_stabilizer **out, int device, int H, int W, int u8, int levels, int window_size, int iters,
+                                    float alpha, float beta, float max_residual, float quality_level, float min_distance,
+                                    int max_corners, int detect_every, int model, int hypotheses, float threshold, unsigned seed,
+                                    const double *weights, int radius)
+{
+    return stabilizer_create(out, device, H, W, FrameLayout::planar(u8 != 0), levels, window_size, iters, alpha, beta, max_residual,
+                             quality_level, min_distance, max_corners, detect_every, model, hypotheses, threshold, seed, weights, radius);
 }
 
 OFLK_API int oflk_stabilizer_create_packed(oflk_stabilizer **out, int device, int H, int W, int channels, int order, int levels,
@@ -5746,18 +5678,9 @@ OFLK_API int oflk_stabilizer_create_packed(oflk_stabilizer **out, int device, in
                                            float quality_level, float min_distance, int max_corners, int detect_every, int model,
                                            int hypotheses, float threshold, unsigned seed, const double *weights, int radius)
 {
-    if (!out) return fail(OFLK_ERR_INVALID, "stabiliser pointer is NULL");
-    *out = nullptr;
-    int rc = check_channels(channels);
-    if (rc || (rc = check_order(order))) return rc;
-    if (H >= 2 && W >= 2 && (size_t)H * (size_t)W * (size_t)channels >= ((size_t)1 << 31))
-        return fail(OFLK_ERR_UNSUPPORTED, "packed frames of 2^31 bytes or more are not supported");
-    if ((rc = oflk_stabilizer_create(out, device, H, W, 1, levels, window_size, iters, alpha, beta, max_residual, quality_level,
-                                     min_distance, max_corners, detect_every, model, hypotheses, threshold, seed, weights, radius)))
-        return rc;
-    (*out)->channels = channels;
-    (*out)->order = order;
-    return OFLK_OK;
+    return stabilizer_create(out, device, H, W, FrameLayout::packed(channels, order), levels, window_size, iters, alpha, beta,
+                             max_residual, quality_level, min_distance, max_corners, detect_every, model, hypotheses, threshold, seed,
+                             weights, radius);
 }
 
 OFLK_API int oflk_stabilizer_create_nv12(oflk_stabilizer **out, int device, int H, int W, int siting, int levels, int window_size,
@@ -5765,16 +5688,8 @@ OFLK_API int oflk_stabilizer_create_nv12(oflk_stabilizer **out, int device, int 
                                          float min_distance, int max_corners, int detect_every, int model, int hypotheses,
                                          float threshold, unsigned seed, const double *weights, int radius)
 {
-    if (!out) return fail(OFLK_ERR_INVALID, "stabiliser pointer is NULL");
-    *out = nullptr;
-    int rc = check_nv12_shape(H, W, siting);
-    if (rc) return rc;
-    if ((rc = oflk_stabilizer_create(out, device, H, W, 1, levels, window_size, iters, alpha, beta, max_residual, quality_level,
-                                     min_distance, max_corners, detect_every, model, hypotheses, threshold, seed, weights, radius)))
-        return rc;
-    (*out)->nv12 = true;
-    (*out)->siting = siting;
-    return OFLK_OK;
+    return stabilizer_create(out, device, H, W, FrameLayout::nv12(siting), levels, window_size, iters, alpha, beta, max_residual,
+                             quality_level, min_distance, max_corners, detect_every, model, hypotheses, threshold, seed, weights, radius);
 }
 
 OFLK_API int oflk_stabilizer_destroy(oflk_stabilizer *st)
@@ -5856,10 +5771,12 @@ OFLK_API int oflk_stabilizer_flush_device(oflk_stabilizer *st, void *d_out, unsi
     if (rc || *count == 0) return rc;
     // frames first .. first + n - 1 lie in consecutive delay slots that wrap at most once: two launches at the most
     const int n = *count, slots = st->r + 1, s0 = *first % slots, n0 = std::min(n, slots - s0);
-    const size_t pb = st->plane_bytes(), plane = (size_t)st->tr->H * st->tr->W;
-    if ((rc = stabilizer_warp(st, st->delay + (size_t)s0 * pb, n0, st->map, d_out, d_inside, s)) ||
-        (n > n0 && (rc = stabilizer_warp(st, st->delay, n - n0, st->map + 6 * (size_t)n0, static_cast<char *>(d_out) + (size_t)n0 * pb,
-                                         d_inside ? d_inside + (size_t)n0 * plane : nullptr, s)))) {
+    const int H = st->tr->H, W = st->tr->W;
+    const size_t pb = st->plane_bytes(), plane = st->layout.inside_bytes(H, W);
+    if ((rc = warp_launch(st->layout, false, st->delay + (size_t)s0 * pb, n0, H, W, st->map, d_out, d_inside, s)) ||
+        (n > n0 && (rc = warp_launch(st->layout, false, st->delay, n - n0, H, W, st->map + 6 * (size_t)n0,
+                                     static_cast<char *>(d_out) + (size_t)n0 * pb, d_inside ? d_inside + (size_t)n0 * plane : nullptr,
+                                     s)))) {
         st->failed = true;
         *count = 0;
     }
@@ -5879,8 +5796,8 @@ OFLK_API int oflk_stabilizer_flush(oflk_stabilizer *st, void *out, unsigned char
     // frame by frame through the one staged frame; the null stream orders a frame's copies ahead of the next warp
     const size_t pb = st->plane_bytes(), plane = (size_t)st->tr->H * st->tr->W;
     for (int i = 0; i < n; i++) {
-        if ((rc = stabilizer_warp(st, st->slot((long long)*first + i), 1, st->map + 6 * (size_t)i, st->stage_out,
-                                  inside ? st->stage_inside : nullptr, nullptr))) {
+        if ((rc = warp_launch(st->layout, false, st->slot((long long)*first + i), 1, st->tr->H, st->tr->W, st->map + 6 * (size_t)i,
+                              st->stage_out, inside ? st->stage_inside : nullptr, nullptr))) {
             st->failed = true;
             (void)hipStreamSynchronize(nullptr);
             return rc;

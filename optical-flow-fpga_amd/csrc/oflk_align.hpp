@@ -176,7 +176,8 @@ __global__ __launch_bounds__(64) void k_align_reduce(AlignReduceArgs a)
             iy = fmaf(a0[2], 0.0f, iy);
             iy = fmaf(a0[1], 0.0f, iy);
             iy = fmaf(a0[0], 0.0f, iy);
-            // the source position: warp_frames' expressions
+            // the source position: the expressions of warp_row and warp_source (oflk_stabilize.hpp), repeated here with the row
+            // products formed per pixel; the kernel is kept off the helper so that its generated code stays what was measured
             const double fy = (double)y;
             [[maybe_unused]] const double w = (m6 * fx + m7 * fy) + m8;
             const double xa = (m0 * fx + m1 * fy) + m2;

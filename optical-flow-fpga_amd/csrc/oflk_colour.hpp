@@ -7,9 +7,9 @@
 //   k_luma<C, VEC>      Y = (77 R + 150 G + 29 B + 128) >> 8 in integers, a streaming kernel over the F H W pixels.  VEC: a lane
 //                       owns 4 consecutive pixels, reads their 4 C bytes as three dwords (C = 3) or one dwordx4 (C = 4) and
 //                       stores one dword of luma; every other shape and alignment runs the element-wise instantiation
-//   k_warp_packed<C, PERSP, VEC>  warp_frames' grid, lane shape, map arithmetic and closed-interval test
-//                       (oflk_stabilize.hpp), formed once per pixel; the four taps are gathered as one dword each, which
-//                       holds all C channels of the tap, and bilinear_finish runs C times on the one set of weights, so
+//   k_warp_packed<C, PERSP, VEC>  warp_frames' grid and lane shape, and its source position and closed-interval test through
+//                       the same warp_row / warp_source (oflk_stabilize.hpp), once per pixel; the four taps are gathered
+//                       as one dword each, which holds all C channels of the tap, and bilinear_finish runs C times on the one set of weights, so
 //                       every channel's byte is the planar kernel's.  VEC stores a lane's 4 pixels as three dwords (C = 3) or
 //                       one dwordx4 (C = 4) and the inside dword; the other instantiation stores byte by byte.  The two
 //                       are two kernels for k_warp_affine's reason.
@@ -112,28 +112,15 @@ __global__ __launch_bounds__(256) void k_warp_packed(const WarpPackedArgs a)
     const double fy = (double)y, Wm1 = (double)(a.W - 1), Hm1 = (double)(a.H - 1);
     for (int f = blockIdx.z; f < a.F; f += gridDim.z) {
         const double *__restrict__ m = a.map + NC * (size_t)f;
-        const double m0 = m[0], m2 = m[2], m3 = m[3], m5 = m[5];
-        const double bx = m[1] * fy, by = m[4] * fy;
-        [[maybe_unused]] double m6 = 0.0, m8 = 1.0, bw = 0.0;
-        if constexpr (PERSP) {
-            m6 = m[6];
-            m8 = m[8];
-            bw = m[7] * fy;
-        }
+        const WarpRow<PERSP> r = warp_row<PERSP>(m, fy);
         const unsigned char *__restrict__ img = a.in + (size_t)f * plane * C;
         unsigned v[kWarpPx];            // a pixel's C bytes, channel c at bits 8 c
         unsigned char in[kWarpPx];
 #pragma unroll
         for (int k = 0; k < kWarpPx; k++) {   // a pixel past the row's end is computed (its taps are clamped) and not stored
             const double fx = (double)(x0 + k);
-            [[maybe_unused]] const double w = (m6 * fx + bw) + m8;
-            const double xa = (m0 * fx + bx) + m2;
-            const double ya = (m3 * fx + by) + m5;
-            const double xs = PERSP ? xa / w : xa;
-            const double ys = PERSP ? ya / w : ya;
-            const bool within = xs >= 0.0 && xs <= Wm1 && ys >= 0.0 && ys <= Hm1;
-            const bool ok = PERSP ? w > 0.0 && within : within;
-            const BilinearTaps t = bilinear_taps(a.H, a.W, ys, xs);
+            const WarpSource p = warp_source(r, fx, Wm1, Hm1);
+            const BilinearTaps t = bilinear_taps(a.H, a.W, p.ys, p.xs);
             const unsigned p00 = ld_tap<C>(img, (unsigned)t.i00, last), p01 = ld_tap<C>(img, (unsigned)t.i01, last);
             const unsigned p10 = ld_tap<C>(img, (unsigned)t.i10, last), p11 = ld_tap<C>(img, (unsigned)t.i11, last);
             unsigned px = 0;
@@ -141,10 +128,10 @@ __global__ __launch_bounds__(256) void k_warp_packed(const WarpPackedArgs a)
             for (int c = 0; c < C; c++) {
                 const float s = bilinear_finish(t, (float)((p00 >> (8 * c)) & 0xffu), (float)((p01 >> (8 * c)) & 0xffu),
                                                 (float)((p10 >> (8 * c)) & 0xffu), (float)((p11 >> (8 * c)) & 0xffu));
-                px |= (unsigned)warp_store_value(ok ? s : 0.0f, (unsigned char)0) << (8 * c);
+                px |= (unsigned)warp_store_value(p.ok ? s : 0.0f, (unsigned char)0) << (8 * c);
             }
             v[k] = px;
-            in[k] = ok ? 1 : 0;
+            in[k] = p.ok ? 1 : 0;
         }
         unsigned char *__restrict__ dst = a.out + ((size_t)f * plane + row) * C;
         if constexpr (VEC) {
@@ -167,7 +154,7 @@ __global__ __launch_bounds__(256) void k_warp_packed(const WarpPackedArgs a)
         if (a.inside) {
             unsigned char *__restrict__ di = a.inside + (size_t)f * plane + row;
             if constexpr (VEC) {
-                *reinterpret_cast<unsigned *>(di) = (unsigned)in[0] | ((unsigned)in[1] << 8) | ((unsigned)in[2] << 16) | ((unsigned)in[3] << 24);
+                *reinterpret_cast<unsigned *>(di) = warp_pack(in);
             } else {
 #pragma unroll
                 for (int k = 0; k < kWarpPx; k++)

@@ -239,6 +239,8 @@ __global__ __launch_bounds__(256) void k_mosaic_accumulate(MosaicArgs<PIX> a)
         while (todo) {
             const int f = f0 + (int)__builtin_ctzll(todo);
             todo &= todo - 1;
+            // the source position: the expressions of warp_row<true> and warp_source<true> (oflk_stabilize.hpp), repeated here:
+            // through the helper two instantiations of this kernel went from 100 / 102 to 114 VGPRs
             const double *__restrict__ m = a.map + 9 * (size_t)f;
             const double m0 = m[0], m2 = m[2], m3 = m[3], m5 = m[5], m6 = m[6], m8 = m[8];
             const double bx1 = m[1] * fy, by1 = m[4] * fy, bw = m[7] * fy;

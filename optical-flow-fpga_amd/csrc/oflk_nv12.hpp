@@ -61,6 +61,8 @@ __device__ __forceinline__ void nv12_chroma_map(const double *__restrict__ m, do
 }
 
 // ---- luma: warp_frames<unsigned char, VEC, PERSP> on the Y planes, which lie H W 3 / 2 bytes apart ----
+// The body repeats warp_frames' around the shared warp_row / warp_source / warp_pack instead of calling a strided warp_frames:
+// through one, the compiler turned the taps' clamps from branches into v_min_f64 / v_max_f64.
 template <bool PERSP, bool VEC>
 __device__ __forceinline__ void nv12_luma(const WarpNv12Args &a)
 {
@@ -73,35 +75,22 @@ __device__ __forceinline__ void nv12_luma(const WarpNv12Args &a)
     const double fy = (double)y, Wm1 = (double)(a.W - 1), Hm1 = (double)(a.H - 1);
     for (int f = blockIdx.z; f < a.F; f += gridDim.z) {
         const double *__restrict__ m = a.map + NC * (size_t)f;
-        const double m0 = m[0], m2 = m[2], m3 = m[3], m5 = m[5];
-        const double bx = m[1] * fy, by = m[4] * fy;
-        [[maybe_unused]] double m6 = 0.0, m8 = 1.0, bw = 0.0;
-        if constexpr (PERSP) {
-            m6 = m[6];
-            m8 = m[8];
-            bw = m[7] * fy;
-        }
+        const WarpRow<PERSP> r = warp_row<PERSP>(m, fy);
         const unsigned char *__restrict__ img = a.in + (size_t)f * fb;
         unsigned char v[kWarpPx], in[kWarpPx];
 #pragma unroll
         for (int k = 0; k < kWarpPx; k++) {   // a pixel past the row's end is computed (its taps are clamped) and not stored
             const double fx = (double)(x0 + k);
-            [[maybe_unused]] const double w = (m6 * fx + bw) + m8;
-            const double xa = (m0 * fx + bx) + m2;
-            const double ya = (m3 * fx + by) + m5;
-            const double xs = PERSP ? xa / w : xa;
-            const double ys = PERSP ? ya / w : ya;
-            const bool within = xs >= 0.0 && xs <= Wm1 && ys >= 0.0 && ys <= Hm1;
-            const bool ok = PERSP ? w > 0.0 && within : within;
-            const BilinearTaps t = bilinear_taps(a.H, a.W, ys, xs);
+            const WarpSource p = warp_source(r, fx, Wm1, Hm1);
+            const BilinearTaps t = bilinear_taps(a.H, a.W, p.ys, p.xs);
             const float s = bilinear_finish(t, ld_pix<unsigned char>(img, (unsigned)t.i00), ld_pix<unsigned char>(img, (unsigned)t.i01),
                                             ld_pix<unsigned char>(img, (unsigned)t.i10), ld_pix<unsigned char>(img, (unsigned)t.i11));
-            v[k] = warp_store_value(ok ? s : 0.0f, (unsigned char)0);
-            in[k] = ok ? 1 : 0;
+            v[k] = warp_store_value(p.ok ? s : 0.0f, (unsigned char)0);
+            in[k] = p.ok ? 1 : 0;
         }
         unsigned char *__restrict__ dst = a.out + (size_t)f * fb + row;
         if constexpr (VEC) {
-            *reinterpret_cast<unsigned *>(dst) = (unsigned)v[0] | ((unsigned)v[1] << 8) | ((unsigned)v[2] << 16) | ((unsigned)v[3] << 24);
+            *reinterpret_cast<unsigned *>(dst) = warp_pack(v);
         } else {
 #pragma unroll
             for (int k = 0; k < kWarpPx; k++)
@@ -110,7 +99,7 @@ __device__ __forceinline__ void nv12_luma(const WarpNv12Args &a)
         if (a.inside) {
             unsigned char *__restrict__ di = a.inside + (size_t)f * plane + row;
             if constexpr (VEC) {
-                *reinterpret_cast<unsigned *>(di) = (unsigned)in[0] | ((unsigned)in[1] << 8) | ((unsigned)in[2] << 16) | ((unsigned)in[3] << 24);
+                *reinterpret_cast<unsigned *>(di) = warp_pack(in);
             } else {
 #pragma unroll
                 for (int k = 0; k < kWarpPx; k++)
@@ -136,22 +125,14 @@ __device__ __forceinline__ void nv12_chroma(const WarpNv12Args &a)
     for (int f = blockIdx.z; f < a.F; f += gridDim.z) {
         double mc[9];
         nv12_chroma_map<PERSP>(a.map + NC * (size_t)f, a.sx, a.sy, mc);
-        const double m0 = mc[0], m2 = mc[2], m3 = mc[3], m5 = mc[5];
-        const double bx = mc[1] * fy, by = mc[4] * fy;
-        [[maybe_unused]] const double m6 = mc[6], m8 = mc[8], bw = mc[7] * fy;
+        const WarpRow<PERSP> r = warp_row<PERSP>(mc, fy);
         const unsigned char *__restrict__ uv = a.in + (size_t)f * fb + plane;
         unsigned v[kWarpPx];   // U in bits 0-7, V in bits 8-15
 #pragma unroll
         for (int k = 0; k < kWarpPx; k++) {   // a pair past the row's end is computed (its taps are clamped) and not stored
             const double fx = (double)(x0 + k);
-            [[maybe_unused]] const double w = (m6 * fx + bw) + m8;
-            const double xa = (m0 * fx + bx) + m2;
-            const double ya = (m3 * fx + by) + m5;
-            const double xs = PERSP ? xa / w : xa;
-            const double ys = PERSP ? ya / w : ya;
-            const bool within = xs >= 0.0 && xs <= Wm1 && ys >= 0.0 && ys <= Hm1;
-            const bool ok = PERSP ? w > 0.0 && within : within;
-            const BilinearTaps t = bilinear_taps(CH, CW, ys, xs);
+            const WarpSource p = warp_source(r, fx, Wm1, Hm1);
+            const BilinearTaps t = bilinear_taps(CH, CW, p.ys, p.xs);
             const unsigned p00 = reinterpret_cast<const TapPair *>(uv + 2u * (unsigned)t.i00)->v;
             const unsigned p01 = reinterpret_cast<const TapPair *>(uv + 2u * (unsigned)t.i01)->v;
             const unsigned p10 = reinterpret_cast<const TapPair *>(uv + 2u * (unsigned)t.i10)->v;
@@ -159,7 +140,7 @@ __device__ __forceinline__ void nv12_chroma(const WarpNv12Args &a)
             const float su = bilinear_finish(t, (float)(p00 & 0xffu), (float)(p01 & 0xffu), (float)(p10 & 0xffu), (float)(p11 & 0xffu));
             const float sv = bilinear_finish(t, (float)(p00 >> 8), (float)(p01 >> 8), (float)(p10 >> 8), (float)(p11 >> 8));
             // outside: U = V = 128, no colour
-            const unsigned bu = warp_store_value(ok ? su : 128.0f, (unsigned char)0), bv = warp_store_value(ok ? sv : 128.0f, (unsigned char)0);
+            const unsigned bu = warp_store_value(p.ok ? su : 128.0f, (unsigned char)0), bv = warp_store_value(p.ok ? sv : 128.0f, (unsigned char)0);
             v[k] = bu | (bv << 8);
         }
         unsigned char *__restrict__ dst = a.out + (size_t)f * fb + row;

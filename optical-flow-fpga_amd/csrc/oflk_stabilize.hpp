@@ -223,10 +223,58 @@ struct WarpAffineArgs {
 __device__ __forceinline__ float warp_store_value(float v, float) { return v; }
 __device__ __forceinline__ unsigned char warp_store_value(float v, unsigned char) { return (unsigned char)rintf(v); }
 
+// ---- the source position of an output pixel: the one statement of it for every frame layout (warp_frames here,
+// k_warp_packed in oflk_colour.hpp, nv12_luma and nv12_chroma in oflk_nv12.hpp) ----
+// What a map m and a row y fix.  PERSP: the map has a third row and the source position is divided by
+// w = (m6 x + m7 y) + m8, two IEEE divisions per pixel (tests/homography_model.py); w <= 0 or a NaN anywhere is outside.
+template <bool PERSP>
+struct WarpRow {
+    double m0, m2, m3, m5, bx, by;
+    double m6, m8, bw;   // read under PERSP only
+};
+
+template <bool PERSP>
+__device__ __forceinline__ WarpRow<PERSP> warp_row(const double *__restrict__ m, double fy)
+{
+    WarpRow<PERSP> r;
+    r.m0 = m[0]; r.m2 = m[2]; r.m3 = m[3]; r.m5 = m[5];
+    r.bx = m[1] * fy; r.by = m[4] * fy;
+    r.m6 = 0.0; r.m8 = 1.0; r.bw = 0.0;
+    if constexpr (PERSP) {
+        r.m6 = m[6];
+        r.m8 = m[8];
+        r.bw = m[7] * fy;
+    }
+    return r;
+}
+
+// A pixel's own: the source position of column fx and whether it lies in the closed interval [0, Wm1] x [0, Hm1]
+struct WarpSource {
+    double xs, ys;
+    bool ok;
+};
+
+template <bool PERSP>
+__device__ __forceinline__ WarpSource warp_source(const WarpRow<PERSP> &r, double fx, double Wm1, double Hm1)
+{
+    [[maybe_unused]] const double w = (r.m6 * fx + r.bw) + r.m8;
+    const double xa = (r.m0 * fx + r.bx) + r.m2;
+    const double ya = (r.m3 * fx + r.by) + r.m5;
+    const double xs = PERSP ? xa / w : xa;
+    const double ys = PERSP ? ya / w : ya;
+    const bool within = xs >= 0.0 && xs <= Wm1 && ys >= 0.0 && ys <= Hm1;
+    return {xs, ys, PERSP ? w > 0.0 && within : within};
+}
+
+// a lane's kWarpPx bytes (pixels of a uint8 plane, or `inside`) as the one dword it stores, byte 0 at the lowest address
+__device__ __forceinline__ unsigned warp_pack(const unsigned char (&b)[4])
+{
+    return (unsigned)b[0] | ((unsigned)b[1] << 8) | ((unsigned)b[2] << 16) | ((unsigned)b[3] << 24);
+}
+
 // VEC: W % kWarpPx == 0 and out (and inside, when given) aligned to a lane's store, so every lane owns kWarpPx whole pixels
 // and stores them at once.  The two forms are two kernels: in one, the compiler folds the wide store into the tail's.
-// PERSP: the map has a third row and the source position is divided by w = (m6 x + m7 y) + m8, two IEEE divisions per pixel
-// (tests/homography_model.py); w <= 0 or a NaN anywhere is outside.
+// PERSP: warp_row's.
 template <class PIX, bool VEC, bool PERSP>
 __device__ __forceinline__ void warp_frames(const WarpAffineArgs<PIX> a)
 {
@@ -239,39 +287,26 @@ __device__ __forceinline__ void warp_frames(const WarpAffineArgs<PIX> a)
     const double fy = (double)y, Wm1 = (double)(a.W - 1), Hm1 = (double)(a.H - 1);
     for (int f = blockIdx.z; f < a.F; f += gridDim.z) {
         const double *__restrict__ m = a.map + NC * (size_t)f;
-        const double m0 = m[0], m2 = m[2], m3 = m[3], m5 = m[5];
-        const double bx = m[1] * fy, by = m[4] * fy;
-        [[maybe_unused]] double m6 = 0.0, m8 = 1.0, bw = 0.0;
-        if constexpr (PERSP) {
-            m6 = m[6];
-            m8 = m[8];
-            bw = m[7] * fy;
-        }
+        const WarpRow<PERSP> r = warp_row<PERSP>(m, fy);
         const PIX *__restrict__ img = a.in + (size_t)f * plane;
         PIX v[kWarpPx];
         unsigned char in[kWarpPx];
 #pragma unroll
         for (int k = 0; k < kWarpPx; k++) {   // a pixel past the row's end is computed (its taps are clamped) and not stored
             const double fx = (double)(x0 + k);
-            [[maybe_unused]] const double w = (m6 * fx + bw) + m8;
-            const double xa = (m0 * fx + bx) + m2;
-            const double ya = (m3 * fx + by) + m5;
-            const double xs = PERSP ? xa / w : xa;
-            const double ys = PERSP ? ya / w : ya;
-            const bool within = xs >= 0.0 && xs <= Wm1 && ys >= 0.0 && ys <= Hm1;
-            const bool ok = PERSP ? w > 0.0 && within : within;
-            const BilinearTaps t = bilinear_taps(a.H, a.W, ys, xs);
+            const WarpSource p = warp_source(r, fx, Wm1, Hm1);
+            const BilinearTaps t = bilinear_taps(a.H, a.W, p.ys, p.xs);
             const float s = bilinear_finish(t, ld_pix<PIX>(img, (unsigned)t.i00), ld_pix<PIX>(img, (unsigned)t.i01),
                                             ld_pix<PIX>(img, (unsigned)t.i10), ld_pix<PIX>(img, (unsigned)t.i11));
-            v[k] = warp_store_value(ok ? s : 0.0f, PIX());
-            in[k] = ok ? 1 : 0;
+            v[k] = warp_store_value(p.ok ? s : 0.0f, PIX());
+            in[k] = p.ok ? 1 : 0;
         }
         PIX *__restrict__ dst = a.out + (size_t)f * plane + row;
         if constexpr (VEC) {
             if constexpr (sizeof(PIX) == 4) {
                 *reinterpret_cast<float4 *>(dst) = make_float4(v[0], v[1], v[2], v[3]);
             } else {
-                *reinterpret_cast<unsigned *>(dst) = (unsigned)v[0] | ((unsigned)v[1] << 8) | ((unsigned)v[2] << 16) | ((unsigned)v[3] << 24);
+                *reinterpret_cast<unsigned *>(dst) = warp_pack(v);
             }
         } else {
 #pragma unroll
@@ -281,7 +316,7 @@ __device__ __forceinline__ void warp_frames(const WarpAffineArgs<PIX> a)
         if (a.inside) {
             unsigned char *__restrict__ di = a.inside + (size_t)f * plane + row;
             if constexpr (VEC) {
-                *reinterpret_cast<unsigned *>(di) = (unsigned)in[0] | ((unsigned)in[1] << 8) | ((unsigned)in[2] << 16) | ((unsigned)in[3] << 24);
+                *reinterpret_cast<unsigned *>(di) = warp_pack(in);
             } else {
 #pragma unroll
                 for (int k = 0; k < kWarpPx; k++)

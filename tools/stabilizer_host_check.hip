@@ -91,7 +91,7 @@ int main()
         for (int order : {OFLK_ORDER_RGB, OFLK_ORDER_BGR}) {
             EXPECT(create_packed(&st, 24, 32, channels, order, 3) == OFLK_OK && st);
             if (!st) continue;
-            EXPECT(st->channels == channels && st->order == order && st->tr->u8);
+            EXPECT(st->layout.kind == FrameKind::Packed && st->layout.channels == channels && st->layout.order == order && st->tr->u8);
             EXPECT(st->plane_bytes() == (size_t)24 * 32 * channels);
             EXPECT(oflk_stabilizer_lag(st) == 3 && oflk_stabilizer_frame_index(st) == -1 && oflk_stabilizer_workspace_bytes(st) == 0);
             int e = 5, first = 5, count = 5;
@@ -142,7 +142,7 @@ int main()
     for (int siting : {OFLK_SITING_LEFT, OFLK_SITING_CENTER}) {
         EXPECT(create_nv12(&st, 24, 32, siting, 3) == OFLK_OK && st);
         if (!st) continue;
-        EXPECT(st->nv12 && st->siting == siting && st->channels == 0 && st->tr->u8);
+        EXPECT(st->layout.kind == FrameKind::Nv12 && st->layout.siting == siting && st->layout.channels == 0 && st->tr->u8);
         EXPECT(st->plane_bytes() == (size_t)24 * 32 * 3 / 2 && st->plane_bytes() == oflk_nv12_frame_bytes(24, 32));
         EXPECT(oflk_stabilizer_lag(st) == 3 && oflk_stabilizer_frame_index(st) == -1 && oflk_stabilizer_workspace_bytes(st) == 0);
         int e = 5, first = 5, count = 5;

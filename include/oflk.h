@@ -114,9 +114,13 @@ int oflk_upsample_flow(const float *flow_u, const float *flow_v, int Hc, int Wc,
  * oflk_upsample_staged: 1 when oflk_upsample_flow (and the flow upsampling of a pyramidal pass) of Hc x Wc to Ht x Wt runs
  * k_upsample, 0 when it runs k_resample.
  * oflk_pyramid_step_fused: 1 when the pyramid step from h x w to ho x wo with a Gaussian of this radius runs k_pyr_down, 0
- * when it runs the unfused chain (always 0 for a radius other than 8). */
+ * when it runs the unfused chain (always 0 for a radius other than 8).
+ * oflk_pyramid_step_form: which of the three paths that step takes.  2: k_pyr_down's tight tile (every 32 x 16 output tile
+ * samples at most 32 x 64 blurred values: the half-scale ratio, every level of an even-sized frame), 1: its general tile
+ * (at most 34 x 66: odd sizes, tiny levels), 0: the unfused chain.  Nonzero exactly when oflk_pyramid_step_fused is 1. */
 int oflk_upsample_staged(int Hc, int Wc, int Ht, int Wt);
 int oflk_pyramid_step_fused(int h, int w, int ho, int wo, int radius);
+int oflk_pyramid_step_form(int h, int w, int ho, int wo, int radius);
 
 /* lucas_kanade_pyramidal(frame_prev, frame_curr, num_levels, window_size, num_iterations) -> (u, v)
  * replaces python/lucas_kanade_pyramidal.py:141-228.

@@ -567,11 +567,18 @@ bool span_ok(int S, int T, int tile, int cap)
     return true;
 }
 
-// does every 32 x 16 coarse tile's source span fit the fused kernel's LDS tile?
-bool pyr_fused_fits(int h, int w, int ho, int wo, const GaussW &g)
+// Which path a pyramid step takes.  Tight: every 32 x 16 coarse tile samples at most 32 x 64 blurred values (the half-scale
+// ratio).  General: at most 34 x 66.  Otherwise the unfused chain.
+enum { PYR_UNFUSED = 0, PYR_GENERAL = 1, PYR_TIGHT = 2 };
+int pyr_form(int h, int w, int ho, int wo, const GaussW &g)
 {
-    return g.radius == 8 && span_ok(h, ho, kPTH, kPBH) && span_ok(w, wo, kPTW, kPBW);
+    if (g.radius != 8) return PYR_UNFUSED;
+    if (span_ok(h, ho, kPTH, kPBHT) && span_ok(w, wo, kPTW, kPBWT)) return PYR_TIGHT;
+    return span_ok(h, ho, kPTH, kPBH) && span_ok(w, wo, kPTW, kPBW) ? PYR_GENERAL : PYR_UNFUSED;
 }
+
+// does every 32 x 16 coarse tile's source span fit one of the fused kernel's LDS tiles?
+bool pyr_fused_fits(int h, int w, int ho, int wo, const GaussW &g) { return pyr_form(h, w, ho, wo, g) != PYR_UNFUSED; }
 
 // does every 256 x 4 output block of k_upsample find its coarse source span inside the staged LDS tile?
 bool upsample_fits(int hc, int wc, int ht, int wt) { return span_ok(hc, ht, kUTH, kUSH) && span_ok(wc, wt, kUTW, kUSW); }
@@ -648,7 +655,7 @@ int launch_pyr_down(oflk_plan *plan, const GaussW &gauss, hipStream_t s, const f
                     float *tmpA, float *tmpB, int nimg, int h, int w, int ho, int wo,
                     const PyrExtra *extra = nullptr)
 {
-    if (pyr_fused_fits(h, w, ho, wo, gauss)) {
+    if (const int form = pyr_form(h, w, ho, wo, gauss); form != PYR_UNFUSED) {
         PyrArgs a{};
         a.in = in;
         a.in2 = in;
@@ -677,7 +684,10 @@ int launch_pyr_down(oflk_plan *plan, const GaussW &gauss, hipStream_t s, const f
         const int arith = contracted_pyramid(plan) ? PYR_CONTRACTED : kExactForm;
         with_pix(extra && extra->u8, [&](auto PIX) {
             with_int<PYR_CONTRACTED, kExactForm>(arith, [&](auto ARITH) {
-                hipLaunchKernelGGL((k_pyr_down<typename decltype(PIX)::type, decltype(ARITH)::value>), grid, dim3(256), 0, s, a);
+                with_bool(form == PYR_TIGHT, [&](auto TIGHT) {
+                    hipLaunchKernelGGL((k_pyr_down<typename decltype(PIX)::type, decltype(ARITH)::value, decltype(TIGHT)::value>), grid,
+                                       dim3(256), 0, s, a);
+                });
             });
         });
         HIP_TRY(hipGetLastError());
@@ -1578,6 +1588,14 @@ OFLK_API int oflk_pyramid_step_fused(int h, int w, int ho, int wo, int radius)
     GaussW g{};
     g.radius = radius;   // the only field of the weights that the decision reads
     return pyr_fused_fits(h, w, ho, wo, g) ? 1 : 0;
+}
+
+OFLK_API int oflk_pyramid_step_form(int h, int w, int ho, int wo, int radius)
+{
+    if (h < 1 || w < 1 || ho < 1 || wo < 1) return 0;
+    GaussW g{};
+    g.radius = radius;
+    return pyr_form(h, w, ho, wo, g);
 }
 
 OFLK_API double oflk_device_mean_error(int path, int level_h, int level_w, double mean)

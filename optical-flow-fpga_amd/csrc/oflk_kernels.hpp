@@ -1858,15 +1858,30 @@ __global__ __launch_bounds__(256) void k_resample(ResampleArgs a)
 // the blurred image never goes to HBM (algorithmic traffic: read 4 B per fine
 // pixel, write 4 B per coarse pixel).
 // The host checks that a tile's source span fits the static LDS tile
-// (pyr_fused_fits) and otherwise uses the unfused chain.
+// (pyr_form) and otherwise uses the unfused chain.
+// Two tile geometries (PyrGeom), chosen by the host per step:
+//   general  blurred span 34 x 66: what a tile of any ratio near 2 may sample (odd sizes, tiny levels)
+//   tight    blurred span 32 x 64: what a tile samples at the half-scale ratio (T = S / 2: floor(i * step) = 2 i for every
+//            i < T - 1, and the last point is capped), i.e. every level of an even-sized frame.  Nothing is blurred that
+//            no sample reads, and passes A, B and C fill their lanes: 48 x 80 = 15 x 256 staged cells, 80 columns x 3
+//            segments of 11 rows, 32 rows x 8 segments of 8 columns.
 // ---------------------------------------------------------------------------
 constexpr int kPTW = 32, kPTH = 16;          // coarse outputs per block
-constexpr int kPBW = 2 * kPTW + 2;           // blurred cols a tile may need (66)
-constexpr int kPBH = 2 * kPTH + 2;           // blurred rows (34)
-constexpr int kPIW = kPBW + 16;              // input cols incl. radius-8 halo (82)
-constexpr int kPIH = kPBH + 16;              // input rows (50)
-constexpr int kPVS = kPIW + 1;               // row stride of the vertical-pass tile (odd)
-constexpr int kPHS = kPBW + 1;               // row stride of the blurred tile
+constexpr int kPBW = 2 * kPTW + 2;           // blurred cols a tile may need (66); the tight form holds 64
+constexpr int kPBH = 2 * kPTH + 2;           // blurred rows (34); tight 32
+constexpr int kPBWT = 2 * kPTW, kPBHT = 2 * kPTH;
+
+template <bool TIGHT>
+struct PyrGeom {
+    static constexpr int BW = TIGHT ? kPBWT : kPBW;   // blurred cols (64 | 66)
+    static constexpr int BH = TIGHT ? kPBHT : kPBH;   // blurred rows (32 | 34)
+    static constexpr int IW = BW + 16;                // input cols incl. radius-8 halo (80 | 82)
+    static constexpr int IH = BH + 16;                // input rows (48 | 50)
+    static constexpr int VS = IW + 1;                 // row stride of the vertical-pass tile (odd)
+    static constexpr int HS = BW + 1;                 // row stride of the blurred tile (odd)
+    static constexpr int RS = TIGHT ? 11 : 12;        // pass B: rows per thread (3 segments cover BH)
+    static constexpr int CS = TIGHT ? 8 : 10;         // pass C: cols per thread (8 | 7 segments cover BW)
+};
 
 struct PyrArgs {
     const float *in;   // [nimg][H][W]; images nsplit .. come from in2 instead (two caller buffers, one launch)
@@ -1956,9 +1971,11 @@ __device__ __forceinline__ void pyr_cert_count(int slot)
 }
 #endif
 
-template <class PIX, int ARITH = PYR_EXACT>
+template <class PIX, int ARITH = PYR_EXACT, bool TIGHT = false>
 __global__ __launch_bounds__(256) void k_pyr_down(PyrArgs a)
 {
+    using G = PyrGeom<TIGHT>;
+    constexpr int kPBW = G::BW, kPBH = G::BH, kPIW = G::IW, kPIH = G::IH, kPVS = G::VS, kPHS = G::HS;   // this geometry's
     __shared__ __attribute__((aligned(16))) float s_in[kPIH * kPIW];   // stage A (8-byte column-pair writes); reused for the blurred tile (stage C output)
     __shared__ float s_v[kPBH * kPVS];
     float *s_h = s_in;
@@ -1996,7 +2013,7 @@ __global__ __launch_bounds__(256) void k_pyr_down(PyrArgs a)
     // addresses: every tile but the frame's border ring), it leaves the image by less than
     // one image size (one mirror step, no division), anything else (tiny images). ------
     {
-        constexpr int NA = (kPIH * kPIW + 255) / 256;  // 17 elements per thread
+        constexpr int NA = (kPIH * kPIW + 255) / 256;  // 17 elements per thread (tight: 15, no remainder)
         constexpr int QA = 256 / kPIW, RA = 256 % kPIW;
         constexpr int NLAST = kPIH * kPIW - (NA - 1) * 256;   // threads that own an element NA-1
         const int ybase = ylo - 8, xbase = xlo - 8;
@@ -2006,7 +2023,7 @@ __global__ __launch_bounds__(256) void k_pyr_down(PyrArgs a)
         if constexpr (sizeof(PIX) == 4 && OFLK_PYR_PAIRS) {
             if (ybase >= 0 && ybase + kPIH <= H && xbase >= 0 && xbase + kPIW <= W) {
                 // interior tile, float32 frames: column PAIRS, one 8-byte load and one 8-byte LDS write each (the tile is
-                // 82 = 2 x 41 columns wide; 2050 pairs = 8 per thread + 2)
+                // 82 = 2 x 41 columns wide; 2050 pairs = 8 per thread + 2.  Tight: 2 x 40, 1920 pairs = 7.5 per thread)
                 constexpr int PWD = kPIW / 2, NPR = kPIH * PWD, NB = (NPR + 255) / 256, QB = 256 / PWD, RB = 256 % PWD;
                 static_assert(kPIW % 2 == 0, "pairs");
                 float2 pv[NB];
@@ -2065,9 +2082,10 @@ __global__ __launch_bounds__(256) void k_pyr_down(PyrArgs a)
     }
     __syncthreads();
 
-    // ---- B: vertical pass; thread = one column, 12 consecutive rows ----------
+    // ---- B: vertical pass; thread = one column, 12 consecutive rows (tight: 11, 33 computed for 32) ----------
     {
-        constexpr int RS = 12;                       // rows per thread (3 segments cover 34)
+        constexpr int RS = G::RS;                    // rows per thread (3 segments cover 34 | 32)
+        static_assert(3 * RS >= kPBH && 3 * kPIW <= 256 && kPIH - 2 * RS > 0, "three segments of one thread per column");
         const int col = tid % kPIW, seg = tid / kPIW;
         if (seg < 3) {
             // the window's rows at a per-thread base plus constants; only the last segment's last rows lie past the
@@ -2114,20 +2132,23 @@ __global__ __launch_bounds__(256) void k_pyr_down(PyrArgs a)
     __syncthreads();
 
     // ---- C: horizontal pass; thread = one row, 10 consecutive columns (34 rows x 7 segments =
-    // 238 busy lanes; the last segment's surplus columns are computed but not stored) --------
+    // 238 busy lanes; the last segment's surplus columns are computed but not stored).  Tight: 8
+    // columns, 32 rows x 8 segments = all 256 lanes, every computed value stored.  A half-wave
+    // holds the 32 rows of one segment: its reads (stride 81) and writes (stride 65) fall on 32
+    // different banks --------
     {
-        constexpr int CS = 10;                       // cols per thread (7 segments cover 66)
+        constexpr int CS = G::CS;                    // cols per thread (7 segments cover 66 | 8 cover 64)
         constexpr int NSEG = (kPBW + CS - 1) / CS;
         static_assert(kPBH * NSEG <= 256, "one thread per (row, segment)");
         const int row = tid % kPBH, seg = tid / kPBH;
-        if (seg < NSEG) {
+        if (kPBH * NSEG == 256 || seg < NSEG) {
             constexpr int KSAFE = kPIW - (NSEG - 1) * CS;   // columns k < KSAFE exist for every segment
             const float *wb = &s_v[row * kPVS + seg * CS];
             float win[CS + 16];
 #pragma unroll
             for (int k = 0; k < CS + 16; k++) win[k] = k < KSAFE ? wb[k] : wb[min(k, kPIW - 1 - seg * CS)];
             auto store = [&](int o, double t) {
-                if (seg * CS + o < kPBW) s_h[row * kPHS + seg * CS + o] = (float)t;
+                if (NSEG * CS == kPBW || seg * CS + o < kPBW) s_h[row * kPHS + seg * CS + o] = (float)t;
             };
             if constexpr (ARITH == PYR_CERTIFIED) {
                 float M = 0.0f;

@@ -739,8 +739,8 @@ int oflk_stabilize_sequence_u8(const unsigned char *frames, int T, int H, int W,
  * and positive, F < 1, H or W < 2, Hc or Wc < 1, an unknown blend, NULL pointers (d_counts, d_held, d_skip, d_count and the
  * sequence call's outputs after `canvas` may be NULL; d_model when T == 1), a map or chain output that is not 8-byte aligned, a
  * state that is too small or not 256-byte aligned: OFLK_ERR_INVALID;  a frame or a canvas of 2^30 pixels or more, a canvas
- * that reaches 2^30 from the origin: OFLK_ERR_UNSUPPORTED.  A temporal median, exposure compensation and bundle adjustment of
- * the chain (its drift grows with the distance from the anchor) are not offered. */
+ * that reaches 2^30 from the origin: OFLK_ERR_UNSUPPORTED.  A temporal median and bundle adjustment of the chain (its drift
+ * grows with the distance from the anchor) are not offered;  exposure compensation is the _exposure forms below. */
 #define OFLK_MOSAIC_MEAN 0
 #define OFLK_MOSAIC_FEATHER 1
 #define OFLK_MOSAIC_FIRST 2
@@ -769,6 +769,30 @@ int oflk_mosaic_composite_host(const float *frames, int F, int H, int W, const d
                                int y0, int Hc, int Wc, int blend, float *out, int *count);
 int oflk_mosaic_composite_host_u8(const unsigned char *frames, int F, int H, int W, const double *map, const unsigned char *skip,
                                   int x0, int y0, int Hc, int Wc, int blend, unsigned char *out, int *count);
+/* Exposure compensation (the statement: tests/mosaic_exposure_model.py).  The photometric alignment below gives every step
+ * t -> t+1 a gain and a bias, "frame t+1 looks like g_t frame t + b_t".  oflk_exposure_chain_host composes them from the
+ * anchor:  (eg_f, eb_f) takes frame f's values to the anchor's exposure, v_anchor = eg_f v_f + eb_f.  photo [T-1][2] float32
+ * (NULL when T == 1), status [T-1] or NULL, exposure [T][2] float64 out.  The float32 inputs are widened first;  everything is
+ * float64, every operation rounded on its own.  A step is held, that is taken as (1, 0), when its status is 0, when g or b is
+ * not finite, or when g <= 0.
+ *   E_anchor = (1, 0)
+ *   forwards, t = anchor .. T-2:    eg_{t+1} = eg_t / g_t;     eb_{t+1} = eb_t - eg_{t+1} b_t
+ *   backwards, t = anchor-1 .. 0:   eg_t = eg_{t+1} g_t;       eb_t = eg_{t+1} b_t + eb_{t+1}
+ * Host only, no device call.  T < 1, an anchor outside [0, T-1], NULL pointers: OFLK_ERR_INVALID.
+ * The compensated accumulation is oflk_mosaic_accumulate with one change: the float32 sample s of frame f enters the blend as
+ * eg_f * f64(s) + eb_f, one multiply and one add, each rounded (d_exposure [F][2] float64, 8-byte aligned; NULL:
+ * OFLK_ERR_INVALID).  The cull, the four blends, the counts and the resolve are unchanged, and so are the refusals.  One gain
+ * and one bias per frame: per-channel gains (colour frames use the luma's pair for every channel), gamma and vignetting are
+ * not modelled. */
+int oflk_exposure_chain_host(const float *photo, const int *status, int T, int anchor, double *exposure);
+int oflk_mosaic_accumulate_exposure(const void *d_frames, int u8, int F, int H, int W, const double *d_map,
+                                    const unsigned char *d_skip, const double *d_exposure, int x0, int y0, int Hc, int Wc, int blend,
+                                    void *d_state, size_t state_bytes, void *stream);
+int oflk_mosaic_composite_exposure_host(const float *frames, int F, int H, int W, const double *map, const unsigned char *skip,
+                                        const double *exposure, int x0, int y0, int Hc, int Wc, int blend, float *out, int *count);
+int oflk_mosaic_composite_exposure_host_u8(const unsigned char *frames, int F, int H, int W, const double *map,
+                                           const unsigned char *skip, const double *exposure, int x0, int y0, int Hc, int Wc,
+                                           int blend, unsigned char *out, int *count);
 /* Frames in, mosaic out.  By statement, byte for byte: oflk_pyramidal_sequence_klt_sparse_replenish on the frames,
  * oflk_tracks_homography on its rows with t0 = 0, oflk_mosaic_chain and oflk_mosaic_canvas, then oflk_mosaic_accumulate of all
  * frames under from_anchor with skip = dropped and the canvas's x0, y0, and oflk_mosaic_resolve.  Pass 1 is the replenish
@@ -835,8 +859,7 @@ int oflk_mosaic_sequence_u8(const unsigned char *frames, int T, int H, int W, in
  * an unknown model, levels outside [1, OFLK_MAX_LEVELS], NULL pointers (d_status_in / status_in may be NULL: every step
  * refined), a workspace that is too small or not 256-byte aligned, d_stats not 8-byte aligned: OFLK_ERR_INVALID;  frames of
  * 2^30 pixels or more, levels whose coarsest would be smaller than 8 x 8: OFLK_ERR_UNSUPPORTED.  Early exit on a small
- * update, the ECC normalisation, photometric gain and bias, translation and similarity models and robust weights are not
- * offered. */
+ * update, the ECC normalisation, translation and similarity models and robust weights are not offered. */
 #define OFLK_ALIGN_AFFINE 0
 #define OFLK_ALIGN_HOMOGRAPHY 1
 /* bytes of the workspace of S steps (the sequence call: S = T - 1).  Host only */
@@ -864,6 +887,51 @@ int oflk_align_sequence_host(const float *frames, int T, int H, int W, int level
 int oflk_align_sequence_host_u8(const unsigned char *frames, int T, int H, int W, int levels, int iterations, int model,
                                 float min_share, const float *model_in, const int *status_in, float *model_out, int *status_out,
                                 double *stats);
+
+/* The photometric form (the statement: tests/align_photo_model.py): the calls above with a gain and a bias estimated beside
+ * every step model, for frames whose exposure differs.  It is the statement above with what follows changed.  A step carries
+ * two more float64 values, g = 1.0 and b = 0.0 at the start: "B under the model looks like g A + b".
+ *   sums_photo(l, M, g, b)   counted, xs, ys, Gx, Gy, xh, yh and sd[0 .. NP-1] as above;  v = sample(B_l, xs, ys) in float32;
+ *                  a = f64(A_l[y][x]);  r = f64(v) - (g a + b), formed in float64, every operation rounded on its own;  the
+ *                  NQ = NP + 2 columns c = [g sd[0], .., g sd[NP-1], a, 1.0];  the NQ (NQ + 1) / 2 + NQ + 2 sums over the
+ *                  counted pixels (67 or 46):  c[i] c[j] for i = 0 .. NQ-1, j = i .. NQ-1;  c[i] r;  r r;  1.0.  The order of
+ *                  every sum is the one above
+ *   before, after  r r / count of sums_photo(L-1, M, 1, 0) under the input model, and of sums_photo(L-1, M, g, b) under the
+ *                  final model and the final g, b;  stats keeps its four entries
+ *   iteration      [G | rhs] of the sums, eliminated without pivoting by the same procedure on NQ rows: q.  The geometric
+ *                  update is the one above on q[0 .. NP-1];  then g' = g + q[NP], b' = b + q[NP + 1].  (Minimising
+ *                  sum (r + g sd.dp - a dg - db)^2, the normal equations in c solve for [-dp, dg, db].)
+ *   freezing       the four conditions above, or g' or b' not finite, or g' <= 0.  A step that freezes keeps M_l, g and b.
+ *                  g and b are not rescaled between levels
+ *   outputs        model, status and stats by the rules above;  photo[s] = (f32(g), f32(b)) where the status is 1, else the
+ *                  bytes of (1.0f, 0.0f), a refused step included
+ * d_photo_out / photo_out [S][2] float32;  NULL: OFLK_ERR_INVALID;  the other refusals are the plain calls'.  The workspace is
+ * larger: oflk_align_photo_workspace.  The device forms are asynchronous on `stream` and can be captured into a graph (one
+ * chain, no parallel branches).  One gain and one bias per step over the whole frame: robust weights, the ECC normalisation,
+ * per-channel gains and gamma are not offered.  The sparse tracker still assumes brightness constancy: a step whose exposure
+ * change exceeds its max_residual (4 grey levels by default) ends tracks before the refinement sees the step. */
+int oflk_align_photo_workspace(int S, int H, int W, int levels, int model, size_t *bytes);
+int oflk_align_refine_photo(const void *d_a, const void *d_b, int u8, int S, int H, int W, int levels, int iterations, int model,
+                            float min_share, const float *d_model_in, const int *d_status_in, void *d_workspace,
+                            size_t workspace_bytes, float *d_model_out, int *d_status_out, double *d_stats, float *d_photo_out,
+                            void *stream);
+int oflk_align_sequence_photo(const void *d_frames, int u8, int T, int H, int W, int levels, int iterations, int model,
+                              float min_share, const float *d_model_in, const int *d_status_in, void *d_workspace,
+                              size_t workspace_bytes, float *d_model_out, int *d_status_out, double *d_stats, float *d_photo_out,
+                              void *stream);
+/* host arrays, synchronous, in the plain host forms' chunks of at most 64 steps */
+int oflk_align_refine_photo_host(const float *a, const float *b, int S, int H, int W, int levels, int iterations, int model,
+                                 float min_share, const float *model_in, const int *status_in, float *model_out, int *status_out,
+                                 double *stats, float *photo_out);
+int oflk_align_refine_photo_host_u8(const unsigned char *a, const unsigned char *b, int S, int H, int W, int levels,
+                                    int iterations, int model, float min_share, const float *model_in, const int *status_in,
+                                    float *model_out, int *status_out, double *stats, float *photo_out);
+int oflk_align_sequence_photo_host(const float *frames, int T, int H, int W, int levels, int iterations, int model,
+                                   float min_share, const float *model_in, const int *status_in, float *model_out, int *status_out,
+                                   double *stats, float *photo_out);
+int oflk_align_sequence_photo_host_u8(const unsigned char *frames, int T, int H, int W, int levels, int iterations, int model,
+                                      float min_share, const float *model_in, const int *status_in, float *model_out,
+                                      int *status_out, double *stats, float *photo_out);
 
 /* ---- online video stabilisation: a fixed-lag stabiliser on the tracker --------------------------------------------------- */
 /* The statement (tests/stabilize_online_model.py) is the trajectory above, read in the order in which a stream delivers its

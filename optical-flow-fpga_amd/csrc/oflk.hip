@@ -4485,12 +4485,14 @@ int mosaic_chain_launch(const float *d_model, const int *d_counts, int T, int an
     return OFLK_OK;
 }
 
-// the one launch that adds F frames to the state on stream s; the arguments are checked
+// the one launch that adds F frames to the state on stream s; the arguments are checked.  d_exposure: NULL, or the frames'
+// (eg, eb) of the exposure-compensated form
 template <class PIX>
 int mosaic_accumulate_launch(const PIX *d_frames, int F, int H, int W, const double *d_map, const unsigned char *d_skip, int x0, int y0,
-                             int Hc, int Wc, int blend, void *d_state, hipStream_t s)
+                             int Hc, int Wc, int blend, void *d_state, hipStream_t s, const double *d_exposure = nullptr)
 {
-    MosaicArgs<PIX> a{};
+    MosaicExposureArgs<PIX> a{};
+    a.exposure = d_exposure;
     a.in = d_frames; a.map = d_map; a.skip = d_skip;
     a.st = mosaic_state(d_state, Hc, Wc).st;
     a.F = F; a.H = H; a.W = W;
@@ -4498,7 +4500,11 @@ int mosaic_accumulate_launch(const PIX *d_frames, int F, int H, int W, const dou
     a.tiles_x = (Wc + kMosaicTileW - 1) / kMosaicTileW;
     const dim3 grid((unsigned)a.tiles_x * (unsigned)((Hc + kMosaicBlockH - 1) / kMosaicBlockH));
     const bool built = with_int<kMosaicMean, kMosaicFeather, kMosaicFirst, kMosaicLast>(blend, [&](auto BLEND) {
-        hipLaunchKernelGGL((k_mosaic_accumulate<PIX, decltype(BLEND)::value>), grid, dim3(256), 0, s, a);
+        if (d_exposure)
+            hipLaunchKernelGGL((k_mosaic_accumulate<PIX, decltype(BLEND)::value, true, MosaicExposureArgs<PIX>>), grid, dim3(256), 0, s, a);
+        else
+            hipLaunchKernelGGL((k_mosaic_accumulate<PIX, decltype(BLEND)::value>), grid, dim3(256), 0, s,
+                               static_cast<const MosaicArgs<PIX> &>(a));
     });
     if (!built) return fail(OFLK_ERR_INVALID, "unknown blend %d", blend);
     HIP_TRY(hipGetLastError());
@@ -4526,7 +4532,7 @@ int mosaic_resolve_launch(void *d_state, int Hc, int Wc, PIX *d_out, int *d_coun
 // samples are added in frame order whatever the cut, so the cut does not show.
 template <class PIX>
 int mosaic_composite_chunks(HostCall &call, const PIX *frames, int F, int H, int W, const double *d_map, const unsigned char *d_skip,
-                            int x0, int y0, int Hc, int Wc, int blend, PIX *out, int *count)
+                            int x0, int y0, int Hc, int Wc, int blend, PIX *out, int *count, const double *d_exposure = nullptr)
 {
     const int C = sparse_chunk_pairs(F, H, W);
     const size_t plane = (size_t)H * W, npix = (size_t)Hc * Wc;
@@ -4543,7 +4549,7 @@ int mosaic_composite_chunks(HostCall &call, const PIX *frames, int F, int H, int
         const int n = std::min(C, F - f0);
         if ((rc = call.to_device(d_in, frames + (size_t)f0 * plane, (size_t)n * plane)) ||
             (rc = mosaic_accumulate_launch<PIX>(d_in, n, H, W, d_map + 9 * (size_t)f0, d_skip ? d_skip + f0 : nullptr, x0, y0, Hc, Wc,
-                                                blend, d_state, nullptr)) ||
+                                                blend, d_state, nullptr, d_exposure ? d_exposure + 2 * (size_t)f0 : nullptr)) ||
             (rc = call.sync()))
             return rc;
     }
@@ -4555,17 +4561,20 @@ int mosaic_composite_chunks(HostCall &call, const PIX *frames, int F, int H, int
 
 template <class PIX>
 int mosaic_composite_host(const PIX *frames, int F, int H, int W, const double *map, const unsigned char *skip, int x0, int y0, int Hc,
-                          int Wc, int blend, PIX *out, int *count)
+                          int Wc, int blend, PIX *out, int *count, bool compensated = false, const double *exposure = nullptr)
 {
     int rc = check_mosaic_frames(frames, F, H, W, map, Hc, Wc, blend);
     if (rc) return rc;
     if (!out) return fail(OFLK_ERR_INVALID, "NULL output argument");
+    if (compensated && !exposure) return fail(OFLK_ERR_INVALID, "NULL exposure");
     HostCall call;
     if ((rc = call.begin())) return rc;
-    double *d_map = nullptr;
+    double *d_map = nullptr, *d_exposure = nullptr;
     unsigned char *d_skip = nullptr;
-    if ((rc = call.upload(&d_map, map, 9 * (size_t)F)) || (skip && (rc = call.upload(&d_skip, skip, (size_t)F)))) return rc;
-    return mosaic_composite_chunks<PIX>(call, frames, F, H, W, d_map, d_skip, x0, y0, Hc, Wc, blend, out, count);
+    if ((rc = call.upload(&d_map, map, 9 * (size_t)F)) || (skip && (rc = call.upload(&d_skip, skip, (size_t)F))) ||
+        (compensated && (rc = call.upload(&d_exposure, exposure, 2 * (size_t)F))))
+        return rc;
+    return mosaic_composite_chunks<PIX>(call, frames, F, H, W, d_map, d_skip, x0, y0, Hc, Wc, blend, out, count, d_exposure);
 }
 
 // oflk_mosaic_sequence: pass 1 is the replenish call itself, as in stabilize_sequence; the rows go up again for the
@@ -4731,6 +4740,59 @@ OFLK_API int oflk_mosaic_accumulate(const void *d_frames, int u8, int F, int H, 
                                                 (hipStream_t)stream);
 }
 
+OFLK_API int oflk_mosaic_accumulate_exposure(const void *d_frames, int u8, int F, int H, int W, const double *d_map,
+                                             const unsigned char *d_skip, const double *d_exposure, int x0, int y0, int Hc, int Wc,
+                                             int blend, void *d_state, size_t state_bytes, void *stream)
+{
+    if (int rc = check_mosaic_frames(d_frames, F, H, W, d_map, Hc, Wc, blend)) return rc;
+    if (!d_state || !d_exposure) return fail(OFLK_ERR_INVALID, "NULL d_state or d_exposure");
+    if (!aligned(d_map, 8) || !aligned(d_exposure, 8)) return fail(OFLK_ERR_INVALID, "d_map and d_exposure must be 8-byte aligned");
+    if (!u8 && !aligned(d_frames, 4)) return fail(OFLK_ERR_INVALID, "float32 frames must be 4-byte aligned");
+    const size_t need = mosaic_state(nullptr, Hc, Wc).bytes;
+    if (state_bytes < need) return fail(OFLK_ERR_INVALID, "state of %zu bytes, %zu needed (oflk_mosaic_state_bytes)", state_bytes, need);
+    if (!aligned(d_state, 256)) return fail(OFLK_ERR_INVALID, "d_state must be 256-byte aligned");
+    return u8 ? mosaic_accumulate_launch<unsigned char>((const unsigned char *)d_frames, F, H, W, d_map, d_skip, x0, y0, Hc, Wc, blend,
+                                                        d_state, (hipStream_t)stream, d_exposure)
+              : mosaic_accumulate_launch<float>((const float *)d_frames, F, H, W, d_map, d_skip, x0, y0, Hc, Wc, blend, d_state,
+                                                (hipStream_t)stream, d_exposure);
+}
+
+OFLK_API int oflk_exposure_chain_host(const float *photo, const int *status, int T, int anchor, double *exposure)
+{
+    if (T < 1) return fail(OFLK_ERR_INVALID, "T must be >= 1 (got %d)", T);
+    if (anchor < 0 || anchor >= T) return fail(OFLK_ERR_INVALID, "anchor must be in [0, %d) (got %d)", T, anchor);
+    if ((T > 1 && !photo) || !exposure) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    // step t's (g, b) widened, or (1, 0) when the step is held
+    auto step = [&](int t, double &g, double &b) {
+        g = (double)photo[2 * (size_t)t];
+        b = (double)photo[2 * (size_t)t + 1];
+        if ((status && status[t] == 0) || !std::isfinite(g) || !std::isfinite(b) || !(g > 0.0)) {
+            g = 1.0;
+            b = 0.0;
+        }
+    };
+    double *e = exposure;
+    e[2 * (size_t)anchor] = 1.0;
+    e[2 * (size_t)anchor + 1] = 0.0;
+    for (int t = anchor; t < T - 1; t++) {
+        double g, b;
+        step(t, g, b);
+        const double eg = e[2 * (size_t)t] / g;
+        const double p = eg * b;
+        e[2 * (size_t)t + 2] = eg;
+        e[2 * (size_t)t + 3] = e[2 * (size_t)t + 1] - p;
+    }
+    for (int t = anchor - 1; t >= 0; t--) {
+        double g, b;
+        step(t, g, b);
+        const double eg = e[2 * (size_t)t + 2];
+        const double p = eg * b;
+        e[2 * (size_t)t] = eg * g;
+        e[2 * (size_t)t + 1] = p + e[2 * (size_t)t + 3];
+    }
+    return OFLK_OK;
+}
+
 OFLK_API int oflk_mosaic_resolve(const void *d_state, int Hc, int Wc, int u8, void *d_out, int *d_count, void *stream)
 {
     if (int rc = check_mosaic_canvas(Hc, Wc)) return rc;
@@ -4754,6 +4816,20 @@ OFLK_API int oflk_mosaic_composite_host_u8(const unsigned char *frames, int F, i
                                            int *count)
 {
     return mosaic_composite_host<unsigned char>(frames, F, H, W, map, skip, x0, y0, Hc, Wc, blend, out, count);
+}
+
+OFLK_API int oflk_mosaic_composite_exposure_host(const float *frames, int F, int H, int W, const double *map,
+                                                 const unsigned char *skip, const double *exposure, int x0, int y0, int Hc, int Wc,
+                                                 int blend, float *out, int *count)
+{
+    return mosaic_composite_host<float>(frames, F, H, W, map, skip, x0, y0, Hc, Wc, blend, out, count, true, exposure);
+}
+
+OFLK_API int oflk_mosaic_composite_exposure_host_u8(const unsigned char *frames, int F, int H, int W, const double *map,
+                                                    const unsigned char *skip, const double *exposure, int x0, int y0, int Hc,
+                                                    int Wc, int blend, unsigned char *out, int *count)
+{
+    return mosaic_composite_host<unsigned char>(frames, F, H, W, map, skip, x0, y0, Hc, Wc, blend, out, count, true, exposure);
 }
 
 OFLK_API int oflk_mosaic_sequence(const float *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
@@ -4783,7 +4859,7 @@ OFLK_API int oflk_mosaic_sequence_u8(const unsigned char *frames, int T, int H, 
 // =============================================================================
 namespace {
 int align_coefficients(int model) { return model == OFLK_ALIGN_HOMOGRAPHY ? 9 : 6; }
-int align_nsums(int model) { return align_sums(model == OFLK_ALIGN_HOMOGRAPHY ? 8 : 6); }
+int align_nsums(int model, bool photo = false) { return align_sums((model == OFLK_ALIGN_HOMOGRAPHY ? 8 : 6) + (photo ? 2 : 0)); }
 int align_tiles(int h, int w) { return ((w + kAlignTileW - 1) / kAlignTileW) * ((h + kAlignTileH - 1) / kAlignTileH); }
 
 // The refusals of the configuration, before any device call; dims receives the level sizes
@@ -4811,15 +4887,17 @@ int check_align(int S, int H, int W, int levels, int iterations, int model, floa
 }
 
 // The workspace, 256-byte aligned pieces: the steps' states [S], the tile sums [S][tiles of the frame][NS], and per level
-// below the frame 2 S images (the pair form: S of A, then S of B; the sequence form: the first S + 1 hold its frames')
+// below the frame 2 S images (the pair form: S of A, then S of B; the sequence form: the first S + 1 hold its frames').  The
+// photometric form has more sums per tile and, behind everything else, the steps' (g, b) [S][2]
 struct AlignWs {
     AlignState *state;
     double *partial;
     float *pyr[OFLK_MAX_LEVELS];
+    double *photo;
     size_t pstride, bytes;
 };
 
-AlignWs align_ws(void *base, int S, int levels, const int *dims, int model)
+AlignWs align_ws(void *base, int S, int levels, const int *dims, int model, bool photo = false)
 {
     char *b = static_cast<char *>(base);
     auto at = [&](size_t o) { return b ? b + o : nullptr; };   // NULL: only the size is wanted
@@ -4827,12 +4905,16 @@ AlignWs align_ws(void *base, int S, int levels, const int *dims, int model)
     size_t o = 0;
     ws.state = reinterpret_cast<AlignState *>(at(o));
     o += round256((size_t)S * sizeof(AlignState));
-    ws.pstride = (size_t)align_tiles(dims[2 * (levels - 1)], dims[2 * (levels - 1) + 1]) * (size_t)align_nsums(model);
+    ws.pstride = (size_t)align_tiles(dims[2 * (levels - 1)], dims[2 * (levels - 1) + 1]) * (size_t)align_nsums(model, photo);
     ws.partial = reinterpret_cast<double *>(at(o));
     o += round256((size_t)S * ws.pstride * sizeof(double));
     for (int l = 0; l < levels - 1; l++) {
         ws.pyr[l] = reinterpret_cast<float *>(at(o));
         o += round256(2 * (size_t)S * (size_t)dims[2 * l] * (size_t)dims[2 * l + 1] * sizeof(float));
+    }
+    if (photo) {
+        ws.photo = reinterpret_cast<double *>(at(o));
+        o += round256(2 * (size_t)S * sizeof(double));
     }
     ws.bytes = o;
     return ws;
@@ -4849,21 +4931,27 @@ int check_align_device(const void *d_a, const void *d_b, int u8, const void *d_m
     return OFLK_OK;
 }
 
+// photo: NULL, or the steps' (g, b) of the photometric form
 template <class PIX, int NP>
-int align_reduce_launch(const AlignReduceArgs &r, int tiles, hipStream_t s)
+int align_reduce_launch(const AlignReduceArgs &r, int tiles, hipStream_t s, const double *photo = nullptr)
 {
-    hipLaunchKernelGGL((k_align_reduce<PIX, NP>), dim3((unsigned)tiles, (unsigned)std::min(r.S, 65535)), dim3(64), 0, s, r);
+    const dim3 grid((unsigned)tiles, (unsigned)std::min(r.S, 65535));
+    if (photo)
+        hipLaunchKernelGGL((k_align_reduce_photo<PIX, NP>), grid, dim3(64 * align_photo_waves(NP)), 0, s, AlignPhotoReduceArgs{r, photo});
+    else
+        hipLaunchKernelGGL((k_align_reduce<PIX, NP>), grid, dim3(64), 0, s, r);
     HIP_TRY(hipGetLastError());
     return OFLK_OK;
 }
 
 // The whole chain of one call on stream s; the arguments are checked.  d_a, d_b: the S templates and images, `step` elements
 // apart (the pair form: two arrays of S frames; the sequence form: d_b = d_a + one frame).  nimg > 0: the sequence form's
-// nimg = S + 1 frames, whose pyramids are built once.
+// nimg = S + 1 frames, whose pyramids are built once.  d_photo_out: NULL, or the photometric
+// form's output (ws is then that form's workspace)
 template <class PIX, int NP>
 int align_launch(const PIX *d_a, const PIX *d_b, int nimg, int S, int H, int W, int levels, const int *dims, int iterations,
                  float min_share, const float *d_model_in, const int *d_status_in, const AlignWs &ws, float *d_model_out,
-                 int *d_status_out, double *d_stats, hipStream_t s)
+                 int *d_status_out, double *d_stats, hipStream_t s, float *d_photo_out = nullptr)
 {
     constexpr int NC = NP == 8 ? 9 : 6;
     const bool seq = nimg > 0;
@@ -4891,6 +4979,11 @@ int align_launch(const PIX *d_a, const PIX *d_b, int nimg, int S, int H, int W, 
     }
     hipLaunchKernelGGL(k_align_begin, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, s, d_model_in, d_status_in, S, NC, ws.state);
     HIP_TRY(hipGetLastError());
+    const double *photo = d_photo_out ? ws.photo : nullptr;
+    if (photo) {
+        hipLaunchKernelGGL(k_align_photo_begin, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, s, S, ws.photo);
+        HIP_TRY(hipGetLastError());
+    }
 
     // the sums of level l under the steps' current models, then the update of the given mode
     auto pass = [&](int l, int mode, int last, int next) -> int {
@@ -4905,11 +4998,11 @@ int align_launch(const PIX *d_a, const PIX *d_b, int nimg, int S, int H, int W, 
         if (l == levels - 1) {
             r.a = d_a;
             r.b = d_b;
-            rc2 = align_reduce_launch<PIX, NP>(r, tiles, s);
+            rc2 = align_reduce_launch<PIX, NP>(r, tiles, s, photo);
         } else {
             r.a = ws.pyr[l];
             r.b = ws.pyr[l] + (seq ? 1 : (size_t)S) * r.stride;
-            rc2 = align_reduce_launch<float, NP>(r, tiles, s);
+            rc2 = align_reduce_launch<float, NP>(r, tiles, s, photo);
         }
         if (rc2) return rc2;
         AlignUpdateArgs u{};
@@ -4923,7 +5016,11 @@ int align_launch(const PIX *d_a, const PIX *d_b, int nimg, int S, int H, int W, 
         }
         u.min_count = (double)min_share * (double)((long long)w * (long long)h);
         u.model_in = d_model_in; u.model_out = d_model_out; u.status_out = d_status_out; u.stats = d_stats;
-        hipLaunchKernelGGL((k_align_update<NP>), dim3((unsigned)std::min(S, 65535)), dim3(64), 0, s, u);
+        if (photo)
+            hipLaunchKernelGGL((k_align_update_photo<NP>), dim3((unsigned)std::min(S, 65535)), dim3(64), 0, s,
+                               AlignPhotoUpdateArgs{u, ws.photo, d_photo_out});
+        else
+            hipLaunchKernelGGL((k_align_update<NP>), dim3((unsigned)std::min(S, 65535)), dim3(64), 0, s, u);
         HIP_TRY(hipGetLastError());
         return OFLK_OK;
     };
@@ -4939,30 +5036,33 @@ int align_launch(const PIX *d_a, const PIX *d_b, int nimg, int S, int H, int W, 
 template <class PIX>
 int align_dispatch(const PIX *d_a, const PIX *d_b, int nimg, int S, int H, int W, int levels, const int *dims, int iterations,
                    int model, float min_share, const float *d_model_in, const int *d_status_in, const AlignWs &ws,
-                   float *d_model_out, int *d_status_out, double *d_stats, hipStream_t s)
+                   float *d_model_out, int *d_status_out, double *d_stats, hipStream_t s, float *d_photo_out = nullptr)
 {
     return model == OFLK_ALIGN_HOMOGRAPHY
                ? align_launch<PIX, 8>(d_a, d_b, nimg, S, H, W, levels, dims, iterations, min_share, d_model_in, d_status_in, ws,
-                                      d_model_out, d_status_out, d_stats, s)
+                                      d_model_out, d_status_out, d_stats, s, d_photo_out)
                : align_launch<PIX, 6>(d_a, d_b, nimg, S, H, W, levels, dims, iterations, min_share, d_model_in, d_status_in, ws,
-                                      d_model_out, d_status_out, d_stats, s);
+                                      d_model_out, d_status_out, d_stats, s, d_photo_out);
 }
 
 int align_device(const void *d_a, const void *d_b, int u8, int nimg, int S, int H, int W, int levels, int iterations, int model,
                  float min_share, const float *d_model_in, const int *d_status_in, void *d_workspace, size_t bytes,
-                 float *d_model_out, int *d_status_out, double *d_stats, hipStream_t s)
+                 float *d_model_out, int *d_status_out, double *d_stats, hipStream_t s, bool photo = false,
+                 float *d_photo_out = nullptr)
 {
     int dims[2 * OFLK_MAX_LEVELS];
     int rc = check_align(S, H, W, levels, iterations, model, min_share, dims);
     if (rc) return rc;
-    const size_t need = align_ws(nullptr, S, levels, dims, model).bytes;
+    const size_t need = align_ws(nullptr, S, levels, dims, model, photo).bytes;
     if ((rc = check_align_device(d_a, d_b, u8, d_model_in, d_workspace, bytes, need, d_model_out, d_status_out, d_stats))) return rc;
-    const AlignWs ws = align_ws(d_workspace, S, levels, dims, model);
+    if (photo && !d_photo_out) return fail(OFLK_ERR_INVALID, "NULL d_photo_out");
+    if (photo && !aligned(d_photo_out, 4)) return fail(OFLK_ERR_INVALID, "d_photo_out must be 4-byte aligned");
+    const AlignWs ws = align_ws(d_workspace, S, levels, dims, model, photo);
     return u8 ? align_dispatch<unsigned char>((const unsigned char *)d_a, (const unsigned char *)d_b, nimg, S, H, W, levels, dims,
                                               iterations, model, min_share, d_model_in, d_status_in, ws, d_model_out, d_status_out,
-                                              d_stats, s)
+                                              d_stats, s, d_photo_out)
               : align_dispatch<float>((const float *)d_a, (const float *)d_b, nimg, S, H, W, levels, dims, iterations, model, min_share,
-                                      d_model_in, d_status_in, ws, d_model_out, d_status_out, d_stats, s);
+                                      d_model_in, d_status_in, ws, d_model_out, d_status_out, d_stats, s, d_photo_out);
 }
 
 // S host steps in chunks of steps through one set of device buffers: a chunk's frames go up, its steps are refined and the
@@ -4970,27 +5070,28 @@ int align_device(const void *d_a, const void *d_b, int u8, int nimg, int S, int 
 // frame alone, so the cut does not show.  seq: frames [S + 1][H][W], a chunk of n steps takes its n + 1 frames (b is unused)
 template <class PIX>
 int align_host(const PIX *a, const PIX *b, bool seq, int S, int H, int W, int levels, int iterations, int model, float min_share,
-               const float *model_in, const int *status_in, float *model_out, int *status_out, double *stats)
+               const float *model_in, const int *status_in, float *model_out, int *status_out, double *stats, bool photo = false,
+               float *photo_out = nullptr)
 {
     int dims[2 * OFLK_MAX_LEVELS];
     int rc = check_align(S, H, W, levels, iterations, model, min_share, dims);
     if (rc) return rc;
-    if (!a || (!seq && !b) || !model_in || !model_out || !status_out || !stats)
+    if (!a || (!seq && !b) || !model_in || !model_out || !status_out || !stats || (photo && !photo_out))
         return fail(OFLK_ERR_INVALID, "NULL input or output argument");
     HostCall call;
     if ((rc = call.begin())) return rc;
     const int C = sparse_chunk_pairs(S, H, W), nc = align_coefficients(model);
     const size_t plane = (size_t)H * W, nS = (size_t)S;
     PIX *d_a = nullptr, *d_b = nullptr;
-    float *d_min = nullptr, *d_mout = nullptr;
+    float *d_min = nullptr, *d_mout = nullptr, *d_photo = nullptr;
     int *d_sin = nullptr, *d_sout = nullptr;
     double *d_stats = nullptr;
     char *d_ws = nullptr;
-    const size_t bytes = align_ws(nullptr, C, levels, dims, model).bytes;
+    const size_t bytes = align_ws(nullptr, C, levels, dims, model, photo).bytes;
     if ((rc = call.alloc(&d_a, (size_t)(C + (seq ? 1 : 0)) * plane)) || (rc = call.alloc(&d_b, (size_t)C * plane, !seq)) ||
         (rc = call.upload(&d_min, model_in, nc * nS)) || (status_in && (rc = call.upload(&d_sin, status_in, nS))) ||
         (rc = call.alloc(&d_mout, nc * nS)) || (rc = call.alloc(&d_sout, nS)) || (rc = call.alloc(&d_stats, 4 * nS)) ||
-        (rc = call.alloc(&d_ws, bytes)))
+        (rc = call.alloc(&d_ws, bytes)) || (rc = call.alloc(&d_photo, 2 * nS, photo)))
         return rc;
     for (int s0 = 0; s0 < S; s0 += C) {
         const int n = std::min(C, S - s0);
@@ -4998,15 +5099,15 @@ int align_host(const PIX *a, const PIX *b, bool seq, int S, int H, int W, int le
         if ((rc = call.to_device(d_a, a + o, (size_t)(n + (seq ? 1 : 0)) * plane)) ||
             (!seq && (rc = call.to_device(d_b, b + o, (size_t)n * plane))))
             return rc;
-        const AlignWs ws = align_ws(d_ws, n, levels, dims, model);
+        const AlignWs ws = align_ws(d_ws, n, levels, dims, model, photo);
         if ((rc = align_dispatch<PIX>(d_a, seq ? d_a + plane : d_b, seq ? n + 1 : 0, n, H, W, levels, dims, iterations, model, min_share,
                                       d_min + (size_t)nc * s0, d_sin ? d_sin + s0 : nullptr, ws, d_mout + (size_t)nc * s0, d_sout + s0,
-                                      d_stats + 4 * (size_t)s0, nullptr)) ||
+                                      d_stats + 4 * (size_t)s0, nullptr, photo ? d_photo + 2 * (size_t)s0 : nullptr)) ||
             (rc = call.sync()))
             return rc;
     }
     if ((rc = call.to_host(model_out, d_mout, nc * nS)) || (rc = call.to_host(status_out, d_sout, nS)) ||
-        (rc = call.to_host(stats, d_stats, 4 * nS)))
+        (rc = call.to_host(stats, d_stats, 4 * nS)) || (photo && (rc = call.to_host(photo_out, d_photo, 2 * nS))))
         return rc;
     return call.sync();
 }
@@ -5073,6 +5174,71 @@ OFLK_API int oflk_align_sequence_host_u8(const unsigned char *frames, int T, int
     if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
     return align_host<unsigned char>(frames, nullptr, true, T - 1, H, W, levels, iterations, model, min_share, model_in, status_in,
                                      model_out, status_out, stats);
+}
+
+OFLK_API int oflk_align_photo_workspace(int S, int H, int W, int levels, int model, size_t *bytes)
+{
+    if (!bytes) return fail(OFLK_ERR_INVALID, "bytes is NULL");
+    *bytes = 0;
+    int dims[2 * OFLK_MAX_LEVELS];
+    if (int rc = check_align(S, H, W, levels, 1, model, 1.0f, dims)) return rc;
+    *bytes = align_ws(nullptr, S, levels, dims, model, true).bytes;
+    return OFLK_OK;
+}
+
+OFLK_API int oflk_align_refine_photo(const void *d_a, const void *d_b, int u8, int S, int H, int W, int levels, int iterations,
+                                     int model, float min_share, const float *d_model_in, const int *d_status_in, void *d_workspace,
+                                     size_t workspace_bytes, float *d_model_out, int *d_status_out, double *d_stats,
+                                     float *d_photo_out, void *stream)
+{
+    return align_device(d_a, d_b, u8, 0, S, H, W, levels, iterations, model, min_share, d_model_in, d_status_in, d_workspace,
+                        workspace_bytes, d_model_out, d_status_out, d_stats, (hipStream_t)stream, true, d_photo_out);
+}
+
+OFLK_API int oflk_align_sequence_photo(const void *d_frames, int u8, int T, int H, int W, int levels, int iterations, int model,
+                                       float min_share, const float *d_model_in, const int *d_status_in, void *d_workspace,
+                                       size_t workspace_bytes, float *d_model_out, int *d_status_out, double *d_stats,
+                                       float *d_photo_out, void *stream)
+{
+    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
+    const void *d_b = d_frames && H > 0 && W > 0 ? static_cast<const char *>(d_frames) + (size_t)H * (size_t)W * (u8 ? 1 : sizeof(float))
+                                                 : d_frames;
+    return align_device(d_frames, d_b, u8, T, T - 1, H, W, levels, iterations, model, min_share, d_model_in, d_status_in, d_workspace,
+                        workspace_bytes, d_model_out, d_status_out, d_stats, (hipStream_t)stream, true, d_photo_out);
+}
+
+OFLK_API int oflk_align_refine_photo_host(const float *a, const float *b, int S, int H, int W, int levels, int iterations, int model,
+                                          float min_share, const float *model_in, const int *status_in, float *model_out,
+                                          int *status_out, double *stats, float *photo_out)
+{
+    return align_host<float>(a, b, false, S, H, W, levels, iterations, model, min_share, model_in, status_in, model_out, status_out,
+                             stats, true, photo_out);
+}
+
+OFLK_API int oflk_align_refine_photo_host_u8(const unsigned char *a, const unsigned char *b, int S, int H, int W, int levels,
+                                             int iterations, int model, float min_share, const float *model_in, const int *status_in,
+                                             float *model_out, int *status_out, double *stats, float *photo_out)
+{
+    return align_host<unsigned char>(a, b, false, S, H, W, levels, iterations, model, min_share, model_in, status_in, model_out,
+                                     status_out, stats, true, photo_out);
+}
+
+OFLK_API int oflk_align_sequence_photo_host(const float *frames, int T, int H, int W, int levels, int iterations, int model,
+                                            float min_share, const float *model_in, const int *status_in, float *model_out,
+                                            int *status_out, double *stats, float *photo_out)
+{
+    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
+    return align_host<float>(frames, nullptr, true, T - 1, H, W, levels, iterations, model, min_share, model_in, status_in, model_out,
+                             status_out, stats, true, photo_out);
+}
+
+OFLK_API int oflk_align_sequence_photo_host_u8(const unsigned char *frames, int T, int H, int W, int levels, int iterations,
+                                               int model, float min_share, const float *model_in, const int *status_in,
+                                               float *model_out, int *status_out, double *stats, float *photo_out)
+{
+    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
+    return align_host<unsigned char>(frames, nullptr, true, T - 1, H, W, levels, iterations, model, min_share, model_in, status_in,
+                                     model_out, status_out, stats, true, photo_out);
 }
 
 // =============================================================================

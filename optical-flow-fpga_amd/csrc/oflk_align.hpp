@@ -369,4 +369,321 @@ __global__ __launch_bounds__(64) void k_align_update(AlignUpdateArgs a)
     }
 }
 
+// =============================================================================
+// the photometric form (oflk_align_refine_photo, oflk_align_sequence_photo): B under the model looks like g A + b
+// =============================================================================
+// The statement is tests/align_photo_model.py.  A step carries g and b beside its AlignState, in an array of their own
+// (photo [S][2], begun at (1, 0)), so that the kernels above keep their code.  The residual is r = f64(v) - (g a + b) and the
+// columns are c = [g sd[0], .., g sd[NP-1], a, 1.0]: NQ = NP + 2 of them, align_sums(NQ) = 46 (affine) or 67 (homography) sums
+// in the order of the plain form.
+//
+//   k_align_photo_begin        one thread per step: (g, b) = (1, 0)
+//   k_align_reduce_photo<PIX, NP>  k_align_reduce's tile, column walk, Sobel window and gather.  NP = 6 is one wave with its 46
+//                              sums.  NP = 8 is a block of two waves on the same tile: each walks all 64 columns and keeps
+//                              one half of the 67 sums (34 and 33), so that a wave stays within 256 registers.  Which wave
+//                              holds a sum does not change the sum's order; the sampling and the sd row are computed twice.
+//                              No LDS, no barrier: each wave's lane 0 writes its own sums
+//   k_align_update_photo<NP>   k_align_update on NQ rows: the first NP entries of the solution move the model as before, the
+//                              last two are added to g and b; a g' or b' that is not finite or a g' <= 0 freezes the step.
+//                              kAlignLast also writes photo_out
+
+constexpr int align_photo_waves(int NP) { return NP == 8 ? 2 : 1; }
+
+__global__ __launch_bounds__(64) void k_align_photo_begin(int S, double *__restrict__ photo)
+{
+    const unsigned s = blockIdx.x * 64u + threadIdx.x;
+    if (s >= (unsigned)S) return;
+    photo[2 * (size_t)s] = 1.0;
+    photo[2 * (size_t)s + 1] = 0.0;
+}
+
+struct AlignPhotoReduceArgs {
+    AlignReduceArgs r;
+    const double *photo;   // [S][2]
+};
+
+// one wave's walk over its tile for the sums K0 .. K1-1 of step s
+template <class PIX, int NP, int K0, int K1>
+__device__ __forceinline__ void align_photo_tile(const AlignPhotoReduceArgs &pa, int s, int lane, int tile)
+{
+    constexpr int NQ = NP + 2;
+    constexpr int NH = NQ * (NQ + 1) / 2;
+    constexpr int NS = align_sums(NQ);
+    constexpr int NK = K1 - K0;
+    static_assert(K0 >= 0 && K0 < K1 && K1 <= NS, "a wave's share of the sums");
+    const AlignReduceArgs &a = pa.r;
+    const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+    const int H = a.H, W = a.W;
+    const int x = tx * kAlignTileW + lane;
+    const bool col = x < W;
+    const int xc = min(x, W - 1), xl = max(xc - 1, 0), xr = min(xc + 1, W - 1);
+    const int y0 = ty * kAlignTileH, rows = min(kAlignTileH, H - y0);
+    const double Wm1 = (double)(W - 1), Hm1 = (double)(H - 1);
+    const double cx = Wm1 / 2.0, cy = Hm1 / 2.0, sc = (double)max(W, H) / 2.0;
+    const double fx = (double)x;
+    const double xh = (fx - cx) / sc;
+    const AlignState *__restrict__ st = a.state + s;
+    const double m0 = st->m[0], m1 = st->m[1], m2 = st->m[2], m3 = st->m[3], m4 = st->m[4], m5 = st->m[5];
+    [[maybe_unused]] double m6 = 0.0, m7 = 0.0, m8 = 1.0;
+    if constexpr (NP == 8) {
+        m6 = st->m[6]; m7 = st->m[7]; m8 = st->m[8];
+    }
+    const double g = pa.photo[2 * (size_t)s], b = pa.photo[2 * (size_t)s + 1];
+    const PIX *__restrict__ A = static_cast<const PIX *>(a.a) + (size_t)s * a.stride;
+    const PIX *__restrict__ B = static_cast<const PIX *>(a.b) + (size_t)s * a.stride;
+    double acc[NK];
+#pragma unroll
+    for (int k = 0; k < NK; k++) acc[k] = 0.0;
+    // sum k, when it is this wave's; k is a constant once the loops are unrolled, so no indexed array is left
+    auto add = [&](int k, double v) {
+        if (k >= K0 && k < K1) acc[k - K0] = acc[k - K0] + v;
+    };
+    auto load3 = [&](int yy, float (&v)[3], float &centre) {
+        const unsigned r = (unsigned)yy * (unsigned)W;
+        const float l = ld_pix<PIX>(A, r + (unsigned)xl), c = ld_pix<PIX>(A, r + (unsigned)xc), q = ld_pix<PIX>(A, r + (unsigned)xr);
+        centre = c;
+        v[0] = (l + l) * 0.5f; v[1] = (c + c) * 0.5f; v[2] = (q + q) * 0.5f;
+    };
+    float am[3], a0[3], ap[3], t0 = 0.0f, tn = 0.0f, unused = 0.0f;
+    load3(max(y0 - 1, 0), am, unused);
+    load3(y0, a0, t0);
+    for (int i = 0; i < rows; i++) {
+        const int y = y0 + i;
+        load3(min(y + 1, H - 1), ap, tn);
+        float ix = ap[2] * -0.125f;
+        ix = fmaf(ap[0], 0.125f, ix);
+        ix = fmaf(a0[2], -0.25f, ix);
+        ix = fmaf(a0[0], 0.25f, ix);
+        ix = fmaf(am[2], -0.125f, ix);
+        ix = fmaf(am[0], 0.125f, ix);
+        float iy = ap[2] * -0.125f;
+        iy = fmaf(ap[1], -0.25f, iy);
+        iy = fmaf(ap[0], -0.125f, iy);
+        iy = fmaf(am[2], 0.125f, iy);
+        iy = fmaf(am[1], 0.25f, iy);
+        iy = fmaf(am[0], 0.125f, iy);
+        ix = fmaf(ap[1], 0.0f, ix);
+        ix = fmaf(a0[1], 0.0f, ix);
+        ix = fmaf(am[1], 0.0f, ix);
+        iy = fmaf(a0[2], 0.0f, iy);
+        iy = fmaf(a0[1], 0.0f, iy);
+        iy = fmaf(a0[0], 0.0f, iy);
+        const double fy = (double)y;
+        [[maybe_unused]] const double w = (m6 * fx + m7 * fy) + m8;
+        const double xa = (m0 * fx + m1 * fy) + m2;
+        const double ya = (m3 * fx + m4 * fy) + m5;
+        const double xs = NP == 8 ? xa / w : xa;
+        const double ys = NP == 8 ? ya / w : ya;
+        const bool within = xs >= 0.0 && xs <= Wm1 && ys >= 0.0 && ys <= Hm1;
+        const bool ok = (NP == 8 ? w > 0.0 && within : within) && col;
+        const BilinearTaps t = bilinear_taps(H, W, ys, xs);
+        const float smp = bilinear_finish(t, ld_pix<PIX>(B, (unsigned)t.i00), ld_pix<PIX>(B, (unsigned)t.i01),
+                                          ld_pix<PIX>(B, (unsigned)t.i10), ld_pix<PIX>(B, (unsigned)t.i11));
+        if (ok) {
+            const double av = (double)t0;
+            const double r = (double)smp - (g * av + b);
+            const double gx = (double)ix, gy = (double)iy;
+            const double yh = (fy - cy) / sc;
+            double sd[NP], c[NQ];
+            sd[0] = gx * xh; sd[1] = gx * yh; sd[2] = gx;
+            sd[3] = gy * xh; sd[4] = gy * yh; sd[5] = gy;
+            if constexpr (NP == 8) {
+                const double tt = sd[0] + sd[4];
+                sd[6] = -(tt * xh);
+                sd[7] = -(tt * yh);
+            }
+#pragma unroll
+            for (int p = 0; p < NP; p++) c[p] = g * sd[p];
+            c[NP] = av;
+            c[NP + 1] = 1.0;
+#pragma unroll
+            for (int p = 0; p < NQ; p++) {
+#pragma unroll
+                for (int q = p; q < NQ; q++) add(align_pair(NQ, p, q), c[p] * c[q]);
+                add(NH + p, c[p] * r);
+            }
+            add(NH + NQ, r * r);
+            add(NH + NQ + 1, 1.0);
+        }
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            am[k] = a0[k];
+            a0[k] = ap[k];
+        }
+        t0 = tn;
+    }
+#pragma unroll
+    for (int stride = kAlignTileW / 2; stride >= 1; stride >>= 1)
+#pragma unroll
+        for (int k = 0; k < NK; k++) acc[k] = acc[k] + __shfl_down(acc[k], (unsigned)stride, 64);
+    if (lane == 0) {
+        double *__restrict__ out = a.partial + (size_t)s * a.pstride + (size_t)tile * NS + K0;
+#pragma unroll
+        for (int k = 0; k < NK; k++) out[k] = acc[k];
+    }
+}
+
+// ---- the photometric sums: grid (tiles, min(S, 65535)), block 64 * align_photo_waves(NP) ----
+template <class PIX, int NP>
+__global__ __launch_bounds__(64 * align_photo_waves(NP)) void k_align_reduce_photo(AlignPhotoReduceArgs pa)
+{
+    constexpr int NS = align_sums(NP + 2);
+    constexpr int NW = align_photo_waves(NP);
+    const int lane = (int)(threadIdx.x & 63);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int tile = (int)blockIdx.x;
+    for (int s = blockIdx.y; s < pa.r.S; s += gridDim.y) {
+        const int flag = pa.r.state[s].flag;
+        if (flag == kAlignDead || (flag == kAlignFrozen && pa.r.skip_frozen)) continue;
+        if constexpr (NW == 1) {
+            align_photo_tile<PIX, NP, 0, NS>(pa, s, lane, tile);
+        } else {
+            constexpr int cut = (NS + 1) / 2;
+            if (wave == 0)
+                align_photo_tile<PIX, NP, 0, cut>(pa, s, lane, tile);
+            else
+                align_photo_tile<PIX, NP, cut, NS>(pa, s, lane, tile);
+        }
+    }
+}
+
+// ---- the photometric update: grid (min(S, 65535)), block 64 ----
+// k_align_update is to stay instruction for instruction what it is, so its serial part is repeated here, not shared with it
+struct AlignPhotoUpdateArgs {
+    AlignUpdateArgs u;
+    double *photo;       // [S][2]
+    float *photo_out;    // [S][2], kAlignLast
+};
+
+template <int NP>
+__global__ __launch_bounds__(64) void k_align_update_photo(AlignPhotoUpdateArgs pa)
+{
+    constexpr int NQ = NP + 2;
+    constexpr int NS = align_sums(NQ);
+    constexpr int NH = NQ * (NQ + 1) / 2;
+    constexpr int NC = NP == 8 ? 9 : 6;
+    __shared__ double sum[NS];
+    const AlignUpdateArgs &a = pa.u;
+    const int lane = (int)threadIdx.x;
+    for (int s = blockIdx.x; s < a.S; s += gridDim.x) {
+        AlignState *__restrict__ st = a.state + s;
+        const int flag = st->flag;
+        const bool summed = flag == kAlignLive || (flag == kAlignFrozen && a.mode != kAlignIterate);
+        __syncthreads();   // sum is rewritten
+        if (summed)
+            for (int k = lane; k < NS; k += 64) {
+                const double *__restrict__ p = a.partial + (size_t)s * a.pstride + k;
+                double t = 0.0;
+                for (int i = 0; i < a.tiles; i++) t = t + p[(size_t)i * NS];
+                sum[k] = t;
+            }
+        __syncthreads();
+        double m[9];
+        for (int k = 0; k < 9; k++) m[k] = st->m[k];
+        double g = pa.photo[2 * (size_t)s], b = pa.photo[2 * (size_t)s + 1];
+        int accepted = st->accepted;
+        const double e = summed ? sum[NH + NQ] : 0.0, cnt = summed ? sum[NH + NQ + 1] : 0.0;
+        if (a.mode == kAlignLast) {
+            if (lane != 0) continue;
+            const float *__restrict__ in = a.model_in + (size_t)NC * s;
+            float *__restrict__ out = a.model_out + (size_t)NC * s;
+            double *__restrict__ stats = a.stats + 4 * (size_t)s;
+            const double before = st->before, after = e / cnt;
+            int status = 1;
+            if (flag == kAlignDead || accepted == 0) status = 0;
+            else if (!(after <= before)) status = 2;
+            for (int k = 0; k < NC; k++) {
+                const float v = __double2float_rn(NP == 8 ? m[k] / m[8] : m[k]);
+                out[k] = status == 1 ? v : in[k];
+            }
+            pa.photo_out[2 * (size_t)s] = status == 1 ? __double2float_rn(g) : 1.0f;
+            pa.photo_out[2 * (size_t)s + 1] = status == 1 ? __double2float_rn(b) : 0.0f;
+            a.status_out[s] = status;
+            const bool dead = flag == kAlignDead;
+            stats[0] = dead ? 0.0 : before;
+            stats[1] = dead ? 0.0 : after;
+            stats[2] = dead ? 0.0 : cnt / (double)((long long)a.W * (long long)a.H);
+            stats[3] = (double)accepted;
+            continue;
+        }
+        if (flag != kAlignLive) continue;
+        const double sx = (double)a.w / (double)a.W, sy = (double)a.h / (double)a.H;
+        bool frozen = false;
+        if (a.mode == kAlignFirst) {
+            if (lane == 0) st->before = e / cnt;
+        } else {
+            frozen = cnt < a.min_count;
+            double G[NQ][NQ + 1], q[NQ];
+#pragma unroll
+            for (int i = 0; i < NQ; i++) {
+#pragma unroll
+                for (int j = i; j < NQ; j++) {
+                    G[i][j] = sum[align_pair(NQ, i, j)];
+                    G[j][i] = G[i][j];
+                }
+                G[i][NQ] = sum[NH + i];
+            }
+            frozen = !align_eliminate<NQ>(G, q) || frozen;
+            const double Wm1 = (double)(a.w - 1), Hm1 = (double)(a.h - 1);
+            const double cx = Wm1 / 2.0, cy = Hm1 / 2.0, sc = (double)max(a.w, a.h) / 2.0;
+            double P[9];
+#pragma unroll
+            for (int k = 0; k < 9; k++) P[k] = 0.0;
+#pragma unroll
+            for (int k = 0; k < NP; k++) P[k] = -(q[k] / sc);
+            double A[9], D[9];
+#pragma unroll
+            for (int r = 0; r < 3; r++) {
+                A[3 * r] = P[3 * r] / sc;
+                A[3 * r + 1] = P[3 * r + 1] / sc;
+                A[3 * r + 2] = P[3 * r + 2] - (A[3 * r] * cx + A[3 * r + 1] * cy);
+            }
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                D[c] = sc * A[c] + cx * A[6 + c];
+                D[3 + c] = sc * A[3 + c] + cy * A[6 + c];
+                D[6 + c] = A[6 + c];
+            }
+            D[0] = D[0] + 1.0;
+            D[4] = D[4] + 1.0;
+            D[8] = D[8] + 1.0;
+            const double adj[9] = {D[4] * D[8] - D[5] * D[7], D[2] * D[7] - D[1] * D[8], D[1] * D[5] - D[2] * D[4],
+                                   D[5] * D[6] - D[3] * D[8], D[0] * D[8] - D[2] * D[6], D[2] * D[3] - D[0] * D[5],
+                                   D[3] * D[7] - D[4] * D[6], D[1] * D[6] - D[0] * D[7], D[0] * D[4] - D[1] * D[3]};
+            double I[9], N[9];
+#pragma unroll
+            for (int k = 0; k < 9; k++) I[k] = adj[k] / adj[8];
+            bool ok = true;
+#pragma unroll
+            for (int r = 0; r < 3; r++)
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    N[3 * r + c] = (m[3 * r] * I[c] + m[3 * r + 1] * I[3 + c]) + m[3 * r + 2] * I[6 + c];
+                    ok = ok && __builtin_isfinite(N[3 * r + c]);
+                }
+            ok = ok && (N[6] * 0.0 + N[7] * 0.0) + N[8] > 0.0 && (N[6] * Wm1 + N[7] * 0.0) + N[8] > 0.0 &&
+                 (N[6] * Wm1 + N[7] * Hm1) + N[8] > 0.0 && (N[6] * 0.0 + N[7] * Hm1) + N[8] > 0.0;
+            const double gn = g + q[NP], bn = b + q[NP + 1];
+            ok = ok && __builtin_isfinite(gn) && __builtin_isfinite(bn) && gn > 0.0;
+            frozen = frozen || !ok;
+            if (!frozen) {
+#pragma unroll
+                for (int k = 0; k < 9; k++) m[k] = N[k];
+                g = gn;
+                b = bn;
+                accepted++;
+            }
+            if (frozen || a.last) align_from_level(m, sx, sy);
+        }
+        if (!frozen && a.nh > 0) align_to_level(m, (double)a.nw / (double)a.W, (double)a.nh / (double)a.H);
+        if (lane == 0) {
+            for (int k = 0; k < 9; k++) st->m[k] = m[k];
+            st->accepted = accepted;
+            st->flag = frozen ? kAlignFrozen : kAlignLive;
+            pa.photo[2 * (size_t)s] = g;
+            pa.photo[2 * (size_t)s + 1] = b;
+        }
+    }
+}
+
 }  // namespace oflk

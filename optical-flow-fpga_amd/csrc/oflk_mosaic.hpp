@@ -198,9 +198,17 @@ __device__ __forceinline__ bool mosaic_touches(const double *__restrict__ m, dou
 
 enum { kMosaicMean = 0, kMosaicFeather = 1, kMosaicFirst = 2, kMosaicLast = 3 };
 
+// the exposure-compensated form's arguments: frame f's sample s enters the blend as eg_f * f64(s) + eb_f
+template <class PIX>
+struct MosaicExposureArgs : MosaicArgs<PIX> {
+    const double *exposure;   // [F][2]: (eg, eb)
+};
+
 // ---- accumulate: grid (tiles_x * ceil(Hc / kMosaicBlockH)), block 256 ----
-template <class PIX, int BLEND>
-__global__ __launch_bounds__(256) void k_mosaic_accumulate(MosaicArgs<PIX> a)
+// EXPOSURE: ARGS is MosaicExposureArgs and the sample is taken to the anchor's exposure first, one multiply and one add, each
+// rounded; everything else is the plain form's, whose instantiations keep their code and their kernel arguments
+template <class PIX, int BLEND, bool EXPOSURE = false, class ARGS = MosaicArgs<PIX>>
+__global__ __launch_bounds__(256) void k_mosaic_accumulate(ARGS a)
 {
     const int lane = (int)(threadIdx.x & 63);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -245,6 +253,11 @@ __global__ __launch_bounds__(256) void k_mosaic_accumulate(MosaicArgs<PIX> a)
             const double m0 = m[0], m2 = m[2], m3 = m[3], m5 = m[5], m6 = m[6], m8 = m[8];
             const double bx1 = m[1] * fy, by1 = m[4] * fy, bw = m[7] * fy;
             const PIX *__restrict__ img = a.in + (size_t)f * plane;
+            [[maybe_unused]] double eg = 1.0, eb = 0.0;
+            if constexpr (EXPOSURE) {
+                eg = a.exposure[2 * (size_t)f];
+                eb = a.exposure[2 * (size_t)f + 1];
+            }
 #pragma unroll
             for (int k = 0; k < kMosaicPx; k++) {
                 const double fx = fxk[k];
@@ -257,7 +270,8 @@ __global__ __launch_bounds__(256) void k_mosaic_accumulate(MosaicArgs<PIX> a)
                 const BilinearTaps t = bilinear_taps(a.H, a.W, ys, xs);
                 const float s = bilinear_finish(t, ld_pix<PIX>(img, (unsigned)t.i00), ld_pix<PIX>(img, (unsigned)t.i01),
                                                 ld_pix<PIX>(img, (unsigned)t.i10), ld_pix<PIX>(img, (unsigned)t.i11));
-                const double sd = (double)s;
+                double sd = (double)s;
+                if constexpr (EXPOSURE) sd = eg * sd + eb;
                 if constexpr (BLEND == kMosaicMean) {
                     sum[k] = ok ? sum[k] + sd : sum[k];
                     wsum[k] = ok ? wsum[k] + 1.0 : wsum[k];

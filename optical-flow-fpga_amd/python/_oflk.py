@@ -149,6 +149,10 @@ SIGNATURES = {
     "oflk_mosaic_composite_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [_f64p, _vp] + [ctypes.c_int] * 5 + [_vp, _i32p]),
     "oflk_mosaic_sequence": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_uint, ctypes.c_int, ctypes.c_double, ctypes.c_int, _f32p, ctypes.c_size_t, _i32p, _i32p, _f64p, _vp, _vp, _f32p, _i32p]),
     "oflk_mosaic_sequence_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_uint, ctypes.c_int, ctypes.c_double, ctypes.c_int, _vp, ctypes.c_size_t, _i32p, _i32p, _f64p, _vp, _vp, _f32p, _i32p]),
+    "oflk_mosaic_accumulate_exposure": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_vp, _vp, _vp] + [ctypes.c_int] * 5 + [_vp, ctypes.c_size_t, _vp]),
+    "oflk_mosaic_composite_exposure_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 3 + [_f64p, _vp, _f64p] + [ctypes.c_int] * 5 + [_f32p, _i32p]),
+    "oflk_mosaic_composite_exposure_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [_f64p, _vp, _f64p] + [ctypes.c_int] * 5 + [_vp, _i32p]),
+    "oflk_exposure_chain_host": (ctypes.c_int, [_f32p, _i32p, ctypes.c_int, ctypes.c_int, _f64p]),
     "oflk_align_workspace": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_size_t)]),
     "oflk_align_refine": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 7 + [ctypes.c_float, _vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp]),
     "oflk_align_sequence": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [ctypes.c_float, _vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp]),
@@ -156,6 +160,13 @@ SIGNATURES = {
     "oflk_align_refine_host_u8": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p]),
     "oflk_align_sequence_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p]),
     "oflk_align_sequence_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p]),
+    "oflk_align_photo_workspace": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_size_t)]),
+    "oflk_align_refine_photo": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 7 + [ctypes.c_float, _vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp]),
+    "oflk_align_sequence_photo": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [ctypes.c_float, _vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp]),
+    "oflk_align_refine_photo_host": (ctypes.c_int, [_f32p, _f32p] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p, _f32p]),
+    "oflk_align_refine_photo_host_u8": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p, _f32p]),
+    "oflk_align_sequence_photo_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p, _f32p]),
+    "oflk_align_sequence_photo_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p, _f32p]),
     "oflk_stabilize_trajectory_ring": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 4 + [_f64p, ctypes.c_int, _vp, _vp, _vp]),
     "oflk_stabilizer_create": (ctypes.c_int, [ctypes.POINTER(_vp)] + [ctypes.c_int] * 7 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int]),
     "oflk_stabilizer_destroy": (ctypes.c_int, [_vp]),
@@ -976,9 +987,15 @@ def mosaic_canvas(box: np.ndarray, dropped: np.ndarray):
 
 
 def mosaic_accumulate(d_frames: int, F: int, H: int, W: int, d_map: int, d_skip: int, x0: int, y0: int, Hc: int, Wc: int, blend: int,
-                      d_state: int, state_bytes: int, u8: bool = False, stream: int = 0) -> None:
+                      d_state: int, state_bytes: int, u8: bool = False, stream: int = 0, d_exposure: Optional[int] = None) -> None:
     """oflk_mosaic_accumulate on device pointers: adds d_frames [F][H][W] (float32, or uint8 with u8) under d_map [F][9] float64
-    (d_skip [F] uint8 or 0) to the canvas state d_state; asynchronous."""
+    (d_skip [F] uint8 or 0) to the canvas state d_state; asynchronous.  d_exposure given: oflk_mosaic_accumulate_exposure with
+    the frames' (eg, eb) [F][2] float64."""
+    if d_exposure is not None:
+        check(lib().oflk_mosaic_accumulate_exposure(d_frames or None, int(bool(u8)), int(F), int(H), int(W), d_map or None,
+                                                    d_skip or None, d_exposure or None, int(x0), int(y0), int(Hc), int(Wc),
+                                                    int(blend), d_state or None, int(state_bytes), stream))
+        return
     check(lib().oflk_mosaic_accumulate(d_frames or None, int(bool(u8)), int(F), int(H), int(W), d_map or None, d_skip or None, int(x0),
                                        int(y0), int(Hc), int(Wc), int(blend), d_state or None, int(state_bytes), stream))
 
@@ -990,17 +1007,33 @@ def mosaic_resolve(d_state: int, Hc: int, Wc: int, d_out: int, d_count: int = 0,
 
 
 def mosaic_composite_host(frames: np.ndarray, maps: np.ndarray, skip: Optional[np.ndarray], x0: int, y0: int, Hc: int, Wc: int,
-                          blend: int, count: bool = False):
+                          blend: int, count: bool = False, exposure: Optional[np.ndarray] = None):
     """oflk_mosaic_composite_host[_u8]: contiguous (F, H, W) float32 or uint8 frames, (F, 9) float64 maps and optional (F,) uint8
-    skip flags in; the (Hc, Wc) mosaic and, when asked for, the int32 count (else None) out"""
+    skip flags in; the (Hc, Wc) mosaic and, when asked for, the int32 count (else None) out.  exposure given (contiguous (F, 2)
+    float64): oflk_mosaic_composite_exposure_host[_u8]"""
     F, H, W = frames.shape
     u8 = frames.dtype == np.uint8
     out = np.empty((Hc, Wc), frames.dtype)
     cnt = np.empty((Hc, Wc), np.int32) if count else None
+    if exposure is not None:
+        fn = lib().oflk_mosaic_composite_exposure_host_u8 if u8 else lib().oflk_mosaic_composite_exposure_host
+        check(fn(frames.ctypes.data if u8 else ptr(frames), F, H, W, _f64(maps), None if skip is None else skip.ctypes.data,
+                 _f64(exposure), int(x0), int(y0), int(Hc), int(Wc), int(blend), out.ctypes.data if u8 else ptr(out),
+                 None if cnt is None else cnt.ctypes.data_as(_i32p)))
+        return out, cnt
     fn = lib().oflk_mosaic_composite_host_u8 if u8 else lib().oflk_mosaic_composite_host
     check(fn(frames.ctypes.data if u8 else ptr(frames), F, H, W, _f64(maps), None if skip is None else skip.ctypes.data, int(x0), int(y0),
              int(Hc), int(Wc), int(blend), out.ctypes.data if u8 else ptr(out), None if cnt is None else cnt.ctypes.data_as(_i32p)))
     return out, cnt
+
+
+def exposure_chain_host(photo: np.ndarray, status: Optional[np.ndarray], T: int, anchor: int) -> np.ndarray:
+    """oflk_exposure_chain_host (host only): contiguous float32 (T-1, 2) step (g, b) and optional int32 (T-1,) statuses in; the
+    frames' (eg, eb) (T, 2) float64 out"""
+    out = np.empty((T, 2), np.float64)
+    check(lib().oflk_exposure_chain_host(ptr(photo) if T > 1 else None,
+                                         None if status is None or T < 2 else status.ctypes.data_as(_i32p), int(T), int(anchor), _f64(out)))
+    return out
 
 
 ALIGN_KINDS = {"affine": 0, "homography": 1}
@@ -1019,18 +1052,26 @@ def check_align_params(kind, levels, iterations, min_share: float) -> Tuple[int,
     return ALIGN_KINDS[kind], int(levels), int(iterations), ms
 
 
-def align_workspace(S: int, H: int, W: int, levels: int, model: int) -> int:
-    """bytes of the workspace of oflk_align_refine for S steps (oflk_align_sequence: S = T - 1)"""
+def align_workspace(S: int, H: int, W: int, levels: int, model: int, photometric: bool = False) -> int:
+    """bytes of the workspace of oflk_align_refine for S steps (oflk_align_sequence: S = T - 1); photometric: of
+    oflk_align_refine_photo (oflk_align_photo_workspace)"""
     n = ctypes.c_size_t(0)
-    check(lib().oflk_align_workspace(int(S), int(H), int(W), int(levels), int(model), ctypes.byref(n)))
+    check((lib().oflk_align_photo_workspace if photometric else lib().oflk_align_workspace)(int(S), int(H), int(W), int(levels), int(model), ctypes.byref(n)))
     return int(n.value)
 
 
 def align_refine(d_a: int, d_b: int, S: int, H: int, W: int, levels: int, iterations: int, model: int, min_share: float,
                  d_model_in: int, d_status_in: int, d_workspace: int, workspace_bytes: int, d_model_out: int, d_status_out: int,
-                 d_stats: int, u8: bool = False, stream: int = 0) -> None:
+                 d_stats: int, u8: bool = False, stream: int = 0, d_photo_out: Optional[int] = None) -> None:
     """oflk_align_refine on device pointers: d_a, d_b [S][H][W] (float32, or uint8 with u8), d_model_in / d_model_out [S][6 | 9]
-    float32, d_status_in [S] int32 or 0, d_status_out [S] int32, d_stats [S][4] float64; asynchronous."""
+    float32, d_status_in [S] int32 or 0, d_status_out [S] int32, d_stats [S][4] float64; asynchronous.  d_photo_out given:
+    oflk_align_refine_photo with (g, b) [S][2] float32 out and a workspace of align_workspace(..., photometric=True) bytes."""
+    if d_photo_out is not None:
+        check(lib().oflk_align_refine_photo(d_a or None, d_b or None, int(bool(u8)), int(S), int(H), int(W), int(levels),
+                                            int(iterations), int(model), float(min_share), d_model_in or None, d_status_in or None,
+                                            d_workspace or None, int(workspace_bytes), d_model_out or None, d_status_out or None,
+                                            d_stats or None, d_photo_out or None, stream))
+        return
     check(lib().oflk_align_refine(d_a or None, d_b or None, int(bool(u8)), int(S), int(H), int(W), int(levels), int(iterations),
                                   int(model), float(min_share), d_model_in or None, d_status_in or None, d_workspace or None,
                                   int(workspace_bytes), d_model_out or None, d_status_out or None, d_stats or None, stream))
@@ -1038,19 +1079,25 @@ def align_refine(d_a: int, d_b: int, S: int, H: int, W: int, levels: int, iterat
 
 def align_sequence(d_frames: int, T: int, H: int, W: int, levels: int, iterations: int, model: int, min_share: float,
                    d_model_in: int, d_status_in: int, d_workspace: int, workspace_bytes: int, d_model_out: int, d_status_out: int,
-                   d_stats: int, u8: bool = False, stream: int = 0) -> None:
+                   d_stats: int, u8: bool = False, stream: int = 0, d_photo_out: Optional[int] = None) -> None:
     """oflk_align_sequence on device pointers: the T-1 steps t -> t+1 of d_frames [T][H][W], with align_refine's other
-    arguments for S = T - 1; asynchronous."""
+    arguments for S = T - 1; asynchronous.  d_photo_out given: oflk_align_sequence_photo."""
+    if d_photo_out is not None:
+        check(lib().oflk_align_sequence_photo(d_frames or None, int(bool(u8)), int(T), int(H), int(W), int(levels), int(iterations),
+                                              int(model), float(min_share), d_model_in or None, d_status_in or None,
+                                              d_workspace or None, int(workspace_bytes), d_model_out or None, d_status_out or None,
+                                              d_stats or None, d_photo_out or None, stream))
+        return
     check(lib().oflk_align_sequence(d_frames or None, int(bool(u8)), int(T), int(H), int(W), int(levels), int(iterations), int(model),
                                     float(min_share), d_model_in or None, d_status_in or None, d_workspace or None,
                                     int(workspace_bytes), d_model_out or None, d_status_out or None, d_stats or None, stream))
 
 
 def align_host(a: np.ndarray, b: Optional[np.ndarray], model_in: np.ndarray, status_in: Optional[np.ndarray], levels: int,
-               iterations: int, model: int, min_share: float):
+               iterations: int, model: int, min_share: float, photometric: bool = False):
     """oflk_align_refine_host[_u8] (b given: contiguous (S, H, W) arrays of one type) or oflk_align_sequence_host[_u8] (b None:
     a holds the S + 1 frames); contiguous float32 (S, 6 | 9) models and optional int32 (S,) statuses in; (model (S, nc) float32,
-    status (S,) int32, stats (S, 4) float64) out"""
+    status (S,) int32, stats (S, 4) float64) out.  photometric: the _photo_ forms, with (g, b) (S, 2) float32 as a fourth output"""
     F, H, W = a.shape
     S = F if b is not None else F - 1
     u8 = a.dtype == np.uint8
@@ -1059,13 +1106,17 @@ def align_host(a: np.ndarray, b: Optional[np.ndarray], model_in: np.ndarray, sta
     pix = (lambda x: x.ctypes.data) if u8 else ptr
     tail = (int(H), int(W), int(levels), int(iterations), int(model), float(min_share), ptr(model_in),
             None if status_in is None else status_in.ctypes.data_as(_i32p), ptr(out), st.ctypes.data_as(_i32p), _f64(stats))
+    photo = None
+    if photometric:
+        photo = np.empty((S, 2), np.float32)
+        tail += (ptr(photo),)
+    name = ("oflk_align_refine" if b is not None else "oflk_align_sequence") + ("_photo" if photometric else "") + "_host" + ("_u8" if u8 else "")
+    fn = getattr(lib(), name)
     if b is not None:
-        fn = lib().oflk_align_refine_host_u8 if u8 else lib().oflk_align_refine_host
         check(fn(pix(a), pix(b), S, *tail))
     else:
-        fn = lib().oflk_align_sequence_host_u8 if u8 else lib().oflk_align_sequence_host
         check(fn(pix(a), F, *tail))
-    return out, st, stats
+    return (out, st, stats, photo) if photometric else (out, st, stats)
 
 
 class Tracker:

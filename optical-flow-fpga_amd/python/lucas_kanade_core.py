@@ -506,7 +506,29 @@ def mosaic_chain(model, status, shape, anchor: int = 0, extent=None) -> MosaicCh
     return MosaicChain(fr.reshape(-1, 3, 3), to.reshape(-1, 3, 3), box, held.astype(bool), drop.astype(bool), (x0, y0), (Hc, Wc))
 
 
-def mosaic_composite(frames, maps, canvas_shape, origin=(0, 0), skip=None, blend: str = "mean", return_count: bool = False):
+def exposure_chain(gain, bias, status=None, anchor: int = 0) -> np.ndarray:
+    """The step gains and biases of a photometric refinement (PhotometricAlignment.gain, .bias of sequence_refine_alignment)
+    composed from frame `anchor`: (T, 2) float64 (eg, eb) with v_anchor = eg[f] v_f + eb[f], what mosaic_composite takes as
+    `exposure`.  gain, bias: (T-1,) -- step t says that frame t+1 looks like gain[t] frame t + bias[t]; status: (T-1,) or None.
+    A step with status 0, with a value that is not finite or with gain <= 0 is held, that is taken as (1, 0).  Host only; the
+    statement is in include/oflk.h."""
+    g, b = np.asarray(gain, np.float32).reshape(-1), np.asarray(bias, np.float32).reshape(-1)
+    if g.shape != b.shape:
+        raise ValueError(f"gain and bias must have one shape, got {np.shape(gain)} and {np.shape(bias)}")
+    S = g.size
+    if isinstance(anchor, bool) or int(anchor) != anchor or not 0 <= int(anchor) <= S:
+        raise ValueError(f"anchor must be an integer in [0, {S}], got {anchor!r}")
+    st = None
+    if status is not None:
+        st = np.asarray(status)
+        if st.shape != (S,):
+            raise ValueError(f"status must have shape {(S,)}, got {st.shape}")
+        st = np.ascontiguousarray(st != 0, np.int32)
+    return _oflk.exposure_chain_host(np.ascontiguousarray(np.stack([g, b], axis=1)), st, S + 1, int(anchor))
+
+
+def mosaic_composite(frames, maps, canvas_shape, origin=(0, 0), skip=None, blend: str = "mean", return_count: bool = False,
+                     exposure=None):
     """Blend frames onto one canvas, on the GPU.  Canvas pixel (x, y) has the coordinates (origin[0] + x, origin[1] + y); frame
     f covers it where maps[f] (3 x 3, canvas coordinates to frame f's, e.g. MosaicChain.from_anchor) takes it inside the
     frame, and contributes its bilinear sample there.  blend: "mean"; "feather" (each sample weighted by one plus its distance
@@ -516,10 +538,13 @@ def mosaic_composite(frames, maps, canvas_shape, origin=(0, 0), skip=None, blend
     cover each pixel.
 
     A 4-D uint8 array (F, H, W, C), C = 3 or 4, is a batch of interleaved colour frames: every channel's plane is blended by a
-    call of its own under the same maps and the canvases are stacked to (Hc, Wc, C); the count is the one count of them all."""
+    call of its own under the same maps and the canvases are stacked to (Hc, Wc, C); the count is the one count of them all.
+
+    exposure: None, or (F, 2) float64 (eg, eb), e.g. of exposure_chain: frame f's sample s enters the blend as eg[f] s + eb[f]
+    (exposure compensation; colour frames: the same pair for every channel)."""
     if _oflk.is_packed(frames):
         arr = _oflk.as_packed(frames)
-        planes = [mosaic_composite(np.ascontiguousarray(arr[..., c]), maps, canvas_shape, origin, skip, blend, True)
+        planes = [mosaic_composite(np.ascontiguousarray(arr[..., c]), maps, canvas_shape, origin, skip, blend, True, exposure)
                   for c in range(arr.shape[-1])]
         canvas = np.stack([p[0] for p in planes], axis=-1)
         return (canvas, planes[0][1]) if return_count else canvas
@@ -544,7 +569,13 @@ def mosaic_composite(frames, maps, canvas_shape, origin=(0, 0), skip=None, blend
         if sk.shape != (F,):
             raise ValueError(f"skip must have shape {(F,)}, got {sk.shape}")
         sk = np.ascontiguousarray(sk != 0, np.uint8)
-    out, cnt = _oflk.mosaic_composite_host(arr, m.reshape(F, 9), sk, int(origin[0]), int(origin[1]), Hc, Wc, code, bool(return_count))
+    ex = None
+    if exposure is not None:
+        ex = np.ascontiguousarray(exposure, np.float64)
+        if ex.shape != (F, 2):
+            raise ValueError(f"exposure must have shape {(F, 2)}, got {ex.shape}")
+    out, cnt = _oflk.mosaic_composite_host(arr, m.reshape(F, 9), sk, int(origin[0]), int(origin[1]), Hc, Wc, code, bool(return_count),
+                                           ex)
     return (out, cnt) if return_count else out
 
 
@@ -553,6 +584,16 @@ class Alignment(NamedTuple):
     model: np.ndarray    # (S, 3, 3) (homography, model[2, 2] == 1) or (S, 2, 3) (affine) float32; the input model where status != 1
     status: np.ndarray   # (S,) int32: 1 refined; 0 not refined (input status 0, not finite, or frozen before an update); 2 rejected
     stats: np.ndarray    # (S, 4) float64: mean squared residual before and after, counted share of the frame, accepted updates
+
+
+class PhotometricAlignment(NamedTuple):
+    """Step models refined together with a gain and a bias (refine_alignment, sequence_refine_alignment with photometric=True):
+    b under the model looks like gain a + bias."""
+    model: np.ndarray    # as Alignment.model
+    status: np.ndarray   # as Alignment.status
+    stats: np.ndarray    # as Alignment.stats, the residuals being b(M x) - (gain a(x) + bias)
+    gain: np.ndarray     # (S,) float32; 1 where status != 1
+    bias: np.ndarray     # (S,) float32; 0 where status != 1
 
 
 def _align_models(model, status, S: int, kind: str):
@@ -569,13 +610,16 @@ def _align_models(model, status, S: int, kind: str):
     return m.reshape(S, nc), st
 
 
-def _alignment(out, st, stats, kind: str, single: bool) -> Alignment:
+def _alignment(out, st, stats, kind: str, single: bool, photo=None):
     out = out.reshape((-1, 3, 3) if kind == "homography" else (-1, 2, 3))
+    if photo is not None:
+        g, b = np.ascontiguousarray(photo[:, 0]), np.ascontiguousarray(photo[:, 1])
+        return PhotometricAlignment(out[0], int(st[0]), stats[0], g[0], b[0]) if single else PhotometricAlignment(out, st, stats, g, b)
     return Alignment(out[0], int(st[0]), stats[0]) if single else Alignment(out, st, stats)
 
 
 def refine_alignment(a, b, model, status=None, kind: str = "homography", levels: int = 3, iterations: int = 5,
-                     min_share: float = 0.25) -> Alignment:
+                     min_share: float = 0.25, photometric: bool = False):
     """Refine step models on the pixels themselves, on the GPU: inverse-compositional Lucas-Kanade registration of frame b to
     the template a over the whole frame, coarse to fine, `iterations` Gauss-Newton updates on each of `levels` pyramid levels.
 
@@ -585,6 +629,9 @@ def refine_alignment(a, b, model, status=None, kind: str = "homography", levels:
     refined (fewer than `min_share` of the pixels land inside b, a flat template, a singular system) keeps its input model
     with status 0, and one whose mean squared residual grew keeps it with status 2.  The same inputs give the same bytes; the
     statement is in include/oflk.h.
+
+    photometric=True estimates a gain and a bias with every step (b under the model looks like gain a + bias: an exposure
+    change between the frames) and returns a PhotometricAlignment; a step also stops when its gain would leave (0, inf).
     """
     code, L, n, ms = _oflk.check_align_params(kind, levels, iterations, min_share)
     single = isinstance(a, np.ndarray) and a.ndim == 2
@@ -593,16 +640,23 @@ def refine_alignment(a, b, model, status=None, kind: str = "homography", levels:
     if fa.shape != fb.shape or ua != ub:
         raise ValueError(f"a and b must have one shape and type, got {fa.shape} {fa.dtype} and {fb.shape} {fb.dtype}")
     m, st = _align_models(model, status, fa.shape[0], kind)
+    if photometric:
+        out, so, stats, photo = _oflk.align_host(fa, fb, m, st, L, n, code, ms, True)
+        return _alignment(out, so, stats, kind, single, photo)
     return _alignment(*_oflk.align_host(fa, fb, m, st, L, n, code, ms), kind, single)
 
 
 def sequence_refine_alignment(frames, model, status=None, kind: str = "homography", levels: int = 3, iterations: int = 5,
-                              min_share: float = 0.25) -> Alignment:
+                              min_share: float = 0.25, photometric: bool = False):
     """refine_alignment on the T-1 steps t -> t+1 of frames (T, H, W): model[t] (e.g. of tracks_homography or tracks_motion)
-    maps frame t's coordinates to frame t+1's.  Every frame's pyramid is built once.  Returns a batched Alignment."""
+    maps frame t's coordinates to frame t+1's.  Every frame's pyramid is built once.  Returns a batched Alignment, or with
+    photometric=True a batched PhotometricAlignment."""
     code, L, n, ms = _oflk.check_align_params(kind, levels, iterations, min_share)
     arr, _ = _oflk.as_frames(frames)
     if arr.shape[0] < 2:
         raise ValueError(f"a sequence needs at least two frames, got {arr.shape[0]}")
     m, st = _align_models(model, status, arr.shape[0] - 1, kind)
+    if photometric:
+        out, so, stats, photo = _oflk.align_host(arr, None, m, st, L, n, code, ms, True)
+        return _alignment(out, so, stats, kind, False, photo)
     return _alignment(*_oflk.align_host(arr, None, m, st, L, n, code, ms), kind, False)

@@ -30,8 +30,9 @@ import numpy as np
 import numpy.typing as npt
 
 import _oflk
-from lucas_kanade_core import (Alignment, Homography, MosaicChain, Motion, Trajectory, estimate_homography,  # noqa: F401
-                               estimate_motion, lucas_kanade_single_scale, mosaic_chain, mosaic_composite, refine_alignment,
+from lucas_kanade_core import (Alignment, Homography, MosaicChain, Motion, PhotometricAlignment, Trajectory,  # noqa: F401
+                               estimate_homography, estimate_motion, exposure_chain, lucas_kanade_single_scale, mosaic_chain,
+                               mosaic_composite, refine_alignment,
                                rgb_to_luma, sequence_refine_alignment, stabilize_trajectory, tracks_homography, tracks_motion, warp_affine,
                                warp_perspective)
 
@@ -477,7 +478,7 @@ def lucas_kanade_pyramidal_sequence_stabilize(frames, max_corners: int, detect_e
                                               num_levels: int = 3, window_size: int = 5, num_iterations: int = 3,
                                               alpha: float = 0.01, beta: float = 0.5, max_residual: float = 4.0,
                                               refine_iterations: int = 0, refine_levels: int = 3,
-                                              order: str = "rgb") -> SequenceStabilized:
+                                              order: str = "rgb", refine_photometric: bool = False) -> SequenceStabilized:
     """Frames in, steadied frames out: lucas_kanade_pyramidal_sequence_klt_sparse_replenish on the frames, tracks_motion on
     its rows, stabilize_trajectory on the models and warp_affine of the frames under its maps, in one call whose
     intermediate rows stay in the library.  The frames go up twice, chunk by chunk (once to track, once to warp); nothing
@@ -486,7 +487,9 @@ def lucas_kanade_pyramidal_sequence_stabilize(frames, max_corners: int, detect_e
 
     refine_iterations > 0: the same chain made of its public parts, with sequence_refine_alignment (kind "affine",
     refine_levels levels, refine_iterations iterations each) between the fit and the trajectory: every fitted step is refined
-    on the pixels of its two frames, and a step that cannot be refined keeps the fitted model.
+    on the pixels of its two frames, and a step that cannot be refined keeps the fitted model.  refine_photometric=True
+    (needs refine_iterations > 0) refines every step together with a gain and a bias, for video whose exposure changes; the
+    stabiliser only uses the better models, the frames keep their values.
 
     A 4-D uint8 array (T, H, W, C), C = 3 or 4, is interleaved colour video with R, G and B where `order` ("rgb" or "bgr")
     says: the motion is tracked, fitted and (with refine_iterations) refined on rgb_to_luma of the frames, exactly as this
@@ -494,6 +497,8 @@ def lucas_kanade_pyramidal_sequence_stabilize(frames, max_corners: int, detect_e
     position; .frames then has the input's shape."""
     if isinstance(refine_iterations, bool) or int(refine_iterations) != refine_iterations or int(refine_iterations) < 0:
         raise ValueError(f"refine_iterations must be an integer >= 0, got {refine_iterations!r}")
+    if refine_photometric and int(refine_iterations) == 0:
+        raise ValueError("refine_photometric needs refine_iterations > 0")
     colour = _oflk.is_packed(frames)
     code_order = _oflk.check_colour_order(order)
     if colour:
@@ -504,7 +509,8 @@ def lucas_kanade_pyramidal_sequence_stabilize(frames, max_corners: int, detect_e
                                                                     num_levels, window_size, num_iterations, alpha, beta, max_residual)
         fit = tracks_motion(rows.tracks, rows.visible, rows.born, model, hypotheses, threshold, seed)
         arr, _ = _oflk.as_sequence(grey)
-        al = sequence_refine_alignment(arr, fit.model, fit.status, "affine", refine_levels, int(refine_iterations))
+        al = sequence_refine_alignment(arr, fit.model, fit.status, "affine", refine_levels, int(refine_iterations),
+                                       photometric=bool(refine_photometric))
         tr = stabilize_trajectory(al.model, fit.status, radius, sigma)
         return SequenceStabilized(warp_affine(packed if colour else arr, tr.map), tr.correction, al.model, fit.status, tr.held)
     a, b = _oflk.check_fb_params(alpha, beta)
@@ -656,12 +662,26 @@ class Mosaic(NamedTuple):
     status: np.ndarray      # (T-1,) int32: 1 where a model was found
 
 
+class PhotometricMosaic(NamedTuple):
+    """Result of lucas_kanade_pyramidal_sequence_mosaic with refine_photometric=True: Mosaic's fields, then the exposure."""
+    canvas: np.ndarray
+    count: np.ndarray
+    origin: tuple
+    to_anchor: np.ndarray
+    held: np.ndarray
+    dropped: np.ndarray
+    model: np.ndarray
+    status: np.ndarray
+    exposure: np.ndarray    # (T, 2) float64 (eg, eb): frame t's values entered the blend as eg[t] v + eb[t], the anchor's exposure
+
+
 def lucas_kanade_pyramidal_sequence_mosaic(frames, max_corners: int = 1000, detect_every: int = 4, hypotheses: int = 256,
                                            threshold: float = 1.0, seed: int = 0, quality_level: float = 0.01,
                                            min_distance: float = 10.0, num_levels: int = 3, window_size: int = 5,
                                            num_iterations: int = 3, alpha: float = 0.01, beta: float = 0.5, max_residual: float = 4.0,
                                            anchor: int = 0, extent=None, blend: str = "feather", max_pixels=None,
-                                           refine_iterations: int = 0, refine_levels: int = 3, order: str = "rgb") -> Mosaic:
+                                           refine_iterations: int = 0, refine_levels: int = 3, order: str = "rgb",
+                                           refine_photometric: bool = False):
     """Frames in, one picture out: lucas_kanade_pyramidal_sequence_klt_sparse_replenish on the frames, tracks_homography on its
     rows, mosaic_chain from frame `anchor`, and mosaic_composite of every frame that is not dropped, in one call whose
     intermediate rows stay in the library.  The frames go up twice, chunk by chunk (once to track, once to blend).  The canvas
@@ -672,26 +692,36 @@ def lucas_kanade_pyramidal_sequence_mosaic(frames, max_corners: int = 1000, dete
     refine_levels levels, refine_iterations iterations each) between the fit and the chain, which answers the chain's drift: a
     product of steps fitted to at most max_corners tracks each.
 
+    refine_photometric=True (needs refine_iterations > 0), for video whose exposure changes: every step is refined together
+    with a gain and a bias (sequence_refine_alignment(..., photometric=True)), exposure_chain composes them from the anchor
+    (a step that was not refined counts as no change), and every frame enters the blend at the anchor's exposure
+    (mosaic_composite(..., exposure=...)).  Returns a PhotometricMosaic: Mosaic's fields and .exposure.
+
     A 4-D uint8 array (T, H, W, C), C = 3 or 4, is interleaved colour video (`order`: "rgb" or "bgr"): this call runs on
     rgb_to_luma of the frames for everything but the canvas, and every channel's plane is then blended by mosaic_composite
     under the chain fitted on the luma; .canvas is (Hc, Wc, C), .count the grey call's."""
     if isinstance(refine_iterations, bool) or int(refine_iterations) != refine_iterations or int(refine_iterations) < 0:
         raise ValueError(f"refine_iterations must be an integer >= 0, got {refine_iterations!r}")
+    if refine_photometric and int(refine_iterations) == 0:
+        raise ValueError("refine_photometric needs refine_iterations > 0")
     _oflk.check_colour_order(order)
     if _oflk.is_packed(frames):
         packed = _oflk.as_packed(frames, "(T, H, W, C)")
         m = lucas_kanade_pyramidal_sequence_mosaic(rgb_to_luma(packed, order), max_corners, detect_every, hypotheses, threshold, seed,
                                                    quality_level, min_distance, num_levels, window_size, num_iterations, alpha, beta,
-                                                   max_residual, anchor, extent, blend, max_pixels, refine_iterations, refine_levels)
+                                                   max_residual, anchor, extent, blend, max_pixels, refine_iterations, refine_levels,
+                                                   refine_photometric=refine_photometric)
         ch = mosaic_chain(m.model, m.status, packed.shape[1:3], anchor, extent)
-        canvas = mosaic_composite(packed, ch.from_anchor, m.canvas.shape, m.origin, ch.dropped, blend)
+        canvas = mosaic_composite(packed, ch.from_anchor, m.canvas.shape, m.origin, ch.dropped, blend,
+                                  exposure=m.exposure if refine_photometric else None)
         return m._replace(canvas=canvas)
     if int(refine_iterations) > 0:
         rows = lucas_kanade_pyramidal_sequence_klt_sparse_replenish(frames, max_corners, detect_every, quality_level, min_distance,
                                                                     num_levels, window_size, num_iterations, alpha, beta, max_residual)
         fit = tracks_homography(rows.tracks, rows.visible, rows.born, hypotheses, threshold, seed)
         arr, _ = _oflk.as_sequence(frames)
-        al = sequence_refine_alignment(arr, fit.model, fit.status, "homography", refine_levels, int(refine_iterations))
+        al = sequence_refine_alignment(arr, fit.model, fit.status, "homography", refine_levels, int(refine_iterations),
+                                       photometric=bool(refine_photometric))
         ch = mosaic_chain(al.model, fit.status, arr.shape[1:], anchor, extent)
         Hc, Wc = ch.canvas_shape
         cap = 16 * arr.shape[1] * arr.shape[2] if max_pixels is None else max_pixels
@@ -700,6 +730,10 @@ def lucas_kanade_pyramidal_sequence_mosaic(frames, max_corners: int = 1000, dete
         if Hc * Wc > int(cap):
             raise _oflk.OflkError(_oflk.OFLK_ERR_UNSUPPORTED,
                                   f"the canvas of {Wc} x {Hc} pixels at {ch.origin} exceeds the capacity of {int(cap)} pixels")
+        if refine_photometric:
+            ex = exposure_chain(al.gain, al.bias, al.status == 1, anchor)
+            canvas, cnt = mosaic_composite(arr, ch.from_anchor, (Hc, Wc), ch.origin, ch.dropped, blend, True, exposure=ex)
+            return PhotometricMosaic(canvas, cnt, ch.origin, ch.to_anchor, ch.held, ch.dropped, al.model, fit.status, ex)
         canvas, cnt = mosaic_composite(arr, ch.from_anchor, (Hc, Wc), ch.origin, ch.dropped, blend, True)
         return Mosaic(canvas, cnt, ch.origin, ch.to_anchor, ch.held, ch.dropped, al.model, fit.status)
     a, b = _oflk.check_fb_params(alpha, beta)

@@ -9,6 +9,10 @@ each with the median and min - max over `--steps` windows of `--reps` back-to-ba
               truth, so that every iteration is accepted and none freezes
   copy        a device copy of the bytes an iteration must read (the S templates and the S images), uint8 and float32
   warp        oflk_warp_perspective of the same S images under the same maps: the nearest existing kernel
+  photometric the same measurement of oflk_align_refine_photo (k_align_reduce_photo and k_align_update_photo) and of the plain call
+              in one process on the same steps, and their ratio.  uint8 and float32 frames, affine and homography
+  accumulate  oflk_mosaic_accumulate and oflk_mosaic_accumulate_exposure of 32 frames of 1080p, 8 px apart, onto one canvas, mean
+              and feather blends, uint8 and float32 frames, and their ratio
   sequence    the whole oflk_align_sequence (pyramids, L = 3, n = 5, both residual passes) on T = 129 resident uint8 frames,
               and oflk_tracks_homography on T rows of K = 1000 tracks with 256 hypotheses: the fit it refines
   chain       lucas_kanade_pyramidal_sequence_mosaic (host frames in, picture out) on 16 frames of 120 x 160 with
@@ -145,23 +149,55 @@ def leg(args):
         print(json.dumps({**out, "dtype": args.dtype, "ms": round(med, 3), "ms_min_max": mm, "ns_per_pixel": round(med * 1e6 / (S * H * W), 4)}),
               flush=True)
         return
+    if args.leg == "accumulate":
+        F, dx = 32, 8
+        Hc, Wc = H, W + dx * (F - 1)
+        fr = frames[:F].contiguous()
+        maps = torch.tensor([[1, 0, -dx * f, 0, 1, 0, 0, 0, 1] for f in range(F)], dtype=torch.float64, device=d).contiguous()
+        expo = torch.tensor([[1.0 + 0.01 * f, -0.5 * f] for f in range(F)], dtype=torch.float64, device=d).contiguous()
+        sb = _oflk.mosaic_state_bytes(Hc, Wc)
+        state = torch.zeros(sb, dtype=torch.uint8, device=d)
+        for blend in ("mean", "feather"):
+            code = _oflk.MOSAIC_BLENDS[blend]
+            res = {}
+            for name, ex in (("plain", None), ("exposure", expo.data_ptr())):
+                res[name] = windows(lambda: _oflk.mosaic_accumulate(fr.data_ptr(), F, H, W, maps.data_ptr(), 0, 0, 0, Hc, Wc, code,
+                                                                    state.data_ptr(), sb, u8, st, ex), args.steps, args.reps)
+            print(json.dumps({**out, "S": F, "dtype": args.dtype, "blend": blend, "canvas": [Wc, Hc], "ms_plain": round(res["plain"][0], 3),
+                              "ms_min_max_plain": res["plain"][1], "ms_exposure": round(res["exposure"][0], 3),
+                              "ms_min_max_exposure": res["exposure"][1], "ratio": round(res["exposure"][0] / res["plain"][0], 3)}), flush=True)
+        return
     code = KINDS[args.kind]
     nc = 9 if code else 6
     m0 = [1, 0, -0.5, 0, 1, 0.3, 0, 0, 1][:nc]   # the truth is (-1, 0)
     model = torch.tensor(m0, dtype=torch.float32, device=d).repeat(S, 1).contiguous()
-    nbytes = _oflk.align_workspace(S, H, W, 1, code)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=d)
     mo, so, ss = torch.empty_like(model), torch.empty(S, dtype=torch.int32, device=d), torch.empty((S, 4), dtype=torch.float64, device=d)
-    res = {}
-    for n in (2, 6):
-        res[n] = windows(lambda: _oflk.align_refine(a.data_ptr(), b.data_ptr(), S, H, W, 1, n, code, 0.25, model.data_ptr(), 0, ws.data_ptr(),
-                                                    nbytes, mo.data_ptr(), so.data_ptr(), ss.data_ptr(), u8, st), args.steps, args.reps)
-        accepted = ss[:, 3].cpu().numpy()
-        assert (accepted == n).all(), f"not every iteration was accepted: {accepted}"
-    per = (res[6][0] - res[2][0]) / 4.0
-    print(json.dumps({**out, "dtype": args.dtype, "kind": args.kind, "ms_n2": round(res[2][0], 3), "ms_n6": round(res[6][0], 3),
-                      "ms_min_max_n2": res[2][1], "ms_min_max_n6": res[6][1], "ms_per_iteration": round(per, 3),
-                      "ns_per_pixel": round(per * 1e6 / (S * H * W), 4), "status_1": int((so == 1).sum().item())}), flush=True)
+    po = torch.empty((S, 2), dtype=torch.float32, device=d)
+
+    def iteration(photo):
+        """(ms per iteration, the two windows' results) of the plain or the photometric call"""
+        nbytes = _oflk.align_workspace(S, H, W, 1, code, photo)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=d)
+        res = {}
+        for n in (2, 6):
+            res[n] = windows(lambda: _oflk.align_refine(a.data_ptr(), b.data_ptr(), S, H, W, 1, n, code, 0.25, model.data_ptr(), 0, ws.data_ptr(),
+                                                        nbytes, mo.data_ptr(), so.data_ptr(), ss.data_ptr(), u8, st,
+                                                        po.data_ptr() if photo else None), args.steps, args.reps)
+            accepted = ss[:, 3].cpu().numpy()
+            assert (accepted == n).all(), f"not every iteration was accepted: {accepted}"
+        return (res[6][0] - res[2][0]) / 4.0, res
+
+    per, res = iteration(False)
+    row = {**out, "dtype": args.dtype, "kind": args.kind, "ms_n2": round(res[2][0], 3), "ms_n6": round(res[6][0], 3),
+           "ms_min_max_n2": res[2][1], "ms_min_max_n6": res[6][1], "ms_per_iteration": round(per, 3),
+           "ns_per_pixel": round(per * 1e6 / (S * H * W), 4), "status_1": int((so == 1).sum().item())}
+    if args.leg == "photometric":
+        pper, pres = iteration(True)
+        row.update({"photo_ms_n2": round(pres[2][0], 3), "photo_ms_n6": round(pres[6][0], 3), "photo_ms_min_max_n2": pres[2][1],
+                    "photo_ms_min_max_n6": pres[6][1], "photo_ms_per_iteration": round(pper, 3),
+                    "photo_ns_per_pixel": round(pper * 1e6 / (S * H * W), 4), "photo_status_1": int((so == 1).sum().item()),
+                    "photo_over_plain": round(pper / per, 3)})
+    print(json.dumps(row), flush=True)
 
 
 def main():
@@ -170,9 +206,10 @@ def main():
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--S", type=int, default=128)
     ap.add_argument("--limit", type=int, default=240, help="seconds a leg may take")
-    ap.add_argument("--leg", choices=["iteration", "copy", "warp", "sequence", "chain"], help="run this one leg in this process")
+    ap.add_argument("--leg", choices=["iteration", "photometric", "accumulate", "copy", "warp", "sequence", "chain"], help="run this one leg in this process")
     ap.add_argument("--dtype", choices=["u8", "f32"], default="u8")
     ap.add_argument("--kind", choices=sorted(KINDS), default="homography")
+    ap.add_argument("--only", help="comma-separated legs: run these alone")
     args = ap.parse_args()
     if args.leg:
         import torch  # noqa: F401  (first: liboflk binds to the HIP runtime torch has loaded)
@@ -180,8 +217,12 @@ def main():
         leg(args)
         return 0
     legs = [("iteration", dt, k) for dt in ("u8", "f32") for k in ("homography", "affine")]
+    legs += [("photometric", dt, k) for dt in ("u8", "f32") for k in ("homography", "affine")]
+    legs += [("accumulate", dt, "homography") for dt in ("u8", "f32")]
     legs += [("copy", dt, "homography") for dt in ("u8", "f32")] + [("warp", dt, "homography") for dt in ("u8", "f32")]
     legs += [("sequence", "u8", "homography"), ("chain", "u8", "homography")]
+    if args.only:
+        legs = [x for x in legs if x[0] in args.only.split(",")]
     for lg, dt, kind in legs:
         cmd = [sys.executable, __file__, "--leg", lg, "--dtype", dt, "--kind", kind, "--steps", str(args.steps), "--reps", str(args.reps),
                "--S", str(args.S)]

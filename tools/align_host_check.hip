@@ -114,6 +114,57 @@ int main()
     EXPECT(oflk_align_sequence_host(nullptr, 2, 32, 40, 2, 1, P, 0.25f, fm, nullptr, fm, im, dm) == OFLK_ERR_INVALID);
     EXPECT(oflk_align_sequence_host_u8(u, 2, 32, 40, 2, -3, P, 0.25f, fm, nullptr, fm, im, dm) == OFLK_ERR_INVALID);
     EXPECT(oflk_align_sequence_host_u8(u, 2, 6, 40, 1, 1, P, 0.25f, fm, nullptr, fm, im, dm) == OFLK_ERR_UNSUPPORTED);
+    // the photometric forms: a larger workspace with the steps' (g, b) behind everything else, the plain refusals, and a NULL
+    // or misaligned photo output
+    for (int model : {A, P}) {
+        size_t plain = 0, photo = 0;
+        EXPECT(oflk_align_workspace(3, 70, 257, 3, model, &plain) == OFLK_OK);
+        EXPECT(oflk_align_photo_workspace(3, 70, 257, 3, model, &photo) == OFLK_OK && photo > plain && photo % 256 == 0);
+        int dims[2 * OFLK_MAX_LEVELS];
+        EXPECT(check_align(3, 70, 257, 3, 1, model, 0.25f, dims) == OFLK_OK);
+        char *b = reinterpret_cast<char *>(g_buf);
+        const AlignWs ws = align_ws(b, 3, 3, dims, model, true);
+        EXPECT(ws.bytes == photo && ws.pstride == 3u * 5u * (size_t)align_sums(model == P ? 10 : 8));
+        EXPECT(reinterpret_cast<const char *>(ws.photo) >= reinterpret_cast<const char *>(ws.pyr[1]) && aligned(ws.photo, 256));
+        EXPECT(reinterpret_cast<const char *>(ws.photo) + 2 * 3 * sizeof(double) <= b + ws.bytes);
+        EXPECT(align_ws(b, 3, 3, dims, model).photo == nullptr);
+    }
+    EXPECT(oflk_align_photo_workspace(2, 32, 40, 2, P, nullptr) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_photo_workspace(2, 32, 40, 2, P, &n) == OFLK_OK);
+    auto photo = [&](const void *a, int S, int it, void *ws, size_t bytes, float *mo, float *po) {
+        return oflk_align_refine_photo(a, d, 0, S, 32, 40, 2, it, P, 0.25f, fm, nullptr, ws, bytes, mo, im, dm, po, nullptr);
+    };
+    EXPECT(photo(d, 0, 1, d, n, fm, fm) == OFLK_ERR_INVALID);
+    EXPECT(photo(d, 2, 0, d, n, fm, fm) == OFLK_ERR_INVALID);
+    EXPECT(photo(nullptr, 2, 1, d, n, fm, fm) == OFLK_ERR_INVALID);
+    EXPECT(photo(d, 2, 1, d, n, nullptr, fm) == OFLK_ERR_INVALID);
+    EXPECT(photo(d, 2, 1, d, n - 1, fm, fm) == OFLK_ERR_INVALID);
+    EXPECT(photo(d, 2, 1, d, n, fm, nullptr) == OFLK_ERR_INVALID);
+    EXPECT(std::string(oflk_last_error()).find("d_photo_out") != std::string::npos);
+    EXPECT(photo(d, 2, 1, d, n, fm, reinterpret_cast<float *>(g_buf + 2)) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_sequence_photo(d, 1, 1, 32, 40, 2, 1, P, 0.25f, fm, nullptr, d, n, fm, im, dm, fm, nullptr) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_sequence_photo(d, 1, 3, 32, 40, 2, 1, P, 0.25f, fm, nullptr, d, n, fm, im, dm, nullptr, nullptr) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_refine_photo_host(fm, fm, 1, 32, 40, 2, 1, P, 0.25f, fm, nullptr, fm, im, dm, nullptr) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_refine_photo_host_u8(u, u, 1, 32, 40, 2, 0, A, 0.25f, fm, nullptr, fm, im, dm, fm) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_sequence_photo_host(fm, 1, 32, 40, 2, 1, P, 0.25f, fm, nullptr, fm, im, dm, fm) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_sequence_photo_host_u8(u, 2, 32, 40, 2, 1, P, 0.25f, fm, nullptr, fm, im, dm, nullptr) == OFLK_ERR_INVALID);
+    // the exposure chain is host code: its refusals, a held step, and forwards against backwards
+    {
+        const float ph[3][2] = {{2.0f, 4.0f}, {-1.0f, 7.0f}, {0.5f, -1.0f}};
+        const int st[3] = {1, 1, 1};
+        double e[4][2];
+        EXPECT(oflk_exposure_chain_host(&ph[0][0], st, 0, 0, &e[0][0]) == OFLK_ERR_INVALID);
+        EXPECT(oflk_exposure_chain_host(&ph[0][0], st, 4, 4, &e[0][0]) == OFLK_ERR_INVALID);
+        EXPECT(oflk_exposure_chain_host(nullptr, st, 4, 0, &e[0][0]) == OFLK_ERR_INVALID);
+        EXPECT(oflk_exposure_chain_host(&ph[0][0], st, 4, 0, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_exposure_chain_host(nullptr, nullptr, 1, 0, &e[0][0]) == OFLK_OK && e[0][0] == 1.0 && e[0][1] == 0.0);
+        EXPECT(oflk_exposure_chain_host(&ph[0][0], nullptr, 4, 0, &e[0][0]) == OFLK_OK);
+        EXPECT(e[0][0] == 1.0 && e[0][1] == 0.0 && e[1][0] == 0.5 && e[1][1] == -2.0);
+        EXPECT(e[2][0] == 0.5 && e[2][1] == -2.0);   // the step with a negative gain is held
+        EXPECT(e[3][0] == 1.0 && e[3][1] == -1.0);
+        EXPECT(oflk_exposure_chain_host(&ph[0][0], nullptr, 4, 3, &e[0][0]) == OFLK_OK);
+        EXPECT(e[3][0] == 1.0 && e[3][1] == 0.0 && e[2][0] == 0.5 && e[2][1] == -1.0 && e[1][0] == 0.5 && e[0][0] == 1.0 && e[0][1] == 1.0);
+    }
     std::printf(g_failed ? "align host check: %d expectation(s) failed\n" : "align host check: ok\n", g_failed);
     return g_failed ? 1 : 0;
 }

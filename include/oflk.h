@@ -859,7 +859,8 @@ int oflk_mosaic_sequence_u8(const unsigned char *frames, int T, int H, int W, in
  * an unknown model, levels outside [1, OFLK_MAX_LEVELS], NULL pointers (d_status_in / status_in may be NULL: every step
  * refined), a workspace that is too small or not 256-byte aligned, d_stats not 8-byte aligned: OFLK_ERR_INVALID;  frames of
  * 2^30 pixels or more, levels whose coarsest would be smaller than 8 x 8: OFLK_ERR_UNSUPPORTED.  Early exit on a small
- * update, the ECC normalisation, translation and similarity models and robust weights are not offered. */
+ * update, the ECC normalisation and translation and similarity models are not offered;  robust weights are the robust form's,
+ * below. */
 #define OFLK_ALIGN_AFFINE 0
 #define OFLK_ALIGN_HOMOGRAPHY 1
 /* bytes of the workspace of S steps (the sequence call: S = T - 1).  Host only */
@@ -907,8 +908,8 @@ int oflk_align_sequence_host_u8(const unsigned char *frames, int T, int H, int W
  *                  bytes of (1.0f, 0.0f), a refused step included
  * d_photo_out / photo_out [S][2] float32;  NULL: OFLK_ERR_INVALID;  the other refusals are the plain calls'.  The workspace is
  * larger: oflk_align_photo_workspace.  The device forms are asynchronous on `stream` and can be captured into a graph (one
- * chain, no parallel branches).  One gain and one bias per step over the whole frame: robust weights, the ECC normalisation,
- * per-channel gains and gamma are not offered.  The sparse tracker still assumes brightness constancy: a step whose exposure
+ * chain, no parallel branches).  One gain and one bias per step over the whole frame: the ECC normalisation, per-channel
+ * gains and gamma are not offered;  robust weights are the robust form's, below.  The sparse tracker still assumes brightness constancy: a step whose exposure
  * change exceeds its max_residual (4 grey levels by default) ends tracks before the refinement sees the step. */
 int oflk_align_photo_workspace(int S, int H, int W, int levels, int model, size_t *bytes);
 int oflk_align_refine_photo(const void *d_a, const void *d_b, int u8, int S, int H, int W, int levels, int iterations, int model,
@@ -932,6 +933,65 @@ int oflk_align_sequence_photo_host(const float *frames, int T, int H, int W, int
 int oflk_align_sequence_photo_host_u8(const unsigned char *frames, int T, int H, int W, int levels, int iterations, int model,
                                       float min_share, const float *model_in, const int *status_in, float *model_out,
                                       int *status_out, double *stats, float *photo_out);
+
+/* The robust form (the statement: tests/align_robust_model.py): the plain calls (photometric == 0) or the photometric ones
+ * (photometric != 0) with a Huber weight on every residual, so that what moves on its own -- a person walking through the shot
+ * -- does not pull the fit: iteratively reweighted least squares.  It is the statements above with what follows changed.
+ * delta = f64(robust_delta), in grey levels, one value for every level.
+ *   sums_robust    counted, r, sd and the columns c as above (plain: c = sd, NQ = NP;  photometric: c = [g sd, a, 1.0],
+ *                  NQ = NP + 2).  Per counted pixel:  ar = |r|;  w = ar > delta ? delta / ar : 1.0;
+ *                  rho = ar > delta ? delta (ar - delta 0.5) : (r r) 0.5;  wc[i] = w c[i].  A NaN r fails the comparison:
+ *                  w = 1 and the NaN poisons the sums as it does above.  The NQ (NQ + 1) / 2 + NQ + 4 sums over the counted
+ *                  pixels (31 affine, 48 homography;  photometric 48, 69):  wc[i] c[j] for i = 0 .. NQ-1, j = i .. NQ-1;
+ *                  wc[i] r;  r r;  1.0;  rho;  w.  The order of every sum is the one above
+ *   iteration      the one above on the weighted [G | b];  the freezes and the g, b update are unchanged.  The weights come
+ *                  from the current residual on every pass, at every level
+ *   before, after  sum(rho) / count at full resolution under the input model (photometric: at (g, b) = (1, 0)) and under the
+ *                  final model (and g, b);  status 2 when not after <= before.  rho is what the iteration minimises: a step
+ *                  that moves an outlier's large residual about while it registers the rest is not rejected for it
+ *   outputs        stats[s] = [mean rho before, mean rho after, c1 / f64(W H), accepted, r r / count before, r r / count
+ *                  after, sum(w) / count before, sum(w) / count after], eight zeros for a refused step;  model, status and
+ *                  photo by the rules above
+ * A suggested robust_delta is 4 grey levels, the sparse tracker's max_residual default in the same unit;  stats[s][7], the mean
+ * weight under the final model, is how a caller tunes it (1.0: nothing was down-weighted).  d_stats / stats [S][8] float64;
+ * d_photo_out / photo_out [S][2] float32 when photometric, otherwise NULL (it is not written).  The workspace is
+ * oflk_align_robust_workspace's.  Refusals, before any device call: robust_delta not finite or <= 0, photometric without
+ * d_photo_out: OFLK_ERR_INVALID;  and the plain calls'.  The device forms are asynchronous on `stream` and can be captured into
+ * a graph (one chain, no parallel branches).  A scale estimated from the data and redescending weights are not offered. */
+int oflk_align_robust_workspace(int S, int H, int W, int levels, int model, int photometric, size_t *bytes);
+int oflk_align_refine_robust(const void *d_a, const void *d_b, int u8, int S, int H, int W, int levels, int iterations, int model,
+                             float min_share, float robust_delta, int photometric, const float *d_model_in,
+                             const int *d_status_in, void *d_workspace, size_t workspace_bytes, float *d_model_out,
+                             int *d_status_out, double *d_stats, float *d_photo_out, void *stream);
+int oflk_align_sequence_robust(const void *d_frames, int u8, int T, int H, int W, int levels, int iterations, int model,
+                               float min_share, float robust_delta, int photometric, const float *d_model_in,
+                               const int *d_status_in, void *d_workspace, size_t workspace_bytes, float *d_model_out,
+                               int *d_status_out, double *d_stats, float *d_photo_out, void *stream);
+/* host arrays, synchronous, in the plain host forms' chunks of at most 64 steps */
+int oflk_align_refine_robust_host(const float *a, const float *b, int S, int H, int W, int levels, int iterations, int model,
+                                  float min_share, float robust_delta, int photometric, const float *model_in,
+                                  const int *status_in, float *model_out, int *status_out, double *stats, float *photo_out);
+int oflk_align_refine_robust_host_u8(const unsigned char *a, const unsigned char *b, int S, int H, int W, int levels,
+                                     int iterations, int model, float min_share, float robust_delta, int photometric,
+                                     const float *model_in, const int *status_in, float *model_out, int *status_out,
+                                     double *stats, float *photo_out);
+int oflk_align_sequence_robust_host(const float *frames, int T, int H, int W, int levels, int iterations, int model,
+                                    float min_share, float robust_delta, int photometric, const float *model_in,
+                                    const int *status_in, float *model_out, int *status_out, double *stats, float *photo_out);
+int oflk_align_sequence_robust_host_u8(const unsigned char *frames, int T, int H, int W, int levels, int iterations, int model,
+                                       float min_share, float robust_delta, int photometric, const float *model_in,
+                                       const int *status_in, float *model_out, int *status_out, double *stats, float *photo_out);
+/* The weight map of S steps at full resolution: weights[s][y][x] = f32(w) of sums_robust at the counted pixels of step s under
+ * model[s] [6 | 9] float32 (no pyramid, no iteration), 0.0f elsewhere;  low values mark what moved on its own.  photo [S][2]
+ * float32 gains and biases (the photometric residual, g = f64(photo[s][0]), b = f64(photo[s][1])) or NULL (the plain one).
+ * Refusals: S, H, W < 1, an unknown model, robust_delta not finite or <= 0, NULL pointers: OFLK_ERR_INVALID;  frames of 2^30
+ * pixels or more: OFLK_ERR_UNSUPPORTED.  The device form is one asynchronous launch on `stream` */
+int oflk_align_weights(const void *d_a, const void *d_b, int u8, int S, int H, int W, int model, float robust_delta,
+                       const float *d_model, const float *d_photo, float *d_weights, void *stream);
+int oflk_align_weights_host(const float *a, const float *b, int S, int H, int W, int model, float robust_delta,
+                            const float *model_in, const float *photo, float *weights);
+int oflk_align_weights_host_u8(const unsigned char *a, const unsigned char *b, int S, int H, int W, int model, float robust_delta,
+                               const float *model_in, const float *photo, float *weights);
 
 /* ---- online video stabilisation: a fixed-lag stabiliser on the tracker --------------------------------------------------- */
 /* The statement (tests/stabilize_online_model.py) is the trajectory above, read in the order in which a stream delivers its

@@ -4859,7 +4859,10 @@ OFLK_API int oflk_mosaic_sequence_u8(const unsigned char *frames, int T, int H, 
 // =============================================================================
 namespace {
 int align_coefficients(int model) { return model == OFLK_ALIGN_HOMOGRAPHY ? 9 : 6; }
-int align_nsums(int model, bool photo = false) { return align_sums((model == OFLK_ALIGN_HOMOGRAPHY ? 8 : 6) + (photo ? 2 : 0)); }
+int align_nsums(int model, bool photo = false, bool robust = false)
+{
+    return align_sums((model == OFLK_ALIGN_HOMOGRAPHY ? 8 : 6) + (photo ? 2 : 0)) + (robust ? 2 : 0);
+}
 int align_tiles(int h, int w) { return ((w + kAlignTileW - 1) / kAlignTileW) * ((h + kAlignTileH - 1) / kAlignTileH); }
 
 // The refusals of the configuration, before any device call; dims receives the level sizes
@@ -4888,16 +4891,18 @@ int check_align(int S, int H, int W, int levels, int iterations, int model, floa
 
 // The workspace, 256-byte aligned pieces: the steps' states [S], the tile sums [S][tiles of the frame][NS], and per level
 // below the frame 2 S images (the pair form: S of A, then S of B; the sequence form: the first S + 1 hold its frames').  The
-// photometric form has more sums per tile and, behind everything else, the steps' (g, b) [S][2]
+// photometric form has more sums per tile and, behind everything else, the steps' (g, b) [S][2].  The robust form has two
+// more sums per tile and, last, the first pass's r r / count and sum(w) / count [S][2]
 struct AlignWs {
     AlignState *state;
     double *partial;
     float *pyr[OFLK_MAX_LEVELS];
     double *photo;
+    double *first;
     size_t pstride, bytes;
 };
 
-AlignWs align_ws(void *base, int S, int levels, const int *dims, int model, bool photo = false)
+AlignWs align_ws(void *base, int S, int levels, const int *dims, int model, bool photo = false, bool robust = false)
 {
     char *b = static_cast<char *>(base);
     auto at = [&](size_t o) { return b ? b + o : nullptr; };   // NULL: only the size is wanted
@@ -4905,7 +4910,7 @@ AlignWs align_ws(void *base, int S, int levels, const int *dims, int model, bool
     size_t o = 0;
     ws.state = reinterpret_cast<AlignState *>(at(o));
     o += round256((size_t)S * sizeof(AlignState));
-    ws.pstride = (size_t)align_tiles(dims[2 * (levels - 1)], dims[2 * (levels - 1) + 1]) * (size_t)align_nsums(model, photo);
+    ws.pstride = (size_t)align_tiles(dims[2 * (levels - 1)], dims[2 * (levels - 1) + 1]) * (size_t)align_nsums(model, photo, robust);
     ws.partial = reinterpret_cast<double *>(at(o));
     o += round256((size_t)S * ws.pstride * sizeof(double));
     for (int l = 0; l < levels - 1; l++) {
@@ -4914,6 +4919,10 @@ AlignWs align_ws(void *base, int S, int levels, const int *dims, int model, bool
     }
     if (photo) {
         ws.photo = reinterpret_cast<double *>(at(o));
+        o += round256(2 * (size_t)S * sizeof(double));
+    }
+    if (robust) {
+        ws.first = reinterpret_cast<double *>(at(o));
         o += round256(2 * (size_t)S * sizeof(double));
     }
     ws.bytes = o;
@@ -4931,12 +4940,18 @@ int check_align_device(const void *d_a, const void *d_b, int u8, const void *d_m
     return OFLK_OK;
 }
 
-// photo: NULL, or the steps' (g, b) of the photometric form
+// photo: NULL, or the steps' (g, b) of the photometric form.  delta > 0: the robust form
 template <class PIX, int NP>
-int align_reduce_launch(const AlignReduceArgs &r, int tiles, hipStream_t s, const double *photo = nullptr)
+int align_reduce_launch(const AlignReduceArgs &r, int tiles, hipStream_t s, const double *photo = nullptr, double delta = 0.0)
 {
     const dim3 grid((unsigned)tiles, (unsigned)std::min(r.S, 65535));
-    if (photo)
+    if (delta > 0.0 && photo)
+        hipLaunchKernelGGL((k_align_reduce_robust<PIX, NP, true>), grid, dim3(64 * align_robust_waves(NP, true)), 0, s,
+                           AlignRobustReduceArgs{r, photo, delta});
+    else if (delta > 0.0)
+        hipLaunchKernelGGL((k_align_reduce_robust<PIX, NP, false>), grid, dim3(64 * align_robust_waves(NP, false)), 0, s,
+                           AlignRobustReduceArgs{r, nullptr, delta});
+    else if (photo)
         hipLaunchKernelGGL((k_align_reduce_photo<PIX, NP>), grid, dim3(64 * align_photo_waves(NP)), 0, s, AlignPhotoReduceArgs{r, photo});
     else
         hipLaunchKernelGGL((k_align_reduce<PIX, NP>), grid, dim3(64), 0, s, r);
@@ -4947,12 +4962,13 @@ int align_reduce_launch(const AlignReduceArgs &r, int tiles, hipStream_t s, cons
 // The whole chain of one call on stream s; the arguments are checked.  d_a, d_b: the S templates and images, `step` elements
 // apart (the pair form: two arrays of S frames; the sequence form: d_b = d_a + one frame).  nimg > 0: the sequence form's
 // nimg = S + 1 frames, whose pyramids are built once.  d_photo_out: NULL, or the photometric
-// form's output (ws is then that form's workspace)
+// form's output (ws is then that form's workspace).  robust_delta > 0: the robust form, d_stats [S][8] and ws that form's
 template <class PIX, int NP>
 int align_launch(const PIX *d_a, const PIX *d_b, int nimg, int S, int H, int W, int levels, const int *dims, int iterations,
                  float min_share, const float *d_model_in, const int *d_status_in, const AlignWs &ws, float *d_model_out,
-                 int *d_status_out, double *d_stats, hipStream_t s, float *d_photo_out = nullptr)
+                 int *d_status_out, double *d_stats, hipStream_t s, float *d_photo_out = nullptr, float robust_delta = 0.0f)
 {
+    const double delta = (double)robust_delta;
     constexpr int NC = NP == 8 ? 9 : 6;
     const bool seq = nimg > 0;
     const int n = seq ? nimg : 2 * S;
@@ -4998,11 +5014,11 @@ int align_launch(const PIX *d_a, const PIX *d_b, int nimg, int S, int H, int W, 
         if (l == levels - 1) {
             r.a = d_a;
             r.b = d_b;
-            rc2 = align_reduce_launch<PIX, NP>(r, tiles, s, photo);
+            rc2 = align_reduce_launch<PIX, NP>(r, tiles, s, photo, delta);
         } else {
             r.a = ws.pyr[l];
             r.b = ws.pyr[l] + (seq ? 1 : (size_t)S) * r.stride;
-            rc2 = align_reduce_launch<float, NP>(r, tiles, s, photo);
+            rc2 = align_reduce_launch<float, NP>(r, tiles, s, photo, delta);
         }
         if (rc2) return rc2;
         AlignUpdateArgs u{};
@@ -5016,7 +5032,13 @@ int align_launch(const PIX *d_a, const PIX *d_b, int nimg, int S, int H, int W, 
         }
         u.min_count = (double)min_share * (double)((long long)w * (long long)h);
         u.model_in = d_model_in; u.model_out = d_model_out; u.status_out = d_status_out; u.stats = d_stats;
-        if (photo)
+        if (delta > 0.0 && photo)
+            hipLaunchKernelGGL((k_align_update_robust<NP, true>), dim3((unsigned)std::min(S, 65535)), dim3(64), 0, s,
+                               AlignRobustUpdateArgs{u, ws.photo, d_photo_out, ws.first});
+        else if (delta > 0.0)
+            hipLaunchKernelGGL((k_align_update_robust<NP, false>), dim3((unsigned)std::min(S, 65535)), dim3(64), 0, s,
+                               AlignRobustUpdateArgs{u, nullptr, nullptr, ws.first});
+        else if (photo)
             hipLaunchKernelGGL((k_align_update_photo<NP>), dim3((unsigned)std::min(S, 65535)), dim3(64), 0, s,
                                AlignPhotoUpdateArgs{u, ws.photo, d_photo_out});
         else
@@ -5036,33 +5058,45 @@ int align_launch(const PIX *d_a, const PIX *d_b, int nimg, int S, int H, int W, 
 template <class PIX>
 int align_dispatch(const PIX *d_a, const PIX *d_b, int nimg, int S, int H, int W, int levels, const int *dims, int iterations,
                    int model, float min_share, const float *d_model_in, const int *d_status_in, const AlignWs &ws,
-                   float *d_model_out, int *d_status_out, double *d_stats, hipStream_t s, float *d_photo_out = nullptr)
+                   float *d_model_out, int *d_status_out, double *d_stats, hipStream_t s, float *d_photo_out = nullptr,
+                   float robust_delta = 0.0f)
 {
     return model == OFLK_ALIGN_HOMOGRAPHY
                ? align_launch<PIX, 8>(d_a, d_b, nimg, S, H, W, levels, dims, iterations, min_share, d_model_in, d_status_in, ws,
-                                      d_model_out, d_status_out, d_stats, s, d_photo_out)
+                                      d_model_out, d_status_out, d_stats, s, d_photo_out, robust_delta)
                : align_launch<PIX, 6>(d_a, d_b, nimg, S, H, W, levels, dims, iterations, min_share, d_model_in, d_status_in, ws,
-                                      d_model_out, d_status_out, d_stats, s, d_photo_out);
+                                      d_model_out, d_status_out, d_stats, s, d_photo_out, robust_delta);
+}
+
+// the robust forms' own refusal
+int check_robust_delta(float robust_delta)
+{
+    if (!(std::isfinite(robust_delta) && robust_delta > 0.0f))
+        return fail(OFLK_ERR_INVALID, "robust_delta must be finite and > 0 (got %g)", (double)robust_delta);
+    return OFLK_OK;
 }
 
 int align_device(const void *d_a, const void *d_b, int u8, int nimg, int S, int H, int W, int levels, int iterations, int model,
                  float min_share, const float *d_model_in, const int *d_status_in, void *d_workspace, size_t bytes,
                  float *d_model_out, int *d_status_out, double *d_stats, hipStream_t s, bool photo = false,
-                 float *d_photo_out = nullptr)
+                 float *d_photo_out = nullptr, bool robust = false, float robust_delta = 0.0f)
 {
     int dims[2 * OFLK_MAX_LEVELS];
     int rc = check_align(S, H, W, levels, iterations, model, min_share, dims);
     if (rc) return rc;
-    const size_t need = align_ws(nullptr, S, levels, dims, model, photo).bytes;
+    if (robust && (rc = check_robust_delta(robust_delta))) return rc;
+    if (!robust) robust_delta = 0.0f;
+    if (!photo) d_photo_out = nullptr;
+    const size_t need = align_ws(nullptr, S, levels, dims, model, photo, robust).bytes;
     if ((rc = check_align_device(d_a, d_b, u8, d_model_in, d_workspace, bytes, need, d_model_out, d_status_out, d_stats))) return rc;
     if (photo && !d_photo_out) return fail(OFLK_ERR_INVALID, "NULL d_photo_out");
     if (photo && !aligned(d_photo_out, 4)) return fail(OFLK_ERR_INVALID, "d_photo_out must be 4-byte aligned");
-    const AlignWs ws = align_ws(d_workspace, S, levels, dims, model, photo);
+    const AlignWs ws = align_ws(d_workspace, S, levels, dims, model, photo, robust);
     return u8 ? align_dispatch<unsigned char>((const unsigned char *)d_a, (const unsigned char *)d_b, nimg, S, H, W, levels, dims,
                                               iterations, model, min_share, d_model_in, d_status_in, ws, d_model_out, d_status_out,
-                                              d_stats, s, d_photo_out)
+                                              d_stats, s, d_photo_out, robust_delta)
               : align_dispatch<float>((const float *)d_a, (const float *)d_b, nimg, S, H, W, levels, dims, iterations, model, min_share,
-                                      d_model_in, d_status_in, ws, d_model_out, d_status_out, d_stats, s, d_photo_out);
+                                      d_model_in, d_status_in, ws, d_model_out, d_status_out, d_stats, s, d_photo_out, robust_delta);
 }
 
 // S host steps in chunks of steps through one set of device buffers: a chunk's frames go up, its steps are refined and the
@@ -5071,11 +5105,14 @@ int align_device(const void *d_a, const void *d_b, int u8, int nimg, int S, int 
 template <class PIX>
 int align_host(const PIX *a, const PIX *b, bool seq, int S, int H, int W, int levels, int iterations, int model, float min_share,
                const float *model_in, const int *status_in, float *model_out, int *status_out, double *stats, bool photo = false,
-               float *photo_out = nullptr)
+               float *photo_out = nullptr, bool robust = false, float robust_delta = 0.0f)
 {
     int dims[2 * OFLK_MAX_LEVELS];
     int rc = check_align(S, H, W, levels, iterations, model, min_share, dims);
     if (rc) return rc;
+    if (robust && (rc = check_robust_delta(robust_delta))) return rc;
+    if (!robust) robust_delta = 0.0f;
+    const size_t ns = robust ? 8 : 4;   // a step's stats
     if (!a || (!seq && !b) || !model_in || !model_out || !status_out || !stats || (photo && !photo_out))
         return fail(OFLK_ERR_INVALID, "NULL input or output argument");
     HostCall call;
@@ -5087,10 +5124,10 @@ int align_host(const PIX *a, const PIX *b, bool seq, int S, int H, int W, int le
     int *d_sin = nullptr, *d_sout = nullptr;
     double *d_stats = nullptr;
     char *d_ws = nullptr;
-    const size_t bytes = align_ws(nullptr, C, levels, dims, model, photo).bytes;
+    const size_t bytes = align_ws(nullptr, C, levels, dims, model, photo, robust).bytes;
     if ((rc = call.alloc(&d_a, (size_t)(C + (seq ? 1 : 0)) * plane)) || (rc = call.alloc(&d_b, (size_t)C * plane, !seq)) ||
         (rc = call.upload(&d_min, model_in, nc * nS)) || (status_in && (rc = call.upload(&d_sin, status_in, nS))) ||
-        (rc = call.alloc(&d_mout, nc * nS)) || (rc = call.alloc(&d_sout, nS)) || (rc = call.alloc(&d_stats, 4 * nS)) ||
+        (rc = call.alloc(&d_mout, nc * nS)) || (rc = call.alloc(&d_sout, nS)) || (rc = call.alloc(&d_stats, ns * nS)) ||
         (rc = call.alloc(&d_ws, bytes)) || (rc = call.alloc(&d_photo, 2 * nS, photo)))
         return rc;
     for (int s0 = 0; s0 < S; s0 += C) {
@@ -5099,15 +5136,15 @@ int align_host(const PIX *a, const PIX *b, bool seq, int S, int H, int W, int le
         if ((rc = call.to_device(d_a, a + o, (size_t)(n + (seq ? 1 : 0)) * plane)) ||
             (!seq && (rc = call.to_device(d_b, b + o, (size_t)n * plane))))
             return rc;
-        const AlignWs ws = align_ws(d_ws, n, levels, dims, model, photo);
+        const AlignWs ws = align_ws(d_ws, n, levels, dims, model, photo, robust);
         if ((rc = align_dispatch<PIX>(d_a, seq ? d_a + plane : d_b, seq ? n + 1 : 0, n, H, W, levels, dims, iterations, model, min_share,
                                       d_min + (size_t)nc * s0, d_sin ? d_sin + s0 : nullptr, ws, d_mout + (size_t)nc * s0, d_sout + s0,
-                                      d_stats + 4 * (size_t)s0, nullptr, photo ? d_photo + 2 * (size_t)s0 : nullptr)) ||
+                                      d_stats + ns * (size_t)s0, nullptr, photo ? d_photo + 2 * (size_t)s0 : nullptr, robust_delta)) ||
             (rc = call.sync()))
             return rc;
     }
     if ((rc = call.to_host(model_out, d_mout, nc * nS)) || (rc = call.to_host(status_out, d_sout, nS)) ||
-        (rc = call.to_host(stats, d_stats, 4 * nS)) || (photo && (rc = call.to_host(photo_out, d_photo, 2 * nS))))
+        (rc = call.to_host(stats, d_stats, ns * nS)) || (photo && (rc = call.to_host(photo_out, d_photo, 2 * nS))))
         return rc;
     return call.sync();
 }
@@ -5239,6 +5276,168 @@ OFLK_API int oflk_align_sequence_photo_host_u8(const unsigned char *frames, int 
     if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
     return align_host<unsigned char>(frames, nullptr, true, T - 1, H, W, levels, iterations, model, min_share, model_in, status_in,
                                      model_out, status_out, stats, true, photo_out);
+}
+
+// ---- the robust forms ----
+OFLK_API int oflk_align_robust_workspace(int S, int H, int W, int levels, int model, int photometric, size_t *bytes)
+{
+    if (!bytes) return fail(OFLK_ERR_INVALID, "bytes is NULL");
+    *bytes = 0;
+    int dims[2 * OFLK_MAX_LEVELS];
+    if (int rc = check_align(S, H, W, levels, 1, model, 1.0f, dims)) return rc;
+    *bytes = align_ws(nullptr, S, levels, dims, model, photometric != 0, true).bytes;
+    return OFLK_OK;
+}
+
+OFLK_API int oflk_align_refine_robust(const void *d_a, const void *d_b, int u8, int S, int H, int W, int levels, int iterations,
+                                      int model, float min_share, float robust_delta, int photometric, const float *d_model_in,
+                                      const int *d_status_in, void *d_workspace, size_t workspace_bytes, float *d_model_out,
+                                      int *d_status_out, double *d_stats, float *d_photo_out, void *stream)
+{
+    return align_device(d_a, d_b, u8, 0, S, H, W, levels, iterations, model, min_share, d_model_in, d_status_in, d_workspace,
+                        workspace_bytes, d_model_out, d_status_out, d_stats, (hipStream_t)stream, photometric != 0, d_photo_out, true,
+                        robust_delta);
+}
+
+OFLK_API int oflk_align_sequence_robust(const void *d_frames, int u8, int T, int H, int W, int levels, int iterations, int model,
+                                        float min_share, float robust_delta, int photometric, const float *d_model_in,
+                                        const int *d_status_in, void *d_workspace, size_t workspace_bytes, float *d_model_out,
+                                        int *d_status_out, double *d_stats, float *d_photo_out, void *stream)
+{
+    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
+    const void *d_b = d_frames && H > 0 && W > 0 ? static_cast<const char *>(d_frames) + (size_t)H * (size_t)W * (u8 ? 1 : sizeof(float))
+                                                 : d_frames;
+    return align_device(d_frames, d_b, u8, T, T - 1, H, W, levels, iterations, model, min_share, d_model_in, d_status_in, d_workspace,
+                        workspace_bytes, d_model_out, d_status_out, d_stats, (hipStream_t)stream, photometric != 0, d_photo_out, true,
+                        robust_delta);
+}
+
+OFLK_API int oflk_align_refine_robust_host(const float *a, const float *b, int S, int H, int W, int levels, int iterations, int model,
+                                           float min_share, float robust_delta, int photometric, const float *model_in,
+                                           const int *status_in, float *model_out, int *status_out, double *stats, float *photo_out)
+{
+    return align_host<float>(a, b, false, S, H, W, levels, iterations, model, min_share, model_in, status_in, model_out, status_out,
+                             stats, photometric != 0, photo_out, true, robust_delta);
+}
+
+OFLK_API int oflk_align_refine_robust_host_u8(const unsigned char *a, const unsigned char *b, int S, int H, int W, int levels,
+                                              int iterations, int model, float min_share, float robust_delta, int photometric,
+                                              const float *model_in, const int *status_in, float *model_out, int *status_out,
+                                              double *stats, float *photo_out)
+{
+    return align_host<unsigned char>(a, b, false, S, H, W, levels, iterations, model, min_share, model_in, status_in, model_out,
+                                     status_out, stats, photometric != 0, photo_out, true, robust_delta);
+}
+
+OFLK_API int oflk_align_sequence_robust_host(const float *frames, int T, int H, int W, int levels, int iterations, int model,
+                                             float min_share, float robust_delta, int photometric, const float *model_in,
+                                             const int *status_in, float *model_out, int *status_out, double *stats, float *photo_out)
+{
+    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
+    return align_host<float>(frames, nullptr, true, T - 1, H, W, levels, iterations, model, min_share, model_in, status_in, model_out,
+                             status_out, stats, photometric != 0, photo_out, true, robust_delta);
+}
+
+OFLK_API int oflk_align_sequence_robust_host_u8(const unsigned char *frames, int T, int H, int W, int levels, int iterations,
+                                                int model, float min_share, float robust_delta, int photometric,
+                                                const float *model_in, const int *status_in, float *model_out, int *status_out,
+                                                double *stats, float *photo_out)
+{
+    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
+    return align_host<unsigned char>(frames, nullptr, true, T - 1, H, W, levels, iterations, model, min_share, model_in, status_in,
+                                     model_out, status_out, stats, photometric != 0, photo_out, true, robust_delta);
+}
+
+// ---- the weight map ----
+namespace {
+// the refusals of the weight map's configuration, before any device call
+int check_align_weights(int S, int H, int W, int model, float robust_delta)
+{
+    if (S < 1) return fail(OFLK_ERR_INVALID, "S must be >= 1 (got %d)", S);
+    if (H < 1 || W < 1) return fail(OFLK_ERR_INVALID, "H and W must be >= 1 (got %d x %d)", H, W);
+    if ((size_t)H * (size_t)W >= ((size_t)1 << 30)) return fail(OFLK_ERR_UNSUPPORTED, "frames of 2^30 pixels or more are not supported");
+    if (H >= kMaxDim || W >= kMaxDim)
+        return fail(OFLK_ERR_UNSUPPORTED, "frames of 2^23 rows or columns or more are not supported (got %d x %d)", H, W);
+    if (model != OFLK_ALIGN_AFFINE && model != OFLK_ALIGN_HOMOGRAPHY) return fail(OFLK_ERR_INVALID, "unknown model %d", model);
+    return check_robust_delta(robust_delta);
+}
+
+template <class PIX, int NP>
+int align_weights_launch(const AlignWeightsArgs &a, hipStream_t s)
+{
+    const dim3 grid((unsigned)(((size_t)a.H * (size_t)a.W + 255) / 256), (unsigned)std::min(a.S, 65535));
+    if (a.photo)
+        hipLaunchKernelGGL((k_align_weights<PIX, NP, true>), grid, dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL((k_align_weights<PIX, NP, false>), grid, dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+
+// the arguments are checked
+int align_weights_dispatch(const void *d_a, const void *d_b, bool u8, int S, int H, int W, int model, float robust_delta,
+                           const float *d_model, const float *d_photo, float *d_weights, hipStream_t s)
+{
+    AlignWeightsArgs a{};
+    a.a = d_a; a.b = d_b;
+    a.H = H; a.W = W; a.S = S;
+    a.model = d_model; a.photo = d_photo;
+    a.delta = (double)robust_delta;
+    a.weights = d_weights;
+    if (model == OFLK_ALIGN_HOMOGRAPHY) return u8 ? align_weights_launch<unsigned char, 8>(a, s) : align_weights_launch<float, 8>(a, s);
+    return u8 ? align_weights_launch<unsigned char, 6>(a, s) : align_weights_launch<float, 6>(a, s);
+}
+
+template <class PIX>
+int align_weights_host(const PIX *a, const PIX *b, int S, int H, int W, int model, float robust_delta, const float *model_in,
+                       const float *photo, float *weights)
+{
+    int rc = check_align_weights(S, H, W, model, robust_delta);
+    if (rc) return rc;
+    if (!a || !b || !model_in || !weights) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const int C = sparse_chunk_pairs(S, H, W), nc = align_coefficients(model);
+    const size_t plane = (size_t)H * W, nS = (size_t)S;
+    PIX *d_a = nullptr, *d_b = nullptr;
+    float *d_model = nullptr, *d_photo = nullptr, *d_w = nullptr;
+    if ((rc = call.alloc(&d_a, (size_t)C * plane)) || (rc = call.alloc(&d_b, (size_t)C * plane)) ||
+        (rc = call.upload(&d_model, model_in, nc * nS)) || (photo && (rc = call.upload(&d_photo, photo, 2 * nS))) ||
+        (rc = call.alloc(&d_w, (size_t)C * plane)))
+        return rc;
+    for (int s0 = 0; s0 < S; s0 += C) {
+        const int n = std::min(C, S - s0);
+        const size_t o = (size_t)s0 * plane;
+        if ((rc = call.to_device(d_a, a + o, (size_t)n * plane)) || (rc = call.to_device(d_b, b + o, (size_t)n * plane)) ||
+            (rc = align_weights_dispatch(d_a, d_b, sizeof(PIX) == 1, n, H, W, model, robust_delta, d_model + (size_t)nc * s0,
+                                         d_photo ? d_photo + 2 * (size_t)s0 : nullptr, d_w, nullptr)) ||
+            (rc = call.to_host(weights + o, d_w, (size_t)n * plane)) || (rc = call.sync()))
+            return rc;
+    }
+    return call.sync();
+}
+}  // namespace
+
+OFLK_API int oflk_align_weights(const void *d_a, const void *d_b, int u8, int S, int H, int W, int model, float robust_delta,
+                                const float *d_model, const float *d_photo, float *d_weights, void *stream)
+{
+    if (int rc = check_align_weights(S, H, W, model, robust_delta)) return rc;
+    if (!d_a || !d_b || !d_model || !d_weights) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    if (!aligned(d_model, 4) || !aligned(d_weights, 4) || (d_photo && !aligned(d_photo, 4)) || (!u8 && (!aligned(d_a, 4) || !aligned(d_b, 4))))
+        return fail(OFLK_ERR_INVALID, "float32 arguments must be 4-byte aligned");
+    return align_weights_dispatch(d_a, d_b, u8 != 0, S, H, W, model, robust_delta, d_model, d_photo, d_weights, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_align_weights_host(const float *a, const float *b, int S, int H, int W, int model, float robust_delta,
+                                     const float *model_in, const float *photo, float *weights)
+{
+    return align_weights_host<float>(a, b, S, H, W, model, robust_delta, model_in, photo, weights);
+}
+
+OFLK_API int oflk_align_weights_host_u8(const unsigned char *a, const unsigned char *b, int S, int H, int W, int model,
+                                        float robust_delta, const float *model_in, const float *photo, float *weights)
+{
+    return align_weights_host<unsigned char>(a, b, S, H, W, model, robust_delta, model_in, photo, weights);
 }
 
 // =============================================================================

@@ -167,6 +167,16 @@ SIGNATURES = {
     "oflk_align_refine_photo_host_u8": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p, _f32p]),
     "oflk_align_sequence_photo_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p, _f32p]),
     "oflk_align_sequence_photo_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p, _f32p]),
+    "oflk_align_robust_workspace": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_size_t)]),
+    "oflk_align_refine_robust": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 7 + [ctypes.c_float, ctypes.c_float, ctypes.c_int, _vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp]),
+    "oflk_align_sequence_robust": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [ctypes.c_float, ctypes.c_float, ctypes.c_int, _vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp]),
+    "oflk_align_refine_robust_host": (ctypes.c_int, [_f32p, _f32p] + [ctypes.c_int] * 6 + [ctypes.c_float, ctypes.c_float, ctypes.c_int, _f32p, _i32p, _f32p, _i32p, _f64p, _f32p]),
+    "oflk_align_refine_robust_host_u8": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 6 + [ctypes.c_float, ctypes.c_float, ctypes.c_int, _f32p, _i32p, _f32p, _i32p, _f64p, _f32p]),
+    "oflk_align_sequence_robust_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float, ctypes.c_float, ctypes.c_int, _f32p, _i32p, _f32p, _i32p, _f64p, _f32p]),
+    "oflk_align_sequence_robust_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float, ctypes.c_float, ctypes.c_int, _f32p, _i32p, _f32p, _i32p, _f64p, _f32p]),
+    "oflk_align_weights": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 5 + [ctypes.c_float, _vp, _vp, _vp, _vp]),
+    "oflk_align_weights_host": (ctypes.c_int, [_f32p, _f32p] + [ctypes.c_int] * 4 + [ctypes.c_float, _f32p, _f32p, _f32p]),
+    "oflk_align_weights_host_u8": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 4 + [ctypes.c_float, _f32p, _f32p, _f32p]),
     "oflk_stabilize_trajectory_ring": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 4 + [_f64p, ctypes.c_int, _vp, _vp, _vp]),
     "oflk_stabilizer_create": (ctypes.c_int, [ctypes.POINTER(_vp)] + [ctypes.c_int] * 7 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int]),
     "oflk_stabilizer_destroy": (ctypes.c_int, [_vp]),
@@ -1052,20 +1062,44 @@ def check_align_params(kind, levels, iterations, min_share: float) -> Tuple[int,
     return ALIGN_KINDS[kind], int(levels), int(iterations), ms
 
 
-def align_workspace(S: int, H: int, W: int, levels: int, model: int, photometric: bool = False) -> int:
+def check_robust_delta(robust_delta) -> float:
+    """the checked Huber threshold of the robust alignment calls, in grey levels; ValueError otherwise"""
+    if isinstance(robust_delta, bool) or not isinstance(robust_delta, (int, float, np.integer, np.floating)):
+        raise ValueError(f"robust_delta must be a number, got {robust_delta!r}")
+    with np.errstate(all="ignore"):
+        d = float(np.float32(robust_delta))
+    if not (np.isfinite(d) and d > 0.0):
+        raise ValueError(f"robust_delta must be finite and > 0 as float32, got {robust_delta!r}")
+    return d
+
+
+def align_workspace(S: int, H: int, W: int, levels: int, model: int, photometric: bool = False, robust: bool = False) -> int:
     """bytes of the workspace of oflk_align_refine for S steps (oflk_align_sequence: S = T - 1); photometric: of
-    oflk_align_refine_photo (oflk_align_photo_workspace)"""
+    oflk_align_refine_photo (oflk_align_photo_workspace); robust: of oflk_align_refine_robust (oflk_align_robust_workspace)"""
     n = ctypes.c_size_t(0)
+    if robust:
+        check(lib().oflk_align_robust_workspace(int(S), int(H), int(W), int(levels), int(model), int(bool(photometric)), ctypes.byref(n)))
+        return int(n.value)
     check((lib().oflk_align_photo_workspace if photometric else lib().oflk_align_workspace)(int(S), int(H), int(W), int(levels), int(model), ctypes.byref(n)))
     return int(n.value)
 
 
 def align_refine(d_a: int, d_b: int, S: int, H: int, W: int, levels: int, iterations: int, model: int, min_share: float,
                  d_model_in: int, d_status_in: int, d_workspace: int, workspace_bytes: int, d_model_out: int, d_status_out: int,
-                 d_stats: int, u8: bool = False, stream: int = 0, d_photo_out: Optional[int] = None) -> None:
+                 d_stats: int, u8: bool = False, stream: int = 0, d_photo_out: Optional[int] = None,
+                 robust_delta: Optional[float] = None) -> None:
     """oflk_align_refine on device pointers: d_a, d_b [S][H][W] (float32, or uint8 with u8), d_model_in / d_model_out [S][6 | 9]
     float32, d_status_in [S] int32 or 0, d_status_out [S] int32, d_stats [S][4] float64; asynchronous.  d_photo_out given:
-    oflk_align_refine_photo with (g, b) [S][2] float32 out and a workspace of align_workspace(..., photometric=True) bytes."""
+    oflk_align_refine_photo with (g, b) [S][2] float32 out and a workspace of align_workspace(..., photometric=True) bytes.
+    robust_delta given: oflk_align_refine_robust (photometric when d_photo_out is given), d_stats [S][8] and a workspace of
+    align_workspace(..., robust=True) bytes; the C call checks robust_delta."""
+    if robust_delta is not None:
+        check(lib().oflk_align_refine_robust(d_a or None, d_b or None, int(bool(u8)), int(S), int(H), int(W), int(levels),
+                                             int(iterations), int(model), float(min_share), float(robust_delta),
+                                             int(d_photo_out is not None), d_model_in or None, d_status_in or None,
+                                             d_workspace or None, int(workspace_bytes), d_model_out or None, d_status_out or None,
+                                             d_stats or None, d_photo_out or None, stream))
+        return
     if d_photo_out is not None:
         check(lib().oflk_align_refine_photo(d_a or None, d_b or None, int(bool(u8)), int(S), int(H), int(W), int(levels),
                                             int(iterations), int(model), float(min_share), d_model_in or None, d_status_in or None,
@@ -1079,9 +1113,18 @@ def align_refine(d_a: int, d_b: int, S: int, H: int, W: int, levels: int, iterat
 
 def align_sequence(d_frames: int, T: int, H: int, W: int, levels: int, iterations: int, model: int, min_share: float,
                    d_model_in: int, d_status_in: int, d_workspace: int, workspace_bytes: int, d_model_out: int, d_status_out: int,
-                   d_stats: int, u8: bool = False, stream: int = 0, d_photo_out: Optional[int] = None) -> None:
+                   d_stats: int, u8: bool = False, stream: int = 0, d_photo_out: Optional[int] = None,
+                   robust_delta: Optional[float] = None) -> None:
     """oflk_align_sequence on device pointers: the T-1 steps t -> t+1 of d_frames [T][H][W], with align_refine's other
-    arguments for S = T - 1; asynchronous.  d_photo_out given: oflk_align_sequence_photo."""
+    arguments for S = T - 1; asynchronous.  d_photo_out given: oflk_align_sequence_photo.  robust_delta given:
+    oflk_align_sequence_robust."""
+    if robust_delta is not None:
+        check(lib().oflk_align_sequence_robust(d_frames or None, int(bool(u8)), int(T), int(H), int(W), int(levels), int(iterations),
+                                               int(model), float(min_share), float(robust_delta), int(d_photo_out is not None),
+                                               d_model_in or None, d_status_in or None, d_workspace or None, int(workspace_bytes),
+                                               d_model_out or None, d_status_out or None, d_stats or None, d_photo_out or None,
+                                               stream))
+        return
     if d_photo_out is not None:
         check(lib().oflk_align_sequence_photo(d_frames or None, int(bool(u8)), int(T), int(H), int(W), int(levels), int(iterations),
                                               int(model), float(min_share), d_model_in or None, d_status_in or None,
@@ -1117,6 +1160,52 @@ def align_host(a: np.ndarray, b: Optional[np.ndarray], model_in: np.ndarray, sta
     else:
         check(fn(pix(a), F, *tail))
     return (out, st, stats, photo) if photometric else (out, st, stats)
+
+
+def align_robust_host(a: np.ndarray, b: Optional[np.ndarray], model_in: np.ndarray, status_in: Optional[np.ndarray], levels: int,
+                      iterations: int, model: int, min_share: float, robust_delta: float, photometric: bool = False):
+    """oflk_align_refine_robust_host[_u8] (b given) or oflk_align_sequence_robust_host[_u8] (b None), with align_host's arrays;
+    (model (S, nc) float32, status (S,) int32, stats (S, 8) float64, photo (S, 2) float32) out, photo (1, 0) without
+    photometric.  The C call checks robust_delta."""
+    F, H, W = a.shape
+    S = F if b is not None else F - 1
+    u8 = a.dtype == np.uint8
+    out = np.empty_like(model_in)
+    st, stats = np.empty(S, np.int32), np.empty((S, 8), np.float64)
+    photo = np.empty((S, 2), np.float32)
+    photo[:] = (1.0, 0.0)
+    pix = (lambda x: x.ctypes.data) if u8 else ptr
+    tail = (int(H), int(W), int(levels), int(iterations), int(model), float(min_share), float(robust_delta), int(bool(photometric)),
+            ptr(model_in), None if status_in is None else status_in.ctypes.data_as(_i32p), ptr(out), st.ctypes.data_as(_i32p),
+            _f64(stats), ptr(photo) if photometric else None)
+    fn = getattr(lib(), ("oflk_align_refine" if b is not None else "oflk_align_sequence") + "_robust_host" + ("_u8" if u8 else ""))
+    if b is not None:
+        check(fn(pix(a), pix(b), S, *tail))
+    else:
+        check(fn(pix(a), F, *tail))
+    return out, st, stats, photo
+
+
+def align_weights(d_a: int, d_b: int, S: int, H: int, W: int, model: int, robust_delta: float, d_model: int, d_photo: int,
+                  d_weights: int, u8: bool = False, stream: int = 0) -> None:
+    """oflk_align_weights on device pointers: d_a, d_b [S][H][W], d_model [S][6 | 9] float32, d_photo [S][2] float32 or 0,
+    d_weights [S][H][W] float32; asynchronous"""
+    check(lib().oflk_align_weights(d_a or None, d_b or None, int(bool(u8)), int(S), int(H), int(W), int(model), float(robust_delta),
+                                   d_model or None, d_photo or None, d_weights or None, stream))
+
+
+def align_weights_host(a: np.ndarray, b: np.ndarray, model_in: np.ndarray, model: int, robust_delta: float,
+                       photo: Optional[np.ndarray] = None) -> np.ndarray:
+    """oflk_align_weights_host[_u8]: contiguous (S, H, W) arrays of one type, float32 (S, 6 | 9) models, optional float32 (S, 2)
+    gains and biases -> (S, H, W) float32"""
+    S, H, W = a.shape
+    u8 = a.dtype == np.uint8
+    out = np.empty((S, H, W), np.float32)
+    pix = (lambda x: x.ctypes.data) if u8 else ptr
+    fn = lib().oflk_align_weights_host_u8 if u8 else lib().oflk_align_weights_host
+    check(fn(pix(a), pix(b), int(S), int(H), int(W), int(model), float(robust_delta), ptr(model_in), None if photo is None else ptr(photo),
+             ptr(out)))
+    return out
 
 
 class Tracker:

@@ -12,7 +12,7 @@ No CPU fallback exists: without the built library or a GPU the calls raise.
 """
 from __future__ import annotations
 
-from typing import NamedTuple, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import numpy.typing as npt
@@ -596,6 +596,16 @@ class PhotometricAlignment(NamedTuple):
     bias: np.ndarray     # (S,) float32; 0 where status != 1
 
 
+class RobustAlignment(NamedTuple):
+    """Step models refined under Huber weights (refine_alignment, sequence_refine_alignment with robust_delta given)."""
+    model: np.ndarray    # as Alignment.model
+    status: np.ndarray   # as Alignment.status; 2: the mean Huber loss grew
+    stats: np.ndarray    # (S, 8) float64: mean Huber loss before and after, counted share, accepted updates, mean squared
+                         # residual before and after, mean weight before and after (1.0: nothing was down-weighted)
+    gain: np.ndarray     # (S,) float32; 1 without photometric or where status != 1
+    bias: np.ndarray     # (S,) float32; 0 without photometric or where status != 1
+
+
 def _align_models(model, status, S: int, kind: str):
     nc = 9 if kind == "homography" else 6
     m = np.ascontiguousarray(model, np.float32)
@@ -618,8 +628,14 @@ def _alignment(out, st, stats, kind: str, single: bool, photo=None):
     return Alignment(out[0], int(st[0]), stats[0]) if single else Alignment(out, st, stats)
 
 
+def _robust_alignment(out, st, stats, photo, kind: str, single: bool):
+    out = out.reshape((-1, 3, 3) if kind == "homography" else (-1, 2, 3))
+    g, b = np.ascontiguousarray(photo[:, 0]), np.ascontiguousarray(photo[:, 1])
+    return RobustAlignment(out[0], int(st[0]), stats[0], g[0], b[0]) if single else RobustAlignment(out, st, stats, g, b)
+
+
 def refine_alignment(a, b, model, status=None, kind: str = "homography", levels: int = 3, iterations: int = 5,
-                     min_share: float = 0.25, photometric: bool = False):
+                     min_share: float = 0.25, photometric: bool = False, robust_delta: Optional[float] = None):
     """Refine step models on the pixels themselves, on the GPU: inverse-compositional Lucas-Kanade registration of frame b to
     the template a over the whole frame, coarse to fine, `iterations` Gauss-Newton updates on each of `levels` pyramid levels.
 
@@ -632,14 +648,24 @@ def refine_alignment(a, b, model, status=None, kind: str = "homography", levels:
 
     photometric=True estimates a gain and a bias with every step (b under the model looks like gain a + bias: an exposure
     change between the frames) and returns a PhotometricAlignment; a step also stops when its gain would leave (0, inf).
+
+    robust_delta (grey levels; None: the plain sum of squares) puts a Huber weight min(1, robust_delta / |residual|) on every
+    pixel, renewed on every iteration, so that an object moving on its own does not pull the fit, and returns a
+    RobustAlignment, with or without photometric; status 2 then means that the mean Huber loss grew.  4.0 is a good start:
+    the sparse tracker's max_residual default, in the same unit and with the same meaning.  stats[:, 7], the mean weight
+    under the refined model, is how to tune it: near 1.0 nothing is down-weighted, far below it the threshold cuts into the
+    static scene.  alignment_weights gives the per-pixel map.
     """
     code, L, n, ms = _oflk.check_align_params(kind, levels, iterations, min_share)
+    delta = None if robust_delta is None else _oflk.check_robust_delta(robust_delta)
     single = isinstance(a, np.ndarray) and a.ndim == 2
     fa, ua = _oflk.as_frames(a)
     fb, ub = _oflk.as_frames(b)
     if fa.shape != fb.shape or ua != ub:
         raise ValueError(f"a and b must have one shape and type, got {fa.shape} {fa.dtype} and {fb.shape} {fb.dtype}")
     m, st = _align_models(model, status, fa.shape[0], kind)
+    if delta is not None:
+        return _robust_alignment(*_oflk.align_robust_host(fa, fb, m, st, L, n, code, ms, delta, bool(photometric)), kind, single)
     if photometric:
         out, so, stats, photo = _oflk.align_host(fa, fb, m, st, L, n, code, ms, True)
         return _alignment(out, so, stats, kind, single, photo)
@@ -647,16 +673,48 @@ def refine_alignment(a, b, model, status=None, kind: str = "homography", levels:
 
 
 def sequence_refine_alignment(frames, model, status=None, kind: str = "homography", levels: int = 3, iterations: int = 5,
-                              min_share: float = 0.25, photometric: bool = False):
+                              min_share: float = 0.25, photometric: bool = False, robust_delta: Optional[float] = None):
     """refine_alignment on the T-1 steps t -> t+1 of frames (T, H, W): model[t] (e.g. of tracks_homography or tracks_motion)
     maps frame t's coordinates to frame t+1's.  Every frame's pyramid is built once.  Returns a batched Alignment, or with
-    photometric=True a batched PhotometricAlignment."""
+    photometric=True a batched PhotometricAlignment, or with robust_delta given (refine_alignment) a batched RobustAlignment."""
     code, L, n, ms = _oflk.check_align_params(kind, levels, iterations, min_share)
+    delta = None if robust_delta is None else _oflk.check_robust_delta(robust_delta)
     arr, _ = _oflk.as_frames(frames)
     if arr.shape[0] < 2:
         raise ValueError(f"a sequence needs at least two frames, got {arr.shape[0]}")
     m, st = _align_models(model, status, arr.shape[0] - 1, kind)
+    if delta is not None:
+        return _robust_alignment(*_oflk.align_robust_host(arr, None, m, st, L, n, code, ms, delta, bool(photometric)), kind, False)
     if photometric:
         out, so, stats, photo = _oflk.align_host(arr, None, m, st, L, n, code, ms, True)
         return _alignment(out, so, stats, kind, False, photo)
     return _alignment(*_oflk.align_host(arr, None, m, st, L, n, code, ms), kind, False)
+
+
+def alignment_weights(a, b, model, kind: str = "homography", robust_delta: float = 4.0, gain=None, bias=None):
+    """The Huber weights of refine_alignment(..., robust_delta=...) under `model`, per pixel and at full resolution, on the
+    GPU: (S, H, W) float32, min(1, robust_delta / |b(model x) - a(x)|) where the model lands inside b and 0 elsewhere.  Low
+    values mark what moved on its own.
+
+    a, b: (H, W) or (S, H, W), float32 or uint8, of one type; model as refine_alignment's (typically its refined output);
+    gain, bias: (S,) or scalars, both or neither -- the residual is then b(model x) - (gain a(x) + bias), as with
+    photometric=True.  The statement is in include/oflk.h (oflk_align_weights)."""
+    if not isinstance(kind, str) or kind not in _oflk.ALIGN_KINDS:
+        raise ValueError(f"kind must be one of {sorted(_oflk.ALIGN_KINDS)}, got {kind!r}")
+    delta = _oflk.check_robust_delta(robust_delta)
+    fa, ua = _oflk.as_frames(a)
+    fb, ub = _oflk.as_frames(b)
+    if fa.shape != fb.shape or ua != ub:
+        raise ValueError(f"a and b must have one shape and type, got {fa.shape} {fa.dtype} and {fb.shape} {fb.dtype}")
+    S = fa.shape[0]
+    m, _ = _align_models(model, None, S, kind)
+    if (gain is None) != (bias is None):
+        raise ValueError("gain and bias go together")
+    photo = None
+    if gain is not None:
+        photo = np.empty((S, 2), np.float32)
+        try:
+            photo[:, 0], photo[:, 1] = np.asarray(gain, np.float32), np.asarray(bias, np.float32)
+        except ValueError:
+            raise ValueError(f"gain and bias must be scalars or have shape {(S,)}, got {np.shape(gain)} and {np.shape(bias)}") from None
+    return _oflk.align_weights_host(fa, fb, m, _oflk.ALIGN_KINDS[kind], delta, photo)

@@ -32,7 +32,7 @@ import numpy.typing as npt
 import _oflk
 from lucas_kanade_core import (Alignment, Homography, MosaicChain, Motion, PhotometricAlignment, Trajectory,  # noqa: F401
                                estimate_homography, estimate_motion, exposure_chain, lucas_kanade_single_scale, mosaic_chain,
-                               mosaic_composite, refine_alignment,
+                               mosaic_composite, refine_alignment, alignment_weights,
                                rgb_to_luma, sequence_refine_alignment, stabilize_trajectory, tracks_homography, tracks_motion, warp_affine,
                                warp_perspective)
 
@@ -478,7 +478,8 @@ def lucas_kanade_pyramidal_sequence_stabilize(frames, max_corners: int, detect_e
                                               num_levels: int = 3, window_size: int = 5, num_iterations: int = 3,
                                               alpha: float = 0.01, beta: float = 0.5, max_residual: float = 4.0,
                                               refine_iterations: int = 0, refine_levels: int = 3,
-                                              order: str = "rgb", refine_photometric: bool = False) -> SequenceStabilized:
+                                              order: str = "rgb", refine_photometric: bool = False,
+                                              refine_robust_delta=None) -> SequenceStabilized:
     """Frames in, steadied frames out: lucas_kanade_pyramidal_sequence_klt_sparse_replenish on the frames, tracks_motion on
     its rows, stabilize_trajectory on the models and warp_affine of the frames under its maps, in one call whose
     intermediate rows stay in the library.  The frames go up twice, chunk by chunk (once to track, once to warp); nothing
@@ -489,7 +490,9 @@ def lucas_kanade_pyramidal_sequence_stabilize(frames, max_corners: int, detect_e
     refine_levels levels, refine_iterations iterations each) between the fit and the trajectory: every fitted step is refined
     on the pixels of its two frames, and a step that cannot be refined keeps the fitted model.  refine_photometric=True
     (needs refine_iterations > 0) refines every step together with a gain and a bias, for video whose exposure changes; the
-    stabiliser only uses the better models, the frames keep their values.
+    stabiliser only uses the better models, the frames keep their values.  refine_robust_delta (grey levels, e.g. 4.0; needs
+    refine_iterations > 0) is sequence_refine_alignment's robust_delta: Huber weights, so that an object moving through the
+    shot does not pull the refined steps.
 
     A 4-D uint8 array (T, H, W, C), C = 3 or 4, is interleaved colour video with R, G and B where `order` ("rgb" or "bgr")
     says: the motion is tracked, fitted and (with refine_iterations) refined on rgb_to_luma of the frames, exactly as this
@@ -499,6 +502,8 @@ def lucas_kanade_pyramidal_sequence_stabilize(frames, max_corners: int, detect_e
         raise ValueError(f"refine_iterations must be an integer >= 0, got {refine_iterations!r}")
     if refine_photometric and int(refine_iterations) == 0:
         raise ValueError("refine_photometric needs refine_iterations > 0")
+    if refine_robust_delta is not None and int(refine_iterations) == 0:
+        raise ValueError("refine_robust_delta needs refine_iterations > 0")
     colour = _oflk.is_packed(frames)
     code_order = _oflk.check_colour_order(order)
     if colour:
@@ -510,7 +515,7 @@ def lucas_kanade_pyramidal_sequence_stabilize(frames, max_corners: int, detect_e
         fit = tracks_motion(rows.tracks, rows.visible, rows.born, model, hypotheses, threshold, seed)
         arr, _ = _oflk.as_sequence(grey)
         al = sequence_refine_alignment(arr, fit.model, fit.status, "affine", refine_levels, int(refine_iterations),
-                                       photometric=bool(refine_photometric))
+                                       photometric=bool(refine_photometric), robust_delta=refine_robust_delta)
         tr = stabilize_trajectory(al.model, fit.status, radius, sigma)
         return SequenceStabilized(warp_affine(packed if colour else arr, tr.map), tr.correction, al.model, fit.status, tr.held)
     a, b = _oflk.check_fb_params(alpha, beta)
@@ -612,13 +617,16 @@ def lucas_kanade_pyramidal_sequence_stabilize_nv12(frames, max_corners: int, det
                                                    num_levels: int = 3, window_size: int = 5, num_iterations: int = 3,
                                                    alpha: float = 0.01, beta: float = 0.5, max_residual: float = 4.0,
                                                    refine_iterations: int = 0, refine_levels: int = 3,
-                                                   siting: str = "left") -> SequenceStabilized:
+                                                   siting: str = "left", refine_robust_delta=None) -> SequenceStabilized:
     """lucas_kanade_pyramidal_sequence_stabilize for NV12 video, frames (T, 3H/2, W) uint8 (nv12_from_planes): the motion is
     tracked, fitted and (with refine_iterations) refined on the Y planes, exactly as that call does on them, and the NV12
     frames are warped under the maps of that trajectory by warp_affine_nv12, the chroma sited as `siting` says.  .frames has
-    the input's shape.  No conversion and no luma pass: the Y plane is the frame's first H W bytes."""
+    the input's shape.  No conversion and no luma pass: the Y plane is the frame's first H W bytes.  refine_robust_delta (needs
+    refine_iterations > 0) is sequence_refine_alignment's robust_delta, as in that call."""
     if isinstance(refine_iterations, bool) or int(refine_iterations) != refine_iterations or int(refine_iterations) < 0:
         raise ValueError(f"refine_iterations must be an integer >= 0, got {refine_iterations!r}")
+    if refine_robust_delta is not None and int(refine_iterations) == 0:
+        raise ValueError("refine_robust_delta needs refine_iterations > 0")
     code_siting = _oflk.check_nv12_siting(siting)
     arr = _oflk.as_nv12(frames, "(T, 3H/2, W)")
     T, R, W = arr.shape
@@ -630,7 +638,8 @@ def lucas_kanade_pyramidal_sequence_stabilize_nv12(frames, max_corners: int, det
         rows = lucas_kanade_pyramidal_sequence_klt_sparse_replenish(grey, max_corners, detect_every, quality_level, min_distance,
                                                                     num_levels, window_size, num_iterations, alpha, beta, max_residual)
         fit = tracks_motion(rows.tracks, rows.visible, rows.born, model, hypotheses, threshold, seed)
-        al = sequence_refine_alignment(grey, fit.model, fit.status, "affine", refine_levels, int(refine_iterations))
+        al = sequence_refine_alignment(grey, fit.model, fit.status, "affine", refine_levels, int(refine_iterations),
+                                       robust_delta=refine_robust_delta)
         tr = stabilize_trajectory(al.model, fit.status, radius, sigma)
         return SequenceStabilized(warp_affine_nv12(arr, tr.map, siting), tr.correction, al.model, fit.status, tr.held)
     a, b = _oflk.check_fb_params(alpha, beta)
@@ -681,7 +690,7 @@ def lucas_kanade_pyramidal_sequence_mosaic(frames, max_corners: int = 1000, dete
                                            num_iterations: int = 3, alpha: float = 0.01, beta: float = 0.5, max_residual: float = 4.0,
                                            anchor: int = 0, extent=None, blend: str = "feather", max_pixels=None,
                                            refine_iterations: int = 0, refine_levels: int = 3, order: str = "rgb",
-                                           refine_photometric: bool = False):
+                                           refine_photometric: bool = False, refine_robust_delta=None):
     """Frames in, one picture out: lucas_kanade_pyramidal_sequence_klt_sparse_replenish on the frames, tracks_homography on its
     rows, mosaic_chain from frame `anchor`, and mosaic_composite of every frame that is not dropped, in one call whose
     intermediate rows stay in the library.  The frames go up twice, chunk by chunk (once to track, once to blend).  The canvas
@@ -697,6 +706,10 @@ def lucas_kanade_pyramidal_sequence_mosaic(frames, max_corners: int = 1000, dete
     (a step that was not refined counts as no change), and every frame enters the blend at the anchor's exposure
     (mosaic_composite(..., exposure=...)).  Returns a PhotometricMosaic: Mosaic's fields and .exposure.
 
+    refine_robust_delta (grey levels, e.g. 4.0; needs refine_iterations > 0) is sequence_refine_alignment's robust_delta, with
+    or without refine_photometric: Huber weights, so that an object moving through the shot does not pull the refined steps.
+    The blend itself is not masked by the weights.
+
     A 4-D uint8 array (T, H, W, C), C = 3 or 4, is interleaved colour video (`order`: "rgb" or "bgr"): this call runs on
     rgb_to_luma of the frames for everything but the canvas, and every channel's plane is then blended by mosaic_composite
     under the chain fitted on the luma; .canvas is (Hc, Wc, C), .count the grey call's."""
@@ -704,13 +717,15 @@ def lucas_kanade_pyramidal_sequence_mosaic(frames, max_corners: int = 1000, dete
         raise ValueError(f"refine_iterations must be an integer >= 0, got {refine_iterations!r}")
     if refine_photometric and int(refine_iterations) == 0:
         raise ValueError("refine_photometric needs refine_iterations > 0")
+    if refine_robust_delta is not None and int(refine_iterations) == 0:
+        raise ValueError("refine_robust_delta needs refine_iterations > 0")
     _oflk.check_colour_order(order)
     if _oflk.is_packed(frames):
         packed = _oflk.as_packed(frames, "(T, H, W, C)")
         m = lucas_kanade_pyramidal_sequence_mosaic(rgb_to_luma(packed, order), max_corners, detect_every, hypotheses, threshold, seed,
                                                    quality_level, min_distance, num_levels, window_size, num_iterations, alpha, beta,
                                                    max_residual, anchor, extent, blend, max_pixels, refine_iterations, refine_levels,
-                                                   refine_photometric=refine_photometric)
+                                                   refine_photometric=refine_photometric, refine_robust_delta=refine_robust_delta)
         ch = mosaic_chain(m.model, m.status, packed.shape[1:3], anchor, extent)
         canvas = mosaic_composite(packed, ch.from_anchor, m.canvas.shape, m.origin, ch.dropped, blend,
                                   exposure=m.exposure if refine_photometric else None)
@@ -721,7 +736,7 @@ def lucas_kanade_pyramidal_sequence_mosaic(frames, max_corners: int = 1000, dete
         fit = tracks_homography(rows.tracks, rows.visible, rows.born, hypotheses, threshold, seed)
         arr, _ = _oflk.as_sequence(frames)
         al = sequence_refine_alignment(arr, fit.model, fit.status, "homography", refine_levels, int(refine_iterations),
-                                       photometric=bool(refine_photometric))
+                                       photometric=bool(refine_photometric), robust_delta=refine_robust_delta)
         ch = mosaic_chain(al.model, fit.status, arr.shape[1:], anchor, extent)
         Hc, Wc = ch.canvas_shape
         cap = 16 * arr.shape[1] * arr.shape[2] if max_pixels is None else max_pixels

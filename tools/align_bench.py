@@ -11,6 +11,9 @@ each with the median and min - max over `--steps` windows of `--reps` back-to-ba
   warp        oflk_warp_perspective of the same S images under the same maps: the nearest existing kernel
   photometric the same measurement of oflk_align_refine_photo (k_align_reduce_photo and k_align_update_photo) and of the plain call
               in one process on the same steps, and their ratio.  uint8 and float32 frames, affine and homography
+  robust      the same measurement of the four forms in one process on the same steps: plain, photometric, robust
+              (oflk_align_refine_robust, k_align_reduce_robust and k_align_update_robust, --delta grey levels) and robust +
+              photometric, and the ratios of the robust forms over their bases.  uint8 and float32 frames, affine and homography
   accumulate  oflk_mosaic_accumulate and oflk_mosaic_accumulate_exposure of 32 frames of 1080p, 8 px apart, onto one canvas, mean
               and feather blends, uint8 and float32 frames, and their ratio
   sequence    the whole oflk_align_sequence (pyramids, L = 3, n = 5, both residual passes) on T = 129 resident uint8 frames,
@@ -19,7 +22,7 @@ each with the median and min - max over `--steps` windows of `--reps` back-to-ba
               refine_iterations = 0 and 5: the price of the refinement in the chain it joins, and the mean absolute difference
               between the mosaic and the image the frames were cut from (the scene of tests/test_gpu_mosaic.py's pan)
 
-    python tools/align_bench.py [--steps 5] [--reps 2] [--S 128] [--limit 240]
+    python tools/align_bench.py [--steps 5] [--reps 2] [--S 128] [--limit 240] [--delta 4.0]
 """
 import argparse
 import json
@@ -171,19 +174,19 @@ def leg(args):
     nc = 9 if code else 6
     m0 = [1, 0, -0.5, 0, 1, 0.3, 0, 0, 1][:nc]   # the truth is (-1, 0)
     model = torch.tensor(m0, dtype=torch.float32, device=d).repeat(S, 1).contiguous()
-    mo, so, ss = torch.empty_like(model), torch.empty(S, dtype=torch.int32, device=d), torch.empty((S, 4), dtype=torch.float64, device=d)
+    mo, so, ss = torch.empty_like(model), torch.empty(S, dtype=torch.int32, device=d), torch.empty((S, 8), dtype=torch.float64, device=d)
     po = torch.empty((S, 2), dtype=torch.float32, device=d)
 
-    def iteration(photo):
-        """(ms per iteration, the two windows' results) of the plain or the photometric call"""
-        nbytes = _oflk.align_workspace(S, H, W, 1, code, photo)
+    def iteration(photo, delta=None):
+        """(ms per iteration, the two windows' results) of the plain or the photometric call, or with delta of their robust forms"""
+        nbytes = _oflk.align_workspace(S, H, W, 1, code, photo, robust=delta is not None)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=d)
         res = {}
         for n in (2, 6):
             res[n] = windows(lambda: _oflk.align_refine(a.data_ptr(), b.data_ptr(), S, H, W, 1, n, code, 0.25, model.data_ptr(), 0, ws.data_ptr(),
                                                         nbytes, mo.data_ptr(), so.data_ptr(), ss.data_ptr(), u8, st,
-                                                        po.data_ptr() if photo else None), args.steps, args.reps)
-            accepted = ss[:, 3].cpu().numpy()
+                                                        po.data_ptr() if photo else None, delta), args.steps, args.reps)
+            accepted = ss.view(-1)[:S * (8 if delta is not None else 4)].view(S, -1)[:, 3].cpu().numpy()
             assert (accepted == n).all(), f"not every iteration was accepted: {accepted}"
         return (res[6][0] - res[2][0]) / 4.0, res
 
@@ -197,6 +200,18 @@ def leg(args):
                     "photo_ms_min_max_n6": pres[6][1], "photo_ms_per_iteration": round(pper, 3),
                     "photo_ns_per_pixel": round(pper * 1e6 / (S * H * W), 4), "photo_status_1": int((so == 1).sum().item()),
                     "photo_over_plain": round(pper / per, 3)})
+    if args.leg == "robust":
+        pper, pres = iteration(True)
+        rper, rres = iteration(False, args.delta)
+        weight = float(ss[:, 7].mean().item())
+        qper, qres = iteration(True, args.delta)
+        for name, x, r in (("photo", pper, pres), ("robust", rper, rres), ("robust_photo", qper, qres)):
+            row.update({f"{name}_ms_n2": round(r[2][0], 3), f"{name}_ms_n6": round(r[6][0], 3), f"{name}_ms_min_max_n2": r[2][1],
+                        f"{name}_ms_min_max_n6": r[6][1], f"{name}_ms_per_iteration": round(x, 3),
+                        f"{name}_ns_per_pixel": round(x * 1e6 / (S * H * W), 4)})
+        row.update({"photo_over_plain": round(pper / per, 3), "robust_over_plain": round(rper / per, 3),
+                    "robust_photo_over_photo": round(qper / pper, 3), "robust_delta": args.delta,
+                    "robust_mean_weight": round(weight, 4)})
     print(json.dumps(row), flush=True)
 
 
@@ -206,9 +221,10 @@ def main():
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--S", type=int, default=128)
     ap.add_argument("--limit", type=int, default=240, help="seconds a leg may take")
-    ap.add_argument("--leg", choices=["iteration", "photometric", "accumulate", "copy", "warp", "sequence", "chain"], help="run this one leg in this process")
+    ap.add_argument("--leg", choices=["iteration", "photometric", "robust", "accumulate", "copy", "warp", "sequence", "chain"], help="run this one leg in this process")
     ap.add_argument("--dtype", choices=["u8", "f32"], default="u8")
     ap.add_argument("--kind", choices=sorted(KINDS), default="homography")
+    ap.add_argument("--delta", type=float, default=4.0, help="robust_delta of the robust leg, grey levels")
     ap.add_argument("--only", help="comma-separated legs: run these alone")
     args = ap.parse_args()
     if args.leg:
@@ -218,6 +234,7 @@ def main():
         return 0
     legs = [("iteration", dt, k) for dt in ("u8", "f32") for k in ("homography", "affine")]
     legs += [("photometric", dt, k) for dt in ("u8", "f32") for k in ("homography", "affine")]
+    legs += [("robust", dt, k) for dt in ("u8", "f32") for k in ("homography", "affine")]
     legs += [("accumulate", dt, "homography") for dt in ("u8", "f32")]
     legs += [("copy", dt, "homography") for dt in ("u8", "f32")] + [("warp", dt, "homography") for dt in ("u8", "f32")]
     legs += [("sequence", "u8", "homography"), ("chain", "u8", "homography")]
@@ -225,7 +242,7 @@ def main():
         legs = [x for x in legs if x[0] in args.only.split(",")]
     for lg, dt, kind in legs:
         cmd = [sys.executable, __file__, "--leg", lg, "--dtype", dt, "--kind", kind, "--steps", str(args.steps), "--reps", str(args.reps),
-               "--S", str(args.S)]
+               "--S", str(args.S), "--delta", str(args.delta)]
         try:
             rc = subprocess.run(cmd, timeout=args.limit).returncode
         except subprocess.TimeoutExpired:

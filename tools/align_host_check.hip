@@ -148,6 +148,77 @@ int main()
     EXPECT(oflk_align_refine_photo_host_u8(u, u, 1, 32, 40, 2, 0, A, 0.25f, fm, nullptr, fm, im, dm, fm) == OFLK_ERR_INVALID);
     EXPECT(oflk_align_sequence_photo_host(fm, 1, 32, 40, 2, 1, P, 0.25f, fm, nullptr, fm, im, dm, fm) == OFLK_ERR_INVALID);
     EXPECT(oflk_align_sequence_photo_host_u8(u, 2, 32, 40, 2, 1, P, 0.25f, fm, nullptr, fm, im, dm, nullptr) == OFLK_ERR_INVALID);
+    // the robust forms: two more sums per tile and the first pass's two values behind everything else, the base forms' refusals,
+    // a delta that is not finite and positive, photometric without its output; the weight map's refusals
+    for (int model : {A, P})
+        for (int ph : {0, 1}) {
+            size_t base = 0, robust = 0;
+            EXPECT((ph ? oflk_align_photo_workspace(3, 70, 257, 3, model, &base) : oflk_align_workspace(3, 70, 257, 3, model, &base)) == OFLK_OK);
+            EXPECT(oflk_align_robust_workspace(3, 70, 257, 3, model, ph, &robust) == OFLK_OK && robust > base && robust % 256 == 0);
+            int dims[2 * OFLK_MAX_LEVELS];
+            EXPECT(check_align(3, 70, 257, 3, 1, model, 0.25f, dims) == OFLK_OK);
+            char *b = reinterpret_cast<char *>(g_buf);
+            const AlignWs ws = align_ws(b, 3, 3, dims, model, ph != 0, true);
+            const size_t ns = (size_t)align_sums((model == P ? 8 : 6) + (ph ? 2 : 0)) + 2;
+            EXPECT(ws.bytes == robust && ws.pstride == 3u * 5u * ns && align_nsums(model, ph != 0, true) == (int)ns);
+            EXPECT(ns == (size_t)(model == P ? (ph ? 69 : 48) : (ph ? 48 : 31)));
+            EXPECT((ws.photo != nullptr) == (ph != 0));
+            EXPECT(reinterpret_cast<const char *>(ws.first) >= reinterpret_cast<const char *>(ws.pyr[1]) && aligned(ws.first, 256));
+            EXPECT(!ph || reinterpret_cast<const char *>(ws.first) >= reinterpret_cast<const char *>(ws.photo) + 2 * 3 * sizeof(double));
+            EXPECT(reinterpret_cast<const char *>(ws.first) + 2 * 3 * sizeof(double) <= b + ws.bytes);
+            EXPECT(align_ws(b, 3, 3, dims, model, ph != 0).first == nullptr);
+        }
+    EXPECT(oflk_align_robust_workspace(2, 32, 40, 2, P, 0, nullptr) == OFLK_ERR_INVALID);
+    EXPECT(oflk_align_robust_workspace(0, 32, 40, 2, P, 0, &n) == OFLK_ERR_INVALID && n == 0);
+    EXPECT(oflk_align_robust_workspace(2, 32, 40, 4, P, 1, &n) == OFLK_ERR_UNSUPPORTED);
+    {
+        const float inf = std::numeric_limits<float>::infinity();
+        size_t np = 0;
+        EXPECT(oflk_align_robust_workspace(2, 32, 40, 2, P, 0, &n) == OFLK_OK && oflk_align_robust_workspace(2, 32, 40, 2, P, 1, &np) == OFLK_OK);
+        auto robust = [&](const void *a, int S, int it, float delta, int ph, void *ws, size_t bytes, float *mo, float *po) {
+            return oflk_align_refine_robust(a, d, 0, S, 32, 40, 2, it, P, 0.25f, delta, ph, fm, nullptr, ws, bytes, mo, im, dm, po, nullptr);
+        };
+        for (float delta : {0.0f, -4.0f, nan, inf, -inf}) {
+            EXPECT(robust(d, 2, 1, delta, 0, d, n, fm, nullptr) == OFLK_ERR_INVALID);
+            EXPECT(std::string(oflk_last_error()).find("robust_delta") != std::string::npos);
+            EXPECT(robust(d, 2, 1, delta, 1, d, np, fm, fm) == OFLK_ERR_INVALID);
+            EXPECT(oflk_align_sequence_robust(d, 1, 3, 32, 40, 2, 1, P, 0.25f, delta, 0, fm, nullptr, d, n, fm, im, dm, nullptr, nullptr) == OFLK_ERR_INVALID);
+            EXPECT(oflk_align_refine_robust_host(fm, fm, 1, 32, 40, 2, 1, P, 0.25f, delta, 0, fm, nullptr, fm, im, dm, nullptr) == OFLK_ERR_INVALID);
+            EXPECT(oflk_align_refine_robust_host_u8(u, u, 1, 32, 40, 2, 1, A, 0.25f, delta, 1, fm, nullptr, fm, im, dm, fm) == OFLK_ERR_INVALID);
+            EXPECT(oflk_align_sequence_robust_host(fm, 2, 32, 40, 2, 1, P, 0.25f, delta, 0, fm, nullptr, fm, im, dm, nullptr) == OFLK_ERR_INVALID);
+            EXPECT(oflk_align_sequence_robust_host_u8(u, 2, 32, 40, 2, 1, P, 0.25f, delta, 0, fm, nullptr, fm, im, dm, nullptr) == OFLK_ERR_INVALID);
+            EXPECT(oflk_align_weights(d, d, 0, 2, 32, 40, P, delta, fm, nullptr, fm, nullptr) == OFLK_ERR_INVALID);
+            EXPECT(oflk_align_weights_host(fm, fm, 2, 32, 40, P, delta, fm, nullptr, fm) == OFLK_ERR_INVALID);
+            EXPECT(oflk_align_weights_host_u8(u, u, 2, 32, 40, A, delta, fm, fm, fm) == OFLK_ERR_INVALID);
+        }
+        EXPECT(robust(d, 0, 1, 4.0f, 0, d, n, fm, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(robust(d, 2, 0, 4.0f, 0, d, n, fm, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(robust(nullptr, 2, 1, 4.0f, 0, d, n, fm, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(robust(d, 2, 1, 4.0f, 0, d, n, nullptr, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(robust(d, 2, 1, 4.0f, 0, d, n - 1, fm, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(robust(d, 2, 1, 4.0f, 1, d, np - 1, fm, fm) == OFLK_ERR_INVALID);
+        EXPECT(robust(d, 2, 1, 4.0f, 1, d, np, fm, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(std::string(oflk_last_error()).find("d_photo_out") != std::string::npos);
+        EXPECT(robust(d, 2, 1, 4.0f, 1, d, np, fm, reinterpret_cast<float *>(g_buf + 2)) == OFLK_ERR_INVALID);
+        EXPECT(oflk_align_sequence_robust(d, 1, 1, 32, 40, 2, 1, P, 0.25f, 4.0f, 0, fm, nullptr, d, n, fm, im, dm, nullptr, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_align_sequence_robust(d, 1, 3, 32, 40, 2, 1, P, 0.25f, 4.0f, 1, fm, nullptr, d, np, fm, im, dm, nullptr, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_align_refine_robust_host(fm, fm, 1, 32, 40, 2, 1, P, 0.25f, 4.0f, 1, fm, nullptr, fm, im, dm, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_align_refine_robust_host(fm, fm, 0, 32, 40, 2, 1, P, 0.25f, 4.0f, 0, fm, nullptr, fm, im, dm, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_align_sequence_robust_host_u8(u, 1, 32, 40, 2, 1, P, 0.25f, 4.0f, 0, fm, nullptr, fm, im, dm, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_align_sequence_robust_host(fm, 2, 32, 40, 4, 1, P, 0.25f, 4.0f, 0, fm, nullptr, fm, im, dm, nullptr) == OFLK_ERR_UNSUPPORTED);
+        EXPECT(oflk_align_weights(d, d, 0, 0, 32, 40, P, 4.0f, fm, nullptr, fm, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_align_weights(d, d, 0, 2, 0, 40, P, 4.0f, fm, nullptr, fm, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_align_weights(d, d, 0, 2, 32, 40, 2, 4.0f, fm, nullptr, fm, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_align_weights(nullptr, d, 0, 2, 32, 40, P, 4.0f, fm, nullptr, fm, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_align_weights(d, d, 0, 2, 32, 40, P, 4.0f, nullptr, nullptr, fm, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_align_weights(d, d, 0, 2, 32, 40, P, 4.0f, fm, nullptr, nullptr, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_align_weights(g_buf + 1, d, 0, 2, 32, 40, P, 4.0f, fm, nullptr, fm, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_align_weights(d, d, 1, 2, 32, 40, P, 4.0f, fm, reinterpret_cast<float *>(g_buf + 2), fm, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_align_weights(d, d, 0, 2, 1 << 15, 1 << 15, P, 4.0f, fm, nullptr, fm, nullptr) == OFLK_ERR_UNSUPPORTED);
+        EXPECT(oflk_align_weights_host(nullptr, fm, 2, 32, 40, P, 4.0f, fm, nullptr, fm) == OFLK_ERR_INVALID);
+        EXPECT(oflk_align_weights_host(fm, fm, 2, 32, 40, P, 4.0f, fm, nullptr, nullptr) == OFLK_ERR_INVALID);
+        EXPECT(oflk_align_weights_host_u8(u, u, 0, 32, 40, P, 4.0f, fm, nullptr, fm) == OFLK_ERR_INVALID);
+    }
     // the exposure chain is host code: its refusals, a held step, and forwards against backwards
     {
         const float ph[3][2] = {{2.0f, 4.0f}, {-1.0f, 7.0f}, {0.5f, -1.0f}};

@@ -4861,7 +4861,7 @@ namespace {
 int align_coefficients(int model) { return model == OFLK_ALIGN_HOMOGRAPHY ? 9 : 6; }
 int align_nsums(int model, bool photo = false, bool robust = false)
 {
-    return align_sums((model == OFLK_ALIGN_HOMOGRAPHY ? 8 : 6) + (photo ? 2 : 0)) + (robust ? 2 : 0);
+    return align_sums(model == OFLK_ALIGN_HOMOGRAPHY ? 8 : 6, photo, robust);
 }
 int align_tiles(int h, int w) { return ((w + kAlignTileW - 1) / kAlignTileW) * ((h + kAlignTileH - 1) / kAlignTileH); }
 
@@ -4940,21 +4940,17 @@ int check_align_device(const void *d_a, const void *d_b, int u8, const void *d_m
     return OFLK_OK;
 }
 
-// photo: NULL, or the steps' (g, b) of the photometric form.  delta > 0: the robust form
+// r.photo: NULL, or the steps' (g, b) of the photometric form.  r.delta > 0: the robust form
 template <class PIX, int NP>
-int align_reduce_launch(const AlignReduceArgs &r, int tiles, hipStream_t s, const double *photo = nullptr, double delta = 0.0)
+int align_reduce_launch(const AlignReduceArgs &r, int tiles, hipStream_t s)
 {
     const dim3 grid((unsigned)tiles, (unsigned)std::min(r.S, 65535));
-    if (delta > 0.0 && photo)
-        hipLaunchKernelGGL((k_align_reduce_robust<PIX, NP, true>), grid, dim3(64 * align_robust_waves(NP, true)), 0, s,
-                           AlignRobustReduceArgs{r, photo, delta});
-    else if (delta > 0.0)
-        hipLaunchKernelGGL((k_align_reduce_robust<PIX, NP, false>), grid, dim3(64 * align_robust_waves(NP, false)), 0, s,
-                           AlignRobustReduceArgs{r, nullptr, delta});
-    else if (photo)
-        hipLaunchKernelGGL((k_align_reduce_photo<PIX, NP>), grid, dim3(64 * align_photo_waves(NP)), 0, s, AlignPhotoReduceArgs{r, photo});
-    else
-        hipLaunchKernelGGL((k_align_reduce<PIX, NP>), grid, dim3(64), 0, s, r);
+    with_bool(r.photo != nullptr, [&](auto PHOTO) {
+        with_bool(r.delta > 0.0, [&](auto ROBUST) {
+            constexpr bool photo = decltype(PHOTO)::value;
+            hipLaunchKernelGGL((k_align_reduce<PIX, NP, photo, decltype(ROBUST)::value>), grid, dim3(64 * align_waves(NP, photo)), 0, s, r);
+        });
+    });
     HIP_TRY(hipGetLastError());
     return OFLK_OK;
 }
@@ -5009,16 +5005,17 @@ int align_launch(const PIX *d_a, const PIX *d_b, int nimg, int S, int H, int W, 
         r.H = h; r.W = w; r.tiles_x = (w + kAlignTileW - 1) / kAlignTileW; r.S = S;
         r.skip_frozen = mode == kAlignIterate;
         r.state = ws.state; r.partial = ws.partial; r.pstride = ws.pstride;
+        r.photo = photo; r.delta = delta;
         const int tiles = align_tiles(h, w);
         int rc2;
         if (l == levels - 1) {
             r.a = d_a;
             r.b = d_b;
-            rc2 = align_reduce_launch<PIX, NP>(r, tiles, s, photo, delta);
+            rc2 = align_reduce_launch<PIX, NP>(r, tiles, s);
         } else {
             r.a = ws.pyr[l];
             r.b = ws.pyr[l] + (seq ? 1 : (size_t)S) * r.stride;
-            rc2 = align_reduce_launch<float, NP>(r, tiles, s, photo, delta);
+            rc2 = align_reduce_launch<float, NP>(r, tiles, s);
         }
         if (rc2) return rc2;
         AlignUpdateArgs u{};
@@ -5032,17 +5029,13 @@ int align_launch(const PIX *d_a, const PIX *d_b, int nimg, int S, int H, int W, 
         }
         u.min_count = (double)min_share * (double)((long long)w * (long long)h);
         u.model_in = d_model_in; u.model_out = d_model_out; u.status_out = d_status_out; u.stats = d_stats;
-        if (delta > 0.0 && photo)
-            hipLaunchKernelGGL((k_align_update_robust<NP, true>), dim3((unsigned)std::min(S, 65535)), dim3(64), 0, s,
-                               AlignRobustUpdateArgs{u, ws.photo, d_photo_out, ws.first});
-        else if (delta > 0.0)
-            hipLaunchKernelGGL((k_align_update_robust<NP, false>), dim3((unsigned)std::min(S, 65535)), dim3(64), 0, s,
-                               AlignRobustUpdateArgs{u, nullptr, nullptr, ws.first});
-        else if (photo)
-            hipLaunchKernelGGL((k_align_update_photo<NP>), dim3((unsigned)std::min(S, 65535)), dim3(64), 0, s,
-                               AlignPhotoUpdateArgs{u, ws.photo, d_photo_out});
-        else
-            hipLaunchKernelGGL((k_align_update<NP>), dim3((unsigned)std::min(S, 65535)), dim3(64), 0, s, u);
+        u.photo = photo ? ws.photo : nullptr; u.photo_out = d_photo_out; u.first = ws.first;
+        with_bool(photo != nullptr, [&](auto PHOTO) {
+            with_bool(delta > 0.0, [&](auto ROBUST) {
+                hipLaunchKernelGGL((k_align_update<NP, decltype(PHOTO)::value, decltype(ROBUST)::value>), dim3((unsigned)std::min(S, 65535)),
+                                   dim3(64), 0, s, u);
+            });
+        });
         HIP_TRY(hipGetLastError());
         return OFLK_OK;
     };

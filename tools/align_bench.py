@@ -9,10 +9,10 @@ each with the median and min - max over `--steps` windows of `--reps` back-to-ba
               truth, so that every iteration is accepted and none freezes
   copy        a device copy of the bytes an iteration must read (the S templates and the S images), uint8 and float32
   warp        oflk_warp_perspective of the same S images under the same maps: the nearest existing kernel
-  photometric the same measurement of oflk_align_refine_photo (k_align_reduce_photo and k_align_update_photo) and of the plain call
+  photometric the same measurement of oflk_align_refine_photo (the kernels' PHOTO instantiations) and of the plain call
               in one process on the same steps, and their ratio.  uint8 and float32 frames, affine and homography
   robust      the same measurement of the four forms in one process on the same steps: plain, photometric, robust
-              (oflk_align_refine_robust, k_align_reduce_robust and k_align_update_robust, --delta grey levels) and robust +
+              (oflk_align_refine_robust, the kernels' ROBUST instantiations, --delta grey levels) and robust +
               photometric, and the ratios of the robust forms over their bases.  uint8 and float32 frames, affine and homography
   accumulate  oflk_mosaic_accumulate and oflk_mosaic_accumulate_exposure of 32 frames of 1080p, 8 px apart, onto one canvas, mean
               and feather blends, uint8 and float32 frames, and their ratio

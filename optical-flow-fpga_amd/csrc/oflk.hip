@@ -3553,7 +3553,7 @@ OFLK_API int oflk_plan_sparse_klt_replenish(oflk_plan *plan, const void *d_frame
 }
 
 // =============================================================================
-// global motion from correspondences: RANSAC and refit (oflk_motion.hpp)
+// global motion from correspondences: RANSAC and refit, four models (oflk_motion.hpp, oflk_homography.hpp)
 // =============================================================================
 namespace {
 // The workspace of the fit, 256-byte aligned pieces: M [S], the compacted correspondences [S][N], score [S][Hn] and the
@@ -3605,26 +3605,34 @@ int check_motion_shape(int S, int N)
     return OFLK_OK;
 }
 
-int check_motion_workspace(const void *ws, size_t bytes, int S, int N, int Hn, int nc = 6)
+int check_motion_workspace(const void *ws, size_t bytes, int S, int N, int Hn, int model)
 {
     if (!ws) return fail(OFLK_ERR_INVALID, "NULL workspace");
-    const size_t need = motion_ws(nullptr, S, N, Hn, nc).bytes;
+    const size_t need = motion_ws(nullptr, S, N, Hn, motion_coeffs(model)).bytes;
     if (bytes < need)
         return fail(OFLK_ERR_INVALID, "workspace of %zu bytes, %zu needed (%s)", bytes, need,
-                    nc == 6 ? "oflk_motion_workspace" : "oflk_homography_workspace");
+                    model == kMotionHomography ? "oflk_homography_workspace" : "oflk_motion_workspace");
     if (!aligned(ws, 256)) return fail(OFLK_ERR_INVALID, "d_workspace must be 256-byte aligned");
     return OFLK_OK;
 }
 
-// The three launches of S steps on stream s; the arguments are checked.  Step s reads src / dst / va / vb / born at
-// [s][N]: NULL masks do not decide.
+// What a step reads, at [s][N]: NULL masks do not decide.
 struct MotionIn {
     const float *src, *dst;
     const unsigned char *va, *vb, *born;
 };
 
-MotionArgs motion_args(const MotionIn &in, int S, int N, unsigned index0, int Hn, float threshold, unsigned seed, const MotionWs &ws,
-                       float *d_model, unsigned char *d_inlier, int *d_counts)
+// the T-1 steps of [T][K] track arrays: row t+1 of an array is row t of the array that begins K elements later, so one
+// stride serves every input
+MotionIn motion_rows(const float *d_tracks, const unsigned char *d_visible, const unsigned char *d_born, int K)
+{
+    return {d_tracks, d_tracks + 2 * (size_t)K, d_visible, d_visible + (size_t)K, d_born ? d_born + (size_t)K : nullptr};
+}
+
+// The three launches of S steps on stream s; the arguments are checked.  `model` is an internal code (kMotionTranslation ..
+// kMotionHomography); ws is motion_ws with its motion_coeffs(model) coefficients per model, as is d_model [S][coeffs]
+int motion_launch(const MotionIn &in, int S, int N, unsigned index0, int model, int Hn, float threshold, unsigned seed,
+                  const MotionWs &ws, float *d_model, unsigned char *d_inlier, int *d_counts, hipStream_t s)
 {
     MotionArgs a{};
     a.src = reinterpret_cast<const float2 *>(in.src);
@@ -3635,18 +3643,11 @@ MotionArgs motion_args(const MotionIn &in, int S, int N, unsigned index0, int Hn
     a.thr2 = threshold * threshold;
     a.M = ws.M; a.pts = ws.pts; a.score = ws.score; a.hmodel = ws.hmodel;
     a.model = d_model; a.inlier = d_inlier; a.counts = d_counts;
-    return a;
-}
-
-int motion_launch(const MotionIn &in, int S, int N, unsigned index0, int model, int Hn, float threshold, unsigned seed,
-                  const MotionWs &ws, float *d_model, unsigned char *d_inlier, int *d_counts, hipStream_t s)
-{
-    const MotionArgs a = motion_args(in, S, N, index0, Hn, threshold, seed, ws, d_model, d_inlier, d_counts);
     const unsigned steps = (unsigned)std::min(S, 65535);
     hipLaunchKernelGGL(k_motion_compact, dim3(steps), dim3(kMotionCompact), 0, s, a);
     HIP_TRY(hipGetLastError());
     const dim3 grid((unsigned)((Hn + kMotionWaves - 1) / kMotionWaves), steps);
-    const bool built = with_int<kMotionTranslation, kMotionSimilarity, kMotionAffine>(model, [&](auto MODEL) {
+    const bool built = with_int<kMotionTranslation, kMotionSimilarity, kMotionAffine, kMotionHomography>(model, [&](auto MODEL) {
         hipLaunchKernelGGL(k_motion_score<decltype(MODEL)::value>, grid, dim3(64 * kMotionWaves), 0, s, a);
         hipLaunchKernelGGL(k_motion_refit<decltype(MODEL)::value>, dim3(steps), dim3(kMotionLanes), 0, s, a);
     });
@@ -3655,68 +3656,71 @@ int motion_launch(const MotionIn &in, int S, int N, unsigned index0, int model, 
     return OFLK_OK;
 }
 
-// The homography fit's three launches (oflk_homography.hpp): the motion fit's compaction, then nine coefficients per model
-// in ws (motion_ws with nc = 9) and in d_model [S][9]
-int homography_launch(const MotionIn &in, int S, int N, unsigned index0, int Hn, float threshold, unsigned seed, const MotionWs &ws,
-                      float *d_model, unsigned char *d_inlier, int *d_counts, hipStream_t s)
-{
-    const MotionArgs a = motion_args(in, S, N, index0, Hn, threshold, seed, ws, d_model, d_inlier, d_counts);
-    const unsigned steps = (unsigned)std::min(S, 65535);
-    hipLaunchKernelGGL(k_motion_compact, dim3(steps), dim3(kMotionCompact), 0, s, a);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_homog_score, dim3((unsigned)((Hn + kMotionWaves - 1) / kMotionWaves), steps), dim3(64 * kMotionWaves), 0, s, a);
-    hipLaunchKernelGGL(k_homog_refit, dim3(steps), dim3(kMotionLanes), 0, s, a);
-    HIP_TRY(hipGetLastError());
-    return OFLK_OK;
-}
-}  // namespace
+// The fit an entry point asks for.  The motion fit's entry points pass their `model` argument on, and the values
+// check_motion accepts are internal codes as they stand; the homography's have no such argument
+struct FitKind {
+    bool homography;
+    int model;
+    int code() const { return homography ? kMotionHomography : model; }
+    int check(int hypotheses, float threshold) const
+    {
+        return homography ? check_ransac(hypotheses, threshold) : check_motion(model, hypotheses, threshold);
+    }
+};
+constexpr FitKind kHomographyFit{true, 0};
 
-OFLK_API int oflk_motion_workspace(int S, int N, int hypotheses, size_t *bytes)
+// ---- one body for each form of an entry point ----
+int fit_workspace(int model, int S, int N, int hypotheses, size_t *bytes)
 {
     if (!bytes) return fail(OFLK_ERR_INVALID, "NULL bytes");
     int rc = check_motion_shape(S, N);
-    if (rc || (rc = check_motion(OFLK_MOTION_AFFINE, hypotheses, 1.0f))) return rc;
-    *bytes = motion_ws(nullptr, S, N, hypotheses).bytes;
+    if (rc || (rc = check_ransac(hypotheses, 1.0f))) return rc;
+    *bytes = motion_ws(nullptr, S, N, hypotheses, motion_coeffs(model)).bytes;
     return OFLK_OK;
 }
 
-OFLK_API int oflk_estimate_motion(const float *d_src, const float *d_dst, const unsigned char *d_valid, int S, int N, int step0,
-                                  int model, int hypotheses, float threshold, unsigned seed, void *d_workspace,
-                                  size_t workspace_bytes, float *d_model, unsigned char *d_inlier, int *d_counts, void *stream)
+// the device forms behind their shape and parameter checks: `in` holds S steps of N
+int fit_device(const MotionIn &in, const char *alignment, int S, int N, int index0, int model, int hypotheses, float threshold,
+               unsigned seed, void *d_workspace, size_t workspace_bytes, float *d_model, unsigned char *d_inlier, int *d_counts,
+               void *stream)
 {
-    int rc = check_motion_shape(S, N);
-    if (rc || (rc = check_motion(model, hypotheses, threshold))) return rc;
-    if (!d_src || !d_dst || !d_model || !d_inlier || !d_counts) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
-    if (!aligned(d_src, 8) || !aligned(d_dst, 8)) return fail(OFLK_ERR_INVALID, "d_src and d_dst must be 8-byte aligned");
-    if ((rc = check_motion_workspace(d_workspace, workspace_bytes, S, N, hypotheses))) return rc;
-    return motion_launch({d_src, d_dst, d_valid, nullptr, nullptr}, S, N, (unsigned)step0, model, hypotheses, threshold, seed,
-                         motion_ws(d_workspace, S, N, hypotheses), d_model, d_inlier, d_counts, (hipStream_t)stream);
+    if (!in.src || !in.dst || !d_model || !d_inlier || !d_counts) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
+    if (!aligned(in.src, 8) || !aligned(in.dst, 8)) return fail(OFLK_ERR_INVALID, "%s must be 8-byte aligned", alignment);
+    if (int rc = check_motion_workspace(d_workspace, workspace_bytes, S, N, hypotheses, model)) return rc;
+    return motion_launch(in, S, N, (unsigned)index0, model, hypotheses, threshold, seed,
+                         motion_ws(d_workspace, S, N, hypotheses, motion_coeffs(model)), d_model, d_inlier, d_counts,
+                         (hipStream_t)stream);
 }
 
-OFLK_API int oflk_tracks_motion(const float *d_tracks, const unsigned char *d_visible, const unsigned char *d_born, int T, int K,
-                                int t0, int model, int hypotheses, float threshold, unsigned seed, void *d_workspace,
-                                size_t workspace_bytes, float *d_model, unsigned char *d_inlier, int *d_counts, void *stream)
+int estimate_device(FitKind fit, const float *d_src, const float *d_dst, const unsigned char *d_valid, int S, int N, int step0,
+                    int hypotheses, float threshold, unsigned seed, void *d_workspace, size_t workspace_bytes, float *d_model,
+                    unsigned char *d_inlier, int *d_counts, void *stream)
+{
+    int rc = check_motion_shape(S, N);
+    if (rc || (rc = fit.check(hypotheses, threshold))) return rc;
+    return fit_device({d_src, d_dst, d_valid, nullptr, nullptr}, "d_src and d_dst", S, N, step0, fit.code(), hypotheses, threshold, seed,
+                      d_workspace, workspace_bytes, d_model, d_inlier, d_counts, stream);
+}
+
+int tracks_device(FitKind fit, const float *d_tracks, const unsigned char *d_visible, const unsigned char *d_born, int T, int K, int t0,
+                  int hypotheses, float threshold, unsigned seed, void *d_workspace, size_t workspace_bytes, float *d_model,
+                  unsigned char *d_inlier, int *d_counts, void *stream)
 {
     if (T < 2) return fail(OFLK_ERR_INVALID, "T must be >= 2 (got %d)", T);
     int rc = check_motion_shape(T - 1, K);
-    if (rc || (rc = check_motion(model, hypotheses, threshold))) return rc;
-    if (!d_tracks || !d_visible || !d_model || !d_inlier || !d_counts) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
-    if (!aligned(d_tracks, 8)) return fail(OFLK_ERR_INVALID, "d_tracks must be 8-byte aligned");
-    if ((rc = check_motion_workspace(d_workspace, workspace_bytes, T - 1, K, hypotheses))) return rc;
-    // row t+1 of a [T][K] array is row t of the array that begins K elements later: one stride for every input
-    const MotionIn in{d_tracks, d_tracks + 2 * (size_t)K, d_visible, d_visible + (size_t)K, d_born ? d_born + (size_t)K : nullptr};
-    return motion_launch(in, T - 1, K, (unsigned)t0, model, hypotheses, threshold, seed, motion_ws(d_workspace, T - 1, K, hypotheses),
-                         d_model, d_inlier, d_counts, (hipStream_t)stream);
+    if (rc || (rc = fit.check(hypotheses, threshold))) return rc;
+    if (!d_tracks || !d_visible) return fail(OFLK_ERR_INVALID, "NULL input or output argument");   // ahead of the row cut
+    return fit_device(motion_rows(d_tracks, d_visible, d_born, K), "d_tracks", T - 1, K, t0, fit.code(), hypotheses, threshold, seed,
+                      d_workspace, workspace_bytes, d_model, d_inlier, d_counts, stream);
 }
 
-namespace {
-// the host form of both fits: model < 0 is the homography fit, nine coefficients per model
-int estimate_host(const float *src, const float *dst, const unsigned char *valid, int S, int N, int step0, int model, int hypotheses,
+int estimate_host(FitKind fit, const float *src, const float *dst, const unsigned char *valid, int S, int N, int step0, int hypotheses,
                   float threshold, unsigned seed, float *model_out, unsigned char *inlier, int *counts)
 {
-    const bool homography = model < 0;
-    const size_t nc = homography ? 9 : 6;
-    int rc;
+    int rc = check_motion_shape(S, N);
+    if (rc || (rc = fit.check(hypotheses, threshold))) return rc;
+    const int model = fit.code();
+    const size_t nc = (size_t)motion_coeffs(model);
     if (!src || !dst || !model_out || !inlier || !counts) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
     HostCall call;
     if ((rc = call.begin())) return rc;
@@ -3730,11 +3734,8 @@ int estimate_host(const float *src, const float *dst, const unsigned char *valid
         (rc = call.alloc(&d_ws, motion_ws(nullptr, S, N, hypotheses, (int)nc).bytes)) || (rc = call.alloc(&d_model, nc * (size_t)S)) ||
         (rc = call.alloc(&d_inl, n)) || (rc = call.alloc(&d_cnt, 3 * (size_t)S)))
         return rc;
-    const MotionIn in{d_src, d_dst, d_valid, nullptr, nullptr};
-    const MotionWs ws = motion_ws(d_ws, S, N, hypotheses, (int)nc);
-    if ((rc = homography ? homography_launch(in, S, N, (unsigned)step0, hypotheses, threshold, seed, ws, d_model, d_inl, d_cnt, nullptr)
-                         : motion_launch(in, S, N, (unsigned)step0, model, hypotheses, threshold, seed, ws, d_model, d_inl, d_cnt,
-                                         nullptr)))
+    if ((rc = motion_launch({d_src, d_dst, d_valid, nullptr, nullptr}, S, N, (unsigned)step0, model, hypotheses, threshold, seed,
+                            motion_ws(d_ws, S, N, hypotheses, (int)nc), d_model, d_inl, d_cnt, nullptr)))
         return rc;
     if ((rc = call.to_host(model_out, d_model, nc * (size_t)S)) || (rc = call.to_host(inlier, d_inl, n)) ||
         (rc = call.to_host(counts, d_cnt, 3 * (size_t)S)))
@@ -3743,61 +3744,61 @@ int estimate_host(const float *src, const float *dst, const unsigned char *valid
 }
 }  // namespace
 
+OFLK_API int oflk_motion_workspace(int S, int N, int hypotheses, size_t *bytes)
+{
+    return fit_workspace(kMotionAffine, S, N, hypotheses, bytes);
+}
+
+OFLK_API int oflk_estimate_motion(const float *d_src, const float *d_dst, const unsigned char *d_valid, int S, int N, int step0,
+                                  int model, int hypotheses, float threshold, unsigned seed, void *d_workspace,
+                                  size_t workspace_bytes, float *d_model, unsigned char *d_inlier, int *d_counts, void *stream)
+{
+    return estimate_device({false, model}, d_src, d_dst, d_valid, S, N, step0, hypotheses, threshold, seed, d_workspace, workspace_bytes,
+                           d_model, d_inlier, d_counts, stream);
+}
+
+OFLK_API int oflk_tracks_motion(const float *d_tracks, const unsigned char *d_visible, const unsigned char *d_born, int T, int K,
+                                int t0, int model, int hypotheses, float threshold, unsigned seed, void *d_workspace,
+                                size_t workspace_bytes, float *d_model, unsigned char *d_inlier, int *d_counts, void *stream)
+{
+    return tracks_device({false, model}, d_tracks, d_visible, d_born, T, K, t0, hypotheses, threshold, seed, d_workspace,
+                         workspace_bytes, d_model, d_inlier, d_counts, stream);
+}
+
 OFLK_API int oflk_estimate_motion_host(const float *src, const float *dst, const unsigned char *valid, int S, int N, int step0,
                                        int model, int hypotheses, float threshold, unsigned seed, float *model_out,
                                        unsigned char *inlier, int *counts)
 {
-    int rc = check_motion_shape(S, N);
-    if (rc || (rc = check_motion(model, hypotheses, threshold))) return rc;
-    return estimate_host(src, dst, valid, S, N, step0, model, hypotheses, threshold, seed, model_out, inlier, counts);
+    return estimate_host({false, model}, src, dst, valid, S, N, step0, hypotheses, threshold, seed, model_out, inlier, counts);
 }
 
-// ---- the homography fit: the same three forms with nine coefficients per model (oflk_homography.hpp) ----
+// ---- the homography fit: the same four forms with the internal model code ----
 OFLK_API int oflk_homography_workspace(int S, int N, int hypotheses, size_t *bytes)
 {
-    if (!bytes) return fail(OFLK_ERR_INVALID, "NULL bytes");
-    int rc = check_motion_shape(S, N);
-    if (rc || (rc = check_ransac(hypotheses, 1.0f))) return rc;
-    *bytes = motion_ws(nullptr, S, N, hypotheses, 9).bytes;
-    return OFLK_OK;
+    return fit_workspace(kMotionHomography, S, N, hypotheses, bytes);
 }
 
 OFLK_API int oflk_estimate_homography(const float *d_src, const float *d_dst, const unsigned char *d_valid, int S, int N, int step0,
                                       int hypotheses, float threshold, unsigned seed, void *d_workspace, size_t workspace_bytes,
                                       float *d_model, unsigned char *d_inlier, int *d_counts, void *stream)
 {
-    int rc = check_motion_shape(S, N);
-    if (rc || (rc = check_ransac(hypotheses, threshold))) return rc;
-    if (!d_src || !d_dst || !d_model || !d_inlier || !d_counts) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
-    if (!aligned(d_src, 8) || !aligned(d_dst, 8)) return fail(OFLK_ERR_INVALID, "d_src and d_dst must be 8-byte aligned");
-    if ((rc = check_motion_workspace(d_workspace, workspace_bytes, S, N, hypotheses, 9))) return rc;
-    return homography_launch({d_src, d_dst, d_valid, nullptr, nullptr}, S, N, (unsigned)step0, hypotheses, threshold, seed,
-                             motion_ws(d_workspace, S, N, hypotheses, 9), d_model, d_inlier, d_counts, (hipStream_t)stream);
+    return estimate_device(kHomographyFit, d_src, d_dst, d_valid, S, N, step0, hypotheses, threshold, seed, d_workspace,
+                           workspace_bytes, d_model, d_inlier, d_counts, stream);
 }
 
 OFLK_API int oflk_tracks_homography(const float *d_tracks, const unsigned char *d_visible, const unsigned char *d_born, int T, int K,
                                     int t0, int hypotheses, float threshold, unsigned seed, void *d_workspace,
                                     size_t workspace_bytes, float *d_model, unsigned char *d_inlier, int *d_counts, void *stream)
 {
-    if (T < 2) return fail(OFLK_ERR_INVALID, "T must be >= 2 (got %d)", T);
-    int rc = check_motion_shape(T - 1, K);
-    if (rc || (rc = check_ransac(hypotheses, threshold))) return rc;
-    if (!d_tracks || !d_visible || !d_model || !d_inlier || !d_counts) return fail(OFLK_ERR_INVALID, "NULL input or output argument");
-    if (!aligned(d_tracks, 8)) return fail(OFLK_ERR_INVALID, "d_tracks must be 8-byte aligned");
-    if ((rc = check_motion_workspace(d_workspace, workspace_bytes, T - 1, K, hypotheses, 9))) return rc;
-    // the rows as oflk_tracks_motion cuts them
-    const MotionIn in{d_tracks, d_tracks + 2 * (size_t)K, d_visible, d_visible + (size_t)K, d_born ? d_born + (size_t)K : nullptr};
-    return homography_launch(in, T - 1, K, (unsigned)t0, hypotheses, threshold, seed, motion_ws(d_workspace, T - 1, K, hypotheses, 9),
-                             d_model, d_inlier, d_counts, (hipStream_t)stream);
+    return tracks_device(kHomographyFit, d_tracks, d_visible, d_born, T, K, t0, hypotheses, threshold, seed, d_workspace,
+                         workspace_bytes, d_model, d_inlier, d_counts, stream);
 }
 
 OFLK_API int oflk_estimate_homography_host(const float *src, const float *dst, const unsigned char *valid, int S, int N, int step0,
                                            int hypotheses, float threshold, unsigned seed, float *model_out, unsigned char *inlier,
                                            int *counts)
 {
-    int rc = check_motion_shape(S, N);
-    if (rc || (rc = check_ransac(hypotheses, threshold))) return rc;
-    return estimate_host(src, dst, valid, S, N, step0, -1, hypotheses, threshold, seed, model_out, inlier, counts);
+    return estimate_host(kHomographyFit, src, dst, valid, S, N, step0, hypotheses, threshold, seed, model_out, inlier, counts);
 }
 
 // =============================================================================
@@ -3961,6 +3962,51 @@ int check_stabilize_config(int H, int W, int levels, int window_size, int iters,
     return OFLK_OK;
 }
 
+// What the sequence stabilisers and the mosaics do up to and including the fit's launch, on checked grey frames: pass 1 is
+// the replenish call itself (its chunk loop; only rows come down, into the host arrays here, which live as long as the
+// caller keeps this); then `call` begins, the rows go up again and the fit of the internal `model` code runs over the T-1
+// steps on the null stream.  Nothing is synchronised.
+struct SequenceFit {
+    std::vector<float> tracks;
+    std::vector<unsigned char> visible, born;
+    std::vector<int> detected;
+    float *d_model = nullptr;   // [T-1][motion_coeffs(model)]
+    int *d_counts = nullptr;    // [T-1][3]
+
+    int run(HostCall &call, const Seq &seq, float alpha, float beta, float max_residual, float q, float md, int K, int detect_every,
+            int model, int hypotheses, float threshold, unsigned seed)
+    {
+        int rc;
+        const int T = seq.T;
+        const size_t row = (size_t)K, nT = (size_t)T, S = nT - 1;
+        try {
+            tracks.resize(nT * 2 * row);
+            visible.resize(nT * row);
+            born.resize(nT * row);
+            detected.resize(nT);
+        } catch (const std::exception &) {
+            return fail(OFLK_ERR_NOMEM, "no host memory for the rows of %d frames of %d slots", T, K);
+        }
+        if ((rc = run_sequence_tracks(seq, SparseTracks{{alpha, beta, max_residual}},
+                                      Replenished{{q, md, K, detect_every}, born.data(), detected.data(), nullptr}, K, tracks.data(),
+                                      visible.data())))
+            return rc;
+        if ((rc = call.begin())) return rc;
+        float *d_tr;
+        unsigned char *d_vis, *d_born, *d_inl;
+        char *d_ws;
+        const int nc = motion_coeffs(model);
+        if ((rc = call.upload(&d_tr, (const float *)tracks.data(), nT * 2 * row)) ||
+            (rc = call.upload(&d_vis, (const unsigned char *)visible.data(), nT * row)) ||
+            (rc = call.upload(&d_born, (const unsigned char *)born.data(), nT * row)) ||
+            (rc = call.alloc(&d_ws, motion_ws(nullptr, T - 1, K, hypotheses, nc).bytes)) || (rc = call.alloc(&d_model, (size_t)nc * S)) ||
+            (rc = call.alloc(&d_inl, S * row)) || (rc = call.alloc(&d_counts, 3 * S)))
+            return rc;
+        return motion_launch(motion_rows(d_tr, d_vis, d_born, K), T - 1, K, 0u, model, hypotheses, threshold, seed,
+                             motion_ws(d_ws, T - 1, K, hypotheses, nc), d_model, d_inl, d_counts, nullptr);
+    }
+};
+
 // Pass 1 and the trajectory of a sequence call on the checked grey frames: begins `call`, leaves the maps of all T frames in
 // its *d_map_out [T][6] and sends the four small outputs on their way (the caller's last chunk synchronises)
 int stabilize_maps(HostCall &call, const void *frames, bool u8, int T, int H, int W, int levels, int window_size, int iters,
@@ -3969,39 +4015,16 @@ int stabilize_maps(HostCall &call, const void *frames, bool u8, int T, int H, in
                    int *counts_out, unsigned char *held, double **d_map_out)
 {
     int rc;
-    const size_t row = (size_t)K, nT = (size_t)T, S = nT - 1;
-    std::vector<float> tracks;
-    std::vector<unsigned char> visible, born;
-    std::vector<int> detected;
-    try {
-        tracks.resize(nT * 2 * row);
-        visible.resize(nT * row);
-        born.resize(nT * row);
-        detected.resize(nT);
-    } catch (const std::exception &) {
-        return fail(OFLK_ERR_NOMEM, "no host memory for the rows of %d frames of %d slots", T, K);
-    }
-    if ((rc = run_sequence_tracks(Seq{frames, u8, T, H, W, levels, window_size, iters},
-                                  SparseTracks{{alpha, beta, max_residual}},
-                                  Replenished{{q, md, K, detect_every}, born.data(), detected.data(), nullptr}, K, tracks.data(),
-                                  visible.data())))
+    const size_t nT = (size_t)T, S = nT - 1;
+    SequenceFit fit;
+    if ((rc = fit.run(call, Seq{frames, u8, T, H, W, levels, window_size, iters}, alpha, beta, max_residual, q, md, K, detect_every,
+                      model, hypotheses, threshold, seed)))
         return rc;
-    if ((rc = call.begin())) return rc;
-    float *d_tr, *d_model, *d_corr;
-    unsigned char *d_vis, *d_born, *d_inl, *d_held;
-    char *d_ws;
-    int *d_cnt;
+    float *const d_model = fit.d_model, *d_corr;
+    int *const d_cnt = fit.d_counts;
+    unsigned char *d_held;
     double *d_map;
-    if ((rc = call.upload(&d_tr, (const float *)tracks.data(), nT * 2 * row)) ||
-        (rc = call.upload(&d_vis, (const unsigned char *)visible.data(), nT * row)) ||
-        (rc = call.upload(&d_born, (const unsigned char *)born.data(), nT * row)) ||
-        (rc = call.alloc(&d_ws, motion_ws(nullptr, T - 1, K, hypotheses).bytes)) || (rc = call.alloc(&d_model, 6 * S)) ||
-        (rc = call.alloc(&d_inl, S * row)) || (rc = call.alloc(&d_cnt, 3 * S)) || (rc = call.alloc(&d_corr, 6 * nT)) ||
-        (rc = call.alloc(&d_map, 6 * nT)) || (rc = call.alloc(&d_held, S)))
-        return rc;
-    const MotionIn in{d_tr, d_tr + 2 * row, d_vis, d_vis + row, d_born + row};
-    if ((rc = motion_launch(in, T - 1, K, 0u, model, hypotheses, threshold, seed, motion_ws(d_ws, T - 1, K, hypotheses), d_model,
-                            d_inl, d_cnt, nullptr)) ||
+    if ((rc = call.alloc(&d_corr, 6 * nT)) || (rc = call.alloc(&d_map, 6 * nT)) || (rc = call.alloc(&d_held, S)) ||
         (rc = trajectory_launch(d_model, d_cnt, T, weights, radius, d_corr, d_map, d_held, nullptr)))
         return rc;
     if ((correction && (rc = call.to_host(correction, d_corr, 6 * nT))) || (model_out && (rc = call.to_host(model_out, d_model, 6 * S))) ||
@@ -4595,44 +4618,26 @@ int mosaic_sequence(const PIX *frames, int T, int H, int W, int levels, int wind
     if ((rc = check_select(q, md, K)) || (rc = check_sparse_test(alpha, beta, max_residual)) ||
         (rc = check_sparse_config(H, W, levels, window_size, iters)) || (rc = check_motion_shape(T - 1, K)))
         return rc;
-    const size_t row = (size_t)K, nT = (size_t)T, S = nT - 1;
-    std::vector<float> tracks;
-    std::vector<unsigned char> visible, born, h_dropped;
-    std::vector<int> detected;
+    const size_t nT = (size_t)T, S = nT - 1;
+    std::vector<unsigned char> h_dropped;
     std::vector<double> h_box;
     try {
-        tracks.resize(nT * 2 * row);
-        visible.resize(nT * row);
-        born.resize(nT * row);
-        detected.resize(nT);
         h_box.resize(4 * nT);
         h_dropped.resize(nT);
     } catch (const std::exception &) {
         return fail(OFLK_ERR_NOMEM, "no host memory for the rows of %d frames of %d slots", T, K);
     }
-    if ((rc = run_sequence_tracks(Seq{frames, sizeof(PIX) == 1, T, H, W, levels, window_size, iters},
-                                  SparseTracks{{alpha, beta, max_residual}},
-                                  Replenished{{q, md, K, detect_every}, born.data(), detected.data(), nullptr}, K, tracks.data(),
-                                  visible.data())))
-        return rc;
+    SequenceFit fit;   // before `call`: the host rows outlive the device buffers
     HostCall call;
-    if ((rc = call.begin())) return rc;
-    float *d_tr, *d_model;
-    unsigned char *d_vis, *d_born, *d_inl, *d_held, *d_drop;
-    char *d_ws;
-    int *d_cnt;
-    double *d_from, *d_to, *d_box;
-    if ((rc = call.upload(&d_tr, (const float *)tracks.data(), nT * 2 * row)) ||
-        (rc = call.upload(&d_vis, (const unsigned char *)visible.data(), nT * row)) ||
-        (rc = call.upload(&d_born, (const unsigned char *)born.data(), nT * row)) ||
-        (rc = call.alloc(&d_ws, motion_ws(nullptr, T - 1, K, hypotheses, 9).bytes)) || (rc = call.alloc(&d_model, 9 * S)) ||
-        (rc = call.alloc(&d_inl, S * row)) || (rc = call.alloc(&d_cnt, 3 * S)) || (rc = call.alloc(&d_from, 9 * nT)) ||
-        (rc = call.alloc(&d_to, 9 * nT)) || (rc = call.alloc(&d_box, 4 * nT)) || (rc = call.alloc(&d_held, S)) ||
-        (rc = call.alloc(&d_drop, nT)))
+    if ((rc = fit.run(call, Seq{frames, sizeof(PIX) == 1, T, H, W, levels, window_size, iters}, alpha, beta, max_residual, q, md, K,
+                      detect_every, kMotionHomography, hypotheses, threshold, seed)))
         return rc;
-    const MotionIn in{d_tr, d_tr + 2 * row, d_vis, d_vis + row, d_born + row};
-    if ((rc = homography_launch(in, T - 1, K, 0u, hypotheses, threshold, seed, motion_ws(d_ws, T - 1, K, hypotheses, 9), d_model, d_inl,
-                                d_cnt, nullptr)) ||
+    float *const d_model = fit.d_model;
+    int *const d_cnt = fit.d_counts;
+    unsigned char *d_held, *d_drop;
+    double *d_from, *d_to, *d_box;
+    if ((rc = call.alloc(&d_from, 9 * nT)) || (rc = call.alloc(&d_to, 9 * nT)) || (rc = call.alloc(&d_box, 4 * nT)) ||
+        (rc = call.alloc(&d_held, S)) || (rc = call.alloc(&d_drop, nT)) ||
         (rc = mosaic_chain_launch(d_model, d_cnt, T, anchor, H, W, extent, d_from, d_to, d_box, d_held, d_drop, nullptr)))
         return rc;
     if ((rc = call.to_host(h_box.data(), d_box, 4 * nT)) || (rc = call.to_host(h_dropped.data(), d_drop, nT)) ||

@@ -34,7 +34,7 @@
 //                          change the sum's order; the sampling and the sd row are computed twice.  No LDS, no barrier, no
 //                          scratch: each wave's lane 0 writes its own sums
 //   k_align_update<NP, PHOTO, ROBUST>  one block of 64 per step: lane k adds sums k, k + 64 of the tiles in raster order;
-//                          then every lane runs the step's serial part in registers (the refusals, k_homog_refit's
+//                          then every lane runs the step's serial part in registers (the refusals, the homography refit's
 //                          elimination on NQ rows, the update's conjugation, the adjugate, the product, the corner test, the
 //                          g, b update, the level's conjugations) and lane 0 writes the state.  mode 0 records the first
 //                          full-resolution residual, mode 2 the last one and writes the outputs; both read the sums of the
@@ -84,9 +84,9 @@ __device__ __forceinline__ void align_from_level(double (&m)[9], double sx, doub
     m[6] = m[6] * sx;        m[7] = m[7] * sy;
 }
 
-// Gaussian elimination without pivoting on the N x (N + 1) array [G | b], then the back substitution into h: k_homog_refit's
-// procedure (tests/homography_model.py, solve8) on N rows, fully unrolled so that no indexed array is left.  A function of its
-// own: sharing one with k_homog_refit changed that kernel's register allocation.  false: a pivot is zero or not finite
+// Gaussian elimination without pivoting on the N x (N + 1) array [G | b], then the back substitution into h: the procedure of
+// the homography's branch of k_motion_refit (tests/homography_model.py, solve8) on N rows, fully unrolled so that no indexed array is left.  A function of its
+// own: sharing one with that kernel changed its register allocation.  false: a pivot is zero or not finite
 template <int N>
 __device__ __forceinline__ bool align_eliminate(double (&G)[N][N + 1], double (&h)[N])
 {

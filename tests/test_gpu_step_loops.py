@@ -3,8 +3,8 @@ python -m pytest tests/test_gpu_step_loops.py -m gpu -q).
 
 Every batched kernel puts its steps on a grid axis of at most 65 535 blocks and reaches later steps by
 `for (s = blockIdx; s < S; s += gridDim)`.  The batches here have S = 65 549 steps of seven kinds (tests/step_loop_scenes.py,
-whose promises tests/test_step_loops_cpu.py asserts), so that 14 blocks of k_motion_compact, k_motion_score, k_motion_refit,
-k_homog_score, k_homog_refit, k_align_reduce, k_align_update and the photometric pair take their loop a second time, from every
+whose promises tests/test_step_loops_cpu.py asserts), so that 14 blocks of k_motion_compact, k_motion_score, k_motion_refit
+(the six-coefficient models' and the homography's), k_align_reduce, k_align_update and the photometric pair take their loop a second time, from every
 kind of step into the next one.  The pair form with two levels also hands 2 S = 131 098 images, the sequence form S + 1 =
 65 550, to the pyramid launch's grid.z.  Everything is compared byte for byte, a NaN equal to a NaN; no tolerance anywhere.
 """
@@ -96,7 +96,7 @@ def test_the_motion_fit_past_the_grid_limit(family):
 
 
 def test_the_homography_fit_past_the_grid_limit():
-    """k_motion_compact, k_homog_score and k_homog_refit, as above"""
+    """k_motion_compact and the homography's k_motion_score and k_motion_refit, as above"""
     assert HM.SAMPLE == SC.sample_size(SC.HOMOGRAPHY)
     _fit_past_the_grid_limit(SC.HOMOGRAPHY, "homography")
 

@@ -2,7 +2,8 @@
 """Device time of the global motion fit (development tool, not part of the bench contract).
 
 Leg 1, the fit alone: one step of K correspondences on the device (a planted similarity, 30 % outliers, every slot valid),
-K in (1 000, 10 000), Hn in (64, 256, 1 024), each model family.  Events around `--reps` back-to-back calls of
+K in (1 000, 10 000), Hn in (64, 256, 1 024), each of the kernel family's four models (the homography through
+oflk_homography_workspace and oflk_estimate_homography, nine floats per model).  Events around `--reps` back-to-back calls of
 oflk_estimate_motion give the time per step; one JSON line per (K, Hn, family) with the median over `--steps` such batches.
 The split into the three launches comes from a separate run under `rocprofv3 --kernel-trace --stats`.
 
@@ -22,7 +23,7 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT / "optical-flow-fpga_amd" / "python"))
 sys.path.insert(0, str(ROOT / "tests"))
 
-FAMILIES = ["translation", "similarity", "affine"]
+FAMILIES = ["translation", "similarity", "affine", "homography"]   # index = the kernels' model code
 
 
 def fit_leg(args):
@@ -37,16 +38,21 @@ def fit_leg(args):
     for K in args.budgets:
         src, dst, planted = MM.planted_scene(K, 0.3, 1)
         t_src, t_dst = torch.from_numpy(src).to(d), torch.from_numpy(dst).to(d)
-        out = torch.empty(6, device=d)
+        out = torch.empty(9, device=d)
         inl = torch.empty(K, dtype=torch.uint8, device=d)
         cnt = torch.empty(3, dtype=torch.int32, device=d)
         for hyps in args.hypotheses:
-            nb = _oflk.motion_workspace(1, K, hyps)
-            ws = torch.empty(nb, dtype=torch.uint8, device=d)
             for code, family in enumerate(FAMILIES):
+                nb = (_oflk.homography_workspace if family == "homography" else _oflk.motion_workspace)(1, K, hyps)
+                ws = torch.empty(nb, dtype=torch.uint8, device=d)
+
                 def call():
-                    _oflk.estimate_motion(t_src.data_ptr(), t_dst.data_ptr(), 0, 1, K, ws.data_ptr(), nb, out.data_ptr(),
-                                          inl.data_ptr(), cnt.data_ptr(), code, hyps, 1.0, 0, 0, st)
+                    if family == "homography":
+                        _oflk.estimate_homography(t_src.data_ptr(), t_dst.data_ptr(), 0, 1, K, ws.data_ptr(), nb, out.data_ptr(),
+                                                  inl.data_ptr(), cnt.data_ptr(), hyps, 1.0, 0, 0, st)
+                    else:
+                        _oflk.estimate_motion(t_src.data_ptr(), t_dst.data_ptr(), 0, 1, K, ws.data_ptr(), nb, out.data_ptr(),
+                                              inl.data_ptr(), cnt.data_ptr(), code, hyps, 1.0, 0, 0, st)
 
                 call()
                 torch.cuda.synchronize()

@@ -739,6 +739,38 @@ int launch_pyr_down(oflk_plan *plan, const GaussW &gauss, hipStream_t s, const f
     return OFLK_OK;
 }
 
+// the first step of a pyramid, from the finest down, that the fused kernel cannot take (its coarser level); -1: none
+int pyr_first_unfused(const int *dims, int levels, const GaussW &gauss)
+{
+    for (int l = levels - 2; l >= 0; l--)
+        if (!pyr_fused_fits(dims[2 * (l + 1)], dims[2 * (l + 1) + 1], dims[2 * l], dims[2 * l + 1], gauss)) return l;
+    return -1;
+}
+
+// the refusal of a caller that has no temporaries for the unfused chain
+int pyr_chain_fits(const int *dims, int levels, const GaussW &gauss)
+{
+    const int l = pyr_first_unfused(dims, levels, gauss), *fine = dims + 2 * (levels - 1);
+    return l < 0 ? OFLK_OK : fail(OFLK_ERR_UNSUPPORTED, "pyramid level %d of %dx%d does not fit the fused pyramid kernel", l, fine[1], fine[0]);
+}
+
+// The level walk of one set of n images: from `fine` (level levels-1) into image img0 onward of out[levels-2] .. out[0]; `first`
+// rides on the first launch.  plan, tmpA, tmpB: a plan's (Prof timing, arithmetic, the unfused chain), or NULL behind pyr_chain_fits
+int pyr_chain(oflk_plan *plan, const GaussW &gauss, hipStream_t s, const float *fine, float *const *out, size_t img0, float *tmpA,
+              float *tmpB, int n, const int *dims, int levels, const PyrExtra &first)
+{
+    const float *in = fine;
+    for (int l = levels - 2; l >= 0; l--) {
+        const int ho = dims[2 * l], wo = dims[2 * l + 1];
+        float *const o = out[l] + img0 * (size_t)ho * (size_t)wo;
+        if (int rc = launch_pyr_down(plan, gauss, s, in, o, tmpA, tmpB, n, dims[2 * (l + 1)], dims[2 * (l + 1) + 1], ho, wo,
+                                     l == levels - 2 ? &first : nullptr))
+            return rc;
+        in = o;
+    }
+    return OFLK_OK;
+}
+
 template <typename T>
 int dmalloc(T **p, size_t n, size_t *total)
 {
@@ -1078,21 +1110,9 @@ int stage_u8(oflk_plan *p, hipStream_t s, const void *d_prev_in, const void *d_c
 // first launch: the call's clear, and whether the frames are uint8.
 int build_pyramids(oflk_plan *p, hipStream_t s, const float *d_prev, const float *d_curr, bool seq, PyrExtra first)
 {
-    const int B = p->B, L = p->L, nimg = seq ? B + 1 : 2 * B;
-    for (int l = L - 2; l >= 0; l--) {
-        int h = p->dims[2 * (l + 1)], w = p->dims[2 * (l + 1) + 1];
-        int ho = p->dims[2 * l], wo = p->dims[2 * l + 1];
-        int rc;
-        if (l == L - 2) {
-            first.in2 = seq ? nullptr : d_curr;
-            first.nsplit = seq ? 0 : B;
-            rc = launch_pyr_down(p, p->gauss, s, d_prev, p->pyr[l], p->tmpA, p->tmpB, nimg, h, w, ho, wo, &first);
-        } else {
-            rc = launch_pyr_down(p, p->gauss, s, p->pyr[l + 1], p->pyr[l], p->tmpA, p->tmpB, nimg, h, w, ho, wo);
-        }
-        if (rc) return rc;
-    }
-    return OFLK_OK;
+    first.in2 = seq ? nullptr : d_curr;
+    first.nsplit = seq ? 0 : p->B;
+    return pyr_chain(p, p->gauss, s, d_prev, p->pyr, 0, p->tmpA, p->tmpB, seq ? p->B + 1 : 2 * p->B, p->dims, p->L, first);
 }
 
 int plan_pyramidal(oflk_plan *p, const void *d_prev_in, const void *d_curr_in, bool u8, float *d_u, float *d_v,
@@ -2370,11 +2390,21 @@ int fb_launch(const float *uf, const float *vf, const float *ub, const float *vb
     return OFLK_OK;
 }
 
+// The settings of the tracking, fit and stabilising calls: one aggregate a group, filled once where an OFLK_API function takes
+// the flat list and passed whole from there on; each has one check (check_sparse_config, check_sparse_test, check_select,
+// check_motion / check_ransac, check_stab_window).  FitConfig::model is OFLK_MOTION_*, or an internal code where the caller says so
+struct PyrWindow { int levels, window_size, iters; };
+struct TrackTest { float alpha, beta, max_residual; };
+struct Selection { float q, md; int K, every; };
+struct FitConfig { int model, hypotheses; float threshold; unsigned seed; };
+struct TrajWindow { const double *weights; int radius; };               // weights [radius + 1]
+struct KltConfig { PyrWindow pyr; TrackTest test; Selection select; };   // what replenished sparse KLT takes besides its frames
+
 // The frames and the flow configuration of a host sequence call
-struct Seq {
+struct Seq : PyrWindow {
     const void *frames;   // [T][H][W], uint8 or float32
     bool u8;
-    int T, H, W, levels, window_size, iters;
+    int T, H, W;
     size_t frame_bytes() const { return (size_t)H * W * (u8 ? 1 : sizeof(float)); }
 };
 
@@ -2429,7 +2459,7 @@ template <class PIXELS>
 int run_sequence_fb(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
                     float *uf, float *vf, float *ub, float *vb, float *ef, float *eb, unsigned char *qf, unsigned char *qb)
 {
-    const Seq seq{frames, sizeof(PIXELS) == 1, T, H, W, levels, window_size, iters};
+    const Seq seq{{levels, window_size, iters}, frames, sizeof(PIXELS) == 1, T, H, W};
     const bool check = ef || eb || qf || qb;
     int rc = BidirChunk::check(seq);
     if (rc || (check && (rc = check_fb(uf, vf, ub, vb, T - 1, H, W, alpha, beta, ef, eb, qf, qb)))) return rc;
@@ -2529,6 +2559,7 @@ int check_select(float q, float md, int K)
     if (K < 1) return fail(OFLK_ERR_INVALID, "max_corners must be >= 1 (got %d)", K);
     return OFLK_OK;
 }
+int check_select(const Selection &k) { return check_select(k.q, k.md, k.K); }   // `every` is the caller's: >= 1 or >= 0
 
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
@@ -3052,9 +3083,7 @@ struct DetectOnce {
 // The slot side of replenished KLT: the K queries are slots, every one dead at first.  On every `every`-th frame s the
 // detection fills free slots (qt = s, qxy) from the slots' row of s, born with them.  The selection's parameters, its
 // workspace (feat_ws(.., 1, .., K)) and the per-row outputs of a pass of B+1 rows
-struct Slots {
-    float q, md;
-    int K, every;
+struct Slots : Selection {
     void *ws = nullptr;
     unsigned char *born = nullptr;   // [B+1][K]
     int *detected = nullptr;         // [B+1]
@@ -3100,7 +3129,7 @@ struct Replenished : Slots {
     {
         if (!tracks || !visible || !h_born || !h_detected) return fail(OFLK_ERR_INVALID, "NULL output argument");
         if (every < 1) return fail(OFLK_ERR_INVALID, "detect_every must be >= 1 (got %d)", every);
-        const int rc = check_select(q, md, K);
+        const int rc = check_select(*this);
         return rc ? rc : check_corner_window(seq.window_size);
     }
     int detect_every(int) const { return every; }
@@ -3177,7 +3206,7 @@ OFLK_API int oflk_pyramidal_sequence_tracks(const float *frames, int T, int H, i
                                             float alpha, float beta, const int *qt, const float *qxy, int N, float *tracks,
                                             unsigned char *visible)
 {
-    return run_sequence_tracks(Seq{frames, false, T, H, W, levels, window_size, iters}, DenseTracks{alpha, beta},
+    return run_sequence_tracks(Seq{{levels, window_size, iters}, frames, false, T, H, W}, DenseTracks{alpha, beta},
                                GivenQueries{qt, qxy, N}, N, tracks, visible);
 }
 
@@ -3185,7 +3214,7 @@ OFLK_API int oflk_pyramidal_sequence_tracks_u8(const unsigned char *frames, int 
                                                int iters, float alpha, float beta, const int *qt, const float *qxy, int N,
                                                float *tracks, unsigned char *visible)
 {
-    return run_sequence_tracks(Seq{frames, true, T, H, W, levels, window_size, iters}, DenseTracks{alpha, beta},
+    return run_sequence_tracks(Seq{{levels, window_size, iters}, frames, true, T, H, W}, DenseTracks{alpha, beta},
                                GivenQueries{qt, qxy, N}, N, tracks, visible);
 }
 
@@ -3193,7 +3222,7 @@ OFLK_API int oflk_pyramidal_sequence_klt(const float *frames, int T, int H, int 
                                          float alpha, float beta, float quality_level, float min_distance, int max_corners,
                                          int *count, float *xy, float *score, float *tracks, unsigned char *visible)
 {
-    return run_sequence_tracks(Seq{frames, false, T, H, W, levels, window_size, iters}, DenseTracks{alpha, beta},
+    return run_sequence_tracks(Seq{{levels, window_size, iters}, frames, false, T, H, W}, DenseTracks{alpha, beta},
                                DetectOnce{quality_level, min_distance, max_corners, count, xy, score}, max_corners, tracks, visible);
 }
 
@@ -3202,7 +3231,7 @@ OFLK_API int oflk_pyramidal_sequence_klt_u8(const unsigned char *frames, int T, 
                                             int max_corners, int *count, float *xy, float *score, float *tracks,
                                             unsigned char *visible)
 {
-    return run_sequence_tracks(Seq{frames, true, T, H, W, levels, window_size, iters}, DenseTracks{alpha, beta},
+    return run_sequence_tracks(Seq{{levels, window_size, iters}, frames, true, T, H, W}, DenseTracks{alpha, beta},
                                DetectOnce{quality_level, min_distance, max_corners, count, xy, score}, max_corners, tracks, visible);
 }
 
@@ -3211,8 +3240,8 @@ OFLK_API int oflk_pyramidal_sequence_klt_replenish(const float *frames, int T, i
                                                    int max_corners, int detect_every, float *tracks, unsigned char *visible,
                                                    unsigned char *born, int *detected)
 {
-    return run_sequence_tracks(Seq{frames, false, T, H, W, levels, window_size, iters}, DenseTracks{alpha, beta},
-                               Replenished{{quality_level, min_distance, max_corners, detect_every}, born, detected, nullptr},
+    return run_sequence_tracks(Seq{{levels, window_size, iters}, frames, false, T, H, W}, DenseTracks{alpha, beta},
+                               Replenished{{{quality_level, min_distance, max_corners, detect_every}}, born, detected, nullptr},
                                max_corners, tracks, visible);
 }
 
@@ -3221,8 +3250,8 @@ OFLK_API int oflk_pyramidal_sequence_klt_replenish_u8(const unsigned char *frame
                                                       float min_distance, int max_corners, int detect_every, float *tracks,
                                                       unsigned char *visible, unsigned char *born, int *detected)
 {
-    return run_sequence_tracks(Seq{frames, true, T, H, W, levels, window_size, iters}, DenseTracks{alpha, beta},
-                               Replenished{{quality_level, min_distance, max_corners, detect_every}, born, detected, nullptr},
+    return run_sequence_tracks(Seq{{levels, window_size, iters}, frames, true, T, H, W}, DenseTracks{alpha, beta},
+                               Replenished{{{quality_level, min_distance, max_corners, detect_every}}, born, detected, nullptr},
                                max_corners, tracks, visible);
 }
 
@@ -3232,8 +3261,9 @@ OFLK_API int oflk_pyramidal_sequence_klt_replenish_u8(const unsigned char *frame
 namespace {
 // The configuration's refusals, before any device call: levels, iterations (INVALID), the window (odd, 3..11) and the
 // level sizes (every dimension >= 2: a level's linspace geometry divides by size - 1) (UNSUPPORTED)
-int check_sparse_config(int H, int W, int levels, int window_size, int iters)
+int check_sparse_config(int H, int W, const PyrWindow &pw)
 {
+    const int levels = pw.levels, window_size = pw.window_size, iters = pw.iters;
     if (H < 1 || W < 1) return fail(OFLK_ERR_INVALID, "H and W must be >= 1 (got %d x %d)", H, W);
     if (levels < 1 || levels > OFLK_MAX_LEVELS)
         return fail(OFLK_ERR_INVALID, "levels must be in [1,%d] (got %d)", OFLK_MAX_LEVELS, levels);
@@ -3250,12 +3280,14 @@ int check_sparse_config(int H, int W, int levels, int window_size, int iters)
     return OFLK_OK;
 }
 
-int check_sparse_test(float alpha, float beta, float max_residual)
+int check_sparse_test(const TrackTest &t)
 {
-    if (int rc = check_alpha_beta(alpha, beta)) return rc;
-    if (!(max_residual >= 0.0f)) return fail(OFLK_ERR_INVALID, "max_residual must be >= 0 (+inf disables the test)");
+    if (int rc = check_alpha_beta(t.alpha, t.beta)) return rc;
+    if (!(t.max_residual >= 0.0f)) return fail(OFLK_ERR_INVALID, "max_residual must be >= 0 (+inf disables the test)");
     return OFLK_OK;
 }
+
+PyrWindow plan_window(const oflk_plan *p) { return {p->L, p->win, p->K}; }
 
 // a pyramid's L levels as the sparse kernels take them: pointers, sizes and upsample_args' ratios
 void sparse_levels(SparseArgs *a, int L, float *const *pyr, const int *dims)
@@ -3284,10 +3316,7 @@ int sparse_pyramids(oflk_plan *p, const void *d_frames, bool u8, hipStream_t s, 
         d_frames = p->u8_stage[0];
         u8 = false;
     }
-    bool unfused = false;
-    for (int l = p->L - 2; l >= 0; l--)
-        unfused = unfused || !pyr_fused_fits(p->dims[2 * (l + 1)], p->dims[2 * (l + 1) + 1], p->dims[2 * l], p->dims[2 * l + 1], p->gauss);
-    if (unfused && (rc = ensure_tmp(p, (size_t)p->B + 1))) return rc;
+    if (pyr_first_unfused(p->dims, p->L, p->gauss) >= 0 && (rc = ensure_tmp(p, (size_t)p->B + 1))) return rc;
     PyrExtra first;
     first.u8 = u8;
     const int arith = p->arith;
@@ -3321,26 +3350,25 @@ int sparse_launch(const oflk_plan *p, const SparseArgs &a, bool u8, hipStream_t 
     return OFLK_OK;
 }
 
-int plan_sparse_tracks(oflk_plan *p, const void *d_frames, bool u8, float alpha, float beta, float max_residual, int t0,
-                       const int *d_qt, const float *d_qxy, int N, float *d_tracks, unsigned char *d_visible, hipStream_t s)
+int plan_sparse_tracks(oflk_plan *p, const void *d_frames, bool u8, const TrackTest &test, int t0, const int *d_qt,
+                       const float *d_qxy, int N, float *d_tracks, unsigned char *d_visible, hipStream_t s)
 {
     if (!p || !d_frames) return fail(OFLK_ERR_INVALID, "NULL argument");
     int rc = check_queries(nullptr, p->B + 1, d_qxy, N, d_tracks, d_visible);
-    if (rc || (rc = check_sparse_test(alpha, beta, max_residual)) || (rc = check_sparse_config(p->H, p->W, p->L, p->win, p->K)))
-        return rc;
+    if (rc || (rc = check_sparse_test(test)) || (rc = check_sparse_config(p->H, p->W, plan_window(p)))) return rc;
     if (t0 < 0) return fail(OFLK_ERR_INVALID, "t0 must be >= 0 (got %d)", t0);
     SparseArgs a;
     if ((rc = sparse_pyramids(p, d_frames, u8, s, &a)) < 0) return rc;
     a.qt = d_qt; a.qxy = d_qxy; a.tracks = d_tracks; a.visible = d_visible;
     a.N = N; a.t0 = t0;
-    a.alpha = alpha; a.beta = beta; a.max_residual = max_residual;
+    a.alpha = test.alpha; a.beta = test.beta; a.max_residual = test.max_residual;
     return sparse_launch<true>(p, a, rc > 0, s);
 }
 
 // A sparse pass on a plan, one chain of launches on stream s with nothing synchronized: the plan's B+1 pyramids once
 // (begin), then one track launch per segment (step).  The host driver's sparse engine and oflk_plan_sparse_klt_replenish.
 struct SparsePass {
-    float alpha, beta, max_residual;
+    TrackTest test;
     oflk_plan *p = nullptr;
     hipStream_t s = nullptr;
     SparseArgs base{};      // the whole pass's
@@ -3364,7 +3392,7 @@ struct SparsePass {
         for (int l = 0; l < p->L - 1; l++) a.pyr[l] = base.pyr[l] + (size_t)r * p->dims[2 * l] * (size_t)p->dims[2 * l + 1];
         a.B = e - s0; a.N = N; a.t0 = s0;
         a.qt = R.qt; a.qxy = R.qxy; a.tracks = R.tr + (size_t)r * 2 * row; a.visible = R.vis + (size_t)r * row;
-        a.alpha = alpha; a.beta = beta; a.max_residual = max_residual;
+        a.alpha = test.alpha; a.beta = test.beta; a.max_residual = test.max_residual;
         return sparse_launch<true>(p, a, fine_u8, s, R.res ? R.res + (size_t)r * row : nullptr);
     }
 };
@@ -3377,7 +3405,7 @@ int sparse_lk_host(const PIXELS *prev, const PIXELS *curr, int H, int W, int lev
     if (rc) return rc;
     if (!pts || !next_pts || !status || !residual) return fail(OFLK_ERR_INVALID, "NULL point or output argument");
     if (N < 1) return fail(OFLK_ERR_INVALID, "N must be >= 1 (got %d)", N);
-    if ((rc = check_sparse_config(H, W, levels, window_size, iters))) return rc;
+    if ((rc = check_sparse_config(H, W, {levels, window_size, iters}))) return rc;
     HostCall call;
     if ((rc = call.begin())) return rc;
     const size_t plane = (size_t)H * W, row = (size_t)N;
@@ -3420,8 +3448,8 @@ struct SparseTracks {
     int check(const Seq &seq) const
     {
         int rc = check_seq(seq);
-        if (rc || (rc = check_sparse_test(pass.alpha, pass.beta, pass.max_residual))) return rc;
-        return check_sparse_config(seq.H, seq.W, seq.levels, seq.window_size, seq.iters);
+        if (rc || (rc = check_sparse_test(pass.test))) return rc;
+        return check_sparse_config(seq.H, seq.W, seq);
     }
     static int pairs(int B, int H, int W) { return sparse_chunk_pairs(B, H, W); }
     int alloc(HostCall &call, const Seq &seq, int C) { return call.alloc(&frames, (size_t)(C + 1) * seq.frame_bytes()); }
@@ -3453,7 +3481,7 @@ OFLK_API int oflk_plan_sparse_tracks(oflk_plan *plan, const void *d_frames, int 
                                      int t0, const int *d_qt, const float *d_qxy, int N, float *d_tracks,
                                      unsigned char *d_visible, void *stream)
 {
-    return plan_sparse_tracks(plan, d_frames, u8 != 0, alpha, beta, max_residual, t0, d_qt, d_qxy, N, d_tracks, d_visible,
+    return plan_sparse_tracks(plan, d_frames, u8 != 0, {alpha, beta, max_residual}, t0, d_qt, d_qxy, N, d_tracks, d_visible,
                               (hipStream_t)stream);
 }
 
@@ -3461,7 +3489,7 @@ OFLK_API int oflk_pyramidal_sequence_sparse_tracks(const float *frames, int T, i
                                                    int iters, float alpha, float beta, float max_residual, const int *qt,
                                                    const float *qxy, int N, float *tracks, unsigned char *visible)
 {
-    return run_sequence_tracks(Seq{frames, false, T, H, W, levels, window_size, iters}, SparseTracks{{alpha, beta, max_residual}},
+    return run_sequence_tracks(Seq{{levels, window_size, iters}, frames, false, T, H, W}, SparseTracks{{{alpha, beta, max_residual}}},
                                GivenQueries{qt, qxy, N}, N, tracks, visible);
 }
 
@@ -3470,7 +3498,7 @@ OFLK_API int oflk_pyramidal_sequence_sparse_tracks_u8(const unsigned char *frame
                                                       const int *qt, const float *qxy, int N, float *tracks,
                                                       unsigned char *visible)
 {
-    return run_sequence_tracks(Seq{frames, true, T, H, W, levels, window_size, iters}, SparseTracks{{alpha, beta, max_residual}},
+    return run_sequence_tracks(Seq{{levels, window_size, iters}, frames, true, T, H, W}, SparseTracks{{{alpha, beta, max_residual}}},
                                GivenQueries{qt, qxy, N}, N, tracks, visible);
 }
 
@@ -3479,7 +3507,7 @@ OFLK_API int oflk_pyramidal_sequence_klt_sparse(const float *frames, int T, int 
                                                 float min_distance, int max_corners, int *count, float *xy, float *score,
                                                 float *tracks, unsigned char *visible)
 {
-    return run_sequence_tracks(Seq{frames, false, T, H, W, levels, window_size, iters}, SparseTracks{{alpha, beta, max_residual}},
+    return run_sequence_tracks(Seq{{levels, window_size, iters}, frames, false, T, H, W}, SparseTracks{{{alpha, beta, max_residual}}},
                                DetectOnce{quality_level, min_distance, max_corners, count, xy, score}, max_corners, tracks, visible);
 }
 
@@ -3488,7 +3516,7 @@ OFLK_API int oflk_pyramidal_sequence_klt_sparse_u8(const unsigned char *frames, 
                                                    float min_distance, int max_corners, int *count, float *xy, float *score,
                                                    float *tracks, unsigned char *visible)
 {
-    return run_sequence_tracks(Seq{frames, true, T, H, W, levels, window_size, iters}, SparseTracks{{alpha, beta, max_residual}},
+    return run_sequence_tracks(Seq{{levels, window_size, iters}, frames, true, T, H, W}, SparseTracks{{{alpha, beta, max_residual}}},
                                DetectOnce{quality_level, min_distance, max_corners, count, xy, score}, max_corners, tracks, visible);
 }
 
@@ -3498,8 +3526,8 @@ OFLK_API int oflk_pyramidal_sequence_klt_sparse_replenish(const float *frames, i
                                                           int detect_every, float *tracks, unsigned char *visible,
                                                           unsigned char *born, int *detected, float *residual)
 {
-    return run_sequence_tracks(Seq{frames, false, T, H, W, levels, window_size, iters}, SparseTracks{{alpha, beta, max_residual}},
-                               Replenished{{quality_level, min_distance, max_corners, detect_every}, born, detected, residual},
+    return run_sequence_tracks(Seq{{levels, window_size, iters}, frames, false, T, H, W}, SparseTracks{{{alpha, beta, max_residual}}},
+                               Replenished{{{quality_level, min_distance, max_corners, detect_every}}, born, detected, residual},
                                max_corners, tracks, visible);
 }
 
@@ -3510,8 +3538,8 @@ OFLK_API int oflk_pyramidal_sequence_klt_sparse_replenish_u8(const unsigned char
                                                              unsigned char *visible, unsigned char *born, int *detected,
                                                              float *residual)
 {
-    return run_sequence_tracks(Seq{frames, true, T, H, W, levels, window_size, iters}, SparseTracks{{alpha, beta, max_residual}},
-                               Replenished{{quality_level, min_distance, max_corners, detect_every}, born, detected, residual},
+    return run_sequence_tracks(Seq{{levels, window_size, iters}, frames, true, T, H, W}, SparseTracks{{{alpha, beta, max_residual}}},
+                               Replenished{{{quality_level, min_distance, max_corners, detect_every}}, born, detected, residual},
                                max_corners, tracks, visible);
 }
 
@@ -3524,10 +3552,10 @@ OFLK_API int oflk_plan_sparse_klt_replenish(oflk_plan *plan, const void *d_frame
     if (!plan || !d_frames) return fail(OFLK_ERR_INVALID, "NULL argument");
     if (!d_workspace || !d_qt || !d_qxy || !d_tracks || !d_visible || !d_born || !d_detected)
         return fail(OFLK_ERR_INVALID, "NULL workspace, slot state or output argument");
-    int rc = check_sparse_test(alpha, beta, max_residual);
-    if (rc || (rc = check_sparse_config(plan->H, plan->W, plan->L, plan->win, plan->K)) ||
-        (rc = check_select(quality_level, min_distance, max_corners)))
-        return rc;
+    const TrackTest test{alpha, beta, max_residual};
+    const Selection select{quality_level, min_distance, max_corners, detect_every};
+    int rc = check_sparse_test(test);
+    if (rc || (rc = check_sparse_config(plan->H, plan->W, plan_window(plan))) || (rc = check_select(select))) return rc;
     if (detect_every < 1) return fail(OFLK_ERR_INVALID, "detect_every must be >= 1 (got %d)", detect_every);
     if (t0 < 0 || t0 > INT_MAX - plan->B) return fail(OFLK_ERR_INVALID, "t0 must be in [0, INT_MAX - B] (got %d)", t0);
     const size_t need = feat_ws(nullptr, 1, plan->H, plan->W, min_distance, max_corners).bytes;
@@ -3539,10 +3567,10 @@ OFLK_API int oflk_plan_sparse_klt_replenish(oflk_plan *plan, const void *d_frame
         return fail(OFLK_ERR_INVALID, "d_workspace must be 256-byte aligned, d_qxy and d_tracks 8-byte aligned");
     // the plan's B+1 pyramids once, then the pairs t0 .. t0+B-1 as the host driver walks a chunk's: one chain of launches
     const hipStream_t s = (hipStream_t)stream;
-    const Slots k{quality_level, min_distance, max_corners, detect_every, d_workspace, d_born, d_detected};
+    const Slots k{select, d_workspace, d_born, d_detected};
     const TrackRows R{d_qt, d_qxy, d_tracks, d_visible, d_residual};
     const size_t fb = (size_t)plan->H * plan->W * (u8 ? 1 : sizeof(float));
-    SparsePass pass{alpha, beta, max_residual};
+    SparsePass pass{test};
     if ((rc = pass.begin(plan, d_frames, u8 != 0, s)) || (rc = slots_begin(k, R, t0, plan->B, s))) return rc;
     return walk_segments(
         t0, plan->B, detect_every,
@@ -3598,6 +3626,8 @@ int check_motion(int model, int hypotheses, float threshold)
         return fail(OFLK_ERR_INVALID, "unknown motion model %d", model);
     return check_ransac(hypotheses, threshold);
 }
+int check_ransac(const FitConfig &f) { return check_ransac(f.hypotheses, f.threshold); }   // f.model is an internal code
+int check_motion(const FitConfig &f) { return check_motion(f.model, f.hypotheses, f.threshold); }
 
 int check_motion_shape(int S, int N)
 {
@@ -3815,6 +3845,7 @@ int check_stab_window(const double *weights, int radius)
             return fail(OFLK_ERR_INVALID, "weights[%d] must be finite and > 0 (got %g)", i, weights[i]);
     return OFLK_OK;
 }
+int check_stab_window(const TrajWindow &w) { return check_stab_window(w.weights, w.radius); }
 
 int check_trajectory(const void *model, int T, const double *weights, int radius, const void *correction, const void *map)
 {
@@ -3948,18 +3979,20 @@ int warp_planar_launch(bool persp, const PIX *d_frames, int F, int H, int W, con
 // down, into this call's own arrays); the rows go up again for the fit and the trajectory of all T frames, and pass 2 warps
 // the frames chunk by chunk.
 // What the sequence calls refuse behind their frames, before any device call
-int check_stabilize_config(int H, int W, int levels, int window_size, int iters, float alpha, float beta, float max_residual, float q,
-                           float md, int K, int detect_every, int model, int hypotheses, float threshold, const double *weights,
-                           int radius)
+// the replenish call's own refusals, ahead of the arrays of a call that runs it as its pass 1 (it repeats them)
+int check_klt(int H, int W, const KltConfig &klt)
 {
-    int rc = check_motion(model, hypotheses, threshold);
-    if (rc || (rc = check_stab_window(weights, radius))) return rc;
-    // the replenish call's own refusals, ahead of this call's arrays (it repeats them)
-    if (detect_every < 1) return fail(OFLK_ERR_INVALID, "detect_every must be >= 1 (got %d)", detect_every);
-    if ((rc = check_select(q, md, K)) || (rc = check_sparse_test(alpha, beta, max_residual)) ||
-        (rc = check_sparse_config(H, W, levels, window_size, iters)))
-        return rc;
-    return OFLK_OK;
+    if (klt.select.every < 1) return fail(OFLK_ERR_INVALID, "detect_every must be >= 1 (got %d)", klt.select.every);
+    int rc = check_select(klt.select);
+    if (rc || (rc = check_sparse_test(klt.test))) return rc;
+    return check_sparse_config(H, W, klt.pyr);
+}
+
+int check_stabilize_config(int H, int W, const KltConfig &klt, const FitConfig &fit, const TrajWindow &window)
+{
+    int rc = check_motion(fit);
+    if (rc || (rc = check_stab_window(window))) return rc;
+    return check_klt(H, W, klt);
 }
 
 // What the sequence stabilisers and the mosaics do up to and including the fit's launch, on checked grey frames: pass 1 is
@@ -3973,11 +4006,10 @@ struct SequenceFit {
     float *d_model = nullptr;   // [T-1][motion_coeffs(model)]
     int *d_counts = nullptr;    // [T-1][3]
 
-    int run(HostCall &call, const Seq &seq, float alpha, float beta, float max_residual, float q, float md, int K, int detect_every,
-            int model, int hypotheses, float threshold, unsigned seed)
+    int run(HostCall &call, const void *frames, bool u8, int T, int H, int W, const KltConfig &klt, const FitConfig &fit)
     {
         int rc;
-        const int T = seq.T;
+        const int K = klt.select.K;
         const size_t row = (size_t)K, nT = (size_t)T, S = nT - 1;
         try {
             tracks.resize(nT * 2 * row);
@@ -3987,45 +4019,41 @@ struct SequenceFit {
         } catch (const std::exception &) {
             return fail(OFLK_ERR_NOMEM, "no host memory for the rows of %d frames of %d slots", T, K);
         }
-        if ((rc = run_sequence_tracks(seq, SparseTracks{{alpha, beta, max_residual}},
-                                      Replenished{{q, md, K, detect_every}, born.data(), detected.data(), nullptr}, K, tracks.data(),
-                                      visible.data())))
+        if ((rc = run_sequence_tracks(Seq{klt.pyr, frames, u8, T, H, W}, SparseTracks{{klt.test}},
+                                      Replenished{{klt.select}, born.data(), detected.data(), nullptr}, K, tracks.data(), visible.data())))
             return rc;
         if ((rc = call.begin())) return rc;
         float *d_tr;
         unsigned char *d_vis, *d_born, *d_inl;
         char *d_ws;
-        const int nc = motion_coeffs(model);
+        const int nc = motion_coeffs(fit.model);
         if ((rc = call.upload(&d_tr, (const float *)tracks.data(), nT * 2 * row)) ||
             (rc = call.upload(&d_vis, (const unsigned char *)visible.data(), nT * row)) ||
             (rc = call.upload(&d_born, (const unsigned char *)born.data(), nT * row)) ||
-            (rc = call.alloc(&d_ws, motion_ws(nullptr, T - 1, K, hypotheses, nc).bytes)) || (rc = call.alloc(&d_model, (size_t)nc * S)) ||
-            (rc = call.alloc(&d_inl, S * row)) || (rc = call.alloc(&d_counts, 3 * S)))
+            (rc = call.alloc(&d_ws, motion_ws(nullptr, T - 1, K, fit.hypotheses, nc).bytes)) ||
+            (rc = call.alloc(&d_model, (size_t)nc * S)) || (rc = call.alloc(&d_inl, S * row)) || (rc = call.alloc(&d_counts, 3 * S)))
             return rc;
-        return motion_launch(motion_rows(d_tr, d_vis, d_born, K), T - 1, K, 0u, model, hypotheses, threshold, seed,
-                             motion_ws(d_ws, T - 1, K, hypotheses, nc), d_model, d_inl, d_counts, nullptr);
+        return motion_launch(motion_rows(d_tr, d_vis, d_born, K), T - 1, K, 0u, fit.model, fit.hypotheses, fit.threshold, fit.seed,
+                             motion_ws(d_ws, T - 1, K, fit.hypotheses, nc), d_model, d_inl, d_counts, nullptr);
     }
 };
 
 // Pass 1 and the trajectory of a sequence call on the checked grey frames: begins `call`, leaves the maps of all T frames in
 // its *d_map_out [T][6] and sends the four small outputs on their way (the caller's last chunk synchronises)
-int stabilize_maps(HostCall &call, const void *frames, bool u8, int T, int H, int W, int levels, int window_size, int iters,
-                   float alpha, float beta, float max_residual, float q, float md, int K, int detect_every, int model, int hypotheses,
-                   float threshold, unsigned seed, const double *weights, int radius, float *correction, float *model_out,
-                   int *counts_out, unsigned char *held, double **d_map_out)
+int stabilize_maps(HostCall &call, const void *frames, bool u8, int T, int H, int W, const KltConfig &klt, const FitConfig &fit,
+                   const TrajWindow &window, float *correction, float *model_out, int *counts_out, unsigned char *held,
+                   double **d_map_out)
 {
     int rc;
     const size_t nT = (size_t)T, S = nT - 1;
-    SequenceFit fit;
-    if ((rc = fit.run(call, Seq{frames, u8, T, H, W, levels, window_size, iters}, alpha, beta, max_residual, q, md, K, detect_every,
-                      model, hypotheses, threshold, seed)))
-        return rc;
-    float *const d_model = fit.d_model, *d_corr;
-    int *const d_cnt = fit.d_counts;
+    SequenceFit steps;
+    if ((rc = steps.run(call, frames, u8, T, H, W, klt, fit))) return rc;
+    float *const d_model = steps.d_model, *d_corr;
+    int *const d_cnt = steps.d_counts;
     unsigned char *d_held;
     double *d_map;
     if ((rc = call.alloc(&d_corr, 6 * nT)) || (rc = call.alloc(&d_map, 6 * nT)) || (rc = call.alloc(&d_held, S)) ||
-        (rc = trajectory_launch(d_model, d_cnt, T, weights, radius, d_corr, d_map, d_held, nullptr)))
+        (rc = trajectory_launch(d_model, d_cnt, T, window.weights, window.radius, d_corr, d_map, d_held, nullptr)))
         return rc;
     if ((correction && (rc = call.to_host(correction, d_corr, 6 * nT))) || (model_out && (rc = call.to_host(model_out, d_model, 6 * S))) ||
         (counts_out && (rc = call.to_host(counts_out, d_cnt, 3 * S))) || (held && (rc = call.to_host(held, d_held, S))))
@@ -4262,18 +4290,14 @@ int warp_device(const FrameLayout &L, bool persp, const void *d_frames, int F, i
 // of luma of this call's own, one byte a pixel: the packed frames' luma comes down in a chunked pass ahead of pass 1 (a
 // third or a quarter of the caller's frames), the NV12 frames' Y planes are gathered with no device work (two thirds).
 // Pass 2 warps the caller's frames in their own layout.
-int stabilize_sequence(const FrameLayout &L, const void *frames, int T, int H, int W, int levels, int window_size, int iters,
-                       float alpha, float beta, float max_residual, float q, float md, int K, int detect_every, int model,
-                       int hypotheses, float threshold, unsigned seed, const double *weights, int radius, void *out,
-                       float *correction, float *model_out, int *counts_out, unsigned char *held)
+int stabilize_sequence(const FrameLayout &L, const void *frames, int T, int H, int W, const KltConfig &klt, const FitConfig &fit,
+                       const TrajWindow &window, void *out, float *correction, float *model_out, int *counts_out,
+                       unsigned char *held)
 {
     int rc = check_layout(L, H, W);
     if (rc) return rc;
     if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
-    if ((rc = check_frames(L, frames, T, H, W, out)) ||
-        (rc = check_stabilize_config(H, W, levels, window_size, iters, alpha, beta, max_residual, q, md, K, detect_every, model,
-                                     hypotheses, threshold, weights, radius)))
-        return rc;
+    if ((rc = check_frames(L, frames, T, H, W, out)) || (rc = check_stabilize_config(H, W, klt, fit, window))) return rc;
     const unsigned char *bytes = static_cast<const unsigned char *>(frames);
     const size_t plane = (size_t)H * W;
     std::vector<unsigned char> luma;
@@ -4301,8 +4325,7 @@ int stabilize_sequence(const FrameLayout &L, const void *frames, int T, int H, i
     const bool planar = L.kind == FrameKind::Planar;
     HostCall call;
     double *d_map = nullptr;
-    if ((rc = stabilize_maps(call, planar ? frames : luma.data(), planar ? L.pix_bytes == 1 : true, T, H, W, levels, window_size, iters,
-                             alpha, beta, max_residual, q, md, K, detect_every, model, hypotheses, threshold, seed, weights, radius,
+    if ((rc = stabilize_maps(call, planar ? frames : luma.data(), planar ? L.pix_bytes == 1 : true, T, H, W, klt, fit, window,
                              correction, model_out, counts_out, held, &d_map)))
         return rc;
     return warp_chunks(call, L, false, frames, T, H, W, d_map, out, nullptr);
@@ -4399,9 +4422,9 @@ OFLK_API int oflk_stabilize_sequence(const float *frames, int T, int H, int W, i
                                      const double *weights, int radius, float *out, float *correction, float *model_out,
                                      int *counts_out, unsigned char *held)
 {
-    return stabilize_sequence(FrameLayout::planar(false), frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual,
-                              quality_level, min_distance, max_corners, detect_every, model, hypotheses, threshold, seed, weights, radius,
-                              out, correction, model_out, counts_out, held);
+    return stabilize_sequence(FrameLayout::planar(false), frames, T, H, W,
+                              {{levels, window_size, iters}, {alpha, beta, max_residual}, {quality_level, min_distance, max_corners, detect_every}},
+                              {model, hypotheses, threshold, seed}, {weights, radius}, out, correction, model_out, counts_out, held);
 }
 
 OFLK_API int oflk_stabilize_sequence_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size, int iters,
@@ -4410,9 +4433,9 @@ OFLK_API int oflk_stabilize_sequence_u8(const unsigned char *frames, int T, int 
                                         unsigned seed, const double *weights, int radius, unsigned char *out, float *correction,
                                         float *model_out, int *counts_out, unsigned char *held)
 {
-    return stabilize_sequence(FrameLayout::planar(true), frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual,
-                              quality_level, min_distance, max_corners, detect_every, model, hypotheses, threshold, seed, weights, radius,
-                              out, correction, model_out, counts_out, held);
+    return stabilize_sequence(FrameLayout::planar(true), frames, T, H, W,
+                              {{levels, window_size, iters}, {alpha, beta, max_residual}, {quality_level, min_distance, max_corners, detect_every}},
+                              {model, hypotheses, threshold, seed}, {weights, radius}, out, correction, model_out, counts_out, held);
 }
 
 OFLK_API int oflk_stabilize_sequence_packed(const unsigned char *frames, int T, int H, int W, int channels, int order, int levels,
@@ -4422,9 +4445,9 @@ OFLK_API int oflk_stabilize_sequence_packed(const unsigned char *frames, int T, 
                                             unsigned char *out, float *correction, float *model_out, int *counts_out,
                                             unsigned char *held)
 {
-    return stabilize_sequence(FrameLayout::packed(channels, order), frames, T, H, W, levels, window_size, iters, alpha, beta,
-                              max_residual, quality_level, min_distance, max_corners, detect_every, model, hypotheses, threshold, seed,
-                              weights, radius, out, correction, model_out, counts_out, held);
+    return stabilize_sequence(FrameLayout::packed(channels, order), frames, T, H, W,
+                              {{levels, window_size, iters}, {alpha, beta, max_residual}, {quality_level, min_distance, max_corners, detect_every}},
+                              {model, hypotheses, threshold, seed}, {weights, radius}, out, correction, model_out, counts_out, held);
 }
 
 OFLK_API int oflk_stabilize_sequence_nv12(const unsigned char *frames, int T, int H, int W, int siting, int levels, int window_size,
@@ -4433,9 +4456,9 @@ OFLK_API int oflk_stabilize_sequence_nv12(const unsigned char *frames, int T, in
                                           float threshold, unsigned seed, const double *weights, int radius, unsigned char *out,
                                           float *correction, float *model_out, int *counts_out, unsigned char *held)
 {
-    return stabilize_sequence(FrameLayout::nv12(siting), frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual,
-                              quality_level, min_distance, max_corners, detect_every, model, hypotheses, threshold, seed, weights, radius,
-                              out, correction, model_out, counts_out, held);
+    return stabilize_sequence(FrameLayout::nv12(siting), frames, T, H, W,
+                              {{levels, window_size, iters}, {alpha, beta, max_residual}, {quality_level, min_distance, max_corners, detect_every}},
+                              {model, hypotheses, threshold, seed}, {weights, radius}, out, correction, model_out, counts_out, held);
 }
 
 // =============================================================================
@@ -4603,20 +4626,17 @@ int mosaic_composite_host(const PIX *frames, int F, int H, int W, const double *
 // oflk_mosaic_sequence: pass 1 is the replenish call itself, as in stabilize_sequence; the rows go up again for the
 // homography fit and the chain; the boxes and drop flags come down for the canvas; pass 2 adds the frames chunk by chunk
 template <class PIX>
-int mosaic_sequence(const PIX *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
-                    float max_residual, float q, float md, int K, int detect_every, int hypotheses, float threshold, unsigned seed,
-                    int anchor, double extent, int blend, PIX *out, size_t capacity, int *canvas, int *count, double *to_anchor,
-                    unsigned char *held, unsigned char *dropped, float *model_out, int *counts_out)
+int mosaic_sequence(const PIX *frames, int T, int H, int W, const KltConfig &klt, const FitConfig &fit, int anchor, double extent,
+                    int blend, PIX *out, size_t capacity, int *canvas, int *count, double *to_anchor, unsigned char *held,
+                    unsigned char *dropped, float *model_out, int *counts_out)
 {
     if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
     if (!canvas) return fail(OFLK_ERR_INVALID, "NULL canvas");
+    const int K = klt.select.K;
     int rc = check_frames(FrameLayout::planar(sizeof(PIX) == 1), frames, T, H, W, out);
-    if (rc || (rc = check_ransac(hypotheses, threshold)) || (rc = check_mosaic_blend(blend)) ||
-        (rc = check_mosaic_chain(frames, T, anchor, H, W, extent, frames, frames, frames, frames)))
-        return rc;
-    if (detect_every < 1) return fail(OFLK_ERR_INVALID, "detect_every must be >= 1 (got %d)", detect_every);
-    if ((rc = check_select(q, md, K)) || (rc = check_sparse_test(alpha, beta, max_residual)) ||
-        (rc = check_sparse_config(H, W, levels, window_size, iters)) || (rc = check_motion_shape(T - 1, K)))
+    if (rc || (rc = check_ransac(fit)) || (rc = check_mosaic_blend(blend)) ||
+        (rc = check_mosaic_chain(frames, T, anchor, H, W, extent, frames, frames, frames, frames)) || (rc = check_klt(H, W, klt)) ||
+        (rc = check_motion_shape(T - 1, K)))
         return rc;
     const size_t nT = (size_t)T, S = nT - 1;
     std::vector<unsigned char> h_dropped;
@@ -4627,13 +4647,11 @@ int mosaic_sequence(const PIX *frames, int T, int H, int W, int levels, int wind
     } catch (const std::exception &) {
         return fail(OFLK_ERR_NOMEM, "no host memory for the rows of %d frames of %d slots", T, K);
     }
-    SequenceFit fit;   // before `call`: the host rows outlive the device buffers
+    SequenceFit steps;   // before `call`: the host rows outlive the device buffers
     HostCall call;
-    if ((rc = fit.run(call, Seq{frames, sizeof(PIX) == 1, T, H, W, levels, window_size, iters}, alpha, beta, max_residual, q, md, K,
-                      detect_every, kMotionHomography, hypotheses, threshold, seed)))
-        return rc;
-    float *const d_model = fit.d_model;
-    int *const d_cnt = fit.d_counts;
+    if ((rc = steps.run(call, frames, sizeof(PIX) == 1, T, H, W, klt, fit))) return rc;   // fit.model: kMotionHomography
+    float *const d_model = steps.d_model;
+    int *const d_cnt = steps.d_counts;
     unsigned char *d_held, *d_drop;
     double *d_from, *d_to, *d_box;
     if ((rc = call.alloc(&d_from, 9 * nT)) || (rc = call.alloc(&d_to, 9 * nT)) || (rc = call.alloc(&d_box, 4 * nT)) ||
@@ -4843,9 +4861,10 @@ OFLK_API int oflk_mosaic_sequence(const float *frames, int T, int H, int W, int 
                                   int blend, float *out, size_t capacity, int *canvas, int *count, double *to_anchor,
                                   unsigned char *held, unsigned char *dropped, float *model_out, int *counts_out)
 {
-    return mosaic_sequence<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, quality_level, min_distance,
-                                  max_corners, detect_every, hypotheses, threshold, seed, anchor, extent, blend, out, capacity, canvas,
-                                  count, to_anchor, held, dropped, model_out, counts_out);
+    return mosaic_sequence<float>(
+        frames, T, H, W, {{levels, window_size, iters}, {alpha, beta, max_residual}, {quality_level, min_distance, max_corners, detect_every}},
+        {kMotionHomography, hypotheses, threshold, seed}, anchor, extent, blend, out, capacity, canvas, count, to_anchor, held, dropped,
+        model_out, counts_out);
 }
 
 OFLK_API int oflk_mosaic_sequence_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size, int iters,
@@ -4854,9 +4873,10 @@ OFLK_API int oflk_mosaic_sequence_u8(const unsigned char *frames, int T, int H, 
                                      double extent, int blend, unsigned char *out, size_t capacity, int *canvas, int *count,
                                      double *to_anchor, unsigned char *held, unsigned char *dropped, float *model_out, int *counts_out)
 {
-    return mosaic_sequence<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, max_residual, quality_level,
-                                          min_distance, max_corners, detect_every, hypotheses, threshold, seed, anchor, extent, blend,
-                                          out, capacity, canvas, count, to_anchor, held, dropped, model_out, counts_out);
+    return mosaic_sequence<unsigned char>(
+        frames, T, H, W, {{levels, window_size, iters}, {alpha, beta, max_residual}, {quality_level, min_distance, max_corners, detect_every}},
+        {kMotionHomography, hypotheses, threshold, seed}, anchor, extent, blend, out, capacity, canvas, count, to_anchor, held, dropped,
+        model_out, counts_out);
 }
 
 // =============================================================================
@@ -4864,14 +4884,28 @@ OFLK_API int oflk_mosaic_sequence_u8(const unsigned char *frames, int T, int H, 
 // =============================================================================
 namespace {
 int align_coefficients(int model) { return model == OFLK_ALIGN_HOMOGRAPHY ? 9 : 6; }
-int align_nsums(int model, bool photo = false, bool robust = false)
+int align_nsums(int model, bool photo, bool robust)
 {
     return align_sums(model == OFLK_ALIGN_HOMOGRAPHY ? 8 : 6, photo, robust);
 }
 int align_tiles(int h, int w) { return ((w + kAlignTileW - 1) / kAlignTileW) * ((h + kAlignTileH - 1) / kAlignTileH); }
 
-// The refusals of the configuration, before any device call; dims receives the level sizes
-int check_align(int S, int H, int W, int levels, int iterations, int model, float min_share, int *dims)
+// One alignment call as every layer takes it: the configuration with its form (photometric, robust; check_align leaves
+// robust_delta 0 without `robust`) and the steps' buffers, device or host: [S][6 | 9], [S] (or NULL), the same two out, stats
+// [S][4 | 8] and the photometric form's (g, b) [S][2] (check_align leaves it NULL without `photo`)
+struct AlignConfig { int levels, iterations, model; float min_share; bool photo, robust; float robust_delta; };
+struct AlignIo { const float *model_in; const int *status_in; float *model_out; int *status_out; double *stats; float *photo_out; };
+
+// the robust forms' own refusal
+int check_robust_delta(float robust_delta)
+{
+    if (!(std::isfinite(robust_delta) && robust_delta > 0.0f))
+        return fail(OFLK_ERR_INVALID, "robust_delta must be finite and > 0 (got %g)", (double)robust_delta);
+    return OFLK_OK;
+}
+
+// the refusals of the steps' shape and model, which the weight map shares
+int check_align_shape(int S, int H, int W, int model)
 {
     if (S < 1) return fail(OFLK_ERR_INVALID, "S must be >= 1 (got %d)", S);
     if (H < 1 || W < 1) return fail(OFLK_ERR_INVALID, "H and W must be >= 1 (got %d x %d)", H, W);
@@ -4879,8 +4913,17 @@ int check_align(int S, int H, int W, int levels, int iterations, int model, floa
     if (H >= kMaxDim || W >= kMaxDim)
         return fail(OFLK_ERR_UNSUPPORTED, "frames of 2^23 rows or columns or more are not supported (got %d x %d)", H, W);
     if (model != OFLK_ALIGN_AFFINE && model != OFLK_ALIGN_HOMOGRAPHY) return fail(OFLK_ERR_INVALID, "unknown model %d", model);
-    if (iterations < 1) return fail(OFLK_ERR_INVALID, "iterations must be >= 1 (got %d)", iterations);
-    if (!(min_share > 0.0f && min_share <= 1.0f)) return fail(OFLK_ERR_INVALID, "min_share must be in (0, 1] (got %g)", (double)min_share);
+    return OFLK_OK;
+}
+
+// The refusals of the configuration, before any device call; dims receives the level sizes.  What a form does not have is
+// taken out of cfg and io: the layers below tell the form by them
+int check_align(int S, int H, int W, AlignConfig &cfg, AlignIo &io, int *dims)
+{
+    if (int rc = check_align_shape(S, H, W, cfg.model)) return rc;
+    if (cfg.iterations < 1) return fail(OFLK_ERR_INVALID, "iterations must be >= 1 (got %d)", cfg.iterations);
+    const int levels = cfg.levels;
+    if (!(cfg.min_share > 0.0f && cfg.min_share <= 1.0f)) return fail(OFLK_ERR_INVALID, "min_share must be in (0, 1] (got %g)", (double)cfg.min_share);
     if (levels < 1 || levels > OFLK_MAX_LEVELS) return fail(OFLK_ERR_INVALID, "levels must be in [1,%d] (got %d)", OFLK_MAX_LEVELS, levels);
     int h = H, w = W;
     for (int l = levels - 1; l >= 0; l--) {
@@ -4891,7 +4934,9 @@ int check_align(int S, int H, int W, int levels, int iterations, int model, floa
         h = (int)((double)h * 0.5);
         w = (int)((double)w * 0.5);
     }
-    return OFLK_OK;
+    if (!cfg.robust) cfg.robust_delta = 0.0f;
+    if (!cfg.photo) io.photo_out = nullptr;
+    return cfg.robust ? check_robust_delta(cfg.robust_delta) : OFLK_OK;
 }
 
 // The workspace, 256-byte aligned pieces: the steps' states [S], the tile sums [S][tiles of the frame][NS], and per level
@@ -4907,26 +4952,27 @@ struct AlignWs {
     size_t pstride, bytes;
 };
 
-AlignWs align_ws(void *base, int S, int levels, const int *dims, int model, bool photo = false, bool robust = false)
+AlignWs align_ws(void *base, int S, const int *dims, const AlignConfig &cfg)
 {
+    const int levels = cfg.levels;
     char *b = static_cast<char *>(base);
     auto at = [&](size_t o) { return b ? b + o : nullptr; };   // NULL: only the size is wanted
     AlignWs ws{};
     size_t o = 0;
     ws.state = reinterpret_cast<AlignState *>(at(o));
     o += round256((size_t)S * sizeof(AlignState));
-    ws.pstride = (size_t)align_tiles(dims[2 * (levels - 1)], dims[2 * (levels - 1) + 1]) * (size_t)align_nsums(model, photo, robust);
+    ws.pstride = (size_t)align_tiles(dims[2 * (levels - 1)], dims[2 * (levels - 1) + 1]) * (size_t)align_nsums(cfg.model, cfg.photo, cfg.robust);
     ws.partial = reinterpret_cast<double *>(at(o));
     o += round256((size_t)S * ws.pstride * sizeof(double));
     for (int l = 0; l < levels - 1; l++) {
         ws.pyr[l] = reinterpret_cast<float *>(at(o));
         o += round256(2 * (size_t)S * (size_t)dims[2 * l] * (size_t)dims[2 * l + 1] * sizeof(float));
     }
-    if (photo) {
+    if (cfg.photo) {
         ws.photo = reinterpret_cast<double *>(at(o));
         o += round256(2 * (size_t)S * sizeof(double));
     }
-    if (robust) {
+    if (cfg.robust) {
         ws.first = reinterpret_cast<double *>(at(o));
         o += round256(2 * (size_t)S * sizeof(double));
     }
@@ -4962,41 +5008,33 @@ int align_reduce_launch(const AlignReduceArgs &r, int tiles, hipStream_t s)
 
 // The whole chain of one call on stream s; the arguments are checked.  d_a, d_b: the S templates and images, `step` elements
 // apart (the pair form: two arrays of S frames; the sequence form: d_b = d_a + one frame).  nimg > 0: the sequence form's
-// nimg = S + 1 frames, whose pyramids are built once.  d_photo_out: NULL, or the photometric
-// form's output (ws is then that form's workspace).  robust_delta > 0: the robust form, d_stats [S][8] and ws that form's
+// nimg = S + 1 frames, whose pyramids are built once.  cfg and io are check_align's: io.photo_out is NULL or the
+// photometric form's output, cfg.robust_delta > 0 in the robust form (io.stats [S][8]), and ws is that form's workspace
 template <class PIX, int NP>
-int align_launch(const PIX *d_a, const PIX *d_b, int nimg, int S, int H, int W, int levels, const int *dims, int iterations,
-                 float min_share, const float *d_model_in, const int *d_status_in, const AlignWs &ws, float *d_model_out,
-                 int *d_status_out, double *d_stats, hipStream_t s, float *d_photo_out = nullptr, float robust_delta = 0.0f)
+int align_launch(const PIX *d_a, const PIX *d_b, int nimg, int S, int H, int W, const int *dims, const AlignConfig &cfg,
+                 const AlignIo &io, const AlignWs &ws, hipStream_t s)
 {
-    const double delta = (double)robust_delta;
+    const int levels = cfg.levels, iterations = cfg.iterations;
+    const double delta = (double)cfg.robust_delta;
     constexpr int NC = NP == 8 ? 9 : 6;
     const bool seq = nimg > 0;
     const int n = seq ? nimg : 2 * S;
     int rc;
     if (levels > 1) {
         GaussW gauss;
-        if ((rc = make_gauss(2.0, &gauss))) return rc;
-        for (int l = levels - 2; l >= 0; l--)
-            if (!pyr_fused_fits(dims[2 * (l + 1)], dims[2 * (l + 1) + 1], dims[2 * l], dims[2 * l + 1], gauss))
-                return fail(OFLK_ERR_UNSUPPORTED, "pyramid level %d of %dx%d does not fit the fused pyramid kernel", l, W, H);
+        if ((rc = make_gauss(2.0, &gauss)) || (rc = pyr_chain_fits(dims, levels, gauss))) return rc;
         PyrExtra first;
         first.u8 = sizeof(PIX) == 1;
         if (!seq) {
             first.in2 = reinterpret_cast<const float *>(d_b);
             first.nsplit = S;
         }
-        const float *in = reinterpret_cast<const float *>(d_a);
-        for (int l = levels - 2; l >= 0; l--) {
-            if ((rc = launch_pyr_down(nullptr, gauss, s, in, ws.pyr[l], nullptr, nullptr, n, dims[2 * (l + 1)], dims[2 * (l + 1) + 1],
-                                      dims[2 * l], dims[2 * l + 1], l == levels - 2 ? &first : nullptr)))
-                return rc;
-            in = ws.pyr[l];
-        }
+        if ((rc = pyr_chain(nullptr, gauss, s, reinterpret_cast<const float *>(d_a), ws.pyr, 0, nullptr, nullptr, n, dims, levels, first)))
+            return rc;
     }
-    hipLaunchKernelGGL(k_align_begin, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, s, d_model_in, d_status_in, S, NC, ws.state);
+    hipLaunchKernelGGL(k_align_begin, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, s, io.model_in, io.status_in, S, NC, ws.state);
     HIP_TRY(hipGetLastError());
-    const double *photo = d_photo_out ? ws.photo : nullptr;
+    const double *photo = io.photo_out ? ws.photo : nullptr;
     if (photo) {
         hipLaunchKernelGGL(k_align_photo_begin, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, s, S, ws.photo);
         HIP_TRY(hipGetLastError());
@@ -5032,9 +5070,9 @@ int align_launch(const PIX *d_a, const PIX *d_b, int nimg, int S, int H, int W, 
             u.nh = dims[2 * next];
             u.nw = dims[2 * next + 1];
         }
-        u.min_count = (double)min_share * (double)((long long)w * (long long)h);
-        u.model_in = d_model_in; u.model_out = d_model_out; u.status_out = d_status_out; u.stats = d_stats;
-        u.photo = photo ? ws.photo : nullptr; u.photo_out = d_photo_out; u.first = ws.first;
+        u.min_count = (double)cfg.min_share * (double)((long long)w * (long long)h);
+        u.model_in = io.model_in; u.model_out = io.model_out; u.status_out = io.status_out; u.stats = io.stats;
+        u.photo = photo ? ws.photo : nullptr; u.photo_out = io.photo_out; u.first = ws.first;
         with_bool(photo != nullptr, [&](auto PHOTO) {
             with_bool(delta > 0.0, [&](auto ROBUST) {
                 hipLaunchKernelGGL((k_align_update<NP, decltype(PHOTO)::value, decltype(ROBUST)::value>), dim3((unsigned)std::min(S, 65535)),
@@ -5053,78 +5091,72 @@ int align_launch(const PIX *d_a, const PIX *d_b, int nimg, int S, int H, int W, 
     return pass(levels - 1, kAlignLast, 0, -1);
 }
 
+// the affine or the homography instantiation of align_launch, by cfg.model
 template <class PIX>
-int align_dispatch(const PIX *d_a, const PIX *d_b, int nimg, int S, int H, int W, int levels, const int *dims, int iterations,
-                   int model, float min_share, const float *d_model_in, const int *d_status_in, const AlignWs &ws,
-                   float *d_model_out, int *d_status_out, double *d_stats, hipStream_t s, float *d_photo_out = nullptr,
-                   float robust_delta = 0.0f)
+int align_dispatch(const PIX *d_a, const PIX *d_b, int nimg, int S, int H, int W, const int *dims, const AlignConfig &cfg,
+                   const AlignIo &io, const AlignWs &ws, hipStream_t s)
 {
-    return model == OFLK_ALIGN_HOMOGRAPHY
-               ? align_launch<PIX, 8>(d_a, d_b, nimg, S, H, W, levels, dims, iterations, min_share, d_model_in, d_status_in, ws,
-                                      d_model_out, d_status_out, d_stats, s, d_photo_out, robust_delta)
-               : align_launch<PIX, 6>(d_a, d_b, nimg, S, H, W, levels, dims, iterations, min_share, d_model_in, d_status_in, ws,
-                                      d_model_out, d_status_out, d_stats, s, d_photo_out, robust_delta);
+    int rc = OFLK_OK;
+    with_int<6, 8>(cfg.model == OFLK_ALIGN_HOMOGRAPHY ? 8 : 6,
+                   [&](auto NP) { rc = align_launch<PIX, decltype(NP)::value>(d_a, d_b, nimg, S, H, W, dims, cfg, io, ws, s); });
+    return rc;
 }
 
-// the robust forms' own refusal
-int check_robust_delta(float robust_delta)
+// The steps of a call: the n pairs of (a, b), or (seq) the n - 1 steps of the n frames at a.  The sequence forms' first
+// refusal; with b, their second image set: the frames one plane on (a NULL, or a shape that is refused later, stays as it is)
+int align_steps(bool seq, int n, const void *a, const void **b, size_t pix_bytes, int H, int W, int *S)
 {
-    if (!(std::isfinite(robust_delta) && robust_delta > 0.0f))
-        return fail(OFLK_ERR_INVALID, "robust_delta must be finite and > 0 (got %g)", (double)robust_delta);
+    if (seq && n < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", n);
+    *S = seq ? n - 1 : n;
+    if (seq && b) *b = a && H > 0 && W > 0 ? static_cast<const char *>(a) + (size_t)H * (size_t)W * pix_bytes : a;
     return OFLK_OK;
 }
 
-int align_device(const void *d_a, const void *d_b, int u8, int nimg, int S, int H, int W, int levels, int iterations, int model,
-                 float min_share, const float *d_model_in, const int *d_status_in, void *d_workspace, size_t bytes,
-                 float *d_model_out, int *d_status_out, double *d_stats, hipStream_t s, bool photo = false,
-                 float *d_photo_out = nullptr, bool robust = false, float robust_delta = 0.0f)
+// Every device form.  n: the S pairs of d_a and d_b, or (seq) the T frames at d_a
+int align_device(const void *d_a, const void *d_b, int u8, bool seq, int n, int H, int W, AlignConfig cfg, AlignIo io,
+                 void *d_workspace, size_t bytes, void *stream)
 {
-    int dims[2 * OFLK_MAX_LEVELS];
-    int rc = check_align(S, H, W, levels, iterations, model, min_share, dims);
-    if (rc) return rc;
-    if (robust && (rc = check_robust_delta(robust_delta))) return rc;
-    if (!robust) robust_delta = 0.0f;
-    if (!photo) d_photo_out = nullptr;
-    const size_t need = align_ws(nullptr, S, levels, dims, model, photo, robust).bytes;
-    if ((rc = check_align_device(d_a, d_b, u8, d_model_in, d_workspace, bytes, need, d_model_out, d_status_out, d_stats))) return rc;
-    if (photo && !d_photo_out) return fail(OFLK_ERR_INVALID, "NULL d_photo_out");
-    if (photo && !aligned(d_photo_out, 4)) return fail(OFLK_ERR_INVALID, "d_photo_out must be 4-byte aligned");
-    const AlignWs ws = align_ws(d_workspace, S, levels, dims, model, photo, robust);
-    return u8 ? align_dispatch<unsigned char>((const unsigned char *)d_a, (const unsigned char *)d_b, nimg, S, H, W, levels, dims,
-                                              iterations, model, min_share, d_model_in, d_status_in, ws, d_model_out, d_status_out,
-                                              d_stats, s, d_photo_out, robust_delta)
-              : align_dispatch<float>((const float *)d_a, (const float *)d_b, nimg, S, H, W, levels, dims, iterations, model, min_share,
-                                      d_model_in, d_status_in, ws, d_model_out, d_status_out, d_stats, s, d_photo_out, robust_delta);
+    int dims[2 * OFLK_MAX_LEVELS], S;
+    int rc = align_steps(seq, n, d_a, &d_b, u8 ? 1 : sizeof(float), H, W, &S);
+    if (rc || (rc = check_align(S, H, W, cfg, io, dims))) return rc;
+    const size_t need = align_ws(nullptr, S, dims, cfg).bytes;
+    if ((rc = check_align_device(d_a, d_b, u8, io.model_in, d_workspace, bytes, need, io.model_out, io.status_out, io.stats))) return rc;
+    if (cfg.photo && !io.photo_out) return fail(OFLK_ERR_INVALID, "NULL d_photo_out");
+    if (cfg.photo && !aligned(io.photo_out, 4)) return fail(OFLK_ERR_INVALID, "d_photo_out must be 4-byte aligned");
+    const AlignWs ws = align_ws(d_workspace, S, dims, cfg);
+    with_pix(u8 != 0, [&](auto PIX) {
+        using P = typename decltype(PIX)::type;
+        rc = align_dispatch<P>(static_cast<const P *>(d_a), static_cast<const P *>(d_b), seq ? n : 0, S, H, W, dims, cfg, io, ws,
+                               (hipStream_t)stream);
+    });
+    return rc;
 }
 
-// S host steps in chunks of steps through one set of device buffers: a chunk's frames go up, its steps are refined and the
-// models, statuses and stats of all steps come down at the end.  Steps are independent and a frame's pyramid depends on the
-// frame alone, so the cut does not show.  seq: frames [S + 1][H][W], a chunk of n steps takes its n + 1 frames (b is unused)
+// Every host form, n_in as align_device's n.  The S steps go in chunks through one set of device buffers: a chunk's frames go up,
+// its steps are refined and the models, statuses and stats of all steps come down at the end.  Steps are independent and a frame's
+// pyramid depends on the frame alone, so the cut does not show.  seq: a chunk of n steps takes its n + 1 frames (b is unused)
 template <class PIX>
-int align_host(const PIX *a, const PIX *b, bool seq, int S, int H, int W, int levels, int iterations, int model, float min_share,
-               const float *model_in, const int *status_in, float *model_out, int *status_out, double *stats, bool photo = false,
-               float *photo_out = nullptr, bool robust = false, float robust_delta = 0.0f)
+int align_host(const PIX *a, const PIX *b, bool seq, int n_in, int H, int W, AlignConfig cfg, AlignIo io)
 {
-    int dims[2 * OFLK_MAX_LEVELS];
-    int rc = check_align(S, H, W, levels, iterations, model, min_share, dims);
-    if (rc) return rc;
-    if (robust && (rc = check_robust_delta(robust_delta))) return rc;
-    if (!robust) robust_delta = 0.0f;
-    const size_t ns = robust ? 8 : 4;   // a step's stats
-    if (!a || (!seq && !b) || !model_in || !model_out || !status_out || !stats || (photo && !photo_out))
+    int dims[2 * OFLK_MAX_LEVELS], S;
+    int rc = align_steps(seq, n_in, a, nullptr, sizeof(PIX), H, W, &S);
+    if (rc || (rc = check_align(S, H, W, cfg, io, dims))) return rc;
+    const bool photo = cfg.photo;
+    const size_t ns = cfg.robust ? 8 : 4;   // a step's stats
+    if (!a || (!seq && !b) || !io.model_in || !io.model_out || !io.status_out || !io.stats || (photo && !io.photo_out))
         return fail(OFLK_ERR_INVALID, "NULL input or output argument");
     HostCall call;
     if ((rc = call.begin())) return rc;
-    const int C = sparse_chunk_pairs(S, H, W), nc = align_coefficients(model);
+    const int C = sparse_chunk_pairs(S, H, W), nc = align_coefficients(cfg.model);
     const size_t plane = (size_t)H * W, nS = (size_t)S;
     PIX *d_a = nullptr, *d_b = nullptr;
     float *d_min = nullptr, *d_mout = nullptr, *d_photo = nullptr;
     int *d_sin = nullptr, *d_sout = nullptr;
     double *d_stats = nullptr;
     char *d_ws = nullptr;
-    const size_t bytes = align_ws(nullptr, C, levels, dims, model, photo, robust).bytes;
+    const size_t bytes = align_ws(nullptr, C, dims, cfg).bytes;
     if ((rc = call.alloc(&d_a, (size_t)(C + (seq ? 1 : 0)) * plane)) || (rc = call.alloc(&d_b, (size_t)C * plane, !seq)) ||
-        (rc = call.upload(&d_min, model_in, nc * nS)) || (status_in && (rc = call.upload(&d_sin, status_in, nS))) ||
+        (rc = call.upload(&d_min, io.model_in, nc * nS)) || (io.status_in && (rc = call.upload(&d_sin, io.status_in, nS))) ||
         (rc = call.alloc(&d_mout, nc * nS)) || (rc = call.alloc(&d_sout, nS)) || (rc = call.alloc(&d_stats, ns * nS)) ||
         (rc = call.alloc(&d_ws, bytes)) || (rc = call.alloc(&d_photo, 2 * nS, photo)))
         return rc;
@@ -5134,91 +5166,89 @@ int align_host(const PIX *a, const PIX *b, bool seq, int S, int H, int W, int le
         if ((rc = call.to_device(d_a, a + o, (size_t)(n + (seq ? 1 : 0)) * plane)) ||
             (!seq && (rc = call.to_device(d_b, b + o, (size_t)n * plane))))
             return rc;
-        const AlignWs ws = align_ws(d_ws, n, levels, dims, model, photo, robust);
-        if ((rc = align_dispatch<PIX>(d_a, seq ? d_a + plane : d_b, seq ? n + 1 : 0, n, H, W, levels, dims, iterations, model, min_share,
-                                      d_min + (size_t)nc * s0, d_sin ? d_sin + s0 : nullptr, ws, d_mout + (size_t)nc * s0, d_sout + s0,
-                                      d_stats + ns * (size_t)s0, nullptr, photo ? d_photo + 2 * (size_t)s0 : nullptr, robust_delta)) ||
+        const AlignIo d_io{d_min + (size_t)nc * s0, d_sin ? d_sin + s0 : nullptr, d_mout + (size_t)nc * s0,
+                           d_sout + s0,             d_stats + ns * (size_t)s0,    photo ? d_photo + 2 * (size_t)s0 : nullptr};
+        const AlignWs ws = align_ws(d_ws, n, dims, cfg);
+        if ((rc = align_dispatch<PIX>(d_a, seq ? d_a + plane : d_b, seq ? n + 1 : 0, n, H, W, dims, cfg, d_io, ws, nullptr)) ||
             (rc = call.sync()))
             return rc;
     }
-    if ((rc = call.to_host(model_out, d_mout, nc * nS)) || (rc = call.to_host(status_out, d_sout, nS)) ||
-        (rc = call.to_host(stats, d_stats, ns * nS)) || (photo && (rc = call.to_host(photo_out, d_photo, 2 * nS))))
+    if ((rc = call.to_host(io.model_out, d_mout, nc * nS)) || (rc = call.to_host(io.status_out, d_sout, nS)) ||
+        (rc = call.to_host(io.stats, d_stats, ns * nS)) || (photo && (rc = call.to_host(io.photo_out, d_photo, 2 * nS))))
         return rc;
     return call.sync();
+}
+
+// the three workspace calls
+int align_workspace(int S, int H, int W, int levels, int model, bool photo, bool robust, size_t *bytes)
+{
+    if (!bytes) return fail(OFLK_ERR_INVALID, "bytes is NULL");
+    *bytes = 0;
+    int dims[2 * OFLK_MAX_LEVELS];
+    AlignConfig cfg{levels, 1, model, 1.0f, photo, robust, 1.0f};   // iterations, min_share, robust_delta: values that pass
+    AlignIo none{};
+    if (int rc = check_align(S, H, W, cfg, none, dims)) return rc;
+    *bytes = align_ws(nullptr, S, dims, cfg).bytes;
+    return OFLK_OK;
 }
 }  // namespace
 
 OFLK_API int oflk_align_workspace(int S, int H, int W, int levels, int model, size_t *bytes)
 {
-    if (!bytes) return fail(OFLK_ERR_INVALID, "bytes is NULL");
-    *bytes = 0;
-    int dims[2 * OFLK_MAX_LEVELS];
-    if (int rc = check_align(S, H, W, levels, 1, model, 1.0f, dims)) return rc;
-    *bytes = align_ws(nullptr, S, levels, dims, model).bytes;
-    return OFLK_OK;
+    return align_workspace(S, H, W, levels, model, false, false, bytes);
 }
 
 OFLK_API int oflk_align_refine(const void *d_a, const void *d_b, int u8, int S, int H, int W, int levels, int iterations, int model,
                                float min_share, const float *d_model_in, const int *d_status_in, void *d_workspace,
                                size_t workspace_bytes, float *d_model_out, int *d_status_out, double *d_stats, void *stream)
 {
-    return align_device(d_a, d_b, u8, 0, S, H, W, levels, iterations, model, min_share, d_model_in, d_status_in, d_workspace,
-                        workspace_bytes, d_model_out, d_status_out, d_stats, (hipStream_t)stream);
+    return align_device(d_a, d_b, u8, false, S, H, W, {levels, iterations, model, min_share, false, false, 0.0f},
+                        {d_model_in, d_status_in, d_model_out, d_status_out, d_stats, nullptr}, d_workspace, workspace_bytes, stream);
 }
 
 OFLK_API int oflk_align_sequence(const void *d_frames, int u8, int T, int H, int W, int levels, int iterations, int model,
                                  float min_share, const float *d_model_in, const int *d_status_in, void *d_workspace,
                                  size_t workspace_bytes, float *d_model_out, int *d_status_out, double *d_stats, void *stream)
 {
-    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
-    const void *d_b = d_frames && H > 0 && W > 0 ? static_cast<const char *>(d_frames) + (size_t)H * (size_t)W * (u8 ? 1 : sizeof(float))
-                                                 : d_frames;
-    return align_device(d_frames, d_b, u8, T, T - 1, H, W, levels, iterations, model, min_share, d_model_in, d_status_in, d_workspace,
-                        workspace_bytes, d_model_out, d_status_out, d_stats, (hipStream_t)stream);
+    return align_device(d_frames, nullptr, u8, true, T, H, W, {levels, iterations, model, min_share, false, false, 0.0f},
+                        {d_model_in, d_status_in, d_model_out, d_status_out, d_stats, nullptr}, d_workspace, workspace_bytes, stream);
 }
 
 OFLK_API int oflk_align_refine_host(const float *a, const float *b, int S, int H, int W, int levels, int iterations, int model,
                                     float min_share, const float *model_in, const int *status_in, float *model_out,
                                     int *status_out, double *stats)
 {
-    return align_host<float>(a, b, false, S, H, W, levels, iterations, model, min_share, model_in, status_in, model_out, status_out,
-                             stats);
+    return align_host<float>(a, b, false, S, H, W, {levels, iterations, model, min_share, false, false, 0.0f},
+                             {model_in, status_in, model_out, status_out, stats, nullptr});
 }
 
 OFLK_API int oflk_align_refine_host_u8(const unsigned char *a, const unsigned char *b, int S, int H, int W, int levels,
                                        int iterations, int model, float min_share, const float *model_in, const int *status_in,
                                        float *model_out, int *status_out, double *stats)
 {
-    return align_host<unsigned char>(a, b, false, S, H, W, levels, iterations, model, min_share, model_in, status_in, model_out,
-                                     status_out, stats);
+    return align_host<unsigned char>(a, b, false, S, H, W, {levels, iterations, model, min_share, false, false, 0.0f},
+                                     {model_in, status_in, model_out, status_out, stats, nullptr});
 }
 
 OFLK_API int oflk_align_sequence_host(const float *frames, int T, int H, int W, int levels, int iterations, int model,
                                       float min_share, const float *model_in, const int *status_in, float *model_out,
                                       int *status_out, double *stats)
 {
-    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
-    return align_host<float>(frames, nullptr, true, T - 1, H, W, levels, iterations, model, min_share, model_in, status_in, model_out,
-                             status_out, stats);
+    return align_host<float>(frames, nullptr, true, T, H, W, {levels, iterations, model, min_share, false, false, 0.0f},
+                             {model_in, status_in, model_out, status_out, stats, nullptr});
 }
 
 OFLK_API int oflk_align_sequence_host_u8(const unsigned char *frames, int T, int H, int W, int levels, int iterations, int model,
                                          float min_share, const float *model_in, const int *status_in, float *model_out,
                                          int *status_out, double *stats)
 {
-    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
-    return align_host<unsigned char>(frames, nullptr, true, T - 1, H, W, levels, iterations, model, min_share, model_in, status_in,
-                                     model_out, status_out, stats);
+    return align_host<unsigned char>(frames, nullptr, true, T, H, W, {levels, iterations, model, min_share, false, false, 0.0f},
+                                     {model_in, status_in, model_out, status_out, stats, nullptr});
 }
 
 OFLK_API int oflk_align_photo_workspace(int S, int H, int W, int levels, int model, size_t *bytes)
 {
-    if (!bytes) return fail(OFLK_ERR_INVALID, "bytes is NULL");
-    *bytes = 0;
-    int dims[2 * OFLK_MAX_LEVELS];
-    if (int rc = check_align(S, H, W, levels, 1, model, 1.0f, dims)) return rc;
-    *bytes = align_ws(nullptr, S, levels, dims, model, true).bytes;
-    return OFLK_OK;
+    return align_workspace(S, H, W, levels, model, true, false, bytes);
 }
 
 OFLK_API int oflk_align_refine_photo(const void *d_a, const void *d_b, int u8, int S, int H, int W, int levels, int iterations,
@@ -5226,8 +5256,8 @@ OFLK_API int oflk_align_refine_photo(const void *d_a, const void *d_b, int u8, i
                                      size_t workspace_bytes, float *d_model_out, int *d_status_out, double *d_stats,
                                      float *d_photo_out, void *stream)
 {
-    return align_device(d_a, d_b, u8, 0, S, H, W, levels, iterations, model, min_share, d_model_in, d_status_in, d_workspace,
-                        workspace_bytes, d_model_out, d_status_out, d_stats, (hipStream_t)stream, true, d_photo_out);
+    return align_device(d_a, d_b, u8, false, S, H, W, {levels, iterations, model, min_share, true, false, 0.0f},
+                        {d_model_in, d_status_in, d_model_out, d_status_out, d_stats, d_photo_out}, d_workspace, workspace_bytes, stream);
 }
 
 OFLK_API int oflk_align_sequence_photo(const void *d_frames, int u8, int T, int H, int W, int levels, int iterations, int model,
@@ -5235,56 +5265,46 @@ OFLK_API int oflk_align_sequence_photo(const void *d_frames, int u8, int T, int 
                                        size_t workspace_bytes, float *d_model_out, int *d_status_out, double *d_stats,
                                        float *d_photo_out, void *stream)
 {
-    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
-    const void *d_b = d_frames && H > 0 && W > 0 ? static_cast<const char *>(d_frames) + (size_t)H * (size_t)W * (u8 ? 1 : sizeof(float))
-                                                 : d_frames;
-    return align_device(d_frames, d_b, u8, T, T - 1, H, W, levels, iterations, model, min_share, d_model_in, d_status_in, d_workspace,
-                        workspace_bytes, d_model_out, d_status_out, d_stats, (hipStream_t)stream, true, d_photo_out);
+    return align_device(d_frames, nullptr, u8, true, T, H, W, {levels, iterations, model, min_share, true, false, 0.0f},
+                        {d_model_in, d_status_in, d_model_out, d_status_out, d_stats, d_photo_out}, d_workspace, workspace_bytes, stream);
 }
 
 OFLK_API int oflk_align_refine_photo_host(const float *a, const float *b, int S, int H, int W, int levels, int iterations, int model,
                                           float min_share, const float *model_in, const int *status_in, float *model_out,
                                           int *status_out, double *stats, float *photo_out)
 {
-    return align_host<float>(a, b, false, S, H, W, levels, iterations, model, min_share, model_in, status_in, model_out, status_out,
-                             stats, true, photo_out);
+    return align_host<float>(a, b, false, S, H, W, {levels, iterations, model, min_share, true, false, 0.0f},
+                             {model_in, status_in, model_out, status_out, stats, photo_out});
 }
 
 OFLK_API int oflk_align_refine_photo_host_u8(const unsigned char *a, const unsigned char *b, int S, int H, int W, int levels,
                                              int iterations, int model, float min_share, const float *model_in, const int *status_in,
                                              float *model_out, int *status_out, double *stats, float *photo_out)
 {
-    return align_host<unsigned char>(a, b, false, S, H, W, levels, iterations, model, min_share, model_in, status_in, model_out,
-                                     status_out, stats, true, photo_out);
+    return align_host<unsigned char>(a, b, false, S, H, W, {levels, iterations, model, min_share, true, false, 0.0f},
+                                     {model_in, status_in, model_out, status_out, stats, photo_out});
 }
 
 OFLK_API int oflk_align_sequence_photo_host(const float *frames, int T, int H, int W, int levels, int iterations, int model,
                                             float min_share, const float *model_in, const int *status_in, float *model_out,
                                             int *status_out, double *stats, float *photo_out)
 {
-    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
-    return align_host<float>(frames, nullptr, true, T - 1, H, W, levels, iterations, model, min_share, model_in, status_in, model_out,
-                             status_out, stats, true, photo_out);
+    return align_host<float>(frames, nullptr, true, T, H, W, {levels, iterations, model, min_share, true, false, 0.0f},
+                             {model_in, status_in, model_out, status_out, stats, photo_out});
 }
 
 OFLK_API int oflk_align_sequence_photo_host_u8(const unsigned char *frames, int T, int H, int W, int levels, int iterations,
                                                int model, float min_share, const float *model_in, const int *status_in,
                                                float *model_out, int *status_out, double *stats, float *photo_out)
 {
-    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
-    return align_host<unsigned char>(frames, nullptr, true, T - 1, H, W, levels, iterations, model, min_share, model_in, status_in,
-                                     model_out, status_out, stats, true, photo_out);
+    return align_host<unsigned char>(frames, nullptr, true, T, H, W, {levels, iterations, model, min_share, true, false, 0.0f},
+                                     {model_in, status_in, model_out, status_out, stats, photo_out});
 }
 
 // ---- the robust forms ----
 OFLK_API int oflk_align_robust_workspace(int S, int H, int W, int levels, int model, int photometric, size_t *bytes)
 {
-    if (!bytes) return fail(OFLK_ERR_INVALID, "bytes is NULL");
-    *bytes = 0;
-    int dims[2 * OFLK_MAX_LEVELS];
-    if (int rc = check_align(S, H, W, levels, 1, model, 1.0f, dims)) return rc;
-    *bytes = align_ws(nullptr, S, levels, dims, model, photometric != 0, true).bytes;
-    return OFLK_OK;
+    return align_workspace(S, H, W, levels, model, photometric != 0, true, bytes);
 }
 
 OFLK_API int oflk_align_refine_robust(const void *d_a, const void *d_b, int u8, int S, int H, int W, int levels, int iterations,
@@ -5292,9 +5312,8 @@ OFLK_API int oflk_align_refine_robust(const void *d_a, const void *d_b, int u8, 
                                       const int *d_status_in, void *d_workspace, size_t workspace_bytes, float *d_model_out,
                                       int *d_status_out, double *d_stats, float *d_photo_out, void *stream)
 {
-    return align_device(d_a, d_b, u8, 0, S, H, W, levels, iterations, model, min_share, d_model_in, d_status_in, d_workspace,
-                        workspace_bytes, d_model_out, d_status_out, d_stats, (hipStream_t)stream, photometric != 0, d_photo_out, true,
-                        robust_delta);
+    return align_device(d_a, d_b, u8, false, S, H, W, {levels, iterations, model, min_share, photometric != 0, true, robust_delta},
+                        {d_model_in, d_status_in, d_model_out, d_status_out, d_stats, d_photo_out}, d_workspace, workspace_bytes, stream);
 }
 
 OFLK_API int oflk_align_sequence_robust(const void *d_frames, int u8, int T, int H, int W, int levels, int iterations, int model,
@@ -5302,20 +5321,16 @@ OFLK_API int oflk_align_sequence_robust(const void *d_frames, int u8, int T, int
                                         const int *d_status_in, void *d_workspace, size_t workspace_bytes, float *d_model_out,
                                         int *d_status_out, double *d_stats, float *d_photo_out, void *stream)
 {
-    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
-    const void *d_b = d_frames && H > 0 && W > 0 ? static_cast<const char *>(d_frames) + (size_t)H * (size_t)W * (u8 ? 1 : sizeof(float))
-                                                 : d_frames;
-    return align_device(d_frames, d_b, u8, T, T - 1, H, W, levels, iterations, model, min_share, d_model_in, d_status_in, d_workspace,
-                        workspace_bytes, d_model_out, d_status_out, d_stats, (hipStream_t)stream, photometric != 0, d_photo_out, true,
-                        robust_delta);
+    return align_device(d_frames, nullptr, u8, true, T, H, W, {levels, iterations, model, min_share, photometric != 0, true, robust_delta},
+                        {d_model_in, d_status_in, d_model_out, d_status_out, d_stats, d_photo_out}, d_workspace, workspace_bytes, stream);
 }
 
 OFLK_API int oflk_align_refine_robust_host(const float *a, const float *b, int S, int H, int W, int levels, int iterations, int model,
                                            float min_share, float robust_delta, int photometric, const float *model_in,
                                            const int *status_in, float *model_out, int *status_out, double *stats, float *photo_out)
 {
-    return align_host<float>(a, b, false, S, H, W, levels, iterations, model, min_share, model_in, status_in, model_out, status_out,
-                             stats, photometric != 0, photo_out, true, robust_delta);
+    return align_host<float>(a, b, false, S, H, W, {levels, iterations, model, min_share, photometric != 0, true, robust_delta},
+                             {model_in, status_in, model_out, status_out, stats, photo_out});
 }
 
 OFLK_API int oflk_align_refine_robust_host_u8(const unsigned char *a, const unsigned char *b, int S, int H, int W, int levels,
@@ -5323,17 +5338,16 @@ OFLK_API int oflk_align_refine_robust_host_u8(const unsigned char *a, const unsi
                                               const float *model_in, const int *status_in, float *model_out, int *status_out,
                                               double *stats, float *photo_out)
 {
-    return align_host<unsigned char>(a, b, false, S, H, W, levels, iterations, model, min_share, model_in, status_in, model_out,
-                                     status_out, stats, photometric != 0, photo_out, true, robust_delta);
+    return align_host<unsigned char>(a, b, false, S, H, W, {levels, iterations, model, min_share, photometric != 0, true, robust_delta},
+                                     {model_in, status_in, model_out, status_out, stats, photo_out});
 }
 
 OFLK_API int oflk_align_sequence_robust_host(const float *frames, int T, int H, int W, int levels, int iterations, int model,
                                              float min_share, float robust_delta, int photometric, const float *model_in,
                                              const int *status_in, float *model_out, int *status_out, double *stats, float *photo_out)
 {
-    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
-    return align_host<float>(frames, nullptr, true, T - 1, H, W, levels, iterations, model, min_share, model_in, status_in, model_out,
-                             status_out, stats, photometric != 0, photo_out, true, robust_delta);
+    return align_host<float>(frames, nullptr, true, T, H, W, {levels, iterations, model, min_share, photometric != 0, true, robust_delta},
+                             {model_in, status_in, model_out, status_out, stats, photo_out});
 }
 
 OFLK_API int oflk_align_sequence_robust_host_u8(const unsigned char *frames, int T, int H, int W, int levels, int iterations,
@@ -5341,9 +5355,8 @@ OFLK_API int oflk_align_sequence_robust_host_u8(const unsigned char *frames, int
                                                 const float *model_in, const int *status_in, float *model_out, int *status_out,
                                                 double *stats, float *photo_out)
 {
-    if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
-    return align_host<unsigned char>(frames, nullptr, true, T - 1, H, W, levels, iterations, model, min_share, model_in, status_in,
-                                     model_out, status_out, stats, photometric != 0, photo_out, true, robust_delta);
+    return align_host<unsigned char>(frames, nullptr, true, T, H, W, {levels, iterations, model, min_share, photometric != 0, true, robust_delta},
+                                     {model_in, status_in, model_out, status_out, stats, photo_out});
 }
 
 // ---- the weight map ----
@@ -5351,12 +5364,7 @@ namespace {
 // the refusals of the weight map's configuration, before any device call
 int check_align_weights(int S, int H, int W, int model, float robust_delta)
 {
-    if (S < 1) return fail(OFLK_ERR_INVALID, "S must be >= 1 (got %d)", S);
-    if (H < 1 || W < 1) return fail(OFLK_ERR_INVALID, "H and W must be >= 1 (got %d x %d)", H, W);
-    if ((size_t)H * (size_t)W >= ((size_t)1 << 30)) return fail(OFLK_ERR_UNSUPPORTED, "frames of 2^30 pixels or more are not supported");
-    if (H >= kMaxDim || W >= kMaxDim)
-        return fail(OFLK_ERR_UNSUPPORTED, "frames of 2^23 rows or columns or more are not supported (got %d x %d)", H, W);
-    if (model != OFLK_ALIGN_AFFINE && model != OFLK_ALIGN_HOMOGRAPHY) return fail(OFLK_ERR_INVALID, "unknown model %d", model);
+    if (int rc = check_align_shape(S, H, W, model)) return rc;
     return check_robust_delta(robust_delta);
 }
 
@@ -5445,9 +5453,9 @@ OFLK_API int oflk_align_weights_host_u8(const unsigned char *a, const unsigned c
 // allocates everything (ensure_state), and no later push allocates.  Frame t lives in ring slot t & 1, and so do its
 // pyramid levels and its row.
 struct oflk_tracker {
-    int device = 0, H = 0, W = 0, L = 0, win = 0, hw = 0, iters = 0, K = 0, every = 0;
+    int device = 0, H = 0, W = 0;
     bool u8 = false;
-    float alpha = 0, beta = 0, max_residual = 0, q = 0, md = 0;
+    KltConfig klt{};   // the configuration, as oflk_tracker_create took it: klt.select.K slots; klt.select.every = 0: never detect
     int dims[2 * OFLK_MAX_LEVELS] = {0};
     GaussW gauss;
     long long t = -1;                 // index of the last pushed frame
@@ -5464,11 +5472,9 @@ struct oflk_tracker {
     float *residual = nullptr;        // [K]
     int *detected = nullptr;          // [1]
     char *feat = nullptr;             // the oflk_replenish_features workspace of one frame
-    // the motion row (oflk_tracker_set_motion): off while m_model < 0; the buffers come with the first push that needs them
-    int m_model = -1, m_hyps = 0;
-    float m_thr = 0;
-    unsigned m_seed = 0;
-    long long m_t = -2;               // the frame whose motion row the buffers hold
+    // the motion row (oflk_tracker_set_motion): off while fit.model < 0; the buffers come with the first push that needs them
+    FitConfig fit{-1, 0, 0.0f, 0u};
+    long long m_t = -2;              // the frame whose motion row the buffers hold
     float *m_out = nullptr;           // [6]
     unsigned char *m_inlier = nullptr;   // [K]
     int *m_counts = nullptr;          // [3]
@@ -5478,8 +5484,9 @@ struct oflk_tracker {
 
     size_t npix(int l) const { return (size_t)dims[2 * l] * (size_t)dims[2 * l + 1]; }
     size_t pix_bytes() const { return u8 ? 1 : sizeof(float); }
-    float *row_xy(long long f) const { return xy + (size_t)(f & 1) * 2 * (size_t)K; }
-    unsigned char *row_vis(long long f) const { return vis + (size_t)(f & 1) * (size_t)K; }
+    int K() const { return klt.select.K; }
+    float *row_xy(long long f) const { return xy + (size_t)(f & 1) * 2 * (size_t)K(); }
+    unsigned char *row_vis(long long f) const { return vis + (size_t)(f & 1) * (size_t)K(); }
     char *frame(long long f) const { return static_cast<char *>(ring) + (size_t)(f & 1) * (size_t)H * W * pix_bytes(); }
 };
 
@@ -5503,17 +5510,17 @@ int tracker_ensure_state(oflk_tracker *tr)
     int rc = ensure_device(tr->device);
     if (rc || tr->ready) return rc;
     if (tr->ws_bytes) return fail(OFLK_ERR_NOMEM, "the tracker's state could not be allocated by an earlier push");
-    const size_t plane = (size_t)tr->H * tr->W, row = (size_t)tr->K;
+    const size_t plane = (size_t)tr->H * tr->W, row = (size_t)tr->K();
     unsigned char *ring = nullptr;
     if ((rc = dmalloc(&ring, 2 * plane * tr->pix_bytes(), &tr->ws_bytes))) return rc;
     tr->ring = ring;
-    for (int l = 0; l < tr->L - 1; l++)
+    for (int l = 0; l < tr->klt.pyr.levels - 1; l++)
         if ((rc = dmalloc(&tr->pyr[l], 2 * tr->npix(l), &tr->ws_bytes))) return rc;
     if ((rc = dmalloc(&tr->xy, 2 * 2 * row, &tr->ws_bytes)) || (rc = dmalloc(&tr->vis, 2 * row, &tr->ws_bytes)) ||
         (rc = dmalloc(&tr->qt, row, &tr->ws_bytes)) || (rc = dmalloc(&tr->qxy, 2 * row, &tr->ws_bytes)) ||
         (rc = dmalloc(&tr->pts, 2 * row, &tr->ws_bytes)) || (rc = dmalloc(&tr->born, row, &tr->ws_bytes)) ||
         (rc = dmalloc(&tr->residual, row, &tr->ws_bytes)) || (rc = dmalloc(&tr->detected, 1, &tr->ws_bytes)) ||
-        (rc = dmalloc(&tr->feat, feat_ws(nullptr, 1, tr->H, tr->W, tr->md, tr->K).bytes, &tr->ws_bytes)))
+        (rc = dmalloc(&tr->feat, feat_ws(nullptr, 1, tr->H, tr->W, tr->klt.select.md, tr->K()).bytes, &tr->ws_bytes)))
         return rc;
     tr->ready = true;
     return OFLK_OK;
@@ -5523,10 +5530,10 @@ int tracker_ensure_state(oflk_tracker *tr)
 int tracker_ensure_motion(oflk_tracker *tr)
 {
     int rc = OFLK_OK;
-    if (!tr->m_out && ((rc = dmalloc(&tr->m_out, 6, &tr->ws_bytes)) || (rc = dmalloc(&tr->m_inlier, (size_t)tr->K, &tr->ws_bytes)) ||
+    if (!tr->m_out && ((rc = dmalloc(&tr->m_out, 6, &tr->ws_bytes)) || (rc = dmalloc(&tr->m_inlier, (size_t)tr->K(), &tr->ws_bytes)) ||
                        (rc = dmalloc(&tr->m_counts, 3, &tr->ws_bytes))))
         return rc;
-    if (tr->m_ws_hyps >= tr->m_hyps) return OFLK_OK;
+    if (tr->m_ws_hyps >= tr->fit.hypotheses) return OFLK_OK;
     if (tr->m_ws) {
         HIP_TRY(hipFree(tr->m_ws));   // waits for the work that uses it
         tr->m_ws = nullptr;
@@ -5534,9 +5541,9 @@ int tracker_ensure_motion(oflk_tracker *tr)
         tr->m_ws_hyps = 0;
     }
     const size_t before = tr->ws_bytes;
-    if ((rc = dmalloc(&tr->m_ws, motion_ws(nullptr, 1, tr->K, tr->m_hyps).bytes, &tr->ws_bytes))) return rc;
+    if ((rc = dmalloc(&tr->m_ws, motion_ws(nullptr, 1, tr->K(), tr->fit.hypotheses).bytes, &tr->ws_bytes))) return rc;
     tr->m_ws_bytes = tr->ws_bytes - before;
-    tr->m_ws_hyps = tr->m_hyps;
+    tr->m_ws_hyps = tr->fit.hypotheses;
     return OFLK_OK;
 }
 
@@ -5545,9 +5552,9 @@ SparseArgs tracker_args(const oflk_tracker *tr)
 {
     SparseArgs a{};
     a.frames = tr->ring;
-    a.L = tr->L; a.K = tr->iters; a.B = 1; a.H = tr->H; a.W = tr->W; a.N = tr->K;
-    sparse_levels(&a, tr->L, tr->pyr, tr->dims);
-    a.alpha = tr->alpha; a.beta = tr->beta; a.max_residual = tr->max_residual;
+    a.L = tr->klt.pyr.levels; a.K = tr->klt.pyr.iters; a.B = 1; a.H = tr->H; a.W = tr->W; a.N = tr->K();
+    sparse_levels(&a, tr->klt.pyr.levels, tr->pyr, tr->dims);
+    a.alpha = tr->klt.test.alpha; a.beta = tr->klt.test.beta; a.max_residual = tr->klt.test.max_residual;
     return a;
 }
 
@@ -5559,8 +5566,8 @@ int tracker_newborn(const oflk_tracker *tr, long long t, const float *qxy, const
     b.born = tr->born; b.qt = tr->qt;
     b.qxy = reinterpret_cast<const float2 *>(qxy);
     b.free = free; b.nfree = nfree;
-    b.n = n; b.K = tr->K; b.t = (int)t;
-    const int threads = free ? std::min(n, tr->K) : tr->K;
+    b.n = n; b.K = tr->K(); b.t = (int)t;
+    const int threads = free ? std::min(n, tr->K()) : tr->K();
     hipLaunchKernelGGL(k_tracker_newborn, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, b);
     HIP_TRY(hipGetLastError());
     return OFLK_OK;
@@ -5579,18 +5586,12 @@ int tracker_enqueue(oflk_tracker *tr, const void *src, hipMemcpyKind kind, hipSt
     const size_t plane = (size_t)tr->H * tr->W;
     char *frame = tr->frame(t);
     HIP_TRY(hipMemcpyAsync(frame, src, plane * tr->pix_bytes(), kind, s));
-    if (tr->L > 1) {
-        const float *in = reinterpret_cast<const float *>(frame);
-        PyrExtra first;
-        first.u8 = tr->u8;
-        for (int l = tr->L - 2; l >= 0; l--) {   // every step is the fused kernel's (oflk_tracker_create), so no temporaries
-            float *out = tr->pyr[l] + (size_t)c * tr->npix(l);
-            if ((rc = launch_pyr_down(nullptr, tr->gauss, s, in, out, nullptr, nullptr, 1, tr->dims[2 * (l + 1)], tr->dims[2 * (l + 1) + 1],
-                                      tr->dims[2 * l], tr->dims[2 * l + 1], l == tr->L - 2 ? &first : nullptr)))
-                return rc;
-            in = out;
-        }
-    }
+    PyrExtra first;
+    first.u8 = tr->u8;
+    // every step is the fused kernel's (oflk_tracker_create), so no temporaries
+    if ((rc = pyr_chain(nullptr, tr->gauss, s, reinterpret_cast<const float *>(frame), tr->pyr, (size_t)c, nullptr, nullptr, 1, tr->dims,
+                        tr->klt.pyr.levels, first)))
+        return rc;
     const SparseArgs a = tracker_args(tr);
     PushArgs r{};
     if (t > 0) {
@@ -5600,28 +5601,30 @@ int tracker_enqueue(oflk_tracker *tr, const void *src, hipMemcpyKind kind, hipSt
     r.xy_out = tr->row_xy(t); r.vis_out = tr->row_vis(t);
     r.residual = tr->residual; r.born = tr->born; r.detected = tr->detected;
     r.ib = c;
-    const bool built = with_half_window(tr->hw, [&](auto HW) {
+    const int hw = tr->klt.pyr.window_size / 2, K = tr->K();
+    const bool built = with_half_window(hw, [&](auto HW) {
         with_pix(tr->u8, [&](auto PIX) {
-            hipLaunchKernelGGL((k_sparse_push<decltype(HW)::value, typename decltype(PIX)::type>), dim3((unsigned)tr->K), dim3(64), 0, s, a, r);
+            hipLaunchKernelGGL((k_sparse_push<decltype(HW)::value, typename decltype(PIX)::type>), dim3((unsigned)K), dim3(64), 0, s, a, r);
         });
     });
-    if (!built) return fail(OFLK_ERR_UNSUPPORTED, "half window %d not built", tr->hw);
+    if (!built) return fail(OFLK_ERR_UNSUPPORTED, "half window %d not built", hw);
     HIP_TRY(hipGetLastError());
-    if (tr->every > 0 && t % tr->every == 0) {
+    const Selection &sel = tr->klt.select;
+    if (sel.every > 0 && t % sel.every == 0) {
         const SlotSide slots{tr->row_xy(t), tr->row_vis(t), tr->qt, tr->born, tr->detected, (int)t};
-        if ((rc = detect_launch(frame, tr->u8, 1, tr->H, tr->W, tr->win, tr->q, tr->md, tr->K,
-                                feat_ws(tr->feat, 1, tr->H, tr->W, tr->md, tr->K), nullptr, tr->qxy, nullptr, &slots, s)) ||
+        if ((rc = detect_launch(frame, tr->u8, 1, tr->H, tr->W, tr->klt.pyr.window_size, sel.q, sel.md, K,
+                                feat_ws(tr->feat, 1, tr->H, tr->W, sel.md, K), nullptr, tr->qxy, nullptr, &slots, s)) ||
             (rc = tracker_newborn(tr, t, tr->qxy, nullptr, nullptr, 0, s)))
             return rc;
     }
-    if (tr->m_model >= 0) {   // the motion row: step t-1 -> t on the two rows and this frame's born
+    if (tr->fit.model >= 0) {   // the motion row: step t-1 -> t on the two rows and this frame's born
         if (t == 0) {
-            hipLaunchKernelGGL(k_motion_none, dim3((unsigned)((std::max(tr->K, 6) + 255) / 256)), dim3(256), 0, s, tr->m_out,
-                               tr->m_inlier, tr->m_counts, tr->K);
+            hipLaunchKernelGGL(k_motion_none, dim3((unsigned)((std::max(K, 6) + 255) / 256)), dim3(256), 0, s, tr->m_out, tr->m_inlier,
+                               tr->m_counts, K);
             HIP_TRY(hipGetLastError());
-        } else if ((rc = motion_launch({tr->row_xy(t - 1), tr->row_xy(t), tr->row_vis(t - 1), tr->row_vis(t), tr->born}, 1, tr->K,
-                                       (unsigned)(t - 1), tr->m_model, tr->m_hyps, tr->m_thr, tr->m_seed,
-                                       motion_ws(tr->m_ws, 1, tr->K, tr->m_hyps), tr->m_out, tr->m_inlier, tr->m_counts, s))) {
+        } else if ((rc = motion_launch({tr->row_xy(t - 1), tr->row_xy(t), tr->row_vis(t - 1), tr->row_vis(t), tr->born}, 1, K,
+                                       (unsigned)(t - 1), tr->fit.model, tr->fit.hypotheses, tr->fit.threshold, tr->fit.seed,
+                                       motion_ws(tr->m_ws, 1, K, tr->fit.hypotheses), tr->m_out, tr->m_inlier, tr->m_counts, s))) {
             return rc;
         }
         tr->m_t = t;
@@ -5637,7 +5640,7 @@ int tracker_push(oflk_tracker *tr, const void *src, hipMemcpyKind kind, hipStrea
     if (tr->t >= (long long)INT_MAX - 1)
         return fail(OFLK_ERR_UNSUPPORTED, "frame index %lld is the last one a tracker takes (reset it)", tr->t);
     int rc = tracker_ensure_state(tr);   // a refusal here has written nothing
-    if (rc || (tr->m_model >= 0 && (rc = tracker_ensure_motion(tr)))) return rc;
+    if (rc || (tr->fit.model >= 0 && (rc = tracker_ensure_motion(tr)))) return rc;
     if ((rc = tracker_enqueue(tr, src, kind, s))) tr->failed = true;
     return rc;
 }
@@ -5648,7 +5651,7 @@ std::vector<float> tracker_filter_points(const oflk_tracker *tr, const float *pt
 {
     std::vector<float> keep;
     const float xmax = (float)(tr->W - 1), ymax = (float)(tr->H - 1);
-    for (int i = 0; i < n && keep.size() < 2 * (size_t)tr->K; i++) {
+    for (int i = 0; i < n && keep.size() < 2 * (size_t)tr->K(); i++) {
         const float x = pts[2 * (size_t)i], y = pts[2 * (size_t)i + 1];
         if (x >= 0.0f && x <= xmax && y >= 0.0f && y <= ymax) {
             keep.push_back(x);
@@ -5664,40 +5667,38 @@ int tracker_pushed(const oflk_tracker *tr)
     if (tr->t < 0) return fail(OFLK_ERR_INVALID, "no frame has been pushed yet");
     return OFLK_OK;
 }
+// oflk_tracker_create behind its flat list; the online stabiliser's creation makes its tracker here too
+int tracker_create(oflk_tracker **out, int device, int H, int W, bool u8, const KltConfig &klt)
+{
+    if (!out) return fail(OFLK_ERR_INVALID, "tracker pointer is NULL");
+    *out = nullptr;
+    if (H < 1 || W < 1) return fail(OFLK_ERR_INVALID, "H and W must be >= 1 (got %d x %d)", H, W);
+    int rc = check_frame_bounds(H, W);   // oflk_plan_create's, which the sequence call meets there
+    if (rc || (rc = check_sparse_test(klt.test)) || (rc = check_sparse_config(H, W, klt.pyr)) || (rc = check_select(klt.select))) return rc;
+    if (klt.select.every < 0) return fail(OFLK_ERR_INVALID, "detect_every must be >= 0 (0: never detect; got %d)", klt.select.every);
+    if (device < 0 || device >= kMaxDevices) return fail(OFLK_ERR_INVALID, "device %d out of range", device);
+    oflk_tracker *tr = new oflk_tracker();
+    tr->device = device; tr->H = H; tr->W = W; tr->u8 = u8; tr->klt = klt;
+    // At the pyramid's scale of 0.5 every step fits the fused kernel: a finer size is 2m or 2m + 1 for the coarser m, so a 32 x
+    // 16 coarse tile spans at most 66 x 34 source elements.  The tracker therefore holds neither the unfused chain's
+    // temporaries nor a float32 stage for uint8 frames, and pyr_chain_fits cannot refuse at that scale; it is here so that
+    // pyr_chain is never handed NULL temporaries it would use
+    if ((rc = level_dims(H, W, klt.pyr.levels, 0.5, tr->dims)) || (rc = make_gauss(2.0, &tr->gauss)) ||
+        (rc = pyr_chain_fits(tr->dims, klt.pyr.levels, tr->gauss))) {
+        delete tr;
+        return rc;
+    }
+    *out = tr;
+    return OFLK_OK;
+}
 }  // namespace
 
 OFLK_API int oflk_tracker_create(oflk_tracker **out, int device, int H, int W, int u8, int levels, int window_size, int iters,
                                  float alpha, float beta, float max_residual, float quality_level, float min_distance,
                                  int max_corners, int detect_every)
 {
-    if (!out) return fail(OFLK_ERR_INVALID, "tracker pointer is NULL");
-    *out = nullptr;
-    if (H < 1 || W < 1) return fail(OFLK_ERR_INVALID, "H and W must be >= 1 (got %d x %d)", H, W);
-    int rc = check_frame_bounds(H, W);   // oflk_plan_create's, which the sequence call meets there
-    if (rc || (rc = check_sparse_test(alpha, beta, max_residual)) || (rc = check_sparse_config(H, W, levels, window_size, iters)) ||
-        (rc = check_select(quality_level, min_distance, max_corners)))
-        return rc;
-    if (detect_every < 0) return fail(OFLK_ERR_INVALID, "detect_every must be >= 0 (0: never detect; got %d)", detect_every);
-    if (device < 0 || device >= kMaxDevices) return fail(OFLK_ERR_INVALID, "device %d out of range", device);
-    oflk_tracker *tr = new oflk_tracker();
-    tr->device = device; tr->H = H; tr->W = W; tr->L = levels; tr->win = window_size; tr->hw = window_size / 2; tr->iters = iters;
-    tr->K = max_corners; tr->every = detect_every; tr->u8 = u8 != 0;
-    tr->alpha = alpha; tr->beta = beta; tr->max_residual = max_residual; tr->q = quality_level; tr->md = min_distance;
-    if ((rc = level_dims(H, W, levels, 0.5, tr->dims)) || (rc = make_gauss(2.0, &tr->gauss))) {
-        delete tr;
-        return rc;
-    }
-    // At the pyramid's scale of 0.5 every step fits the fused kernel: a finer size is 2m or 2m + 1 for the coarser m, so a 32 x
-    // 16 coarse tile spans at most 66 x 34 source elements.  The tracker therefore holds neither the unfused chain's
-    // temporaries nor a float32 stage for uint8 frames, and this guard cannot fire at that scale; it is here so that
-    // launch_pyr_down below is never handed NULL temporaries it would use
-    for (int l = levels - 2; l >= 0; l--)
-        if (!pyr_fused_fits(tr->dims[2 * (l + 1)], tr->dims[2 * (l + 1) + 1], tr->dims[2 * l], tr->dims[2 * l + 1], tr->gauss)) {
-            delete tr;
-            return fail(OFLK_ERR_UNSUPPORTED, "pyramid level %d of %dx%d does not fit the fused pyramid kernel", l, W, H);
-        }
-    *out = tr;
-    return OFLK_OK;
+    return tracker_create(out, device, H, W, u8 != 0,
+                          {{levels, window_size, iters}, {alpha, beta, max_residual}, {quality_level, min_distance, max_corners, detect_every}});
 }
 
 OFLK_API int oflk_tracker_destroy(oflk_tracker *tr)
@@ -5744,7 +5745,7 @@ OFLK_API int oflk_tracker_read_row(oflk_tracker *tr, float *xy, unsigned char *v
     if (int rc = tracker_pushed(tr)) return rc;
     HIP_TRY(hipSetDevice(tr->device));
     hipStream_t s = (hipStream_t)stream;
-    const size_t row = (size_t)tr->K;
+    const size_t row = (size_t)tr->K();
     if (xy) HIP_TRY(hipMemcpyAsync(xy, tr->row_xy(tr->t), 2 * row * sizeof(float), hipMemcpyDeviceToHost, s));
     if (visible) HIP_TRY(hipMemcpyAsync(visible, tr->row_vis(tr->t), row, hipMemcpyDeviceToHost, s));
     if (born) HIP_TRY(hipMemcpyAsync(born, tr->born, row, hipMemcpyDeviceToHost, s));
@@ -5777,8 +5778,8 @@ OFLK_API int oflk_tracker_add_points(oflk_tracker *tr, const float *pts, int n, 
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemcpyAsync(tr->pts, keep.data(), keep.size() * sizeof(float), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));   // `keep` is this call's
-    const FeatWs ws = feat_ws(tr->feat, 1, tr->H, tr->W, tr->md, tr->K);
-    hipLaunchKernelGGL(k_free_list, dim3(1), dim3(256), 0, s, (const unsigned char *)tr->row_vis(tr->t), tr->K, ws.free, ws.nfree);
+    const FeatWs ws = feat_ws(tr->feat, 1, tr->H, tr->W, tr->klt.select.md, tr->K());
+    hipLaunchKernelGGL(k_free_list, dim3(1), dim3(256), 0, s, (const unsigned char *)tr->row_vis(tr->t), tr->K(), ws.free, ws.nfree);
     HIP_TRY(hipGetLastError());
     return tracker_newborn(tr, tr->t, tr->pts, ws.free, ws.nfree, (int)(keep.size() / 2), s);
 }
@@ -5787,11 +5788,12 @@ OFLK_API int oflk_tracker_set_motion(oflk_tracker *tr, int model, int hypotheses
 {
     if (!tr) return fail(OFLK_ERR_INVALID, "NULL tracker");
     if (model == -1) {
-        tr->m_model = -1;
+        tr->fit.model = -1;
         return OFLK_OK;
     }
-    if (int rc = check_motion(model, hypotheses, threshold)) return rc;
-    tr->m_model = model; tr->m_hyps = hypotheses; tr->m_thr = threshold; tr->m_seed = seed;
+    const FitConfig fit{model, hypotheses, threshold, seed};
+    if (int rc = check_motion(fit)) return rc;
+    tr->fit = fit;
     return OFLK_OK;
 }
 
@@ -5820,7 +5822,7 @@ OFLK_API int oflk_tracker_read_motion(oflk_tracker *tr, float *model, unsigned c
     HIP_TRY(hipSetDevice(tr->device));
     hipStream_t s = (hipStream_t)stream;
     if (model) HIP_TRY(hipMemcpyAsync(model, tr->m_out, 6 * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (inlier) HIP_TRY(hipMemcpyAsync(inlier, tr->m_inlier, (size_t)tr->K, hipMemcpyDeviceToHost, s));
+    if (inlier) HIP_TRY(hipMemcpyAsync(inlier, tr->m_inlier, (size_t)tr->K(), hipMemcpyDeviceToHost, s));
     if (counts) HIP_TRY(hipMemcpyAsync(counts, tr->m_counts, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return OFLK_OK;
@@ -6015,9 +6017,8 @@ OFLK_API int oflk_stabilize_trajectory_ring(const float *d_model_ring, const int
 
 namespace {
 // the creation of every layout: the layout's own refusals, the shape, the byte count of a packed frame, then the tracker's
-int stabilizer_create(oflk_stabilizer **out, int device, int H, int W, const FrameLayout &L, int levels, int window_size, int iters,
-                      float alpha, float beta, float max_residual, float q, float md, int K, int detect_every, int model,
-                      int hypotheses, float threshold, unsigned seed, const double *weights, int radius)
+int stabilizer_create(oflk_stabilizer **out, int device, int H, int W, const FrameLayout &L, const KltConfig &klt, const FitConfig &fit,
+                      const TrajWindow &window)
 {
     if (!out) return fail(OFLK_ERR_INVALID, "stabiliser pointer is NULL");
     *out = nullptr;
@@ -6026,20 +6027,16 @@ int stabilizer_create(oflk_stabilizer **out, int device, int H, int W, const Fra
     if (H < 2 || W < 2) return fail(OFLK_ERR_INVALID, "H and W must be >= 2 (got %d x %d)", H, W);
     if (L.kind == FrameKind::Packed && L.frame_bytes(H, W) >= ((size_t)1 << 31))
         return fail(OFLK_ERR_UNSUPPORTED, "packed frames of 2^31 bytes or more are not supported");
-    if ((rc = check_motion(model, hypotheses, threshold)) || (rc = check_stab_window(weights, radius))) return rc;
+    if ((rc = check_motion(fit)) || (rc = check_stab_window(window))) return rc;
     oflk_tracker *tr = nullptr;
-    if ((rc = oflk_tracker_create(&tr, device, H, W, L.pix_bytes == 1, levels, window_size, iters, alpha, beta, max_residual, q, md, K,
-                                  detect_every)) ||
-        (rc = oflk_tracker_set_motion(tr, model, hypotheses, threshold, seed))) {
-        tracker_free(tr);
-        return rc;
-    }
+    if ((rc = tracker_create(&tr, device, H, W, L.pix_bytes == 1, klt))) return rc;
+    tr->fit = fit;   // checked above, as oflk_tracker_set_motion would
     oflk_stabilizer *st = new oflk_stabilizer();
     st->tr = tr;
     st->layout = L;
-    st->r = radius;
-    st->cap = std::max(2 * radius, 1);
-    for (int i = 0; i <= radius; i++) st->wt.w[i] = weights[i];
+    st->r = window.radius;
+    st->cap = std::max(2 * window.radius, 1);
+    for (int i = 0; i <= window.radius; i++) st->wt.w[i] = window.weights[i];
     *out = st;
     return OFLK_OK;
 }
@@ -6050,8 +6047,9 @@ OFLK_API int oflk_stabilizer_create(oflk_stabilizer **out, int device, int H, in
                                     int max_corners, int detect_every, int model, int hypotheses, float threshold, unsigned seed,
                                     const double *weights, int radius)
 {
-    return stabilizer_create(out, device, H, W, FrameLayout::planar(u8 != 0), levels, window_size, iters, alpha, beta, max_residual,
-                             quality_level, min_distance, max_corners, detect_every, model, hypotheses, threshold, seed, weights, radius);
+    return stabilizer_create(out, device, H, W, FrameLayout::planar(u8 != 0),
+                             {{levels, window_size, iters}, {alpha, beta, max_residual}, {quality_level, min_distance, max_corners, detect_every}},
+                             {model, hypotheses, threshold, seed}, {weights, radius});
 }
 
 OFLK_API int oflk_stabilizer_create_packed(oflk_stabilizer **out, int device, int H, int W, int channels, int order, int levels,
@@ -6059,9 +6057,9 @@ OFLK_API int oflk_stabilizer_create_packed(oflk_stabilizer **out, int device, in
                                            float quality_level, float min_distance, int max_corners, int detect_every, int model,
                                            int hypotheses, float threshold, unsigned seed, const double *weights, int radius)
 {
-    return stabilizer_create(out, device, H, W, FrameLayout::packed(channels, order), levels, window_size, iters, alpha, beta,
-                             max_residual, quality_level, min_distance, max_corners, detect_every, model, hypotheses, threshold, seed,
-                             weights, radius);
+    return stabilizer_create(out, device, H, W, FrameLayout::packed(channels, order),
+                             {{levels, window_size, iters}, {alpha, beta, max_residual}, {quality_level, min_distance, max_corners, detect_every}},
+                             {model, hypotheses, threshold, seed}, {weights, radius});
 }
 
 OFLK_API int oflk_stabilizer_create_nv12(oflk_stabilizer **out, int device, int H, int W, int siting, int levels, int window_size,
@@ -6069,8 +6067,9 @@ OFLK_API int oflk_stabilizer_create_nv12(oflk_stabilizer **out, int device, int 
                                          float min_distance, int max_corners, int detect_every, int model, int hypotheses,
                                          float threshold, unsigned seed, const double *weights, int radius)
 {
-    return stabilizer_create(out, device, H, W, FrameLayout::nv12(siting), levels, window_size, iters, alpha, beta, max_residual,
-                             quality_level, min_distance, max_corners, detect_every, model, hypotheses, threshold, seed, weights, radius);
+    return stabilizer_create(out, device, H, W, FrameLayout::nv12(siting),
+                             {{levels, window_size, iters}, {alpha, beta, max_residual}, {quality_level, min_distance, max_corners, detect_every}},
+                             {model, hypotheses, threshold, seed}, {weights, radius});
 }
 
 OFLK_API int oflk_stabilizer_destroy(oflk_stabilizer *st)

@@ -40,13 +40,15 @@ int main()
         for (int L : {1, 3})
             for (int S : {1, 5}) {
                 int dims[2 * OFLK_MAX_LEVELS];
-                EXPECT(check_align(S, 70, 257, L, 1, model, 0.25f, dims) == OFLK_OK);
+                AlignConfig cfg{L, 1, model, 0.25f, false, false, 0.0f};
+                AlignIo io{};
+                EXPECT(check_align(S, 70, 257, cfg, io, dims) == OFLK_OK);
                 EXPECT(dims[2 * (L - 1)] == 70 && dims[2 * (L - 1) + 1] == 257);
-                const AlignWs ws = align_ws(g_buf, S, L, dims, model);
+                const AlignWs ws = align_ws(g_buf, S, dims, cfg);
                 EXPECT(oflk_align_workspace(S, 70, 257, L, model, &n) == OFLK_OK && n == ws.bytes);
                 // the pieces follow each other on 256-byte boundaries and end inside the size
                 const size_t ns = model == P ? 46 : 29, tiles = 5 * 3;
-                EXPECT(ws.pstride == tiles * ns && align_nsums(model) == (int)ns && align_tiles(70, 257) == (int)tiles);
+                EXPECT(ws.pstride == tiles * ns && align_nsums(model, false, false) == (int)ns && align_tiles(70, 257) == (int)tiles);
                 const char *b = reinterpret_cast<const char *>(g_buf);
                 EXPECT(reinterpret_cast<const char *>(ws.state) == b);
                 EXPECT(reinterpret_cast<const char *>(ws.partial) >= b + S * sizeof(AlignState) && aligned(ws.partial, 256));
@@ -121,13 +123,16 @@ int main()
         EXPECT(oflk_align_workspace(3, 70, 257, 3, model, &plain) == OFLK_OK);
         EXPECT(oflk_align_photo_workspace(3, 70, 257, 3, model, &photo) == OFLK_OK && photo > plain && photo % 256 == 0);
         int dims[2 * OFLK_MAX_LEVELS];
-        EXPECT(check_align(3, 70, 257, 3, 1, model, 0.25f, dims) == OFLK_OK);
+        AlignConfig cfg{3, 1, model, 0.25f, true, false, 0.0f};
+        AlignIo io{};
+        EXPECT(check_align(3, 70, 257, cfg, io, dims) == OFLK_OK);
         char *b = reinterpret_cast<char *>(g_buf);
-        const AlignWs ws = align_ws(b, 3, 3, dims, model, true);
+        const AlignWs ws = align_ws(b, 3, dims, cfg);
         EXPECT(ws.bytes == photo && ws.pstride == 3u * 5u * (size_t)align_sums(model == P ? 10 : 8));
         EXPECT(reinterpret_cast<const char *>(ws.photo) >= reinterpret_cast<const char *>(ws.pyr[1]) && aligned(ws.photo, 256));
         EXPECT(reinterpret_cast<const char *>(ws.photo) + 2 * 3 * sizeof(double) <= b + ws.bytes);
-        EXPECT(align_ws(b, 3, 3, dims, model).photo == nullptr);
+        cfg.photo = false;
+        EXPECT(align_ws(b, 3, dims, cfg).photo == nullptr);
     }
     EXPECT(oflk_align_photo_workspace(2, 32, 40, 2, P, nullptr) == OFLK_ERR_INVALID);
     EXPECT(oflk_align_photo_workspace(2, 32, 40, 2, P, &n) == OFLK_OK);
@@ -156,9 +161,11 @@ int main()
             EXPECT((ph ? oflk_align_photo_workspace(3, 70, 257, 3, model, &base) : oflk_align_workspace(3, 70, 257, 3, model, &base)) == OFLK_OK);
             EXPECT(oflk_align_robust_workspace(3, 70, 257, 3, model, ph, &robust) == OFLK_OK && robust > base && robust % 256 == 0);
             int dims[2 * OFLK_MAX_LEVELS];
-            EXPECT(check_align(3, 70, 257, 3, 1, model, 0.25f, dims) == OFLK_OK);
+            AlignConfig cfg{3, 1, model, 0.25f, ph != 0, true, 4.0f};
+            AlignIo io{};
+            EXPECT(check_align(3, 70, 257, cfg, io, dims) == OFLK_OK);
             char *b = reinterpret_cast<char *>(g_buf);
-            const AlignWs ws = align_ws(b, 3, 3, dims, model, ph != 0, true);
+            const AlignWs ws = align_ws(b, 3, dims, cfg);
             const size_t ns = (size_t)align_sums((model == P ? 8 : 6) + (ph ? 2 : 0)) + 2;
             EXPECT(ws.bytes == robust && ws.pstride == 3u * 5u * ns && align_nsums(model, ph != 0, true) == (int)ns);
             EXPECT(ns == (size_t)(model == P ? (ph ? 69 : 48) : (ph ? 48 : 31)));
@@ -166,7 +173,8 @@ int main()
             EXPECT(reinterpret_cast<const char *>(ws.first) >= reinterpret_cast<const char *>(ws.pyr[1]) && aligned(ws.first, 256));
             EXPECT(!ph || reinterpret_cast<const char *>(ws.first) >= reinterpret_cast<const char *>(ws.photo) + 2 * 3 * sizeof(double));
             EXPECT(reinterpret_cast<const char *>(ws.first) + 2 * 3 * sizeof(double) <= b + ws.bytes);
-            EXPECT(align_ws(b, 3, 3, dims, model, ph != 0).first == nullptr);
+            cfg.robust = false;
+            EXPECT(align_ws(b, 3, dims, cfg).first == nullptr);
         }
     EXPECT(oflk_align_robust_workspace(2, 32, 40, 2, P, 0, nullptr) == OFLK_ERR_INVALID);
     EXPECT(oflk_align_robust_workspace(0, 32, 40, 2, P, 0, &n) == OFLK_ERR_INVALID && n == 0);

@@ -87,11 +87,11 @@ int main()
     oflk_tracker *tr = nullptr;
     EXPECT(oflk_tracker_create(&tr, 0, 24, 32, 1, 3, 5, 3, 0.01f, 0.5f, 4.0f, 0.01f, 3.0f, 8, 2) == OFLK_OK && tr);
     if (tr) {
-        EXPECT(oflk_tracker_set_motion(tr, OFLK_MOTION_AFFINE, 64, 1.5f, 7u) == OFLK_OK && tr->m_model == 2 && tr->m_hyps == 64);
-        EXPECT(oflk_tracker_set_motion(tr, 3, 64, 1.0f, 0) == OFLK_ERR_INVALID && tr->m_model == 2);
+        EXPECT(oflk_tracker_set_motion(tr, OFLK_MOTION_AFFINE, 64, 1.5f, 7u) == OFLK_OK && tr->fit.model == 2 && tr->fit.hypotheses == 64);
+        EXPECT(oflk_tracker_set_motion(tr, 3, 64, 1.0f, 0) == OFLK_ERR_INVALID && tr->fit.model == 2);
         EXPECT(oflk_tracker_set_motion(tr, -2, 64, 1.0f, 0) == OFLK_ERR_INVALID);
         EXPECT(oflk_tracker_set_motion(tr, 1, 0, 1.0f, 0) == OFLK_ERR_INVALID && oflk_tracker_set_motion(tr, 1, 64, 0.0f, 0) == OFLK_ERR_INVALID);
-        EXPECT(oflk_tracker_set_motion(tr, -1, 0, nan, 0) == OFLK_OK && tr->m_model == -1);   // off: the rest is ignored
+        EXPECT(oflk_tracker_set_motion(tr, -1, 0, nan, 0) == OFLK_OK && tr->fit.model == -1);   // off: the rest is ignored
         const float *m = nullptr;
         EXPECT(oflk_tracker_motion_device(tr, &m, nullptr, nullptr) == OFLK_ERR_INVALID && !m);
         EXPECT(oflk_tracker_read_motion(tr, om, oi, oc, nullptr) == OFLK_ERR_INVALID);

@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes
 import os
 from pathlib import Path
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -28,6 +28,19 @@ _f32p = ctypes.POINTER(ctypes.c_float)
 _i32p = ctypes.POINTER(ctypes.c_int)
 _f64p = ctypes.POINTER(ctypes.c_double)
 _vp = ctypes.c_void_p
+_I, _U, _F, _D, _Z = ctypes.c_int, ctypes.c_uint, ctypes.c_float, ctypes.c_double, ctypes.c_size_t
+
+# The runs of arguments that many declarations share, in the field order of the C side's structs (and of the records below)
+_KLT = [_I] * 3 + [_F] * 5 + [_I]   # KltConfig: levels, window_size, iters, alpha, beta, max_residual, quality_level, min_distance, max_corners
+_TRACKING = _KLT + [_I]             # ... and detect_every (Tracking)
+_RANSAC = [_I, _F, _U]              # hypotheses, threshold, seed
+_FIT = [_I] + _RANSAC               # FitConfig: model, then the above (Fit)
+_WINDOW = [_f64p, _I]               # TrajWindow: weights, radius (Window)
+_ALIGN = [_I] * 5 + [_F]            # AlignConfig: H, W, levels, iterations, model, min_share
+_ROBUST = [_F, _I]                  # ... robust_delta, photometric, of the robust forms
+_ALIGN_D_IO = [_vp, _vp, _vp, _Z, _vp, _vp, _vp]        # d_model_in, d_status_in, d_workspace, workspace_bytes, d_model_out, d_status_out, d_stats
+_ALIGN_H_IO = [_f32p, _i32p, _f32p, _i32p, _f64p]       # model_in, status_in, model_out, status_out, stats
+_STAB_OUT = [_f32p, _f32p, _i32p, _vp]                  # correction, model_out, counts_out, held (behind the frames out)
 
 # every exported symbol of include/oflk.h: name -> (restype, argtypes)
 SIGNATURES = {
@@ -88,10 +101,10 @@ SIGNATURES = {
     "oflk_plan_sparse_tracks": (ctypes.c_int, [_vp, _vp, ctypes.c_int] + [ctypes.c_float] * 3 + [ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, _vp]),
     "oflk_pyramidal_sequence_sparse_tracks": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 3 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
     "oflk_pyramidal_sequence_sparse_tracks_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 3 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
-    "oflk_pyramidal_sequence_klt_sparse": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int, _i32p, _f32p, _f32p, _f32p, _vp]),
-    "oflk_pyramidal_sequence_klt_sparse_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int, _i32p, _f32p, _f32p, _f32p, _vp]),
-    "oflk_pyramidal_sequence_klt_sparse_replenish": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 2 + [_f32p, _vp, _vp, _i32p, _f32p]),
-    "oflk_pyramidal_sequence_klt_sparse_replenish_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 2 + [_f32p, _vp, _vp, _i32p, _f32p]),
+    "oflk_pyramidal_sequence_klt_sparse": (ctypes.c_int, [_f32p] + [_I] * 3 + _KLT + [_i32p, _f32p, _f32p, _f32p, _vp]),
+    "oflk_pyramidal_sequence_klt_sparse_u8": (ctypes.c_int, [_vp] + [_I] * 3 + _KLT + [_i32p, _f32p, _f32p, _f32p, _vp]),
+    "oflk_pyramidal_sequence_klt_sparse_replenish": (ctypes.c_int, [_f32p] + [_I] * 3 + _TRACKING + [_f32p, _vp, _vp, _i32p, _f32p]),
+    "oflk_pyramidal_sequence_klt_sparse_replenish_u8": (ctypes.c_int, [_vp] + [_I] * 3 + _TRACKING + [_f32p, _vp, _vp, _i32p, _f32p]),
     "oflk_plan_sparse_klt_replenish": (ctypes.c_int, [_vp, _vp, ctypes.c_int] + [ctypes.c_float] * 5 + [ctypes.c_int] * 3 + [_vp, ctypes.c_size_t] + [_vp] * 8),
     "oflk_corner_score": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_vp, _vp]),
     "oflk_corner_score_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 4 + [_f32p]),
@@ -108,7 +121,7 @@ SIGNATURES = {
     "oflk_replenish_features_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [ctypes.c_int] * 2 + [_f32p, _vp, _i32p, _f32p, _vp, _i32p]),
     "oflk_replenish_features_workspace": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
     "oflk_replenish_features": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [ctypes.c_float] * 2 + [ctypes.c_int] * 2 + [_vp, _vp, _vp, ctypes.c_size_t] + [_vp] * 5),
-    "oflk_tracker_create": (ctypes.c_int, [ctypes.POINTER(_vp)] + [ctypes.c_int] * 7 + [ctypes.c_float] * 5 + [ctypes.c_int] * 2),
+    "oflk_tracker_create": (ctypes.c_int, [ctypes.POINTER(_vp)] + [_I] * 4 + _TRACKING),
     "oflk_tracker_destroy": (ctypes.c_int, [_vp]),
     "oflk_tracker_reset": (ctypes.c_int, [_vp, _vp]),
     "oflk_tracker_workspace_bytes": (ctypes.c_size_t, [_vp]),
@@ -119,26 +132,26 @@ SIGNATURES = {
     "oflk_tracker_push": (ctypes.c_int, [_vp, _vp, _f32p, _vp, _vp, _i32p, _f32p, _i32p]),
     "oflk_tracker_add_points": (ctypes.c_int, [_vp, _f32p, ctypes.c_int, _vp]),
     "oflk_motion_workspace": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)]),
-    "oflk_estimate_motion": (ctypes.c_int, [_vp] * 3 + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_uint, _vp, ctypes.c_size_t] + [_vp] * 4),
-    "oflk_tracks_motion": (ctypes.c_int, [_vp] * 3 + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_uint, _vp, ctypes.c_size_t] + [_vp] * 4),
-    "oflk_estimate_motion_host": (ctypes.c_int, [_f32p, _f32p, _vp] + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_uint, _f32p, _vp, _i32p]),
+    "oflk_estimate_motion": (ctypes.c_int, [_vp] * 3 + [_I] * 3 + _FIT + [_vp, _Z] + [_vp] * 4),
+    "oflk_tracks_motion": (ctypes.c_int, [_vp] * 3 + [_I] * 3 + _FIT + [_vp, _Z] + [_vp] * 4),
+    "oflk_estimate_motion_host": (ctypes.c_int, [_f32p, _f32p, _vp] + [_I] * 3 + _FIT + [_f32p, _vp, _i32p]),
     "oflk_homography_workspace": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)]),
-    "oflk_estimate_homography": (ctypes.c_int, [_vp] * 3 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _vp, ctypes.c_size_t] + [_vp] * 4),
-    "oflk_tracks_homography": (ctypes.c_int, [_vp] * 3 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _vp, ctypes.c_size_t] + [_vp] * 4),
-    "oflk_estimate_homography_host": (ctypes.c_int, [_f32p, _f32p, _vp] + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f32p, _vp, _i32p]),
-    "oflk_tracker_set_motion": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_uint]),
+    "oflk_estimate_homography": (ctypes.c_int, [_vp] * 3 + [_I] * 3 + _RANSAC + [_vp, _Z] + [_vp] * 4),
+    "oflk_tracks_homography": (ctypes.c_int, [_vp] * 3 + [_I] * 3 + _RANSAC + [_vp, _Z] + [_vp] * 4),
+    "oflk_estimate_homography_host": (ctypes.c_int, [_f32p, _f32p, _vp] + [_I] * 3 + _RANSAC + [_f32p, _vp, _i32p]),
+    "oflk_tracker_set_motion": (ctypes.c_int, [_vp] + _FIT),
     "oflk_tracker_motion_device": (ctypes.c_int, [_vp] + [ctypes.POINTER(_vp)] * 3),
     "oflk_tracker_read_motion": (ctypes.c_int, [_vp, _f32p, _vp, _i32p, _vp]),
-    "oflk_stabilize_trajectory": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _f64p, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "oflk_stabilize_trajectory": (ctypes.c_int, [_vp, _vp, _I] + _WINDOW + [_vp] * 4),
     "oflk_warp_affine": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_vp] * 4),
-    "oflk_stabilize_trajectory_host": (ctypes.c_int, [_f32p, _i32p, ctypes.c_int, _f64p, ctypes.c_int, _f32p, _f64p, _vp]),
+    "oflk_stabilize_trajectory_host": (ctypes.c_int, [_f32p, _i32p, _I] + _WINDOW + [_f32p, _f64p, _vp]),
     "oflk_warp_affine_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 3 + [_f64p, _f32p, _vp]),
     "oflk_warp_affine_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [_f64p, _vp, _vp]),
     "oflk_warp_perspective": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_vp] * 4),
     "oflk_warp_perspective_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 3 + [_f64p, _f32p, _vp]),
     "oflk_warp_perspective_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [_f64p, _vp, _vp]),
-    "oflk_stabilize_sequence": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int, _f32p, _f32p, _f32p, _i32p, _vp]),
-    "oflk_stabilize_sequence_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int, _vp, _f32p, _f32p, _i32p, _vp]),
+    "oflk_stabilize_sequence": (ctypes.c_int, [_f32p] + [_I] * 3 + _TRACKING + _FIT + _WINDOW + [_f32p] + _STAB_OUT),
+    "oflk_stabilize_sequence_u8": (ctypes.c_int, [_vp] + [_I] * 3 + _TRACKING + _FIT + _WINDOW + [_vp] + _STAB_OUT),
     "oflk_mosaic_chain": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 4 + [ctypes.c_double] + [_vp] * 6),
     "oflk_mosaic_chain_host": (ctypes.c_int, [_f32p, _i32p] + [ctypes.c_int] * 4 + [ctypes.c_double, _f64p, _f64p, _f64p, _vp, _vp]),
     "oflk_mosaic_canvas": (ctypes.c_int, [_f64p, _vp, ctypes.c_int] + [_i32p] * 4),
@@ -147,38 +160,38 @@ SIGNATURES = {
     "oflk_mosaic_resolve": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [_vp] * 3),
     "oflk_mosaic_composite_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 3 + [_f64p, _vp] + [ctypes.c_int] * 5 + [_f32p, _i32p]),
     "oflk_mosaic_composite_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [_f64p, _vp] + [ctypes.c_int] * 5 + [_vp, _i32p]),
-    "oflk_mosaic_sequence": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_uint, ctypes.c_int, ctypes.c_double, ctypes.c_int, _f32p, ctypes.c_size_t, _i32p, _i32p, _f64p, _vp, _vp, _f32p, _i32p]),
-    "oflk_mosaic_sequence_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 5 + [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_uint, ctypes.c_int, ctypes.c_double, ctypes.c_int, _vp, ctypes.c_size_t, _i32p, _i32p, _f64p, _vp, _vp, _f32p, _i32p]),
+    "oflk_mosaic_sequence": (ctypes.c_int, [_f32p] + [_I] * 3 + _TRACKING + _RANSAC + [_I, _D, _I, _f32p, _Z, _i32p, _i32p, _f64p, _vp, _vp, _f32p, _i32p]),
+    "oflk_mosaic_sequence_u8": (ctypes.c_int, [_vp] + [_I] * 3 + _TRACKING + _RANSAC + [_I, _D, _I, _vp, _Z, _i32p, _i32p, _f64p, _vp, _vp, _f32p, _i32p]),
     "oflk_mosaic_accumulate_exposure": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_vp, _vp, _vp] + [ctypes.c_int] * 5 + [_vp, ctypes.c_size_t, _vp]),
     "oflk_mosaic_composite_exposure_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 3 + [_f64p, _vp, _f64p] + [ctypes.c_int] * 5 + [_f32p, _i32p]),
     "oflk_mosaic_composite_exposure_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [_f64p, _vp, _f64p] + [ctypes.c_int] * 5 + [_vp, _i32p]),
     "oflk_exposure_chain_host": (ctypes.c_int, [_f32p, _i32p, ctypes.c_int, ctypes.c_int, _f64p]),
     "oflk_align_workspace": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_size_t)]),
-    "oflk_align_refine": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 7 + [ctypes.c_float, _vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp]),
-    "oflk_align_sequence": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [ctypes.c_float, _vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp]),
-    "oflk_align_refine_host": (ctypes.c_int, [_f32p, _f32p] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p]),
-    "oflk_align_refine_host_u8": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p]),
-    "oflk_align_sequence_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p]),
-    "oflk_align_sequence_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p]),
+    "oflk_align_refine": (ctypes.c_int, [_vp, _vp, _I, _I] + _ALIGN + _ALIGN_D_IO + [_vp]),
+    "oflk_align_sequence": (ctypes.c_int, [_vp, _I, _I] + _ALIGN + _ALIGN_D_IO + [_vp]),
+    "oflk_align_refine_host": (ctypes.c_int, [_f32p, _f32p, _I] + _ALIGN + _ALIGN_H_IO),
+    "oflk_align_refine_host_u8": (ctypes.c_int, [_vp, _vp, _I] + _ALIGN + _ALIGN_H_IO),
+    "oflk_align_sequence_host": (ctypes.c_int, [_f32p, _I] + _ALIGN + _ALIGN_H_IO),
+    "oflk_align_sequence_host_u8": (ctypes.c_int, [_vp, _I] + _ALIGN + _ALIGN_H_IO),
     "oflk_align_photo_workspace": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_size_t)]),
-    "oflk_align_refine_photo": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 7 + [ctypes.c_float, _vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp]),
-    "oflk_align_sequence_photo": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [ctypes.c_float, _vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp]),
-    "oflk_align_refine_photo_host": (ctypes.c_int, [_f32p, _f32p] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p, _f32p]),
-    "oflk_align_refine_photo_host_u8": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p, _f32p]),
-    "oflk_align_sequence_photo_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p, _f32p]),
-    "oflk_align_sequence_photo_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float, _f32p, _i32p, _f32p, _i32p, _f64p, _f32p]),
+    "oflk_align_refine_photo": (ctypes.c_int, [_vp, _vp, _I, _I] + _ALIGN + _ALIGN_D_IO + [_vp, _vp]),
+    "oflk_align_sequence_photo": (ctypes.c_int, [_vp, _I, _I] + _ALIGN + _ALIGN_D_IO + [_vp, _vp]),
+    "oflk_align_refine_photo_host": (ctypes.c_int, [_f32p, _f32p, _I] + _ALIGN + _ALIGN_H_IO + [_f32p]),
+    "oflk_align_refine_photo_host_u8": (ctypes.c_int, [_vp, _vp, _I] + _ALIGN + _ALIGN_H_IO + [_f32p]),
+    "oflk_align_sequence_photo_host": (ctypes.c_int, [_f32p, _I] + _ALIGN + _ALIGN_H_IO + [_f32p]),
+    "oflk_align_sequence_photo_host_u8": (ctypes.c_int, [_vp, _I] + _ALIGN + _ALIGN_H_IO + [_f32p]),
     "oflk_align_robust_workspace": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_size_t)]),
-    "oflk_align_refine_robust": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 7 + [ctypes.c_float, ctypes.c_float, ctypes.c_int, _vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp]),
-    "oflk_align_sequence_robust": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [ctypes.c_float, ctypes.c_float, ctypes.c_int, _vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp]),
-    "oflk_align_refine_robust_host": (ctypes.c_int, [_f32p, _f32p] + [ctypes.c_int] * 6 + [ctypes.c_float, ctypes.c_float, ctypes.c_int, _f32p, _i32p, _f32p, _i32p, _f64p, _f32p]),
-    "oflk_align_refine_robust_host_u8": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 6 + [ctypes.c_float, ctypes.c_float, ctypes.c_int, _f32p, _i32p, _f32p, _i32p, _f64p, _f32p]),
-    "oflk_align_sequence_robust_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float, ctypes.c_float, ctypes.c_int, _f32p, _i32p, _f32p, _i32p, _f64p, _f32p]),
-    "oflk_align_sequence_robust_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float, ctypes.c_float, ctypes.c_int, _f32p, _i32p, _f32p, _i32p, _f64p, _f32p]),
+    "oflk_align_refine_robust": (ctypes.c_int, [_vp, _vp, _I, _I] + _ALIGN + _ROBUST + _ALIGN_D_IO + [_vp, _vp]),
+    "oflk_align_sequence_robust": (ctypes.c_int, [_vp, _I, _I] + _ALIGN + _ROBUST + _ALIGN_D_IO + [_vp, _vp]),
+    "oflk_align_refine_robust_host": (ctypes.c_int, [_f32p, _f32p, _I] + _ALIGN + _ROBUST + _ALIGN_H_IO + [_f32p]),
+    "oflk_align_refine_robust_host_u8": (ctypes.c_int, [_vp, _vp, _I] + _ALIGN + _ROBUST + _ALIGN_H_IO + [_f32p]),
+    "oflk_align_sequence_robust_host": (ctypes.c_int, [_f32p, _I] + _ALIGN + _ROBUST + _ALIGN_H_IO + [_f32p]),
+    "oflk_align_sequence_robust_host_u8": (ctypes.c_int, [_vp, _I] + _ALIGN + _ROBUST + _ALIGN_H_IO + [_f32p]),
     "oflk_align_weights": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 5 + [ctypes.c_float, _vp, _vp, _vp, _vp]),
     "oflk_align_weights_host": (ctypes.c_int, [_f32p, _f32p] + [ctypes.c_int] * 4 + [ctypes.c_float, _f32p, _f32p, _f32p]),
     "oflk_align_weights_host_u8": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 4 + [ctypes.c_float, _f32p, _f32p, _f32p]),
-    "oflk_stabilize_trajectory_ring": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 4 + [_f64p, ctypes.c_int, _vp, _vp, _vp]),
-    "oflk_stabilizer_create": (ctypes.c_int, [ctypes.POINTER(_vp)] + [ctypes.c_int] * 7 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int]),
+    "oflk_stabilize_trajectory_ring": (ctypes.c_int, [_vp, _vp] + [_I] * 4 + _WINDOW + [_vp] * 3),
+    "oflk_stabilizer_create": (ctypes.c_int, [ctypes.POINTER(_vp)] + [_I] * 4 + _TRACKING + _FIT + _WINDOW),
     "oflk_stabilizer_destroy": (ctypes.c_int, [_vp]),
     "oflk_stabilizer_reset": (ctypes.c_int, [_vp, _vp]),
     "oflk_stabilizer_workspace_bytes": (ctypes.c_size_t, [_vp]),
@@ -196,15 +209,15 @@ SIGNATURES = {
     "oflk_warp_perspective_packed": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_vp] * 4),
     "oflk_warp_affine_packed_host": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_f64p, _vp, _vp]),
     "oflk_warp_perspective_packed_host": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_f64p, _vp, _vp]),
-    "oflk_stabilize_sequence_packed": (ctypes.c_int, [_vp] + [ctypes.c_int] * 8 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int, _vp, _f32p, _f32p, _i32p, _vp]),
-    "oflk_stabilizer_create_packed": (ctypes.c_int, [ctypes.POINTER(_vp)] + [ctypes.c_int] * 8 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int]),
+    "oflk_stabilize_sequence_packed": (ctypes.c_int, [_vp] + [_I] * 5 + _TRACKING + _FIT + _WINDOW + [_vp] + _STAB_OUT),
+    "oflk_stabilizer_create_packed": (ctypes.c_int, [ctypes.POINTER(_vp)] + [_I] * 5 + _TRACKING + _FIT + _WINDOW),
     "oflk_nv12_frame_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
     "oflk_warp_affine_nv12": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_vp] * 4),
     "oflk_warp_perspective_nv12": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_vp] * 4),
     "oflk_warp_affine_nv12_host": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_f64p, _vp, _vp]),
     "oflk_warp_perspective_nv12_host": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_f64p, _vp, _vp]),
-    "oflk_stabilize_sequence_nv12": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int, _vp, _f32p, _f32p, _i32p, _vp]),
-    "oflk_stabilizer_create_nv12": (ctypes.c_int, [ctypes.POINTER(_vp)] + [ctypes.c_int] * 7 + [ctypes.c_float] * 5 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, _f64p, ctypes.c_int]),
+    "oflk_stabilize_sequence_nv12": (ctypes.c_int, [_vp] + [_I] * 4 + _TRACKING + _FIT + _WINDOW + [_vp] + _STAB_OUT),
+    "oflk_stabilizer_create_nv12": (ctypes.c_int, [ctypes.POINTER(_vp)] + [_I] * 4 + _TRACKING + _FIT + _WINDOW),
     "oflk_shard_range": (None, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, _i32p]),
     "oflk_single_scale_fp16": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, _f32p, _f32p]),
     "oflk_rtl_stream_length": (ctypes.c_long, [ctypes.c_int, ctypes.c_int]),
@@ -298,6 +311,16 @@ def both_u8(a, b) -> bool:
 
 def ptr(a: np.ndarray):
     return a.ctypes.data_as(_f32p)
+
+
+def pix(arr: np.ndarray):
+    """the C pointer of a contiguous float32 or uint8 frame array"""
+    return arr.ctypes.data if arr.dtype == np.uint8 else ptr(arr)
+
+
+def pixels(arr: np.ndarray, name: str):
+    """The one pixel-type dispatch: (pix(arr), the library's function `name`, `name`_u8 for a uint8 array)"""
+    return pix(arr), getattr(lib(), name + ("_u8" if arr.dtype == np.uint8 else ""))
 
 
 def as_sequence(frames) -> Tuple[np.ndarray, bool]:
@@ -470,6 +493,14 @@ class Plan:
         return {names[i].decode(): {"total_ms": ms[i], "launches": cnt[i]} for i in range(k)}
 
 
+def check_int(name: str, v, lo: int, hi: Optional[int] = None, what: Optional[str] = None) -> int:
+    """v as an int; ValueError "`name` must be an integer `what`, got v" unless v is integral (not a bool) and in [lo, hi].
+    what defaults to ">= lo", or "in [lo, hi]" with hi."""
+    if isinstance(v, bool) or int(v) != v or int(v) < lo or (hi is not None and int(v) > hi):
+        raise ValueError(f"{name} must be an integer {what or (f'>= {lo}' if hi is None else f'in [{lo}, {hi}]')}, got {v!r}")
+    return int(v)
+
+
 def check_fb_params(alpha: float, beta: float) -> Tuple[float, float]:
     """alpha, beta of the forward-backward test as float32; ValueError unless both are finite and >= 0."""
     with np.errstate(over="ignore"):   # a value beyond float32's range becomes inf, and is refused below
@@ -517,9 +548,8 @@ def check_sparse_params(shape, num_levels, window_size, num_iterations, max_resi
     """The sparse tracker's configuration as the C ABI takes it: (levels, window, iterations, max_residual as float32).
     ValueError unless levels >= 1, iterations >= 1, the window is odd in [3, 11], every pyramid level of `shape` = (H, W)
     is at least 2 x 2 and max_residual is >= 0 (inf allowed: no residual test).  Nothing here touches a device."""
-    for name, v in (("num_levels", num_levels), ("num_iterations", num_iterations)):
-        if isinstance(v, bool) or int(v) != v or int(v) < 1:
-            raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+    check_int("num_levels", num_levels, 1)
+    check_int("num_iterations", num_iterations, 1)
     if window_size not in CORNER_WINDOWS:
         raise ValueError(f"window_size must be one of {CORNER_WINDOWS}, got {window_size!r}")
     h, w = int(shape[0]), int(shape[1])
@@ -562,8 +592,7 @@ def sparse_klt_replenish(plan: "Plan", d_frames: int, d_workspace: int, workspac
 def check_feature_params(max_corners, quality_level: float, min_distance: float, window_size: int) -> Tuple[int, float, float, int]:
     """The detection parameters as the C ABI takes them: (K, q, md, window) with q, md float32; ValueError unless K >= 1,
     q in [0, 1], md finite and >= 0 and the window odd in [3, 11].  Nothing here touches a device."""
-    if isinstance(max_corners, bool) or int(max_corners) != max_corners or int(max_corners) < 1:
-        raise ValueError(f"max_corners must be an integer >= 1, got {max_corners!r}")
+    check_int("max_corners", max_corners, 1)
     with np.errstate(over="ignore"):
         q, md = np.float32(quality_level), np.float32(min_distance)
     if not (np.isfinite(q) and 0 <= q <= 1):
@@ -573,6 +602,100 @@ def check_feature_params(max_corners, quality_level: float, min_distance: float,
     if window_size not in CORNER_WINDOWS:
         raise ValueError(f"window_size must be one of {CORNER_WINDOWS}, got {window_size!r}")
     return int(max_corners), float(q), float(md), int(window_size)
+
+
+DETECT_EVERY_MAX = 2 ** 31 - 1
+
+
+def check_detect_every(detect_every, lo: int = 1) -> int:
+    """detect_every as the C int: an integer >= lo (1 for the sequence calls, 0 -- never detect -- for the online ones),
+    clamped to DETECT_EVERY_MAX, which no sequence reaches; ValueError otherwise"""
+    return min(check_int("detect_every", detect_every, lo), DETECT_EVERY_MAX)
+
+
+class Tracking(NamedTuple):
+    """The sparse tracker's settings, checked, in the field order of the C side's KltConfig, then detect_every: the record
+    is the run of arguments that every C call which takes them takes (`*tracking`; .klt for a call without detect_every,
+    whose record says DETECT_EVERY_MAX: it detects on frame 0 alone)."""
+    levels: int
+    window_size: int
+    iters: int
+    alpha: float
+    beta: float
+    max_residual: float
+    quality_level: float
+    min_distance: float
+    max_corners: int
+    detect_every: int = DETECT_EVERY_MAX   # a call that takes none detects on frame 0 alone, which is what this value says
+
+    @property
+    def klt(self) -> tuple:
+        return self[:9]
+
+
+def check_tracking(shape, num_levels, window_size, num_iterations, alpha, beta, max_residual, max_corners, quality_level,
+                   min_distance, detect_every=None, min_every: int = 1) -> Tracking:
+    """The Tracking record of a caller's arguments, refused in this order: check_fb_params, check_sparse_params for frames
+    of `shape` = (H, W), check_feature_params, check_detect_every (detect_every None: the call takes none).  A caller that
+    parses its frames between the first two calls check_fb_params itself before it does: the order is the caller's."""
+    a, b = check_fb_params(alpha, beta)
+    L, win, it, r = check_sparse_params(shape, num_levels, window_size, num_iterations, max_residual)
+    K, q, md, win = check_feature_params(max_corners, quality_level, min_distance, win)
+    return Tracking(L, win, it, a, b, r, q, md, K, *(() if detect_every is None else (check_detect_every(detect_every, min_every),)))
+
+
+class Fit(NamedTuple):
+    """The RANSAC fit's settings, checked (check_motion_params), in the field order of the C side's FitConfig: `*fit` is
+    the run of C arguments; .ransac the run of the homography calls, which take no model (check_ransac_params gives it)."""
+    model: int
+    hypotheses: int
+    threshold: float
+    seed: int
+
+    @property
+    def ransac(self) -> tuple:
+        return self[1:]
+
+
+class Window(NamedTuple):
+    """The trajectory filter's window (check_window), as the C side's TrajWindow: .args is the run of C arguments"""
+    weights: np.ndarray   # radius + 1 float64, contiguous
+    radius: int
+
+    @property
+    def args(self) -> tuple:
+        return _f64(self.weights), self.radius
+
+
+def check_window(radius, sigma=None) -> Window:
+    """the Window of stabilize_weights(radius, sigma), with its ValueErrors"""
+    w = stabilize_weights(radius, sigma)
+    return Window(w, int(w.size) - 1)
+
+
+def check_refine(refine_iterations, refine_photometric=False, refine_robust_delta=None) -> int:
+    """refine_iterations of the stabilise and mosaic calls as an int >= 0; ValueError for anything else, or for
+    refine_photometric or refine_robust_delta without it"""
+    n = check_int("refine_iterations", refine_iterations, 0)
+    if refine_photometric and n == 0:
+        raise ValueError("refine_photometric needs refine_iterations > 0")
+    if refine_robust_delta is not None and n == 0:
+        raise ValueError("refine_robust_delta needs refine_iterations > 0")
+    return n
+
+
+class FrameLayout(NamedTuple):
+    """How a frame lies in memory, as the C side's FrameLayout: planes of one value per pixel (the default), interleaved
+    colour ("_packed", args (channels, order)) or NV12 ("_nv12", args (siting,)).  suffix names the form of
+    oflk_stabilize_sequence* / oflk_stabilizer_create*, args is what that form takes behind H and W."""
+    suffix: str = ""
+    args: tuple = ()
+
+    def frame_shape(self, H: int, W: int) -> tuple:
+        """the shape of one H x W frame's array"""
+        if self.suffix == "_nv12":
+            return (3 * H // 2, W)
+        return (H, W, self.args[0]) if self.suffix else (H, W)
 
 
 def as_frames(frames) -> Tuple[np.ndarray, bool]:
@@ -643,27 +766,25 @@ MOTION_MODELS = {"translation": 0, "similarity": 1, "affine": 2}
 MOTION_MAX_HYPOTHESES = 65536
 
 
-def check_motion_params(model, hypotheses, threshold: float, seed) -> Tuple[int, int, float, int]:
-    """The fit's parameters as the C ABI takes them: (model code, hypotheses, threshold as float32, seed as uint32);
+def check_motion_params(model, hypotheses, threshold: float, seed) -> "Fit":
+    """The fit's parameters as the C ABI takes them, a Fit: (model code, hypotheses, threshold as float32, seed as uint32);
     ValueError for an unknown model, hypotheses outside [1, MOTION_MAX_HYPOTHESES], a threshold that is not finite and
     positive or a seed outside uint32.  Nothing here touches a device."""
     code = MOTION_MODELS.get(model) if isinstance(model, str) else (model if model in (0, 1, 2) and not isinstance(model, bool) else None)
     if code is None:
         raise ValueError(f"model must be one of {sorted(MOTION_MODELS)}, got {model!r}")
-    return (int(code),) + check_ransac_params(hypotheses, threshold, seed)
+    return Fit(int(code), *check_ransac_params(hypotheses, threshold, seed))
 
 
 def check_ransac_params(hypotheses, threshold: float, seed) -> Tuple[int, float, int]:
     """What the motion and the homography fit share of check_motion_params: (hypotheses, threshold as float32, seed as
     uint32), with its ValueErrors"""
-    if isinstance(hypotheses, bool) or int(hypotheses) != hypotheses or not 1 <= int(hypotheses) <= MOTION_MAX_HYPOTHESES:
-        raise ValueError(f"hypotheses must be an integer in [1, {MOTION_MAX_HYPOTHESES}], got {hypotheses!r}")
+    check_int("hypotheses", hypotheses, 1, MOTION_MAX_HYPOTHESES)
     with np.errstate(over="ignore"):
         thr = np.float32(threshold)
     if not (np.isfinite(thr) and thr > 0):
         raise ValueError(f"threshold must be finite and > 0, got {threshold!r}")
-    if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 32:
-        raise ValueError(f"seed must be an integer in [0, 2^32), got {seed!r}")
+    check_int("seed", seed, 0, 2 ** 32 - 1, "in [0, 2^32)")
     return int(hypotheses), float(thr), int(seed)
 
 
@@ -753,9 +874,7 @@ def stabilize_weights(radius, sigma=None) -> np.ndarray:
     """The window of the trajectory filter as the C ABI takes it: radius + 1 float64 Gaussian weights
     exp(-0.5 (i / sigma)^2), sigma defaulting to radius / 2 (1.0 for radius 0), formed here on the host.  ValueError for a
     radius outside [0, STABILIZE_MAX_RADIUS], a sigma that is not finite and positive, or a weight that underflows to 0."""
-    if isinstance(radius, bool) or int(radius) != radius or not 0 <= int(radius) <= STABILIZE_MAX_RADIUS:
-        raise ValueError(f"radius must be an integer in [0, {STABILIZE_MAX_RADIUS}], got {radius!r}")
-    radius = int(radius)
+    radius = check_int("radius", radius, 0, STABILIZE_MAX_RADIUS)
     if sigma is None:
         sigma = radius / 2 if radius > 0 else 1.0
     sigma = float(sigma)
@@ -819,14 +938,10 @@ def warp_affine_host(frames: np.ndarray, maps: np.ndarray, inside: bool = False)
     """oflk_warp_affine_host[_u8] -- oflk_warp_perspective_host[_u8] for (F, 9) maps --: contiguous (F, H, W) float32 or uint8
     frames and (F, 6) float64 maps in; the warped frames and, when asked for, the inside mask (else None) out"""
     F, H, W = frames.shape
-    u8 = frames.dtype == np.uint8
     out = np.empty_like(frames)
     ins = np.empty((F, H, W), np.uint8) if inside else None
-    fn = lib().oflk_warp_affine_host_u8 if u8 else lib().oflk_warp_affine_host
-    if maps.shape[-1] == 9:
-        fn = lib().oflk_warp_perspective_host_u8 if u8 else lib().oflk_warp_perspective_host
-    check(fn(frames.ctypes.data if u8 else ptr(frames), F, H, W, _f64(maps), out.ctypes.data if u8 else ptr(out),
-             None if ins is None else ins.ctypes.data))
+    src, fn = pixels(frames, "oflk_warp_perspective_host" if maps.shape[-1] == 9 else "oflk_warp_affine_host")
+    check(fn(src, F, H, W, _f64(maps), pix(out), None if ins is None else ins.ctypes.data))
     return out, ins
 
 
@@ -1001,13 +1116,10 @@ def mosaic_accumulate(d_frames: int, F: int, H: int, W: int, d_map: int, d_skip:
     """oflk_mosaic_accumulate on device pointers: adds d_frames [F][H][W] (float32, or uint8 with u8) under d_map [F][9] float64
     (d_skip [F] uint8 or 0) to the canvas state d_state; asynchronous.  d_exposure given: oflk_mosaic_accumulate_exposure with
     the frames' (eg, eb) [F][2] float64."""
-    if d_exposure is not None:
-        check(lib().oflk_mosaic_accumulate_exposure(d_frames or None, int(bool(u8)), int(F), int(H), int(W), d_map or None,
-                                                    d_skip or None, d_exposure or None, int(x0), int(y0), int(Hc), int(Wc),
-                                                    int(blend), d_state or None, int(state_bytes), stream))
-        return
-    check(lib().oflk_mosaic_accumulate(d_frames or None, int(bool(u8)), int(F), int(H), int(W), d_map or None, d_skip or None, int(x0),
-                                       int(y0), int(Hc), int(Wc), int(blend), d_state or None, int(state_bytes), stream))
+    fn = lib().oflk_mosaic_accumulate if d_exposure is None else lib().oflk_mosaic_accumulate_exposure
+    check(fn(d_frames or None, int(bool(u8)), int(F), int(H), int(W), d_map or None, d_skip or None,
+             *(() if d_exposure is None else (d_exposure or None,)), int(x0), int(y0), int(Hc), int(Wc), int(blend), d_state or None,
+             int(state_bytes), stream))
 
 
 def mosaic_resolve(d_state: int, Hc: int, Wc: int, d_out: int, d_count: int = 0, u8: bool = False, stream: int = 0) -> None:
@@ -1022,18 +1134,11 @@ def mosaic_composite_host(frames: np.ndarray, maps: np.ndarray, skip: Optional[n
     skip flags in; the (Hc, Wc) mosaic and, when asked for, the int32 count (else None) out.  exposure given (contiguous (F, 2)
     float64): oflk_mosaic_composite_exposure_host[_u8]"""
     F, H, W = frames.shape
-    u8 = frames.dtype == np.uint8
     out = np.empty((Hc, Wc), frames.dtype)
     cnt = np.empty((Hc, Wc), np.int32) if count else None
-    if exposure is not None:
-        fn = lib().oflk_mosaic_composite_exposure_host_u8 if u8 else lib().oflk_mosaic_composite_exposure_host
-        check(fn(frames.ctypes.data if u8 else ptr(frames), F, H, W, _f64(maps), None if skip is None else skip.ctypes.data,
-                 _f64(exposure), int(x0), int(y0), int(Hc), int(Wc), int(blend), out.ctypes.data if u8 else ptr(out),
-                 None if cnt is None else cnt.ctypes.data_as(_i32p)))
-        return out, cnt
-    fn = lib().oflk_mosaic_composite_host_u8 if u8 else lib().oflk_mosaic_composite_host
-    check(fn(frames.ctypes.data if u8 else ptr(frames), F, H, W, _f64(maps), None if skip is None else skip.ctypes.data, int(x0), int(y0),
-             int(Hc), int(Wc), int(blend), out.ctypes.data if u8 else ptr(out), None if cnt is None else cnt.ctypes.data_as(_i32p)))
+    src, fn = pixels(frames, "oflk_mosaic_composite_host" if exposure is None else "oflk_mosaic_composite_exposure_host")
+    check(fn(src, F, H, W, _f64(maps), None if skip is None else skip.ctypes.data, *(() if exposure is None else (_f64(exposure),)),
+             int(x0), int(y0), int(Hc), int(Wc), int(blend), pix(out), None if cnt is None else cnt.ctypes.data_as(_i32p)))
     return out, cnt
 
 
@@ -1053,9 +1158,8 @@ def check_align_params(kind, levels, iterations, min_share: float) -> Tuple[int,
     """the C ABI's model code and the checked levels, iterations and min_share of the alignment calls; ValueError otherwise"""
     if not isinstance(kind, str) or kind not in ALIGN_KINDS:
         raise ValueError(f"kind must be one of {sorted(ALIGN_KINDS)}, got {kind!r}")
-    for name, v in (("levels", levels), ("iterations", iterations)):
-        if isinstance(v, bool) or int(v) != v or int(v) < 1:
-            raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+    check_int("levels", levels, 1)
+    check_int("iterations", iterations, 1)
     ms = float(min_share)
     if not 0.0 < ms <= 1.0:
         raise ValueError(f"min_share must be in (0, 1], got {min_share!r}")
@@ -1077,11 +1181,23 @@ def align_workspace(S: int, H: int, W: int, levels: int, model: int, photometric
     """bytes of the workspace of oflk_align_refine for S steps (oflk_align_sequence: S = T - 1); photometric: of
     oflk_align_refine_photo (oflk_align_photo_workspace); robust: of oflk_align_refine_robust (oflk_align_robust_workspace)"""
     n = ctypes.c_size_t(0)
-    if robust:
-        check(lib().oflk_align_robust_workspace(int(S), int(H), int(W), int(levels), int(model), int(bool(photometric)), ctypes.byref(n)))
-        return int(n.value)
-    check((lib().oflk_align_photo_workspace if photometric else lib().oflk_align_workspace)(int(S), int(H), int(W), int(levels), int(model), ctypes.byref(n)))
+    fn = getattr(lib(), "oflk_align_robust_workspace" if robust else "oflk_align_photo_workspace" if photometric else "oflk_align_workspace")
+    check(fn(int(S), int(H), int(W), int(levels), int(model), *((int(bool(photometric)),) if robust else ()), ctypes.byref(n)))
     return int(n.value)
+
+
+def _align_device(name: str, frames: tuple, levels, iterations, model, min_share, d_model_in, d_status_in, d_workspace,
+                  workspace_bytes, d_model_out, d_status_out, d_stats, stream, d_photo_out, robust_delta) -> None:
+    """the one body of align_refine and align_sequence: chooses the plain, _photo or _robust form of `name` and gives it
+    that form's extra arguments (robust_delta and the photometric flag behind min_share, d_photo_out before the stream)"""
+    form, settings, photo = "", (), ()
+    if robust_delta is not None:
+        form, settings, photo = "_robust", (float(robust_delta), int(d_photo_out is not None)), (d_photo_out or None,)
+    elif d_photo_out is not None:
+        form, photo = "_photo", (d_photo_out or None,)
+    check(getattr(lib(), name + form)(*frames, int(levels), int(iterations), int(model), float(min_share), *settings,
+                                      d_model_in or None, d_status_in or None, d_workspace or None, int(workspace_bytes),
+                                      d_model_out or None, d_status_out or None, d_stats or None, *photo, stream))
 
 
 def align_refine(d_a: int, d_b: int, S: int, H: int, W: int, levels: int, iterations: int, model: int, min_share: float,
@@ -1093,22 +1209,9 @@ def align_refine(d_a: int, d_b: int, S: int, H: int, W: int, levels: int, iterat
     oflk_align_refine_photo with (g, b) [S][2] float32 out and a workspace of align_workspace(..., photometric=True) bytes.
     robust_delta given: oflk_align_refine_robust (photometric when d_photo_out is given), d_stats [S][8] and a workspace of
     align_workspace(..., robust=True) bytes; the C call checks robust_delta."""
-    if robust_delta is not None:
-        check(lib().oflk_align_refine_robust(d_a or None, d_b or None, int(bool(u8)), int(S), int(H), int(W), int(levels),
-                                             int(iterations), int(model), float(min_share), float(robust_delta),
-                                             int(d_photo_out is not None), d_model_in or None, d_status_in or None,
-                                             d_workspace or None, int(workspace_bytes), d_model_out or None, d_status_out or None,
-                                             d_stats or None, d_photo_out or None, stream))
-        return
-    if d_photo_out is not None:
-        check(lib().oflk_align_refine_photo(d_a or None, d_b or None, int(bool(u8)), int(S), int(H), int(W), int(levels),
-                                            int(iterations), int(model), float(min_share), d_model_in or None, d_status_in or None,
-                                            d_workspace or None, int(workspace_bytes), d_model_out or None, d_status_out or None,
-                                            d_stats or None, d_photo_out or None, stream))
-        return
-    check(lib().oflk_align_refine(d_a or None, d_b or None, int(bool(u8)), int(S), int(H), int(W), int(levels), int(iterations),
-                                  int(model), float(min_share), d_model_in or None, d_status_in or None, d_workspace or None,
-                                  int(workspace_bytes), d_model_out or None, d_status_out or None, d_stats or None, stream))
+    _align_device("oflk_align_refine", (d_a or None, d_b or None, int(bool(u8)), int(S), int(H), int(W)), levels, iterations, model,
+                  min_share, d_model_in, d_status_in, d_workspace, workspace_bytes, d_model_out, d_status_out, d_stats, stream,
+                  d_photo_out, robust_delta)
 
 
 def align_sequence(d_frames: int, T: int, H: int, W: int, levels: int, iterations: int, model: int, min_share: float,
@@ -1118,22 +1221,35 @@ def align_sequence(d_frames: int, T: int, H: int, W: int, levels: int, iteration
     """oflk_align_sequence on device pointers: the T-1 steps t -> t+1 of d_frames [T][H][W], with align_refine's other
     arguments for S = T - 1; asynchronous.  d_photo_out given: oflk_align_sequence_photo.  robust_delta given:
     oflk_align_sequence_robust."""
-    if robust_delta is not None:
-        check(lib().oflk_align_sequence_robust(d_frames or None, int(bool(u8)), int(T), int(H), int(W), int(levels), int(iterations),
-                                               int(model), float(min_share), float(robust_delta), int(d_photo_out is not None),
-                                               d_model_in or None, d_status_in or None, d_workspace or None, int(workspace_bytes),
-                                               d_model_out or None, d_status_out or None, d_stats or None, d_photo_out or None,
-                                               stream))
-        return
-    if d_photo_out is not None:
-        check(lib().oflk_align_sequence_photo(d_frames or None, int(bool(u8)), int(T), int(H), int(W), int(levels), int(iterations),
-                                              int(model), float(min_share), d_model_in or None, d_status_in or None,
-                                              d_workspace or None, int(workspace_bytes), d_model_out or None, d_status_out or None,
-                                              d_stats or None, d_photo_out or None, stream))
-        return
-    check(lib().oflk_align_sequence(d_frames or None, int(bool(u8)), int(T), int(H), int(W), int(levels), int(iterations), int(model),
-                                    float(min_share), d_model_in or None, d_status_in or None, d_workspace or None,
-                                    int(workspace_bytes), d_model_out or None, d_status_out or None, d_stats or None, stream))
+    _align_device("oflk_align_sequence", (d_frames or None, int(bool(u8)), int(T), int(H), int(W)), levels, iterations, model,
+                  min_share, d_model_in, d_status_in, d_workspace, workspace_bytes, d_model_out, d_status_out, d_stats, stream,
+                  d_photo_out, robust_delta)
+
+
+def _align_host(a: np.ndarray, b: Optional[np.ndarray], model_in: np.ndarray, status_in: Optional[np.ndarray], levels: int,
+                iterations: int, model: int, min_share: float, photometric: bool, robust_delta: Optional[float]):
+    """the one body of align_host and align_robust_host: (model, status, stats, photo) of the plain, _photo or _robust host
+    form.  The forms differ in the stats' width (4, robust 8), in the photo output (none, (S, 2), robust: (S, 2) preset to
+    (1, 0) and passed only with photometric) and in the robust form's two scalars behind min_share."""
+    robust = robust_delta is not None
+    F, H, W = a.shape
+    S = F if b is not None else F - 1
+    out = np.empty_like(model_in)
+    st, stats = np.empty(S, np.int32), np.empty((S, 8 if robust else 4), np.float64)
+    photo = np.empty((S, 2), np.float32) if robust or photometric else None
+    if robust:
+        photo[:] = (1.0, 0.0)
+    settings = (int(H), int(W), int(levels), int(iterations), int(model), float(min_share))
+    io = (ptr(model_in), None if status_in is None else status_in.ctypes.data_as(_i32p), ptr(out), st.ctypes.data_as(_i32p), _f64(stats))
+    if robust:
+        settings += (float(robust_delta), int(bool(photometric)))
+        io += (ptr(photo) if photometric else None,)
+    elif photometric:
+        io += (ptr(photo),)
+    pa, fn = pixels(a, ("oflk_align_refine" if b is not None else "oflk_align_sequence")
+                    + ("_robust" if robust else "_photo" if photometric else "") + "_host")
+    check(fn(*((pa, pix(b), S) if b is not None else (pa, F)), *settings, *io))
+    return out, st, stats, photo
 
 
 def align_host(a: np.ndarray, b: Optional[np.ndarray], model_in: np.ndarray, status_in: Optional[np.ndarray], levels: int,
@@ -1141,25 +1257,8 @@ def align_host(a: np.ndarray, b: Optional[np.ndarray], model_in: np.ndarray, sta
     """oflk_align_refine_host[_u8] (b given: contiguous (S, H, W) arrays of one type) or oflk_align_sequence_host[_u8] (b None:
     a holds the S + 1 frames); contiguous float32 (S, 6 | 9) models and optional int32 (S,) statuses in; (model (S, nc) float32,
     status (S,) int32, stats (S, 4) float64) out.  photometric: the _photo_ forms, with (g, b) (S, 2) float32 as a fourth output"""
-    F, H, W = a.shape
-    S = F if b is not None else F - 1
-    u8 = a.dtype == np.uint8
-    out = np.empty_like(model_in)
-    st, stats = np.empty(S, np.int32), np.empty((S, 4), np.float64)
-    pix = (lambda x: x.ctypes.data) if u8 else ptr
-    tail = (int(H), int(W), int(levels), int(iterations), int(model), float(min_share), ptr(model_in),
-            None if status_in is None else status_in.ctypes.data_as(_i32p), ptr(out), st.ctypes.data_as(_i32p), _f64(stats))
-    photo = None
-    if photometric:
-        photo = np.empty((S, 2), np.float32)
-        tail += (ptr(photo),)
-    name = ("oflk_align_refine" if b is not None else "oflk_align_sequence") + ("_photo" if photometric else "") + "_host" + ("_u8" if u8 else "")
-    fn = getattr(lib(), name)
-    if b is not None:
-        check(fn(pix(a), pix(b), S, *tail))
-    else:
-        check(fn(pix(a), F, *tail))
-    return (out, st, stats, photo) if photometric else (out, st, stats)
+    r = _align_host(a, b, model_in, status_in, levels, iterations, model, min_share, photometric, None)
+    return r if photometric else r[:3]
 
 
 def align_robust_host(a: np.ndarray, b: Optional[np.ndarray], model_in: np.ndarray, status_in: Optional[np.ndarray], levels: int,
@@ -1167,23 +1266,7 @@ def align_robust_host(a: np.ndarray, b: Optional[np.ndarray], model_in: np.ndarr
     """oflk_align_refine_robust_host[_u8] (b given) or oflk_align_sequence_robust_host[_u8] (b None), with align_host's arrays;
     (model (S, nc) float32, status (S,) int32, stats (S, 8) float64, photo (S, 2) float32) out, photo (1, 0) without
     photometric.  The C call checks robust_delta."""
-    F, H, W = a.shape
-    S = F if b is not None else F - 1
-    u8 = a.dtype == np.uint8
-    out = np.empty_like(model_in)
-    st, stats = np.empty(S, np.int32), np.empty((S, 8), np.float64)
-    photo = np.empty((S, 2), np.float32)
-    photo[:] = (1.0, 0.0)
-    pix = (lambda x: x.ctypes.data) if u8 else ptr
-    tail = (int(H), int(W), int(levels), int(iterations), int(model), float(min_share), float(robust_delta), int(bool(photometric)),
-            ptr(model_in), None if status_in is None else status_in.ctypes.data_as(_i32p), ptr(out), st.ctypes.data_as(_i32p),
-            _f64(stats), ptr(photo) if photometric else None)
-    fn = getattr(lib(), ("oflk_align_refine" if b is not None else "oflk_align_sequence") + "_robust_host" + ("_u8" if u8 else ""))
-    if b is not None:
-        check(fn(pix(a), pix(b), S, *tail))
-    else:
-        check(fn(pix(a), F, *tail))
-    return out, st, stats, photo
+    return _align_host(a, b, model_in, status_in, levels, iterations, model, min_share, photometric, robust_delta)
 
 
 def align_weights(d_a: int, d_b: int, S: int, H: int, W: int, model: int, robust_delta: float, d_model: int, d_photo: int,
@@ -1199,11 +1282,9 @@ def align_weights_host(a: np.ndarray, b: np.ndarray, model_in: np.ndarray, model
     """oflk_align_weights_host[_u8]: contiguous (S, H, W) arrays of one type, float32 (S, 6 | 9) models, optional float32 (S, 2)
     gains and biases -> (S, H, W) float32"""
     S, H, W = a.shape
-    u8 = a.dtype == np.uint8
     out = np.empty((S, H, W), np.float32)
-    pix = (lambda x: x.ctypes.data) if u8 else ptr
-    fn = lib().oflk_align_weights_host_u8 if u8 else lib().oflk_align_weights_host
-    check(fn(pix(a), pix(b), int(S), int(H), int(W), int(model), float(robust_delta), ptr(model_in), None if photo is None else ptr(photo),
+    pa, fn = pixels(a, "oflk_align_weights_host")
+    check(fn(pa, pix(b), int(S), int(H), int(W), int(model), float(robust_delta), ptr(model_in), None if photo is None else ptr(photo),
              ptr(out)))
     return out
 
@@ -1218,9 +1299,9 @@ class Tracker:
                  quality_level: float = 0.01, min_distance: float = 10.0):
         self._h = _vp()
         self.H, self.W, self.u8, self.K = int(H), int(W), bool(u8), int(max_corners)
-        check(lib().oflk_tracker_create(ctypes.byref(self._h), int(device), int(H), int(W), int(bool(u8)), int(levels),
-                                        int(window_size), int(iters), float(alpha), float(beta), float(max_residual),
-                                        float(quality_level), float(min_distance), int(max_corners), int(detect_every)))
+        trk = Tracking(int(levels), int(window_size), int(iters), float(alpha), float(beta), float(max_residual), float(quality_level),
+                       float(min_distance), int(max_corners), int(detect_every))
+        check(lib().oflk_tracker_create(ctypes.byref(self._h), int(device), int(H), int(W), int(bool(u8)), *trk))
 
     _owned = True   # False: the handle belongs to a Stabilizer
 
@@ -1327,20 +1408,17 @@ class Stabilizer:
         self.nv12 = bool(nv12)          # NV12 uint8 frames (3H/2, W), their Y plane to the tracker
         w = np.ascontiguousarray(weights, np.float64)
         self.radius = int(w.size) - 1
-        tail = (int(levels), int(window_size), int(iters), float(alpha), float(beta), float(max_residual), float(quality_level),
-                float(min_distance), int(max_corners), int(detect_every), int(model), int(hypotheses), float(threshold), int(seed),
-                _f64(w), self.radius)
-        if self.nv12:
-            if not self.u8 or self.channels:
-                raise ValueError("NV12 frames are uint8 and have no channel axis")
-            check(lib().oflk_stabilizer_create_nv12(ctypes.byref(self._h), int(device), int(H), int(W), int(siting), *tail))
-        elif self.channels:
-            if not self.u8:
-                raise ValueError("colour frames must be uint8 (float32 colour is not offered)")
-            check(lib().oflk_stabilizer_create_packed(ctypes.byref(self._h), int(device), int(H), int(W), self.channels, int(order),
-                                                      *tail))
-        else:
-            check(lib().oflk_stabilizer_create(ctypes.byref(self._h), int(device), int(H), int(W), int(bool(u8)), *tail))
+        trk = Tracking(int(levels), int(window_size), int(iters), float(alpha), float(beta), float(max_residual), float(quality_level),
+                       float(min_distance), int(max_corners), int(detect_every))
+        tail = (*trk, *Fit(int(model), int(hypotheses), float(threshold), int(seed)), *Window(w, self.radius).args)
+        if self.nv12 and (not self.u8 or self.channels):
+            raise ValueError("NV12 frames are uint8 and have no channel axis")
+        if self.channels and not self.nv12 and not self.u8:
+            raise ValueError("colour frames must be uint8 (float32 colour is not offered)")
+        self.layout = (FrameLayout("_nv12", (int(siting),)) if self.nv12 else
+                       FrameLayout("_packed", (self.channels, int(order))) if self.channels else FrameLayout())
+        create = getattr(lib(), "oflk_stabilizer_create" + self.layout.suffix)
+        check(create(ctypes.byref(self._h), int(device), int(H), int(W), *(self.layout.args or (int(bool(u8)),)), *tail))
         self.tracker = Tracker._borrowed(_vp(lib().oflk_stabilizer_tracker(self._h)), H, W, u8, max_corners)
 
     def close(self) -> None:
@@ -1393,9 +1471,7 @@ class Stabilizer:
         return np.uint8 if self.u8 else np.float32
 
     def _shape(self):
-        if self.nv12:
-            return (3 * self.H // 2, self.W)
-        return (self.H, self.W, self.channels) if self.channels else (self.H, self.W)
+        return self.layout.frame_shape(self.H, self.W)
 
     def push(self, frame: np.ndarray, inside: bool = False):
         """a contiguous host frame (H, W) -- (H, W, channels) for a colour stabiliser -- of the stabiliser's element type in;

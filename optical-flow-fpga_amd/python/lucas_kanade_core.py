@@ -37,6 +37,14 @@ def compute_gradients(
     return Ix, Iy, It
 
 
+def _pair(frame_prev, frame_curr):
+    """(prev, curr, u8): two raw 8-bit frames as they are (converted on the device: the values of .astype(np.float32) first),
+    anything else as float32"""
+    if _oflk.both_u8(frame_prev, frame_curr):
+        return np.ascontiguousarray(frame_prev), np.ascontiguousarray(frame_curr), True
+    return _oflk.as_f32(frame_prev), _oflk.as_f32(frame_curr), False
+
+
 def lucas_kanade_single_scale(
     frame_prev: npt.NDArray[np.float32],
     frame_curr: npt.NDArray[np.float32],
@@ -46,21 +54,12 @@ def lucas_kanade_single_scale(
 
     Replaces reference lucas_kanade_core.py:48-70 (oflk_single_scale).
     """
-    if _oflk.both_u8(frame_prev, frame_curr):
-        # raw 8-bit frames: converted on the device (same values as .astype(np.float32) first)
-        p, c = np.ascontiguousarray(frame_prev), np.ascontiguousarray(frame_curr)
-        H, W = _oflk.same_shape(p, c)
-        u = np.empty((H, W), np.float32)
-        v = np.empty((H, W), np.float32)
-        _oflk.check(_oflk.lib().oflk_single_scale_u8(p.ctypes.data, c.ctypes.data, 1, H, W, int(window_size),
-                                                     _oflk.ptr(u), _oflk.ptr(v)))
-        return u, v
-    p, c = _oflk.as_f32(frame_prev), _oflk.as_f32(frame_curr)
+    p, c, u8 = _pair(frame_prev, frame_curr)
     H, W = _oflk.same_shape(p, c)
     u = np.empty((H, W), np.float32)
     v = np.empty((H, W), np.float32)
-    _oflk.check(_oflk.lib().oflk_single_scale(_oflk.ptr(p), _oflk.ptr(c), H, W, int(window_size),
-                                              _oflk.ptr(u), _oflk.ptr(v)))
+    src, fn = _oflk.pixels(p, "oflk_single_scale")
+    _oflk.check(fn(src, _oflk.pix(c), *((1,) if u8 else ()), H, W, int(window_size), _oflk.ptr(u), _oflk.ptr(v)))
     return u, v
 
 
@@ -117,13 +116,11 @@ def corner_min_eigenvalue(frame_or_frames, window_size: int = 5) -> npt.NDArray[
     solve covers.  Returns float32 of the input's shape.  The arithmetic is stated in include/oflk.h.
     """
     _, _, _, win = _oflk.check_feature_params(1, 0.0, 0.0, window_size)
-    arr, u8 = _oflk.as_frames(frame_or_frames)
+    arr, _ = _oflk.as_frames(frame_or_frames)
     F, H, W = arr.shape
     S = np.empty((F, H, W), np.float32)
-    if u8:
-        _oflk.check(_oflk.lib().oflk_corner_score_host_u8(arr.ctypes.data, F, H, W, win, _oflk.ptr(S)))
-    else:
-        _oflk.check(_oflk.lib().oflk_corner_score_host(_oflk.ptr(arr), F, H, W, win, _oflk.ptr(S)))
+    src, fn = _oflk.pixels(arr, "oflk_corner_score_host")
+    _oflk.check(fn(src, F, H, W, win, _oflk.ptr(S)))
     return S[0] if np.ndim(frame_or_frames) == 2 else S
 
 
@@ -137,13 +134,12 @@ def good_features_to_track_batch(frames, max_corners: int, quality_level: float 
     score (F, K) float32, 0 beyond the count; count (F,) int32).
     """
     K, q, md, win = _oflk.check_feature_params(max_corners, quality_level, min_distance, window_size)
-    arr, u8 = _oflk.as_frames(frames)
+    arr, _ = _oflk.as_frames(frames)
     F, H, W = arr.shape
     count = np.empty(F, np.int32)
     xy = np.empty((F, K, 2), np.float32)
     score = np.empty((F, K), np.float32)
-    fn = _oflk.lib().oflk_good_features_host_u8 if u8 else _oflk.lib().oflk_good_features_host
-    src = arr.ctypes.data if u8 else _oflk.ptr(arr)
+    src, fn = _oflk.pixels(arr, "oflk_good_features_host")
     _oflk.check(fn(src, F, H, W, win, q, md, K, count.ctypes.data_as(_oflk._i32p), _oflk.ptr(xy), _oflk.ptr(score)))
     return xy, score, count
 
@@ -194,9 +190,8 @@ def replenish_features(frame, xy, visible, max_corners=None, quality_level: floa
     if max_corners is not None and int(max_corners) != K:
         raise ValueError(f"max_corners {max_corners!r} is not the number of slots {K}")
     K, q, md, win = _oflk.check_feature_params(K, quality_level, min_distance, window_size)
-    if isinstance(t, bool) or int(t) != t or int(t) < 0:
-        raise ValueError(f"t must be an integer >= 0, got {t!r}")
-    arr, u8 = _oflk.as_frames(frame)
+    _oflk.check_int("t", t, 0)
+    arr, _ = _oflk.as_frames(frame)
     _, H, W = arr.shape
     qt = np.full(K, -1, np.int32) if qt is None else np.array(qt, np.int32, copy=True, order="C")
     qxy = np.full((K, 2), np.nan, np.float32) if qxy is None else np.array(qxy, np.float32, copy=True, order="C")
@@ -204,8 +199,7 @@ def replenish_features(frame, xy, visible, max_corners=None, quality_level: floa
         raise ValueError(f"expected qt ({K},) and qxy ({K}, 2), got {qt.shape} and {qxy.shape}")
     born = np.empty(K, np.uint8)
     detected = np.zeros(1, np.int32)
-    fn = _oflk.lib().oflk_replenish_features_host_u8 if u8 else _oflk.lib().oflk_replenish_features_host
-    src = arr.ctypes.data if u8 else _oflk.ptr(arr)
+    src, fn = _oflk.pixels(arr, "oflk_replenish_features_host")
     _oflk.check(fn(src, H, W, win, q, md, K, int(t), _oflk.ptr(xy), vis.ctypes.data, qt.ctypes.data_as(_oflk._i32p),
                    _oflk.ptr(qxy), born.ctypes.data, detected.ctypes.data_as(_oflk._i32p)))
     return qt, qxy, born.astype(bool), int(detected[0])
@@ -258,9 +252,9 @@ def estimate_motion(src, dst, valid=None, model: str = "similarity", hypotheses:
     is in include/oflk.h; this call fits six coefficients (estimate_homography fits nine) and iterative re-estimation is not
     offered.
     """
-    code, hn, thr, sd = _oflk.check_motion_params(model, hypotheses, threshold, seed)
+    fit = _oflk.check_motion_params(model, hypotheses, threshold, seed)
     a, b, v, batched = _correspondences(src, dst, valid, step0)
-    return _motion(*_oflk.estimate_motion_host(a, b, v, code, hn, thr, sd, int(step0)), batched)
+    return _motion(*_oflk.estimate_motion_host(a, b, v, *fit, int(step0)), batched)
 
 
 def _correspondences(src, dst, valid, step0):
@@ -278,8 +272,7 @@ def _correspondences(src, dst, valid, step0):
         v = v if batched else v[None]
         if v.shape != a.shape[:2]:
             raise ValueError(f"valid must have shape {a.shape[:2] if batched else a.shape[1:2]}, got {np.shape(valid)}")
-    if isinstance(step0, bool) or int(step0) != step0 or not 0 <= int(step0) < 2 ** 31:
-        raise ValueError(f"step0 must be an integer in [0, 2^31), got {step0!r}")
+    _oflk.check_int("step0", step0, 0, 2 ** 31 - 1, "in [0, 2^31)")
     return a, b, v, batched
 
 
@@ -327,9 +320,9 @@ def estimate_homography(src, dst, valid=None, hypotheses: int = 256, threshold: 
     over its inliers by the normalised direct linear transform.  The same inputs give the same bytes.  The statement is in
     include/oflk.h.
     """
-    hn, thr, sd = _oflk.check_ransac_params(hypotheses, threshold, seed)
+    ransac = _oflk.check_ransac_params(hypotheses, threshold, seed)
     a, b, v, batched = _correspondences(src, dst, valid, step0)
-    out, inl, cnt = _oflk.estimate_homography_host(a, b, v, hn, thr, sd, int(step0))
+    out, inl, cnt = _oflk.estimate_homography_host(a, b, v, *ransac, int(step0))
     m = Homography(out.reshape(-1, 3, 3), inl.astype(bool), cnt[:, 0].copy(), cnt[:, 1].copy(), cnt[:, 2].copy())
     return m if batched else Homography(m.model[0], m.inlier[0], int(m.n_inliers[0]), int(m.n_valid[0]), int(m.status[0]))
 
@@ -360,7 +353,7 @@ def stabilize_trajectory(models, status=None, radius: int = 15, sigma=None) -> T
     the window is always symmetric, so the first and last frame are never moved and a uniform camera motion is left alone.
     The same inputs give the same bytes; the statement is in include/oflk.h.
     """
-    w = _oflk.stabilize_weights(radius, sigma)
+    w = _oflk.check_window(radius, sigma).weights
     m = np.ascontiguousarray(models, np.float32)
     if m.ndim == 3 and m.shape[1:] == (2, 3):
         m = m.reshape(-1, 6)
@@ -392,16 +385,31 @@ def rgb_to_luma(frames, order: str = "rgb"):
     return out[0] if single else out
 
 
-def _warp_packed(frames, maps, return_inside: bool, n: int):
-    """warp_affine (n = 6) / warp_perspective (n = 9) of a 4-D array: interleaved colour frames"""
-    arr = _oflk.as_packed(frames)
-    F = arr.shape[0]
+def _maps(maps, F: int, n: int) -> np.ndarray:
+    """F affine (n = 6: (2, 3) or (6,) each) or perspective (n = 9: (3, 3) or (9,)) maps as one contiguous float64 (F, n) array;
+    ValueError for any other shape"""
     m = np.ascontiguousarray(maps, np.float64)
-    rows = (3, 6) if n == 6 else (3, 9)
-    if m.size != n * F or m.ndim not in (1, 2, 3) or m.shape[-1] not in rows or (n == 9 and m.shape[-1] == 3 and (m.ndim < 2 or m.shape[-2] != 3)):
+    if m.size != n * F or m.ndim not in (1, 2, 3) or m.shape[-1] not in (3, n) or (n == 9 and m.shape[-1] == 3 and (m.ndim < 2 or m.shape[-2] != 3)):
         raise ValueError(f"expected {F} maps of shape {(2, 3) if n == 6 else (3, 3)} or ({n},), got {np.shape(maps)}")
-    out, ins = _oflk.warp_packed_host(arr, m.reshape(F, n), bool(return_inside))
-    return (out, ins.astype(bool)) if return_inside else out
+    return m.reshape(F, n)
+
+
+def _warp(frames, maps, return_inside: bool, n: int):
+    """warp_affine (n = 6) / warp_perspective (n = 9): a 4-D array is interleaved colour frames"""
+    if _oflk.is_packed(frames):
+        arr = _oflk.as_packed(frames)
+        out, ins = _oflk.warp_packed_host(arr, _maps(maps, arr.shape[0], n), bool(return_inside))
+        return (out, ins.astype(bool)) if return_inside else out
+    single = isinstance(frames, np.ndarray) and frames.ndim == 2
+    arr, _ = _oflk.as_frames(frames)
+    F, H, W = arr.shape
+    if H < 2 or W < 2:
+        raise ValueError(f"frames must be at least 2 x 2, got {H} x {W}")
+    out, ins = _oflk.warp_affine_host(arr, _maps(maps, F, n), bool(return_inside))
+    out = out[0] if single else out
+    if not return_inside:
+        return out
+    return out, (ins[0] if single else ins).astype(bool)
 
 
 def warp_affine(frames, maps, return_inside: bool = False):
@@ -414,21 +422,7 @@ def warp_affine(frames, maps, return_inside: bool = False):
     per pixel and every channel is sampled there, each channel's bytes being those of this call on its plane; the result has
     the same shape and the mask stays (F, H, W).  A 3-D array keeps meaning (F, H, W) grey frames, so one colour frame is
     passed as frame[None]; float32 colour is refused."""
-    if _oflk.is_packed(frames):
-        return _warp_packed(frames, maps, return_inside, 6)
-    single = isinstance(frames, np.ndarray) and frames.ndim == 2
-    arr, _ = _oflk.as_frames(frames)
-    F, H, W = arr.shape
-    if H < 2 or W < 2:
-        raise ValueError(f"frames must be at least 2 x 2, got {H} x {W}")
-    m = np.ascontiguousarray(maps, np.float64)
-    if m.size != 6 * F or m.ndim not in (1, 2, 3) or m.shape[-1] not in (3, 6):
-        raise ValueError(f"expected {F} maps of shape (2, 3) or (6,), got {np.shape(maps)}")
-    out, ins = _oflk.warp_affine_host(arr, m.reshape(F, 6), bool(return_inside))
-    out = out[0] if single else out
-    if not return_inside:
-        return out
-    return out, (ins[0] if single else ins).astype(bool)
+    return _warp(frames, maps, return_inside, 6)
 
 
 def warp_perspective(frames, maps, return_inside: bool = False):
@@ -441,21 +435,7 @@ def warp_perspective(frames, maps, return_inside: bool = False):
 
     A 4-D uint8 array (F, H, W, C), C = 3 or 4, is a batch of interleaved colour frames, as in warp_affine: the same shape
     comes back, the mask stays (F, H, W), a 3-D array keeps meaning (F, H, W) grey frames and float32 colour is refused."""
-    if _oflk.is_packed(frames):
-        return _warp_packed(frames, maps, return_inside, 9)
-    single = isinstance(frames, np.ndarray) and frames.ndim == 2
-    arr, _ = _oflk.as_frames(frames)
-    F, H, W = arr.shape
-    if H < 2 or W < 2:
-        raise ValueError(f"frames must be at least 2 x 2, got {H} x {W}")
-    m = np.ascontiguousarray(maps, np.float64)
-    if m.size != 9 * F or m.ndim not in (1, 2, 3) or m.shape[-1] not in (3, 9) or (m.shape[-1] == 3 and (m.ndim < 2 or m.shape[-2] != 3)):
-        raise ValueError(f"expected {F} maps of shape (3, 3) or (9,), got {np.shape(maps)}")
-    out, ins = _oflk.warp_affine_host(arr, m.reshape(F, 9), bool(return_inside))
-    out = out[0] if single else out
-    if not return_inside:
-        return out
-    return out, (ins[0] if single else ins).astype(bool)
+    return _warp(frames, maps, return_inside, 9)
 
 
 class MosaicChain(NamedTuple):
@@ -489,8 +469,7 @@ def mosaic_chain(model, status, shape, anchor: int = 0, extent=None) -> MosaicCh
             raise ValueError(f"expected models of shape (T-1, 3, 3) or (T-1, 9), got {np.shape(model)}")
         m = m.reshape(0, 9)
     S = m.shape[0]
-    if isinstance(anchor, bool) or int(anchor) != anchor or not 0 <= int(anchor) <= S:
-        raise ValueError(f"anchor must be an integer in [0, {S}], got {anchor!r}")
+    _oflk.check_int("anchor", anchor, 0, S)
     extent = 8.0 * max(H, W) if extent is None else float(extent)
     if not (np.isfinite(extent) and extent > 0):
         raise ValueError(f"extent must be finite and > 0, got {extent!r}")
@@ -516,8 +495,7 @@ def exposure_chain(gain, bias, status=None, anchor: int = 0) -> np.ndarray:
     if g.shape != b.shape:
         raise ValueError(f"gain and bias must have one shape, got {np.shape(gain)} and {np.shape(bias)}")
     S = g.size
-    if isinstance(anchor, bool) or int(anchor) != anchor or not 0 <= int(anchor) <= S:
-        raise ValueError(f"anchor must be an integer in [0, {S}], got {anchor!r}")
+    _oflk.check_int("anchor", anchor, 0, S)
     st = None
     if status is not None:
         st = np.asarray(status)
@@ -560,9 +538,7 @@ def mosaic_composite(frames, maps, canvas_shape, origin=(0, 0), skip=None, blend
         raise ValueError(f"a canvas of 2^30 pixels or more is not supported, got {Hc} x {Wc}")
     if len(origin) != 2 or any(isinstance(v, bool) or int(v) != v or abs(int(v)) >= 2 ** 31 for v in origin):
         raise ValueError(f"origin must be two integers (x0, y0), got {origin!r}")
-    m = np.ascontiguousarray(maps, np.float64)
-    if m.size != 9 * F or m.ndim not in (1, 2, 3) or m.shape[-1] not in (3, 9) or (m.shape[-1] == 3 and (m.ndim < 2 or m.shape[-2] != 3)):
-        raise ValueError(f"expected {F} maps of shape (3, 3) or (9,), got {np.shape(maps)}")
+    m = _maps(maps, F, 9)
     sk = None
     if skip is not None:
         sk = np.asarray(skip)
@@ -574,7 +550,7 @@ def mosaic_composite(frames, maps, canvas_shape, origin=(0, 0), skip=None, blend
         ex = np.ascontiguousarray(exposure, np.float64)
         if ex.shape != (F, 2):
             raise ValueError(f"exposure must have shape {(F, 2)}, got {ex.shape}")
-    out, cnt = _oflk.mosaic_composite_host(arr, m.reshape(F, 9), sk, int(origin[0]), int(origin[1]), Hc, Wc, code, bool(return_count),
+    out, cnt = _oflk.mosaic_composite_host(arr, m, sk, int(origin[0]), int(origin[1]), Hc, Wc, code, bool(return_count),
                                            ex)
     return (out, cnt) if return_count else out
 
@@ -620,18 +596,22 @@ def _align_models(model, status, S: int, kind: str):
     return m.reshape(S, nc), st
 
 
-def _alignment(out, st, stats, kind: str, single: bool, photo=None):
-    out = out.reshape((-1, 3, 3) if kind == "homography" else (-1, 2, 3))
+def _alignment(result, out, st, stats, photo, kind: str, single: bool):
+    """the `result` record (Alignment; with photo, PhotometricAlignment or RobustAlignment) of a host alignment call's arrays"""
+    fields = (out.reshape((-1, 3, 3) if kind == "homography" else (-1, 2, 3)), st, stats)
     if photo is not None:
-        g, b = np.ascontiguousarray(photo[:, 0]), np.ascontiguousarray(photo[:, 1])
-        return PhotometricAlignment(out[0], int(st[0]), stats[0], g[0], b[0]) if single else PhotometricAlignment(out, st, stats, g, b)
-    return Alignment(out[0], int(st[0]), stats[0]) if single else Alignment(out, st, stats)
+        fields += (np.ascontiguousarray(photo[:, 0]), np.ascontiguousarray(photo[:, 1]))
+    return result(fields[0][0], int(st[0]), *(f[0] for f in fields[2:])) if single else result(*fields)
 
 
-def _robust_alignment(out, st, stats, photo, kind: str, single: bool):
-    out = out.reshape((-1, 3, 3) if kind == "homography" else (-1, 2, 3))
-    g, b = np.ascontiguousarray(photo[:, 0]), np.ascontiguousarray(photo[:, 1])
-    return RobustAlignment(out[0], int(st[0]), stats[0], g[0], b[0]) if single else RobustAlignment(out, st, stats, g, b)
+def _refine(a, b, m, st, kind: str, settings, delta, photometric: bool, single: bool):
+    """refine_alignment's (b given) and sequence_refine_alignment's (b None) call, once their arguments are checked"""
+    code, L, n, ms = settings
+    if delta is not None:
+        return _alignment(RobustAlignment, *_oflk.align_robust_host(a, b, m, st, L, n, code, ms, delta, bool(photometric)), kind, single)
+    if photometric:
+        return _alignment(PhotometricAlignment, *_oflk.align_host(a, b, m, st, L, n, code, ms, True), kind, single)
+    return _alignment(Alignment, *_oflk.align_host(a, b, m, st, L, n, code, ms), None, kind, single)
 
 
 def refine_alignment(a, b, model, status=None, kind: str = "homography", levels: int = 3, iterations: int = 5,
@@ -656,7 +636,7 @@ def refine_alignment(a, b, model, status=None, kind: str = "homography", levels:
     under the refined model, is how to tune it: near 1.0 nothing is down-weighted, far below it the threshold cuts into the
     static scene.  alignment_weights gives the per-pixel map.
     """
-    code, L, n, ms = _oflk.check_align_params(kind, levels, iterations, min_share)
+    settings = _oflk.check_align_params(kind, levels, iterations, min_share)
     delta = None if robust_delta is None else _oflk.check_robust_delta(robust_delta)
     single = isinstance(a, np.ndarray) and a.ndim == 2
     fa, ua = _oflk.as_frames(a)
@@ -664,12 +644,7 @@ def refine_alignment(a, b, model, status=None, kind: str = "homography", levels:
     if fa.shape != fb.shape or ua != ub:
         raise ValueError(f"a and b must have one shape and type, got {fa.shape} {fa.dtype} and {fb.shape} {fb.dtype}")
     m, st = _align_models(model, status, fa.shape[0], kind)
-    if delta is not None:
-        return _robust_alignment(*_oflk.align_robust_host(fa, fb, m, st, L, n, code, ms, delta, bool(photometric)), kind, single)
-    if photometric:
-        out, so, stats, photo = _oflk.align_host(fa, fb, m, st, L, n, code, ms, True)
-        return _alignment(out, so, stats, kind, single, photo)
-    return _alignment(*_oflk.align_host(fa, fb, m, st, L, n, code, ms), kind, single)
+    return _refine(fa, fb, m, st, kind, settings, delta, photometric, single)
 
 
 def sequence_refine_alignment(frames, model, status=None, kind: str = "homography", levels: int = 3, iterations: int = 5,
@@ -677,18 +652,13 @@ def sequence_refine_alignment(frames, model, status=None, kind: str = "homograph
     """refine_alignment on the T-1 steps t -> t+1 of frames (T, H, W): model[t] (e.g. of tracks_homography or tracks_motion)
     maps frame t's coordinates to frame t+1's.  Every frame's pyramid is built once.  Returns a batched Alignment, or with
     photometric=True a batched PhotometricAlignment, or with robust_delta given (refine_alignment) a batched RobustAlignment."""
-    code, L, n, ms = _oflk.check_align_params(kind, levels, iterations, min_share)
+    settings = _oflk.check_align_params(kind, levels, iterations, min_share)
     delta = None if robust_delta is None else _oflk.check_robust_delta(robust_delta)
     arr, _ = _oflk.as_frames(frames)
     if arr.shape[0] < 2:
         raise ValueError(f"a sequence needs at least two frames, got {arr.shape[0]}")
     m, st = _align_models(model, status, arr.shape[0] - 1, kind)
-    if delta is not None:
-        return _robust_alignment(*_oflk.align_robust_host(arr, None, m, st, L, n, code, ms, delta, bool(photometric)), kind, False)
-    if photometric:
-        out, so, stats, photo = _oflk.align_host(arr, None, m, st, L, n, code, ms, True)
-        return _alignment(out, so, stats, kind, False, photo)
-    return _alignment(*_oflk.align_host(arr, None, m, st, L, n, code, ms), kind, False)
+    return _refine(arr, None, m, st, kind, settings, delta, photometric, False)
 
 
 def alignment_weights(a, b, model, kind: str = "homography", robust_delta: float = 4.0, gain=None, bias=None):

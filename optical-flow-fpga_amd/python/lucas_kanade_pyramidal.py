@@ -24,13 +24,13 @@ import argparse
 import ctypes
 import os
 from pathlib import Path
-from typing import List, NamedTuple, Optional, Tuple
+from typing import Callable, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import numpy.typing as npt
 
 import _oflk
-from lucas_kanade_core import (Alignment, Homography, MosaicChain, Motion, PhotometricAlignment, Trajectory,  # noqa: F401
+from lucas_kanade_core import (_maps, _pair, Alignment, Homography, MosaicChain, Motion, PhotometricAlignment, Trajectory,  # noqa: F401
                                estimate_homography, estimate_motion, exposure_chain, lucas_kanade_single_scale, mosaic_chain,
                                mosaic_composite, refine_alignment, alignment_weights,
                                rgb_to_luma, sequence_refine_alignment, stabilize_trajectory, tracks_homography, tracks_motion, warp_affine,
@@ -131,23 +131,13 @@ def lucas_kanade_pyramidal_with_log(
     """
     log = np.zeros((max(num_levels, 1), max(num_iterations, 1), 2), np.float32)
     runs = np.zeros(max(num_levels, 1), np.int32)
-    if _oflk.both_u8(frame_prev, frame_curr):
-        # raw 8-bit frames: converted on the device (same values as .astype(np.float32) first)
-        p, c = np.ascontiguousarray(frame_prev), np.ascontiguousarray(frame_curr)
-        H, W = _oflk.same_shape(p, c)
-        u = np.empty((H, W), np.float32)
-        v = np.empty((H, W), np.float32)
-        _oflk.check(_oflk.lib().oflk_pyramidal_u8(p.ctypes.data, c.ctypes.data, 1, H, W, int(num_levels),
-                                                  int(window_size), int(num_iterations), _oflk.ptr(u),
-                                                  _oflk.ptr(v), _oflk.ptr(log), runs.ctypes.data_as(_i32p)))
-        return u, v, log, runs
-    p, c = _oflk.as_f32(frame_prev), _oflk.as_f32(frame_curr)
+    p, c, u8 = _pair(frame_prev, frame_curr)
     H, W = _oflk.same_shape(p, c)
     u = np.empty((H, W), np.float32)
     v = np.empty((H, W), np.float32)
-    _oflk.check(_oflk.lib().oflk_pyramidal(_oflk.ptr(p), _oflk.ptr(c), H, W, int(num_levels),
-                                           int(window_size), int(num_iterations), _oflk.ptr(u),
-                                           _oflk.ptr(v), _oflk.ptr(log), runs.ctypes.data_as(_i32p)))
+    src, fn = _oflk.pixels(p, "oflk_pyramidal")
+    _oflk.check(fn(src, _oflk.pix(c), *((1,) if u8 else ()), H, W, int(num_levels), int(window_size), int(num_iterations),
+                   _oflk.ptr(u), _oflk.ptr(v), _oflk.ptr(log), runs.ctypes.data_as(_i32p)))
     return u, v, log, runs
 
 
@@ -200,20 +190,15 @@ def lucas_kanade_pyramidal_sequence_with_log(frames, num_levels: int = 3, window
     as lucas_kanade_pyramidal_with_log gives them.  Every flow equals that of the pair (frames[t], frames[t+1]); the
     library uploads each frame once and builds its pyramid once.  The reference has no sequence function: nothing is printed.
     """
-    arr, u8 = _oflk.as_sequence(frames)
+    arr, _ = _oflk.as_sequence(frames)
     T, H, W = arr.shape
     log = np.zeros((T - 1, max(num_levels, 1), max(num_iterations, 1), 2), np.float32)
     runs = np.zeros((T - 1, max(num_levels, 1)), np.int32)
     u = np.empty((T - 1, H, W), np.float32)
     v = np.empty((T - 1, H, W), np.float32)
-    if u8:
-        _oflk.check(_oflk.lib().oflk_pyramidal_sequence_u8(arr.ctypes.data, T, H, W, int(num_levels), int(window_size),
-                                                           int(num_iterations), _oflk.ptr(u), _oflk.ptr(v), _oflk.ptr(log),
-                                                           runs.ctypes.data_as(_i32p)))
-    else:
-        _oflk.check(_oflk.lib().oflk_pyramidal_sequence(_oflk.ptr(arr), T, H, W, int(num_levels), int(window_size),
-                                                        int(num_iterations), _oflk.ptr(u), _oflk.ptr(v), _oflk.ptr(log),
-                                                        runs.ctypes.data_as(_i32p)))
+    src, fn = _oflk.pixels(arr, "oflk_pyramidal_sequence")
+    _oflk.check(fn(src, T, H, W, int(num_levels), int(window_size), int(num_iterations), _oflk.ptr(u), _oflk.ptr(v), _oflk.ptr(log),
+                   runs.ctypes.data_as(_i32p)))
     return u, v, log, runs
 
 
@@ -247,12 +232,11 @@ def lucas_kanade_pyramidal_sequence_fb(frames, num_levels: int = 3, window_size:
     is the same with F and G exchanged.  Each frame is uploaded once and its pyramid built once for both directions.
     """
     a, b = _oflk.check_fb_params(alpha, beta)
-    arr, u8 = _oflk.as_sequence(frames)
+    arr, _ = _oflk.as_sequence(frames)
     T, H, W = arr.shape
     out = [np.empty((T - 1, H, W), np.float32) for _ in range(6)]
     valid = [np.empty((T - 1, H, W), np.uint8) for _ in range(2)]
-    fn = _oflk.lib().oflk_pyramidal_sequence_fb_u8 if u8 else _oflk.lib().oflk_pyramidal_sequence_fb
-    src = arr.ctypes.data if u8 else _oflk.ptr(arr)
+    src, fn = _oflk.pixels(arr, "oflk_pyramidal_sequence_fb")
     _oflk.check(fn(src, T, H, W, int(num_levels), int(window_size), int(num_iterations), a, b,
                    *(_oflk.ptr(o) for o in out), valid[0].ctypes.data, valid[1].ctypes.data))
     return SequenceFB(*out[:4], out[4], out[5], valid[0].astype(bool), valid[1].astype(bool))
@@ -275,13 +259,12 @@ def lucas_kanade_pyramidal_sequence_tracks(frames, queries, num_levels: int = 3,
     starts.  The flows stay on the device: only the tracks come back.
     """
     a, b = _oflk.check_fb_params(alpha, beta)
-    arr, u8 = _oflk.as_sequence(frames)
+    arr, _ = _oflk.as_sequence(frames)
     T, H, W = arr.shape
     qt, qxy = _oflk.as_queries(queries, T)
     N = qxy.shape[0]
     tracks, visible = np.empty((T, N, 2), np.float32), np.empty((T, N), np.uint8)
-    fn = _oflk.lib().oflk_pyramidal_sequence_tracks_u8 if u8 else _oflk.lib().oflk_pyramidal_sequence_tracks
-    src = arr.ctypes.data if u8 else _oflk.ptr(arr)
+    src, fn = _oflk.pixels(arr, "oflk_pyramidal_sequence_tracks")
     _oflk.check(fn(src, T, H, W, int(num_levels), int(window_size), int(num_iterations), a, b,
                    None if qt is None else qt.ctypes.data_as(_oflk._i32p), _oflk.ptr(qxy), N, _oflk.ptr(tracks),
                    visible.ctypes.data))
@@ -305,13 +288,12 @@ def lucas_kanade_pyramidal_sequence_klt(frames, max_corners: int, quality_level:
     """
     a, b = _oflk.check_fb_params(alpha, beta)
     K, q, md, win = _oflk.check_feature_params(max_corners, quality_level, min_distance, window_size)
-    arr, u8 = _oflk.as_sequence(frames)
+    arr, _ = _oflk.as_sequence(frames)
     T, H, W = arr.shape
     count = np.zeros(1, np.int32)
     xy, score = np.empty((K, 2), np.float32), np.empty(K, np.float32)
     tracks, visible = np.empty((T, K, 2), np.float32), np.empty((T, K), np.uint8)
-    fn = _oflk.lib().oflk_pyramidal_sequence_klt_u8 if u8 else _oflk.lib().oflk_pyramidal_sequence_klt
-    src = arr.ctypes.data if u8 else _oflk.ptr(arr)
+    src, fn = _oflk.pixels(arr, "oflk_pyramidal_sequence_klt")
     _oflk.check(fn(src, T, H, W, int(num_levels), win, int(num_iterations), a, b, q, md, K, count.ctypes.data_as(_oflk._i32p),
                    _oflk.ptr(xy), _oflk.ptr(score), _oflk.ptr(tracks), visible.ctypes.data))
     n = int(count[0])
@@ -327,9 +309,7 @@ def lucas_kanade_sparse(frame_prev, frame_curr, points, num_levels: int = 3, win
     N * window_size^2 * num_levels * num_iterations, and no flow field exists anywhere.  status is False where the last
     2x2 system had no solution or the point left the frame; a point outside the frame gives NaN.  Both frames uint8: the
     uint8 path."""
-    u8 = _oflk.both_u8(frame_prev, frame_curr)
-    p, c = (np.ascontiguousarray(frame_prev), np.ascontiguousarray(frame_curr)) if u8 else (_oflk.as_f32(frame_prev),
-                                                                                            _oflk.as_f32(frame_curr))
+    p, c, _ = _pair(frame_prev, frame_curr)
     H, W = _oflk.same_shape(p, c)
     L, win, K, _ = _oflk.check_sparse_params((H, W), num_levels, window_size, num_iterations)
     pts = np.asarray(points)
@@ -338,12 +318,8 @@ def lucas_kanade_sparse(frame_prev, frame_curr, points, num_levels: int = 3, win
     pts = np.ascontiguousarray(pts, np.float32)
     N = pts.shape[0]
     nxt, status, res = np.empty((N, 2), np.float32), np.empty(N, np.uint8), np.empty(N, np.float32)
-    if u8:
-        _oflk.check(_oflk.lib().oflk_sparse_lk_u8(p.ctypes.data, c.ctypes.data, H, W, L, win, K, _oflk.ptr(pts), N, _oflk.ptr(nxt),
-                                                  status.ctypes.data, _oflk.ptr(res)))
-    else:
-        _oflk.check(_oflk.lib().oflk_sparse_lk(_oflk.ptr(p), _oflk.ptr(c), H, W, L, win, K, _oflk.ptr(pts), N, _oflk.ptr(nxt),
-                                               status.ctypes.data, _oflk.ptr(res)))
+    src, fn = _oflk.pixels(p, "oflk_sparse_lk")
+    _oflk.check(fn(src, _oflk.pix(c), H, W, L, win, K, _oflk.ptr(pts), N, _oflk.ptr(nxt), status.ctypes.data, _oflk.ptr(res)))
     return nxt, status.astype(bool), res
 
 
@@ -356,17 +332,26 @@ def lucas_kanade_pyramidal_sequence_sparse_tracks(frames, queries, num_levels: i
     No dense flow is computed: only frames go up and rows come down.  frames, queries and the result as
     lucas_kanade_pyramidal_sequence_tracks."""
     a, b = _oflk.check_fb_params(alpha, beta)
-    arr, u8 = _oflk.as_sequence(frames)
+    arr, _ = _oflk.as_sequence(frames)
     T, H, W = arr.shape
     L, win, K, r = _oflk.check_sparse_params((H, W), num_levels, window_size, num_iterations, max_residual)
     qt, qxy = _oflk.as_queries(queries, T)
     N = qxy.shape[0]
     tracks, visible = np.empty((T, N, 2), np.float32), np.empty((T, N), np.uint8)
-    fn = _oflk.lib().oflk_pyramidal_sequence_sparse_tracks_u8 if u8 else _oflk.lib().oflk_pyramidal_sequence_sparse_tracks
-    src = arr.ctypes.data if u8 else _oflk.ptr(arr)
+    src, fn = _oflk.pixels(arr, "oflk_pyramidal_sequence_sparse_tracks")
     _oflk.check(fn(src, T, H, W, L, win, K, a, b, r, None if qt is None else qt.ctypes.data_as(_oflk._i32p), _oflk.ptr(qxy), N,
                    _oflk.ptr(tracks), visible.ctypes.data))
     return SequenceTracks(tracks, visible.astype(bool))
+
+
+def _tracking(frames, num_levels, window_size, num_iterations, alpha, beta, max_residual, max_corners, quality_level, min_distance,
+              detect_every=None):
+    """(the frames of a sequence as as_sequence gives them, their checked _oflk.Tracking), refused in the sparse sequence
+    calls' order: alpha and beta, the frames, then check_tracking's"""
+    _oflk.check_fb_params(alpha, beta)
+    arr, _ = _oflk.as_sequence(frames)
+    return arr, _oflk.check_tracking(arr.shape[1:], num_levels, window_size, num_iterations, alpha, beta, max_residual, max_corners,
+                                     quality_level, min_distance, detect_every)
 
 
 def lucas_kanade_pyramidal_sequence_klt_sparse(frames, max_corners: int, quality_level: float = 0.01, min_distance: float = 10.0,
@@ -375,18 +360,15 @@ def lucas_kanade_pyramidal_sequence_klt_sparse(frames, max_corners: int, quality
     """Detect, then track, sparsely: good_features_to_track on frame 0 (the LK window is the detection window), then
     lucas_kanade_pyramidal_sequence_sparse_tracks on those points, in one call: the features are born on the device,
     straight into the tracker's query buffer.  Result as lucas_kanade_pyramidal_sequence_klt."""
-    a, b = _oflk.check_fb_params(alpha, beta)
-    arr, u8 = _oflk.as_sequence(frames)
-    T, H, W = arr.shape
-    L, win, it, r = _oflk.check_sparse_params((H, W), num_levels, window_size, num_iterations, max_residual)
-    K, q, md, win = _oflk.check_feature_params(max_corners, quality_level, min_distance, win)
+    arr, trk = _tracking(frames, num_levels, window_size, num_iterations, alpha, beta, max_residual, max_corners, quality_level,
+                         min_distance)
+    (T, H, W), K = arr.shape, trk.max_corners
     count = np.zeros(1, np.int32)
     xy, score = np.empty((K, 2), np.float32), np.empty(K, np.float32)
     tracks, visible = np.empty((T, K, 2), np.float32), np.empty((T, K), np.uint8)
-    fn = _oflk.lib().oflk_pyramidal_sequence_klt_sparse_u8 if u8 else _oflk.lib().oflk_pyramidal_sequence_klt_sparse
-    src = arr.ctypes.data if u8 else _oflk.ptr(arr)
-    _oflk.check(fn(src, T, H, W, L, win, it, a, b, r, q, md, K, count.ctypes.data_as(_oflk._i32p), _oflk.ptr(xy),
-                   _oflk.ptr(score), _oflk.ptr(tracks), visible.ctypes.data))
+    src, fn = _oflk.pixels(arr, "oflk_pyramidal_sequence_klt_sparse")
+    _oflk.check(fn(src, T, H, W, *trk.klt, count.ctypes.data_as(_oflk._i32p), _oflk.ptr(xy), _oflk.ptr(score), _oflk.ptr(tracks),
+                   visible.ctypes.data))
     n = int(count[0])
     return SequenceKLT(xy[:n], tracks[:, :n], visible[:, :n].astype(bool))
 
@@ -412,16 +394,14 @@ def lucas_kanade_pyramidal_sequence_klt_replenish(frames, max_corners: int, dete
     """
     a, b = _oflk.check_fb_params(alpha, beta)
     K, q, md, win = _oflk.check_feature_params(max_corners, quality_level, min_distance, window_size)
-    if isinstance(detect_every, bool) or int(detect_every) != detect_every or int(detect_every) < 1:
-        raise ValueError(f"detect_every must be an integer >= 1, got {detect_every!r}")
-    arr, u8 = _oflk.as_sequence(frames)
+    every = _oflk.check_detect_every(detect_every)
+    arr, _ = _oflk.as_sequence(frames)
     T, H, W = arr.shape
     tracks, visible = np.empty((T, K, 2), np.float32), np.empty((T, K), np.uint8)
     born, detected = np.empty((T, K), np.uint8), np.empty(T, np.int32)
-    fn = _oflk.lib().oflk_pyramidal_sequence_klt_replenish_u8 if u8 else _oflk.lib().oflk_pyramidal_sequence_klt_replenish
-    src = arr.ctypes.data if u8 else _oflk.ptr(arr)
-    _oflk.check(fn(src, T, H, W, int(num_levels), win, int(num_iterations), a, b, q, md, K, min(int(detect_every), 2 ** 31 - 1),
-                   _oflk.ptr(tracks), visible.ctypes.data, born.ctypes.data, detected.ctypes.data_as(_oflk._i32p)))
+    src, fn = _oflk.pixels(arr, "oflk_pyramidal_sequence_klt_replenish")
+    _oflk.check(fn(src, T, H, W, int(num_levels), win, int(num_iterations), a, b, q, md, K, every, _oflk.ptr(tracks),
+                   visible.ctypes.data, born.ctypes.data, detected.ctypes.data_as(_oflk._i32p)))
     return SequenceKLTReplenish(tracks, visible.astype(bool), born.astype(bool), detected)
 
 
@@ -445,21 +425,15 @@ def lucas_kanade_pyramidal_sequence_klt_sparse_replenish(frames, max_corners: in
     absolute window difference (what max_residual is compared with) for every slot that was alive on frame t-1 and whose
     forward step succeeded, also where the track ends on that step; NaN elsewhere.  lucas_kanade_core.split_tracks(visible,
     born) lists the tracks.  Frames go up; the rows come down."""
-    a, b = _oflk.check_fb_params(alpha, beta)
-    arr, u8 = _oflk.as_sequence(frames)
-    T, H, W = arr.shape
-    L, win, it, r = _oflk.check_sparse_params((H, W), num_levels, window_size, num_iterations, max_residual)
-    K, q, md, win = _oflk.check_feature_params(max_corners, quality_level, min_distance, win)
-    if isinstance(detect_every, bool) or int(detect_every) != detect_every or int(detect_every) < 1:
-        raise ValueError(f"detect_every must be an integer >= 1, got {detect_every!r}")
+    arr, trk = _tracking(frames, num_levels, window_size, num_iterations, alpha, beta, max_residual, max_corners, quality_level,
+                         min_distance, detect_every)
+    (T, H, W), K = arr.shape, trk.max_corners
     tracks, visible = np.empty((T, K, 2), np.float32), np.empty((T, K), np.uint8)
     born, detected = np.empty((T, K), np.uint8), np.empty(T, np.int32)
     residual = np.empty((T, K), np.float32)
-    fn = (_oflk.lib().oflk_pyramidal_sequence_klt_sparse_replenish_u8 if u8
-          else _oflk.lib().oflk_pyramidal_sequence_klt_sparse_replenish)
-    src = arr.ctypes.data if u8 else _oflk.ptr(arr)
-    _oflk.check(fn(src, T, H, W, L, win, it, a, b, r, q, md, K, min(int(detect_every), 2 ** 31 - 1), _oflk.ptr(tracks),
-                   visible.ctypes.data, born.ctypes.data, detected.ctypes.data_as(_oflk._i32p), _oflk.ptr(residual)))
+    src, fn = _oflk.pixels(arr, "oflk_pyramidal_sequence_klt_sparse_replenish")
+    _oflk.check(fn(src, T, H, W, *trk, _oflk.ptr(tracks), visible.ctypes.data, born.ctypes.data, detected.ctypes.data_as(_oflk._i32p),
+                   _oflk.ptr(residual)))
     return SequenceKLTSparseReplenish(tracks, visible.astype(bool), born.astype(bool), detected, residual)
 
 
@@ -498,55 +472,62 @@ def lucas_kanade_pyramidal_sequence_stabilize(frames, max_corners: int, detect_e
     says: the motion is tracked, fitted and (with refine_iterations) refined on rgb_to_luma of the frames, exactly as this
     call does on that luma, and the colour frames are warped under the maps of that trajectory, every channel at one source
     position; .frames then has the input's shape."""
-    if isinstance(refine_iterations, bool) or int(refine_iterations) != refine_iterations or int(refine_iterations) < 0:
-        raise ValueError(f"refine_iterations must be an integer >= 0, got {refine_iterations!r}")
-    if refine_photometric and int(refine_iterations) == 0:
-        raise ValueError("refine_photometric needs refine_iterations > 0")
-    if refine_robust_delta is not None and int(refine_iterations) == 0:
-        raise ValueError("refine_robust_delta needs refine_iterations > 0")
-    colour = _oflk.is_packed(frames)
+    refine = _oflk.check_refine(refine_iterations, refine_photometric, refine_robust_delta)
     code_order = _oflk.check_colour_order(order)
-    if colour:
+    if _oflk.is_packed(frames):
         packed = _oflk.as_packed(frames, "(T, H, W, C)")
-    if int(refine_iterations) > 0:
-        grey = rgb_to_luma(packed, order) if colour else frames
+        video = _Video(lambda: (packed,) + packed.shape[1:3], _oflk.FrameLayout("_packed", (packed.shape[3], code_order)),
+                       lambda: rgb_to_luma(packed, order), lambda grey, maps: warp_affine(packed, maps))
+    else:
+        def grey_frames():
+            arr, _ = _oflk.as_sequence(frames)
+            return (arr,) + arr.shape[1:]
+        video = _Video(grey_frames, _oflk.FrameLayout(), lambda: frames, warp_affine)
+    return _sequence_stabilize(video, max_corners, detect_every, model, radius, sigma, hypotheses, threshold, seed, quality_level,
+                               min_distance, num_levels, window_size, num_iterations, alpha, beta, max_residual, refine, refine_levels,
+                               refine_photometric, refine_robust_delta)
+
+
+class _Video(NamedTuple):
+    """What differs between the grey, the interleaved colour and the NV12 form of the sequence stabiliser"""
+    frames: Callable    # () -> (the contiguous frames as the C call takes them, H, W); called once alpha and beta are checked
+    layout: "_oflk.FrameLayout"   # names the form of oflk_stabilize_sequence* and holds its arguments behind H, W
+    luma: Callable      # () -> the grey frames that the refine chain tracks, fits and refines on
+    warp: Callable      # (those grey frames as an array, maps (T, 2, 3)) -> the refined path's steadied frames
+
+
+def _sequence_stabilize(video: _Video, max_corners, detect_every, model, radius, sigma, hypotheses, threshold, seed, quality_level,
+                        min_distance, num_levels, window_size, num_iterations, alpha, beta, max_residual, refine: int, refine_levels,
+                        refine_photometric, refine_robust_delta) -> SequenceStabilized:
+    """the one body of lucas_kanade_pyramidal_sequence_stabilize and _stabilize_nv12, once the layout's own arguments are checked"""
+    if refine > 0:
+        grey = video.luma()
         rows = lucas_kanade_pyramidal_sequence_klt_sparse_replenish(grey, max_corners, detect_every, quality_level, min_distance,
                                                                     num_levels, window_size, num_iterations, alpha, beta, max_residual)
         fit = tracks_motion(rows.tracks, rows.visible, rows.born, model, hypotheses, threshold, seed)
         arr, _ = _oflk.as_sequence(grey)
-        al = sequence_refine_alignment(arr, fit.model, fit.status, "affine", refine_levels, int(refine_iterations),
-                                       photometric=bool(refine_photometric), robust_delta=refine_robust_delta)
+        al = sequence_refine_alignment(arr, fit.model, fit.status, "affine", refine_levels, refine, photometric=bool(refine_photometric),
+                                       robust_delta=refine_robust_delta)
         tr = stabilize_trajectory(al.model, fit.status, radius, sigma)
-        return SequenceStabilized(warp_affine(packed if colour else arr, tr.map), tr.correction, al.model, fit.status, tr.held)
-    a, b = _oflk.check_fb_params(alpha, beta)
-    if colour:
-        if packed.shape[0] < 2:
-            raise ValueError(f"a sequence needs at least 2 frames, got {packed.shape[0]}")
-        arr, u8 = packed, True
-        T, H, W, C = arr.shape
-    else:
-        arr, u8 = _oflk.as_sequence(frames)
-        T, H, W = arr.shape
-    L, win, it, r = _oflk.check_sparse_params((H, W), num_levels, window_size, num_iterations, max_residual)
-    K, q, md, win = _oflk.check_feature_params(max_corners, quality_level, min_distance, win)
-    if isinstance(detect_every, bool) or int(detect_every) != detect_every or int(detect_every) < 1:
-        raise ValueError(f"detect_every must be an integer >= 1, got {detect_every!r}")
-    code, hn, thr, sd = _oflk.check_motion_params(model, hypotheses, threshold, seed)
-    w = _oflk.stabilize_weights(radius, sigma)
+        return SequenceStabilized(video.warp(arr, tr.map), tr.correction, al.model, fit.status, tr.held)
+    _oflk.check_fb_params(alpha, beta)
+    arr, H, W = video.frames()
+    T = arr.shape[0]
+    if T < 2:
+        raise ValueError(f"a sequence needs at least 2 frames, got {T}")
+    trk = _oflk.check_tracking((H, W), num_levels, window_size, num_iterations, alpha, beta, max_residual, max_corners, quality_level,
+                               min_distance, detect_every)
+    fit = _oflk.check_motion_params(model, hypotheses, threshold, seed)
+    win = _oflk.check_window(radius, sigma)
     out = np.empty_like(arr)
     corr, mod = np.empty((T, 6), np.float32), np.empty((T - 1, 6), np.float32)
     cnt, held = np.empty((T - 1, 3), np.int32), np.empty(T - 1, np.uint8)
-    if colour:
-        _oflk.check(_oflk.lib().oflk_stabilize_sequence_packed(
-            arr.ctypes.data, T, H, W, C, code_order, L, win, it, a, b, r, q, md, K, min(int(detect_every), 2 ** 31 - 1), code, hn, thr,
-            sd, _oflk._f64(w), int(w.size) - 1, out.ctypes.data, _oflk.ptr(corr), _oflk.ptr(mod), cnt.ctypes.data_as(_oflk._i32p),
-            held.ctypes.data))
-        return SequenceStabilized(out, corr.reshape(T, 2, 3), mod.reshape(T - 1, 2, 3), cnt[:, 2].copy(), held.astype(bool))
-    fn = _oflk.lib().oflk_stabilize_sequence_u8 if u8 else _oflk.lib().oflk_stabilize_sequence
-    _oflk.check(fn(arr.ctypes.data if u8 else _oflk.ptr(arr), T, H, W, L, win, it, a, b, r, q, md, K,
-                   min(int(detect_every), 2 ** 31 - 1), code, hn, thr, sd, _oflk._f64(w), int(w.size) - 1,
-                   out.ctypes.data if u8 else _oflk.ptr(out), _oflk.ptr(corr), _oflk.ptr(mod), cnt.ctypes.data_as(_oflk._i32p),
-                   held.ctypes.data))
+    if video.layout.suffix:
+        src, fn = _oflk.pix(arr), getattr(_oflk.lib(), "oflk_stabilize_sequence" + video.layout.suffix)
+    else:   # the grey form has the pixel type in its name
+        src, fn = _oflk.pixels(arr, "oflk_stabilize_sequence")
+    _oflk.check(fn(src, T, H, W, *video.layout.args, *trk, *fit, *win.args, _oflk.pix(out), _oflk.ptr(corr), _oflk.ptr(mod),
+                   cnt.ctypes.data_as(_oflk._i32p), held.ctypes.data))
     return SequenceStabilized(out, corr.reshape(T, 2, 3), mod.reshape(T - 1, 2, 3), cnt[:, 2].copy(), held.astype(bool))
 
 
@@ -587,11 +568,7 @@ def _warp_nv12(frames, maps, siting, return_inside: bool, n: int):
     single = isinstance(frames, np.ndarray) and frames.ndim == 2
     arr = _oflk.as_nv12(frames[None] if single else frames, "(F, 3H/2, W) or (3H/2, W)")
     F = arr.shape[0]
-    m = np.ascontiguousarray(maps, np.float64)
-    rows = (3, 6) if n == 6 else (3, 9)
-    if m.size != n * F or m.ndim not in (1, 2, 3) or m.shape[-1] not in rows or (n == 9 and m.shape[-1] == 3 and (m.ndim < 2 or m.shape[-2] != 3)):
-        raise ValueError(f"expected {F} maps of shape {(2, 3) if n == 6 else (3, 3)} or ({n},), got {np.shape(maps)}")
-    out, ins = _oflk.warp_nv12_host(arr, m.reshape(F, n), code, bool(return_inside))
+    out, ins = _oflk.warp_nv12_host(arr, _maps(maps, F, n), code, bool(return_inside))
     if single:
         out, ins = out[0], None if ins is None else ins[0]
     return (out, ins.astype(bool)) if return_inside else out
@@ -623,40 +600,18 @@ def lucas_kanade_pyramidal_sequence_stabilize_nv12(frames, max_corners: int, det
     frames are warped under the maps of that trajectory by warp_affine_nv12, the chroma sited as `siting` says.  .frames has
     the input's shape.  No conversion and no luma pass: the Y plane is the frame's first H W bytes.  refine_robust_delta (needs
     refine_iterations > 0) is sequence_refine_alignment's robust_delta, as in that call."""
-    if isinstance(refine_iterations, bool) or int(refine_iterations) != refine_iterations or int(refine_iterations) < 0:
-        raise ValueError(f"refine_iterations must be an integer >= 0, got {refine_iterations!r}")
-    if refine_robust_delta is not None and int(refine_iterations) == 0:
-        raise ValueError("refine_robust_delta needs refine_iterations > 0")
+    refine = _oflk.check_refine(refine_iterations, False, refine_robust_delta)
     code_siting = _oflk.check_nv12_siting(siting)
     arr = _oflk.as_nv12(frames, "(T, 3H/2, W)")
     T, R, W = arr.shape
     H = 2 * R // 3
     if T < 2:
         raise ValueError(f"a sequence needs at least 2 frames, got {T}")
-    if int(refine_iterations) > 0:
-        grey = np.ascontiguousarray(arr[:, :H, :])
-        rows = lucas_kanade_pyramidal_sequence_klt_sparse_replenish(grey, max_corners, detect_every, quality_level, min_distance,
-                                                                    num_levels, window_size, num_iterations, alpha, beta, max_residual)
-        fit = tracks_motion(rows.tracks, rows.visible, rows.born, model, hypotheses, threshold, seed)
-        al = sequence_refine_alignment(grey, fit.model, fit.status, "affine", refine_levels, int(refine_iterations),
-                                       robust_delta=refine_robust_delta)
-        tr = stabilize_trajectory(al.model, fit.status, radius, sigma)
-        return SequenceStabilized(warp_affine_nv12(arr, tr.map, siting), tr.correction, al.model, fit.status, tr.held)
-    a, b = _oflk.check_fb_params(alpha, beta)
-    L, win, it, r = _oflk.check_sparse_params((H, W), num_levels, window_size, num_iterations, max_residual)
-    K, q, md, win = _oflk.check_feature_params(max_corners, quality_level, min_distance, win)
-    if isinstance(detect_every, bool) or int(detect_every) != detect_every or int(detect_every) < 1:
-        raise ValueError(f"detect_every must be an integer >= 1, got {detect_every!r}")
-    code, hn, thr, sd = _oflk.check_motion_params(model, hypotheses, threshold, seed)
-    w = _oflk.stabilize_weights(radius, sigma)
-    out = np.empty_like(arr)
-    corr, mod = np.empty((T, 6), np.float32), np.empty((T - 1, 6), np.float32)
-    cnt, held = np.empty((T - 1, 3), np.int32), np.empty(T - 1, np.uint8)
-    _oflk.check(_oflk.lib().oflk_stabilize_sequence_nv12(
-        arr.ctypes.data, T, H, W, code_siting, L, win, it, a, b, r, q, md, K, min(int(detect_every), 2 ** 31 - 1), code, hn, thr, sd,
-        _oflk._f64(w), int(w.size) - 1, out.ctypes.data, _oflk.ptr(corr), _oflk.ptr(mod), cnt.ctypes.data_as(_oflk._i32p),
-        held.ctypes.data))
-    return SequenceStabilized(out, corr.reshape(T, 2, 3), mod.reshape(T - 1, 2, 3), cnt[:, 2].copy(), held.astype(bool))
+    video = _Video(lambda: (arr, H, W), _oflk.FrameLayout("_nv12", (code_siting,)), lambda: np.ascontiguousarray(arr[:, :H, :]),
+                   lambda grey, maps: warp_affine_nv12(arr, maps, siting))
+    return _sequence_stabilize(video, max_corners, detect_every, model, radius, sigma, hypotheses, threshold, seed, quality_level,
+                               min_distance, num_levels, window_size, num_iterations, alpha, beta, max_residual, refine, refine_levels,
+                               False, refine_robust_delta)
 
 
 class Mosaic(NamedTuple):
@@ -713,12 +668,7 @@ def lucas_kanade_pyramidal_sequence_mosaic(frames, max_corners: int = 1000, dete
     A 4-D uint8 array (T, H, W, C), C = 3 or 4, is interleaved colour video (`order`: "rgb" or "bgr"): this call runs on
     rgb_to_luma of the frames for everything but the canvas, and every channel's plane is then blended by mosaic_composite
     under the chain fitted on the luma; .canvas is (Hc, Wc, C), .count the grey call's."""
-    if isinstance(refine_iterations, bool) or int(refine_iterations) != refine_iterations or int(refine_iterations) < 0:
-        raise ValueError(f"refine_iterations must be an integer >= 0, got {refine_iterations!r}")
-    if refine_photometric and int(refine_iterations) == 0:
-        raise ValueError("refine_photometric needs refine_iterations > 0")
-    if refine_robust_delta is not None and int(refine_iterations) == 0:
-        raise ValueError("refine_robust_delta needs refine_iterations > 0")
+    refine = _oflk.check_refine(refine_iterations, refine_photometric, refine_robust_delta)
     _oflk.check_colour_order(order)
     if _oflk.is_packed(frames):
         packed = _oflk.as_packed(frames, "(T, H, W, C)")
@@ -730,59 +680,53 @@ def lucas_kanade_pyramidal_sequence_mosaic(frames, max_corners: int = 1000, dete
         canvas = mosaic_composite(packed, ch.from_anchor, m.canvas.shape, m.origin, ch.dropped, blend,
                                   exposure=m.exposure if refine_photometric else None)
         return m._replace(canvas=canvas)
-    if int(refine_iterations) > 0:
+    if refine > 0:
         rows = lucas_kanade_pyramidal_sequence_klt_sparse_replenish(frames, max_corners, detect_every, quality_level, min_distance,
                                                                     num_levels, window_size, num_iterations, alpha, beta, max_residual)
         fit = tracks_homography(rows.tracks, rows.visible, rows.born, hypotheses, threshold, seed)
         arr, _ = _oflk.as_sequence(frames)
-        al = sequence_refine_alignment(arr, fit.model, fit.status, "homography", refine_levels, int(refine_iterations),
+        al = sequence_refine_alignment(arr, fit.model, fit.status, "homography", refine_levels, refine,
                                        photometric=bool(refine_photometric), robust_delta=refine_robust_delta)
         ch = mosaic_chain(al.model, fit.status, arr.shape[1:], anchor, extent)
         Hc, Wc = ch.canvas_shape
-        cap = 16 * arr.shape[1] * arr.shape[2] if max_pixels is None else max_pixels
-        if isinstance(cap, bool) or int(cap) != cap or int(cap) < 1:
-            raise ValueError(f"max_pixels must be an integer >= 1, got {max_pixels!r}")
-        if Hc * Wc > int(cap):
+        cap = _max_pixels(max_pixels, arr.shape[1], arr.shape[2])
+        if Hc * Wc > cap:
             raise _oflk.OflkError(_oflk.OFLK_ERR_UNSUPPORTED,
-                                  f"the canvas of {Wc} x {Hc} pixels at {ch.origin} exceeds the capacity of {int(cap)} pixels")
-        if refine_photometric:
-            ex = exposure_chain(al.gain, al.bias, al.status == 1, anchor)
-            canvas, cnt = mosaic_composite(arr, ch.from_anchor, (Hc, Wc), ch.origin, ch.dropped, blend, True, exposure=ex)
-            return PhotometricMosaic(canvas, cnt, ch.origin, ch.to_anchor, ch.held, ch.dropped, al.model, fit.status, ex)
-        canvas, cnt = mosaic_composite(arr, ch.from_anchor, (Hc, Wc), ch.origin, ch.dropped, blend, True)
-        return Mosaic(canvas, cnt, ch.origin, ch.to_anchor, ch.held, ch.dropped, al.model, fit.status)
-    a, b = _oflk.check_fb_params(alpha, beta)
-    arr, u8 = _oflk.as_sequence(frames)
+                                  f"the canvas of {Wc} x {Hc} pixels at {ch.origin} exceeds the capacity of {cap} pixels")
+        ex = exposure_chain(al.gain, al.bias, al.status == 1, anchor) if refine_photometric else None
+        canvas, cnt = mosaic_composite(arr, ch.from_anchor, (Hc, Wc), ch.origin, ch.dropped, blend, True, exposure=ex)
+        m = Mosaic(canvas, cnt, ch.origin, ch.to_anchor, ch.held, ch.dropped, al.model, fit.status)
+        return PhotometricMosaic(*m, ex) if refine_photometric else m
+    _oflk.check_fb_params(alpha, beta)
+    arr, _ = _oflk.as_sequence(frames)
     T, H, W = arr.shape
     if H < 2 or W < 2:
         raise ValueError(f"frames must be at least 2 x 2, got {H} x {W}")
-    L, win, it, r = _oflk.check_sparse_params((H, W), num_levels, window_size, num_iterations, max_residual)
-    K, q, md, win = _oflk.check_feature_params(max_corners, quality_level, min_distance, win)
-    if isinstance(detect_every, bool) or int(detect_every) != detect_every or int(detect_every) < 1:
-        raise ValueError(f"detect_every must be an integer >= 1, got {detect_every!r}")
-    hn, thr, sd = _oflk.check_ransac_params(hypotheses, threshold, seed)
+    trk = _oflk.check_tracking((H, W), num_levels, window_size, num_iterations, alpha, beta, max_residual, max_corners, quality_level,
+                               min_distance, detect_every)
+    ransac = _oflk.check_ransac_params(hypotheses, threshold, seed)
     code = _oflk.check_mosaic_blend(blend)
-    if isinstance(anchor, bool) or int(anchor) != anchor or not 0 <= int(anchor) < T:
-        raise ValueError(f"anchor must be an integer in [0, {T - 1}], got {anchor!r}")
+    anchor = _oflk.check_int("anchor", anchor, 0, T - 1)
     extent = 8.0 * max(H, W) if extent is None else float(extent)
     if not (np.isfinite(extent) and extent > 0):
         raise ValueError(f"extent must be finite and > 0, got {extent!r}")
-    cap = 16 * H * W if max_pixels is None else max_pixels
-    if isinstance(cap, bool) or int(cap) != cap or int(cap) < 1:
-        raise ValueError(f"max_pixels must be an integer >= 1, got {max_pixels!r}")
-    cap = min(int(cap), 2 ** 30 - 1)
+    cap = min(_max_pixels(max_pixels, H, W), 2 ** 30 - 1)
     out, cnt = np.empty(cap, arr.dtype), np.empty(cap, np.int32)
     canvas = np.zeros(4, np.int32)
     to, mod = np.empty((T, 9), np.float64), np.empty((T - 1, 9), np.float32)
     counts, held, drop = np.empty((T - 1, 3), np.int32), np.empty(T - 1, np.uint8), np.empty(T, np.uint8)
-    fn = _oflk.lib().oflk_mosaic_sequence_u8 if u8 else _oflk.lib().oflk_mosaic_sequence
-    _oflk.check(fn(arr.ctypes.data if u8 else _oflk.ptr(arr), T, H, W, L, win, it, a, b, r, q, md, K,
-                   min(int(detect_every), 2 ** 31 - 1), hn, thr, sd, int(anchor), extent, code,
-                   out.ctypes.data if u8 else _oflk.ptr(out), cap, canvas.ctypes.data_as(_oflk._i32p), cnt.ctypes.data_as(_oflk._i32p),
-                   _oflk._f64(to), held.ctypes.data, drop.ctypes.data, _oflk.ptr(mod), counts.ctypes.data_as(_oflk._i32p)))
+    src, fn = _oflk.pixels(arr, "oflk_mosaic_sequence")
+    _oflk.check(fn(src, T, H, W, *trk, *ransac, anchor, extent, code, _oflk.pix(out), cap, canvas.ctypes.data_as(_oflk._i32p),
+                   cnt.ctypes.data_as(_oflk._i32p), _oflk._f64(to), held.ctypes.data, drop.ctypes.data, _oflk.ptr(mod),
+                   counts.ctypes.data_as(_oflk._i32p)))
     x0, y0, Wc, Hc = (int(v) for v in canvas)
     return Mosaic(out[:Hc * Wc].reshape(Hc, Wc).copy(), cnt[:Hc * Wc].reshape(Hc, Wc).copy(), (x0, y0), to.reshape(T, 3, 3),
                   held.astype(bool), drop.astype(bool), mod.reshape(T - 1, 3, 3), counts[:, 2].copy())
+
+
+def _max_pixels(max_pixels, H: int, W: int) -> int:
+    """the mosaic's canvas capacity: max_pixels, by default 16 H W"""
+    return _oflk.check_int("max_pixels", 16 * H * W if max_pixels is None else max_pixels, 1)
 
 
 class TrackerRow(NamedTuple):
@@ -814,14 +758,11 @@ class SparseKltTracker:
         self.dtype = np.dtype(dtype)
         if self.dtype not in (np.dtype(np.uint8), np.dtype(np.float32)):
             raise ValueError(f"dtype must be uint8 or float32, got {dtype!r}")
-        a, b = _oflk.check_fb_params(alpha, beta)
         H, W = int(shape[0]), int(shape[1])
-        L, win, it, r = _oflk.check_sparse_params((H, W), num_levels, window_size, num_iterations, max_residual)
-        K, q, md, win = _oflk.check_feature_params(max_corners, quality_level, min_distance, win)
-        if isinstance(detect_every, bool) or int(detect_every) != detect_every or int(detect_every) < 0:
-            raise ValueError(f"detect_every must be an integer >= 0, got {detect_every!r}")
-        self.shape, self.max_corners, self.detect_every = (H, W), K, min(int(detect_every), 2 ** 31 - 1)
-        self._t = _oflk.Tracker(device, H, W, self.dtype == np.uint8, K, self.detect_every, L, win, it, a, b, r, q, md)
+        trk = _oflk.check_tracking((H, W), num_levels, window_size, num_iterations, alpha, beta, max_residual, max_corners,
+                                   quality_level, min_distance, detect_every, min_every=0)
+        self.shape, self.max_corners, self.detect_every = (H, W), trk.max_corners, trk.detect_every
+        self._t = _oflk.Tracker(device, H, W, self.dtype == np.uint8, **trk._asdict())
         if motion is not None:
             self.set_motion(**motion) if isinstance(motion, dict) else self.set_motion(motion)
 
@@ -955,20 +896,15 @@ class OnlineStabilizer:
             raise ValueError("colour frames must be uint8 (float32 colour is not offered)")
         if nv12 and self.dtype != np.dtype(np.uint8):
             raise ValueError("NV12 frames must be uint8")
-        a, b = _oflk.check_fb_params(alpha, beta)
         H, W = int(shape[0]), int(shape[1])
-        L, win, it, r = _oflk.check_sparse_params((H, W), num_levels, window_size, num_iterations, max_residual)
-        K, q, md, win = _oflk.check_feature_params(max_corners, quality_level, min_distance, win)
-        if isinstance(detect_every, bool) or int(detect_every) != detect_every or int(detect_every) < 0:
-            raise ValueError(f"detect_every must be an integer >= 0, got {detect_every!r}")
-        code, hn, thr, sd = _oflk.check_motion_params(model, hypotheses, threshold, seed)
-        w = _oflk.stabilize_weights(radius, sigma)
-        self.shape, self.max_corners, self.detect_every = (H, W, channels) if channels else (H, W), K, min(int(detect_every), 2 ** 31 - 1)
-        if nv12:
-            self.shape = (3 * H // 2, W)
-        self.radius, self.inside = int(w.size) - 1, bool(inside)
-        self._s = _oflk.Stabilizer(device, H, W, self.dtype == np.uint8, K, self.detect_every, code, w, hn, thr, sd, L, win, it, a, b, r,
-                                   q, md, channels, code_order, nv12, code_siting)
+        trk = _oflk.check_tracking((H, W), num_levels, window_size, num_iterations, alpha, beta, max_residual, max_corners,
+                                   quality_level, min_distance, detect_every, min_every=0)
+        fit = _oflk.check_motion_params(model, hypotheses, threshold, seed)
+        win = _oflk.check_window(radius, sigma)
+        self.max_corners, self.detect_every, self.radius, self.inside = trk.max_corners, trk.detect_every, win.radius, bool(inside)
+        self._s = _oflk.Stabilizer(device, H, W, self.dtype == np.uint8, **trk._asdict(), **fit._asdict(), weights=win.weights,
+                                   channels=channels, order=code_order, nv12=nv12, siting=code_siting)
+        self.shape = self._s.layout.frame_shape(H, W)
 
     def _frame(self, index, frame, corr, ins) -> StabilizedFrame:
         return StabilizedFrame(int(index), frame, corr.reshape(2, 3), None if ins is None else ins.astype(bool))

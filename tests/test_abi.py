@@ -35,6 +35,60 @@ def test_library_exports_every_declared_symbol():
     assert set(_oflk.SIGNATURES) == set(declared_functions())
 
 
+def declarations():
+    """{name: (return class, [parameter classes])} of every function include/oflk.h declares; a class is one of pointer,
+    int, unsigned, float, double, size_t, long, void"""
+    text = (ROOT / "include" / "oflk.h").read_text()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    text = re.sub(r"^\s*#[^\n]*", "", text, flags=re.M)       # preprocessor lines
+    text = re.sub(r'extern\s+"C"\s*\{', "", text)
+
+    def kind(decl):
+        decl = decl.strip()
+        if "*" in decl:
+            return "pointer"
+        words = [w for w in re.findall(r"[A-Za-z_][A-Za-z0-9_]*", decl) if w != "const"]
+        assert words, decl
+        if words[0] == "unsigned":
+            assert words[1:2] != ["char"] and words[1:2] != ["long"], decl
+            return "unsigned"
+        assert words[0] in ("int", "float", "double", "size_t", "long", "void"), decl
+        return words[0]
+
+    out = {}
+    for stmt in text.split(";"):
+        m = re.search(r"([A-Za-z_][A-Za-z0-9_ \t\n\*]*?)\b(oflk_[a-z0-9_]+)\s*\(([^()]*)\)\s*$", stmt, flags=re.S)
+        if not m or "typedef" in m.group(1):
+            continue
+        params = m.group(3).strip()
+        out[m.group(2)] = (kind(m.group(1)), [] if params in ("", "void") else [kind(p) for p in params.split(",")])
+    return out
+
+
+def ctypes_class(t):
+    """the class of a ctypes restype / argtypes entry, in the words of declarations()"""
+    if t is None:
+        return "void"
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return "pointer"
+    plain = {ctypes.c_int: "int", ctypes.c_uint: "unsigned", ctypes.c_float: "float", ctypes.c_double: "double",
+             ctypes.c_size_t: "size_t", ctypes.c_long: "long"}
+    return plain[t]
+
+
+def test_every_signature_has_the_classes_of_its_declaration():
+    """SIGNATURES against the header, type by type: the return type and every parameter, position by position, fall in the
+    same class (pointer, int, unsigned, float, double, size_t, long, void) as the declaration's"""
+    import _oflk
+
+    decl = declarations()
+    assert set(decl) == set(declared_functions()) == set(_oflk.SIGNATURES)
+    for name, (res, args) in _oflk.SIGNATURES.items():
+        got = (ctypes_class(res), [ctypes_class(a) for a in args])
+        assert got == decl[name], f"{name}: ctypes {got}, header {decl[name]}"
+
+
 def test_version_and_device_count_never_fail():
     import _oflk
 

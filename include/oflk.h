@@ -117,10 +117,15 @@ int oflk_upsample_flow(const float *flow_u, const float *flow_v, int Hc, int Wc,
  * when it runs the unfused chain (always 0 for a radius other than 8).
  * oflk_pyramid_step_form: which of the three paths that step takes.  2: k_pyr_down's tight tile (every 32 x 16 output tile
  * samples at most 32 x 64 blurred values: the half-scale ratio, every level of an even-sized frame), 1: its general tile
- * (at most 34 x 66: odd sizes, tiny levels), 0: the unfused chain.  Nonzero exactly when oflk_pyramid_step_fused is 1. */
+ * (at most 34 x 66: odd sizes, tiny levels), 0: the unfused chain.  Nonzero exactly when oflk_pyramid_step_fused is 1.
+ * oflk_pyramid_step_half: 1 when that step runs the tight tile's half-scale instantiation (tap and staging offsets fixed at
+ * compile time): oflk_pyramid_step_form is 2, ho and wo are at least 2, and on both axes floor(i * step) == 2 i for every
+ * output i but the last, step being np.linspace(0, S - 1, T)'s.  Every level of an even-sized frame at scale factor 0.5; 0
+ * for a tight step at another ratio of the band, which runs the tight tile as before.  Same values either way. */
 int oflk_upsample_staged(int Hc, int Wc, int Ht, int Wt);
 int oflk_pyramid_step_fused(int h, int w, int ho, int wo, int radius);
 int oflk_pyramid_step_form(int h, int w, int ho, int wo, int radius);
+int oflk_pyramid_step_half(int h, int w, int ho, int wo, int radius);
 
 /* lucas_kanade_pyramidal(frame_prev, frame_curr, num_levels, window_size, num_iterations) -> (u, v)
  * replaces python/lucas_kanade_pyramidal.py:141-228.

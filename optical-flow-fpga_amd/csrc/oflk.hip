@@ -577,6 +577,22 @@ int pyr_form(int h, int w, int ho, int wo, const GaussW &g)
     return span_ok(h, ho, kPTH, kPBH) && span_ok(w, wo, kPTW, kPBW) ? PYR_GENERAL : PYR_UNFUSED;
 }
 
+// Is a tight step at the exact half-scale ratio, i.e. does np.linspace(0, S - 1, T) put every point but its last in
+// [2 i, 2 i + 1) on both axes?  Evaluated on the values the kernel receives.  The tight form alone does not say so: its spans
+// also fit at other ratios of the radius-8 band (scale factor 0.52, say), where floor(i * step) leaves 2 i.
+bool half_axis(int S, int T)
+{
+    if (T < 2) return false;
+    const Linspace l = make_linspace(S, T);
+    for (int i = 0; i < T - 1; i++)
+        if (std::floor((double)i * l.step) != (double)(2 * i)) return false;
+    return true;
+}
+bool pyr_half(int h, int w, int ho, int wo, const GaussW &g)
+{
+    return pyr_form(h, w, ho, wo, g) == PYR_TIGHT && half_axis(h, ho) && half_axis(w, wo);
+}
+
 // does every 32 x 16 coarse tile's source span fit one of the fused kernel's LDS tiles?
 bool pyr_fused_fits(int h, int w, int ho, int wo, const GaussW &g) { return pyr_form(h, w, ho, wo, g) != PYR_UNFUSED; }
 
@@ -682,10 +698,12 @@ int launch_pyr_down(oflk_plan *plan, const GaussW &gauss, hipStream_t s, const f
         // plan at all) runs them behind the rounding certificate, which leaves SciPy's results
         constexpr int kExactForm = OFLK_PYR_CERT ? PYR_CERTIFIED : PYR_EXACT;
         const int arith = contracted_pyramid(plan) ? PYR_CONTRACTED : kExactForm;
+        // the tile: a tight step at the exact half-scale ratio takes the instantiation with compile-time tap and staging offsets
+        const int tile = form != PYR_TIGHT ? PYR_TILE_GENERAL : (pyr_half(h, w, ho, wo, gauss) ? PYR_TILE_HALF : PYR_TILE_TIGHT);
         with_pix(extra && extra->u8, [&](auto PIX) {
             with_int<PYR_CONTRACTED, kExactForm>(arith, [&](auto ARITH) {
-                with_bool(form == PYR_TIGHT, [&](auto TIGHT) {
-                    hipLaunchKernelGGL((k_pyr_down<typename decltype(PIX)::type, decltype(ARITH)::value, decltype(TIGHT)::value>), grid,
+                with_int<PYR_TILE_GENERAL, PYR_TILE_TIGHT, PYR_TILE_HALF>(tile, [&](auto TILE) {
+                    hipLaunchKernelGGL((k_pyr_down<typename decltype(PIX)::type, decltype(ARITH)::value, decltype(TILE)::value>), grid,
                                        dim3(256), 0, s, a);
                 });
             });
@@ -1616,6 +1634,14 @@ OFLK_API int oflk_pyramid_step_form(int h, int w, int ho, int wo, int radius)
     GaussW g{};
     g.radius = radius;
     return pyr_form(h, w, ho, wo, g);
+}
+
+OFLK_API int oflk_pyramid_step_half(int h, int w, int ho, int wo, int radius)
+{
+    if (h < 1 || w < 1 || ho < 1 || wo < 1) return 0;
+    GaussW g{};
+    g.radius = radius;
+    return pyr_half(h, w, ho, wo, g) ? 1 : 0;
 }
 
 OFLK_API double oflk_device_mean_error(int path, int level_h, int level_w, double mean)

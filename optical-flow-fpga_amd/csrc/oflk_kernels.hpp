@@ -27,6 +27,9 @@
 #ifndef OFLK_PYR_CERT
 #define OFLK_PYR_CERT 1    // k_pyr_down: the exact arithmetic runs the certified form (0: SciPy's sequence throughout)
 #endif
+#ifndef OFLK_PYR_HALF
+#define OFLK_PYR_HALF 3    // k_pyr_down's half-scale tile: bit 0 its staging (stage A), bit 1 its sampling (stage D); a
+#endif                     // diagnostic build clears one to time the other alone
 #ifndef OFLK_LK16_PF
 #define OFLK_LK16_PF 2   // rows of frame loads in flight per wave (k_lk16d)
 #endif
@@ -1859,20 +1862,32 @@ __global__ __launch_bounds__(256) void k_resample(ResampleArgs a)
 // pixel, write 4 B per coarse pixel).
 // The host checks that a tile's source span fits the static LDS tile
 // (pyr_form) and otherwise uses the unfused chain.
-// Two tile geometries (PyrGeom), chosen by the host per step:
+// Three tiles (PyrGeom, PYR_TILE_*), chosen by the host per step:
 //   general  blurred span 34 x 66: what a tile of any ratio near 2 may sample (odd sizes, tiny levels)
 //   tight    blurred span 32 x 64: what a tile samples at the half-scale ratio (T = S / 2: floor(i * step) = 2 i for every
 //            i < T - 1, and the last point is capped), i.e. every level of an even-sized frame.  Nothing is blurred that
 //            no sample reads, and passes A, B and C fill their lanes: 48 x 80 = 15 x 256 staged cells, 80 columns x 3
 //            segments of 11 rows, 32 rows x 8 segments of 8 columns.
+//   half     the tight tile of a step where floor(i * step) == 2 i holds for every output but the last of each axis
+//            (pyr_half; every level of an even-sized frame).  The tile then starts at source (2 i0, 2 j0) and output
+//            (r, c) of the tile samples blurred cells (2 r, 2 c) .. (2 r + 1, 2 c + 1): stage A stages fixed rows of a
+//            fixed column per thread, stage D reads its four taps at compile-time offsets of one LDS address and forms
+//            the x side once for a thread's two outputs.  Only the blocks of the last tile row / column, which hold the
+//            capped last point and the partial tiles, keep run-time tap indices.  Values as in the tight form.
 // ---------------------------------------------------------------------------
 constexpr int kPTW = 32, kPTH = 16;          // coarse outputs per block
 constexpr int kPBW = 2 * kPTW + 2;           // blurred cols a tile may need (66); the tight form holds 64
 constexpr int kPBH = 2 * kPTH + 2;           // blurred rows (34); tight 32
 constexpr int kPBWT = 2 * kPTW, kPBHT = 2 * kPTH;
 
-template <bool TIGHT>
+// PYR_TILE_HALF is the tight tile of a step at the exact half-scale ratio (pyr_half: floor(i * step) == 2 i for every output
+// but the last of an axis): same LDS layout and passes B and C, with the index arithmetic of stages A and D done when the
+// kernel is compiled (see there).
+enum { PYR_TILE_GENERAL = 0, PYR_TILE_TIGHT = 1, PYR_TILE_HALF = 2 };
+
+template <int TILE>
 struct PyrGeom {
+    static constexpr bool TIGHT = TILE != PYR_TILE_GENERAL;
     static constexpr int BW = TIGHT ? kPBWT : kPBW;   // blurred cols (64 | 66)
     static constexpr int BH = TIGHT ? kPBHT : kPBH;   // blurred rows (32 | 34)
     static constexpr int IW = BW + 16;                // input cols incl. radius-8 halo (80 | 82)
@@ -1971,10 +1986,11 @@ __device__ __forceinline__ void pyr_cert_count(int slot)
 }
 #endif
 
-template <class PIX, int ARITH = PYR_EXACT, bool TIGHT = false>
+template <class PIX, int ARITH = PYR_EXACT, int TILE = PYR_TILE_GENERAL>
 __global__ __launch_bounds__(256) void k_pyr_down(PyrArgs a)
 {
-    using G = PyrGeom<TIGHT>;
+    using G = PyrGeom<TILE>;
+    constexpr bool HALF_A = TILE == PYR_TILE_HALF && (OFLK_PYR_HALF & 1), HALF_D = TILE == PYR_TILE_HALF && (OFLK_PYR_HALF & 2);
     constexpr int kPBW = G::BW, kPBH = G::BH, kPIW = G::IW, kPIH = G::IH, kPVS = G::VS, kPHS = G::HS;   // this geometry's
     __shared__ __attribute__((aligned(16))) float s_in[kPIH * kPIW];   // stage A (8-byte column-pair writes); reused for the blurred tile (stage C output)
     __shared__ float s_v[kPBH * kPVS];
@@ -2000,8 +2016,9 @@ __global__ __launch_bounds__(256) void k_pyr_down(PyrArgs a)
     const int j0 = blockIdx.x * kPTW, i0 = blockIdx.y * kPTH;
     // first blurred row / column any tap of this tile touches (a sample that lands
     // exactly on the last row reads the mirrored row H-2 with weight 0)
-    int ylo = (int)floor(linspace_at(a.ly, i0));
-    int xlo = (int)floor(linspace_at(a.lx, j0));
+    // (half: a tile's first output is never the last of its axis unless it is the only one, and then the cap below sets it)
+    int ylo = TILE == PYR_TILE_HALF ? 2 * i0 : (int)floor(linspace_at(a.ly, i0));
+    int xlo = TILE == PYR_TILE_HALF ? 2 * j0 : (int)floor(linspace_at(a.lx, j0));
     if (i0 + kPTH >= a.Ho) ylo = min(ylo, max(H - 2, 0));
     if (j0 + kPTW >= a.Wo) xlo = min(xlo, max(W - 2, 0));
 
@@ -2026,34 +2043,68 @@ __global__ __launch_bounds__(256) void k_pyr_down(PyrArgs a)
                 // 82 = 2 x 41 columns wide; 2050 pairs = 8 per thread + 2.  Tight: 2 x 40, 1920 pairs = 7.5 per thread)
                 constexpr int PWD = kPIW / 2, NPR = kPIH * PWD, NB = (NPR + 255) / 256, QB = 256 / PWD, RB = 256 % PWD;
                 static_assert(kPIW % 2 == 0, "pairs");
-                float2 pv[NB];
-                int r = tid / PWD, c = tid - r * PWD;
-                unsigned off = (unsigned)__mul24(ybase + r, W) + (unsigned)(xbase + 2 * c);
-                const unsigned step = (unsigned)__mul24(QB, W) + 2 * RB, wrap = (unsigned)(W - kPIW);
-                int cc = c;
+                if constexpr (HALF_A) {
+                    // a thread keeps its column pair and takes every RH-th row: the rows advance by a wave-uniform
+                    // constant and pair (r + RH k, c) is LDS pair tid + NT k, so no load carries a compare or a select
+                    constexpr int RH = 6, NT = RH * PWD, NK = kPIH / RH;   // 240 threads, 8 rows each
+                    static_assert(kPIH % RH == 0 && NT <= 256, "whole rows, one block");
+                    if (tid < NT) {
+                        const int r = tid / PWD, c = tid - r * PWD;
+                        const unsigned off = ((unsigned)__mul24(ybase + r, W) + (unsigned)(xbase + 2 * c)) * 4u;
+                        const size_t rows = (size_t)(RH * W) * sizeof(float);
+                        float2 pv[NK];
 #pragma unroll
-                for (int k = 0; k < NB; k++) {
-                    if ((k + 1) * 256 <= NPR || tid + k * 256 < NPR) pv[k] = ld_off<float2>(src, off * 4u);
-                    off += step; cc += RB;
-                    if (cc >= PWD) { cc -= PWD; off += wrap; }
+                        for (int k = 0; k < NK; k++) pv[k] = ld_off<float2>(reinterpret_cast<const char *>(src) + k * rows, off);
+#pragma unroll
+                        for (int k = 0; k < NK; k++) reinterpret_cast<float2 *>(s_in)[tid + k * NT] = pv[k];
+                    }
+                } else {
+                    float2 pv[NB];
+                    int r = tid / PWD, c = tid - r * PWD;
+                    unsigned off = (unsigned)__mul24(ybase + r, W) + (unsigned)(xbase + 2 * c);
+                    const unsigned step = (unsigned)__mul24(QB, W) + 2 * RB, wrap = (unsigned)(W - kPIW);
+                    int cc = c;
+#pragma unroll
+                    for (int k = 0; k < NB; k++) {
+                        if ((k + 1) * 256 <= NPR || tid + k * 256 < NPR) pv[k] = ld_off<float2>(src, off * 4u);
+                        off += step; cc += RB;
+                        if (cc >= PWD) { cc -= PWD; off += wrap; }
+                    }
+#pragma unroll
+                    for (int k = 0; k < NB; k++)
+                        if ((k + 1) * 256 <= NPR || tid + k * 256 < NPR) reinterpret_cast<float2 *>(s_in)[tid + k * 256] = pv[k];   // pair e -> cells 2e, 2e+1
                 }
-#pragma unroll
-                for (int k = 0; k < NB; k++)
-                    if ((k + 1) * 256 <= NPR || tid + k * 256 < NPR) reinterpret_cast<float2 *>(s_in)[tid + k * 256] = pv[k];   // pair e -> cells 2e, 2e+1
                 staged = true;
             }
         }
         if (staged) {
         } else
         if (ybase >= 0 && ybase + kPIH <= H && xbase >= 0 && xbase + kPIW <= W) {
-            unsigned off = (unsigned)__mul24(ybase + r0, W) + (unsigned)(xbase + c0);   // element offsets
-            const unsigned step = (unsigned)__mul24(QA, W) + RA, wrap = (unsigned)(W - kPIW);
-            int c = c0;
+            if constexpr (HALF_A) {
+                // element-wise interior tile (uint8 frames), as the pairs above: a thread keeps its column and takes every
+                // RH-th row; element (r + RH k, c) is LDS cell tid + NT k
+                constexpr int RH = 3, NT = RH * kPIW, NK = kPIH / RH;   // 240 threads, 16 rows each
+                static_assert(kPIH % RH == 0 && NT <= 256, "whole rows, one block");
+                if (tid < NT) {
+                    const unsigned off = (unsigned)__mul24(ybase + r0, W) + (unsigned)(xbase + c0);
+                    const size_t rows = (size_t)(RH * W);
+                    float ev[NK];
 #pragma unroll
-            for (int k = 0; k < NA; k++) {
-                if (k < NA - 1 || tid < NLAST) vals[k] = ld_pix<PIX>(src, off);
-                off += step; c += RA;
-                if (c >= kPIW) { c -= kPIW; off += wrap; }
+                    for (int k = 0; k < NK; k++) ev[k] = ld_pix<PIX>(src + k * rows, off);
+#pragma unroll
+                    for (int k = 0; k < NK; k++) s_in[tid + k * NT] = ev[k];
+                }
+                staged = true;
+            } else {
+                unsigned off = (unsigned)__mul24(ybase + r0, W) + (unsigned)(xbase + c0);   // element offsets
+                const unsigned step = (unsigned)__mul24(QA, W) + RA, wrap = (unsigned)(W - kPIW);
+                int c = c0;
+#pragma unroll
+                for (int k = 0; k < NA; k++) {
+                    if (k < NA - 1 || tid < NLAST) vals[k] = ld_pix<PIX>(src, off);
+                    off += step; c += RA;
+                    if (c >= kPIW) { c -= kPIW; off += wrap; }
+                }
             }
         } else {
             // one mirror step covers indices in [-n, 2n): scipy "reflect" (d c b a | a b c d | d c b a)
@@ -2184,6 +2235,65 @@ __global__ __launch_bounds__(256) void k_pyr_down(PyrArgs a)
 
     // ---- D: bilinear sampling from the blurred tile ----------------------------
     float *__restrict__ dst = a.out + (size_t)blockIdx.z * op;
+    // the four terms of one output in the reference's order: p00, p01 on tap row 0, p10, p11 on tap row 1 (the general and
+    // tight tiles below keep their own copy of these lines: routed through here their certified kernels compile differently)
+    auto bilinear = [](float p00, float p01, float p10, float p11, double wy0, double wy1, double wx0, double wx1) -> float {
+        double acc = 0.0, c;
+        if constexpr (ARITH == PYR_CONTRACTED) {
+            c = (double)p00; c = c * wy0; acc = c * wx0;
+            c = (double)p01; c = c * wy0; acc = __builtin_fma(c, wx1, acc);
+            c = (double)p10; c = c * wy1; acc = __builtin_fma(c, wx0, acc);
+            c = (double)p11; c = c * wy1; acc = __builtin_fma(c, wx1, acc);
+        } else {
+            c = (double)p00; c = c * wy0; c = c * wx0; acc = acc + c;
+            c = (double)p01; c = c * wy0; c = c * wx1; acc = acc + c;
+            c = (double)p10; c = c * wy1; c = c * wx0; acc = acc + c;
+            c = (double)p11; c = c * wy1; c = c * wx1; acc = acc + c;
+        }
+        return (float)acc;
+    };
+    if constexpr (HALF_D) {
+        // Thread (tr, tc) produces outputs (i, j) and (i + 8, j).  floor(i * step) is 2 i for every output but the last of
+        // an axis (the host's pyr_half), and 2 i is exact in fp64, so the fraction i * step - 2 i is the reference's
+        // y - floor(y) without the floor or a conversion to int; the x side serves both outputs.
+        const int tr = tid / kPTW, tc = tid % kPTW;
+        const int i = i0 + tr, j = j0 + tc;
+        const unsigned ooff = ((unsigned)__mul24(i, a.Wo) + (unsigned)j) * 4u, orow = (unsigned)(8 * a.Wo) * 4u;
+        const double dj = (double)j;
+        if (i0 + kPTH < a.Ho && j0 + kPTW < a.Wo) {
+            // no capped point and no partial tile in this block (ylo = 2 i0, xlo = 2 j0): the taps of (i, j) are the cells
+            // (2 tr, 2 tc) .. (2 tr + 1, 2 tc + 1) of the blurred tile, at compile-time offsets of one address
+            const float *b = s_h + 2 * tr * kPHS + 2 * tc;
+            const double wx0 = 1.0 - (dj * a.lx.step - (dj + dj)), wx1 = 1.0 - wx0;
+            double di = (double)i;
+#pragma unroll
+            for (int k = 0; k < 2; k++, di += 8.0) {
+                const float *t = b + k * 16 * kPHS;
+                const double wy0 = 1.0 - (di * a.ly.step - (di + di)), wy1 = 1.0 - wy0;
+                st_off<float>(dst, ooff + k * orow, bilinear(t[0], t[1], t[kPHS], t[kPHS + 1], wy0, wy1, wx0, wx1));
+            }
+        } else {
+            // last tile row / column: the capped last point (floor S - 1, second tap the mirrored S - 2) and outputs past
+            // the level keep run-time tap indices; a lane past the level reads cells of the tile's storage and stores nothing
+            const bool lastx = j == a.Wo - 1;
+            const double x = lastx ? a.lx.last : dj * a.lx.step, fx = lastx ? a.lx.last : dj + dj;
+            const double wx0 = 1.0 - (x - fx), wx1 = 1.0 - wx0;
+            const int x0 = lastx ? W - 1 : 2 * j, x1 = (x0 + 1 < W) ? x0 + 1 : (W > 1 ? W - 2 : 0);
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                const int ii = i + 8 * k;
+                const bool lasty = ii == a.Ho - 1;
+                const double di = (double)ii;
+                const double y = lasty ? a.ly.last : di * a.ly.step, fy = lasty ? a.ly.last : di + di;
+                const double wy0 = 1.0 - (y - fy), wy1 = 1.0 - wy0;
+                const int y0 = lasty ? H - 1 : 2 * ii, y1 = (y0 + 1 < H) ? y0 + 1 : (H > 1 ? H - 2 : 0);
+                const float *r0 = s_h + (y0 - ylo) * kPHS - xlo, *r1 = s_h + (y1 - ylo) * kPHS - xlo;
+                const float r = bilinear(r0[x0], r0[x1], r1[x0], r1[x1], wy0, wy1, wx0, wx1);
+                if (ii < a.Ho && j < a.Wo) st_off<float>(dst, ooff + k * orow, r);
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int k = 0; k < 2; k++) {
         int o = tid + k * 256;

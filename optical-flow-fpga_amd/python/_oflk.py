@@ -60,6 +60,7 @@ SIGNATURES = {
     "oflk_upsample_staged": (ctypes.c_int, [ctypes.c_int] * 4),
     "oflk_pyramid_step_fused": (ctypes.c_int, [ctypes.c_int] * 5),
     "oflk_pyramid_step_form": (ctypes.c_int, [ctypes.c_int] * 5),
+    "oflk_pyramid_step_half": (ctypes.c_int, [ctypes.c_int] * 5),
     "oflk_pyramidal": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f32p, _f32p, _f32p, _i32p]),
     "oflk_single_scale_batch": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f32p, _f32p]),
     "oflk_pyramidal_batch": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f32p, _f32p, _f32p, _i32p]),

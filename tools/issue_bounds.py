@@ -121,7 +121,7 @@ def main():
     res = dict({"kernel": "k_lkw<2, MODE_ITER, true> finest level, 32 x 1920x1080 (tools/kbench.py under rocprofv3 --pmc)",
                 "pairs": 32, "shape": [1080, 1920], "price_classes_cycles": prices}, **res)
     try:
-        res["pyr_down"] = kernel_bounds(pmc_dir, "k_pyr_down<float", "_ZN4oflk10k_pyr_downIfLi2ELb1EEEvNS_7PyrArgsE", asm, prices)   # certified, tight tile: what 1080p launches
+        res["pyr_down"] = kernel_bounds(pmc_dir, "k_pyr_down<float", "_ZN4oflk10k_pyr_downIfLi2ELi2EEEvNS_7PyrArgsE", asm, prices)   # certified, half-scale tile: what 1080p launches
     except Exception as e:   # counters of that kernel missing
         res["pyr_down"] = {"error": str(e)}
     # round 4: the single-scale kernels on their own (32 pairs of 1080p, tools/profiles_r04.sh) and the streaming iteration

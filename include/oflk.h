@@ -252,6 +252,53 @@ int oflk_track_points_host(const float *uf, const float *vf, const float *ub, co
                            float alpha, float beta, const int *qt, const float *qxy, int N, float *tracks,
                            unsigned char *visible);
 
+/* ---- motion-compensated frame interpolation on the dense flows ----------------------------------------------------- */
+/* Frames in, in-between frames out: the statement (tests/interp_model.py).  Pair b has frames A = frame b and B = frame
+ * b+1, each float32 or uint8, F = (uf, vf) the flow A -> B and G = (ub, vb) the flow B -> A.  The output time tau is a
+ * double in the open interval (0, 1).  sample(img, x, y) is the reference's warp_image at one float64 point (map_coordinates,
+ * order 1, cval 0; float32 result); a coordinate that is not inside [0, W-1] x [0, H-1] -- the negated closed comparison in
+ * float64, so NaN and the infinities are not inside -- samples as 0 and reads no tap: a flow value never becomes an
+ * address.  Every float32 and float64 operation is rounded on its own.  For output pixel (x, y), R = refine >= 1:
+ *   side(img, F, G, s):                       s = f64(tau) for the A side, 1.0 - f64(tau) (one subtraction) for the B side
+ *     px = f64(x); py = f64(y)
+ *     repeat R times:                         the fixed-point solve of p + s F(p) = (x, y): gathers only, no scatter
+ *       us = sample(F.u, px, py); vs = sample(F.v, px, py)
+ *       px = f64(x) - s * f64(us); py = f64(y) - s * f64(vs)            product, then subtraction
+ *     us = sample(F.u, px, py); vs = sample(F.v, px, py)                the flow at the solved point
+ *     qx = px + f64(us); qy = py + f64(vs)                              where that point lies in the other frame
+ *     bu = sample(G.u, qx, qy); bv = sample(G.v, qx, qy)
+ *     eu = us + bu; ev = vs + bv; e2 = eu*eu + ev*ev; m2 = (us*us + vs*vs) + (bu*bu + bv*bv)
+ *     ok = inside(px, py) and inside(qx, qy) and e2 <= f32(alpha)*m2 + f32(beta)
+ *     return sample(img, px, py), ok          uint8 frames: the taps converted to float32 first, as the warps do
+ *   a, ok_a = side(A, F, G, tau);  b, ok_b = side(B, G, F, 1 - tau);  t = f32(tau)
+ *   both: out = a + t*(b - a);  only ok_a: out = a;  only ok_b: out = b;  neither: out = A[y][x] + t*(B[y][x] - A[y][x])
+ *   status = ok_a | (ok_b << 1)               3, 1, 2, 0: a byte per output pixel
+ *   uint8 frames: (unsigned char)rintf(out), half to even;  float32 frames: out
+ * Grey planes only; no splatting and no occlusion ordering beyond the forward-backward test; the flows are taken as they are.
+ *
+ * oflk_interpolate_sequence{,_u8}: T frames [T][H][W] in, the (T-1) * n new frames out [T-1][n][H][W] (the frames' type), time
+ * taus[j] of pair t at out[t][j], and status [T-1][n][H][W] (may be NULL).  oflk_pyramidal_sequence_fb's chunk loop (the
+ * bidirectional plan pass, flagged pairs of both directions resolved, oflk_last_resolved() counts them,
+ * oflk_set_host_arithmetic applies to the flows), then one interpolation launch per chunk: only out and status come down, no
+ * flow leaves the device.  It equals oflk_pyramidal_sequence_fb followed by oflk_interpolate_frames_host on those flows, byte
+ * for byte.  Refused before any device call: whatever oflk_pyramidal_sequence_fb refuses, with its codes; and, all
+ * OFLK_ERR_INVALID, n < 1 or n > OFLK_INTERP_MAX_TAUS, a tau that is not finite or not strictly between 0 and 1, refine
+ * outside [1, 8], alpha or beta negative or not finite, NULL taus or out, out overlapping the frames.
+ * oflk_interpolate_frames_host{,_u8}: oflk_interpolate_frames (below) on host arrays -- frames [B+1][H][W], flows [B][H][W],
+ * out and status (may be NULL) [B][n][H][W] -- synchronous; its refusals, NULL flows included. */
+#define OFLK_INTERP_MAX_TAUS 16
+int oflk_interpolate_sequence(const float *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
+                              float beta, int refine, const double *taus, int n, float *out, unsigned char *status);
+int oflk_interpolate_sequence_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                 float alpha, float beta, int refine, const double *taus, int n, unsigned char *out,
+                                 unsigned char *status);
+int oflk_interpolate_frames_host(const float *frames, int B, int H, int W, const float *uf, const float *vf, const float *ub,
+                                 const float *vb, float alpha, float beta, int refine, const double *taus, int n, float *out,
+                                 unsigned char *status);
+int oflk_interpolate_frames_host_u8(const unsigned char *frames, int B, int H, int W, const float *uf, const float *vf,
+                                    const float *ub, const float *vb, float alpha, float beta, int refine, const double *taus,
+                                    int n, unsigned char *out, unsigned char *status);
+
 /* ---- sparse pyramidal LK: points in, points out, no dense flow --------------------------------------------------------- */
 /* The statement (tests/sparse_model.py).  The shape of calcOpticalFlowPyrLK: points in, next points + status + error out,
  * at a cost proportional to N * window^2 * levels * iterations, not to H*W.  Pyramids: build_gaussian_pyramid of each frame,
@@ -1306,6 +1353,16 @@ int oflk_fb_consistency(const float *d_uf, const float *d_vf, const float *d_ub,
 int oflk_track_points(const float *d_uf, const float *d_vf, const float *d_ub, const float *d_vb, int B, int H, int W,
                       float alpha, float beta, int t0, const int *d_qt, const float *d_qxy, int N, float *d_tracks,
                       unsigned char *d_visible, void *stream);
+/* In-between frames of B pairs on their flows (the statement at oflk_interpolate_sequence), device pointers: d_frames
+ * [B+1][H][W] float32, or uint8 with u8 != 0, in the sequence layout (pair b is frames b, b+1); the flows [B][H][W]; taus a
+ * HOST array of n doubles, copied into the launch arguments; d_out [B][n][H][W] of the frames' type and d_status
+ * [B][n][H][W] (may be NULL).  One thread per output pixel, the n times of a pair in adjacent slices of the grid; where B * n
+ * exceeds the grid's z limit the slices go in several launches.  Asynchronous, and capturable into a graph.  B < 1, n < 1 or
+ * n > OFLK_INTERP_MAX_TAUS, a tau that is not finite or not strictly between 0 and 1, refine outside [1, 8], alpha or beta
+ * negative or not finite, NULL d_frames, flows, taus or d_out, d_out overlapping d_frames: OFLK_ERR_INVALID. */
+int oflk_interpolate_frames(const void *d_frames, int u8, int B, int H, int W, const float *d_uf, const float *d_vf,
+                            const float *d_ub, const float *d_vb, float alpha, float beta, int refine, const double *taus,
+                            int n, void *d_out, unsigned char *d_status, void *stream);
 /* Sparse tracks (statement at oflk_sparse_lk) through the plan's B pairs, device pointers: d_frames [B+1][H][W] float32, or
  * uint8 with u8 != 0, are frames t0 .. t0+B.  Builds the B+1 pyramids once, then one track launch (one wave per query,
  * looping over the pairs).  d_qt, d_qxy, N, t0, d_tracks [B+1][N][2], d_visible [B+1][N] and the use of row 0 as

@@ -17,6 +17,7 @@
 #include "oflk_align.hpp"
 #include "oflk_colour.hpp"
 #include "oflk_nv12.hpp"
+#include "oflk_interp.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -2565,6 +2566,172 @@ OFLK_API int oflk_pyramidal_sequence_fb_u8(const unsigned char *frames, int T, i
 {
     return run_sequence_fb<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, uf, vf, ub, vb, err_f, err_b,
                                           valid_f, valid_b);
+}
+
+// ---- motion-compensated frame interpolation --------------------------------------------------------------------------
+namespace {
+// the times, the refinement count and the test's parameters of an interpolation call
+struct InterpConfig { float alpha, beta; int refine; const double *taus; int n; };
+
+bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return pa < pb + nb && pb < pa + na;
+}
+
+// what every form refuses of its settings and of its output (every value OFLK_ERR_INVALID); F frames of px-byte pixels
+int check_interp(const InterpConfig &cfg, const void *frames, int F, int H, int W, size_t px, const void *out)
+{
+    if (cfg.n < 1 || cfg.n > OFLK_INTERP_MAX_TAUS)
+        return fail(OFLK_ERR_INVALID, "n must be in [1, %d] (got %d)", OFLK_INTERP_MAX_TAUS, cfg.n);
+    if (!cfg.taus) return fail(OFLK_ERR_INVALID, "NULL taus");
+    for (int j = 0; j < cfg.n; j++)
+        if (!(std::isfinite(cfg.taus[j]) && cfg.taus[j] > 0.0 && cfg.taus[j] < 1.0))
+            return fail(OFLK_ERR_INVALID, "taus[%d] must be finite and strictly between 0 and 1 (got %g)", j, cfg.taus[j]);
+    if (cfg.refine < 1 || cfg.refine > 8) return fail(OFLK_ERR_INVALID, "refine must be in [1, 8] (got %d)", cfg.refine);
+    if (int rc = check_alpha_beta(cfg.alpha, cfg.beta)) return rc;
+    if (!out) return fail(OFLK_ERR_INVALID, "NULL output");
+    const size_t plane = (size_t)H * W * px;
+    if (ranges_overlap(out, (size_t)(F - 1) * cfg.n * plane, frames, (size_t)F * plane))
+        return fail(OFLK_ERR_INVALID, "the output overlaps the frames");
+    return OFLK_OK;
+}
+
+// the checks of the forms that take flows: B pairs of frames [B+1][H][W]
+int check_interp_flows(const void *frames, bool u8, int B, int H, int W, const void *uf, const void *vf, const void *ub,
+                       const void *vb, const InterpConfig &cfg, const void *out)
+{
+    if (!uf || !vf || !ub || !vb) return fail(OFLK_ERR_INVALID, "NULL flow argument");
+    if (int rc = check_hw(frames, frames, H, W)) return rc;
+    if (B < 1) return fail(OFLK_ERR_INVALID, "B must be >= 1 (got %d)", B);
+    return check_interp(cfg, frames, B + 1, H, W, u8 ? 1 : sizeof(float), out);
+}
+
+// B * n slices of k_interp, cut at the grid's z limit
+int interp_launch(const void *frames, bool u8, int B, int H, int W, const float *uf, const float *vf, const float *ub,
+                  const float *vb, const InterpConfig &cfg, void *out, unsigned char *status, hipStream_t s)
+{
+    constexpr unsigned kMaxZ = 65535;
+    InterpArgs a{};
+    a.H = H; a.W = W; a.n = cfg.n;
+    a.refine = cfg.refine;
+    a.alpha = cfg.alpha; a.beta = cfg.beta;
+    for (int j = 0; j < cfg.n; j++) a.tau[j] = cfg.taus[j];
+    const size_t plane = (size_t)H * W, px = u8 ? 1 : sizeof(float), slices = (size_t)B * cfg.n;
+    for (size_t z0 = 0; z0 < slices; z0 += kMaxZ) {
+        // a launch starts at its first pair: the arrays move there, and the kernel counts slices from that pair's time z0 % n
+        const size_t b0 = z0 / cfg.n;
+        a.z0 = (unsigned)(z0 % cfg.n);
+        a.frames = static_cast<const char *>(frames) + b0 * plane * px;
+        a.uf = uf + b0 * plane; a.vf = vf + b0 * plane; a.ub = ub + b0 * plane; a.vb = vb + b0 * plane;
+        a.out = static_cast<char *>(out) + b0 * cfg.n * plane * px;
+        a.status = status ? status + b0 * cfg.n * plane : nullptr;
+        const dim3 grid = grid2d(W, H, (int)std::min<size_t>(kMaxZ, slices - z0));
+        with_pix(u8, [&](auto PIX) {
+            with_bool(status != nullptr, [&](auto STATUS) {
+                with_bool(W == 1, [&](auto NARROW) {
+                    hipLaunchKernelGGL((k_interp<typename decltype(PIX)::type, decltype(STATUS)::value, decltype(NARROW)::value>),
+                                       grid, dim3(256), 0, s, a);
+                });
+            });
+        });
+        HIP_TRY(hipGetLastError());
+    }
+    return OFLK_OK;
+}
+
+int interp_host(const void *frames, bool u8, int B, int H, int W, const float *uf, const float *vf, const float *ub,
+                const float *vb, const InterpConfig &cfg, void *out, unsigned char *status)
+{
+    int rc = check_interp_flows(frames, u8, B, H, W, uf, vf, ub, vb, cfg, out);
+    if (rc) return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const size_t plane = (size_t)H * W, px = u8 ? 1 : sizeof(float), n_out = (size_t)B * cfg.n * plane;
+    const float *in[4] = {uf, vf, ub, vb};
+    char *d_frames, *d_out;
+    float *d[4];
+    unsigned char *d_status;
+    if ((rc = call.upload(&d_frames, static_cast<const char *>(frames), (size_t)(B + 1) * plane * px))) return rc;
+    for (int i = 0; i < 4; i++)
+        if ((rc = call.upload(&d[i], in[i], (size_t)B * plane))) return rc;
+    if ((rc = call.alloc(&d_out, n_out * px)) || (rc = call.alloc(&d_status, n_out, status)) ||
+        (rc = interp_launch(d_frames, u8, B, H, W, d[0], d[1], d[2], d[3], cfg, d_out, d_status, nullptr)) ||
+        (rc = call.to_host(static_cast<char *>(out), d_out, n_out * px)) || (status && (rc = call.to_host(status, d_status, n_out))))
+        return rc;
+    return call.sync();
+}
+
+// Frames in, in-between frames out, host pointers: run_sequence_fb's chunk loop with one k_interp launch per chunk in the
+// place of the check launch; only out and status come down
+template <class PIXELS>
+int run_sequence_interp(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters,
+                        const InterpConfig &cfg, PIXELS *out, unsigned char *status)
+{
+    const Seq seq{{levels, window_size, iters}, frames, sizeof(PIXELS) == 1, T, H, W};
+    int rc = BidirChunk::check(seq);
+    if (rc || (rc = check_interp(cfg, frames, T, H, W, sizeof(PIXELS), out))) return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const int B = T - 1, C = chunk_pairs(B, H, W);
+    const size_t plane = (size_t)H * W;
+    BidirChunk k{};
+    PIXELS *d_out;
+    unsigned char *d_status;
+    if ((rc = k.alloc(call, seq, C)) || (rc = call.alloc(&d_out, (size_t)C * cfg.n * plane)) ||
+        (rc = call.alloc(&d_status, (size_t)C * cfg.n * plane, status)))
+        return rc;
+    for (int b0 = 0; b0 < B; b0 += C) {
+        const int nb = std::min(C, B - b0);
+        const size_t off = (size_t)b0 * cfg.n * plane, cnt = (size_t)nb * cfg.n * plane;
+        if ((rc = k.run(call, seq, b0, nb)) ||
+            (rc = interp_launch(k.frames, seq.u8, nb, H, W, k.d[0], k.d[1], k.d[2], k.d[3], cfg, d_out, d_status, nullptr)) ||
+            (rc = call.to_host(out + off, d_out, cnt)) || (status && (rc = call.to_host(status + off, d_status, cnt))) ||
+            (rc = call.sync()))
+            return rc;
+    }
+    return OFLK_OK;
+}
+}  // namespace
+
+OFLK_API int oflk_interpolate_frames(const void *d_frames, int u8, int B, int H, int W, const float *d_uf, const float *d_vf,
+                                     const float *d_ub, const float *d_vb, float alpha, float beta, int refine,
+                                     const double *taus, int n, void *d_out, unsigned char *d_status, void *stream)
+{
+    const InterpConfig cfg{alpha, beta, refine, taus, n};
+    int rc = check_interp_flows(d_frames, u8 != 0, B, H, W, d_uf, d_vf, d_ub, d_vb, cfg, d_out);
+    if (rc) return rc;
+    return interp_launch(d_frames, u8 != 0, B, H, W, d_uf, d_vf, d_ub, d_vb, cfg, d_out, d_status, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_interpolate_frames_host(const float *frames, int B, int H, int W, const float *uf, const float *vf,
+                                          const float *ub, const float *vb, float alpha, float beta, int refine,
+                                          const double *taus, int n, float *out, unsigned char *status)
+{
+    return interp_host(frames, false, B, H, W, uf, vf, ub, vb, InterpConfig{alpha, beta, refine, taus, n}, out, status);
+}
+
+OFLK_API int oflk_interpolate_frames_host_u8(const unsigned char *frames, int B, int H, int W, const float *uf, const float *vf,
+                                             const float *ub, const float *vb, float alpha, float beta, int refine,
+                                             const double *taus, int n, unsigned char *out, unsigned char *status)
+{
+    return interp_host(frames, true, B, H, W, uf, vf, ub, vb, InterpConfig{alpha, beta, refine, taus, n}, out, status);
+}
+
+OFLK_API int oflk_interpolate_sequence(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                       float alpha, float beta, int refine, const double *taus, int n, float *out,
+                                       unsigned char *status)
+{
+    return run_sequence_interp<float>(frames, T, H, W, levels, window_size, iters, InterpConfig{alpha, beta, refine, taus, n},
+                                      out, status);
+}
+
+OFLK_API int oflk_interpolate_sequence_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size,
+                                          int iters, float alpha, float beta, int refine, const double *taus, int n,
+                                          unsigned char *out, unsigned char *status)
+{
+    return run_sequence_interp<unsigned char>(frames, T, H, W, levels, window_size, iters,
+                                              InterpConfig{alpha, beta, refine, taus, n}, out, status);
 }
 
 // ---- Shi-Tomasi corners ----------------------------------------------------------------------------------------------

@@ -41,6 +41,7 @@ _ROBUST = [_F, _I]                  # ... robust_delta, photometric, of the robu
 _ALIGN_D_IO = [_vp, _vp, _vp, _Z, _vp, _vp, _vp]        # d_model_in, d_status_in, d_workspace, workspace_bytes, d_model_out, d_status_out, d_stats
 _ALIGN_H_IO = [_f32p, _i32p, _f32p, _i32p, _f64p]       # model_in, status_in, model_out, status_out, stats
 _STAB_OUT = [_f32p, _f32p, _i32p, _vp]                  # correction, model_out, counts_out, held (behind the frames out)
+_INTERP = [_F, _F, _I, _f64p, _I]   # InterpConfig: alpha, beta, refine, taus, n (Interp)
 
 # every exported symbol of include/oflk.h: name -> (restype, argtypes)
 SIGNATURES = {
@@ -93,6 +94,11 @@ SIGNATURES = {
     "oflk_fb_consistency_host": (ctypes.c_int, [_f32p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [_f32p, _f32p, _vp, _vp]),
     "oflk_pyramidal_sequence_fb": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 2 + [_f32p] * 6 + [_vp, _vp]),
     "oflk_pyramidal_sequence_fb_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 2 + [_f32p] * 6 + [_vp, _vp]),
+    "oflk_interpolate_frames": (ctypes.c_int, [_vp] + [_I] * 4 + [_vp] * 4 + _INTERP + [_vp, _vp, _vp]),
+    "oflk_interpolate_frames_host": (ctypes.c_int, [_f32p] + [_I] * 3 + [_f32p] * 4 + _INTERP + [_f32p, _vp]),
+    "oflk_interpolate_frames_host_u8": (ctypes.c_int, [_vp] + [_I] * 3 + [_f32p] * 4 + _INTERP + [_vp, _vp]),
+    "oflk_interpolate_sequence": (ctypes.c_int, [_f32p] + [_I] * 6 + _INTERP + [_f32p, _vp]),
+    "oflk_interpolate_sequence_u8": (ctypes.c_int, [_vp] + [_I] * 6 + _INTERP + [_vp, _vp]),
     "oflk_track_points": (ctypes.c_int, [_vp] * 4 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, _vp]),
     "oflk_track_points_host": (ctypes.c_int, [_f32p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
     "oflk_pyramidal_sequence_tracks": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 2 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
@@ -516,6 +522,47 @@ def fb_consistency(d_uf: int, d_vf: int, d_ub: int, d_vb: int, B: int, H: int, W
     """oflk_fb_consistency on device pointers ([B][H][W]; err float32, valid uint8); 0 leaves an output out (not all four)."""
     check(lib().oflk_fb_consistency(d_uf, d_vf, d_ub, d_vb, int(B), int(H), int(W), float(alpha), float(beta),
                                     d_err_f or None, d_err_b or None, d_valid_f or None, d_valid_b or None, stream))
+
+
+INTERP_MAX_TAUS = 16   # OFLK_INTERP_MAX_TAUS
+
+
+class Interp(NamedTuple):
+    """The settings of the interpolation calls, in the argument order of the C ABI (InterpConfig); taus is kept alive here"""
+    alpha: float
+    beta: float
+    refine: int
+    taus: np.ndarray   # float64 (n,)
+
+    def args(self):
+        return self.alpha, self.beta, self.refine, _f64(self.taus), len(self.taus)
+
+
+def check_interp(alpha: float, beta: float, refine, taus, factor=None) -> Interp:
+    """The interpolation settings as the library takes them.  taus None: factor = k >= 2 stands for j / k, j = 1 .. k-1,
+    formed in float64.  ValueError for alpha, beta as check_fb_params, a refine outside [1, 8], a factor that is not an
+    integer in [2, INTERP_MAX_TAUS + 1], taus that are not 1 .. INTERP_MAX_TAUS finite values strictly between 0 and 1."""
+    a, b = check_fb_params(alpha, beta)
+    refine = check_int("refine", refine, 1, 8)
+    if taus is None:
+        k = check_int("factor", factor, 2, INTERP_MAX_TAUS + 1)
+        taus = np.arange(1, k, dtype=np.float64) / np.float64(k)
+    t = np.ascontiguousarray(taus, np.float64)
+    if t.ndim != 1 or not 1 <= t.size <= INTERP_MAX_TAUS:
+        raise ValueError(f"taus must be 1 to {INTERP_MAX_TAUS} values, got shape {t.shape}")
+    if not np.all(np.isfinite(t) & (t > 0) & (t < 1)):
+        raise ValueError(f"every tau must be finite and strictly between 0 and 1, got {t.tolist()!r}")
+    return Interp(a, b, refine, t)
+
+
+def interpolate_frames(d_frames: int, B: int, H: int, W: int, d_uf: int, d_vf: int, d_ub: int, d_vb: int, taus, d_out: int,
+                       d_status: int = 0, alpha: float = 0.01, beta: float = 0.5, refine: int = 2, u8: bool = False,
+                       stream: int = 0) -> None:
+    """oflk_interpolate_frames on device pointers: frames [B+1][H][W] (uint8 with u8), flows [B][H][W], the in-between frames
+    of the times taus into d_out [B][n][H][W] of the frames' type and d_status [B][n][H][W] uint8 (0: no status)."""
+    cfg = check_interp(alpha, beta, refine, taus)
+    check(lib().oflk_interpolate_frames(d_frames, int(bool(u8)), int(B), int(H), int(W), d_uf, d_vf, d_ub, d_vb, *cfg.args(),
+                                        d_out, d_status or None, stream))
 
 
 def as_queries(queries, T: int) -> Tuple[Optional[np.ndarray], np.ndarray]:

@@ -271,6 +271,61 @@ def lucas_kanade_pyramidal_sequence_tracks(frames, queries, num_levels: int = 3,
     return SequenceTracks(tracks, visible.astype(bool))
 
 
+def interpolate_frames(frames, u_fwd, v_fwd, u_bwd, v_bwd, taus=(0.5,), alpha: float = 0.01, beta: float = 0.5, refine: int = 2,
+                       return_status: bool = False):
+    """In-between frames of a (B+1, H, W) frame sequence on given dense flows, motion compensated.
+
+    frames: as lucas_kanade_pyramidal_sequence_fb (all uint8: the uint8 path); the flows are (B, H, W) float32 as that call
+    returns them.  Returns new (B, n, H, W) in the frames' type, new[b, j] at time taus[j] in (0, 1) between frames b and
+    b+1; with return_status also status (B, n, H, W) uint8: bit 0 the sample of frame b passed, bit 1 that of frame b+1.
+    Each side solves p + s F(p) = (x, y) by `refine` fixed-point steps (gathers only), samples its frame at p when p and its
+    target pass the forward-backward test (alpha, beta), and the two are blended by tau; where only one side passes it is
+    taken alone, where neither does the frames are cross-faded.
+    """
+    cfg = _oflk.check_interp(alpha, beta, refine, taus)
+    arr, _ = _oflk.as_sequence(frames)
+    T, H, W = arr.shape
+    flows = [np.ascontiguousarray(f, np.float32) for f in (u_fwd, v_fwd, u_bwd, v_bwd)]
+    for f in flows:
+        if f.shape != (T - 1, H, W):
+            raise ValueError(f"every flow must have shape {(T - 1, H, W)}, got {f.shape}")
+    n = len(cfg.taus)
+    new, status = np.empty((T - 1, n, H, W), arr.dtype), np.empty((T - 1, n, H, W), np.uint8)
+    src, fn = _oflk.pixels(arr, "oflk_interpolate_frames_host")
+    _oflk.check(fn(src, T - 1, H, W, *(_oflk.ptr(f) for f in flows), *cfg.args(), _oflk.pix(new),
+                   status.ctypes.data if return_status else None))
+    return (new, status) if return_status else new
+
+
+class SequenceInterpolated(NamedTuple):
+    """Result of lucas_kanade_pyramidal_sequence_interpolate on T frames and n times a pair"""
+    frames: np.ndarray   # ((T-1) * n + T, H, W) in the input type: the originals and the new frames in time order
+    new: np.ndarray      # (T-1, n, H, W): new[t, j] at time taus[j] between frames t and t+1
+    status: np.ndarray   # (T-1, n, H, W) uint8: bit 0 frame t's sample passed, bit 1 frame t+1's
+
+
+def lucas_kanade_pyramidal_sequence_interpolate(frames, factor: int = 2, taus=None, num_levels: int = 3, window_size: int = 5,
+                                                num_iterations: int = 3, alpha: float = 0.01, beta: float = 0.5,
+                                                refine: int = 2) -> SequenceInterpolated:
+    """Frame-rate conversion: frames in, the in-between frames of every consecutive pair out.
+
+    factor=k inserts the k-1 frames at times j / k, j = 1 .. k-1 (formed in float64); explicit taus (ascending for `frames`
+    to be in time order) override it.  The flows of lucas_kanade_pyramidal_sequence_fb and the interpolation of
+    interpolate_frames run on the device: only the new frames and their status come back.
+    """
+    cfg = _oflk.check_interp(alpha, beta, refine, taus, factor)
+    arr, _ = _oflk.as_sequence(frames)
+    T, H, W = arr.shape
+    n = len(cfg.taus)
+    both = np.empty((T - 1, n + 1, H, W), arr.dtype)   # frame t, then its n new frames
+    new, status = np.empty((T - 1, n, H, W), arr.dtype), np.empty((T - 1, n, H, W), np.uint8)
+    src, fn = _oflk.pixels(arr, "oflk_interpolate_sequence")
+    _oflk.check(fn(src, T, H, W, int(num_levels), int(window_size), int(num_iterations), *cfg.args(), _oflk.pix(new),
+                   status.ctypes.data))
+    both[:, 0], both[:, 1:] = arr[:-1], new
+    return SequenceInterpolated(np.concatenate([both.reshape(-1, H, W), arr[-1:]]), new, status)
+
+
 class SequenceKLT(NamedTuple):
     """Result of lucas_kanade_pyramidal_sequence_klt: n features of frame 0 and their tracks (row t is frame t)."""
     xy: np.ndarray        # (n, 2) float32 (x, y) in acceptance order

@@ -274,7 +274,8 @@ int oflk_track_points_host(const float *uf, const float *vf, const float *ub, co
  *   both: out = a + t*(b - a);  only ok_a: out = a;  only ok_b: out = b;  neither: out = A[y][x] + t*(B[y][x] - A[y][x])
  *   status = ok_a | (ok_b << 1)               3, 1, 2, 0: a byte per output pixel
  *   uint8 frames: (unsigned char)rintf(out), half to even;  float32 frames: out
- * Grey planes only; no splatting and no occlusion ordering beyond the forward-backward test; the flows are taken as they are.
+ * These are grey planes (packed colour and NV12: below); no splatting and no occlusion ordering beyond the forward-backward
+ * test; the flows are taken as they are.
  *
  * oflk_interpolate_sequence{,_u8}: T frames [T][H][W] in, the (T-1) * n new frames out [T-1][n][H][W] (the frames' type), time
  * taus[j] of pair t at out[t][j], and status [T-1][n][H][W] (may be NULL).  oflk_pyramidal_sequence_fb's chunk loop (the
@@ -298,6 +299,54 @@ int oflk_interpolate_frames_host(const float *frames, int B, int H, int W, const
 int oflk_interpolate_frames_host_u8(const unsigned char *frames, int B, int H, int W, const float *uf, const float *vf,
                                     const float *ub, const float *vb, float alpha, float beta, int refine, const double *taus,
                                     int n, unsigned char *out, unsigned char *status);
+
+/* Interpolation of colour and NV12 video: the statement (tests/interp_colour_model.py) on top of the grey one above, whose
+ * side, sample, inside, status cases and rintf these are.  One solve per output position serves every channel.
+ *
+ * Packed colour: frames uint8 [B+1][H][W][C], C = 3 or 4, the flows [B][H][W] float32 taken as given, out [B][n][H][W][C],
+ * status [B][n][H][W].  For every channel c, out[..., c] is the uint8 grey statement on the planes frames[..., c] under these
+ * flows, and status is that statement's: ok depends on the flows only, so it is the same for every channel.  A fourth channel
+ * is interpolated like the others.
+ *
+ * NV12: layout, siting and shapes as the NV12 warps' (oflk_nv12_frame_bytes, OFLK_SITING_*, H and W even and >= 4); out
+ * [B][n][H W 3 / 2], status [B][n][H][W].  The Y plane of out is the uint8 grey statement on the Y planes (H W 3 / 2 bytes
+ * apart) and status is that statement's.  Chroma: CH = H/2, CW = W/2, P_c[f] the CH x CW plane UV[f][:, :, c], c in {U, V};
+ * the siting gives sx in {0, 0.5} and sy = 0.5.  Output chroma sample (column i, row j) sits at the luma position
+ * X = f64(2 i) + sx, Y = f64(2 j) + sy, both exact, and runs the grey side's solve with (f64(x), f64(y)) replaced by (X, Y):
+ * the same flows, R, forward-backward test and inside tests against the H x W luma frame.  That gives (px, py) and ok of the A
+ * side (s = f64(tau)) and of the B side (s = 1.0 - f64(tau)).  A side's value for channel c is sample(P_c, cx, cy) with
+ *     cx = clamp(0.5 * (px - sx), 0, CW - 1);  cy = clamp(0.5 * (py - sy), 0, CH - 1)        one subtraction, one product, float64
+ *     clamp(v, lo, hi) = v < lo ? lo : (v > hi ? hi : v)
+ * The clamp: a point inside the luma frame lies up to half a chroma sample beyond the chroma plane's first or last row or
+ * column, where the sample's cval 0 would bleed saturated green into the frame's edge.  Where (px, py) is not inside the luma
+ * frame ok is 0 and the value is not used (no chroma tap of that point is read).  With t = f32(tau): both sides ok
+ * a + t*(b - a); only one its value; neither P_c[A][j][i] + t*(P_c[B][j][i] - P_c[A][j][i]); then (unsigned char)rintf(.).  The
+ * chroma positions' ok bits are not returned.
+ *
+ * oflk_interpolate_sequence_packed: frames [T][H][W][C] in, out [T-1][n][H][W][C] and status [T-1][n][H][W] (may be NULL).  It
+ * equals oflk_luma_u8_host(order) on the frames, oflk_pyramidal_sequence_fb_u8 on that luma and
+ * oflk_interpolate_frames_packed_host on the colour frames and those flows, byte for byte.  oflk_interpolate_sequence_nv12:
+ * frames [T][H W 3 / 2], out [T-1][n][H W 3 / 2]; it equals oflk_pyramidal_sequence_fb_u8 on the Y planes gathered
+ * contiguously, then oflk_interpolate_frames_nv12_host.  Both run oflk_interpolate_sequence's chunk loop: a chunk's frames go
+ * up once in their own layout, the luma or the Y planes of the flow pass are formed from them on the device, no flow leaves
+ * it and only out and status come down; oflk_last_resolved() and oflk_set_host_arithmetic as there.
+ * Refused before any device call, in this order: channels other than 3 or 4, an order (sequence call) or a siting that is
+ * not one of the constants, H or W odd or below 4 (NV12): OFLK_ERR_INVALID; T < 2 (B < 1); H or W < 2, NULL frames or out:
+ * OFLK_ERR_INVALID; 2^30 pixels or more, 2^23 rows or columns or more, packed frames of 2^31 bytes or more:
+ * OFLK_ERR_UNSUPPORTED; then what the grey forms refuse, with out overlapping the frames measured in the layout's frame
+ * bytes.  The _host forms: oflk_interpolate_frames_packed / _nv12 (below) on host arrays, synchronous. */
+int oflk_interpolate_sequence_packed(const unsigned char *frames, int T, int H, int W, int channels, int order, int levels,
+                                     int window_size, int iters, float alpha, float beta, int refine, const double *taus,
+                                     int n, unsigned char *out, unsigned char *status);
+int oflk_interpolate_sequence_nv12(const unsigned char *frames, int T, int H, int W, int siting, int levels, int window_size,
+                                   int iters, float alpha, float beta, int refine, const double *taus, int n,
+                                   unsigned char *out, unsigned char *status);
+int oflk_interpolate_frames_packed_host(const unsigned char *frames, int B, int H, int W, int channels, const float *uf,
+                                        const float *vf, const float *ub, const float *vb, float alpha, float beta,
+                                        int refine, const double *taus, int n, unsigned char *out, unsigned char *status);
+int oflk_interpolate_frames_nv12_host(const unsigned char *frames, int B, int H, int W, int siting, const float *uf,
+                                      const float *vf, const float *ub, const float *vb, float alpha, float beta, int refine,
+                                      const double *taus, int n, unsigned char *out, unsigned char *status);
 
 /* ---- sparse pyramidal LK: points in, points out, no dense flow --------------------------------------------------------- */
 /* The statement (tests/sparse_model.py).  The shape of calcOpticalFlowPyrLK: points in, next points + status + error out,
@@ -1363,6 +1412,24 @@ int oflk_track_points(const float *d_uf, const float *d_vf, const float *d_ub, c
 int oflk_interpolate_frames(const void *d_frames, int u8, int B, int H, int W, const float *d_uf, const float *d_vf,
                             const float *d_ub, const float *d_vb, float alpha, float beta, int refine, const double *taus,
                             int n, void *d_out, unsigned char *d_status, void *stream);
+/* The same for packed colour frames (the statement at oflk_interpolate_sequence_packed), device pointers: d_frames uint8
+ * [B+1][H][W][channels], channels 3 or 4, d_out [B][n][H][W][channels], d_status [B][n][H][W] (may be NULL); flows and taus as
+ * oflk_interpolate_frames.  One thread per output pixel: the two solves, the ok bits and the bilinear weights are formed once
+ * and every channel is finished on them; a tap is one dword that holds all channels of its pixel, and no load leaves its
+ * frame.  Slices and the grid's z limit as oflk_interpolate_frames.  No alignment is asked of any array.  Asynchronous, and
+ * capturable into a graph.  Refusals: the list at oflk_interpolate_sequence_packed, with NULL flows. */
+int oflk_interpolate_frames_packed(const unsigned char *d_frames, int B, int H, int W, int channels, const float *d_uf,
+                                   const float *d_vf, const float *d_ub, const float *d_vb, float alpha, float beta, int refine,
+                                   const double *taus, int n, unsigned char *d_out, unsigned char *d_status, void *stream);
+/* The same for NV12 frames (the statement at oflk_interpolate_sequence_packed), device pointers: d_frames [B+1][H W 3 / 2],
+ * d_out [B][n][H W 3 / 2], d_status [B][n][H][W] (may be NULL), siting OFLK_SITING_*; the flows [B][H][W] are the Y planes'.  One
+ * launch for both planes of the slices: luma blocks, then the blocks of the H/2 x W/2 chroma plane, where a lane does one
+ * solve per chroma sample, gathers each tap as one 2-byte load holding U and V and finishes both on one set of weights.  No
+ * alignment is asked of any array.  Asynchronous, and capturable into a graph.  Refusals: the list at
+ * oflk_interpolate_sequence_packed, with NULL flows. */
+int oflk_interpolate_frames_nv12(const unsigned char *d_frames, int B, int H, int W, int siting, const float *d_uf,
+                                 const float *d_vf, const float *d_ub, const float *d_vb, float alpha, float beta, int refine,
+                                 const double *taus, int n, unsigned char *d_out, unsigned char *d_status, void *stream);
 /* Sparse tracks (statement at oflk_sparse_lk) through the plan's B pairs, device pointers: d_frames [B+1][H][W] float32, or
  * uint8 with u8 != 0, are frames t0 .. t0+B.  Builds the B+1 pyramids once, then one track launch (one wave per query,
  * looping over the pairs).  d_qt, d_qxy, N, t0, d_tracks [B+1][N][2], d_visible [B+1][N] and the use of row 0 as

@@ -2467,10 +2467,19 @@ struct BidirChunk {
     int run(HostCall &call, const Seq &seq, int b0, int nb)
     {
         const size_t fb = seq.frame_bytes();
+        return compute(call, seq, nb, [&] {
+            return call.to_device(frames, static_cast<const char *>(seq.frames) + (size_t)b0 * fb, (size_t)(nb + 1) * fb);
+        });
+    }
+    // the same for nb pairs whose nb+1 frames fill() puts into `frames` on the null stream, from wherever it has them (a
+    // colour or NV12 call forms them on the device from the chunk it has sent up): seq.frames is not read
+    template <class FILL>
+    int compute(HostCall &call, const Seq &seq, int nb, FILL &&fill)
+    {
+        const size_t fb = seq.frame_bytes();
         oflk_plan *p = nullptr;
         int rc = host_plan(*call.c, call.dev, nb, seq.H, seq.W, seq.levels, seq.window_size, seq.iters, &p);
-        if (rc || (rc = call.to_device(frames, static_cast<const char *>(seq.frames) + (size_t)b0 * fb, (size_t)(nb + 1) * fb)) ||
-            (rc = plan_pyramidal(p, frames, frames + fb, seq.u8, d[0], d[1], nullptr, true, d[2], d[3])))
+        if (rc || (rc = fill()) || (rc = plan_pyramidal(p, frames, frames + fb, seq.u8, d[0], d[1], nullptr, true, d[2], d[3])))
             return rc;
         int n_res = 0;
         if (seq.iters > 0 && (rc = resolve_uncertain_fb(p, frames, seq.u8, d[0], d[1], d[2], d[3], nullptr, &n_res))) return rc;
@@ -2566,172 +2575,6 @@ OFLK_API int oflk_pyramidal_sequence_fb_u8(const unsigned char *frames, int T, i
 {
     return run_sequence_fb<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, uf, vf, ub, vb, err_f, err_b,
                                           valid_f, valid_b);
-}
-
-// ---- motion-compensated frame interpolation --------------------------------------------------------------------------
-namespace {
-// the times, the refinement count and the test's parameters of an interpolation call
-struct InterpConfig { float alpha, beta; int refine; const double *taus; int n; };
-
-bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb + nb && pb < pa + na;
-}
-
-// what every form refuses of its settings and of its output (every value OFLK_ERR_INVALID); F frames of px-byte pixels
-int check_interp(const InterpConfig &cfg, const void *frames, int F, int H, int W, size_t px, const void *out)
-{
-    if (cfg.n < 1 || cfg.n > OFLK_INTERP_MAX_TAUS)
-        return fail(OFLK_ERR_INVALID, "n must be in [1, %d] (got %d)", OFLK_INTERP_MAX_TAUS, cfg.n);
-    if (!cfg.taus) return fail(OFLK_ERR_INVALID, "NULL taus");
-    for (int j = 0; j < cfg.n; j++)
-        if (!(std::isfinite(cfg.taus[j]) && cfg.taus[j] > 0.0 && cfg.taus[j] < 1.0))
-            return fail(OFLK_ERR_INVALID, "taus[%d] must be finite and strictly between 0 and 1 (got %g)", j, cfg.taus[j]);
-    if (cfg.refine < 1 || cfg.refine > 8) return fail(OFLK_ERR_INVALID, "refine must be in [1, 8] (got %d)", cfg.refine);
-    if (int rc = check_alpha_beta(cfg.alpha, cfg.beta)) return rc;
-    if (!out) return fail(OFLK_ERR_INVALID, "NULL output");
-    const size_t plane = (size_t)H * W * px;
-    if (ranges_overlap(out, (size_t)(F - 1) * cfg.n * plane, frames, (size_t)F * plane))
-        return fail(OFLK_ERR_INVALID, "the output overlaps the frames");
-    return OFLK_OK;
-}
-
-// the checks of the forms that take flows: B pairs of frames [B+1][H][W]
-int check_interp_flows(const void *frames, bool u8, int B, int H, int W, const void *uf, const void *vf, const void *ub,
-                       const void *vb, const InterpConfig &cfg, const void *out)
-{
-    if (!uf || !vf || !ub || !vb) return fail(OFLK_ERR_INVALID, "NULL flow argument");
-    if (int rc = check_hw(frames, frames, H, W)) return rc;
-    if (B < 1) return fail(OFLK_ERR_INVALID, "B must be >= 1 (got %d)", B);
-    return check_interp(cfg, frames, B + 1, H, W, u8 ? 1 : sizeof(float), out);
-}
-
-// B * n slices of k_interp, cut at the grid's z limit
-int interp_launch(const void *frames, bool u8, int B, int H, int W, const float *uf, const float *vf, const float *ub,
-                  const float *vb, const InterpConfig &cfg, void *out, unsigned char *status, hipStream_t s)
-{
-    constexpr unsigned kMaxZ = 65535;
-    InterpArgs a{};
-    a.H = H; a.W = W; a.n = cfg.n;
-    a.refine = cfg.refine;
-    a.alpha = cfg.alpha; a.beta = cfg.beta;
-    for (int j = 0; j < cfg.n; j++) a.tau[j] = cfg.taus[j];
-    const size_t plane = (size_t)H * W, px = u8 ? 1 : sizeof(float), slices = (size_t)B * cfg.n;
-    for (size_t z0 = 0; z0 < slices; z0 += kMaxZ) {
-        // a launch starts at its first pair: the arrays move there, and the kernel counts slices from that pair's time z0 % n
-        const size_t b0 = z0 / cfg.n;
-        a.z0 = (unsigned)(z0 % cfg.n);
-        a.frames = static_cast<const char *>(frames) + b0 * plane * px;
-        a.uf = uf + b0 * plane; a.vf = vf + b0 * plane; a.ub = ub + b0 * plane; a.vb = vb + b0 * plane;
-        a.out = static_cast<char *>(out) + b0 * cfg.n * plane * px;
-        a.status = status ? status + b0 * cfg.n * plane : nullptr;
-        const dim3 grid = grid2d(W, H, (int)std::min<size_t>(kMaxZ, slices - z0));
-        with_pix(u8, [&](auto PIX) {
-            with_bool(status != nullptr, [&](auto STATUS) {
-                with_bool(W == 1, [&](auto NARROW) {
-                    hipLaunchKernelGGL((k_interp<typename decltype(PIX)::type, decltype(STATUS)::value, decltype(NARROW)::value>),
-                                       grid, dim3(256), 0, s, a);
-                });
-            });
-        });
-        HIP_TRY(hipGetLastError());
-    }
-    return OFLK_OK;
-}
-
-int interp_host(const void *frames, bool u8, int B, int H, int W, const float *uf, const float *vf, const float *ub,
-                const float *vb, const InterpConfig &cfg, void *out, unsigned char *status)
-{
-    int rc = check_interp_flows(frames, u8, B, H, W, uf, vf, ub, vb, cfg, out);
-    if (rc) return rc;
-    HostCall call;
-    if ((rc = call.begin())) return rc;
-    const size_t plane = (size_t)H * W, px = u8 ? 1 : sizeof(float), n_out = (size_t)B * cfg.n * plane;
-    const float *in[4] = {uf, vf, ub, vb};
-    char *d_frames, *d_out;
-    float *d[4];
-    unsigned char *d_status;
-    if ((rc = call.upload(&d_frames, static_cast<const char *>(frames), (size_t)(B + 1) * plane * px))) return rc;
-    for (int i = 0; i < 4; i++)
-        if ((rc = call.upload(&d[i], in[i], (size_t)B * plane))) return rc;
-    if ((rc = call.alloc(&d_out, n_out * px)) || (rc = call.alloc(&d_status, n_out, status)) ||
-        (rc = interp_launch(d_frames, u8, B, H, W, d[0], d[1], d[2], d[3], cfg, d_out, d_status, nullptr)) ||
-        (rc = call.to_host(static_cast<char *>(out), d_out, n_out * px)) || (status && (rc = call.to_host(status, d_status, n_out))))
-        return rc;
-    return call.sync();
-}
-
-// Frames in, in-between frames out, host pointers: run_sequence_fb's chunk loop with one k_interp launch per chunk in the
-// place of the check launch; only out and status come down
-template <class PIXELS>
-int run_sequence_interp(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters,
-                        const InterpConfig &cfg, PIXELS *out, unsigned char *status)
-{
-    const Seq seq{{levels, window_size, iters}, frames, sizeof(PIXELS) == 1, T, H, W};
-    int rc = BidirChunk::check(seq);
-    if (rc || (rc = check_interp(cfg, frames, T, H, W, sizeof(PIXELS), out))) return rc;
-    HostCall call;
-    if ((rc = call.begin())) return rc;
-    const int B = T - 1, C = chunk_pairs(B, H, W);
-    const size_t plane = (size_t)H * W;
-    BidirChunk k{};
-    PIXELS *d_out;
-    unsigned char *d_status;
-    if ((rc = k.alloc(call, seq, C)) || (rc = call.alloc(&d_out, (size_t)C * cfg.n * plane)) ||
-        (rc = call.alloc(&d_status, (size_t)C * cfg.n * plane, status)))
-        return rc;
-    for (int b0 = 0; b0 < B; b0 += C) {
-        const int nb = std::min(C, B - b0);
-        const size_t off = (size_t)b0 * cfg.n * plane, cnt = (size_t)nb * cfg.n * plane;
-        if ((rc = k.run(call, seq, b0, nb)) ||
-            (rc = interp_launch(k.frames, seq.u8, nb, H, W, k.d[0], k.d[1], k.d[2], k.d[3], cfg, d_out, d_status, nullptr)) ||
-            (rc = call.to_host(out + off, d_out, cnt)) || (status && (rc = call.to_host(status + off, d_status, cnt))) ||
-            (rc = call.sync()))
-            return rc;
-    }
-    return OFLK_OK;
-}
-}  // namespace
-
-OFLK_API int oflk_interpolate_frames(const void *d_frames, int u8, int B, int H, int W, const float *d_uf, const float *d_vf,
-                                     const float *d_ub, const float *d_vb, float alpha, float beta, int refine,
-                                     const double *taus, int n, void *d_out, unsigned char *d_status, void *stream)
-{
-    const InterpConfig cfg{alpha, beta, refine, taus, n};
-    int rc = check_interp_flows(d_frames, u8 != 0, B, H, W, d_uf, d_vf, d_ub, d_vb, cfg, d_out);
-    if (rc) return rc;
-    return interp_launch(d_frames, u8 != 0, B, H, W, d_uf, d_vf, d_ub, d_vb, cfg, d_out, d_status, (hipStream_t)stream);
-}
-
-OFLK_API int oflk_interpolate_frames_host(const float *frames, int B, int H, int W, const float *uf, const float *vf,
-                                          const float *ub, const float *vb, float alpha, float beta, int refine,
-                                          const double *taus, int n, float *out, unsigned char *status)
-{
-    return interp_host(frames, false, B, H, W, uf, vf, ub, vb, InterpConfig{alpha, beta, refine, taus, n}, out, status);
-}
-
-OFLK_API int oflk_interpolate_frames_host_u8(const unsigned char *frames, int B, int H, int W, const float *uf, const float *vf,
-                                             const float *ub, const float *vb, float alpha, float beta, int refine,
-                                             const double *taus, int n, unsigned char *out, unsigned char *status)
-{
-    return interp_host(frames, true, B, H, W, uf, vf, ub, vb, InterpConfig{alpha, beta, refine, taus, n}, out, status);
-}
-
-OFLK_API int oflk_interpolate_sequence(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
-                                       float alpha, float beta, int refine, const double *taus, int n, float *out,
-                                       unsigned char *status)
-{
-    return run_sequence_interp<float>(frames, T, H, W, levels, window_size, iters, InterpConfig{alpha, beta, refine, taus, n},
-                                      out, status);
-}
-
-OFLK_API int oflk_interpolate_sequence_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size,
-                                          int iters, float alpha, float beta, int refine, const double *taus, int n,
-                                          unsigned char *out, unsigned char *status)
-{
-    return run_sequence_interp<unsigned char>(frames, T, H, W, levels, window_size, iters,
-                                              InterpConfig{alpha, beta, refine, taus, n}, out, status);
 }
 
 // ---- Shi-Tomasi corners ----------------------------------------------------------------------------------------------
@@ -4652,6 +4495,290 @@ OFLK_API int oflk_stabilize_sequence_nv12(const unsigned char *frames, int T, in
     return stabilize_sequence(FrameLayout::nv12(siting), frames, T, H, W,
                               {{levels, window_size, iters}, {alpha, beta, max_residual}, {quality_level, min_distance, max_corners, detect_every}},
                               {model, hypotheses, threshold, seed}, {weights, radius}, out, correction, model_out, counts_out, held);
+}
+
+// =============================================================================
+// motion-compensated frame interpolation of every layout (oflk_interp.hpp)
+// =============================================================================
+namespace {
+// the times, the refinement count and the test's parameters of an interpolation call
+struct InterpConfig { float alpha, beta; int refine; const double *taus; int n; };
+// the four flows of the pairs of an interpolation call, [B][H][W] each
+struct InterpFlows {
+    const float *uf, *vf, *ub, *vb;
+    bool any_null() const { return !uf || !vf || !ub || !vb; }
+};
+
+bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return pa < pb + nb && pb < pa + na;
+}
+
+// what every form refuses of its settings and of its output (every value OFLK_ERR_INVALID); F frames of frame_bytes each
+int check_interp(const InterpConfig &cfg, const void *frames, int F, size_t frame_bytes, const void *out)
+{
+    if (cfg.n < 1 || cfg.n > OFLK_INTERP_MAX_TAUS)
+        return fail(OFLK_ERR_INVALID, "n must be in [1, %d] (got %d)", OFLK_INTERP_MAX_TAUS, cfg.n);
+    if (!cfg.taus) return fail(OFLK_ERR_INVALID, "NULL taus");
+    for (int j = 0; j < cfg.n; j++)
+        if (!(std::isfinite(cfg.taus[j]) && cfg.taus[j] > 0.0 && cfg.taus[j] < 1.0))
+            return fail(OFLK_ERR_INVALID, "taus[%d] must be finite and strictly between 0 and 1 (got %g)", j, cfg.taus[j]);
+    if (cfg.refine < 1 || cfg.refine > 8) return fail(OFLK_ERR_INVALID, "refine must be in [1, 8] (got %d)", cfg.refine);
+    if (int rc = check_alpha_beta(cfg.alpha, cfg.beta)) return rc;
+    if (!out) return fail(OFLK_ERR_INVALID, "NULL output");
+    if (ranges_overlap(out, (size_t)(F - 1) * cfg.n * frame_bytes, frames, (size_t)F * frame_bytes))
+        return fail(OFLK_ERR_INVALID, "the output overlaps the frames");
+    return OFLK_OK;
+}
+
+// The checks of the forms that take flows: B pairs of frames [B+1] of layout L.  A packed or NV12 call refuses its layout
+// first and its frames as every call of that layout does (check_frames), then what the grey forms refuse.
+int check_interp_flows(const FrameLayout &L, const void *frames, int B, int H, int W, const InterpFlows &fl, const InterpConfig &cfg,
+                       const void *out)
+{
+    if (L.kind == FrameKind::Planar) {
+        if (fl.any_null()) return fail(OFLK_ERR_INVALID, "NULL flow argument");
+        if (int rc = check_hw(frames, frames, H, W)) return rc;
+        if (B < 1) return fail(OFLK_ERR_INVALID, "B must be >= 1 (got %d)", B);
+    } else {
+        if (int rc = check_layout(L, H, W)) return rc;
+        if (B < 1) return fail(OFLK_ERR_INVALID, "B must be >= 1 (got %d)", B);
+        if (int rc = check_frames(L, frames, B + 1, H, W, out)) return rc;
+        if (fl.any_null()) return fail(OFLK_ERR_INVALID, "NULL flow argument");
+    }
+    return check_interp(cfg, frames, B + 1, L.frame_bytes(H, W), out);
+}
+
+// B * n slices of the layout's kernel, cut at the grid's z limit; the arguments are checked
+int interp_launch(const FrameLayout &L, const void *frames, int B, int H, int W, const InterpFlows &fl, const InterpConfig &cfg,
+                  void *out, unsigned char *status, hipStream_t s)
+{
+    constexpr unsigned kMaxZ = 65535;
+    InterpNv12Args nv{};
+    InterpArgs &a = nv.g;
+    a.H = H; a.W = W; a.n = cfg.n;
+    a.refine = cfg.refine;
+    a.alpha = cfg.alpha; a.beta = cfg.beta;
+    for (int j = 0; j < cfg.n; j++) a.tau[j] = cfg.taus[j];
+    nv.sx = L.siting == OFLK_SITING_CENTER ? 0.5 : 0.0;
+    nv.sy = 0.5;
+    const unsigned cols = (unsigned)((W + 63) / 64);
+    nv.luma_groups = (unsigned)((H + 3) / 4);
+    nv.chroma_cols = (unsigned)((W / 2 + 63) / 64);
+    const unsigned chroma_blocks = (unsigned)((H / 2 + 3) / 4) * nv.chroma_cols;
+    const size_t plane = (size_t)H * W, fb = L.frame_bytes(H, W), slices = (size_t)B * cfg.n;
+    for (size_t z0 = 0; z0 < slices; z0 += kMaxZ) {
+        // a launch starts at its first pair: the arrays move there, and the kernel counts slices from that pair's time z0 % n
+        const size_t b0 = z0 / cfg.n;
+        a.z0 = (unsigned)(z0 % cfg.n);
+        a.frames = static_cast<const char *>(frames) + b0 * fb;
+        a.uf = fl.uf + b0 * plane; a.vf = fl.vf + b0 * plane; a.ub = fl.ub + b0 * plane; a.vb = fl.vb + b0 * plane;
+        a.out = static_cast<char *>(out) + b0 * cfg.n * fb;
+        a.status = status ? status + b0 * cfg.n * plane : nullptr;
+        const int nz = (int)std::min<size_t>(kMaxZ, slices - z0);
+        with_bool(status != nullptr, [&](auto STATUS) {
+            constexpr bool ST = decltype(STATUS)::value;
+            switch (L.kind) {
+            case FrameKind::Planar:
+                with_pix(L.pix_bytes == 1, [&](auto PIX) {
+                    with_bool(W == 1, [&](auto NARROW) {
+                        hipLaunchKernelGGL((k_interp<typename decltype(PIX)::type, ST, decltype(NARROW)::value>), grid2d(W, H, nz),
+                                           dim3(256), 0, s, a);
+                    });
+                });
+                break;
+            case FrameKind::Packed:   // a lane's store: one dword for C = 4 where out is 4-byte aligned, else bytes
+                with_int<3, 4>(L.channels, [&](auto C) {
+                    with_bool(L.channels == 4 && aligned(a.out, 4), [&](auto VEC) {
+                        if constexpr (decltype(C)::value == 4 || !decltype(VEC)::value)
+                            hipLaunchKernelGGL((k_interp_packed<decltype(C)::value, ST, decltype(VEC)::value>), grid2d(W, H, nz),
+                                               dim3(256), 0, s, a);
+                    });
+                });
+                break;
+            case FrameKind::Nv12:   // a chroma lane's store: its pair as 2 bytes at once where out is 2-byte aligned
+                with_bool(aligned(a.out, 2), [&](auto VEC) {
+                    hipLaunchKernelGGL((k_interp_nv12<ST, decltype(VEC)::value>),
+                                       dim3(nv.luma_groups + (chroma_blocks + cols - 1) / cols, cols, (unsigned)nz), dim3(256), 0, s, nv);
+                });
+                break;
+            }
+        });
+        HIP_TRY(hipGetLastError());
+    }
+    return OFLK_OK;
+}
+
+int interp_device(const FrameLayout &L, const void *d_frames, int B, int H, int W, const InterpFlows &fl, const InterpConfig &cfg,
+                  void *d_out, unsigned char *d_status, void *stream)
+{
+    if (int rc = check_interp_flows(L, d_frames, B, H, W, fl, cfg, d_out)) return rc;
+    return interp_launch(L, d_frames, B, H, W, fl, cfg, d_out, d_status, (hipStream_t)stream);
+}
+
+int interp_host(const FrameLayout &L, const void *frames, int B, int H, int W, const InterpFlows &fl, const InterpConfig &cfg,
+                void *out, unsigned char *status)
+{
+    int rc = check_interp_flows(L, frames, B, H, W, fl, cfg, out);
+    if (rc) return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const size_t plane = (size_t)H * W, fb = L.frame_bytes(H, W), n_out = (size_t)B * cfg.n;
+    const float *in[4] = {fl.uf, fl.vf, fl.ub, fl.vb};
+    char *d_frames, *d_out;
+    float *d[4];
+    unsigned char *d_status;
+    if ((rc = call.upload(&d_frames, static_cast<const char *>(frames), (size_t)(B + 1) * fb))) return rc;
+    for (int i = 0; i < 4; i++)
+        if ((rc = call.upload(&d[i], in[i], (size_t)B * plane))) return rc;
+    if ((rc = call.alloc(&d_out, n_out * fb)) || (rc = call.alloc(&d_status, n_out * plane, status)) ||
+        (rc = interp_launch(L, d_frames, B, H, W, {d[0], d[1], d[2], d[3]}, cfg, d_out, d_status, nullptr)) ||
+        (rc = call.to_host(static_cast<char *>(out), d_out, n_out * fb)) ||
+        (status && (rc = call.to_host(status, d_status, n_out * plane))))
+        return rc;
+    return call.sync();
+}
+
+// Frames in, in-between frames out, host pointers: run_sequence_fb's chunk loop with one interpolation launch per chunk in
+// the place of the check launch; only out and status come down.  Grey frames are the flow pass's own.  A chunk of packed or
+// NV12 frames goes up once into a buffer of the layout; the planes the flows are tracked on are formed from it on the device
+// (the luma of packed frames by luma_launch, the Y planes of NV12 frames by one strided copy) and the interpolation reads
+// the chunk where it lies.
+int run_sequence_interp(const FrameLayout &L, const void *frames, int T, int H, int W, const PyrWindow &pyr, const InterpConfig &cfg,
+                        void *out, unsigned char *status)
+{
+    const bool planar = L.kind == FrameKind::Planar;
+    const Seq seq{pyr, frames, L.pix_bytes == 1, T, H, W};
+    t_resolved = 0;
+    int rc = OFLK_OK;
+    if (!planar) {
+        if ((rc = check_layout(L, H, W))) return rc;
+        if (T < 2) return fail(OFLK_ERR_INVALID, "a sequence needs T >= 2 frames (got %d)", T);
+        if ((rc = check_frames(L, frames, T, H, W, out))) return rc;
+    }
+    const size_t plane = (size_t)H * W, fb = L.frame_bytes(H, W);
+    if ((rc = BidirChunk::check(seq)) || (rc = check_interp(cfg, frames, T, fb, out))) return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const int B = T - 1, C = chunk_pairs(B, H, W);
+    BidirChunk k{};
+    char *d_out;
+    unsigned char *d_status, *d_video = nullptr;
+    if ((rc = k.alloc(call, seq, C)) || (rc = call.alloc(&d_video, (size_t)(C + 1) * fb, !planar)) ||
+        (rc = call.alloc(&d_out, (size_t)C * cfg.n * fb)) || (rc = call.alloc(&d_status, (size_t)C * cfg.n * plane, status)))
+        return rc;
+    const unsigned char *src = static_cast<const unsigned char *>(frames);
+    unsigned char *luma = reinterpret_cast<unsigned char *>(k.frames);
+    for (int b0 = 0; b0 < B; b0 += C) {
+        const int nb = std::min(C, B - b0);
+        const size_t o = (size_t)b0 * cfg.n, cnt = (size_t)nb * cfg.n;
+        if (planar) {
+            rc = k.run(call, seq, b0, nb);
+        } else {
+            rc = k.compute(call, seq, nb, [&] {
+                if (int e = call.to_device(d_video, src + (size_t)b0 * fb, (size_t)(nb + 1) * fb)) return e;
+                if (L.kind == FrameKind::Packed) return luma_launch(d_video, nb + 1, H, W, L.channels, L.order, luma, nullptr);
+                HIP_TRY(hipMemcpy2DAsync(luma, plane, d_video, fb, plane, (size_t)(nb + 1), hipMemcpyDeviceToDevice, nullptr));
+                return (int)OFLK_OK;
+            });
+        }
+        if (rc || (rc = interp_launch(L, planar ? k.frames : reinterpret_cast<char *>(d_video), nb, H, W, {k.d[0], k.d[1], k.d[2], k.d[3]},
+                                      cfg, d_out, d_status, nullptr)) ||
+            (rc = call.to_host(static_cast<char *>(out) + o * fb, d_out, cnt * fb)) ||
+            (status && (rc = call.to_host(status + o * plane, d_status, cnt * plane))) || (rc = call.sync()))
+            return rc;
+    }
+    return OFLK_OK;
+}
+}  // namespace
+
+// ---- the interpolation calls: device, host and sequence forms of the four layouts ----
+OFLK_API int oflk_interpolate_frames(const void *d_frames, int u8, int B, int H, int W, const float *d_uf, const float *d_vf,
+                                     const float *d_ub, const float *d_vb, float alpha, float beta, int refine,
+                                     const double *taus, int n, void *d_out, unsigned char *d_status, void *stream)
+{
+    return interp_device(FrameLayout::planar(u8 != 0), d_frames, B, H, W, {d_uf, d_vf, d_ub, d_vb}, {alpha, beta, refine, taus, n},
+                         d_out, d_status, stream);
+}
+
+OFLK_API int oflk_interpolate_frames_packed(const unsigned char *d_frames, int B, int H, int W, int channels, const float *d_uf,
+                                            const float *d_vf, const float *d_ub, const float *d_vb, float alpha, float beta,
+                                            int refine, const double *taus, int n, unsigned char *d_out, unsigned char *d_status,
+                                            void *stream)
+{
+    return interp_device(FrameLayout::packed(channels, OFLK_ORDER_RGB), d_frames, B, H, W, {d_uf, d_vf, d_ub, d_vb},
+                         {alpha, beta, refine, taus, n}, d_out, d_status, stream);
+}
+
+OFLK_API int oflk_interpolate_frames_nv12(const unsigned char *d_frames, int B, int H, int W, int siting, const float *d_uf,
+                                          const float *d_vf, const float *d_ub, const float *d_vb, float alpha, float beta,
+                                          int refine, const double *taus, int n, unsigned char *d_out, unsigned char *d_status,
+                                          void *stream)
+{
+    return interp_device(FrameLayout::nv12(siting), d_frames, B, H, W, {d_uf, d_vf, d_ub, d_vb}, {alpha, beta, refine, taus, n}, d_out,
+                         d_status, stream);
+}
+
+OFLK_API int oflk_interpolate_frames_host(const float *frames, int B, int H, int W, const float *uf, const float *vf,
+                                          const float *ub, const float *vb, float alpha, float beta, int refine,
+                                          const double *taus, int n, float *out, unsigned char *status)
+{
+    return interp_host(FrameLayout::planar(false), frames, B, H, W, {uf, vf, ub, vb}, {alpha, beta, refine, taus, n}, out, status);
+}
+
+OFLK_API int oflk_interpolate_frames_host_u8(const unsigned char *frames, int B, int H, int W, const float *uf, const float *vf,
+                                             const float *ub, const float *vb, float alpha, float beta, int refine,
+                                             const double *taus, int n, unsigned char *out, unsigned char *status)
+{
+    return interp_host(FrameLayout::planar(true), frames, B, H, W, {uf, vf, ub, vb}, {alpha, beta, refine, taus, n}, out, status);
+}
+
+OFLK_API int oflk_interpolate_frames_packed_host(const unsigned char *frames, int B, int H, int W, int channels, const float *uf,
+                                                 const float *vf, const float *ub, const float *vb, float alpha, float beta,
+                                                 int refine, const double *taus, int n, unsigned char *out, unsigned char *status)
+{
+    return interp_host(FrameLayout::packed(channels, OFLK_ORDER_RGB), frames, B, H, W, {uf, vf, ub, vb},
+                       {alpha, beta, refine, taus, n}, out, status);
+}
+
+OFLK_API int oflk_interpolate_frames_nv12_host(const unsigned char *frames, int B, int H, int W, int siting, const float *uf,
+                                               const float *vf, const float *ub, const float *vb, float alpha, float beta,
+                                               int refine, const double *taus, int n, unsigned char *out, unsigned char *status)
+{
+    return interp_host(FrameLayout::nv12(siting), frames, B, H, W, {uf, vf, ub, vb}, {alpha, beta, refine, taus, n}, out, status);
+}
+
+OFLK_API int oflk_interpolate_sequence(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                       float alpha, float beta, int refine, const double *taus, int n, float *out,
+                                       unsigned char *status)
+{
+    return run_sequence_interp(FrameLayout::planar(false), frames, T, H, W, {levels, window_size, iters},
+                               {alpha, beta, refine, taus, n}, out, status);
+}
+
+OFLK_API int oflk_interpolate_sequence_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size,
+                                          int iters, float alpha, float beta, int refine, const double *taus, int n,
+                                          unsigned char *out, unsigned char *status)
+{
+    return run_sequence_interp(FrameLayout::planar(true), frames, T, H, W, {levels, window_size, iters},
+                               {alpha, beta, refine, taus, n}, out, status);
+}
+
+OFLK_API int oflk_interpolate_sequence_packed(const unsigned char *frames, int T, int H, int W, int channels, int order,
+                                              int levels, int window_size, int iters, float alpha, float beta, int refine,
+                                              const double *taus, int n, unsigned char *out, unsigned char *status)
+{
+    return run_sequence_interp(FrameLayout::packed(channels, order), frames, T, H, W, {levels, window_size, iters},
+                               {alpha, beta, refine, taus, n}, out, status);
+}
+
+OFLK_API int oflk_interpolate_sequence_nv12(const unsigned char *frames, int T, int H, int W, int siting, int levels,
+                                            int window_size, int iters, float alpha, float beta, int refine, const double *taus,
+                                            int n, unsigned char *out, unsigned char *status)
+{
+    return run_sequence_interp(FrameLayout::nv12(siting), frames, T, H, W, {levels, window_size, iters},
+                               {alpha, beta, refine, taus, n}, out, status);
 }
 
 // =============================================================================

@@ -99,6 +99,12 @@ SIGNATURES = {
     "oflk_interpolate_frames_host_u8": (ctypes.c_int, [_vp] + [_I] * 3 + [_f32p] * 4 + _INTERP + [_vp, _vp]),
     "oflk_interpolate_sequence": (ctypes.c_int, [_f32p] + [_I] * 6 + _INTERP + [_f32p, _vp]),
     "oflk_interpolate_sequence_u8": (ctypes.c_int, [_vp] + [_I] * 6 + _INTERP + [_vp, _vp]),
+    "oflk_interpolate_frames_packed": (ctypes.c_int, [_vp] + [_I] * 4 + [_vp] * 4 + _INTERP + [_vp, _vp, _vp]),
+    "oflk_interpolate_frames_nv12": (ctypes.c_int, [_vp] + [_I] * 4 + [_vp] * 4 + _INTERP + [_vp, _vp, _vp]),
+    "oflk_interpolate_frames_packed_host": (ctypes.c_int, [_vp] + [_I] * 4 + [_f32p] * 4 + _INTERP + [_vp, _vp]),
+    "oflk_interpolate_frames_nv12_host": (ctypes.c_int, [_vp] + [_I] * 4 + [_f32p] * 4 + _INTERP + [_vp, _vp]),
+    "oflk_interpolate_sequence_packed": (ctypes.c_int, [_vp] + [_I] * 8 + _INTERP + [_vp, _vp]),
+    "oflk_interpolate_sequence_nv12": (ctypes.c_int, [_vp] + [_I] * 7 + _INTERP + [_vp, _vp]),
     "oflk_track_points": (ctypes.c_int, [_vp] * 4 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, _vp]),
     "oflk_track_points_host": (ctypes.c_int, [_f32p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
     "oflk_pyramidal_sequence_tracks": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 2 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
@@ -563,6 +569,51 @@ def interpolate_frames(d_frames: int, B: int, H: int, W: int, d_uf: int, d_vf: i
     cfg = check_interp(alpha, beta, refine, taus)
     check(lib().oflk_interpolate_frames(d_frames, int(bool(u8)), int(B), int(H), int(W), d_uf, d_vf, d_ub, d_vb, *cfg.args(),
                                         d_out, d_status or None, stream))
+
+
+def interpolate_frames_layout(layout: "FrameLayout", d_frames: int, B: int, H: int, W: int, d_uf: int, d_vf: int, d_ub: int,
+                              d_vb: int, taus, d_out: int, d_status: int = 0, alpha: float = 0.01, beta: float = 0.5,
+                              refine: int = 2, stream: int = 0) -> None:
+    """oflk_interpolate_frames_packed (layout ("_packed", (channels,))) or oflk_interpolate_frames_nv12 (("_nv12", (siting,)))
+    on device pointers: uint8 frames [B+1] and d_out [B][n] of the layout's frames, flows [B][H][W], d_status [B][n][H][W]
+    (0: no status); asynchronous."""
+    cfg = check_interp(alpha, beta, refine, taus)
+    fn = getattr(lib(), "oflk_interpolate_frames" + layout.suffix)
+    check(fn(d_frames or None, int(B), int(H), int(W), int(layout.args[0]), d_uf or None, d_vf or None, d_ub or None, d_vb or None,
+             *cfg.args(), d_out or None, d_status or None, stream))
+
+
+def interpolate_host(layout: "FrameLayout", arr: np.ndarray, H: int, W: int, flows, cfg: Interp, status: bool):
+    """oflk_interpolate_frames_host[_u8] (the default layout) or oflk_interpolate_frames{_packed,_nv12}_host on a contiguous
+    array of B+1 frames of the layout and four float32 flows (B, H, W): (new (B, n) + the frame's shape, status (B, n, H, W)
+    or None)"""
+    B, n = arr.shape[0] - 1, len(cfg.taus)
+    flows = [np.ascontiguousarray(f, np.float32) for f in flows]
+    for f in flows:
+        if f.shape != (B, H, W):
+            raise ValueError(f"every flow must have shape {(B, H, W)}, got {f.shape}")
+    new = np.empty((B, n) + arr.shape[1:], arr.dtype)
+    st = np.empty((B, n, H, W), np.uint8) if status else None
+    if layout.suffix:
+        src, fn = arr.ctypes.data, getattr(lib(), "oflk_interpolate_frames" + layout.suffix + "_host")
+    else:
+        src, fn = pixels(arr, "oflk_interpolate_frames_host")
+    check(fn(src, B, H, W, *layout.args[:1], *(ptr(f) for f in flows), *cfg.args(), pix(new), None if st is None else st.ctypes.data))
+    return new, st
+
+
+def interpolate_sequence_host(layout: "FrameLayout", arr: np.ndarray, H: int, W: int, levels: int, window_size: int, iters: int,
+                              cfg: Interp):
+    """oflk_interpolate_sequence[_u8] (the default layout) or oflk_interpolate_sequence{_packed,_nv12} on a contiguous array
+    of T frames of the layout: (new (T-1, n) + the frame's shape, status (T-1, n, H, W))"""
+    T, n = arr.shape[0], len(cfg.taus)
+    new, st = np.empty((T - 1, n) + arr.shape[1:], arr.dtype), np.empty((T - 1, n, H, W), np.uint8)
+    if layout.suffix:
+        src, fn = arr.ctypes.data, getattr(lib(), "oflk_interpolate_sequence" + layout.suffix)
+    else:
+        src, fn = pixels(arr, "oflk_interpolate_sequence")
+    check(fn(src, T, H, W, *layout.args, int(levels), int(window_size), int(iters), *cfg.args(), pix(new), st.ctypes.data))
+    return new, st
 
 
 def as_queries(queries, T: int) -> Tuple[Optional[np.ndarray], np.ndarray]:

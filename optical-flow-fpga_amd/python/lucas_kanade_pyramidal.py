@@ -271,6 +271,30 @@ def lucas_kanade_pyramidal_sequence_tracks(frames, queries, num_levels: int = 3,
     return SequenceTracks(tracks, visible.astype(bool))
 
 
+def _interp_layout(frames, order, what):
+    """(layout, contiguous array, H, W) of grey frames (the default layout) or of a 4-D uint8 array of colour frames"""
+    if _oflk.is_packed(frames):
+        arr = _oflk.as_packed(frames, what)
+        if arr.shape[0] < 2:
+            raise ValueError(f"a sequence needs at least 2 frames, got {arr.shape[0]}")
+        return _oflk.FrameLayout("_packed", (arr.shape[3], _oflk.check_colour_order(order))), arr, arr.shape[1], arr.shape[2]
+    arr, _ = _oflk.as_sequence(frames)
+    return _oflk.FrameLayout(), arr, arr.shape[1], arr.shape[2]
+
+
+def _interp_nv12(frames, siting, what):
+    code = _oflk.check_nv12_siting(siting)
+    arr = _oflk.as_nv12(frames, what)
+    if arr.shape[0] < 2:
+        raise ValueError(f"a sequence needs at least 2 frames, got {arr.shape[0]}")
+    return _oflk.FrameLayout("_nv12", (code,)), arr, 2 * arr.shape[1] // 3, arr.shape[2]
+
+
+def _interpolate_frames(layout, arr, H, W, flows, cfg, return_status):
+    new, status = _oflk.interpolate_host(layout, arr, H, W, flows, cfg, bool(return_status))
+    return (new, status) if return_status else new
+
+
 def interpolate_frames(frames, u_fwd, v_fwd, u_bwd, v_bwd, taus=(0.5,), alpha: float = 0.01, beta: float = 0.5, refine: int = 2,
                        return_status: bool = False):
     """In-between frames of a (B+1, H, W) frame sequence on given dense flows, motion compensated.
@@ -281,49 +305,65 @@ def interpolate_frames(frames, u_fwd, v_fwd, u_bwd, v_bwd, taus=(0.5,), alpha: f
     Each side solves p + s F(p) = (x, y) by `refine` fixed-point steps (gathers only), samples its frame at p when p and its
     target pass the forward-backward test (alpha, beta), and the two are blended by tau; where only one side passes it is
     taken alone, where neither does the frames are cross-faded.
+    A 4-D uint8 array (B+1, H, W, C), C = 3 or 4, is interleaved colour: new is (B, n, H, W, C), every channel the grey result
+    of its plane from one solve per pixel, and status stays (B, n, H, W).
     """
     cfg = _oflk.check_interp(alpha, beta, refine, taus)
-    arr, _ = _oflk.as_sequence(frames)
-    T, H, W = arr.shape
-    flows = [np.ascontiguousarray(f, np.float32) for f in (u_fwd, v_fwd, u_bwd, v_bwd)]
-    for f in flows:
-        if f.shape != (T - 1, H, W):
-            raise ValueError(f"every flow must have shape {(T - 1, H, W)}, got {f.shape}")
-    n = len(cfg.taus)
-    new, status = np.empty((T - 1, n, H, W), arr.dtype), np.empty((T - 1, n, H, W), np.uint8)
-    src, fn = _oflk.pixels(arr, "oflk_interpolate_frames_host")
-    _oflk.check(fn(src, T - 1, H, W, *(_oflk.ptr(f) for f in flows), *cfg.args(), _oflk.pix(new),
-                   status.ctypes.data if return_status else None))
-    return (new, status) if return_status else new
+    layout, arr, H, W = _interp_layout(frames, "rgb", "(B+1, H, W, C)")
+    return _interpolate_frames(layout, arr, H, W, (u_fwd, v_fwd, u_bwd, v_bwd), cfg, return_status)
+
+
+def interpolate_frames_nv12(video, u_fwd, v_fwd, u_bwd, v_bwd, taus=(0.5,), siting: str = "left", alpha: float = 0.01,
+                            beta: float = 0.5, refine: int = 2, return_status: bool = False):
+    """interpolate_frames for NV12 frames, both planes in one launch: video (B+1, 3H/2, W) uint8 (nv12_from_planes), the flows
+    (B, H, W) those of the Y planes.  new is (B, n, 3H/2, W): its Y plane is interpolate_frames' on the Y planes, a chroma
+    sample solves from its luma position (`siting`: "left" or "center") and samples U and V there, clamped to the chroma
+    plane; status (B, n, H, W) is the Y plane's."""
+    cfg = _oflk.check_interp(alpha, beta, refine, taus)
+    layout, arr, H, W = _interp_nv12(video, siting, "(B+1, 3H/2, W)")
+    return _interpolate_frames(layout, arr, H, W, (u_fwd, v_fwd, u_bwd, v_bwd), cfg, return_status)
 
 
 class SequenceInterpolated(NamedTuple):
-    """Result of lucas_kanade_pyramidal_sequence_interpolate on T frames and n times a pair"""
-    frames: np.ndarray   # ((T-1) * n + T, H, W) in the input type: the originals and the new frames in time order
-    new: np.ndarray      # (T-1, n, H, W): new[t, j] at time taus[j] between frames t and t+1
+    """Result of lucas_kanade_pyramidal_sequence_interpolate on T frames and n times a pair; a frame is (H, W), (H, W, C) for
+    colour or (3H/2, W) for NV12"""
+    frames: np.ndarray   # ((T-1) * n + T,) + frame in the input type: the originals and the new frames in time order
+    new: np.ndarray      # (T-1, n) + frame: new[t, j] at time taus[j] between frames t and t+1
     status: np.ndarray   # (T-1, n, H, W) uint8: bit 0 frame t's sample passed, bit 1 frame t+1's
+
+
+def _sequence_interpolate(layout, arr, H, W, num_levels, window_size, num_iterations, cfg) -> SequenceInterpolated:
+    new, status = _oflk.interpolate_sequence_host(layout, arr, H, W, num_levels, window_size, num_iterations, cfg)
+    T, n = arr.shape[0], len(cfg.taus)
+    both = np.empty((T - 1, n + 1) + arr.shape[1:], arr.dtype)   # frame t, then its n new frames
+    both[:, 0], both[:, 1:] = arr[:-1], new
+    return SequenceInterpolated(np.concatenate([both.reshape((-1,) + arr.shape[1:]), arr[-1:]]), new, status)
 
 
 def lucas_kanade_pyramidal_sequence_interpolate(frames, factor: int = 2, taus=None, num_levels: int = 3, window_size: int = 5,
                                                 num_iterations: int = 3, alpha: float = 0.01, beta: float = 0.5,
-                                                refine: int = 2) -> SequenceInterpolated:
+                                                refine: int = 2, order: str = "rgb") -> SequenceInterpolated:
     """Frame-rate conversion: frames in, the in-between frames of every consecutive pair out.
 
     factor=k inserts the k-1 frames at times j / k, j = 1 .. k-1 (formed in float64); explicit taus (ascending for `frames`
     to be in time order) override it.  The flows of lucas_kanade_pyramidal_sequence_fb and the interpolation of
     interpolate_frames run on the device: only the new frames and their status come back.
+    A 4-D uint8 array (T, H, W, C), C = 3 or 4, is interleaved colour: the flows are tracked on its luma (rgb_to_luma, `order`
+    "rgb" or "bgr"), formed on the device, and every channel is interpolated on them.
     """
     cfg = _oflk.check_interp(alpha, beta, refine, taus, factor)
-    arr, _ = _oflk.as_sequence(frames)
-    T, H, W = arr.shape
-    n = len(cfg.taus)
-    both = np.empty((T - 1, n + 1, H, W), arr.dtype)   # frame t, then its n new frames
-    new, status = np.empty((T - 1, n, H, W), arr.dtype), np.empty((T - 1, n, H, W), np.uint8)
-    src, fn = _oflk.pixels(arr, "oflk_interpolate_sequence")
-    _oflk.check(fn(src, T, H, W, int(num_levels), int(window_size), int(num_iterations), *cfg.args(), _oflk.pix(new),
-                   status.ctypes.data))
-    both[:, 0], both[:, 1:] = arr[:-1], new
-    return SequenceInterpolated(np.concatenate([both.reshape(-1, H, W), arr[-1:]]), new, status)
+    layout, arr, H, W = _interp_layout(frames, order, "(T, H, W, C)")
+    return _sequence_interpolate(layout, arr, H, W, num_levels, window_size, num_iterations, cfg)
+
+
+def lucas_kanade_pyramidal_sequence_interpolate_nv12(video, factor: int = 2, taus=None, num_levels: int = 3, window_size: int = 5,
+                                                     num_iterations: int = 3, alpha: float = 0.01, beta: float = 0.5,
+                                                     refine: int = 2, siting: str = "left") -> SequenceInterpolated:
+    """lucas_kanade_pyramidal_sequence_interpolate for NV12 video (T, 3H/2, W) uint8 (nv12_from_planes): the flows are tracked
+    on the Y planes where they lie, and both planes of the new frames come from interpolate_frames_nv12's kernel."""
+    cfg = _oflk.check_interp(alpha, beta, refine, taus, factor)
+    layout, arr, H, W = _interp_nv12(video, siting, "(T, 3H/2, W)")
+    return _sequence_interpolate(layout, arr, H, W, num_levels, window_size, num_iterations, cfg)
 
 
 class SequenceKLT(NamedTuple):

@@ -1494,7 +1494,21 @@ int oflk_replenish_features(const void *d_frame, int u8, int H, int W, int windo
  * this statement).  Exit decisions and iteration counts are the reference's.
  * Non-finite values: NaN and +-inf pixels and flows give the reference's values in every entry point, flows and stages
  * (oflk_gradients included: the zero taps of the Sobel kernels are multiplied too, so 0 * inf is NaN, as in the
- * reference's convolve2d). */
+ * reference's convolve2d).
+ * Subnormal values: a Sobel product a * (1/8) or a * (1/4) is exact unless it is subnormal, where it rounds; convolve2d
+ * rounds the product and then adds it, and so do oflk_gradients and the alignment kernels' template gradients (whose
+ * float64 sums count subnormal gradients), value for value.  The flow kernels and the sparse tracker fuse the product
+ * into the addition; where that could differ every product of two gradients underflows to 0, det is 0 and nothing is
+ * solved, as in the reference.
+ * Beyond the flow paths, the float32 forms of these calls are held to their statements on frames outside [0, 255]
+ * (signed, x 257, x 1e9, x 1e12 with pixels near +-3e38, subnormal on and off the 2^9-ulp grid, underflowing products,
+ * NaN / +-inf pixels; tests/test_gpu_ranges_features.py, every cell): oflk_sparse_lk, the sparse tracks and the online
+ * tracker; oflk_warp_affine and oflk_warp_perspective; oflk_interpolate_frames; the mosaic's accumulate / resolve with
+ * and without exposure; oflk_align_refine, its photometric and robust forms and oflk_align_weights.  A non-finite pixel
+ * is a value like any other there: it reaches an output through every sample that reads it, with weight 0 too (0 * inf
+ * and 0 * NaN are NaN, as in map_coordinates), and through no other; masks, counts and the status of interpolation
+ * depend on positions only.  A sample at a NaN coordinate is cval 0, as one outside the frame (oflk_sparse_lk's residual
+ * where the displacement is NaN: finite frames whose window sums overflow give that). */
 int oflk_plan_read_log(oflk_plan *plan, float *residual_log, int *iters_run, void *stream);
 
 /* After oflk_plan_pyramidal + read_log: uncertain[b*levels + l] has bit k set when the early-exit test

@@ -205,19 +205,21 @@ __device__ __forceinline__ void align_tile(const AlignReduceArgs &a, int s, int 
     for (int i = 0; i < rows; i++) {
         const int y = y0 + i;
         load3(min(y + 1, H - 1), ap, tn);
-        // compute_gradients' Sobel / 8 (k_gradients: the same taps in the same order, the kernels' zero taps last)
+        // compute_gradients' Sobel / 8 (k_gradients: the same taps in the same order, each product rounded on its own --
+        // exact unless it is subnormal -- and then added; the kernels' zero taps last).  Two roundings a tap only because the
+        // translation unit is built with -ffp-contract=off, as at k_gradients.
         float ix = ap[2] * -0.125f;
-        ix = fmaf(ap[0], 0.125f, ix);
-        ix = fmaf(a0[2], -0.25f, ix);
-        ix = fmaf(a0[0], 0.25f, ix);
-        ix = fmaf(am[2], -0.125f, ix);
-        ix = fmaf(am[0], 0.125f, ix);
+        ix = ix + ap[0] * 0.125f;
+        ix = ix + a0[2] * -0.25f;
+        ix = ix + a0[0] * 0.25f;
+        ix = ix + am[2] * -0.125f;
+        ix = ix + am[0] * 0.125f;
         float iy = ap[2] * -0.125f;
-        iy = fmaf(ap[1], -0.25f, iy);
-        iy = fmaf(ap[0], -0.125f, iy);
-        iy = fmaf(am[2], 0.125f, iy);
-        iy = fmaf(am[1], 0.25f, iy);
-        iy = fmaf(am[0], 0.125f, iy);
+        iy = iy + ap[1] * -0.25f;
+        iy = iy + ap[0] * -0.125f;
+        iy = iy + am[2] * 0.125f;
+        iy = iy + am[1] * 0.25f;
+        iy = iy + am[0] * 0.125f;
         ix = fmaf(ap[1], 0.0f, ix);
         ix = fmaf(a0[1], 0.0f, ix);
         ix = fmaf(am[1], 0.0f, ix);

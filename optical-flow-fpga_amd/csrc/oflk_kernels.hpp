@@ -53,11 +53,12 @@ struct BilinearTaps {
 __device__ __forceinline__ BilinearTaps bilinear_taps(int H, int W, double y, double x)
 {
     BilinearTaps t;
-    t.inside = !(y < 0.0 || y > (double)(H - 1) || x < 0.0 || x > (double)(W - 1));
+    // the closed range test, written positively: a NaN coordinate is outside, as for map_coordinates, which gives cval there
+    t.inside = y >= 0.0 && y <= (double)(H - 1) && x >= 0.0 && x <= (double)(W - 1);
     double fy = floor(y), fx = floor(x);
     int y0 = (int)fy, x0 = (int)fx;
-    // keep addresses legal for non-finite coordinates (never produced from finite
-    // inputs; the value is discarded or multiplied into NaN anyway)
+    // keep addresses legal for non-finite coordinates (finite frames produce them: a window sum that overflows to
+    // inf - inf gives a NaN displacement); such a point is outside and its taps are not used
     y0 = min(max(y0, 0), H - 1);
     x0 = min(max(x0, 0), W - 1);
     double ry = y - fy, rx = x - fx;
@@ -3149,18 +3150,27 @@ __global__ __launch_bounds__(256) void k_gradients(const float *__restrict__ pre
     float a_mm = avg(y - 1, x - 1), a_m0 = avg(y - 1, x), a_mp = avg(y - 1, x + 1);
     float a_0m = avg(y, x - 1), a_0p = avg(y, x + 1);
     float a_pm = avg(y + 1, x - 1), a_p0 = avg(y + 1, x), a_pp = avg(y + 1, x + 1);
-    float ix = a_pp * -0.125f;
-    ix = fmaf(a_pm, 0.125f, ix);
-    ix = fmaf(a_0p, -0.25f, ix);
-    ix = fmaf(a_0m, 0.25f, ix);
-    ix = fmaf(a_mp, -0.125f, ix);
-    ix = fmaf(a_mm, 0.125f, ix);
-    float iy = a_pp * -0.125f;
-    iy = fmaf(a_p0, -0.25f, iy);
-    iy = fmaf(a_pm, -0.125f, iy);
-    iy = fmaf(a_mp, 0.125f, iy);
-    iy = fmaf(a_m0, 0.25f, iy);
-    iy = fmaf(a_mm, 0.125f, iy);
+    // convolve2d rounds every product and then adds it.  A product by a power of two is exact unless it is subnormal, where
+    // it rounds: an fma would round once and differ on ties, so the six products are formed on their own and added in
+    // convolve2d's order.  Like every "rounded on its own" in this library, that rests on -ffp-contract=off, which the
+    // Makefile gives the one translation unit (__fmul_rn / __fadd_rn are plain * and + in this toolchain's headers and
+    // contract like them).
+    const float x_pp = a_pp * -0.125f, x_pm = a_pm * 0.125f, x_0p = a_0p * -0.25f, x_0m = a_0m * 0.25f;
+    const float x_mp = a_mp * -0.125f, x_mm = a_mm * 0.125f;
+    float ix = x_pp;
+    ix = ix + x_pm;
+    ix = ix + x_0p;
+    ix = ix + x_0m;
+    ix = ix + x_mp;
+    ix = ix + x_mm;
+    const float y_pp = a_pp * -0.125f, y_p0 = a_p0 * -0.25f, y_pm = a_pm * -0.125f, y_mp = a_mp * 0.125f;
+    const float y_m0 = a_m0 * 0.25f, y_mm = a_mm * 0.125f;
+    float iy = y_pp;
+    iy = iy + y_p0;
+    iy = iy + y_pm;
+    iy = iy + y_mp;
+    iy = iy + y_m0;
+    iy = iy + y_mm;
     // convolve2d also multiplies the kernels' zero taps (the middle column of Sobel x, the middle row of Sobel y): they
     // add +-0 to a sum, which only moves the sign of a zero result, except that 0 * inf is NaN.  Added last, as fmas.
     const float a_00 = avg(y, x);

@@ -57,6 +57,8 @@ template <class T>
 __device__ __forceinline__ float sparse_sample(const void *img, int h, int w, double y, double x)
 {
     const BilinearTaps t = bilinear_taps(h, w, y, x);   // offsets are clamped into the plane for every coordinate
+    // cval at a point outside, a NaN coordinate included (a displacement is NaN where a window sum overflowed to
+    // inf - inf, on finite frames too)
     if (!t.inside) return 0.0f;
     return bilinear_finish(t, ld_pix<T>(img, (unsigned)t.i00), ld_pix<T>(img, (unsigned)t.i01), ld_pix<T>(img, (unsigned)t.i10),
                            ld_pix<T>(img, (unsigned)t.i11));
@@ -113,7 +115,9 @@ __device__ __forceinline__ void sparse_level(SparseLds<HW> &m, int lane, const v
             const float a_mm = a[-M::S - 1], a_m0 = a[-M::S], a_mp = a[-M::S + 1];
             const float a_0m = a[-1], a_0p = a[1];
             const float a_pm = a[M::S - 1], a_p0 = a[M::S], a_pp = a[M::S + 1];
-            float ix, iy;   // Sobel / 8 in convolve2d's order, as k_lk_generic (the products by powers of two are exact)
+            // Sobel / 8 in convolve2d's order, as k_lk_generic.  The products by powers of two are exact unless the product is
+            // subnormal; there every product of two gradients underflows to 0, det = 0 and nothing is solved either way.
+            float ix, iy;
             ix = a_pp * -0.125f;
             ix = fmaf(a_pm, 0.125f, ix);
             ix = fmaf(a_0p, -0.25f, ix);

@@ -834,8 +834,14 @@ int oflk_stabilize_sequence_u8(const unsigned char *frames, int T, int H, int W,
  *   OFLK_MOSAIC_LAST      sum = f64(s), wsum = 1.0
  * and count += 1 in every mode.  A pixel's samples are added one by one in frame order, so a canvas accumulated in several
  * calls (frames 0 .. k, then k+1 .. F-1) holds the bytes of one call: a video may be fed as it arrives.
- * Resolve: where count > 0, out = f32(sum / wsum), for uint8 output (unsigned char) rintf of that;  elsewhere 0.  The state
- * is not changed.
+ * Resolve: where count > 0, v = f32(sum / wsum);  float32 output: v;  uint8 output: 0 if v is a NaN, otherwise
+ * min(max(rint(v), 0), 255), rint half to even: -0.5 gives 0, 254.5 gives 254, 255.5 and everything above (+inf too) 255,
+ * everything below -0.5 (-inf too) 0.  Elsewhere 0.  The state is not changed.  The resolve saturates because v need not lie
+ * in [0, 255]: an exposure takes a sample anywhere, and the u8 flag here is the output's, so a state accumulated from float32
+ * frames can be resolved to bytes.  The warps and the interpolation convert with a bare rintf and need no clamp: a bilinear
+ * sample of bytes, and a + t (b - a) with a, b such samples and 0 < t < 1, each operation rounded to nearest, lies in
+ * [0, 255] to within a float32 rounding, far inside the (-0.5, 255.5) that rintf takes to a byte
+ * (tests/test_byte_range_cpu.py checks it on frames of 0 and 255).
  * Refusals, before any device call: T < 1 (the sequence call: T < 2), an anchor outside [0, T-1], an extent that is not finite
  * and positive, F < 1, H or W < 2, Hc or Wc < 1, an unknown blend, NULL pointers (d_counts, d_held, d_skip, d_count and the
  * sequence call's outputs after `canvas` may be NULL; d_model when T == 1), a map or chain output that is not 8-byte aligned, a
@@ -882,7 +888,9 @@ int oflk_mosaic_composite_host_u8(const unsigned char *frames, int F, int H, int
  * Host only, no device call.  T < 1, an anchor outside [0, T-1], NULL pointers: OFLK_ERR_INVALID.
  * The compensated accumulation is oflk_mosaic_accumulate with one change: the float32 sample s of frame f enters the blend as
  * eg_f * f64(s) + eb_f, one multiply and one add, each rounded (d_exposure [F][2] float64, 8-byte aligned; NULL:
- * OFLK_ERR_INVALID).  The cull, the four blends, the counts and the resolve are unchanged, and so are the refusals.  One gain
+ * OFLK_ERR_INVALID).  The cull, the four blends, the counts and the resolve are unchanged, and so are the refusals.  A frame
+ * darker than the anchor has eg_f > 1 and takes a highlight above 255, a negative eb_f takes a shadow below 0: the uint8
+ * resolve saturates such a pixel to 255 or 0 by the rule above, it does not wrap.  One gain
  * and one bias per frame: per-channel gains (colour frames use the luma's pair for every channel), gamma and vignetting are
  * not modelled. */
 int oflk_exposure_chain_host(const float *photo, const int *status, int T, int anchor, double *exposure);

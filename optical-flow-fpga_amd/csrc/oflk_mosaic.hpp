@@ -19,7 +19,9 @@
 //                       frame's nine coefficients come through the scalar cache.  The per-pixel body is warp_frames' under a
 //                       3 x 3 map (bilinear_taps / bilinear_finish), with the state update in place of the store
 //   k_mosaic_resolve<PIX, VEC>  streaming: a lane reads the state of kMosaicPx pixels, divides, and stores them at once (VEC:
-//                       the row length a multiple of kMosaicPx and the outputs aligned to a lane's store) or one by one
+//                       the row length a multiple of kMosaicPx and the outputs aligned to a lane's store) or one by one;
+//                       bytes through mosaic_store_value, which saturates: the one uint8 store here whose value can leave
+//                       [0, 255]
 //
 // The state (private to this file and to mosaic_state in oflk.hip): three planes of pitch Wp = Wc rounded up to kMosaicPx,
 // [Hc][Wp] float64 sum, [Hc][Wp] float64 wsum, [Hc][Wp] int32 count, each plane on a 256-byte boundary.  A lane's pixels are
@@ -307,6 +309,16 @@ struct MosaicResolveArgs {
     int Hc, Wc;
 };
 
+// The resolve's own conversion.  What a warp or an interpolation stores is a convex combination of bytes and lies in [0, 255];
+// sum / wsum does not: an exposure takes a sample anywhere, and a state accumulated from float32 frames can be resolved to
+// bytes.  uint8: 0 for a NaN (r >= 0 is false), otherwise rint(v), half to even, held to [0, 255]; -0 converts to 0
+__device__ __forceinline__ float mosaic_store_value(float v, float) { return v; }
+__device__ __forceinline__ unsigned char mosaic_store_value(float v, unsigned char)
+{
+    const float r = rintf(v);
+    return (unsigned char)(r >= 0.0f ? (r <= 255.0f ? r : 255.0f) : 0.0f);
+}
+
 template <class PIX, bool VEC>
 __global__ __launch_bounds__(256) void k_mosaic_resolve(MosaicResolveArgs<PIX> a)
 {
@@ -322,7 +334,7 @@ __global__ __launch_bounds__(256) void k_mosaic_resolve(MosaicResolveArgs<PIX> a
     const int c[kMosaicPx] = {c4.x, c4.y, c4.z, c4.w};
     PIX v[kMosaicPx];
 #pragma unroll
-    for (int k = 0; k < kMosaicPx; k++) v[k] = warp_store_value(c[k] > 0 ? __double2float_rn(s[k] / w[k]) : 0.0f, PIX());
+    for (int k = 0; k < kMosaicPx; k++) v[k] = mosaic_store_value(c[k] > 0 ? __double2float_rn(s[k] / w[k]) : 0.0f, PIX());
     const size_t o = (size_t)y * (size_t)a.Wc + (size_t)x;
     if constexpr (VEC) {
         if constexpr (sizeof(PIX) == 4) {

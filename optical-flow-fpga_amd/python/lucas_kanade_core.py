@@ -511,8 +511,8 @@ def mosaic_composite(frames, maps, canvas_shape, origin=(0, 0), skip=None, blend
     f covers it where maps[f] (3 x 3, canvas coordinates to frame f's, e.g. MosaicChain.from_anchor) takes it inside the
     frame, and contributes its bilinear sample there.  blend: "mean"; "feather" (each sample weighted by one plus its distance
     from the frame's nearest edge); "first" / "last" (the lowest / highest frame that covers the pixel).  frames: (F, H, W)
-    float32 or uint8 (uint8 out: rounded half to even); skip: (F,) flags of frames to leave out, e.g. MosaicChain.dropped.
-    Returns the (Hc, Wc) canvas, zero where no frame reaches; with return_count also the (Hc, Wc) int32 number of frames that
+    float32 or uint8 (uint8 out: rounded half to even and saturated to [0, 255]); skip: (F,) flags of frames to leave out,
+    e.g. MosaicChain.dropped.  Returns the (Hc, Wc) canvas, zero where no frame reaches; with return_count also the (Hc, Wc) int32 number of frames that
     cover each pixel.
 
     A 4-D uint8 array (F, H, W, C), C = 3 or 4, is a batch of interleaved colour frames: every channel's plane is blended by a

@@ -754,7 +754,8 @@ def lucas_kanade_pyramidal_sequence_mosaic(frames, max_corners: int = 1000, dete
     refine_photometric=True (needs refine_iterations > 0), for video whose exposure changes: every step is refined together
     with a gain and a bias (sequence_refine_alignment(..., photometric=True)), exposure_chain composes them from the anchor
     (a step that was not refined counts as no change), and every frame enters the blend at the anchor's exposure
-    (mosaic_composite(..., exposure=...)).  Returns a PhotometricMosaic: Mosaic's fields and .exposure.
+    (mosaic_composite(..., exposure=...)).  Returns a PhotometricMosaic: Mosaic's fields and .exposure.  A uint8 canvas is
+    rounded half to even and saturated to [0, 255]: a highlight that the anchor's exposure takes above 255 reads 255.
 
     refine_robust_delta (grey levels, e.g. 4.0; needs refine_iterations > 0) is sequence_refine_alignment's robust_delta, with
     or without refine_photometric: Huber weights, so that an object moving through the shot does not pull the refined steps.

@@ -151,13 +151,14 @@ def exposed(frame, gain, bias):
     return (np.float32(gain) * np.asarray(frame, np.float32) + np.float32(bias)).astype(np.float32)
 
 
-def pan_scene(T=8, H=96, W=128, step=5, seed=3):
+def pan_scene(T=8, H=96, W=128, step=5, seed=3, contrast=(40.0, 0.5)):
     """The 8-frame pan of a static scene under a changing exposure.  The source smooth_field(104, 171, seed) is compressed to
-    40 + 0.5 v; frame t is the (H, W) window `step` px further right from offset (4, 4), exposed with gain 1 + 0.03 t and bias
-    -2 t and rounded to uint8.  -> (frames (T, H, W) uint8, source float64, gains (T,), biases (T,))"""
+    40 + 0.5 v (contrast=(0.0, 1.0): left at 0 .. 255, so that exposed frames clip); frame t is the (H, W) window `step` px
+    further right from offset (4, 4), exposed with gain 1 + 0.03 t and bias -2 t, rounded and clipped to uint8.
+    -> (frames (T, H, W) uint8, source float64, gains (T,), biases (T,))"""
     import mosaic_model as MM
 
-    src = 40.0 + 0.5 * MM.smooth_field(104, 171, seed).astype(np.float64)
+    src = contrast[0] + contrast[1] * MM.smooth_field(104, 171, seed).astype(np.float64)
     t = np.arange(T, dtype=np.float64)
     gains, biases = 1.0 + 0.03 * t, -2.0 * t
     frames = np.stack([np.clip(np.rint(gains[k] * src[4:4 + H, 4 + step * k:4 + step * k + W] + biases[k]), 0, 255).astype(np.uint8)

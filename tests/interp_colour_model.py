@@ -88,8 +88,9 @@ def chroma_side(P, Fu, Fv, Gu, Gv, s, sx, sy, alpha, beta, refine, clamped=True)
     return val.reshape(CH, CW, 2), ok.reshape(CH, CW)
 
 
-def chroma_pair(PA, PB, uf, vf, ub, vb, tau, siting="left", alpha=0.01, beta=0.5, refine=2, clamped=True):
-    """the (CH, CW, 2) uint8 chroma of the frame at time tau between the frames whose chroma planes are PA and PB"""
+def chroma_value(PA, PB, uf, vf, ub, vb, tau, siting="left", alpha=0.01, beta=0.5, refine=2, clamped=True):
+    """the (CH, CW, 2) float32 chroma, before its conversion to uint8, of the frame at time tau between the frames whose chroma
+    planes are PA and PB"""
     sx, sy = NM.SITINGS[siting]
     tau = np.float64(tau)
     uf, vf, ub, vb = (np.ascontiguousarray(f, np.float32) for f in (uf, vf, ub, vb))
@@ -103,7 +104,12 @@ def chroma_pair(PA, PB, uf, vf, ub, vb, tau, siting="left", alpha=0.01, beta=0.5
     out[ok_a & ~ok_b] = a[ok_a & ~ok_b]
     out[ok_b & ~ok_a] = b[ok_b & ~ok_a]
     assert out.dtype == np.float32
-    return np.rint(out).astype(np.uint8)
+    return out
+
+
+def chroma_pair(PA, PB, uf, vf, ub, vb, tau, siting="left", alpha=0.01, beta=0.5, refine=2, clamped=True):
+    """the (CH, CW, 2) uint8 chroma of the frame at time tau between the frames whose chroma planes are PA and PB"""
+    return np.rint(chroma_value(PA, PB, uf, vf, ub, vb, tau, siting, alpha, beta, refine, clamped)).astype(np.uint8)
 
 
 def interpolate_nv12(frames, uf, vf, ub, vb, taus, siting="left", alpha=0.01, beta=0.5, refine=2, clamped=True):

@@ -39,8 +39,10 @@ transcendental, and nothing depends on how a call is cut.
        last      sum = f64(s), wsum = 1
    and count += 1 in every mode.  Samples are added one by one in frame order, so a canvas accumulated in several calls holds
    what one call gives.
-4. Resolve (`resolve`): where count > 0, out = f32(sum / wsum), for uint8 output (uint8) rint of that, half to even;
-   elsewhere 0.  The state is not changed.
+4. Resolve (`resolve`): where count > 0, v = f32(sum / wsum); float32 output: v; uint8 output (`saturate`): 0 if v is a NaN,
+   otherwise min(max(rint(v), 0), 255), rint half to even -- -0.5 gives 0, 254.5 gives 254, 255.5 gives 255, +-inf give 255
+   and 0.  Elsewhere 0.  The state is not changed.  v leaves [0, 255] under an exposure (mosaic_exposure_model) and when a
+   state accumulated from float32 frames is resolved to bytes; inside [0, 255] the rule is rint alone.
 """
 import numpy as np
 
@@ -178,12 +180,20 @@ def accumulate(state, frames, maps, skip, x0, y0, blend):
     return state
 
 
+def saturate(v):
+    """the resolve's uint8 conversion of float32 values: 0 for a NaN, otherwise rint (half to even) held to [0, 255].  The NaN
+    is replaced and the value clipped before the cast, so the cast never leaves uint8's domain and nothing here warns"""
+    v = np.asarray(v, np.float32)
+    r = np.rint(np.where(np.isnan(v), np.float32(0), v))
+    return np.minimum(np.maximum(r, np.float32(0)), np.float32(255)).astype(np.uint8)
+
+
 def resolve(state, u8):
     """-> (out (Hc, Wc) float32 or uint8, count (Hc, Wc) int32)"""
     some = state["count"] > 0
-    with np.errstate(all="ignore"):
+    with np.errstate(all="ignore"):   # the division and its rounding to float32 only: inf / inf, an overflow
         v = np.where(some, (state["sum"] / np.where(some, state["wsum"], 1.0)).astype(np.float32), np.float32(0))
-    return (np.rint(v).astype(np.uint8) if u8 else v.astype(np.float32)), state["count"].copy()
+    return (saturate(v) if u8 else v.astype(np.float32)), state["count"].copy()
 
 
 def composite(frames, maps, skip, x0, y0, Hc, Wc, blend, cuts=()):

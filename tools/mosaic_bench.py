@@ -15,10 +15,16 @@ Legs, each in a process of its own under its own time limit (a leg that fails or
 Events around `--reps` back-to-back repetitions give one window; one JSON line per leg with the median and min - max over
 `--steps` windows, the number of covered (pixel, frame) pairs and the time per covered pair.
 
+  resolve         (only with --leg resolve) oflk_mosaic_resolve alone, uint8 output with the count, on the pan's canvas made
+                  `--extra-columns` wider (a width that is a multiple of 4 takes the dword store, any other the byte store);
+                  the state holds the first 4 frames under exposures that put a third of the pixels beyond either end of the
+                  byte range.  Compare two libraries with OFLK_LIB, their runs alternating
+
     python tools/mosaic_bench.py [--steps 7] [--reps 3] [--frames 129] [--limit 240]
 """
 import argparse
 import json
+import os
 import statistics
 import subprocess
 import sys
@@ -61,7 +67,9 @@ def leg(args):
     st = torch.cuda.current_stream().cuda_stream
     maps, (x0, y0, Wc, Hc) = scene(args.scene, F)
     rng = np.random.default_rng(0)
-    frames = torch.from_numpy(rng.integers(0, 256, (F, H, W), dtype=np.uint8)).to(d)
+    if args.leg == "resolve":
+        Wc += args.extra_columns
+    frames = torch.from_numpy(rng.integers(0, 256, (4 if args.leg == "resolve" else F, H, W), dtype=np.uint8)).to(d)
     out = torch.empty((Hc, Wc), dtype=torch.uint8, device=d)
     count = torch.empty((Hc, Wc), dtype=torch.int32, device=d)
     if args.leg == "baseline":
@@ -79,6 +87,16 @@ def leg(args):
             s = torch.sum(warped, 0, dtype=torch.float32)
             count.copy_(torch.sum(inside, 0, dtype=torch.int32))
             out.copy_(torch.where(count > 0, s / count.clamp(min=1), torch.zeros_like(s)).round().to(torch.uint8))
+    elif args.leg == "resolve":
+        nbytes = _oflk.mosaic_state_bytes(Hc, Wc)
+        state = torch.zeros(nbytes, dtype=torch.uint8, device=d)
+        t_map = torch.from_numpy(maps[:4].copy()).to(d)
+        t_exp = torch.from_numpy(np.array([[3.0, -255.0]] * 4)).to(d)
+        _oflk.mosaic_accumulate(frames.data_ptr(), 4, H, W, t_map.data_ptr(), 0, x0, y0, Hc, Wc, _oflk.MOSAIC_BLENDS["mean"], state.data_ptr(),
+                                nbytes, True, st, t_exp.data_ptr())
+
+        def run():
+            _oflk.mosaic_resolve(state.data_ptr(), Hc, Wc, out.data_ptr(), count.data_ptr(), True, st)
     else:
         blend = _oflk.MOSAIC_BLENDS[args.leg]
         nbytes = _oflk.mosaic_state_bytes(Hc, Wc)
@@ -109,7 +127,10 @@ def leg(args):
                       "covered_pairs": pairs, "pairs_over_canvas_times_F": round(pairs / (Wc * Hc * F), 4),
                       "ns_per_covered_pair": round(med * 1e6 / max(pairs, 1), 4),
                       "us_per_frame_area_covered": round(med * 1e3 / max(pairs / (H * W), 1e-9), 2),
-                      "max_count": int(count.max().item()), "reps": args.reps, "steps": args.steps}), flush=True)
+                      "max_count": int(count.max().item()), "reps": args.reps, "steps": args.steps,
+                      **({"us_per_resolve": round(med * 1e3, 2), "us_min_max": [round(min(ms) * 1e3, 2), round(max(ms) * 1e3, 2)],
+                          "bytes_at_0_and_255": [int((out == 0).sum().item()), int((out == 255).sum().item())],
+                          "library": os.environ.get("OFLK_LIB", "")} if args.leg == "resolve" else {})}), flush=True)
 
 
 def main():
@@ -119,7 +140,8 @@ def main():
     ap.add_argument("--frames", type=int, default=129)
     ap.add_argument("--limit", type=int, default=240, help="seconds a leg may take")
     ap.add_argument("--scene", choices=["pan", "still"])
-    ap.add_argument("--leg", choices=["mean", "feather", "baseline"], help="run this one leg in this process")
+    ap.add_argument("--leg", choices=["mean", "feather", "baseline", "resolve"], help="run this one leg in this process")
+    ap.add_argument("--extra-columns", type=int, default=0, help="the resolve leg: columns added to the canvas")
     args = ap.parse_args()
     if args.leg:
         import torch  # noqa: F401  (first: liboflk binds to the HIP runtime torch has loaded)

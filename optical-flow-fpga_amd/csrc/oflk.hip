@@ -234,10 +234,6 @@ struct oflk_plan {
     int kernels = OFLK_KERNELS_AUTO;   // oflk_plan_set_kernels
     // single-scale 5x5 on integer-valued frames: the streaming kernel's list of doubtful tiles (LkArgs::redo)
     unsigned *redo = nullptr;
-#ifdef OFLK_STAMPS
-    unsigned *stamps = nullptr;      // diagnostic build: per-wave section cycle sums of the last finest-level launch
-    size_t stamps_blocks = 0;
-#endif
     // profiling
     bool prof = false;
     int prof_only = -1;  // >= 0: bracket only launches of this kernel class
@@ -392,9 +388,7 @@ Segments wave_segments(int H, long strips, long slots, int seg_rows, int thin_ro
 
 // resident blocks of the redo pass after the streaming single-scale kernel: one per CU -- an empty list (the common case)
 // then costs 7 us instead of the 22 us of a full round of 1024 blocks, a long one is walked four times slower
-#ifndef OFLK_REDO_BLOCKS
-#define OFLK_REDO_BLOCKS 256
-#endif
+constexpr long kRedoBlocks = 256;
 
 // u8: a.prev / a.curr point at uint8 frames (finest level of a uint8 plan); never with MODE_GRADS
 template <int MODE>
@@ -441,7 +435,7 @@ int launch_lk(oflk_plan *plan, hipStream_t s, int cls, int hw, const LkArgs &a_i
     if (MODE == MODE_SINGLE && a.redo_pass) {
         // redo pass of the streaming kernel: resident blocks that walk the device-side list of flagged tiles
         a.nseg = 0;
-        nblocks = (unsigned)std::min<long>((long)B * tiles_x * tiles_y, OFLK_REDO_BLOCKS);
+        nblocks = (unsigned)std::min<long>((long)B * tiles_x * tiles_y, kRedoBlocks);
     } else if (cap <= 1) {
         a.nseg = 0;
         nblocks = (unsigned)(tiles_x * tiles_y * B);
@@ -460,19 +454,6 @@ int launch_lk(oflk_plan *plan, hipStream_t s, int cls, int hw, const LkArgs &a_i
         nblocks = 8u * (unsigned)((strips + 7) / 8) * (unsigned)n;
     }
     dim3 grid(nblocks);
-#ifdef OFLK_STAMPS
-    a.stamps = nullptr;
-    if (plan && cls == KC_LK_ITER_FINEST) {
-        if (plan->stamps_blocks < nblocks) {
-            if (plan->stamps) (void)hipFree(plan->stamps);
-            plan->stamps = nullptr;
-            HIP_TRY(hipMalloc((void **)&plan->stamps, (size_t)nblocks * 520 * sizeof(unsigned)));
-            plan->stamps_blocks = nblocks;
-        }
-        HIP_TRY(hipMemsetAsync(plan->stamps, 0, (size_t)nblocks * 520 * sizeof(unsigned), s));
-        a.stamps = plan->stamps;
-    }
-#endif
     // the VEC instantiation moves 16 / 8 bytes per lane: every plane must start 16-byte aligned
     // (each row then does, W % 4 == 0); anything else takes the element-wise instantiation
     const bool frames_ok = u8 ? (aligned(a.prev, 4) && aligned(a.curr, 4)) : (aligned(a.prev, 16) && aligned(a.curr, 16));   // uint8: 4 pixels per dword
@@ -505,9 +486,7 @@ int launch_lk(oflk_plan *plan, hipStream_t s, int cls, int hw, const LkArgs &a_i
 // not be in NumPy's order (the tolerant mode's fine levels; single-scale on integer-valued frames, where any order is
 // exact).  One wave per (strip of 120 output columns, segment of Hs rows); wave_segments sizes the segments, ~128 rows each
 // when there are rounds to spare (a segment pays 2 (hw + 1) extra rows).
-#ifndef OFLK_LKS_SEG_ROWS
-#define OFLK_LKS_SEG_ROWS 128
-#endif
+constexpr int kLksSegRows = 128;
 template <int MODE>
 int launch_lks(oflk_plan *plan, hipStream_t s, int cls, const LkArgs &a_in, int B, bool u8, int warp, int hw = 2)
 {
@@ -515,9 +494,9 @@ int launch_lks(oflk_plan *plan, hipStream_t s, int cls, const LkArgs &a_in, int 
     a.B = B;
     Prof pr(plan, s, cls);
     const long strips = ((long)a.W + kLksOutW - 1) / kLksOutW * B;
-    const long slots = 256 * 4 * (MODE == MODE_SINGLE ? 4 : OFLK_LKS_WAVES);   // wave slots of the chip at the kernel's occupancy (SINGLE: ~100 VGPRs)
+    const long slots = 256 * 4 * (MODE == MODE_SINGLE ? 4 : kLksWaves);   // wave slots of the chip at the kernel's occupancy (SINGLE: ~100 VGPRs)
     // a segment pays 6 extra rows; a launch that cannot fill the slots (a single pair in the tolerant mode) goes down to 12 rows
-    const Segments sg = wave_segments(a.H, strips, slots, OFLK_LKS_SEG_ROWS, 12);
+    const Segments sg = wave_segments(a.H, strips, slots, kLksSegRows, 12);
     a.Hs = sg.rows;
     a.segs = sg.segs;
     const long nwave = strips * a.segs;
@@ -697,7 +676,7 @@ int launch_pyr_down(oflk_plan *plan, const GaussW &gauss, hipStream_t s, const f
         Prof pr(plan, s, KC_PYR_FUSED);
         // contracted / tolerant plans: the opt-in fused sums as they are.  The exact arithmetic (every other plan, and no
         // plan at all) runs them behind the rounding certificate, which leaves SciPy's results
-        constexpr int kExactForm = OFLK_PYR_CERT ? PYR_CERTIFIED : PYR_EXACT;
+        constexpr int kExactForm = PYR_CERTIFIED;
         const int arith = contracted_pyramid(plan) ? PYR_CONTRACTED : kExactForm;
         // the tile: a tight step at the exact half-scale ratio takes the instantiation with compile-time tap and staging offsets
         const int tile = form != PYR_TIGHT ? PYR_TILE_GENERAL : (pyr_half(h, w, ho, wo, gauss) ? PYR_TILE_HALF : PYR_TILE_TIGHT);
@@ -851,9 +830,6 @@ void plan_free(oflk_plan *p)
             if (q) (void)hipFree(q);
     for (float *q : {p->exact.warped, p->exact.du, p->exact.dv, p->exact.f32[0], p->exact.f32[1], p->exact.pieces})
         if (q) (void)hipFree(q);
-#ifdef OFLK_STAMPS
-    if (p->stamps) (void)hipFree(p->stamps);
-#endif
     for (auto &e : p->pending) {
         (void)hipEventDestroy(e.a);
         (void)hipEventDestroy(e.b);
@@ -1308,47 +1284,6 @@ OFLK_API int oflk_plan_read_log(oflk_plan *p, float *residual_log, int *iters_ru
     HIP_TRY(hipStreamSynchronize(s));
     return OFLK_OK;
 }
-
-#ifdef OFLK_DIAG
-// diagnostic build only (tools/pyr_redo.py): waves of k_pyr_down's passes B and C on the current device since the last
-// reset, [B ran, B redone, C ran, C redone]
-OFLK_API int oflk_debug_pyr_cert_waves(unsigned long long *out, int reset)
-{
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pyr_cert_waves), 4 * sizeof(unsigned long long)) != hipSuccess) return -1;
-    if (reset) {
-        const unsigned long long z[4] = {0, 0, 0, 0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_pyr_cert_waves), z, sizeof(z)) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#endif
-
-#ifdef OFLK_STAMPS
-// diagnostic build only (tools/stamps.py): [blocks][4 waves][8 tiles][16] s_memtime stamps of the last
-// finest-level iteration launch; returns the number of blocks
-OFLK_API long oflk_debug_stamps(oflk_plan *p, unsigned *out, long max_blocks)
-{
-    if (!p || !p->stamps) return 0;
-    (void)hipSetDevice(p->device);
-    (void)hipDeviceSynchronize();
-    const long n = std::min<long>((long)p->stamps_blocks, max_blocks);
-    if (out && hipMemcpy(out, p->stamps, (size_t)n * 512 * sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    return (long)p->stamps_blocks;
-}
-
-// [blocks][8]: entry, loop start, loop end, exit on the 100 MHz chip-wide clock; HW_ID; XCC_ID; tiles; valid
-OFLK_API long oflk_debug_block_times(oflk_plan *p, unsigned *out, long max_blocks)
-{
-    if (!p || !p->stamps) return 0;
-    (void)hipSetDevice(p->device);
-    (void)hipDeviceSynchronize();
-    const long n = std::min<long>((long)p->stamps_blocks, max_blocks);
-    if (out && hipMemcpy(out, p->stamps + (size_t)p->stamps_blocks * 512, (size_t)n * 8 * sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess)
-        return -1;
-    return (long)p->stamps_blocks;
-}
-#endif
 
 namespace {
 

@@ -21,19 +21,6 @@
 
 #pragma clang fp contract(off)
 
-#ifndef OFLK_PYR_PAIRS
-#define OFLK_PYR_PAIRS 1   // k_pyr_down: interior float32 tiles staged as column pairs (8-byte loads)
-#endif
-#ifndef OFLK_PYR_CERT
-#define OFLK_PYR_CERT 1    // k_pyr_down: the exact arithmetic runs the certified form (0: SciPy's sequence throughout)
-#endif
-#ifndef OFLK_PYR_HALF
-#define OFLK_PYR_HALF 3    // k_pyr_down's half-scale tile: bit 0 its staging (stage A), bit 1 its sampling (stage D); a
-#endif                     // diagnostic build clears one to time the other alone
-#ifndef OFLK_LK16_PF
-#define OFLK_LK16_PF 2   // rows of frame loads in flight per wave (k_lk16d)
-#endif
-
 namespace oflk {
 
 constexpr int kMaxRadius = 64;
@@ -354,13 +341,6 @@ __device__ __forceinline__ void div2_shared_rcp(float nu, float nv, float d, flo
     qv = __builtin_fmaf(e, r, q);
 }
 
-#ifndef OFLK_PROBE_FASTDIV
-#define OFLK_PROBE_FASTDIV 0   // diagnostic builds only: the shared-reciprocal quotients everywhere, unguarded (timing probe)
-#endif
-#if OFLK_PROBE_FASTDIV && !defined(OFLK_DIAG)
-#error "OFLK_PROBE_FASTDIV is a diagnostic build: add -DOFLK_DIAG"
-#endif
-
 // 2x2 Cramer solve, every op individually rounded (lucas_kanade_core.py:122-133).  SAFE_RANGE: the caller guarantees
 // div2_shared_rcp's range conditions, and the two divisions share their reciprocal (same values).
 template <bool SAFE_RANGE = false>
@@ -377,7 +357,7 @@ __device__ __forceinline__ void lk_solve(float Sxx, float Syy, float Sxy, float 
         float n0 = Syy * b0, n1 = Sxy * b1;
         float n2 = Sxx * b1, n3 = Sxy * b0;
         float nu = n0 - n1, nv = n2 - n3;
-        if constexpr (SAFE_RANGE || OFLK_PROBE_FASTDIV) {
+        if constexpr (SAFE_RANGE) {
             div2_shared_rcp(nu, nv, det, u, v);
         } else {
             u = nu / det;
@@ -445,16 +425,13 @@ struct LkArgs {
     int Hc, Wc;
     Linspace up_ly, up_lx;       // np.linspace(0, Hc-1, H), np.linspace(0, Wc-1, W)
     float up_sx, up_sy;          // float32(W / Wc), float32(H / Hc)
-#ifdef OFLK_STAMPS
-    unsigned *stamps;   // diagnostic build only: [block][wave][16] cycle sums per code section
-#endif
 };
 
 // ---------------------------------------------------------------------------
 // K1/K7: the fused kernel k_lkw<HW, MODE, VEC>; the 5x5 window (window_size 4 or 5) is the
 // hot case and has a specialised sum stage.
 //
-// Tile 64 x 24 per 256-thread block (OFLK_NY = 3), each thread 2 (x) x 3 (y) outputs; large
+// Tile 64 x 24 per 256-thread block (k5NY = 3), each thread 2 (x) x 3 (y) outputs; large
 // launches let one block walk several vertically adjacent tiles (see k_lkw).
 //
 // Exact window sums with fewer adds.  NumPy sums the 25 products a[0..24]
@@ -472,13 +449,6 @@ struct LkArgs {
 // frame-average / It staging tiles alias the product planes (gradients wait in
 // registers across the barrier).
 // ---------------------------------------------------------------------------
-// build-time tuning knobs (defaults are the measured best on MI355X)
-#ifndef OFLK_NY
-#define OFLK_NY 3      // output rows per thread: tile = 64 x 8*NY
-#endif
-#ifndef OFLK_BATCH
-#define OFLK_BATCH 7   // warp cells whose gathers are in flight together (ITER stage 1, 5x5 window)
-#endif
 // XCD-aware tile order (speed only, never correctness).  Workgroups of a 1-D grid are
 // dealt round-robin over the 8 XCDs (ids i and i+8 share an XCD, each with its own L2).
 // Giving XCD x the contiguous tile range [x*chunk, (x+1)*chunk) makes x- and
@@ -514,7 +484,7 @@ __device__ __forceinline__ float wave_sum_to_lane63(float x)
     return x;
 }
 
-constexpr int k5NY = OFLK_NY;      // output rows per thread
+constexpr int k5NY = 3;            // output rows per thread: tile = 64 x 8*NY (the measured best on MI355X)
 constexpr int k5TX = 64;
 constexpr int k5TY = 8 * k5NY;     // 8 thread rows x NY
 
@@ -522,19 +492,10 @@ constexpr int k5TY = 8 * k5NY;     // 8 thread rows x NY
 // sink its computation past later fences (keeps the row-streaming order, and with it
 // the register footprint, of the window-sum code).  No instruction is emitted.
 __device__ __forceinline__ void pin(float &x) { asm volatile("" : "+v"(x)); }
-__device__ __forceinline__ void pin(float2 &x)
-{
-    double d = __builtin_bit_cast(double, x);
-    asm volatile("" : "+v"(d));
-    x = __builtin_bit_cast(float2, d);
-}
 
-// Two planes summed side by side.  OFLK_PK_SUMS = 1 adds them with one v_pk_add_f32 (float2);
-// 0 (default) with two v_add_f32: on gfx950 a packed fp32 add occupies the vector ALU 2.7x as long
-// as a scalar one (tools/ubench/valu_cycles.hip), so two scalar adds are the cheaper pair.
-#ifndef OFLK_PK_SUMS
-#define OFLK_PK_SUMS 0
-#endif
+// Two planes summed side by side with two v_add_f32, not as a float2 with one v_pk_add_f32: on gfx950 a packed
+// fp32 add occupies the vector ALU 2.7x as long as a scalar one (tools/ubench/valu_cycles.hip), so two scalar
+// adds are the cheaper pair (470 -> 786 us with the packed form).
 struct F2 {
     float x, y;
 };
@@ -544,18 +505,10 @@ __device__ __forceinline__ void pin(F2 &v)
     asm volatile("" : "+v"(v.x));
     asm volatile("" : "+v"(v.y));
 }
-#if OFLK_PK_SUMS
-using Sum2 = float2;
-__device__ __forceinline__ Sum2 sum2(float a, float b) { return make_float2(a, b); }
-#else
-using Sum2 = F2;
-__device__ __forceinline__ Sum2 sum2(float a, float b) { return F2{a, b}; }
-#endif
 
 template <typename T> __device__ __forceinline__ T zero_of();
 template <> __device__ __forceinline__ F2 zero_of<F2>() { return F2{0.0f, 0.0f}; }
 template <> __device__ __forceinline__ float zero_of<float>() { return 0.0f; }
-template <> __device__ __forceinline__ float2 zero_of<float2>() { return make_float2(0.0f, 0.0f); }
 
 // Window sums of a 2 (x) by NY (y) output patch, streaming the NY+4 product rows
 // top to bottom: at most three rows and three output rows' partial r's are live.
@@ -975,73 +928,6 @@ __global__ __launch_bounds__(256) void k_lk_generic(LkArgs a, int hw)
 template <int HW, int MODE>
 constexpr bool kLkChain = HW <= 2 && MODE != MODE_GRADS;
 
-// In-kernel timeline (diagnostic build -DOFLK_STAMPS only; tools/stamps.py): every wave keeps the
-// s_memtime value of each stamp of each of its (up to 8) tiles in LDS and copies them out once.
-// The values go to a buffer of their own; no output is computed from them.
-#if defined(OFLK_STAMPS) && !defined(OFLK_DIAG)
-#error "OFLK_STAMPS is a diagnostic build: add -DOFLK_DIAG"
-#endif
-#ifdef OFLK_STAMPS
-#ifndef OFLK_STAMP_MASK
-#define OFLK_STAMP_MASK 0xffff
-#endif
-#define OFLK_STAMP(i)                                                                              \
-    if ((OFLK_STAMP_MASK >> (i)) & 1) do {                                                         \
-        __builtin_amdgcn_sched_barrier(0);                                                         \
-        unsigned long long t_;                                                                     \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");               \
-        __builtin_amdgcn_sched_barrier(0);                                                         \
-        s_st[st_wave][st_tile & 7][i] = (unsigned)t_;                                              \
-    } while (0)
-#define OFLK_STAMP_OCC
-#else
-#define OFLK_STAMP(i) do { } while (0)
-#define OFLK_STAMP_OCC
-#endif
-
-
-// Sensitivity probes (diagnostic builds only, -DOFLK_DIAG -DOFLK_PROBE=(site << 8 | kind); tools/abn.sh): extra
-// instructions of one kind at one place of the tile loop, to read off what an instruction of that kind costs the
-// launch.  site 1 = stage 1 after the coalesced loads are issued, 3 = stage 3 after the window sums; kind 1 = 96
-// v_add_f32, 2 = 96 v_add_f64, 3 = 96 s_mov_b32, 4 = 24 dependent ds_read_b32.  Results stay correct.
-#if defined(OFLK_DIAG) && defined(OFLK_PROBE)
-#define OFLK_PROBE_SITE_KIND OFLK_PROBE
-#else
-#define OFLK_PROBE_SITE_KIND 0
-#endif
-template <int SITE>
-__device__ __forceinline__ void probe(const float *lds)
-{
-    if constexpr ((OFLK_PROBE_SITE_KIND >> 8) == SITE) {
-        constexpr int KIND = OFLK_PROBE_SITE_KIND & 255;
-        if constexpr (KIND == 1) {
-            float r[8] = {1, 2, 3, 4, 5, 6, 7, 8};
-#pragma unroll
-            for (int i = 0; i < 12; i++)
-                asm volatile("v_add_f32 %0, %0, %0\nv_add_f32 %1, %1, %1\nv_add_f32 %2, %2, %2\nv_add_f32 %3, %3, %3\n"
-                             "v_add_f32 %4, %4, %4\nv_add_f32 %5, %5, %5\nv_add_f32 %6, %6, %6\nv_add_f32 %7, %7, %7\n"
-                             : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7]));
-        } else if constexpr (KIND == 2) {
-            double r[4] = {1, 2, 3, 4};
-#pragma unroll
-            for (int i = 0; i < 24; i++)
-                asm volatile("v_add_f64 %0, %0, %0\nv_add_f64 %1, %1, %1\nv_add_f64 %2, %2, %2\nv_add_f64 %3, %3, %3\n"
-                             : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]));
-        } else if constexpr (KIND == 3) {
-            int r[4] = {1, 2, 3, 4};
-#pragma unroll
-            for (int i = 0; i < 24; i++)
-                asm volatile("s_mov_b32 %0, %1\ns_mov_b32 %1, %2\ns_mov_b32 %2, %3\ns_mov_b32 %3, %0\n"
-                             : "+s"(r[0]), "+s"(r[1]), "+s"(r[2]), "+s"(r[3]));
-        } else if constexpr (KIND == 4) {
-            float acc = 0.0f;
-#pragma unroll
-            for (int i = 0; i < 24; i++) acc += *(const volatile float *)(lds + threadIdx.x + 64 * i);
-            asm volatile("" ::"v"(acc));
-        }
-    }
-}
-
 // REDOL: the instantiation of a window without vertical chaining (7x7) that can walk the streaming kernel's redo list
 // (the 5x5 kernel walks it with its chaining loop); a separate instantiation, so that the ordinary 7x7 kernel keeps its registers
 template <int HW, int MODE, bool VEC, class PIX = float, bool REDOL = false>
@@ -1079,11 +965,6 @@ __global__ __launch_bounds__(256) void k_lkw(LkArgs a)
     // rows (frame average, It) that a tile shares with the tile below it are carried over in
     // registers instead of being recomputed: the exact fp64 warp, the dominant cost, runs on
     // 24 new rows per tile instead of 30.
-#ifdef OFLK_STAMPS
-    // block lifetime on the chip-wide 100 MHz clock: entry, tile loop start / end, exit; plus where it ran
-    unsigned bt[4];
-    bt[0] = (unsigned)__builtin_amdgcn_s_memrealtime();
-#endif
     const int H = a.H, W = a.W;
     const int tiles_x = (W + k5TX - 1) / k5TX, tiles_y = (H + k5TY - 1) / k5TY;
     // windows above 5x5 run one tile per block: their sum stage needs the registers the loop
@@ -1188,14 +1069,6 @@ __global__ __launch_bounds__(256) void k_lkw(LkArgs a)
             }
         }
     };
-#ifdef OFLK_STAMPS
-    __shared__ unsigned s_st[4][8][16];
-    const int st_wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int st_tile = 0;
-    for (int i = threadIdx.x; i < 4 * 8 * 16; i += 256) (&s_st[0][0][0])[i] = 0u;
-    __syncthreads();
-    bt[1] = (unsigned)__builtin_amdgcn_s_memrealtime();
-#endif
 
     for (int it = 0; it < (LOOPS ? ntile : 1); it++) {
         // re-derived per tile behind an opaque move: otherwise every per-thread address of all
@@ -1219,10 +1092,6 @@ __global__ __launch_bounds__(256) void k_lkw(LkArgs a)
         const int tile_y = redo ? tile_y_first : tile_y_first + it;
         const int y0 = tile_y * k5TY;
         const int rstart = (!CHAIN || it == 0 || redo) ? 0 : 2 * R;  // first staging row to compute
-#ifdef OFLK_STAMPS
-        st_tile = it;
-#endif
-        OFLK_STAMP(0);   // [0] top of the tile
 
         float gix[NGA], giy[NGA], git[NGA];
         if (MODE == MODE_GRADS) {
@@ -1263,7 +1132,8 @@ __global__ __launch_bounds__(256) void k_lkw(LkArgs a)
                     constexpr int RPW = (NR + 3) / 4;                // rows (= main cells) per wave / thread
                     constexpr int NHP = (ST1_HC * RPW + 63) / 64;    // halo cells per thread
                     constexpr int NCELL = RPW + NHP;
-                    constexpr int BATCH = HW != 2 ? 4 : (NCELL <= OFLK_BATCH ? NCELL : (NCELL + 1) / 2);
+                    constexpr int kBatchMax = 7;   // warp cells whose gathers are in flight together (5x5 window; the measured best)
+                    constexpr int BATCH = HW != 2 ? 4 : (NCELL <= kBatchMax ? NCELL : (NCELL + 1) / 2);
                     constexpr int SC = SX - R;                       // staging column of cell column 0
                     const int lane = tid & 63;
                     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1274,8 +1144,6 @@ __global__ __launch_bounds__(256) void k_lkw(LkArgs a)
                     float p[NCELL], q[NCELL];
                     float2 f[NCELL];
                     st1_loads(rs, tid, y0, p, f);
-                    OFLK_STAMP(1);   // [1] carry -> LDS, addresses, issue of the coalesced loads (prev, u, v)
-                    probe<1>(s_mem);
     #pragma unroll
                     for (int k0 = 0; k0 < NCELL; k0 += BATCH) {
                         LeanFrac tp[BATCH];
@@ -1300,7 +1168,6 @@ __global__ __launch_bounds__(256) void k_lkw(LkArgs a)
                                 lean_load<false, PIX>(lg, curr, tp[j], pr0[j], pr1[j]);
                             }
                         }
-                        OFLK_STAMP(k0 == 0 ? 2 : 4);   // [2]/[4] wait for u, v; taps; gathers issued
     #pragma unroll
                         for (int j = 0; j < BATCH; j++)
                             if (k0 + j < NCELL) {
@@ -1308,7 +1175,6 @@ __global__ __launch_bounds__(256) void k_lkw(LkArgs a)
                                 pin(q[k0 + j]);  // finished here, not sunk to its use after the last batch
                             }
                         __builtin_amdgcn_sched_barrier(0);  // one batch of taps in flight at a time
-                        OFLK_STAMP(k0 == 0 ? 3 : 5);   // [3]/[5] wait for the gathers; fp64 tap sums
                     }
     #pragma unroll
                     for (int k = 0; k < NCELL; k++) {
@@ -1384,9 +1250,7 @@ __global__ __launch_bounds__(256) void k_lkw(LkArgs a)
             };
             if (rstart == 0) stage1(std::integral_constant<int, 0>{});
             else stage1(std::integral_constant<int, 2 * R>{});
-            OFLK_STAMP(6);    // [6] avg / It -> LDS
-            __syncthreads();
-            OFLK_STAMP(7);    // [7] barrier 1
+            __syncthreads();  // barrier 1: avg / It are in LDS
             // ---- stage 2: Sobel/8 in convolve2d's tap order; gradients stay in registers
             // Lane = column, wave = RPW2 consecutive rows of the PH x PW gradient tile (the last wave's rows
             // overlap its neighbour's when PH is not a multiple of 4: same values twice).  A wave walks down its
@@ -1446,9 +1310,7 @@ __global__ __launch_bounds__(256) void k_lkw(LkArgs a)
                     }
                 }
             }
-            OFLK_STAMP(8);    // [8] stage 2: Sobel from LDS, carry rows
-            __syncthreads();  // everyone is done reading avg / It: the planes may overwrite them
-            OFLK_STAMP(9);    // [9] barrier 2
+            __syncthreads();  // barrier 2: everyone is done reading avg / It: the planes may overwrite them
         }
         // ---- products into the interleaved planes --------------------------------
         if (MODE == MODE_GRADS) {
@@ -1481,9 +1343,7 @@ __global__ __launch_bounds__(256) void k_lkw(LkArgs a)
                 s_pc[e] = iy * itv;
             }
         }
-        OFLK_STAMP(10);   // [10] products -> LDS
-        __syncthreads();
-        OFLK_STAMP(11);   // [11] barrier 3
+        __syncthreads();  // barrier 3: the products are in LDS
 
         // ---- stage 3: window sums in NumPy order (pk over plane pairs), solve, write -----
         // thread = 2 (x) by NY (y) outputs; a half-wave spans one tile row, so the
@@ -1491,16 +1351,16 @@ __global__ __launch_bounds__(256) void k_lkw(LkArgs a)
         constexpr int NY = k5NY;
         constexpr int RW = 2 + 2 * HW;   // product columns a thread reads per row
         const int tx = tid & 31, ty = tid >> 5;
-        Sum2 sA[NY][2], sB[NY][2];
+        F2 sA[NY][2], sB[NY][2];
         float sC[NY][2];
         // rows of the interleaved planes: RW float2 = RW/2 aligned 16-byte reads; RW floats = RW/2 8-byte reads
-        auto load_f2 = [](const float2 *src, Sum2 (&row)[RW]) {
+        auto load_f2 = [](const float2 *src, F2 (&row)[RW]) {
             const float4 *r4 = reinterpret_cast<const float4 *>(src);
 #pragma unroll
             for (int j = 0; j < RW / 2; j++) {
                 float4 qv = r4[j];
-                row[2 * j] = sum2(qv.x, qv.y);
-                row[2 * j + 1] = sum2(qv.z, qv.w);
+                row[2 * j] = F2{qv.x, qv.y};
+                row[2 * j + 1] = F2{qv.z, qv.w};
             }
         };
         auto load_f1 = [](const float *src, float (&row)[RW]) {
@@ -1530,9 +1390,9 @@ __global__ __launch_bounds__(256) void k_lkw(LkArgs a)
         };
         if constexpr (HW == 2) {
             const float2 *ba = &s_pa[(NY * ty) * PW + 2 * tx];
-            patch5_sums<Sum2, NY>([&](int i, Sum2 (&row)[6]) { load_f2(ba + i * PW, row); }, sA);
+            patch5_sums<F2, NY>([&](int i, F2 (&row)[6]) { load_f2(ba + i * PW, row); }, sA);
             const float2 *bb = &s_pb[(NY * ty) * PW + 2 * tx];
-            patch5_sums<Sum2, NY>([&](int i, Sum2 (&row)[6]) { load_f2(bb + i * PW, row); }, sB);
+            patch5_sums<F2, NY>([&](int i, F2 (&row)[6]) { load_f2(bb + i * PW, row); }, sB);
             if constexpr (PRELOAD) preload();
             const float *bc = &s_pc[(NY * ty) * PW + 2 * tx];
             patch5_sums<float, NY>([&](int i, float (&row)[6]) { load_f1(bc + i * PW, row); }, sC);
@@ -1540,10 +1400,10 @@ __global__ __launch_bounds__(256) void k_lkw(LkArgs a)
 #pragma unroll
             for (int oy = 0; oy < NY; oy++) {
                 const float2 *ba = &s_pa[(NY * ty + oy) * PW + 2 * tx];
-                window_sums_row<Sum2, HW, 2>([&](int i, Sum2 (&row)[RW]) { load_f2(ba + i * PW, row); }, sA[oy]);
+                window_sums_row<F2, HW, 2>([&](int i, F2 (&row)[RW]) { load_f2(ba + i * PW, row); }, sA[oy]);
                 __builtin_amdgcn_sched_barrier(0);
                 const float2 *bb = &s_pb[(NY * ty + oy) * PW + 2 * tx];
-                window_sums_row<Sum2, HW, 2>([&](int i, Sum2 (&row)[RW]) { load_f2(bb + i * PW, row); }, sB[oy]);
+                window_sums_row<F2, HW, 2>([&](int i, F2 (&row)[RW]) { load_f2(bb + i * PW, row); }, sB[oy]);
                 __builtin_amdgcn_sched_barrier(0);
                 const float *bc = &s_pc[(NY * ty + oy) * PW + 2 * tx];
                 window_sums_row<float, HW, 2>([&](int i, float (&row)[RW]) { load_f1(bc + i * PW, row); }, sC[oy]);
@@ -1551,8 +1411,6 @@ __global__ __launch_bounds__(256) void k_lkw(LkArgs a)
             }
         }
 
-        probe<3>(s_mem);
-        OFLK_STAMP(12);   // [12] stage 3: window sums
         const int gxb = x0 + 2 * tx;
         float su = 0.0f, sv = 0.0f;
         // planar outputs (SINGLE / GRADS always; ITER when this launch delivers the call's result)
@@ -1634,18 +1492,13 @@ __global__ __launch_bounds__(256) void k_lkw(LkArgs a)
                 s_red[1][tid >> 6] = (double)sv;
             }
         }
-        OFLK_STAMP(13);   // [13] solve, flow += d, stores, |d| reduction
-        // stage 3 has read the planes (the next tile's staging overwrites them) and s_red is complete
+        // barrier 4: stage 3 has read the planes (the next tile's staging overwrites them) and s_red is complete
         if (MODE == MODE_ITER || (LOOPS && it + 1 < ntile)) __syncthreads();
-        OFLK_STAMP(14);   // [14] barrier 4
         if (MODE == MODE_ITER && tid == 0) {
             blk_u += (s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3]);
             blk_v += (s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3]);
         }
     }
-#ifdef OFLK_STAMPS
-    bt[2] = (unsigned)__builtin_amdgcn_s_memrealtime();
-#endif
     if (MODE == MODE_ITER && threadIdx.x == 0) lk_report(a, b, blk_u, blk_v);
     if constexpr (CAN_REDO) {
         // every block read the count when it started; the last one to finish leaves the list empty for the next call
@@ -1657,24 +1510,6 @@ __global__ __launch_bounds__(256) void k_lkw(LkArgs a)
             }
         }
     }
-#ifdef OFLK_STAMPS
-    __syncthreads();
-    if (a.stamps) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the report's atomics have been issued and acknowledged
-        bt[3] = (unsigned)__builtin_amdgcn_s_memrealtime();
-        if (threadIdx.x == 0) {
-            unsigned *o = a.stamps + (size_t)gridDim.x * 512 + (size_t)blockIdx.x * 8;
-            o[0] = bt[0]; o[1] = bt[1]; o[2] = bt[2]; o[3] = bt[3];
-            o[4] = __builtin_amdgcn_s_getreg(4 | (31 << 11));    // HW_ID: wave, simd, pipe, cu, sh, se ...
-            o[5] = __builtin_amdgcn_s_getreg(20 | (31 << 11));   // XCC_ID
-            o[6] = (unsigned)ntile;
-            o[7] = 1u;
-        }
-        if (threadIdx.x < 4) s_st[threadIdx.x][0][15] = (unsigned)ntile;
-        __syncthreads();
-        for (int i = threadIdx.x; i < 4 * 8 * 16; i += 256) a.stamps[(size_t)blockIdx.x * 512 + i] = (&s_st[0][0][0])[i];
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -1978,20 +1813,11 @@ struct PyrCert {
     }
 };
 
-#ifdef OFLK_DIAG
-// diagnostic build only: waves of passes B and C that ran, and that took the exact redo ([B ran, B redo, C ran, C redo])
-__device__ unsigned long long g_pyr_cert_waves[4];
-__device__ __forceinline__ void pyr_cert_count(int slot)
-{
-    if (__ffsll((long long)__ballot(1)) - 1 == (int)(threadIdx.x & 63)) atomicAdd(&g_pyr_cert_waves[slot], 1ull);
-}
-#endif
-
 template <class PIX, int ARITH = PYR_EXACT, int TILE = PYR_TILE_GENERAL>
 __global__ __launch_bounds__(256) void k_pyr_down(PyrArgs a)
 {
     using G = PyrGeom<TILE>;
-    constexpr bool HALF_A = TILE == PYR_TILE_HALF && (OFLK_PYR_HALF & 1), HALF_D = TILE == PYR_TILE_HALF && (OFLK_PYR_HALF & 2);
+    constexpr bool HALF = TILE == PYR_TILE_HALF;   // the half-scale tile: its own staging (stage A) and sampling (stage D)
     constexpr int kPBW = G::BW, kPBH = G::BH, kPIW = G::IW, kPIH = G::IH, kPVS = G::VS, kPHS = G::HS;   // this geometry's
     __shared__ __attribute__((aligned(16))) float s_in[kPIH * kPIW];   // stage A (8-byte column-pair writes); reused for the blurred tile (stage C output)
     __shared__ float s_v[kPBH * kPVS];
@@ -2038,13 +1864,13 @@ __global__ __launch_bounds__(256) void k_pyr_down(PyrArgs a)
         const int r0 = tid / kPIW, c0 = tid - r0 * kPIW;
         float vals[NA];
         bool staged = false;
-        if constexpr (sizeof(PIX) == 4 && OFLK_PYR_PAIRS) {
+        if constexpr (sizeof(PIX) == 4) {
             if (ybase >= 0 && ybase + kPIH <= H && xbase >= 0 && xbase + kPIW <= W) {
                 // interior tile, float32 frames: column PAIRS, one 8-byte load and one 8-byte LDS write each (the tile is
                 // 82 = 2 x 41 columns wide; 2050 pairs = 8 per thread + 2.  Tight: 2 x 40, 1920 pairs = 7.5 per thread)
                 constexpr int PWD = kPIW / 2, NPR = kPIH * PWD, NB = (NPR + 255) / 256, QB = 256 / PWD, RB = 256 % PWD;
                 static_assert(kPIW % 2 == 0, "pairs");
-                if constexpr (HALF_A) {
+                if constexpr (HALF) {
                     // a thread keeps its column pair and takes every RH-th row: the rows advance by a wave-uniform
                     // constant and pair (r + RH k, c) is LDS pair tid + NT k, so no load carries a compare or a select
                     constexpr int RH = 6, NT = RH * PWD, NK = kPIH / RH;   // 240 threads, 8 rows each
@@ -2081,7 +1907,7 @@ __global__ __launch_bounds__(256) void k_pyr_down(PyrArgs a)
         if (staged) {
         } else
         if (ybase >= 0 && ybase + kPIH <= H && xbase >= 0 && xbase + kPIW <= W) {
-            if constexpr (HALF_A) {
+            if constexpr (HALF) {
                 // element-wise interior tile (uint8 frames), as the pairs above: a thread keeps its column and takes every
                 // RH-th row; element (r + RH k, c) is LDS cell tid + NT k
                 constexpr int RH = 3, NT = RH * kPIW, NK = kPIH / RH;   // 240 threads, 16 rows each
@@ -2162,13 +1988,7 @@ __global__ __launch_bounds__(256) void k_pyr_down(PyrArgs a)
                     cert.add(t, (float)t);
                     store(o, t);
                 }
-#ifdef OFLK_DIAG
-                pyr_cert_count(0);
-#endif
                 if (__any(!cert.safe(M))) {   // wave-uniform: SciPy's sequence for this wave's outputs
-#ifdef OFLK_DIAG
-                    pyr_cert_count(1);
-#endif
                     // the window made opaque: shared with the fast path, the pair sums of all outputs would stay live
 #pragma unroll
                     for (int k = 0; k < RS + 16; k++) asm volatile("" : "+v"(win[k]));
@@ -2213,13 +2033,7 @@ __global__ __launch_bounds__(256) void k_pyr_down(PyrArgs a)
                     cert.add(t, (float)t);
                     store(o, t);
                 }
-#ifdef OFLK_DIAG
-                pyr_cert_count(2);
-#endif
                 if (__any(!cert.safe(M))) {
-#ifdef OFLK_DIAG
-                    pyr_cert_count(3);
-#endif
                     // the window made opaque: shared with the fast path, the pair sums of all outputs would stay live
 #pragma unroll
                     for (int k = 0; k < CS + 16; k++) asm volatile("" : "+v"(win[k]));
@@ -2253,7 +2067,7 @@ __global__ __launch_bounds__(256) void k_pyr_down(PyrArgs a)
         }
         return (float)acc;
     };
-    if constexpr (HALF_D) {
+    if constexpr (HALF) {
         // Thread (tr, tc) produces outputs (i, j) and (i + 8, j).  floor(i * step) is 2 i for every output but the last of
         // an axis (the host's pyr_half), and 2 i is exact in fp64, so the fraction i * step - 2 i is the reference's
         // y - floor(y) without the floor or a conversion to int; the x side serves both outputs.
@@ -2755,7 +2569,7 @@ template <int HW, bool VEC>
 __global__ __launch_bounds__(256) void k_lk16d(Lk16sArgs a)
 {
     constexpr bool ODD = HW % 2 == 1;
-    constexpr int R = HW + 1, S = 2 * HW + 1, HL = (R + 1) / 2, K = ODD ? (HW - 1) / 2 : HW / 2, OUTW = 2 * (64 - 2 * HL), PF = OFLK_LK16_PF, WPB = 4;
+    constexpr int R = HW + 1, S = 2 * HW + 1, HL = (R + 1) / 2, K = ODD ? (HW - 1) / 2 : HW / 2, OUTW = 2 * (64 - 2 * HL), PF = 2, WPB = 4;   // PF: rows of frame loads in flight per wave
     constexpr int SHR = 0x138, SHL = 0x130;   // DPP wave_shr:1 / wave_shl:1
     const int lane = threadIdx.x & 63;
     const int H = a.H, W = a.W;

@@ -56,18 +56,9 @@ __device__ __forceinline__ float wshift(float v)   // 0x138: lane i takes lane i
 }
 
 constexpr int kLksOutW = 120;   // output columns per wave
-#ifndef OFLK_LKS_PFROWS
-#define OFLK_LKS_PFROWS 0     // the prefetch of `curr` runs this many rows ahead of the coalesced loads
-#endif
-#ifndef OFLK_LKS_LD_SINGLE
-#define OFLK_LKS_LD_SINGLE 3
-#endif
-#ifndef OFLK_LKS_LD_ITER
-#define OFLK_LKS_LD_ITER 3
-#endif
-#ifndef OFLK_LKS_WAVES
-#define OFLK_LKS_WAVES 2      // waves per SIMD the kernel's register count allows (185 - 193 VGPRs; the host sizes segments with it)
-#endif
+constexpr int kLksLdSingle = 3; // rows the coalesced loads run ahead of the arithmetic (k_lks's LD), MODE_SINGLE
+constexpr int kLksLdIter = 3;   // ... MODE_ITER
+constexpr int kLksWaves = 2;    // waves per SIMD the kernel's register count allows (185 - 193 VGPRs; the host sizes segments with it)
 
 // MODE_SINGLE on integer-valued frames p, q in [0, 255] (lucas_kanade_core.py:36-43, :110-119): avg = (p + q)/2 is a
 // multiple of 1/2, Ix and Iy (Sobel weights 1/8, 1/4) multiples of 1/16 with |Ix| <= 127.5, It = p - q an integer with
@@ -83,25 +74,12 @@ constexpr int kLksOutW = 120;   // output columns per wave
 // integer) flags its tile for the NumPy-order kernel.
 constexpr float kLksExactBound = 65536.0f;
 
-// timing-only ablations (diagnostic builds, wrong results): 1 no gathers (warp from the coalesced prefetch), 2 no flow
-// re-read, 4 no stores, 8 no solve, 16 no horizontal sums, 32 no lerp arithmetic
-#if defined(OFLK_LKS_ABL) && !defined(OFLK_DIAG)
-#error "OFLK_LKS_ABL is a diagnostic build: add -DOFLK_DIAG"
-#endif
-#ifndef OFLK_LKS_ABL
-#define OFLK_LKS_ABL 0
-#endif
-#ifdef OFLK_LKS_FORCE_WAVES
-#define OFLK_LKS_ATTR __attribute__((amdgpu_waves_per_eu(OFLK_LKS_FORCE_WAVES)))
-#else
-#define OFLK_LKS_ATTR
-#endif
 struct __attribute__((packed, aligned(8))) Flow2 { float u0, v0, u1, v1; };   // two adjacent {u, v} cells at an 8-byte aligned address
 
 // HW = 2 (5x5) everywhere; HW = 3 (7x7) for MODE_SINGLE only: there the order of the 49 additions does not matter on 8-bit
 // frames (same bound: sum |Ix It| <= sqrt(2^16 * 49 * 255^2) = 456 960 < 2^20), so the association of the sums below is free.
 template <int MODE, bool VEC, int WARPV, class PIX = float, bool UPS = false, int HW = 2>
-__global__ __launch_bounds__(256) OFLK_LKS_ATTR void k_lks(LkArgs a)
+__global__ __launch_bounds__(256) void k_lks(LkArgs a)
 {
     static_assert(MODE == MODE_SINGLE || MODE == MODE_ITER, "gradient planes take the tile kernel");
     static_assert(!UPS || MODE == MODE_ITER, "the fused flow upsampling belongs to an iteration");
@@ -226,7 +204,7 @@ __global__ __launch_bounds__(256) OFLK_LKS_ATTR void k_lks(LkArgs a)
     // coalesced loads run LD rows ahead of the arithmetic (a multiple of 3, the period of the other rings: the row loop is
     // unrolled LD times so that every ring slot is a compile-time index).  Bytes in flight are what a streaming kernel lives
     // on: a wave holds LD rows of 16 - 28 bytes per lane
-    constexpr int LD = MODE == MODE_SINGLE ? OFLK_LKS_LD_SINGLE : OFLK_LKS_LD_ITER;
+    constexpr int LD = MODE == MODE_SINGLE ? kLksLdSingle : kLksLdIter;
     static_assert(LD % 3 == 0, "the load ring's period must be a multiple of the other rings' period");
     constexpr int U = LD % QR == 0 ? LD : LD * QR / 3;   // unroll: lcm of the ring periods (LD and QR are multiples of 3)
     float2 Pr[LD];                        // prev rows
@@ -273,12 +251,12 @@ __global__ __launch_bounds__(256) OFLK_LKS_ATTR void k_lks(LkArgs a)
             Ub[slot][0] = ld_off<float2>(row0, oc);
             Ua[slot][1] = ld_off<Flow2>(row1, ob);
             Ub[slot][1] = ld_off<float2>(row1, oc);
-            Cr[slot] = ld_pix<PIX>(scalar_ptr(curr + row_e(r + OFLK_LKS_PFROWS)), (unsigned)c0);
+            Cr[slot] = ld_pix<PIX>(scalar_ptr(curr + row_e(r)), (unsigned)c0);
         } else if constexpr (MODE == MODE_ITER) {
             Fr[slot] = load_flow2(fin, rowe);
             // the warp's gathers two rows later find `curr` in the L2 instead of paying the HBM's latency inside the row loop:
             // a coalesced read of the same row brings its lines in (flows of a few pixels stay inside them)
-            Cr[slot] = ld_pix<PIX>(scalar_ptr(curr + row_e(r + OFLK_LKS_PFROWS)), (unsigned)c0);
+            Cr[slot] = ld_pix<PIX>(scalar_ptr(curr + row_e(r)), (unsigned)c0);
         } else {
             Qr[slot] = load_pix2(curr, rowe);
         }
@@ -314,10 +292,8 @@ __global__ __launch_bounds__(256) OFLK_LKS_ATTR void k_lks(LkArgs a)
             // int64 + float32 -> float64, as the reference (lucas_kanade_pyramidal.py:88-95)
             gt[0] = lean_frac_at(lg, yd + (double)f.y, gxd0 + (double)f.x);
             gt[1] = lean_frac_at(lg, yd + (double)f.w, gxd1 + (double)f.z);
-            if constexpr (!(OFLK_LKS_ABL & 1)) {
-                lean_load<false, PIX>(lg, curr, gt[0], g0[0], g1[0]);
-                lean_load<false, PIX>(lg, curr, gt[1], g0[1], g1[1]);
-            }
+            lean_load<false, PIX>(lg, curr, gt[0], g0[0], g1[0]);
+            lean_load<false, PIX>(lg, curr, gt[1], g0[1], g1[1]);
         }
     };
 
@@ -339,11 +315,7 @@ __global__ __launch_bounds__(256) OFLK_LKS_ATTR void k_lks(LkArgs a)
             if constexpr (MODE == MODE_ITER) touch = fmaxf(touch, Cr[jl]);
             float2 q;
             if constexpr (MODE == MODE_ITER) {
-                if constexpr ((OFLK_LKS_ABL & 1) != 0) {
-                    q.x = Cr[jl] + (float)gt[0].rx; q.y = Cr[jl] + (float)gt[1].ry;
-                } else if constexpr ((OFLK_LKS_ABL & 32) != 0) {
-                    q.x = g0[0].a + g1[0].b + (float)gt[0].rx; q.y = g0[1].a + g1[1].b + (float)gt[1].ry;
-                } else if constexpr (WARPV == WARP_LERP64) {
+                if constexpr (WARPV == WARP_LERP64) {
                     q.x = lerp64_finish(gt[0], g0[0], g1[0]);
                     q.y = lerp64_finish(gt[1], g0[1], g1[1]);
                 } else {
@@ -375,8 +347,7 @@ __global__ __launch_bounds__(256) OFLK_LKS_ATTR void k_lks(LkArgs a)
             // loads three rows ahead -- and every wait leaves the younger ones in flight.
             float4 pf = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             if constexpr (MODE == MODE_ITER) {
-                if constexpr (!(OFLK_LKS_ABL & 2))
-                    if (o_live) pf = ring[(o & (FRING - 1)) * 64];   // written four iterations ago by this lane
+                if (o_live) pf = ring[(o & (FRING - 1)) * 64];   // written four iterations ago by this lane
                 issue_gathers((jl + 1) % LD, r + 1);          // used by the next row, after this row's arithmetic
             }
             issue_loads(jl, r + LD);
@@ -450,15 +421,13 @@ __global__ __launch_bounds__(256) OFLK_LKS_ATTR void k_lks(LkArgs a)
                     S[pl][0] = X + wshift<SHR>(wshift<SHR>(hi));   // even column c: ... + V[c-3]
                     S[pl][1] = X + wshift<SHL>(wshift<SHL>(lo));   // odd column c:  ... + V[c+3]
                 }
-                if constexpr ((OFLK_LKS_ABL & 16) != 0) { S[pl][0] = lo; S[pl][1] = hi; }
             }
             const bool oky = o >= HW && o < H - HW;            // borders stay 0 (lucas_kanade_core.py:101-108)
             float du[2], dv[2];
 #pragma unroll
             for (int c = 0; c < 2; c++) {
                 float uu, vv;
-                if constexpr ((OFLK_LKS_ABL & 8) != 0) { uu = S[0][c] + S[1][c] + S[2][c]; vv = S[3][c] + S[4][c]; }
-                else if constexpr (MODE == MODE_SINGLE) {
+                if constexpr (MODE == MODE_SINGLE) {
                     // Where the result is kept (integer frames in [0, 255], Sxx, Syy < 2^16 -- everything else is redone by the
                     // tile kernel) the quotients' operands are in div2_shared_rcp's range: 1e-4 < |det| <= Sxx Syy < 2^32;
                     // a numerator is the rounded difference of two exact multiples of 2^-12 (sums are multiples of 2^-8 and
@@ -479,7 +448,7 @@ __global__ __launch_bounds__(256) OFLK_LKS_ATTR void k_lks(LkArgs a)
                     }
                 }
             }
-            if (lane_out && o_live && (!(OFLK_LKS_ABL & 4) || du[0] == 1.25e37f)) {
+            if (lane_out && o_live) {
                 const unsigned orow = (unsigned)(o * W);
                 float2 ru = make_float2(du[0], du[1]), rv = make_float2(dv[0], dv[1]);
                 if constexpr (MODE == MODE_ITER) {

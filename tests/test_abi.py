@@ -156,21 +156,24 @@ def test_product_modules_never_touch_the_oracle():
 
 
 def test_product_translation_unit_carries_no_development_switches():
-    """the shipped library reads no environment variable and carries no timing / ablation switches: diagnostic code
-    (in-kernel stamps, sensitivity probes) only exists under -DOFLK_DIAG"""
+    """the shipped library reads no environment variable and its translation unit has no build switches: no timing /
+    ablation / diagnostic code, no preprocessor conditional, no macro besides OFLK_API and HIP_TRY, and a Makefile that
+    passes no -D"""
     import re
 
     csrc = ROOT / "optical-flow-fpga_amd" / "csrc"
-    hip = (csrc / "oflk.hip").read_text()
-    hpp = (csrc / "oflk_kernels.hpp").read_text()
-    assert "getenv" not in hip and "getenv" not in hpp
-    for word in ("OFLK_ABLATE", "OFLK_LK16_ABL", "OFLK_LK16_TILED", "OFLK_LK16_COLS", "OFLK_TPB", "OFLK_X_"):
-        assert word not in hip, word
-    for word in ("OFLK_ABLATE", "OFLK_LK16_ABL", "k_lk16s", "k_lk16<"):
-        assert word not in hpp, word
-    # every stamp / probe site is behind the diagnostic build
-    assert re.search(r"#if defined\(OFLK_STAMPS\) && !defined\(OFLK_DIAG\)\s*\n#error", hpp)
-    assert "#if defined(OFLK_DIAG) && defined(OFLK_PROBE)" in hpp
+    sources = sorted(csrc.glob("*.hip")) + sorted(csrc.glob("*.hpp"))
+    assert {"oflk.hip", "oflk_kernels.hpp", "oflk_stream.hpp"} <= {f.name for f in sources}
+    for f in sources:
+        text = f.read_text()
+        assert "getenv" not in text, f.name
+        for word in ("OFLK_ABLATE", "OFLK_LK16_ABL", "OFLK_LK16_TILED", "OFLK_LK16_COLS", "OFLK_TPB", "OFLK_X_", "k_lk16s",
+                     "k_lk16<", "OFLK_DIAG", "OFLK_STAMP", "OFLK_PROBE", "OFLK_LKS_ABL"):
+            assert word not in text, (f.name, word)
+        for n, line in enumerate(text.splitlines(), 1):
+            assert not re.match(r"\s*#\s*(if|ifdef|ifndef|elif|else|endif)\b", line), (f.name, n, line)
+            m = re.match(r"\s*#\s*define\s+(\w+)", line)
+            assert not m or m.group(1) in ("OFLK_API", "HIP_TRY"), (f.name, n, line)
     mk = (csrc / "Makefile").read_text()
-    default_flags = [l for l in mk.splitlines() if l.startswith("FLAGS")][0]
-    assert "OFLK_DIAG" not in default_flags
+    assert "DEFS" not in mk
+    assert not re.search(r"(?<![\w-])-D", mk), "the Makefile passes no -D"

@@ -258,7 +258,7 @@ def test_every_envelope_cell_on_the_bench_pair(oracle):
 # ---------------------------------------------------------------------------------------------------------------
 SUM_TILES, SUM_STREAM, SUM_HOST = 0, 1, 2   # include/oflk.h OFLK_SUM_*
 U32 = 2.0 ** -24
-K5NY = 3                                    # csrc/oflk_kernels.hpp k5NY (OFLK_NY): a tile is 64 x 8 K5NY outputs
+K5NY = 3                                    # csrc/oflk_kernels.hpp k5NY: a tile is 64 x 8 K5NY outputs
 
 
 def numpy_mean_error(npix: int) -> float:
@@ -392,8 +392,8 @@ def _const(pattern: str, file: str) -> int:
 def _lks_segments(H: int, W: int, B: int):
     """(segments, rows per segment) of a k_lks iteration launch: wave_segments as launch_lks calls it in csrc/oflk.hip, restated"""
     out_w = _const(r"constexpr int kLksOutW = (\d+);", "oflk_stream.hpp")
-    waves = _const(r"#define OFLK_LKS_WAVES (\d+)", "oflk_stream.hpp")
-    seg_rows = _const(r"#define OFLK_LKS_SEG_ROWS (\d+)", "oflk.hip")
+    waves = _const(r"constexpr int kLksWaves = (\d+);", "oflk_stream.hpp")
+    seg_rows = _const(r"constexpr int kLksSegRows = (\d+);", "oflk.hip")
     strips = -(-W // out_w) * B
     slots = 256 * 4 * waves
     segs = -(-H // seg_rows)
@@ -414,9 +414,9 @@ def test_band_mirror_is_the_library():
     kernel constants the mirror assumes are the sources'"""
     import _oflk
 
-    assert _const(r"#define OFLK_NY (\d+)", "oflk_kernels.hpp") == K5NY
+    assert _const(r"constexpr int k5NY = (\d+);", "oflk_kernels.hpp") == K5NY
     assert _const(r"constexpr int k5TX = (\d+);", "oflk_kernels.hpp") == 64
-    assert _const(r"#define OFLK_LKS_LD_ITER (\d+)", "oflk_stream.hpp") == 3   # 2 x 3 fp32 terms per lane before fp64
+    assert _const(r"constexpr int kLksLdIter = (\d+);", "oflk_stream.hpp") == 3   # 2 x 3 fp32 terms per lane before fp64
     L = _oflk.lib()
     for H, W in ((1, 1), (3, 5), (6, 8), (23, 21), (30, 40), (60, 80), (97, 131), (240, 320), (241, 323), (1080, 1920),
                  (2160, 3840), (4320, 7680)):

@@ -1,10 +1,8 @@
 #!/usr/bin/env python3
-"""k_pyr_down on one kind of 1080p frames: time per launch and, with a diagnostic build (make DEFS=-DOFLK_DIAG OUT=...,
-named by OFLK_LIB), the share of waves of passes B and C that left the certified fast path for the exact redo.
+"""k_pyr_down on one kind of 1080p frames: time per launch.
 
-    OFLK_LIB=tools/variants/cert_diag.so python3 tools/pyr_redo.py --frames bench|dots [--pairs 8]"""
+    python3 tools/pyr_redo.py --frames bench|dots [--pairs 8]"""
 import argparse
-import ctypes
 import json
 import sys
 from pathlib import Path
@@ -41,11 +39,6 @@ def main():
     for _ in range(2):
         plan.pyramidal(prev.data_ptr(), curr.data_ptr(), u.data_ptr(), v.data_ptr(), st)
     torch.cuda.synchronize()
-    L = _oflk.lib()
-    counts = (ctypes.c_ulonglong * 4)()
-    diag = hasattr(L, "oflk_debug_pyr_cert_waves")
-    if diag:
-        L.oflk_debug_pyr_cert_waves(counts, 1)
     plan.set_profiling(True)
     for _ in range(args.reps):
         plan.pyramidal(prev.data_ptr(), curr.data_ptr(), u.data_ptr(), v.data_ptr(), st)
@@ -53,11 +46,6 @@ def main():
     t = plan.kernel_times()["pyr_down_fused"]
     out = {"frames": args.frames, "pairs": B, "lib": str(_oflk.LIB_PATH.name),
            "pyr_down_us_per_launch": round(1e3 * t["total_ms"] / t["launches"], 1), "launches": t["launches"]}
-    if diag:
-        L.oflk_debug_pyr_cert_waves(counts, 0)
-        b, br, c, cr = (int(x) for x in counts)
-        out.update({"waves_B": b, "redo_B": br, "redo_share_B": round(br / max(b, 1), 5),
-                    "waves_C": c, "redo_C": cr, "redo_share_C": round(cr / max(c, 1), 5)})
     plan.close()
     print(json.dumps(out))
 

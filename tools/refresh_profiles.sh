@@ -48,16 +48,7 @@ python3 tools/issue_bounds.py gpurun_out/pmc_$TAG profiles/${TAG}_valu_wall.txt 
 #     partner kernel on a second stream takes from the step
 bash tools/pmc_calib.sh ${TAG}_calib > gpurun_out/calib_$TAG.log 2>&1 && cp gpurun_out/pmc_${TAG}_calib/summary.txt profiles/${TAG}_sq_counter_calibration.txt || true
 [ -f tools/ubench/libspin.so ] && timeout -k 10 400 python3 tools/corun.py --out profiles/${TAG}_corun.json > gpurun_out/corun_$TAG.log 2>&1 || true
-# 6. in-kernel timeline of the same launch (diagnostic build)                  -> profiles/<tag>_stamps_timeline.{json,txt}
-if [ -f tools/liboflk_stamps.so ]; then
-  OFLK_LIB=tools/liboflk_stamps.so timeout -k 10 200 python3 tools/stamps.py profiles/${TAG}_stamps_timeline.json > profiles/${TAG}_stamps_timeline.txt 2>&1 || true
-  rm -f profiles/${TAG}_stamps_timeline.raw.npy
-fi
-# 6b. block lifetimes of the same launch, fp16 mode counters / memory-pattern ceilings / EPE report
-if [ -f tools/liboflk_bt.so ]; then
-  OFLK_LIB=tools/liboflk_bt.so timeout -k 10 200 python3 tools/block_times.py profiles/${TAG}_block_times.json > gpurun_out/bt_$TAG.log 2>&1 || true
-  rm -f profiles/${TAG}_block_times.raw.npy
-fi
+# 6. fp16 mode counters / memory-pattern ceilings / EPE report
 bash tools/pmc_fp16.sh $TAG > gpurun_out/pmc_fp16_$TAG.log 2>&1 && cp gpurun_out/pmc_fp16_$TAG/summary.txt profiles/${TAG}_pmc_fp16.txt || true
 python3 tools/hbm_probe.py > profiles/${TAG}_hbm_probe.txt 2>&1 || true
 [ -x tools/ubench/rowwalk ] && timeout -k 10 120 tools/ubench/rowwalk 76 > profiles/${TAG}_rowwalk.txt 2>&1 || true

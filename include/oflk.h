@@ -846,8 +846,9 @@ int oflk_stabilize_sequence_u8(const unsigned char *frames, int T, int H, int W,
  * and positive, F < 1, H or W < 2, Hc or Wc < 1, an unknown blend, NULL pointers (d_counts, d_held, d_skip, d_count and the
  * sequence call's outputs after `canvas` may be NULL; d_model when T == 1), a map or chain output that is not 8-byte aligned, a
  * state that is too small or not 256-byte aligned: OFLK_ERR_INVALID;  a frame or a canvas of 2^30 pixels or more, a canvas
- * that reaches 2^30 from the origin: OFLK_ERR_UNSUPPORTED.  A temporal median and bundle adjustment of the chain (its drift
- * grows with the distance from the anchor) are not offered;  exposure compensation is the _exposure forms below. */
+ * that reaches 2^30 from the origin: OFLK_ERR_UNSUPPORTED.  Bundle adjustment of the chain (its drift grows with the distance
+ * from the anchor) is not offered;  exposure compensation is the _exposure forms below, the temporal median
+ * oflk_mosaic_median further down. */
 #define OFLK_MOSAIC_MEAN 0
 #define OFLK_MOSAIC_FEATHER 1
 #define OFLK_MOSAIC_FIRST 2
@@ -902,6 +903,37 @@ int oflk_mosaic_composite_exposure_host(const float *frames, int F, int H, int W
 int oflk_mosaic_composite_exposure_host_u8(const unsigned char *frames, int F, int H, int W, const double *map,
                                            const unsigned char *skip, const double *exposure, int x0, int y0, int Hc, int Wc,
                                            int blend, unsigned char *out, int *count);
+/* The temporal median: the blend that drops what moves through (the statement: tests/mosaic_median_model.py).  The four
+ * blends above paint an object that moves on its own into the canvas;  the median of a pixel's samples does not, wherever the
+ * background is seen in more than half of the frames that cover the pixel.  It needs every sample of a pixel at once, so it
+ * is no fifth blend of the accumulate / resolve pair but a call of its own with all F frames resident and no state.
+ * Canvas pixel coordinates, w, xs, ys, inside and the float32 bilinear sample s of frame f are oflk_mosaic_accumulate's;
+ * frames with skip[f] != 0 take no part.
+ *   value     e = s;  with an exposure e = f32(eg_f * f64(s) + eb_f): the product rounded, then the sum, then to float32
+ *   order     ascending by the uint32 key of e's bits b:  key = ~b when the sign bit is set, else b ^ 0x80000000, which is
+ *             -NaN < -inf < negatives < -0 < +0 < positives < +inf < +NaN.  Equal keys are equal bytes, so ties cannot show,
+ *             and the result does not depend on the frame order, on the selection method or on the launch geometry
+ *   median    n = the number of covering frames, e_(0) <= .. <= e_(n-1) in that order.  n odd: v = e_((n-1)/2);  n even:
+ *             v = f32((f64(e_(n/2-1)) + f64(e_(n/2))) * 0.5), so inf + -inf is a NaN;  n == 0: v = 0
+ *   store     float32: v;  uint8: the resolve's saturating conversion of v (254.5 gives 254, a NaN 0);  count = n
+ * (The sign of a NaN that an operation makes of other values -- inf * 0 in the sample, inf - inf -- is the hardware's;  a NaN
+ * that comes in with a frame or an exposure keeps its own.)
+ * u8 is the type of both the frames and the output.  One launch, no workspace, no atomics;  asynchronous on `stream`.  A pixel
+ * keeps its oflk_mosaic_median_capacity() smallest samples on chip (host only, no device call), which holds the median of up
+ * to twice as many frames less one;  a pixel covered by more gives the same bytes, more slowly: the frames are gathered again,
+ * once for every further capacity's worth of samples below the median.
+ * Refusals, before any device call, those of oflk_mosaic_accumulate without the blend: F < 1, H or W < 2, Hc or Wc < 1, NULL
+ * frames, map or output, a map or exposure that is not 8-byte aligned: OFLK_ERR_INVALID;  a frame or a canvas of 2^30 pixels
+ * or more: OFLK_ERR_UNSUPPORTED.  d_skip, d_exposure ([F][2] float64 (eg, eb)) and d_count may be NULL.  The host forms
+ * upload all F frames at once -- the price of a median -- and return OFLK_ERR_NOMEM when the device cannot hold them.
+ * A weighted median, a vector median for colour and a sequence call are not offered. */
+int oflk_mosaic_median_capacity(void);
+int oflk_mosaic_median(const void *d_frames, int u8, int F, int H, int W, const double *d_map, const unsigned char *d_skip,
+                       const double *d_exposure, int x0, int y0, int Hc, int Wc, void *d_out, int *d_count, void *stream);
+int oflk_mosaic_median_host(const float *frames, int F, int H, int W, const double *map, const unsigned char *skip,
+                            const double *exposure, int x0, int y0, int Hc, int Wc, float *out, int *count);
+int oflk_mosaic_median_host_u8(const unsigned char *frames, int F, int H, int W, const double *map, const unsigned char *skip,
+                               const double *exposure, int x0, int y0, int Hc, int Wc, unsigned char *out, int *count);
 /* Frames in, mosaic out.  By statement, byte for byte: oflk_pyramidal_sequence_klt_sparse_replenish on the frames,
  * oflk_tracks_homography on its rows with t0 = 0, oflk_mosaic_chain and oflk_mosaic_canvas, then oflk_mosaic_accumulate of all
  * frames under from_anchor with skip = dropped and the canvas's x0, y0, and oflk_mosaic_resolve.  Pass 1 is the replenish

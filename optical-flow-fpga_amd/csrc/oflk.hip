@@ -4927,6 +4927,60 @@ int mosaic_sequence(const PIX *frames, int T, int H, int W, const KltConfig &klt
                     capacity);
     return mosaic_composite_chunks<PIX>(call, frames, T, H, W, d_from, d_drop, x0, y0, Hc, Wc, blend, out, count);
 }
+
+// the temporal median's refusals: check_mosaic_frames' without the blend, then the pointers the median reads and writes
+int check_mosaic_median(const void *frames, bool u8, int F, int H, int W, const double *map, const double *exposure, int Hc, int Wc,
+                        const void *out)
+{
+    if (int rc = check_mosaic_frames(frames, F, H, W, map, Hc, Wc, OFLK_MOSAIC_MEAN)) return rc;
+    if (!out) return fail(OFLK_ERR_INVALID, "NULL output argument");
+    if (!aligned(map, 8) || !aligned(exposure, 8)) return fail(OFLK_ERR_INVALID, "the map and the exposure must be 8-byte aligned");
+    if (!u8 && (!aligned(frames, 4) || !aligned(out, 4))) return fail(OFLK_ERR_INVALID, "float32 frames and output must be 4-byte aligned");
+    return OFLK_OK;
+}
+
+// the one launch of the median on stream s; the arguments are checked.  d_exposure: NULL, or the frames' (eg, eb)
+template <class PIX>
+int mosaic_median_launch(const PIX *d_frames, int F, int H, int W, const double *d_map, const unsigned char *d_skip,
+                         const double *d_exposure, int x0, int y0, int Hc, int Wc, PIX *d_out, int *d_count, hipStream_t s)
+{
+    MosaicMedianArgs<PIX> a{};
+    a.in = d_frames; a.map = d_map; a.skip = d_skip; a.exposure = d_exposure;
+    a.out = d_out; a.count = d_count;
+    a.F = F; a.H = H; a.W = W;
+    a.x0 = x0; a.y0 = y0; a.Hc = Hc; a.Wc = Wc;
+    a.tiles_x = (Wc + kMedianBlockW - 1) / kMedianBlockW;
+    const dim3 grid((unsigned)a.tiles_x * (unsigned)((Hc + kMedianTileH - 1) / kMedianTileH));
+    if (d_exposure)
+        hipLaunchKernelGGL((k_mosaic_median<PIX, true>), grid, dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL((k_mosaic_median<PIX, false>), grid, dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return OFLK_OK;
+}
+
+// host arrays: every frame goes up before the one launch -- a median needs all samples of a pixel at once
+template <class PIX>
+int mosaic_median_host(const PIX *frames, int F, int H, int W, const double *map, const unsigned char *skip, const double *exposure,
+                       int x0, int y0, int Hc, int Wc, PIX *out, int *count)
+{
+    int rc = check_mosaic_median(frames, sizeof(PIX) == 1, F, H, W, map, exposure, Hc, Wc, out);
+    if (rc) return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const size_t plane = (size_t)H * W, npix = (size_t)Hc * Wc;
+    double *d_map = nullptr, *d_exposure = nullptr;
+    unsigned char *d_skip = nullptr;
+    PIX *d_in = nullptr, *d_out = nullptr;
+    int *d_count = nullptr;
+    if ((rc = call.upload(&d_map, map, 9 * (size_t)F)) || (skip && (rc = call.upload(&d_skip, skip, (size_t)F))) ||
+        (exposure && (rc = call.upload(&d_exposure, exposure, 2 * (size_t)F))) || (rc = call.upload(&d_in, frames, (size_t)F * plane)) ||
+        (rc = call.alloc(&d_out, npix)) || (rc = call.alloc(&d_count, npix, count != nullptr)) ||
+        (rc = mosaic_median_launch<PIX>(d_in, F, H, W, d_map, d_skip, d_exposure, x0, y0, Hc, Wc, d_out, d_count, nullptr)) ||
+        (rc = call.to_host(out, d_out, npix)) || (count && (rc = call.to_host(count, d_count, npix))))
+        return rc;
+    return call.sync();
+}
 }  // namespace
 
 OFLK_API size_t oflk_mosaic_state_bytes(int Hc, int Wc)
@@ -5108,6 +5162,30 @@ OFLK_API int oflk_mosaic_composite_exposure_host_u8(const unsigned char *frames,
                                                     int Wc, int blend, unsigned char *out, int *count)
 {
     return mosaic_composite_host<unsigned char>(frames, F, H, W, map, skip, x0, y0, Hc, Wc, blend, out, count, true, exposure);
+}
+
+OFLK_API int oflk_mosaic_median_capacity(void) { return kMedianCap; }
+
+OFLK_API int oflk_mosaic_median(const void *d_frames, int u8, int F, int H, int W, const double *d_map, const unsigned char *d_skip,
+                                const double *d_exposure, int x0, int y0, int Hc, int Wc, void *d_out, int *d_count, void *stream)
+{
+    if (int rc = check_mosaic_median(d_frames, u8 != 0, F, H, W, d_map, d_exposure, Hc, Wc, d_out)) return rc;
+    return u8 ? mosaic_median_launch<unsigned char>((const unsigned char *)d_frames, F, H, W, d_map, d_skip, d_exposure, x0, y0, Hc, Wc,
+                                                    (unsigned char *)d_out, d_count, (hipStream_t)stream)
+              : mosaic_median_launch<float>((const float *)d_frames, F, H, W, d_map, d_skip, d_exposure, x0, y0, Hc, Wc, (float *)d_out,
+                                            d_count, (hipStream_t)stream);
+}
+
+OFLK_API int oflk_mosaic_median_host(const float *frames, int F, int H, int W, const double *map, const unsigned char *skip,
+                                     const double *exposure, int x0, int y0, int Hc, int Wc, float *out, int *count)
+{
+    return mosaic_median_host<float>(frames, F, H, W, map, skip, exposure, x0, y0, Hc, Wc, out, count);
+}
+
+OFLK_API int oflk_mosaic_median_host_u8(const unsigned char *frames, int F, int H, int W, const double *map, const unsigned char *skip,
+                                        const double *exposure, int x0, int y0, int Hc, int Wc, unsigned char *out, int *count)
+{
+    return mosaic_median_host<unsigned char>(frames, F, H, W, map, skip, exposure, x0, y0, Hc, Wc, out, count);
 }
 
 OFLK_API int oflk_mosaic_sequence(const float *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,

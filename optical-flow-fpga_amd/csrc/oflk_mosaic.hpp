@@ -22,6 +22,9 @@
 //                       the row length a multiple of kMosaicPx and the outputs aligned to a lane's store) or one by one;
 //                       bytes through mosaic_store_value, which saturates: the one uint8 store here whose value can leave
 //                       [0, 255]
+//   k_mosaic_median<PIX, EXPOSURE>  the temporal median (oflk_mosaic_median; the statement is tests/mosaic_median_model.py): all
+//                       frames resident, one launch, no state: a pixel's samples as sortable keys in a column of LDS and a
+//                       bitwise selection there.  Its comment is at the end of this file
 //
 // The state (private to this file and to mosaic_state in oflk.hip): three planes of pitch Wp = Wc rounded up to kMosaicPx,
 // [Hc][Wp] float64 sum, [Hc][Wp] float64 wsum, [Hc][Wp] int32 count, each plane on a 256-byte boundary.  A lane's pixels are
@@ -350,6 +353,163 @@ __global__ __launch_bounds__(256) void k_mosaic_resolve(MosaicResolveArgs<PIX> a
                 a.out[o + k] = v[k];
                 if (a.count) a.count[o + k] = c[k];
             }
+    }
+}
+
+// ---- the temporal median: grid (tiles_x * ceil(Hc / kMedianTileH)), block 256 ----
+// The statement is tests/mosaic_median_model.py.  A lane owns one canvas pixel, a wave a tile of 16 x 4, a block four such
+// tiles side by side: 64 x 4.  The walk over the frames is k_mosaic_accumulate's (the cull on the wave's tile, 64 frames a
+// ballot, the per-pixel source expressions repeated once more); what a covering frame leaves is not a sum but the uint32 key
+// of its value, which goes to the lane's column of LDS, keys[wave][slot][lane]: the bank is the lane, so no access
+// conflicts, no lane reads another's and no barrier is needed.  A lane indexes no private array, so nothing goes to scratch.
+//
+// The column is kept sorted: a key is inserted where it belongs, the larger ones moving up one slot (one straight-line sweep
+// of min and max over the slots, whose LDS reads do not depend on one another), and once the column is full a key enters only
+// by pushing the largest out.  After one walk the column therefore holds the kMedianCap smallest keys of the pixel; the ranks (n-1)/2 and n/2 are read off when they are below kMedianCap, which they are for every pixel that up
+// to 2 kMedianCap - 1 frames cover.  Otherwise the walk is repeated (the gather is deterministic) for the keys above the
+// largest one held, T: the pass counts the keys <= T -- those beyond the column's are all equal to T, so a rank below the
+// count is T itself -- and collects the kMedianCap smallest keys above T, and so on: ceil((n/2 + 1) / kMedianCap) walks, and
+// only in the waves that have such a pixel.  Equal keys are equal bytes, so where a tie lands does not show, and neither does
+// the order the keys came in.
+//
+// kMedianCap keys a pixel is 32 KiB a block: 5 blocks a CU by LDS, all of its 160 KiB.  The kernel has 114 VGPRs, which is 4
+// waves a SIMD: the sweep unrolled over all 32 slots keeps its reads in flight together.  Unrolled by 8 it has fewer registers and 5 waves
+// and is 11 - 14 % slower on both scenes of tools/mosaic_bench.py.
+constexpr int kMedianCap = 32;     // keys of a pixel in LDS (oflk_mosaic_median_capacity)
+constexpr int kMedianTileW = 16;   // a wave's tile: 16 lanes across ...
+constexpr int kMedianTileH = 4;    // ... and 4 rows
+constexpr int kMedianBlockW = 64;  // a block's: four waves side by side
+
+template <class PIX>
+struct MosaicMedianArgs {
+    const PIX *in;               // [F][H][W], all resident
+    const double *map;           // [F][9]
+    const unsigned char *skip;   // [F] or NULL
+    const double *exposure;      // [F][2] (EXPOSURE) or unused
+    PIX *out;                    // [Hc][Wc]
+    int *count;                  // [Hc][Wc] or NULL
+    int F, H, W;
+    int x0, y0, Hc, Wc;
+    int tiles_x;                 // blocks across the canvas
+};
+
+// the order of the statement: ascending keys are -NaN < -inf < negatives < -0 < +0 < positives < +inf < +NaN
+__device__ __forceinline__ unsigned median_key(float e)
+{
+    const unsigned b = __float_as_uint(e);
+    return (b & 0x80000000u) ? ~b : b ^ 0x80000000u;
+}
+
+__device__ __forceinline__ float median_value(unsigned key)
+{
+    return __uint_as_float((key & 0x80000000u) ? key ^ 0x80000000u : ~key);
+}
+
+// every frame that may touch the wave's tile, ascending: sink(covers, key) once per such frame for the lane's pixel (fx, fy)
+template <class PIX, bool EXPOSURE, class SINK>
+__device__ __forceinline__ void mosaic_median_walk(const MosaicMedianArgs<PIX> &a, int lane, double X0, double X1, double Y0, double Y1,
+                                                   double fx, double fy, SINK &&sink)
+{
+    const double Wm1 = (double)(a.W - 1), Hm1 = (double)(a.H - 1);
+    const size_t plane = (size_t)a.H * (size_t)a.W;
+    for (int f0 = 0; f0 < a.F; f0 += 64) {
+        const int fl = f0 + lane;
+        bool keep = fl < a.F;
+        if (keep && a.skip) keep = a.skip[fl] == 0;
+        if (keep) keep = mosaic_touches(a.map + 9 * (size_t)fl, X0, X1, Y0, Y1, Wm1, Hm1);
+        unsigned long long todo = __ballot(keep);
+        while (todo) {
+            const int f = f0 + (int)__builtin_ctzll(todo);
+            todo &= todo - 1;
+            // the source position: k_mosaic_accumulate's expressions, repeated here as they are there
+            const double *__restrict__ m = a.map + 9 * (size_t)f;
+            const double m0 = m[0], m2 = m[2], m3 = m[3], m5 = m[5], m6 = m[6], m8 = m[8];
+            const double bx1 = m[1] * fy, by1 = m[4] * fy, bw = m[7] * fy;
+            const PIX *__restrict__ img = a.in + (size_t)f * plane;
+            const double w = (m6 * fx + bw) + m8;
+            const double xa = (m0 * fx + bx1) + m2;
+            const double ya = (m3 * fx + by1) + m5;
+            const double xs = xa / w;
+            const double ys = ya / w;
+            const bool ok = w > 0.0 && xs >= 0.0 && xs <= Wm1 && ys >= 0.0 && ys <= Hm1;
+            const BilinearTaps t = bilinear_taps(a.H, a.W, ys, xs);
+            float e = bilinear_finish(t, ld_pix<PIX>(img, (unsigned)t.i00), ld_pix<PIX>(img, (unsigned)t.i01),
+                                      ld_pix<PIX>(img, (unsigned)t.i10), ld_pix<PIX>(img, (unsigned)t.i11));
+            if constexpr (EXPOSURE) {
+                const double eg = a.exposure[2 * (size_t)f], eb = a.exposure[2 * (size_t)f + 1];
+                e = __double2float_rn(eg * (double)e + eb);
+            }
+            sink(ok, median_key(e));
+        }
+    }
+}
+
+template <class PIX, bool EXPOSURE>
+__global__ __launch_bounds__(256) void k_mosaic_median(MosaicMedianArgs<PIX> a)
+{
+    __shared__ unsigned keys[4][kMedianCap][64];
+    const int lane = (int)(threadIdx.x & 63);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int bx = (int)(blockIdx.x % (unsigned)a.tiles_x), by = (int)(blockIdx.x / (unsigned)a.tiles_x);
+    const int tx = bx * kMedianBlockW + wave * kMedianTileW, ty = by * kMedianTileH;
+    if (tx >= a.Wc) return;   // the whole wave; there is no barrier below
+    const int x = tx + (lane & 15), y = ty + (lane >> 4);
+    const bool live = y < a.Hc && x < a.Wc;   // a lane that is not computes (its taps are clamped) and stores nothing
+    // the tile's rectangle in map coordinates (the whole tile, also where it hangs over the canvas) and the lane's own pixel
+    const double X0 = (double)((long)a.x0 + (long)tx), X1 = (double)((long)a.x0 + (long)(tx + kMedianTileW - 1));
+    const double Y0 = (double)((long)a.y0 + (long)ty), Y1 = (double)((long)a.y0 + (long)(ty + kMedianTileH - 1));
+    const double fx = (double)((long)a.x0 + (long)x), fy = (double)((long)a.y0 + (long)y);
+    unsigned(*col)[64] = keys[wave];
+
+    int n = 0;
+    unsigned k_lo = 0u, k_hi = 0u, T = 0u;
+    bool got_lo = false, got_hi = false;
+    bool above = false;   // wave-uniform: this is a later walk, for the keys above T
+    for (;;) {
+        int m = 0, le = 0, seen = 0;   // keys in the column, keys <= T, covering frames
+        unsigned top = 0xFFFFFFFFu;    // the column's last slot
+        const bool idle = got_lo && got_hi;
+#pragma unroll
+        for (int j = 0; j < kMedianCap; j++) col[j][lane] = 0xFFFFFFFFu;   // an empty slot holds the largest key there is
+        mosaic_median_walk<PIX, EXPOSURE>(a, lane, X0, X1, Y0, Y1, fx, fy, [&](bool ok, unsigned key) {
+            const bool below = above && key <= T;
+            seen += ok ? 1 : 0;
+            le += ok && below ? 1 : 0;
+            // the insertion, straight-line: the key is carried up the column, every slot keeps the smaller of the two and
+            // hands on the larger; what falls off the end is the largest.  The reads do not wait for one another
+            if (ok && !below && !idle && (m < kMedianCap || key < top)) {
+                unsigned carry = key;
+#pragma unroll
+                for (int j = 0; j < kMedianCap; j++) {
+                    const unsigned c = col[j][lane];
+                    top = min(c, carry);
+                    carry = max(c, carry);
+                    col[j][lane] = top;
+                }
+                m = min(m + 1, kMedianCap);
+            }
+        });
+        n = seen;
+        const int r_lo = n > 0 ? (n - 1) >> 1 : 0, r_hi = n >> 1;
+        if (!got_lo && (r_lo < le || r_lo - le < m || n == 0)) {
+            k_lo = r_lo < le || n == 0 ? T : col[r_lo - le][lane];
+            got_lo = true;
+        }
+        if (!got_hi && (r_hi < le || r_hi - le < m || n == 0)) {
+            k_hi = r_hi < le || n == 0 ? T : col[r_hi - le][lane];
+            got_hi = true;
+        }
+        if (__ballot(!(got_lo && got_hi)) == 0ull) break;
+        T = m == kMedianCap ? top : 0xFFFFFFFFu;   // a lane with a rank to find has a full column
+        above = true;
+    }
+    const float e_lo = median_value(k_lo), e_hi = median_value(k_hi);
+    const float mid = __double2float_rn(((double)e_lo + (double)e_hi) * 0.5);
+    const float v = n == 0 ? 0.0f : ((n & 1) ? e_lo : mid);
+    if (live) {
+        const size_t o = (size_t)y * (size_t)a.Wc + (size_t)x;
+        a.out[o] = mosaic_store_value(v, PIX());
+        if (a.count) a.count[o] = n;
     }
 }
 

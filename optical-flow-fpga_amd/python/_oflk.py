@@ -178,6 +178,10 @@ SIGNATURES = {
     "oflk_mosaic_accumulate_exposure": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_vp, _vp, _vp] + [ctypes.c_int] * 5 + [_vp, ctypes.c_size_t, _vp]),
     "oflk_mosaic_composite_exposure_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 3 + [_f64p, _vp, _f64p] + [ctypes.c_int] * 5 + [_f32p, _i32p]),
     "oflk_mosaic_composite_exposure_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [_f64p, _vp, _f64p] + [ctypes.c_int] * 5 + [_vp, _i32p]),
+    "oflk_mosaic_median_capacity": (ctypes.c_int, []),
+    "oflk_mosaic_median": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_vp, _vp, _vp] + [ctypes.c_int] * 4 + [_vp, _vp, _vp]),
+    "oflk_mosaic_median_host": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 3 + [_f64p, _vp, _f64p] + [ctypes.c_int] * 4 + [_f32p, _i32p]),
+    "oflk_mosaic_median_host_u8": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3 + [_f64p, _vp, _f64p] + [ctypes.c_int] * 4 + [_vp, _i32p]),
     "oflk_exposure_chain_host": (ctypes.c_int, [_f32p, _i32p, ctypes.c_int, ctypes.c_int, _f64p]),
     "oflk_align_workspace": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_size_t)]),
     "oflk_align_refine": (ctypes.c_int, [_vp, _vp, _I, _I] + _ALIGN + _ALIGN_D_IO + [_vp]),
@@ -1238,6 +1242,61 @@ def mosaic_composite_host(frames: np.ndarray, maps: np.ndarray, skip: Optional[n
     src, fn = pixels(frames, "oflk_mosaic_composite_host" if exposure is None else "oflk_mosaic_composite_exposure_host")
     check(fn(src, F, H, W, _f64(maps), None if skip is None else skip.ctypes.data, *(() if exposure is None else (_f64(exposure),)),
              int(x0), int(y0), int(Hc), int(Wc), int(blend), pix(out), None if cnt is None else cnt.ctypes.data_as(_i32p)))
+    return out, cnt
+
+
+def check_mosaic_canvas(canvas_shape, origin):
+    """canvas_shape and origin of mosaic_composite and mosaic_median as (Hc, Wc, x0, y0); ValueError otherwise"""
+    if len(canvas_shape) != 2 or int(canvas_shape[0]) < 1 or int(canvas_shape[1]) < 1:
+        raise ValueError(f"canvas_shape must be (Hc, Wc) with Hc, Wc >= 1, got {canvas_shape!r}")
+    Hc, Wc = int(canvas_shape[0]), int(canvas_shape[1])
+    if Hc * Wc >= 2 ** 30:
+        raise ValueError(f"a canvas of 2^30 pixels or more is not supported, got {Hc} x {Wc}")
+    if len(origin) != 2 or any(isinstance(v, bool) or int(v) != v or abs(int(v)) >= 2 ** 31 for v in origin):
+        raise ValueError(f"origin must be two integers (x0, y0), got {origin!r}")
+    return Hc, Wc, int(origin[0]), int(origin[1])
+
+
+def check_mosaic_flags(F: int, skip, exposure):
+    """skip as contiguous (F,) uint8 flags or None, exposure as contiguous (F, 2) float64 or None; ValueError otherwise"""
+    sk = None
+    if skip is not None:
+        sk = np.asarray(skip)
+        if sk.shape != (F,):
+            raise ValueError(f"skip must have shape {(F,)}, got {sk.shape}")
+        sk = np.ascontiguousarray(sk != 0, np.uint8)
+    ex = None
+    if exposure is not None:
+        ex = np.ascontiguousarray(exposure, np.float64)
+        if ex.shape != (F, 2):
+            raise ValueError(f"exposure must have shape {(F, 2)}, got {ex.shape}")
+    return sk, ex
+
+
+def mosaic_median_capacity() -> int:
+    """oflk_mosaic_median_capacity (host only): the samples a pixel of the temporal median keeps on chip"""
+    return int(lib().oflk_mosaic_median_capacity())
+
+
+def mosaic_median(d_frames: int, F: int, H: int, W: int, d_map: int, d_skip: int, d_exposure: int, x0: int, y0: int, Hc: int, Wc: int,
+                  d_out: int, d_count: int = 0, u8: bool = False, stream: int = 0) -> None:
+    """oflk_mosaic_median on device pointers: the temporal median of d_frames [F][H][W] (float32, or uint8 with u8) under d_map
+    [F][9] float64 (d_skip [F] uint8 or 0, d_exposure [F][2] float64 or 0) -> d_out [Hc][Wc] of the frames' type, d_count
+    [Hc][Wc] int32 or 0; asynchronous."""
+    check(lib().oflk_mosaic_median(d_frames or None, int(bool(u8)), int(F), int(H), int(W), d_map or None, d_skip or None,
+                                   d_exposure or None, int(x0), int(y0), int(Hc), int(Wc), d_out or None, d_count or None, stream))
+
+
+def mosaic_median_host(frames: np.ndarray, maps: np.ndarray, skip: Optional[np.ndarray], exposure: Optional[np.ndarray], x0: int, y0: int,
+                       Hc: int, Wc: int, count: bool = False):
+    """oflk_mosaic_median_host[_u8]: contiguous (F, H, W) float32 or uint8 frames, (F, 9) float64 maps, optional (F,) uint8 skip
+    flags and optional (F, 2) float64 exposure in; the (Hc, Wc) median and, when asked for, the int32 count (else None) out"""
+    F, H, W = frames.shape
+    out = np.empty((Hc, Wc), frames.dtype)
+    cnt = np.empty((Hc, Wc), np.int32) if count else None
+    src, fn = pixels(frames, "oflk_mosaic_median_host")
+    check(fn(src, F, H, W, _f64(maps), None if skip is None else skip.ctypes.data, None if exposure is None else _f64(exposure),
+             int(x0), int(y0), int(Hc), int(Wc), pix(out), None if cnt is None else cnt.ctypes.data_as(_i32p)))
     return out, cnt
 
 

@@ -531,27 +531,39 @@ def mosaic_composite(frames, maps, canvas_shape, origin=(0, 0), skip=None, blend
     if H < 2 or W < 2:
         raise ValueError(f"frames must be at least 2 x 2, got {H} x {W}")
     code = _oflk.check_mosaic_blend(blend)
-    if len(canvas_shape) != 2 or int(canvas_shape[0]) < 1 or int(canvas_shape[1]) < 1:
-        raise ValueError(f"canvas_shape must be (Hc, Wc) with Hc, Wc >= 1, got {canvas_shape!r}")
-    Hc, Wc = int(canvas_shape[0]), int(canvas_shape[1])
-    if Hc * Wc >= 2 ** 30:
-        raise ValueError(f"a canvas of 2^30 pixels or more is not supported, got {Hc} x {Wc}")
-    if len(origin) != 2 or any(isinstance(v, bool) or int(v) != v or abs(int(v)) >= 2 ** 31 for v in origin):
-        raise ValueError(f"origin must be two integers (x0, y0), got {origin!r}")
+    Hc, Wc, x0, y0 = _oflk.check_mosaic_canvas(canvas_shape, origin)
     m = _maps(maps, F, 9)
-    sk = None
-    if skip is not None:
-        sk = np.asarray(skip)
-        if sk.shape != (F,):
-            raise ValueError(f"skip must have shape {(F,)}, got {sk.shape}")
-        sk = np.ascontiguousarray(sk != 0, np.uint8)
-    ex = None
-    if exposure is not None:
-        ex = np.ascontiguousarray(exposure, np.float64)
-        if ex.shape != (F, 2):
-            raise ValueError(f"exposure must have shape {(F, 2)}, got {ex.shape}")
-    out, cnt = _oflk.mosaic_composite_host(arr, m, sk, int(origin[0]), int(origin[1]), Hc, Wc, code, bool(return_count),
-                                           ex)
+    sk, ex = _oflk.check_mosaic_flags(F, skip, exposure)
+    out, cnt = _oflk.mosaic_composite_host(arr, m, sk, x0, y0, Hc, Wc, code, bool(return_count), ex)
+    return (out, cnt) if return_count else out
+
+
+def mosaic_median(frames, maps, canvas_shape, origin=(0, 0), skip=None, return_count: bool = False, exposure=None):
+    """The temporal median of frames on one canvas, on the GPU: the blend that drops what moves through.  Canvas pixels, maps,
+    skip, exposure and the count are mosaic_composite's; a pixel's value is the median of the bilinear samples of the frames
+    that cover it (each taken to exposure[f] first when that is given), the mean of the two middle ones when their number is
+    even, and 0 where no frame reaches.  An object that crosses the shot is in a minority of a pixel's samples wherever the
+    background is seen more often than not, and leaves no trace there; "mean" and "feather" paint it in.  The result does not
+    depend on the order of the frames.  frames: (F, H, W) float32 or uint8 (uint8 out: rounded half to even and saturated to
+    [0, 255]).  All F frames are on the device at once, which is the price of a median; the statement is in include/oflk.h.
+
+    A 4-D uint8 array (F, H, W, C), C = 3 or 4, is a batch of interleaved colour frames: every channel's plane goes through
+    the grey call under the same maps and the canvases are stacked to (Hc, Wc, C).  This is a per-channel median, not a vector
+    median: a pixel's three channels may come from different frames."""
+    if _oflk.is_packed(frames):
+        arr = _oflk.as_packed(frames)
+        planes = [mosaic_median(np.ascontiguousarray(arr[..., c]), maps, canvas_shape, origin, skip, True, exposure)
+                  for c in range(arr.shape[-1])]
+        canvas = np.stack([p[0] for p in planes], axis=-1)
+        return (canvas, planes[0][1]) if return_count else canvas
+    arr, _ = _oflk.as_frames(frames)
+    F, H, W = arr.shape
+    if H < 2 or W < 2:
+        raise ValueError(f"frames must be at least 2 x 2, got {H} x {W}")
+    Hc, Wc, x0, y0 = _oflk.check_mosaic_canvas(canvas_shape, origin)
+    m = _maps(maps, F, 9)
+    sk, ex = _oflk.check_mosaic_flags(F, skip, exposure)
+    out, cnt = _oflk.mosaic_median_host(arr, m, sk, ex, x0, y0, Hc, Wc, bool(return_count))
     return (out, cnt) if return_count else out
 
 

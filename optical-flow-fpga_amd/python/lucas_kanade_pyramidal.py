@@ -32,7 +32,7 @@ import numpy.typing as npt
 import _oflk
 from lucas_kanade_core import (_maps, _pair, Alignment, Homography, MosaicChain, Motion, PhotometricAlignment, Trajectory,  # noqa: F401
                                estimate_homography, estimate_motion, exposure_chain, lucas_kanade_single_scale, mosaic_chain,
-                               mosaic_composite, refine_alignment, alignment_weights,
+                               mosaic_composite, mosaic_median, refine_alignment, alignment_weights,
                                rgb_to_luma, sequence_refine_alignment, stabilize_trajectory, tracks_homography, tracks_motion, warp_affine,
                                warp_perspective)
 
@@ -818,6 +818,59 @@ def lucas_kanade_pyramidal_sequence_mosaic(frames, max_corners: int = 1000, dete
     x0, y0, Wc, Hc = (int(v) for v in canvas)
     return Mosaic(out[:Hc * Wc].reshape(Hc, Wc).copy(), cnt[:Hc * Wc].reshape(Hc, Wc).copy(), (x0, y0), to.reshape(T, 3, 3),
                   held.astype(bool), drop.astype(bool), mod.reshape(T - 1, 3, 3), counts[:, 2].copy())
+
+
+def lucas_kanade_pyramidal_sequence_mosaic_median(frames, max_corners: int = 1000, detect_every: int = 4, hypotheses: int = 256,
+                                                  threshold: float = 1.0, seed: int = 0, quality_level: float = 0.01,
+                                                  min_distance: float = 10.0, num_levels: int = 3, window_size: int = 5,
+                                                  num_iterations: int = 3, alpha: float = 0.01, beta: float = 0.5,
+                                                  max_residual: float = 4.0, anchor: int = 0, extent=None, max_pixels=None,
+                                                  refine_iterations: int = 0, refine_levels: int = 3, order: str = "rgb",
+                                                  refine_photometric: bool = False, refine_robust_delta=None):
+    """lucas_kanade_pyramidal_sequence_mosaic with the temporal median for a blend: the clean plate of a panning shot, without
+    the objects that move through it.  Made of the public parts and equal to their chain byte for byte:
+    lucas_kanade_pyramidal_sequence_klt_sparse_replenish, tracks_homography, sequence_refine_alignment when refine_iterations >
+    0, mosaic_chain from frame `anchor`, exposure_chain when refine_photometric, and mosaic_median of every frame that is not
+    dropped.  The parameters are that call's without `blend`; a canvas of more than max_pixels (default 16 H W) pixels raises
+    OflkError.  All frames are on the device at once for the median.  Returns a Mosaic, or a PhotometricMosaic with
+    refine_photometric=True.
+
+    A 4-D uint8 array (T, H, W, C), C = 3 or 4, is interleaved colour video: rgb_to_luma of the frames carries everything but
+    the canvas, and every channel's plane then goes through mosaic_median under the chain fitted on the luma (a per-channel
+    median); .canvas is (Hc, Wc, C)."""
+    refine = _oflk.check_refine(refine_iterations, refine_photometric, refine_robust_delta)
+    _oflk.check_colour_order(order)
+    packed = _oflk.as_packed(frames, "(T, H, W, C)") if _oflk.is_packed(frames) else None
+    arr, _ = _oflk.as_sequence(frames if packed is None else rgb_to_luma(packed, order))
+    T, H, W = arr.shape
+    if H < 2 or W < 2:
+        raise ValueError(f"frames must be at least 2 x 2, got {H} x {W}")
+    # what the parts below refuse, before the first of them runs
+    _oflk.check_fb_params(alpha, beta)
+    _oflk.check_tracking((H, W), num_levels, window_size, num_iterations, alpha, beta, max_residual, max_corners, quality_level,
+                         min_distance, detect_every)
+    _oflk.check_ransac_params(hypotheses, threshold, seed)
+    anchor = _oflk.check_int("anchor", anchor, 0, T - 1)
+    if extent is not None and not (np.isfinite(float(extent)) and float(extent) > 0):
+        raise ValueError(f"extent must be finite and > 0, got {extent!r}")
+    cap = _max_pixels(max_pixels, H, W)
+    rows = lucas_kanade_pyramidal_sequence_klt_sparse_replenish(arr, max_corners, detect_every, quality_level, min_distance, num_levels,
+                                                                window_size, num_iterations, alpha, beta, max_residual)
+    fit = tracks_homography(rows.tracks, rows.visible, rows.born, hypotheses, threshold, seed)
+    model, al = fit.model, None
+    if refine > 0:
+        al = sequence_refine_alignment(arr, fit.model, fit.status, "homography", refine_levels, refine,
+                                       photometric=bool(refine_photometric), robust_delta=refine_robust_delta)
+        model = al.model
+    ch = mosaic_chain(model, fit.status, (H, W), anchor, extent)
+    Hc, Wc = ch.canvas_shape
+    if Hc * Wc > cap:
+        raise _oflk.OflkError(_oflk.OFLK_ERR_UNSUPPORTED,
+                              f"the canvas of {Wc} x {Hc} pixels at {ch.origin} exceeds the capacity of {cap} pixels")
+    ex = exposure_chain(al.gain, al.bias, al.status == 1, anchor) if refine_photometric else None
+    canvas, cnt = mosaic_median(arr if packed is None else packed, ch.from_anchor, (Hc, Wc), ch.origin, ch.dropped, True, ex)
+    m = Mosaic(canvas, cnt, ch.origin, ch.to_anchor, ch.held, ch.dropped, model, fit.status)
+    return PhotometricMosaic(*m, ex) if refine_photometric else m
 
 
 def _max_pixels(max_pixels, H: int, W: int) -> int:

@@ -10,6 +10,9 @@ covers every pixel and the cull can save nothing, which prices it.
 Legs, each in a process of its own under its own time limit (a leg that fails or runs out of time ends the run):
   mean, feather   oflk_mosaic_accumulate (one launch for the F frames, on a state cleared in the same window) and
                   oflk_mosaic_resolve with the count
+  median          oflk_mosaic_median with the count: one launch, no state.  A pixel of the pan is covered by up to 84 frames,
+                  one of the still scene by all 129: both are beyond twice oflk_mosaic_median_capacity(), the still scene
+                  everywhere, so the frames are walked two and three times there
   baseline        what the library offered before: the frames padded to the canvas size (prepared outside the timed window),
                   oflk_warp_perspective with inside over them, the sum and the count over the frames taken with torch
 Events around `--reps` back-to-back repetitions give one window; one JSON line per leg with the median and min - max over
@@ -97,6 +100,11 @@ def leg(args):
 
         def run():
             _oflk.mosaic_resolve(state.data_ptr(), Hc, Wc, out.data_ptr(), count.data_ptr(), True, st)
+    elif args.leg == "median":
+        t_map = torch.from_numpy(maps).to(d)
+
+        def run():
+            _oflk.mosaic_median(frames.data_ptr(), F, H, W, t_map.data_ptr(), 0, 0, x0, y0, Hc, Wc, out.data_ptr(), count.data_ptr(), True, st)
     else:
         blend = _oflk.MOSAIC_BLENDS[args.leg]
         nbytes = _oflk.mosaic_state_bytes(Hc, Wc)
@@ -140,7 +148,7 @@ def main():
     ap.add_argument("--frames", type=int, default=129)
     ap.add_argument("--limit", type=int, default=240, help="seconds a leg may take")
     ap.add_argument("--scene", choices=["pan", "still"])
-    ap.add_argument("--leg", choices=["mean", "feather", "baseline", "resolve"], help="run this one leg in this process")
+    ap.add_argument("--leg", choices=["mean", "feather", "median", "baseline", "resolve"], help="run this one leg in this process")
     ap.add_argument("--extra-columns", type=int, default=0, help="the resolve leg: columns added to the canvas")
     args = ap.parse_args()
     if args.leg:
@@ -149,7 +157,7 @@ def main():
         leg(args)
         return 0
     for sc in ("pan", "still"):
-        for lg in ("mean", "feather", "baseline"):
+        for lg in ("mean", "feather", "median", "baseline"):
             cmd = [sys.executable, __file__, "--scene", sc, "--leg", lg, "--steps", str(args.steps), "--reps", str(args.reps),
                    "--frames", str(args.frames)]
             try:

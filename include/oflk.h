@@ -348,6 +348,50 @@ int oflk_interpolate_frames_nv12_host(const unsigned char *frames, int B, int H,
                                       const float *vf, const float *ub, const float *vb, float alpha, float beta, int refine,
                                       const double *taus, int n, unsigned char *out, unsigned char *status);
 
+/* ---- median filtering of dense flows ------------------------------------------------------------------------------------ */
+/* The statement (tests/flow_median_model.py).  A plane p is [H][W] float32, the window size x size with size in {3, 5, 7, 9}.
+ * Output pixel (y, x) takes the size^2 values p[clamp(y + j, 0, H-1)][clamp(x + i, 0, W-1)], i and j in -size/2 .. size/2 (the
+ * border is replicated), orders them by their bits -- the key of bits b is ~b when the sign bit is set, else b ^ 0x80000000,
+ * which gives -NaN < -inf < negatives < -0 < +0 < positives < +inf < +NaN, the temporal-median mosaic's order -- and returns
+ * the value of rank size^2 / 2.  size^2 is odd, so the result is one of the inputs: nothing is averaged, nothing is rounded,
+ * and equal keys are equal bytes, so the selection method cannot show.  Every plane is filtered on its own: of a flow this is
+ * the component-wise median of u and of v, not a vector median, and it is one pass (a caller may call twice).
+ *
+ * oflk_flow_median_host: in and out are host arrays of P contiguous planes [P][H][W]; synchronous.  A large call goes in
+ * chunks of min(64, 2^27 / (4 H W)) planes (one at least) through one pair of device buffers; planes are independent, so the
+ * result does not depend on the cut.  The device form is oflk_flow_median (below).  Refused before any device call, all
+ * OFLK_ERR_INVALID: NULL in or out, P < 1, a size that is not 3, 5, 7 or 9; then H or W < 1: OFLK_ERR_INVALID, 2^30 pixels or
+ * more or 2^23 rows or columns or more: OFLK_ERR_UNSUPPORTED; then out overlapping in (the filter is not in place):
+ * OFLK_ERR_INVALID.
+ *
+ * The _median sequence forms are oflk_pyramidal_sequence_fb{,_u8}, oflk_interpolate_sequence{,_u8},
+ * oflk_interpolate_sequence_packed and oflk_interpolate_sequence_nv12 with one more setting, flow_median: 0 is that call
+ * itself, byte for byte, with no launch and no buffer added; 3, 5, 7 or 9 filters the four flow arrays of every chunk on the
+ * device, after the flagged pairs are resolved (oflk_last_resolved() is that call's), through one more [C][H][W] buffer.  The
+ * flows that come down from oflk_pyramidal_sequence_fb_median are the filtered ones, and the errors, the masks, the status
+ * bytes and the new frames are computed from them: the call equals the unfiltered call's flows put through
+ * oflk_flow_median_host and then oflk_fb_consistency_host (oflk_interpolate_frames*_host), byte for byte.  The chunks are the
+ * unfiltered call's.  Any other flow_median: OFLK_ERR_INVALID before any device call, beside what the unfiltered call refuses. */
+int oflk_flow_median_host(const float *in, float *out, int P, int H, int W, int size);
+int oflk_pyramidal_sequence_fb_median(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                      float alpha, float beta, int flow_median, float *uf, float *vf, float *ub, float *vb,
+                                      float *err_f, float *err_b, unsigned char *valid_f, unsigned char *valid_b);
+int oflk_pyramidal_sequence_fb_median_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size,
+                                         int iters, float alpha, float beta, int flow_median, float *uf, float *vf, float *ub,
+                                         float *vb, float *err_f, float *err_b, unsigned char *valid_f, unsigned char *valid_b);
+int oflk_interpolate_sequence_median(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                     float alpha, float beta, int refine, const double *taus, int n, int flow_median, float *out,
+                                     unsigned char *status);
+int oflk_interpolate_sequence_median_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                        float alpha, float beta, int refine, const double *taus, int n, int flow_median,
+                                        unsigned char *out, unsigned char *status);
+int oflk_interpolate_sequence_packed_median(const unsigned char *frames, int T, int H, int W, int channels, int order, int levels,
+                                            int window_size, int iters, float alpha, float beta, int refine, const double *taus,
+                                            int n, int flow_median, unsigned char *out, unsigned char *status);
+int oflk_interpolate_sequence_nv12_median(const unsigned char *frames, int T, int H, int W, int siting, int levels,
+                                          int window_size, int iters, float alpha, float beta, int refine, const double *taus,
+                                          int n, int flow_median, unsigned char *out, unsigned char *status);
+
 /* ---- sparse pyramidal LK: points in, points out, no dense flow --------------------------------------------------------- */
 /* The statement (tests/sparse_model.py).  The shape of calcOpticalFlowPyrLK: points in, next points + status + error out,
  * at a cost proportional to N * window^2 * levels * iterations, not to H*W.  Pyramids: build_gaussian_pyramid of each frame,
@@ -1470,6 +1514,14 @@ int oflk_interpolate_frames_packed(const unsigned char *d_frames, int B, int H, 
 int oflk_interpolate_frames_nv12(const unsigned char *d_frames, int B, int H, int W, int siting, const float *d_uf,
                                  const float *d_vf, const float *d_ub, const float *d_vb, float alpha, float beta, int refine,
                                  const double *taus, int n, unsigned char *d_out, unsigned char *d_status, void *stream);
+/* The median of flow planes (the statement at oflk_flow_median_host), device pointers: d_in and d_out are P contiguous planes
+ * [P][H][W] float32.  One launch per 65535 planes: a block is a tile of oflk_flow_median_tile's rows x columns of one plane,
+ * stages it and a halo of size / 2 in LDS as sort keys through clamped addresses (no load leaves the plane) and each lane
+ * selects the middle of its size^2 keys in registers.  No workspace.  Asynchronous, and capturable into a graph.  Refusals:
+ * the list at oflk_flow_median_host. */
+int oflk_flow_median(const float *d_in, float *d_out, int P, int H, int W, int size, void *stream);
+/* the rows and columns of output pixels of one block of oflk_flow_median (host only, no device call); NULL: OFLK_ERR_INVALID */
+int oflk_flow_median_tile(int *tile_h, int *tile_w);
 /* Sparse tracks (statement at oflk_sparse_lk) through the plan's B pairs, device pointers: d_frames [B+1][H][W] float32, or
  * uint8 with u8 != 0, are frames t0 .. t0+B.  Builds the B+1 pyramids once, then one track launch (one wave per query,
  * looping over the pairs).  d_qt, d_qxy, N, t0, d_tracks [B+1][N][2], d_visible [B+1][N] and the use of row 0 as

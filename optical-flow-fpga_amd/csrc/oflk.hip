@@ -14,6 +14,7 @@
 #include "oflk_homography.hpp"
 #include "oflk_stabilize.hpp"
 #include "oflk_mosaic.hpp"
+#include "oflk_flowmedian.hpp"
 #include "oflk_align.hpp"
 #include "oflk_colour.hpp"
 #include "oflk_nv12.hpp"
@@ -2362,11 +2363,42 @@ struct FitConfig { int model, hypotheses; float threshold; unsigned seed; };
 struct TrajWindow { const double *weights; int radius; };               // weights [radius + 1]
 struct KltConfig { PyrWindow pyr; TrackTest test; Selection select; };   // what replenished sparse KLT takes besides its frames
 
+bool is_flow_median_size(int size) { return size == 3 || size == 5 || size == 7 || size == 9; }
+
+int check_flow_median_size(int size)
+{
+    if (!is_flow_median_size(size)) return fail(OFLK_ERR_INVALID, "size must be 3, 5, 7 or 9 (got %d)", size);
+    return OFLK_OK;
+}
+
+// P planes through k_flow_median<size>, cut at the grid's z limit; the arguments are checked
+int flow_median_launch(const float *d_in, float *d_out, size_t P, int H, int W, int size, hipStream_t s)
+{
+    constexpr size_t kMaxZ = 65535;
+    FlowMedianArgs a{};
+    a.H = H; a.W = W;
+    a.tiles_x = (W + kFlowMedianTileW - 1) / kFlowMedianTileW;
+    const unsigned tiles = (unsigned)a.tiles_x * (unsigned)((H + kFlowMedianTileH - 1) / kFlowMedianTileH);   // < 2^24 (check_hw)
+    const size_t plane = (size_t)H * W;
+    for (size_t z0 = 0; z0 < P; z0 += kMaxZ) {
+        a.in = d_in + z0 * plane;
+        a.out = d_out + z0 * plane;
+        const dim3 grid(tiles, 1, (unsigned)std::min(kMaxZ, P - z0));
+        const bool built = with_int<3, 5, 7, 9>(size, [&](auto SIZE) {
+            hipLaunchKernelGGL((k_flow_median<decltype(SIZE)::value>), grid, dim3(256), 0, s, a);
+        });
+        if (!built) return fail(OFLK_ERR_INVALID, "size must be 3, 5, 7 or 9 (got %d)", size);
+        HIP_TRY(hipGetLastError());
+    }
+    return OFLK_OK;
+}
+
 // The frames and the flow configuration of a host sequence call
 struct Seq : PyrWindow {
     const void *frames;   // [T][H][W], uint8 or float32
     bool u8;
     int T, H, W;
+    int flow_median = 0;  // 0, or the window of the median that every flow plane of a chunk goes through (3, 5, 7, 9)
     size_t frame_bytes() const { return (size_t)H * W * (u8 ? 1 : sizeof(float)); }
 };
 
@@ -2378,16 +2410,20 @@ int check_seq(const Seq &seq)
 }
 
 // One chunk of both directions of a sequence on the null stream: the device buffers of C+1 frames and of the four flows
-// of C pairs (chunk_pairs), and what fills them
+// of C pairs (chunk_pairs), and what fills them.  With seq.flow_median one more [C][H][W] buffer: each flow array is filtered
+// into it and the two pointers are exchanged, so d[0..3] are the filtered flows for whatever follows
 struct BidirChunk {
     char *frames = nullptr;   // [C+1][H][W] of the call's pixels
     float *d[4] = {};         // uf, vf, ub, vb: [C][H][W] each
+    float *spare = nullptr;   // [C][H][W] with seq.flow_median, else none
 
     static int check(const Seq &seq)   // what both directions refuse before any device call; t_resolved starts at 0
     {
         t_resolved = 0;
         if (int rc = check_seq(seq)) return rc;
         if (seq.levels < 1) return fail(OFLK_ERR_INVALID, "levels must be in [1,%d] (got %d)", OFLK_MAX_LEVELS, seq.levels);
+        if (seq.flow_median != 0 && !is_flow_median_size(seq.flow_median))
+            return fail(OFLK_ERR_INVALID, "flow_median must be 0, 3, 5, 7 or 9 (got %d)", seq.flow_median);
         return OFLK_OK;
     }
     int alloc(HostCall &call, const Seq &seq, int C)
@@ -2395,6 +2431,7 @@ struct BidirChunk {
         int rc = call.alloc(&frames, (size_t)(C + 1) * seq.frame_bytes());
         for (auto &q : d)
             if (!rc) rc = call.alloc(&q, (size_t)C * seq.H * seq.W);
+        if (!rc) rc = call.alloc(&spare, (size_t)C * seq.H * seq.W, seq.flow_median != 0);
         return rc;
     }
     // pairs b0 .. b0+nb-1: their nb+1 frames go up, one bidirectional plan pass writes d, and the flagged pairs of both
@@ -2419,6 +2456,11 @@ struct BidirChunk {
         int n_res = 0;
         if (seq.iters > 0 && (rc = resolve_uncertain_fb(p, frames, seq.u8, d[0], d[1], d[2], d[3], nullptr, &n_res))) return rc;
         t_resolved += n_res;
+        if (!seq.flow_median) return OFLK_OK;
+        for (auto &q : d) {   // the resolved flows are the ones filtered
+            if ((rc = flow_median_launch(q, spare, (size_t)nb, seq.H, seq.W, seq.flow_median, nullptr))) return rc;
+            std::swap(q, spare);
+        }
         return OFLK_OK;
     }
 };
@@ -2428,9 +2470,10 @@ struct BidirChunk {
 // as the next chunk reuses the buffers.
 template <class PIXELS>
 int run_sequence_fb(const PIXELS *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha, float beta,
-                    float *uf, float *vf, float *ub, float *vb, float *ef, float *eb, unsigned char *qf, unsigned char *qb)
+                    float *uf, float *vf, float *ub, float *vb, float *ef, float *eb, unsigned char *qf, unsigned char *qb,
+                    int flow_median = 0)
 {
-    const Seq seq{{levels, window_size, iters}, frames, sizeof(PIXELS) == 1, T, H, W};
+    const Seq seq{{levels, window_size, iters}, frames, sizeof(PIXELS) == 1, T, H, W, flow_median};
     const bool check = ef || eb || qf || qb;
     int rc = BidirChunk::check(seq);
     if (rc || (check && (rc = check_fb(uf, vf, ub, vb, T - 1, H, W, alpha, beta, ef, eb, qf, qb)))) return rc;
@@ -2510,6 +2553,24 @@ OFLK_API int oflk_pyramidal_sequence_fb_u8(const unsigned char *frames, int T, i
 {
     return run_sequence_fb<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, uf, vf, ub, vb, err_f, err_b,
                                           valid_f, valid_b);
+}
+
+OFLK_API int oflk_pyramidal_sequence_fb_median(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                               float alpha, float beta, int flow_median, float *uf, float *vf, float *ub,
+                                               float *vb, float *err_f, float *err_b, unsigned char *valid_f,
+                                               unsigned char *valid_b)
+{
+    return run_sequence_fb<float>(frames, T, H, W, levels, window_size, iters, alpha, beta, uf, vf, ub, vb, err_f, err_b, valid_f,
+                                  valid_b, flow_median);
+}
+
+OFLK_API int oflk_pyramidal_sequence_fb_median_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size,
+                                                  int iters, float alpha, float beta, int flow_median, float *uf, float *vf,
+                                                  float *ub, float *vb, float *err_f, float *err_b, unsigned char *valid_f,
+                                                  unsigned char *valid_b)
+{
+    return run_sequence_fb<unsigned char>(frames, T, H, W, levels, window_size, iters, alpha, beta, uf, vf, ub, vb, err_f, err_b,
+                                          valid_f, valid_b, flow_median);
 }
 
 // ---- Shi-Tomasi corners ----------------------------------------------------------------------------------------------
@@ -4581,10 +4642,10 @@ int interp_host(const FrameLayout &L, const void *frames, int B, int H, int W, c
 // (the luma of packed frames by luma_launch, the Y planes of NV12 frames by one strided copy) and the interpolation reads
 // the chunk where it lies.
 int run_sequence_interp(const FrameLayout &L, const void *frames, int T, int H, int W, const PyrWindow &pyr, const InterpConfig &cfg,
-                        void *out, unsigned char *status)
+                        void *out, unsigned char *status, int flow_median = 0)
 {
     const bool planar = L.kind == FrameKind::Planar;
-    const Seq seq{pyr, frames, L.pix_bytes == 1, T, H, W};
+    const Seq seq{pyr, frames, L.pix_bytes == 1, T, H, W, flow_median};
     t_resolved = 0;
     int rc = OFLK_OK;
     if (!planar) {
@@ -4714,6 +4775,94 @@ OFLK_API int oflk_interpolate_sequence_nv12(const unsigned char *frames, int T, 
 {
     return run_sequence_interp(FrameLayout::nv12(siting), frames, T, H, W, {levels, window_size, iters},
                                {alpha, beta, refine, taus, n}, out, status);
+}
+
+// the same four with the flows of every chunk median filtered before they are used (flow_median: 0, 3, 5, 7 or 9)
+OFLK_API int oflk_interpolate_sequence_median(const float *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                              float alpha, float beta, int refine, const double *taus, int n, int flow_median,
+                                              float *out, unsigned char *status)
+{
+    return run_sequence_interp(FrameLayout::planar(false), frames, T, H, W, {levels, window_size, iters},
+                               {alpha, beta, refine, taus, n}, out, status, flow_median);
+}
+
+OFLK_API int oflk_interpolate_sequence_median_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size,
+                                                 int iters, float alpha, float beta, int refine, const double *taus, int n,
+                                                 int flow_median, unsigned char *out, unsigned char *status)
+{
+    return run_sequence_interp(FrameLayout::planar(true), frames, T, H, W, {levels, window_size, iters},
+                               {alpha, beta, refine, taus, n}, out, status, flow_median);
+}
+
+OFLK_API int oflk_interpolate_sequence_packed_median(const unsigned char *frames, int T, int H, int W, int channels, int order,
+                                                     int levels, int window_size, int iters, float alpha, float beta, int refine,
+                                                     const double *taus, int n, int flow_median, unsigned char *out,
+                                                     unsigned char *status)
+{
+    return run_sequence_interp(FrameLayout::packed(channels, order), frames, T, H, W, {levels, window_size, iters},
+                               {alpha, beta, refine, taus, n}, out, status, flow_median);
+}
+
+OFLK_API int oflk_interpolate_sequence_nv12_median(const unsigned char *frames, int T, int H, int W, int siting, int levels,
+                                                   int window_size, int iters, float alpha, float beta, int refine,
+                                                   const double *taus, int n, int flow_median, unsigned char *out,
+                                                   unsigned char *status)
+{
+    return run_sequence_interp(FrameLayout::nv12(siting), frames, T, H, W, {levels, window_size, iters},
+                               {alpha, beta, refine, taus, n}, out, status, flow_median);
+}
+
+// =============================================================================
+// median filtering of flow planes (oflk_flowmedian.hpp): the device and the host form
+// =============================================================================
+namespace {
+// what both forms refuse before any device call (every value OFLK_ERR_INVALID, then check_hw's with its codes)
+int check_flow_median(const float *in, const float *out, int P, int H, int W, int size)
+{
+    if (!in || !out) return fail(OFLK_ERR_INVALID, "NULL array argument");
+    if (P < 1) return fail(OFLK_ERR_INVALID, "P must be >= 1 (got %d)", P);
+    if (int rc = check_flow_median_size(size)) return rc;
+    if (int rc = check_hw(in, out, H, W)) return rc;
+    const size_t bytes = (size_t)P * H * W * sizeof(float);
+    if (ranges_overlap(out, bytes, in, bytes)) return fail(OFLK_ERR_INVALID, "the output overlaps the input: the filter is not in place");
+    return OFLK_OK;
+}
+}  // namespace
+
+OFLK_API int oflk_flow_median_tile(int *tile_h, int *tile_w)
+{
+    if (!tile_h || !tile_w) return fail(OFLK_ERR_INVALID, "NULL output");
+    *tile_h = kFlowMedianTileH;
+    *tile_w = kFlowMedianTileW;
+    return OFLK_OK;
+}
+
+OFLK_API int oflk_flow_median(const float *d_in, float *d_out, int P, int H, int W, int size, void *stream)
+{
+    if (int rc = check_flow_median(d_in, d_out, P, H, W, size)) return rc;
+    return flow_median_launch(d_in, d_out, (size_t)P, H, W, size, (hipStream_t)stream);
+}
+
+// Host planes in chunks of sparse_chunk_pairs planes (~128 MB of float32, 64 planes at most) through one pair of device
+// buffers, as the warps' frames go (warp_chunks).  Planes are independent, so the result does not depend on the cut.
+OFLK_API int oflk_flow_median_host(const float *in, float *out, int P, int H, int W, int size)
+{
+    int rc = check_flow_median(in, out, P, H, W, size);
+    if (rc) return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const int C = sparse_chunk_pairs(P, H, W);
+    const size_t plane = (size_t)H * W;
+    float *d_in = nullptr, *d_out = nullptr;
+    if ((rc = call.alloc(&d_in, (size_t)C * plane)) || (rc = call.alloc(&d_out, (size_t)C * plane))) return rc;
+    for (int p0 = 0; p0 < P; p0 += C) {
+        const size_t o = (size_t)p0 * plane, len = (size_t)std::min(C, P - p0) * plane;
+        if ((rc = call.to_device(d_in, in + o, len)) ||
+            (rc = flow_median_launch(d_in, d_out, (size_t)std::min(C, P - p0), H, W, size, nullptr)) ||
+            (rc = call.to_host(out + o, d_out, len)) || (rc = call.sync()))
+            return rc;
+    }
+    return OFLK_OK;
 }
 
 // =============================================================================

@@ -105,6 +105,15 @@ SIGNATURES = {
     "oflk_interpolate_frames_nv12_host": (ctypes.c_int, [_vp] + [_I] * 4 + [_f32p] * 4 + _INTERP + [_vp, _vp]),
     "oflk_interpolate_sequence_packed": (ctypes.c_int, [_vp] + [_I] * 8 + _INTERP + [_vp, _vp]),
     "oflk_interpolate_sequence_nv12": (ctypes.c_int, [_vp] + [_I] * 7 + _INTERP + [_vp, _vp]),
+    "oflk_flow_median": (ctypes.c_int, [_vp, _vp] + [_I] * 4 + [_vp]),
+    "oflk_flow_median_host": (ctypes.c_int, [_f32p, _f32p] + [_I] * 4),
+    "oflk_flow_median_tile": (ctypes.c_int, [_i32p, _i32p]),
+    "oflk_pyramidal_sequence_fb_median": (ctypes.c_int, [_f32p] + [_I] * 6 + [_F] * 2 + [_I] + [_f32p] * 6 + [_vp, _vp]),
+    "oflk_pyramidal_sequence_fb_median_u8": (ctypes.c_int, [_vp] + [_I] * 6 + [_F] * 2 + [_I] + [_f32p] * 6 + [_vp, _vp]),
+    "oflk_interpolate_sequence_median": (ctypes.c_int, [_f32p] + [_I] * 6 + _INTERP + [_I, _f32p, _vp]),
+    "oflk_interpolate_sequence_median_u8": (ctypes.c_int, [_vp] + [_I] * 6 + _INTERP + [_I, _vp, _vp]),
+    "oflk_interpolate_sequence_packed_median": (ctypes.c_int, [_vp] + [_I] * 8 + _INTERP + [_I, _vp, _vp]),
+    "oflk_interpolate_sequence_nv12_median": (ctypes.c_int, [_vp] + [_I] * 7 + _INTERP + [_I, _vp, _vp]),
     "oflk_track_points": (ctypes.c_int, [_vp] * 4 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, _vp]),
     "oflk_track_points_host": (ctypes.c_int, [_f32p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
     "oflk_pyramidal_sequence_tracks": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 2 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
@@ -607,17 +616,56 @@ def interpolate_host(layout: "FrameLayout", arr: np.ndarray, H: int, W: int, flo
 
 
 def interpolate_sequence_host(layout: "FrameLayout", arr: np.ndarray, H: int, W: int, levels: int, window_size: int, iters: int,
-                              cfg: Interp):
+                              cfg: Interp, flow_median: int = 0):
     """oflk_interpolate_sequence[_u8] (the default layout) or oflk_interpolate_sequence{_packed,_nv12} on a contiguous array
-    of T frames of the layout: (new (T-1, n) + the frame's shape, status (T-1, n, H, W))"""
+    of T frames of the layout: (new (T-1, n) + the frame's shape, status (T-1, n, H, W)).  flow_median (checked: 0, 3, 5, 7 or
+    9) other than 0: the _median form of that call"""
     T, n = arr.shape[0], len(cfg.taus)
     new, st = np.empty((T - 1, n) + arr.shape[1:], arr.dtype), np.empty((T - 1, n, H, W), np.uint8)
+    median = "_median" if flow_median else ""
     if layout.suffix:
-        src, fn = arr.ctypes.data, getattr(lib(), "oflk_interpolate_sequence" + layout.suffix)
+        src, fn = arr.ctypes.data, getattr(lib(), "oflk_interpolate_sequence" + layout.suffix + median)
     else:
-        src, fn = pixels(arr, "oflk_interpolate_sequence")
-    check(fn(src, T, H, W, *layout.args, int(levels), int(window_size), int(iters), *cfg.args(), pix(new), st.ctypes.data))
+        src, fn = pixels(arr, "oflk_interpolate_sequence" + median)
+    check(fn(src, T, H, W, *layout.args, int(levels), int(window_size), int(iters), *cfg.args(), *((flow_median,) if flow_median else ()),
+             pix(new), st.ctypes.data))
     return new, st
+
+
+FLOW_MEDIAN_SIZES = (3, 5, 7, 9)
+
+
+def check_flow_median(flow_median) -> int:
+    """the flow_median setting of the sequence calls as an int: 0 (off) or a window of FLOW_MEDIAN_SIZES; ValueError otherwise"""
+    if isinstance(flow_median, bool) or not isinstance(flow_median, (int, np.integer)) or int(flow_median) not in (0,) + FLOW_MEDIAN_SIZES:
+        raise ValueError(f"flow_median must be 0, 3, 5, 7 or 9, got {flow_median!r}")
+    return int(flow_median)
+
+
+def flow_median_tile() -> Tuple[int, int]:
+    """oflk_flow_median_tile (host only): the (rows, columns) of output pixels of one block of oflk_flow_median"""
+    th, tw = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().oflk_flow_median_tile(ctypes.byref(th), ctypes.byref(tw)))
+    return th.value, tw.value
+
+
+def flow_median(d_in: int, d_out: int, P: int, H: int, W: int, size: int = 5, stream: int = 0) -> None:
+    """oflk_flow_median on device pointers: the size x size median of each of the P planes d_in [P][H][W] float32 into d_out
+    (not d_in); asynchronous."""
+    check(lib().oflk_flow_median(d_in or None, d_out or None, int(P), int(H), int(W), int(size), stream))
+
+
+def flow_median_host(planes: np.ndarray, size: int = 5) -> np.ndarray:
+    """oflk_flow_median_host on a float32 array (..., H, W): every plane's size x size median, the same shape"""
+    if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or int(size) not in FLOW_MEDIAN_SIZES:
+        raise ValueError(f"size must be 3, 5, 7 or 9, got {size!r}")
+    a = np.ascontiguousarray(planes, np.float32)
+    if a.ndim < 2 or a.size == 0:
+        raise ValueError(f"expected a non-empty (..., H, W) array of flow planes, got shape {a.shape}")
+    H, W = a.shape[-2:]
+    out = np.empty_like(a)
+    check(lib().oflk_flow_median_host(ptr(a), ptr(out), a.size // (H * W), H, W, int(size)))
+    return out
 
 
 def as_queries(queries, T: int) -> Tuple[Optional[np.ndarray], np.ndarray]:

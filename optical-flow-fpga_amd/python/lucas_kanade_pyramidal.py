@@ -222,7 +222,7 @@ class SequenceFB(NamedTuple):
 
 
 def lucas_kanade_pyramidal_sequence_fb(frames, num_levels: int = 3, window_size: int = 5, num_iterations: int = 3,
-                                       alpha: float = 0.01, beta: float = 0.5) -> SequenceFB:
+                                       alpha: float = 0.01, beta: float = 0.5, flow_median: int = 0) -> SequenceFB:
     """Forward and backward flows of every consecutive pair of a frame sequence, and their consistency.
 
     frames: a (T, H, W) array or a sequence of T 2-D arrays, T >= 2 (all uint8: the uint8 path).  u_fwd / v_fwd equal
@@ -230,16 +230,27 @@ def lucas_kanade_pyramidal_sequence_fb(frames, num_levels: int = 3, window_size:
     forward vector is valid when its target lies inside frame t+1 and |F + G(x + F)|^2 <= alpha (|F|^2 + |G(x + F)|^2) +
     beta (Sundaram, Brox & Keutzer 2010; G(x + F) is warp_image's bilinear sample, 0 outside the frame); the backward test
     is the same with F and G exchanged.  Each frame is uploaded once and its pyramid built once for both directions.
+    flow_median = 3, 5, 7 or 9: the four flows go through median_filter_flow of that size on the device before the test; the
+    filtered flows are the ones returned and tested.
     """
     a, b = _oflk.check_fb_params(alpha, beta)
+    k = _oflk.check_flow_median(flow_median)
     arr, _ = _oflk.as_sequence(frames)
     T, H, W = arr.shape
     out = [np.empty((T - 1, H, W), np.float32) for _ in range(6)]
     valid = [np.empty((T - 1, H, W), np.uint8) for _ in range(2)]
-    src, fn = _oflk.pixels(arr, "oflk_pyramidal_sequence_fb")
-    _oflk.check(fn(src, T, H, W, int(num_levels), int(window_size), int(num_iterations), a, b,
+    src, fn = _oflk.pixels(arr, "oflk_pyramidal_sequence_fb" + ("_median" if k else ""))
+    _oflk.check(fn(src, T, H, W, int(num_levels), int(window_size), int(num_iterations), a, b, *((k,) if k else ()),
                    *(_oflk.ptr(o) for o in out), valid[0].ctypes.data, valid[1].ctypes.data))
     return SequenceFB(*out[:4], out[4], out[5], valid[0].astype(bool), valid[1].astype(bool))
+
+
+def median_filter_flow(flow, size: int = 5):
+    """The size x size median (size 3, 5, 7 or 9) of every plane of a float32 array (..., H, W), the same shape: each output
+    value is the middle one of the window's size^2 values, the border replicated, in the order of the values' bits (-NaN <
+    -inf < ... < -0 < +0 < ... < +inf < +NaN), so it is one of the inputs, bit for bit.  Of a flow this is the component-wise
+    median of u and of v: the standard regulariser of a local flow method."""
+    return _oflk.flow_median_host(flow, size)
 
 
 class SequenceTracks(NamedTuple):
@@ -332,8 +343,8 @@ class SequenceInterpolated(NamedTuple):
     status: np.ndarray   # (T-1, n, H, W) uint8: bit 0 frame t's sample passed, bit 1 frame t+1's
 
 
-def _sequence_interpolate(layout, arr, H, W, num_levels, window_size, num_iterations, cfg) -> SequenceInterpolated:
-    new, status = _oflk.interpolate_sequence_host(layout, arr, H, W, num_levels, window_size, num_iterations, cfg)
+def _sequence_interpolate(layout, arr, H, W, num_levels, window_size, num_iterations, cfg, flow_median=0) -> SequenceInterpolated:
+    new, status = _oflk.interpolate_sequence_host(layout, arr, H, W, num_levels, window_size, num_iterations, cfg, flow_median)
     T, n = arr.shape[0], len(cfg.taus)
     both = np.empty((T - 1, n + 1) + arr.shape[1:], arr.dtype)   # frame t, then its n new frames
     both[:, 0], both[:, 1:] = arr[:-1], new
@@ -342,7 +353,7 @@ def _sequence_interpolate(layout, arr, H, W, num_levels, window_size, num_iterat
 
 def lucas_kanade_pyramidal_sequence_interpolate(frames, factor: int = 2, taus=None, num_levels: int = 3, window_size: int = 5,
                                                 num_iterations: int = 3, alpha: float = 0.01, beta: float = 0.5,
-                                                refine: int = 2, order: str = "rgb") -> SequenceInterpolated:
+                                                refine: int = 2, order: str = "rgb", flow_median: int = 0) -> SequenceInterpolated:
     """Frame-rate conversion: frames in, the in-between frames of every consecutive pair out.
 
     factor=k inserts the k-1 frames at times j / k, j = 1 .. k-1 (formed in float64); explicit taus (ascending for `frames`
@@ -350,20 +361,24 @@ def lucas_kanade_pyramidal_sequence_interpolate(frames, factor: int = 2, taus=No
     interpolate_frames run on the device: only the new frames and their status come back.
     A 4-D uint8 array (T, H, W, C), C = 3 or 4, is interleaved colour: the flows are tracked on its luma (rgb_to_luma, `order`
     "rgb" or "bgr"), formed on the device, and every channel is interpolated on them.
+    flow_median = 3, 5, 7 or 9: the flows go through median_filter_flow of that size, on the device, before they are used.
     """
     cfg = _oflk.check_interp(alpha, beta, refine, taus, factor)
+    k = _oflk.check_flow_median(flow_median)
     layout, arr, H, W = _interp_layout(frames, order, "(T, H, W, C)")
-    return _sequence_interpolate(layout, arr, H, W, num_levels, window_size, num_iterations, cfg)
+    return _sequence_interpolate(layout, arr, H, W, num_levels, window_size, num_iterations, cfg, k)
 
 
 def lucas_kanade_pyramidal_sequence_interpolate_nv12(video, factor: int = 2, taus=None, num_levels: int = 3, window_size: int = 5,
                                                      num_iterations: int = 3, alpha: float = 0.01, beta: float = 0.5,
-                                                     refine: int = 2, siting: str = "left") -> SequenceInterpolated:
+                                                     refine: int = 2, siting: str = "left",
+                                                     flow_median: int = 0) -> SequenceInterpolated:
     """lucas_kanade_pyramidal_sequence_interpolate for NV12 video (T, 3H/2, W) uint8 (nv12_from_planes): the flows are tracked
     on the Y planes where they lie, and both planes of the new frames come from interpolate_frames_nv12's kernel."""
     cfg = _oflk.check_interp(alpha, beta, refine, taus, factor)
+    k = _oflk.check_flow_median(flow_median)
     layout, arr, H, W = _interp_nv12(video, siting, "(T, 3H/2, W)")
-    return _sequence_interpolate(layout, arr, H, W, num_levels, window_size, num_iterations, cfg)
+    return _sequence_interpolate(layout, arr, H, W, num_levels, window_size, num_iterations, cfg, k)
 
 
 class SequenceKLT(NamedTuple):

@@ -392,6 +392,62 @@ int oflk_interpolate_sequence_nv12_median(const unsigned char *frames, int T, in
                                           int window_size, int iters, float alpha, float beta, int refine, const double *taus,
                                           int n, int flow_median, unsigned char *out, unsigned char *status);
 
+/* ---- motion-compensated temporal denoising on the dense flows ----------------------------------------------------------- */
+/* Frames in, the same frames out with their noise averaged along the motion: the statement (tests/denoise_model.py).  Frames
+ * are [T][H][W], float32 or uint8.  F_s = (uf[s], vf[s]) is the flow from frame s to frame s+1 and G_s = (ub[s], vb[s]) the
+ * flow from frame s+1 to frame s, taken as they are.  sample and inside are the interpolation's (above): a point that is not
+ * inside samples as 0 and reads no tap, so a flow value never becomes an address.  R = radius is in [1,
+ * OFLK_DENOISE_MAX_RADIUS]; h2 = f32(strength) * f32(strength).  Every float32 and float64 operation is rounded on its own.
+ *   for output frame t, pixel (x, y):
+ *     c = f32(frame[t][y][x]);  num = c;  den = 1.0f;  count = 0
+ *     two chains, backward (sgn = -1) and forward (sgn = +1), each: (px, py) = (f64(x), f64(y)), alive
+ *     for k = 1 .. R:   for sgn in (-1, +1), in this order:
+ *       s' = t + sgn*k;  the chain has ended, or s' < 0, or s' > T-1: nothing
+ *       forward:  (A, B) = (F_{s'-1}, G_{s'-1});   backward: (A, B) = (G_{s'}, F_{s'})
+ *       us = sample(A.u, px, py); vs = sample(A.v, px, py)
+ *       qx = px + f64(us); qy = py + f64(vs)
+ *       bu = sample(B.u, qx, qy); bv = sample(B.v, qx, qy)
+ *       eu = us + bu; ev = vs + bv; e2 = eu*eu + ev*ev; m2 = (us*us + vs*vs) + (bu*bu + bv*bv)
+ *       ok = inside(qx, qy) and e2 <= f32(alpha)*m2 + f32(beta)
+ *       not ok: the chain ends (no sample from this frame or any beyond it on this side)
+ *       ok: (px, py) = (qx, qy);  v = sample(frame[s'], qx, qy);  d = v - c;  w = 1.0f - (d*d) / h2
+ *           if w > 0:  num = num + w*v;  den = den + w;  count += 1        (a NaN w is not > 0)
+ *     out = num / den     (float32 division, correctly rounded)
+ *     uint8 frames: out clamped to [0, 255], then (unsigned char) rintf, half to even
+ * This is the interpolation's side test with the point carried from frame to frame.  The weight has compact support: a
+ * neighbour that differs from the pixel by `strength` grey levels or more contributes nothing, which keeps a wrong vector or
+ * an uncovered background from ghosting; 3 x the noise's sigma is the suggested strength.  A non-finite pixel is a value like
+ * any other: it reaches out as the centre c, and as a neighbour its w is not > 0 and it is skipped.  count is the number of
+ * neighbours that entered the average, 2 R at most.  These are grey planes; the weight is temporal only (no patch and no
+ * spatial term), and the caller gives strength (no noise estimate).
+ *
+ * oflk_denoise_frames_host{,_u8}: frames [B+1][H][W] and the four flows [B][H][W] in, out [B+1][H][W] of the frames' type and
+ * count [B+1][H][W] uint8 (may be NULL); host arrays, synchronous, staged like oflk_interpolate_frames_host.  One lane per
+ * output pixel of one output frame, the frames along the grid's z, cut at 65535.
+ * oflk_denoise_sequence{,_u8}: T frames in, out and count [T][H][W].  It runs oflk_pyramidal_sequence_fb_median's chunk loop
+ * on its chunks (flow_median 0, 3, 5, 7 or 9; the bidirectional plan pass, flagged pairs of both directions resolved,
+ * oflk_last_resolved() counts them, oflk_set_host_arithmetic applies to the flows): every pair's flows are computed exactly
+ * once.  The flows of the last 2 R pairs and their frames stay on the device from chunk to chunk; a frame is emitted once the R
+ * pairs ahead of it exist, the rest after the last chunk, and the result does not depend on the cut.  It equals
+ * oflk_pyramidal_sequence_fb_median{,_u8} on the frames followed by oflk_denoise_frames_host{,_u8} on those flows, byte for
+ * byte; only out and count come down, no flow leaves the device.
+ * Refused before any device call: by the sequence forms whatever oflk_pyramidal_sequence_fb_median refuses, with its codes;
+ * by the host forms NULL flows, NULL frames, H or W < 1, B < 1: OFLK_ERR_INVALID, and 2^30 pixels or more or 2^23 rows or
+ * columns or more: OFLK_ERR_UNSUPPORTED; then by all, OFLK_ERR_INVALID: radius outside [1, OFLK_DENOISE_MAX_RADIUS], strength
+ * not finite or not > 0, alpha or beta negative or not finite, NULL out, out overlapping the frames. */
+#define OFLK_DENOISE_MAX_RADIUS 4
+int oflk_denoise_frames_host(const float *frames, int B, int H, int W, const float *uf, const float *vf, const float *ub,
+                             const float *vb, float alpha, float beta, int radius, float strength, float *out,
+                             unsigned char *count);
+int oflk_denoise_frames_host_u8(const unsigned char *frames, int B, int H, int W, const float *uf, const float *vf,
+                                const float *ub, const float *vb, float alpha, float beta, int radius, float strength,
+                                unsigned char *out, unsigned char *count);
+int oflk_denoise_sequence(const float *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
+                          float beta, int flow_median, int radius, float strength, float *out, unsigned char *count);
+int oflk_denoise_sequence_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size, int iters,
+                             float alpha, float beta, int flow_median, int radius, float strength, unsigned char *out,
+                             unsigned char *count);
+
 /* ---- sparse pyramidal LK: points in, points out, no dense flow --------------------------------------------------------- */
 /* The statement (tests/sparse_model.py).  The shape of calcOpticalFlowPyrLK: points in, next points + status + error out,
  * at a cost proportional to N * window^2 * levels * iterations, not to H*W.  Pyramids: build_gaussian_pyramid of each frame,

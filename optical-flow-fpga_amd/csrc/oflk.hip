@@ -19,6 +19,7 @@
 #include "oflk_colour.hpp"
 #include "oflk_nv12.hpp"
 #include "oflk_interp.hpp"
+#include "oflk_denoise.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -4810,6 +4811,177 @@ OFLK_API int oflk_interpolate_sequence_nv12_median(const unsigned char *frames, 
 {
     return run_sequence_interp(FrameLayout::nv12(siting), frames, T, H, W, {levels, window_size, iters},
                                {alpha, beta, refine, taus, n}, out, status, flow_median);
+}
+
+// =============================================================================
+// motion-compensated temporal denoising on the dense flows (oflk_denoise.hpp): the host and the sequence forms
+// =============================================================================
+namespace {
+// the test's parameters, the reach in frames and the weight's cutoff of a denoising call
+struct DenoiseConfig { float alpha, beta; int radius; float strength; };
+
+// what every form refuses of its settings and of its output (every value OFLK_ERR_INVALID); F frames of frame_bytes each
+int check_denoise(const DenoiseConfig &cfg, const void *frames, int F, size_t frame_bytes, const void *out)
+{
+    if (cfg.radius < 1 || cfg.radius > OFLK_DENOISE_MAX_RADIUS)
+        return fail(OFLK_ERR_INVALID, "radius must be in [1, %d] (got %d)", OFLK_DENOISE_MAX_RADIUS, cfg.radius);
+    if (!(std::isfinite(cfg.strength) && cfg.strength > 0.0f))
+        return fail(OFLK_ERR_INVALID, "strength must be finite and > 0 (got %g)", (double)cfg.strength);
+    if (int rc = check_alpha_beta(cfg.alpha, cfg.beta)) return rc;
+    if (!out) return fail(OFLK_ERR_INVALID, "NULL output");
+    if (ranges_overlap(out, (size_t)F * frame_bytes, frames, (size_t)F * frame_bytes))
+        return fail(OFLK_ERR_INVALID, "the output overlaps the frames");
+    return OFLK_OK;
+}
+
+// The device arrays a launch reads: rings of fcap frames and of pcap pairs' flows (oflk_denoise.hpp: frame s in slot
+// s % fcap, pair s in slot s % pcap)
+struct DenoiseRings {
+    const void *frames;
+    InterpFlows fl;
+    int fcap, pcap;
+};
+
+// Output frames t0 .. t0+n-1 of a sequence of T frames into out [n][H][W] (and count), cut at the grid's z limit; the
+// rings hold every frame and pair within cfg.radius of those frames.  The arguments are checked.
+int denoise_launch(bool u8, const DenoiseRings &r, int T, int t0, int n, int H, int W, const DenoiseConfig &cfg, void *out,
+                   unsigned char *count, hipStream_t s)
+{
+    constexpr int kMaxZ = 65535;
+    DenoiseArgs a{};
+    a.frames = r.frames;
+    a.uf = r.fl.uf; a.vf = r.fl.vf; a.ub = r.fl.ub; a.vb = r.fl.vb;
+    a.H = H; a.W = W; a.T = T;
+    a.fcap = r.fcap; a.pcap = r.pcap;
+    a.radius = cfg.radius;
+    a.alpha = cfg.alpha; a.beta = cfg.beta;
+    a.h2 = cfg.strength * cfg.strength;
+    const size_t plane = (size_t)H * W, fb = plane * (u8 ? 1 : sizeof(float));
+    for (int z0 = 0; z0 < n; z0 += kMaxZ) {
+        a.t0 = t0 + z0;
+        a.out = static_cast<char *>(out) + (size_t)z0 * fb;
+        a.count = count ? count + (size_t)z0 * plane : nullptr;
+        const int nz = std::min(kMaxZ, n - z0);
+        with_pix(u8, [&](auto PIX) {
+            with_bool(count != nullptr, [&](auto COUNT) {
+                with_bool(W == 1, [&](auto NARROW) {
+                    hipLaunchKernelGGL((k_denoise<typename decltype(PIX)::type, decltype(COUNT)::value, decltype(NARROW)::value>),
+                                       grid2d(W, H, nz), dim3(256), 0, s, a);
+                });
+            });
+        });
+        HIP_TRY(hipGetLastError());
+    }
+    return OFLK_OK;
+}
+
+int denoise_host(bool u8, const void *frames, int B, int H, int W, const InterpFlows &fl, const DenoiseConfig &cfg, void *out,
+                 unsigned char *count)
+{
+    if (fl.any_null()) return fail(OFLK_ERR_INVALID, "NULL flow argument");
+    int rc = check_hw(frames, frames, H, W);
+    if (rc) return rc;
+    if (B < 1) return fail(OFLK_ERR_INVALID, "B must be >= 1 (got %d)", B);
+    const size_t plane = (size_t)H * W, fb = plane * (u8 ? 1 : sizeof(float)), F = (size_t)B + 1;
+    if ((rc = check_denoise(cfg, frames, B + 1, fb, out))) return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const float *in[4] = {fl.uf, fl.vf, fl.ub, fl.vb};
+    char *d_frames, *d_out;
+    float *d[4];
+    unsigned char *d_count;
+    if ((rc = call.upload(&d_frames, static_cast<const char *>(frames), F * fb))) return rc;
+    for (int i = 0; i < 4; i++)
+        if ((rc = call.upload(&d[i], in[i], (size_t)B * plane))) return rc;
+    if ((rc = call.alloc(&d_out, F * fb)) || (rc = call.alloc(&d_count, F * plane, count)) ||
+        (rc = denoise_launch(u8, {d_frames, {d[0], d[1], d[2], d[3]}, B + 1, B}, B + 1, 0, B + 1, H, W, cfg, d_out, d_count, nullptr)) ||
+        (rc = call.to_host(static_cast<char *>(out), d_out, F * fb)) || (count && (rc = call.to_host(count, d_count, F * plane))))
+        return rc;
+    return call.sync();
+}
+
+// Frames in, denoised frames out, host pointers: run_sequence_fb's chunk loop on its chunks, so that every pair's flows are
+// computed exactly once and are that call's.  A frame needs the flows of R = radius pairs on either side, more than a chunk
+// may hold, so the flows and frames a later frame still needs stay on the device in rings: after the chunk that ends with
+// frame `top`, frames next .. top - R have all their pairs and are emitted (next .. T - 1 after the last chunk).  The oldest
+// frame and pair they read is next - R, and next is the chunk before's top - R + 1: with this chunk's C pairs the rings span
+// C + 2 R pairs and C + 2 R + 1 frames at most, which is their size, and a chunk's slots replace only what no frame still to
+// be emitted reads.  What a frame reads does not depend on the cut.  Only out and count come down.
+int run_sequence_denoise(bool u8, const void *frames, int T, int H, int W, const PyrWindow &pyr, const DenoiseConfig &cfg,
+                         int flow_median, void *out, unsigned char *count)
+{
+    const Seq seq{pyr, frames, u8, T, H, W, flow_median};
+    const size_t plane = (size_t)H * W, fb = seq.frame_bytes();
+    int rc = BidirChunk::check(seq);
+    if (rc || (rc = check_denoise(cfg, frames, T, fb, out))) return rc;
+    HostCall call;
+    if ((rc = call.begin())) return rc;
+    const int B = T - 1, C = chunk_pairs(B, H, W), R = cfg.radius;
+    const int pcap = C + 2 * R, fcap = pcap + 1, ocap = std::min(T, C + R + 1);   // a step emits C + R + 1 frames at most
+    BidirChunk k{};
+    char *ring_frames, *d_out;
+    float *ring[4];
+    unsigned char *d_count;
+    if ((rc = k.alloc(call, seq, C)) || (rc = call.alloc(&ring_frames, (size_t)fcap * fb))) return rc;
+    for (auto &q : ring)
+        if ((rc = call.alloc(&q, (size_t)pcap * plane))) return rc;
+    if ((rc = call.alloc(&d_out, (size_t)ocap * fb)) || (rc = call.alloc(&d_count, (size_t)ocap * plane, count))) return rc;
+    // planes s0 .. s0+n-1 of a chunk's buffer into their slots of a ring of cap planes
+    auto to_ring = [&](char *dst, int cap, const char *src, int s0, int n, size_t bytes) {
+        for (int i = 0; i < n; i++)
+            HIP_TRY(hipMemcpyAsync(dst + (size_t)((s0 + i) % cap) * bytes, src + (size_t)i * bytes, bytes, hipMemcpyDeviceToDevice, nullptr));
+        return (int)OFLK_OK;
+    };
+    int next = 0;
+    for (int b0 = 0; b0 < B; b0 += C) {
+        const int nb = std::min(C, B - b0), top = b0 + nb;
+        if ((rc = k.run(call, seq, b0, nb)) || (rc = to_ring(ring_frames, fcap, k.frames, b0, nb + 1, fb))) return rc;
+        for (int i = 0; i < 4; i++)
+            if ((rc = to_ring(reinterpret_cast<char *>(ring[i]), pcap, reinterpret_cast<const char *>(k.d[i]), b0, nb, plane * sizeof(float))))
+                return rc;
+        const int end = top == B ? T : top - R + 1;   // one past the last frame whose R pairs ahead exist
+        if (end > next) {
+            const int n = end - next;
+            if ((rc = denoise_launch(u8, {ring_frames, {ring[0], ring[1], ring[2], ring[3]}, fcap, pcap}, T, next, n, H, W, cfg, d_out,
+                                     d_count, nullptr)) ||
+                (rc = call.to_host(static_cast<char *>(out) + (size_t)next * fb, d_out, (size_t)n * fb)) ||
+                (count && (rc = call.to_host(count + (size_t)next * plane, d_count, (size_t)n * plane))))
+                return rc;
+            next = end;
+        }
+        if ((rc = call.sync())) return rc;
+    }
+    return OFLK_OK;
+}
+}  // namespace
+
+OFLK_API int oflk_denoise_frames_host(const float *frames, int B, int H, int W, const float *uf, const float *vf, const float *ub,
+                                      const float *vb, float alpha, float beta, int radius, float strength, float *out,
+                                      unsigned char *count)
+{
+    return denoise_host(false, frames, B, H, W, {uf, vf, ub, vb}, {alpha, beta, radius, strength}, out, count);
+}
+
+OFLK_API int oflk_denoise_frames_host_u8(const unsigned char *frames, int B, int H, int W, const float *uf, const float *vf,
+                                         const float *ub, const float *vb, float alpha, float beta, int radius, float strength,
+                                         unsigned char *out, unsigned char *count)
+{
+    return denoise_host(true, frames, B, H, W, {uf, vf, ub, vb}, {alpha, beta, radius, strength}, out, count);
+}
+
+OFLK_API int oflk_denoise_sequence(const float *frames, int T, int H, int W, int levels, int window_size, int iters, float alpha,
+                                   float beta, int flow_median, int radius, float strength, float *out, unsigned char *count)
+{
+    return run_sequence_denoise(false, frames, T, H, W, {levels, window_size, iters}, {alpha, beta, radius, strength}, flow_median,
+                                out, count);
+}
+
+OFLK_API int oflk_denoise_sequence_u8(const unsigned char *frames, int T, int H, int W, int levels, int window_size, int iters,
+                                      float alpha, float beta, int flow_median, int radius, float strength, unsigned char *out,
+                                      unsigned char *count)
+{
+    return run_sequence_denoise(true, frames, T, H, W, {levels, window_size, iters}, {alpha, beta, radius, strength}, flow_median,
+                                out, count);
 }
 
 // =============================================================================

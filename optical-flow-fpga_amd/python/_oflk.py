@@ -42,6 +42,7 @@ _ALIGN_D_IO = [_vp, _vp, _vp, _Z, _vp, _vp, _vp]        # d_model_in, d_status_i
 _ALIGN_H_IO = [_f32p, _i32p, _f32p, _i32p, _f64p]       # model_in, status_in, model_out, status_out, stats
 _STAB_OUT = [_f32p, _f32p, _i32p, _vp]                  # correction, model_out, counts_out, held (behind the frames out)
 _INTERP = [_F, _F, _I, _f64p, _I]   # InterpConfig: alpha, beta, refine, taus, n (Interp)
+_DENOISE = [_I, _F]                 # radius, strength, behind alpha, beta (and the sequence forms' flow_median) (Denoise)
 
 # every exported symbol of include/oflk.h: name -> (restype, argtypes)
 SIGNATURES = {
@@ -114,6 +115,10 @@ SIGNATURES = {
     "oflk_interpolate_sequence_median_u8": (ctypes.c_int, [_vp] + [_I] * 6 + _INTERP + [_I, _vp, _vp]),
     "oflk_interpolate_sequence_packed_median": (ctypes.c_int, [_vp] + [_I] * 8 + _INTERP + [_I, _vp, _vp]),
     "oflk_interpolate_sequence_nv12_median": (ctypes.c_int, [_vp] + [_I] * 7 + _INTERP + [_I, _vp, _vp]),
+    "oflk_denoise_frames_host": (ctypes.c_int, [_f32p] + [_I] * 3 + [_f32p] * 4 + [_F, _F] + _DENOISE + [_f32p, _vp]),
+    "oflk_denoise_frames_host_u8": (ctypes.c_int, [_vp] + [_I] * 3 + [_f32p] * 4 + [_F, _F] + _DENOISE + [_vp, _vp]),
+    "oflk_denoise_sequence": (ctypes.c_int, [_f32p] + [_I] * 6 + [_F, _F, _I] + _DENOISE + [_f32p, _vp]),
+    "oflk_denoise_sequence_u8": (ctypes.c_int, [_vp] + [_I] * 6 + [_F, _F, _I] + _DENOISE + [_vp, _vp]),
     "oflk_track_points": (ctypes.c_int, [_vp] * 4 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, _vp]),
     "oflk_track_points_host": (ctypes.c_int, [_f32p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
     "oflk_pyramidal_sequence_tracks": (ctypes.c_int, [_f32p] + [ctypes.c_int] * 6 + [ctypes.c_float] * 2 + [_i32p, _f32p, ctypes.c_int, _f32p, _vp]),
@@ -666,6 +671,57 @@ def flow_median_host(planes: np.ndarray, size: int = 5) -> np.ndarray:
     out = np.empty_like(a)
     check(lib().oflk_flow_median_host(ptr(a), ptr(out), a.size // (H * W), H, W, int(size)))
     return out
+
+
+DENOISE_MAX_RADIUS = 4   # OFLK_DENOISE_MAX_RADIUS
+
+
+class Denoise(NamedTuple):
+    """The settings of the denoising calls, in the argument order of the C ABI (DenoiseConfig, flow_median between the
+    test's parameters and the rest in the sequence forms)"""
+    alpha: float
+    beta: float
+    radius: int
+    strength: float
+
+
+def check_denoise(alpha: float, beta: float, radius, strength) -> Denoise:
+    """The denoising settings as the library takes them.  ValueError for alpha, beta as check_fb_params, a radius that is
+    not an integer in [1, DENOISE_MAX_RADIUS], a strength that is not finite and > 0 as a float32."""
+    a, b = check_fb_params(alpha, beta)
+    radius = check_int("radius", radius, 1, DENOISE_MAX_RADIUS)
+    with np.errstate(over="ignore"):   # a value beyond float32's range becomes inf, and is refused below
+        s = np.float32(strength)
+    if not (np.isfinite(s) and s > 0):
+        raise ValueError(f"strength must be finite and > 0, got {strength!r}")
+    return Denoise(a, b, radius, float(s))
+
+
+def denoise_host(arr: np.ndarray, flows, cfg: Denoise, count: bool):
+    """oflk_denoise_frames_host[_u8] on a contiguous (B+1, H, W) array of frames and four float32 flows (B, H, W): (out of the
+    frames' shape and type, count (B+1, H, W) uint8 or None)"""
+    B, H, W = arr.shape[0] - 1, arr.shape[1], arr.shape[2]
+    flows = [np.ascontiguousarray(f, np.float32) for f in flows]
+    for f in flows:
+        if f.shape != (B, H, W):
+            raise ValueError(f"every flow must have shape {(B, H, W)}, got {f.shape}")
+    out = np.empty_like(arr)
+    cnt = np.empty(arr.shape, np.uint8) if count else None
+    src, fn = pixels(arr, "oflk_denoise_frames_host")
+    check(fn(src, B, H, W, *(ptr(f) for f in flows), *cfg, pix(out), None if cnt is None else cnt.ctypes.data))
+    return out, cnt
+
+
+def denoise_sequence_host(arr: np.ndarray, levels: int, window_size: int, iters: int, cfg: Denoise, flow_median: int, count: bool):
+    """oflk_denoise_sequence[_u8] on a contiguous (T, H, W) array of frames; flow_median is checked (0, 3, 5, 7 or 9): (out of
+    the frames' shape and type, count (T, H, W) uint8 or None)"""
+    T, H, W = arr.shape
+    out = np.empty_like(arr)
+    cnt = np.empty(arr.shape, np.uint8) if count else None
+    src, fn = pixels(arr, "oflk_denoise_sequence")
+    check(fn(src, T, H, W, int(levels), int(window_size), int(iters), cfg.alpha, cfg.beta, int(flow_median), cfg.radius, cfg.strength,
+             pix(out), None if cnt is None else cnt.ctypes.data))
+    return out, cnt
 
 
 def as_queries(queries, T: int) -> Tuple[Optional[np.ndarray], np.ndarray]:

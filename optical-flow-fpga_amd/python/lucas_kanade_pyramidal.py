@@ -381,6 +381,42 @@ def lucas_kanade_pyramidal_sequence_interpolate_nv12(video, factor: int = 2, tau
     return _sequence_interpolate(layout, arr, H, W, num_levels, window_size, num_iterations, cfg, k)
 
 
+def denoise_frames(frames, u_fwd, v_fwd, u_bwd, v_bwd, strength: float, radius: int = 2, alpha: float = 0.01, beta: float = 4.0,
+                   return_count: bool = False):
+    """Temporal noise reduction of a (B+1, H, W) frame sequence on given dense flows, motion compensated.
+
+    frames: as lucas_kanade_pyramidal_sequence_fb (all uint8: the uint8 path); the flows are (B, H, W) float32 as that call
+    returns them.  Returns the frames' shape and type: each pixel averaged with where it was in the `radius` frames before and
+    after (fewer at the ends of the sequence).  A pixel is carried from frame to frame along the flows while every step
+    passes the forward-backward test (alpha, beta) at the carried point; a chain ends at its first failure.  A neighbour v of
+    the pixel c has the weight 1 - (v - c)^2 / strength^2 where that is positive and none otherwise, so a value `strength`
+    grey levels or more away never enters; 3 x the noise's sigma is the suggested strength.  With return_count also count
+    (B+1, H, W) uint8, the neighbours that entered each average (2 * radius at most).
+    """
+    cfg = _oflk.check_denoise(alpha, beta, radius, strength)
+    arr, _ = _oflk.as_sequence(frames)
+    out, count = _oflk.denoise_host(arr, (u_fwd, v_fwd, u_bwd, v_bwd), cfg, bool(return_count))
+    return (out, count) if return_count else out
+
+
+def lucas_kanade_pyramidal_sequence_denoise(frames, strength: float, radius: int = 2, alpha: float = 0.01, beta: float = 4.0,
+                                            flow_median: int = 9, num_levels: int = 3, window_size: int = 5,
+                                            num_iterations: int = 3, return_count: bool = False):
+    """Temporal noise reduction of a frame sequence: frames in, the denoised frames out, (T, H, W) in the frames' type.
+
+    The flows of lucas_kanade_pyramidal_sequence_fb (flow_median = 3, 5, 7 or 9: through median_filter_flow of that size; 0:
+    as they are) and the average of denoise_frames run on the device: only the frames (and with return_count the counts)
+    come back, and a long sequence goes in chunks whose cut does not show in the result.  The defaults are the ones the
+    feature works with on this library's flows of noisy frames: the 9 x 9 median and a forward-backward test looser
+    (beta = 4.0) than the other callers'.
+    """
+    cfg = _oflk.check_denoise(alpha, beta, radius, strength)
+    k = _oflk.check_flow_median(flow_median)
+    arr, _ = _oflk.as_sequence(frames)
+    out, count = _oflk.denoise_sequence_host(arr, num_levels, window_size, num_iterations, cfg, k, bool(return_count))
+    return (out, count) if return_count else out
+
+
 class SequenceKLT(NamedTuple):
     """Result of lucas_kanade_pyramidal_sequence_klt: n features of frame 0 and their tracks (row t is frame t)."""
     xy: np.ndarray        # (n, 2) float32 (x, y) in acceptance order
